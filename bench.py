@@ -10,9 +10,12 @@ inputs : synthetic: latents N(0,1) [4,4,64,64] seed 0, text em
 N > 1  : one process per GPU (torchrun), weak scaling: every rank denoises its own 4 latents; rank 0
          broadcasts the text embeddings and images are all-gathered (RCCL over xGMI).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant kernel,
-measured live with HIP events on the launch stream) and `cpu_baseline` (the fp32 CPU oracle timed
-on a bounded sample of the same workload; N=1 only).
+Prints ONE JSON line on rank 0: the headline figure (`metric`, `value`, `unit`, `ms_per_step`, ...).  A plain
+run only sets up, warms up, times --steps passes and reports.  `--full` also measures what takes runs of its own:
+`box_probe` (the box's sustained MFMA / copy rate), the 1024 px pass under `extra`, UNet-only / VAE-only times,
+`roofline` (dominant kernel, measured live with HIP events on the launch stream) and `cpu_baseline` (the fp32
+CPU oracle timed on a bounded sample of the same workload; N=1 only).
+`--dump-outputs DIR` writes the images of the last timed pass as DIR/images.npy (float32).
 """
 from __future__ import annotations
 
@@ -45,10 +48,28 @@ HBM_PEAK_GBS = 8000.0       # spec; 6.29 TB/s achievable (MI355X_MICROARCH.md:36
 # algorithmic TFLOP per unit (2*MAC of conv / linear / QK^T / PV only)
 UNET_TFLOP_PER_SAMPLE = {"sd15": {32: 0.1803, 64: 0.8032, 96: 2.148, 128: 4.674}, "sdxl": {128: 6.761}}
 VAE_TFLOP_PER_IMAGE = {32: 0.622, 64: 2.515, 96: 5.754, 128: 10.470}
+DUMP_LIMIT_BYTES = 64 << 20   # --dump-outputs writes at most this much
 
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+def dump_outputs(dirname: str, imgs):
+    """The images the timed path returned in its last pass ([N, 3, H, W], float32) as DIR/images.npy.  Past
+    DUMP_LIMIT_BYTES a fixed subset is written: whole images at seeded (seed 0), sorted batch indices, and if one
+    image alone is too large, every k-th value of one such image."""
+    import numpy as np
+    a = imgs.float().cpu().numpy()
+    if a.nbytes > DUMP_LIMIT_BYTES:
+        keep = max(1, DUMP_LIMIT_BYTES // a[0].nbytes)
+        a = a[np.sort(np.random.default_rng(0).permutation(a.shape[0])[:keep])]
+        if a.nbytes > DUMP_LIMIT_BYTES:
+            a = a.reshape(-1)[:: -(-a.nbytes // DUMP_LIMIT_BYTES)]
+    os.makedirs(dirname, exist_ok=True)
+    path = os.path.join(dirname, "images.npy")
+    np.save(path, np.ascontiguousarray(a, dtype=np.float32))
+    log(f"[bench] wrote {path}: {list(a.shape)} float32")
 
 
 def build_models(device, preset="sd15", seed=2):
@@ -348,13 +369,20 @@ def main():
                          "--scheduler 'DPM++ 2M' = config C4")
     ap.add_argument("--scheduler", default="DDIM", choices=["DDIM", "DPM++ 2M", "euler"])
     ap.add_argument("--graph", action="store_true", help="replay the UNet forward from a hipGraph")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the box probe, the 1024 px pass, UNet-/VAE-only timing, the live roofline and the "
+                         "CPU baseline (each can still be left out with its --no-* option)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-large", action="store_true",
                     help="skip the extra 4x128x128-latent (1024 px) pass reported under `extra`")
     ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the images of the last timed pass to DIR/images.npy (float32)")
     ap.add_argument("--rehearse", action="store_true",
                     help="ranks only rendezvous over gloo and count each other (launcher self-test, no GPU)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -383,7 +411,7 @@ def main():
     model.set_scheduler(args.scheduler)
     pipe = StableDiffusionUnifiedPipeline(do_cfg=True, device=str(device))
 
-    probe = box_probe(lib) if rank == 0 else None
+    probe = box_probe(lib) if args.full and rank == 0 else None
     B = args.batch
     lat_hw = args.res // 8
     total = B * n_gpus
@@ -424,11 +452,14 @@ def main():
 
     ms_per_step = dt / args.steps * 1e3
     value = total * args.steps / dt
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, imgs)
 
+    # everything below the headline figure runs with --full only.
     # north_star also asks for the 4x128x128-latent input: one warm-up + one timed pass of the same
     # loop at 2x the resolution (reported under `extra`, never mixed into `value`)
     large = None
-    if not args.no_large and args.preset == "sd15" and args.res == 512:
+    if args.full and not args.no_large and args.preset == "sd15" and args.res == 512:
         lres, lhw = 2 * args.res, 2 * lat_hw
         lat_big = torch.randn(total, 4, lhw, lhw, generator=torch.Generator().manual_seed(0)).half().to(device)
 
@@ -453,25 +484,26 @@ def main():
         del big, lat_big
 
     # UNet-only / VAE-only times (per GPU), same shapes as the loop
-    x8 = torch.randn(2 * B, 4, lat_hw, lat_hw, device=device, dtype=torch.float16)
-    e8 = torch.cat([ne_full[:B], pe_full[:B]])
-    tt = torch.tensor(501.0)
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
-    added = None
-    if args.preset == "sdxl":
-        added = {"text_embeds": torch.cat([npooled[:B], pooled[:B]]),
-                 "time_ids": torch.tensor([[args.res, args.res, 0, 0, args.res, args.res]] * (2 * B), dtype=torch.float32)}
-    unet(x8, tt, e8, added_cond_kwargs=added); vae.decode(x8[:B])
-    torch.cuda.synchronize()
-    ev[0].record()
-    for _ in range(10):
-        unet(x8, tt, e8, added_cond_kwargs=added)
-    ev[1].record(); ev[2].record()
-    for _ in range(3):
-        vae.decode(x8[:B])
-    ev[3].record(); torch.cuda.synchronize()
-    unet_ms = ev[0].elapsed_time(ev[1]) / 10
-    vae_ms = ev[2].elapsed_time(ev[3]) / 3
+    if args.full:
+        x8 = torch.randn(2 * B, 4, lat_hw, lat_hw, device=device, dtype=torch.float16)
+        e8 = torch.cat([ne_full[:B], pe_full[:B]])
+        tt = torch.tensor(501.0)
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+        added = None
+        if args.preset == "sdxl":
+            added = {"text_embeds": torch.cat([npooled[:B], pooled[:B]]),
+                     "time_ids": torch.tensor([[args.res, args.res, 0, 0, args.res, args.res]] * (2 * B), dtype=torch.float32)}
+        unet(x8, tt, e8, added_cond_kwargs=added); vae.decode(x8[:B])
+        torch.cuda.synchronize()
+        ev[0].record()
+        for _ in range(10):
+            unet(x8, tt, e8, added_cond_kwargs=added)
+        ev[1].record(); ev[2].record()
+        for _ in range(3):
+            vae.decode(x8[:B])
+        ev[3].record(); torch.cuda.synchronize()
+        unet_ms = ev[0].elapsed_time(ev[1]) / 10
+        vae_ms = ev[2].elapsed_time(ev[3]) / 3
 
     result = None
     if rank == 0:
@@ -486,20 +518,22 @@ def main():
                                    f"{args.denoise_steps}-step {args.scheduler}, "
                                    f"batch {B}/GPU, CFG on (UNet batch {2 * B}), UNet + VAE decode HIP kernels",
                        "global_batch": total, "parallelism": f"dp{n_gpus}", "guidance_scale": args.guidance},
-            "unet_forward_ms": round(unet_ms, 3), "vae_decode_ms": round(vae_ms, 3),
-            "outputs_finite": finite, "unet_hipgraph": bool(args.graph), "box_probe": probe,
-            "extra": {"latents_4x128x128": large},
+            "outputs_finite": finite, "unet_hipgraph": bool(args.graph), "full": bool(args.full),
         }
+        if args.full:
+            result.update({"unet_forward_ms": round(unet_ms, 3), "vae_decode_ms": round(vae_ms, 3), "box_probe": probe,
+                           "extra": {"latents_4x128x128": large}})
         if probe:
             result["value_per_probe_pflops"] = round(value / (probe["mfma_tflops"] / 1e3), 4)
         if u_tf and v_tf:
             tflop = args.denoise_steps * 2 * B * u_tf + B * v_tf     # per GPU per pass
             result["whole_path_mfma_frac"] = round(tflop / (ms_per_step / 1e3) / MFMA_PEAK_TFLOPS, 4)
-            result["unet_forward_mfma_frac"] = round(2 * B * u_tf / (unet_ms / 1e3) / MFMA_PEAK_TFLOPS, 4)
-        if not args.no_roofline:
+            if args.full:
+                result["unet_forward_mfma_frac"] = round(2 * B * u_tf / (unet_ms / 1e3) / MFMA_PEAK_TFLOPS, 4)
+        if args.full and not args.no_roofline:
             urows, vrows = live_roofline(lib, unet, vae, B, lat_hw, e8, device, added)
             result.update(roofline_report(urows, vrows))
-        if n_gpus == 1 and not args.no_cpu_baseline and args.preset == "sd15":
+        if args.full and n_gpus == 1 and not args.no_cpu_baseline and args.preset == "sd15":
             del unet, vae, model
             torch.cuda.empty_cache()
             result["cpu_baseline"] = cpu_baseline(ucfg, vcfg, usd, vsd, args.denoise_steps, lat_hw, 77)

@@ -154,6 +154,10 @@ def load():
         raise EngineError(
             f"{LIB_PATH} not found: build it with `python -m stablediffusion_amd.build` "
             "(hipcc --offload-arch=gfx950). The HIP engine is mandatory; there is no CPU fallback.")
+    # The engine works on torch's device pointers, so it must share torch's HIP runtime.  torch ships its own
+    # libamdhip64 under the system library's soname: with torch loaded first the engine binds to that copy; loaded
+    # before torch, the process would end up with two HIP / HSA runtimes and the engine's would see no device.
+    import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in SIGNATURES.items():
         fn = getattr(lib, name)          # AttributeError if the symbol is missing

@@ -36,6 +36,20 @@ def test_struct_layout_matches_header():
         assert names == [f[0] for f in cls._fields_], struct
 
 
+def test_engine_shares_torchs_hip_runtime(engine_lib):
+    """Loading the engine before anything imported torch (what build() does) must not bring a second HIP runtime
+    into the process: checked in a fresh interpreter through the libraries it has mapped."""
+    import json
+    import subprocess
+    import sys
+    code = ("import json; from stablediffusion_amd import _lib; _lib.load(); import torch; "
+            "print(json.dumps(sorted({l.split()[-1] for l in open('/proc/self/maps') if 'libamdhip64' in l})))")
+    r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr
+    hip = json.loads(r.stdout.strip().splitlines()[-1])
+    assert len(hip) == 1, hip
+
+
 def test_library_identity(engine_lib):
     assert engine_lib.sd_engine_arch() == b"gfx950"
     assert engine_lib.sd_engine_version() >= 1

@@ -45,7 +45,7 @@ def short(k):
 
 f, w = agg(fetch_dir, "FETCH_SIZE"), agg(write_dir, "WRITE_SIZE")
 res = {"_note": "HBM bytes per launch, rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE (separate passes) over "
-                "`bench.py --steps 1 --warmup 0 --denoise-steps 2 --no-cpu-baseline --no-roofline`; kB * 1024, "
+                "`bench.py --full --steps 1 --warmup 0 --denoise-steps 2 --no-cpu-baseline --no-roofline`; kB * 1024, "
                 "FETCH_SIZE doubled for gfx950; averages over every launch of the kernel (UNet + VAE shapes mixed)."}
 for k in f:
     if "sd" not in k:
