@@ -299,6 +299,26 @@ int sd_op_unet_conv_out(const void* x_nhwc, const void* gamma, const void* beta,
 int sd_op_ffn_geglu(const void* x, const void* ln_gamma, const void* ln_beta, float ln_eps, const void* w1, const void* b1,
                     const void* w2, const void* b2, void* y, int M, int C, int iters, float* ms_per_launch, int* fused,
                     void* stream);
+/* The folded LayerNorm of a transformer block (norm1 / norm2 / norm3 folded into the next linear), in two calls that share
+ * the row statistics, so each side's kernel can be forced on its own (sd_igemm_force).
+ * Producer: y1 = x W0^T + b0 (+ res); x [M, K], res / y1 [M, C] f16, w0 [C, K] f16, b0 [C] f32.  stat (device, at least
+ * M * ceil(C / 64) * 2 floats) receives the row statistics the engine's own producer leaves: *parts (mean, M2) pairs per
+ * row, part k over the columns [k *part_w, min((k + 1) *part_w, C)).  *producer: the igemm2 variant whose epilogue wrote
+ * them (13 = wsgemm, 18 = igemm3), or -1 for the stand-alone row-statistics kernel.
+ * Consumer: y2 = LayerNorm(y1; gamma, beta, eps) W1^T + b1 from those statistics.  geglu = 0: w1 [O, C], the first
+ * rows_scaled output columns times row_scale (the query scale of q|k|v); geglu = 1: w1 [2 O, C] = [hidden | gate] rows,
+ * b1 [2 O], y2 = hidden * gelu(gate) [M, O].  *consumer: the igemm2 variant (13 / 14 = wsgemm, 18 = igemm3) or 100 for
+ * the persistent GEGLU kernel. */
+int sd_op_linear_rowstats(const void* x, const void* w0, const void* b0, const void* res, void* y1, float* stat, int M,
+                          int K, int C, int* parts, int* part_w, int* producer, void* stream);
+int sd_op_ln_linear(const void* y1, const float* stat, int parts, int part_w, const void* gamma, const void* beta, float eps,
+                    const void* w1, const void* b1, void* y2, int M, int C, int O, int geglu, int rows_scaled, float row_scale,
+                    int* consumer, void* stream);
+/* sd_op_ffn_geglu on row statistics of x a producer left (the stat / parts / part_w of sd_op_linear_rowstats) instead of
+ * statistics it computes itself: the form the UNet runs. */
+int sd_op_ln_ffn_geglu(const void* x, const float* stat, int parts, int part_w, const void* ln_gamma, const void* ln_beta,
+                       float ln_eps, const void* w1, const void* b1, const void* w2, const void* b2, void* y, int M, int C,
+                       int* fused, void* stream);
 /* Same operator, timed: `iters` back-to-back launches bracketed by HIP events on `stream`
  * (after two warm-up launches); used by tools/tune_igemm.py to pick tile variants per shape. */
 int sd_bench_conv2d(const void* x_nhwc, const void* w_oihw, void* y_nhwc, int N, int H, int W, int Cin,

@@ -498,9 +498,9 @@ int sd_op_groupnorm_conv2d(const void* x, const void* gamma_f32, const void* bet
                        iters > 0 ? iters : 1, iters > 0 ? ms_per_launch : nullptr, nullptr, &gh);
 }
 
-int sd_op_ffn_geglu(const void* x, const void* ln_gamma, const void* ln_beta, float ln_eps, const void* w1, const void* b1,
-                    const void* w2, const void* b2, void* y, int M, int C, int iters, float* ms_per_launch, int* fused,
-                    void* stream) {
+static int ffn_geglu_impl(const void* x, const float* x_stat, int stat_parts, int stat_w, const void* ln_gamma,
+                          const void* ln_beta, float ln_eps, const void* w1, const void* b1, const void* w2, const void* b2,
+                          void* y, int M, int C, int iters, float* ms_per_launch, int* fused, void* stream) {
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (!x || !ln_gamma || !ln_beta || !w1 || !b1 || !w2 || !b2 || !y || M < 1 || C % 64 != 0) { set_error("sd_op_ffn_geglu: bad arguments"); return SD_ERR_INVALID; }
     const long H4 = 4L * C, O1 = 8L * C;
@@ -514,7 +514,7 @@ int sd_op_ffn_geglu(const void* x, const void* ln_gamma, const void* ln_beta, fl
     SD_DEV_ALLOC(scope, wsum, (size_t)r1 * 4);
     SD_DEV_ALLOC(scope, w2p, (size_t)r2 * H4 * 2);
     SD_DEV_ALLOC(scope, b2p, (size_t)r2 * 4);
-    SD_DEV_ALLOC(scope, stat, (size_t)M * 2 * 4);
+    if (!x_stat) SD_DEV_ALLOC(scope, stat, (size_t)M * 2 * 4);
     SD_HIP_CHECK(hipMemsetAsync(wg, 0, (size_t)r1 * C * 2, s));
     SD_HIP_CHECK(hipMemsetAsync(bg, 0, (size_t)r1 * 4, s));
     SD_HIP_CHECK(hipMemsetAsync(nb, 0, (size_t)r1 * 4, s));
@@ -533,13 +533,15 @@ int sd_op_ffn_geglu(const void* x, const void* ln_gamma, const void* ln_beta, fl
     SD_HIP_CHECK(hipMemcpyAsync(w2p, w2, (size_t)C * H4 * 2, hipMemcpyDeviceToDevice, s));
     SD_HIP_CHECK(hipMemcpyAsync(b2p, b2, (size_t)C * 4, hipMemcpyDeviceToDevice, s));
     int rc = launch_ln_fold(wg, C, (int)O1, static_cast<const float*>(ln_gamma), static_cast<const float*>(ln_beta), bg, nb, wsum, 0, 1.0f, s);
-    if (!rc) rc = launch_row_stats(static_cast<const half_t*>(x), C, stat, M, C, s);
+    if (!rc && !x_stat) rc = launch_row_stats(static_cast<const half_t*>(x), C, stat, M, C, s);
     if (rc) return rc;
+    const float* st = x_stat ? x_stat : stat;
+    const int parts = x_stat ? stat_parts : 1, part_w = x_stat ? stat_w : C;
     FfnParams p;
     p.x = static_cast<const half_t*>(x); p.ldx = C; p.y = static_cast<half_t*>(y); p.ldy = C;
     p.w1 = wg; p.b1 = nb; p.wsum1 = wsum; p.w1_rows = (int)r1;
     p.w2 = w2p; p.b2 = b2p; p.w2_rows = (int)r2;
-    p.ln_stat = stat; p.ln_parts = 1; p.ln_eps = ln_eps;
+    p.ln_stat = st; p.ln_parts = parts; p.ln_part_w = part_w; p.ln_eps = ln_eps;
     p.M = M; p.C = C; p.hidden = (int)H4;
     const bool use_fused = ffn_fused_supported(p);
     if (fused) *fused = use_fused ? 1 : 0;
@@ -547,7 +549,7 @@ int sd_op_ffn_geglu(const void* x, const void* ln_gamma, const void* ln_beta, fl
     if (!use_fused || ms_per_launch) SD_DEV_ALLOC(scope, hid, (size_t)M * H4 * 2);
     g1.x = p.x; g1.ldx = C; g1.w = wg; g1.bias = nb; g1.y = hid; g1.ldy = H4; g1.N = 1; g1.H = M; g1.W = 1; g1.Cin = C; g1.OH = M; g1.OW = 1;
     g1.Cout = (int)O1; g1.KS = 1; g1.stride = 1; g1.pad = 0; g1.up = 0; g1.M = M; g1.K = C; g1.geglu = 1;
-    g1.ln_stat = stat; g1.ln_parts = 1; g1.ln_C = C; g1.ln_eps = ln_eps; g1.ln_wsum = wsum;
+    g1.ln_stat = st; g1.ln_parts = parts; g1.ln_part_w = part_w; g1.ln_C = C; g1.ln_eps = ln_eps; g1.ln_wsum = wsum;
     g2.x = hid; g2.ldx = H4; g2.w = w2p; g2.bias = b2p; g2.res = p.x; g2.ldres = C; g2.y = p.y; g2.ldy = C; g2.N = 1; g2.H = M; g2.W = 1;
     g2.Cin = (int)H4; g2.OH = M; g2.OW = 1; g2.Cout = C; g2.KS = 1; g2.stride = 1; g2.pad = 0; g2.up = 0; g2.M = M; g2.K = (int)H4;
     float* partial = nullptr;
@@ -583,6 +585,119 @@ int sd_op_ffn_geglu(const void* x, const void* ln_gamma, const void* ln_beta, fl
         }
     }
     if (e0) { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); }
+    hipError_t e = hipStreamSynchronize(s);
+    if (!rc && e != hipSuccess) { set_error(hipGetErrorString(e)); rc = SD_ERR_HIP; }
+    return rc;
+}
+
+int sd_op_ffn_geglu(const void* x, const void* ln_gamma, const void* ln_beta, float ln_eps, const void* w1, const void* b1,
+                    const void* w2, const void* b2, void* y, int M, int C, int iters, float* ms_per_launch, int* fused,
+                    void* stream) {
+    return ffn_geglu_impl(x, nullptr, 0, 0, ln_gamma, ln_beta, ln_eps, w1, b1, w2, b2, y, M, C, iters, ms_per_launch, fused,
+                          stream);
+}
+
+// The same feed-forward on the row statistics a producer left (sd_op_linear_rowstats), as the UNet runs it.
+int sd_op_ln_ffn_geglu(const void* x, const float* stat, int parts, int part_w, const void* ln_gamma, const void* ln_beta,
+                       float ln_eps, const void* w1, const void* b1, const void* w2, const void* b2, void* y, int M, int C,
+                       int* fused, void* stream) {
+    if (!stat || parts < 1 || part_w < 1 || (long)parts * part_w < C || (long)(parts - 1) * part_w >= C) {
+        set_error("sd_op_ln_ffn_geglu: bad statistics layout"); return SD_ERR_INVALID;
+    }
+    return ffn_geglu_impl(x, stat, parts, part_w, ln_gamma, ln_beta, ln_eps, w1, b1, w2, b2, y, M, C, 0, nullptr, fused, stream);
+}
+
+// The folded-LayerNorm chain of a transformer block at op level (unet.cpp run_xformer), in two calls that share the
+// row-statistics buffer so a test can force the producer's and the consumer's kernel separately (sd_igemm_force).
+// Producer: y1 = x W0^T + b0 (+ res) with op_conv's rule for the statistics: from the GEMM epilogue when the launch
+// can emit them (igemm2_emits_rowstats), row_stats_kernel over y1 otherwise.
+int sd_op_linear_rowstats(const void* x, const void* w0, const void* b0, const void* res, void* y1, float* stat, int M,
+                          int K, int C, int* parts, int* part_w, int* producer, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!x || !w0 || !y1 || !stat || !parts || !part_w || !producer || M < 1 || K % 64 != 0 || K < 64 || C % 8 != 0 || C < 8) {
+        set_error("sd_op_linear_rowstats: bad arguments"); return SD_ERR_INVALID;
+    }
+    const long rows = ((long)C + kWeightRowPad - 1) / kWeightRowPad * kWeightRowPad;
+    DevScope scope;
+    half_t* wp = nullptr;
+    float *bp = nullptr, *partial = nullptr;
+    SD_DEV_ALLOC(scope, wp, (size_t)rows * K * 2);
+    SD_DEV_ALLOC(scope, bp, (size_t)rows * 4);
+    SD_HIP_CHECK(hipMemsetAsync(wp, 0, (size_t)rows * K * 2, s));
+    SD_HIP_CHECK(hipMemsetAsync(bp, 0, (size_t)rows * 4, s));
+    int rc = launch_pack_conv(static_cast<const half_t*>(w0), wp, C, K, 1, 1, K, s);
+    if (rc) return rc;
+    if (b0) SD_HIP_CHECK(hipMemcpyAsync(bp, b0, (size_t)C * 4, hipMemcpyDeviceToDevice, s));
+    IGemmParams p{};
+    p.x = static_cast<const half_t*>(x); p.ldx = K; p.w = wp; p.bias = bp;
+    p.res = static_cast<const half_t*>(res); p.ldres = C; p.y = static_cast<half_t*>(y1); p.ldy = C;
+    p.N = 1; p.H = M; p.W = 1; p.Cin = K; p.OH = M; p.OW = 1; p.Cout = C; p.KS = 1; p.stride = 1; p.pad = 0; p.up = 0;
+    p.M = M; p.K = K;
+    int np = 1, w = C;
+    const bool own = igemm2_emits_rowstats(p, &np, &w);
+    if (own) p.rowstat_out = stat;
+    const long pf = igemm2_partial_floats(p);
+    if (pf > 0) SD_DEV_ALLOC(scope, partial, (size_t)pf * 4);
+    *producer = own ? igemm2_launch_kind(p, partial != nullptr) : -1;
+    *parts = own ? np : 1;
+    *part_w = own ? w : C;
+    rc = launch_igemm2(p, partial, s);
+    if (!rc && !own) rc = launch_row_stats(p.y, C, stat, M, C, s);
+    hipError_t e = hipStreamSynchronize(s);
+    if (!rc && e != hipSuccess) { set_error(hipGetErrorString(e)); rc = SD_ERR_HIP; }
+    return rc;
+}
+
+// Consumer: y2 = LayerNorm(y1) W1^T + b1 with the norm folded into W1 (launch_ln_fold, as WeightStore::fold_ln) and
+// its statistics from the producer's buffer.  geglu = 0: W1 [O, C], the first rows_scaled outputs times row_scale
+// (the q of q|k|v); geglu = 1: W1 [2 O, C] = [hidden | gate] rows, y2 = hidden * gelu(gate) [M, O].
+int sd_op_ln_linear(const void* y1, const float* stat, int parts, int part_w, const void* gamma, const void* beta, float eps,
+                    const void* w1, const void* b1, void* y2, int M, int C, int O, int geglu, int rows_scaled, float row_scale,
+                    int* consumer, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!y1 || !stat || !gamma || !beta || !w1 || !y2 || !consumer || M < 1 || C % 64 != 0 || C < 64 || O % 64 != 0 ||
+        O < 64 || parts < 1 || part_w < 1 || (long)parts * part_w < C || (long)(parts - 1) * part_w >= C) {
+        set_error("sd_op_ln_linear: bad arguments"); return SD_ERR_INVALID;
+    }
+    const long cols = geglu ? 2L * O : (long)O;
+    const long rows = (cols + kWeightRowPad - 1) / kWeightRowPad * kWeightRowPad;
+    DevScope scope;
+    half_t *wp = nullptr, *wf = nullptr;
+    float *bp = nullptr, *bf = nullptr, *nb = nullptr, *wsum = nullptr;
+    SD_DEV_ALLOC(scope, wp, (size_t)rows * C * 2);
+    SD_DEV_ALLOC(scope, bp, (size_t)rows * 4);
+    SD_DEV_ALLOC(scope, nb, (size_t)rows * 4);
+    SD_DEV_ALLOC(scope, wsum, (size_t)rows * 4);
+    SD_HIP_CHECK(hipMemsetAsync(wp, 0, (size_t)rows * C * 2, s));
+    SD_HIP_CHECK(hipMemsetAsync(bp, 0, (size_t)rows * 4, s));
+    SD_HIP_CHECK(hipMemsetAsync(nb, 0, (size_t)rows * 4, s));
+    SD_HIP_CHECK(hipMemsetAsync(wsum, 0, (size_t)rows * 4, s));
+    int rc = launch_pack_conv(static_cast<const half_t*>(w1), wp, (int)cols, C, 1, 1, C, s);
+    if (rc) return rc;
+    if (b1) SD_HIP_CHECK(hipMemcpyAsync(bp, b1, (size_t)cols * 4, hipMemcpyDeviceToDevice, s));
+    wf = wp; bf = bp;
+    if (geglu) {            // every 128-row group = 64 hidden rows, then their 64 gate rows (WeightStore::pack_geglu)
+        SD_DEV_ALLOC(scope, wf, (size_t)rows * C * 2);
+        SD_DEV_ALLOC(scope, bf, (size_t)rows * 4);
+        SD_HIP_CHECK(hipMemsetAsync(wf, 0, (size_t)rows * C * 2, s));
+        SD_HIP_CHECK(hipMemsetAsync(bf, 0, (size_t)rows * 4, s));
+        for (long blk = 0; blk < O / 64; ++blk) {
+            SD_HIP_CHECK(hipMemcpyAsync(wf + blk * 128 * C, wp + blk * 64 * C, (size_t)64 * C * 2, hipMemcpyDeviceToDevice, s));
+            SD_HIP_CHECK(hipMemcpyAsync(wf + (blk * 128 + 64) * C, wp + (O + blk * 64) * C, (size_t)64 * C * 2, hipMemcpyDeviceToDevice, s));
+            SD_HIP_CHECK(hipMemcpyAsync(bf + blk * 128, bp + blk * 64, 64 * 4, hipMemcpyDeviceToDevice, s));
+            SD_HIP_CHECK(hipMemcpyAsync(bf + blk * 128 + 64, bp + O + blk * 64, 64 * 4, hipMemcpyDeviceToDevice, s));
+        }
+    }
+    rc = launch_ln_fold(wf, C, (int)cols, static_cast<const float*>(gamma), static_cast<const float*>(beta), bf, nb, wsum,
+                        geglu ? 0 : rows_scaled, row_scale, s);
+    if (rc) return rc;
+    IGemmParams g{};
+    g.x = static_cast<const half_t*>(y1); g.ldx = C; g.w = wf; g.bias = nb; g.y = static_cast<half_t*>(y2); g.ldy = O;
+    g.N = 1; g.H = M; g.W = 1; g.Cin = C; g.OH = M; g.OW = 1; g.Cout = (int)cols; g.KS = 1; g.stride = 1; g.pad = 0; g.up = 0;
+    g.M = M; g.K = C; g.geglu = geglu;
+    g.ln_stat = stat; g.ln_parts = parts; g.ln_part_w = part_w; g.ln_C = C; g.ln_eps = eps; g.ln_wsum = wsum;
+    *consumer = igemm2_launch_kind(g, false);
+    rc = launch_igemm2(g, nullptr, s);
     hipError_t e = hipStreamSynchronize(s);
     if (!rc && e != hipSuccess) { set_error(hipGetErrorString(e)); rc = SD_ERR_HIP; }
     return rc;

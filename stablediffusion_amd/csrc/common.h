@@ -76,4 +76,60 @@ __device__ __forceinline__ int xcd_remap(int orig, int nwg) {
     const int base = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
     return base + (orig >> 3);
 }
+
+// ---- centred norm statistics (mean, M2 = sum (x - mean)^2) of the values a GEMM epilogue stores ----
+// Plain sums and sums of squares lose the variance when |mean| >> std (E[x^2] - mean^2 cancels in fp32); every
+// producer therefore sums its values shifted by a pivot taken from the same data (a constant piece gives exactly
+// (value, 0)), turns those sums into (mean, M2) of small pieces, and the pieces are merged by the pairwise (Chan)
+// update in a fixed order.
+// Chan's merge of (nB, mB, qB) into (nA, mA, qA); nB == 0 leaves A as it is.
+__device__ __forceinline__ void stat_merge(float& nA, float& mA, float& qA, float nB, float mB, float qB) {
+    if (nB <= 0.f) return;
+    const float n = nA + nB;
+    const float d = mB - mA;
+    const float f = nB / n;
+    mA += d * f;
+    qA += qB + d * d * nA * f;
+    nA = n;
+}
+// (mean, M2) of 8 values from sums shifted by the first (the row-statistics chunk of the igemm2 / igemm3 output pass).
+__device__ __forceinline__ float2 chunk8_stats(const h8& v) {
+    const float p = (float)v[0];
+    float s = 0.f, q = 0.f;
+#pragma unroll
+    for (int e = 1; e < 8; ++e) { const float d = (float)v[e] - p; s += d; q += d * d; }
+    const float a = s * 0.125f;
+    return float2{p + a, q - s * a};
+}
+// (mean, M2) of a row's `nch` chunk summaries of 8 values each (the igemm2 / igemm3 output pass), in chunk order, in one
+// pass: chunk means shifted by the first one (they differ by O(std), so nothing cancels).
+__device__ __forceinline__ float2 row_part_stats(const float* red, int nch) {
+    const float p = red[0];
+    float s = 0.f, q = 0.f;
+    for (int k = 0; k < nch; ++k) { const float d = red[k * 2] - p; s += d; q += red[k * 2 + 1] + 8.f * d * d; }
+    const float a = s / (float)nch;
+    return float2{p + a, q - 8.f * s * a};
+}
+// LayerNorm mean / rstd of a row from its producer's parts: part k is (mean, M2) of columns [k w, min((k+1) w, C)).
+// mean = sum n_k m_k / C, M2 = sum (M2_k + n_k (m_k - mean)^2): the grouped form of the pairwise merge, fixed order.
+template <int MAXP>
+__device__ __forceinline__ void ln_row_stats(const float2 (&pv)[MAXP], int parts, int w, int C, float eps, float& mean,
+                                             float& rstd) {
+    const float inv = 1.0f / (float)C;
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < MAXP; ++k) {
+        const int nk = C - k * w < w ? C - k * w : w;
+        s += k < parts ? (float)nk * pv[k].x : 0.f;
+    }
+    mean = s * inv;
+    float q = 0.f;
+#pragma unroll
+    for (int k = 0; k < MAXP; ++k) {
+        const int nk = C - k * w < w ? C - k * w : w;
+        const float d = pv[k].x - mean;
+        q += k < parts ? pv[k].y + (float)nk * d * d : 0.f;
+    }
+    rstd = rsqrtf(q * inv + eps);
+}
 #endif

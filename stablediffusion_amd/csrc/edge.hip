@@ -20,16 +20,6 @@
 namespace sd {
 namespace {
 
-__device__ __forceinline__ void edge_chan_merge(float& nA, float& mA, float& qA, float nB, float mB, float qB) {
-    if (nB <= 0.f) return;
-    const float n = nA + nB;
-    const float d = mB - mA;
-    const float f = nB / n;
-    mA += d * f;
-    qA += qB + d * d * nA * f;
-    nA = n;
-}
-
 // ------------------------------------------------------------------------------------------------------------------
 // conv_in
 // ------------------------------------------------------------------------------------------------------------------
@@ -218,7 +208,7 @@ __global__ __launch_bounds__(512) void conv_tail_kernel(TailParams p) {
             for (int k = pi; k < p.gn_S; k += kTailMaxParts) {
                 long rows = HW - (long)k * p.gn_rows;
                 if (rows > p.gn_rows) rows = p.gn_rows;
-                edge_chan_merge(nA, mA, qA, (float)rows * (float)cpg, src[(long)k * p.G * 2], src[(long)k * p.G * 2 + 1]);
+                stat_merge(nA, mA, qA, (float)rows * (float)cpg, src[(long)k * p.G * 2], src[(long)k * p.G * 2 + 1]);
             }
             sRed[(pi * p.G + gi) * 3] = nA; sRed[(pi * p.G + gi) * 3 + 1] = mA; sRed[(pi * p.G + gi) * 3 + 2] = qA;
         }
@@ -226,7 +216,7 @@ __global__ __launch_bounds__(512) void conv_tail_kernel(TailParams p) {
     __syncthreads();
     if (tid < p.G) {
         float nA = sRed[tid * 3], mA = sRed[tid * 3 + 1], qA = sRed[tid * 3 + 2];
-        for (int k = 1; k < kTailMaxParts; ++k) edge_chan_merge(nA, mA, qA, sRed[(k * p.G + tid) * 3], sRed[(k * p.G + tid) * 3 + 1], sRed[(k * p.G + tid) * 3 + 2]);
+        for (int k = 1; k < kTailMaxParts; ++k) stat_merge(nA, mA, qA, sRed[(k * p.G + tid) * 3], sRed[(k * p.G + tid) * 3 + 1], sRed[(k * p.G + tid) * 3 + 2]);
         const float var = qA / ((float)HW * (float)cpg);
         sGS[tid * 2] = mA;
         sGS[tid * 2 + 1] = rsqrtf((var < 0.f ? 0.f : var) + p.eps);

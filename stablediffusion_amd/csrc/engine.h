@@ -50,12 +50,13 @@ struct ConvW {          // conv or linear, packed [rows_pad][K] fp16 + fp32 bias
     long K = 0;         // packed K (>= ks*ks*cin, multiple of 64)
     float* wsum = nullptr;   // row sums of the packed weights: set when a LayerNorm was folded in (fold_ln)
 };
-// Per-row (sum, sum of squares) partials of an activation tensor, `parts` pairs per row: written by
-// the GEMM that produced the tensor (or by launch_row_stats), consumed by the GEMM that applies the
-// folded LayerNorm (IGemmParams::rowstat_out / ln_stat).
+// Per-row (mean, M2) parts of an activation tensor, `parts` pairs per row, part k over the columns
+// [k width, min((k + 1) width, C)): written by the GEMM that produced the tensor (or by launch_row_stats,
+// one part of width C), consumed by the GEMM that applies the folded LayerNorm (IGemmParams::rowstat_out / ln_stat).
 struct RowStat {
     float* p = nullptr;
     int parts = 0;
+    int width = 0;
 };
 // GroupNorm summaries of an activation tensor written by the convolution that produced it: `buf` is
 // caller-allocated (gnstat_floats), `st` is filled in by op_conv when the launch really emits them

@@ -81,18 +81,10 @@ __global__ __launch_bounds__(512) void ffn_fused_kernel(FfnParams p) {
         const float2* src = reinterpret_cast<const float2*>(p.ln_stat) + (long)(m0 + tid) * p.ln_parts;
 #pragma unroll
         for (int k = 0; k < kFfMaxLnParts; ++k) pv[k] = src[k < p.ln_parts ? k : p.ln_parts - 1];
-        float sm = 0.f, sq = 0.f;
-#pragma unroll
-        for (int k = 0; k < kFfMaxLnParts; ++k) {
-            sm += k < p.ln_parts ? pv[k].x : 0.f;
-            sq += k < p.ln_parts ? pv[k].y : 0.f;
-        }
-        const float inv = 1.0f / (float)C;
-        const float mean = sm * inv;
-        float var = sq * inv - mean * mean;
-        var = var < 0.f ? 0.f : var;
+        float mean, rstd;
+        ln_row_stats(pv, p.ln_parts, p.ln_part_w, C, p.ln_eps, mean, rstd);
         sStat[tid * 2] = mean;
-        sStat[tid * 2 + 1] = rsqrtf(var + p.ln_eps);
+        sStat[tid * 2 + 1] = rstd;
     }
     __syncthreads();
 

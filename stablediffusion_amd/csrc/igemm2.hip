@@ -56,33 +56,68 @@ struct IGemm2Lds {
 };
 
 // GroupNorm summaries of one output tile (all BM rows inside one image): every thread hands in the
-// sums / sums of squares of its column chunk's channels, split over the (at most two) groups the chunk
-// touches; one thread per group of the tile adds them in a fixed order and stores
-// (mean, M2 = Q - S * mean) at dst[g * 2].  Tile-level plain sums (BM * cpg <= a few thousand values),
-// merged across tiles with chan_merge by the consumer.
+// (mean, M2) of its column chunk's channels over its rows, split over the (at most two) groups the chunk
+// touches (gn_chunk_accum / gn_part_finish); one thread per group of the tile merges them in a fixed order (Chan) and stores
+// (mean, M2) at dst[g * 2], merged across tiles with stat_merge by the consumer.
 template <int BM, int BN, int NT>
-__device__ __forceinline__ void gn_tile_stats(float* sG, int tid, float gs0, float gq0, float gs1, float gq1, int n0,
+__device__ __forceinline__ void gn_tile_stats(float* sG, int tid, float gm0, float gq0, float gm1, float gq1, int n0,
                                               int Cout, int cpg, int groups, float* dst) {
     constexpr int CH = BN / 8;
     constexpr int RPP = NT / CH;
-    *reinterpret_cast<f4*>(sG + tid * 4) = f4{gs0, gq0, gs1, gq1};
+    *reinterpret_cast<f4*>(sG + tid * 4) = f4{gm0, gq0, gm1, gq1};
     __syncthreads();
     const int cols = Cout - n0 < BN ? Cout - n0 : BN;
     const int ng = cols / cpg;                           // groups of this tile (tile columns start on a group)
     if (tid < ng) {
         const int g = n0 / cpg + tid;                    // global group
         const int cfirst = (tid * cpg) / 8, clast = ((tid + 1) * cpg - 1) / 8;
-        float sm = 0.f, sq = 0.f;
+        // grouped form of the pairwise merge in one pass, piece means shifted by the first piece's (they differ by
+        // O(std)): mean = P + S / n, M2 = sum (M2_k + n_k d_k^2) - S^2 / n with d_k = m_k - P, S = sum n_k d_k; fixed order
+        const int cf = n0 + cfirst * 8;
+        const float pvt = sG[((cf / cpg == g) ? 0 : 2) + cfirst * 4];   // (rr = 0, chunk cfirst)
+        float s = 0.f, q = 0.f;
         for (int c8 = cfirst; c8 <= clast; ++c8) {
-            const int part = ((n0 + c8 * 8) / cpg == g) ? 0 : 2;     // the chunk's first group, or its second
+            const int c0 = n0 + c8 * 8;
+            const int part = (c0 / cpg == g) ? 0 : 2;    // the chunk's first group, or its second
+            const int lo = c0 > g * cpg ? c0 : g * cpg, hi = c0 + 8 < (g + 1) * cpg ? c0 + 8 : (g + 1) * cpg;
             for (int rr = 0; rr < RPP; ++rr) {
                 const float2 v = *reinterpret_cast<const float2*>(sG + (rr * CH + c8) * 4 + part);
-                sm += v.x; sq += v.y;
+                const float nk = (float)(((BM - rr + RPP - 1) / RPP) * (hi - lo));   // rows rr, rr + RPP, ... < BM
+                const float d = v.x - pvt;
+                s += nk * d;
+                q += v.y + nk * d * d;
             }
         }
-        const float mean = sm / (float)(BM * cpg);
-        *reinterpret_cast<float2*>(dst + (long)g * 2) = float2{mean, sq - sm * mean};
+        const float a = s / (float)(BM * cpg);
+        *reinterpret_cast<float2*>(dst + (long)g * 2) = float2{pvt + a, q - s * a};
     }
+}
+// One stored row chunk (8 channels from n) into the thread's sums of the chunk's first group (channels e < gsplit) and
+// of its second, each shifted by a pivot: the first value of that part the thread sees (first = its first row).  The
+// sums then cancel nothing whatever |mean| / std is; gn_part_finish turns them into (mean, M2).
+__device__ __forceinline__ void gn_chunk_accum(const h8& v, int gsplit, bool first, float& p0, float& p1, float& s0,
+                                               float& q0, float& s1, float& q1) {
+    if (first) {
+        p0 = (float)v[0];
+        float b = (float)v[7];
+#pragma unroll
+        for (int e = 1; e < 7; ++e) b = e == gsplit ? (float)v[e] : b;
+        p1 = b;
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const float f = (float)v[e];
+        if (e < gsplit) { const float d = f - p0; s0 += d; q0 += d * d; } else { const float d = f - p1; s1 += d; q1 += d * d; }
+    }
+}
+// Shifted sums over `rows` stored rows -> (mean, M2) of each part, in place (s -> mean, q -> M2).
+__device__ __forceinline__ void gn_part_finish(int gsplit, int rows, float p0, float p1, float& s0, float& q0, float& s1,
+                                               float& q1) {
+    const int c0 = gsplit < 8 ? gsplit : 8;
+    const float n0 = (float)(rows * c0), n1 = (float)(rows * (8 - c0));
+    const float a0 = n0 > 0.f ? s0 / n0 : 0.f, a1 = n1 > 0.f ? s1 / n1 : 0.f;
+    q0 -= s0 * a0; q1 -= s1 * a1;
+    s0 = p0 + a0; s1 = p1 + a1;
 }
 
 template <int BM, int BN, int WAVES_M, int WAVES_N, int STAGES, bool PW, bool STAG, int BKT>
@@ -269,18 +304,10 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void igemm2_kernel(IGemmPar
             // wait per element)
 #pragma unroll
             for (int k = 0; k < kMaxLnParts; ++k) pv[k] = src[k < p.ln_parts ? k : p.ln_parts - 1];
-            float sm = 0.f, sq = 0.f;
-#pragma unroll
-            for (int k = 0; k < kMaxLnParts; ++k) {
-                sm += k < p.ln_parts ? pv[k].x : 0.f;
-                sq += k < p.ln_parts ? pv[k].y : 0.f;
-            }
-            const float inv = 1.0f / (float)p.ln_C;
-            const float mean = sm * inv;
-            float var = sq * inv - mean * mean;
-            var = var < 0.f ? 0.f : var;
+            float mean, rstd;
+            ln_row_stats(pv, p.ln_parts, p.ln_part_w, p.ln_C, p.ln_eps, mean, rstd);
             sStat[tid * 2] = mean;
-            sStat[tid * 2 + 1] = rsqrtf(var + p.ln_eps);
+            sStat[tid * 2 + 1] = rstd;
         }
     }
 
@@ -456,7 +483,9 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void igemm2_kernel(IGemmPar
     const int cpg = p.gnstat_out ? p.Cout / p.gn_groups : 8;
     const int g_first = n / cpg;
     const int gsplit = (g_first + 1) * cpg - n;          // channels e < gsplit belong to g_first
-    float gs0 = 0.f, gq0 = 0.f, gs1 = 0.f, gq1 = 0.f;
+    float gm0 = 0.f, gq0 = 0.f, gm1 = 0.f, gq1 = 0.f;     // pivot-shifted sums per group part, then (mean, M2)
+    float gp0 = 0.f, gp1 = 0.f;
+    int gnv = 0;                                         // rows stored by this thread
 #pragma unroll
     for (int it = 0; it < ITER; ++it) {
         const int r = rr + it * RPP;
@@ -468,35 +497,25 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void igemm2_kernel(IGemmPar
                 for (int e = 0; e < 8; ++e) v[e] = (half_t)((float)v[e] + (float)rv[it][e]);
             }
             *reinterpret_cast<h8*>(p.y + (long)m * p.ldy + n) = v;
-            if (p.rowstat_out) {
-                float sm = 0.f, sq = 0.f;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) { const float f = (float)v[e]; sm += f; sq += f * f; }
-                *reinterpret_cast<float2*>(sRed + (r * CH + c8) * 2) = float2{sm, sq};
-            }
-            if (p.gnstat_out) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const float f = (float)v[e];
-                    if (e < gsplit) { gs0 += f; gq0 += f * f; } else { gs1 += f; gq1 += f * f; }
-                }
-            }
+            if (p.rowstat_out) *reinterpret_cast<float2*>(sRed + (r * CH + c8) * 2) = chunk8_stats(v);
+            if (p.gnstat_out) { gn_chunk_accum(v, gsplit, it == 0, gp0, gp1, gm0, gq0, gm1, gq1); ++gnv; }
         }
     }
     // Row statistics of the stored tile for a LayerNorm that follows (IGemmParams::rowstat_out): the
-    // chunk partials are added per row in chunk order (fixed order: bitwise reproducible).
+    // chunk summaries are merged per row in chunk order (fixed order: bitwise reproducible).
     if (p.rowstat_out) {
         __syncthreads();
         if (tid < BM && m0 + tid < p.M) {
             const int nch = (p.Cout - n0 < BN ? p.Cout - n0 : BN) / 8;
-            float sm = 0.f, sq = 0.f;
-            for (int k = 0; k < nch; ++k) { const float2 v = *reinterpret_cast<const float2*>(sRed + (tid * CH + k) * 2); sm += v.x; sq += v.y; }
-            *reinterpret_cast<float2*>(p.rowstat_out + ((long)(m0 + tid) * p.rowstat_parts + tn) * 2) = float2{sm, sq};
+            *reinterpret_cast<float2*>(p.rowstat_out + ((long)(m0 + tid) * p.rowstat_parts + tn) * 2) =
+                row_part_stats(sRed + tid * CH * 2, nch);
         }
     }
-    if (p.gnstat_out)
-        gn_tile_stats<BM, BN, NT>(sG, tid, gs0, gq0, gs1, gq1, n0, p.Cout, cpg, p.gn_groups,
+    if (p.gnstat_out) {
+        gn_part_finish(gsplit, gnv, gp0, gp1, gm0, gq0, gm1, gq1);
+        gn_tile_stats<BM, BN, NT>(sG, tid, gm0, gq0, gm1, gq1, n0, p.Cout, cpg, p.gn_groups,
                                   p.gnstat_out + ((long)(m0 / OHW) * (OHW / BM) + (m0 % OHW) / BM) * p.gn_groups * 2);
+    }
 #endif  // __HIP_DEVICE_COMPILE__
 }
 
@@ -605,29 +624,33 @@ __global__ __launch_bounds__(256) void splitk_epilogue_gs_kernel(IGemmParams p, 
         }
         *reinterpret_cast<h8*>(p.y + m * p.ldy + n) = o;
         const int gsplit = (n / cpg + 1) * cpg - n;          // channels e < gsplit belong to the chunk's first group
-        float gs0 = 0.f, gq0 = 0.f, gs1 = 0.f, gq1 = 0.f;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const float f = (float)o[e];
-            if (e < gsplit) { gs0 += f; gq0 += f * f; } else { gs1 += f; gq1 += f * f; }
-        }
-        *reinterpret_cast<f4*>(sI + (long)idx * 4) = f4{gs0, gq0, gs1, gq1};
+        float gm0 = 0.f, gq0 = 0.f, gm1 = 0.f, gq1 = 0.f, gp0 = 0.f, gp1 = 0.f;
+        gn_chunk_accum(o, gsplit, true, gp0, gp1, gm0, gq0, gm1, gq1);
+        gn_part_finish(gsplit, 1, gp0, gp1, gm0, gq0, gm1, gq1);
+        *reinterpret_cast<f4*>(sI + (long)idx * 4) = f4{gm0, gq0, gm1, gq1};
     }
     __syncthreads();
     const int gl = threadIdx.x;                              // group inside the column block
     if (gl < cw / cpg) {
         const int cfirst = (gl * cpg) / 8, clast = ((gl + 1) * cpg - 1) / 8;
-        float sm = 0.f, sq = 0.f;
+        // one pass, piece means shifted by the first piece's (as gn_tile_stats)
+        const float pvt = sI[(long)cfirst * 4 + (((cfirst * 8) / cpg == gl) ? 0 : 2)];
+        float s = 0.f, q = 0.f;
         for (int c8 = cfirst; c8 <= clast; ++c8) {
             const int off = ((c8 * 8) / cpg == gl) ? 0 : 2;
+            const int lo = c8 * 8 > gl * cpg ? c8 * 8 : gl * cpg, hi = c8 * 8 + 8 < (gl + 1) * cpg ? c8 * 8 + 8 : (gl + 1) * cpg;
+            const float nk = (float)(hi - lo);
             for (int r = 0; r < RB; ++r) {
                 const float2 v = *reinterpret_cast<const float2*>(sI + ((long)r * CH + c8) * 4 + off);
-                sm += v.x; sq += v.y;
+                const float d = v.x - pvt;
+                s += nk * d;
+                q += v.y + nk * d * d;
             }
         }
-        const float mean = sm / (float)(RB * cpg);
+        const float a = s / (float)(RB * cpg);
         const long img = m0 / OHW, sl = (m0 - img * OHW) / RB;
-        *reinterpret_cast<float2*>(p.gnstat_out + ((img * (OHW / RB) + sl) * p.gn_groups + c0 / cpg + gl) * 2) = float2{mean, sq - sm * mean};
+        *reinterpret_cast<float2*>(p.gnstat_out + ((img * (OHW / RB) + sl) * p.gn_groups + c0 / cpg + gl) * 2) =
+            float2{pvt + a, q - s * a};
     }
 }
 // Rows per block of that kernel for a problem (0: it cannot leave the summaries) and its column block
@@ -1062,7 +1085,9 @@ __global__ __launch_bounds__(512) void conv3x3_halo_kernel(IGemmParams p, float*
     const int cpg = (GN && p.gnstat_out) ? p.Cout / p.gn_groups : 8;
     const int g_first = n / cpg;
     const int gsplit = (g_first + 1) * cpg - n;
-    float gs0 = 0.f, gq0 = 0.f, gs1 = 0.f, gq1 = 0.f;
+    float gm0 = 0.f, gq0 = 0.f, gm1 = 0.f, gq1 = 0.f;     // pivot-shifted sums per group part, then (mean, M2)
+    float gp0 = 0.f, gp1 = 0.f;
+    int gnv = 0;                                         // rows stored by this thread
 #pragma unroll
     for (int it = 0; it < ITER; ++it) {
         const int r = rr + it * RPP;
@@ -1073,19 +1098,14 @@ __global__ __launch_bounds__(512) void conv3x3_halo_kernel(IGemmParams p, float*
                 for (int e = 0; e < 8; ++e) v[e] = (half_t)((float)v[e] + (float)rv[it][e]);
             }
             *reinterpret_cast<h8*>(p.y + (long)row_of(r) * p.ldy + n) = v;
-            if (GN && p.gnstat_out) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const float f = (float)v[e];
-                    if (e < gsplit) { gs0 += f; gq0 += f * f; } else { gs1 += f; gq1 += f * f; }
-                }
-            }
+            if (GN && p.gnstat_out) { gn_chunk_accum(v, gsplit, it == 0, gp0, gp1, gm0, gq0, gm1, gq1); ++gnv; }
         }
     }
     if constexpr (GN) {
         if (p.gnstat_out) {
             float* sG = reinterpret_cast<float*>(smem + ((BM * LDC * 2 + 15) & ~15));     // behind the staging tile
-            gn_tile_stats<BM, BN, NT>(sG, tid, gs0, gq0, gs1, gq1, n0, p.Cout, cpg, p.gn_groups,
+            gn_part_finish(gsplit, gnv, gp0, gp1, gm0, gq0, gm1, gq1);
+            gn_tile_stats<BM, BN, NT>(sG, tid, gm0, gq0, gm1, gq1, n0, p.Cout, cpg, p.gn_groups,
                                       p.gnstat_out + ((long)img * patches + pidx) * p.gn_groups * 2);
         }
     }
@@ -1284,7 +1304,7 @@ void igemm2_pick(const IGemmParams& p, int* variant, int* splits) {
     if (*variant == 14 && !p.geglu) *variant = 13;
 }
 
-bool igemm2_emits_rowstats(const IGemmParams& p, int* parts) {
+bool igemm2_emits_rowstats(const IGemmParams& p, int* parts, int* part_w) {
     if (!igemm2_supported(p) || p.geglu) return false;
     int v, sp;
     IGemmParams q = p;                                  // the choice as it will be made WITH the statistics requested
@@ -1292,10 +1312,11 @@ bool igemm2_emits_rowstats(const IGemmParams& p, int* parts) {
     if (!q.rowstat_out) q.rowstat_out = &sentinel;
     igemm2_pick(q, &v, &sp);
     if (sp > 1 || v == 10 || v == 15) return false;
-    if (v == 13) { *parts = wsgemm_rowstat_parts(p); return *parts <= kMaxLnParts; }
+    if (v == 13) { *parts = wsgemm_rowstat_parts(p); *part_w = 80; return *parts <= kMaxLnParts; }
     int bm, bn;
     tile_dims(v, &bm, &bn);
     *parts = cdiv(p.Cout, bn);
+    *part_w = bn;
     return *parts <= kMaxLnParts;
 }
 
@@ -1379,13 +1400,29 @@ long igemm2_partial_floats(const IGemmParams& p) {
     return sp > 1 ? (long)sp * p.M * p.Cout : 0;
 }
 
+static bool takes_pgemm_geglu(const IGemmParams& p, int v) {
+    static const bool pg_k320 = getenv("SD_PGEMM_K320") != nullptr;       // A/B: the K = 320 GEGLU on it instead of wsgemm
+    return p.geglu && ((v != 13 && v != 14) || pg_k320) && g_force_variant.load() < 0 && pgemm_geglu_supported(p);
+}
+static bool takes_igemm3(const IGemmParams& p, int v, int sp) {
+    static const bool g3_auto = getenv("SD_IGEMM3") != nullptr;        // off by default: measured not faster (igemm3.hip)
+    return (v == 11 || v == 12 || v == 18) && sp <= 1 && (v == 18 || (g3_auto && g_force_variant.load() < 0)) && igemm3_supported(p);
+}
+
+int igemm2_launch_kind(const IGemmParams& p, bool have_partial) {
+    int v, sp;
+    igemm2_pick(p, &v, &sp);
+    if (sp > 1 && !have_partial) sp = 1;
+    if (takes_pgemm_geglu(p, v)) return kKindPgemmGeglu;
+    if (takes_igemm3(p, v, sp)) return 18;
+    return v == 18 ? 12 : v;
+}
+
 int launch_igemm2(const IGemmParams& p, float* partial, hipStream_t s) {
     int v, sp;
     igemm2_pick(p, &v, &sp);
     if (sp > 1 && !partial) sp = 1;
-    static const bool pg_k320 = getenv("SD_PGEMM_K320") != nullptr;       // A/B: the K = 320 GEGLU on it instead of wsgemm
-    if (p.geglu && ((v != 13 && v != 14) || pg_k320) && g_force_variant.load() < 0 && pgemm_geglu_supported(p))
-        return launch_pgemm_geglu(p, s);
+    if (takes_pgemm_geglu(p, v)) return launch_pgemm_geglu(p, s);
     switch (v) {
         case 0: return launch_v2<256, 128, 4, 2, 3>(p, partial, sp, s);
         case 1: return launch_v2<128, 128, 2, 2, 2>(p, partial, sp, s);
@@ -1404,11 +1441,7 @@ int launch_igemm2(const IGemmParams& p, float* partial, hipStream_t s) {
         case 18:
             // 18 = igemm3_kernel (activation operand through the ordinary load path instead of the LDS-DMA ring) asked for by
             // name (tests, tuner), falling back to the 3-stage DMA tile for problems it does not take
-            {
-                static const bool g3_auto = getenv("SD_IGEMM3") != nullptr;        // off by default: measured not faster (igemm3.hip)
-                if (sp <= 1 && (v == 18 || (g3_auto && g_force_variant.load() < 0)) && igemm3_supported(p))
-                    return launch_igemm3(p, weights_outweigh_activations(p), s);
-            }
+            if (takes_igemm3(p, v, sp)) return launch_igemm3(p, weights_outweigh_activations(p), s);
             if (v == 11) return launch_v2<128, 80, 4, 1, 2>(p, partial, sp, s);
             return launch_v2<128, 80, 4, 1, 3>(p, partial, sp, s);
         case 16: return launch_v2<128, 80, 4, 1, 4>(p, partial, sp, s);

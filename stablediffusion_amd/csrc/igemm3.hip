@@ -156,18 +156,10 @@ __global__ __launch_bounds__(256) void igemm3_kernel(IGemmParams p) {
             const float2* src = reinterpret_cast<const float2*>(p.ln_stat) + (long)(m < p.M ? m : 0) * p.ln_parts;
 #pragma unroll
             for (int k = 0; k < kG3MaxLnParts; ++k) pv[k] = src[k < p.ln_parts ? k : p.ln_parts - 1];
-            float sm = 0.f, sq = 0.f;
-#pragma unroll
-            for (int k = 0; k < kG3MaxLnParts; ++k) {
-                sm += k < p.ln_parts ? pv[k].x : 0.f;
-                sq += k < p.ln_parts ? pv[k].y : 0.f;
-            }
-            const float inv = 1.0f / (float)p.ln_C;
-            const float mean = sm * inv;
-            float var = sq * inv - mean * mean;
-            var = var < 0.f ? 0.f : var;
+            float mean, rstd;
+            ln_row_stats(pv, p.ln_parts, p.ln_part_w, p.ln_C, p.ln_eps, mean, rstd);
             sStat[tid * 2] = mean;
-            sStat[tid * 2 + 1] = rsqrtf(var + p.ln_eps);
+            sStat[tid * 2 + 1] = rstd;
         }
     }
 
@@ -261,21 +253,15 @@ __global__ __launch_bounds__(256) void igemm3_kernel(IGemmParams p) {
                 for (int e = 0; e < 8; ++e) v[e] = (half_t)((float)v[e] + (float)rv[it][e]);
             }
             *reinterpret_cast<h8*>(p.y + (long)m * p.ldy + n) = v;
-            if (p.rowstat_out) {
-                float sm = 0.f, sq = 0.f;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) { const float f = (float)v[e]; sm += f; sq += f * f; }
-                *reinterpret_cast<float2*>(sRed + (r * CH + c8) * 2) = float2{sm, sq};
-            }
+            if (p.rowstat_out) *reinterpret_cast<float2*>(sRed + (r * CH + c8) * 2) = chunk8_stats(v);
         }
     }
     if (p.rowstat_out) {
         __syncthreads();
         if (tid < BM && m0 + tid < p.M) {
             const int nch = (p.Cout - n0 < BN ? p.Cout - n0 : BN) / 8;
-            float sm = 0.f, sq = 0.f;
-            for (int k = 0; k < nch; ++k) { const float2 v = *reinterpret_cast<const float2*>(sRed + (tid * CH + k) * 2); sm += v.x; sq += v.y; }
-            *reinterpret_cast<float2*>(p.rowstat_out + ((long)(m0 + tid) * p.rowstat_parts + tn) * 2) = float2{sm, sq};
+            *reinterpret_cast<float2*>(p.rowstat_out + ((long)(m0 + tid) * p.rowstat_parts + tn) * 2) =
+                row_part_stats(sRed + tid * CH * 2, nch);
         }
     }
 #endif  // __HIP_DEVICE_COMPILE__

@@ -32,16 +32,17 @@ struct IGemmParams {
     int act = 0;            // activation after bias, before residual (LDS-DMA kernels, no split-K):
                             // 0 none, 1 quick_gelu x*sigmoid(1.702x) (CLIP-L MLP), 2 exact-erf gelu (OpenCLIP MLP)
     // ---- LayerNorm folded across the GEMM (LDS-DMA kernels, pointwise, no split-K) ----
-    // Producer side: the epilogue also writes, per output row and per column tile of this launch, the sum
-    // and the sum of squares of the fp16 values it stores: rowstat_out[(m * rowstat_parts + tile_n) * 2 + {0,1}].
+    // Producer side: the epilogue also writes, per output row and per column tile of this launch, the mean and
+    // M2 = sum (v - mean)^2 of the fp16 values it stores: rowstat_out[(m * rowstat_parts + tile_n) * 2 + {0,1}].
     float* rowstat_out = nullptr;
     int rowstat_parts = 0;          // = column tiles of the launch (filled in by the launcher)
     // Consumer side: y = LN(x) W^T + b with LN's affine folded into the weights at pack time
     // (W' = W diag(gamma), b' = b + W beta, wsum_n = sum_k W'_nk) becomes
     //     y[m, n] = rstd_m * (acc[m, n] - mean_m * wsum[n]) + b'[n],   acc = x W'^T on the raw x
-    // with mean / rstd of row m from the producer's partial sums (ln_parts of them, over ln_C channels).
+    // with mean / rstd of row m from the producer's (mean, M2) parts: ln_parts of them, part k over the columns
+    // [k ln_part_w, min((k + 1) ln_part_w, ln_C)).
     const float* ln_stat = nullptr;
-    int ln_parts = 0, ln_C = 0;
+    int ln_parts = 0, ln_C = 0, ln_part_w = 0;
     float ln_eps = 0.f;
     const float* ln_wsum = nullptr;
     // ---- GroupNorm statistics of the output, for the GroupNorm that follows (LDS-DMA kernels, no split-K,
@@ -73,8 +74,9 @@ bool igemm2_scales_ok(const IGemmParams& p);
 // Whether launch_igemm2 will honour p.gnstat_out for `groups` groups; *rows = pixels per tile (GnStats::rows).
 bool igemm2_emits_gnstats(const IGemmParams& p, int groups, int* rows);
 // Whether launch_igemm2 will honour p.rowstat_out for this problem (LDS-DMA kernel, no split-K); when not,
-// the caller runs launch_row_stats on the output instead.  Fills *parts with the column-tile count.
-bool igemm2_emits_rowstats(const IGemmParams& p, int* parts);
+// the caller runs launch_row_stats on the output instead.  Fills *parts with the column-tile count and *part_w with
+// the columns per part (the last one ragged).
+bool igemm2_emits_rowstats(const IGemmParams& p, int* parts, int* part_w);
 int launch_igemm(const IGemmParams& p, hipStream_t s);
 const char* igemm_variant(const IGemmParams& p);   // name of the tile variant launch_igemm picks
 // LDS-DMA pipeline variants (igemm2.hip); falls back to launch_igemm when !igemm2_supported().
@@ -83,6 +85,10 @@ void igemm2_pick(const IGemmParams& p, int* variant, int* splits);
 const char* igemm2_name(int variant);
 long igemm2_partial_floats(const IGemmParams& p);      // fp32 workspace needed for split-K (0 if none)
 int launch_igemm2(const IGemmParams& p, float* partial, hipStream_t s);
+// Which kernel launch_igemm2 runs for p: the variant id (18 only when igemm3_kernel takes the problem), or
+// kKindPgemmGeglu for geglu_persist_kernel.  have_partial: a split-K workspace is passed.
+constexpr int kKindPgemmGeglu = 100;
+int igemm2_launch_kind(const IGemmParams& p, bool have_partial);
 void igemm2_force(int variant, int splits);            // tuner / tests: -1 restores the heuristic
 // Pointwise 128 x 80 tile with the activation operand fetched straight into registers (igemm3.hip): launch_igemm2 takes
 // it instead of the 128 x 80 LDS-DMA variants when the problem allows (no split-K, GEGLU, row add, GroupNorm summaries).
@@ -110,6 +116,7 @@ struct FfnParams {
     const half_t* w2; const float* b2; int w2_rows;                          // [w2_rows >= 384][4C]
     const float* ln_stat; int ln_parts; float ln_eps;
     int M, C, hidden;
+    int ln_part_w;                      // columns per ln_stat part (IGemmParams::ln_part_w)
 };
 bool ffn_fused_supported(const FfnParams& p);
 int launch_ffn_fused(const FfnParams& p, hipStream_t s);

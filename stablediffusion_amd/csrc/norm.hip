@@ -25,23 +25,14 @@ __host__ __device__ inline int gn_block_channels(int C, int G) {
     return cb > C ? C : cb;
 }
 
-// Merge of two (count, mean, M2) summaries (Chan et al.): exact up to rounding whatever |mean| / std is,
-// unlike E[x^2] - mean^2 (a VAE group spans up to 4 M elements with eps = 1e-6).
-__device__ __forceinline__ void chan_merge(float& nA, float& mA, float& qA, float nB, float mB, float qB) {
-    if (nB <= 0.f) return;
-    const float n = nA + nB;
-    const float d = mB - mA;
-    const float f = nB / n;
-    mA += d * f;
-    qA += qB + d * d * nA * f;
-    nA = n;
-}
+// Merges of (count, mean, M2) summaries: stat_merge (common.h), Chan's update -- exact up to rounding whatever
+// |mean| / std is, unlike E[x^2] - mean^2 (a VAE group spans up to 4 M elements with eps = 1e-6).
 
 // Pass 1: per-(n, slab, group) statistics as (mean, M2 = sum (x - mean)^2) of the slab's
 // rows_per x channels-per-group elements:  part[((n*S + s)*G + g)*2 + {0,1}].  Each thread accumulates
 // its pixels per channel SHIFTED by the first value it sees for that channel (sums of x - x0 and their
 // squares cancel nothing even when |mean| >> std); thread, channel and slab summaries are then merged
-// with chan_merge in a fixed order.
+// with stat_merge in a fixed order.
 __global__ __launch_bounds__(256) void gn_stats_kernel(const half_t* __restrict__ x, long ldx,
                                                        float* __restrict__ part, long HW, int C,
                                                        int G, int S, int CB) {
@@ -111,7 +102,7 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const half_t* __restrict_
             const float nB = rcnt[t];
             float nn = nA;
 #pragma unroll
-            for (int e = 0; e < 8; ++e) { nn = nA; chan_merge(nn, mA[e], qA[e], nB, red[t * 16 + e], red[t * 16 + 8 + e]); }
+            for (int e = 0; e < 8; ++e) { nn = nA; stat_merge(nn, mA[e], qA[e], nB, red[t * 16 + e], red[t * 16 + 8 + e]); }
             nA = nn;
         }
 #pragma unroll
@@ -124,7 +115,7 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const half_t* __restrict_
     if (tid < ng) {
         const float per = (float)(p1 - p0);          // every channel of the slab saw p1 - p0 pixels
         float nA = per, mA = chan[(tid * cpg) * 2], qA = chan[(tid * cpg) * 2 + 1];
-        for (int c = 1; c < cpg; ++c) chan_merge(nA, mA, qA, per, chan[(tid * cpg + c) * 2], chan[(tid * cpg + c) * 2 + 1]);
+        for (int c = 1; c < cpg; ++c) stat_merge(nA, mA, qA, per, chan[(tid * cpg + c) * 2], chan[(tid * cpg + c) * 2 + 1]);
         float* dst = part + (((long)n * S + s) * G + c0 / cpg + tid) * 2;
         dst[0] = mA; dst[1] = qA;
     }
@@ -143,12 +134,12 @@ __global__ __launch_bounds__(256) void gn_finalize_kernel(const float* __restric
         long rows = HW - (long)k * rows_per;
         if (rows > rows_per) rows = rows_per;
         const float2 v = *reinterpret_cast<const float2*>(part + (((long)n * S + k) * G + g) * 2);
-        chan_merge(nA, mA, qA, (float)rows * (float)cpg, v.x, v.y);
+        stat_merge(nA, mA, qA, (float)rows * (float)cpg, v.x, v.y);
     }
     rn[tid] = nA; rm[tid] = mA; rq[tid] = qA;
     __syncthreads();
     if (tid == 0) {
-        for (int k = 1; k < 256 && k < S; ++k) chan_merge(nA, mA, qA, rn[k], rm[k], rq[k]);
+        for (int k = 1; k < 256 && k < S; ++k) stat_merge(nA, mA, qA, rn[k], rm[k], rq[k]);
         float* dst = out + ((long)n * G + g) * 2;
         dst[0] = mA; dst[1] = qA;
     }
@@ -195,7 +186,7 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const half_t* __restrict_
         }
     }
     // slab summaries (mean, M2) -> mean / rstd: 256 / G threads per group merge interleaved slabs, then
-    // thread g merges those in order (chan_merge: fixed order, no cancellation)
+    // thread g merges those in order (stat_merge: fixed order, no cancellation)
     const int parts = 256 / G;
     {
         const int g = tid % G, part_i = tid / G;
@@ -205,7 +196,7 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const half_t* __restrict_
             for (int k = part_i; k < S; k += parts) {
                 long rows = HW - (long)k * stat_rows;
                 if (rows > stat_rows) rows = stat_rows;
-                chan_merge(nA, mA, qA, (float)rows * (float)cpg, src[(long)k * G * 2], src[(long)k * G * 2 + 1]);
+                stat_merge(nA, mA, qA, (float)rows * (float)cpg, src[(long)k * G * 2], src[(long)k * G * 2 + 1]);
             }
             red[(part_i * G + g) * 3] = nA;
             red[(part_i * G + g) * 3 + 1] = mA;
@@ -215,7 +206,7 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const half_t* __restrict_
     __syncthreads();
     if (tid < G) {
         float nA = red[tid * 3], mA = red[tid * 3 + 1], qA = red[tid * 3 + 2];
-        for (int k = 1; k < parts; ++k) chan_merge(nA, mA, qA, red[(k * G + tid) * 3], red[(k * G + tid) * 3 + 1], red[(k * G + tid) * 3 + 2]);
+        for (int k = 1; k < parts; ++k) stat_merge(nA, mA, qA, red[(k * G + tid) * 3], red[(k * G + tid) * 3 + 1], red[(k * G + tid) * 3 + 2]);
         const float var = qA / ((float)HW * (float)cpg);
         st[tid * 2] = mA;
         st[tid * 2 + 1] = rsqrtf((var < 0.f ? 0.f : var) + eps);
@@ -284,7 +275,7 @@ __global__ __launch_bounds__(256) void gn_apply2_kernel(const half_t* __restrict
     // equal-count summaries (every slab has stat_rows rows), p = the first slab's mean,
     //   a = sum (m_k - p),  b = sum (m_k - p)^2,  q = sum M2_k:   mean = p + a / S,   M2 = q + cnt (b - a^2 / S)
     // (the shift by p keeps b - a^2 / S free of cancellation whatever |mean| / std is).  A ragged last slab takes the
-    // general chan_merge path.
+    // general stat_merge path.
     const bool equal = HW % stat_rows == 0;
     constexpr int KPRE = 4;
     // few summaries (S * ng <= 128: the 32 x 32 maps): wave 0 alone fetches and merges them -- no second barrier, the
@@ -353,14 +344,14 @@ __global__ __launch_bounds__(256) void gn_apply2_kernel(const half_t* __restrict
             for (int k = pi; k < S; k += parts) {
                 long rows = HW - (long)k * stat_rows;
                 if (rows > stat_rows) rows = stat_rows;
-                chan_merge(nA, mA, qA, (float)rows * (float)cpg, src[(long)k * G * 2], src[(long)k * G * 2 + 1]);
+                stat_merge(nA, mA, qA, (float)rows * (float)cpg, src[(long)k * G * 2], src[(long)k * G * 2 + 1]);
             }
             red[(pi * ng + gi) * 3] = nA; red[(pi * ng + gi) * 3 + 1] = mA; red[(pi * ng + gi) * 3 + 2] = qA;
         }
         __syncthreads();
         if (tid < ng) {
             float nA = red[tid * 3], mA = red[tid * 3 + 1], qA = red[tid * 3 + 2];
-            for (int k = 1; k < parts; ++k) chan_merge(nA, mA, qA, red[(k * ng + tid) * 3], red[(k * ng + tid) * 3 + 1], red[(k * ng + tid) * 3 + 2]);
+            for (int k = 1; k < parts; ++k) stat_merge(nA, mA, qA, red[(k * ng + tid) * 3], red[(k * ng + tid) * 3 + 1], red[(k * ng + tid) * 3 + 2]);
             const float var = qA / ((float)HW * (float)cpg);
             st[tid * 2] = mA;
             st[tid * 2 + 1] = rsqrtf((var < 0.f ? 0.f : var) + eps);
@@ -676,23 +667,33 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const half_t* __restrict
     }
 }
 
-// Per-row sum and sum of squares (one wave per row): the stand-alone producer of the LayerNorm
-// statistics for tensors whose GEMM could not emit them from its epilogue (split-K launches).
+// Per-row (mean, M2) in two passes over the row (one wave per row; the second pass reads it from cache): the
+// stand-alone producer of the LayerNorm statistics, one part of width C, for tensors whose GEMM could not emit them
+// from its epilogue (split-K launches).
 __global__ __launch_bounds__(256) void row_stats_kernel(const half_t* __restrict__ x, long ldx, float* __restrict__ stat,
                                                         long rows, int C) {
     const int lane = threadIdx.x & 63;
     const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
     const int CC = C >> 3;
-    float sm = 0.f, sq = 0.f;
+    float sm = 0.f;
     for (int cc = lane; cc < CC; cc += 64) {
         const h8 v = *reinterpret_cast<const h8*>(x + row * ldx + cc * 8);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) { const float f = (float)v[e]; sm += f; sq += f * f; }
+        for (int e = 0; e < 8; ++e) sm += (float)v[e];
     }
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) { sm += __shfl_xor(sm, off); sq += __shfl_xor(sq, off); }
-    if (lane == 0) { stat[row * 2] = sm; stat[row * 2 + 1] = sq; }
+    for (int off = 32; off > 0; off >>= 1) sm += __shfl_xor(sm, off);
+    const float mean = sm / (float)C;
+    float sq = 0.f;
+    for (int cc = lane; cc < CC; cc += 64) {
+        const h8 v = *reinterpret_cast<const h8*>(x + row * ldx + cc * 8);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { const float d = (float)v[e] - mean; sq += d * d; }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) sq += __shfl_xor(sq, off);
+    if (lane == 0) { stat[row * 2] = mean; stat[row * 2 + 1] = sq; }
 }
 
 int gn_slabs(int N, long HW, int C, int G) {

@@ -361,7 +361,7 @@ void op_conv(Ctx& c, const ConvW& w, View x, int N, int H, int W, View y, int st
     p.act = act;
     if (ln_in) {
         if (!w.wsum) { set_error("op_conv: LayerNorm statistics passed to a linear without folded weights"); c.err = 1; return; }
-        p.ln_stat = ln_in->p; p.ln_parts = ln_in->parts; p.ln_C = (int)w.K; p.ln_eps = ln_eps; p.ln_wsum = w.wsum;
+        p.ln_stat = ln_in->p; p.ln_parts = ln_in->parts; p.ln_part_w = ln_in->width; p.ln_C = (int)w.K; p.ln_eps = ln_eps; p.ln_wsum = w.wsum;
     }
     if (fuse && fuse->gn_in) {
         p.gni_part = fuse->gn_in_stats.part; p.gni_S = fuse->gn_in_stats.S; p.gni_rows = fuse->gn_in_stats.rows;
@@ -389,9 +389,10 @@ void op_conv(Ctx& c, const ConvW& w, View x, int N, int H, int W, View y, int st
     // (after the GroupNorm request: the tile choice, and with it the partial count, depends on it)
     bool own_stats = false;      // the GEMM's epilogue writes the row statistics itself
     if (stat_out) {
-        int parts = 1;
-        own_stats = igemm2_emits_rowstats(p, &parts);
+        int parts = 1, part_w = w.cout;
+        own_stats = igemm2_emits_rowstats(p, &parts, &part_w);
         stat_out->parts = own_stats ? parts : 1;
+        stat_out->width = own_stats ? part_w : w.cout;
         if (own_stats) p.rowstat_out = stat_out->p;
     }
     if (act && !v2) { set_error("op_conv: activation epilogue needs the LDS-DMA kernel (Cin % 64, Cout % 8)"); c.err = 1; return; }
@@ -513,7 +514,7 @@ bool op_ffn_fused(Ctx& c, const ConvW& ff1, const ConvW& ff2, View x, const RowS
     p.w1_rows = (int)(((long)ff1.cout + kWeightRowPad - 1) / kWeightRowPad * kWeightRowPad);
     p.w2 = ff2.w; p.b2 = ff2.bias;
     p.w2_rows = (int)(((long)ff2.cout + kWeightRowPad - 1) / kWeightRowPad * kWeightRowPad);
-    p.ln_stat = x_stat.p; p.ln_parts = x_stat.parts; p.ln_eps = ln_eps;
+    p.ln_stat = x_stat.p; p.ln_parts = x_stat.parts; p.ln_part_w = x_stat.width; p.ln_eps = ln_eps;
     p.M = (int)M; p.C = (int)ff1.K; p.hidden = (int)ff2.K;
     if (c.dry) p.ln_stat = reinterpret_cast<const float*>(8);          // planning pass: only "is set" matters
     if (ff1.ks != 1 || ff2.ks != 1 || ff2.cout != ff1.K || ff1.cout != 2 * ff2.K || x.C != p.C || !ff1.wsum) return false;

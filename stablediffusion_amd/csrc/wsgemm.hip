@@ -192,7 +192,7 @@ __global__ __launch_bounds__(512) void wsgemm_kernel(IGemmParams p, int tiles_m,
 #pragma unroll
             for (int j = 0; j < TN; ++j) { acc[i][j] = f4{0.f, 0.f, 0.f, 0.f}; prev[i][j] = acc[i][j]; }
         float mean[TM] = {0.f, 0.f}, rstd[TM] = {1.f, 1.f};
-        float rsum[TM] = {0.f, 0.f}, rsq[TM] = {0.f, 0.f};
+        float rsum[TM] = {0.f, 0.f}, rsq[TM] = {0.f, 0.f}, rpiv[TM] = {0.f, 0.f};   // row statistics: pivot-shifted sums
         int slot_c = 0;
         h8 fb[TN][2];                                    // W fragments of the step about to run (prefetched by the step before)
 #pragma unroll
@@ -277,18 +277,10 @@ __global__ __launch_bounds__(512) void wsgemm_kernel(IGemmParams p, int tiles_m,
                         for (int i = 0; i < TM; ++i) {
                             const float2* src = reinterpret_cast<const float2*>(sStat + ((t - 1) & 1) * (kWsStatParts * 256)) +
                                                 (wm * 32 + i * 16 + fr) * parts;
-                            float sm = 0.f, sq = 0.f;
+                            float2 pv[kWsStatParts];
 #pragma unroll
-                            for (int k = 0; k < kWsStatParts; ++k) {
-                                const float2 v = src[k < parts ? k : parts - 1];
-                                sm += k < parts ? v.x : 0.f;
-                                sq += k < parts ? v.y : 0.f;
-                            }
-                            const float inv = 1.0f / (float)p.ln_C;
-                            mean[i] = sm * inv;
-                            float var = sq * inv - mean[i] * mean[i];
-                            var = var < 0.f ? 0.f : var;
-                            rstd[i] = rsqrtf(var + p.ln_eps);
+                            for (int k = 0; k < kWsStatParts; ++k) pv[k] = src[k < parts ? k : parts - 1];
+                            ln_row_stats(pv, parts, p.ln_part_w, p.ln_C, p.ln_eps, mean[i], rstd[i]);
                         }
                     }
                     if constexpr (KT < NCH) {
@@ -324,17 +316,26 @@ __global__ __launch_bounds__(512) void wsgemm_kernel(IGemmParams p, int tiles_m,
                                     for (int e = 0; e < 4; ++e) o[e] = (half_t)((float)o[e] + (float)rv[e]);
                                 }
                                 *reinterpret_cast<h4*>(yrow[i] + j * 16) = o;
-                                if constexpr (RS) {
+                                if constexpr (RS) {     // shifted by the lane's first value of the row in this tile
+                                    if constexpr (j == 0) rpiv[i] = (float)o[0];
 #pragma unroll
-                                    for (int e = 0; e < 4; ++e) { const float f = (float)o[e]; rsum[i] += f; rsq[i] += f * f; }
+                                    for (int e = 0; e < 4; ++e) { const float d = (float)o[e] - rpiv[i]; rsum[i] += d; rsq[i] += d * d; }
                                 }
                             }
                             if constexpr (RS && j == NCH - 1) {      // the wave's 80 columns of each row: one partial
 #pragma unroll
                                 for (int i = 0; i < TM; ++i) {
-                                    float sm = rsum[i], sq = rsq[i];
-                                    sm += __shfl_xor(sm, 16); sq += __shfl_xor(sq, 16);
-                                    sm += __shfl_xor(sm, 32); sq += __shfl_xor(sq, 32);
+                                    // the lane's (mean, M2) over its 4 NCH values, then the four lanes' merged pairwise (equal counts)
+                                    const float a = rsum[i] * (1.0f / (4 * NCH));
+                                    float sm = rpiv[i] + a, sq = rsq[i] - rsum[i] * a;
+                                    {
+                                        const float om = __shfl_xor(sm, 16), oq = __shfl_xor(sq, 16), d = om - sm;
+                                        sm += 0.5f * d; sq += oq + d * d * (2.f * NCH);
+                                    }
+                                    {
+                                        const float om = __shfl_xor(sm, 32), oq = __shfl_xor(sq, 32), d = om - sm;
+                                        sm += 0.5f * d; sq += oq + d * d * (4.f * NCH);
+                                    }
                                     if (fq == 0)
                                         *reinterpret_cast<float2*>(p.rowstat_out + (mrow[i] * p.rowstat_parts + tn * 2 + wn) * 2) = float2{sm, sq};
                                     rsum[i] = 0.f; rsq[i] = 0.f;

@@ -228,10 +228,15 @@ def synth_state_dict(manifest, seed: int = 0, dtype=torch.float32, perturb: floa
     profile="heavy_tail": checkpoint-like dynamic range for the fp16 stress tests, since real weights
     cannot be had offline -- 1 % of the output channels of every conv / linear behind a norm are outliers (rows x 30), biases ~ N(0, 0.5), norm gains log-uniform in [0.2, 3] with shifts ~ N(0, 0.5): activations are no longer O(1)
     everywhere (group statistics dominated by single channels, residual streams in the hundreds, saturating softmax rows).
+
+    profile="offset:<v>": the perturb recipe plus a common-mode bias v on every layer whose output a LayerNorm or a
+    GroupNorm reads next (proj_in, attention to_out, resnet conv2), so the residual streams and the norm inputs sit at a
+    mean that is large next to their spread (the norm statistics left by GEMM epilogues must stay centred there).
     """
     g = torch.Generator(device="cpu").manual_seed(seed)
     heavy = profile.startswith("heavy_tail")
-    if profile and not heavy:
+    offset = float(profile.split(":")[1]) if profile.startswith("offset:") else 0.0
+    if profile and not heavy and not profile.startswith("offset:"):
         raise ValueError(f"unknown weight profile {profile!r}")
     outlier = float(profile.split(":")[1]) if ":" in profile else 30.0        # "heavy_tail:<row scale>"
     sd: Dict[str, torch.Tensor] = {}
@@ -261,6 +266,8 @@ def synth_state_dict(manifest, seed: int = 0, dtype=torch.float32, perturb: floa
             if heavy and shape[0] >= 100 and not any(t_ in key for t_ in ("conv_shortcut", "upsamplers", "downsamplers")):
                 rows = torch.randperm(shape[0], generator=g)[: max(1, shape[0] // 100)]
                 t[rows] *= outlier
+        if offset and len(shape) == 1 and key.endswith((".proj_in.bias", ".to_out.0.bias", ".conv2.bias")):
+            t = t + offset
         sd[key] = t.to(dtype)
     return sd
 

@@ -334,6 +334,36 @@ def oracle_unet_fp16_on_gpu(cfg, sd16, x, t, ehs):
         unet_ref.timestep_sinusoid = orig
 
 
+def test_sd15_unet_and_vae_with_offset_norm_inputs_at_benchmark_size(engine_lib):
+    """weights.synth_state_dict(profile="offset:20"): a common-mode bias of 20 behind every proj_in / to_out / resnet
+    conv2, so the rows and groups the folded LayerNorms and the conv-epilogue GroupNorm summaries see have means far
+    above their spread.  Full-width SD1.5 UNet (C2 shapes) and VAE decode against the fp32 oracle on the GPU."""
+    cfg = config.sd15_unet()
+    sd = weights.synth_state_dict(weights.unet_manifest(cfg), seed=53, dtype=torch.float16, perturb=0.1, profile="offset:20")
+    net = HipUNet2DConditionModel(cfg).load_state_dict(sd)
+    g = torch.Generator().manual_seed(13)
+    x = torch.randn(8, 4, 64, 64, generator=g).half()
+    ehs = torch.randn(8, 77, 768, generator=g).half()
+    got = net(x.cuda(), torch.tensor(501.0), ehs.cuda())[0]
+    ref = oracle_unet_on_gpu(cfg, sd, x, torch.tensor(501.0), ehs)
+    assert torch.isfinite(got.float()).all()
+    err = rel_l2(got, ref)
+    print(f"    UNet rel-L2 vs the fp32 oracle: {err:.2e} (tolerance {TOL:.0e})")
+    assert err < TOL
+    del net
+    vcfg = config.sd15_vae()
+    vsd = weights.synth_state_dict(weights.vae_manifest(vcfg), seed=54, dtype=torch.float16, perturb=0.1, profile="offset:20")
+    vae = HipAutoencoderKL(vcfg).load_state_dict(vsd)
+    z = torch.randn(4, 4, 64, 64, generator=torch.Generator().manual_seed(8)).half()
+    img = vae.decode(z.cuda())[0]
+    with torch.no_grad():
+        vref = vae_ref.vae_decode(vcfg, {k: v.float().cuda() for k, v in vsd.items()}, z.float().cuda())
+    assert torch.isfinite(img.float()).all()
+    verr = rel_l2(img, vref)
+    print(f"    VAE decode rel-L2 vs the fp32 oracle: {verr:.2e} (tolerance {TOL:.0e})")
+    assert verr < TOL
+
+
 @pytest.mark.parametrize("row_scale,in_scale", [(8.0, 2.0), (16.0, 4.0)])
 def test_sd15_unet_heavy_tailed_weights_at_benchmark_size(engine_lib, row_scale, in_scale):
     cfg = config.sd15_unet()

@@ -232,6 +232,19 @@ CONV_GN_CASES = [
 def test_conv_groupnorm_statistics_from_the_conv_epilogue(engine_lib, case):
     """conv -> GroupNorm(+SiLU) with the GroupNorm summaries written by the convolution's epilogue
     (IGemmParams::gnstat_out) against conv2d + group_norm in fp32; also checks which path ran."""
+    _conv_groupnorm_case(engine_lib, case, None)
+
+
+@pytest.mark.parametrize("case", CONV_GN_CASES)
+def test_conv_groupnorm_statistics_at_a_large_offset(engine_lib, case):
+    """The same at outputs 50 +- 0.1 (biases near 50, weights and residual scaled to a spread of about 0.1), where
+    summaries from plain sums and sums of squares lose the variance.  Output-channel group 1 has zero weights, one common
+    bias and no residual: a constant group, whose M2 must come out exactly 0 (not negative), so its GroupNorm returns
+    silu(beta) to fp16 rounding."""
+    _conv_groupnorm_case(engine_lib, case, 50.0)
+
+
+def _conv_groupnorm_case(engine_lib, case, offset):
     N, H, W, Cin, Cout, k, stride, up, with_res, expect = case
     g = torch.Generator().manual_seed(hash(case) % 2**31)
     x = torch.randn(N, Cin, H, W, generator=g).half()
@@ -239,9 +252,18 @@ def test_conv_groupnorm_statistics_from_the_conv_epilogue(engine_lib, case):
     bias = torch.randn(Cout, generator=g) * 0.5 + 0.3
     gamma = 1 + 0.2 * torch.randn(Cout, generator=g)
     beta = 0.2 * torch.randn(Cout, generator=g)
+    const = slice(Cout // 32, 2 * Cout // 32)           # output-channel group 1
+    if offset is not None:
+        w = (0.1 * w.float()).half()
+        w[const] = 0
+        bias = offset + 0.05 * torch.randn(Cout, generator=g)
+        bias[const] = offset
     xin = F.interpolate(x.float(), scale_factor=2.0, mode="nearest") if up else x.float()
     conv = F.conv2d(xin, w.float(), bias, stride=stride, padding=1 if k == 3 else 0)
     res = torch.randn(conv.shape, generator=g).half() if with_res else None
+    if res is not None and offset is not None:
+        res = (0.07 * res.float()).half()
+        res[:, const] = 0
     conv = conv.half().float()
     if res is not None:
         conv = (conv + res.float()).half().float()
@@ -261,7 +283,18 @@ def test_conv_groupnorm_statistics_from_the_conv_epilogue(engine_lib, case):
     if expect is not None:
         assert fused.value == expect
     assert rel_l2(yc.permute(0, 3, 1, 2), conv) < 2e-3
+    if offset is not None:
+        # at 50 +- 0.1 one fp16 step of the conv output is a third of the spread: the GroupNorm is checked on the
+        # engine's own stored conv output, so only the summaries and the apply pass are measured
+        # (float64 on a contiguous copy: torch's channels-last CPU group_norm loses the variance here itself)
+        yc64 = yc.permute(0, 3, 1, 2).double().cpu().contiguous()
+        ref = F.silu(F.group_norm(yc64, 32, gamma.double(), beta.double(), 1e-5)).float()
     assert rel_l2(yg.permute(0, 3, 1, 2), ref) < 3e-3
+    if offset is not None:
+        assert torch.isfinite(yg.float()).all()
+        ygc = yg.permute(0, 3, 1, 2)[:, const].float().cpu()
+        want = F.silu(beta[const]).view(1, -1, 1, 1).expand_as(ygc)
+        assert torch.allclose(ygc, want, rtol=2e-3, atol=1e-3), (ygc - want).abs().max().item()
 
 
 @pytest.mark.parametrize("rows,C", [(300, 320), (1000, 640), (77, 1280), (5, 64)])
@@ -561,6 +594,14 @@ def test_groupnorm_conv2d(engine_lib, case):
     assert rel_l2(out[:, :, ring], ref[:, :, ring]) < 4e-3
 
 
+@pytest.mark.parametrize("case", GN_CONV_CASES)
+@pytest.mark.parametrize("offset", [50.0, -30.0])
+def test_groupnorm_conv2d_at_a_large_offset(engine_lib, case, offset):
+    """The same with every case's input at offset +- 0.1 (plus 0.3-scale per-channel shifts): the (mean, M2) summaries
+    the halo consumer merges must keep the variance."""
+    test_groupnorm_conv2d(engine_lib, case[:8] + (0.1, offset))
+
+
 @pytest.mark.parametrize("M,C,scale", [(8192, 320, 1.0), (32768, 320, 1.0), (8320, 320, 3.0), (4096, 640, 1.0)])
 def test_ffn_geglu_fused(engine_lib, M, C, scale):
     """x + GEGLU(LN(x) W1 + b1) W2 + b2 against LayerNorm -> Linear -> chunk -> h * gelu(g) -> Linear -> + x in fp32.
@@ -600,12 +641,24 @@ def test_ffn_geglu_fused(engine_lib, M, C, scale):
 def test_unet_conv_in_one_launch(engine_lib, N, Cin, H, W):
     """conv_head_kernel: conv_in straight from the NCHW latents (im2col tile in LDS), output NHWC, plus the GroupNorm
     summaries (mean, M2) of every 128-pixel tile x group of the STORED fp16 output."""
-    import ctypes
+    _conv_in_case(engine_lib, N, Cin, H, W, None)
+
+
+@pytest.mark.parametrize("N,Cin,H,W", [(8, 4, 64, 64), (2, 7, 16, 24)])
+def test_unet_conv_in_one_launch_at_a_large_offset(engine_lib, N, Cin, H, W):
+    """The same with outputs 50 +- 0.1 (biases near 50, weights scaled by 0.1): summaries checked against float64."""
+    _conv_in_case(engine_lib, N, Cin, H, W, 50.0)
+
+
+def _conv_in_case(engine_lib, N, Cin, H, W, offset):
     Cout, G = 320, 32
     g = torch.Generator().manual_seed(N * H + Cin)
     x = torch.randn(N, Cin, H, W, generator=g).half()
     w = (torch.randn(Cout, Cin, 3, 3, generator=g) / (9 * Cin) ** 0.5).half()
     b = torch.randn(Cout, generator=g) * 0.3
+    if offset is not None:
+        w = (0.1 * w.float()).half()
+        b = offset + 0.05 * torch.randn(Cout, generator=g)
     ref = F.conv2d(x.float(), w.float(), b, padding=1)
     y = torch.zeros(N, H, W, Cout, dtype=torch.float16, device="cuda")
     S = H * W // 128
@@ -621,11 +674,13 @@ def test_unet_conv_in_one_launch(engine_lib, N, Cin, H, W):
     assert rel_l2(out[:, :, ring], ref[:, :, ring]) < 1e-3
     # summaries of the stored values, tile = 128 consecutive pixels of one image
     t = y.float().cpu().reshape(N, S, 128, G, Cout // G)
+    if offset is not None:
+        t = t.double()
     mean = t.mean(dim=(2, 4))
     m2 = ((t - mean[:, :, None, :, None]) ** 2).sum(dim=(2, 4))
     got = summ.cpu()
-    assert torch.allclose(got[..., 0], mean, atol=2e-5, rtol=1e-4)
-    assert torch.allclose(got[..., 1], m2, atol=1e-3, rtol=1e-4)
+    assert torch.allclose(got[..., 0], mean.float(), atol=2e-5, rtol=1e-4)
+    assert torch.allclose(got[..., 1], m2.float(), atol=1e-3, rtol=1e-4)
 
 
 def test_unet_conv_in_refuses_other_shapes(engine_lib):
@@ -641,14 +696,27 @@ def test_unet_conv_in_refuses_other_shapes(engine_lib):
 def test_unet_conv_out_one_launch(engine_lib, N, H, W, Cout, silu):
     """conv_tail_kernel: GroupNorm + SiLU + 3x3 convolution to <= 4 channels + NCHW in one launch against
     group_norm -> silu -> conv2d in fp32 (the normalised activations are rounded to fp16 once, as the separate kernels do)."""
+    _conv_out_case(engine_lib, N, H, W, Cout, silu, None)
+
+
+@pytest.mark.parametrize("N,H,W,Cout,silu", [(8, 64, 64, 4, 1), (2, 8, 32, 3, 0)])
+def test_unet_conv_out_one_launch_at_a_large_offset(engine_lib, N, H, W, Cout, silu):
+    """The same on inputs offset +- 0.1 (per-channel shifts of 0.03): the statistics behind the tail must keep the
+    variance; the reference norm runs in float64."""
+    _conv_out_case(engine_lib, N, H, W, Cout, silu, 50.0)
+
+
+def _conv_out_case(engine_lib, N, H, W, Cout, silu, offset):
     C_, G = 320, 32
     g = torch.Generator().manual_seed(N * H + Cout)
     x = (torch.randn(N, C_, H, W, generator=g) * (1 + torch.rand(1, C_, 1, 1, generator=g)) + torch.randn(1, C_, 1, 1, generator=g)).half()
+    if offset is not None:
+        x = (offset + 0.1 * torch.randn(N, C_, H, W, generator=g) + 0.03 * torch.randn(1, C_, 1, 1, generator=g)).half()
     gamma = 1 + 0.2 * torch.randn(C_, generator=g)
     beta = 0.2 * torch.randn(C_, generator=g)
     w = (torch.randn(Cout, C_, 3, 3, generator=g) / (9 * C_) ** 0.5).half()
     b = torch.randn(Cout, generator=g) * 0.3
-    hn = F.group_norm(x.float(), G, gamma, beta, 1e-5)
+    hn = F.group_norm(x.double(), G, gamma.double(), beta.double(), 1e-5).float()
     if silu:
         hn = F.silu(hn)
     ref = F.conv2d(hn, w.float(), b, padding=1)
