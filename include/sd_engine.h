@@ -91,6 +91,7 @@ typedef struct sd_clip_config {
 typedef struct sd_unet sd_unet;
 typedef struct sd_vae sd_vae;
 typedef struct sd_clip sd_clip;
+typedef struct sd_ip_adapter sd_ip_adapter;
 
 /* -- library ------------------------------------------------------------------------------- */
 const char* sd_last_error(void);
@@ -134,8 +135,41 @@ int sd_unet_use_graph(sd_unet* u, int enable);
  * them.  Every call of this function -- with 1 or 0 -- invalidates what is cached: call it (again) whenever
  * the CONTENTS behind the pointer may have changed, i.e. at the start of each pipeline call.  Off by default. */
 int sd_unet_text_kv_cache(sd_unet* u, int enable);
+/* sd_unet_forward with IP-Adapter image prompts (sd_unified_pipeline.py:441-449, diffusers 0.27.2
+ * added_cond_kwargs["image_embeds"]):
+ *   image_embeds [B,n_img,D_img] f16 or NULL   image encoder embeddings, one row per image (CFG: negative half first)
+ * With an adapter attached (sd_unet_set_ip_adapter) image_embeds is required and every cross-attention computes
+ *   SDPA(q, K_text, V_text) + scale * SDPA(q, K_ip, V_ip)
+ * in one launch per site; n_img * num_tokens <= 64 and ehs_len <= 160, graph replay (sd_unet_use_graph) is
+ * rejected (SD_ERR_UNSUPPORTED).  The image K / V follow sd_unet_text_kv_cache: kept across the forwards of one loop
+ * for one (pointer, B, n_img), invalidated by every sd_unet_text_kv_cache call.  Without an adapter, image_embeds
+ * must be NULL and the call is sd_unet_forward. */
+int sd_unet_forward_ex(sd_unet* u, const void* sample, const float* timesteps, const void* ehs, int ehs_len,
+                       const void* add_text, const float* add_time_ids, const void* image_embeds, int n_img, void* out,
+                       int B, int H, int W, void* stream);
+/* Attach an IP-Adapter created for this UNet's configuration (NULL detaches: the forward is again exactly the plain
+ * one).  One adapter per UNet; attaching it to another UNet detaches it from the first.  The scale (lambda of
+ * set_ip_adapter_scale, default 1.0) belongs to the UNet; 0 computes the text attention alone. */
+int sd_unet_set_ip_adapter(sd_unet* u, sd_ip_adapter* adapter);
+int sd_unet_set_ip_adapter_scale(sd_unet* u, float scale);
 /* Bytes of device memory held (packed weights, workspace). */
 int sd_unet_memory(const sd_unet* u, int64_t* weight_bytes, int64_t* workspace_bytes);
+
+/* -- IP-Adapter: the `encoder_hid_proj` ImageProjection and every attn2's to_k_ip / to_v_ip that diffusers'
+ *    load_ip_adapter adds to the UNet (sd_unified_pipeline.py:441-449).  Weight names are diffusers' post-load keys:
+ *      encoder_hid_proj.image_projection_layers.0.{image_embeds,norm}.{weight,bias}
+ *      <down / up / mid transformer block>.attn2.processor.to_{k,v}_ip.0.weight   [C, cross_attention_dim]
+ *    (stablediffusion_amd/ip_adapter.py converts the original files).  image_embed_dim: 1024 (ViT-H/14), 1280
+ *    (ViT-bigG), any positive multiple of 64; num_tokens in [1, 16] (4 for the base adapters).  SD_ERR_UNSUPPORTED:
+ *    cross_attention_dim % 64 != 0, num_tokens out of range, a head dim outside {32, 40, 64, 80, 160}.  Destroying an
+ *    attached adapter detaches it first: the UNet's next forward is the plain one (and rejects image_embeds). ------ */
+int sd_ip_adapter_create(const sd_unet* u, int image_embed_dim, int num_tokens, sd_ip_adapter** out);
+int sd_ip_adapter_destroy(sd_ip_adapter* a);
+int sd_ip_adapter_num_weights(const sd_ip_adapter* a);
+int sd_ip_adapter_weight_info(const sd_ip_adapter* a, int index, const char** key, int64_t* shape4, int* ndim);
+int sd_ip_adapter_set_weight(sd_ip_adapter* a, const char* key, const void* data, const int64_t* shape, int ndim,
+                             int dtype);
+int sd_ip_adapter_finalize(sd_ip_adapter* a);
 
 /* -- VAE: replaces the object in SDModelWrapper.vae (stable_diffusion.py:110-116) ------------ */
 int sd_vae_create(const sd_vae_config* cfg, sd_vae** out);
@@ -360,6 +394,17 @@ int sd_op_attention(const void* q, const void* k, const void* v, void* out, int 
 int sd_op_attention_ex(const void* q, const void* k, const void* v, void* out, int B, int Tq, int Tk,
                        int heads, int d, int ldq, int ldk, int ldv, int ldo, int causal, int prescaled,
                        void* stream);
+/* IP-Adapter's decoupled cross-attention (diffusers IPAdapterAttnProcessor2_0 at every attn2), one launch:
+ *   out = softmax(s q k^T) v + ip_scale * softmax(s q k_ip^T) v_ip,   s = 1/sqrt(d), or 1 with prescaled = 1
+ * q [B,Tq,heads*d], k / v [B,L,heads*d], k_ip / v_ip [B,T_ip,heads*d], out like q, each with its own row stride
+ * (multiples of 8).  d in {32, 40, 64, 80, 160}, 1 <= L <= 160, 1 <= T_ip <= 64 (SD_ERR_UNSUPPORTED otherwise);
+ * ip_scale = 0 gives the text attention alone.  iters > 0 (timing; synchronises): ms_per_launch[0..2] = the fused
+ * kernel, the text-only attention launch of sd_op_attention_ex on the same operands, and the unfused composition
+ * (text attention + image attention + add), `iters` back-to-back launches each between HIP events. */
+int sd_op_ip_cross_attention(const void* q, const void* k, const void* v, const void* k_ip, const void* v_ip, void* out,
+                             int B, int Tq, int L, int T_ip, int heads, int d, int ldq, int ldk, int ldv, int ldk_ip,
+                             int ldv_ip, int ldo, float ip_scale, int prescaled, int iters, float* ms_per_launch,
+                             void* stream);
 
 #ifdef __cplusplus
 }

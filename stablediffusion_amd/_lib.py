@@ -88,6 +88,15 @@ SIGNATURES = {
     "sd_unet_use_graph": (_I, [_P, _I]),
     "sd_unet_text_kv_cache": (_I, [_P, _I]),
     "sd_unet_memory": (_I, [_P, C.POINTER(_I64), C.POINTER(_I64)]),
+    "sd_unet_forward_ex": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _I, _P, _I, _I, _I, _P]),
+    "sd_unet_set_ip_adapter": (_I, [_P, _P]),
+    "sd_unet_set_ip_adapter_scale": (_I, [_P, _F]),
+    "sd_ip_adapter_create": (_I, [_P, _I, _I, C.POINTER(_P)]),
+    "sd_ip_adapter_destroy": (_I, [_P]),
+    "sd_ip_adapter_num_weights": (_I, [_P]),
+    "sd_ip_adapter_weight_info": (_I, [_P, _I, C.POINTER(C.c_char_p), C.POINTER(_I64), C.POINTER(_I)]),
+    "sd_ip_adapter_set_weight": (_I, [_P, C.c_char_p, _P, C.POINTER(_I64), _I, _I]),
+    "sd_ip_adapter_finalize": (_I, [_P]),
     "sd_vae_create": (_I, [C.POINTER(SdVAEConfig), C.POINTER(_P)]),
     "sd_vae_destroy": (_I, [_P]),
     "sd_vae_num_weights": (_I, [_P]),
@@ -139,6 +148,8 @@ SIGNATURES = {
     "sd_op_small_linear": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "sd_op_layernorm": (_I, [_P, _P, _P, _P, _I, _I, _F, _P]),
     "sd_op_attention": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "sd_op_ip_cross_attention": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _I, _I,
+                                      C.POINTER(_F), _P]),
 }
 
 _lib = None

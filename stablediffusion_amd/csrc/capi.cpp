@@ -11,6 +11,11 @@ using namespace sd;
 struct sd_unet { UNet impl; explicit sd_unet(const sd_unet_config& c) : impl(c) {} };
 struct sd_vae { VAE impl; explicit sd_vae(const sd_vae_config& c) : impl(c) {} };
 struct sd_clip { CLIP impl; explicit sd_clip(const sd_clip_config& c) : impl(c) {} };
+struct sd_ip_adapter {
+    IPAdapter impl;
+    sd_ip_adapter(const sd_unet_config& c, int d, int n) : impl(c, d, n) {}
+    ~sd_ip_adapter() { if (impl.attached) impl.attached->set_ip_adapter(nullptr); }
+};
 
 namespace {
 
@@ -40,6 +45,23 @@ bool bad_cfg(const sd_unet_config* c) {
         if ((ad & 1) || pin % 64 != 0 || pin - 6 * ad <= 0) return true;
     }
     return c->cross_attention_dim % 64 != 0 || c->in_channels <= 0 || c->in_channels > 16;
+}
+
+// field by field (no padding bytes compared): the configuration an IP-Adapter was created for
+bool same_topology(const sd_unet_config& a, const sd_unet_config& b) {
+    if (a.in_channels != b.in_channels || a.out_channels != b.out_channels || a.num_blocks != b.num_blocks ||
+        a.layers_per_block != b.layers_per_block || a.cross_attention_dim != b.cross_attention_dim ||
+        a.use_linear_projection != b.use_linear_projection || a.norm_num_groups != b.norm_num_groups ||
+        a.norm_eps != b.norm_eps || a.flip_sin_to_cos != b.flip_sin_to_cos || a.freq_shift != b.freq_shift ||
+        a.addition_time_embed_dim != b.addition_time_embed_dim ||
+        a.projection_class_embeddings_input_dim != b.projection_class_embeddings_input_dim)
+        return false;
+    for (int i = 0; i < SD_MAX_BLOCKS; ++i)
+        if (a.block_out_channels[i] != b.block_out_channels[i] || a.down_block_has_attn[i] != b.down_block_has_attn[i] ||
+            a.up_block_has_attn[i] != b.up_block_has_attn[i] || a.num_heads[i] != b.num_heads[i] ||
+            a.transformer_layers[i] != b.transformer_layers[i])
+            return false;
+    return true;
 }
 
 }  // namespace
@@ -95,7 +117,75 @@ int sd_unet_text_kv_cache(sd_unet* u, int enable) {
     if (!u) { set_error("null handle"); return SD_ERR_INVALID; }
     u->impl.kv_cache_on = enable != 0;
     u->impl.kv_valid = false;           // every call invalidates: the next forward recomputes
+    u->impl.ipkv_valid = false;         // (the IP-Adapter's image K / V alike)
     return SD_OK;
+}
+int sd_unet_forward_ex(sd_unet* u, const void* sample, const float* timesteps, const void* ehs, int ehs_len,
+                       const void* add_text, const float* add_time_ids, const void* image_embeds, int n_img, void* out,
+                       int B, int H, int W, void* stream) {
+    if (!u || !sample || !timesteps || !ehs || !out) { set_error("null argument"); return SD_ERR_INVALID; }
+    return u->impl.forward(static_cast<const half_t*>(sample), timesteps, static_cast<const half_t*>(ehs),
+                           ehs_len, static_cast<const half_t*>(add_text), add_time_ids,
+                           static_cast<half_t*>(out), B, H, W, static_cast<hipStream_t>(stream),
+                           static_cast<const half_t*>(image_embeds), image_embeds ? n_img : 0);
+}
+int sd_unet_set_ip_adapter(sd_unet* u, sd_ip_adapter* a) {
+    if (!u) { set_error("null handle"); return SD_ERR_INVALID; }
+    if (a) {
+        if (!a->impl.finalized) { set_error("sd_unet_set_ip_adapter: adapter not finalized"); return SD_ERR_STATE; }
+        if (!same_topology(a->impl.cfg, u->impl.cfg)) {
+            set_error("sd_unet_set_ip_adapter: the adapter was created for another UNet configuration");
+            return SD_ERR_INVALID;
+        }
+    }
+    u->impl.set_ip_adapter(a ? &a->impl : nullptr);
+    return SD_OK;
+}
+int sd_unet_set_ip_adapter_scale(sd_unet* u, float scale) {
+    if (!u) { set_error("null handle"); return SD_ERR_INVALID; }
+    if (!(scale == scale)) { set_error("sd_unet_set_ip_adapter_scale: NaN"); return SD_ERR_INVALID; }
+    u->impl.ip_scale = scale;
+    return SD_OK;
+}
+
+// ------------------------------------------------------------------------------------- IP-Adapter
+int sd_ip_adapter_create(const sd_unet* u, int image_embed_dim, int num_tokens, sd_ip_adapter** out) {
+    if (!u || !out) { set_error("null argument"); return SD_ERR_INVALID; }
+    const sd_unet_config& c = u->impl.cfg;
+    if (c.cross_attention_dim % 64 != 0) { set_error("sd_ip_adapter_create: cross_attention_dim % 64 != 0"); return SD_ERR_UNSUPPORTED; }
+    if (num_tokens < 1 || num_tokens > 16) { set_error("sd_ip_adapter_create: num_tokens must be in [1, 16]"); return SD_ERR_UNSUPPORTED; }
+    if (image_embed_dim <= 0 || image_embed_dim % 64 != 0) {
+        set_error("sd_ip_adapter_create: image_embed_dim must be a positive multiple of 64");
+        return SD_ERR_UNSUPPORTED;
+    }
+    for (const auto& site : unet_xattn_sites(c, true)) {
+        int heads = 0;
+        for (int i = 0; i < c.num_blocks; ++i)
+            if (c.block_out_channels[i] == site.second) heads = c.num_heads[i];
+        if (heads <= 0 || !ip_attention_supported(site.second / heads)) {
+            set_error("sd_ip_adapter_create: head dim of " + site.first + " not in {32, 40, 64, 80, 160}");
+            return SD_ERR_UNSUPPORTED;
+        }
+    }
+    *out = new (std::nothrow) sd_ip_adapter(c, image_embed_dim, num_tokens);
+    if (!*out) { set_error("out of host memory"); return SD_ERR_INVALID; }
+    return SD_OK;
+}
+int sd_ip_adapter_destroy(sd_ip_adapter* a) { delete a; return SD_OK; }
+int sd_ip_adapter_num_weights(const sd_ip_adapter* a) { return a ? (int)a->impl.ws.order.size() : 0; }
+int sd_ip_adapter_weight_info(const sd_ip_adapter* a, int index, const char** key, int64_t* shape4, int* ndim) {
+    if (!a) { set_error("null handle"); return SD_ERR_INVALID; }
+    return weight_info(a->impl.ws, index, key, shape4, ndim);
+}
+int sd_ip_adapter_set_weight(sd_ip_adapter* a, const char* key, const void* data, const int64_t* shape, int ndim,
+                             int dtype) {
+    if (!a || !key || !data || !shape) { set_error("null argument"); return SD_ERR_INVALID; }
+    if (a->impl.finalized) { set_error("set_weight after finalize"); return SD_ERR_STATE; }
+    return a->impl.ws.set(key, data, shape, ndim, dtype);
+}
+int sd_ip_adapter_finalize(sd_ip_adapter* a) {
+    if (!a) { set_error("null handle"); return SD_ERR_INVALID; }
+    return a->impl.finalize();
 }
 int sd_unet_memory(const sd_unet* u, int64_t* weight_bytes, int64_t* workspace_bytes) {
     if (!u) { set_error("null handle"); return SD_ERR_INVALID; }
@@ -913,6 +1003,59 @@ int sd_op_attention_ex(const void* q, const void* k, const void* v, void* out, i
     return launch_attention(static_cast<const half_t*>(q), static_cast<const half_t*>(k),
                             static_cast<const half_t*>(v), static_cast<half_t*>(out), B, Tq, Tk, heads, d, ldq, ldk,
                             ldv, ldo, static_cast<hipStream_t>(stream), causal, prescaled);
+}
+
+int sd_op_ip_cross_attention(const void* q, const void* k, const void* v, const void* k_ip, const void* v_ip, void* out,
+                             int B, int Tq, int L, int T_ip, int heads, int d, int ldq, int ldk, int ldv, int ldk_ip,
+                             int ldv_ip, int ldo, float ip_scale, int prescaled, int iters, float* ms_per_launch,
+                             void* stream) {
+    const half_t *qh = static_cast<const half_t*>(q), *kh = static_cast<const half_t*>(k), *vh = static_cast<const half_t*>(v);
+    const half_t *kih = static_cast<const half_t*>(k_ip), *vih = static_cast<const half_t*>(v_ip);
+    half_t* oh = static_cast<half_t*>(out);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    auto fused = [&]() {
+        return launch_ip_attention(qh, kh, vh, kih, vih, oh, B, Tq, L, T_ip, heads, d, ldq, ldk, ldv, ldk_ip, ldv_ip, ldo,
+                                   ip_scale, prescaled, s);
+    };
+    int rc = fused();
+    if (rc || iters <= 0) return rc;
+    if (!ms_per_launch) { set_error("sd_op_ip_cross_attention: ms_per_launch required with iters > 0"); return SD_ERR_INVALID; }
+    if (!attention_supported(d)) { set_error("sd_op_ip_cross_attention: timing needs a head dim of the text kernel"); return SD_ERR_UNSUPPORTED; }
+    // [0] the fused kernel, [1] the text-only cross-attention launch on the same operands, [2] the unfused
+    // composition: text attention, image attention into a scratch tensor, out += ip_scale * scratch
+    half_t* tmp = nullptr;
+    SD_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&tmp), (size_t)B * Tq * heads * d * sizeof(half_t)));
+    const long ldt = (long)heads * d;
+    auto text = [&]() {
+        return launch_attention(qh, kh, vh, oh, B, Tq, L, heads, d, ldq, ldk, ldv, ldo, s, 0, prescaled);
+    };
+    auto unfused = [&]() {
+        int r = text();
+        if (!r) r = launch_attention(qh, kih, vih, tmp, B, Tq, T_ip, heads, d, ldq, ldk_ip, ldv_ip, ldt, s, 0, prescaled);
+        if (!r) r = launch_axpy_f16(oh, ldo, tmp, ldt, (long)B * Tq, heads * d, ip_scale, s);
+        return r;
+    };
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) rc = SD_ERR_HIP;
+    for (int variant = 0; variant < 3 && !rc; ++variant) {
+        auto one = [&]() { return variant == 0 ? fused() : variant == 1 ? text() : unfused(); };
+        for (int it = 0; it < 2 && !rc; ++it) rc = one();
+        if (rc) break;
+        (void)hipEventRecord(e0, s);
+        for (int it = 0; it < iters && !rc; ++it) rc = one();
+        (void)hipEventRecord(e1, s);
+        float ms = 0.f;
+        hipError_t e = hipEventSynchronize(e1);
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
+        if (e != hipSuccess) { set_error(hipGetErrorString(e)); rc = SD_ERR_HIP; }
+        ms_per_launch[variant] = ms / (float)iters;
+    }
+    if (!rc) rc = fused();                  // leave the fused result in out
+    if (!rc && hipStreamSynchronize(s) != hipSuccess) rc = SD_ERR_HIP;
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    (void)hipFree(tmp);
+    return rc;
 }
 
 }  // extern "C"

@@ -137,6 +137,11 @@ struct Ctx {
     GnStatBuf gnpool[kGnPool];
     int gn_next = 0;
     int gn_groups = 0;
+    // IP-Adapter image K / V of this forward ([B T_ip, sum 2C], TBlock::ip_kv_off) when an adapter is attached:
+    // run_xformer then issues the fused decoupled cross-attention instead of the text-only one
+    View ip_kv;
+    int ip_T = 0;
+    float ip_scale = 1.f;
 };
 void ctx_gnpool_init(Ctx& c, int N, long HW_max, int G);
 GnStatBuf* ctx_gnbuf(Ctx& c);       // next ring slot with `st` cleared; nullptr when the pool is not set up
@@ -172,5 +177,8 @@ void op_layernorm(Ctx& c, const NormW& n, View x, View y, long rows, float eps);
 bool op_ffn_fused(Ctx& c, const ConvW& ff1, const ConvW& ff2, View x, const RowStat& x_stat, float ln_eps, long M, View y);
 void op_attention(Ctx& c, View q, View k, View v, View out, int B, int Tq, int Tk, int heads, int d, int causal = 0,
                   int prescaled = 0);
+// out = softmax(q k^T) v + ip_scale softmax(q k_ip^T) v_ip (prescaled queries, ip_attention.hip)
+void op_ip_attention(Ctx& c, View q, View k, View v, View k_ip, View v_ip, View out, int B, int Tq, int L, int T_ip,
+                     int heads, int d, float ip_scale);
 
 }  // namespace sd

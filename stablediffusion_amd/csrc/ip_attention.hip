@@ -1,0 +1,306 @@
+// Decoupled cross-attention of IP-Adapter for gfx950 (CDNA4, wave64), one launch per attn2 site:
+//   out = softmax(s q K_t^T) V_t + lambda * softmax(s q K_ip^T) V_ip
+// fp16 in/out, fp32 scores and accumulators.  diffusers 0.27.2 IPAdapterAttnProcessor2_0 computes the same
+// thing as two scaled_dot_product_attention calls and an add; here the IP branch costs a few more MFMAs on
+// queries that are already in registers, and the output is written once.
+//
+// Both key sets are short (text L <= 154 -- 77 in practice --, image tokens T_ip <= 64), so unlike the streaming
+// attn_kernel (attention.hip) this kernel:
+//   * stages ALL keys and values of one (batch, head) -- text and image -- into LDS once per block, zero-padded to
+//     multiples of 32 keys, and runs several query tiles against them (the block loops over its share of tiles);
+//   * computes each softmax exactly: max over the whole segment, exp, row sum, no running max and no rescale.  The
+//     probabilities are normalised (times lambda for the image segment) BEFORE they are rounded to fp16 and fed to
+//     the PV product, so both segments accumulate into one set of fp32 output registers and nothing is left to
+//     divide at the end.
+// Shared with attention.hip: the swapped products S^T = K Q^T (a query's scores sit in one lane column, so the
+// softmax needs two cross-lane reductions and nothing else), P^T taken straight from the S^T accumulators as the B
+// operand of O^T = V^T P^T, V^T read with ds_read_b64_tr_b16 from row-major V, odd-multiple-of-32-byte LDS row
+// strides (conflict-free fragment and transposed reads), 16x16x32 MFMAs.  The ones-column denominator is not used:
+// the exact softmax has its sum before the PV product.
+// lambda == 0 skips the image segment (wave-uniform branch): the result is the text attention alone.
+#include "kernels.h"
+
+namespace sd {
+namespace {
+
+constexpr int ip_odd32_bytes(int bytes) { return ((((bytes + 31) / 32) | 1)) * 32; }
+constexpr int ip_kstr(int D) { return ip_odd32_bytes((D + 31) / 32 * 32 * 2) / 2; }   // halves
+constexpr int ip_vstr(int D) { return ip_odd32_bytes((D + 15) / 16 * 16 * 2) / 2; }   // halves
+constexpr int kMaxTextSteps = 5;      // 32-key PV steps: L <= 160
+constexpr int kMaxIpSteps = 2;        // T_ip <= 64
+
+__device__ __forceinline__ unsigned pack_rte(float a, float b) {
+    h2 v = {(half_t)a, (half_t)b};
+    return __builtin_bit_cast(unsigned, v);
+}
+
+// Stage rows [0, n) of a [rows, D] head slice (row stride ld) into LDS rows of `str` halves, zero beyond n / D.
+template <int D>
+__device__ __forceinline__ void stage_rows(half_t* dst, int str, const half_t* src, long ld, int n, int rows, int tid,
+                                           int nth) {
+    const int cpr = str / 8;
+    for (int idx = tid; idx < rows * cpr; idx += nth) {
+        const int r = idx / cpr, c = (idx - r * cpr) * 8;
+        h8 val = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (r < n && c < D) val = *reinterpret_cast<const h8*>(src + (long)r * ld + c);
+        *reinterpret_cast<h8*>(dst + r * str + c) = val;
+    }
+}
+
+// One softmax segment of one wave's 16 * QT queries: o += coef * softmax(scale q K^T) V over keys [0, n).
+// nkk (<= NKK) 32-key steps are staged in cK / cV.
+template <int D, int QT, int NKK>
+__device__ __forceinline__ void ip_segment(const half_t* cK, const half_t* cV, int n, int nkk, float coef,
+                                           float scale_log2e, const h8 (&qf)[QT][(D + 31) / 32],
+                                           f4 (&o)[(D + 15) / 16][QT], int fr, int fq) {
+    constexpr int KS = (D + 31) / 32;
+    constexpr int DT = (D + 15) / 16;
+    constexpr int KSTR = ip_kstr(D), VSTR = ip_vstr(D);
+    constexpr int NSUB = 2 * NKK;
+    const int nsub = 2 * nkk;
+
+    // ---- S^T = K Q^T ----
+    f4 s[NSUB][QT];
+#pragma unroll
+    for (int ksub = 0; ksub < NSUB; ++ksub)
+#pragma unroll
+        for (int t = 0; t < QT; ++t) s[ksub][t] = f4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int ksub = 0; ksub < NSUB; ++ksub) {
+        if (ksub < nsub) {
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) {
+                const h8 kf = *reinterpret_cast<const h8*>(cK + (ksub * 16 + fr) * KSTR + ks * 32 + fq * 8);
+#pragma unroll
+                for (int t = 0; t < QT; ++t)
+                    s[ksub][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf, qf[t][ks], s[ksub][t], 0, 0, 0);
+            }
+        }
+    }
+    // ---- exact softmax per query (= per lane column): keys >= n never win and weigh 0 ----
+    unsigned pf[QT][NKK][4];
+#pragma unroll
+    for (int t = 0; t < QT; ++t) {
+        float m = -INFINITY;
+#pragma unroll
+        for (int ksub = 0; ksub < NSUB; ++ksub) {
+            if (ksub < nsub) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if (ksub * 16 + fq * 4 + j >= n) s[ksub][t][j] = -INFINITY;
+                    m = fmaxf(m, s[ksub][t][j]);
+                }
+            }
+        }
+        m = fmaxf(m, __shfl_xor(m, 16));
+        m = fmaxf(m, __shfl_xor(m, 32));
+        const float nm = -m * scale_log2e;
+        float l = 0.f;
+#pragma unroll
+        for (int ksub = 0; ksub < NSUB; ++ksub) {
+            if (ksub < nsub) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(s[ksub][t][j], scale_log2e, nm));
+                    s[ksub][t][j] = p;
+                    l += p;
+                }
+            }
+        }
+        l += __shfl_xor(l, 16);
+        l += __shfl_xor(l, 32);
+        const float w = coef / l;
+#pragma unroll
+        for (int ksub = 0; ksub < NSUB; ++ksub) {
+            if (ksub < nsub) {
+                pf[t][ksub >> 1][(ksub & 1) * 2] = pack_rte(s[ksub][t][0] * w, s[ksub][t][1] * w);
+                pf[t][ksub >> 1][(ksub & 1) * 2 + 1] = pack_rte(s[ksub][t][2] * w, s[ksub][t][3] * w);
+            }
+        }
+    }
+    // ---- O^T += V^T P^T ----
+#pragma unroll
+    for (int kk = 0; kk < NKK; ++kk) {
+        if (kk < nkk) {
+#pragma unroll
+            for (int i = 0; i < DT; ++i) {
+                const half_t* a0 = cV + (kk * 32 + fq * 4 + (fr >> 2)) * VSTR + i * 16 + (fr & 3) * 4;
+                const s4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4v*)(a0));
+                const s4v hi =
+                    __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4v*)(a0 + 16 * VSTR));
+                union { struct { s4v a, b; } p; h8 v; } u;
+                u.p.a = lo; u.p.b = hi;
+#pragma unroll
+                for (int t = 0; t < QT; ++t) {
+                    union { unsigned w[4]; h8 v; } pb;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) pb.w[e] = pf[t][kk][e];
+                    o[i][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(u.v, pb.v, o[i][t], 0, 0, 0);
+                }
+            }
+        }
+    }
+}
+
+// Grid: B * heads * qblocks blocks, (batch, head) slow, pushed through the XCD remap so that the blocks of one
+// (batch, head) share one L2.  Block: NWV waves x 16 QT queries per tile; the block walks the query tiles
+// qblk, qblk + qblocks, ... against the K / V it staged once.
+template <int D, int QT, int NWV>
+__global__ __launch_bounds__(64 * NWV) void ip_xattn_kernel(const half_t* __restrict__ q, const half_t* __restrict__ k,
+                                                        const half_t* __restrict__ v, const half_t* __restrict__ kip,
+                                                        const half_t* __restrict__ vip, half_t* __restrict__ out,
+                                                        int Tq, int L, int Tip, int heads, long ldq, long ldk, long ldv,
+                                                        long ldki, long ldvi, long ldo, float scale_log2e, float lam,
+                                                        int qblocks) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    constexpr int KS = (D + 31) / 32;
+    constexpr int DT = (D + 15) / 16;
+    constexpr int KSTR = ip_kstr(D), VSTR = ip_vstr(D);
+    constexpr int QB = 16 * QT * NWV;
+    constexpr int NTH = 64 * NWV;
+    const int nkt = (L + 31) / 32, nki = (Tip + 31) / 32;
+    const int rows_t = nkt * 32, rows_i = nki * 32;
+
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    half_t* sKt = reinterpret_cast<half_t*>(smem);
+    half_t* sVt = sKt + rows_t * KSTR;
+    half_t* sKi = sVt + rows_t * VSTR;
+    half_t* sVi = sKi + rows_i * KSTR;
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int fr = lane & 15, fq = lane >> 4;
+    const int bid = xcd_remap(blockIdx.x, gridDim.x);
+    const int bh = bid / qblocks, qblk = bid - bh * qblocks;
+    const int b = bh / heads, h = bh - b * heads;
+    const bool with_ip = lam != 0.f;
+
+    stage_rows<D>(sKt, KSTR, k + (long)b * L * ldk + h * D, ldk, L, rows_t, tid, NTH);
+    stage_rows<D>(sVt, VSTR, v + (long)b * L * ldv + h * D, ldv, L, rows_t, tid, NTH);
+    if (with_ip) {
+        stage_rows<D>(sKi, KSTR, kip + (long)b * Tip * ldki + h * D, ldki, Tip, rows_i, tid, NTH);
+        stage_rows<D>(sVi, VSTR, vip + (long)b * Tip * ldvi + h * D, ldvi, Tip, rows_i, tid, NTH);
+    }
+    __syncthreads();
+
+    const half_t* qb = q + (long)b * Tq * ldq + h * D;
+    half_t* ob = out + (long)b * Tq * ldo + h * D;
+    const int qtiles = (Tq + QB - 1) / QB;
+    for (int qt = qblk; qt < qtiles; qt += qblocks) {
+        const int q0 = qt * QB + wave * 16 * QT;
+        if (q0 >= Tq) break;                 // wave-uniform; no barrier below
+        h8 qf[QT][KS];
+#pragma unroll
+        for (int t = 0; t < QT; ++t) {
+            const int qi = q0 + t * 16 + fr;
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) {
+                const int c = ks * 32 + fq * 8;
+                h8 val = {0, 0, 0, 0, 0, 0, 0, 0};
+                if (qi < Tq && c < D) val = *reinterpret_cast<const h8*>(qb + (long)qi * ldq + c);
+                qf[t][ks] = val;
+            }
+        }
+        f4 o[DT][QT];
+#pragma unroll
+        for (int i = 0; i < DT; ++i)
+#pragma unroll
+            for (int t = 0; t < QT; ++t) o[i][t] = f4{0.f, 0.f, 0.f, 0.f};
+        ip_segment<D, QT, kMaxTextSteps>(sKt, sVt, L, nkt, 1.f, scale_log2e, qf, o, fr, fq);
+        if (with_ip) ip_segment<D, QT, kMaxIpSteps>(sKi, sVi, Tip, nki, lam, scale_log2e, qf, o, fr, fq);
+        // lane holds 4 consecutive d of one query
+#pragma unroll
+        for (int t = 0; t < QT; ++t) {
+            const int qi = q0 + t * 16 + fr;
+#pragma unroll
+            for (int i = 0; i < DT; ++i) {
+                const int dd = i * 16 + fq * 4;
+                if (qi < Tq && dd < D) {
+                    const f4 val = o[i][t];
+                    h4 w = {(half_t)val[0], (half_t)val[1], (half_t)val[2], (half_t)val[3]};
+                    *reinterpret_cast<h4*>(ob + (long)qi * ldo + dd) = w;
+                }
+            }
+        }
+    }
+#endif  // __HIP_DEVICE_COMPILE__
+}
+
+template <int D, int QT, int NWV>
+int launch_ip(const half_t* q, const half_t* k, const half_t* v, const half_t* kip, const half_t* vip, half_t* out, int B,
+              int Tq, int L, int Tip, int heads, long ldq, long ldk, long ldv, long ldki, long ldvi, long ldo, float lam,
+              bool prescaled, hipStream_t s) {
+    constexpr int STR = ip_kstr(D) + ip_vstr(D);
+    constexpr size_t lds_max = (size_t)32 * (kMaxTextSteps + kMaxIpSteps) * STR * 2;
+    static_assert(lds_max <= 160 * 1024, "LDS");
+    static PerDeviceOnce attr_once;
+    if (attr_once.first()) {
+        SD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&ip_xattn_kernel<D, QT, NWV>),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
+    }
+    const int rows = 32 * ((L + 31) / 32) + (lam != 0.f ? 32 * ((Tip + 31) / 32) : 0);
+    const size_t lds = (size_t)rows * STR * 2;
+    const float scale_log2e = prescaled ? 1.0f : 1.4426950408889634f / sqrtf((float)D);
+    // enough blocks for about four per CU, each walking several query tiles against the K / V it staged
+    constexpr int QB = 16 * QT * NWV;
+    const int qtiles = cdiv(Tq, QB);
+    const long bh = (long)B * heads;
+    int qblocks = (int)((1024 + bh - 1) / bh);
+    if (qblocks > qtiles) qblocks = qtiles;
+    if (qblocks < 1) qblocks = 1;
+    hipLaunchKernelGGL((ip_xattn_kernel<D, QT, NWV>), dim3((unsigned)(bh * qblocks)), dim3(64 * NWV), lds, s, q, k, v, kip,
+                       vip, out, Tq, L, Tip, heads, ldq, ldk, ldv, ldki, ldvi, ldo, scale_log2e, lam, qblocks);
+    SD_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// y += a x on [rows, cols] fp16 slices (cols % 8 == 0): the add of the unfused composition that
+// tools/run_ip_attn.py times against the fused kernel
+__global__ void axpy_f16_kernel(half_t* __restrict__ y, long ldy, const half_t* __restrict__ x, long ldx, long rows,
+                                int cols, float a) {
+    const int cpr = cols / 8;
+    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= rows * cpr) return;
+    const long r = idx / cpr;
+    const int c = (int)(idx - r * cpr) * 8;
+    const h8 xv = *reinterpret_cast<const h8*>(x + r * ldx + c);
+    h8 yv = *reinterpret_cast<const h8*>(y + r * ldy + c);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) yv[e] = (half_t)((float)yv[e] + a * (float)xv[e]);
+    *reinterpret_cast<h8*>(y + r * ldy + c) = yv;
+}
+
+}  // namespace
+
+int launch_axpy_f16(half_t* y, long ldy, const half_t* x, long ldx, long rows, int cols, float a, hipStream_t s) {
+    if (cols % 8 != 0 || (ldx | ldy) % 8 != 0) { set_error("axpy_f16: cols and strides must be multiples of 8"); return 1; }
+    const long n = rows * (cols / 8);
+    if (n <= 0) return 0;
+    hipLaunchKernelGGL(axpy_f16_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, s, y, ldy, x, ldx, rows, cols, a);
+    SD_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+bool ip_attention_supported(int d) { return d == 32 || d == 40 || d == 64 || d == 80 || d == 160; }
+
+int launch_ip_attention(const half_t* q, const half_t* k, const half_t* v, const half_t* kip, const half_t* vip,
+                        half_t* out, int B, int Tq, int L, int Tip, int heads, int d, long ldq, long ldk, long ldv,
+                        long ldki, long ldvi, long ldo, float ip_scale, int prescaled, hipStream_t s) {
+    if ((ldq | ldk | ldv | ldki | ldvi | ldo) % 8 != 0) { set_error("ip attention: row strides must be multiples of 8"); return 1; }
+    if (B <= 0 || Tq <= 0 || heads <= 0) return 0;
+    if (L < 1 || L > 32 * kMaxTextSteps) { set_error("ip attention: text length must be in [1, 160]"); return 4; }
+    if (Tip < 1 || Tip > 32 * kMaxIpSteps) { set_error("ip attention: image tokens must be in [1, 64]"); return 4; }
+    if (!(ip_scale == ip_scale)) { set_error("ip attention: scale is NaN"); return 1; }
+    const bool ps = prescaled != 0;
+    switch (d) {
+        case 32: return launch_ip<32, 1, 4>(q, k, v, kip, vip, out, B, Tq, L, Tip, heads, ldq, ldk, ldv, ldki, ldvi, ldo, ip_scale, ps, s);
+        case 40: return launch_ip<40, 1, 4>(q, k, v, kip, vip, out, B, Tq, L, Tip, heads, ldq, ldk, ldv, ldki, ldvi, ldo, ip_scale, ps, s);
+        case 64: return launch_ip<64, 1, 4>(q, k, v, kip, vip, out, B, Tq, L, Tip, heads, ldq, ldk, ldv, ldki, ldvi, ldo, ip_scale, ps, s);
+        case 80: return launch_ip<80, 1, 4>(q, k, v, kip, vip, out, B, Tq, L, Tip, heads, ldq, ldk, ldv, ldki, ldvi, ldo, ip_scale, ps, s);
+        case 160: return launch_ip<160, 1, 4>(q, k, v, kip, vip, out, B, Tq, L, Tip, heads, ldq, ldk, ldv, ldki, ldvi, ldo, ip_scale, ps, s);
+        default:
+            set_error("ip attention: unsupported head dim " + std::to_string(d));
+            return 4;
+    }
+}
+
+}  // namespace sd

@@ -170,6 +170,15 @@ int launch_attention(const half_t* q, const half_t* k, const half_t* v, half_t* 
 // prescaled = 1: q already carries log2(e)/sqrt(d) (the UNet folds it into its query projections at
 // pack time, launch_scale_f16), which lets the kernel drop its per-score scale-and-subtract FMA.
 bool attention_supported(int d);
+// IP-Adapter decoupled cross-attention (ip_attention.hip), one launch:
+//   out = softmax(s q k^T) v + ip_scale * softmax(s q k_ip^T) v_ip,   s = 1/sqrt(d) (or 1 with prescaled)
+// q [B,Tq,heads*d], k / v [B,L,..], k_ip / v_ip [B,Tip,..] with their own row strides; 1 <= L <= 160,
+// 1 <= Tip <= 64; ip_scale = 0 skips the image keys.  Returns 4 for unsupported shapes / head dims.
+int launch_ip_attention(const half_t* q, const half_t* k, const half_t* v, const half_t* kip, const half_t* vip,
+                        half_t* out, int B, int Tq, int L, int Tip, int heads, int d, long ldq, long ldk, long ldv,
+                        long ldki, long ldvi, long ldo, float ip_scale, int prescaled, hipStream_t s);
+bool ip_attention_supported(int d);
+int launch_axpy_f16(half_t* y, long ldy, const half_t* x, long ldx, long rows, int cols, float a, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------
 // Small / elementwise kernels (misc.hip)

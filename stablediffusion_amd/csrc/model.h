@@ -18,6 +18,7 @@ struct TBlock {
     NormW ln1, ln2, ln3;
     ConvW qkv, out1, q2, out2, ff1, ff2;
     int kv_off = 0;     // column offset of this block's [K | V] text projection in UNet::kv_all
+    int ip_kv_off = 0;  // column offset of its [K_ip | V_ip] image projection in IPAdapter::kv_all (same site order)
     bool fold = false;  // ln1 / ln2 / ln3 are folded into qkv / q2 / ff1 (no LayerNorm launches)
 };
 struct Xformer {
@@ -48,12 +49,37 @@ void run_xformer(Ctx& c, const Xformer& t, View x, int N, int H, int W, View out
                  const GnStatBuf* x_stats = nullptr, GnStatBuf** out_stats = nullptr, GnStatBuf* out_buf = nullptr,
                  int out_groups = 0);
 
+struct UNet;
+
+// Every attn2 of a UNet topology as (transformer block prefix, channels): diffusers' attn_processors order
+// (down, up, mid) with mid_last, the engine's kv_all order (down, mid, up) without.
+std::vector<std::pair<std::string, int>> unet_xattn_sites(const sd_unet_config& cfg, bool mid_last);
+
+// IP-Adapter image prompt bound to a UNet topology (diffusers 0.27.2 ImageProjection + IPAdapterAttnProcessor2_0):
+// tokens = LayerNorm(reshape(image_embeds x W_proj^T + b, [n_tok, ctx])), then at every attn2
+// o = SDPA(q, K_text, V_text) + scale * SDPA(q, tokens W_k_ip^T, tokens W_v_ip^T).
+struct IPAdapter {
+    IPAdapter(const sd_unet_config& c, int image_embed_dim, int num_tokens);
+    int finalize();
+
+    sd_unet_config cfg;
+    int d_img = 0, n_tok = 0;
+    WeightStore ws;
+    bool finalized = false;
+    ConvW proj;                         // image_embeds linear [n_tok ctx][d_img]
+    NormW norm;                         // LayerNorm over ctx, eps 1e-5
+    ConvW kv_all;                       // every to_k_ip / to_v_ip, row-concatenated in UNet::kv_all's site order
+    int kv_total = 0;
+    UNet* attached = nullptr;           // the UNet it is attached to (sd_unet_set_ip_adapter), if any
+};
+
 struct UNet {
     explicit UNet(const sd_unet_config& c);
     int finalize();
     int forward(const half_t* sample, const float* timesteps, const half_t* ehs, int L,
                 const half_t* add_text, const float* add_time_ids, half_t* out, int B, int H, int W,
-                hipStream_t stream);
+                hipStream_t stream, const half_t* image_embeds = nullptr, int n_img = 0);
+    void set_ip_adapter(IPAdapter* a);
 
     sd_unet_config cfg;
     WeightStore ws;
@@ -87,6 +113,17 @@ struct UNet {
     const half_t* kv_src = nullptr;
     int kv_B = 0, kv_L = 0;
 
+    // ---- IP-Adapter (sd_unet_set_ip_adapter): nullptr = plain cross-attention, the forward as without the feature.
+    // Its stacked K / V of the image tokens follow the text K / V's cache rules: kept across the forwards of one loop
+    // for one (pointer, batch, images per prompt), invalidated by every sd_unet_text_kv_cache call, not under graphs.
+    IPAdapter* ip = nullptr;
+    float ip_scale = 1.f;
+    bool ipkv_valid = false;
+    half_t* ipkv_cache = nullptr;
+    size_t ipkv_cap = 0;
+    const half_t* ipkv_src = nullptr;
+    int ipkv_B = 0, ipkv_n = 0;
+
     ConvW conv_in, conv_out, te1, te2, ae1, ae2, temb_stack;
     ConvW kv_all;                       // every attn2.to_k / to_v of the model, row-concatenated
     std::vector<std::string> kv_keys;   // (finalize only)
@@ -103,7 +140,8 @@ struct UNet {
     int pack_resnet(const std::string& p, Resnet* r, std::vector<std::string>* tw, std::vector<std::string>* tb);
     int pack_xformer(const std::string& p, Xformer* x, int heads, int depth);
     int run(Ctx& c, const half_t* sample, const float* timesteps, const half_t* ehs, int L,
-            const half_t* add_text, const float* add_time_ids, half_t* out, int B, int H, int W);
+            const half_t* add_text, const float* add_time_ids, half_t* out, int B, int H, int W,
+            const half_t* image_embeds = nullptr, int n_img = 0);
 };
 
 struct VAE {

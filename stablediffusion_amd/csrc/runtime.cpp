@@ -548,4 +548,18 @@ void op_attention(Ctx& c, View q, View k, View v, View out, int B, int Tq, int T
     prof_close(c.stream);
 }
 
+void op_ip_attention(Ctx& c, View q, View k, View v, View k_ip, View v_ip, View out, int B, int Tq, int L, int T_ip,
+                     int heads, int d, float ip_scale) {
+    if (c.dry || c.err) return;
+    if (prof_enabled()) {
+        static thread_local char name[32];
+        snprintf(name, sizeof(name), "ip_xattn_kernel<%d>", d);
+        prof_open(c.stream, name, 4.0 * B * heads * (double)Tq * (L + T_ip) * d,
+                  2.0 * B * heads * d * (2.0 * Tq + 2.0 * L + 2.0 * T_ip));
+    }
+    c.err = launch_ip_attention(q.p, k.p, v.p, k_ip.p, v_ip.p, out.p, B, Tq, L, T_ip, heads, d, q.ld, k.ld, v.ld, k_ip.ld,
+                                v_ip.ld, out.ld, ip_scale, 1, c.stream);
+    prof_close(c.stream);
+}
+
 }  // namespace sd

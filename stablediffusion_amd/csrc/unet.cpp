@@ -173,6 +173,7 @@ int UNet::pack_xformer(const std::string& p, Xformer* x, int heads, int depth) {
         // text K/V projections depend only on encoder_hidden_states: all of them are stacked into
         // one GEMM (kv_all) issued once per forward instead of one small launch per block
         b.kv_off = kv_total;
+        b.ip_kv_off = kv_total;          // IPAdapter::kv_all stacks its sites in this same order and width
         kv_total += 2 * x->C;
         kv_keys.push_back(q + ".attn2.to_k.weight");
         kv_keys.push_back(q + ".attn2.to_v.weight");
@@ -252,6 +253,85 @@ int UNet::finalize() {
     ws.free_raw();
     finalized = true;
     return 0;
+}
+
+// ------------------------------------------------------------------------------------------ IP-Adapter
+std::vector<std::pair<std::string, int>> unet_xattn_sites(const sd_unet_config& cfg, bool mid_last) {
+    const int nb = cfg.num_blocks;
+    const int* boc = cfg.block_out_channels;
+    std::vector<std::pair<std::string, int>> down, up, mid;
+    auto add = [](std::vector<std::pair<std::string, int>>& v, const std::string& p, int depth, int C) {
+        for (int k = 0; k < depth; ++k) v.emplace_back(p + ".transformer_blocks." + std::to_string(k), C);
+    };
+    for (int i = 0; i < nb; ++i)
+        if (cfg.down_block_has_attn[i])
+            for (int j = 0; j < cfg.layers_per_block; ++j)
+                add(down, "down_blocks." + std::to_string(i) + ".attentions." + std::to_string(j), cfg.transformer_layers[i], boc[i]);
+    add(mid, "mid_block.attentions.0", cfg.transformer_layers[nb - 1], boc[nb - 1]);
+    for (int i = 0; i < nb; ++i)
+        if (cfg.up_block_has_attn[i])
+            for (int j = 0; j < cfg.layers_per_block + 1; ++j)
+                add(up, "up_blocks." + std::to_string(i) + ".attentions." + std::to_string(j),
+                    cfg.transformer_layers[nb - 1 - i], boc[nb - 1 - i]);
+    std::vector<std::pair<std::string, int>> all = down;
+    const auto& second = mid_last ? up : mid;
+    const auto& third = mid_last ? mid : up;
+    all.insert(all.end(), second.begin(), second.end());
+    all.insert(all.end(), third.begin(), third.end());
+    return all;
+}
+
+namespace {
+const char* kIpProj = "encoder_hid_proj.image_projection_layers.0";
+}
+
+IPAdapter::IPAdapter(const sd_unet_config& c, int image_embed_dim, int num_tokens)
+    : cfg(c), d_img(image_embed_dim), n_tok(num_tokens) {
+    const int ctx = cfg.cross_attention_dim;
+    const std::string p = kIpProj;
+    ws.declare(p + ".image_embeds.weight", {(int64_t)n_tok * ctx, d_img});
+    ws.declare(p + ".image_embeds.bias", {(int64_t)n_tok * ctx});
+    ws.declare(p + ".norm.weight", {ctx});
+    ws.declare(p + ".norm.bias", {ctx});
+    for (const auto& site : unet_xattn_sites(cfg, true)) {
+        ws.declare(site.first + ".attn2.processor.to_k_ip.0.weight", {site.second, ctx});
+        ws.declare(site.first + ".attn2.processor.to_v_ip.0.weight", {site.second, ctx});
+    }
+}
+
+int IPAdapter::finalize() {
+    if (finalized) return 0;
+    std::string missing;
+    if (!ws.complete(&missing)) { set_error("ip adapter finalize: weight not set: " + missing); return 2; }
+    const std::string p = kIpProj;
+    int rc;
+    if ((rc = ws.pack_conv(p + ".image_embeds", &proj))) return rc;
+    if ((rc = ws.pack_norm(p + ".norm", &norm))) return rc;
+    // stacked in the UNet's kv_all order, so that a block's ip_kv_off equals its kv_off
+    std::vector<std::string> keys;
+    kv_total = 0;
+    for (const auto& site : unet_xattn_sites(cfg, false)) {
+        keys.push_back(site.first + ".attn2.processor.to_k_ip.0.weight");
+        keys.push_back(site.first + ".attn2.processor.to_v_ip.0.weight");
+        kv_total += 2 * site.second;
+    }
+    if ((rc = ws.pack_rows(keys, {}, &kv_all))) return rc;
+    SD_HIP_CHECK(hipDeviceSynchronize());
+    ws.free_raw();
+    finalized = true;
+    return 0;
+}
+
+void UNet::set_ip_adapter(IPAdapter* a) {
+    if (ip == a) return;
+    if (ip) ip->attached = nullptr;
+    if (a) {
+        if (a->attached && a->attached != this) a->attached->set_ip_adapter(nullptr);
+        a->attached = this;
+    }
+    ip = a;
+    ipkv_valid = false;
+    planned_key = -1;
 }
 
 // ------------------------------------------------------------------------------------------ blocks
@@ -334,7 +414,12 @@ void run_xformer(Ctx& c, const Xformer& t, View x, int N, int H, int W, View out
             op_layernorm(c, b.ln2, t2, n, M, 1e-5f);
             op_conv(c, b.q2, n, N, H, W, q);
         }
-        op_attention(c, q, text_kv.slice(b.kv_off, C), text_kv.slice(b.kv_off + C, C), att, N, T, L, t.heads, d, 0, 1);
+        // IP-Adapter attached: text and image attention in one launch (scale 0: the text attention alone, as without one)
+        if (c.ip_kv.p && c.ip_scale != 0.f)
+            op_ip_attention(c, q, text_kv.slice(b.kv_off, C), text_kv.slice(b.kv_off + C, C), c.ip_kv.slice(b.ip_kv_off, C),
+                            c.ip_kv.slice(b.ip_kv_off + C, C), att, N, T, L, c.ip_T, t.heads, d, c.ip_scale);
+        else
+            op_attention(c, q, text_kv.slice(b.kv_off, C), text_kv.slice(b.kv_off + C, C), att, N, T, L, t.heads, d, 0, 1);
         View t3(a.alloc_h(M * C), C, C);
         op_conv(c, b.out2, att, N, H, W, t3, 1, 0, nullptr, 0, &t2, 0, -1, 0, fold ? &f_t3 : nullptr);
         // norm3 -> GEGLU feed-forward -> + residual: one launch with the 4C-wide hidden tensor kept on the CU where the
@@ -363,7 +448,8 @@ void run_xformer(Ctx& c, const Xformer& t, View x, int N, int H, int W, View out
 
 // ----------------------------------------------------------------------------------------- forward
 int UNet::run(Ctx& c, const half_t* sample, const float* timesteps, const half_t* ehs, int L,
-              const half_t* add_text, const float* add_time_ids, half_t* out, int B, int H, int W) {
+              const half_t* add_text, const float* add_time_ids, half_t* out, int B, int H, int W,
+              const half_t* image_embeds, int n_img) {
     Arena& a = *c.arena;
     const int nb = cfg.num_blocks;
     const int* boc = cfg.block_out_channels;
@@ -418,6 +504,40 @@ int UNet::run(Ctx& c, const half_t* sample, const float* timesteps, const half_t
     if (!(kv_cached && kv_valid && kv_src == ehs && kv_B == B && kv_L == L)) {
         op_conv(c, kv_all, View(const_cast<half_t*>(ehs), cfg.cross_attention_dim, cfg.cross_attention_dim), B, L, 1, text_kv);
         if (kv_cached && go && !c.err) { kv_valid = true; kv_src = ehs; kv_B = B; kv_L = L; }
+    }
+
+    // ---- IP-Adapter: image tokens = LayerNorm(image_embeds W_proj^T + b) [B n_img n_tok, ctx], then their K / V for
+    //      every cross-attention block in one GEMM: [B T_ip, ctx] x [ctx, sum 2C] ----
+    if (ip && image_embeds) {
+        const int ctx = cfg.cross_attention_dim, T_ip = n_img * ip->n_tok;
+        const long rows = (long)B * n_img, ntc = (long)ip->n_tok * ctx;
+        const bool ip_cached = kv_cache_on && !graph_enabled && ipkv_cache != nullptr;
+        View ip_kv(ip_cached ? ipkv_cache : a.alloc_h((long)B * T_ip * ip->kv_total), ip->kv_total, ip->kv_total);
+        // the planning pass always takes the computing branch: its temporaries live between mark and release, so the
+        // live pass skipping them (cache hit) allocates less and every later tensor keeps its planned address
+        const bool hit = ip_cached && ipkv_valid && ipkv_src == image_embeds && ipkv_B == B && ipkv_n == n_img;
+        if (c.dry || !hit) {
+            const size_t mk = a.mark();
+            float* e32 = a.alloc_f(rows * ip->d_img);
+            float* p32 = a.alloc_f(rows * ntc);
+            half_t* p16 = a.alloc_h(rows * ntc);
+            half_t* tok = a.alloc_h(rows * ntc);
+            if (go && !c.err) c.err = launch_f16_to_f32(image_embeds, e32, rows * ip->d_img, s);
+            if (go && !c.err) {
+                prof_open(s, "small_linear_kernel", 2.0 * rows * ntc * ip->d_img, 2.0 * ntc * ip->d_img);
+                c.err = launch_small_linear(e32, ip->d_img, ip->proj.w, ip->proj.bias, p32, ntc, (int)rows, ip->d_img,
+                                            (int)ntc, 0, 0, s);
+                prof_close(s);
+            }
+            if (go && !c.err) c.err = launch_f32_to_f16(p32, p16, rows * ntc, s);
+            op_layernorm(c, ip->norm, View(p16, ctx, ctx), View(tok, ctx, ctx), rows * ip->n_tok, 1e-5f);
+            op_conv(c, ip->kv_all, View(tok, ctx, ctx), B, T_ip, 1, ip_kv);
+            a.release(mk);
+            if (ip_cached && go && !c.err) { ipkv_valid = true; ipkv_src = image_embeds; ipkv_B = B; ipkv_n = n_img; }
+        }
+        c.ip_kv = ip_kv;
+        c.ip_T = T_ip;
+        c.ip_scale = ip_scale;
     }
 
     // ---- skip / concat buffer plan ----
@@ -684,6 +804,8 @@ UNet::~UNet() {
     if (gstream) (void)hipStreamDestroy(gstream);
     if (io_slab) (void)hipFree(io_slab);
     if (kv_cache) (void)hipFree(kv_cache);
+    if (ipkv_cache) (void)hipFree(ipkv_cache);
+    if (ip) ip->attached = nullptr;
 }
 
 // Graph path: stage I/O through engine-owned buffers, capture the forward once per shape on an
@@ -760,10 +882,20 @@ int UNet::forward_graph(const half_t* sample, const float* timesteps, const half
 }
 
 int UNet::forward(const half_t* sample, const float* timesteps, const half_t* ehs, int L, const half_t* add_text,
-                  const float* add_time_ids, half_t* out, int B, int H, int W, hipStream_t stream) {
+                  const float* add_time_ids, half_t* out, int B, int H, int W, hipStream_t stream,
+                  const half_t* image_embeds, int n_img) {
     if (!finalized) { set_error("unet: forward before finalize"); return 2; }
     const int div = 1 << (cfg.num_blocks - 1);
     if (B <= 0 || H % div != 0 || W % div != 0) { set_error("unet: H and W must be divisible by 2^(blocks-1)"); return 1; }
+    if (ip && !image_embeds) { set_error("unet: an IP-Adapter is attached: image_embeds required"); return 1; }
+    if (!ip && image_embeds) { set_error("unet: image_embeds given but no IP-Adapter is attached"); return 1; }
+    if (ip) {
+        if (n_img < 1 || n_img * ip->n_tok > 64) { set_error("unet: images per prompt x adapter tokens must be in [1, 64]"); return 4; }
+        if (L < 1 || L > 160) { set_error("unet: with an IP-Adapter the text length must be in [1, 160]"); return 4; }
+        if (graph_enabled) { set_error("unet: graph replay with an IP-Adapter attached is not supported"); return 4; }
+    } else {
+        n_img = 0;
+    }
     if (graph_enabled && !prof_enabled())
         return forward_graph(sample, timesteps, ehs, L, add_text, add_time_ids, out, B, H, W, stream);
     if (kv_cache_on) {          // persistent buffer for the text K/V (outside the per-forward arena)
@@ -775,12 +907,24 @@ int UNet::forward(const half_t* sample, const float* timesteps, const half_t* eh
             SD_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&kv_cache), need));
             kv_cap = need;
         }
+        if (ip) {
+            const size_t ineed = (size_t)B * n_img * ip->n_tok * ip->kv_total * sizeof(half_t);
+            if (ineed > ipkv_cap) {
+                SD_HIP_CHECK(hipDeviceSynchronize());
+                if (ipkv_cache) (void)hipFree(ipkv_cache);
+                ipkv_cache = nullptr; ipkv_cap = 0; ipkv_valid = false;
+                SD_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&ipkv_cache), ineed));
+                ipkv_cap = ineed;
+            }
+        }
     }
-    const long key = ((long)B << 40) ^ ((long)H << 20) ^ (long)W ^ ((long)L << 52) ^ (kv_cache_on ? (1L << 62) : 0);
+    // (the IP-Adapter's image token count joins the key: set_ip_adapter resets the plan)
+    const long key = ((long)B << 40) ^ ((long)H << 20) ^ (long)W ^ ((long)L << 52) ^ (kv_cache_on ? (1L << 62) : 0) ^
+                     (ip ? (long)(n_img * ip->n_tok) << 32 : 0);
     if (key != planned_key) {
         Ctx dry{&arena, stream, true};
         arena.begin(true);
-        int rc = run(dry, sample, timesteps, ehs, L, add_text, add_time_ids, out, B, H, W);
+        int rc = run(dry, sample, timesteps, ehs, L, add_text, add_time_ids, out, B, H, W, image_embeds, n_img);
         if (rc) return rc;
         // growing the slab frees the old one: make sure nothing enqueued earlier still uses it
         if (arena.peak() > arena.capacity()) {
@@ -792,7 +936,7 @@ int UNet::forward(const half_t* sample, const float* timesteps, const half_t* eh
     }
     Ctx ctx{&arena, stream, false};
     arena.begin(false);
-    int rc = run(ctx, sample, timesteps, ehs, L, add_text, add_time_ids, out, B, H, W);
+    int rc = run(ctx, sample, timesteps, ehs, L, add_text, add_time_ids, out, B, H, W, image_embeds, n_img);
     if (!rc && arena.overflow()) { set_error("unet: workspace overflow (planner bug)"); return 2; }
     return rc;
 }

@@ -114,6 +114,17 @@ def max_over_ranks(x: float, device) -> float:
     return float(t.item())
 
 
+def _shard_cfg_rows(e: torch.Tensor, total: int, rank: int, world: int) -> torch.Tensor:
+    """This rank's rows of a per-sample tensor laid out [negative | positive] (2 total rows) or [positive] (total);
+    anything else (one row broadcast to the batch) is left whole."""
+    if e.shape[0] == 2 * total:
+        neg, pos = e.chunk(2)
+        return torch.cat([shard(neg, rank, world), shard(pos, rank, world)])
+    if e.shape[0] == total:
+        return shard(e, rank, world)
+    return e
+
+
 def sharded_txt2img(pipeline, model, latents_full: torch.Tensor, prompt_embeds_full: torch.Tensor,
                     negative_embeds_full: torch.Tensor, rank: int, world: int,
                     pooled_full: Optional[torch.Tensor] = None, negative_pooled_full: Optional[torch.Tensor] = None,
@@ -134,5 +145,11 @@ def sharded_txt2img(pipeline, model, latents_full: torch.Tensor, prompt_embeds_f
     if pooled_full is not None:      # SDXL pooled text embeddings ride along with the same split
         call_kwargs = dict(call_kwargs, pooled_prompt_embeds=shard(pooled_full, rank, world),
                            negative_pooled_prompt_embeds=shard(negative_pooled_full, rank, world))
+    ip = call_kwargs.get("ip_adapter_image_embeds")
+    if ip is not None:               # IP-Adapter image embeds [neg | pos] (or one half without CFG): the same split
+        ip = [ip] if isinstance(ip, torch.Tensor) else list(ip)
+        if broadcast:
+            broadcast_tensors(ip)
+        call_kwargs = dict(call_kwargs, ip_adapter_image_embeds=[_shard_cfg_rows(e, total, rank, world) for e in ip])
     images = pipeline(model, prompt_embeds=pe, negative_prompt_embeds=ne, latents=lat, **call_kwargs)
     return all_gather_batch(images, total)

@@ -17,6 +17,7 @@ PyTorch is plumbing here (device buffers + the current HIP stream); all arithmet
 from __future__ import annotations
 
 import ctypes as C
+import weakref
 from types import SimpleNamespace
 from typing import Dict, Optional
 
@@ -109,6 +110,8 @@ class HipUNet2DConditionModel:
             self.add_embedding = SimpleNamespace(
                 linear_1=SimpleNamespace(in_features=config.projection_class_embeddings_input_dim))
         self._finalized = False
+        self._ip = None                # attached HipIPAdapter (attach_ip_adapter)
+        self._ip_scale = 1.0
 
     # -- weights -------------------------------------------------------------------------------
     def load_state_dict(self, state_dict: Dict[str, torch.Tensor], strict: bool = True):
@@ -148,6 +151,55 @@ class HipUNet2DConditionModel:
         _lib.check(self._lib.sd_unet_text_kv_cache(self._h, int(bool(enable))), "sd_unet_text_kv_cache")
         return self
 
+    def attach_ip_adapter(self, adapter: Optional["HipIPAdapter"]):
+        """Attach an IP-Adapter built for this configuration (None detaches).  While attached, every call needs
+        added_cond_kwargs["image_embeds"] and each cross-attention adds scale * SDPA(q, K_ip, V_ip)."""
+        if adapter is not None and adapter.cfg.to_dict() != self.cfg.to_dict():
+            raise ValueError("IP-Adapter was built for another UNet configuration")
+        _lib.check(self._lib.sd_unet_set_ip_adapter(self._h, adapter._h if adapter is not None else None),
+                   "sd_unet_set_ip_adapter")
+        if self._ip is not None and self._ip is not adapter:
+            self._ip._unet = None
+        if adapter is not None:
+            old = adapter._unet() if adapter._unet is not None else None
+            if old is not None and old is not self:
+                old._ip = None
+            adapter._unet = weakref.ref(self)      # (no cycle: a dropped engine frees its device memory at once)
+        self._ip = adapter
+        return self
+
+    def make_ip_adapter(self, state_dict: Dict[str, torch.Tensor], image_embed_dim: int, num_tokens: int):
+        """A HipIPAdapter for this engine's configuration, loaded from diffusers-named weights."""
+        return HipIPAdapter(self, image_embed_dim, num_tokens).load_state_dict(state_dict)
+
+    @property
+    def ip_adapter(self):
+        return self._ip
+
+    def set_ip_adapter_scale(self, scale: float):
+        """diffusers' set_ip_adapter_scale: lambda of the image branch (default 1.0; 0 = text attention only)."""
+        _lib.check(self._lib.sd_unet_set_ip_adapter_scale(self._h, float(scale)), "sd_unet_set_ip_adapter_scale")
+        self._ip_scale = float(scale)
+        return self
+
+    def _image_embeds(self, added_cond_kwargs, B, dev):
+        embeds = (added_cond_kwargs or {}).get("image_embeds")
+        if self._ip is None:
+            if embeds is not None:
+                raise ValueError("added_cond_kwargs['image_embeds'] given but no IP-Adapter is attached")
+            return None
+        if embeds is None:
+            raise ValueError("an IP-Adapter is attached: added_cond_kwargs['image_embeds'] is required")
+        if isinstance(embeds, (list, tuple)):
+            if len(embeds) != 1:
+                raise ValueError(f"one IP-Adapter is attached, got image_embeds for {len(embeds)}")
+            embeds = embeds[0]
+        if embeds.ndim == 2:               # deprecated diffusers form [B, D_img]: one image per prompt
+            embeds = embeds[:, None]
+        if embeds.ndim != 3 or embeds.shape[0] != B or embeds.shape[2] != self._ip.image_embed_dim:
+            raise ValueError(f"image_embeds: expected [{B}, n_img, {self._ip.image_embed_dim}], got {tuple(embeds.shape)}")
+        return _as_f16(embeds, dev)
+
     # -- reference surface ---------------------------------------------------------------------
     def to(self, device=None, dtype=None):
         if device is not None and torch.device(device).type != "cuda":
@@ -183,11 +235,18 @@ class HipUNet2DConditionModel:
             add_text = _as_f16(added_cond_kwargs["text_embeds"], dev)
             add_ids = added_cond_kwargs["time_ids"].to(device=dev, dtype=torch.float32).contiguous()
             pt, pi = C.c_void_p(add_text.data_ptr()), C.c_void_p(add_ids.data_ptr())
+        img = self._image_embeds(added_cond_kwargs, B, dev)
         out = torch.empty((B, self.cfg.out_channels, H, W), device=dev, dtype=torch.float16)
         with torch.cuda.device(dev):
-            rc = self._lib.sd_unet_forward(self._h, C.c_void_p(sample.data_ptr()), C.c_void_p(t.data_ptr()),
-                                           C.c_void_p(ehs.data_ptr()), ehs.shape[1], pt, pi,
-                                           C.c_void_p(out.data_ptr()), B, H, W, C.c_void_p(_stream_ptr()))
+            if img is None:
+                rc = self._lib.sd_unet_forward(self._h, C.c_void_p(sample.data_ptr()), C.c_void_p(t.data_ptr()),
+                                               C.c_void_p(ehs.data_ptr()), ehs.shape[1], pt, pi,
+                                               C.c_void_p(out.data_ptr()), B, H, W, C.c_void_p(_stream_ptr()))
+            else:
+                rc = self._lib.sd_unet_forward_ex(self._h, C.c_void_p(sample.data_ptr()), C.c_void_p(t.data_ptr()),
+                                                  C.c_void_p(ehs.data_ptr()), ehs.shape[1], pt, pi,
+                                                  C.c_void_p(img.data_ptr()), img.shape[1],
+                                                  C.c_void_p(out.data_ptr()), B, H, W, C.c_void_p(_stream_ptr()))
         _lib.check(rc, "sd_unet_forward")
         if return_dict:
             return SimpleNamespace(sample=out)
@@ -209,6 +268,42 @@ class HipUNet2DConditionModel:
         try:
             if getattr(self, "_h", None):
                 self._lib.sd_unet_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+
+class HipIPAdapter:
+    """IP-Adapter image projection + per-site to_k_ip / to_v_ip on the engine, bound to a UNet configuration
+    (sd_ip_adapter_*).  Weights in diffusers' post-load naming (stablediffusion_amd.ip_adapter.convert)."""
+
+    def __init__(self, unet: HipUNet2DConditionModel, image_embed_dim: int, num_tokens: int = 4):
+        self._lib = _lib.load()
+        self.cfg = unet.cfg
+        self.device = unet.device
+        self.image_embed_dim = int(image_embed_dim)
+        self.num_tokens = int(num_tokens)
+        self._unet = None
+        self._h = C.c_void_p()
+        _lib.check(self._lib.sd_ip_adapter_create(unet._h, self.image_embed_dim, self.num_tokens, C.byref(self._h)),
+                   "sd_ip_adapter_create")
+        self._finalized = False
+
+    def load_state_dict(self, state_dict: Dict[str, torch.Tensor], strict: bool = True):
+        _lib.require_gpu()
+        with torch.cuda.device(self.device):
+            _load_weights(self._lib, self._h, "ip_adapter", state_dict, strict)
+            _lib.check(self._lib.sd_ip_adapter_finalize(self._h), "sd_ip_adapter_finalize")
+        self._finalized = True
+        return self
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None):
+                u = self._unet() if self._unet is not None else None
+                if u is not None:
+                    u._ip = None
+                self._lib.sd_ip_adapter_destroy(self._h)     # (detaches it first)
                 self._h = None
         except Exception:
             pass

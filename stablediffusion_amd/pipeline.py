@@ -36,8 +36,16 @@ class SDModelWrapper:
                  text_encoder_2=None, tokenizer_2=None, model_type: str = "sd15", device: str = "cuda",
                  model_name: Optional[str] = None, unet_state_dict: Optional[Dict[str, torch.Tensor]] = None,
                  text_encoder_state_dict: Optional[Dict[str, torch.Tensor]] = None,
-                 text_encoder_2_state_dict: Optional[Dict[str, torch.Tensor]] = None):
+                 text_encoder_2_state_dict: Optional[Dict[str, torch.Tensor]] = None,
+                 image_encoder=None, feature_extractor=None):
         self.base = base
+        # IP-Adapter (sd_unified_pipeline.py:441-449): host image encoder (e.g. transformers'
+        # CLIPVisionModelWithProjection) and its CLIPImageProcessor, built by the caller; the adapter's converted
+        # weights stay here so that a LoRA re-fuse (which rebuilds .base) can attach it again
+        self.image_encoder = image_encoder
+        self.feature_extractor = feature_extractor
+        self._ip = None                  # (diffusers-named state dict, image_embed_dim, num_tokens)
+        self._ip_scale = 1.0
         # host copies of the weights the LoRA adapters are folded into (load_lora_weights); the engine
         # itself keeps only its packed device copy
         self._lora = None
@@ -122,7 +130,36 @@ class SDModelWrapper:
         base = self._base_factory(fused)
         if graph and hasattr(base, "use_graph"):
             base.use_graph(True)
+        if self._ip is not None:             # the IP-Adapter survives the re-fuse
+            self._attach_ip(base)
         return base
+
+    # ---- IP-Adapter (diffusers load_ip_adapter / set_ip_adapter_scale / unload_ip_adapter) ----
+    def _attach_ip(self, base):
+        sd, d_img, n_tok = self._ip
+        base.attach_ip_adapter(base.make_ip_adapter(sd, d_img, n_tok))
+        base.set_ip_adapter_scale(self._ip_scale)
+
+    def load_ip_adapter(self, pretrained_model_name_or_path_or_dict):
+        """An original IP-Adapter file (`.bin` / `.safetensors`, a local path) or its state dict: converted, checked
+        against the UNet and attached (stablediffusion_amd.ip_adapter).  Replaces an adapter loaded before."""
+        from . import ip_adapter
+        sd, d_img, n_tok = ip_adapter.convert(pretrained_model_name_or_path_or_dict, self.base.cfg)
+        self._ip = (sd, d_img, n_tok)
+        self._ip_scale = 1.0
+        self._attach_ip(self.base)
+
+    def set_ip_adapter_scale(self, scale: float):
+        self._ip_scale = float(scale)
+        if self._ip is not None:
+            self.base.set_ip_adapter_scale(self._ip_scale)
+
+    def unload_ip_adapter(self):
+        if self._ip is not None:
+            self.base.attach_ip_adapter(None)
+            self.base.set_ip_adapter_scale(1.0)
+        self._ip = None
+        self._ip_scale = 1.0
 
     def _refuse(self):
         # (kept for callers that want the rebuild now; load / set / delete only mark the state changed)
@@ -235,6 +272,9 @@ class StableDiffusionUnifiedPipeline:
         negative_prompt_embeds: Optional[torch.Tensor] = None,
         pooled_prompt_embeds: Optional[torch.Tensor] = None,
         negative_pooled_prompt_embeds: Optional[torch.Tensor] = None,
+        # IP-Adapter image prompts (the reference's commented block at :441-449)
+        ip_adapter_image=None,
+        ip_adapter_image_embeds: Optional[List[torch.Tensor]] = None,
     ):
         if model.device != self.device:
             model.to(self.device)
@@ -360,6 +400,14 @@ class StableDiffusionUnifiedPipeline:
                                  "time_ids": add_time_ids.to(self.device)}
         else:
             added_cond_kwargs = None
+
+        if ip_adapter_image is not None or ip_adapter_image_embeds is not None:
+            image_embeds = self.prepare_ip_adapter_image_embeds(ip_adapter_image, ip_adapter_image_embeds, self.device,
+                                                                batch_size * num_images_per_prompt,
+                                                                self.do_classifier_free_guidance)
+            if self.device.type == "cuda":       # one fp16 buffer for the whole loop: the engine caches its image K/V
+                image_embeds = [e.to(torch.float16).contiguous() for e in image_embeds]
+            added_cond_kwargs = dict(added_cond_kwargs or {}, image_embeds=image_embeds)
 
         if self.do_classifier_free_guidance:
             prompt_embeds = torch.cat([negative_prompt_embeds, prompt_embeds], dim=0)
@@ -489,6 +537,54 @@ class StableDiffusionUnifiedPipeline:
             raise RuntimeError(lib.sd_last_error().decode())
         model.scheduler.fused_commit()
         return out, hist
+
+    def encode_image(self, image, device, num_images_per_prompt):
+        """diffusers 0.27.2 `encode_image` for the base adapters' ImageProjection: image_encoder(feature_extractor(image)
+        .pixel_values).image_embeds, repeated per prompt image; the negative is zeros_like (it still goes through the
+        adapter's projection in the UNet, so its tokens are not zero).  Host PyTorch, once per call."""
+        m = self.model
+        if m.image_encoder is None:
+            raise ValueError("ip_adapter_image needs model.image_encoder (or pass ip_adapter_image_embeds)")
+        p = next(iter(m.image_encoder.parameters()), None)
+        enc_device = p.device if p is not None else torch.device("cpu")
+        dtype = p.dtype if p is not None else torch.float32
+        if not isinstance(image, torch.Tensor):
+            if m.feature_extractor is None:
+                raise ValueError("ip_adapter_image needs model.feature_extractor for non-tensor images")
+            image = m.feature_extractor(image, return_tensors="pt").pixel_values
+        image = image.to(device=enc_device, dtype=dtype)
+        image_embeds = m.image_encoder(image).image_embeds
+        image_embeds = image_embeds.repeat_interleave(num_images_per_prompt, dim=0)
+        return image_embeds.to(device), torch.zeros_like(image_embeds).to(device)
+
+    def prepare_ip_adapter_image_embeds(self, ip_adapter_image, ip_adapter_image_embeds, device, num_images_per_prompt,
+                                        do_classifier_free_guidance):
+        """diffusers 0.27.2 `prepare_ip_adapter_image_embeds` for one adapter -> a list of one [N(.2), n_img, D_img]
+        tensor, N = batch x images per prompt, negative half first under CFG (the order of the prompt embeddings).
+        Precomputed embeds ([R(.2), n_img, D_img], negative half first under CFG) pass unchanged when R = N and are
+        repeated N / R times otherwise (diffusers repeats them N times: the same for the usual R = 1)."""
+        if ip_adapter_image_embeds is None:
+            if isinstance(ip_adapter_image, list) and len(ip_adapter_image) == 1:
+                ip_adapter_image = ip_adapter_image[0]
+            pos, neg = self.encode_image(ip_adapter_image, device, 1)
+            pos = torch.stack([pos] * num_images_per_prompt, dim=0)
+            neg = torch.stack([neg] * num_images_per_prompt, dim=0)
+            return [torch.cat([neg, pos]).to(device) if do_classifier_free_guidance else pos.to(device)]
+        if isinstance(ip_adapter_image_embeds, torch.Tensor):
+            ip_adapter_image_embeds = [ip_adapter_image_embeds]
+        if len(ip_adapter_image_embeds) != 1:
+            raise ValueError(f"one IP-Adapter is supported, got image embeds for {len(ip_adapter_image_embeds)}")
+        e = ip_adapter_image_embeds[0]
+        if e.ndim != 3:
+            raise ValueError(f"ip_adapter_image_embeds: expected [batch, n_img, D_img], got {tuple(e.shape)}")
+        halves = e.chunk(2) if do_classifier_free_guidance else (e,)
+        rows = halves[0].shape[0]
+        if rows == num_images_per_prompt:
+            return [e.to(device)]
+        if num_images_per_prompt % rows != 0 or any(h.shape[0] != rows for h in halves):
+            raise ValueError(f"ip_adapter_image_embeds: {rows} rows per half do not divide the batch {num_images_per_prompt}")
+        rep = num_images_per_prompt // rows
+        return [torch.cat([h.repeat(rep, 1, 1) for h in halves]).to(device)]
 
     def encode_prompt(self, prompt, prompt_2=None, negative_prompt=None, negative_prompt_2=None,
                       num_images_per_prompt=1, lora_scale=None, clip_skip=None):
