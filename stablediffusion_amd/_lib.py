@@ -69,6 +69,11 @@ class SdProfEntry(C.Structure):
                 ("ms", C.c_double), ("launches", C.c_int64)]
 
 
+class SdCnProblem(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("ldx", C.c_int64), ("w", C.c_void_p), ("bias", C.c_void_p),
+                ("y", C.c_void_p), ("ldy", C.c_int64), ("M", C.c_int), ("C", C.c_int)]
+
+
 # name -> (restype, argtypes); every symbol include/sd_engine.h declares
 _P = C.c_void_p
 _I = C.c_int
@@ -97,6 +102,14 @@ SIGNATURES = {
     "sd_ip_adapter_weight_info": (_I, [_P, _I, C.POINTER(C.c_char_p), C.POINTER(_I64), C.POINTER(_I)]),
     "sd_ip_adapter_set_weight": (_I, [_P, C.c_char_p, _P, C.POINTER(_I64), _I, _I]),
     "sd_ip_adapter_finalize": (_I, [_P]),
+    "sd_unet_set_controlnet": (_I, [_P, _P]),
+    "sd_unet_forward_cn": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _I, _P, _I, _F, _P, _I, _I, _I, _P]),
+    "sd_controlnet_create": (_I, [_P, C.POINTER(SdUNetConfig), _I, C.POINTER(_P)]),
+    "sd_controlnet_destroy": (_I, [_P]),
+    "sd_controlnet_num_weights": (_I, [_P]),
+    "sd_controlnet_weight_info": (_I, [_P, _I, C.POINTER(C.c_char_p), C.POINTER(_I64), C.POINTER(_I)]),
+    "sd_controlnet_set_weight": (_I, [_P, C.c_char_p, _P, C.POINTER(_I64), _I, _I]),
+    "sd_controlnet_finalize": (_I, [_P]),
     "sd_vae_create": (_I, [C.POINTER(SdVAEConfig), C.POINTER(_P)]),
     "sd_vae_destroy": (_I, [_P]),
     "sd_vae_num_weights": (_I, [_P]),
@@ -150,6 +163,8 @@ SIGNATURES = {
     "sd_op_attention": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "sd_op_ip_cross_attention": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _I, _I,
                                       C.POINTER(_F), _P]),
+    "sd_op_controlnet_residuals": (_I, [C.POINTER(SdCnProblem), _I, _F, _I, _I, C.POINTER(_F), _P]),
+    "sd_op_controlnet_cond_embed": (_I, [_P, _P, _I, _I, _I, _P, _I, C.POINTER(_F), _P]),
 }
 
 _lib = None

@@ -11,6 +11,10 @@ using namespace sd;
 struct sd_unet { UNet impl; explicit sd_unet(const sd_unet_config& c) : impl(c) {} };
 struct sd_vae { VAE impl; explicit sd_vae(const sd_vae_config& c) : impl(c) {} };
 struct sd_clip { CLIP impl; explicit sd_clip(const sd_clip_config& c) : impl(c) {} };
+struct sd_controlnet {
+    ControlNet impl;
+    sd_controlnet(const sd_unet_config& c, int cc) : impl(c, cc) {}
+};
 struct sd_ip_adapter {
     IPAdapter impl;
     sd_ip_adapter(const sd_unet_config& c, int d, int n) : impl(c, d, n) {}
@@ -61,6 +65,25 @@ bool same_topology(const sd_unet_config& a, const sd_unet_config& b) {
             a.up_block_has_attn[i] != b.up_block_has_attn[i] || a.num_heads[i] != b.num_heads[i] ||
             a.transformer_layers[i] != b.transformer_layers[i])
             return false;
+    return true;
+}
+
+// Whether a ControlNet of configuration n can feed a UNet of configuration u: its residuals must have the shapes of
+// u's skips and mid-block output, and it must read the same sample, text and text_time conditioning.
+bool controlnet_fits(const sd_unet_config& u, const sd_unet_config& n, std::string* why) {
+    if (n.num_blocks != u.num_blocks || n.layers_per_block != u.layers_per_block) {
+        *why = "num_blocks / layers_per_block differ from the UNet's";
+        return false;
+    }
+    for (int i = 0; i < u.num_blocks; ++i)
+        if (n.block_out_channels[i] != u.block_out_channels[i]) { *why = "block_out_channels differ from the UNet's"; return false; }
+    if (n.cross_attention_dim != u.cross_attention_dim) { *why = "cross_attention_dim differs from the UNet's"; return false; }
+    if (n.in_channels != u.in_channels) { *why = "in_channels differs from the UNet's (9-channel inpaint UNets take no ControlNet)"; return false; }
+    if (n.addition_time_embed_dim != u.addition_time_embed_dim ||
+        n.projection_class_embeddings_input_dim != u.projection_class_embeddings_input_dim) {
+        *why = "text_time conditioning differs from the UNet's";
+        return false;
+    }
     return true;
 }
 
@@ -118,6 +141,8 @@ int sd_unet_text_kv_cache(sd_unet* u, int enable) {
     u->impl.kv_cache_on = enable != 0;
     u->impl.kv_valid = false;           // every call invalidates: the next forward recomputes
     u->impl.ipkv_valid = false;         // (the IP-Adapter's image K / V alike)
+    u->impl.cond_valid = false;         // (and the ControlNet's conditioning embedding and text K / V)
+    u->impl.cnkv_valid = false;
     return SD_OK;
 }
 int sd_unet_forward_ex(sd_unet* u, const void* sample, const float* timesteps, const void* ehs, int ehs_len,
@@ -140,6 +165,27 @@ int sd_unet_set_ip_adapter(sd_unet* u, sd_ip_adapter* a) {
     }
     u->impl.set_ip_adapter(a ? &a->impl : nullptr);
     return SD_OK;
+}
+int sd_unet_set_controlnet(sd_unet* u, sd_controlnet* cn) {
+    if (!u) { set_error("null handle"); return SD_ERR_INVALID; }
+    if (cn) {
+        if (!cn->impl.finalized) { set_error("sd_unet_set_controlnet: ControlNet not finalized"); return SD_ERR_STATE; }
+        std::string why;
+        if (!controlnet_fits(u->impl.cfg, cn->impl.cfg, &why)) { set_error("sd_unet_set_controlnet: " + why); return SD_ERR_INVALID; }
+    }
+    u->impl.set_controlnet(cn ? &cn->impl : nullptr);
+    return SD_OK;
+}
+int sd_unet_forward_cn(sd_unet* u, const void* sample, const float* timesteps, const void* ehs, int ehs_len,
+                       const void* add_text, const float* add_time_ids, const void* image_embeds, int n_img,
+                       const void* control_image, int n_ctrl, float cond_scale, void* out, int B, int H, int W,
+                       void* stream) {
+    if (!u || !sample || !timesteps || !ehs || !out) { set_error("null argument"); return SD_ERR_INVALID; }
+    return u->impl.forward(static_cast<const half_t*>(sample), timesteps, static_cast<const half_t*>(ehs),
+                           ehs_len, static_cast<const half_t*>(add_text), add_time_ids,
+                           static_cast<half_t*>(out), B, H, W, static_cast<hipStream_t>(stream),
+                           static_cast<const half_t*>(image_embeds), image_embeds ? n_img : 0,
+                           static_cast<const half_t*>(control_image), control_image ? n_ctrl : 0, cond_scale);
 }
 int sd_unet_set_ip_adapter_scale(sd_unet* u, float scale) {
     if (!u) { set_error("null handle"); return SD_ERR_INVALID; }
@@ -186,6 +232,41 @@ int sd_ip_adapter_set_weight(sd_ip_adapter* a, const char* key, const void* data
 int sd_ip_adapter_finalize(sd_ip_adapter* a) {
     if (!a) { set_error("null handle"); return SD_ERR_INVALID; }
     return a->impl.finalize();
+}
+// ------------------------------------------------------------------------------------- ControlNet
+int sd_controlnet_create(const sd_unet* u, const sd_unet_config* cn_cfg, int conditioning_channels, sd_controlnet** out) {
+    if (!u || !cn_cfg || !out) { set_error("null argument"); return SD_ERR_INVALID; }
+    if (conditioning_channels != 3) { set_error("sd_controlnet_create: conditioning_channels must be 3"); return SD_ERR_UNSUPPORTED; }
+    // (only the encoder half of the configuration is read: make the up-path fields consistent for bad_cfg)
+    sd_unet_config c = *cn_cfg;
+    for (int i = 0; i < SD_MAX_BLOCKS; ++i) c.up_block_has_attn[i] = 0;
+    if (bad_cfg(&c)) { set_error("sd_controlnet_create: unsupported encoder configuration"); return SD_ERR_UNSUPPORTED; }
+    std::string why;
+    if (!controlnet_fits(u->impl.cfg, c, &why)) { set_error("sd_controlnet_create: " + why); return SD_ERR_INVALID; }
+    if (u->impl.cfg.in_channels != 4) { set_error("sd_controlnet_create: the UNet must take 4 latent channels"); return SD_ERR_INVALID; }
+    if (1 + c.num_blocks * c.layers_per_block + (c.num_blocks - 1) + 1 > kCnMaxProblems) {
+        set_error("sd_controlnet_create: more residual sites than one grouped launch takes (16)");
+        return SD_ERR_UNSUPPORTED;
+    }
+    *out = new (std::nothrow) sd_controlnet(c, conditioning_channels);
+    if (!*out) { set_error("out of host memory"); return SD_ERR_INVALID; }
+    return SD_OK;
+}
+int sd_controlnet_destroy(sd_controlnet* cn) { delete cn; return SD_OK; }
+int sd_controlnet_num_weights(const sd_controlnet* cn) { return cn ? (int)cn->impl.ws.order.size() : 0; }
+int sd_controlnet_weight_info(const sd_controlnet* cn, int index, const char** key, int64_t* shape4, int* ndim) {
+    if (!cn) { set_error("null handle"); return SD_ERR_INVALID; }
+    return weight_info(cn->impl.ws, index, key, shape4, ndim);
+}
+int sd_controlnet_set_weight(sd_controlnet* cn, const char* key, const void* data, const int64_t* shape, int ndim,
+                             int dtype) {
+    if (!cn || !key || !data || !shape) { set_error("null argument"); return SD_ERR_INVALID; }
+    if (cn->impl.finalized) { set_error("set_weight after finalize"); return SD_ERR_STATE; }
+    return cn->impl.ws.set(key, data, shape, ndim, dtype);
+}
+int sd_controlnet_finalize(sd_controlnet* cn) {
+    if (!cn) { set_error("null handle"); return SD_ERR_INVALID; }
+    return cn->impl.finalize();
 }
 int sd_unet_memory(const sd_unet* u, int64_t* weight_bytes, int64_t* workspace_bytes) {
     if (!u) { set_error("null handle"); return SD_ERR_INVALID; }
@@ -1056,6 +1137,120 @@ int sd_op_ip_cross_attention(const void* q, const void* k, const void* v, const 
     if (e1) (void)hipEventDestroy(e1);
     (void)hipFree(tmp);
     return rc;
+}
+
+}  // extern "C"
+
+namespace {
+// Runs `body(ctx)` once as a planning pass and once for real on a private arena (the op entries' workspace), `iters`
+// more times between events when timing.
+template <class F>
+int run_op_on_arena(hipStream_t s, int iters, float* ms, F body) {
+    Arena arena;
+    Ctx dry{&arena, s, true};
+    arena.begin(true);
+    body(dry);
+    if (dry.err) return dry.err;
+    if (int rc = arena.reserve(arena.peak() > 0 ? arena.peak() : 256)) return rc;
+    auto live = [&]() {
+        Ctx c{&arena, s, false};
+        arena.begin(false);
+        body(c);
+        return c.err;
+    };
+    int rc = live();
+    if (!rc && iters > 0) {
+        if (!ms) { set_error("ms_per_launch required with iters > 0"); return SD_ERR_INVALID; }
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) rc = SD_ERR_HIP;
+        if (!rc) rc = live();                       // warm-up
+        if (!rc) (void)hipEventRecord(e0, s);
+        for (int it = 0; it < iters && !rc; ++it) rc = live();
+        if (!rc) {
+            (void)hipEventRecord(e1, s);
+            float t = 0.f;
+            hipError_t e = hipEventSynchronize(e1);
+            if (e == hipSuccess) e = hipEventElapsedTime(&t, e0, e1);
+            if (e != hipSuccess) { set_error(hipGetErrorString(e)); rc = SD_ERR_HIP; }
+            *ms = t / (float)iters;
+        }
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+    }
+    const hipError_t e = hipStreamSynchronize(s);
+    if (!rc && e != hipSuccess) { set_error(hipGetErrorString(e)); rc = SD_ERR_HIP; }
+    return rc;
+}
+}  // namespace
+
+extern "C" {
+
+int sd_op_controlnet_residuals(const sd_cn_problem* problems, int count, float scale, int mode, int iters,
+                               float* ms_per_launch, void* stream) {
+    if (!problems || count < 1 || count > kCnMaxProblems) { set_error("sd_op_controlnet_residuals: 1..16 problems"); return SD_ERR_INVALID; }
+    if (mode != 0 && mode != 1) { set_error("sd_op_controlnet_residuals: mode must be 0 (grouped) or 1 (unfused)"); return SD_ERR_INVALID; }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    CnResParams rp;
+    rp.scale = scale;
+    for (int i = 0; i < count; ++i) {
+        const sd_cn_problem& q = problems[i];
+        CnResProblem& d = rp.p[rp.count++];
+        d.x = static_cast<const half_t*>(q.x); d.ldx = q.ldx; d.w = static_cast<const half_t*>(q.w); d.bias = q.bias;
+        d.y = static_cast<half_t*>(q.y); d.ldy = q.ldy; d.M = q.M; d.C = q.C; d.first = rp.total;
+        if (q.C <= 0 || q.C % 64 != 0 || q.M <= 0) { set_error("sd_op_controlnet_residuals: C % 64 == 0 and M >= 1 required"); return SD_ERR_UNSUPPORTED; }
+        rp.total += cn_residual_tiles(q.M, q.C);
+    }
+    if (!cn_residual_supported(rp)) { set_error("sd_op_controlnet_residuals: unsupported strides or alignment"); return SD_ERR_UNSUPPORTED; }
+    if (mode == 0) return run_op_on_arena(s, iters, ms_per_launch, [&](Ctx& c) { if (!c.dry) c.err = launch_cn_residual(rp, s); });
+    // unfused: one GEMM per problem, y = scale (x W^T) + scale b + y; the GEMM kernels read whole weight tiles, so the
+    // weights and biases are copied into row-padded buffers first
+    std::vector<ConvW> ws((size_t)count);
+    std::vector<void*> owned;
+    int rc = 0;
+    for (int i = 0; i < count && !rc; ++i) {
+        const sd_cn_problem& q = problems[i];
+        const long rows = ((long)q.C + kWeightRowPad - 1) / kWeightRowPad * kWeightRowPad;
+        void *w = nullptr, *b = nullptr;
+        if (hipMalloc(&w, (size_t)rows * q.C * sizeof(half_t)) != hipSuccess || hipMalloc(&b, (size_t)rows * sizeof(float)) != hipSuccess) {
+            set_error("sd_op_controlnet_residuals: out of device memory"); rc = SD_ERR_HIP;
+        }
+        if (w) owned.push_back(w);
+        if (b) owned.push_back(b);
+        if (rc) break;
+        if (hipMemsetAsync(w, 0, (size_t)rows * q.C * sizeof(half_t), s) != hipSuccess ||
+            hipMemsetAsync(b, 0, (size_t)rows * sizeof(float), s) != hipSuccess ||
+            hipMemcpyAsync(w, q.w, (size_t)q.C * q.C * sizeof(half_t), hipMemcpyDeviceToDevice, s) != hipSuccess ||
+            hipMemcpyAsync(b, q.bias, (size_t)q.C * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) {
+            set_error("sd_op_controlnet_residuals: copy failed"); rc = SD_ERR_HIP;
+        }
+        ConvW& cw = ws[(size_t)i];
+        cw.w = static_cast<half_t*>(w); cw.bias = static_cast<float*>(b); cw.cin = q.C; cw.cout = q.C; cw.ks = 1; cw.K = q.C;
+    }
+    if (!rc && scale != 0.f)
+        rc = run_op_on_arena(s, iters, ms_per_launch, [&](Ctx& c) {
+            for (int i = 0; i < count; ++i) {
+                const sd_cn_problem& q = problems[i];
+                View y(static_cast<half_t*>(q.y), q.ldy, q.C);
+                ConvFuse f;
+                f.acc_scale = scale; f.bias_scale = scale;
+                op_conv(c, ws[(size_t)i], View(const_cast<half_t*>(static_cast<const half_t*>(q.x)), q.ldx, q.C), 1, q.M, 1,
+                        y, 1, 0, nullptr, 0, &y, 0, -1, 0, &f);
+            }
+        });
+    (void)hipStreamSynchronize(s);
+    for (void* p : owned) (void)hipFree(p);
+    return rc;
+}
+
+int sd_op_controlnet_cond_embed(sd_controlnet* cn, const void* image, int n, int H, int W, void* out, int iters,
+                                float* ms_per_launch, void* stream) {
+    if (!cn || !image || !out) { set_error("null argument"); return SD_ERR_INVALID; }
+    if (!cn->impl.finalized) { set_error("sd_op_controlnet_cond_embed: ControlNet not finalized"); return SD_ERR_STATE; }
+    if (n < 1 || H < 1 || W < 1) { set_error("sd_op_controlnet_cond_embed: bad shape"); return SD_ERR_INVALID; }
+    const int C0 = cn->impl.cfg.block_out_channels[0];
+    return run_op_on_arena(static_cast<hipStream_t>(stream), iters, ms_per_launch, [&](Ctx& c) {
+        cn->impl.run_cond_embed(c, static_cast<const half_t*>(image), n, H, W, View(static_cast<half_t*>(out), C0, C0));
+    });
 }
 
 }  // extern "C"

@@ -181,6 +181,45 @@ bool ip_attention_supported(int d);
 int launch_axpy_f16(half_t* y, long ldy, const half_t* x, long ldx, long rows, int cols, float a, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------
+// ControlNet (controlnet.hip)
+// ---------------------------------------------------------------------------------------------
+// Grouped zero-convs: for every problem i, y_i[m, :C] = fp16(y_i[m, :C] + scale (x_i[m, :] W_i^T + b_i)), one launch.
+// W_i packed [>= C rows][C] (WeightStore::pack_conv of a 1x1 conv), bias fp32 (16-byte aligned), x / y NHWC views with
+// their own row strides (ldx % 8 == 0, ldy % 4 == 0); y's columns past C are not touched.  C % 64 == 0, any M >= 1.
+// first = the problem's first tile in the joint list (cn_residual_tiles of the ones before it), total = all tiles.
+// scale == 0 launches nothing.
+constexpr int kCnMaxProblems = 16;
+struct CnResProblem {
+    const half_t* x = nullptr; long ldx = 0;
+    const half_t* w = nullptr;
+    const float* bias = nullptr;
+    half_t* y = nullptr; long ldy = 0;
+    int M = 0, C = 0;
+    int first = 0;
+};
+struct CnResParams {
+    CnResProblem p[kCnMaxProblems];
+    int count = 0, total = 0;
+    float scale = 1.f;
+};
+int cn_residual_tiles(int M, int C);
+bool cn_residual_supported(const CnResParams& p);
+int launch_cn_residual(const CnResParams& p, hipStream_t s);
+// One layer of ControlNetConditioningEmbedding: y = act(conv3x3(x) + bias), stride 1 or 2, pad 1.  x NCHW fp16 with
+// Cin = 3 (nchw = 1: the control image) or NHWC fp16 with Cin in {16, 32, 96}; y NHWC fp16 [N, OH, OW, Cout],
+// Cout % 16 == 0; w from launch_cn_pack_cond, bias fp32 [Cout]; silu = 1 applies SiLU.
+struct CnCondConvParams {
+    const half_t* x = nullptr; int nchw = 0;
+    const float* w = nullptr; const float* bias = nullptr;
+    half_t* y = nullptr;
+    int N = 0, IH = 0, IW = 0, Cin = 0, OH = 0, OW = 0, Cout = 0, stride = 1, silu = 1;
+};
+bool cn_cond_conv_supported(const CnCondConvParams& p);
+int launch_cn_cond_conv(const CnCondConvParams& p, hipStream_t s);
+// OIHW fp16 [O][I][3][3] -> [O / 16][3][3][I][16] fp32 (the weight layout cn_cond_conv_kernel reads)
+int launch_cn_pack_cond(const half_t* w_oihw, float* out, int O, int I, hipStream_t s);
+
+// ---------------------------------------------------------------------------------------------
 // Small / elementwise kernels (misc.hip)
 // ---------------------------------------------------------------------------------------------
 // out[b, :] = [cos(t_b f_i) | sin(t_b f_i)] (flip) or [sin | cos]; f_i = exp(-ln(1e4) i/(half-shift))

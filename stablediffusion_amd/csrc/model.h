@@ -3,6 +3,8 @@
 #include "../../include/sd_engine.h"
 #include "engine.h"
 
+#include <functional>
+
 namespace sd {
 
 const std::string& last_error();
@@ -73,19 +75,88 @@ struct IPAdapter {
     UNet* attached = nullptr;           // the UNet it is attached to (sd_unet_set_ip_adapter), if any
 };
 
-struct UNet {
+// conv_in, time / add embedding, down path and mid block of a UNet2DConditionModel topology: the part a UNet and a
+// ControlNet (its encoder copy) share -- weight declaration, packing and the forward pieces.
+struct Encoder {
+    explicit Encoder(const sd_unet_config& c) : cfg(c) {}
+
+    sd_unet_config cfg;
+    WeightStore ws;
+    ConvW conv_in, te1, te2, ae1, ae2, temb_stack;
+    ConvW kv_all;                       // every attn2.to_k / to_v of the model, row-concatenated
+    std::vector<std::string> kv_keys;   // (finalize only)
+    std::vector<std::vector<Resnet>> down_res;
+    std::vector<std::vector<Xformer>> down_att;
+    std::vector<ConvW> down_ds;
+    Resnet mid_r0, mid_r1;
+    Xformer mid_att;
+    int temb_total = 0;
+    int kv_total = 0;
+
+    // Skip tensors the down path produces, in order: conv_in's output, every down resnet / transformer output, every
+    // downsampler output (the residual sites of a ControlNet, the skips of a UNet).
+    int num_skips() const;
+    // where skip `si` goes and which GroupNorm-summary buffer its producer fills (nullptr: a ring slot or none)
+    using SkipDst = std::function<View(int si)>;
+    using SkipStat = std::function<GnStatBuf*(int si, long HW, int C)>;
+
+  protected:
+    void declare_encoder();
+    int pack_encoder(std::vector<std::string>* tw, std::vector<std::string>* tb);
+    int pack_resnet(const std::string& p, Resnet* r, std::vector<std::string>* tw, std::vector<std::string>* tb);
+    int pack_xformer(const std::string& p, Xformer* x, int heads, int depth);
+    // time (+ text_time) embedding -> every resnet's time_emb_proj(silu(emb)) in one GEMV: [B, temb_total] fp32
+    int run_temb(Ctx& c, const float* timesteps, const half_t* add_text, const float* add_time_ids, int B, float** tproj);
+    // conv_in into y0: straight from the NCHW latents when the edge kernel takes it and there is no residual, else
+    // im2col + GEMM with `res` added in its epilogue.  *xs = the GroupNorm summaries of y0 it left (or nullptr).
+    void run_conv_in(Ctx& c, const half_t* sample, int B, int H, int W, View y0, GnStatBuf* gb, const View* res,
+                     GnStatBuf** xs);
+    // down path from x = skip 0 (summaries xs) at h x w: writes skips 1.. through dst / stat, returns the last one
+    View run_down(Ctx& c, View x, GnStatBuf*& xs, int B, int& h, int& w, View text_kv, int L, const float* tproj,
+                  const SkipDst& dst, const SkipStat& stat);
+    void run_mid(Ctx& c, View x, GnStatBuf* xs, int B, int h, int w, View text_kv, int L, const float* tproj, View dst);
+};
+
+// ControlNet (diffusers 0.27.2 ControlNetModel): its own encoder copy of the UNet topology, the conditioning
+// embedding of the control image, and one zero-conv (1x1, C -> C) per skip plus one for the mid block.
+struct ControlNet : Encoder {
+    ControlNet(const sd_unet_config& c, int conditioning_channels);
+    ~ControlNet();
+    int finalize();
+
+    int cond_channels = 3;
+    bool finalized = false;
+    static constexpr int kCondLayers = 7;          // conv_in, blocks.0-5 (3x3, SiLU after each)
+    float* cond_w[kCondLayers] = {};                // [Cout / 16][9 Cin][16] fp32 (launch_cn_pack_cond)
+    float* cond_b[kCondLayers] = {};                // [Cout] fp32
+    int cond_cin[kCondLayers] = {}, cond_cout[kCondLayers] = {}, cond_stride[kCondLayers] = {};
+    ConvW cond_out;                                 // 256 -> block_out_channels[0], 3x3, through igemm2
+    std::vector<ConvW> zero;                        // controlnet_down_blocks.i, one per skip
+    ConvW zero_mid;                                 // controlnet_mid_block
+    UNet* attached = nullptr;
+
+    // the conditioning embedding of n control images [n, cond_channels, 8H, 8W] f16 into out [n H W, C0] (NHWC)
+    void run_cond_embed(Ctx& c, const half_t* image, int n, int H, int W, View out);
+    // the encoder on (sample, timestep, text) with emb added after conv_in: the pre-zero-conv hidden tensors of every
+    // skip (sites[i]) and of the mid block (mid), all [B h w, C] in the arena
+    int run(Ctx& c, const half_t* sample, const float* timesteps, View text_kv, int L, const half_t* add_text,
+            const float* add_time_ids, int B, int H, int W, View emb, const std::vector<View>& sites, View mid);
+};
+
+struct UNet : Encoder {
     explicit UNet(const sd_unet_config& c);
     int finalize();
     int forward(const half_t* sample, const float* timesteps, const half_t* ehs, int L,
                 const half_t* add_text, const float* add_time_ids, half_t* out, int B, int H, int W,
-                hipStream_t stream, const half_t* image_embeds = nullptr, int n_img = 0);
+                hipStream_t stream, const half_t* image_embeds = nullptr, int n_img = 0,
+                const half_t* control = nullptr, int n_ctrl = 0, float cn_scale = 0.f);
     void set_ip_adapter(IPAdapter* a);
+    void set_controlnet(ControlNet* n);
 
-    sd_unet_config cfg;
-    WeightStore ws;
     Arena arena;
     bool finalized = false;
     long planned_key = -1;
+    long planned_cn = -1;
 
     // ---- optional hipGraph replay of the whole forward (sd_unet_use_graph) ----
     // One captured graph per input shape; inputs / output are staged through engine-owned buffers so
@@ -124,24 +195,36 @@ struct UNet {
     const half_t* ipkv_src = nullptr;
     int ipkv_B = 0, ipkv_n = 0;
 
-    ConvW conv_in, conv_out, te1, te2, ae1, ae2, temb_stack;
-    ConvW kv_all;                       // every attn2.to_k / to_v of the model, row-concatenated
-    std::vector<std::string> kv_keys;   // (finalize only)
+    // ---- ControlNet (sd_unet_set_controlnet): nullptr = the forward as without the feature.  Its conditioning
+    // embedding ([B H W, C0], sample b from control image b mod n_ctrl) and its text K / V follow the text K / V's cache
+    // rules: kept across the forwards of one loop for one (pointer, B, n_ctrl, H, W) / (pointer, B, L), invalidated by
+    // every sd_unet_text_kv_cache call and by set_controlnet, not under graphs.
+    ControlNet* cn = nullptr;
+    bool cond_valid = false, cnkv_valid = false;
+    half_t* cond_cache = nullptr;
+    size_t cond_cap = 0;
+    const half_t* cond_src = nullptr;
+    int cond_B = 0, cond_n = 0, cond_H = 0, cond_W = 0;
+    half_t* cnkv_cache = nullptr;
+    size_t cnkv_cap = 0;
+    const half_t* cnkv_src = nullptr;
+    int cnkv_B = 0, cnkv_L = 0;
+
+    ConvW conv_out;
     NormW norm_out;
-    std::vector<std::vector<Resnet>> down_res, up_res;
-    std::vector<std::vector<Xformer>> down_att, up_att;
-    std::vector<ConvW> down_ds, up_us;
-    Resnet mid_r0, mid_r1;
-    Xformer mid_att;
-    int temb_total = 0;
-    int kv_total = 0;
+    std::vector<std::vector<Resnet>> up_res;
+    std::vector<std::vector<Xformer>> up_att;
+    std::vector<ConvW> up_us;
 
   private:
-    int pack_resnet(const std::string& p, Resnet* r, std::vector<std::string>* tw, std::vector<std::string>* tb);
-    int pack_xformer(const std::string& p, Xformer* x, int heads, int depth);
     int run(Ctx& c, const half_t* sample, const float* timesteps, const half_t* ehs, int L,
             const half_t* add_text, const float* add_time_ids, half_t* out, int B, int H, int W,
-            const half_t* image_embeds = nullptr, int n_img = 0);
+            const half_t* image_embeds = nullptr, int n_img = 0, const half_t* control = nullptr, int n_ctrl = 0,
+            float cn_scale = 0.f);
+    // ControlNet step of run(): its hidden tensors into sites / mid (allocated by the caller)
+    int run_controlnet(Ctx& c, const half_t* sample, const float* timesteps, const half_t* ehs, int L,
+                       const half_t* add_text, const float* add_time_ids, int B, int H, int W, const half_t* control,
+                       int n_ctrl, const std::vector<View>& sites, View mid);
 };
 
 struct VAE {

@@ -6,6 +6,7 @@
 // NHWC fp16 activations, skip connections written straight into the concatenation buffers of the
 // up path (no torch.cat copies), fused qkv / GEGLU / residual / time-embedding epilogues, one
 // stacked GEMV for all 22 time_emb_proj layers, and a stack-discipline workspace arena.
+#include <algorithm>
 #include <vector>
 
 #include "model.h"
@@ -69,7 +70,7 @@ void declare_xformer(WeightStore& ws, const std::string& p, int c, int depth, in
 
 }  // namespace
 
-UNet::UNet(const sd_unet_config& c) : cfg(c) {
+void Encoder::declare_encoder() {
     const int nb = cfg.num_blocks;
     const int* boc = cfg.block_out_channels;
     const int temb = boc[0] * 4;
@@ -106,6 +107,16 @@ UNet::UNet(const sd_unet_config& c) : cfg(c) {
     declare_resnet(ws, "mid_block.resnets.0", mid, mid, temb);
     declare_xformer(ws, "mid_block.attentions.0", mid, cfg.transformer_layers[nb - 1], ctx, lin);
     declare_resnet(ws, "mid_block.resnets.1", mid, mid, temb);
+}
+
+UNet::UNet(const sd_unet_config& c) : Encoder(c) {
+    declare_encoder();
+    const int nb = cfg.num_blocks;
+    const int* boc = cfg.block_out_channels;
+    const int temb = boc[0] * 4;
+    const int ctx = cfg.cross_attention_dim;
+    const bool lin = cfg.use_linear_projection != 0;
+    int out_ch;
     out_ch = boc[nb - 1];
     for (int i = 0; i < nb; ++i) {
         const int prev = out_ch;
@@ -131,7 +142,7 @@ UNet::UNet(const sd_unet_config& c) : cfg(c) {
     ws.declare("conv_out.bias", {cfg.out_channels});
 }
 
-int UNet::pack_resnet(const std::string& p, Resnet* r, std::vector<std::string>* tw, std::vector<std::string>* tb) {
+int Encoder::pack_resnet(const std::string& p, Resnet* r, std::vector<std::string>* tw, std::vector<std::string>* tb) {
     int rc;
     if ((rc = ws.pack_norm(p + ".norm1", &r->n1))) return rc;
     if ((rc = ws.pack_conv(p + ".conv1", &r->c1))) return rc;
@@ -149,7 +160,7 @@ int UNet::pack_resnet(const std::string& p, Resnet* r, std::vector<std::string>*
     return 0;
 }
 
-int UNet::pack_xformer(const std::string& p, Xformer* x, int heads, int depth) {
+int Encoder::pack_xformer(const std::string& p, Xformer* x, int heads, int depth) {
     int rc;
     if ((rc = ws.pack_norm(p + ".norm", &x->gn))) return rc;
     if ((rc = ws.pack_conv(p + ".proj_in", &x->pin))) return rc;
@@ -198,6 +209,35 @@ int UNet::pack_xformer(const std::string& p, Xformer* x, int heads, int depth) {
     return 0;
 }
 
+int Encoder::pack_encoder(std::vector<std::string>* tw, std::vector<std::string>* tb) {
+    const int nb = cfg.num_blocks;
+    int rc;
+    if ((rc = ws.pack_conv("conv_in", &conv_in))) return rc;
+    if ((rc = ws.pack_conv("time_embedding.linear_1", &te1))) return rc;
+    if ((rc = ws.pack_conv("time_embedding.linear_2", &te2))) return rc;
+    if (cfg.addition_time_embed_dim > 0) {
+        if ((rc = ws.pack_conv("add_embedding.linear_1", &ae1))) return rc;
+        if ((rc = ws.pack_conv("add_embedding.linear_2", &ae2))) return rc;
+    }
+    down_res.assign((size_t)nb, {}); down_att.assign((size_t)nb, {}); down_ds.assign((size_t)nb, ConvW());
+    for (int i = 0; i < nb; ++i) {
+        const std::string p = "down_blocks." + std::to_string(i);
+        down_res[i].resize((size_t)cfg.layers_per_block);
+        if (cfg.down_block_has_attn[i]) down_att[i].resize((size_t)cfg.layers_per_block);
+        for (int j = 0; j < cfg.layers_per_block; ++j) {
+            if ((rc = pack_resnet(p + ".resnets." + std::to_string(j), &down_res[i][j], tw, tb))) return rc;
+            if (cfg.down_block_has_attn[i] &&
+                (rc = pack_xformer(p + ".attentions." + std::to_string(j), &down_att[i][j], cfg.num_heads[i],
+                                   cfg.transformer_layers[i]))) return rc;
+        }
+        if (i != nb - 1 && (rc = ws.pack_conv(p + ".downsamplers.0.conv", &down_ds[i]))) return rc;
+    }
+    if ((rc = pack_resnet("mid_block.resnets.0", &mid_r0, tw, tb))) return rc;
+    if ((rc = pack_xformer("mid_block.attentions.0", &mid_att, cfg.num_heads[nb - 1], cfg.transformer_layers[nb - 1]))) return rc;
+    if ((rc = pack_resnet("mid_block.resnets.1", &mid_r1, tw, tb))) return rc;
+    return 0;
+}
+
 int UNet::finalize() {
     if (finalized) return 0;
     std::string missing;
@@ -208,30 +248,8 @@ int UNet::finalize() {
     temb_total = 0;
     kv_total = 0;
     kv_keys.clear();
-    if ((rc = ws.pack_conv("conv_in", &conv_in))) return rc;
-    if ((rc = ws.pack_conv("time_embedding.linear_1", &te1))) return rc;
-    if ((rc = ws.pack_conv("time_embedding.linear_2", &te2))) return rc;
-    if (cfg.addition_time_embed_dim > 0) {
-        if ((rc = ws.pack_conv("add_embedding.linear_1", &ae1))) return rc;
-        if ((rc = ws.pack_conv("add_embedding.linear_2", &ae2))) return rc;
-    }
-    down_res.assign((size_t)nb, {}); down_att.assign((size_t)nb, {}); down_ds.assign((size_t)nb, ConvW());
+    if ((rc = pack_encoder(&tw, &tb))) return rc;
     up_res.assign((size_t)nb, {}); up_att.assign((size_t)nb, {}); up_us.assign((size_t)nb, ConvW());
-    for (int i = 0; i < nb; ++i) {
-        const std::string p = "down_blocks." + std::to_string(i);
-        down_res[i].resize((size_t)cfg.layers_per_block);
-        if (cfg.down_block_has_attn[i]) down_att[i].resize((size_t)cfg.layers_per_block);
-        for (int j = 0; j < cfg.layers_per_block; ++j) {
-            if ((rc = pack_resnet(p + ".resnets." + std::to_string(j), &down_res[i][j], &tw, &tb))) return rc;
-            if (cfg.down_block_has_attn[i] &&
-                (rc = pack_xformer(p + ".attentions." + std::to_string(j), &down_att[i][j], cfg.num_heads[i],
-                                   cfg.transformer_layers[i]))) return rc;
-        }
-        if (i != nb - 1 && (rc = ws.pack_conv(p + ".downsamplers.0.conv", &down_ds[i]))) return rc;
-    }
-    if ((rc = pack_resnet("mid_block.resnets.0", &mid_r0, &tw, &tb))) return rc;
-    if ((rc = pack_xformer("mid_block.attentions.0", &mid_att, cfg.num_heads[nb - 1], cfg.transformer_layers[nb - 1]))) return rc;
-    if ((rc = pack_resnet("mid_block.resnets.1", &mid_r1, &tw, &tb))) return rc;
     for (int i = 0; i < nb; ++i) {
         const std::string p = "up_blocks." + std::to_string(i);
         up_res[i].resize((size_t)cfg.layers_per_block + 1);
@@ -447,23 +465,19 @@ void run_xformer(Ctx& c, const Xformer& t, View x, int N, int H, int W, View out
 }
 
 // ----------------------------------------------------------------------------------------- forward
-int UNet::run(Ctx& c, const half_t* sample, const float* timesteps, const half_t* ehs, int L,
-              const half_t* add_text, const float* add_time_ids, half_t* out, int B, int H, int W,
-              const half_t* image_embeds, int n_img) {
+int Encoder::run_temb(Ctx& c, const float* timesteps, const half_t* add_text, const float* add_time_ids, int B,
+                      float** tproj_out) {
     Arena& a = *c.arena;
-    const int nb = cfg.num_blocks;
     const int* boc = cfg.block_out_channels;
-    const int G = cfg.norm_num_groups;
-    const float eps = cfg.norm_eps;
     const int temb = boc[0] * 4;
     hipStream_t s = c.stream;
     const bool go = !c.dry;
-
     // ---- time embedding (fp32, batch-sized GEMVs) ----
     float* sinus = a.alloc_f((long)B * boc[0]);
     float* e1 = a.alloc_f((long)B * temb);
     float* emb = a.alloc_f((long)B * temb);
     float* tproj = a.alloc_f((long)B * temb_total);
+    *tproj_out = tproj;
     if (go && !c.err) c.err = launch_timestep_sinusoid(timesteps, 1, sinus, B, boc[0], cfg.flip_sin_to_cos, cfg.freq_shift, boc[0], s);
     if (go && !c.err) c.err = launch_small_linear(sinus, boc[0], te1.w, te1.bias, e1, temb, B, boc[0], temb, 0, 1, s);
     // (without text_time conditioning the SiLU every resnet applies to the embedding rides on this launch)
@@ -497,6 +511,119 @@ int UNet::run(Ctx& c, const half_t* sample, const float* timesteps, const half_t
     // every resnet consumes the embedding only as time_emb_proj(silu(emb)): the SiLU is applied once
     // here instead of inside the weight-bandwidth-bound stacked GEMV
     if (go && !c.err) c.err = launch_small_linear(emb, temb, temb_stack.w, temb_stack.bias, tproj, temb_total, B, temb, temb_total, 0, 0, s);
+
+    return c.err;
+}
+
+void Encoder::run_conv_in(Ctx& c, const half_t* sample, int B, int H, int W, View y0, GnStatBuf* gb, const View* res,
+                          GnStatBuf** xs) {
+    Arena& a = *c.arena;
+    const int* boc = cfg.block_out_channels;
+    const int G = cfg.norm_num_groups;
+    hipStream_t s = c.stream;
+    const bool go = !c.dry;
+    const size_t mk = a.mark();
+    const long M = (long)B * H * W;
+    HeadParams hp;
+    hp.x_nchw = sample; hp.w = conv_in.w; hp.K = conv_in.K; hp.bias = conv_in.bias; hp.y = y0.p; hp.ldy = y0.ld;
+    hp.gnstat_out = (gb && gb->buf) ? gb->buf : nullptr; hp.G = G;
+    hp.N = B; hp.Cin = cfg.in_channels; hp.H = H; hp.W = W; hp.Cout = boc[0];
+    if (!res && conv_head_supported(hp)) {
+        if (gb) {
+            gb->st = GnStats();
+            if (hp.gnstat_out) { gb->st.part = gb->buf; gb->st.rows = 128; gb->st.S = (int)((long)H * W / 128); }
+        }
+        if (go && !c.err) {
+            prof_open(s, "conv_head_kernel", 2.0 * M * boc[0] * 9.0 * cfg.in_channels, 2.0 * M * (boc[0] + cfg.in_channels));
+            c.err = launch_conv_head(hp, s);
+            prof_close(s);
+        }
+        *xs = gb;
+    } else {
+        half_t* col = a.alloc_h(M * conv_in.K);
+        if (go && !c.err) c.err = launch_im2col_nchw3x3(sample, col, B, cfg.in_channels, H, W, (int)conv_in.K, s);
+        ConvW pw = conv_in; pw.ks = 1;
+        ConvFuse f;
+        f.gn_out = gb;
+        f.gn_groups = G;
+        op_conv(c, pw, View(col, conv_in.K, (int)conv_in.K), B, H, W, y0, 1, 0, nullptr, 0, res, 0, -1, 0, &f);
+        *xs = f.gn_out;
+    }
+    a.release(mk);
+}
+
+View Encoder::run_down(Ctx& c, View x, GnStatBuf*& xs, int B, int& h, int& w, View text_kv, int L, const float* tproj,
+                       const SkipDst& skip_view, const SkipStat& skip_stat) {
+    Arena& a = *c.arena;
+    const int nb = cfg.num_blocks;
+    const int G = cfg.norm_num_groups;
+    const float eps = cfg.norm_eps;
+    int skip_i = 1;
+    for (int i = 0; i < nb; ++i) {
+        for (int j = 0; j < cfg.layers_per_block; ++j) {
+            const Resnet& r = down_res[i][j];
+            if (cfg.down_block_has_attn[i]) {
+                const size_t mk = a.mark();
+                View tmp(a.alloc_h((long)B * h * w * r.cout), r.cout, r.cout);
+                GnStatBuf* rs = nullptr;
+                run_resnet(c, r, x, B, h, w, tmp, G, eps, tproj, temb_total, xs, &rs);
+                View dst = skip_view(skip_i);
+                run_xformer(c, down_att[i][j], tmp, B, h, w, dst, G, text_kv, L, rs, &xs, skip_stat(skip_i, (long)h * w, r.cout));
+                a.release(mk);
+                x = dst;
+            } else {
+                View dst = skip_view(skip_i);
+                run_resnet(c, r, x, B, h, w, dst, G, eps, tproj, temb_total, xs, &xs, 1.f, skip_stat(skip_i, (long)h * w, r.cout));
+                x = dst;
+            }
+            ++skip_i;
+        }
+        if (i != nb - 1) {
+            ConvFuse f;
+            f.gn_out = skip_stat(skip_i, (long)(h / 2) * (w / 2), down_ds[i].cout);
+            View dst = skip_view(skip_i++);
+            f.gn_groups = G;
+            op_conv(c, down_ds[i], x, B, h, w, dst, 2, 0, nullptr, 0, nullptr, 0, -1, 0, &f);
+            xs = f.gn_out;
+            h /= 2; w /= 2;
+            x = dst;
+        }
+    }
+
+    return x;
+}
+
+void Encoder::run_mid(Ctx& c, View x, GnStatBuf* xs, int B, int h, int w, View text_kv, int L, const float* tproj,
+                      View dst) {
+    Arena& a = *c.arena;
+    const int nb = cfg.num_blocks;
+    const int* boc = cfg.block_out_channels;
+    const int G = cfg.norm_num_groups;
+    const float eps = cfg.norm_eps;
+    const int C = boc[nb - 1];
+    const long M = (long)B * h * w;
+    View m0(a.alloc_h(M * C), C, C), m1(a.alloc_h(M * C), C, C);
+    GnStatBuf *s0 = nullptr, *s1 = nullptr;
+    run_resnet(c, mid_r0, x, B, h, w, m0, G, eps, tproj, temb_total, xs, &s0);
+    run_xformer(c, mid_att, m0, B, h, w, m1, G, text_kv, L, s0, &s1);
+    run_resnet(c, mid_r1, m1, B, h, w, dst, G, eps, tproj, temb_total, s1);   // output joins a concat: no consumer
+}
+
+int Encoder::num_skips() const { return 1 + cfg.num_blocks * cfg.layers_per_block + (cfg.num_blocks - 1); }
+
+int UNet::run(Ctx& c, const half_t* sample, const float* timesteps, const half_t* ehs, int L,
+              const half_t* add_text, const float* add_time_ids, half_t* out, int B, int H, int W,
+              const half_t* image_embeds, int n_img, const half_t* control, int n_ctrl, float cn_scale) {
+    Arena& a = *c.arena;
+    const int nb = cfg.num_blocks;
+    const int* boc = cfg.block_out_channels;
+    const int G = cfg.norm_num_groups;
+    const float eps = cfg.norm_eps;
+    hipStream_t s = c.stream;
+    const bool go = !c.dry;
+
+    float* tproj = nullptr;
+    if (int rc = run_temb(c, timesteps, add_text, add_time_ids, B, &tproj)) return rc;
 
     // ---- text K/V of every cross-attention block in one GEMM: [B*L, ctx] x [ctx, sum 2C] ----
     const bool kv_cached = kv_cache_on && !graph_enabled && kv_cache != nullptr;
@@ -588,87 +715,65 @@ int UNet::run(Ctx& c, const half_t* sample, const float* timesteps, const half_t
         return (sst[(size_t)si].buf && gn_wants_stats(HWs, C, G)) ? &sst[(size_t)si] : nullptr;
     };
 
+    // ---- ControlNet: its encoder on the same sample, timestep and text.  The pre-zero-conv hidden tensors of every
+    //      skip and of the mid block live above the concatenation buffers (released after the residual adds); the
+    //      ControlNet runs on a GroupNorm ring of its own, this forward's ring is restored after it ----
+    const bool use_cn = cn && control && cn_scale != 0.f;
+    const size_t cn_mark = a.mark();
+    std::vector<View> cn_sites;
+    std::vector<int> cn_rows;
+    View cn_mid;
+    if (use_cn) {
+        int hh = H, ww = W;
+        auto site = [&](int C) {
+            cn_sites.emplace_back(a.alloc_h((long)B * hh * ww * C), C, C);
+            cn_rows.push_back(B * hh * ww);
+        };
+        site(boc[0]);
+        for (int i = 0; i < nb; ++i) {
+            for (int j = 0; j < cfg.layers_per_block; ++j) site(boc[i]);
+            if (i != nb - 1) { hh /= 2; ww /= 2; site(boc[i]); }
+        }
+        cn_mid = View(a.alloc_h((long)B * hh * ww * boc[nb - 1]), boc[nb - 1], boc[nb - 1]);
+        cn_rows.push_back(B * hh * ww);
+        GnStatBuf ring[Ctx::kGnPool];
+        for (int i = 0; i < Ctx::kGnPool; ++i) ring[i] = c.gnpool[i];
+        const int ring_next = c.gn_next, ring_groups = c.gn_groups;
+        if (int rc = run_controlnet(c, sample, timesteps, ehs, L, add_text, add_time_ids, B, H, W, control, n_ctrl, cn_sites,
+                                    cn_mid)) return rc;
+        for (int i = 0; i < Ctx::kGnPool; ++i) c.gnpool[i] = ring[i];
+        c.gn_next = ring_next; c.gn_groups = ring_groups;
+    }
+
     // ---- conv_in: one launch straight from the NCHW latents (edge.hip); otherwise (inpainting's 9 channels, odd maps)
     //      im2col into a 64-wide K, then the GEMM kernel ----
     int h = H, w = W;
-    {
-        const size_t mk = a.mark();
-        const long M = (long)B * H * W;
-        GnStatBuf* gb = skip_stat(skip_i, (long)H * W, boc[0]);
-        const View y0 = skip_view(skip_i);
-        HeadParams hp;
-        hp.x_nchw = sample; hp.w = conv_in.w; hp.K = conv_in.K; hp.bias = conv_in.bias; hp.y = y0.p; hp.ldy = y0.ld;
-        hp.gnstat_out = (gb && gb->buf) ? gb->buf : nullptr; hp.G = G;
-        hp.N = B; hp.Cin = cfg.in_channels; hp.H = H; hp.W = W; hp.Cout = boc[0];
-        if (conv_head_supported(hp)) {
-            if (gb) {
-                gb->st = GnStats();
-                if (hp.gnstat_out) { gb->st.part = gb->buf; gb->st.rows = 128; gb->st.S = (int)((long)H * W / 128); }
-            }
-            if (go && !c.err) {
-                prof_open(s, "conv_head_kernel", 2.0 * M * boc[0] * 9.0 * cfg.in_channels, 2.0 * M * (boc[0] + cfg.in_channels));
-                c.err = launch_conv_head(hp, s);
-                prof_close(s);
-            }
-            xs = gb;
-        } else {
-            half_t* col = a.alloc_h(M * conv_in.K);
-            if (go && !c.err) c.err = launch_im2col_nchw3x3(sample, col, B, cfg.in_channels, H, W, (int)conv_in.K, s);
-            ConvW pw = conv_in; pw.ks = 1;
-            ConvFuse f;
-            f.gn_out = gb;
-            f.gn_groups = G;
-            op_conv(c, pw, View(col, conv_in.K, (int)conv_in.K), B, H, W, y0, 1, 0, nullptr, 0, nullptr, 0, -1, 0, &f);
-            xs = f.gn_out;
-        }
-        a.release(mk);
-    }
+    run_conv_in(c, sample, B, H, W, skip_view(skip_i), skip_stat(skip_i, (long)H * W, boc[0]), nullptr, &xs);
     View x = skip_view(skip_i++);
 
     // ---- down path ----
-    for (int i = 0; i < nb; ++i) {
-        for (int j = 0; j < cfg.layers_per_block; ++j) {
-            const Resnet& r = down_res[i][j];
-            if (cfg.down_block_has_attn[i]) {
-                const size_t mk = a.mark();
-                View tmp(a.alloc_h((long)B * h * w * r.cout), r.cout, r.cout);
-                GnStatBuf* rs = nullptr;
-                run_resnet(c, r, x, B, h, w, tmp, G, eps, tproj, temb_total, xs, &rs);
-                View dst = skip_view(skip_i);
-                run_xformer(c, down_att[i][j], tmp, B, h, w, dst, G, text_kv, L, rs, &xs, skip_stat(skip_i, (long)h * w, r.cout));
-                a.release(mk);
-                x = dst;
-            } else {
-                View dst = skip_view(skip_i);
-                run_resnet(c, r, x, B, h, w, dst, G, eps, tproj, temb_total, xs, &xs, 1.f, skip_stat(skip_i, (long)h * w, r.cout));
-                x = dst;
-            }
-            ++skip_i;
-        }
-        if (i != nb - 1) {
-            ConvFuse f;
-            f.gn_out = skip_stat(skip_i, (long)(h / 2) * (w / 2), down_ds[i].cout);
-            View dst = skip_view(skip_i++);
-            f.gn_groups = G;
-            op_conv(c, down_ds[i], x, B, h, w, dst, 2, 0, nullptr, 0, nullptr, 0, -1, 0, &f);
-            xs = f.gn_out;
-            h /= 2; w /= 2;
-            x = dst;
-        }
-    }
+    x = run_down(c, x, xs, B, h, w, text_kv, L, tproj, [&](int si) { return skip_view(si); },
+                 [&](int si, long HWs, int C) { return skip_stat(si, HWs, C); });
 
     // ---- mid block ----
-    {
-        const int C = boc[nb - 1];
-        const long M = (long)B * h * w;
-        View m0(a.alloc_h(M * C), C, C), m1(a.alloc_h(M * C), C, C);
-        GnStatBuf *s0 = nullptr, *s1 = nullptr;
-        run_resnet(c, mid_r0, x, B, h, w, m0, G, eps, tproj, temb_total, xs, &s0);
-        run_xformer(c, mid_att, m0, B, h, w, m1, G, text_kv, L, s0, &s1);
-        const Cat& ct = cats[0];
-        View dst(ct.p, ct.c1 + ct.c2, ct.c1);
-        run_resnet(c, mid_r1, m1, B, h, w, dst, G, eps, tproj, temb_total, s1);   // output joins a concat: no consumer
+    run_mid(c, x, xs, B, h, w, text_kv, L, tproj, View(cats[0].p, cats[0].c1 + cats[0].c2, cats[0].c1));
+
+    // ---- ControlNet residuals: skip_i += s (h_i W_i^T + b_i) in the skip half of every concatenation and
+    //      mid += s (h_mid W_mid^T + b_mid) in the hidden half of the first, one GEMM per site with the scale and the
+    //      residual in its epilogue.  After the mid block: the skips were the down path's inputs too, and diffusers adds
+    //      the residuals only to what the up path reads.  (The grouped cn_residual_kernel is slower than these launches
+    //      today: DESIGN.md §4.)  Then the ControlNet's tensors and the mid block's temporaries are dead. ----
+    if (use_cn) {
+        ConvFuse f;
+        f.acc_scale = cn_scale; f.bias_scale = cn_scale;
+        for (int si = 0; si <= nskip; ++si) {
+            const View xh = si < nskip ? cn_sites[(size_t)si] : cn_mid;
+            const View y = si < nskip ? skip_view(si) : View(cats[0].p, cats[0].c1 + cats[0].c2, cats[0].c1);
+            const ConvW& zw = si < nskip ? cn->zero[(size_t)si] : cn->zero_mid;
+            op_conv(c, zw, xh, 1, cn_rows[(size_t)si], 1, y, 1, 0, nullptr, 0, &y, 0, -1, 0, &f);
+        }
     }
+    if (use_cn) a.release(cn_mark);
 
     // ---- up path ----
     View final_x;
@@ -680,7 +785,9 @@ int UNet::run(Ctx& c, const half_t* sample, const float* timesteps, const half_t
     // profiles/r03_groupnorm_apply.txt); every concatenation's norm1 then runs its own statistics pass.
     const GnStatBuf* hid_ready = nullptr;
     int hid_groups = 0;
-    static const bool no_cat_stats = getenv("SD_GN_CAT") == nullptr;
+    // (with a ControlNet the skips' summaries predate the residual add: norm1 always runs its own statistics pass)
+    static const bool no_cat_env = getenv("SD_GN_CAT") == nullptr;
+    const bool no_cat_stats = no_cat_env || use_cn;
     for (int i = 0; i < nb; ++i) {
         for (int j = 0; j < cfg.layers_per_block + 1; ++j, ++k) {
             const Cat& ct = cats[(size_t)k];
@@ -805,7 +912,10 @@ UNet::~UNet() {
     if (io_slab) (void)hipFree(io_slab);
     if (kv_cache) (void)hipFree(kv_cache);
     if (ipkv_cache) (void)hipFree(ipkv_cache);
+    if (cond_cache) (void)hipFree(cond_cache);
+    if (cnkv_cache) (void)hipFree(cnkv_cache);
     if (ip) ip->attached = nullptr;
+    if (cn) cn->attached = nullptr;
 }
 
 // Graph path: stage I/O through engine-owned buffers, capture the forward once per shape on an
@@ -883,7 +993,7 @@ int UNet::forward_graph(const half_t* sample, const float* timesteps, const half
 
 int UNet::forward(const half_t* sample, const float* timesteps, const half_t* ehs, int L, const half_t* add_text,
                   const float* add_time_ids, half_t* out, int B, int H, int W, hipStream_t stream,
-                  const half_t* image_embeds, int n_img) {
+                  const half_t* image_embeds, int n_img, const half_t* control, int n_ctrl, float cn_scale) {
     if (!finalized) { set_error("unet: forward before finalize"); return 2; }
     const int div = 1 << (cfg.num_blocks - 1);
     if (B <= 0 || H % div != 0 || W % div != 0) { set_error("unet: H and W must be divisible by 2^(blocks-1)"); return 1; }
@@ -896,6 +1006,17 @@ int UNet::forward(const half_t* sample, const float* timesteps, const half_t* eh
     } else {
         n_img = 0;
     }
+    if (cn && !control) { set_error("unet: a ControlNet is attached: control image required"); return 1; }
+    if (!cn && control) { set_error("unet: control image given but no ControlNet is attached"); return 1; }
+    if (cn) {
+        if (n_ctrl < 1 || B % n_ctrl != 0) { set_error("unet: the control image count must divide the batch"); return 1; }
+        if (!(cn_scale == cn_scale)) { set_error("unet: conditioning scale is NaN"); return 1; }
+        if (graph_enabled) { set_error("unet: graph replay with a ControlNet attached is not supported"); return 4; }
+    } else {
+        n_ctrl = 0;
+        cn_scale = 0.f;
+    }
+    const bool use_cn = cn && cn_scale != 0.f;
     if (graph_enabled && !prof_enabled())
         return forward_graph(sample, timesteps, ehs, L, add_text, add_time_ids, out, B, H, W, stream);
     if (kv_cache_on) {          // persistent buffer for the text K/V (outside the per-forward arena)
@@ -917,14 +1038,35 @@ int UNet::forward(const half_t* sample, const float* timesteps, const half_t* eh
                 ipkv_cap = ineed;
             }
         }
+        if (use_cn) {
+            const size_t cneed = (size_t)B * H * W * cn->cfg.block_out_channels[0] * sizeof(half_t);
+            if (cneed > cond_cap) {
+                SD_HIP_CHECK(hipDeviceSynchronize());
+                if (cond_cache) (void)hipFree(cond_cache);
+                cond_cache = nullptr; cond_cap = 0; cond_valid = false;
+                SD_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&cond_cache), cneed));
+                cond_cap = cneed;
+            }
+            const size_t kneed = (size_t)B * L * cn->kv_total * sizeof(half_t);
+            if (kneed > cnkv_cap) {
+                SD_HIP_CHECK(hipDeviceSynchronize());
+                if (cnkv_cache) (void)hipFree(cnkv_cache);
+                cnkv_cache = nullptr; cnkv_cap = 0; cnkv_valid = false;
+                SD_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&cnkv_cache), kneed));
+                cnkv_cap = kneed;
+            }
+        }
     }
     // (the IP-Adapter's image token count joins the key: set_ip_adapter resets the plan)
     const long key = ((long)B << 40) ^ ((long)H << 20) ^ (long)W ^ ((long)L << 52) ^ (kv_cache_on ? (1L << 62) : 0) ^
                      (ip ? (long)(n_img * ip->n_tok) << 32 : 0);
-    if (key != planned_key) {
+    // (the ControlNet's arena use depends on whether it runs and on n_ctrl: set_controlnet resets the plan)
+    const long cn_key = use_cn ? n_ctrl : 0;
+    if (key != planned_key || cn_key != planned_cn) {
         Ctx dry{&arena, stream, true};
         arena.begin(true);
-        int rc = run(dry, sample, timesteps, ehs, L, add_text, add_time_ids, out, B, H, W, image_embeds, n_img);
+        int rc = run(dry, sample, timesteps, ehs, L, add_text, add_time_ids, out, B, H, W, image_embeds, n_img, control,
+                     n_ctrl, cn_scale);
         if (rc) return rc;
         // growing the slab frees the old one: make sure nothing enqueued earlier still uses it
         if (arena.peak() > arena.capacity()) {
@@ -933,10 +1075,12 @@ int UNet::forward(const half_t* sample, const float* timesteps, const half_t* eh
             if (rc) return rc;
         }
         planned_key = key;
+        planned_cn = cn_key;
     }
     Ctx ctx{&arena, stream, false};
     arena.begin(false);
-    int rc = run(ctx, sample, timesteps, ehs, L, add_text, add_time_ids, out, B, H, W, image_embeds, n_img);
+    int rc = run(ctx, sample, timesteps, ehs, L, add_text, add_time_ids, out, B, H, W, image_embeds, n_img, control, n_ctrl,
+                 cn_scale);
     if (!rc && arena.overflow()) { set_error("unet: workspace overflow (planner bug)"); return 2; }
     return rc;
 }

@@ -151,5 +151,9 @@ def sharded_txt2img(pipeline, model, latents_full: torch.Tensor, prompt_embeds_f
         if broadcast:
             broadcast_tensors(ip)
         call_kwargs = dict(call_kwargs, ip_adapter_image_embeds=[_shard_cfg_rows(e, total, rank, world) for e in ip])
+    ci = call_kwargs.get("control_image")
+    if isinstance(ci, torch.Tensor) and ci.ndim == 4 and ci.shape[0] == total and total > 1:
+        # ControlNet: a per-sample control image batch is split with the latents; one image is broadcast as is
+        call_kwargs = dict(call_kwargs, control_image=shard(ci, rank, world))
     images = pipeline(model, prompt_embeds=pe, negative_prompt_embeds=ne, latents=lat, **call_kwargs)
     return all_gather_batch(images, total)

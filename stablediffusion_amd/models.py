@@ -75,6 +75,30 @@ def _load_weights(lib, handle, prefix: str, state_dict: Dict[str, torch.Tensor],
     return expected
 
 
+def _unet_config_struct(config: UNetConfig):
+    nb = len(config.block_out_channels)
+    c = _lib.SdUNetConfig()
+    c.in_channels = config.in_channels
+    c.out_channels = config.out_channels
+    c.num_blocks = nb
+    for i in range(nb):
+        c.block_out_channels[i] = config.block_out_channels[i]
+        c.down_block_has_attn[i] = int(config.down_block_types[i] == "CrossAttnDownBlock2D")
+        c.up_block_has_attn[i] = int(config.up_block_types[i] == "CrossAttnUpBlock2D")
+        c.num_heads[i] = config.attention_head_dim[i]
+        c.transformer_layers[i] = config.transformer_layers_per_block[i]
+    c.layers_per_block = config.layers_per_block
+    c.cross_attention_dim = config.cross_attention_dim
+    c.use_linear_projection = int(config.use_linear_projection)
+    c.norm_num_groups = config.norm_num_groups
+    c.norm_eps = config.norm_eps
+    c.flip_sin_to_cos = int(config.flip_sin_to_cos)
+    c.freq_shift = float(config.freq_shift)
+    c.addition_time_embed_dim = config.addition_time_embed_dim or 0
+    c.projection_class_embeddings_input_dim = config.projection_class_embeddings_input_dim or 0
+    return c
+
+
 class HipUNet2DConditionModel:
     """gfx950 engine behind the `UNet2DConditionModel` call surface the reference uses."""
 
@@ -83,26 +107,7 @@ class HipUNet2DConditionModel:
         self.cfg = config
         self.device = torch.device(device)
         self.dtype = torch.float16
-        nb = len(config.block_out_channels)
-        c = _lib.SdUNetConfig()
-        c.in_channels = config.in_channels
-        c.out_channels = config.out_channels
-        c.num_blocks = nb
-        for i in range(nb):
-            c.block_out_channels[i] = config.block_out_channels[i]
-            c.down_block_has_attn[i] = int(config.down_block_types[i] == "CrossAttnDownBlock2D")
-            c.up_block_has_attn[i] = int(config.up_block_types[i] == "CrossAttnUpBlock2D")
-            c.num_heads[i] = config.attention_head_dim[i]
-            c.transformer_layers[i] = config.transformer_layers_per_block[i]
-        c.layers_per_block = config.layers_per_block
-        c.cross_attention_dim = config.cross_attention_dim
-        c.use_linear_projection = int(config.use_linear_projection)
-        c.norm_num_groups = config.norm_num_groups
-        c.norm_eps = config.norm_eps
-        c.flip_sin_to_cos = int(config.flip_sin_to_cos)
-        c.freq_shift = float(config.freq_shift)
-        c.addition_time_embed_dim = config.addition_time_embed_dim or 0
-        c.projection_class_embeddings_input_dim = config.projection_class_embeddings_input_dim or 0
+        c = _unet_config_struct(config)
         self._h = C.c_void_p()
         _lib.check(self._lib.sd_unet_create(C.byref(c), C.byref(self._h)), "sd_unet_create")
         self.config = _Config(**config.to_dict())
@@ -112,6 +117,7 @@ class HipUNet2DConditionModel:
         self._finalized = False
         self._ip = None                # attached HipIPAdapter (attach_ip_adapter)
         self._ip_scale = 1.0
+        self._cn = None                # attached HipControlNetModel (attach_controlnet)
 
     # -- weights -------------------------------------------------------------------------------
     def load_state_dict(self, state_dict: Dict[str, torch.Tensor], strict: bool = True):
@@ -182,6 +188,46 @@ class HipUNet2DConditionModel:
         self._ip_scale = float(scale)
         return self
 
+    def attach_controlnet(self, controlnet: Optional["HipControlNetModel"]):
+        """Attach a ControlNet built for this UNet (None detaches).  While attached, every call needs controlnet_cond=
+        and controlnet_conditioning_scale=; the residuals are added inside the engine's forward."""
+        _lib.check(self._lib.sd_unet_set_controlnet(self._h, controlnet._h if controlnet is not None else None),
+                   "sd_unet_set_controlnet")
+        if self._cn is not None and self._cn is not controlnet:
+            self._cn._unet = None
+        if controlnet is not None:
+            old = controlnet._unet() if controlnet._unet is not None else None
+            if old is not None and old is not self:
+                old._cn = None
+            controlnet._unet = weakref.ref(self)
+        self._cn = controlnet
+        return self
+
+    def make_controlnet(self, cn_config: UNetConfig, state_dict: Dict[str, torch.Tensor]):
+        """A HipControlNetModel for this engine, loaded from diffusers-named weights."""
+        return HipControlNetModel(self, cn_config).load_state_dict(state_dict)
+
+    @property
+    def controlnet(self):
+        return self._cn
+
+    def _control(self, controlnet_cond, scale, B, H, W, dev):
+        if self._cn is None:
+            if controlnet_cond is not None or scale is not None:
+                raise ValueError("controlnet_cond / controlnet_conditioning_scale given but no ControlNet is attached")
+            return None, 0.0
+        if controlnet_cond is None or scale is None:
+            raise ValueError("a ControlNet is attached: controlnet_cond and controlnet_conditioning_scale are required")
+        if isinstance(controlnet_cond, (list, tuple)) or isinstance(scale, (list, tuple)):
+            raise NotImplementedError("MultiControlNet (lists of control images / scales) is not supported")
+        cond = _as_f16(controlnet_cond, dev)
+        n = cond.shape[0]
+        if cond.ndim != 4 or cond.shape[1] != 3 or cond.shape[2] != 8 * H or cond.shape[3] != 8 * W:
+            raise ValueError(f"controlnet_cond: expected [n, 3, {8 * H}, {8 * W}], got {tuple(cond.shape)}")
+        if n < 1 or B % n:
+            raise ValueError(f"controlnet_cond: {n} images do not divide the batch {B}")
+        return cond, float(scale)
+
     def _image_embeds(self, added_cond_kwargs, B, dev):
         embeds = (added_cond_kwargs or {}).get("image_embeds")
         if self._ip is None:
@@ -210,7 +256,16 @@ class HipUNet2DConditionModel:
         return self
 
     def __call__(self, sample, timestep, encoder_hidden_states, cross_attention_kwargs=None,
-                 added_cond_kwargs=None, return_dict=False, **unused):
+                 added_cond_kwargs=None, return_dict=False, controlnet_cond=None, controlnet_conditioning_scale=None,
+                 **unused):
+        # diffusers' residual-tensor interface (a ControlNet run outside the engine): not taken -- silently dropping
+        # it would return the plain UNet's output.  Attach the ControlNet instead (attach_controlnet).
+        for k in ("down_block_additional_residuals", "mid_block_additional_residual", "down_intrablock_additional_residuals",
+                  "guess_mode"):
+            v = unused.get(k)
+            if v is not None and v is not False:
+                raise NotImplementedError(f"HipUNet2DConditionModel: {k} is not supported; attach the ControlNet to the "
+                                          "engine (attach_controlnet) and pass controlnet_cond=")
         if not self._finalized:
             raise _lib.EngineError("weights not loaded")
         dev = self.device
@@ -236,9 +291,17 @@ class HipUNet2DConditionModel:
             add_ids = added_cond_kwargs["time_ids"].to(device=dev, dtype=torch.float32).contiguous()
             pt, pi = C.c_void_p(add_text.data_ptr()), C.c_void_p(add_ids.data_ptr())
         img = self._image_embeds(added_cond_kwargs, B, dev)
+        ctrl, cscale = self._control(controlnet_cond, controlnet_conditioning_scale, B, H, W, dev)
         out = torch.empty((B, self.cfg.out_channels, H, W), device=dev, dtype=torch.float16)
         with torch.cuda.device(dev):
-            if img is None:
+            if ctrl is not None:
+                rc = self._lib.sd_unet_forward_cn(self._h, C.c_void_p(sample.data_ptr()), C.c_void_p(t.data_ptr()),
+                                                  C.c_void_p(ehs.data_ptr()), ehs.shape[1], pt, pi,
+                                                  C.c_void_p(img.data_ptr()) if img is not None else None,
+                                                  img.shape[1] if img is not None else 0,
+                                                  C.c_void_p(ctrl.data_ptr()), ctrl.shape[0], cscale,
+                                                  C.c_void_p(out.data_ptr()), B, H, W, C.c_void_p(_stream_ptr()))
+            elif img is None:
                 rc = self._lib.sd_unet_forward(self._h, C.c_void_p(sample.data_ptr()), C.c_void_p(t.data_ptr()),
                                                C.c_void_p(ehs.data_ptr()), ehs.shape[1], pt, pi,
                                                C.c_void_p(out.data_ptr()), B, H, W, C.c_void_p(_stream_ptr()))
@@ -304,6 +367,56 @@ class HipIPAdapter:
                 if u is not None:
                     u._ip = None
                 self._lib.sd_ip_adapter_destroy(self._h)     # (detaches it first)
+                self._h = None
+        except Exception:
+            pass
+
+
+class HipControlNetModel:
+    """diffusers ControlNetModel on the engine, bound to a UNet (sd_controlnet_*): attach it with
+    HipUNet2DConditionModel.attach_controlnet; the UNet's forward then runs it.  Weights in diffusers naming
+    (stablediffusion_amd.controlnet converts original files)."""
+
+    def __init__(self, unet: HipUNet2DConditionModel, cn_config: UNetConfig, conditioning_channels: int = 3):
+        self._lib = _lib.load()
+        self.cfg = cn_config
+        self.device = unet.device
+        self._unet = None
+        c = _unet_config_struct(cn_config)
+        self._h = C.c_void_p()
+        _lib.check(self._lib.sd_controlnet_create(unet._h, C.byref(c), int(conditioning_channels), C.byref(self._h)),
+                   "sd_controlnet_create")
+        self._finalized = False
+
+    def load_state_dict(self, state_dict: Dict[str, torch.Tensor], strict: bool = True):
+        _lib.require_gpu()
+        with torch.cuda.device(self.device):
+            _load_weights(self._lib, self._h, "controlnet", state_dict, strict)
+            _lib.check(self._lib.sd_controlnet_finalize(self._h), "sd_controlnet_finalize")
+        self._finalized = True
+        return self
+
+    def cond_embedding(self, image: torch.Tensor) -> torch.Tensor:
+        """controlnet_cond_embedding(image): [n, 3, 8h, 8w] -> [n, C0, h, w] (fp16)."""
+        x = _as_f16(image, self.device)
+        n, _, H8, W8 = x.shape
+        if H8 % 8 or W8 % 8:
+            raise ValueError("control image height and width must be multiples of 8")
+        c0 = self.cfg.block_out_channels[0]
+        out = torch.empty((n, H8 // 8, W8 // 8, c0), device=self.device, dtype=torch.float16)
+        with torch.cuda.device(self.device):
+            rc = self._lib.sd_op_controlnet_cond_embed(self._h, C.c_void_p(x.data_ptr()), n, H8 // 8, W8 // 8,
+                                                       C.c_void_p(out.data_ptr()), 0, None, C.c_void_p(_stream_ptr()))
+        _lib.check(rc, "sd_op_controlnet_cond_embed")
+        return out.permute(0, 3, 1, 2)
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None):
+                u = self._unet() if self._unet is not None else None
+                if u is not None:
+                    u._cn = None
+                self._lib.sd_controlnet_destroy(self._h)     # (detaches it first)
                 self._h = None
         except Exception:
             pass

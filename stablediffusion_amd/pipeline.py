@@ -46,6 +46,7 @@ class SDModelWrapper:
         self.feature_extractor = feature_extractor
         self._ip = None                  # (diffusers-named state dict, image_embed_dim, num_tokens)
         self._ip_scale = 1.0
+        self._cn = None                  # ControlNet (configuration, diffusers-named state dict): load_controlnet
         # host copies of the weights the LoRA adapters are folded into (load_lora_weights); the engine
         # itself keeps only its packed device copy
         self._lora = None
@@ -132,7 +133,34 @@ class SDModelWrapper:
             base.use_graph(True)
         if self._ip is not None:             # the IP-Adapter survives the re-fuse
             self._attach_ip(base)
+        if self._cn is not None:             # and so does the ControlNet
+            self._attach_cn(base)
         return base
+
+    # ---- ControlNet (diffusers ControlNetModel, one per model; the pipeline takes control_image=) ----
+    def _attach_cn(self, base):
+        cfg, sd = self._cn
+        base.attach_controlnet(base.make_controlnet(cfg, sd))
+
+    def load_controlnet(self, pretrained_model_name_or_path_or_dict):
+        """A ControlNet for this model's UNet: a diffusers folder (config.json + weights), an original (lllyasviel 1.0 /
+        1.1) `.pth` / `.safetensors` file, or a state dict (stablediffusion_amd.controlnet.load: converted, checked).
+        Replaces a ControlNet loaded before.  Lists (MultiControlNet) are not supported."""
+        from . import controlnet
+        if isinstance(pretrained_model_name_or_path_or_dict, (list, tuple)):
+            raise NotImplementedError("MultiControlNet (a list of ControlNets) is not supported")
+        cfg, sd = controlnet.load(pretrained_model_name_or_path_or_dict, self.base.cfg)
+        self._cn = (cfg, sd)
+        self._attach_cn(self.base)
+
+    def unload_controlnet(self):
+        if self._cn is not None:
+            self.base.attach_controlnet(None)
+        self._cn = None
+
+    @property
+    def has_controlnet(self) -> bool:
+        return self._cn is not None
 
     # ---- IP-Adapter (diffusers load_ip_adapter / set_ip_adapter_scale / unload_ip_adapter) ----
     def _attach_ip(self, base):
@@ -275,7 +303,26 @@ class StableDiffusionUnifiedPipeline:
         # IP-Adapter image prompts (the reference's commented block at :441-449)
         ip_adapter_image=None,
         ip_adapter_image_embeds: Optional[List[torch.Tensor]] = None,
+        # ControlNet (diffusers StableDiffusionControlNetPipeline and its SDXL / img2img / inpaint twins)
+        control_image=None,
+        controlnet_conditioning_scale: float = 1.0,
+        control_guidance_start: float = 0.0,
+        control_guidance_end: float = 1.0,
+        guess_mode: bool = False,
     ):
+        if guess_mode:
+            raise NotImplementedError("ControlNet guess_mode is not supported")
+        has_cn = bool(getattr(model, "has_controlnet", False))
+        if control_image is not None and not has_cn:
+            raise ValueError("control_image given but no ControlNet is loaded (SDModelWrapper.load_controlnet)")
+        if has_cn and control_image is None:
+            raise ValueError("a ControlNet is loaded: control_image is required (or unload_controlnet)")
+        if has_cn:
+            if any(isinstance(v, (list, tuple)) for v in (controlnet_conditioning_scale, control_guidance_start,
+                                                          control_guidance_end)):
+                raise NotImplementedError("MultiControlNet (lists of scales / guidance windows) is not supported")
+            if not 0.0 <= control_guidance_start < control_guidance_end <= 1.0:
+                raise ValueError("need 0 <= control_guidance_start < control_guidance_end <= 1")
         if model.device != self.device:
             model.to(self.device)
         self.model = model
@@ -292,6 +339,10 @@ class StableDiffusionUnifiedPipeline:
             image = model.image_processor.preprocess(image)
             if image.shape[1] != 4:
                 height, width = image.shape[-2], image.shape[-1]
+        if has_cn and image is None and (height is None or width is None):
+            # txt2img: the run's size comes from the control image (diffusers' check_image / prepare_image)
+            ci = self.control_image_processor(model).preprocess(control_image, height=height, width=width)
+            height, width = ci.shape[-2], ci.shape[-1]
         height = height or model.base.config.sample_size * model.vae_scale_factor
         width = width or model.base.config.sample_size * model.vae_scale_factor
 
@@ -409,6 +460,12 @@ class StableDiffusionUnifiedPipeline:
                 image_embeds = [e.to(torch.float16).contiguous() for e in image_embeds]
             added_cond_kwargs = dict(added_cond_kwargs or {}, image_embeds=image_embeds)
 
+        control = None
+        if has_cn:
+            if num_channels_unet != 4:
+                raise ValueError("ControlNet needs a 4-channel UNet (9-channel inpaint UNets are not supported)")
+            control = self.prepare_control_image(model, control_image, height, width, batch_size, num_images_per_prompt)
+
         if self.do_classifier_free_guidance:
             prompt_embeds = torch.cat([negative_prompt_embeds, prompt_embeds], dim=0)
         prompt_embeds = prompt_embeds.to(self.device)
@@ -419,6 +476,14 @@ class StableDiffusionUnifiedPipeline:
         # the UNet forward of every step.  One copy of the schedule to the host before the loop
         # removes those 50 bubbles; the values are the same.
         timesteps_host = [float(v) for v in timesteps.tolist()]
+        # ControlNet guidance window (diffusers' controlnet_keep) over this loop's steps; the UNet gets the image once
+        # per prompt image (its batch under CFG maps sample b onto image b mod N: diffusers' cat([image] * 2))
+        cn_scales = None
+        if control is not None:
+            n = len(timesteps_host)
+            cn_scales = [float(controlnet_conditioning_scale) *
+                         (1.0 - float(i / n < control_guidance_start or (i + 1) / n > control_guidance_end))
+                         for i in range(n)]
         # prompt_embeds is the same tensor on every step: the engine keeps its cross-attention K/V
         # projections for the duration of this loop (switched off again right after it)
         kv_cache = getattr(model.base, "text_kv_cache", None)
@@ -437,10 +502,12 @@ class StableDiffusionUnifiedPipeline:
             blend = (f16(image_latents), f16(noise), f16(m1.expand(latents.shape[0], 1, *latents.shape[2:])))
         try:
             for i, t in enumerate(timesteps_host):
+                cn_kwargs = {} if control is None else dict(controlnet_cond=control,
+                                                            controlnet_conditioning_scale=cn_scales[i])
                 if fused_step:
                     latents, fused_hist = self._fused_cfg_iteration(model, latents, fused_hist, t, prompt_embeds,
                                                                     cross_attention_kwargs, added_cond_kwargs,
-                                                                    guidance_scale)
+                                                                    guidance_scale, **cn_kwargs)
                     if blend is not None:
                         last = i == len(timesteps_host) - 1
                         a, b = (1.0, 0.0) if last else model.scheduler.add_noise_coefficients(timesteps_host[i + 1])
@@ -453,7 +520,7 @@ class StableDiffusionUnifiedPipeline:
                                                     masked_image_latents_2b.to(latent_model_input.dtype)], dim=1)
                 noise_pred = model.base(latent_model_input, t, prompt_embeds,
                                         cross_attention_kwargs=cross_attention_kwargs,
-                                        added_cond_kwargs=added_cond_kwargs, return_dict=False)[0]
+                                        added_cond_kwargs=added_cond_kwargs, return_dict=False, **cn_kwargs)[0]
                 if self.do_classifier_free_guidance:
                     noise_pred_uncond, noise_pred_text = noise_pred.chunk(2)
                     noise_pred = guidance_scale * (noise_pred_text - noise_pred_uncond) + noise_pred_uncond
@@ -513,7 +580,7 @@ class StableDiffusionUnifiedPipeline:
                 and hasattr(model.base, "_lib") and latents.is_cuda and latents.dtype == torch.float16)
 
     def _fused_cfg_iteration(self, model, latents, hist, t, prompt_embeds, cross_attention_kwargs, added_cond_kwargs,
-                             guidance_scale):
+                             guidance_scale, **unet_kwargs):
         import ctypes as C
         lib = model.base._lib
         plan = model.scheduler.fused_plan(t)
@@ -526,7 +593,7 @@ class StableDiffusionUnifiedPipeline:
         if rc:
             raise RuntimeError(lib.sd_last_error().decode())
         noise_pred = model.base(lat2, t, prompt_embeds, cross_attention_kwargs=cross_attention_kwargs,
-                                added_cond_kwargs=added_cond_kwargs, return_dict=False)[0]
+                                added_cond_kwargs=added_cond_kwargs, return_dict=False, **unet_kwargs)[0]
         if plan.use_hist and hist is None:
             hist = torch.zeros(latents.shape, device=latents.device, dtype=torch.float32)
         out = latents.clone()
@@ -537,6 +604,29 @@ class StableDiffusionUnifiedPipeline:
             raise RuntimeError(lib.sd_last_error().decode())
         model.scheduler.fused_commit()
         return out, hist
+
+    @staticmethod
+    def control_image_processor(model):
+        # diffusers: VaeImageProcessor(vae_scale_factor, do_convert_rgb=True, do_normalize=False)
+        return VaeImageProcessor(vae_scale_factor=model.vae_scale_factor, do_convert_rgb=True, do_normalize=False)
+
+    def prepare_control_image(self, model, image, height, width, batch_size, num_images_per_prompt):
+        """diffusers prepare_image without the CFG doubling: [N, 3, height, width] in [0, 1], N = batch_size x
+        num_images_per_prompt (a one-image batch repeats by N, a larger one by num_images_per_prompt).  On the HIP
+        device one fp16 buffer for the whole loop (the engine caches the conditioning embedding by its address)."""
+        if isinstance(image, (list, tuple)) and image and isinstance(image[0], (list, tuple)):
+            raise NotImplementedError("MultiControlNet (a list of control-image lists) is not supported")
+        img = self.control_image_processor(model).preprocess(image, height=height, width=width).to(torch.float32)
+        if img.shape[1] != 3:
+            raise ValueError(f"control_image must have 3 channels, got {img.shape[1]}")
+        repeat_by = batch_size * num_images_per_prompt if img.shape[0] == 1 else num_images_per_prompt
+        img = img.repeat_interleave(repeat_by, dim=0)
+        if img.shape[0] != batch_size * num_images_per_prompt:
+            raise ValueError(f"control_image batch {img.shape[0] // repeat_by} does not match the prompt batch {batch_size}")
+        img = img.to(self.device)
+        if img.is_cuda:
+            img = img.to(torch.float16).contiguous()
+        return img
 
     def encode_image(self, image, device, num_images_per_prompt):
         """diffusers 0.27.2 `encode_image` for the base adapters' ImageProjection: image_encoder(feature_extractor(image)
