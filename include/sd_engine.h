@@ -268,6 +268,17 @@ int sd_cfg_linear_step(const void* noise_pred_2b, void* latents, float* hist_f32
                        float guidance_scale, float c_x, float c_eps, float c_hist, float h_x, float h_eps,
                        void* stream);
 
+/* sd_cfg_linear_step with guidance rescale (Lin et al., "Common Diffusion Noise Schedules and Sample Steps are Flawed",
+ * section 3.4; rescale_noise_cfg at sd_unified_pipeline.py:46-57).  Per sample b of n_per_sample elements:
+ *   eps = fp16(u + g (t - u));  k_b = 1 + guidance_rescale (std(t_b) / std(eps_b) - 1);  eps <- k_b eps
+ * and then the update of sd_cfg_linear_step (hist <- h_x x + h_eps k_b eps).  std is the unbiased one over the whole
+ * sample; the statistics are fp32 and centred.  std(eps_b) = 0 gives an infinite or NaN k_b, as the reference function
+ * does: no epsilon is added.  Two launches, no host synchronisation.  factors_out [B] f32 (device, nullable) receives
+ * k_b.  SD_ERR_INVALID: null noise_pred_2b / latents, B < 1, n_per_sample < 2 (nothing is launched). */
+int sd_cfg_rescale_linear_step(const void* noise_pred_2b, void* latents, float* hist_f32, int B, int64_t n_per_sample,
+                               float guidance_scale, float guidance_rescale, float c_x, float c_eps, float c_hist,
+                               float h_x, float h_eps, float* factors_out, void* stream);
+
 /* Inpainting with a 4-channel UNet, after every scheduler step (sd_unified_pipeline.py:492-506):
  *   latents <- m latents + (1 - m) (a image_latents + b noise),  m = mask [B,1,H,W] f16 over channels;
  * (a, b) = scheduler.add_noise coefficients at the NEXT timestep, or noise = NULL on the last step. */

@@ -135,6 +135,7 @@ SIGNATURES = {
     "sd_inpaint_blend": (_I, [_P, _P, _P, _P, _F, _F, _I, _I, _I, _I, _P]),
     "sd_images_to_uint8": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "sd_cfg_linear_step": (_I, [_P, _P, _P, _I64, _F, _F, _F, _F, _F, _F, _P]),
+    "sd_cfg_rescale_linear_step": (_I, [_P, _P, _P, _I, _I64, _F, _F, _F, _F, _F, _F, _F, _P, _P]),
     "sd_igemm_force": (_I, [_I, _I]),
     "sd_probe_mfma": (_I, [_I, C.POINTER(_F), _P]),
     "sd_probe_lds_dma": (_I, [_I64, _I, _I, _I, C.POINTER(_F), _P]),

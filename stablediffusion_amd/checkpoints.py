@@ -88,6 +88,24 @@ def load_diffusers_folder(root: str) -> Tuple[UNetConfig, Dict[str, torch.Tensor
     return ucfg, usd, vcfg, vsd
 
 
+SCHEDULER_FIELDS = ("num_train_timesteps", "beta_start", "beta_end", "steps_offset", "timestep_spacing",
+                    "prediction_type", "rescale_betas_zero_snr")
+
+
+def read_scheduler_config(folder: str) -> dict:
+    """`<folder>/scheduler/scheduler_config.json` of a diffusers checkpoint directory -> the fields the engine's schedulers
+    understand (SCHEDULER_FIELDS; everything else, `_class_name` included, is dropped: SDModelWrapper.set_scheduler picks
+    the class).  This is where a folder says that its UNet predicts v (SD 2.x-768, zero-terminal-SNR fine-tunes); A1111
+    single files carry no such record, there the caller passes `prediction_type=`.  Only `scaled_linear` betas exist
+    here: another `beta_schedule` is an error rather than a silently different model."""
+    with open(os.path.join(folder, "scheduler", "scheduler_config.json")) as f:
+        d = json.load(f)
+    sched = d.get("beta_schedule", "scaled_linear")
+    if sched != "scaled_linear":
+        raise ValueError(f"scheduler_config.json: beta_schedule {sched!r} is not supported (scaled_linear only)")
+    return {k: d[k] for k in SCHEDULER_FIELDS if k in d}
+
+
 # ---------------------------------------------------------------------------------------------
 # A1111 / LDM single file -> diffusers names
 # ---------------------------------------------------------------------------------------------

@@ -383,6 +383,17 @@ int sd_cfg_linear_step(const void* noise_pred_2b, void* latents, float* hist_f32
     return launch_cfg_linear(static_cast<const half_t*>(noise_pred_2b), static_cast<half_t*>(latents), hist_f32, (long)n,
                              guidance_scale, c_x, c_eps, c_hist, h_x, h_eps, static_cast<hipStream_t>(stream));
 }
+int sd_cfg_rescale_linear_step(const void* noise_pred_2b, void* latents, float* hist_f32, int B, int64_t n_per_sample,
+                               float guidance_scale, float guidance_rescale, float c_x, float c_eps, float c_hist, float h_x,
+                               float h_eps, float* factors_out, void* stream) {
+    if (!noise_pred_2b || !latents || B < 1 || n_per_sample < 2) {
+        set_error("sd_cfg_rescale_linear_step: bad arguments (non-null tensors, B >= 1, n_per_sample >= 2)");
+        return SD_ERR_INVALID;
+    }
+    return launch_cfg_rescale_linear(static_cast<const half_t*>(noise_pred_2b), static_cast<half_t*>(latents), hist_f32, B,
+                                     (long)n_per_sample, guidance_scale, guidance_rescale, c_x, c_eps, c_hist, h_x, h_eps,
+                                     factors_out, static_cast<hipStream_t>(stream));
+}
 int sd_images_to_uint8(const void* images_nchw_f16, void* out_nhwc_u8, int B, int C, int H, int W, void* stream) {
     if (!images_nchw_f16 || !out_nhwc_u8 || B < 0 || C < 1 || C > 4 || H < 1 || W < 1) {
         set_error("sd_images_to_uint8: bad arguments (1..4 channels)");

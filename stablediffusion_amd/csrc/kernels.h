@@ -294,6 +294,10 @@ int launch_cfg_linear(const half_t* eps2b, half_t* lat, float* hist, long n, flo
                       float hx, float he, hipStream_t s);
 int launch_cfg_ddim(const half_t* eps2b, half_t* lat, long n, float g, float cx, float ce,
                     hipStream_t s);
+// launch_cfg_linear on k_b * eps, k_b = 1 + phi (std(text_b) / std(eps_b) - 1) per sample b of n elements (guidance
+// rescale): a statistics launch and an update launch; factors [B] (nullable) receives k_b
+int launch_cfg_rescale_linear(const half_t* eps2b, half_t* lat, float* hist, int B, long n, float g, float phi, float cx,
+                              float ce, float ch, float hx, float he, float* factors, hipStream_t s);
 
 // Box probe (probe.hip): back-to-back 16x16x32 f16 MFMA loop (TFLOP/s) and a 16-byte-per-lane copy (GB/s, read + write)
 int probe_mfma(int iters, float* tflops, hipStream_t s);

@@ -1,7 +1,11 @@
 // Small / HBM-bound helper kernels for the gfx950 denoise engine: timestep sinusoid, batch-sized
 // linear layers (time-embedding MLPs), layout changes at the NCHW boundary, weight packing and the
 // CFG + DDIM elementwise update.  wave64 throughout.
+#include <cstdint>
 #include <cstdlib>
+#include <map>
+#include <mutex>
+#include <utility>
 
 #include "kernels.h"
 
@@ -222,6 +226,165 @@ __global__ void cfg_linear_kernel(const half_t* __restrict__ eps2b, half_t* __re
         hist[i] = hx * x + he * e;
     }
     lat[i] = (half_t)out;
+}
+
+// ---- guidance rescale (Lin et al. 2023, section 3.4; diffusers rescale_noise_cfg) in front of the same linear update ----
+//   e = fp16(u + g (t - u));  k_b = 1 + phi (std(t_b) / std(e_b) - 1);  the update of cfg_linear_kernel on k_b e
+// std is per sample over all n elements; std(t) / std(e) = sqrt(M2(t) / M2(e)) (the ddof cancels), M2 = sum (x - mean)^2.
+// Two launches: rs_stats_kernel leaves one centred (count, mean, M2) triple per tensor and chunk of a sample, every wave of
+// rs_apply_kernel merges its sample's triples (Chan et al.) in the same order, so all blocks of a sample agree on k_b bit
+// for bit, and applies the update.  M2 is never formed as E[x^2] - E[x]^2: at a mean of 100 and a deviation of 0.5 that
+// difference has lost every digit in fp32 (commit 4edffab's lesson for the GroupNorm summaries).
+constexpr int RS_MAX_PARTS = 64;          // chunks per sample: one per lane of the wave that merges them
+constexpr int RS_MIN_CHUNK = 2048;        // elements: one 16-byte load per thread and tensor
+
+struct RsStat { float n, mean, m2; };
+
+__device__ __forceinline__ RsStat rs_merge(const RsStat a, const RsStat b) {
+    RsStat r;
+    r.n = a.n + b.n;
+    const float d = b.mean - a.mean;
+    const float w = r.n > 0.f ? b.n / r.n : 0.f;
+    r.mean = a.mean + d * w;
+    r.m2 = a.m2 + b.m2 + d * d * a.n * w;
+    return r;
+}
+__device__ __forceinline__ RsStat rs_wave_merge(RsStat s) {
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        RsStat o;
+        o.n = __shfl_xor(s.n, off);
+        o.mean = __shfl_xor(s.mean, off);
+        o.m2 = __shfl_xor(s.m2, off);
+        // the lower lane of a pair is always the left operand, so both lanes compute the same value
+        s = (threadIdx.x & off) ? rs_merge(o, s) : rs_merge(s, o);
+    }
+    return s;
+}
+__device__ __forceinline__ float rs_cfg(float eu, float et, float g) { return (float)(half_t)(g * (et - eu) + eu); }
+// a x + b e with the roundings cfg_linear_kernel's `a * x + b * e` compiles to under -ffp-contract=fast: the product b e is
+// rounded, a x is fused into the add.  Written out because the contraction the compiler picks depends on the code around
+// the expression, and k_b = 1 has to reproduce that kernel bit for bit.
+__device__ __forceinline__ float rs_axpby(float a, float x, float b, float e) { return __builtin_fmaf(a, x, b * e); }
+
+// part [B][parts][2] triples: (t, e) of chunk p of sample b.  VEC: n % 8 == 0 and 16-byte aligned bases.
+template <bool VEC>
+__global__ __launch_bounds__(256) void rs_stats_kernel(const half_t* __restrict__ eps2b, RsStat* __restrict__ part, long n,
+                                                       long chunk, long total, float g) {
+    const int b = blockIdx.y, p = blockIdx.x;
+    const half_t* u = eps2b + (long)b * n;
+    const half_t* t = u + total;
+    const long lo = (long)p * chunk, hi = lo + chunk < n ? lo + chunk : n;
+    RsStat st = {0.f, 0.f, 0.f}, se = {0.f, 0.f, 0.f};
+    if (VEC) {
+        for (long i = lo + (long)threadIdx.x * 8; i < hi; i += 256 * 8) {
+            const h8 vu = *reinterpret_cast<const h8*>(u + i);
+            const h8 vt = *reinterpret_cast<const h8*>(t + i);
+            float ft[8], fe[8], sumt = 0.f, sume = 0.f;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                ft[k] = (float)vt[k];
+                fe[k] = rs_cfg((float)vu[k], ft[k], g);
+                sumt += ft[k];
+                sume += fe[k];
+            }
+            RsStat vt8 = {8.f, sumt * 0.125f, 0.f}, ve8 = {8.f, sume * 0.125f, 0.f};
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const float dt = ft[k] - vt8.mean, de = fe[k] - ve8.mean;
+                vt8.m2 += dt * dt;
+                ve8.m2 += de * de;
+            }
+            st = rs_merge(st, vt8);
+            se = rs_merge(se, ve8);
+        }
+    } else {
+        for (long i = lo + threadIdx.x; i < hi; i += 256) {
+            const float ft = (float)t[i];
+            const RsStat a = {1.f, ft, 0.f}, c = {1.f, rs_cfg((float)u[i], ft, g), 0.f};
+            st = rs_merge(st, a);
+            se = rs_merge(se, c);
+        }
+    }
+    st = rs_wave_merge(st);
+    se = rs_wave_merge(se);
+    __shared__ RsStat sh[4][2];
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { sh[wave][0] = st; sh[wave][1] = se; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        RsStat* o = part + ((long)b * gridDim.x + p) * 2;
+        o[0] = rs_merge(rs_merge(sh[0][0], sh[1][0]), rs_merge(sh[2][0], sh[3][0]));
+        o[1] = rs_merge(rs_merge(sh[0][1], sh[1][1]), rs_merge(sh[2][1], sh[3][1]));
+    }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void rs_apply_kernel(const half_t* __restrict__ eps2b, half_t* __restrict__ lat,
+                                                       float* __restrict__ hist, const RsStat* __restrict__ part, int parts,
+                                                       long n, long total, float g, float phi, float cx, float ce, float ch,
+                                                       float hx, float he, float* __restrict__ factors) {
+    const int b = blockIdx.y, lane = threadIdx.x & 63;
+    RsStat st = {0.f, 0.f, 0.f}, se = {0.f, 0.f, 0.f};
+    if (lane < parts) {
+        const RsStat* q = part + ((long)b * parts + lane) * 2;
+        st = q[0];
+        se = q[1];
+    }
+    st = rs_wave_merge(st);
+    se = rs_wave_merge(se);
+    // std(e) = 0 gives inf or nan, as the reference function does: no epsilon
+    const float k = 1.f + phi * (sqrtf(st.m2 / se.m2) - 1.f);
+    if (factors && blockIdx.x == 0 && threadIdx.x == 0) factors[b] = k;
+    const long base = (long)b * n;
+    const half_t* u = eps2b + base;
+    const half_t* t = u + total;
+    half_t* x = lat + base;
+    float* h = hist ? hist + base : nullptr;
+    if (VEC) {
+        const long i = ((long)blockIdx.x * 256 + threadIdx.x) * 8;
+        if (i >= n) return;
+        const h8 vu = *reinterpret_cast<const h8*>(u + i);
+        const h8 vt = *reinterpret_cast<const h8*>(t + i);
+        const h8 vx = *reinterpret_cast<const h8*>(x + i);
+        float hv[8], x0[8];
+        if (h) {
+            const f4 h0 = *reinterpret_cast<const f4*>(h + i), h1 = *reinterpret_cast<const f4*>(h + i + 4);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { hv[j] = h0[j]; hv[j + 4] = h1[j]; }
+        }
+        h8 o;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const float e = k * rs_cfg((float)vu[j], (float)vt[j], g);
+            const float xf = (float)vx[j];
+            float out = rs_axpby(cx, xf, ce, e);
+            if (h) {
+                out = __builtin_fmaf(ch, hv[j], out);
+                x0[j] = rs_axpby(hx, xf, he, e);
+            }
+            o[j] = (half_t)out;
+        }
+        *reinterpret_cast<h8*>(x + i) = o;
+        if (h) {
+            f4 h0, h1;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { h0[j] = x0[j]; h1[j] = x0[j + 4]; }
+            *reinterpret_cast<f4*>(h + i) = h0;
+            *reinterpret_cast<f4*>(h + i + 4) = h1;
+        }
+    } else {
+        const long i = (long)blockIdx.x * 256 + threadIdx.x;
+        if (i >= n) return;
+        const float e = k * rs_cfg((float)u[i], (float)t[i], g);
+        const float xf = (float)x[i];
+        float out = rs_axpby(cx, xf, ce, e);
+        if (h) {
+            out = __builtin_fmaf(ch, h[i], out);
+            h[i] = rs_axpby(hx, xf, he, e);
+        }
+        x[i] = (half_t)out;
+    }
 }
 
 // convert_pt_to_numpy (runpod-worker/handler_logic.py:21-29) on the device: the reference runs
@@ -585,6 +748,57 @@ int launch_cfg_ddim(const half_t* eps2b, half_t* lat, long n, float g, float cx,
 int launch_cfg_linear(const half_t* eps2b, half_t* lat, float* hist, long n, float g, float cx, float ce, float ch,
                       float hx, float he, hipStream_t s) {
     hipLaunchKernelGGL(cfg_linear_kernel, grid1d(n), dim3(256), 0, s, eps2b, lat, hist, n, g, cx, ce, ch, hx, he);
+    SD_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+// Chunk summaries of launch_cfg_rescale_linear: one grow-only buffer per (device, stream), so that calls on different
+// streams never share one and calls on one stream are ordered by it.  Allocated on the first call for a stream (or when
+// B grows); a steady loop allocates nothing and never synchronises.
+static RsStat* rs_workspace(int B, hipStream_t s) {
+    struct Buf { RsStat* p = nullptr; int B = 0; };
+    static std::mutex mu;
+    static std::map<std::pair<int, hipStream_t>, Buf> bufs;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return nullptr;
+    std::lock_guard<std::mutex> lock(mu);
+    Buf& b = bufs[{dev, s}];
+    if (b.B < B) {
+        if (b.p) (void)hipFree(b.p);          // waits for the device: nothing queued still reads it
+        b.p = nullptr;
+        b.B = 0;
+        if (hipMalloc(reinterpret_cast<void**>(&b.p), (size_t)B * RS_MAX_PARTS * 2 * sizeof(RsStat)) != hipSuccess) {
+            b.p = nullptr;
+            return nullptr;
+        }
+        b.B = B;
+    }
+    return b.p;
+}
+int launch_cfg_rescale_linear(const half_t* eps2b, half_t* lat, float* hist, int B, long n, float g, float phi, float cx,
+                              float ce, float ch, float hx, float he, float* factors, hipStream_t s) {
+    RsStat* part = rs_workspace(B, s);
+    if (!part) { set_error("cfg_rescale_linear: no device memory for the chunk summaries"); return 1; }
+    const long total = (long)B * n;
+    const bool vec = n % 8 == 0 && ((reinterpret_cast<uintptr_t>(eps2b) | reinterpret_cast<uintptr_t>(lat) |
+                                     reinterpret_cast<uintptr_t>(hist)) & 15) == 0;
+    long parts = (n + RS_MIN_CHUNK - 1) / RS_MIN_CHUNK;
+    if (parts > RS_MAX_PARTS) parts = RS_MAX_PARTS;
+    long chunk = (n + parts - 1) / parts;
+    chunk = (chunk + 7) / 8 * 8;
+    parts = (n + chunk - 1) / chunk;
+    const long per_block = vec ? 256 * 8 : 256;
+    const long blocks = (n + per_block - 1) / per_block;
+    if (blocks > 0x7fffffffL) { set_error("cfg_rescale_linear: sample too large"); return 1; }
+    const dim3 gs((unsigned)parts, (unsigned)B), ga((unsigned)blocks, (unsigned)B);
+    if (vec) {
+        hipLaunchKernelGGL(rs_stats_kernel<true>, gs, dim3(256), 0, s, eps2b, part, n, chunk, total, g);
+        hipLaunchKernelGGL(rs_apply_kernel<true>, ga, dim3(256), 0, s, eps2b, lat, hist, part, (int)parts, n, total, g, phi, cx,
+                           ce, ch, hx, he, factors);
+    } else {
+        hipLaunchKernelGGL(rs_stats_kernel<false>, gs, dim3(256), 0, s, eps2b, part, n, chunk, total, g);
+        hipLaunchKernelGGL(rs_apply_kernel<false>, ga, dim3(256), 0, s, eps2b, lat, hist, part, (int)parts, n, total, g, phi, cx,
+                           ce, ch, hx, he, factors);
+    }
     SD_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -37,7 +37,7 @@ class SDModelWrapper:
                  model_name: Optional[str] = None, unet_state_dict: Optional[Dict[str, torch.Tensor]] = None,
                  text_encoder_state_dict: Optional[Dict[str, torch.Tensor]] = None,
                  text_encoder_2_state_dict: Optional[Dict[str, torch.Tensor]] = None,
-                 image_encoder=None, feature_extractor=None):
+                 image_encoder=None, feature_extractor=None, prediction_type: Optional[str] = None):
         self.base = base
         # IP-Adapter (sd_unified_pipeline.py:441-449): host image encoder (e.g. transformers'
         # CLIPVisionModelWithProjection) and its CLIPImageProcessor, built by the caller; the adapter's converted
@@ -65,6 +65,8 @@ class SDModelWrapper:
         # set_scheduler("euler") on a wrapper built around another scheduler really switches
         if type(self.scheduler) is _sched.EulerDiscreteScheduler:     # (not its euler_a subclass: ADVICE r2)
             self.scheduler_name = "euler"
+        if prediction_type is not None:      # single-file checkpoints carry no scheduler configuration: the caller says
+            self.configure_scheduler(prediction_type=prediction_type)
         self.vae_scale_factor = 2 ** (len(self.vae.config.block_out_channels) - 1)
         # models/stable_diffusion.py:96-101
         self.image_processor = VaeImageProcessor(vae_scale_factor=self.vae_scale_factor)
@@ -216,6 +218,19 @@ class SDModelWrapper:
             return
         self._lora.scale = float(scale)
 
+    def configure_scheduler(self, **fields):
+        """Rebuild the current scheduler (same class) with configuration fields changed: `prediction_type`
+        ("epsilon" / "v_prediction"), `rescale_betas_zero_snr`, `timestep_spacing`, the beta range, ...  They live in
+        `scheduler.config`, so a later set_scheduler(name) carries them to the next class."""
+        self.scheduler = type(self.scheduler).from_config(self.scheduler.config, **fields)
+
+    def load_scheduler_config(self, folder):
+        """`scheduler/scheduler_config.json` of a diffusers checkpoint folder (checkpoints.read_scheduler_config) applied
+        to this wrapper's scheduler: what makes an SD 2.x-768 / zero-terminal-SNR folder run as the v-prediction model it
+        is.  The scheduler class stays the wrapper's own (set_scheduler chooses it)."""
+        from . import checkpoints
+        self.configure_scheduler(**checkpoints.read_scheduler_config(folder))
+
     def set_scheduler(self, scheduler_name):
         """Registry of models/stable_diffusion.py:199-227 (names the engine's host code implements)."""
         if getattr(self, "scheduler_name", None) == scheduler_name:
@@ -249,6 +264,19 @@ def convert_pt_to_numpy(images: torch.Tensor):
         img = (images[idx] / 2 + 0.5).clamp(0, 1)
         np_images.append((img.permute(1, 2, 0) * 255).to(torch.uint8).cpu().numpy())
     return np_images
+
+
+def rescale_noise_cfg(noise_cfg, noise_pred_text, guidance_rescale=0.0):
+    """sd_unified_pipeline.py:46-57 (defined there, never called): guidance rescale of Lin et al., "Common Diffusion
+    Noise Schedules and Sample Steps are Flawed", section 3.4.  The guided prediction is brought to the per-sample
+    standard deviation of the text-conditioned one and mixed back with weight `guidance_rescale`.  torch's default
+    (unbiased) std over everything but the batch axis, in the tensors' own dtype; std(noise_cfg) = 0 gives inf / nan
+    as it does there.  The device form is sd_cfg_rescale_linear_step."""
+    dims = list(range(1, noise_pred_text.ndim))
+    std_text = noise_pred_text.std(dim=dims, keepdim=True)
+    std_cfg = noise_cfg.std(dim=dims, keepdim=True)
+    rescaled = noise_cfg * (std_text / std_cfg)
+    return guidance_rescale * rescaled + (1 - guidance_rescale) * noise_cfg
 
 
 def retrieve_timesteps(scheduler, num_inference_steps=None, device=None, **kwargs):
@@ -312,6 +340,10 @@ class StableDiffusionUnifiedPipeline:
     ):
         if guess_mode:
             raise NotImplementedError("ControlNet guess_mode is not supported")
+        if not 0.0 <= float(guidance_rescale) <= 1.0:
+            raise ValueError(f"guidance_rescale must lie in [0, 1], got {guidance_rescale}")
+        # as in diffusers: only with CFG on and a positive value
+        guidance_rescale = float(guidance_rescale) if self.do_classifier_free_guidance else 0.0
         has_cn = bool(getattr(model, "has_controlnet", False))
         if control_image is not None and not has_cn:
             raise ValueError("control_image given but no ControlNet is loaded (SDModelWrapper.load_controlnet)")
@@ -507,7 +539,8 @@ class StableDiffusionUnifiedPipeline:
                 if fused_step:
                     latents, fused_hist = self._fused_cfg_iteration(model, latents, fused_hist, t, prompt_embeds,
                                                                     cross_attention_kwargs, added_cond_kwargs,
-                                                                    guidance_scale, **cn_kwargs)
+                                                                    guidance_scale, guidance_rescale=guidance_rescale,
+                                                                    **cn_kwargs)
                     if blend is not None:
                         last = i == len(timesteps_host) - 1
                         a, b = (1.0, 0.0) if last else model.scheduler.add_noise_coefficients(timesteps_host[i + 1])
@@ -524,6 +557,8 @@ class StableDiffusionUnifiedPipeline:
                 if self.do_classifier_free_guidance:
                     noise_pred_uncond, noise_pred_text = noise_pred.chunk(2)
                     noise_pred = guidance_scale * (noise_pred_text - noise_pred_uncond) + noise_pred_uncond
+                    if guidance_rescale > 0.0:
+                        noise_pred = rescale_noise_cfg(noise_pred, noise_pred_text, guidance_rescale)
                 latents = model.scheduler.step(noise_pred, t, latents, return_dict=False)[0]
                 if self.is_inpaint and num_channels_unet == 4:          # :492-506
                     init_latents_proper = image_latents
@@ -571,8 +606,8 @@ class StableDiffusionUnifiedPipeline:
         """CFG combine + scheduler update as ONE device kernel each side of the UNet:
         the scheduler still computes its coefficients on the host (`fused_plan`: DDIM, Euler, DPM++ 2M are
         all affine in x, eps and the previous x0 prediction), the engine applies them
-        (`sd_cfg_duplicate`, `sd_cfg_linear_step`), and for inpainting with a 4-channel UNet the mask blend
-        of `:492-506` follows as a third kernel (`sd_inpaint_blend`).  Only with CFG on the HIP engine;
+        (`sd_cfg_duplicate`, `sd_cfg_linear_step`, or `sd_cfg_rescale_linear_step` when guidance_rescale > 0),
+        and for inpainting with a 4-channel UNet the mask blend of `:492-506` follows as a third kernel (`sd_inpaint_blend`).  Only with CFG on the HIP engine;
         9-channel inpainting UNets and non-CFG calls take the generic path."""
         return (self.do_classifier_free_guidance and (not self.is_inpaint or num_channels_unet == 4)
                 and hasattr(model.scheduler, "fused_plan") and getattr(model.scheduler, "supports_fused", True)
@@ -580,7 +615,7 @@ class StableDiffusionUnifiedPipeline:
                 and hasattr(model.base, "_lib") and latents.is_cuda and latents.dtype == torch.float16)
 
     def _fused_cfg_iteration(self, model, latents, hist, t, prompt_embeds, cross_attention_kwargs, added_cond_kwargs,
-                             guidance_scale, **unet_kwargs):
+                             guidance_scale, guidance_rescale=0.0, **unet_kwargs):
         import ctypes as C
         lib = model.base._lib
         plan = model.scheduler.fused_plan(t)
@@ -597,9 +632,15 @@ class StableDiffusionUnifiedPipeline:
         if plan.use_hist and hist is None:
             hist = torch.zeros(latents.shape, device=latents.device, dtype=torch.float32)
         out = latents.clone()
-        rc = lib.sd_cfg_linear_step(C.c_void_p(noise_pred.data_ptr()), C.c_void_p(out.data_ptr()),
-                                    C.c_void_p(hist.data_ptr()) if plan.use_hist else None, out.numel(),
-                                    float(guidance_scale), plan.c_x, plan.c_eps, plan.c_hist, plan.h_x, plan.h_eps, st)
+        hist_p = C.c_void_p(hist.data_ptr()) if plan.use_hist else None
+        if guidance_rescale > 0.0:
+            # the rescale needs a standard deviation per sample, so it is not affine: its own statistics + update kernels
+            rc = lib.sd_cfg_rescale_linear_step(C.c_void_p(noise_pred.data_ptr()), C.c_void_p(out.data_ptr()), hist_p, B,
+                                                out[0].numel(), float(guidance_scale), float(guidance_rescale), plan.c_x,
+                                                plan.c_eps, plan.c_hist, plan.h_x, plan.h_eps, None, st)
+        else:
+            rc = lib.sd_cfg_linear_step(C.c_void_p(noise_pred.data_ptr()), C.c_void_p(out.data_ptr()), hist_p, out.numel(),
+                                        float(guidance_scale), plan.c_x, plan.c_eps, plan.c_hist, plan.h_x, plan.h_eps, st)
         if rc:
             raise RuntimeError(lib.sd_last_error().decode())
         model.scheduler.fused_commit()

@@ -8,6 +8,12 @@ from diffusers (`/root/reference/models/stable_diffusion.py:199-227`) and are dr
 Constants follow `/root/reference/scripts/convert_from_A1111.py:947-959` (scaled_linear betas
 0.00085..0.012, T=1000, steps_offset=1, set_alpha_to_one=False, clip_sample=False, epsilon).
 Coefficients are evaluated in float64 on the host; tensors are updated in fp32 and cast back.
+
+Beyond the reference's constants: `prediction_type="v_prediction"` (every scheduler: the model output is converted with
+eps = a v + s x at the step it was made for, then the epsilon update runs), `rescale_betas_zero_snr` (Lin et al., "Common
+Diffusion Noise Schedules and Sample Steps are Flawed", Alg. 1; DDIM and Euler) and `timestep_spacing="trailing"` (DDIM,
+Euler, the DPM++ 2M family) -- what SD 2.x-768 and zero-terminal-SNR checkpoints are sampled with.  The fields live in
+`.config` and travel through `from_config`.
 """
 from __future__ import annotations
 
@@ -29,16 +35,39 @@ def _alphas_cumprod(T, beta_start, beta_end):
     return np.cumprod(1.0 - betas)
 
 
+def _rescale_zero_terminal_snr(ac):
+    """Lin et al., "Common Diffusion Noise Schedules and Sample Steps are Flawed", Alg. 1, on sqrt(alpha-bar):
+    shifted so that the last value is 0 and scaled so that the first keeps its value."""
+    r = ac ** 0.5
+    r0, rT = r[0], r[-1]
+    r = (r - rT) * r0 / (r0 - rT)
+    return r ** 2
+
+
+PREDICTION_TYPES = ("epsilon", "v_prediction")
+
+
 class _Base:
     order = 1
+    zero_snr = False              # rescale_betas_zero_snr is implemented (DDIM, Euler)
+    zero_snr_floor = 0.0          # what alpha-bar_T becomes under it (a sigma-space scheduler cannot take 0)
+    trailing = False              # timestep_spacing="trailing" is implemented (DDIM, Euler, the DPM++ 2M family)
 
     def __init__(self, num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, steps_offset=1,
-                 timestep_spacing="leading", **extra):
+                 timestep_spacing="leading", prediction_type="epsilon", rescale_betas_zero_snr=False, **extra):
+        if prediction_type not in PREDICTION_TYPES:
+            raise ValueError(f"prediction_type must be one of {PREDICTION_TYPES}, got {prediction_type!r}")
+        if rescale_betas_zero_snr and not self.zero_snr:
+            raise ValueError(f"{type(self).__name__} does not implement rescale_betas_zero_snr (DDIM and euler do)")
         self.config = SimpleNamespace(num_train_timesteps=num_train_timesteps, beta_start=beta_start,
                                       beta_end=beta_end, beta_schedule="scaled_linear",
                                       steps_offset=steps_offset, timestep_spacing=timestep_spacing,
-                                      prediction_type="epsilon", **extra)
+                                      prediction_type=prediction_type,
+                                      rescale_betas_zero_snr=bool(rescale_betas_zero_snr), **extra)
         self.ac = _alphas_cumprod(num_train_timesteps, beta_start, beta_end)
+        if rescale_betas_zero_snr:
+            self.ac = _rescale_zero_terminal_snr(self.ac)
+            self.ac[-1] = self.zero_snr_floor
         self.init_noise_sigma = 1.0
         self.timesteps = None
         self.num_inference_steps = None
@@ -47,15 +76,38 @@ class _Base:
     def from_config(cls, config, **kw):
         d = dict(vars(config)) if not isinstance(config, dict) else dict(config)
         keep = {k: d[k] for k in ("num_train_timesteps", "beta_start", "beta_end", "steps_offset",
-                                  "timestep_spacing") if k in d}
+                                  "timestep_spacing", "prediction_type", "rescale_betas_zero_snr") if k in d}
         keep.update(kw)
         return cls(**keep)
 
+    @property
+    def v_prediction(self):
+        return self.config.prediction_type == "v_prediction"
+
     def _leading(self, n, extra=0):
+        if self.config.timestep_spacing == "trailing":
+            raise ValueError(f"{type(self).__name__} does not implement timestep_spacing='trailing' "
+                             "(DDIM, euler and the DPM++ 2M family do)")
         T = self.config.num_train_timesteps
         ratio = T // (n + extra)
         ts = (np.arange(0, n + extra) * ratio).round()[::-1].copy().astype(np.int64)
         return ts + self.config.steps_offset
+
+    def _trailing(self, n):
+        T = self.config.num_train_timesteps
+        return np.round(np.arange(T, 0, -T / n)).astype(np.int64) - 1
+
+    @staticmethod
+    def _eps_from_v(v, x, a, s):
+        """v-prediction -> epsilon in the space where x = a x0 + s eps (a^2 + s^2 = 1): eps = a v + s x."""
+        return float(a) * v.float() + float(s) * x.float()
+
+    @staticmethod
+    def _plan_from_v(plan, a, s):
+        """The same affine update written for a model that predicts v: eps = a v + s x substituted."""
+        return FusedPlan(in_scale=plan.in_scale, c_x=float(plan.c_x + plan.c_eps * s), c_eps=float(plan.c_eps * a),
+                         c_hist=plan.c_hist, h_x=float(plan.h_x + plan.h_eps * s), h_eps=float(plan.h_eps * a),
+                         use_hist=plan.use_hist)
 
     def scale_model_input(self, sample, timestep=None):
         return sample
@@ -96,6 +148,8 @@ class _Base:
 
 class DDIMScheduler(_Base):
     """eta = 0 DDIM."""
+    zero_snr = True
+    trailing = True
 
     def __init__(self, **kw):
         kw.setdefault("timestep_spacing", "leading")
@@ -104,14 +158,25 @@ class DDIMScheduler(_Base):
 
     def set_timesteps(self, num_inference_steps, device=None, **kw):
         self.num_inference_steps = num_inference_steps
-        self.timesteps = torch.from_numpy(self._leading(num_inference_steps)).to(device)
+        trailing = self.config.timestep_spacing == "trailing"
+        ts = self._trailing(num_inference_steps) if trailing else self._leading(num_inference_steps)
+        self.timesteps = torch.from_numpy(ts).to(device)
 
     def step_coefficients(self, timestep):
-        """x_prev = c_x * x + c_eps * eps (DDIM eta=0 as one affine update)."""
+        """x_prev = c_x * x + c_eps * model_output (DDIM eta=0 as one affine update), for the configured
+        prediction type.  v-prediction: x0 = a x - s v, eps = a v + s x (a = sqrt(alpha-bar_t), s = sqrt(1 - alpha-bar_t)),
+        which stays finite at alpha-bar_t = 0 (zero terminal SNR) where epsilon-prediction does not."""
         t = int(timestep)
         prev = t - self.config.num_train_timesteps // self.num_inference_steps
         a_t = self.ac[t]
         a_prev = self.ac[prev] if prev >= 0 else self.final_alpha_cumprod
+        if self.v_prediction:
+            a, s_ = a_t ** 0.5, (1 - a_t) ** 0.5
+            ap, sp = a_prev ** 0.5, (1 - a_prev) ** 0.5
+            return float(ap * a + sp * s_), float(sp * a - ap * s_)
+        if a_t <= 0.0:
+            raise ValueError(f"epsilon-prediction cannot step from timestep {t}: alpha-bar is 0 there (zero terminal SNR "
+                             "needs prediction_type='v_prediction')")
         c_x = (a_prev / a_t) ** 0.5
         c_eps = (1 - a_prev) ** 0.5 - (a_prev * (1 - a_t) / a_t) ** 0.5
         return float(c_x), float(c_eps)
@@ -131,6 +196,7 @@ class DDIMScheduler(_Base):
 
 class DPMSolverMultistepScheduler(_Base):
     """DPM-Solver++(2M), midpoint, lower_order_final, final sigma 0 ("DPM++ 2M" in the registry)."""
+    trailing = True
 
     def __init__(self, **kw):
         kw.setdefault("timestep_spacing", "linspace")
@@ -141,6 +207,8 @@ class DPMSolverMultistepScheduler(_Base):
         T = self.config.num_train_timesteps
         if self.config.timestep_spacing == "linspace":
             ts = np.linspace(0, T - 1, n + 1).round()[::-1][:-1].copy().astype(np.int64)
+        elif self.config.timestep_spacing == "trailing":
+            ts = self._trailing(n)
         else:
             ts = self._leading(n, extra=1)[:-1]
         sig_all = ((1 - self.ac) / self.ac) ** 0.5
@@ -174,8 +242,9 @@ class DPMSolverMultistepScheduler(_Base):
             r0 = (lam0 - (np.log(a1) - np.log(sg1))) / h
             b = -a_t * em1 * (1.0 + 0.5 / r0)
             c_hist = 0.5 * a_t * em1 / r0
-        return FusedPlan(in_scale=1.0, c_x=float(sg_t / sg0 + b * h_x), c_eps=float(b * h_eps), c_hist=float(c_hist),
+        plan = FusedPlan(in_scale=1.0, c_x=float(sg_t / sg0 + b * h_x), c_eps=float(b * h_eps), c_hist=float(c_hist),
                          h_x=float(h_x), h_eps=float(h_eps), use_hist=True)
+        return self._plan_from_v(plan, a0, sg0) if self.v_prediction else plan
 
     def fused_commit(self):
         self._fused_hist = True
@@ -187,6 +256,8 @@ class DPMSolverMultistepScheduler(_Base):
         a0, sg0 = self._alpha_sigma(self.sigmas[i])
         a_t, sg_t = self._alpha_sigma(self.sigmas[i + 1])
         x = sample.float()
+        if self.v_prediction:
+            model_output = self._eps_from_v(model_output, sample, a0, sg0)
         m0 = (x - sg0 * model_output.float()) / a0
         lam0 = np.log(a0) - np.log(sg0)
         lam_t = np.log(a_t) - np.log(sg_t) if sg_t > 0 else np.inf
@@ -208,6 +279,9 @@ class DPMSolverMultistepScheduler(_Base):
 
 class EulerDiscreteScheduler(_Base):
     """The reference's default scheduler (stable_diffusion.py:135-138)."""
+    zero_snr = True
+    zero_snr_floor = 2.0 ** -24   # sigma_T = sqrt(1 / floor - 1) ~ 4096 (recalled from diffusers, unpinned: DESIGN.md section 8)
+    trailing = True
 
     def __init__(self, **kw):
         kw.setdefault("timestep_spacing", "leading")
@@ -215,7 +289,8 @@ class EulerDiscreteScheduler(_Base):
 
     def set_timesteps(self, num_inference_steps, device=None, **kw):
         n = num_inference_steps
-        ts = self._leading(n).astype(np.float64)
+        trailing = self.config.timestep_spacing == "trailing"
+        ts = (self._trailing(n) if trailing else self._leading(n)).astype(np.float64)
         sig_all = ((1 - self.ac) / self.ac) ** 0.5
         sig = np.interp(ts, np.arange(0, len(sig_all)), sig_all)
         self.sigmas = np.concatenate([sig, [0.0]])
@@ -243,11 +318,18 @@ class EulerDiscreteScheduler(_Base):
             s = s.unsqueeze(-1)
         return (original.float() + s * noise.float()).to(original.dtype)
 
+    @staticmethod
+    def _v_terms(s):
+        """(a, b) of eps = a v + b x for the UNSCALED sample x (the model saw x / sqrt(sigma^2 + 1)):
+        eps = v / sqrt(sigma^2 + 1) + sigma x / (sigma^2 + 1)."""
+        return 1.0 / (s * s + 1) ** 0.5, s / (s * s + 1)
+
     def fused_plan(self, timestep=None):
         i = self._begin(timestep)
         s, s_next = self.sigmas[i], self.sigmas[i + 1]
-        return FusedPlan(in_scale=float(1.0 / (s * s + 1) ** 0.5), c_x=1.0, c_eps=float(s_next - s), c_hist=0.0,
+        plan = FusedPlan(in_scale=float(1.0 / (s * s + 1) ** 0.5), c_x=1.0, c_eps=float(s_next - s), c_hist=0.0,
                          h_x=0.0, h_eps=0.0, use_hist=False)
+        return self._plan_from_v(plan, *self._v_terms(s)) if self.v_prediction else plan
 
     def fused_commit(self):
         self._i += 1
@@ -255,7 +337,14 @@ class EulerDiscreteScheduler(_Base):
     def step(self, model_output, timestep, sample, return_dict=False, **kw):
         i = self._begin(timestep)
         s, s_next = self.sigmas[i], self.sigmas[i + 1]
-        prev = (sample.float() + model_output.float() * float(s_next - s)).to(sample.dtype)
+        if self.v_prediction:
+            # x + eps (s_next - s) with eps = a v + b x, collected on the host in float64: at a zero-terminal-SNR sigma
+            # (~4096) the two x terms cancel to 1 part in 300, which fp32 tensors would pay for
+            a, b = self._v_terms(s)
+            prev = (float(1.0 + b * (s_next - s)) * sample.float() + float(a * (s_next - s)) * model_output.float())
+            prev = prev.to(sample.dtype)
+        else:
+            prev = (sample.float() + model_output.float() * float(s_next - s)).to(sample.dtype)
         self._i += 1
         return (prev,) if not return_dict else SimpleNamespace(prev_sample=prev)
 
@@ -266,6 +355,7 @@ class EulerAncestralDiscreteScheduler(EulerDiscreteScheduler):
     from torch's global generator on the sample's device; `generator=` / `noise=` are accepted for tests."""
 
     supports_fused = False                    # stochastic: no affine device step
+    zero_snr = False
 
     def step(self, model_output, timestep, sample, return_dict=False, generator=None, noise=None, **kw):
         i = self._begin(timestep)
@@ -273,7 +363,11 @@ class EulerAncestralDiscreteScheduler(EulerDiscreteScheduler):
         s_up = (s_to ** 2 * (s ** 2 - s_to ** 2) / s ** 2) ** 0.5
         s_down = (s_to ** 2 - s_up ** 2) ** 0.5
         x = sample.float()
-        prev = x + model_output.float() * float(s_down - s)      # derivative (x - x0) / sigma = eps
+        if self.v_prediction:
+            a, b = self._v_terms(s)                              # as in EulerDiscreteScheduler.step
+            prev = float(1.0 + b * (s_down - s)) * x + float(a * (s_down - s)) * model_output.float()
+        else:
+            prev = x + model_output.float() * float(s_down - s)  # derivative (x - x0) / sigma = eps
         if noise is None:
             noise = torch.randn(sample.shape, generator=generator, device=sample.device, dtype=sample.dtype)
         prev = prev + noise.float() * float(s_up)
@@ -331,6 +425,8 @@ class DPMSolverSDEScheduler(DPMSolverMultistepScheduler):
         a0, sg0 = self._alpha_sigma(self.sigmas[i])
         a_t, sg_t = self._alpha_sigma(self.sigmas[i + 1])
         x = sample.float()
+        if self.v_prediction:
+            model_output = self._eps_from_v(model_output, sample, a0, sg0)
         m0 = (x - sg0 * model_output.float()) / a0
         lam0 = np.log(a0) - np.log(sg0)
         lam_t = np.log(a_t) - np.log(sg_t) if sg_t > 0 else np.inf
@@ -380,6 +476,8 @@ class PNDMScheduler(_Base):
         t = int(timestep)
         ratio = self.config.num_train_timesteps // self.num_inference_steps
         prev_t = t - ratio
+        if self.v_prediction:                 # converted at the timestep and sample the model saw, then PLMS on eps
+            model_output = self._eps_from_v(model_output, sample, self.ac[t] ** 0.5, (1 - self.ac[t]) ** 0.5)
         eps = model_output.float()
         x = sample.float()
         if self.counter != 1:
@@ -487,6 +585,8 @@ class UniPCMultistepScheduler(_Base):
         n = len(self.timesteps)
         x = sample.float()
         a_i, sg_i, _ = self._al(self.sigmas[i])
+        if self.v_prediction:
+            model_output = self._eps_from_v(model_output, sample, a_i, sg_i)
         x0 = (x - float(sg_i) * model_output.float()) / float(a_i)
         if i > 0 and self.last_sample is not None:
             x = self._correct(x0, self.last_sample, self.this_order)
