@@ -317,9 +317,21 @@ int sd_probe_copy(int64_t bytes, int iters, float* gbs, void* stream);
  * own (an activation operand); shared bit 1: the same walk with ordinary 16-byte loads into registers.  *gbs = aggregate GB/s.  DESIGN.md section 4 reads the GEMM family's ceiling against it. */
 int sd_probe_lds_dma(int64_t region_bytes, int passes, int depth, int shared, float* gbs, void* stream);
 
-/* Tuner / test hook: force the LDS-DMA conv kernel's tile variant (0..5) and split-K factor for
- * every following launch; variant -1 restores the built-in per-shape choice. */
+/* Tuner / test hook: force the LDS-DMA conv kernel's tile variant (an id of the variant table in csrc/igemm2.hip)
+ * and split-K factor for every following launch; variant -1 restores the built-in per-shape choice. */
 int sd_igemm_force(int variant, int splits);
+/* Tuner / test hook, host only (no device needed): how a convolution / linear launch would be planned.
+ *   geom[9]   = N, H, W, Cin, Cout, ksize, stride, upsample2x, pad (-1: the kernel size's default)
+ *   flags[10] = geglu, act, residual present, row add present, bias present, ln_parts (> 0: LayerNorm folded in, that
+ *               many statistics parts per row), row statistics wanted, GroupNorm summaries wanted for that many
+ *               groups, GroupNorm of the input fused in with that many groups, scaled epilogue
+ *   out[12]   = kind (the variant id that runs, 100: persistent GEGLU, -1: not an LDS-DMA problem), variant (the tile
+ *               the choice landed on), split-K slices, split-K workspace in floats, row statistics from the epilogue
+ *               (0 / 1), their parts per row, columns per part, GroupNorm summaries from the launch (0 / 1), pixels per
+ *               summary, scales honoured (0 / 1), tile rows, tile columns
+ *   name[64]  = the kernel's name as rocprofv3 prints it
+ * Returns SD_ERR_INVALID with "igemm2: bad variant" when a forced id is not in the table. */
+int sd_igemm_plan(const int* geom, const int* flags, int64_t* out, char* name);
 
 /* -- single operators, exported for the parity tests (tests/test_ops_gpu.py) ----------------- */
 /* Implicit-GEMM convolution / linear on NHWC f16:

@@ -436,6 +436,40 @@ int sd_probe_copy(int64_t bytes, int iters, float* gbs, void* stream) {
 // ------------------------------------------------------------------------------------------ tuning
 int sd_igemm_force(int variant, int splits) { igemm2_force(variant, splits); return SD_OK; }
 
+int sd_igemm_plan(const int* geom, const int* flags, int64_t* out, char* name) {
+    if (!geom || !flags || !out || !name) { set_error("sd_igemm_plan: null argument"); return SD_ERR_INVALID; }
+    const int N = geom[0], H = geom[1], W = geom[2], Cin = geom[3], Cout = geom[4], ks = geom[5], stride = geom[6], up = geom[7];
+    if (N < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1 || (ks != 1 && ks != 3) || stride < 1 || up < 0 || up > 1) {
+        set_error("sd_igemm_plan: bad geometry"); return SD_ERR_INVALID;
+    }
+    float* const set = reinterpret_cast<float*>(8);          // "present": the planner only asks whether a pointer is set
+    const half_t* const seth = reinterpret_cast<const half_t*>(set);
+    IGemmParams p{};
+    p.x = seth; p.ldx = Cin; p.w = seth; p.y = reinterpret_cast<half_t*>(set);
+    p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.KS = ks; p.stride = stride; p.up = up;
+    p.pad = geom[8] >= 0 ? geom[8] : (ks == 3 ? 1 : 0);
+    const int IH = H << up, IW = W << up;                    // output size as op_conv derives it
+    if (stride == 1) { p.OH = IH; p.OW = IW; }
+    else if (p.pad == 0) { p.OH = (IH + 1 - ks) / stride + 1; p.OW = (IW + 1 - ks) / stride + 1; }
+    else { p.OH = (IH + 2 * p.pad - ks) / stride + 1; p.OW = (IW + 2 * p.pad - ks) / stride + 1; }
+    p.M = N * p.OH * p.OW; p.K = ks * ks * Cin;
+    p.geglu = flags[0]; p.act = flags[1];
+    p.ldy = p.geglu ? Cout / 2 : Cout;
+    if (flags[2]) { p.res = seth; p.ldres = p.ldy; }
+    if (flags[3]) { p.rowadd = set; p.rowadd_ld = Cout; }
+    if (flags[4]) p.bias = set;
+    if (flags[5] > 0) { p.ln_stat = set; p.ln_parts = flags[5]; p.ln_part_w = (p.K + flags[5] - 1) / flags[5]; p.ln_C = p.K; p.ln_eps = 1e-5f; p.ln_wsum = set; }
+    if (flags[8] > 0) { p.gni_part = set; p.gni_S = 1; p.gni_rows = (long)H * W; p.gni_groups = flags[8]; p.gni_eps = 1e-5f; p.gni_gb = set; }
+    if (flags[9]) { p.acc_scale = 0.5f; p.bias_scale = 0.5f; }
+    const IGemmPlan pl = igemm2_plan(p, IGemmRequest{flags[6] ? set : nullptr, flags[7] > 0 ? set : nullptr, flags[7]});
+    if (pl.kind == kKindBadVariant) return SD_ERR_INVALID;
+    const int64_t o[12] = {pl.kind, pl.variant, pl.splits, pl.partial_floats, pl.rowstats, pl.rs_parts, pl.rs_part_w,
+                           pl.gnstats, pl.gn_rows, pl.scales_ok, pl.bm, pl.bn};
+    for (int i = 0; i < 12; ++i) out[i] = o[i];
+    snprintf(name, 64, "%s", pl.name);
+    return SD_OK;
+}
+
 // --------------------------------------------------------------------------------------- profiling
 int sd_prof_enable(int on) { prof_enable(on != 0); return SD_OK; }
 int sd_prof_collect(sd_prof_entry* out, int max_entries, int* n_entries) {
@@ -470,7 +504,7 @@ struct DevScope {
     } while (0)
 
 // Optional GroupNorm behind the convolution (sd_op_conv2d_groupnorm): the conv's epilogue leaves the
-// GroupNorm summaries when the launch can (igemm2_emits_gnstats), the GroupNorm then skips its own pass.
+// GroupNorm summaries when the launch can (IGemmPlan::gnstats), the GroupNorm then skips its own pass.
 struct GnTail {
     const float* gamma; const float* beta; void* y; int groups; float eps; int silu; int* fused;
 };
@@ -481,6 +515,27 @@ struct GnTail {
 struct GnHead {
     const float* gamma; const float* beta; int groups; float eps; int silu; int* fused;
 };
+
+// [hidden | gate] rows (half_rows each) -> every 128-row group = 64 hidden rows, then their 64 gate rows, weights
+// [.][K] and bias alike: mirrors WeightStore::pack_geglu.
+static int geglu_interleave(half_t* wg, float* bg, const half_t* w, const float* b, long half_rows, long K, hipStream_t s) {
+    for (long blk = 0; blk < half_rows / 64; ++blk) {
+        SD_HIP_CHECK(hipMemcpyAsync(wg + blk * 128 * K, w + blk * 64 * K, (size_t)64 * K * 2, hipMemcpyDeviceToDevice, s));
+        SD_HIP_CHECK(hipMemcpyAsync(wg + (blk * 128 + 64) * K, w + (half_rows + blk * 64) * K, (size_t)64 * K * 2, hipMemcpyDeviceToDevice, s));
+        SD_HIP_CHECK(hipMemcpyAsync(bg + blk * 128, b + blk * 64, 64 * 4, hipMemcpyDeviceToDevice, s));
+        SD_HIP_CHECK(hipMemcpyAsync(bg + blk * 128 + 64, b + half_rows + blk * 64, 64 * 4, hipMemcpyDeviceToDevice, s));
+    }
+    return 0;
+}
+
+// y[M, ldy] = x[M, K] W^T + bias as a pointwise problem of Cout GEMM columns (one image of M x 1 pixels)
+static IGemmParams pointwise_params(const half_t* x, const half_t* w, const float* bias, half_t* y, long ldy, int M, int K, int Cout) {
+    IGemmParams p{};
+    p.x = x; p.ldx = K; p.w = w; p.bias = bias; p.y = y; p.ldy = ldy;
+    p.N = 1; p.H = M; p.W = 1; p.Cin = K; p.OH = M; p.OW = 1; p.Cout = Cout; p.KS = 1; p.stride = 1; p.pad = 0; p.up = 0;
+    p.M = M; p.K = K;
+    return p;
+}
 
 static int conv2d_impl(const void* x, const void* w_oihw, const void* bias_f32, const void* rowadd_f32, const void* res,
                        void* y, int N, int H, int W, int Cin, int Cout, int ksize, int stride, int upsample2x,
@@ -501,19 +556,12 @@ static int conv2d_impl(const void* x, const void* w_oihw, const void* bias_f32, 
     if (!rc && bias_f32)
         SD_HIP_CHECK(hipMemcpyAsync(bp, bias_f32, (size_t)Cout * sizeof(float), hipMemcpyDeviceToDevice, s));
     if (!rc && geglu) {
-        // interleave hidden / gate rows per 64 exactly as WeightStore::pack_geglu does
         half_t* wg = nullptr; float* bg = nullptr;
         SD_DEV_ALLOC(scope, wg, (size_t)rows * K * sizeof(half_t));
         SD_DEV_ALLOC(scope, bg, (size_t)rows * sizeof(float));
         SD_HIP_CHECK(hipMemsetAsync(wg, 0, (size_t)rows * K * sizeof(half_t), s));
         SD_HIP_CHECK(hipMemsetAsync(bg, 0, (size_t)rows * sizeof(float), s));
-        const long half_rows = Cout / 2;
-        for (long blk = 0; blk < half_rows / 64; ++blk) {
-            SD_HIP_CHECK(hipMemcpyAsync(wg + blk * 128 * K, wp + blk * 64 * K, (size_t)64 * K * 2, hipMemcpyDeviceToDevice, s));
-            SD_HIP_CHECK(hipMemcpyAsync(wg + (blk * 128 + 64) * K, wp + (half_rows + blk * 64) * K, (size_t)64 * K * 2, hipMemcpyDeviceToDevice, s));
-            SD_HIP_CHECK(hipMemcpyAsync(bg + blk * 128, bp + blk * 64, 64 * 4, hipMemcpyDeviceToDevice, s));
-            SD_HIP_CHECK(hipMemcpyAsync(bg + blk * 128 + 64, bp + half_rows + blk * 64, 64 * 4, hipMemcpyDeviceToDevice, s));
-        }
+        if (int r = geglu_interleave(wg, bg, wp, bp, Cout / 2, K, s)) return r;
         SD_HIP_CHECK(hipStreamSynchronize(s));
         scope.drop(wp); scope.drop(bp);
         wp = wg; bp = bg;
@@ -533,24 +581,12 @@ static int conv2d_impl(const void* x, const void* w_oihw, const void* bias_f32, 
         p.Cout = Cout; p.M = N * p.OH * p.OW; p.K = (int)K; p.geglu = geglu;
         const int ocols = geglu ? Cout / 2 : Cout;
         p.ldres = ocols; p.y = static_cast<half_t*>(y); p.ldy = ocols;
-        const bool v2 = igemm2_supported(p);
-        if (v2) {
-            const long pf = igemm2_partial_floats(p);
-            if (pf > 0) SD_DEV_ALLOC(scope, partial, (size_t)pf * sizeof(float));
-        }
         float* gnbuf = nullptr;
         float* gnscratch = nullptr;
-        GnStats gst;
         if (gn) {
-            int rows = 0;
             if (gn->fused) *gn->fused = 0;
             SD_DEV_ALLOC(scope, gnscratch, (size_t)gn_scratch_floats(N, (long)p.OH * p.OW, Cout, gn->groups) * 4);
-            if (igemm2_emits_gnstats(p, gn->groups, &rows)) {
-                SD_DEV_ALLOC(scope, gnbuf, (size_t)gnstat_floats(N, (long)p.OH * p.OW, gn->groups) * 4);
-                p.gnstat_out = gnbuf; p.gn_groups = gn->groups;
-                gst.part = gnbuf; gst.rows = rows; gst.S = p.OH * p.OW / rows;
-                if (gn->fused) *gn->fused = 1;
-            }
+            SD_DEV_ALLOC(scope, gnbuf, (size_t)gnstat_floats(N, (long)p.OH * p.OW, gn->groups) * 4);
         }
         if (gh) {
             if (gh->fused) *gh->fused = 0;
@@ -572,10 +608,6 @@ static int conv2d_impl(const void* x, const void* w_oihw, const void* bias_f32, 
                 p.gni_part = st.part; p.gni_S = st.S; p.gni_rows = st.rows; p.gni_groups = gh->groups; p.gni_eps = gh->eps;
                 p.gni_silu = gh->silu; p.gni_gb = gb;
                 if (gh->fused) *gh->fused = 1;
-                if (v2 && !partial) {
-                    const long pf = igemm2_partial_floats(p);
-                    if (pf > 0) SD_DEV_ALLOC(scope, partial, (size_t)pf * sizeof(float));
-                }
             } else {
                 half_t* hn = nullptr;
                 SD_DEV_ALLOC(scope, hn, (size_t)N * HW * Cin * sizeof(half_t));
@@ -583,17 +615,24 @@ static int conv2d_impl(const void* x, const void* w_oihw, const void* bias_f32, 
                 p.x = hn;
             }
         }
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (ms_out) { SD_HIP_CHECK(hipEventCreate(&e0)); SD_HIP_CHECK(hipEventCreate(&e1)); }
-        // SD_BENCH_COLD_MB=<n> (tuner): rotate through copies of the packed weights totalling n MB, so
-        // every timed launch streams its weights from HBM as it does inside a UNet forward (1.7 GB of
-        // weights per forward never stay in the 256 MB Infinity Cache); unset = same buffer every launch.
         half_t* res_bench = nullptr;   // SD_BENCH_RES=1 (tuner): time the launch with the fused residual add
         if (ms_out && !res && getenv("SD_BENCH_RES")) {
             SD_DEV_ALLOC(scope, res_bench, (size_t)p.M * ocols * sizeof(half_t));
             SD_HIP_CHECK(hipMemsetAsync(res_bench, 0, (size_t)p.M * ocols * sizeof(half_t), s));
             p.res = res_bench;
         }
+        const IGemmPlan plan = igemm2_plan(p, IGemmRequest{nullptr, gnbuf, gn ? gn->groups : 0});
+        if (plan.partial_floats > 0) SD_DEV_ALLOC(scope, partial, (size_t)plan.partial_floats * sizeof(float));
+        GnStats gst;
+        if (plan.gnstats) {
+            gst.part = gnbuf; gst.rows = plan.gn_rows; gst.S = p.OH * p.OW / plan.gn_rows;
+            if (gn->fused) *gn->fused = 1;
+        }
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        if (ms_out) { SD_HIP_CHECK(hipEventCreate(&e0)); SD_HIP_CHECK(hipEventCreate(&e1)); }
+        // SD_BENCH_COLD_MB=<n> (tuner): rotate through copies of the packed weights totalling n MB, so
+        // every timed launch streams its weights from HBM as it does inside a UNet forward (1.7 GB of
+        // weights per forward never stay in the 256 MB Infinity Cache); unset = same buffer every launch.
         half_t* wring = nullptr;
         long nrot = 1;
         const size_t wbytes = (size_t)rows * K * sizeof(half_t);
@@ -614,7 +653,7 @@ static int conv2d_impl(const void* x, const void* w_oihw, const void* bias_f32, 
         for (int it = 0; it < iters + (ms_out ? 2 : 0) && !rc; ++it) {
             if (ms_out && it == 2) SD_HIP_CHECK(hipEventRecord(e0, s));     // two warm-up launches
             if (wring) p.w = reinterpret_cast<half_t*>(reinterpret_cast<char*>(wring) + wbytes * (size_t)(it % nrot));
-            rc = v2 ? launch_igemm2(p, partial, s) : launch_igemm(p, s);
+            rc = launch_igemm2(p, partial, s, &plan);
         }
         if (gn && !rc)
             rc = launch_groupnorm(p.y, p.ldy, gn->gamma, gn->beta, static_cast<half_t*>(gn->y), Cout, N, (long)p.OH * p.OW, Cout,
@@ -703,15 +742,7 @@ static int ffn_geglu_impl(const void* x, const float* x_stat, int stat_parts, in
     SD_HIP_CHECK(hipMemsetAsync(wsum, 0, (size_t)r1 * 4, s));
     SD_HIP_CHECK(hipMemsetAsync(w2p, 0, (size_t)r2 * H4 * 2, s));
     SD_HIP_CHECK(hipMemsetAsync(b2p, 0, (size_t)r2 * 4, s));
-    // the GEGLU packing of WeightStore::pack_geglu: every 128-row group = 64 hidden rows, then their 64 gate rows
-    const half_t* w1h = static_cast<const half_t*>(w1);
-    const float* b1f = static_cast<const float*>(b1);
-    for (long blk = 0; blk < H4 / 64; ++blk) {
-        SD_HIP_CHECK(hipMemcpyAsync(wg + blk * 128 * C, w1h + blk * 64 * C, (size_t)64 * C * 2, hipMemcpyDeviceToDevice, s));
-        SD_HIP_CHECK(hipMemcpyAsync(wg + (blk * 128 + 64) * C, w1h + (H4 + blk * 64) * C, (size_t)64 * C * 2, hipMemcpyDeviceToDevice, s));
-        SD_HIP_CHECK(hipMemcpyAsync(bg + blk * 128, b1f + blk * 64, 64 * 4, hipMemcpyDeviceToDevice, s));
-        SD_HIP_CHECK(hipMemcpyAsync(bg + blk * 128 + 64, b1f + H4 + blk * 64, 64 * 4, hipMemcpyDeviceToDevice, s));
-    }
+    if (int r = geglu_interleave(wg, bg, static_cast<const half_t*>(w1), static_cast<const float*>(b1), H4, C, s)) return r;
     SD_HIP_CHECK(hipMemcpyAsync(w2p, w2, (size_t)C * H4 * 2, hipMemcpyDeviceToDevice, s));
     SD_HIP_CHECK(hipMemcpyAsync(b2p, b2, (size_t)C * 4, hipMemcpyDeviceToDevice, s));
     int rc = launch_ln_fold(wg, C, (int)O1, static_cast<const float*>(ln_gamma), static_cast<const float*>(ln_beta), bg, nb, wsum, 0, 1.0f, s);
@@ -727,19 +758,17 @@ static int ffn_geglu_impl(const void* x, const float* x_stat, int stat_parts, in
     p.M = M; p.C = C; p.hidden = (int)H4;
     const bool use_fused = ffn_fused_supported(p);
     if (fused) *fused = use_fused ? 1 : 0;
-    IGemmParams g1{}, g2{};                // the two-GEMM form: projection with its GEGLU epilogue, output linear with its residual
+    // the two-GEMM form: projection with its GEGLU epilogue, output linear with its residual
     if (!use_fused || ms_per_launch) SD_DEV_ALLOC(scope, hid, (size_t)M * H4 * 2);
-    g1.x = p.x; g1.ldx = C; g1.w = wg; g1.bias = nb; g1.y = hid; g1.ldy = H4; g1.N = 1; g1.H = M; g1.W = 1; g1.Cin = C; g1.OH = M; g1.OW = 1;
-    g1.Cout = (int)O1; g1.KS = 1; g1.stride = 1; g1.pad = 0; g1.up = 0; g1.M = M; g1.K = C; g1.geglu = 1;
+    IGemmParams g1 = pointwise_params(p.x, wg, nb, hid, H4, M, C, (int)O1);
+    g1.geglu = 1;
     g1.ln_stat = st; g1.ln_parts = parts; g1.ln_part_w = part_w; g1.ln_C = C; g1.ln_eps = ln_eps; g1.ln_wsum = wsum;
-    g2.x = hid; g2.ldx = H4; g2.w = w2p; g2.bias = b2p; g2.res = p.x; g2.ldres = C; g2.y = p.y; g2.ldy = C; g2.N = 1; g2.H = M; g2.W = 1;
-    g2.Cin = (int)H4; g2.OH = M; g2.OW = 1; g2.Cout = C; g2.KS = 1; g2.stride = 1; g2.pad = 0; g2.up = 0; g2.M = M; g2.K = (int)H4;
+    IGemmParams g2 = pointwise_params(hid, w2p, b2p, p.y, C, M, (int)H4, C);
+    g2.res = p.x; g2.ldres = C;
+    const IGemmPlan plan1 = igemm2_plan(g1), plan2 = igemm2_plan(g2);
     float* partial = nullptr;
-    if (!use_fused || ms_per_launch) {
-        const long pf = igemm2_partial_floats(g2);
-        if (pf > 0) SD_DEV_ALLOC(scope, partial, (size_t)pf * 4);
-    }
-    auto two_gemms = [&]() { int r = launch_igemm2(g1, nullptr, s); return r ? r : launch_igemm2(g2, partial, s); };
+    if ((!use_fused || ms_per_launch) && plan2.partial_floats > 0) SD_DEV_ALLOC(scope, partial, (size_t)plan2.partial_floats * 4);
+    auto two_gemms = [&]() { int r = launch_igemm2(g1, nullptr, s, &plan1); return r ? r : launch_igemm2(g2, partial, s, &plan2); };
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (ms_per_launch) { SD_HIP_CHECK(hipEventCreate(&e0)); SD_HIP_CHECK(hipEventCreate(&e1)); }
     const int n = ms_per_launch ? iters + 2 : 1;
@@ -792,7 +821,7 @@ int sd_op_ln_ffn_geglu(const void* x, const float* stat, int parts, int part_w, 
 // The folded-LayerNorm chain of a transformer block at op level (unet.cpp run_xformer), in two calls that share the
 // row-statistics buffer so a test can force the producer's and the consumer's kernel separately (sd_igemm_force).
 // Producer: y1 = x W0^T + b0 (+ res) with op_conv's rule for the statistics: from the GEMM epilogue when the launch
-// can emit them (igemm2_emits_rowstats), row_stats_kernel over y1 otherwise.
+// can emit them (IGemmPlan::rowstats), row_stats_kernel over y1 otherwise.
 int sd_op_linear_rowstats(const void* x, const void* w0, const void* b0, const void* res, void* y1, float* stat, int M,
                           int K, int C, int* parts, int* part_w, int* producer, void* stream) {
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -810,20 +839,15 @@ int sd_op_linear_rowstats(const void* x, const void* w0, const void* b0, const v
     int rc = launch_pack_conv(static_cast<const half_t*>(w0), wp, C, K, 1, 1, K, s);
     if (rc) return rc;
     if (b0) SD_HIP_CHECK(hipMemcpyAsync(bp, b0, (size_t)C * 4, hipMemcpyDeviceToDevice, s));
-    IGemmParams p{};
-    p.x = static_cast<const half_t*>(x); p.ldx = K; p.w = wp; p.bias = bp;
-    p.res = static_cast<const half_t*>(res); p.ldres = C; p.y = static_cast<half_t*>(y1); p.ldy = C;
-    p.N = 1; p.H = M; p.W = 1; p.Cin = K; p.OH = M; p.OW = 1; p.Cout = C; p.KS = 1; p.stride = 1; p.pad = 0; p.up = 0;
-    p.M = M; p.K = K;
-    int np = 1, w = C;
-    const bool own = igemm2_emits_rowstats(p, &np, &w);
-    if (own) p.rowstat_out = stat;
-    const long pf = igemm2_partial_floats(p);
-    if (pf > 0) SD_DEV_ALLOC(scope, partial, (size_t)pf * 4);
-    *producer = own ? igemm2_launch_kind(p, partial != nullptr) : -1;
-    *parts = own ? np : 1;
-    *part_w = own ? w : C;
-    rc = launch_igemm2(p, partial, s);
+    IGemmParams p = pointwise_params(static_cast<const half_t*>(x), wp, bp, static_cast<half_t*>(y1), C, M, K, C);
+    p.res = static_cast<const half_t*>(res); p.ldres = C;
+    const IGemmPlan plan = igemm2_plan(p, IGemmRequest{stat});
+    const bool own = plan.rowstats;
+    if (plan.partial_floats > 0) SD_DEV_ALLOC(scope, partial, (size_t)plan.partial_floats * 4);
+    *producer = own ? plan.kind : -1;
+    *parts = plan.rs_parts;
+    *part_w = plan.rs_part_w;
+    rc = launch_igemm2(p, partial, s, &plan);
     if (!rc && !own) rc = launch_row_stats(p.y, C, stat, M, C, s);
     hipError_t e = hipStreamSynchronize(s);
     if (!rc && e != hipSuccess) { set_error(hipGetErrorString(e)); rc = SD_ERR_HIP; }
@@ -858,28 +882,22 @@ int sd_op_ln_linear(const void* y1, const float* stat, int parts, int part_w, co
     if (rc) return rc;
     if (b1) SD_HIP_CHECK(hipMemcpyAsync(bp, b1, (size_t)cols * 4, hipMemcpyDeviceToDevice, s));
     wf = wp; bf = bp;
-    if (geglu) {            // every 128-row group = 64 hidden rows, then their 64 gate rows (WeightStore::pack_geglu)
+    if (geglu) {
         SD_DEV_ALLOC(scope, wf, (size_t)rows * C * 2);
         SD_DEV_ALLOC(scope, bf, (size_t)rows * 4);
         SD_HIP_CHECK(hipMemsetAsync(wf, 0, (size_t)rows * C * 2, s));
         SD_HIP_CHECK(hipMemsetAsync(bf, 0, (size_t)rows * 4, s));
-        for (long blk = 0; blk < O / 64; ++blk) {
-            SD_HIP_CHECK(hipMemcpyAsync(wf + blk * 128 * C, wp + blk * 64 * C, (size_t)64 * C * 2, hipMemcpyDeviceToDevice, s));
-            SD_HIP_CHECK(hipMemcpyAsync(wf + (blk * 128 + 64) * C, wp + (O + blk * 64) * C, (size_t)64 * C * 2, hipMemcpyDeviceToDevice, s));
-            SD_HIP_CHECK(hipMemcpyAsync(bf + blk * 128, bp + blk * 64, 64 * 4, hipMemcpyDeviceToDevice, s));
-            SD_HIP_CHECK(hipMemcpyAsync(bf + blk * 128 + 64, bp + O + blk * 64, 64 * 4, hipMemcpyDeviceToDevice, s));
-        }
+        if (int r = geglu_interleave(wf, bf, wp, bp, O, C, s)) return r;
     }
     rc = launch_ln_fold(wf, C, (int)cols, static_cast<const float*>(gamma), static_cast<const float*>(beta), bf, nb, wsum,
                         geglu ? 0 : rows_scaled, row_scale, s);
     if (rc) return rc;
-    IGemmParams g{};
-    g.x = static_cast<const half_t*>(y1); g.ldx = C; g.w = wf; g.bias = nb; g.y = static_cast<half_t*>(y2); g.ldy = O;
-    g.N = 1; g.H = M; g.W = 1; g.Cin = C; g.OH = M; g.OW = 1; g.Cout = (int)cols; g.KS = 1; g.stride = 1; g.pad = 0; g.up = 0;
-    g.M = M; g.K = C; g.geglu = geglu;
+    IGemmParams g = pointwise_params(static_cast<const half_t*>(y1), wf, nb, static_cast<half_t*>(y2), O, M, C, (int)cols);
+    g.geglu = geglu;
     g.ln_stat = stat; g.ln_parts = parts; g.ln_part_w = part_w; g.ln_C = C; g.ln_eps = eps; g.ln_wsum = wsum;
-    *consumer = igemm2_launch_kind(g, false);
-    rc = launch_igemm2(g, nullptr, s);
+    const IGemmPlan plan = igemm2_plan(g, IGemmRequest{nullptr, nullptr, 0, true});      // (no workspace: never split)
+    *consumer = plan.kind;
+    rc = launch_igemm2(g, nullptr, s, &plan);
     hipError_t e = hipStreamSynchronize(s);
     if (!rc && e != hipSuccess) { set_error(hipGetErrorString(e)); rc = SD_ERR_HIP; }
     return rc;

@@ -13,7 +13,7 @@
 //   * optional split-K (gridDim.y): every z-slice writes an fp32 partial slab; the epilogue kernel
 //     splitk_epilogue_kernel reduces the slabs in a fixed order (deterministic) and applies
 //     bias / time-embedding row add / residual / GEGLU.
-// Tile variants (BM x BN, waves, stages) are chosen per shape by pick_variant().
+// Tile variants (BM x BN, waves, stages): the table kVariants below; igemm2_plan chooses one per launch.
 #include <atomic>
 #include <cstdlib>
 #include <mutex>
@@ -1203,39 +1203,122 @@ int launch_v2(const IGemmParams& p, float* partial, int splits, hipStream_t s) {
 std::atomic<int> g_force_variant{-1};
 std::atomic<int> g_force_splits{0};
 
-}  // namespace
-
-// Variant ids (also used by the tuner in tests/tools): keep in sync with kIgemm2Names.
-//   0: 256x128 8 waves 3 stages   1: 128x128 4 waves 2 stages   2: 128x160 4 waves 2 stages
-//   3: 128x64 4 waves 2 stages    4: 64x64 4 waves 2 stages     5: 256x160 4 waves (4x1) 3 stages
-//   6 / 7: 256x128 / 256x160, 8 waves, staggered DMA issue
-//   10 / 15: conv3x3_halo_kernel<160> / <128> (256x160 / 256x128, A halo tile resident across the taps; 3x3 stride-1
-//          convs, W in 16/32/64; the 128-column form for the VAE's 128 / 256 / 512 widths, and it can leave
-//          GroupNorm summaries)
-//   11 / 12: 128x80 (4 x 1 waves, 2- / 3-deep ring): M = 2048, N = 1280 is exactly 256 such tiles -- one per CU at the
-//          least L2 -> LDS traffic a 256-tile grid can have there (133 MB against the 64x64 tile's 205 MB)
-//   13 / 14: wsgemm.hip -- persistent, weight-stationary 128x160 / 128x128 (GEGLU) tiles for the K = 320 pointwise
-//          problems of the 64x64 level; taken whenever wsgemm_supported() (SD_NO_WSGEMM=1 turns that off)
-//   8 / 9: 128x64 / 128x160 with a 3-deep ring: only pays on the small-M, deep-K shapes of the 8x8 and
-//          16x16 levels when their weights come cold from HBM (as they do inside a forward); with the
-//          weights cache-resident the 2-deep rings win everywhere (tools/tune_igemm.py, SD_BENCH_COLD_MB)
+// ---------------------------------------------------------------------------------------------
+// The variant table: one row per variant id.  The ids are an external contract (sd_igemm_force, the tuner's
+// profiles/tune/*.json, igemm2_table.inc, the tests): a new variant gets the next id, an id never changes its meaning.
+//   Tile: igemm2_kernel, both operands streamed through the LDS-DMA ring (BM x BN, waves M x N, ring depth)
+//   Halo: conv3x3_halo_kernel, the A halo tile resident across the nine taps (3x3 stride-1 convs, W in 16/32/64; the
+//         128-column form for the VAE's 128 / 256 / 512 widths)
+//   Ws:   wsgemm.hip, persistent weight-stationary tiles for the K = 320 pointwise problems of the 64x64 level
+//   Reg:  igemm3.hip, the activation operand through the ordinary load path into registers
+// Notes on rows: 128x80 (11, 12) -- M = 2048, N = 1280 is exactly 256 such tiles, one per CU at the least L2 -> LDS
+// traffic a 256-tile grid can have there (133 MB against the 64x64 tile's 205 MB).  The 3-deep 128x64 / 128x160 (8, 9)
+// only pay on the small-M, deep-K shapes of the 8x8 and 16x16 levels when their weights come cold from HBM (as they do
+// inside a forward); with the weights cache-resident the 2-deep rings win everywhere (tools/tune_igemm.py,
+// SD_BENCH_COLD_MB).
 // Measured and dropped in round 2 (profiles/tune/r02_deep_rings.txt): 4- and 6-deep rings on 128x64 / 64x64 /
 // 128x128 / 128x160 tiles (one block per CU, 3-5 slabs in flight) for the small-grid linears of the 16x16 /
 // 8x8 levels: 0-60 % slower than the 2- / 3-deep rings at 2-3 blocks per CU on every UNet shape.  Those
 // launches are bound by the L2 -> LDS transfer rate per CU and by their prologue + epilogue, not by the
 // per-slab round trip a deeper ring hides.  (The ring-depth template parameter still goes to 8.)
-// printf formats of the kernel names as rocprofv3 prints them (%s = the pointwise flag)
-static const char* kIgemm2Names[] = {
-    "igemm2_kernel<256,128,4,2,3,%s,false,64>", "igemm2_kernel<128,128,2,2,2,%s,false,64>",
-    "igemm2_kernel<128,160,2,2,2,%s,false,64>", "igemm2_kernel<128,64,2,2,2,%s,false,64>",
-    "igemm2_kernel<64,64,2,2,2,%s,false,64>",   "igemm2_kernel<256,160,4,1,3,%s,false,64>",
-    "igemm2_kernel<256,128,4,2,3,%s,true,64>",  "igemm2_kernel<256,160,4,2,3,%s,true,64>",
-    "igemm2_kernel<128,64,2,2,3,%s,false,64>",  "igemm2_kernel<128,160,2,2,3,%s,false,64>",
-    "conv3x3_halo_kernel<160>",
-    "igemm2_kernel<128,80,4,1,2,%s,false,64>", "igemm2_kernel<128,80,4,1,3,%s,false,64>",
-    "wsgemm_kernel<160,false,...>", "wsgemm_kernel<128,true,...>", "conv3x3_halo_kernel<128>",
-    "igemm2_kernel<128,80,4,1,4,%s,false,64>", "igemm2_kernel<128,80,4,1,5,%s,false,64>", "igemm3_kernel"};
-constexpr int kNumVariants = 19;
+// ---------------------------------------------------------------------------------------------
+enum class Family { Tile, Halo, Ws, Reg };
+struct Variant {
+    int id, bm, bn;
+    Family family;
+    bool geglu;             // takes GEGLU problems (a 128-column tile over two wave columns, or wsgemm's GEGLU form)
+    bool reg_alt;           // SD_IGEMM3=1 hands its unsplit launches to igemm3_kernel where that takes the problem
+    const char* name;       // printf format of the kernel name as rocprofv3 prints it (%s = the pointwise flag)
+    int (*launch)(const IGemmParams&, float* partial, int splits, hipStream_t);
+};
+int launch_ws(const IGemmParams& p, float*, int, hipStream_t s) { return launch_wsgemm(p, s); }
+int launch_reg(const IGemmParams& p, float*, int, hipStream_t s) { return launch_igemm3(p, weights_outweigh_activations(p), s); }
+const Variant kVariants[] = {
+    {0, 256, 128, Family::Tile, true, false, "igemm2_kernel<256,128,4,2,3,%s,false,64>", &launch_v2<256, 128, 4, 2, 3>},
+    {1, 128, 128, Family::Tile, true, false, "igemm2_kernel<128,128,2,2,2,%s,false,64>", &launch_v2<128, 128, 2, 2, 2>},
+    {2, 128, 160, Family::Tile, false, false, "igemm2_kernel<128,160,2,2,2,%s,false,64>", &launch_v2<128, 160, 2, 2, 2>},
+    {3, 128, 64, Family::Tile, false, false, "igemm2_kernel<128,64,2,2,2,%s,false,64>", &launch_v2<128, 64, 2, 2, 2>},
+    {4, 64, 64, Family::Tile, false, false, "igemm2_kernel<64,64,2,2,2,%s,false,64>", &launch_v2<64, 64, 2, 2, 2>},
+    {5, 256, 160, Family::Tile, false, false, "igemm2_kernel<256,160,4,1,3,%s,false,64>", &launch_v2<256, 160, 4, 1, 3>},
+    {6, 256, 128, Family::Tile, true, false, "igemm2_kernel<256,128,4,2,3,%s,true,64>", &launch_v2<256, 128, 4, 2, 3, true>},
+    {7, 256, 160, Family::Tile, false, false, "igemm2_kernel<256,160,4,2,3,%s,true,64>", &launch_v2<256, 160, 4, 2, 3, true>},
+    {8, 128, 64, Family::Tile, false, false, "igemm2_kernel<128,64,2,2,3,%s,false,64>", &launch_v2<128, 64, 2, 2, 3>},
+    {9, 128, 160, Family::Tile, false, false, "igemm2_kernel<128,160,2,2,3,%s,false,64>", &launch_v2<128, 160, 2, 2, 3>},
+    {10, 256, 160, Family::Halo, false, false, "conv3x3_halo_kernel<160>", &launch_halo<160>},
+    {11, 128, 80, Family::Tile, false, true, "igemm2_kernel<128,80,4,1,2,%s,false,64>", &launch_v2<128, 80, 4, 1, 2>},
+    {12, 128, 80, Family::Tile, false, true, "igemm2_kernel<128,80,4,1,3,%s,false,64>", &launch_v2<128, 80, 4, 1, 3>},
+    {13, 128, 160, Family::Ws, true, false, "wsgemm_kernel<160,false,...>", &launch_ws},      // (GEGLU: becomes 14)
+    {14, 128, 128, Family::Ws, true, false, "wsgemm_kernel<128,true,...>", &launch_ws},       // (no GEGLU: becomes 13)
+    {15, 256, 128, Family::Halo, false, false, "conv3x3_halo_kernel<128>", &launch_halo<128>},
+    {16, 128, 80, Family::Tile, false, false, "igemm2_kernel<128,80,4,1,4,%s,false,64>", &launch_v2<128, 80, 4, 1, 4>},
+    {17, 128, 80, Family::Tile, false, false, "igemm2_kernel<128,80,4,1,5,%s,false,64>", &launch_v2<128, 80, 4, 1, 5>},
+    {18, 128, 80, Family::Reg, false, false, "igemm3_kernel", &launch_reg},
+};
+constexpr int kNumVariants = sizeof(kVariants) / sizeof(kVariants[0]);
+// The rows the rules below name (the only variant numbers outside the table)
+enum : int {
+    kT256x128 = 0, kT128x128 = 1, kT128x160 = 2, kT128x64 = 3, kT64x64 = 4,       // what the heuristic chooses among
+    kHalo160 = 10, kHalo128 = 15,                   // a GroupNorm fused into the input: only the halo kernel does that
+    kWsPlain = 13, kWsGeglu = 14,                   // the weight-stationary route, by the problem's GEGLU flag
+    kHaloFallback = 7,                              // halo asked for, shape not halo-able -> 256x160 staggered
+    kGegluFallback = kT128x128,                     // a tile without the GEGLU epilogue forced on a GEGLU problem
+    kWsFallbackGeglu = kT128x128, kWsFallbackPlain = kT128x160,   // wsgemm forced on a problem it does not take
+    kReg = 18, kRegFallback = 12,                   // igemm3 asked for by id on a problem it does not take -> 128x80, 3-deep
+};
+bool valid_id(int v) { return v >= 0 && v < kNumVariants && kVariants[v].id == v; }
+bool is_halo(int v) { return kVariants[v].family == Family::Halo; }
+bool is_ws(int v) { return kVariants[v].family == Family::Ws; }
+
+// Per-shape choices measured on MI355X by tools/tune_igemm.py (profiles/tune/*.json).
+struct TunedEntry { int M, N, K, ks, stride, up, geglu, variant, splits; float us; int alt_variant; float alt_us; };   // (alt_*: unused)
+const TunedEntry kTuned[] = {
+#include "igemm2_table.inc"
+};
+
+// Tile variant + split-K for a problem, before the routes of igemm2_plan: the force override, the tuned table when the
+// shape is in it, otherwise a rule distilled from the same measurements: 128x160 tiles whenever Cout is a multiple of
+// 160 (every UNet / VAE width is), 128x128 otherwise; narrow tiles for small, shallow problems; split-K until about two
+// blocks per CU (512) are in flight, keeping >= 12 K-slabs per slice.  Does not look at the statistics requests.
+void pick_tile(const IGemmParams& p, int* variant, int* splits) {
+    if (g_force_variant.load() >= 0) {
+        int v = g_force_variant.load();
+        *splits = g_force_splits.load() > 0 ? g_force_splits.load() : 1;
+        if (p.geglu && !(valid_id(v) && kVariants[v].geglu)) v = kGegluFallback;
+        if (p.geglu || p.act) *splits = 1;
+        if (valid_id(v) && is_halo(v) && !halo_supported(p)) v = kHaloFallback;
+        *variant = v;
+        return;
+    }
+    for (const TunedEntry& e : kTuned)
+        if (!p.act && e.M == p.M && e.N == p.Cout && e.K == p.K && e.ks == p.KS && e.stride == p.stride && e.up == p.up &&
+            e.geglu == p.geglu) {
+            *variant = is_halo(e.variant) && !halo_supported(p) ? kHaloFallback : e.variant;   // (same M x N x K from another image shape)
+            *splits = e.splits;
+            return;
+        }
+    auto tiles_of = [&](int v) { return (long)cdiv(p.M, kVariants[v].bm) * cdiv(p.Cout, kVariants[v].bn); };
+    const int narrow = tiles_of(kT128x64) >= 256 ? kT128x64 : kT64x64;
+    *splits = 1;
+    if (p.act) {                 // the activation lives in the fused epilogue only: never split K
+        *variant = tiles_of(kT128x128) >= 256 ? kT128x128 : narrow;
+        return;
+    }
+    const int nk = p.K / BK;
+    int v;
+    if (p.geglu) v = tiles_of(kT256x128) >= 512 ? kT256x128 : kT128x128;
+    else v = p.Cout % 160 == 0 ? kT128x160 : kT128x128;
+    if (!p.geglu && tiles_of(v) < 256 && nk <= 40) v = narrow;      // small and shallow: narrow tiles fill more CUs
+    const long tiles = tiles_of(v);
+    if (!p.geglu && tiles < 384 && nk >= 24) {
+        int sp = (int)((512 + tiles / 2) / tiles);
+        if (sp > 8) sp = 8;
+        while (sp > 1 && nk / sp < 12) --sp;
+        *splits = sp;
+    }
+    *variant = v;
+}
+
+}  // namespace
 
 void igemm2_force(int variant, int splits) { g_force_variant = variant; g_force_splits = splits; }
 
@@ -1246,210 +1329,103 @@ bool igemm2_supported(const IGemmParams& p) {
            wrows * p.K * 2 < (1L << 31) && (!p.geglu || p.Cout % 128 == 0) && !(p.geglu && p.act);
 }
 
-static void tile_dims(int v, int* bm, int* bn) {
-    static const int dims[kNumVariants][2] = {{256, 128}, {128, 128}, {128, 160}, {128, 64}, {64, 64}, {256, 160}, {256, 128}, {256, 160},
-                                               {128, 64}, {128, 160}, {256, 160}, {128, 80}, {128, 80}, {128, 80}, {128, 128}, {256, 128},
-                                               {128, 80}, {128, 80}, {128, 80}};
-    *bm = dims[v][0]; *bn = dims[v][1];
-}
-
-// Per-shape choices measured on MI355X by tools/tune_igemm.py (profiles/tune/*.json).
-struct TunedEntry { int M, N, K, ks, stride, up, geglu, variant, splits; float us; int alt_variant; float alt_us; };
-static const TunedEntry kTuned[] = {
-#include "igemm2_table.inc"
-};
-
-// Tile variant + split-K for a problem: the tuned table when the shape is in it, otherwise a rule
-// distilled from the same measurements: 128x160 tiles whenever Cout is a multiple of 160 (every
-// UNet / VAE width is), 128x128 otherwise; narrow tiles for small, shallow problems; split-K until
-// about two blocks per CU (512) are in flight, keeping >= 12 K-slabs per slice.
-static void igemm2_pick_raw(const IGemmParams& p, int* variant, int* splits);
-
-static bool wsgemm_enabled() {
-    static const bool off = getenv("SD_NO_WSGEMM") != nullptr;
-    return !off;
-}
-
-bool igemm2_scales_ok(const IGemmParams& p) {
-    if (!igemm2_supported(p) || p.geglu) return false;
-    int v, sp;
-    igemm2_pick(p, &v, &sp);
-    return v != 13 && v != 14;
-}
-
 bool igemm2_gn_fusable(const IGemmParams& p, int groups) {
     return igemm2_supported(p) && halo_supported(p) && p.up == 0 && groups >= 1 && groups <= 32 && 512 % groups == 0 &&
            p.Cin % groups == 0;
 }
 
-void igemm2_pick(const IGemmParams& p, int* variant, int* splits) {
-    igemm2_pick_raw(p, variant, splits);
-    if (p.gni_part && *variant != 10 && *variant != 15) {
-        // a GroupNorm is applied to the input inside the kernel: only the halo kernel does that.  160 columns where they
-        // divide the width, split over the slabs until about one block per CU is in flight (>= 4 slabs per slice)
-        *variant = p.Cout % 160 == 0 ? 10 : 15;
-        const long tiles = (long)(p.M / 256) * cdiv(p.Cout, *variant == 10 ? 160 : 128);
-        int sp = 1;
-        const int nslab = p.Cin / 64;
-        while (tiles * sp < 192 && nslab / (sp + 1) >= 4 && sp < 8) ++sp;
-        *splits = sp;
+IGemmPlan igemm2_plan(IGemmParams& p, const IGemmRequest& rq) {
+    IGemmPlan pl;
+    pl.rs_part_w = p.Cout;
+    if (!igemm2_supported(p)) {
+        snprintf(pl.name, sizeof(pl.name), "%s", igemm_variant(p));
+        return pl;
     }
-    if (p.ln_stat) *splits = 1;          // the LayerNorm correction lives in the fused epilogue only
-    const bool ws_ok = wsgemm_supported(p);
-    if ((*variant == 13 || *variant == 14) && !ws_ok) { *variant = p.geglu ? 1 : 2; *splits = 1; }     // (forced on a problem it does not take)
-    // (with a residual the streamed tiles win by 1-6 us per launch -- profiles/r02_wsgemm.txt -- so those stay on them
-    // unless variant 13 is forced)
-    if (g_force_variant.load() < 0 && ws_ok && !p.res && wsgemm_enabled()) { *variant = p.geglu ? 14 : 13; *splits = 1; }
-    if (*variant == 13 && p.geglu) *variant = 14;
-    if (*variant == 14 && !p.geglu) *variant = 13;
-}
-
-bool igemm2_emits_rowstats(const IGemmParams& p, int* parts, int* part_w) {
-    if (!igemm2_supported(p) || p.geglu) return false;
-    int v, sp;
-    IGemmParams q = p;                                  // the choice as it will be made WITH the statistics requested
-    static float sentinel;
-    if (!q.rowstat_out) q.rowstat_out = &sentinel;
-    igemm2_pick(q, &v, &sp);
-    if (sp > 1 || v == 10 || v == 15) return false;
-    if (v == 13) { *parts = wsgemm_rowstat_parts(p); *part_w = 80; return *parts <= kMaxLnParts; }
-    int bm, bn;
-    tile_dims(v, &bm, &bn);
-    *parts = cdiv(p.Cout, bn);
-    *part_w = bn;
-    return *parts <= kMaxLnParts;
-}
-
-bool igemm2_emits_gnstats(const IGemmParams& p, int groups, int* rows) {
-    if (!igemm2_supported(p) || p.geglu || groups <= 0 || p.Cout % groups != 0) return false;
-    const int cpg = p.Cout / groups;
-    if (!(cpg >= 8 || cpg == 4)) return false;          // a 16-byte chunk may touch at most two groups
-    int v, sp;
-    IGemmParams q = p;                                  // the choice as it will be made WITH the summaries requested
-    static float sentinel;
-    q.gnstat_out = &sentinel;
-    igemm2_pick(q, &v, &sp);
-    if (v == 13 || v == 14) return false;
-    if (sp > 1) {                                       // split-K: the reduction kernel leaves them
-        const int rb = splitk_gs_rows(p, groups);
-        if (!rb) return false;
-        *rows = rb;
-        return true;
-    }
-    if ((v == 10 || v == 15) && !halo_supported(p)) v = 7;
-    int bm, bn;
-    tile_dims(v, &bm, &bn);
-    const int OHW = p.OH * p.OW;
-    if (OHW % bm != 0) return false;                    // every tile inside one image
-    if (bn % cpg != 0 && p.Cout > bn) return false;     // group boundaries on tile boundaries
-    *rows = bm;
-    return true;
-}
-
-static void igemm2_pick_raw(const IGemmParams& p, int* variant, int* splits) {
-    if (g_force_variant.load() >= 0) {
-        *variant = g_force_variant.load();
-        *splits = g_force_splits.load() > 0 ? g_force_splits.load() : 1;
-        if (p.geglu && *variant != 0 && *variant != 1 && *variant != 6 && *variant != 13 && *variant != 14) *variant = 1;
-        if (p.geglu || p.act) *splits = 1;
-        if ((*variant == 10 || *variant == 15) && !halo_supported(p)) *variant = 7;
-        return;
-    }
-    for (const TunedEntry& e : kTuned)
-        if (!p.act && e.M == p.M && e.N == p.Cout && e.K == p.K && e.ks == p.KS && e.stride == p.stride && e.up == p.up &&
-            e.geglu == p.geglu) {
-            *variant = e.variant; *splits = e.splits;
-            if ((*variant == 10 || *variant == 15) && !halo_supported(p)) *variant = 7;   // (same M x N x K from another image shape)
-            return;
-        }
-    const int nk = p.K / BK;
-    int v;
-    if (p.act) {                 // the activation lives in the fused epilogue only: never split K
-        v = (long)cdiv(p.M, 128) * cdiv(p.Cout, 64) >= 256 ? 3 : 4;
-        if ((long)cdiv(p.M, 128) * cdiv(p.Cout, 128) >= 256) v = 1;
-        *variant = v;
-        *splits = 1;
-        return;
-    }
-    if (p.geglu) v = (long)cdiv(p.M, 256) * cdiv(p.Cout, 128) >= 512 ? 0 : 1;
-    else if (p.Cout % 160 == 0) v = 2;
-    else v = 1;
-    int bm, bn;
-    tile_dims(v, &bm, &bn);
-    long tiles = (long)cdiv(p.M, bm) * cdiv(p.Cout, bn);
-    if (!p.geglu && tiles < 256 && nk <= 40) {          // small and shallow: narrow tiles fill more CUs
-        v = (long)cdiv(p.M, 128) * cdiv(p.Cout, 64) >= 256 ? 3 : 4;
-        tile_dims(v, &bm, &bn);
-        tiles = (long)cdiv(p.M, bm) * cdiv(p.Cout, bn);
-    }
-    int sp = 1;
-    if (!p.geglu && tiles < 384 && nk >= 24) {
-        sp = (int)((512 + tiles / 2) / tiles);
-        if (sp > 8) sp = 8;
-        while (sp > 1 && nk / sp < 12) --sp;
-    }
-    *variant = v;
-    *splits = sp;
-}
-
-const char* igemm2_name(int variant) { return kIgemm2Names[variant]; }
-
-long igemm2_partial_floats(const IGemmParams& p) {
-    int v, sp;
-    igemm2_pick(p, &v, &sp);
-    return sp > 1 ? (long)sp * p.M * p.Cout : 0;
-}
-
-static bool takes_pgemm_geglu(const IGemmParams& p, int v) {
-    static const bool pg_k320 = getenv("SD_PGEMM_K320") != nullptr;       // A/B: the K = 320 GEGLU on it instead of wsgemm
-    return p.geglu && ((v != 13 && v != 14) || pg_k320) && g_force_variant.load() < 0 && pgemm_geglu_supported(p);
-}
-static bool takes_igemm3(const IGemmParams& p, int v, int sp) {
+    static const bool ws_on = getenv("SD_NO_WSGEMM") == nullptr;
+    static const bool pg_k320 = getenv("SD_PGEMM_K320") != nullptr;    // A/B: the K = 320 GEGLU on pgemm instead of wsgemm
     static const bool g3_auto = getenv("SD_IGEMM3") != nullptr;        // off by default: measured not faster (igemm3.hip)
-    return (v == 11 || v == 12 || v == 18) && sp <= 1 && (v == 18 || (g3_auto && g_force_variant.load() < 0)) && igemm3_supported(p);
-}
-
-int igemm2_launch_kind(const IGemmParams& p, bool have_partial) {
+    const bool forced = g_force_variant.load() >= 0;
+    int v0, sp0;
+    pick_tile(p, &v0, &sp0);
+    if (!valid_id(v0)) { set_error("igemm2: bad variant"); pl.kind = kKindBadVariant; return pl; }
+    // The routes on top of the tile choice, for p as it stands (they read p.gnstat_out / p.rowstat_out through the
+    // *_supported predicates, so they are taken again after each request that is granted)
     int v, sp;
-    igemm2_pick(p, &v, &sp);
-    if (sp > 1 && !have_partial) sp = 1;
-    if (takes_pgemm_geglu(p, v)) return kKindPgemmGeglu;
-    if (takes_igemm3(p, v, sp)) return 18;
-    return v == 18 ? 12 : v;
-}
-
-int launch_igemm2(const IGemmParams& p, float* partial, hipStream_t s) {
-    int v, sp;
-    igemm2_pick(p, &v, &sp);
-    if (sp > 1 && !partial) sp = 1;
-    if (takes_pgemm_geglu(p, v)) return launch_pgemm_geglu(p, s);
-    switch (v) {
-        case 0: return launch_v2<256, 128, 4, 2, 3>(p, partial, sp, s);
-        case 1: return launch_v2<128, 128, 2, 2, 2>(p, partial, sp, s);
-        case 2: return launch_v2<128, 160, 2, 2, 2>(p, partial, sp, s);
-        case 3: return launch_v2<128, 64, 2, 2, 2>(p, partial, sp, s);
-        case 4: return launch_v2<64, 64, 2, 2, 2>(p, partial, sp, s);
-        case 5: return launch_v2<256, 160, 4, 1, 3>(p, partial, sp, s);
-        case 6: return launch_v2<256, 128, 4, 2, 3, true>(p, partial, sp, s);
-        case 7: return launch_v2<256, 160, 4, 2, 3, true>(p, partial, sp, s);
-        case 8: return launch_v2<128, 64, 2, 2, 3>(p, partial, sp, s);
-        case 9: return launch_v2<128, 160, 2, 2, 3>(p, partial, sp, s);
-        case 10: return launch_halo<160>(p, partial, sp, s);
-        case 15: return launch_halo<128>(p, partial, sp, s);
-        case 11:
-        case 12:
-        case 18:
-            // 18 = igemm3_kernel (activation operand through the ordinary load path instead of the LDS-DMA ring) asked for by
-            // name (tests, tuner), falling back to the 3-stage DMA tile for problems it does not take
-            if (takes_igemm3(p, v, sp)) return launch_igemm3(p, weights_outweigh_activations(p), s);
-            if (v == 11) return launch_v2<128, 80, 4, 1, 2>(p, partial, sp, s);
-            return launch_v2<128, 80, 4, 1, 3>(p, partial, sp, s);
-        case 16: return launch_v2<128, 80, 4, 1, 4>(p, partial, sp, s);
-        case 17: return launch_v2<128, 80, 4, 1, 5>(p, partial, sp, s);
-        case 13:
-        case 14: return launch_wsgemm(p, s);
-        default: set_error("igemm2: bad variant"); return 1;
+    auto route = [&]() {
+        v = v0; sp = sp0;
+        if (p.gni_part && !is_halo(v)) {
+            // a GroupNorm is applied to the input inside the kernel: only the halo kernel does that.  160 columns where they
+            // divide the width, split over the slabs until about one block per CU is in flight (>= 4 slabs per slice)
+            v = p.Cout % 160 == 0 ? kHalo160 : kHalo128;
+            const long tiles = (long)(p.M / kVariants[v].bm) * cdiv(p.Cout, kVariants[v].bn);
+            const int nslab = p.Cin / 64;
+            sp = 1;
+            while (tiles * sp < 192 && nslab / (sp + 1) >= 4 && sp < 8) ++sp;
+        }
+        if (p.ln_stat) sp = 1;               // the LayerNorm correction lives in the fused epilogue only
+        const bool ws_ok = wsgemm_supported(p);
+        if (is_ws(v) && !ws_ok) { v = p.geglu ? kWsFallbackGeglu : kWsFallbackPlain; sp = 1; }
+        // (with a residual the streamed tiles win by 1-6 us per launch -- profiles/r02_wsgemm.txt -- so those stay on them
+        // unless the weight-stationary variant is forced)
+        if (!forced && ws_ok && !p.res && ws_on) { v = kWsPlain; sp = 1; }
+        if (is_ws(v)) v = p.geglu ? kWsGeglu : kWsPlain;
+        if (rq.no_workspace) sp = 1;         // a split without a workspace runs unsplit
+    };
+    route();
+    // (asked of the problem before the requests below, as op_conv always has)
+    pl.scales_ok = !p.geglu && !is_ws(v);
+    // 1. GroupNorm summaries of the output: from the epilogue when every tile lies inside one image and group boundaries
+    //    fall on tile boundaries, from the split-K reduction kernel when the launch splits; a 16-byte chunk may touch at
+    //    most two groups
+    const int G = rq.gn_groups, cpg = G > 0 && p.Cout % G == 0 ? p.Cout / G : 0;
+    if (rq.gnstat && !p.geglu && (cpg >= 8 || cpg == 4)) {
+        p.gnstat_out = rq.gnstat; p.gn_groups = G;
+        route();
+        const Variant& t = kVariants[is_halo(v) && !halo_supported(p) ? kHaloFallback : v];
+        if (is_ws(v)) pl.gn_rows = 0;
+        else if (sp > 1) pl.gn_rows = splitk_gs_rows(p, G);
+        else pl.gn_rows = (p.OH * p.OW) % t.bm == 0 && (t.bn % cpg == 0 || p.Cout <= t.bn) ? t.bm : 0;
+        pl.gnstats = pl.gn_rows > 0;
+        if (!pl.gnstats) { p.gnstat_out = nullptr; p.gn_groups = 0; }
     }
+    // 2. row statistics of the output: from the epilogue of an unsplit launch, one part per column tile (wsgemm: per
+    //    80 columns), at most kMaxLnParts of them; otherwise the caller runs launch_row_stats (one part)
+    if (rq.rowstat && !p.geglu) {
+        p.rowstat_out = rq.rowstat;
+        route();
+        const int parts = is_ws(v) ? wsgemm_rowstat_parts(p) : cdiv(p.Cout, kVariants[v].bn);
+        pl.rowstats = sp <= 1 && !is_halo(v) && parts <= kMaxLnParts;
+        if (pl.rowstats) { pl.rs_parts = parts; pl.rs_part_w = is_ws(v) ? p.Cout / parts : kVariants[v].bn; }
+        else p.rowstat_out = nullptr;
+    }
+    // 3. what runs, and its workspace
+    route();
+    pl.variant = v;
+    pl.splits = sp;
+    pl.partial_floats = sp > 1 ? (long)sp * p.M * p.Cout : 0;
+    if (p.geglu && (!is_ws(v) || pg_k320) && !forced && pgemm_geglu_supported(p)) pl.kind = kKindPgemmGeglu;
+    else if ((v == kReg || (kVariants[v].reg_alt && g3_auto && !forced)) && sp <= 1 && igemm3_supported(p)) pl.kind = kReg;
+    else pl.kind = v == kReg ? kRegFallback : v;
+    const Variant& t = kVariants[pl.kind == kKindPgemmGeglu ? v : pl.kind];
+    pl.bm = t.bm; pl.bn = t.bn;
+    // (split-K launches keep the kernel's name: a profiler bracket also covers the small splitk_epilogue_kernel)
+    if (pl.kind == kKindPgemmGeglu) snprintf(pl.name, sizeof(pl.name), "geglu_persist_kernel");
+    else snprintf(pl.name, sizeof(pl.name), t.name, p.KS == 1 && p.stride == 1 && p.up == 0 ? "true" : "false");
+    return pl;
+}
+
+int launch_igemm2(const IGemmParams& p, float* partial, hipStream_t s, const IGemmPlan* plan) {
+    IGemmParams q = p;
+    IGemmPlan own;
+    if (!plan || (plan->splits > 1 && !partial)) {
+        q.rowstat_out = nullptr; q.gnstat_out = nullptr;
+        own = igemm2_plan(q, IGemmRequest{p.rowstat_out, p.gnstat_out, p.gn_groups, partial == nullptr});
+        plan = &own;
+    }
+    if (plan->kind == kKindIgemm1) return launch_igemm(q, s);
+    if (plan->kind == kKindPgemmGeglu) return launch_pgemm_geglu(q, s);
+    if (plan->kind == kKindBadVariant) { set_error("igemm2: bad variant"); return 1; }
+    return kVariants[plan->kind].launch(q, partial, plan->splits, s);
 }
 
 }  // namespace sd

@@ -46,7 +46,7 @@ struct IGemmParams {
     float ln_eps = 0.f;
     const float* ln_wsum = nullptr;
     // ---- GroupNorm statistics of the output, for the GroupNorm that follows (LDS-DMA kernels, no split-K,
-    //      every tile inside one image, group boundaries on tile boundaries: igemm2_emits_gnstats) ----
+    //      every tile inside one image, group boundaries on tile boundaries: IGemmPlan::gnstats) ----
     // gnstat_out[((img * tiles_per_image + tile) * gn_groups + g) * 2 + {0,1}] = (mean, M2) of the tile's rows
     // x the group's channels (the GnStats layout of launch_groupnorm)
     float* gnstat_out = nullptr;
@@ -64,32 +64,47 @@ struct IGemmParams {
     const float* gni_gb = nullptr;
     int dbg_unchecked = 0;          // tests: wsgemm's residual descriptor without its range check
     // ---- y = acc_scale * (x W^T) + bias_scale * bias (+ rowadd + res): the VAE encoder's range-scaled form (LDS-DMA
-    //      kernels and their split-K reductions; igemm2_scales_ok).  Scales are powers of two.  See VAE::run_encode. ----
+    //      kernels and their split-K reductions; IGemmPlan::scales_ok).  Scales are powers of two.  See VAE::run_encode. ----
     float acc_scale = 1.f, bias_scale = 1.f;
 };
 // Whether launch_igemm2 can apply a GroupNorm of `groups` groups to this problem's input (p.gni_* set by the caller).
 bool igemm2_gn_fusable(const IGemmParams& p, int groups);
-// Whether launch_igemm2 honours acc_scale / bias_scale for this problem (not the GEGLU / weight-stationary forms)
-bool igemm2_scales_ok(const IGemmParams& p);
-// Whether launch_igemm2 will honour p.gnstat_out for `groups` groups; *rows = pixels per tile (GnStats::rows).
-bool igemm2_emits_gnstats(const IGemmParams& p, int groups, int* rows);
-// Whether launch_igemm2 will honour p.rowstat_out for this problem (LDS-DMA kernel, no split-K); when not,
-// the caller runs launch_row_stats on the output instead.  Fills *parts with the column-tile count and *part_w with
-// the columns per part (the last one ragged).
-bool igemm2_emits_rowstats(const IGemmParams& p, int* parts, int* part_w);
 int launch_igemm(const IGemmParams& p, hipStream_t s);
 const char* igemm_variant(const IGemmParams& p);   // name of the tile variant launch_igemm picks
-// LDS-DMA pipeline variants (igemm2.hip); falls back to launch_igemm when !igemm2_supported().
+// LDS-DMA pipeline variants (igemm2.hip)
 bool igemm2_supported(const IGemmParams& p);
-void igemm2_pick(const IGemmParams& p, int* variant, int* splits);
-const char* igemm2_name(int variant);
-long igemm2_partial_floats(const IGemmParams& p);      // fp32 workspace needed for split-K (0 if none)
-int launch_igemm2(const IGemmParams& p, float* partial, hipStream_t s);
-// Which kernel launch_igemm2 runs for p: the variant id (18 only when igemm3_kernel takes the problem), or
-// kKindPgemmGeglu for geglu_persist_kernel.  have_partial: a split-K workspace is passed.
-constexpr int kKindPgemmGeglu = 100;
-int igemm2_launch_kind(const IGemmParams& p, bool have_partial);
 void igemm2_force(int variant, int splits);            // tuner / tests: -1 restores the heuristic
+// What a launch's caller may ask for on top of the problem: buffers the launch should fill if it can.
+struct IGemmRequest {
+    float* rowstat = nullptr;       // row statistics of the output (IGemmParams::rowstat_out)
+    float* gnstat = nullptr;        // GroupNorm summaries of the output for gn_groups groups (IGemmParams::gnstat_out)
+    int gn_groups = 0;
+    bool no_workspace = false;      // no split-K workspace will be passed: the launch runs unsplit
+};
+// How one launch runs, decided once (igemm2_plan) and handed to launch_igemm2.
+constexpr int kKindPgemmGeglu = 100;    // geglu_persist_kernel (pgemm.hip)
+constexpr int kKindIgemm1 = -1;         // not an LDS-DMA problem (!igemm2_supported): launch_igemm
+constexpr int kKindBadVariant = -2;     // a forced variant id outside the table: the launch fails
+struct IGemmPlan {
+    int kind = kKindIgemm1;         // the kernel that runs: a variant id of igemm2.hip's table, or one of the above
+    int variant = -1;               // the tile the choice landed on (differs from kind where pgemm / igemm3 / its fallback take over)
+    int splits = 1;                 // split-K slices
+    long partial_floats = 0;        // fp32 workspace the caller passes as `partial` (0: none)
+    int bm = 0, bn = 0;             // the tile
+    bool rowstats = false;          // the epilogue writes the row statistics; otherwise the caller runs launch_row_stats
+    int rs_parts = 1, rs_part_w = 0;    // their layout either way: parts per row, columns per part (the last one ragged)
+    bool gnstats = false;           // the epilogue, or the split-K reduction, leaves the GroupNorm summaries
+    int gn_rows = 0;                // pixels per summary (GnStats::rows)
+    bool scales_ok = false;         // acc_scale / bias_scale are honoured (not the GEGLU / weight-stationary forms)
+    char name[64] = "";             // the kernel as rocprofv3 names it
+};
+// Plans the launch of p.  Requests are resolved in the order GroupNorm summaries, row statistics, workspace (each granted
+// one can change the tile, and with it the next answer); p.gnstat_out / p.gn_groups / p.rowstat_out are set to the
+// buffers the launch will fill and left null for the rest.  Host code only.
+IGemmPlan igemm2_plan(IGemmParams& p, const IGemmRequest& rq = IGemmRequest());
+// Runs p as planned; plans it itself (requests = p's own rowstat_out / gnstat_out) when no plan is passed.  A plan that
+// splits K needs `partial` of plan->partial_floats; without it the launch is planned again and runs unsplit.
+int launch_igemm2(const IGemmParams& p, float* partial, hipStream_t s, const IGemmPlan* plan = nullptr);
 // Pointwise 128 x 80 tile with the activation operand fetched straight into registers (igemm3.hip): launch_igemm2 takes
 // it instead of the 128 x 80 LDS-DMA variants when the problem allows (no split-K, GEGLU, row add, GroupNorm summaries).
 bool igemm3_supported(const IGemmParams& p);

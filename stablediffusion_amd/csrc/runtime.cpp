@@ -369,68 +369,41 @@ void op_conv(Ctx& c, const ConvW& w, View x, int N, int H, int W, View y, int st
         p.gni_gb = fuse->gn_in->gb;
         if (c.dry) p.gni_part = reinterpret_cast<const float*>(8);      // planning pass: only "is set" matters (tile choice)
     }
-    if (fuse && (fuse->acc_scale != 1.f || fuse->bias_scale != 1.f)) {
-        p.acc_scale = fuse->acc_scale; p.bias_scale = fuse->bias_scale;
-        if (!igemm2_scales_ok(p)) { set_error("op_conv: output scaling needs the LDS-DMA kernels (not GEGLU / weight-stationary)"); c.err = 1; return; }
-    }
-    const bool v2 = igemm2_supported(p);
+    if (fuse && (fuse->acc_scale != 1.f || fuse->bias_scale != 1.f)) { p.acc_scale = fuse->acc_scale; p.bias_scale = fuse->bias_scale; }
+    // one plan per launch: the tile, what the epilogue leaves of the requested statistics, the workspace, the name
+    const IGemmPlan plan = igemm2_plan(p, IGemmRequest{stat_out ? stat_out->p : nullptr, gn_out ? gn_out->buf : nullptr,
+                                                       fuse ? fuse->gn_groups : 0});
+    const bool v2 = plan.kind != kKindIgemm1;
+    if ((p.acc_scale != 1.f || p.bias_scale != 1.f) && !plan.scales_ok) { set_error("op_conv: output scaling needs the LDS-DMA kernels (not GEGLU / weight-stationary)"); c.err = 1; return; }
     if (ln_in && !v2) { set_error("op_conv: the LayerNorm fold needs the LDS-DMA kernel"); c.err = 1; return; }
-    if (gn_out) {
-        int rows = 0;
-        gn_out->st = GnStats();
-        if (gn_out->buf && igemm2_emits_gnstats(p, fuse->gn_groups, &rows)) {
-            p.gnstat_out = gn_out->buf;
-            p.gn_groups = fuse->gn_groups;
-            gn_out->st.part = gn_out->buf;
-            gn_out->st.rows = rows;
-            gn_out->st.S = p.OH * p.OW / rows;
-        }
-    }
-    // (after the GroupNorm request: the tile choice, and with it the partial count, depends on it)
-    bool own_stats = false;      // the GEMM's epilogue writes the row statistics itself
-    if (stat_out) {
-        int parts = 1, part_w = w.cout;
-        own_stats = igemm2_emits_rowstats(p, &parts, &part_w);
-        stat_out->parts = own_stats ? parts : 1;
-        stat_out->width = own_stats ? part_w : w.cout;
-        if (own_stats) p.rowstat_out = stat_out->p;
-    }
     if (act && !v2) { set_error("op_conv: activation epilogue needs the LDS-DMA kernel (Cin % 64, Cout % 8)"); c.err = 1; return; }
-    float* partial = nullptr;
-    if (v2) {
-        const long pf = igemm2_partial_floats(p);
-        if (pf > 0) partial = c.arena->alloc_f(pf);
+    if (gn_out) {
+        gn_out->st = GnStats();
+        if (plan.gnstats) { gn_out->st.part = gn_out->buf; gn_out->st.rows = plan.gn_rows; gn_out->st.S = p.OH * p.OW / plan.gn_rows; }
     }
+    const bool own_stats = plan.rowstats;      // the GEMM's epilogue writes the row statistics itself
+    if (stat_out) { stat_out->parts = plan.rs_parts; stat_out->width = plan.rs_part_w; }
+    float* partial = plan.partial_floats > 0 ? c.arena->alloc_f(plan.partial_floats) : nullptr;
     if (c.dry || c.err) return;
     if (prof_enabled()) {
         const double kreal = (double)w.ks * w.ks * w.cin;
         const double in_px = (double)N * H * W;
-        const char* name = igemm_variant(p);
-        static thread_local char nbuf[64], fbuf[56];
-        if (v2) {
-            int var, sp;
-            igemm2_pick(p, &var, &sp);
-            const bool pw = p.KS == 1 && p.stride == 1 && p.up == 0;
-            // split-K launches keep the kernel's name: their bracket also covers the small
-            // splitk_epilogue_kernel, so the reported rate is slightly pessimistic for them
-            snprintf(nbuf, sizeof(nbuf), igemm2_name(var), pw ? "true" : "false");
-            const bool pg = p.geglu && var != 13 && var != 14 && pgemm_geglu_supported(p);
-            if (pg) snprintf(nbuf, sizeof(nbuf), "geglu_persist_kernel");
-            (void)fbuf;
-            // SD_PROF_SHAPES=1 (tools/profile_layers.py): one row per (tile variant, split-K, problem shape,
-            // fused extras) instead of one per kernel instantiation
-            static const bool by_shape = getenv("SD_PROF_SHAPES") != nullptr;
-            if (by_shape)
-                snprintf(nbuf, sizeof(nbuf), "%s%d/k%d %dx%dx%d ks%d%s%s%s%s%s%s", pg ? "pg" : "v", var, sp, p.M, p.Cout, p.K, p.KS, res ? " res" : "",
-                         geglu ? " geglu" : "", p.ln_stat ? " ln" : "", p.rowstat_out ? " rs" : "", p.gnstat_out ? " gs" : "",
-                         p.gni_part ? " gn" : "");
+        const char* name = plan.name;
+        // SD_PROF_SHAPES=1 (tools/profile_layers.py): one row per (tile variant, split-K, problem shape,
+        // fused extras) instead of one per kernel instantiation
+        static const bool by_shape = getenv("SD_PROF_SHAPES") != nullptr;
+        char nbuf[64];
+        if (v2 && by_shape) {
+            snprintf(nbuf, sizeof(nbuf), "%s%d/k%d %dx%dx%d ks%d%s%s%s%s%s%s", plan.kind == kKindPgemmGeglu ? "pg" : "v", plan.variant,
+                     plan.splits, p.M, p.Cout, p.K, p.KS, res ? " res" : "", geglu ? " geglu" : "", p.ln_stat ? " ln" : "",
+                     p.rowstat_out ? " rs" : "", p.gnstat_out ? " gs" : "", p.gni_part ? " gn" : "");
             name = nbuf;
         }
         prof_open(c.stream, name, 2.0 * p.M * w.cout * kreal,
                   2.0 * (in_px * (w.ks == 1 ? (double)w.K : w.cin) + (double)w.cout * w.K +
                          (double)p.M * (geglu ? w.cout / 2 : w.cout) * (res ? 2 : 1)));
     }
-    c.err = v2 ? launch_igemm2(p, partial, c.stream) : launch_igemm(p, c.stream);
+    c.err = launch_igemm2(p, partial, c.stream, &plan);
     prof_close(c.stream);
     if (stat_out && !own_stats && !c.err) {
         prof_open(c.stream, "row_stats_kernel", 0.0, 2.0 * p.M * w.cout);
@@ -443,8 +416,6 @@ void op_groupnorm(Ctx& c, const NormW& n, View x, View y, int N, long HW, int G,
                   const GnStatBuf* pre) {
     float* scratch = c.arena->alloc_f(gn_scratch_floats(N, HW, n.C, G));
     if (c.dry || c.err) return;
-    static const bool gn_old = getenv("SD_GN_OLD") != nullptr;
-    (void)gn_old;
     const GnStats* st = (pre && pre->st.part && gn_wants_stats(HW, n.C, G)) ? &pre->st : nullptr;
     // bytes really moved: the single-kernel form and the apply pass read x and write y; only the
     // stand-alone statistics pass reads x once more
