@@ -451,6 +451,12 @@ int sd_op_attention(const void* q, const void* k, const void* v, void* out, int 
 int sd_op_attention_ex(const void* q, const void* k, const void* v, void* out, int B, int Tq, int Tk,
                        int heads, int d, int ldq, int ldk, int ldv, int ldo, int causal, int prescaled,
                        void* stream);
+/* Test hook, host only (no device needed): which instantiation of the attention kernel sd_op_attention_ex would launch
+ * for this problem (the launch dispatches on the same function).  out5 = head dim, 16-query subtiles per wave, keys per
+ * tile, accumulator-start form for pre-scaled queries (0 / 1), waves per block; a block holds 16 * out5[1] * out5[4]
+ * queries.  SD_ERR_UNSUPPORTED for a head dim the launch rejects.  The SD_ATTN_NWV / SD_ATTN_NWV80 switches are read
+ * once per process, as by the launch. */
+int sd_attention_plan(int B, int Tq, int Tk, int heads, int d, int causal, int prescaled, int* out5);
 /* IP-Adapter's decoupled cross-attention (diffusers IPAdapterAttnProcessor2_0 at every attn2), one launch:
  *   out = softmax(s q k^T) v + ip_scale * softmax(s q k_ip^T) v_ip,   s = 1/sqrt(d), or 1 with prescaled = 1
  * q [B,Tq,heads*d], k / v [B,L,heads*d], k_ip / v_ip [B,T_ip,heads*d], out like q, each with its own row stride

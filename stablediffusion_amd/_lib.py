@@ -163,6 +163,7 @@ SIGNATURES = {
     "sd_op_small_linear": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "sd_op_layernorm": (_I, [_P, _P, _P, _P, _I, _I, _F, _P]),
     "sd_op_attention": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "sd_attention_plan": (_I, [_I, _I, _I, _I, _I, _I, _I, C.POINTER(_I)]),
     "sd_op_ip_cross_attention": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _I, _I,
                                       C.POINTER(_F), _P]),
     "sd_op_controlnet_residuals": (_I, [C.POINTER(SdCnProblem), _I, _F, _I, _I, C.POINTER(_F), _P]),

@@ -338,7 +338,12 @@ __global__ __launch_bounds__(64 * NWV) void attn_kernel(const half_t* __restrict
             if (__any(grow)) {                     // wave-uniform: rescale everything kept at the old max
     #pragma unroll
                 for (int t = 0; t < QT; ++t) {
-                    const float mnew = fmaxf(mrun[t], mx[t]);
+                    // A new reference is set a hair (2^-22 relative) BELOW the rounded maximum: the per-score FMA
+                    // below subtracts it from the UNROUNDED product s * scale, so a reference rounded upwards
+                    // left the row's largest probability at exp2(-tiny) = 1 - 2^-24, which the fp16 truncation
+                    // turns into 1 - 2^-11 while the !ONES denominator keeps 1 (a single key then returned
+                    // v * (1 - 2^-11) instead of v).  From below it is 1 <= p < 1 + 2^-10 and truncates to 1.
+                    const float mnew = mx[t] > mrun[t] ? mx[t] - fabsf(mx[t]) * 0x1p-22f : mrun[t];
                     const float alpha = __builtin_amdgcn_exp2f(mrun[t] - mnew);
                     mrun[t] = mnew;
                     lrun[t] *= alpha;
@@ -448,46 +453,65 @@ bool attention_supported(int d) {
     return d == 32 || d == 40 || d == 64 || d == 80 || d == 128 || d == 160 || d == 512;
 }
 
-int launch_attention(const half_t* q, const half_t* k, const half_t* v, half_t* out, int B, int Tq,
-                     int Tk, int heads, int d, long ldq, long ldk, long ldv, long ldo, hipStream_t s, int causal,
-                     int prescaled) {
-    if ((ldq | ldk | ldv | ldo) % 8 != 0) { set_error("attention: row strides must be multiples of 8"); return 1; }
-    if (Tk <= 0 || Tq <= 0) return 0;
-    // FAST: whether the accumulator-start form pays for this head dim (measured with the DMA staging:
-    // -11 % at d = 40, where the loop is VALU-issue-bound; a wash or slightly worse from d = 64 up);
-    // otherwise pre-scaled queries run the general kernel with a unit scale
-#define SD_ATTN_CASE(DD, QQ, KK, FAST) \
-    case DD: return (prescaled && FAST) \
-        ? launch_attn<DD, QQ, KK, FAST>(q, k, v, out, B, Tq, Tk, heads, ldq, ldk, ldv, ldo, causal, true, s) \
-        : launch_attn<DD, QQ, KK, false>(q, k, v, out, B, Tq, Tk, heads, ldq, ldk, ldv, ldo, causal, prescaled != 0, s)
+// The one place that decides which attn_kernel<D, QT, KT, PRESC, NWV> a problem runs (host only, no device
+// needed; sd_attention_plan exposes it).  launch_attention dispatches on the answer; tests/test_attention_plan.py
+// lists every instantiation reachable from here and pins the choice for the engine's shapes.
+AttnPlan attention_plan(int B, int Tq, int Tk, int heads, int d, int causal, int prescaled) {
+    (void)Tk;                                  // no threshold looks at the key count
     // Few, long query blocks leave CUs idle on the small maps (16 x 16 latents: 256 queries x 64 (batch, head)
     // pairs = 128 blocks of 128 queries for 256 CUs): halve the block there.  (d = 40 was also tried at 48 / 32 /
     // 16 queries per wave for more waves per SIMD: 299 -> 318 / 318 / 403 us on the 4096-token case: it is not
     // latency-bound.)
     // eight waves per block where there are enough query blocks to fill the chip with them (SD_ATTN_NWV=4: A/B switch)
     static const int nwv = getenv("SD_ATTN_NWV") ? atoi(getenv("SD_ATTN_NWV")) : 8;
-    if (d == 40 && prescaled && !causal && nwv == 8 && (long)cdiv(Tq, 512) * B * heads >= 512)
-        return launch_attn<40, 4, 64, true, 8>(q, k, v, out, B, Tq, Tk, heads, ldq, ldk, ldv, ldo, causal, true, s);
+    if (d == 40 && prescaled && !causal && nwv == 8 && (long)cdiv(Tq, 512) * B * heads >= 512) return {40, 4, 64, 1, 8};
     // d = 80 (the 32 x 32 level): 256 queries per block where that still gives one block per CU -- 42.5 -> 36.9 us on the
     // 1024-token self-attention; d = 64 (SDXL) measured slower with eight waves (259.6 -> 269.8, 42.5 -> 48.3 us) and stays at four
     static const int nwv80 = getenv("SD_ATTN_NWV80") ? atoi(getenv("SD_ATTN_NWV80")) : 8;
-    if (nwv80 == 8 && !causal && d == 80 && (long)cdiv(Tq, 256) * B * heads >= 256)
-        return launch_attn<80, 2, 64, false, 8>(q, k, v, out, B, Tq, Tk, heads, ldq, ldk, ldv, ldo, causal, prescaled != 0, s);
-    if (d == 160 && (long)cdiv(Tq, 128) * B * heads < 256)
-        return launch_attn<160, 1, 64, false>(q, k, v, out, B, Tq, Tk, heads, ldq, ldk, ldv, ldo, causal, prescaled != 0, s);
+    if (nwv80 == 8 && !causal && d == 80 && (long)cdiv(Tq, 256) * B * heads >= 256) return {80, 2, 64, 0, 8};
+    if (d == 160 && (long)cdiv(Tq, 128) * B * heads < 256) return {160, 1, 64, 0, 4};
+    // PRESC, the accumulator-start form for pre-scaled queries, only where it pays for the head dim (measured with
+    // the DMA staging: -11 % at d = 40, where the loop is VALU-issue-bound; a wash or slightly worse from d = 64 up);
+    // otherwise pre-scaled queries run the general kernel with a unit scale
+    const int fast = prescaled ? 1 : 0;
     switch (d) {
-        SD_ATTN_CASE(32, 2, 64, true);
-        SD_ATTN_CASE(40, 4, 64, true);
-        SD_ATTN_CASE(64, 2, 64, false);
-        SD_ATTN_CASE(80, 2, 64, false);
-        SD_ATTN_CASE(128, 2, 64, false);
-        SD_ATTN_CASE(160, 2, 64, false);
-        SD_ATTN_CASE(512, 1, 64, false);
-        default:
-            set_error("attention: unsupported head dim " + std::to_string(d));
-            return 4;
+        case 32: return {32, 2, 64, fast, 4};
+        case 40: return {40, 4, 64, fast, 4};
+        case 64: return {64, 2, 64, 0, 4};
+        case 80: return {80, 2, 64, 0, 4};
+        case 128: return {128, 2, 64, 0, 4};
+        case 160: return {160, 2, 64, 0, 4};
+        case 512: return {512, 1, 64, 0, 4};
+        default: return {0, 0, 0, 0, 0};
     }
-#undef SD_ATTN_CASE
+}
+
+int launch_attention(const half_t* q, const half_t* k, const half_t* v, half_t* out, int B, int Tq,
+                     int Tk, int heads, int d, long ldq, long ldk, long ldv, long ldo, hipStream_t s, int causal,
+                     int prescaled) {
+    if ((ldq | ldk | ldv | ldo) % 8 != 0) { set_error("attention: row strides must be multiples of 8"); return 1; }
+    if (Tk <= 0 || Tq <= 0) return 0;
+    const AttnPlan pl = attention_plan(B, Tq, Tk, heads, d, causal, prescaled);
+    if (pl.D == 0) { set_error("attention: unsupported head dim " + std::to_string(d)); return 4; }
+    // one row per instantiation attention_plan can name
+#define SD_ATTN_RUN(DD, QQ, PP, WW) \
+    if (pl.D == DD && pl.QT == QQ && pl.KT == 64 && pl.PRESC == (PP ? 1 : 0) && pl.NWV == WW) \
+        return launch_attn<DD, QQ, 64, PP, WW>(q, k, v, out, B, Tq, Tk, heads, ldq, ldk, ldv, ldo, causal, prescaled != 0, s)
+    SD_ATTN_RUN(40, 4, true, 8);
+    SD_ATTN_RUN(80, 2, false, 8);
+    SD_ATTN_RUN(160, 1, false, 4);
+    SD_ATTN_RUN(32, 2, true, 4);
+    SD_ATTN_RUN(32, 2, false, 4);
+    SD_ATTN_RUN(40, 4, true, 4);
+    SD_ATTN_RUN(40, 4, false, 4);
+    SD_ATTN_RUN(64, 2, false, 4);
+    SD_ATTN_RUN(80, 2, false, 4);
+    SD_ATTN_RUN(128, 2, false, 4);
+    SD_ATTN_RUN(160, 2, false, 4);
+    SD_ATTN_RUN(512, 1, false, 4);
+#undef SD_ATTN_RUN
+    set_error("attention: no kernel for the planned instantiation");      // a plan row without a launch row
+    return 4;
 }
 
 }  // namespace sd

@@ -1115,6 +1115,15 @@ int sd_op_attention_ex(const void* q, const void* k, const void* v, void* out, i
                             ldv, ldo, static_cast<hipStream_t>(stream), causal, prescaled);
 }
 
+int sd_attention_plan(int B, int Tq, int Tk, int heads, int d, int causal, int prescaled, int* out5) {
+    if (!out5) { set_error("sd_attention_plan: null argument"); return SD_ERR_INVALID; }
+    const AttnPlan pl = attention_plan(B, Tq, Tk, heads, d, causal, prescaled);
+    if (pl.D == 0) { set_error("attention: unsupported head dim " + std::to_string(d)); return SD_ERR_UNSUPPORTED; }
+    const int o[5] = {pl.D, pl.QT, pl.KT, pl.PRESC, pl.NWV};
+    for (int i = 0; i < 5; ++i) out5[i] = o[i];
+    return SD_OK;
+}
+
 int sd_op_ip_cross_attention(const void* q, const void* k, const void* v, const void* k_ip, const void* v_ip, void* out,
                              int B, int Tq, int L, int T_ip, int heads, int d, int ldq, int ldk, int ldv, int ldk_ip,
                              int ldv_ip, int ldo, float ip_scale, int prescaled, int iters, float* ms_per_launch,

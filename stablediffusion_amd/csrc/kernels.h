@@ -185,6 +185,11 @@ int launch_attention(const half_t* q, const half_t* k, const half_t* v, half_t* 
 // prescaled = 1: q already carries log2(e)/sqrt(d) (the UNet folds it into its query projections at
 // pack time, launch_scale_f16), which lets the kernel drop its per-score scale-and-subtract FMA.
 bool attention_supported(int d);
+// Which attn_kernel<D, QT, KT, PRESC, NWV> launch_attention runs for a problem: head dim, 16-query subtiles per wave,
+// keys per tile, accumulator-start form for pre-scaled queries, waves per block (16 * QT * NWV queries per block).
+// D == 0: unsupported head dim.  Host only; launch_attention dispatches on it.
+struct AttnPlan { int D, QT, KT, PRESC, NWV; };
+AttnPlan attention_plan(int B, int Tq, int Tk, int heads, int d, int causal, int prescaled);
 // IP-Adapter decoupled cross-attention (ip_attention.hip), one launch:
 //   out = softmax(s q k^T) v + ip_scale * softmax(s q k_ip^T) v_ip,   s = 1/sqrt(d) (or 1 with prescaled)
 // q [B,Tq,heads*d], k / v [B,L,..], k_ip / v_ip [B,Tip,..] with their own row strides; 1 <= L <= 160,
