@@ -169,6 +169,24 @@ int sd_unet_forward_cn(sd_unet* u, const void* sample, const float* timesteps, c
                        const void* add_text, const float* add_time_ids, const void* image_embeds, int n_img,
                        const void* control_image, int n_ctrl, float cond_scale, void* out, int B, int H, int W,
                        void* stream);
+/* The UNet forward of one classifier-free-guidance step from the UN-duplicated latents: what
+ * sd_cfg_duplicate(latents, in_scale) followed by sd_unet_forward(_ex) returns, negative half first.
+ *   latents   [B,C,H,W] f16        timesteps [B] f32 (both halves share them)
+ *   ehs       [2B,ehs_len,ctx] f16  add_text / add_time_ids / image_embeds: 2B rows, as sd_unet_forward_ex takes them
+ *   in_scale  the scheduler's scale_model_input factor, applied as fp16(latents * in_scale)
+ *   out       [2B,Cout,H,W] f16
+ * With share != 0 and a topology for which sd_unet_cfg_share answers 1, everything in front of the first cross-attention
+ * (conv_in, down_blocks.0.resnets.0, the first transformer's norm, proj_in, q|k|v, self-attention, to_out, attn2.to_q)
+ * runs once per latent, on B images, and is widened to 2B in one copy launch: the two halves hold the same values there.
+ * Otherwise -- share == 0, graph replay on, SD_NO_CFG_SHARE or SD_GN_CAT set in the environment, such a topology -- the
+ * engine duplicates into a buffer of its own and runs the ordinary forward: bit for bit the two-call result.  An attached
+ * ControlNet needs its control image: use sd_cfg_duplicate + sd_unet_forward_cn. */
+int sd_unet_forward_cfg(sd_unet* u, const void* latents, const float* timesteps, const void* ehs, int ehs_len,
+                        const void* add_text, const float* add_time_ids, const void* image_embeds, int n_img,
+                        float in_scale, int share, void* out, int B, int H, int W, void* stream);
+/* 1 when the topology lets sd_unet_forward_cfg share: no per-sample additional embedding (text_time makes the time
+ * embedding differ between the halves) and a transformer in down block 0.  Needs no device. */
+int sd_unet_cfg_share(const sd_unet_config* cfg);
 /* Bytes of device memory held (packed weights, workspace). */
 int sd_unet_memory(const sd_unet* u, int64_t* weight_bytes, int64_t* workspace_bytes);
 

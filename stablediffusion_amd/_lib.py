@@ -94,6 +94,8 @@ SIGNATURES = {
     "sd_unet_text_kv_cache": (_I, [_P, _I]),
     "sd_unet_memory": (_I, [_P, C.POINTER(_I64), C.POINTER(_I64)]),
     "sd_unet_forward_ex": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _I, _P, _I, _I, _I, _P]),
+    "sd_unet_forward_cfg": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _I, _F, _I, _P, _I, _I, _I, _P]),
+    "sd_unet_cfg_share": (_I, [C.POINTER(SdUNetConfig)]),
     "sd_unet_set_ip_adapter": (_I, [_P, _P]),
     "sd_unet_set_ip_adapter_scale": (_I, [_P, _F]),
     "sd_ip_adapter_create": (_I, [_P, _I, _I, C.POINTER(_P)]),

@@ -187,6 +187,17 @@ int sd_unet_forward_cn(sd_unet* u, const void* sample, const float* timesteps, c
                            static_cast<const half_t*>(image_embeds), image_embeds ? n_img : 0,
                            static_cast<const half_t*>(control_image), control_image ? n_ctrl : 0, cond_scale);
 }
+int sd_unet_forward_cfg(sd_unet* u, const void* latents, const float* timesteps, const void* ehs, int ehs_len,
+                        const void* add_text, const float* add_time_ids, const void* image_embeds, int n_img,
+                        float in_scale, int share, void* out, int B, int H, int W, void* stream) {
+    if (!u || !latents || !timesteps || !ehs || !out) { set_error("null argument"); return SD_ERR_INVALID; }
+    if (!(in_scale == in_scale)) { set_error("sd_unet_forward_cfg: in_scale is NaN"); return SD_ERR_INVALID; }
+    return u->impl.forward_cfg(static_cast<const half_t*>(latents), timesteps, static_cast<const half_t*>(ehs), ehs_len,
+                               static_cast<const half_t*>(add_text), add_time_ids,
+                               static_cast<const half_t*>(image_embeds), image_embeds ? n_img : 0, in_scale, share != 0,
+                               static_cast<half_t*>(out), B, H, W, static_cast<hipStream_t>(stream));
+}
+int sd_unet_cfg_share(const sd_unet_config* cfg) { return cfg && sd::unet_cfg_share_eligible(*cfg) ? 1 : 0; }
 int sd_unet_set_ip_adapter_scale(sd_unet* u, float scale) {
     if (!u) { set_error("null handle"); return SD_ERR_INVALID; }
     if (!(scale == scale)) { set_error("sd_unet_set_ip_adapter_scale: NaN"); return SD_ERR_INVALID; }

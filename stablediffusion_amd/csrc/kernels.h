@@ -300,6 +300,17 @@ int launch_conv_tail(const TailParams& p, hipStream_t s);
 int launch_pack_conv(const half_t* w_oihw, half_t* wp, int O, int I, int KH, int KW, long Kpad,
                      hipStream_t s);
 int launch_cfg_duplicate(const half_t* lat, half_t* out, long n_total, float scale, hipStream_t s);
+// Copies `rows` rows of row_bytes bytes (row stride ld_bytes) from src to dst for up to kRowDupMax tensors in one launch;
+// everything 16-byte aligned.  The shared CFG prefix widens its B-row tensors to 2B rows with it (dst = src + B rows).
+constexpr int kRowDupMax = 8;
+struct RowDupSeg {
+    const void* src = nullptr;
+    void* dst = nullptr;
+    long ld_bytes = 0, row_bytes = 0, rows = 0;
+};
+int launch_row_dup(const RowDupSeg* segs, int count, hipStream_t s);
+int launch_scale_copy_f16(const half_t* x, half_t* out, long n, float scale, hipStream_t s);   // out = fp16(x * scale)
+int launch_dup_f32(const float* x, float* out, long n, hipStream_t s);                         // out[0:n] = out[n:2n] = x
 // CLIP text embeddings: out[b, t, :] = token_table[ids[b, t], :] + position_table[t, :]  (ids clamped to the table)
 int launch_clip_embed(const int* ids, const half_t* tok, const half_t* pos, half_t* out, int B, int T, int H, int vocab,
                       hipStream_t s);

@@ -199,6 +199,53 @@ __global__ void cfg_duplicate_kernel(const half_t* __restrict__ lat, half_t* __r
     out[i] = v;
     out[n + i] = v;
 }
+// Shared CFG prefix (UNet::run): the first B rows of a tensor that the 2B-row remainder of the forward reads are copied
+// onto its second B rows.  One launch for every such tensor: segment i is `rows` rows of w16 16-byte units, row stride
+// ld16 units, copied from src to dst; its blocks are [first, next segment's first), RD_UNITS units each.
+constexpr int RD_PER_THREAD = 4;
+constexpr int RD_UNITS = 256 * RD_PER_THREAD;
+struct RowDupDev {
+    const uint4* src[kRowDupMax];
+    uint4* dst[kRowDupMax];
+    long ld16[kRowDupMax], w16[kRowDupMax], units[kRowDupMax];
+    int first[kRowDupMax + 1];
+    int count;
+};
+__global__ __launch_bounds__(256) void row_dup_kernel(RowDupDev p) {
+    int sg = 0;
+    while (sg + 1 < p.count && (int)blockIdx.x >= p.first[sg + 1]) ++sg;
+    const uint4* __restrict__ src = p.src[sg];
+    uint4* __restrict__ dst = p.dst[sg];
+    const long ld = p.ld16[sg], w = p.w16[sg], n = p.units[sg];
+    const long base = (long)((int)blockIdx.x - p.first[sg]) * RD_UNITS + threadIdx.x;
+    uint4 v[RD_PER_THREAD];
+    long off[RD_PER_THREAD];
+#pragma unroll
+    for (int j = 0; j < RD_PER_THREAD; ++j) {
+        const long i = base + j * 256;
+        off[j] = -1;
+        if (i < n) {
+            const long r = i / w;
+            off[j] = r * ld + (i - r * w);
+            v[j] = src[off[j]];
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < RD_PER_THREAD; ++j)
+        if (off[j] >= 0) dst[off[j]] = v[j];
+}
+// out[i] = fp16(lat[i] * scale): cfg_duplicate_kernel's rounding, one copy
+__global__ void scale_copy_f16_kernel(const half_t* __restrict__ lat, half_t* __restrict__ out, long n, float scale) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = (half_t)((float)lat[i] * scale);
+}
+__global__ void dup_f32_kernel(const float* __restrict__ x, float* __restrict__ out, long n) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float v = x[i];
+    out[i] = v;
+    out[n + i] = v;
+}
 // sd_unified_pipeline.py:484-489 with DDIM eta=0 folded into x <- cx*x + ce*eps.
 __global__ void cfg_ddim_kernel(const half_t* __restrict__ eps2b, half_t* __restrict__ lat, long n,
                                 float g, float cx, float ce) {
@@ -737,6 +784,48 @@ int launch_pack_conv(const half_t* w, half_t* wp, int O, int I, int KH, int KW, 
 }
 int launch_cfg_duplicate(const half_t* lat, half_t* out, long n, float scale, hipStream_t s) {
     hipLaunchKernelGGL(cfg_duplicate_kernel, grid1d(n), dim3(256), 0, s, lat, out, n, scale);
+    SD_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+int launch_row_dup(const RowDupSeg* segs, int count, hipStream_t s) {
+    if (count < 0 || count > kRowDupMax) { set_error("row_dup: too many segments"); return 1; }
+    RowDupDev p;
+    int blocks = 0, k = 0;
+    for (int i = 0; i < count; ++i) {
+        const RowDupSeg& g = segs[i];
+        if (g.rows <= 0 || g.row_bytes <= 0) continue;
+        if (((reinterpret_cast<uintptr_t>(g.src) | reinterpret_cast<uintptr_t>(g.dst) | (uintptr_t)g.ld_bytes |
+              (uintptr_t)g.row_bytes) & 15) != 0 || g.row_bytes > g.ld_bytes) {
+            set_error("row_dup: segments must be 16-byte aligned with row_bytes <= ld_bytes");
+            return 1;
+        }
+        p.src[k] = static_cast<const uint4*>(g.src);
+        p.dst[k] = static_cast<uint4*>(g.dst);
+        p.ld16[k] = g.ld_bytes / 16;
+        p.w16[k] = g.row_bytes / 16;
+        p.units[k] = g.rows * p.w16[k];
+        p.first[k] = blocks;
+        const long nb = (p.units[k] + RD_UNITS - 1) / RD_UNITS;
+        if (nb + blocks > 0x7fffffffL) { set_error("row_dup: too large"); return 1; }
+        blocks += (int)nb;
+        ++k;
+    }
+    if (k == 0) return 0;
+    p.first[k] = blocks;
+    p.count = k;
+    hipLaunchKernelGGL(row_dup_kernel, dim3((unsigned)blocks), dim3(256), 0, s, p);
+    SD_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+int launch_scale_copy_f16(const half_t* x, half_t* out, long n, float scale, hipStream_t s) {
+    if (n <= 0) return 0;
+    hipLaunchKernelGGL(scale_copy_f16_kernel, grid1d(n), dim3(256), 0, s, x, out, n, scale);
+    SD_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+int launch_dup_f32(const float* x, float* out, long n, hipStream_t s) {
+    if (n <= 0) return 0;
+    hipLaunchKernelGGL(dup_f32_kernel, grid1d(n), dim3(256), 0, s, x, out, n);
     SD_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -44,12 +44,21 @@ struct VaeAttn {
 // out_buf / out_groups: where and at which granularity those summaries are written (default: the next ring slot, G
 // groups) -- a skip connection's live until the up path reads them, and an output that becomes the hidden half of a
 // concatenation is summarised over the sub-groups that concatenation's GroupNorm can merge (gn_cat_unit).
+// Shared CFG prefix (UNet::run with a CfgIn): the N images are the two halves of a classifier-free-guidance batch built
+// from the same N / 2 latents, and up to the first cross-attention of the first transformer nothing tells the halves
+// apart.  The layers before it run on the first N / 2 images only; `segs` are the tensors the caller wants widened to N
+// images (second half = first half) in the one copy launch run_xformer issues in front of that cross-attention, together
+// with its own (its input, which proj_out adds back, t2 and the attn2 query).
+struct CfgShare {
+    std::vector<RowDupSeg> segs;
+};
+
 void run_resnet(Ctx& c, const Resnet& r, View x, int N, int H, int W, View out, int G, float eps,
                 const float* tproj, int tproj_ld, const GnStatBuf* x_stats = nullptr, GnStatBuf** out_stats = nullptr,
                 float stream_scale = 1.f, GnStatBuf* out_buf = nullptr, int out_groups = 0);
 void run_xformer(Ctx& c, const Xformer& t, View x, int N, int H, int W, View out, int G, View text_kv, int L,
                  const GnStatBuf* x_stats = nullptr, GnStatBuf** out_stats = nullptr, GnStatBuf* out_buf = nullptr,
-                 int out_groups = 0);
+                 int out_groups = 0, const CfgShare* share = nullptr);
 
 struct UNet;
 
@@ -106,14 +115,18 @@ struct Encoder {
     int pack_resnet(const std::string& p, Resnet* r, std::vector<std::string>* tw, std::vector<std::string>* tb);
     int pack_xformer(const std::string& p, Xformer* x, int heads, int depth);
     // time (+ text_time) embedding -> every resnet's time_emb_proj(silu(emb)) in one GEMV: [B, temb_total] fp32
-    int run_temb(Ctx& c, const float* timesteps, const half_t* add_text, const float* add_time_ids, int B, float** tproj);
+    // (rows_alloc > B: the buffer is sized for that many rows, the first B are written)
+    int run_temb(Ctx& c, const float* timesteps, const half_t* add_text, const float* add_time_ids, int B, float** tproj,
+                 int rows_alloc = 0);
     // conv_in into y0: straight from the NCHW latents when the edge kernel takes it and there is no residual, else
     // im2col + GEMM with `res` added in its epilogue.  *xs = the GroupNorm summaries of y0 it left (or nullptr).
     void run_conv_in(Ctx& c, const half_t* sample, int B, int H, int W, View y0, GnStatBuf* gb, const View* res,
                      GnStatBuf** xs);
-    // down path from x = skip 0 (summaries xs) at h x w: writes skips 1.. through dst / stat, returns the last one
+    // down path from x = skip 0 (summaries xs) at h x w: writes skips 1.. through dst / stat, returns the last one.
+    // share: x, xs and tproj hold the first B / 2 images; the first resnet and the start of the first transformer run on
+    // those (CfgShare), everything after on all B.
     View run_down(Ctx& c, View x, GnStatBuf*& xs, int B, int& h, int& w, View text_kv, int L, const float* tproj,
-                  const SkipDst& dst, const SkipStat& stat);
+                  const SkipDst& dst, const SkipStat& stat, const CfgShare* share = nullptr);
     void run_mid(Ctx& c, View x, GnStatBuf* xs, int B, int h, int w, View text_kv, int L, const float* tproj, View dst);
 };
 
@@ -143,13 +156,34 @@ struct ControlNet : Encoder {
             const float* add_time_ids, int B, int H, int W, View emb, const std::vector<View>& sites, View mid);
 };
 
+// Whether a UNet topology allows the shared CFG prefix: no per-sample additional embedding (text_time makes the time
+// embedding differ between the halves) and a transformer in down block 0 (where the text first enters).
+bool unet_cfg_share_eligible(const sd_unet_config& cfg);
+
+// Input of a forward in shared-CFG mode: the un-duplicated latents [B / 2, C, H, W] and the scheduler's input scale;
+// the timesteps argument then holds B / 2 entries and `sample` is unused.
+struct CfgIn {
+    const half_t* latents = nullptr;
+    float in_scale = 1.f;
+};
+
 struct UNet : Encoder {
     explicit UNet(const sd_unet_config& c);
     int finalize();
+    // The forward on cat([latents * in_scale] * 2) with both halves at the same timesteps [B]: ehs / image_embeds / out
+    // hold 2B rows, negative half first.  Runs the CFG-shared prefix once per latent when `share`, the topology and the
+    // engine's state allow (unet_cfg_share_eligible, no graph replay, no ControlNet, SD_GN_CAT and SD_NO_CFG_SHARE unset);
+    // otherwise duplicates into a buffer of its own and runs forward(): bit for bit what callers did before.
+    int forward_cfg(const half_t* latents, const float* timesteps, const half_t* ehs, int L, const half_t* add_text,
+                    const float* add_time_ids, const half_t* image_embeds, int n_img, float in_scale, bool share,
+                    half_t* out, int B, int H, int W, hipStream_t stream);
+    bool cfg_share_active(bool share) const;
+    char* cfg_slab = nullptr;           // forward_cfg's duplicated latents + timesteps when it does not share
+    size_t cfg_cap = 0;
     int forward(const half_t* sample, const float* timesteps, const half_t* ehs, int L,
                 const half_t* add_text, const float* add_time_ids, half_t* out, int B, int H, int W,
                 hipStream_t stream, const half_t* image_embeds = nullptr, int n_img = 0,
-                const half_t* control = nullptr, int n_ctrl = 0, float cn_scale = 0.f);
+                const half_t* control = nullptr, int n_ctrl = 0, float cn_scale = 0.f, const CfgIn* cfg_in = nullptr);
     void set_ip_adapter(IPAdapter* a);
     void set_controlnet(ControlNet* n);
 
@@ -220,7 +254,7 @@ struct UNet : Encoder {
     int run(Ctx& c, const half_t* sample, const float* timesteps, const half_t* ehs, int L,
             const half_t* add_text, const float* add_time_ids, half_t* out, int B, int H, int W,
             const half_t* image_embeds = nullptr, int n_img = 0, const half_t* control = nullptr, int n_ctrl = 0,
-            float cn_scale = 0.f);
+            float cn_scale = 0.f, const CfgIn* cfg_in = nullptr);
     // ControlNet step of run(): its hidden tensors into sites / mid (allocated by the caller)
     int run_controlnet(Ctx& c, const half_t* sample, const float* timesteps, const half_t* ehs, int L,
                        const half_t* add_text, const float* add_time_ids, int B, int H, int W, const half_t* control,

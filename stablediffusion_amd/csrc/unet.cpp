@@ -386,7 +386,7 @@ void run_resnet(Ctx& c, const Resnet& r, View x, int N, int H, int W, View out, 
 }
 
 void run_xformer(Ctx& c, const Xformer& t, View x, int N, int H, int W, View out, int G, View text_kv, int L,
-                 const GnStatBuf* x_stats, GnStatBuf** out_stats, GnStatBuf* out_buf, int out_groups) {
+                 const GnStatBuf* x_stats, GnStatBuf** out_stats, GnStatBuf* out_buf, int out_groups, const CfgShare* share) {
     Arena& a = *c.arena;
     const size_t mk = a.mark();
     const int C = t.C;
@@ -394,8 +394,12 @@ void run_xformer(Ctx& c, const Xformer& t, View x, int N, int H, int W, View out
     const long M = (long)N * T;
     const int d = C / t.heads;
     const bool fold = !t.blocks.empty() && t.blocks[0].fold;
+    // Shared CFG prefix: x holds N / 2 images, and so does everything up to the first block's attn2 query.  Buffers keep
+    // their N-image size (the arena plan is the unshared forward's); Np / Mp are what the prefix launches run on.
+    int Np = share ? N / 2 : N;
+    long Mp = (long)Np * T;
     View hn(a.alloc_h(M * C), C, C);
-    op_groupnorm(c, t.gn, x, hn, N, T, G, 1e-6f, 0, x_stats);
+    op_groupnorm(c, t.gn, x, hn, Np, T, G, 1e-6f, 0, x_stats);
     View cur(a.alloc_h(M * C), C, C), nxt(a.alloc_h(M * C), C, C);
     // row statistics of the residual stream at the three LayerNorm sites (cur -> ln1, t2 -> ln2, t3 -> ln3)
     RowStat st_cur, st_t2, st_t3;
@@ -408,7 +412,7 @@ void run_xformer(Ctx& c, const Xformer& t, View x, int N, int H, int W, View out
     f_cur.stat_out = &st_cur; f_t2.stat_out = &st_t2; f_t3.stat_out = &st_t3;
     f_ln1.ln_in = &st_cur; f_ln2.ln_in = &st_t2; f_ln3.ln_in = &st_t3;
     f_ln1.ln_eps = f_ln2.ln_eps = f_ln3.ln_eps = 1e-5f;
-    op_conv(c, t.pin, hn, N, H, W, cur, 1, 0, nullptr, 0, nullptr, 0, -1, 0, fold ? &f_cur : nullptr);
+    op_conv(c, t.pin, hn, Np, H, W, cur, 1, 0, nullptr, 0, nullptr, 0, -1, 0, fold ? &f_cur : nullptr);
     for (size_t bi = 0; bi < t.blocks.size(); ++bi) {
         const TBlock& b = t.blocks[bi];
         const bool more = bi + 1 < t.blocks.size();
@@ -416,21 +420,40 @@ void run_xformer(Ctx& c, const Xformer& t, View x, int N, int H, int W, View out
         View n(fold ? nullptr : a.alloc_h(M * C), C, C);
         View qkv(a.alloc_h(M * 3 * C), 3 * C, 3 * C);
         if (fold) {
-            op_conv(c, b.qkv, cur, N, H, W, qkv, 1, 0, nullptr, 0, nullptr, 0, -1, 0, &f_ln1);
+            op_conv(c, b.qkv, cur, Np, H, W, qkv, 1, 0, nullptr, 0, nullptr, 0, -1, 0, &f_ln1);
         } else {
-            op_layernorm(c, b.ln1, cur, n, M, 1e-5f);
-            op_conv(c, b.qkv, n, N, H, W, qkv);
+            op_layernorm(c, b.ln1, cur, n, Mp, 1e-5f);
+            op_conv(c, b.qkv, n, Np, H, W, qkv);
         }
         View att(a.alloc_h(M * C), C, C);
-        op_attention(c, qkv.slice(0, C), qkv.slice(C, C), qkv.slice(2 * C, C), att, N, T, T, t.heads, d, 0, 1);
+        op_attention(c, qkv.slice(0, C), qkv.slice(C, C), qkv.slice(2 * C, C), att, Np, T, T, t.heads, d, 0, 1);
         View t2(a.alloc_h(M * C), C, C);
-        op_conv(c, b.out1, att, N, H, W, t2, 1, 0, nullptr, 0, &cur, 0, -1, 0, fold ? &f_t2 : nullptr);
+        op_conv(c, b.out1, att, Np, H, W, t2, 1, 0, nullptr, 0, &cur, 0, -1, 0, fold ? &f_t2 : nullptr);
         View q(a.alloc_h(M * C), C, C);
         if (fold) {
-            op_conv(c, b.q2, t2, N, H, W, q, 1, 0, nullptr, 0, nullptr, 0, -1, 0, &f_ln2);
+            op_conv(c, b.q2, t2, Np, H, W, q, 1, 0, nullptr, 0, nullptr, 0, -1, 0, &f_ln2);
         } else {
-            op_layernorm(c, b.ln2, t2, n, M, 1e-5f);
-            op_conv(c, b.q2, n, N, H, W, q);
+            op_layernorm(c, b.ln2, t2, n, Mp, 1e-5f);
+            op_conv(c, b.q2, n, Np, H, W, q);
+        }
+        if (Np != N) {
+            // the text enters here: from now on the halves differ.  Widen what the N-image remainder reads -- the
+            // query, t2 (out2's residual), x (proj_out's residual) and the caller's tensors -- in one launch.
+            std::vector<RowDupSeg> segs = share->segs;
+            for (const View& v : {q, t2, x}) {
+                RowDupSeg g;
+                g.src = v.p; g.dst = v.p + Mp * v.ld;
+                g.ld_bytes = v.ld * 2; g.row_bytes = (long)v.C * 2; g.rows = Mp;
+                segs.push_back(g);
+            }
+            if (!c.dry && !c.err) {
+                double bytes = 0;
+                for (const RowDupSeg& g : segs) bytes += 2.0 * g.rows * g.row_bytes;
+                prof_open(c.stream, "row_dup_kernel", 0.0, bytes);
+                c.err = launch_row_dup(segs.data(), (int)segs.size(), c.stream);
+                prof_close(c.stream);
+            }
+            Np = N; Mp = M;
         }
         // IP-Adapter attached: text and image attention in one launch (scale 0: the text attention alone, as without one)
         if (c.ip_kv.p && c.ip_scale != 0.f)
@@ -466,7 +489,7 @@ void run_xformer(Ctx& c, const Xformer& t, View x, int N, int H, int W, View out
 
 // ----------------------------------------------------------------------------------------- forward
 int Encoder::run_temb(Ctx& c, const float* timesteps, const half_t* add_text, const float* add_time_ids, int B,
-                      float** tproj_out) {
+                      float** tproj_out, int rows_alloc) {
     Arena& a = *c.arena;
     const int* boc = cfg.block_out_channels;
     const int temb = boc[0] * 4;
@@ -476,7 +499,7 @@ int Encoder::run_temb(Ctx& c, const float* timesteps, const half_t* add_text, co
     float* sinus = a.alloc_f((long)B * boc[0]);
     float* e1 = a.alloc_f((long)B * temb);
     float* emb = a.alloc_f((long)B * temb);
-    float* tproj = a.alloc_f((long)B * temb_total);
+    float* tproj = a.alloc_f((long)std::max(B, rows_alloc) * temb_total);
     *tproj_out = tproj;
     if (go && !c.err) c.err = launch_timestep_sinusoid(timesteps, 1, sinus, B, boc[0], cfg.flip_sin_to_cos, cfg.freq_shift, boc[0], s);
     if (go && !c.err) c.err = launch_small_linear(sinus, boc[0], te1.w, te1.bias, e1, temb, B, boc[0], temb, 0, 1, s);
@@ -553,7 +576,7 @@ void Encoder::run_conv_in(Ctx& c, const half_t* sample, int B, int H, int W, Vie
 }
 
 View Encoder::run_down(Ctx& c, View x, GnStatBuf*& xs, int B, int& h, int& w, View text_kv, int L, const float* tproj,
-                       const SkipDst& skip_view, const SkipStat& skip_stat) {
+                       const SkipDst& skip_view, const SkipStat& skip_stat, const CfgShare* share) {
     Arena& a = *c.arena;
     const int nb = cfg.num_blocks;
     const int G = cfg.norm_num_groups;
@@ -566,9 +589,11 @@ View Encoder::run_down(Ctx& c, View x, GnStatBuf*& xs, int B, int& h, int& w, Vi
                 const size_t mk = a.mark();
                 View tmp(a.alloc_h((long)B * h * w * r.cout), r.cout, r.cout);
                 GnStatBuf* rs = nullptr;
-                run_resnet(c, r, x, B, h, w, tmp, G, eps, tproj, temb_total, xs, &rs);
+                const CfgShare* sh = (i == 0 && j == 0) ? share : nullptr;
+                run_resnet(c, r, x, sh ? B / 2 : B, h, w, tmp, G, eps, tproj, temb_total, xs, &rs);
                 View dst = skip_view(skip_i);
-                run_xformer(c, down_att[i][j], tmp, B, h, w, dst, G, text_kv, L, rs, &xs, skip_stat(skip_i, (long)h * w, r.cout));
+                run_xformer(c, down_att[i][j], tmp, B, h, w, dst, G, text_kv, L, rs, &xs, skip_stat(skip_i, (long)h * w, r.cout),
+                            0, sh);
                 a.release(mk);
                 x = dst;
             } else {
@@ -613,7 +638,7 @@ int Encoder::num_skips() const { return 1 + cfg.num_blocks * cfg.layers_per_bloc
 
 int UNet::run(Ctx& c, const half_t* sample, const float* timesteps, const half_t* ehs, int L,
               const half_t* add_text, const float* add_time_ids, half_t* out, int B, int H, int W,
-              const half_t* image_embeds, int n_img, const half_t* control, int n_ctrl, float cn_scale) {
+              const half_t* image_embeds, int n_img, const half_t* control, int n_ctrl, float cn_scale, const CfgIn* cfg_in) {
     Arena& a = *c.arena;
     const int nb = cfg.num_blocks;
     const int* boc = cfg.block_out_channels;
@@ -622,8 +647,29 @@ int UNet::run(Ctx& c, const half_t* sample, const float* timesteps, const half_t
     hipStream_t s = c.stream;
     const bool go = !c.dry;
 
+    // ---- shared CFG prefix (forward_cfg): B = 2 Bp images from Bp latents and Bp timesteps.  conv_in, the first
+    //      resnet and the first transformer up to its attn2 query run on Bp images; run_xformer widens what the rest
+    //      reads.  The scaled latents get their buffer whatever the scale, so every step of a loop keeps one plan. ----
+    const int Bp = cfg_in ? B / 2 : B;
+    CfgShare share;
+    if (cfg_in) {
+        const long n = (long)Bp * cfg.in_channels * H * W;
+        half_t* scaled = a.alloc_h(n);
+        sample = cfg_in->latents;
+        if (cfg_in->in_scale != 1.f) {
+            if (go && !c.err) c.err = launch_scale_copy_f16(cfg_in->latents, scaled, n, cfg_in->in_scale, s);
+            sample = scaled;
+        }
+    }
+
     float* tproj = nullptr;
-    if (int rc = run_temb(c, timesteps, add_text, add_time_ids, B, &tproj)) return rc;
+    if (int rc = run_temb(c, timesteps, add_text, add_time_ids, Bp, &tproj, B)) return rc;
+    if (cfg_in) {
+        RowDupSeg g;
+        g.src = tproj; g.dst = tproj + (long)Bp * temb_total;
+        g.ld_bytes = g.row_bytes = (long)Bp * temb_total * 4; g.rows = 1;
+        share.segs.push_back(g);
+    }
 
     // ---- text K/V of every cross-attention block in one GEMM: [B*L, ctx] x [ctx, sum 2C] ----
     const bool kv_cached = kv_cache_on && !graph_enabled && kv_cache != nullptr;
@@ -718,7 +764,7 @@ int UNet::run(Ctx& c, const half_t* sample, const float* timesteps, const half_t
     // ---- ControlNet: its encoder on the same sample, timestep and text.  The pre-zero-conv hidden tensors of every
     //      skip and of the mid block live above the concatenation buffers (released after the residual adds); the
     //      ControlNet runs on a GroupNorm ring of its own, this forward's ring is restored after it ----
-    const bool use_cn = cn && control && cn_scale != 0.f;
+    const bool use_cn = cn && control && cn_scale != 0.f && !cfg_in;
     const size_t cn_mark = a.mark();
     std::vector<View> cn_sites;
     std::vector<int> cn_rows;
@@ -748,12 +794,20 @@ int UNet::run(Ctx& c, const half_t* sample, const float* timesteps, const half_t
     // ---- conv_in: one launch straight from the NCHW latents (edge.hip); otherwise (inpainting's 9 channels, odd maps)
     //      im2col into a 64-wide K, then the GEMM kernel ----
     int h = H, w = W;
-    run_conv_in(c, sample, B, H, W, skip_view(skip_i), skip_stat(skip_i, (long)H * W, boc[0]), nullptr, &xs);
+    run_conv_in(c, sample, Bp, H, W, skip_view(skip_i), skip_stat(skip_i, (long)H * W, boc[0]), nullptr, &xs);
     View x = skip_view(skip_i++);
+    if (cfg_in) {
+        // skip 0 is read again by the last up resnet, on all B images.  (Its GroupNorm summaries are not: their only
+        // reader besides the first resnet is the SD_GN_CAT merge, which forward_cfg does not share under.)
+        RowDupSeg g;
+        g.src = x.p; g.dst = x.p + (long)Bp * H * W * x.ld;
+        g.ld_bytes = x.ld * 2; g.row_bytes = (long)x.C * 2; g.rows = (long)Bp * H * W;
+        share.segs.push_back(g);
+    }
 
     // ---- down path ----
     x = run_down(c, x, xs, B, h, w, text_kv, L, tproj, [&](int si) { return skip_view(si); },
-                 [&](int si, long HWs, int C) { return skip_stat(si, HWs, C); });
+                 [&](int si, long HWs, int C) { return skip_stat(si, HWs, C); }, cfg_in ? &share : nullptr);
 
     // ---- mid block ----
     run_mid(c, x, xs, B, h, w, text_kv, L, tproj, View(cats[0].p, cats[0].c1 + cats[0].c2, cats[0].c1));
@@ -914,6 +968,7 @@ UNet::~UNet() {
     if (ipkv_cache) (void)hipFree(ipkv_cache);
     if (cond_cache) (void)hipFree(cond_cache);
     if (cnkv_cache) (void)hipFree(cnkv_cache);
+    if (cfg_slab) (void)hipFree(cfg_slab);
     if (ip) ip->attached = nullptr;
     if (cn) cn->attached = nullptr;
 }
@@ -993,8 +1048,12 @@ int UNet::forward_graph(const half_t* sample, const float* timesteps, const half
 
 int UNet::forward(const half_t* sample, const float* timesteps, const half_t* ehs, int L, const half_t* add_text,
                   const float* add_time_ids, half_t* out, int B, int H, int W, hipStream_t stream,
-                  const half_t* image_embeds, int n_img, const half_t* control, int n_ctrl, float cn_scale) {
+                  const half_t* image_embeds, int n_img, const half_t* control, int n_ctrl, float cn_scale, const CfgIn* cfg_in) {
     if (!finalized) { set_error("unet: forward before finalize"); return 2; }
+    if (cfg_in && (B % 2 != 0 || graph_enabled || control || !unet_cfg_share_eligible(cfg))) {
+        set_error("unet: shared CFG prefix not available for this call");
+        return 2;
+    }
     const int div = 1 << (cfg.num_blocks - 1);
     if (B <= 0 || H % div != 0 || W % div != 0) { set_error("unet: H and W must be divisible by 2^(blocks-1)"); return 1; }
     if (ip && !image_embeds) { set_error("unet: an IP-Adapter is attached: image_embeds required"); return 1; }
@@ -1059,14 +1118,14 @@ int UNet::forward(const half_t* sample, const float* timesteps, const half_t* eh
     }
     // (the IP-Adapter's image token count joins the key: set_ip_adapter resets the plan)
     const long key = ((long)B << 40) ^ ((long)H << 20) ^ (long)W ^ ((long)L << 52) ^ (kv_cache_on ? (1L << 62) : 0) ^
-                     (ip ? (long)(n_img * ip->n_tok) << 32 : 0);
+                     (ip ? (long)(n_img * ip->n_tok) << 32 : 0) ^ (cfg_in ? (1L << 61) : 0);
     // (the ControlNet's arena use depends on whether it runs and on n_ctrl: set_controlnet resets the plan)
     const long cn_key = use_cn ? n_ctrl : 0;
     if (key != planned_key || cn_key != planned_cn) {
         Ctx dry{&arena, stream, true};
         arena.begin(true);
         int rc = run(dry, sample, timesteps, ehs, L, add_text, add_time_ids, out, B, H, W, image_embeds, n_img, control,
-                     n_ctrl, cn_scale);
+                     n_ctrl, cn_scale, cfg_in);
         if (rc) return rc;
         // growing the slab frees the old one: make sure nothing enqueued earlier still uses it
         if (arena.peak() > arena.capacity()) {
@@ -1080,9 +1139,52 @@ int UNet::forward(const half_t* sample, const float* timesteps, const half_t* eh
     Ctx ctx{&arena, stream, false};
     arena.begin(false);
     int rc = run(ctx, sample, timesteps, ehs, L, add_text, add_time_ids, out, B, H, W, image_embeds, n_img, control, n_ctrl,
-                 cn_scale);
+                 cn_scale, cfg_in);
     if (!rc && arena.overflow()) { set_error("unet: workspace overflow (planner bug)"); return 2; }
     return rc;
+}
+
+bool unet_cfg_share_eligible(const sd_unet_config& cfg) {
+    return cfg.addition_time_embed_dim == 0 && cfg.num_blocks >= 1 && cfg.down_block_has_attn[0] != 0 &&
+           cfg.transformer_layers[0] >= 1;
+}
+
+bool UNet::cfg_share_active(bool share) const {
+    // read once per process, like the other A/B switches
+    static const bool off = getenv("SD_NO_CFG_SHARE") != nullptr;
+    static const bool gn_cat = getenv("SD_GN_CAT") != nullptr;
+    // (an attached ControlNet needs its control image: forward() says so)
+    return share && !off && !gn_cat && !graph_enabled && !cn && unet_cfg_share_eligible(cfg);
+}
+
+int UNet::forward_cfg(const half_t* latents, const float* timesteps, const half_t* ehs, int L, const half_t* add_text,
+                      const float* add_time_ids, const half_t* image_embeds, int n_img, float in_scale, bool share,
+                      half_t* out, int B, int H, int W, hipStream_t stream) {
+    if (!finalized) { set_error("unet: forward before finalize"); return 2; }
+    if (B <= 0 || H <= 0 || W <= 0) { set_error("unet: forward_cfg: empty batch"); return 1; }
+    if (cfg_share_active(share)) {
+        CfgIn in;
+        in.latents = latents;
+        in.in_scale = in_scale;
+        return forward(nullptr, timesteps, ehs, L, add_text, add_time_ids, out, 2 * B, H, W, stream, image_embeds, n_img,
+                       nullptr, 0, 0.f, &in);
+    }
+    // not shared: cat([latents * in_scale] * 2) and the doubled timesteps in a buffer of the engine's, then the forward
+    // every caller ran before.  (One buffer: calls on one stream are ordered by it, like the graph path's staging.)
+    const size_t n = (size_t)B * cfg.in_channels * H * W;
+    const size_t lat_bytes = (2 * n * sizeof(half_t) + 255) & ~size_t(255), need = lat_bytes + 2 * (size_t)B * sizeof(float);
+    if (need > cfg_cap) {
+        SD_HIP_CHECK(hipDeviceSynchronize());
+        if (cfg_slab) (void)hipFree(cfg_slab);
+        cfg_slab = nullptr; cfg_cap = 0;
+        SD_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&cfg_slab), need));
+        cfg_cap = need;
+    }
+    half_t* lat2 = reinterpret_cast<half_t*>(cfg_slab);
+    float* ts2 = reinterpret_cast<float*>(cfg_slab + lat_bytes);
+    if (int rc = launch_cfg_duplicate(latents, lat2, (long)n, in_scale, stream)) return rc;
+    if (int rc = launch_dup_f32(timesteps, ts2, B, stream)) return rc;
+    return forward(lat2, ts2, ehs, L, add_text, add_time_ids, out, 2 * B, H, W, stream, image_embeds, n_img);
 }
 
 }  // namespace sd

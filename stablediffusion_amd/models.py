@@ -317,6 +317,58 @@ class HipUNet2DConditionModel:
 
     forward = __call__
 
+    @property
+    def cfg_share_eligible(self) -> bool:
+        """Whether this topology lets forward_cfg run the CFG-shared start of the UNet once per latent."""
+        c = _unet_config_struct(self.cfg)
+        return bool(self._lib.sd_unet_cfg_share(C.byref(c)))
+
+    def forward_cfg(self, latents, timestep, encoder_hidden_states, added_cond_kwargs=None, in_scale: float = 1.0,
+                    share: bool = True):
+        """One classifier-free-guidance forward from the UN-duplicated latents [B, C, H, W]: what
+        self(torch.cat([fp16(latents * in_scale)] * 2), timestep, encoder_hidden_states) returns ([2B, ...], negative
+        half first; encoder_hidden_states and added_cond_kwargs hold 2B rows).  With `share` the engine runs everything
+        in front of the first cross-attention once per latent where the topology allows (sd_unet_forward_cfg);
+        otherwise it duplicates itself and the result is bitwise the two-step one.  Not for an attached ControlNet."""
+        if not self._finalized:
+            raise _lib.EngineError("weights not loaded")
+        if self._cn is not None:
+            raise ValueError("forward_cfg takes no ControlNet: duplicate the latents and call the model")
+        dev = self.device
+        latents = _as_f16(latents, dev)
+        B, _, H, W = latents.shape
+        ehs = _as_f16(encoder_hidden_states, dev)
+        if ehs.shape[0] != 2 * B:
+            raise ValueError(f"encoder_hidden_states batch {ehs.shape[0]} != 2 x latents batch {B}")
+        if ehs.shape[2] != self.cfg.cross_attention_dim:
+            raise ValueError("encoder_hidden_states width != cross_attention_dim")
+        if isinstance(timestep, (int, float)):
+            t = torch.full((B,), float(timestep), device=dev, dtype=torch.float32)
+        else:
+            t = torch.as_tensor(timestep, device=dev).to(torch.float32).reshape(-1)
+            if t.numel() not in (1, B):
+                raise ValueError(f"timestep: expected a scalar or {B} values (one per latent), got {t.numel()}")
+            t = t.expand(B).contiguous() if t.numel() == 1 else t.contiguous()
+        pt = pi = None
+        if self.cfg.addition_embed_type == "text_time":
+            if not added_cond_kwargs or "text_embeds" not in added_cond_kwargs or "time_ids" not in added_cond_kwargs:
+                raise ValueError("added_cond_kwargs needs text_embeds and time_ids for text_time conditioning")
+            add_text = _as_f16(added_cond_kwargs["text_embeds"], dev)
+            add_ids = added_cond_kwargs["time_ids"].to(device=dev, dtype=torch.float32).contiguous()
+            if add_text.shape[0] != 2 * B or add_ids.shape[0] != 2 * B:
+                raise ValueError("text_embeds / time_ids must hold 2 x latents batch rows")
+            pt, pi = C.c_void_p(add_text.data_ptr()), C.c_void_p(add_ids.data_ptr())
+        img = self._image_embeds(added_cond_kwargs, 2 * B, dev)
+        out = torch.empty((2 * B, self.cfg.out_channels, H, W), device=dev, dtype=torch.float16)
+        with torch.cuda.device(dev):
+            rc = self._lib.sd_unet_forward_cfg(self._h, C.c_void_p(latents.data_ptr()), C.c_void_p(t.data_ptr()),
+                                               C.c_void_p(ehs.data_ptr()), ehs.shape[1], pt, pi,
+                                               C.c_void_p(img.data_ptr()) if img is not None else None,
+                                               img.shape[1] if img is not None else 0, float(in_scale), int(bool(share)),
+                                               C.c_void_p(out.data_ptr()), B, H, W, C.c_void_p(_stream_ptr()))
+        _lib.check(rc, "sd_unet_forward_cfg")
+        return (out,)
+
     # LoRA adapters arrive fused into the weights (stablediffusion_amd.weights.fuse_lora); the
     # reference's runtime adapter switches (stable_diffusion.py:252-335) are not part of the engine.
     def set_adapters(self, *a, **k):

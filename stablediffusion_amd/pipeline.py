@@ -295,6 +295,9 @@ class StableDiffusionUnifiedPipeline:
         self.device = torch.device(device) if device is not None else torch.device("cpu")
         self.output_type = output_type if output_type is not None else "pt"
         self.model: Optional[SDModelWrapper] = None
+        # the fused CFG step lets the engine run the start of the UNet once per latent (HipUNet2DConditionModel.forward_cfg);
+        # False keeps the engine's duplicate-then-forward form
+        self.cfg_share = True
 
     # ------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -622,13 +625,19 @@ class StableDiffusionUnifiedPipeline:
         latents = latents.contiguous()
         B = latents.shape[0]
         st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        lat2 = torch.empty((2 * B,) + tuple(latents.shape[1:]), device=latents.device, dtype=latents.dtype)
-        rc = lib.sd_cfg_duplicate(C.c_void_p(latents.data_ptr()), C.c_void_p(lat2.data_ptr()),
-                                  latents[0].numel(), B, plan.in_scale, st)
-        if rc:
-            raise RuntimeError(lib.sd_last_error().decode())
-        noise_pred = model.base(lat2, t, prompt_embeds, cross_attention_kwargs=cross_attention_kwargs,
-                                added_cond_kwargs=added_cond_kwargs, return_dict=False, **unet_kwargs)[0]
+        if not unet_kwargs and hasattr(model.base, "forward_cfg") and getattr(model.base, "controlnet", None) is None:
+            # the engine takes the un-duplicated latents: no 2B-row copy, and the layers in front of the first
+            # cross-attention run once per latent
+            noise_pred = model.base.forward_cfg(latents, t, prompt_embeds, added_cond_kwargs=added_cond_kwargs,
+                                                in_scale=plan.in_scale, share=self.cfg_share)[0]
+        else:               # ControlNet calls: duplicate, then the forward that takes the control image
+            lat2 = torch.empty((2 * B,) + tuple(latents.shape[1:]), device=latents.device, dtype=latents.dtype)
+            rc = lib.sd_cfg_duplicate(C.c_void_p(latents.data_ptr()), C.c_void_p(lat2.data_ptr()),
+                                      latents[0].numel(), B, plan.in_scale, st)
+            if rc:
+                raise RuntimeError(lib.sd_last_error().decode())
+            noise_pred = model.base(lat2, t, prompt_embeds, cross_attention_kwargs=cross_attention_kwargs,
+                                    added_cond_kwargs=added_cond_kwargs, return_dict=False, **unet_kwargs)[0]
         if plan.use_hist and hist is None:
             hist = torch.zeros(latents.shape, device=latents.device, dtype=torch.float32)
         out = latents.clone()
