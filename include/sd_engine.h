@@ -187,6 +187,14 @@ int sd_unet_forward_cfg(sd_unet* u, const void* latents, const float* timesteps,
 /* 1 when the topology lets sd_unet_forward_cfg share: no per-sample additional embedding (text_time makes the time
  * embedding differ between the halves) and a transformer in down block 0.  Needs no device. */
 int sd_unet_cfg_share(const sd_unet_config* cfg);
+/* UNet2DConditionModel.enable_freeu(s1, s2, b1, b2) / disable_freeu() of diffusers 0.27.2 (enable = 0: the factors are
+ * ignored and the forward is again exactly the plain one).  On, every resnet of up blocks 0 and 1 reads
+ *   cat([hidden with its first C1 / 2 channels times b, fourier_filter(skip, threshold = 1, scale = s)])
+ * with (b, s) = (b1, s1) in block 0 and (b2, s2) in block 1 (diffusers' apply_freeu), after any ControlNet residual was
+ * added to the skip: one in-place launch per resnet (sd_op_freeu).  Holds for sd_unet_forward, _ex, _cn and _cfg.
+ * Non-finite factors: SD_ERR_INVALID.  Graph replay (sd_unet_use_graph) with FreeU on is rejected by the forward
+ * (SD_ERR_UNSUPPORTED). */
+int sd_unet_set_freeu(sd_unet* u, int enable, float s1, float s2, float b1, float b2);
 /* Bytes of device memory held (packed weights, workspace). */
 int sd_unet_memory(const sd_unet* u, int64_t* weight_bytes, int64_t* workspace_bytes);
 
@@ -457,6 +465,12 @@ int sd_op_timestep_sinusoid(const float* t, float* out, int count, int dim, int 
  * W f16 row-major [n_out, k]. */
 int sd_op_small_linear(const float* x, const void* w_f16, const float* bias, float* y, int B, int K, int n_out,
                        int silu_in, int silu_out, void* stream);
+/* diffusers 0.27.2 apply_freeu on one concatenation cat_nhwc [N, H, W, C1 + C2] f16, in place:
+ *   cat[..., :C1 / 2] *= b;   cat[..., C1:] = fourier_filter(cat[..., C1:], threshold = 1, scale = s) over (H, W)
+ * i.e. the skip's frequencies {-1, 0} x {-1, 0} times s and the real part kept, computed in closed form from seven fp32
+ * moments per (image, channel) plane and rounded to f16 once; cat[..., C1 / 2 : C1] is not touched.  C1 even, C2 >= 1,
+ * finite factors (SD_ERR_INVALID otherwise); H + W <= 4096 (SD_ERR_UNSUPPORTED beyond). */
+int sd_op_freeu(void* cat_nhwc, int N, int H, int W, int C1, int C2, float b, float s, void* stream);
 /* LayerNorm over the last dim of [rows, C] f16. */
 int sd_op_layernorm(const void* x, const void* gamma, const void* beta, void* y, int rows, int C,
                     float eps, void* stream);

@@ -98,6 +98,7 @@ SIGNATURES = {
     "sd_unet_cfg_share": (_I, [C.POINTER(SdUNetConfig)]),
     "sd_unet_set_ip_adapter": (_I, [_P, _P]),
     "sd_unet_set_ip_adapter_scale": (_I, [_P, _F]),
+    "sd_unet_set_freeu": (_I, [_P, _I, _F, _F, _F, _F]),
     "sd_ip_adapter_create": (_I, [_P, _I, _I, C.POINTER(_P)]),
     "sd_ip_adapter_destroy": (_I, [_P]),
     "sd_ip_adapter_num_weights": (_I, [_P]),
@@ -163,6 +164,7 @@ SIGNATURES = {
     "sd_bench_groupnorm": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _I, C.POINTER(_F), _P]),
     "sd_op_timestep_sinusoid": (_I, [_P, _P, _I, _I, _I, _F, _P]),
     "sd_op_small_linear": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "sd_op_freeu": (_I, [_P, _I, _I, _I, _I, _I, _F, _F, _P]),
     "sd_op_layernorm": (_I, [_P, _P, _P, _P, _I, _I, _F, _P]),
     "sd_op_attention": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "sd_attention_plan": (_I, [_I, _I, _I, _I, _I, _I, _I, C.POINTER(_I)]),

@@ -1,5 +1,6 @@
 // extern "C" surface of libsd_engine.so -- see include/sd_engine.h for the contract and for the
 // reference interfaces (file:line) each entry point replaces.
+#include <cmath>
 #include <cstdio>
 #include <new>
 
@@ -202,6 +203,17 @@ int sd_unet_set_ip_adapter_scale(sd_unet* u, float scale) {
     if (!u) { set_error("null handle"); return SD_ERR_INVALID; }
     if (!(scale == scale)) { set_error("sd_unet_set_ip_adapter_scale: NaN"); return SD_ERR_INVALID; }
     u->impl.ip_scale = scale;
+    return SD_OK;
+}
+int sd_unet_set_freeu(sd_unet* u, int enable, float s1, float s2, float b1, float b2) {
+    if (!u) { set_error("null handle"); return SD_ERR_INVALID; }
+    if (!enable) { u->impl.freeu_on = false; return SD_OK; }
+    if (!std::isfinite(s1) || !std::isfinite(s2) || !std::isfinite(b1) || !std::isfinite(b2)) {
+        set_error("sd_unet_set_freeu: s1, s2, b1, b2 must be finite");
+        return SD_ERR_INVALID;
+    }
+    u->impl.freeu_on = true;
+    u->impl.freeu_s1 = s1; u->impl.freeu_s2 = s2; u->impl.freeu_b1 = b1; u->impl.freeu_b2 = b2;
     return SD_OK;
 }
 
@@ -1110,6 +1122,11 @@ int sd_op_layernorm(const void* x, const void* gamma_f32, const void* beta_f32, 
     return launch_layernorm(static_cast<const half_t*>(x), C, static_cast<const float*>(gamma_f32),
                             static_cast<const float*>(beta_f32), static_cast<half_t*>(y), C, rows, C, eps,
                             static_cast<hipStream_t>(stream));
+}
+
+int sd_op_freeu(void* cat_nhwc, int N, int H, int W, int C1, int C2, float b, float s, void* stream) {
+    if (!cat_nhwc) { set_error("sd_op_freeu: null argument"); return SD_ERR_INVALID; }
+    return launch_freeu(static_cast<half_t*>(cat_nhwc), (long)C1 + C2, N, H, W, C1, C2, b, s, static_cast<hipStream_t>(stream));
 }
 
 int sd_op_attention(const void* q, const void* k, const void* v, void* out, int B, int Tq, int Tk, int heads, int d,

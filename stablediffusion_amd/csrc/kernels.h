@@ -240,6 +240,16 @@ int launch_cn_cond_conv(const CnCondConvParams& p, hipStream_t s);
 int launch_cn_pack_cond(const half_t* w_oihw, float* out, int O, int I, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------
+// FreeU (freeu.hip)
+// ---------------------------------------------------------------------------------------------
+// In place on a concatenation view x [N, H W, ld] fp16, hidden = columns [0, C1), skip = [C1, C1 + C2):
+//   hidden[:, :C1 / 2] *= b;   skip = fourier_filter(skip, threshold 1, scale s) over (H, W)
+// (diffusers 0.27.2 apply_freeu), one launch for both halves and all N images; fp32 moments and correction, one
+// rounding to fp16.  C1 even, C2 >= 1, ld >= C1 + C2; columns past C1 + C2 and hidden[:, C1 / 2:] are not touched.
+// Returns 1 for arguments outside that domain or non-finite factors, 4 for H + W > 4096.
+int launch_freeu(half_t* x, long ld, int N, int H, int W, int C1, int C2, float b, float s, hipStream_t st);
+
+// ---------------------------------------------------------------------------------------------
 // Small / elementwise kernels (misc.hip)
 // ---------------------------------------------------------------------------------------------
 // out[b, :] = [cos(t_b f_i) | sin(t_b f_i)] (flip) or [sin | cos]; f_i = exp(-ln(1e4) i/(half-shift))

@@ -244,6 +244,12 @@ struct UNet : Encoder {
     const half_t* cnkv_src = nullptr;
     int cnkv_B = 0, cnkv_L = 0;
 
+    // ---- FreeU (sd_unet_set_freeu): off = the forward as without the feature.  On, every resnet of up blocks 0 and 1
+    // gets one in-place launch on its concatenation buffer before norm1 reads it: (b1, s1) in block 0, (b2, s2) in
+    // block 1.  It allocates nothing, so the arena plan does not depend on it; not under graphs.
+    bool freeu_on = false;
+    float freeu_s1 = 1.f, freeu_s2 = 1.f, freeu_b1 = 1.f, freeu_b2 = 1.f;
+
     ConvW conv_out;
     NormW norm_out;
     std::vector<std::vector<Resnet>> up_res;

@@ -848,6 +848,19 @@ int UNet::run(Ctx& c, const half_t* sample, const float* timesteps, const half_t
             const Resnet& r = up_res[i][j];
             View xin(ct.p, ct.c1 + ct.c2, ct.c1 + ct.c2);
             const bool last_in_block = (j == cfg.layers_per_block);
+            // FreeU (diffusers apply_freeu, up blocks 0 and 1): scale the first half of the hidden channels and filter
+            // the skip, in place in the concatenation, after the ControlNet's residuals and before norm1 reads it.  Both
+            // producers' GroupNorm summaries are stale afterwards: norm1 of such a resnet runs its own statistics pass,
+            // and nobody emits summaries into a hidden half that FreeU will rescale (fu_next).
+            const bool fu = freeu_on && i < 2;
+            const bool fu_next = freeu_on && (last_in_block ? i + 1 : i) < 2;
+            if (fu && go && !c.err) {
+                const double elems = (double)B * h * w * (ct.c1 / 2 + ct.c2);
+                prof_open(s, "freeu_kernel", 16.0 * B * h * w * ct.c2, 4.0 * elems);
+                c.err = launch_freeu(xin.p, xin.ld, B, h, w, ct.c1, ct.c2, i == 0 ? freeu_b1 : freeu_b2,
+                                     i == 0 ? freeu_s1 : freeu_s2, s);
+                prof_close(s);
+            }
             const bool last = last_in_block && i == nb - 1;
             // destination of this layer's output: next cat's hidden half, an upsample input, or the tail
             View dst;
@@ -866,7 +879,7 @@ int UNet::run(Ctx& c, const half_t* sample, const float* timesteps, const half_t
             const int Ccat = ct.c1 + ct.c2, si = nskip - 1 - k;
             GnStatBuf catst;
             const GnStatBuf* xin_stats = nullptr;
-            if (!no_cat_stats && hid_ready && hid_ready->st.part && sst[(size_t)si].st.part && gn_wants_stats(HWc, Ccat, G) &&
+            if (!no_cat_stats && !fu && hid_ready && hid_ready->st.part && sst[(size_t)si].st.part && gn_wants_stats(HWc, Ccat, G) &&
                 ct.c2 % G == 0 && (Ccat / G) % (ct.c2 / G) == 0 && ct.c1 % (ct.c2 / G) == 0) {
                 float* fin = a.alloc_f((long)B * G * 2);
                 if (go && !c.err) {
@@ -881,7 +894,7 @@ int UNet::run(Ctx& c, const half_t* sample, const float* timesteps, const half_t
             hid_ready = nullptr;
             // what the NEXT concatenation's norm1 needs from this layer's output (or from the upsample convolution after it)
             int nx_groups = 0;
-            if (!last && hid.buf && !no_cat_stats) {
+            if (!last && hid.buf && !no_cat_stats && !fu_next) {
                 const Cat& nx = cats[(size_t)k + 1];
                 const int u = gn_cat_unit(nx.c1, nx.c2, G);
                 if (gn_wants_stats(last_in_block ? HWc * 4 : HWc, nx.c1 + nx.c2, G) && (u >= 8 || u == 4) && nx.c1 / u <= 128) nx_groups = nx.c1 / u;
@@ -1076,6 +1089,7 @@ int UNet::forward(const half_t* sample, const float* timesteps, const half_t* eh
         cn_scale = 0.f;
     }
     const bool use_cn = cn && cn_scale != 0.f;
+    if (freeu_on && graph_enabled) { set_error("unet: graph replay with FreeU enabled is not supported"); return 4; }
     if (graph_enabled && !prof_enabled())
         return forward_graph(sample, timesteps, ehs, L, add_text, add_time_ids, out, B, H, W, stream);
     if (kv_cache_on) {          // persistent buffer for the text K/V (outside the per-forward arena)

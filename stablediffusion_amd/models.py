@@ -17,6 +17,7 @@ PyTorch is plumbing here (device buffers + the current HIP stream); all arithmet
 from __future__ import annotations
 
 import ctypes as C
+import math
 import weakref
 from types import SimpleNamespace
 from typing import Dict, Optional
@@ -118,6 +119,7 @@ class HipUNet2DConditionModel:
         self._ip = None                # attached HipIPAdapter (attach_ip_adapter)
         self._ip_scale = 1.0
         self._cn = None                # attached HipControlNetModel (attach_controlnet)
+        self._freeu = None             # (s1, s2, b1, b2) while FreeU is on (enable_freeu)
 
     # -- weights -------------------------------------------------------------------------------
     def load_state_dict(self, state_dict: Dict[str, torch.Tensor], strict: bool = True):
@@ -131,7 +133,8 @@ class HipUNet2DConditionModel:
     def rebuild(self, state_dict: Dict[str, torch.Tensor]):
         """A fresh engine of the same configuration on the same device with other weights (LoRA re-fuse:
         the packed weights are immutable once finalized)."""
-        return type(self)(self.cfg, self.device).load_state_dict(state_dict)
+        new = type(self)(self.cfg, self.device).load_state_dict(state_dict)
+        return new.enable_freeu(*self._freeu) if self._freeu is not None else new     # FreeU survives the rebuild
 
     def rebuild_factory(self):
         """`rebuild` without a reference to this engine: the LoRA re-fuse drops the old engine (and its device memory)
@@ -186,6 +189,23 @@ class HipUNet2DConditionModel:
         """diffusers' set_ip_adapter_scale: lambda of the image branch (default 1.0; 0 = text attention only)."""
         _lib.check(self._lib.sd_unet_set_ip_adapter_scale(self._h, float(scale)), "sd_unet_set_ip_adapter_scale")
         self._ip_scale = float(scale)
+        return self
+
+    def enable_freeu(self, s1: float, s2: float, b1: float, b2: float):
+        """diffusers' UNet2DConditionModel.enable_freeu (same argument order): in up blocks 0 and 1 the first half of
+        the backbone channels is scaled by b1 / b2 and the skip's lowest frequencies by s1 / s2, one in-place engine
+        launch per resnet.  The settings survive `rebuild`.  Not available under `use_graph`."""
+        vals = tuple(float(v) for v in (s1, s2, b1, b2))
+        if not all(math.isfinite(v) for v in vals):
+            raise ValueError(f"enable_freeu: s1, s2, b1, b2 must be finite, got {vals}")
+        _lib.check(self._lib.sd_unet_set_freeu(self._h, 1, *vals), "sd_unet_set_freeu")
+        self._freeu = vals
+        return self
+
+    def disable_freeu(self):
+        """diffusers' disable_freeu: the forward is again exactly the plain one."""
+        _lib.check(self._lib.sd_unet_set_freeu(self._h, 0, 1.0, 1.0, 1.0, 1.0), "sd_unet_set_freeu")
+        self._freeu = None
         return self
 
     def attach_controlnet(self, controlnet: Optional["HipControlNetModel"]):

@@ -47,6 +47,7 @@ class SDModelWrapper:
         self._ip = None                  # (diffusers-named state dict, image_embed_dim, num_tokens)
         self._ip_scale = 1.0
         self._cn = None                  # ControlNet (configuration, diffusers-named state dict): load_controlnet
+        self._freeu = None               # (s1, s2, b1, b2) while FreeU is on: enable_freeu
         # host copies of the weights the LoRA adapters are folded into (load_lora_weights); the engine
         # itself keeps only its packed device copy
         self._lora = None
@@ -114,9 +115,10 @@ class SDModelWrapper:
         fused = self._lora.fused("unet")
         old = self.base
         graph = bool(getattr(old, "_graph_on", False))
+        freeu = getattr(old, "_freeu", self._freeu)     # the engine's own record wins: enable_freeu may be called on .base
         self.base = None                     # the old engine's device memory goes before the new one is packed
         del old
-        self.base = self._rebuild_from(fused, graph)
+        self.base = self._rebuild_from(fused, graph, freeu)
         for part in ("text_encoder", "text_encoder_2"):
             if self._te_sd[part] is not None and (self._lora.touches(part) or self._lora_applied is not None):
                 enc = getattr(self, part, None)
@@ -129,7 +131,7 @@ class SDModelWrapper:
                     raise ValueError(f"{type(enc).__name__} cannot take fused text-encoder LoRA weights")
         self._lora_applied = sig
 
-    def _rebuild_from(self, fused, graph):
+    def _rebuild_from(self, fused, graph, freeu=None):
         base = self._base_factory(fused)
         if graph and hasattr(base, "use_graph"):
             base.use_graph(True)
@@ -137,7 +139,19 @@ class SDModelWrapper:
             self._attach_ip(base)
         if self._cn is not None:             # and so does the ControlNet
             self._attach_cn(base)
+        self._freeu = freeu
+        if freeu is not None:                # and FreeU
+            base.enable_freeu(*freeu)
         return base
+
+    # ---- FreeU (diffusers pipelines' enable_freeu / disable_freeu: forwarded to the UNet) ----
+    def enable_freeu(self, s1: float, s2: float, b1: float, b2: float):
+        self.base.enable_freeu(s1, s2, b1, b2)
+        self._freeu = (float(s1), float(s2), float(b1), float(b2))
+
+    def disable_freeu(self):
+        self.base.disable_freeu()
+        self._freeu = None
 
     # ---- ControlNet (diffusers ControlNetModel, one per model; the pipeline takes control_image=) ----
     def _attach_cn(self, base):
