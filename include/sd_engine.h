@@ -61,6 +61,7 @@ typedef struct sd_unet_config {
     float   freq_shift;
     int32_t addition_time_embed_dim;               /* 0 = no text_time conditioning (SD1.5) */
     int32_t projection_class_embeddings_input_dim; /* SDXL: 2816 */
+    int32_t time_cond_proj_dim;                    /* 0 = no time_embedding.cond_proj; LCM-distilled UNets: 256; <= 1024 */
 } sd_unet_config;
 
 /* AutoencoderKL hyper-parameters (convert_from_A1111.py:490-511). */
@@ -148,6 +149,20 @@ int sd_unet_text_kv_cache(sd_unet* u, int enable);
 int sd_unet_forward_ex(sd_unet* u, const void* sample, const float* timesteps, const void* ehs, int ehs_len,
                        const void* add_text, const float* add_time_ids, const void* image_embeds, int n_img, void* out,
                        int B, int H, int W, void* stream);
+/* sd_unet_forward_ex of a guidance-embedded UNet (time_cond_proj_dim > 0: Latent Consistency Models; diffusers 0.27.2
+ * UNet2DConditionModel.forward(timestep_cond=), TimestepEmbedding.cond_proj):
+ *   timestep_cond [B,cond_dim] f32 (device) or NULL   the guidance-scale embedding; cond_dim = time_cond_proj_dim
+ * The time embedding's input becomes sinusoid(t) + timestep_cond W_cond^T (no bias), formed by one launch
+ * (sd_op_timestep_cond_embedding) in the place of the sinusoid's, so the forward has as many launches as the plain one.
+ * NULL skips the projection, as diffusers does: the call is sd_unet_forward_ex.  SD_ERR_INVALID: a non-NULL
+ * timestep_cond on a UNet without the projection, cond_dim != time_cond_proj_dim.  An attached IP-Adapter works as in
+ * sd_unet_forward_ex; an attached ControlNet is SD_ERR_UNSUPPORTED (diffusers' ControlNetModel has no such projection
+ * and no guidance-embedded checkpoint ships one).  FreeU holds as for the other entries.  Graph replay
+ * (sd_unet_use_graph) is supported: timestep_cond is staged like timesteps, its presence is part of the graph's shape
+ * key, and replay is bitwise the eager result. */
+int sd_unet_forward_tc(sd_unet* u, const void* sample, const float* timesteps, const void* ehs, int ehs_len,
+                       const void* add_text, const float* add_time_ids, const void* image_embeds, int n_img,
+                       const float* timestep_cond, int cond_dim, void* out, int B, int H, int W, void* stream);
 /* Attach an IP-Adapter created for this UNet's configuration (NULL detaches: the forward is again exactly the plain
  * one).  One adapter per UNet; attaching it to another UNet detaches it from the first.  The scale (lambda of
  * set_ip_adapter_scale, default 1.0) belongs to the UNet; 0 computes the text attention alone. */
@@ -305,6 +320,20 @@ int sd_cfg_rescale_linear_step(const void* noise_pred_2b, void* latents, float* 
                                float guidance_scale, float guidance_rescale, float c_x, float c_eps, float c_hist,
                                float h_x, float h_eps, float* factors_out, void* stream);
 
+/* One step of a scheduler that adds noise (LCMScheduler.step; schedulers.py `fused_plan`), one launch:
+ *   m   = model_out[i]                                   (rows == 1)
+ *   m   = fp16(u + g (t - u)), u = out[i], t = out[n+i]  (rows == 2: [uncond ; text], rounded as sd_cfg_linear_step does)
+ *   den = d_x x + d_out m;   denoised[i] = fp16(den)     (denoised nullable)
+ *   latents[i] = fp16(p_den den + p_noise noise[i])      (noise nullable: the term is absent, p_noise must be 0)
+ * x = latents[i]; all tensors f16, n elements (model_out: rows * n).  den and the update are evaluated in fp64 from the
+ * f32 coefficients: d_x x and d_out m cancel (|d| ~ 15 on the first of four steps) and f16 resolves 6e-8 around zero,
+ * finer than an fp32 evaluation of the two products (the host scheduler.step computes in fp32: the device step is the
+ * more exact of the two).  What the fp64 arithmetic costs next to the four f16 streams: DESIGN.md section 4.
+ * 16-byte accesses when n % 8 == 0 and every pointer is 16-byte aligned, a scalar kernel otherwise.
+ * SD_ERR_INVALID: rows not 1 or 2, n <= 0, null model_out / latents, a null noise with p_noise != 0. */
+int sd_lcm_step(const void* model_out, int rows, void* latents, const void* noise, void* denoised, int64_t n,
+                float guidance_scale, float d_x, float d_out, float p_den, float p_noise, void* stream);
+
 /* Inpainting with a 4-channel UNet, after every scheduler step (sd_unified_pipeline.py:492-506):
  *   latents <- m latents + (1 - m) (a image_latents + b noise),  m = mask [B,1,H,W] f16 over channels;
  * (a, b) = scheduler.add_noise coefficients at the NEXT timestep, or noise = NULL on the last step. */
@@ -460,6 +489,12 @@ int sd_bench_groupnorm(const void* x_nhwc, const void* gamma, const void* beta, 
  * (flip_sin_to_cos = 1) or [sin | cos], f_i = exp(-ln(1e4) i / (dim/2 - freq_shift)).  t, out: f32 device. */
 int sd_op_timestep_sinusoid(const float* t, float* out, int count, int dim, int flip_sin_to_cos, float freq_shift,
                             void* stream);
+/* The input of a guidance-embedded UNet's time embedding (TimestepEmbedding with cond_proj_dim), one launch:
+ *   out[b, j] = sinusoid(t_b)[j] + sum_k W[j, k] cond[b, k]
+ * t [B], cond [B, cond_dim], out [B, dim] f32; w_f16 [dim, cond_dim] f16 row-major (no bias); fp32 accumulation, the sum
+ * added last: cond = 0 gives sd_op_timestep_sinusoid's bits.  dim even, 1 <= cond_dim <= 1024 (SD_ERR_INVALID). */
+int sd_op_timestep_cond_embedding(const float* t, const float* cond, const void* w_f16, float* out, int B, int dim,
+                                  int cond_dim, int flip_sin_to_cos, float freq_shift, void* stream);
 /* The small-batch linear of the time-embedding MLPs (TimestepEmbedding.linear_1 / linear_2, time_emb_proj):
  * y[b, n] = act_out(bias[n] + sum_k act_in(x[b, k]) * W[n, k]), act = SiLU when the flag is set.  x, bias, y f32,
  * W f16 row-major [n_out, k]. */

@@ -35,6 +35,7 @@ class SdUNetConfig(C.Structure):
         ("freq_shift", C.c_float),
         ("addition_time_embed_dim", C.c_int32),
         ("projection_class_embeddings_input_dim", C.c_int32),
+        ("time_cond_proj_dim", C.c_int32),
     ]
 
 
@@ -94,6 +95,7 @@ SIGNATURES = {
     "sd_unet_text_kv_cache": (_I, [_P, _I]),
     "sd_unet_memory": (_I, [_P, C.POINTER(_I64), C.POINTER(_I64)]),
     "sd_unet_forward_ex": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _I, _P, _I, _I, _I, _P]),
+    "sd_unet_forward_tc": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _I, _P, _I, _P, _I, _I, _I, _P]),
     "sd_unet_forward_cfg": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _I, _F, _I, _P, _I, _I, _I, _P]),
     "sd_unet_cfg_share": (_I, [C.POINTER(SdUNetConfig)]),
     "sd_unet_set_ip_adapter": (_I, [_P, _P]),
@@ -139,6 +141,7 @@ SIGNATURES = {
     "sd_images_to_uint8": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "sd_cfg_linear_step": (_I, [_P, _P, _P, _I64, _F, _F, _F, _F, _F, _F, _P]),
     "sd_cfg_rescale_linear_step": (_I, [_P, _P, _P, _I, _I64, _F, _F, _F, _F, _F, _F, _F, _P, _P]),
+    "sd_lcm_step": (_I, [_P, _I, _P, _P, _P, _I64, _F, _F, _F, _F, _F, _P]),
     "sd_igemm_force": (_I, [_I, _I]),
     "sd_igemm_plan": (_I, [C.POINTER(_I), C.POINTER(_I), C.POINTER(_I64), C.c_char_p]),
     "sd_probe_mfma": (_I, [_I, C.POINTER(_F), _P]),
@@ -163,6 +166,7 @@ SIGNATURES = {
     "sd_op_groupnorm_concat": (_I, [_P, _I, _I, _P, _P, _P, _I, _I, _I, _F, _I, _P]),
     "sd_bench_groupnorm": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _I, C.POINTER(_F), _P]),
     "sd_op_timestep_sinusoid": (_I, [_P, _P, _I, _I, _I, _F, _P]),
+    "sd_op_timestep_cond_embedding": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _F, _P]),
     "sd_op_small_linear": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "sd_op_freeu": (_I, [_P, _I, _I, _I, _I, _I, _F, _F, _P]),
     "sd_op_layernorm": (_I, [_P, _P, _P, _P, _I, _I, _F, _P]),

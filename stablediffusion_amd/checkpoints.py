@@ -55,7 +55,8 @@ def unet_config_from_json(d: dict) -> UNetConfig:
         flip_sin_to_cos=d.get("flip_sin_to_cos", True), freq_shift=d.get("freq_shift", 0),
         addition_embed_type=d.get("addition_embed_type"),
         addition_time_embed_dim=d.get("addition_time_embed_dim"),
-        projection_class_embeddings_input_dim=d.get("projection_class_embeddings_input_dim"))
+        projection_class_embeddings_input_dim=d.get("projection_class_embeddings_input_dim"),
+        time_cond_proj_dim=d.get("time_cond_proj_dim"))
 
 
 def vae_config_from_json(d: dict) -> VAEConfig:
@@ -89,7 +90,7 @@ def load_diffusers_folder(root: str) -> Tuple[UNetConfig, Dict[str, torch.Tensor
 
 
 SCHEDULER_FIELDS = ("num_train_timesteps", "beta_start", "beta_end", "steps_offset", "timestep_spacing",
-                    "prediction_type", "rescale_betas_zero_snr")
+                    "prediction_type", "rescale_betas_zero_snr", "original_inference_steps", "timestep_scaling")
 
 
 def read_scheduler_config(folder: str) -> dict:

@@ -37,6 +37,9 @@ class UNetConfig:
     addition_embed_type: Optional[str] = None
     addition_time_embed_dim: Optional[int] = None
     projection_class_embeddings_input_dim: Optional[int] = None
+    # guidance-embedded UNets (Latent Consistency Models): width of `timestep_cond`, projected by
+    # time_embedding.cond_proj onto the sinusoid (diffusers TimestepEmbedding cond_proj_dim); LCM checkpoints: 256
+    time_cond_proj_dim: Optional[int] = None
 
     @property
     def time_embed_dim(self) -> int:
@@ -137,7 +140,7 @@ def sdxl_vae() -> VAEConfig:
     return VAEConfig(scaling_factor=0.13025, force_upcast=True, sample_size=1024)
 
 
-def tiny_unet(linear: bool = False, sdxl_cond: bool = False) -> UNetConfig:
+def tiny_unet(linear: bool = False, sdxl_cond: bool = False, time_cond: int = 0) -> UNetConfig:
     """Width-reduced UNet with the SD1.5 topology; used for golden fixtures and fast parity tests."""
     kw = dict(
         sample_size=16,
@@ -149,6 +152,8 @@ def tiny_unet(linear: bool = False, sdxl_cond: bool = False) -> UNetConfig:
     if sdxl_cond:
         kw.update(addition_embed_type="text_time", addition_time_embed_dim=32,
                   projection_class_embeddings_input_dim=6 * 32 + 64)
+    if time_cond:
+        kw.update(time_cond_proj_dim=time_cond)
     return UNetConfig(**kw)
 
 

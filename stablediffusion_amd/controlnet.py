@@ -42,6 +42,7 @@ def _up_types(down):
 def encoder_config(cfg: UNetConfig, **changes) -> UNetConfig:
     """A ControlNet configuration for a UNet configuration (same encoder; `changes` override fields)."""
     d = cfg.to_dict()
+    d["time_cond_proj_dim"] = None          # ControlNetModel has no cond_proj (and the engine's never declares one)
     d.update(changes)
     d["up_block_types"] = _up_types(d["down_block_types"])
     d["out_channels"] = d.get("out_channels", 4)

@@ -105,6 +105,10 @@ int sd_unet_create(const sd_unet_config* cfg, sd_unet** out) {
                   "addition_time_embed_dim and projection_class_embeddings_input_dim % 64 == 0 and > 6 x it)");
         return SD_ERR_UNSUPPORTED;
     }
+    if (cfg->time_cond_proj_dim < 0 || cfg->time_cond_proj_dim > 1024) {
+        set_error("sd_unet_create: time_cond_proj_dim must be in [0, 1024] (0: no time_embedding.cond_proj)");
+        return SD_ERR_INVALID;
+    }
     *out = new (std::nothrow) sd_unet(*cfg);
     if (!*out) { set_error("out of host memory"); return SD_ERR_INVALID; }
     return SD_OK;
@@ -154,6 +158,24 @@ int sd_unet_forward_ex(sd_unet* u, const void* sample, const float* timesteps, c
                            ehs_len, static_cast<const half_t*>(add_text), add_time_ids,
                            static_cast<half_t*>(out), B, H, W, static_cast<hipStream_t>(stream),
                            static_cast<const half_t*>(image_embeds), image_embeds ? n_img : 0);
+}
+int sd_unet_forward_tc(sd_unet* u, const void* sample, const float* timesteps, const void* ehs, int ehs_len,
+                       const void* add_text, const float* add_time_ids, const void* image_embeds, int n_img,
+                       const float* timestep_cond, int cond_dim, void* out, int B, int H, int W, void* stream) {
+    if (!u || !sample || !timesteps || !ehs || !out) { set_error("null argument"); return SD_ERR_INVALID; }
+    if (timestep_cond) {
+        const int want = u->impl.cfg.time_cond_proj_dim;
+        if (want <= 0) { set_error("sd_unet_forward_tc: timestep_cond given but the UNet has no time_cond_proj_dim"); return SD_ERR_INVALID; }
+        if (cond_dim != want) {
+            set_error("sd_unet_forward_tc: cond_dim " + std::to_string(cond_dim) + " != time_cond_proj_dim " + std::to_string(want));
+            return SD_ERR_INVALID;
+        }
+    }
+    return u->impl.forward(static_cast<const half_t*>(sample), timesteps, static_cast<const half_t*>(ehs),
+                           ehs_len, static_cast<const half_t*>(add_text), add_time_ids,
+                           static_cast<half_t*>(out), B, H, W, static_cast<hipStream_t>(stream),
+                           static_cast<const half_t*>(image_embeds), image_embeds ? n_img : 0, nullptr, 0, 0.f, nullptr,
+                           timestep_cond);
 }
 int sd_unet_set_ip_adapter(sd_unet* u, sd_ip_adapter* a) {
     if (!u) { set_error("null handle"); return SD_ERR_INVALID; }
@@ -263,6 +285,7 @@ int sd_controlnet_create(const sd_unet* u, const sd_unet_config* cn_cfg, int con
     // (only the encoder half of the configuration is read: make the up-path fields consistent for bad_cfg)
     sd_unet_config c = *cn_cfg;
     for (int i = 0; i < SD_MAX_BLOCKS; ++i) c.up_block_has_attn[i] = 0;
+    c.time_cond_proj_dim = 0;            // (ControlNetModel has no cond_proj; the UNet rejects timestep_cond with one attached)
     if (bad_cfg(&c)) { set_error("sd_controlnet_create: unsupported encoder configuration"); return SD_ERR_UNSUPPORTED; }
     std::string why;
     if (!controlnet_fits(u->impl.cfg, c, &why)) { set_error("sd_controlnet_create: " + why); return SD_ERR_INVALID; }
@@ -416,6 +439,17 @@ int sd_cfg_rescale_linear_step(const void* noise_pred_2b, void* latents, float* 
     return launch_cfg_rescale_linear(static_cast<const half_t*>(noise_pred_2b), static_cast<half_t*>(latents), hist_f32, B,
                                      (long)n_per_sample, guidance_scale, guidance_rescale, c_x, c_eps, c_hist, h_x, h_eps,
                                      factors_out, static_cast<hipStream_t>(stream));
+}
+int sd_lcm_step(const void* model_out, int rows, void* latents, const void* noise, void* denoised, int64_t n,
+                float guidance_scale, float d_x, float d_out, float p_den, float p_noise, void* stream) {
+    if (!model_out || !latents || (rows != 1 && rows != 2) || n <= 0) {
+        set_error("sd_lcm_step: bad arguments (non-null model_out / latents, rows 1 or 2, n > 0)");
+        return SD_ERR_INVALID;
+    }
+    if (!noise && p_noise != 0.f) { set_error("sd_lcm_step: p_noise != 0 needs a noise tensor"); return SD_ERR_INVALID; }
+    return launch_lcm_step(static_cast<const half_t*>(model_out), rows, static_cast<half_t*>(latents),
+                           static_cast<const half_t*>(noise), static_cast<half_t*>(denoised), (long)n, guidance_scale, d_x,
+                           d_out, p_den, p_noise, static_cast<hipStream_t>(stream));
 }
 int sd_images_to_uint8(const void* images_nchw_f16, void* out_nhwc_u8, int B, int C, int H, int W, void* stream) {
     if (!images_nchw_f16 || !out_nhwc_u8 || B < 0 || C < 1 || C > 4 || H < 1 || W < 1) {
@@ -1108,6 +1142,16 @@ int sd_op_timestep_sinusoid(const float* t, float* out, int count, int dim, int 
                             void* stream) {
     if (!t || !out || count < 1 || dim < 2 || (dim & 1)) { set_error("sd_op_timestep_sinusoid: bad arguments"); return SD_ERR_INVALID; }
     return launch_timestep_sinusoid(t, 1, out, count, dim, flip_sin_to_cos, freq_shift, dim, static_cast<hipStream_t>(stream));
+}
+
+int sd_op_timestep_cond_embedding(const float* t, const float* cond, const void* w_f16, float* out, int B, int dim,
+                                  int cond_dim, int flip_sin_to_cos, float freq_shift, void* stream) {
+    if (!t || !cond || !w_f16 || !out || B < 1 || dim < 2 || (dim & 1) || cond_dim < 1 || cond_dim > 1024) {
+        set_error("sd_op_timestep_cond_embedding: bad arguments (even dim, cond_dim in [1, 1024])");
+        return SD_ERR_INVALID;
+    }
+    return launch_timestep_cond(t, cond, static_cast<const half_t*>(w_f16), cond_dim, out, B, dim, cond_dim, flip_sin_to_cos,
+                                freq_shift, static_cast<hipStream_t>(stream));
 }
 
 int sd_op_small_linear(const float* x, const void* w_f16, const float* bias, float* y, int B, int K, int n_out, int silu_in,

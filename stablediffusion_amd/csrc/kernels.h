@@ -255,6 +255,10 @@ int launch_freeu(half_t* x, long ld, int N, int H, int W, int C1, int C2, float 
 // out[b, :] = [cos(t_b f_i) | sin(t_b f_i)] (flip) or [sin | cos]; f_i = exp(-ln(1e4) i/(half-shift))
 int launch_timestep_sinusoid(const float* t, int t_stride, float* out, int count, int dim, int flip, float shift,
                              long out_ld, hipStream_t s);
+// out[b, j] = sinusoid(t_b)[j] + sum_k w[j, k] cond[b, k]: launch_timestep_sinusoid (t_stride 1, out_ld dim) with the
+// cond_proj of a guidance-embedded UNet added, one launch.  w [dim rows][ldw] f16, cond [count, cond_dim] f32.
+int launch_timestep_cond(const float* t, const float* cond, const half_t* w, long ldw, float* out, int count, int dim,
+                         int cond_dim, int flip, float shift, hipStream_t s);
 // y[b, n] = bias[n] + sum_k act(x[b, k]) * W[n, k]  for small b (time-embedding MLPs); fp32 in/out.
 int launch_small_linear(const float* x, long ldx, const half_t* w, const float* bias, float* y,
                         long ldy, int B, int K, int Nout, int silu_in, int silu_out, hipStream_t s);
@@ -335,6 +339,10 @@ int launch_cfg_linear(const half_t* eps2b, half_t* lat, float* hist, long n, flo
                       float hx, float he, hipStream_t s);
 int launch_cfg_ddim(const half_t* eps2b, half_t* lat, long n, float g, float cx, float ce,
                     hipStream_t s);
+// den = dx x + dout m, x <- pden den + pnoise noise (m: model_out, or its CFG combine when rows == 2); noise / denoised
+// nullable.  The scheduler step of LCMScheduler in one launch.
+int launch_lcm_step(const half_t* model_out, int rows, half_t* lat, const half_t* noise, half_t* denoised, long n, float g,
+                    float dx, float dout, float pden, float pnoise, hipStream_t s);
 // launch_cfg_linear on k_b * eps, k_b = 1 + phi (std(text_b) / std(eps_b) - 1) per sample b of n elements (guidance
 // rescale): a statistics launch and an update launch; factors [B] (nullable) receives k_b
 int launch_cfg_rescale_linear(const half_t* eps2b, half_t* lat, float* hist, int B, long n, float g, float phi, float cx,

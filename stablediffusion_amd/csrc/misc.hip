@@ -28,6 +28,61 @@ __global__ void sinusoid_kernel(const float* __restrict__ t, int t_stride, float
     if (flip) { o[f] = cs; o[half + f] = sn; } else { o[f] = sn; o[half + f] = cs; }
 }
 
+// The input of a guidance-embedded UNet's time embedding (diffusers TimestepEmbedding with cond_proj_dim, LCM):
+//   out[b, j] = sinusoid(t_b)[j] + sum_k W[j, k] cond[b, k]
+// in the place of sinusoid_kernel's launch.  One wave per (b, f): it owns the output pair (f, half + f) like a thread of
+// sinusoid_kernel does, so the sinusoid is that kernel's expression instruction for instruction, and the two dot
+// products (fp16 weights, fp32 accumulation, lanes over k, butterfly reduction) are added to it last: cond = 0 leaves the
+// sinusoid's bits.  w rows are ldw halves apart (the packed K of WeightStore::pack_conv, zero padded; cond_dim itself for
+// a raw matrix); VEC: ldw % 8 == 0 and a 16-byte aligned base, 16-byte weight loads.  A few hundred KB of weights: the
+// launch costs what the sinusoid's did.
+template <bool VEC>
+__global__ __launch_bounds__(256) void temb_cond_kernel(const float* __restrict__ t, const float* __restrict__ cond,
+                                                        const half_t* __restrict__ w, long ldw, float* __restrict__ out,
+                                                        int count, int dim, int cond_dim, int flip, float shift) {
+    const int half = dim >> 1;
+    const int lane = threadIdx.x & 63;
+    const int i = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);      // wave-uniform
+    if (i >= count * half) return;
+    const int b = i / half, f = i - b * half;
+    const int r0 = flip ? half + f : f, r1 = flip ? f : half + f;            // rows of the sin and of the cos output
+    const half_t* w0 = w + (long)r0 * ldw;
+    const half_t* w1 = w + (long)r1 * ldw;
+    const float* c = cond + (long)b * cond_dim;
+    float a0 = 0.f, a1 = 0.f;
+    if (VEC) {
+        for (int k = lane * 8; k < cond_dim; k += 64 * 8) {
+            const h8 v0 = *reinterpret_cast<const h8*>(w0 + k);
+            const h8 v1 = *reinterpret_cast<const h8*>(w1 + k);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const float ce = k + e < cond_dim ? c[k + e] : 0.f;
+                a0 = __builtin_fmaf((float)v0[e], ce, a0);
+                a1 = __builtin_fmaf((float)v1[e], ce, a1);
+            }
+        }
+    } else {
+        for (int k = lane; k < cond_dim; k += 64) {
+            const float ce = c[k];
+            a0 = __builtin_fmaf((float)w0[k], ce, a0);
+            a1 = __builtin_fmaf((float)w1[k], ce, a1);
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        a0 += __shfl_xor(a0, off);
+        a1 += __shfl_xor(a1, off);
+    }
+    if (lane != 0) return;
+    const float freq = __expf(-9.210340371976184f * (float)f / ((float)half - shift));
+    const float ang = t[b] * freq;
+    float sn, cs;
+    sincosf(ang, &sn, &cs);
+    float* o = out + (long)b * dim;
+    o[r0] = sn + a0;
+    o[r1] = cs + a1;
+}
+
 // y[b, n] = bias[n] + sum_k act(x[b,k]) W[n,k] for a handful of rows b (time-embedding MLPs).
 // Weight-bandwidth bound (the stacked time_emb_proj matrix is 67 MB): one wave owns SL_COLS output
 // columns so it keeps SL_COLS independent 16-byte weight loads in flight per lane; the activation
@@ -273,6 +328,55 @@ __global__ void cfg_linear_kernel(const half_t* __restrict__ eps2b, half_t* __re
         hist[i] = hx * x + he * e;
     }
     lat[i] = (half_t)out;
+}
+
+// One step of a scheduler that adds noise (LCMScheduler.step), the guidance combine included:
+//   m = model_out (ROWS == 1) or fp16(u + g (t - u)) (ROWS == 2, cfg_linear_kernel's rounding: one fma, then fp16)
+//   den = dx x + dout m;  denoised <- fp16(den);  x <- fp16(pden den + pnoise noise)
+// den and the update are evaluated in fp64: dx x and dout m cancel (|dx|, |dout| ~ 15 on the first of four steps, the
+// result O(1) and often near 0) and fp16 resolves 2^-24 around zero, so the 4e-7 an fp32 evaluation of the two products
+// is off by there would be several fp16 ulps.  A dozen fp64 FMAs per element next to four or five fp16 streams; the
+// kernel's time next to the fp32 step kernel of the same traffic is in DESIGN.md section 4.
+// VEC: n % 8 == 0 and 16-byte aligned bases.
+template <int ROWS>
+__device__ __forceinline__ void lcm_element(float eu, float et, float xf, float nz, float g, double dx, double dout,
+                                            double pden, double pnoise, half_t* den16, half_t* x16) {
+    const float m = ROWS == 2 ? (float)(half_t)__builtin_fmaf(g, et - eu, eu) : eu;
+    const double den = __builtin_fma(dx, (double)xf, dout * (double)m);
+    *den16 = (half_t)den;
+    *x16 = (half_t)__builtin_fma(pden, den, pnoise * (double)nz);
+}
+template <int ROWS, bool VEC>
+__global__ __launch_bounds__(256) void lcm_step_kernel(const half_t* __restrict__ mo, half_t* __restrict__ lat,
+                                                       const half_t* __restrict__ noise, half_t* __restrict__ denoised,
+                                                       long n, float g, float dx, float dout, float pden, float pnoise) {
+    if (VEC) {
+        const long i = ((long)blockIdx.x * 256 + threadIdx.x) * 8;
+        if (i >= n) return;
+        const h8 vu = *reinterpret_cast<const h8*>(mo + i);
+        h8 vt = vu, vn = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (ROWS == 2) vt = *reinterpret_cast<const h8*>(mo + n + i);
+        const h8 vx = *reinterpret_cast<const h8*>(lat + i);
+        if (noise) vn = *reinterpret_cast<const h8*>(noise + i);
+        h8 od, ox;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            half_t d, x;
+            lcm_element<ROWS>((float)vu[j], (float)vt[j], (float)vx[j], (float)vn[j], g, dx, dout, pden, pnoise, &d, &x);
+            od[j] = d;
+            ox[j] = x;
+        }
+        *reinterpret_cast<h8*>(lat + i) = ox;
+        if (denoised) *reinterpret_cast<h8*>(denoised + i) = od;
+    } else {
+        const long i = (long)blockIdx.x * 256 + threadIdx.x;
+        if (i >= n) return;
+        half_t d, x;
+        lcm_element<ROWS>((float)mo[i], ROWS == 2 ? (float)mo[n + i] : 0.f, (float)lat[i], noise ? (float)noise[i] : 0.f, g,
+                          dx, dout, pden, pnoise, &d, &x);
+        lat[i] = x;
+        if (denoised) denoised[i] = d;
+    }
 }
 
 // ---- guidance rescale (Lin et al. 2023, section 3.4; diffusers rescale_noise_cfg) in front of the same linear update ----
@@ -631,6 +735,20 @@ int launch_timestep_sinusoid(const float* t, int t_stride, float* out, int count
     return 0;
 }
 
+int launch_timestep_cond(const float* t, const float* cond, const half_t* w, long ldw, float* out, int count, int dim,
+                         int cond_dim, int flip, float shift, hipStream_t s) {
+    const long waves = (long)count * (dim / 2);
+    if (waves <= 0) return 0;
+    const bool vec = ldw % 8 == 0 && (reinterpret_cast<uintptr_t>(w) & 15) == 0;
+    const dim3 grid((unsigned)((waves + 3) / 4));
+    if (vec)
+        hipLaunchKernelGGL(temb_cond_kernel<true>, grid, dim3(256), 0, s, t, cond, w, ldw, out, count, dim, cond_dim, flip, shift);
+    else
+        hipLaunchKernelGGL(temb_cond_kernel<false>, grid, dim3(256), 0, s, t, cond, w, ldw, out, count, dim, cond_dim, flip, shift);
+    SD_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
 // The same operator on the matrix cores, for the shapes of the time-embedding path (B <= 16 rows, K <= 1280):
 // small_linear_kernel re-reads the activation rows through L1 once per wave and column group -- four times the bytes
 // of the weights it streams -- and reduces every output over the 64 lanes with shuffles: 26 us per launch on average,
@@ -837,6 +955,19 @@ int launch_cfg_ddim(const half_t* eps2b, half_t* lat, long n, float g, float cx,
 int launch_cfg_linear(const half_t* eps2b, half_t* lat, float* hist, long n, float g, float cx, float ce, float ch,
                       float hx, float he, hipStream_t s) {
     hipLaunchKernelGGL(cfg_linear_kernel, grid1d(n), dim3(256), 0, s, eps2b, lat, hist, n, g, cx, ce, ch, hx, he);
+    SD_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+int launch_lcm_step(const half_t* model_out, int rows, half_t* lat, const half_t* noise, half_t* denoised, long n, float g,
+                    float dx, float dout, float pden, float pnoise, hipStream_t s) {
+    const bool vec = n % 8 == 0 && ((reinterpret_cast<uintptr_t>(model_out) | reinterpret_cast<uintptr_t>(lat) |
+                                     reinterpret_cast<uintptr_t>(noise) | reinterpret_cast<uintptr_t>(denoised)) & 15) == 0;
+    const dim3 grid = grid1d(vec ? n / 8 : n);
+#define SD_LCM_LAUNCH(R, V) \
+    hipLaunchKernelGGL((lcm_step_kernel<R, V>), grid, dim3(256), 0, s, model_out, lat, noise, denoised, n, g, dx, dout, pden, pnoise)
+    if (rows == 2) { if (vec) SD_LCM_LAUNCH(2, true); else SD_LCM_LAUNCH(2, false); }
+    else { if (vec) SD_LCM_LAUNCH(1, true); else SD_LCM_LAUNCH(1, false); }
+#undef SD_LCM_LAUNCH
     SD_HIP_CHECK(hipGetLastError());
     return 0;
 }

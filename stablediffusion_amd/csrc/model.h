@@ -92,6 +92,7 @@ struct Encoder {
     sd_unet_config cfg;
     WeightStore ws;
     ConvW conv_in, te1, te2, ae1, ae2, temb_stack;
+    ConvW tcp;                          // time_embedding.cond_proj (time_cond_proj_dim > 0: guidance-embedded UNets), no bias
     ConvW kv_all;                       // every attn2.to_k / to_v of the model, row-concatenated
     std::vector<std::string> kv_keys;   // (finalize only)
     std::vector<std::vector<Resnet>> down_res;
@@ -116,8 +117,9 @@ struct Encoder {
     int pack_xformer(const std::string& p, Xformer* x, int heads, int depth);
     // time (+ text_time) embedding -> every resnet's time_emb_proj(silu(emb)) in one GEMV: [B, temb_total] fp32
     // (rows_alloc > B: the buffer is sized for that many rows, the first B are written)
+    // tcond [B, time_cond_proj_dim] fp32 (or nullptr): cond_proj(tcond) is added to the sinusoid, in its launch
     int run_temb(Ctx& c, const float* timesteps, const half_t* add_text, const float* add_time_ids, int B, float** tproj,
-                 int rows_alloc = 0);
+                 int rows_alloc = 0, const float* tcond = nullptr);
     // conv_in into y0: straight from the NCHW latents when the edge kernel takes it and there is no residual, else
     // im2col + GEMM with `res` added in its epilogue.  *xs = the GroupNorm summaries of y0 it left (or nullptr).
     void run_conv_in(Ctx& c, const half_t* sample, int B, int H, int W, View y0, GnStatBuf* gb, const View* res,
@@ -183,7 +185,8 @@ struct UNet : Encoder {
     int forward(const half_t* sample, const float* timesteps, const half_t* ehs, int L,
                 const half_t* add_text, const float* add_time_ids, half_t* out, int B, int H, int W,
                 hipStream_t stream, const half_t* image_embeds = nullptr, int n_img = 0,
-                const half_t* control = nullptr, int n_ctrl = 0, float cn_scale = 0.f, const CfgIn* cfg_in = nullptr);
+                const half_t* control = nullptr, int n_ctrl = 0, float cn_scale = 0.f, const CfgIn* cfg_in = nullptr,
+                const float* tcond = nullptr);
     void set_ip_adapter(IPAdapter* a);
     void set_controlnet(ControlNet* n);
 
@@ -205,7 +208,8 @@ struct UNet : Encoder {
     char* io_slab = nullptr;
     size_t io_cap = 0;
     int forward_graph(const half_t* sample, const float* timesteps, const half_t* ehs, int L, const half_t* add_text,
-                      const float* add_time_ids, half_t* out, int B, int H, int W, hipStream_t stream);
+                      const float* add_time_ids, half_t* out, int B, int H, int W, hipStream_t stream,
+                      const float* tcond = nullptr);
     ~UNet();
 
     // ---- text K/V kept across the forwards of one denoise loop (sd_unet_text_kv_cache) ----
@@ -260,7 +264,7 @@ struct UNet : Encoder {
     int run(Ctx& c, const half_t* sample, const float* timesteps, const half_t* ehs, int L,
             const half_t* add_text, const float* add_time_ids, half_t* out, int B, int H, int W,
             const half_t* image_embeds = nullptr, int n_img = 0, const half_t* control = nullptr, int n_ctrl = 0,
-            float cn_scale = 0.f, const CfgIn* cfg_in = nullptr);
+            float cn_scale = 0.f, const CfgIn* cfg_in = nullptr, const float* tcond = nullptr);
     // ControlNet step of run(): its hidden tensors into sites / mid (allocated by the caller)
     int run_controlnet(Ctx& c, const half_t* sample, const float* timesteps, const half_t* ehs, int L,
                        const half_t* add_text, const float* add_time_ids, int B, int H, int W, const half_t* control,

@@ -82,6 +82,7 @@ void Encoder::declare_encoder() {
     ws.declare("time_embedding.linear_1.bias", {temb});
     ws.declare("time_embedding.linear_2.weight", {temb, temb});
     ws.declare("time_embedding.linear_2.bias", {temb});
+    if (cfg.time_cond_proj_dim > 0) ws.declare("time_embedding.cond_proj.weight", {boc[0], cfg.time_cond_proj_dim});
     if (cfg.addition_time_embed_dim > 0) {
         ws.declare("add_embedding.linear_1.weight", {temb, cfg.projection_class_embeddings_input_dim});
         ws.declare("add_embedding.linear_1.bias", {temb});
@@ -215,6 +216,7 @@ int Encoder::pack_encoder(std::vector<std::string>* tw, std::vector<std::string>
     if ((rc = ws.pack_conv("conv_in", &conv_in))) return rc;
     if ((rc = ws.pack_conv("time_embedding.linear_1", &te1))) return rc;
     if ((rc = ws.pack_conv("time_embedding.linear_2", &te2))) return rc;
+    if (cfg.time_cond_proj_dim > 0 && (rc = ws.pack_conv("time_embedding.cond_proj", &tcp, false))) return rc;
     if (cfg.addition_time_embed_dim > 0) {
         if ((rc = ws.pack_conv("add_embedding.linear_1", &ae1))) return rc;
         if ((rc = ws.pack_conv("add_embedding.linear_2", &ae2))) return rc;
@@ -489,7 +491,7 @@ void run_xformer(Ctx& c, const Xformer& t, View x, int N, int H, int W, View out
 
 // ----------------------------------------------------------------------------------------- forward
 int Encoder::run_temb(Ctx& c, const float* timesteps, const half_t* add_text, const float* add_time_ids, int B,
-                      float** tproj_out, int rows_alloc) {
+                      float** tproj_out, int rows_alloc, const float* tcond) {
     Arena& a = *c.arena;
     const int* boc = cfg.block_out_channels;
     const int temb = boc[0] * 4;
@@ -501,7 +503,11 @@ int Encoder::run_temb(Ctx& c, const float* timesteps, const half_t* add_text, co
     float* emb = a.alloc_f((long)B * temb);
     float* tproj = a.alloc_f((long)std::max(B, rows_alloc) * temb_total);
     *tproj_out = tproj;
-    if (go && !c.err) c.err = launch_timestep_sinusoid(timesteps, 1, sinus, B, boc[0], cfg.flip_sin_to_cos, cfg.freq_shift, boc[0], s);
+    // (a guidance-embedded UNet: sinusoid + cond_proj(timestep_cond) from one launch in the sinusoid's place)
+    if (go && !c.err)
+        c.err = tcond ? launch_timestep_cond(timesteps, tcond, tcp.w, tcp.K, sinus, B, boc[0], cfg.time_cond_proj_dim,
+                                             cfg.flip_sin_to_cos, cfg.freq_shift, s)
+                      : launch_timestep_sinusoid(timesteps, 1, sinus, B, boc[0], cfg.flip_sin_to_cos, cfg.freq_shift, boc[0], s);
     if (go && !c.err) c.err = launch_small_linear(sinus, boc[0], te1.w, te1.bias, e1, temb, B, boc[0], temb, 0, 1, s);
     // (without text_time conditioning the SiLU every resnet applies to the embedding rides on this launch)
     const bool aug_path = cfg.addition_time_embed_dim > 0;
@@ -638,7 +644,8 @@ int Encoder::num_skips() const { return 1 + cfg.num_blocks * cfg.layers_per_bloc
 
 int UNet::run(Ctx& c, const half_t* sample, const float* timesteps, const half_t* ehs, int L,
               const half_t* add_text, const float* add_time_ids, half_t* out, int B, int H, int W,
-              const half_t* image_embeds, int n_img, const half_t* control, int n_ctrl, float cn_scale, const CfgIn* cfg_in) {
+              const half_t* image_embeds, int n_img, const half_t* control, int n_ctrl, float cn_scale, const CfgIn* cfg_in,
+              const float* tcond) {
     Arena& a = *c.arena;
     const int nb = cfg.num_blocks;
     const int* boc = cfg.block_out_channels;
@@ -663,7 +670,7 @@ int UNet::run(Ctx& c, const half_t* sample, const float* timesteps, const half_t
     }
 
     float* tproj = nullptr;
-    if (int rc = run_temb(c, timesteps, add_text, add_time_ids, Bp, &tproj, B)) return rc;
+    if (int rc = run_temb(c, timesteps, add_text, add_time_ids, Bp, &tproj, B, tcond)) return rc;
     if (cfg_in) {
         RowDupSeg g;
         g.src = tproj; g.dst = tproj + (long)Bp * temb_total;
@@ -991,14 +998,15 @@ UNet::~UNet() {
 // stream by two events.
 int UNet::forward_graph(const half_t* sample, const float* timesteps, const half_t* ehs, int L,
                         const half_t* add_text, const float* add_time_ids, half_t* out, int B, int H, int W,
-                        hipStream_t stream) {
+                        hipStream_t stream, const float* tcond) {
     const bool sdxl = cfg.addition_time_embed_dim > 0;
     const int pdim = sdxl ? cfg.projection_class_embeddings_input_dim - 6 * cfg.addition_time_embed_dim : 0;
     auto up = [](size_t v) { return (v + 255) & ~size_t(255); };
     const size_t n_sample = up((size_t)B * cfg.in_channels * H * W * 2), n_t = up((size_t)B * 4);
     const size_t n_ehs = up((size_t)B * L * cfg.cross_attention_dim * 2), n_text = up((size_t)B * pdim * 2);
     const size_t n_ids = up((size_t)B * 6 * 4), n_out = up((size_t)B * cfg.out_channels * H * W * 2);
-    const size_t need = n_sample + n_t + n_ehs + n_text + n_ids + n_out;
+    const size_t n_tc = tcond ? up((size_t)B * cfg.time_cond_proj_dim * 4) : 0;
+    const size_t need = n_sample + n_t + n_ehs + n_text + n_ids + n_tc + n_out;
     if (!gstream) {
         SD_HIP_CHECK(hipStreamCreateWithFlags(&gstream, hipStreamNonBlocking));
         SD_HIP_CHECK(hipEventCreateWithFlags(&ev_in, hipEventDisableTiming));
@@ -1017,6 +1025,7 @@ int UNet::forward_graph(const half_t* sample, const float* timesteps, const half
     half_t* g_ehs = reinterpret_cast<half_t*>(ptr); ptr += n_ehs;
     half_t* g_text = sdxl ? reinterpret_cast<half_t*>(ptr) : nullptr; ptr += n_text;
     float* g_ids = sdxl ? reinterpret_cast<float*>(ptr) : nullptr; ptr += n_ids;
+    float* g_tc = tcond ? reinterpret_cast<float*>(ptr) : nullptr; ptr += n_tc;
     half_t* g_out = reinterpret_cast<half_t*>(ptr);
     SD_HIP_CHECK(hipMemcpyAsync(g_sample, sample, (size_t)B * cfg.in_channels * H * W * 2, hipMemcpyDeviceToDevice, stream));
     SD_HIP_CHECK(hipMemcpyAsync(g_t, timesteps, (size_t)B * 4, hipMemcpyDeviceToDevice, stream));
@@ -1026,13 +1035,15 @@ int UNet::forward_graph(const half_t* sample, const float* timesteps, const half
         SD_HIP_CHECK(hipMemcpyAsync(g_text, add_text, (size_t)B * pdim * 2, hipMemcpyDeviceToDevice, stream));
         SD_HIP_CHECK(hipMemcpyAsync(g_ids, add_time_ids, (size_t)B * 6 * 4, hipMemcpyDeviceToDevice, stream));
     }
-    const long key = ((long)B << 40) ^ ((long)H << 20) ^ (long)W ^ ((long)L << 52);
+    if (tcond) SD_HIP_CHECK(hipMemcpyAsync(g_tc, tcond, (size_t)B * cfg.time_cond_proj_dim * 4, hipMemcpyDeviceToDevice, stream));
+    // (timestep_cond's width is the configuration's: its presence is what changes the captured launches)
+    const long key = ((long)B << 40) ^ ((long)H << 20) ^ (long)W ^ ((long)L << 52) ^ (tcond ? (1L << 62) : 0);
     int rc = 0;
     if (key != graph_key || !gexec) {
         // (re)plan + one eager run on the caller's stream: sets every kernel's LDS attribute (not
         // allowed while capturing) and produces this call's result
         graph_enabled = false;
-        rc = forward(g_sample, g_t, g_ehs, L, g_text, g_ids, g_out, B, H, W, stream);
+        rc = forward(g_sample, g_t, g_ehs, L, g_text, g_ids, g_out, B, H, W, stream, nullptr, 0, nullptr, 0, 0.f, nullptr, g_tc);
         graph_enabled = true;
         if (rc) return rc;
         if (gexec) { (void)hipGraphExecDestroy(gexec); gexec = nullptr; }
@@ -1040,7 +1051,7 @@ int UNet::forward_graph(const half_t* sample, const float* timesteps, const half
         SD_HIP_CHECK(hipStreamBeginCapture(gstream, hipStreamCaptureModeRelaxed));
         Ctx ctx{&arena, gstream, false};
         arena.begin(false);
-        rc = run(ctx, g_sample, g_t, g_ehs, L, g_text, g_ids, g_out, B, H, W);
+        rc = run(ctx, g_sample, g_t, g_ehs, L, g_text, g_ids, g_out, B, H, W, nullptr, 0, nullptr, 0, 0.f, nullptr, g_tc);
         hipError_t e = hipStreamEndCapture(gstream, &graph);
         if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
         if (e != hipSuccess) { set_error(std::string("hipStreamEndCapture: ") + hipGetErrorString(e)); return 3; }
@@ -1061,8 +1072,12 @@ int UNet::forward_graph(const half_t* sample, const float* timesteps, const half
 
 int UNet::forward(const half_t* sample, const float* timesteps, const half_t* ehs, int L, const half_t* add_text,
                   const float* add_time_ids, half_t* out, int B, int H, int W, hipStream_t stream,
-                  const half_t* image_embeds, int n_img, const half_t* control, int n_ctrl, float cn_scale, const CfgIn* cfg_in) {
+                  const half_t* image_embeds, int n_img, const half_t* control, int n_ctrl, float cn_scale, const CfgIn* cfg_in,
+                  const float* tcond) {
     if (!finalized) { set_error("unet: forward before finalize"); return 2; }
+    if (tcond && cfg.time_cond_proj_dim <= 0) { set_error("unet: timestep_cond given but the UNet has no time_cond_proj_dim"); return 1; }
+    if (tcond && cfg_in) { set_error("unet: timestep_cond with the shared CFG prefix (a guidance-embedded UNet runs without CFG)"); return 1; }
+    if (tcond && cn) { set_error("unet: timestep_cond with a ControlNet attached is not supported"); return 4; }
     if (cfg_in && (B % 2 != 0 || graph_enabled || control || !unet_cfg_share_eligible(cfg))) {
         set_error("unet: shared CFG prefix not available for this call");
         return 2;
@@ -1091,7 +1106,7 @@ int UNet::forward(const half_t* sample, const float* timesteps, const half_t* eh
     const bool use_cn = cn && cn_scale != 0.f;
     if (freeu_on && graph_enabled) { set_error("unet: graph replay with FreeU enabled is not supported"); return 4; }
     if (graph_enabled && !prof_enabled())
-        return forward_graph(sample, timesteps, ehs, L, add_text, add_time_ids, out, B, H, W, stream);
+        return forward_graph(sample, timesteps, ehs, L, add_text, add_time_ids, out, B, H, W, stream, tcond);
     if (kv_cache_on) {          // persistent buffer for the text K/V (outside the per-forward arena)
         const size_t need = (size_t)B * L * kv_total * sizeof(half_t);
         if (need > kv_cap) {
@@ -1139,7 +1154,7 @@ int UNet::forward(const half_t* sample, const float* timesteps, const half_t* eh
         Ctx dry{&arena, stream, true};
         arena.begin(true);
         int rc = run(dry, sample, timesteps, ehs, L, add_text, add_time_ids, out, B, H, W, image_embeds, n_img, control,
-                     n_ctrl, cn_scale, cfg_in);
+                     n_ctrl, cn_scale, cfg_in, tcond);
         if (rc) return rc;
         // growing the slab frees the old one: make sure nothing enqueued earlier still uses it
         if (arena.peak() > arena.capacity()) {
@@ -1153,7 +1168,7 @@ int UNet::forward(const half_t* sample, const float* timesteps, const half_t* eh
     Ctx ctx{&arena, stream, false};
     arena.begin(false);
     int rc = run(ctx, sample, timesteps, ehs, L, add_text, add_time_ids, out, B, H, W, image_embeds, n_img, control, n_ctrl,
-                 cn_scale, cfg_in);
+                 cn_scale, cfg_in, tcond);
     if (!rc && arena.overflow()) { set_error("unet: workspace overflow (planner bug)"); return 2; }
     return rc;
 }

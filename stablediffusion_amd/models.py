@@ -97,6 +97,7 @@ def _unet_config_struct(config: UNetConfig):
     c.freq_shift = float(config.freq_shift)
     c.addition_time_embed_dim = config.addition_time_embed_dim or 0
     c.projection_class_embeddings_input_dim = config.projection_class_embeddings_input_dim or 0
+    c.time_cond_proj_dim = getattr(config, "time_cond_proj_dim", None) or 0
     return c
 
 
@@ -277,7 +278,7 @@ class HipUNet2DConditionModel:
 
     def __call__(self, sample, timestep, encoder_hidden_states, cross_attention_kwargs=None,
                  added_cond_kwargs=None, return_dict=False, controlnet_cond=None, controlnet_conditioning_scale=None,
-                 **unused):
+                 timestep_cond=None, **unused):
         # diffusers' residual-tensor interface (a ControlNet run outside the engine): not taken -- silently dropping
         # it would return the plain UNet's output.  Attach the ControlNet instead (attach_controlnet).
         for k in ("down_block_additional_residuals", "mid_block_additional_residual", "down_intrablock_additional_residuals",
@@ -312,9 +313,25 @@ class HipUNet2DConditionModel:
             pt, pi = C.c_void_p(add_text.data_ptr()), C.c_void_p(add_ids.data_ptr())
         img = self._image_embeds(added_cond_kwargs, B, dev)
         ctrl, cscale = self._control(controlnet_cond, controlnet_conditioning_scale, B, H, W, dev)
+        tc = None
+        if timestep_cond is not None:
+            # guidance-embedded UNet (LCM): [B, time_cond_proj_dim], fp32 for the engine.  A tensor that is fp32 and
+            # contiguous on the device already -- what the pipeline makes once per call -- passes through untouched.
+            if self._cn is not None:
+                raise NotImplementedError("timestep_cond with a ControlNet attached is not supported")
+            tc = timestep_cond.to(device=dev, dtype=torch.float32).contiguous()
+            if tc.ndim != 2 or tc.shape[0] != B:
+                raise ValueError(f"timestep_cond: expected [{B}, time_cond_proj_dim], got {tuple(tc.shape)}")
         out = torch.empty((B, self.cfg.out_channels, H, W), device=dev, dtype=torch.float16)
         with torch.cuda.device(dev):
-            if ctrl is not None:
+            if tc is not None:
+                rc = self._lib.sd_unet_forward_tc(self._h, C.c_void_p(sample.data_ptr()), C.c_void_p(t.data_ptr()),
+                                                  C.c_void_p(ehs.data_ptr()), ehs.shape[1], pt, pi,
+                                                  C.c_void_p(img.data_ptr()) if img is not None else None,
+                                                  img.shape[1] if img is not None else 0,
+                                                  C.c_void_p(tc.data_ptr()), tc.shape[1],
+                                                  C.c_void_p(out.data_ptr()), B, H, W, C.c_void_p(_stream_ptr()))
+            elif ctrl is not None:
                 rc = self._lib.sd_unet_forward_cn(self._h, C.c_void_p(sample.data_ptr()), C.c_void_p(t.data_ptr()),
                                                   C.c_void_p(ehs.data_ptr()), ehs.shape[1], pt, pi,
                                                   C.c_void_p(img.data_ptr()) if img is not None else None,

@@ -249,9 +249,10 @@ class SDModelWrapper:
         """Registry of models/stable_diffusion.py:199-227 (names the engine's host code implements)."""
         if getattr(self, "scheduler_name", None) == scheduler_name:
             return
-        if scheduler_name not in _sched.REGISTRY:
+        make = _sched.REGISTRY.get(scheduler_name) or _sched.EXTRA_SCHEDULERS.get(scheduler_name)
+        if make is None:
             raise ValueError(f"Unknown scheduler name: {scheduler_name}")
-        self.scheduler = _sched.REGISTRY[scheduler_name](self.scheduler.config)
+        self.scheduler = make(self.scheduler.config)
         self.scheduler_name = scheduler_name
 
 
@@ -293,6 +294,20 @@ def rescale_noise_cfg(noise_cfg, noise_pred_text, guidance_rescale=0.0):
     return guidance_rescale * rescaled + (1 - guidance_rescale) * noise_cfg
 
 
+def guidance_scale_embedding(w: torch.Tensor, embedding_dim: int = 512, dtype=torch.float32) -> torch.Tensor:
+    """The `timestep_cond` of a guidance-embedded UNet (diffusers 0.27.2 LatentConsistencyModelPipeline.get_guidance_scale_embedding,
+    recalled): w [B] (guidance_scale - 1) -> [B, embedding_dim] = [sin(1000 w f_i) | cos(1000 w f_i)],
+    f_i = exp(-i ln(1e4) / (half - 1)), half = embedding_dim // 2, one zero column appended when embedding_dim is odd."""
+    w = torch.as_tensor(w, dtype=dtype).reshape(-1) * 1000.0
+    half = embedding_dim // 2
+    freq = torch.exp(torch.arange(half, dtype=dtype) * -(torch.log(torch.tensor(10000.0, dtype=dtype)) / (half - 1)))
+    ang = w[:, None] * freq[None, :]
+    emb = torch.cat([torch.sin(ang), torch.cos(ang)], dim=1)
+    if embedding_dim % 2 == 1:
+        emb = torch.nn.functional.pad(emb, (0, 1))
+    return emb
+
+
 def retrieve_timesteps(scheduler, num_inference_steps=None, device=None, **kwargs):
     """sd_unified_pipeline.py:61-95 (the custom timesteps / sigmas branches are never reached there)."""
     scheduler.set_timesteps(num_inference_steps, device=device, **kwargs)
@@ -305,13 +320,24 @@ def denoising_value_valid(dnv):
 
 class StableDiffusionUnifiedPipeline:
     def __init__(self, do_cfg: bool = True, device: Optional[str] = None, output_type: Optional[str] = None):
-        self.do_classifier_free_guidance = bool(do_cfg)
+        self._do_cfg = bool(do_cfg)
+        self._guidance_embedded = False      # set per call: the UNet takes the guidance scale as `timestep_cond`
         self.device = torch.device(device) if device is not None else torch.device("cpu")
         self.output_type = output_type if output_type is not None else "pt"
         self.model: Optional[SDModelWrapper] = None
         # the fused CFG step lets the engine run the start of the UNet once per latent (HipUNet2DConditionModel.forward_cfg);
         # False keeps the engine's duplicate-then-forward form
         self.cfg_share = True
+
+    @property
+    def do_classifier_free_guidance(self) -> bool:
+        # a guidance-embedded UNet (time_cond_proj_dim: Latent Consistency Models) runs without CFG whatever the
+        # constructor said; the negative prompt is unused, as in diffusers' LCM pipeline
+        return self._do_cfg and not self._guidance_embedded
+
+    @do_classifier_free_guidance.setter
+    def do_classifier_free_guidance(self, value):
+        self._do_cfg = bool(value)
 
     # ------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -357,6 +383,8 @@ class StableDiffusionUnifiedPipeline:
     ):
         if guess_mode:
             raise NotImplementedError("ControlNet guess_mode is not supported")
+        tc_dim = int(getattr(model.base.config, "time_cond_proj_dim", None) or 0)
+        self._guidance_embedded = tc_dim > 0
         if not 0.0 <= float(guidance_rescale) <= 1.0:
             raise ValueError(f"guidance_rescale must lie in [0, 1], got {guidance_rescale}")
         # as in diffusers: only with CFG on and a positive value
@@ -509,6 +537,14 @@ class StableDiffusionUnifiedPipeline:
                 image_embeds = [e.to(torch.float16).contiguous() for e in image_embeds]
             added_cond_kwargs = dict(added_cond_kwargs or {}, image_embeds=image_embeds)
 
+        # guidance-embedded UNet: the guidance scale goes in as an embedding, once per call, to every forward
+        tc_kwargs = {}
+        if tc_dim:
+            if has_cn:
+                raise NotImplementedError("a guidance-embedded UNet (time_cond_proj_dim) with a ControlNet is not supported")
+            w = torch.full((batch_size * num_images_per_prompt,), float(guidance_scale) - 1.0)
+            tc_kwargs = {"timestep_cond": guidance_scale_embedding(w, tc_dim).to(self.device)}
+
         control = None
         if has_cn:
             if num_channels_unet != 4:
@@ -543,9 +579,22 @@ class StableDiffusionUnifiedPipeline:
                 prompt_embeds = prompt_embeds.to(torch.float16).contiguous()
             kv_cache(True)
         fused_step = self._fused_step_available(model, latents, num_channels_unet)
+        # LCMScheduler: one noise draw per non-final step from a generator of this call's own (seeded with `seed`), made the
+        # same way at the same point whether the step then runs on the device (sd_lcm_step) or in scheduler.step
+        lcm = isinstance(model.scheduler, _sched.LCMScheduler)
+        lcm_step = lcm and self._lcm_step_available(model, latents, num_channels_unet, guidance_rescale)
+        loop_gen = lcm_final_t = None
+        if lcm:
+            # the scheduler's own last step adds no noise (a loop cut short by denoising_end does not reach it)
+            lcm_final_t = float(model.scheduler.timesteps[-1])
+            loop_gen = torch.Generator(device=latents.device)
+            if seed is not None:
+                loop_gen.manual_seed(int(seed))
+            else:
+                loop_gen.seed()
         fused_hist = None
         blend = None
-        if fused_step and self.is_inpaint:       # 4-channel inpainting: device-side blend after every step
+        if (fused_step or lcm_step) and self.is_inpaint:       # 4-channel inpainting: device-side blend after every step
             f16 = lambda x: x.to(device=latents.device, dtype=torch.float16).contiguous()
             m1 = mask.chunk(2)[0] if self.do_classifier_free_guidance else mask
             blend = (f16(image_latents), f16(noise), f16(m1.expand(latents.shape[0], 1, *latents.shape[2:])))
@@ -553,13 +602,23 @@ class StableDiffusionUnifiedPipeline:
             for i, t in enumerate(timesteps_host):
                 cn_kwargs = {} if control is None else dict(controlnet_cond=control,
                                                             controlnet_conditioning_scale=cn_scales[i])
+                last = i == len(timesteps_host) - 1
+                step_noise = None
+                if lcm and t != lcm_final_t:
+                    step_noise = torch.randn(latents.shape, dtype=latents.dtype, device=latents.device, generator=loop_gen)
+                if lcm_step:
+                    latents = self._lcm_iteration(model, latents, step_noise, t, prompt_embeds, cross_attention_kwargs,
+                                                  added_cond_kwargs, guidance_scale, **cn_kwargs, **tc_kwargs)
+                    if blend is not None:
+                        a, b = (1.0, 0.0) if last else model.scheduler.add_noise_coefficients(timesteps_host[i + 1])
+                        self._device_inpaint_blend(model, latents, blend, a, b, with_noise=not last)
+                    continue
                 if fused_step:
                     latents, fused_hist = self._fused_cfg_iteration(model, latents, fused_hist, t, prompt_embeds,
                                                                     cross_attention_kwargs, added_cond_kwargs,
                                                                     guidance_scale, guidance_rescale=guidance_rescale,
                                                                     **cn_kwargs)
                     if blend is not None:
-                        last = i == len(timesteps_host) - 1
                         a, b = (1.0, 0.0) if last else model.scheduler.add_noise_coefficients(timesteps_host[i + 1])
                         self._device_inpaint_blend(model, latents, blend, a, b, with_noise=not last)
                     continue
@@ -570,13 +629,16 @@ class StableDiffusionUnifiedPipeline:
                                                     masked_image_latents_2b.to(latent_model_input.dtype)], dim=1)
                 noise_pred = model.base(latent_model_input, t, prompt_embeds,
                                         cross_attention_kwargs=cross_attention_kwargs,
-                                        added_cond_kwargs=added_cond_kwargs, return_dict=False, **cn_kwargs)[0]
+                                        added_cond_kwargs=added_cond_kwargs, return_dict=False, **cn_kwargs, **tc_kwargs)[0]
                 if self.do_classifier_free_guidance:
                     noise_pred_uncond, noise_pred_text = noise_pred.chunk(2)
                     noise_pred = guidance_scale * (noise_pred_text - noise_pred_uncond) + noise_pred_uncond
                     if guidance_rescale > 0.0:
                         noise_pred = rescale_noise_cfg(noise_pred, noise_pred_text, guidance_rescale)
-                latents = model.scheduler.step(noise_pred, t, latents, return_dict=False)[0]
+                if lcm:
+                    latents = model.scheduler.step(noise_pred, t, latents, noise=step_noise, return_dict=False)[0]
+                else:
+                    latents = model.scheduler.step(noise_pred, t, latents, return_dict=False)[0]
                 if self.is_inpaint and num_channels_unet == 4:          # :492-506
                     init_latents_proper = image_latents
                     init_mask = mask.chunk(2)[0] if self.do_classifier_free_guidance else mask
@@ -639,19 +701,8 @@ class StableDiffusionUnifiedPipeline:
         latents = latents.contiguous()
         B = latents.shape[0]
         st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        if not unet_kwargs and hasattr(model.base, "forward_cfg") and getattr(model.base, "controlnet", None) is None:
-            # the engine takes the un-duplicated latents: no 2B-row copy, and the layers in front of the first
-            # cross-attention run once per latent
-            noise_pred = model.base.forward_cfg(latents, t, prompt_embeds, added_cond_kwargs=added_cond_kwargs,
-                                                in_scale=plan.in_scale, share=self.cfg_share)[0]
-        else:               # ControlNet calls: duplicate, then the forward that takes the control image
-            lat2 = torch.empty((2 * B,) + tuple(latents.shape[1:]), device=latents.device, dtype=latents.dtype)
-            rc = lib.sd_cfg_duplicate(C.c_void_p(latents.data_ptr()), C.c_void_p(lat2.data_ptr()),
-                                      latents[0].numel(), B, plan.in_scale, st)
-            if rc:
-                raise RuntimeError(lib.sd_last_error().decode())
-            noise_pred = model.base(lat2, t, prompt_embeds, cross_attention_kwargs=cross_attention_kwargs,
-                                    added_cond_kwargs=added_cond_kwargs, return_dict=False, **unet_kwargs)[0]
+        noise_pred = self._cfg_forward(model, latents, plan.in_scale, t, prompt_embeds, cross_attention_kwargs,
+                                       added_cond_kwargs, **unet_kwargs)
         if plan.use_hist and hist is None:
             hist = torch.zeros(latents.shape, device=latents.device, dtype=torch.float32)
         out = latents.clone()
@@ -668,6 +719,57 @@ class StableDiffusionUnifiedPipeline:
             raise RuntimeError(lib.sd_last_error().decode())
         model.scheduler.fused_commit()
         return out, hist
+
+    def _cfg_forward(self, model, latents, in_scale, t, prompt_embeds, cross_attention_kwargs, added_cond_kwargs,
+                     **unet_kwargs):
+        """The UNet forward of one CFG step from the un-duplicated fp16 latents: [2B, ...], negative half first."""
+        import ctypes as C
+        lib = model.base._lib
+        B = latents.shape[0]
+        if not unet_kwargs and hasattr(model.base, "forward_cfg") and getattr(model.base, "controlnet", None) is None:
+            # the engine takes the un-duplicated latents: no 2B-row copy, and the layers in front of the first
+            # cross-attention run once per latent
+            return model.base.forward_cfg(latents, t, prompt_embeds, added_cond_kwargs=added_cond_kwargs,
+                                          in_scale=in_scale, share=self.cfg_share)[0]
+        # ControlNet calls: duplicate, then the forward that takes the control image
+        lat2 = torch.empty((2 * B,) + tuple(latents.shape[1:]), device=latents.device, dtype=latents.dtype)
+        rc = lib.sd_cfg_duplicate(C.c_void_p(latents.data_ptr()), C.c_void_p(lat2.data_ptr()),
+                                  latents[0].numel(), B, in_scale, C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        if rc:
+            raise RuntimeError(lib.sd_last_error().decode())
+        return model.base(lat2, t, prompt_embeds, cross_attention_kwargs=cross_attention_kwargs,
+                          added_cond_kwargs=added_cond_kwargs, return_dict=False, **unet_kwargs)[0]
+
+    def _lcm_step_available(self, model, latents, num_channels_unet=4, guidance_rescale=0.0) -> bool:
+        """LCMScheduler's step as one device kernel (`sd_lcm_step`: guidance combine, boundary condition, re-noising) on
+        the HIP engine with fp16 CUDA latents -- with or without CFG, unlike `_fused_step_available`.  9-channel
+        inpainting UNets and guidance_rescale (a per-sample statistic) take scheduler.step."""
+        return ((not self.is_inpaint or num_channels_unet == 4) and not guidance_rescale > 0.0
+                and hasattr(model.base, "_lib") and latents.is_cuda and latents.dtype == torch.float16)
+
+    def _lcm_iteration(self, model, latents, noise, t, prompt_embeds, cross_attention_kwargs, added_cond_kwargs,
+                       guidance_scale, **unet_kwargs):
+        import ctypes as C
+        lib = model.base._lib
+        plan = model.scheduler.fused_plan(t)
+        latents = latents.contiguous()
+        if self.do_classifier_free_guidance:         # an ordinary UNet (LCM-LoRA): rows = [uncond ; text]
+            rows = 2
+            model_out = self._cfg_forward(model, latents, plan.in_scale, t, prompt_embeds, cross_attention_kwargs,
+                                          added_cond_kwargs, **unet_kwargs)
+        else:                                        # guidance-embedded (timestep_cond in unet_kwargs), or no guidance
+            rows = 1
+            model_out = model.base(latents, t, prompt_embeds, cross_attention_kwargs=cross_attention_kwargs,
+                                   added_cond_kwargs=added_cond_kwargs, return_dict=False, **unet_kwargs)[0]
+        out = latents.clone()
+        noise_p = C.c_void_p(noise.contiguous().data_ptr()) if plan.needs_noise else None
+        rc = lib.sd_lcm_step(C.c_void_p(model_out.data_ptr()), rows, C.c_void_p(out.data_ptr()), noise_p, None, out.numel(),
+                             float(guidance_scale), plan.d_x, plan.d_out, plan.p_den, plan.p_noise,
+                             C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        if rc:
+            raise RuntimeError(lib.sd_last_error().decode())
+        model.scheduler.fused_commit()
+        return out
 
     @staticmethod
     def control_image_processor(model):

@@ -601,6 +601,108 @@ class UniPCMultistepScheduler(_Base):
         return (prev,) if not return_dict else SimpleNamespace(prev_sample=prev)
 
 
+class LCMScheduler(_Base):
+    """Latent Consistency Model sampling (Luo et al. 2023; diffusers 0.27.2 `LCMScheduler`, recalled and unpinned:
+    DESIGN.md section 8): the model output becomes an x0 prediction, the consistency boundary condition mixes it with the
+    sample (c_skip, c_out), and every step but the last re-noises the result to the NEXT timestep of the schedule.
+    2-8 steps, taken from the `original_inference_steps` the model was distilled on.  For guidance-embedded UNets
+    (`time_cond_proj_dim`) and for ordinary checkpoints with an LCM-LoRA fused in.
+
+    Stochastic, and not affine in (x, eps) alone: its device step is `sd_lcm_step` (`fused_plan` returns that kernel's
+    coefficients), not the CFG step of the deterministic schedulers (`supports_fused = False` keeps it off that path)."""
+
+    supports_fused = False
+    sigma_data = 0.5
+
+    def __init__(self, original_inference_steps=50, timestep_scaling=10.0, set_alpha_to_one=True, **kw):
+        if kw.get("timestep_spacing", "leading") == "trailing":
+            raise ValueError("LCMScheduler does not implement timestep_spacing='trailing'")
+        kw["timestep_spacing"] = "leading"         # (unused: the schedule is a subset of the distillation's)
+        super().__init__(original_inference_steps=int(original_inference_steps), timestep_scaling=float(timestep_scaling),
+                         set_alpha_to_one=bool(set_alpha_to_one), **kw)
+        self.final_alpha_cumprod = 1.0 if set_alpha_to_one else self.ac[0]
+        self._i = None
+
+    @classmethod
+    def from_config(cls, config, **kw):
+        d = dict(vars(config)) if not isinstance(config, dict) else dict(config)
+        keep = {k: d[k] for k in ("num_train_timesteps", "beta_start", "beta_end", "steps_offset", "prediction_type",
+                                  "rescale_betas_zero_snr", "original_inference_steps", "timestep_scaling",
+                                  "set_alpha_to_one") if k in d}
+        if d.get("timestep_spacing") == "trailing":      # another scheduler's linspace / leading says nothing here
+            keep["timestep_spacing"] = "trailing"
+        keep.update(kw)
+        return cls(**keep)
+
+    def set_timesteps(self, num_inference_steps, device=None, original_inference_steps=None, strength=1.0, **kw):
+        n = int(num_inference_steps)
+        T = self.config.num_train_timesteps
+        original = int(original_inference_steps or self.config.original_inference_steps)
+        if original > T:
+            raise ValueError(f"original_inference_steps {original} cannot exceed num_train_timesteps {T}")
+        if n > original:
+            raise ValueError(f"num_inference_steps {n} cannot exceed original_inference_steps {original}")
+        k = T // original
+        origin = np.arange(1, int(original * strength) + 1) * k - 1
+        if n < 1 or len(origin) // n < 1:
+            raise ValueError(f"{len(origin)} distillation timesteps (original_inference_steps {original} x strength "
+                             f"{strength}) are fewer than num_inference_steps {n}")
+        origin = origin[::-1].copy()
+        idx = np.floor(np.linspace(0, len(origin), n, endpoint=False)).astype(np.int64)
+        self.num_inference_steps = n
+        self.timesteps = torch.from_numpy(origin[idx].astype(np.int64)).to(device)
+        self._ts = [int(v) for v in origin[idx]]
+        self._i = None
+
+    def _boundary(self, t):
+        s = float(t) * self.config.timestep_scaling
+        sd2 = self.sigma_data ** 2
+        return sd2 / (s * s + sd2), s / (s * s + sd2) ** 0.5          # c_skip, c_out
+
+    def _coefficients(self, timestep):
+        """(d_x, d_out, p_den, p_noise, last) of the step at this position, float64:
+            denoised = d_x x + d_out model_output;   prev = p_den denoised + p_noise noise"""
+        i = self._begin(timestep)
+        t = self._ts[i]
+        last = i == len(self._ts) - 1
+        a = self.ac[t]
+        ra, rb = a ** 0.5, (1 - a) ** 0.5
+        c_skip, c_out = self._boundary(t)
+        if self.v_prediction:                      # x0 = ra x - rb v
+            d_x, d_out = c_skip + c_out * ra, -c_out * rb
+        else:                                      # x0 = (x - rb eps) / ra
+            if a <= 0.0:
+                raise ValueError(f"epsilon-prediction cannot step from timestep {t}: alpha-bar is 0 there")
+            d_x, d_out = c_skip + c_out / ra, -c_out * rb / ra
+        if last:
+            return float(d_x), float(d_out), 1.0, 0.0, True
+        a_prev = self.ac[self._ts[i + 1]]
+        return float(d_x), float(d_out), float(a_prev ** 0.5), float((1 - a_prev) ** 0.5), False
+
+    def fused_plan(self, timestep=None):
+        """The step as `sd_lcm_step` applies it; v-prediction is eps = a v + s x substituted into d_x / d_out (what
+        `_plan_from_v` does for the affine schedulers -- `_coefficients` writes both forms out)."""
+        d_x, d_out, p_den, p_noise, last = self._coefficients(timestep)
+        return FusedPlan(in_scale=1.0, d_x=d_x, d_out=d_out, p_den=p_den, p_noise=p_noise, needs_noise=not last)
+
+    def fused_commit(self):
+        self._i += 1
+
+    def step(self, model_output, timestep, sample, generator=None, noise=None, return_dict=False, **kw):
+        """-> (prev_sample, denoised).  The last step adds no noise: prev_sample is denoised."""
+        d_x, d_out, p_den, p_noise, last = self._coefficients(timestep)
+        denoised = d_x * sample.float() + d_out * model_output.float()
+        prev = denoised
+        if not last:
+            if noise is None:
+                noise = torch.randn(model_output.shape, generator=generator, device=model_output.device,
+                                    dtype=model_output.dtype)
+            prev = p_den * denoised + p_noise * noise.float()
+        self._i += 1
+        prev, denoised = prev.to(sample.dtype), denoised.to(sample.dtype)
+        return (prev, denoised) if not return_dict else SimpleNamespace(prev_sample=prev, denoised=denoised)
+
+
 REGISTRY = {
     # names of /root/reference/models/stable_diffusion.py:199-227 (all eight)
     "DDIM": lambda cfg: DDIMScheduler.from_config(cfg),
@@ -611,4 +713,9 @@ REGISTRY = {
     "DPM++ 2M SDE Karras": lambda cfg: DPMSolverSDEScheduler.from_config(cfg),
     "PNDM": lambda cfg: PNDMScheduler.from_config(cfg),
     "uni_pc": lambda cfg: UniPCMultistepScheduler.from_config(cfg),
+}
+
+# Schedulers beyond the reference's eight (REGISTRY stays the reference's list); SDModelWrapper.set_scheduler looks here next.
+EXTRA_SCHEDULERS = {
+    "lcm": lambda cfg: LCMScheduler.from_config(cfg),
 }

@@ -83,6 +83,8 @@ def unet_manifest(cfg: UNetConfig) -> "OrderedDict[str, Tuple[int, ...]]":
     m["time_embedding.linear_1.bias"] = (temb,)
     m["time_embedding.linear_2.weight"] = (temb, temb)
     m["time_embedding.linear_2.bias"] = (temb,)
+    if cfg.time_cond_proj_dim:
+        m["time_embedding.cond_proj.weight"] = (boc[0], cfg.time_cond_proj_dim)
     if cfg.addition_embed_type == "text_time":
         pin = cfg.projection_class_embeddings_input_dim
         m["add_embedding.linear_1.weight"] = (temb, pin)
