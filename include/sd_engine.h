@@ -397,6 +397,23 @@ int sd_igemm_plan(const int* geom, const int* flags, int64_t* out, char* name);
 int sd_op_conv2d(const void* x_nhwc, const void* w_oihw, const void* bias, const void* rowadd,
                  const void* res_nhwc, void* y_nhwc, int N, int H, int W, int Cin, int Cout,
                  int ksize, int stride, int upsample2x, int geglu, void* stream);
+/* sd_op_conv2d with the operands as the engine passes them, for the element-wise kernel tests (tests/test_conv_gpu.py):
+ *   ldx, ldres, ldy   row strides in elements of x, res and y: the dense width (Cin; Cout, or Cout / 2 under geglu) or a
+ *                     wider multiple of 8, so that an operand can be a column slice of a wider buffer
+ *   pad               -1: the kernel size's default (1 for 3x3, 0 for 1x1); 0 with stride 2 is the VAE encoder's
+ *                     downsample (right / bottom zero column), output size as in sd_igemm_plan
+ *   act               0 none, 1 quick-GELU, 2 erf-GELU after the bias
+ *   acc_scale, bias_scale   y = acc_scale * conv + bias_scale * bias (+ rowadd + res), powers of two
+ *   gn_groups         > 0: the launch is also asked for the GroupNorm summaries of y for that many groups (left in a
+ *                     buffer dropped on return); a split launch then reduces with splitk_epilogue_gs_kernel
+ *   ran[4]            out: kind and tile variant of the plan the launch ran (as sd_igemm_plan's out[0], out[1]), the
+ *                     split-K slices the launcher started (at most the planned count), the reduction kernel behind
+ *                     them (0 none, 1 splitk_epilogue_kernel, 2 splitk_epilogue_gs_kernel)
+ * SD_ERR_INVALID for a bad stride, and for scales or an activation the planned kernel does not take. */
+int sd_op_conv2d_ex(const void* x_nhwc, const void* w_oihw, const void* bias, const void* rowadd,
+                    const void* res_nhwc, void* y_nhwc, int N, int H, int W, int Cin, int Cout, int ksize,
+                    int stride, int upsample2x, int geglu, int64_t ldx, int64_t ldres, int64_t ldy, int pad, int act,
+                    float acc_scale, float bias_scale, int gn_groups, int* ran, void* stream);
 /* conv_out: 3x3 / stride 1 / pad 1 convolution to 1..4 output channels (UNet2DConditionModel.conv_out 320 -> 4,
  * AutoencoderKL decoder.conv_out 128 -> 3; diffusers modules under sd_unified_pipeline.py:475-482, :523) with
  * the NHWC -> NCHW change of layout fused: x NHWC f16, w OIHW f16, bias f32, y NCHW f16.  Cin % 64 == 0. */

@@ -150,6 +150,8 @@ SIGNATURES = {
     "sd_prof_enable": (_I, [_I]),
     "sd_prof_collect": (_I, [C.POINTER(SdProfEntry), _I, C.POINTER(_I)]),
     "sd_op_conv2d": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "sd_op_conv2d_ex": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I64, _I64, _I64, _I, _I, _F, _F, _I,
+                             C.POINTER(_I), _P]),
     "sd_op_conv3x3_small_cout": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "sd_op_conv2d_groupnorm": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _I,
                                     C.POINTER(_I), _P]),

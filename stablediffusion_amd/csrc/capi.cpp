@@ -594,10 +594,21 @@ static IGemmParams pointwise_params(const half_t* x, const half_t* w, const floa
     return p;
 }
 
+// What sd_op_conv2d_ex adds to the plain entry: operand strides in elements, an explicit padding (-1: the kernel size's
+// default), the epilogue's activation and scales, GroupNorm summaries asked of the launch (into a buffer dropped on
+// return: they pick the split-K reduction kernel), and `ran` = kind, variant, split-K slices launched, reduction kernel.
+struct ConvEx {
+    long ldx, ldres, ldy;
+    int pad, act;
+    float acc_scale, bias_scale;
+    int gn_groups;
+    int* ran;
+};
+
 static int conv2d_impl(const void* x, const void* w_oihw, const void* bias_f32, const void* rowadd_f32, const void* res,
                        void* y, int N, int H, int W, int Cin, int Cout, int ksize, int stride, int upsample2x,
                        int geglu, void* stream, int iters, float* ms_out, const GnTail* gn = nullptr,
-                       const GnHead* gh = nullptr) {
+                       const GnHead* gh = nullptr, const ConvEx* ex = nullptr) {
     hipStream_t s = static_cast<hipStream_t>(stream);
     const long K = (long)ksize * ksize * Cin;
     if (K % 64 != 0 || Cin % 64 != 0) { set_error("sd_op_conv2d: Cin must be a multiple of 64"); return SD_ERR_INVALID; }
@@ -635,11 +646,22 @@ static int conv2d_impl(const void* x, const void* w_oihw, const void* bias_f32, 
         const int IH = H << upsample2x, IW = W << upsample2x;
         p.OH = (IH + 2 * p.pad - ksize) / stride + 1;
         p.OW = (IW + 2 * p.pad - ksize) / stride + 1;
+        if (ex && ex->pad >= 0) {               // output size as op_conv derives it from an explicit padding
+            p.pad = ex->pad;
+            if (stride == 1) { p.OH = IH; p.OW = IW; }
+            else if (p.pad == 0) { p.OH = (IH + 1 - ksize) / stride + 1; p.OW = (IW + 1 - ksize) / stride + 1; }
+            else { p.OH = (IH + 2 * p.pad - ksize) / stride + 1; p.OW = (IW + 2 * p.pad - ksize) / stride + 1; }
+        }
         p.Cout = Cout; p.M = N * p.OH * p.OW; p.K = (int)K; p.geglu = geglu;
         const int ocols = geglu ? Cout / 2 : Cout;
         p.ldres = ocols; p.y = static_cast<half_t*>(y); p.ldy = ocols;
         float* gnbuf = nullptr;
         float* gnscratch = nullptr;
+        if (ex) {
+            p.ldx = ex->ldx; p.ldres = ex->ldres; p.ldy = ex->ldy;
+            p.act = ex->act; p.acc_scale = ex->acc_scale; p.bias_scale = ex->bias_scale;
+            if (ex->gn_groups > 0) SD_DEV_ALLOC(scope, gnbuf, (size_t)gnstat_floats(N, (long)p.OH * p.OW, ex->gn_groups) * 4);
+        }
         if (gn) {
             if (gn->fused) *gn->fused = 0;
             SD_DEV_ALLOC(scope, gnscratch, (size_t)gn_scratch_floats(N, (long)p.OH * p.OW, Cout, gn->groups) * 4);
@@ -678,12 +700,18 @@ static int conv2d_impl(const void* x, const void* w_oihw, const void* bias_f32, 
             SD_HIP_CHECK(hipMemsetAsync(res_bench, 0, (size_t)p.M * ocols * sizeof(half_t), s));
             p.res = res_bench;
         }
-        const IGemmPlan plan = igemm2_plan(p, IGemmRequest{nullptr, gnbuf, gn ? gn->groups : 0});
+        const IGemmPlan plan = igemm2_plan(p, IGemmRequest{nullptr, gnbuf, gn ? gn->groups : ex ? ex->gn_groups : 0});
+        if (ex && !plan.scales_ok && (p.acc_scale != 1.f || p.bias_scale != 1.f)) {
+            set_error("sd_op_conv2d_ex: the planned kernel does not take acc_scale / bias_scale"); return SD_ERR_INVALID;
+        }
+        if (ex && plan.kind == kKindIgemm1 && p.act) {
+            set_error("sd_op_conv2d_ex: the planned kernel has no activation epilogue"); return SD_ERR_INVALID;
+        }
         if (plan.partial_floats > 0) SD_DEV_ALLOC(scope, partial, (size_t)plan.partial_floats * sizeof(float));
         GnStats gst;
         if (plan.gnstats) {
             gst.part = gnbuf; gst.rows = plan.gn_rows; gst.S = p.OH * p.OW / plan.gn_rows;
-            if (gn->fused) *gn->fused = 1;
+            if (gn && gn->fused) *gn->fused = 1;
         }
         hipEvent_t e0 = nullptr, e1 = nullptr;
         if (ms_out) { SD_HIP_CHECK(hipEventCreate(&e0)); SD_HIP_CHECK(hipEventCreate(&e1)); }
@@ -712,6 +740,10 @@ static int conv2d_impl(const void* x, const void* w_oihw, const void* bias_f32, 
             if (wring) p.w = reinterpret_cast<half_t*>(reinterpret_cast<char*>(wring) + wbytes * (size_t)(it % nrot));
             rc = launch_igemm2(p, partial, s, &plan);
         }
+        if (ex && ex->ran) {
+            const IGemmLaunchNote note = igemm2_last_launch();
+            ex->ran[0] = plan.kind; ex->ran[1] = plan.variant; ex->ran[2] = note.splits; ex->ran[3] = note.reducer;
+        }
         if (gn && !rc)
             rc = launch_groupnorm(p.y, p.ldy, gn->gamma, gn->beta, static_cast<half_t*>(gn->y), Cout, N, (long)p.OH * p.OW, Cout,
                                   gn->groups, gn->eps, gn->silu, gnscratch, s, gst.part ? &gst : nullptr);
@@ -736,6 +768,29 @@ int sd_op_conv2d(const void* x, const void* w_oihw, const void* bias_f32, const 
                  int geglu, void* stream) {
     return conv2d_impl(x, w_oihw, bias_f32, rowadd_f32, res, y, N, H, W, Cin, Cout, ksize, stride, upsample2x, geglu,
                        stream, 1, nullptr);
+}
+
+int sd_op_conv2d_ex(const void* x, const void* w_oihw, const void* bias_f32, const void* rowadd_f32, const void* res,
+                    void* y, int N, int H, int W, int Cin, int Cout, int ksize, int stride, int upsample2x, int geglu,
+                    int64_t ldx, int64_t ldres, int64_t ldy, int pad, int act, float acc_scale, float bias_scale,
+                    int gn_groups, int* ran, void* stream) {
+    if (!x || !w_oihw || !y || !ran || N < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1 || (ksize != 1 && ksize != 3) ||
+        stride < 1 || upsample2x < 0 || upsample2x > 1 || (geglu && Cout % 2 != 0)) {
+        set_error("sd_op_conv2d_ex: bad arguments"); return SD_ERR_INVALID;
+    }
+    const int ocols = geglu ? Cout / 2 : Cout;
+    // a stride is the dense width or a wider multiple of 8 elements (the kernels move 16-byte chunks)
+    auto ld_ok = [](int64_t ld, int dense) { return ld == dense || (ld > dense && ld % 8 == 0); };
+    if (!ld_ok(ldx, Cin) || !ld_ok(ldy, ocols) || (res && !ld_ok(ldres, ocols))) {
+        set_error("sd_op_conv2d_ex: ldx / ldres / ldy must be the dense width or a wider multiple of 8"); return SD_ERR_INVALID;
+    }
+    if (pad < -1 || pad > 1 || act < 0 || act > 2 || gn_groups < 0 || !(acc_scale > 0.f) || !(bias_scale > 0.f)) {
+        set_error("sd_op_conv2d_ex: pad in -1..1, act in 0..2, positive scales"); return SD_ERR_INVALID;
+    }
+    for (int i = 0; i < 4; ++i) ran[i] = 0;
+    const ConvEx ex{(long)ldx, (long)ldres, (long)ldy, pad, act, acc_scale, bias_scale, gn_groups, ran};
+    return conv2d_impl(x, w_oihw, bias_f32, rowadd_f32, res, y, N, H, W, Cin, Cout, ksize, stride, upsample2x, geglu,
+                       stream, 1, nullptr, nullptr, nullptr, &ex);
 }
 
 int sd_op_conv3x3_small_cout(const void* x, const void* w_oihw, const void* bias_f32, void* y_nchw, int N, int H, int W,

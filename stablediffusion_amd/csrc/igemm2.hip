@@ -671,8 +671,15 @@ inline int splitk_gs_cols(const IGemmParams& p) {
     while (cb + unit <= 320 && cb + unit <= p.Cout) cb += unit;
     return cb;
 }
+// What the calling thread's last launch_igemm2 did about split-K, noted where it is decided: the slices by the tile
+// launchers (after their cdiv collapse), the reduction kernel here.  Read through igemm2_last_launch().
+thread_local IGemmLaunchNote t_note;
+inline void note_splits(int eff_splits) { t_note.splits = eff_splits; }
+inline void note_reducer(int reducer) { t_note.reducer = reducer; }
+
 inline int launch_splitk_epilogue(const IGemmParams& p, const float* partial, int splits, hipStream_t s) {
     const int rb = p.gnstat_out ? splitk_gs_rows(p, p.gn_groups) : 0;
+    note_reducer(rb ? 2 : 1);
     if (rb) {
         const int cb = splitk_gs_cols(p);
         const size_t lds = (size_t)rb * (cb / 8) * 16;
@@ -1141,6 +1148,7 @@ int launch_halo_t(const IGemmParams& p, float* partial, int splits, hipStream_t 
     const int nslab = p.Cin / 64;
     const int per = cdiv(nslab, splits);
     const int eff_splits = cdiv(nslab, per);
+    note_splits(eff_splits);
     IGemmParams q = p;
     q.mfast = weights_outweigh_activations(p);
     if (eff_splits > 1) q.gnstat_out = nullptr;
@@ -1179,6 +1187,7 @@ int launch_v2p(const IGemmParams& p, float* partial, int splits, hipStream_t s) 
     const int nk = p.K / BKT;
     const int per = cdiv(nk, splits);
     const int eff_splits = cdiv(nk, per);
+    note_splits(eff_splits);
     IGemmParams q = p;
     q.mfast = weights_outweigh_activations(p);
     q.rowstat_parts = cdiv(p.Cout, BN);
@@ -1414,7 +1423,10 @@ IGemmPlan igemm2_plan(IGemmParams& p, const IGemmRequest& rq) {
     return pl;
 }
 
+IGemmLaunchNote igemm2_last_launch() { return t_note; }
+
 int launch_igemm2(const IGemmParams& p, float* partial, hipStream_t s, const IGemmPlan* plan) {
+    t_note = IGemmLaunchNote();
     IGemmParams q = p;
     IGemmPlan own;
     if (!plan || (plan->splits > 1 && !partial)) {

@@ -105,6 +105,13 @@ IGemmPlan igemm2_plan(IGemmParams& p, const IGemmRequest& rq = IGemmRequest());
 // Runs p as planned; plans it itself (requests = p's own rowstat_out / gnstat_out) when no plan is passed.  A plan that
 // splits K needs `partial` of plan->partial_floats; without it the launch is planned again and runs unsplit.
 int launch_igemm2(const IGemmParams& p, float* partial, hipStream_t s, const IGemmPlan* plan = nullptr);
+// What the calling thread's last launch_igemm2 launched on top of the plan: the split-K slices after the launcher's
+// collapse (cdiv(slabs, cdiv(slabs, plan.splits)), at most plan.splits) and the reduction kernel behind them.
+struct IGemmLaunchNote {
+    int splits = 1;
+    int reducer = 0;                // 0 none, 1 splitk_epilogue_kernel, 2 splitk_epilogue_gs_kernel
+};
+IGemmLaunchNote igemm2_last_launch();
 // Pointwise 128 x 80 tile with the activation operand fetched straight into registers (igemm3.hip): launch_igemm2 takes
 // it instead of the 128 x 80 LDS-DMA variants when the problem allows (no split-K, GEGLU, row add, GroupNorm summaries).
 bool igemm3_supported(const IGemmParams& p);
