@@ -334,6 +334,36 @@ int sd_cfg_rescale_linear_step(const void* noise_pred_2b, void* latents, float* 
 int sd_lcm_step(const void* model_out, int rows, void* latents, const void* noise, void* denoised, int64_t n,
                 float guidance_scale, float d_x, float d_out, float p_den, float p_noise, void* stream);
 
+/* One step of any scheduler whose update is affine in a slightly larger state than sd_cfg_linear_step's: the sample, the
+ * model output, fresh noise and up to four fp32 history tensors the scheduler keeps between steps (euler_a, DPM++ 2M SDE,
+ * PNDM, UniPC; schedulers.py `affine_plan`).  Per element i, with the operand vector
+ *   v = (x, m, z, h_0 .. h_3),   x = latents[i],  z = noise[i],  h_k = bank[k * bank_stride + i],
+ *   m = model_out[i] (rows == 1)  or  fp16(u + g (t - u)), u = model_out[i], t = model_out[n + i] (rows == 2, rounded as
+ *       sd_cfg_linear_step and sd_lcm_step round it),
+ * the step is up to three rows of coefficients, every one evaluated from the OLD values (all loads precede all stores,
+ * so a slot may be read and written in one step):
+ *   latents[i] <- fp16(out . v);   bank[write_slot[j] * bank_stride + i] <- fp32(write[j] . v),  j < n_writes.
+ * The dot products run in fp64 from the float64 coefficients (predictor / corrector rows cancel) and are rounded once.
+ * A coefficient that is exactly 0 contributes nothing and an operand whose column is 0 in every used row is not loaded:
+ * an unwritten slot may hold anything, and noise may be NULL when its column is 0.  latents and noise f16 [n], model_out
+ * f16 [rows * n], bank f32.  One launch, no host synchronisation; 16-byte accesses when n % 8 == 0, every base is 16-byte
+ * aligned and bank_stride % 4 == 0, a scalar kernel otherwise.
+ * SD_ERR_INVALID (nothing is launched): rows not 1 or 2, n <= 0, null model_out / latents / plan, n_slots outside 0..4,
+ * n_writes outside 0..2, a write_slot >= n_slots or repeated, a null bank or bank_stride < n with n_slots > 0, a null noise
+ * with a non-zero z coefficient in a used row, a non-finite coefficient in a used row and column (rows: out and the first
+ * n_writes of write; columns: x, m, z and the first n_slots slots -- the rest is ignored). */
+#define SD_STEP_MAX_SLOTS 4
+#define SD_STEP_MAX_WRITES 2
+typedef struct sd_step_plan {
+    int32_t n_slots;                                             /* 0..4 fp32 history slots */
+    int32_t n_writes;                                            /* 0..2 of them are written this step */
+    int32_t write_slot[SD_STEP_MAX_WRITES];                      /* distinct, < n_slots */
+    double out[3+SD_STEP_MAX_SLOTS];                             /* latents <- fp16(out . v) */
+    double write[SD_STEP_MAX_WRITES][3+SD_STEP_MAX_SLOTS];       /* bank[write_slot[j]] <- fp32(write[j] . v) */
+} sd_step_plan;
+int sd_sched_affine_step(const void* model_out, int rows, void* latents, const void* noise, float* bank,
+                         int64_t bank_stride, int64_t n, float guidance_scale, const sd_step_plan* plan, void* stream);
+
 /* Inpainting with a 4-channel UNet, after every scheduler step (sd_unified_pipeline.py:492-506):
  *   latents <- m latents + (1 - m) (a image_latents + b noise),  m = mask [B,1,H,W] f16 over channels;
  * (a, b) = scheduler.add_noise coefficients at the NEXT timestep, or noise = NULL on the last step. */

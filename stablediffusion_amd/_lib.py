@@ -12,6 +12,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libsd_engine.so")
 
 SD_MAX_BLOCKS = 4
+SD_STEP_MAX_SLOTS = 4
+SD_STEP_MAX_WRITES = 2
 SD_DTYPE_F16 = 0
 SD_DTYPE_F32 = 1
 
@@ -73,6 +75,25 @@ class SdProfEntry(C.Structure):
 class SdCnProblem(C.Structure):
     _fields_ = [("x", C.c_void_p), ("ldx", C.c_int64), ("w", C.c_void_p), ("bias", C.c_void_p),
                 ("y", C.c_void_p), ("ldy", C.c_int64), ("M", C.c_int), ("C", C.c_int)]
+
+
+class SdStepPlan(C.Structure):
+    """One scheduler step for sd_sched_affine_step: rows of float64 coefficients over (x, m, z, h_0 .. h_3)."""
+    _fields_ = [("n_slots", C.c_int32), ("n_writes", C.c_int32), ("write_slot", C.c_int32 * SD_STEP_MAX_WRITES),
+                ("out", C.c_double * (3 + SD_STEP_MAX_SLOTS)),
+                ("write", C.c_double * (3 + SD_STEP_MAX_SLOTS) * SD_STEP_MAX_WRITES)]
+
+
+def step_plan(plan) -> SdStepPlan:
+    """schedulers.AffinePlan -> the struct sd_sched_affine_step takes."""
+    if len(plan.writes) > SD_STEP_MAX_WRITES or plan.n_slots > SD_STEP_MAX_SLOTS:
+        raise ValueError(f"an affine step has at most {SD_STEP_MAX_WRITES} writes and {SD_STEP_MAX_SLOTS} slots")
+    p = SdStepPlan(n_slots=plan.n_slots, n_writes=len(plan.writes))
+    p.out[:] = plan.out
+    for j, (slot, row) in enumerate(plan.writes):
+        p.write_slot[j] = slot
+        p.write[j][:] = row
+    return p
 
 
 # name -> (restype, argtypes); every symbol include/sd_engine.h declares
@@ -142,6 +163,7 @@ SIGNATURES = {
     "sd_cfg_linear_step": (_I, [_P, _P, _P, _I64, _F, _F, _F, _F, _F, _F, _P]),
     "sd_cfg_rescale_linear_step": (_I, [_P, _P, _P, _I, _I64, _F, _F, _F, _F, _F, _F, _F, _P, _P]),
     "sd_lcm_step": (_I, [_P, _I, _P, _P, _P, _I64, _F, _F, _F, _F, _F, _P]),
+    "sd_sched_affine_step": (_I, [_P, _I, _P, _P, _P, _I64, _I64, _F, C.POINTER(SdStepPlan), _P]),
     "sd_igemm_force": (_I, [_I, _I]),
     "sd_igemm_plan": (_I, [C.POINTER(_I), C.POINTER(_I), C.POINTER(_I64), C.c_char_p]),
     "sd_probe_mfma": (_I, [_I, C.POINTER(_F), _P]),

@@ -451,6 +451,46 @@ int sd_lcm_step(const void* model_out, int rows, void* latents, const void* nois
                            static_cast<const half_t*>(noise), static_cast<half_t*>(denoised), (long)n, guidance_scale, d_x,
                            d_out, p_den, p_noise, static_cast<hipStream_t>(stream));
 }
+int sd_sched_affine_step(const void* model_out, int rows, void* latents, const void* noise, float* bank,
+                         int64_t bank_stride, int64_t n, float guidance_scale, const sd_step_plan* plan, void* stream) {
+    static_assert(STEP_SLOTS == SD_STEP_MAX_SLOTS && STEP_WRITES == SD_STEP_MAX_WRITES, "sd_step_plan and StepRows differ");
+    if (!model_out || !latents || !plan || (rows != 1 && rows != 2) || n <= 0) {
+        set_error("sd_sched_affine_step: bad arguments (non-null model_out / latents / plan, rows 1 or 2, n > 0)");
+        return SD_ERR_INVALID;
+    }
+    const int ns = plan->n_slots, nw = plan->n_writes;
+    if (ns < 0 || ns > SD_STEP_MAX_SLOTS || nw < 0 || nw > SD_STEP_MAX_WRITES) {
+        set_error("sd_sched_affine_step: n_slots must be 0..4 and n_writes 0..2");
+        return SD_ERR_INVALID;
+    }
+    for (int j = 0; j < nw; ++j)
+        if (plan->write_slot[j] < 0 || plan->write_slot[j] >= ns || (j == 1 && plan->write_slot[1] == plan->write_slot[0])) {
+            set_error("sd_sched_affine_step: write_slot must be distinct slots below n_slots");
+            return SD_ERR_INVALID;
+        }
+    if (ns > 0 && (!bank || bank_stride < n)) {
+        set_error("sd_sched_affine_step: n_slots > 0 needs a bank with bank_stride >= n");
+        return SD_ERR_INVALID;
+    }
+    StepRows r = {};                                   // the used rows and columns; everything else stays 0
+    r.n_writes = nw;
+    for (int j = 0; j < nw; ++j) r.write_slot[j] = plan->write_slot[j];
+    bool finite = true, z_used = false;
+    for (int row = 0; row <= nw; ++row) {
+        const double* src = row == 0 ? plan->out : plan->write[row - 1];
+        double* dst = row == 0 ? r.out : r.write[row - 1];
+        for (int k = 0; k < 3 + ns; ++k) {
+            dst[k] = src[k];
+            finite = finite && std::isfinite(src[k]);
+        }
+        z_used = z_used || dst[2] != 0.0;
+    }
+    if (!finite) { set_error("sd_sched_affine_step: a coefficient of a used row is not finite"); return SD_ERR_INVALID; }
+    if (z_used && !noise) { set_error("sd_sched_affine_step: a non-zero noise coefficient needs a noise tensor"); return SD_ERR_INVALID; }
+    return launch_sched_affine_step(static_cast<const half_t*>(model_out), rows, static_cast<half_t*>(latents),
+                                    static_cast<const half_t*>(noise), bank, (long)bank_stride, (long)n, guidance_scale, r,
+                                    static_cast<hipStream_t>(stream));
+}
 int sd_images_to_uint8(const void* images_nchw_f16, void* out_nhwc_u8, int B, int C, int H, int W, void* stream) {
     if (!images_nchw_f16 || !out_nhwc_u8 || B < 0 || C < 1 || C > 4 || H < 1 || W < 1) {
         set_error("sd_images_to_uint8: bad arguments (1..4 channels)");

@@ -350,6 +350,18 @@ int launch_cfg_ddim(const half_t* eps2b, half_t* lat, long n, float g, float cx,
 // nullable.  The scheduler step of LCMScheduler in one launch.
 int launch_lcm_step(const half_t* model_out, int rows, half_t* lat, const half_t* noise, half_t* denoised, long n, float g,
                     float dx, float dout, float pden, float pnoise, hipStream_t s);
+// One scheduler step as up to three rows of fp64 coefficients over v = (x, m, z, h_0 .. h_3) (sd_step_plan, validated, with
+// the unused rows and columns zeroed): lat <- fp16(out . v), bank[write_slot[j]] <- fp32(write[j] . v), all from the old
+// values.  m as in launch_lcm_step; noise nullable when its column is zero; bank slots are `stride` floats apart.
+constexpr int STEP_SLOTS = 4, STEP_WRITES = 2, STEP_COLS = 3 + STEP_SLOTS;
+struct StepRows {
+    double out[STEP_COLS];
+    double write[STEP_WRITES][STEP_COLS];
+    int n_writes;
+    int write_slot[STEP_WRITES];
+};
+int launch_sched_affine_step(const half_t* model_out, int rows, half_t* lat, const half_t* noise, float* bank, long stride,
+                             long n, float g, const StepRows& p, hipStream_t s);
 // launch_cfg_linear on k_b * eps, k_b = 1 + phi (std(text_b) / std(eps_b) - 1) per sample b of n elements (guidance
 // rescale): a statistics launch and an update launch; factors [B] (nullable) receives k_b
 int launch_cfg_rescale_linear(const half_t* eps2b, half_t* lat, float* hist, int B, long n, float g, float phi, float cx,

@@ -379,6 +379,91 @@ __global__ __launch_bounds__(256) void lcm_step_kernel(const half_t* __restrict_
     }
 }
 
+// One step of a scheduler that is affine in (x, m, z) and up to four fp32 history tensors (EulerAncestral, DPM++ 2M SDE,
+// PNDM, UniPC: schedulers.py `affine_plan`), the guidance combine included:
+//   v = (x, m, z, h_0 .. h_3), m as in lcm_element;  x <- fp16(out . v);  h[write_slot[j]] <- fp32(write[j] . v)
+// Every row is a chain of fp64 FMAs over the columns whose coefficient is not 0 (the plan is a kernel argument: the
+// branches are uniform), rounded once: UniPC's collected predictor / corrector rows and the sigma-space x and m terms of
+// the first steps cancel, as lcm_element's do.  `use` has bit k set when column k is non-zero in some used row; the
+// other operands are never loaded, so an unwritten slot or an absent noise tensor may hold anything.  A thread loads all
+// its operands before it stores anything and no other thread touches its elements, so a slot may be read and written.
+// VEC: n % 8 == 0, stride % 4 == 0 and 16-byte aligned bases.
+template <int W>
+__device__ __forceinline__ void step_load(const half_t* __restrict__ p, float* o) {
+    if constexpr (W == 8) {
+        const h8 v = *reinterpret_cast<const h8*>(p);
+#pragma unroll
+        for (int j = 0; j < W; ++j) o[j] = (float)v[j];
+    } else {
+        o[0] = (float)p[0];
+    }
+}
+__device__ __forceinline__ double step_row(const double* c, const double* v) {
+    double acc = 0.0;
+#pragma unroll
+    for (int k = 0; k < STEP_COLS; ++k)
+        if (c[k] != 0.0) acc = __builtin_fma(c[k], v[k], acc);
+    return acc;
+}
+template <int ROWS, bool VEC>
+__global__ __launch_bounds__(256) void sched_affine_kernel(const half_t* __restrict__ mo, half_t* __restrict__ lat,
+                                                           const half_t* __restrict__ noise, float* __restrict__ bank,
+                                                           long stride, long n, float g, StepRows p, unsigned use) {
+    constexpr int W = VEC ? 8 : 1;
+    const long i = ((long)blockIdx.x * 256 + threadIdx.x) * W;
+    if (i >= n) return;
+    float x[W] = {}, u[W] = {}, t[W] = {}, z[W] = {}, h[STEP_SLOTS][W] = {};
+    if (use & 1u) step_load<W>(lat + i, x);
+    if (use & 2u) {
+        step_load<W>(mo + i, u);
+        if (ROWS == 2) step_load<W>(mo + n + i, t);
+    }
+    if (use & 4u) step_load<W>(noise + i, z);
+#pragma unroll
+    for (int k = 0; k < STEP_SLOTS; ++k) {
+        if (!(use & (8u << k))) continue;
+        const float* src = bank + k * stride + i;
+        if constexpr (VEC) {
+            const float4 a = *reinterpret_cast<const float4*>(src), b = *reinterpret_cast<const float4*>(src + 4);
+            h[k][0] = a.x; h[k][1] = a.y; h[k][2] = a.z; h[k][3] = a.w;
+            h[k][4] = b.x; h[k][5] = b.y; h[k][6] = b.z; h[k][7] = b.w;
+        } else {
+            h[k][0] = src[0];
+        }
+    }
+    half_t ox[W];
+    float ow[STEP_WRITES][W];
+#pragma unroll
+    for (int j = 0; j < W; ++j) {
+        const float m = ROWS == 2 ? (float)(half_t)__builtin_fmaf(g, t[j] - u[j], u[j]) : u[j];
+        double v[STEP_COLS] = {(double)x[j], (double)m, (double)z[j]};
+#pragma unroll
+        for (int k = 0; k < STEP_SLOTS; ++k) v[3 + k] = (double)h[k][j];
+        ox[j] = (half_t)step_row(p.out, v);
+#pragma unroll
+        for (int w = 0; w < STEP_WRITES; ++w) ow[w][j] = (float)step_row(p.write[w], v);
+    }
+    if constexpr (VEC) {
+        h8 o;
+#pragma unroll
+        for (int j = 0; j < W; ++j) o[j] = ox[j];
+        *reinterpret_cast<h8*>(lat + i) = o;
+    } else {
+        lat[i] = ox[0];
+    }
+#pragma unroll
+    for (int w = 0; w < STEP_WRITES; ++w) {
+        if (w >= p.n_writes) break;
+        float* dst = bank + p.write_slot[w] * stride + i;
+        if constexpr (VEC) {
+            *reinterpret_cast<float4*>(dst) = make_float4(ow[w][0], ow[w][1], ow[w][2], ow[w][3]);
+            *reinterpret_cast<float4*>(dst + 4) = make_float4(ow[w][4], ow[w][5], ow[w][6], ow[w][7]);
+        } else {
+            dst[0] = ow[w][0];
+        }
+    }
+}
+
 // ---- guidance rescale (Lin et al. 2023, section 3.4; diffusers rescale_noise_cfg) in front of the same linear update ----
 //   e = fp16(u + g (t - u));  k_b = 1 + phi (std(t_b) / std(e_b) - 1);  the update of cfg_linear_kernel on k_b e
 // std is per sample over all n elements; std(t) / std(e) = sqrt(M2(t) / M2(e)) (the ddof cancels), M2 = sum (x - mean)^2.
@@ -968,6 +1053,26 @@ int launch_lcm_step(const half_t* model_out, int rows, half_t* lat, const half_t
     if (rows == 2) { if (vec) SD_LCM_LAUNCH(2, true); else SD_LCM_LAUNCH(2, false); }
     else { if (vec) SD_LCM_LAUNCH(1, true); else SD_LCM_LAUNCH(1, false); }
 #undef SD_LCM_LAUNCH
+    SD_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+int launch_sched_affine_step(const half_t* model_out, int rows, half_t* lat, const half_t* noise, float* bank, long stride,
+                             long n, float g, const StepRows& p, hipStream_t s) {
+    unsigned use = 0;                                       // columns that some row reads
+    for (int k = 0; k < STEP_COLS; ++k) {
+        bool any = p.out[k] != 0.0;
+        for (int w = 0; w < p.n_writes; ++w) any = any || p.write[w][k] != 0.0;
+        if (any) use |= 1u << k;
+    }
+    const bool vec = n % 8 == 0 && stride % 4 == 0 &&
+                     ((reinterpret_cast<uintptr_t>(model_out) | reinterpret_cast<uintptr_t>(lat) |
+                       reinterpret_cast<uintptr_t>(noise) | reinterpret_cast<uintptr_t>(bank)) & 15) == 0;
+    const dim3 grid = grid1d(vec ? n / 8 : n);
+#define SD_STEP_LAUNCH(R, V) \
+    hipLaunchKernelGGL((sched_affine_kernel<R, V>), grid, dim3(256), 0, s, model_out, lat, noise, bank, stride, n, g, p, use)
+    if (rows == 2) { if (vec) SD_STEP_LAUNCH(2, true); else SD_STEP_LAUNCH(2, false); }
+    else { if (vec) SD_STEP_LAUNCH(1, true); else SD_STEP_LAUNCH(1, false); }
+#undef SD_STEP_LAUNCH
     SD_HIP_CHECK(hipGetLastError());
     return 0;
 }

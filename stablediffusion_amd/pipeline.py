@@ -592,9 +592,18 @@ class StableDiffusionUnifiedPipeline:
                 loop_gen.manual_seed(int(seed))
             else:
                 loop_gen.seed()
+        # euler_a, DPM++ 2M SDE, PNDM, UniPC: one device kernel per step over the latents and an fp32 history bank of this
+        # loop's own.  The stochastic two draw their noise here as their `step` does: from the global generator, once per
+        # step (the last included, whose noise coefficient is 0), so the device and the host loop consume the same stream
+        affine_step = (not fused_step and not lcm_step
+                       and self._affine_step_available(model, latents, num_channels_unet, guidance_rescale))
+        affine_bank = None
+        if affine_step and model.scheduler.affine_slots:
+            affine_bank = torch.empty((model.scheduler.affine_slots,) + tuple(latents.shape), device=latents.device,
+                                      dtype=torch.float32)
         fused_hist = None
         blend = None
-        if (fused_step or lcm_step) and self.is_inpaint:       # 4-channel inpainting: device-side blend after every step
+        if (fused_step or lcm_step or affine_step) and self.is_inpaint:       # 4-channel inpainting: device-side blend after every step
             f16 = lambda x: x.to(device=latents.device, dtype=torch.float16).contiguous()
             m1 = mask.chunk(2)[0] if self.do_classifier_free_guidance else mask
             blend = (f16(image_latents), f16(noise), f16(m1.expand(latents.shape[0], 1, *latents.shape[2:])))
@@ -609,6 +618,16 @@ class StableDiffusionUnifiedPipeline:
                 if lcm_step:
                     latents = self._lcm_iteration(model, latents, step_noise, t, prompt_embeds, cross_attention_kwargs,
                                                   added_cond_kwargs, guidance_scale, **cn_kwargs, **tc_kwargs)
+                    if blend is not None:
+                        a, b = (1.0, 0.0) if last else model.scheduler.add_noise_coefficients(timesteps_host[i + 1])
+                        self._device_inpaint_blend(model, latents, blend, a, b, with_noise=not last)
+                    continue
+                if affine_step:
+                    if getattr(model.scheduler, "affine_noise", False):
+                        step_noise = torch.randn(latents.shape, device=latents.device, dtype=latents.dtype)
+                    latents = self._affine_iteration(model, latents, affine_bank, step_noise, t, prompt_embeds,
+                                                     cross_attention_kwargs, added_cond_kwargs, guidance_scale,
+                                                     **cn_kwargs, **tc_kwargs)
                     if blend is not None:
                         a, b = (1.0, 0.0) if last else model.scheduler.add_noise_coefficients(timesteps_host[i + 1])
                         self._device_inpaint_blend(model, latents, blend, a, b, with_noise=not last)
@@ -769,6 +788,42 @@ class StableDiffusionUnifiedPipeline:
         if rc:
             raise RuntimeError(lib.sd_last_error().decode())
         model.scheduler.fused_commit()
+        return out
+
+    def _affine_step_available(self, model, latents, num_channels_unet=4, guidance_rescale=0.0) -> bool:
+        """The step of a scheduler with an `affine_plan` (euler_a, DPM++ 2M SDE, PNDM, UniPC) as one device kernel
+        (`sd_sched_affine_step`: guidance combine, update, history writes) on the HIP engine with fp16 CUDA latents, with
+        or without CFG.  9-channel inpainting UNets and guidance_rescale (a per-sample statistic) take scheduler.step."""
+        inpaint = getattr(self, "is_inpaint", False)            # (set by a call: a fresh pipeline has not inpainted)
+        return (hasattr(model.scheduler, "affine_plan") and (not inpaint or num_channels_unet == 4)
+                and not guidance_rescale > 0.0 and hasattr(model.base, "_lib") and latents.is_cuda
+                and latents.dtype == torch.float16)
+
+    def _affine_iteration(self, model, latents, bank, noise, t, prompt_embeds, cross_attention_kwargs, added_cond_kwargs,
+                          guidance_scale, **unet_kwargs):
+        import ctypes as C
+        from ._lib import step_plan
+        lib = model.base._lib
+        plan = model.scheduler.affine_plan(t)
+        latents = latents.contiguous()
+        if self.do_classifier_free_guidance:         # rows = [uncond ; text], from the un-duplicated latents
+            rows = 2
+            model_out = self._cfg_forward(model, latents, plan.in_scale, t, prompt_embeds, cross_attention_kwargs,
+                                          added_cond_kwargs, **unet_kwargs)
+        else:
+            rows = 1
+            model_out = model.base(model.scheduler.scale_model_input(latents, t), t, prompt_embeds,
+                                   cross_attention_kwargs=cross_attention_kwargs, added_cond_kwargs=added_cond_kwargs,
+                                   return_dict=False, **unet_kwargs)[0]
+        out = latents.clone()
+        noise_p = C.c_void_p(noise.contiguous().data_ptr()) if plan.needs_noise else None
+        bank_p = C.c_void_p(bank.data_ptr()) if bank is not None else None
+        rc = lib.sd_sched_affine_step(C.c_void_p(model_out.data_ptr()), rows, C.c_void_p(out.data_ptr()), noise_p, bank_p,
+                                      out.numel(), out.numel(), float(guidance_scale), C.byref(step_plan(plan)),
+                                      C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        if rc:
+            raise RuntimeError(lib.sd_last_error().decode())
+        model.scheduler.affine_commit()
         return out
 
     @staticmethod

@@ -30,6 +30,36 @@ class FusedPlan(SimpleNamespace):
     carries an x0 history.  Coefficients are float64 host values."""
 
 
+class AffinePlan(SimpleNamespace):
+    """One denoise step as rows of float64 coefficients over v = (x, m, z, h_0 .. h_3) -- the sample, the model output,
+    fresh noise and the fp32 history slots the scheduler keeps on the device (`sd_sched_affine_step`):
+        x <- out . v;   h[slot] <- row . v  for (slot, row) in writes, every row from the old values
+    `in_scale` multiplies the UNet input, `n_slots` is how many slots exist, `needs_noise` whether z has a non-zero
+    coefficient.  The scheduler's `affine_plan` runs the arithmetic of its `step` on unit vectors in place of tensors, so
+    a slot the step does not read has the coefficient 0 exactly; which slot holds which history entry is the scheduler's
+    bookkeeping (a ring rotates by renaming), advanced by `affine_commit` once the step has been applied."""
+
+
+AFFINE_COLS = 7
+
+
+def _unit(k):
+    v = np.zeros(AFFINE_COLS)
+    v[k] = 1.0
+    return v
+
+
+def _slot(k):
+    return _unit(3 + k)
+
+
+def _affine_plan(in_scale, n_slots, out, writes):
+    rows = [out] + [r for _, r in writes]
+    return AffinePlan(in_scale=float(in_scale), n_slots=int(n_slots), out=[float(c) for c in out],
+                      writes=[(int(k), [float(c) for c in r]) for k, r in writes],
+                      needs_noise=any(r[2] != 0.0 for r in rows))
+
+
 def _alphas_cumprod(T, beta_start, beta_end):
     betas = np.linspace(beta_start ** 0.5, beta_end ** 0.5, T, dtype=np.float64) ** 2
     return np.cumprod(1.0 - betas)
@@ -375,6 +405,25 @@ class EulerAncestralDiscreteScheduler(EulerDiscreteScheduler):
         prev = prev.to(sample.dtype)
         return (prev,) if not return_dict else SimpleNamespace(prev_sample=prev)
 
+    affine_slots = 0
+    affine_noise = True                       # `step` draws noise on every step: the device loop draws it the same way
+
+    def affine_plan(self, timestep=None):
+        """The arithmetic of `step` on (x, m, z): no history.  The last step has sigma_up = 0: no noise term."""
+        i = self._begin(timestep)
+        s, s_to = self.sigmas[i], self.sigmas[i + 1]
+        s_up = (s_to ** 2 * (s ** 2 - s_to ** 2) / s ** 2) ** 0.5
+        s_down = (s_to ** 2 - s_up ** 2) ** 0.5
+        x, eps, z = _unit(0), _unit(1), _unit(2)
+        if self.v_prediction:
+            a, b = self._v_terms(s)
+            eps = a * eps + b * x
+        out = x + eps * (s_down - s) + z * s_up
+        return _affine_plan(1.0 / (s * s + 1) ** 0.5, 0, out, [])
+
+    def affine_commit(self):
+        self._i += 1
+
 
 def _karras_sigmas(sig_all, n, rho=7.0):
     """diffusers `_convert_to_karras` on the flipped training sigmas: n values from sigma_max down to sigma_min."""
@@ -444,6 +493,38 @@ class DPMSolverSDEScheduler(DPMSolverMultistepScheduler):
         prev = out.to(sample.dtype)
         return (prev,) if not return_dict else SimpleNamespace(prev_sample=prev)
 
+    affine_slots = 1                          # the previous x0 prediction
+    affine_noise = True
+
+    def set_timesteps(self, num_inference_steps, device=None, **kw):
+        super().set_timesteps(num_inference_steps, device=device, **kw)
+        self._aff_hist = False                # affine_plan: slot 0 has been written
+
+    def affine_plan(self, timestep=None):
+        """The arithmetic of `step` on (x, m, z, previous x0).  The last step goes to sigma 0: its noise coefficient
+        is 0."""
+        i, n = self._begin(timestep), self.num_inference_steps
+        a0, sg0 = self._alpha_sigma(self.sigmas[i])
+        a_t, sg_t = self._alpha_sigma(self.sigmas[i + 1])
+        x, eps, z = _unit(0), _unit(1), _unit(2)
+        if self.v_prediction:
+            eps = a0 * eps + sg0 * x
+        m0 = (x - sg0 * eps) / a0
+        lam0 = np.log(a0) - np.log(sg0)
+        lam_t = np.log(a_t) - np.log(sg_t) if sg_t > 0 else np.inf
+        h = lam_t - lam0
+        e1, e2 = float(np.exp(-h)), float(1.0 - np.exp(-2.0 * h))
+        out = (sg_t / sg0 * e1) * x + (a_t * e2) * m0 + (sg_t * e2 ** 0.5) * z
+        if not (i == n - 1 or not self._aff_hist):
+            a1, sg1 = self._alpha_sigma(self.sigmas[i - 1])
+            r0 = (lam0 - (np.log(a1) - np.log(sg1))) / h
+            out = out + (0.5 * a_t * e2 / r0) * (m0 - _slot(0))
+        return _affine_plan(1.0, 1, out, [(0, m0)])
+
+    def affine_commit(self):
+        self._aff_hist = True
+        self._i += 1
+
 
 class PNDMScheduler(_Base):
     """PLMS (PNDM with skip_prk_steps=True, as every SD scheduler config has it): 4th-order linear multistep
@@ -463,6 +544,9 @@ class PNDMScheduler(_Base):
         self.ets = []
         self.counter = 0
         self.cur_sample = None
+        self._aff_ets = []                    # affine_plan: the slots of the kept epsilons, oldest first
+        self._aff_cur = None                  # ... and the slot of the saved sample
+        self._aff_next = None
 
     def _prev_sample(self, sample, t, prev_t, eps):
         a_t = self.ac[t]
@@ -502,6 +586,48 @@ class PNDMScheduler(_Base):
         self.counter += 1
         return (prev,) if not return_dict else SimpleNamespace(prev_sample=prev)
 
+    affine_slots = 3                          # three earlier epsilons; the saved sample borrows one on the first two steps
+
+    def affine_plan(self, timestep):
+        """The arithmetic of `step` on (x, m, kept epsilons, saved sample).  `step` keeps four epsilons, the newest being
+        this step's own: three slots hold the earlier ones and the new one overwrites the oldest (read in the same step).
+        The sample saved by the first step is read by the second only, before the ring needs its slot."""
+        t = int(timestep)
+        ratio = self.config.num_train_timesteps // self.num_inference_steps
+        prev_t = t - ratio
+        x, eps = _unit(0), _unit(1)
+        if self.v_prediction:
+            eps = self.ac[t] ** 0.5 * eps + (1 - self.ac[t]) ** 0.5 * x
+        slots, cur, writes = list(self._aff_ets), self._aff_cur, []
+        ets = [_slot(k) for k in slots]
+        if self.counter != 1:
+            ets = ets[-3:] + [eps]
+            free = [k for k in range(self.affine_slots) if k not in slots]
+            new = free[0] if free else slots.pop(0)
+            writes.append((new, eps))
+            slots.append(new)
+        else:
+            prev_t = t
+            t = t + ratio
+        if len(ets) == 1 and self.counter == 0:
+            cur = next(k for k in range(self.affine_slots) if k not in slots)
+            writes.append((cur, x))
+        elif len(ets) == 1 and self.counter == 1:
+            eps = (eps + ets[-1]) / 2
+            x, cur = _slot(cur), None
+        elif len(ets) == 2:
+            eps = (3 * ets[-1] - ets[-2]) / 2
+        elif len(ets) == 3:
+            eps = (23 * ets[-1] - 16 * ets[-2] + 5 * ets[-3]) / 12
+        else:
+            eps = (55 * ets[-1] - 59 * ets[-2] + 37 * ets[-3] - 9 * ets[-4]) / 24
+        self._aff_next = (slots, cur)
+        return _affine_plan(1.0, self.affine_slots, self._prev_sample(x, t, prev_t, eps), writes)
+
+    def affine_commit(self):
+        self._aff_ets, self._aff_cur = self._aff_next
+        self.counter += 1
+
 
 class UniPCMultistepScheduler(_Base):
     """UniPC (order 2, bh2, predict_x0, lower_order_final): UniP predictor + UniC corrector on the data
@@ -528,6 +654,9 @@ class UniPCMultistepScheduler(_Base):
         self.lower_order_nums = 0
         self.last_sample = None
         self.this_order = 1
+        self._aff_x0 = []                     # affine_plan: the slots (0, 1) of the x0 predictions, oldest first
+        self._aff_last = False                # ... and whether slot 2 holds the corrected sample
+        self._aff_next = None
 
     @staticmethod
     def _al(s):
@@ -546,9 +675,10 @@ class UniPCMultistepScheduler(_Base):
             h_phi_k = h_phi_k / hh - 1 / fact
         return h_phi_1, B_h, np.array(b)
 
-    def _predict(self, sample, order):
+    def _predict(self, sample, order, outputs=None):
         i = self._i
-        m0 = self.model_outputs[-1]
+        outputs = self.model_outputs if outputs is None else outputs
+        m0 = outputs[-1]
         a_t, sg_t, lam_t = self._al(self.sigmas[i + 1])
         a_0, sg_0, lam_0 = self._al(self.sigmas[i])
         h = lam_t - lam_0
@@ -557,13 +687,14 @@ class UniPCMultistepScheduler(_Base):
         if order == 2:
             _, _, lam_1 = self._al(self.sigmas[i - 1])
             rk = (lam_1 - lam_0) / h
-            d1 = (self.model_outputs[-2] - m0) / float(rk)
+            d1 = (outputs[-2] - m0) / float(rk)
             x_t = x_t - float(a_t * B_h * 0.5) * d1
         return x_t
 
-    def _correct(self, model_t, last_sample, order):
+    def _correct(self, model_t, last_sample, order, outputs=None):
         i = self._i
-        m0 = self.model_outputs[-1]
+        outputs = self.model_outputs if outputs is None else outputs
+        m0 = outputs[-1]
         a_t, sg_t, lam_t = self._al(self.sigmas[i])
         a_0, sg_0, lam_0 = self._al(self.sigmas[i - 1])
         h = lam_t - lam_0
@@ -577,7 +708,7 @@ class UniPCMultistepScheduler(_Base):
             rk = (lam_1 - lam_0) / h
             R = np.array([[1.0, 1.0], [rk, 1.0]])
             rhos = np.linalg.solve(R, b)
-            corr = float(rhos[0]) * ((self.model_outputs[-2] - m0) / float(rk))
+            corr = float(rhos[0]) * ((outputs[-2] - m0) / float(rk))
         return x_t - float(a_t * B_h) * (corr + float(rhos[-1]) * (model_t - m0))
 
     def step(self, model_output, timestep, sample, return_dict=False, **kw):
@@ -599,6 +730,39 @@ class UniPCMultistepScheduler(_Base):
             self.lower_order_nums += 1
         self._i += 1
         return (prev,) if not return_dict else SimpleNamespace(prev_sample=prev)
+
+    affine_slots = 3                          # two x0 predictions and the corrected sample
+
+    def affine_plan(self, timestep=None):
+        """The arithmetic of `step` on (x, m, the two kept x0 predictions, the corrected sample of the previous step):
+        `_correct` and `_predict` themselves, on unit vectors.  Every step writes its x0 over the older of the two
+        (which the corrector still reads) and its corrected sample to slot 2."""
+        i = self._begin(timestep)
+        n = len(self.timesteps)
+        x, eps = _unit(0), _unit(1)
+        a_i, sg_i, _ = self._al(self.sigmas[i])
+        if self.v_prediction:
+            eps = a_i * eps + sg_i * x
+        x0 = (x - sg_i * eps) / a_i
+        slots = list(self._aff_x0)
+        outputs = [None] * (self.solver_order - len(slots)) + [_slot(k) for k in slots]
+        if i > 0 and self._aff_last:
+            x = self._correct(x0, _slot(2), self.this_order, outputs)
+        outputs = outputs[1:] + [x0]
+        order = min(self.solver_order, n - i)                    # lower_order_final
+        this_order = min(order, self.lower_order_nums + 1)
+        out = self._predict(x, this_order, outputs)
+        free = [k for k in range(self.solver_order) if k not in slots]
+        new = free[0] if free else slots.pop(0)
+        self._aff_next = (slots + [new], this_order)
+        return _affine_plan(1.0, self.affine_slots, out, [(new, x0), (2, x)])
+
+    def affine_commit(self):
+        self._aff_x0, self.this_order = self._aff_next
+        self._aff_last = True
+        if self.lower_order_nums < self.solver_order:
+            self.lower_order_nums += 1
+        self._i += 1
 
 
 class LCMScheduler(_Base):
