@@ -512,6 +512,27 @@ int sd_op_ln_linear(const void* y1, const float* stat, int parts, int part_w, co
 int sd_op_ln_ffn_geglu(const void* x, const float* stat, int parts, int part_w, const void* ln_gamma, const void* ln_beta,
                        float ln_eps, const void* w1, const void* b1, const void* w2, const void* b2, void* y, int M, int C,
                        int* fused, void* stream);
+/* Pack-time fold of a linear `outer` (w_outer [O, J] f16, b_outer [O] f32) over the linear `inner` it follows
+ * (w_inner [J, K] f16, b_inner [J] f32) with only inner's residual r in between:
+ *   outer(inner(g) + r) = [g | r] W'^T + b',   W' = [W_o W_i | W_o]  ([O, K + J]),   b' = W_o b_i + b_o
+ * as the engine packs proj_out over the last ff.net.2 of a transformer.  w_folded [O, K + J] f16 (the product accumulated in
+ * fp32 and rounded once), b_folded [O] f32; (K + J) % 64 == 0.  The biases are rounded to f16 on the way in, as every
+ * weight of a model is. */
+int sd_op_fold_linear(const void* w_outer, const void* b_outer, const void* w_inner, const void* b_inner, void* w_folded,
+                      float* b_folded, int O, int J, int K, void* stream);
+/* The end of a transformer as the UNet runs it (the last block's feed-forward and proj_out):
+ *   y = x_in + proj_out(t3 + FF(LayerNorm(t3; gamma, beta, 1e-5)); w_po, b_po),   FF as in the feed-forward entry above
+ * x_in, t3, y [M, C] f16 (M rows = imgs images of M / imgs pixels); w1 [8C, C], w2 [C, 4C], w_po [C, C] f16; gamma, beta,
+ * b1, b2, b_po f32 (rounded to f16 on the way in, as a model's weights are).  Packed and run by the functions the UNet
+ * uses: proj_out folded over ff.net.2 into one GEMM with K = 5C, or -- for C = 320, where ffn.hip can take the
+ * feed-forward, and under SD_NO_POUT_FOLD=1 -- the feed-forward followed by proj_out (*fused = 1 when ffn.hip ran).
+ * gn_summaries (optional, with gn_rows): the GroupNorm summaries of y for 32 groups that the last launch leaves, (mean, M2)
+ * per image, tile of *gn_rows pixels and group: [imgs][M / imgs / *gn_rows][32][2] floats in a buffer of at least
+ * imgs * max(64, ceil(M / imgs / 64)) * 64 floats; *gn_rows = 0 when the launch left none. */
+int sd_op_ffn_geglu_proj_out(const void* x_in, const void* t3, const void* ln_gamma, const void* ln_beta, float ln_eps,
+                             const void* w1, const void* b1, const void* w2, const void* b2, const void* w_po,
+                             const void* b_po, void* y, float* gn_summaries, int* gn_rows, int M, int C, int imgs, int* fused,
+                             void* stream);
 /* Same operator, timed: `iters` back-to-back launches bracketed by HIP events on `stream`
  * (after two warm-up launches); used by tools/tune_igemm.py to pick tile variants per shape. */
 int sd_bench_conv2d(const void* x_nhwc, const void* w_oihw, void* y_nhwc, int N, int H, int W, int Cin,

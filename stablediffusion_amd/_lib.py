@@ -185,6 +185,9 @@ SIGNATURES = {
     "sd_op_linear_rowstats": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), _P]),
     "sd_op_ln_linear": (_I, [_P, _P, _I, _I, _P, _P, _F, _P, _P, _P, _I, _I, _I, _I, _I, _F, C.POINTER(_I), _P]),
     "sd_op_ln_ffn_geglu": (_I, [_P, _P, _I, _I, _P, _P, _F, _P, _P, _P, _P, _P, _I, _I, C.POINTER(_I), _P]),
+    "sd_op_fold_linear": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "sd_op_ffn_geglu_proj_out": (_I, [_P, _P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(_I), _I, _I, _I,
+                                      C.POINTER(_I), _P]),
     "sd_bench_conv2d": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(_F), _P]),
     "sd_op_groupnorm": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _P]),
     "sd_op_groupnorm_concat": (_I, [_P, _I, _I, _P, _P, _P, _I, _I, _I, _F, _I, _P]),

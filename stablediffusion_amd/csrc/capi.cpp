@@ -1458,4 +1458,90 @@ int sd_op_controlnet_cond_embed(sd_controlnet* cn, const void* image, int n, int
     });
 }
 
+int sd_op_fold_linear(const void* w_outer, const void* b_outer, const void* w_inner, const void* b_inner, void* w_folded,
+                      float* b_folded, int O, int J, int K, void* stream) {
+    if (!w_outer || !b_outer || !w_inner || !b_inner || !w_folded || !b_folded || O < 1 || J < 1 || K < 1 || (K + J) % 64 != 0) {
+        set_error("sd_op_fold_linear: bad arguments (K + J must be a multiple of 64)"); return SD_ERR_INVALID;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    SD_HIP_CHECK(hipStreamSynchronize(s));              // the pack helpers work on the null stream
+    WeightStore ws;
+    const int64_t so[2] = {O, J}, si[2] = {J, K}, sbo[1] = {O}, sbi[1] = {J};
+    ws.declare("o.weight", {O, J}); ws.declare("o.bias", {O});
+    ws.declare("i.weight", {J, K}); ws.declare("i.bias", {J});
+    int rc;
+    if ((rc = ws.set("o.weight", w_outer, so, 2, 0)) || (rc = ws.set("o.bias", b_outer, sbo, 1, 1)) ||
+        (rc = ws.set("i.weight", w_inner, si, 2, 0)) || (rc = ws.set("i.bias", b_inner, sbi, 1, 1))) return rc;
+    ConvW f;
+    if ((rc = ws.fold_linear("o", "i", &f))) return rc;
+    SD_HIP_CHECK(hipMemcpy(w_folded, f.w, (size_t)O * f.K * sizeof(half_t), hipMemcpyDeviceToDevice));
+    SD_HIP_CHECK(hipMemcpy(b_folded, f.bias, (size_t)O * sizeof(float), hipMemcpyDeviceToDevice));
+    SD_HIP_CHECK(hipDeviceSynchronize());
+    return SD_OK;
+}
+
+int sd_op_ffn_geglu_proj_out(const void* x_in, const void* t3, const void* ln_gamma, const void* ln_beta, float ln_eps,
+                             const void* w1, const void* b1, const void* w2, const void* b2, const void* w_po,
+                             const void* b_po, void* y, float* gn_summaries, int* gn_rows, int M, int C, int imgs, int* fused,
+                             void* stream) {
+    if (!x_in || !t3 || !ln_gamma || !ln_beta || !w1 || !b1 || !w2 || !b2 || !w_po || !b_po || !y || M < 1 || C < 64 ||
+        C % 64 != 0 || imgs < 1 || M % imgs != 0 || ln_eps != 1e-5f) {
+        set_error("sd_op_ffn_geglu_proj_out: bad arguments (C % 64, M % imgs, ln_eps = 1e-5: the transformer's)"); return SD_ERR_INVALID;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    SD_HIP_CHECK(hipStreamSynchronize(s));              // the pack helpers work on the null stream
+    const int G = 32;                                   // the UNet's GroupNorm groups
+    WeightStore ws;
+    const int64_t C8 = 8L * C, C4 = 4L * C;
+    const int64_t s1[2] = {C8, C}, s2[2] = {C, C4}, so[2] = {C, C}, sc[1] = {C}, s8[1] = {C8};
+    ws.declare("norm3.weight", {C}); ws.declare("norm3.bias", {C});
+    ws.declare("ff.net.0.proj.weight", {C8, C}); ws.declare("ff.net.0.proj.bias", {C8});
+    ws.declare("ff.net.2.weight", {C, C4}); ws.declare("ff.net.2.bias", {C});
+    ws.declare("proj_out.weight", {C, C}); ws.declare("proj_out.bias", {C});
+    int rc;
+    if ((rc = ws.set("norm3.weight", ln_gamma, sc, 1, 1)) || (rc = ws.set("norm3.bias", ln_beta, sc, 1, 1)) ||
+        (rc = ws.set("ff.net.0.proj.weight", w1, s1, 2, 0)) || (rc = ws.set("ff.net.0.proj.bias", b1, s8, 1, 1)) ||
+        (rc = ws.set("ff.net.2.weight", w2, s2, 2, 0)) || (rc = ws.set("ff.net.2.bias", b2, sc, 1, 1)) ||
+        (rc = ws.set("proj_out.weight", w_po, so, 2, 0)) || (rc = ws.set("proj_out.bias", b_po, sc, 1, 1))) return rc;
+    // packed as Encoder::pack_xformer packs the last block of a transformer
+    Xformer t;
+    t.C = C;
+    t.blocks.resize(1);
+    TBlock& b = t.blocks[0];
+    if ((rc = ws.pack_norm("norm3", &b.ln3)) || (rc = ws.pack_geglu("ff.net.0.proj", &b.ff1))) return rc;
+    b.fold = true;
+    if ((rc = ws.fold_ln(&b.ff1, b.ln3, 0, 1.0f)) || (rc = pack_xformer_tail(ws, "proj_out", "ff.net.2", &t, &b))) return rc;
+    SD_HIP_CHECK(hipDeviceSynchronize());
+    const long HW = M / imgs;
+    if (gn_summaries && (!gn_rows || !gn_wants_stats(HW, C, G))) {
+        set_error("sd_op_ffn_geglu_proj_out: summaries need gn_rows and a map the GroupNorm takes summaries for"); return SD_ERR_INVALID;
+    }
+    bool ran_fused = false;
+    GnStatBuf gb;
+    rc = run_op_on_arena(s, 0, nullptr, [&](Ctx& c) {
+        Arena& a = *c.arena;
+        RowStat st;
+        st.p = a.alloc_f(rowstat_floats(M, C));
+        st.parts = 1; st.width = C;
+        View t3v = xformer_tail_t3(a, t, M);
+        View nxt(a.alloc_h((long)M * C), C, C);
+        if (!c.dry) {
+            hipError_t e = hipMemcpy2DAsync(t3v.p, (size_t)t3v.ld * 2, t3, (size_t)C * 2, (size_t)C * 2, (size_t)M,
+                                            hipMemcpyDeviceToDevice, s);
+            if (e != hipSuccess) { set_error(hipGetErrorString(e)); c.err = SD_ERR_HIP; return; }
+            c.err = launch_row_stats(t3v.p, t3v.ld, st.p, M, C, s);
+        }
+        gb = GnStatBuf();
+        gb.buf = gn_summaries;
+        ConvFuse fo;
+        fo.gn_out = gn_summaries ? &gb : nullptr;
+        fo.gn_groups = G;
+        View x(const_cast<half_t*>(static_cast<const half_t*>(x_in)), C, C);
+        ran_fused = run_xformer_tail(c, t, t3v, st, View(), nxt, x, imgs, (int)HW, 1, View(static_cast<half_t*>(y), C, C), fo);
+    });
+    if (fused) *fused = ran_fused ? 1 : 0;
+    if (gn_rows) *gn_rows = gb.st.part ? (int)gb.st.rows : 0;
+    return rc;
+}
+
 }  // extern "C"

@@ -80,6 +80,8 @@ struct ConvFuse {
     int gn_in_silu = 0;
     // y = acc_scale * (x W^T) + bias_scale * bias + ...: the range-scaled VAE encoder (powers of two; VAE::run_encode)
     float acc_scale = 1.f, bias_scale = 1.f;
+    // tile hint of this launch (IGemmRequest::hint_variant / hint_splits): -1 = none
+    int tile_variant = -1, tile_splits = 0;
 };
 struct NormW {
     float* gamma = nullptr;
@@ -111,6 +113,10 @@ class WeightStore {
     // Fold LayerNorm `ln` (applied to the GEMM's input) into the packed linear `w`: W <- W diag(gamma)
     // (rows < rows_scaled additionally times row_scale), bias <- bias + W beta, w->wsum = row sums.
     int fold_ln(ConvW* w, const NormW& ln, int rows_scaled, float row_scale);
+    // Fold the linear (or 1x1 conv) `outer` over the linear `inner` it follows with nothing in between, as one packed
+    // linear on [inner's input | inner's residual]: W' = [W_o W_i | W_o] ([O][K_i + J]), b' = W_o b_i + b_o.  The product
+    // is accumulated in fp32 on the device and rounded to fp16 once; pack_conv's padding rules.
+    int fold_linear(const std::string& outer, const std::string& inner, ConvW* out);
     void free_raw();
     void* dmalloc(size_t bytes);                                // tracked device allocation
     int64_t packed_bytes() const { return packed_bytes_; }

@@ -256,9 +256,13 @@ __global__ __launch_bounds__(512) void ffn_fused_kernel(FfnParams p) {
 
 }  // namespace
 
-bool ffn_fused_supported(const FfnParams& p) {
+bool ffn_fused_width(int C, int hidden) {
     static const bool off = getenv("SD_NO_FFN_FUSE") != nullptr;
-    return !off && p.C == FF_C && p.hidden == 4 * FF_C && p.M % FF_BM == 0 && p.M / FF_BM >= 64 && p.ln_stat && p.ln_parts >= 1 &&
+    return !off && C == FF_C && hidden == 4 * FF_C;
+}
+
+bool ffn_fused_supported(const FfnParams& p) {
+    return ffn_fused_width(p.C, p.hidden) && p.M % FF_BM == 0 && p.M / FF_BM >= 64 && p.ln_stat && p.ln_parts >= 1 &&
            p.ln_parts <= kFfMaxLnParts && p.w1_rows >= 2 * p.hidden && p.w2_rows >= FF_C &&
            (long)p.M * p.ldx * 2 < (1L << 31) && p.b1 && p.b2 && p.wsum1;
 }

@@ -1288,10 +1288,14 @@ const TunedEntry kTuned[] = {
 // shape is in it, otherwise a rule distilled from the same measurements: 128x160 tiles whenever Cout is a multiple of
 // 160 (every UNet / VAE width is), 128x128 otherwise; narrow tiles for small, shallow problems; split-K until about two
 // blocks per CU (512) are in flight, keeping >= 12 K-slabs per slice.  Does not look at the statistics requests.
-void pick_tile(const IGemmParams& p, int* variant, int* splits) {
-    if (g_force_variant.load() >= 0) {
-        int v = g_force_variant.load();
-        *splits = g_force_splits.load() > 0 ? g_force_splits.load() : 1;
+// A per-launch hint (IGemmRequest::hint_variant) stands between the force override and the table: the caller knows a
+// measured choice for a problem the table does not hold.
+void pick_tile(const IGemmParams& p, int* variant, int* splits, int hint_variant = -1, int hint_splits = 0) {
+    const bool force = g_force_variant.load() >= 0;
+    if (force || valid_id(hint_variant)) {              // (a hint outside the table is no hint)
+        int v = force ? g_force_variant.load() : hint_variant;
+        const int sp = force ? g_force_splits.load() : hint_splits;
+        *splits = sp > 0 ? sp : 1;
         if (p.geglu && !(valid_id(v) && kVariants[v].geglu)) v = kGegluFallback;
         if (p.geglu || p.act) *splits = 1;
         if (valid_id(v) && is_halo(v) && !halo_supported(p)) v = kHaloFallback;
@@ -1331,6 +1335,16 @@ void pick_tile(const IGemmParams& p, int* variant, int* splits) {
 
 void igemm2_force(int variant, int splits) { g_force_variant = variant; g_force_splits = splits; }
 
+bool igemm2_tuned_pointwise(int M, int N, int K, int* variant, int* splits) {
+    for (const TunedEntry& e : kTuned)
+        if (e.M == M && e.N == N && e.K == K && e.ks == 1 && e.stride == 1 && e.up == 0 && !e.geglu) {
+            *variant = e.variant;
+            *splits = e.splits;
+            return true;
+        }
+    return false;
+}
+
 bool igemm2_supported(const IGemmParams& p) {
     const long x_bytes = (long)p.N * p.H * p.W * p.ldx * 2;
     const long wrows = ((long)p.Cout + kWeightRowPad - 1) / kWeightRowPad * kWeightRowPad;
@@ -1355,7 +1369,7 @@ IGemmPlan igemm2_plan(IGemmParams& p, const IGemmRequest& rq) {
     static const bool g3_auto = getenv("SD_IGEMM3") != nullptr;        // off by default: measured not faster (igemm3.hip)
     const bool forced = g_force_variant.load() >= 0;
     int v0, sp0;
-    pick_tile(p, &v0, &sp0);
+    pick_tile(p, &v0, &sp0, rq.hint_variant, rq.hint_splits);
     if (!valid_id(v0)) { set_error("igemm2: bad variant"); pl.kind = kKindBadVariant; return pl; }
     // The routes on top of the tile choice, for p as it stands (they read p.gnstat_out / p.rowstat_out through the
     // *_supported predicates, so they are taken again after each request that is granted)

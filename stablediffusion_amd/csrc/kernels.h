@@ -80,7 +80,12 @@ struct IGemmRequest {
     float* gnstat = nullptr;        // GroupNorm summaries of the output for gn_groups groups (IGemmParams::gnstat_out)
     int gn_groups = 0;
     bool no_workspace = false;      // no split-K workspace will be passed: the launch runs unsplit
+    // Tile hint of this launch: taken ahead of the tuned table (behind sd_igemm_force), with the force override's
+    // validity fallbacks; -1 = none, the plan as without the field.  hint_splits < 1 runs unsplit.
+    int hint_variant = -1, hint_splits = 0;
 };
+// The tuned table's row for a plain pointwise problem (ks 1, stride 1, no upsample, no GEGLU), if it has one.
+bool igemm2_tuned_pointwise(int M, int N, int K, int* variant, int* splits);
 // How one launch runs, decided once (igemm2_plan) and handed to launch_igemm2.
 constexpr int kKindPgemmGeglu = 100;    // geglu_persist_kernel (pgemm.hip)
 constexpr int kKindIgemm1 = -1;         // not an LDS-DMA problem (!igemm2_supported): launch_igemm
@@ -141,6 +146,8 @@ struct FfnParams {
     int ln_part_w;                      // columns per ln_stat part (IGemmParams::ln_part_w)
 };
 bool ffn_fused_supported(const FfnParams& p);
+// The part of that answer known at pack time: the widths the kernel is built for (and SD_NO_FFN_FUSE unset).
+bool ffn_fused_width(int C, int hidden);
 int launch_ffn_fused(const FfnParams& p, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------
@@ -182,6 +189,11 @@ int launch_row_stats(const half_t* x, long ldx, float* stat, long rows, int C, h
 // bias_in may be null (no bias); bias / wsum are fp32 arrays of `rows` entries.
 int launch_ln_fold(half_t* w, long K, int rows, const float* gamma, const float* beta, const float* bias_in,
                    float* bias, float* wsum, int rows_scaled, float row_scale, hipStream_t s);
+
+// Pack-time fold of an outer linear wo [O][J] over an inner one wi [J][K] (both fp16, row-major) into the rows of a
+// packed matrix wp [>= O rows][Kp >= K + J]: wp[n] = [fp16(wo[n] wi) | wo[n]] (fp32 accumulation, one rounding); columns
+// from K + J up are left as they are (the pack's zero padding).
+int launch_fold_linear(const half_t* wo, const half_t* wi, half_t* wp, int O, int J, int K, long Kp, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------
 // Attention (attention.hip): out = softmax(q k^T / sqrt(d)) v per (batch, head)

@@ -720,6 +720,25 @@ __global__ __launch_bounds__(256) void ln_fold_kernel(half_t* __restrict__ w, lo
 }
 
 
+// Pack-time fold of an outer linear over an inner one (launch_fold_linear), one thread per output element:
+// wp[n][k] = fp16(sum_j wo[n][j] wi[j][k]) for k < K, wo[n][k - K] for K <= k < K + J.  A product of two fp16 values is
+// exact in fp32 and the sum is compensated (Kahan), so the one rounding to fp16 is the only error of note.
+__global__ __launch_bounds__(256) void fold_linear_kernel(const half_t* __restrict__ wo, const half_t* __restrict__ wi,
+                                                          half_t* __restrict__ wp, int J, int K, long Kp) {
+    const long k = (long)blockIdx.x * 256 + threadIdx.x;
+    const long n = blockIdx.y;
+    if (k >= (long)K + J) return;
+    if (k >= K) { wp[n * Kp + k] = wo[n * J + (k - K)]; return; }
+    float s = 0.f, c = 0.f;
+    for (int j = 0; j < J; ++j) {
+        const float y = fmaf((float)wo[n * J + j], (float)wi[(long)j * K + k], -c);
+        const float t = s + y;
+        c = (t - s) - y;
+        s = t;
+    }
+    wp[n * Kp + k] = (half_t)s;
+}
+
 // ---------------------------------------------------------------------------------------------------
 // conv_out: 3x3 / stride 1 / pad 1 convolution to a handful of output channels (UNet 320 -> 4, VAE decoder
 // 128 -> 3; diffusers `conv_out` under sd_unified_pipeline.py:475-482 / :523), NHWC f16 in, NCHW f16 out.
@@ -1154,6 +1173,12 @@ int launch_ln_fold(half_t* w, long K, int rows, const float* gamma, const float*
     if (rows <= 0) return 0;
     hipLaunchKernelGGL(ln_fold_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, w, K, rows, gamma, beta, bias_in, bias, wsum,
                        rows_scaled, row_scale);
+    SD_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+int launch_fold_linear(const half_t* wo, const half_t* wi, half_t* wp, int O, int J, int K, long Kp, hipStream_t s) {
+    if (O <= 0 || J <= 0 || K <= 0 || O > 65535 || Kp < (long)K + J) { set_error("fold_linear: bad shape"); return 1; }
+    hipLaunchKernelGGL(fold_linear_kernel, dim3((unsigned)((K + J + 255) / 256), (unsigned)O), dim3(256), 0, s, wo, wi, wp, J, K, Kp);
     SD_HIP_CHECK(hipGetLastError());
     return 0;
 }

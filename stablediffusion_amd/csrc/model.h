@@ -28,6 +28,10 @@ struct Xformer {
     ConvW pin, pout;
     std::vector<TBlock> blocks;
     int C = 0, heads = 1;
+    // proj_out folded over the last block's ff.net.2 (pack_xformer_tail): ff2p = [W_po W_ff2 | W_po] is packed INSTEAD of
+    // that block's ff2 and of pout, and run_xformer_tail issues one GEMM over [g | t3] where two ran.
+    bool pout_fold = false;
+    ConvW ff2p;
 };
 struct VaeAttn {
     NormW gn;
@@ -59,6 +63,19 @@ void run_resnet(Ctx& c, const Resnet& r, View x, int N, int H, int W, View out, 
 void run_xformer(Ctx& c, const Xformer& t, View x, int N, int H, int W, View out, int G, View text_kv, int L,
                  const GnStatBuf* x_stats = nullptr, GnStatBuf** out_stats = nullptr, GnStatBuf* out_buf = nullptr,
                  int out_groups = 0, const CfgShare* share = nullptr);
+
+// The end of a transformer, from the residual stream after attn2 (t3, row statistics st_t3 when the LayerNorms are
+// folded) to its output: out = proj_out(t3 + ff(norm3(t3))) + x, with `fo` (the GroupNorm-summary request) on the launch
+// that writes `out`.  Packed by pack_xformer_tail (after the last block's ff1), in one of two forms:
+//   folded (t.pout_fold): t3 is the view xformer_tail_t3 returned, the last C columns of an [M, hidden + C] buffer; the
+//     GEGLU projection writes g into the columns in front and one GEMM with K = hidden + C does ff.net.2, its residual
+//     and proj_out, on the tile the tuned table holds for the unfolded ff.net.2 of the same M;
+//   unfolded: the feed-forward (one fused launch where ffn.hip takes it, else two GEMMs) into nxt, then proj_out.
+// n: scratch [M, C] for the unfolded LayerNorm (SD_NO_LN_FOLD), nxt: scratch [M, C].  Returns whether ffn.hip ran.
+int pack_xformer_tail(WeightStore& ws, const std::string& proj_out, const std::string& ff2, Xformer* x, TBlock* last);
+View xformer_tail_t3(Arena& a, const Xformer& t, long M);
+bool run_xformer_tail(Ctx& c, const Xformer& t, View t3, const RowStat& st_t3, View n, View nxt, View x, int N, int H, int W,
+                      View out, const ConvFuse& fo);
 
 struct UNet;
 

@@ -270,6 +270,37 @@ int WeightStore::fold_ln(ConvW* w, const NormW& ln, int rows_scaled, float row_s
     return 0;
 }
 
+int WeightStore::fold_linear(const std::string& outer, const std::string& inner, ConvW* out) {
+    const RawTensor* wo = raw(outer + ".weight");
+    const RawTensor* wi = raw(inner + ".weight");
+    if (!wo || !wi) { set_error("missing weight: " + (wo ? inner : outer) + ".weight"); return 2; }
+    for (size_t d = 2; d < wo->shape.size(); ++d)
+        if (wo->shape[d] != 1) { set_error("fold_linear: " + outer + " is not pointwise"); return 1; }
+    if (wi->shape.size() != 2 || wo->shape.size() < 2 || wo->shape[1] != wi->shape[0]) {
+        set_error("fold_linear: " + outer + " does not take the output of " + inner); return 1;
+    }
+    const int O = (int)wo->shape[0], J = (int)wo->shape[1], Ki = (int)wi->shape[1];
+    const long K = round_up((long)Ki + J, 64);
+    const long rows = round_up(O, kWeightRowPad);
+    out->cin = Ki + J; out->cout = O; out->ks = 1; out->K = K;
+    out->w = static_cast<half_t*>(dmalloc((size_t)rows * K * sizeof(half_t)));
+    if (!out->w) { set_error("hipMalloc failed (weights)"); return 3; }
+    SD_HIP_CHECK(hipMemsetAsync(out->w, 0, (size_t)rows * K * sizeof(half_t), 0));
+    int rc = launch_fold_linear(wo->dev, wi->dev, out->w, O, J, Ki, K, 0);
+    if (rc) return rc;
+    std::vector<float> wof, bi, bo, b((size_t)O);
+    if ((rc = host_floats(outer + ".weight", &wof))) return rc;
+    if ((rc = host_floats(inner + ".bias", &bi))) return rc;
+    if ((rc = host_floats(outer + ".bias", &bo))) return rc;
+    if ((long)bi.size() != J || (long)bo.size() != O) { set_error("fold_linear: bias length mismatch"); return 1; }
+    for (int n = 0; n < O; ++n) {
+        double acc = bo[(size_t)n];
+        for (int j = 0; j < J; ++j) acc += (double)wof[(size_t)n * J + j] * bi[(size_t)j];
+        b[(size_t)n] = (float)acc;
+    }
+    return upload_bias(this, b, O, &out->bias);
+}
+
 // ---------------------------------------------------------------------------------------- profiler
 namespace {
 // The profiler is process-wide (bench.py brackets one forward at a time); the record list is guarded so that
@@ -371,8 +402,9 @@ void op_conv(Ctx& c, const ConvW& w, View x, int N, int H, int W, View y, int st
     }
     if (fuse && (fuse->acc_scale != 1.f || fuse->bias_scale != 1.f)) { p.acc_scale = fuse->acc_scale; p.bias_scale = fuse->bias_scale; }
     // one plan per launch: the tile, what the epilogue leaves of the requested statistics, the workspace, the name
-    const IGemmPlan plan = igemm2_plan(p, IGemmRequest{stat_out ? stat_out->p : nullptr, gn_out ? gn_out->buf : nullptr,
-                                                       fuse ? fuse->gn_groups : 0});
+    IGemmRequest rq{stat_out ? stat_out->p : nullptr, gn_out ? gn_out->buf : nullptr, fuse ? fuse->gn_groups : 0};
+    if (fuse) { rq.hint_variant = fuse->tile_variant; rq.hint_splits = fuse->tile_splits; }
+    const IGemmPlan plan = igemm2_plan(p, rq);
     const bool v2 = plan.kind != kKindIgemm1;
     if ((p.acc_scale != 1.f || p.bias_scale != 1.f) && !plan.scales_ok) { set_error("op_conv: output scaling needs the LDS-DMA kernels (not GEGLU / weight-stationary)"); c.err = 1; return; }
     if (ln_in && !v2) { set_error("op_conv: the LayerNorm fold needs the LDS-DMA kernel"); c.err = 1; return; }
@@ -489,7 +521,7 @@ bool op_ffn_fused(Ctx& c, const ConvW& ff1, const ConvW& ff2, View x, const RowS
     p.M = (int)M; p.C = (int)ff1.K; p.hidden = (int)ff2.K;
     if (c.dry) p.ln_stat = reinterpret_cast<const float*>(8);          // planning pass: only "is set" matters
     if (ff1.ks != 1 || ff2.ks != 1 || ff2.cout != ff1.K || ff1.cout != 2 * ff2.K || x.C != p.C || !ff1.wsum) return false;
-    if (c.dry ? !(p.C == 320 && p.hidden == 1280 && M % 128 == 0 && M / 128 >= 64 && !getenv("SD_NO_FFN_FUSE")) : !ffn_fused_supported(p))
+    if (c.dry ? !(ffn_fused_width(p.C, p.hidden) && M % 128 == 0 && M / 128 >= 64) : !ffn_fused_supported(p))
         return false;
     if (c.dry || c.err) return true;
     prof_open(c.stream, "ffn_fused_kernel", 2.0 * M * ((double)ff1.cout * ff1.K + (double)ff2.cout * ff2.K),

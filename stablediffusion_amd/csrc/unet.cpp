@@ -165,7 +165,7 @@ int Encoder::pack_xformer(const std::string& p, Xformer* x, int heads, int depth
     int rc;
     if ((rc = ws.pack_norm(p + ".norm", &x->gn))) return rc;
     if ((rc = ws.pack_conv(p + ".proj_in", &x->pin))) return rc;
-    if ((rc = ws.pack_conv(p + ".proj_out", &x->pout))) return rc;
+    if (depth == 0 && (rc = ws.pack_conv(p + ".proj_out", &x->pout))) return rc;
     x->C = x->pin.cout;
     x->heads = heads;
     x->blocks.resize((size_t)depth);
@@ -191,7 +191,8 @@ int Encoder::pack_xformer(const std::string& p, Xformer* x, int heads, int depth
         kv_keys.push_back(q + ".attn2.to_v.weight");
         if ((rc = ws.pack_conv(q + ".attn2.to_out.0", &b.out2))) return rc;
         if ((rc = ws.pack_geglu(q + ".ff.net.0.proj", &b.ff1))) return rc;
-        if ((rc = ws.pack_conv(q + ".ff.net.2", &b.ff2))) return rc;
+        const bool last = d + 1 == depth;
+        if (!last && (rc = ws.pack_conv(q + ".ff.net.2", &b.ff2))) return rc;
         // The three LayerNorms feed one linear each (norm1 -> q|k|v, norm2 -> attn2.to_q, norm3 -> the GEGLU
         // projection): their affine is folded into those weights here and their statistics come out of the
         // epilogue of the GEMM that produces the normalised tensor, so a forward launches no LayerNorm
@@ -206,8 +207,28 @@ int Encoder::pack_xformer(const std::string& p, Xformer* x, int heads, int depth
             if ((rc = launch_scale_f16(b.qkv.w, (long)x->C * b.qkv.K, qs, 0))) return rc;
             if ((rc = launch_scale_f16(b.q2.w, (long)x->C * b.q2.K, qs, 0))) return rc;
         }
+        if (last && (rc = pack_xformer_tail(ws, p + ".proj_out", q + ".ff.net.2", x, &b))) return rc;
     }
     return 0;
+}
+
+// proj_out follows the last block's ff.net.2 with nothing but that linear's residual in between:
+//     out = proj_out(ff2(g) + b_ff2 + t3) + b_po + x = [g | t3] [W_po W_ff2 | W_po]^T + (W_po b_ff2 + b_po) + x
+// so the two launches become one with K = hidden + C: same FLOPs and weight bytes, one launch and one round trip of an
+// [M, C] tensor (and its fp16 rounding) less.  Kept as two launches where ffn.hip can take the feed-forward (its kernel
+// has no proj_out slabs), with the LayerNorm fold off, and under SD_NO_POUT_FOLD=1 (the A/B switch).
+int pack_xformer_tail(WeightStore& ws, const std::string& proj_out, const std::string& ff2, Xformer* x, TBlock* last) {
+    static const bool off = getenv("SD_NO_POUT_FOLD") != nullptr;
+    const RawTensor* w2 = ws.raw(ff2 + ".weight");
+    const RawTensor* wo = ws.raw(proj_out + ".weight");
+    const int C = x->C;
+    const long hidden = w2 && w2->shape.size() == 2 ? w2->shape[1] : 0;
+    x->pout_fold = !off && last->fold && w2 && wo && hidden > 0 && w2->shape[0] == C && wo->shape[0] == C && wo->shape[1] == C &&
+                   (hidden + C) % 64 == 0 && last->ff1.cout == 2 * hidden && !ffn_fused_width(C, (int)hidden);
+    if (x->pout_fold) return ws.fold_linear(proj_out, ff2, &x->ff2p);
+    int rc;
+    if ((rc = ws.pack_conv(ff2, &last->ff2))) return rc;
+    return ws.pack_conv(proj_out, &x->pout);
 }
 
 int Encoder::pack_encoder(std::vector<std::string>* tw, std::vector<std::string>* tb) {
@@ -415,6 +436,9 @@ void run_xformer(Ctx& c, const Xformer& t, View x, int N, int H, int W, View out
     f_ln1.ln_in = &st_cur; f_ln2.ln_in = &st_t2; f_ln3.ln_in = &st_t3;
     f_ln1.ln_eps = f_ln2.ln_eps = f_ln3.ln_eps = 1e-5f;
     op_conv(c, t.pin, hn, Np, H, W, cur, 1, 0, nullptr, 0, nullptr, 0, -1, 0, fold ? &f_cur : nullptr);
+    ConvFuse fo;                                               // the launch that writes `out`
+    fo.gn_out = (out_stats && gn_wants_stats(T, C, G)) ? (out_buf ? out_buf : ctx_gnbuf(c)) : nullptr;
+    fo.gn_groups = out_groups > 0 ? out_groups : G;
     for (size_t bi = 0; bi < t.blocks.size(); ++bi) {
         const TBlock& b = t.blocks[bi];
         const bool more = bi + 1 < t.blocks.size();
@@ -463,12 +487,11 @@ void run_xformer(Ctx& c, const Xformer& t, View x, int N, int H, int W, View out
                             c.ip_kv.slice(b.ip_kv_off + C, C), att, N, T, L, c.ip_T, t.heads, d, c.ip_scale);
         else
             op_attention(c, q, text_kv.slice(b.kv_off, C), text_kv.slice(b.kv_off + C, C), att, N, T, L, t.heads, d, 0, 1);
-        View t3(a.alloc_h(M * C), C, C);
+        View t3 = more ? View(a.alloc_h(M * C), C, C) : xformer_tail_t3(a, t, M);
         op_conv(c, b.out2, att, N, H, W, t3, 1, 0, nullptr, 0, &t2, 0, -1, 0, fold ? &f_t3 : nullptr);
-        // norm3 -> GEGLU feed-forward -> + residual: one launch with the 4C-wide hidden tensor kept on the CU where the
-        // problem fits it (the 64 x 64 level: ffn.hip), otherwise the projection with its GEGLU epilogue and the output
-        // linear with its residual epilogue
-        if (!(fold && !more && op_ffn_fused(c, b.ff1, b.ff2, t3, st_t3, 1e-5f, M, nxt))) {
+        if (more) {
+            // norm3 -> GEGLU feed-forward -> + residual: the projection with its GEGLU epilogue and the output linear with
+            // its residual epilogue
             View g(a.alloc_h(M * 4 * C), 4 * C, 4 * C);
             if (fold) {
                 op_conv(c, b.ff1, t3, N, H, W, g, 1, 0, nullptr, 0, nullptr, 1, -1, 0, &f_ln3);
@@ -476,17 +499,65 @@ void run_xformer(Ctx& c, const Xformer& t, View x, int N, int H, int W, View out
                 op_layernorm(c, b.ln3, t3, n, M, 1e-5f);
                 op_conv(c, b.ff1, n, N, H, W, g, 1, 0, nullptr, 0, nullptr, 1);
             }
-            op_conv(c, b.ff2, g, N, H, W, nxt, 1, 0, nullptr, 0, &t3, 0, -1, 0, (fold && more) ? &f_cur : nullptr);
+            op_conv(c, b.ff2, g, N, H, W, nxt, 1, 0, nullptr, 0, &t3, 0, -1, 0, fold ? &f_cur : nullptr);
+        } else {
+            // the last block: its feed-forward and proj_out
+            run_xformer_tail(c, t, t3, st_t3, n, nxt, x, N, H, W, out, fo);
         }
         a.release(mb);
         View tmp = cur; cur = nxt; nxt = tmp;
     }
-    ConvFuse fo;
-    fo.gn_out = (out_stats && gn_wants_stats(T, C, G)) ? (out_buf ? out_buf : ctx_gnbuf(c)) : nullptr;
-    fo.gn_groups = out_groups > 0 ? out_groups : G;
-    op_conv(c, t.pout, cur, N, H, W, out, 1, 0, nullptr, 0, &x, 0, -1, 0, &fo);
+    if (t.blocks.empty()) op_conv(c, t.pout, cur, N, H, W, out, 1, 0, nullptr, 0, &x, 0, -1, 0, &fo);
     if (out_stats) *out_stats = fo.gn_out;
     a.release(mk);
+}
+
+View xformer_tail_t3(Arena& a, const Xformer& t, long M) {
+    if (!t.pout_fold) return View(a.alloc_h(M * t.C), t.C, t.C);
+    const long ld = t.ff2p.cin;             // hidden + C
+    return View(a.alloc_h(M * ld) + (ld - t.C), ld, t.C);
+}
+
+bool run_xformer_tail(Ctx& c, const Xformer& t, View t3, const RowStat& st_t3, View n, View nxt, View x, int N, int H, int W,
+                      View out, const ConvFuse& fo) {
+    Arena& a = *c.arena;
+    const TBlock& b = t.blocks.back();
+    const int C = t.C;
+    const long M = (long)N * H * W;
+    const int hidden = b.ff1.cout / 2;
+    ConvFuse f_ln3;
+    f_ln3.ln_in = &st_t3; f_ln3.ln_eps = 1e-5f;
+    if (t.pout_fold) {
+        if (t3.ld != hidden + C || t.ff2p.cin != hidden + C) { set_error("run_xformer_tail: t3 is not xformer_tail_t3's view"); c.err = 1; return false; }
+        View gt(t3.p - hidden, t3.ld, hidden + C);          // [g | t3]
+        op_conv(c, b.ff1, t3, N, H, W, gt.slice(0, hidden), 1, 0, nullptr, 0, nullptr, 1, -1, 0, &f_ln3);
+        // K = hidden + C is in no tuned table: the tile measured for ff.net.2 alone (same M and N, K = hidden) is the
+        // nearest measured answer, and keeps the table's split-K where it has one
+        ConvFuse f = fo;
+        int v, sp;
+        if (igemm2_tuned_pointwise((int)M, C, hidden, &v, &sp)) { f.tile_variant = v; f.tile_splits = sp; }
+        op_conv(c, t.ff2p, gt, N, H, W, out, 1, 0, nullptr, 0, &x, 0, -1, 0, &f);
+        return false;
+    }
+    const bool fold = b.fold;
+    // norm3 -> GEGLU feed-forward -> + residual: one launch with the 4C-wide hidden tensor kept on the CU where the
+    // problem fits it (the 64 x 64 level: ffn.hip), otherwise the projection with its GEGLU epilogue and the output
+    // linear with its residual epilogue
+    const bool fused = fold && op_ffn_fused(c, b.ff1, b.ff2, t3, st_t3, 1e-5f, M, nxt);
+    if (!fused) {
+        const size_t mk = a.mark();
+        View g(a.alloc_h(M * hidden), hidden, hidden);
+        if (fold) {
+            op_conv(c, b.ff1, t3, N, H, W, g, 1, 0, nullptr, 0, nullptr, 1, -1, 0, &f_ln3);
+        } else {
+            op_layernorm(c, b.ln3, t3, n, M, 1e-5f);
+            op_conv(c, b.ff1, n, N, H, W, g, 1, 0, nullptr, 0, nullptr, 1);
+        }
+        op_conv(c, b.ff2, g, N, H, W, nxt, 1, 0, nullptr, 0, &t3, 0, -1, 0, nullptr);
+        a.release(mk);
+    }
+    op_conv(c, t.pout, nxt, N, H, W, out, 1, 0, nullptr, 0, &x, 0, -1, 0, &fo);
+    return fused;
 }
 
 // ----------------------------------------------------------------------------------------- forward
