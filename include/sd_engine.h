@@ -60,7 +60,8 @@ typedef struct sd_unet_config {
     int32_t flip_sin_to_cos;
     float   freq_shift;
     int32_t addition_time_embed_dim;               /* 0 = no text_time conditioning (SD1.5) */
-    int32_t projection_class_embeddings_input_dim; /* SDXL: 2816 */
+    int32_t projection_class_embeddings_input_dim; /* SDXL: 2816; SDXL refiner: 2560 */
+    int32_t num_time_ids;                          /* columns of add_time_ids: 0 = 6 (SDXL base); the refiner has 5; 1..8 */
     int32_t time_cond_proj_dim;                    /* 0 = no time_embedding.cond_proj; LCM-distilled UNets: 256; <= 1024 */
 } sd_unet_config;
 
@@ -121,7 +122,9 @@ int sd_unet_finalize(sd_unet* u);
  *   timesteps  [B] f32 (device)     `t` broadcast to the batch
  *   ehs        [B,L,D] f16          prompt_embeds
  *   add_text   [B,P] f16 or NULL    added_cond_kwargs["text_embeds"]  (SDXL, :430-433)
- *   add_time_ids [B,6] f32 or NULL  added_cond_kwargs["time_ids"]
+ *   add_time_ids [B,n] f32 or NULL  added_cond_kwargs["time_ids"]; n = num_time_ids (0 in the configuration: 6).
+ *                                   The pooled width is P = projection_class_embeddings_input_dim - n * addition_time_embed_dim.
+ * Every forward entry below (_ex, _tc, _cn, _cfg) and the graph replay's staging copy take add_time_ids as [B,n].
  *   out        [B,Cout,H,W] f16     noise_pred
  */
 int sd_unet_forward(sd_unet* u, const void* sample, const float* timesteps, const void* ehs,
@@ -188,6 +191,7 @@ int sd_unet_forward_cn(sd_unet* u, const void* sample, const float* timesteps, c
  * sd_cfg_duplicate(latents, in_scale) followed by sd_unet_forward(_ex) returns, negative half first.
  *   latents   [B,C,H,W] f16        timesteps [B] f32 (both halves share them)
  *   ehs       [2B,ehs_len,ctx] f16  add_text / add_time_ids / image_embeds: 2B rows, as sd_unet_forward_ex takes them
+ *                                   (add_time_ids [2B,num_time_ids]; with text_time the duplicate path runs)
  *   in_scale  the scheduler's scale_model_input factor, applied as fp16(latents * in_scale)
  *   out       [2B,Cout,H,W] f16
  * With share != 0 and a topology for which sd_unet_cfg_share answers 1, everything in front of the first cross-attention
@@ -557,6 +561,14 @@ int sd_bench_groupnorm(const void* x_nhwc, const void* gamma, const void* beta, 
  * (flip_sin_to_cos = 1) or [sin | cos], f_i = exp(-ln(1e4) i / (dim/2 - freq_shift)).  t, out: f32 device. */
 int sd_op_timestep_sinusoid(const float* t, float* out, int count, int dim, int flip_sin_to_cos, float freq_shift,
                             void* stream);
+/* The input of add_embedding.linear_1 (text_time conditioning), one launch:
+ *   out[b, :P]             = f32(add_text[b, :])
+ *   out[b, P + j*ad + i]   = sd_op_timestep_sinusoid(ids[b, j], dim = ad)[i]      j < n_ids
+ * add_text [B,P] f16, ids [B,n_ids] f32, out [B, P + n_ids*ad] f32 (all device).  The sinusoid is the device function
+ * sd_op_timestep_sinusoid runs: the bits are equal.  SD_ERR_INVALID (nothing is launched): n_ids outside 1..8, odd or
+ * non-positive ad, P <= 0, B < 1, a NULL pointer. */
+int sd_op_text_time_input(const void* add_text, const float* ids, float* out, int B, int P, int ad, int n_ids,
+                          int flip_sin_to_cos, float freq_shift, void* stream);
 /* The input of a guidance-embedded UNet's time embedding (TimestepEmbedding with cond_proj_dim), one launch:
  *   out[b, j] = sinusoid(t_b)[j] + sum_k W[j, k] cond[b, k]
  * t [B], cond [B, cond_dim], out [B, dim] f32; w_f16 [dim, cond_dim] f16 row-major (no bias); fp32 accumulation, the sum

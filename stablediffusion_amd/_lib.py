@@ -37,6 +37,7 @@ class SdUNetConfig(C.Structure):
         ("freq_shift", C.c_float),
         ("addition_time_embed_dim", C.c_int32),
         ("projection_class_embeddings_input_dim", C.c_int32),
+        ("num_time_ids", C.c_int32),
         ("time_cond_proj_dim", C.c_int32),
     ]
 
@@ -193,6 +194,7 @@ SIGNATURES = {
     "sd_op_groupnorm_concat": (_I, [_P, _I, _I, _P, _P, _P, _I, _I, _I, _F, _I, _P]),
     "sd_bench_groupnorm": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _I, C.POINTER(_F), _P]),
     "sd_op_timestep_sinusoid": (_I, [_P, _P, _I, _I, _I, _F, _P]),
+    "sd_op_text_time_input": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _F, _P]),
     "sd_op_timestep_cond_embedding": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _F, _P]),
     "sd_op_small_linear": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "sd_op_freeu": (_I, [_P, _I, _I, _I, _I, _I, _F, _F, _P]),

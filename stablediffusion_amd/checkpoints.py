@@ -41,7 +41,23 @@ def _as_tuple(v, n):
     return tuple(v) if isinstance(v, (list, tuple)) else (v,) * n
 
 
+def _pooled_projection_dim(d: dict) -> Optional[int]:
+    if d.get("pooled_projection_dim") is not None:
+        return int(d["pooled_projection_dim"])
+    ad, pin = d.get("addition_time_embed_dim"), d.get("projection_class_embeddings_input_dim")
+    if ad and pin and d.get("cross_attention_dim") == 1280 and pin - 5 * ad == 1280:
+        return 1280
+    return None
+
+
 def unet_config_from_json(d: dict) -> UNetConfig:
+    """diffusers `unet/config.json` -> UNetConfig.
+
+    `pooled_projection_dim` (this project's field: the width of `text_embeds`, which fixes the number of time ids) is
+    read when present.  diffusers' own files do not carry it; then the SDXL refiner is recognised by its signature:
+    `cross_attention_dim == 1280` (text_encoder_2 alone) and
+    `projection_class_embeddings_input_dim - 5 * addition_time_embed_dim == 1280` give pooled 1280, i.e. five ids.
+    Everything else keeps the SDXL-base reading (None: six ids)."""
     nb = len(d["block_out_channels"])
     heads = d.get("num_attention_heads") or d["attention_head_dim"]   # diffusers quirk: head_dim == heads
     return UNetConfig(
@@ -56,7 +72,8 @@ def unet_config_from_json(d: dict) -> UNetConfig:
         addition_embed_type=d.get("addition_embed_type"),
         addition_time_embed_dim=d.get("addition_time_embed_dim"),
         projection_class_embeddings_input_dim=d.get("projection_class_embeddings_input_dim"),
-        time_cond_proj_dim=d.get("time_cond_proj_dim"))
+        time_cond_proj_dim=d.get("time_cond_proj_dim"),
+        pooled_projection_dim=_pooled_projection_dim(d))
 
 
 def vae_config_from_json(d: dict) -> VAEConfig:
@@ -87,6 +104,17 @@ def load_diffusers_folder(root: str) -> Tuple[UNetConfig, Dict[str, torch.Tensor
     usd = load_safetensors(_find_weights(os.path.join(root, "unet")))
     vsd = load_safetensors(_find_weights(os.path.join(root, "vae")))
     return ucfg, usd, vcfg, vsd
+
+
+def load_unet_folder(root: str) -> Tuple[UNetConfig, Dict[str, torch.Tensor]]:
+    """A UNet-only diffusers folder (an SDXL refiner's `unet/`): `<root>/unet/config.json` plus weights, or `root`
+    itself holding the two files."""
+    folder = os.path.join(root, "unet")
+    if not os.path.exists(os.path.join(folder, "config.json")):
+        folder = root
+    with open(os.path.join(folder, "config.json")) as f:
+        ucfg = unet_config_from_json(json.load(f))
+    return ucfg, load_safetensors(_find_weights(folder))
 
 
 SCHEDULER_FIELDS = ("num_train_timesteps", "beta_start", "beta_end", "steps_offset", "timestep_spacing",

@@ -40,10 +40,28 @@ class UNetConfig:
     # guidance-embedded UNets (Latent Consistency Models): width of `timestep_cond`, projected by
     # time_embedding.cond_proj onto the sinusoid (diffusers TimestepEmbedding cond_proj_dim); LCM checkpoints: 256
     time_cond_proj_dim: Optional[int] = None
+    # text_time conditioning: width of the pooled text embedding (`text_embeds`).  None: the SDXL-base layout, six time
+    # ids, pooled = projection_class_embeddings_input_dim - 6 * addition_time_embed_dim.  The SDXL refiner has five
+    # ids (original size, crop, aesthetic score): 2560 = 1280 + 5 * 256.
+    pooled_projection_dim: Optional[int] = None
 
     @property
     def time_embed_dim(self) -> int:
         return self.block_out_channels[0] * 4
+
+    @property
+    def num_time_ids(self) -> int:
+        """Columns of `added_cond_kwargs["time_ids"]` (0 without text_time conditioning)."""
+        if not self.addition_time_embed_dim:
+            return 0
+        if self.pooled_projection_dim is None:
+            return 6
+        n, rem = divmod(self.projection_class_embeddings_input_dim - self.pooled_projection_dim,
+                        self.addition_time_embed_dim)
+        if rem or n < 1:
+            raise ValueError("projection_class_embeddings_input_dim - pooled_projection_dim is no positive multiple of "
+                             "addition_time_embed_dim")
+        return n
 
     def heads_for_block(self, i: int) -> int:
         return self.attention_head_dim[i]
@@ -136,6 +154,25 @@ def sdxl_unet() -> UNetConfig:
     )
 
 
+def sdxl_refiner_unet() -> UNetConfig:
+    """SDXL refiner: 2 259 526 660 parameters, five time ids (original size, crop, aesthetic score), text_encoder_2 only.
+    The values are recalled from the published configuration, not pinned to a file."""
+    return UNetConfig(
+        sample_size=128,
+        down_block_types=("DownBlock2D", "CrossAttnDownBlock2D", "CrossAttnDownBlock2D", "DownBlock2D"),
+        up_block_types=("UpBlock2D", "CrossAttnUpBlock2D", "CrossAttnUpBlock2D", "UpBlock2D"),
+        block_out_channels=(384, 768, 1536, 1536),
+        cross_attention_dim=1280,
+        attention_head_dim=(6, 12, 24, 24),
+        transformer_layers_per_block=(4, 4, 4, 4),
+        use_linear_projection=True,
+        addition_embed_type="text_time",
+        addition_time_embed_dim=256,
+        projection_class_embeddings_input_dim=2560,
+        pooled_projection_dim=1280,
+    )
+
+
 def sdxl_vae() -> VAEConfig:
     return VAEConfig(scaling_factor=0.13025, force_upcast=True, sample_size=1024)
 
@@ -157,6 +194,24 @@ def tiny_unet(linear: bool = False, sdxl_cond: bool = False, time_cond: int = 0)
     return UNetConfig(**kw)
 
 
+def tiny_refiner_unet() -> UNetConfig:
+    """Width-reduced UNet with the SDXL refiner's topology and its five time ids."""
+    return UNetConfig(
+        sample_size=16,
+        down_block_types=("DownBlock2D", "CrossAttnDownBlock2D", "CrossAttnDownBlock2D", "DownBlock2D"),
+        up_block_types=("UpBlock2D", "CrossAttnUpBlock2D", "CrossAttnUpBlock2D", "UpBlock2D"),
+        block_out_channels=(64, 128, 256, 256),
+        cross_attention_dim=64,
+        attention_head_dim=(2, 4, 8, 8),
+        transformer_layers_per_block=(1, 2, 2, 2),
+        use_linear_projection=True,
+        addition_embed_type="text_time",
+        addition_time_embed_dim=32,
+        projection_class_embeddings_input_dim=5 * 32 + 64,
+        pooled_projection_dim=64,
+    )
+
+
 def tiny_vae() -> VAEConfig:
     return VAEConfig(block_out_channels=(64, 64, 128, 128), sample_size=64)
 
@@ -164,5 +219,6 @@ def tiny_vae() -> VAEConfig:
 PRESETS = {
     "sd15": (sd15_unet, sd15_vae),
     "sdxl": (sdxl_unet, sdxl_vae),
+    "sdxl_refiner": (sdxl_refiner_unet, sdxl_vae),
     "tiny": (tiny_unet, tiny_vae),
 }

@@ -43,14 +43,20 @@ bool bad_cfg(const sd_unet_config* c) {
             !attention_supported(c->block_out_channels[i] / c->num_heads[i])) return true;
     }
     if (c->addition_time_embed_dim > 0) {
-        // text_time conditioning: add_embedding.linear_1 reads [pooled text | 6 sinusoids of `ad`] rows of
+        // text_time conditioning: add_embedding.linear_1 reads [pooled text | n sinusoids of `ad`] rows of
         // projection_class_embeddings_input_dim halves with 16-byte loads against weight rows packed to a
         // multiple of 64 (UNet::run): anything else reads misaligned / wrong rows silently
         const int ad = c->addition_time_embed_dim, pin = c->projection_class_embeddings_input_dim;
-        if ((ad & 1) || pin % 64 != 0 || pin - 6 * ad <= 0) return true;
+        const int n = c->num_time_ids ? c->num_time_ids : 6;          // (0: a zero-initialised caller's SDXL base)
+        // (six ids: the row is assembled at its own width, so it must be the packed K itself; any other count is
+        //  built by one launch that pads the row to the packed K with zeros, and pin % 8 is enough)
+        if (n < 1 || n > 8 || (ad & 1) || pin % (n == 6 ? 64 : 8) != 0 || pin - n * ad <= 0) return true;
     }
     return c->cross_attention_dim % 64 != 0 || c->in_channels <= 0 || c->in_channels > 16;
 }
+
+// columns of add_time_ids a configuration asks for (0 in the struct: 6); only read with text_time conditioning
+int time_ids_of(const sd_unet_config& c) { return c.addition_time_embed_dim > 0 ? (c.num_time_ids ? c.num_time_ids : 6) : 0; }
 
 // field by field (no padding bytes compared): the configuration an IP-Adapter was created for
 bool same_topology(const sd_unet_config& a, const sd_unet_config& b) {
@@ -59,7 +65,8 @@ bool same_topology(const sd_unet_config& a, const sd_unet_config& b) {
         a.use_linear_projection != b.use_linear_projection || a.norm_num_groups != b.norm_num_groups ||
         a.norm_eps != b.norm_eps || a.flip_sin_to_cos != b.flip_sin_to_cos || a.freq_shift != b.freq_shift ||
         a.addition_time_embed_dim != b.addition_time_embed_dim ||
-        a.projection_class_embeddings_input_dim != b.projection_class_embeddings_input_dim)
+        a.projection_class_embeddings_input_dim != b.projection_class_embeddings_input_dim ||
+        time_ids_of(a) != time_ids_of(b))
         return false;
     for (int i = 0; i < SD_MAX_BLOCKS; ++i)
         if (a.block_out_channels[i] != b.block_out_channels[i] || a.down_block_has_attn[i] != b.down_block_has_attn[i] ||
@@ -81,7 +88,8 @@ bool controlnet_fits(const sd_unet_config& u, const sd_unet_config& n, std::stri
     if (n.cross_attention_dim != u.cross_attention_dim) { *why = "cross_attention_dim differs from the UNet's"; return false; }
     if (n.in_channels != u.in_channels) { *why = "in_channels differs from the UNet's (9-channel inpaint UNets take no ControlNet)"; return false; }
     if (n.addition_time_embed_dim != u.addition_time_embed_dim ||
-        n.projection_class_embeddings_input_dim != u.projection_class_embeddings_input_dim) {
+        n.projection_class_embeddings_input_dim != u.projection_class_embeddings_input_dim ||
+        time_ids_of(n) != time_ids_of(u)) {
         *why = "text_time conditioning differs from the UNet's";
         return false;
     }
@@ -102,7 +110,8 @@ int sd_unet_create(const sd_unet_config* cfg, sd_unet** out) {
     if (bad_cfg(cfg)) {
         set_error("sd_unet_create: unsupported config (channels must be multiples of 64 and of the group "
                   "count, head dims in {32,40,64,80,128,160}, cross_attention_dim % 64 == 0, text_time: even "
-                  "addition_time_embed_dim and projection_class_embeddings_input_dim % 64 == 0 and > 6 x it)");
+                  "addition_time_embed_dim, num_time_ids in 1..8 (0: 6) and projection_class_embeddings_input_dim "
+                  "> num_time_ids x addition_time_embed_dim, % 64 == 0 with six ids and % 8 == 0 otherwise)");
         return SD_ERR_UNSUPPORTED;
     }
     if (cfg->time_cond_proj_dim < 0 || cfg->time_cond_proj_dim > 1024) {
@@ -1237,6 +1246,16 @@ int sd_op_timestep_sinusoid(const float* t, float* out, int count, int dim, int 
                             void* stream) {
     if (!t || !out || count < 1 || dim < 2 || (dim & 1)) { set_error("sd_op_timestep_sinusoid: bad arguments"); return SD_ERR_INVALID; }
     return launch_timestep_sinusoid(t, 1, out, count, dim, flip_sin_to_cos, freq_shift, dim, static_cast<hipStream_t>(stream));
+}
+
+int sd_op_text_time_input(const void* add_text, const float* ids, float* out, int B, int P, int ad, int n_ids,
+                          int flip_sin_to_cos, float freq_shift, void* stream) {
+    if (!add_text || !ids || !out || B < 1 || P <= 0 || ad < 2 || (ad & 1) || n_ids < 1 || n_ids > 8) {
+        set_error("sd_op_text_time_input: bad arguments (P > 0, even ad, n_ids in [1, 8])");
+        return SD_ERR_INVALID;
+    }
+    return launch_text_time_input(static_cast<const half_t*>(add_text), ids, out, B, P, ad, n_ids, flip_sin_to_cos,
+                                  freq_shift, P + n_ids * ad, static_cast<hipStream_t>(stream));
 }
 
 int sd_op_timestep_cond_embedding(const float* t, const float* cond, const void* w_f16, float* out, int B, int dim,

@@ -274,6 +274,11 @@ int launch_freeu(half_t* x, long ld, int N, int H, int W, int C1, int C2, float 
 // out[b, :] = [cos(t_b f_i) | sin(t_b f_i)] (flip) or [sin | cos]; f_i = exp(-ln(1e4) i/(half-shift))
 int launch_timestep_sinusoid(const float* t, int t_stride, float* out, int count, int dim, int flip, float shift,
                              long out_ld, hipStream_t s);
+// The input of add_embedding.linear_1: out[b] = [f32(text[b, :P]) | sinusoid(ids[b, 0]) | .. | sinusoid(ids[b, n - 1]) | 0 ..],
+// rows out_ld >= P + n * ad floats apart (the rest zeroed), one launch; the sinusoids are launch_timestep_sinusoid's
+// bits.  ad even, n >= 1.
+int launch_text_time_input(const half_t* text, const float* ids, float* out, int B, int P, int ad, int n, int flip,
+                           float shift, int out_ld, hipStream_t s);
 // out[b, j] = sinusoid(t_b)[j] + sum_k w[j, k] cond[b, k]: launch_timestep_sinusoid (t_stride 1, out_ld dim) with the
 // cond_proj of a guidance-embedded UNet added, one launch.  w [dim rows][ldw] f16, cond [count, cond_dim] f32.
 int launch_timestep_cond(const float* t, const float* cond, const half_t* w, long ldw, float* out, int count, int dim,

@@ -14,17 +14,46 @@ namespace {
 
 // diffusers get_timestep_embedding (Timesteps): restated for UNet2DConditionModel.time_proj /
 // add_time_proj under /root/reference/pipelines/sd_unified_pipeline.py:475-482.
+// One (sin, cos) pair of the embedding: every kernel that writes a sinusoid calls this, so their bits agree.
+__device__ __forceinline__ void sinusoid_pair(float t, int f, int half, float shift, float* sn, float* cs) {
+    const float freq = __expf(-9.210340371976184f * (float)f / ((float)half - shift));
+    const float ang = t * freq;
+    sincosf(ang, sn, cs);
+}
+
 __global__ void sinusoid_kernel(const float* __restrict__ t, int t_stride, float* __restrict__ out, int count,
                                 int dim, int flip, float shift, long out_ld) {
     const int half = dim >> 1;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= count * half) return;
     const int b = i / half, f = i - b * half;
-    const float freq = __expf(-9.210340371976184f * (float)f / ((float)half - shift));
-    const float ang = t[(long)b * t_stride] * freq;
     float sn, cs;
-    sincosf(ang, &sn, &cs);
+    sinusoid_pair(t[(long)b * t_stride], f, half, shift, &sn, &cs);
     float* o = out + (long)b * out_ld;
+    if (flip) { o[f] = cs; o[half + f] = sn; } else { o[f] = sn; o[half + f] = cs; }
+}
+
+// The input of add_embedding.linear_1 (text_time conditioning), one launch for B rows of P + n * ad floats, out_ld apart:
+//   out[b, :P] = f32(text[b, :]),   out[b, P + j*ad + (f | half + f)] = sinusoid(ids[b, j]) pair f,   j < n
+// and zeros in the columns [P + n * ad, out_ld) (the row padded to the packed weight's K).  One thread per output unit
+// of a row: the first P units convert one pooled value each (exact), the next n * ad / 2 each own one (sin, cos) pair
+// as a thread of sinusoid_kernel does, the last out_ld - (P + n * ad) write one zero each.
+__global__ __launch_bounds__(256) void text_time_input_kernel(const half_t* __restrict__ text, const float* __restrict__ ids,
+                                                              float* __restrict__ out, int B, int P, int ad, int n,
+                                                              int flip, float shift, int out_ld) {
+    const int half = ad >> 1;
+    const int width = P + n * ad;
+    const int per_row = P + n * half + (out_ld - width);
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long)B * per_row) return;
+    const int b = (int)(i / per_row), u = (int)(i - (long)b * per_row);
+    float* o = out + (long)b * out_ld;
+    if (u < P) { o[u] = (float)text[(long)b * P + u]; return; }
+    if (u >= P + n * half) { o[width + (u - P - n * half)] = 0.f; return; }
+    const int j = (u - P) / half, f = (u - P) - j * half;
+    float sn, cs;
+    sinusoid_pair(ids[(long)b * n + j], f, half, shift, &sn, &cs);
+    o += P + j * ad;
     if (flip) { o[f] = cs; o[half + f] = sn; } else { o[f] = sn; o[half + f] = cs; }
 }
 
@@ -74,10 +103,8 @@ __global__ __launch_bounds__(256) void temb_cond_kernel(const float* __restrict_
         a1 += __shfl_xor(a1, off);
     }
     if (lane != 0) return;
-    const float freq = __expf(-9.210340371976184f * (float)f / ((float)half - shift));
-    const float ang = t[b] * freq;
     float sn, cs;
-    sincosf(ang, &sn, &cs);
+    sinusoid_pair(t[b], f, half, shift, &sn, &cs);
     float* o = out + (long)b * dim;
     o[r0] = sn + a0;
     o[r1] = cs + a1;
@@ -835,6 +862,17 @@ int launch_timestep_sinusoid(const float* t, int t_stride, float* out, int count
                              long out_ld, hipStream_t s) {
     hipLaunchKernelGGL(sinusoid_kernel, grid1d((long)count * (dim / 2)), dim3(256), 0, s, t, t_stride, out, count,
                        dim, flip, shift, out_ld);
+    SD_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int launch_text_time_input(const half_t* text, const float* ids, float* out, int B, int P, int ad, int n, int flip,
+                           float shift, int out_ld, hipStream_t s) {
+    if (out_ld < P + n * ad) { set_error("text_time_input: out_ld < P + n * ad"); return 1; }
+    const long units = (long)B * (P + n * (ad / 2) + (out_ld - (P + n * ad)));
+    if (units <= 0) return 0;
+    hipLaunchKernelGGL(text_time_input_kernel, grid1d(units), dim3(256), 0, s, text, ids, out, B, P, ad, n, flip, shift,
+                       out_ld);
     SD_HIP_CHECK(hipGetLastError());
     return 0;
 }

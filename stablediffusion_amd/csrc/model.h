@@ -120,6 +120,9 @@ struct Encoder {
     int temb_total = 0;
     int kv_total = 0;
 
+    // columns of add_time_ids (text_time conditioning): 6 for SDXL base and for a zero field, 5 for the SDXL refiner
+    int num_time_ids() const { return cfg.num_time_ids ? cfg.num_time_ids : 6; }
+
     // Skip tensors the down path produces, in order: conv_in's output, every down resnet / transformer output, every
     // downsampler output (the residual sites of a ControlNet, the skips of a UNet).
     int num_skips() const;

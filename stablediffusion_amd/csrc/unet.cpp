@@ -586,25 +586,34 @@ int Encoder::run_temb(Ctx& c, const float* timesteps, const half_t* add_text, co
     if (aug_path) {
         const int ad = cfg.addition_time_embed_dim;
         const int pin = cfg.projection_class_embeddings_input_dim;
-        const int tdim = pin - 6 * ad;          // pooled text embedding width
+        const int nid = num_time_ids();
+        const int tdim = pin - nid * ad;        // pooled text embedding width
         if (!add_text || !add_time_ids) { set_error("unet: add_text / add_time_ids required for text_time conditioning"); return 1; }
-        float* addin = a.alloc_f((long)B * pin);
+        // (rows as wide as add_embedding.linear_1's packed K: pin itself with six ids, zero padded otherwise)
+        const int kin = nid == 6 ? pin : (int)ae1.K;
+        float* addin = a.alloc_f((long)B * kin);
         float* a1 = a.alloc_f((long)B * temb);
         float* aug = a.alloc_f((long)B * temb);
-        float* txt = a.alloc_f((long)B * tdim);
-        if (go && !c.err) c.err = launch_f16_to_f32(add_text, txt, (long)B * tdim, s);
-        if (go && !c.err) {
-            hipError_t e = hipMemcpy2DAsync(addin, (size_t)pin * 4, txt, (size_t)tdim * 4, (size_t)tdim * 4, (size_t)B,
-                                            hipMemcpyDeviceToDevice, s);
-            if (e != hipSuccess) { set_error(hipGetErrorString(e)); c.err = 3; }
+        if (nid != 6) {
+            if (go && !c.err) c.err = launch_text_time_input(add_text, add_time_ids, addin, B, tdim, ad, nid,
+                                                             cfg.flip_sin_to_cos, cfg.freq_shift, kin, s);
+        } else {
+            // six ids (SDXL base) keep the launch sequence they always had
+            float* txt = a.alloc_f((long)B * tdim);
+            if (go && !c.err) c.err = launch_f16_to_f32(add_text, txt, (long)B * tdim, s);
+            if (go && !c.err) {
+                hipError_t e = hipMemcpy2DAsync(addin, (size_t)pin * 4, txt, (size_t)tdim * 4, (size_t)tdim * 4, (size_t)B,
+                                                hipMemcpyDeviceToDevice, s);
+                if (e != hipSuccess) { set_error(hipGetErrorString(e)); c.err = 3; }
+            }
+            // time_ids.flatten() -> [B*6] scalars -> sinusoid(ad) each -> [B, 6*ad] placed after the text
+            if (go && !c.err) {
+                for (int j = 0; j < 6 && !c.err; ++j)
+                    c.err = launch_timestep_sinusoid(add_time_ids + j, 6, addin + tdim + j * ad, B, ad,
+                                                             cfg.flip_sin_to_cos, cfg.freq_shift, pin, s);
+            }
         }
-        // time_ids.flatten() -> [B*6] scalars -> sinusoid(ad) each -> [B, 6*ad] placed after the text
-        if (go && !c.err) {
-            for (int j = 0; j < 6 && !c.err; ++j)
-                c.err = launch_timestep_sinusoid(add_time_ids + j, 6, addin + tdim + j * ad, B, ad,
-                                                         cfg.flip_sin_to_cos, cfg.freq_shift, pin, s);
-        }
-        if (go && !c.err) c.err = launch_small_linear(addin, pin, ae1.w, ae1.bias, a1, temb, B, pin, temb, 0, 1, s);
+        if (go && !c.err) c.err = launch_small_linear(addin, kin, ae1.w, ae1.bias, a1, temb, B, kin, temb, 0, 1, s);
         if (go && !c.err) c.err = launch_small_linear(a1, temb, ae2.w, ae2.bias, aug, temb, B, temb, temb, 0, 0, s);
         if (go && !c.err) c.err = launch_add_f32(emb, aug, (long)B * temb, 1, s);      // silu(emb + aug_emb)
     }
@@ -1071,11 +1080,12 @@ int UNet::forward_graph(const half_t* sample, const float* timesteps, const half
                         const half_t* add_text, const float* add_time_ids, half_t* out, int B, int H, int W,
                         hipStream_t stream, const float* tcond) {
     const bool sdxl = cfg.addition_time_embed_dim > 0;
-    const int pdim = sdxl ? cfg.projection_class_embeddings_input_dim - 6 * cfg.addition_time_embed_dim : 0;
+    const int pdim = sdxl ? cfg.projection_class_embeddings_input_dim - num_time_ids() * cfg.addition_time_embed_dim : 0;
+    const int nid = sdxl ? num_time_ids() : 0;
     auto up = [](size_t v) { return (v + 255) & ~size_t(255); };
     const size_t n_sample = up((size_t)B * cfg.in_channels * H * W * 2), n_t = up((size_t)B * 4);
     const size_t n_ehs = up((size_t)B * L * cfg.cross_attention_dim * 2), n_text = up((size_t)B * pdim * 2);
-    const size_t n_ids = up((size_t)B * 6 * 4), n_out = up((size_t)B * cfg.out_channels * H * W * 2);
+    const size_t n_ids = up((size_t)B * nid * 4), n_out = up((size_t)B * cfg.out_channels * H * W * 2);
     const size_t n_tc = tcond ? up((size_t)B * cfg.time_cond_proj_dim * 4) : 0;
     const size_t need = n_sample + n_t + n_ehs + n_text + n_ids + n_tc + n_out;
     if (!gstream) {
@@ -1104,7 +1114,7 @@ int UNet::forward_graph(const half_t* sample, const float* timesteps, const half
     if (sdxl) {
         if (!add_text || !add_time_ids) { set_error("unet: add_text / add_time_ids required for text_time conditioning"); return 1; }
         SD_HIP_CHECK(hipMemcpyAsync(g_text, add_text, (size_t)B * pdim * 2, hipMemcpyDeviceToDevice, stream));
-        SD_HIP_CHECK(hipMemcpyAsync(g_ids, add_time_ids, (size_t)B * 6 * 4, hipMemcpyDeviceToDevice, stream));
+        SD_HIP_CHECK(hipMemcpyAsync(g_ids, add_time_ids, (size_t)B * nid * 4, hipMemcpyDeviceToDevice, stream));
     }
     if (tcond) SD_HIP_CHECK(hipMemcpyAsync(g_tc, tcond, (size_t)B * cfg.time_cond_proj_dim * 4, hipMemcpyDeviceToDevice, stream));
     // (timestep_cond's width is the configuration's: its presence is what changes the captured launches)

@@ -97,8 +97,14 @@ def _unet_config_struct(config: UNetConfig):
     c.freq_shift = float(config.freq_shift)
     c.addition_time_embed_dim = config.addition_time_embed_dim or 0
     c.projection_class_embeddings_input_dim = config.projection_class_embeddings_input_dim or 0
+    c.num_time_ids = config.num_time_ids
     c.time_cond_proj_dim = getattr(config, "time_cond_proj_dim", None) or 0
     return c
+
+
+def _check_time_ids(add_ids, cfg: UNetConfig):
+    if add_ids.ndim != 2 or add_ids.shape[1] != cfg.num_time_ids:
+        raise ValueError(f"time_ids: expected [B, {cfg.num_time_ids}] for this UNet, got {tuple(add_ids.shape)}")
 
 
 class HipUNet2DConditionModel:
@@ -310,6 +316,7 @@ class HipUNet2DConditionModel:
                 raise ValueError("added_cond_kwargs needs text_embeds and time_ids for text_time conditioning")
             add_text = _as_f16(added_cond_kwargs["text_embeds"], dev)
             add_ids = added_cond_kwargs["time_ids"].to(device=dev, dtype=torch.float32).contiguous()
+            _check_time_ids(add_ids, self.cfg)
             pt, pi = C.c_void_p(add_text.data_ptr()), C.c_void_p(add_ids.data_ptr())
         img = self._image_embeds(added_cond_kwargs, B, dev)
         ctrl, cscale = self._control(controlnet_cond, controlnet_conditioning_scale, B, H, W, dev)
@@ -392,6 +399,7 @@ class HipUNet2DConditionModel:
                 raise ValueError("added_cond_kwargs needs text_embeds and time_ids for text_time conditioning")
             add_text = _as_f16(added_cond_kwargs["text_embeds"], dev)
             add_ids = added_cond_kwargs["time_ids"].to(device=dev, dtype=torch.float32).contiguous()
+            _check_time_ids(add_ids, self.cfg)
             if add_text.shape[0] != 2 * B or add_ids.shape[0] != 2 * B:
                 raise ValueError("text_embeds / time_ids must hold 2 x latents batch rows")
             pt, pi = C.c_void_p(add_text.data_ptr()), C.c_void_p(add_ids.data_ptr())

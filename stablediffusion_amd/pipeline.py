@@ -21,6 +21,7 @@ Differences from the reference, on purpose:
 """
 from __future__ import annotations
 
+import os
 from typing import Any, Dict, List, Optional, Union
 
 import torch
@@ -37,8 +38,11 @@ class SDModelWrapper:
                  model_name: Optional[str] = None, unet_state_dict: Optional[Dict[str, torch.Tensor]] = None,
                  text_encoder_state_dict: Optional[Dict[str, torch.Tensor]] = None,
                  text_encoder_2_state_dict: Optional[Dict[str, torch.Tensor]] = None,
-                 image_encoder=None, feature_extractor=None, prediction_type: Optional[str] = None):
+                 image_encoder=None, feature_extractor=None, prediction_type: Optional[str] = None, refiner=None):
         self.base = base
+        # the third UNet-shaped slot of models/stable_diffusion.py:40-103: the SDXL refiner (load_refiner).  LoRA, FreeU,
+        # IP-Adapter and ControlNet address .base, as the reference's loaders do; a LoRA re-fuse leaves it alone
+        self.refiner = refiner
         # IP-Adapter (sd_unified_pipeline.py:441-449): host image encoder (e.g. transformers'
         # CLIPVisionModelWithProjection) and its CLIPImageProcessor, built by the caller; the adapter's converted
         # weights stay here so that a LoRA re-fuse (which rebuilds .base) can attach it again
@@ -81,11 +85,52 @@ class SDModelWrapper:
     def to(self, device):
         self.vae.to(device)
         self.base.to(device)
+        if self.refiner is not None:
+            self.refiner.to(device)
         if self.text_encoder is not None:
             self.text_encoder.to(device)
         if getattr(self, "text_encoder_2", None) is not None:
             self.text_encoder_2.to(device)
         self.device = torch.device(device)
+
+    # ---- SDXL refiner (models/stable_diffusion.py load_refiner; the pipeline takes use_refiner= / refiner_start=) ----
+    def load_refiner(self, refiner, config=None):
+        """The refiner UNet: an engine UNet (HipUNet2DConditionModel, or anything with its call surface), or a local
+        path -- a UNet-only diffusers folder (`unet/config.json` + weights, or the folder itself:
+        checkpoints.load_unet_folder) or a `.safetensors` file, single-file LDM naming or diffusers naming, read with
+        `config` (default: config.sdxl_refiner_unet()).  The reference downloads its default from the hub; nothing here
+        reaches the network, so None is an error.  Replaces a refiner loaded before."""
+        if refiner is None:
+            raise ValueError("load_refiner needs an engine UNet or a local folder / .safetensors file "
+                             "(hub downloads are not supported)")
+        if not isinstance(refiner, (str, os.PathLike)):
+            if not (callable(refiner) and hasattr(refiner, "config")):
+                raise ValueError("load_refiner needs an engine UNet or a local folder / .safetensors file, "
+                                 f"got {type(refiner).__name__}")
+            self.refiner = refiner
+            return
+        from . import checkpoints
+        from .config import sdxl_refiner_unet
+        from .models import HipUNet2DConditionModel
+        path = os.fspath(refiner)
+        if os.path.isdir(path):
+            cfg, sd = checkpoints.load_unet_folder(path)
+        elif path.endswith(".safetensors") and os.path.isfile(path):
+            cfg = config if config is not None else sdxl_refiner_unet()
+            sd = checkpoints.load_safetensors(path)
+            if any(k.startswith(checkpoints.UNET_PREFIX) for k in sd):
+                sd = checkpoints.ldm_to_diffusers_unet(sd, cfg)
+        else:
+            raise ValueError(f"load_refiner: {path!r} is neither a folder nor a .safetensors file")
+        self.refiner = None                  # an old refiner's device memory goes before the new one is packed
+        self.refiner = HipUNet2DConditionModel(cfg, str(self.device)).load_state_dict(sd)
+
+    def unload_refiner(self):
+        self.refiner = None
+
+    @property
+    def has_refiner(self) -> bool:
+        return self.refiner is not None
 
     # ---- LoRA adapters (models/stable_diffusion.py:229-335), folded into the weights on the host ----
     def _adapters(self):
@@ -328,6 +373,11 @@ class StableDiffusionUnifiedPipeline:
         # the fused CFG step lets the engine run the start of the UNet once per latent (HipUNet2DConditionModel.forward_cfg);
         # False keeps the engine's duplicate-then-forward form
         self.cfg_share = True
+        self._use_refiner = False            # set per call: the UNet of this call is model.refiner
+
+    def _unet(self, model):
+        """The UNet this call runs: `.base`, or `.refiner` under use_refiner=True."""
+        return model.refiner if self._use_refiner else model.base
 
     @property
     def do_classifier_free_guidance(self) -> bool:
@@ -380,16 +430,35 @@ class StableDiffusionUnifiedPipeline:
         control_guidance_start: float = 0.0,
         control_guidance_end: float = 1.0,
         guess_mode: bool = False,
+        # SDXL refiner (diffusers StableDiffusionXLImg2ImgPipeline on model.refiner; the reference's handler TODO)
+        use_refiner: bool = False,
+        refiner_start: Optional[float] = None,
+        aesthetic_score: float = 6.0,
+        negative_aesthetic_score: float = 2.5,
     ):
+        if refiner_start is not None:
+            call = {k: v for k, v in locals().items() if k != "self"}
+            return self._ensemble_of_experts(call)
         if guess_mode:
             raise NotImplementedError("ControlNet guess_mode is not supported")
-        tc_dim = int(getattr(model.base.config, "time_cond_proj_dim", None) or 0)
+        self._use_refiner = bool(use_refiner)
+        if use_refiner:
+            if getattr(model, "refiner", None) is None:
+                raise ValueError("use_refiner=True but the model has no refiner (SDModelWrapper.load_refiner)")
+            if prompt_embeds is None and (getattr(model, "text_encoder_2", None) is None
+                                          or getattr(model, "tokenizer_2", None) is None):
+                raise ValueError("the refiner reads text_encoder_2 / tokenizer_2, which this model does not have")
+            if control_image is not None or ip_adapter_image is not None or ip_adapter_image_embeds is not None:
+                raise ValueError("the refiner takes no ControlNet or IP-Adapter inputs (they belong to model.base)")
+            if image is None:
+                raise ValueError("use_refiner=True is an image-to-image call: image= (pixels or 4-channel latents) is required")
+        tc_dim = int(getattr(self._unet(model).config, "time_cond_proj_dim", None) or 0)
         self._guidance_embedded = tc_dim > 0
         if not 0.0 <= float(guidance_rescale) <= 1.0:
             raise ValueError(f"guidance_rescale must lie in [0, 1], got {guidance_rescale}")
         # as in diffusers: only with CFG on and a positive value
         guidance_rescale = float(guidance_rescale) if self.do_classifier_free_guidance else 0.0
-        has_cn = bool(getattr(model, "has_controlnet", False))
+        has_cn = bool(getattr(model, "has_controlnet", False)) and not use_refiner     # (a ControlNet belongs to .base)
         if control_image is not None and not has_cn:
             raise ValueError("control_image given but no ControlNet is loaded (SDModelWrapper.load_controlnet)")
         if has_cn and control_image is None:
@@ -410,18 +479,24 @@ class StableDiffusionUnifiedPipeline:
             model.set_lora_scale(1.0 if lora_scale is None else lora_scale)
         if hasattr(model, "apply_adapters"):
             model.apply_adapters()
+        unet = self._unet(model)             # (after the re-fuse, which replaces model.base)
         if image is not None and mask_image is None:
             # img2img keeps the image's own size (`:238` preprocesses without height / width); PIL, numpy and
             # tensor inputs alike go through the image processor (rounded down to a multiple of the VAE factor)
             image = model.image_processor.preprocess(image)
             if image.shape[1] != 4:
                 height, width = image.shape[-2], image.shape[-1]
+            elif use_refiner:
+                # the hand-off passes latents: the size the time ids state is theirs (diffusers' img2img reads it back
+                # from the prepared latents), not the refiner's sample_size
+                height = height or image.shape[-2] * model.vae_scale_factor
+                width = width or image.shape[-1] * model.vae_scale_factor
         if has_cn and image is None and (height is None or width is None):
             # txt2img: the run's size comes from the control image (diffusers' check_image / prepare_image)
             ci = self.control_image_processor(model).preprocess(control_image, height=height, width=width)
             height, width = ci.shape[-2], ci.shape[-1]
-        height = height or model.base.config.sample_size * model.vae_scale_factor
-        width = width or model.base.config.sample_size * model.vae_scale_factor
+        height = height or unet.config.sample_size * model.vae_scale_factor
+        width = width or unet.config.sample_size * model.vae_scale_factor
 
         if prompt is not None and isinstance(prompt, str):
             batch_size = 1
@@ -447,9 +522,9 @@ class StableDiffusionUnifiedPipeline:
 
         self.is_inpaint = False
         mask = masked_image_latents_2b = image_latents = noise = None
-        num_channels_unet = model.base.config.in_channels
+        num_channels_unet = unet.config.in_channels
         if image is None:
-            shape = (batch_size * num_images_per_prompt, model.base.config.in_channels,
+            shape = (batch_size * num_images_per_prompt, unet.config.in_channels,
                      height // model.vae_scale_factor, width // model.vae_scale_factor)
             latents = self.prepare_latents_txt2img(shape, prompt_embeds.dtype, seed, latents)
         elif mask_image is not None:
@@ -495,7 +570,7 @@ class StableDiffusionUnifiedPipeline:
                     raise ValueError("Incorrect configuration settings! latents + mask + masked image channels "
                                      f"!= unet in_channels ({num_channels_unet})")
             elif num_channels_unet != 4:
-                raise ValueError(f"The unet {model.base.__class__} should have either 4 or 9 input channels, "
+                raise ValueError(f"The unet {unet.__class__} should have either 4 or 9 input channels, "
                                  f"not {num_channels_unet}.")
             height, width = (d * model.vae_scale_factor for d in latents.shape[-2:])
             self.is_inpaint = True
@@ -517,13 +592,22 @@ class StableDiffusionUnifiedPipeline:
             timesteps = timesteps[:num_inference_steps]
 
         # SDXL added conditions (:407-435)
-        if getattr(model.base.config, "addition_embed_type", None) == "text_time":
+        if getattr(unet.config, "addition_embed_type", None) == "text_time":
             add_text_embeds = pooled_prompt_embeds
-            add_time_ids = self._get_add_time_ids((height, width), (0, 0), (height, width), prompt_embeds.dtype)
+            if use_refiner:
+                # StableDiffusionXLImg2ImgPipeline with requires_aesthetics_score: the score takes target_size's place,
+                # and the negative half carries its own
+                add_time_ids, add_neg_time_ids = self._get_add_time_ids(
+                    (height, width), (0, 0), None, prompt_embeds.dtype, aesthetic_score=aesthetic_score,
+                    negative_aesthetic_score=negative_aesthetic_score)
+            else:
+                add_time_ids = self._get_add_time_ids((height, width), (0, 0), (height, width), prompt_embeds.dtype)
+                add_neg_time_ids = add_time_ids
             add_time_ids = add_time_ids.repeat(batch_size * num_images_per_prompt, 1)
             if self.do_classifier_free_guidance:
+                add_neg_time_ids = add_neg_time_ids.repeat(batch_size * num_images_per_prompt, 1)
                 add_text_embeds = torch.cat([negative_pooled_prompt_embeds, add_text_embeds], dim=0)
-                add_time_ids = torch.cat([add_time_ids, add_time_ids], dim=0)
+                add_time_ids = torch.cat([add_neg_time_ids, add_time_ids], dim=0)
             added_cond_kwargs = {"text_embeds": add_text_embeds.to(self.device),
                                  "time_ids": add_time_ids.to(self.device)}
         else:
@@ -571,7 +655,7 @@ class StableDiffusionUnifiedPipeline:
                          for i in range(n)]
         # prompt_embeds is the same tensor on every step: the engine keeps its cross-attention K/V
         # projections for the duration of this loop (switched off again right after it)
-        kv_cache = getattr(model.base, "text_kv_cache", None)
+        kv_cache = getattr(unet, "text_kv_cache", None)
         if kv_cache is not None:
             # the cache is keyed by the buffer's address: hand the engine ONE fp16 contiguous tensor for the whole loop
             # (a per-step conversion inside the shim would make a fresh temporary each step: ADVICE r2)
@@ -646,7 +730,7 @@ class StableDiffusionUnifiedPipeline:
                 if self.is_inpaint and num_channels_unet == 9:
                     latent_model_input = torch.cat([latent_model_input, mask.to(latent_model_input.dtype),
                                                     masked_image_latents_2b.to(latent_model_input.dtype)], dim=1)
-                noise_pred = model.base(latent_model_input, t, prompt_embeds,
+                noise_pred = unet(latent_model_input, t, prompt_embeds,
                                         cross_attention_kwargs=cross_attention_kwargs,
                                         added_cond_kwargs=added_cond_kwargs, return_dict=False, **cn_kwargs, **tc_kwargs)[0]
                 if self.do_classifier_free_guidance:
@@ -691,7 +775,7 @@ class StableDiffusionUnifiedPipeline:
     # ------------------------------------------------------------------------------------------
     def _device_inpaint_blend(self, model, latents, blend, a, b, with_noise):
         import ctypes as C
-        lib = model.base._lib
+        lib = self._unet(model)._lib
         img, noise, m = blend
         B, Cc, H, W = latents.shape
         rc = lib.sd_inpaint_blend(C.c_void_p(latents.data_ptr()), C.c_void_p(img.data_ptr()),
@@ -710,12 +794,12 @@ class StableDiffusionUnifiedPipeline:
         return (self.do_classifier_free_guidance and (not self.is_inpaint or num_channels_unet == 4)
                 and hasattr(model.scheduler, "fused_plan") and getattr(model.scheduler, "supports_fused", True)
                 and hasattr(model.scheduler, "add_noise_coefficients")
-                and hasattr(model.base, "_lib") and latents.is_cuda and latents.dtype == torch.float16)
+                and hasattr(self._unet(model), "_lib") and latents.is_cuda and latents.dtype == torch.float16)
 
     def _fused_cfg_iteration(self, model, latents, hist, t, prompt_embeds, cross_attention_kwargs, added_cond_kwargs,
                              guidance_scale, guidance_rescale=0.0, **unet_kwargs):
         import ctypes as C
-        lib = model.base._lib
+        lib = self._unet(model)._lib
         plan = model.scheduler.fused_plan(t)
         latents = latents.contiguous()
         B = latents.shape[0]
@@ -743,12 +827,13 @@ class StableDiffusionUnifiedPipeline:
                      **unet_kwargs):
         """The UNet forward of one CFG step from the un-duplicated fp16 latents: [2B, ...], negative half first."""
         import ctypes as C
-        lib = model.base._lib
+        lib = self._unet(model)._lib
         B = latents.shape[0]
-        if not unet_kwargs and hasattr(model.base, "forward_cfg") and getattr(model.base, "controlnet", None) is None:
+        unet = self._unet(model)
+        if not unet_kwargs and hasattr(unet, "forward_cfg") and getattr(unet, "controlnet", None) is None:
             # the engine takes the un-duplicated latents: no 2B-row copy, and the layers in front of the first
             # cross-attention run once per latent
-            return model.base.forward_cfg(latents, t, prompt_embeds, added_cond_kwargs=added_cond_kwargs,
+            return unet.forward_cfg(latents, t, prompt_embeds, added_cond_kwargs=added_cond_kwargs,
                                           in_scale=in_scale, share=self.cfg_share)[0]
         # ControlNet calls: duplicate, then the forward that takes the control image
         lat2 = torch.empty((2 * B,) + tuple(latents.shape[1:]), device=latents.device, dtype=latents.dtype)
@@ -756,7 +841,7 @@ class StableDiffusionUnifiedPipeline:
                                   latents[0].numel(), B, in_scale, C.c_void_p(torch.cuda.current_stream().cuda_stream))
         if rc:
             raise RuntimeError(lib.sd_last_error().decode())
-        return model.base(lat2, t, prompt_embeds, cross_attention_kwargs=cross_attention_kwargs,
+        return unet(lat2, t, prompt_embeds, cross_attention_kwargs=cross_attention_kwargs,
                           added_cond_kwargs=added_cond_kwargs, return_dict=False, **unet_kwargs)[0]
 
     def _lcm_step_available(self, model, latents, num_channels_unet=4, guidance_rescale=0.0) -> bool:
@@ -764,12 +849,12 @@ class StableDiffusionUnifiedPipeline:
         the HIP engine with fp16 CUDA latents -- with or without CFG, unlike `_fused_step_available`.  9-channel
         inpainting UNets and guidance_rescale (a per-sample statistic) take scheduler.step."""
         return ((not self.is_inpaint or num_channels_unet == 4) and not guidance_rescale > 0.0
-                and hasattr(model.base, "_lib") and latents.is_cuda and latents.dtype == torch.float16)
+                and hasattr(self._unet(model), "_lib") and latents.is_cuda and latents.dtype == torch.float16)
 
     def _lcm_iteration(self, model, latents, noise, t, prompt_embeds, cross_attention_kwargs, added_cond_kwargs,
                        guidance_scale, **unet_kwargs):
         import ctypes as C
-        lib = model.base._lib
+        lib = self._unet(model)._lib
         plan = model.scheduler.fused_plan(t)
         latents = latents.contiguous()
         if self.do_classifier_free_guidance:         # an ordinary UNet (LCM-LoRA): rows = [uncond ; text]
@@ -778,7 +863,7 @@ class StableDiffusionUnifiedPipeline:
                                           added_cond_kwargs, **unet_kwargs)
         else:                                        # guidance-embedded (timestep_cond in unet_kwargs), or no guidance
             rows = 1
-            model_out = model.base(latents, t, prompt_embeds, cross_attention_kwargs=cross_attention_kwargs,
+            model_out = self._unet(model)(latents, t, prompt_embeds, cross_attention_kwargs=cross_attention_kwargs,
                                    added_cond_kwargs=added_cond_kwargs, return_dict=False, **unet_kwargs)[0]
         out = latents.clone()
         noise_p = C.c_void_p(noise.contiguous().data_ptr()) if plan.needs_noise else None
@@ -796,14 +881,14 @@ class StableDiffusionUnifiedPipeline:
         or without CFG.  9-channel inpainting UNets and guidance_rescale (a per-sample statistic) take scheduler.step."""
         inpaint = getattr(self, "is_inpaint", False)            # (set by a call: a fresh pipeline has not inpainted)
         return (hasattr(model.scheduler, "affine_plan") and (not inpaint or num_channels_unet == 4)
-                and not guidance_rescale > 0.0 and hasattr(model.base, "_lib") and latents.is_cuda
+                and not guidance_rescale > 0.0 and hasattr(self._unet(model), "_lib") and latents.is_cuda
                 and latents.dtype == torch.float16)
 
     def _affine_iteration(self, model, latents, bank, noise, t, prompt_embeds, cross_attention_kwargs, added_cond_kwargs,
                           guidance_scale, **unet_kwargs):
         import ctypes as C
         from ._lib import step_plan
-        lib = model.base._lib
+        lib = self._unet(model)._lib
         plan = model.scheduler.affine_plan(t)
         latents = latents.contiguous()
         if self.do_classifier_free_guidance:         # rows = [uncond ; text], from the un-duplicated latents
@@ -812,7 +897,7 @@ class StableDiffusionUnifiedPipeline:
                                           added_cond_kwargs, **unet_kwargs)
         else:
             rows = 1
-            model_out = model.base(model.scheduler.scale_model_input(latents, t), t, prompt_embeds,
+            model_out = self._unet(model)(model.scheduler.scale_model_input(latents, t), t, prompt_embeds,
                                    cross_attention_kwargs=cross_attention_kwargs, added_cond_kwargs=added_cond_kwargs,
                                    return_dict=False, **unet_kwargs)[0]
         out = latents.clone()
@@ -901,13 +986,22 @@ class StableDiffusionUnifiedPipeline:
                       num_images_per_prompt=1, lora_scale=None, clip_skip=None):
         """sd_unified_pipeline.py:532-719: CLIP stays host PyTorch-ROCm (north_star)."""
         m = self.model
-        if m.tokenizer is None or m.text_encoder is None:
+        refiner = self._use_refiner
+        if refiner:
+            if getattr(m, "tokenizer_2", None) is None or getattr(m, "text_encoder_2", None) is None:
+                raise ValueError("the refiner reads text_encoder_2 / tokenizer_2, which this model does not have")
+        elif m.tokenizer is None or m.text_encoder is None:
             raise ValueError("model has no tokenizer / text_encoder: pass prompt_embeds instead")
         sdxl = hasattr(m, "text_encoder_2") and hasattr(m, "tokenizer_2")
         prompt = [prompt] if isinstance(prompt, str) else prompt
         batch_size = len(prompt)
         toks, encs, prompts = [m.tokenizer], [m.text_encoder], [prompt]
-        if sdxl:
+        if refiner:
+            # diffusers' StableDiffusionXLImg2ImgPipeline without tokenizer / text_encoder: the second pair alone
+            prompt_2 = prompt_2 or prompt
+            prompt_2 = [prompt_2] if isinstance(prompt_2, str) else prompt_2
+            toks, encs, prompts = [m.tokenizer_2], [m.text_encoder_2], [prompt_2]
+        elif sdxl:
             prompt_2 = prompt_2 or prompt
             prompt_2 = [prompt_2] if isinstance(prompt_2, str) else prompt_2
             toks, encs, prompts = [m.tokenizer, m.tokenizer_2], [m.text_encoder, m.text_encoder_2], [prompt, prompt_2]
@@ -940,8 +1034,8 @@ class StableDiffusionUnifiedPipeline:
                                  else negative_prompt_2)
             if batch_size != len(negative_prompt):
                 raise ValueError("`negative_prompt` batch size does not match `prompt`")
-            neg_embeds, neg_pooled = run([negative_prompt, negative_prompt_2])
-        dt = m.base.dtype
+            neg_embeds, neg_pooled = run([negative_prompt_2] if refiner else [negative_prompt, negative_prompt_2])
+        dt = self._unet(m).dtype
         bs, seq, _ = prompt_embeds.shape
         prompt_embeds = prompt_embeds.to(dtype=dt, device=self.device).repeat(1, num_images_per_prompt, 1)
         prompt_embeds = prompt_embeds.view(bs * num_images_per_prompt, seq, -1)
@@ -1065,14 +1159,61 @@ class StableDiffusionUnifiedPipeline:
         z = dist.sample(generator)
         return (z * vae.config.scaling_factor).to(image.dtype)
 
-    def _get_add_time_ids(self, original_size, crops_coords_top_left, target_size, dtype):
-        """sd_unified_pipeline.py:979-1014."""
-        ids = list(original_size + crops_coords_top_left + target_size)
-        cfg = self.model.base.config
-        passed = cfg.addition_time_embed_dim * len(ids) + (cfg.projection_class_embeddings_input_dim
-                                                          - 6 * cfg.addition_time_embed_dim)
-        expected = self.model.base.add_embedding.linear_1.in_features
-        if passed != expected:
-            raise ValueError(f"Model expects an added time embedding vector of length {expected}, "
-                             f"but a vector of {passed} was created.")
-        return torch.tensor([ids], dtype=dtype)
+    def _get_add_time_ids(self, original_size, crops_coords_top_left, target_size, dtype, aesthetic_score=None,
+                          negative_aesthetic_score=None):
+        """sd_unified_pipeline.py:979-1014.  With `aesthetic_score` (the refiner: diffusers' img2img form with
+        requires_aesthetics_score) the score takes target_size's place and the result is (ids, negative ids)."""
+        cfg = self._unet(self.model).config
+        ad = cfg.addition_time_embed_dim
+        pooled = getattr(cfg, "pooled_projection_dim", None) or cfg.projection_class_embeddings_input_dim - 6 * ad
+        if aesthetic_score is None:
+            ids = list(original_size + crops_coords_top_left + target_size)
+            neg = None
+        else:
+            ids = list(original_size + crops_coords_top_left + (aesthetic_score,))
+            neg = list(original_size + crops_coords_top_left + (negative_aesthetic_score,))
+        passed = ad * len(ids) + pooled
+        expected = self._unet(self.model).add_embedding.linear_1.in_features
+        if expected < passed and passed - expected == ad:
+            raise ValueError(f"Model expects an added time embedding vector of length {expected}, but a vector of "
+                             f"{passed} was created. Please make sure to disable `requires_aesthetics_score` with "
+                             "`pipe.register_to_config(requires_aesthetics_score=False)` to make sure `target_size` "
+                             f"{target_size} is correctly used by the model.")
+        elif passed != expected:
+            raise ValueError(f"Model expects an added time embedding vector of length {expected}, but a vector of "
+                             f"{passed} was created. The model has an incorrect config. Please check "
+                             "`unet.config.time_embedding_type` and `text_encoder_2.config.projection_dim`.")
+        if neg is None:
+            return torch.tensor([ids], dtype=dtype)
+        return torch.tensor([ids], dtype=dtype), torch.tensor([neg], dtype=dtype)
+
+    def _ensemble_of_experts(self, call):
+        """`refiner_start=r`: the base denoises the timesteps at or above the cut-off and the refiner the rest, as two
+        calls of this pipeline with the same prompts, seed and steps -- A: base, denoising_end=r, latents out;
+        B: use_refiner=True, image = A's latents, denoising_start=r (the scheduler is set again at the hand-off, as two
+        diffusers calls do).  The latents stay where A left them (on the device)."""
+        r = call.pop("refiner_start")
+        if isinstance(r, bool) or not isinstance(r, (int, float)) or not 0.0 < float(r) < 1.0:
+            raise ValueError(f"refiner_start must lie in (0, 1), got {r!r}")
+        if call["use_refiner"]:
+            raise ValueError("refiner_start runs base and refiner in one call: it cannot be combined with use_refiner=True")
+        if call["denoising_end"] is not None:
+            raise ValueError("refiner_start sets the base's denoising_end itself: pass one or the other")
+        model = call["model"]
+        if getattr(model, "refiner", None) is None:
+            raise ValueError("refiner_start given but the model has no refiner (SDModelWrapper.load_refiner)")
+        if getattr(model, "text_encoder_2", None) is None or getattr(model, "tokenizer_2", None) is None:
+            raise ValueError("the refiner reads text_encoder_2 / tokenizer_2, which this model does not have")
+        if call["prompt_embeds"] is not None:
+            raise ValueError("refiner_start needs prompts: base and refiner take different embeddings")
+        if call["mask_image"] is not None:
+            raise NotImplementedError("refiner_start with inpainting is not supported")
+        saved = self.output_type
+        self.output_type = "latents"
+        try:
+            latents = self(**dict(call, denoising_end=float(r)))
+        finally:
+            self.output_type = saved
+        # the refiner's half: no start latents, ControlNet or IP-Adapter inputs of the base's
+        return self(**dict(call, use_refiner=True, image=latents, denoising_start=float(r), latents=None, strength=1.0,
+                           control_image=None, ip_adapter_image=None, ip_adapter_image_embeds=None))
