@@ -299,13 +299,9 @@ int sd_clip_memory(const sd_clip* c, int64_t* weight_bytes, int64_t* workspace_b
 /* latent_model_input = cat([latents]*2) * in_scale   (in_scale = 1 for DDIM / DPM++) */
 int sd_cfg_duplicate(const void* latents, void* out2b, int64_t n_per_batch, int B, float in_scale,
                      void* stream);
-/* noise = u + g (t - u);  x <- c_x * x + c_eps * noise   (DDIM eta=0 written as an affine update;
- * coefficients computed on the host by the scheduler).  noise_pred_2b = [uncond ; text]. */
-int sd_cfg_ddim_step(const void* noise_pred_2b, void* latents, int64_t n, float guidance_scale,
-                     float c_x, float c_eps, void* stream);
 
-/* The same for every scheduler of the reference's registry (stable_diffusion.py:199-227) whose update
- * is linear in (x, eps, previous x0 prediction) -- DDIM, Euler, DPM-Solver++(2M):
+/* The CFG combine and the update of every scheduler of the reference's registry (stable_diffusion.py:199-227) whose
+ * update is linear in (x, eps, previous x0 prediction) -- DDIM, Euler, DPM-Solver++(2M); noise_pred_2b = [uncond ; text]:
  *   eps = u + g (t - u);  x0 = h_x x + h_eps eps;  x <- c_x x + c_eps eps + c_hist hist;  hist <- x0
  * hist_f32 [n] is the scheduler's history (nullable: then c_hist / h_* are ignored).  Coefficients
  * come from the host scheduler (schedulers.py `fused_plan`), replacing scheduler.step at :489. */

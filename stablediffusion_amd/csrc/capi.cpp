@@ -518,12 +518,6 @@ int sd_inpaint_blend(void* latents, const void* image_latents, const void* noise
                                 static_cast<const half_t*>(noise), static_cast<const half_t*>(mask), a, b, B, C,
                                 (long)H * W, static_cast<hipStream_t>(stream));
 }
-int sd_cfg_ddim_step(const void* noise_pred_2b, void* latents, int64_t n, float guidance_scale, float c_x,
-                     float c_eps, void* stream) {
-    if (!noise_pred_2b || !latents) { set_error("null argument"); return SD_ERR_INVALID; }
-    return launch_cfg_ddim(static_cast<const half_t*>(noise_pred_2b), static_cast<half_t*>(latents), (long)n,
-                           guidance_scale, c_x, c_eps, static_cast<hipStream_t>(stream));
-}
 
 // ------------------------------------------------------------------------------------------- probe
 int sd_probe_mfma(int iters, float* tflops, void* stream) {

@@ -361,8 +361,6 @@ int launch_scale_f16(half_t* x, long n, float scale, hipStream_t s);     // x *=
 int launch_image_to_uint8(const half_t* img, unsigned char* out, int B, int C, long HW, hipStream_t s);
 int launch_cfg_linear(const half_t* eps2b, half_t* lat, float* hist, long n, float g, float cx, float ce, float ch,
                       float hx, float he, hipStream_t s);
-int launch_cfg_ddim(const half_t* eps2b, half_t* lat, long n, float g, float cx, float ce,
-                    hipStream_t s);
 // den = dx x + dout m, x <- pden den + pnoise noise (m: model_out, or its CFG combine when rows == 2); noise / denoised
 // nullable.  The scheduler step of LCMScheduler in one launch.
 int launch_lcm_step(const half_t* model_out, int rows, half_t* lat, const half_t* noise, half_t* denoised, long n, float g,

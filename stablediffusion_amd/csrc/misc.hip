@@ -328,17 +328,8 @@ __global__ void dup_f32_kernel(const float* __restrict__ x, float* __restrict__ 
     out[i] = v;
     out[n + i] = v;
 }
-// sd_unified_pipeline.py:484-489 with DDIM eta=0 folded into x <- cx*x + ce*eps.
-__global__ void cfg_ddim_kernel(const half_t* __restrict__ eps2b, half_t* __restrict__ lat, long n,
-                                float g, float cx, float ce) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float eu = (float)eps2b[i], et = (float)eps2b[n + i];
-    const float e = (float)(half_t)(g * (et - eu) + eu);
-    lat[i] = (half_t)(cx * (float)lat[i] + ce * e);
-}
 
-// Any scheduler whose update is linear in (x, eps, previous x0 prediction): DDIM, Euler, DPM-Solver++(2M).
+// sd_unified_pipeline.py:484-489 for any scheduler whose update is linear in (x, eps, previous x0 prediction): DDIM, Euler, DPM-Solver++(2M).
 //   eps = u + g (t - u);  x0 = hx x + he eps;  x <- cx x + ce eps + ch hist;  hist <- x0
 // (hist fp32, like the host schedulers keep their history; null when the scheduler has none)
 __global__ void cfg_linear_kernel(const half_t* __restrict__ eps2b, half_t* __restrict__ lat,
@@ -1089,10 +1080,10 @@ int launch_dup_f32(const float* x, float* out, long n, hipStream_t s) {
     SD_HIP_CHECK(hipGetLastError());
     return 0;
 }
-int launch_cfg_ddim(const half_t* eps2b, half_t* lat, long n, float g, float cx, float ce, hipStream_t s) {
-    hipLaunchKernelGGL(cfg_ddim_kernel, grid1d(n), dim3(256), 0, s, eps2b, lat, n, g, cx, ce);
-    SD_HIP_CHECK(hipGetLastError());
-    return 0;
+// What the VEC kernels ask of a launch: n % 8 == 0 and every base (a null one passes) 16-byte aligned.
+static bool vec8_ok(long n, const void* a, const void* b, const void* c, const void* d = nullptr) {
+    return n % 8 == 0 && ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c) |
+                           reinterpret_cast<uintptr_t>(d)) & 15) == 0;
 }
 int launch_cfg_linear(const half_t* eps2b, half_t* lat, float* hist, long n, float g, float cx, float ce, float ch,
                       float hx, float he, hipStream_t s) {
@@ -1102,8 +1093,7 @@ int launch_cfg_linear(const half_t* eps2b, half_t* lat, float* hist, long n, flo
 }
 int launch_lcm_step(const half_t* model_out, int rows, half_t* lat, const half_t* noise, half_t* denoised, long n, float g,
                     float dx, float dout, float pden, float pnoise, hipStream_t s) {
-    const bool vec = n % 8 == 0 && ((reinterpret_cast<uintptr_t>(model_out) | reinterpret_cast<uintptr_t>(lat) |
-                                     reinterpret_cast<uintptr_t>(noise) | reinterpret_cast<uintptr_t>(denoised)) & 15) == 0;
+    const bool vec = vec8_ok(n, model_out, lat, noise, denoised);
     const dim3 grid = grid1d(vec ? n / 8 : n);
 #define SD_LCM_LAUNCH(R, V) \
     hipLaunchKernelGGL((lcm_step_kernel<R, V>), grid, dim3(256), 0, s, model_out, lat, noise, denoised, n, g, dx, dout, pden, pnoise)
@@ -1121,9 +1111,7 @@ int launch_sched_affine_step(const half_t* model_out, int rows, half_t* lat, con
         for (int w = 0; w < p.n_writes; ++w) any = any || p.write[w][k] != 0.0;
         if (any) use |= 1u << k;
     }
-    const bool vec = n % 8 == 0 && stride % 4 == 0 &&
-                     ((reinterpret_cast<uintptr_t>(model_out) | reinterpret_cast<uintptr_t>(lat) |
-                       reinterpret_cast<uintptr_t>(noise) | reinterpret_cast<uintptr_t>(bank)) & 15) == 0;
+    const bool vec = stride % 4 == 0 && vec8_ok(n, model_out, lat, noise, bank);
     const dim3 grid = grid1d(vec ? n / 8 : n);
 #define SD_STEP_LAUNCH(R, V) \
     hipLaunchKernelGGL((sched_affine_kernel<R, V>), grid, dim3(256), 0, s, model_out, lat, noise, bank, stride, n, g, p, use)
@@ -1161,8 +1149,7 @@ int launch_cfg_rescale_linear(const half_t* eps2b, half_t* lat, float* hist, int
     RsStat* part = rs_workspace(B, s);
     if (!part) { set_error("cfg_rescale_linear: no device memory for the chunk summaries"); return 1; }
     const long total = (long)B * n;
-    const bool vec = n % 8 == 0 && ((reinterpret_cast<uintptr_t>(eps2b) | reinterpret_cast<uintptr_t>(lat) |
-                                     reinterpret_cast<uintptr_t>(hist)) & 15) == 0;
+    const bool vec = vec8_ok(n, eps2b, lat, hist);
     long parts = (n + RS_MIN_CHUNK - 1) / RS_MIN_CHUNK;
     if (parts > RS_MAX_PARTS) parts = RS_MAX_PARTS;
     long chunk = (n + parts - 1) / parts;

@@ -21,12 +21,14 @@ Differences from the reference, on purpose:
 """
 from __future__ import annotations
 
+import ctypes as C
 import os
+from types import SimpleNamespace
 from typing import Any, Dict, List, Optional, Union
 
 import torch
 
-from . import schedulers as _sched
+from . import _lib, schedulers as _sched
 from .image_processor import VaeImageProcessor
 
 
@@ -301,22 +303,30 @@ class SDModelWrapper:
         self.scheduler_name = scheduler_name
 
 
+def _ptr(t: torch.Tensor):
+    return C.c_void_p(t.data_ptr())
+
+
+def _stream():
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _check(lib, rc):
+    if rc:
+        raise RuntimeError(lib.sd_last_error().decode())
+
+
 def convert_pt_to_numpy(images: torch.Tensor):
     """`/root/reference/runpod-worker/handler_logic.py:21-29`: decoded images -> list of HWC uint8 arrays.
     fp16 CUDA tensors go through the engine's `sd_images_to_uint8` (one kernel, one [B,H,W,C] byte copy
     to the host instead of four torch ops and one copy per image; same roundings and truncation as
     the reference's op sequence); anything else runs that op sequence itself."""
     if images.is_cuda and images.dtype == torch.float16 and images.dim() == 4 and images.shape[1] <= 4:
-        import ctypes as C
-        from . import _lib
         lib = _lib.load()
         images = images.contiguous()
         B, Cc, H, W = images.shape
         out = torch.empty(B, H, W, Cc, dtype=torch.uint8, device=images.device)
-        rc = lib.sd_images_to_uint8(C.c_void_p(images.data_ptr()), C.c_void_p(out.data_ptr()), B, Cc, H, W,
-                                    C.c_void_p(torch.cuda.current_stream().cuda_stream))
-        if rc:
-            raise RuntimeError(lib.sd_last_error().decode())
+        _check(lib, lib.sd_images_to_uint8(_ptr(images), _ptr(out), B, Cc, H, W, _stream()))
         host = out.cpu().numpy()
         return [host[i] for i in range(B)]
     np_images = []
@@ -374,6 +384,7 @@ class StableDiffusionUnifiedPipeline:
         # False keeps the engine's duplicate-then-forward form
         self.cfg_share = True
         self._use_refiner = False            # set per call: the UNet of this call is model.refiner
+        self.is_inpaint = False              # set per call
 
     def _unet(self, model):
         """The UNet this call runs: `.base`, or `.refiner` under use_refiner=True."""
@@ -639,7 +650,42 @@ class StableDiffusionUnifiedPipeline:
             prompt_embeds = torch.cat([negative_prompt_embeds, prompt_embeds], dim=0)
         prompt_embeds = prompt_embeds.to(self.device)
 
-        # ---- denoising loop (:465-507) ----
+        latents = self._denoise(model, latents, timesteps, prompt_embeds, cross_attention_kwargs, added_cond_kwargs,
+                                tc_kwargs, guidance_scale, guidance_rescale, seed, control=control,
+                                controlnet_conditioning_scale=controlnet_conditioning_scale,
+                                control_guidance_start=control_guidance_start, control_guidance_end=control_guidance_end,
+                                mask=mask, masked_image_latents=masked_image_latents_2b, image_latents=image_latents,
+                                image_noise=noise)
+
+        # ---- decode (:511-529) ----
+        if self.output_type == "pt":
+            cfg = model.vae.config
+            mean = getattr(cfg, "latents_mean", None)
+            std = getattr(cfg, "latents_std", None)
+            if mean is not None and std is not None:
+                m = torch.tensor(mean).view(1, -1, 1, 1).to(latents.device, latents.dtype)
+                s = torch.tensor(std).view(1, -1, 1, 1).to(latents.device, latents.dtype)
+                latents = latents * s / cfg.scaling_factor + m
+            else:
+                latents = latents / cfg.scaling_factor
+            images = model.vae.decode(latents, return_dict=False)[0]
+        elif self.output_type == "latents":
+            images = latents
+        else:
+            raise ValueError(f"Unknown output_type = '{self.output_type}'")
+        return images
+
+    # ------------------------------------------------------------------------------------------
+    def _denoise(self, model, latents, timesteps, prompt_embeds, cross_attention_kwargs, added_cond_kwargs, tc_kwargs,
+                 guidance_scale, guidance_rescale, seed, control=None, controlnet_conditioning_scale=1.0,
+                 control_guidance_start=0.0, control_guidance_end=1.0, mask=None, masked_image_latents=None,
+                 image_latents=None, image_noise=None):
+        """The denoising loop (:465-507): `timesteps` over `latents`, the scheduler's update on the device where
+        `_device_step_kind` finds one (`_device_iteration`) and in `scheduler.step` otherwise.  `tc_kwargs` is the
+        guidance-embedded UNet's `timestep_cond`, `control` the prepared ControlNet image; `mask`, `masked_image_latents`
+        (doubled under CFG), `image_latents` and `image_noise` are the inpainting tensors."""
+        unet = self._unet(model)
+        num_channels_unet = unet.config.in_channels
         # The reference iterates over the device tensor `timesteps`; reading each element on the host
         # (scheduler.step does int(t)) is a stream-ordered device->host copy, i.e. a full sync behind
         # the UNet forward of every step.  One copy of the schedule to the host before the loop
@@ -662,66 +708,50 @@ class StableDiffusionUnifiedPipeline:
             if prompt_embeds.device.type == "cuda" and (prompt_embeds.dtype != torch.float16 or not prompt_embeds.is_contiguous()):
                 prompt_embeds = prompt_embeds.to(torch.float16).contiguous()
             kv_cache(True)
-        fused_step = self._fused_step_available(model, latents, num_channels_unet)
+        kind = self._device_step_kind(model, latents, num_channels_unet, guidance_rescale)
+        # what the device steps keep from one iteration to the next: "linear"'s fp32 history (made by the first plan that
+        # reads one), "affine"'s fp32 bank of `affine_slots` latents-sized slots, LCM's noise generator
+        state = SimpleNamespace(hist=None, bank=None, gen=None)
         # LCMScheduler: one noise draw per non-final step from a generator of this call's own (seeded with `seed`), made the
         # same way at the same point whether the step then runs on the device (sd_lcm_step) or in scheduler.step
         lcm = isinstance(model.scheduler, _sched.LCMScheduler)
-        lcm_step = lcm and self._lcm_step_available(model, latents, num_channels_unet, guidance_rescale)
-        loop_gen = lcm_final_t = None
         if lcm:
             # the scheduler's own last step adds no noise (a loop cut short by denoising_end does not reach it)
             lcm_final_t = float(model.scheduler.timesteps[-1])
-            loop_gen = torch.Generator(device=latents.device)
+            state.gen = torch.Generator(device=latents.device)
             if seed is not None:
-                loop_gen.manual_seed(int(seed))
+                state.gen.manual_seed(int(seed))
             else:
-                loop_gen.seed()
-        # euler_a, DPM++ 2M SDE, PNDM, UniPC: one device kernel per step over the latents and an fp32 history bank of this
-        # loop's own.  The stochastic two draw their noise here as their `step` does: from the global generator, once per
-        # step (the last included, whose noise coefficient is 0), so the device and the host loop consume the same stream
-        affine_step = (not fused_step and not lcm_step
-                       and self._affine_step_available(model, latents, num_channels_unet, guidance_rescale))
-        affine_bank = None
-        if affine_step and model.scheduler.affine_slots:
-            affine_bank = torch.empty((model.scheduler.affine_slots,) + tuple(latents.shape), device=latents.device,
-                                      dtype=torch.float32)
-        fused_hist = None
+                state.gen.seed()
+        if kind == "affine" and model.scheduler.affine_slots:
+            state.bank = torch.empty((model.scheduler.affine_slots,) + tuple(latents.shape), device=latents.device,
+                                     dtype=torch.float32)
         blend = None
-        if (fused_step or lcm_step or affine_step) and self.is_inpaint:       # 4-channel inpainting: device-side blend after every step
+        if kind and self.is_inpaint:         # 4-channel inpainting: device-side blend after every step
             f16 = lambda x: x.to(device=latents.device, dtype=torch.float16).contiguous()
             m1 = mask.chunk(2)[0] if self.do_classifier_free_guidance else mask
-            blend = (f16(image_latents), f16(noise), f16(m1.expand(latents.shape[0], 1, *latents.shape[2:])))
+            blend = (f16(image_latents), f16(image_noise), f16(m1.expand(latents.shape[0], 1, *latents.shape[2:])))
         try:
             for i, t in enumerate(timesteps_host):
                 cn_kwargs = {} if control is None else dict(controlnet_cond=control,
                                                             controlnet_conditioning_scale=cn_scales[i])
-                last = i == len(timesteps_host) - 1
+                # the step's noise, drawn before the forward.  The affine schedulers that add noise draw it as their `step`
+                # does: from the global generator, once per step (the last included, whose noise coefficient is 0), so the
+                # device and the host loop consume the same stream
                 step_noise = None
                 if lcm and t != lcm_final_t:
-                    step_noise = torch.randn(latents.shape, dtype=latents.dtype, device=latents.device, generator=loop_gen)
-                if lcm_step:
-                    latents = self._lcm_iteration(model, latents, step_noise, t, prompt_embeds, cross_attention_kwargs,
-                                                  added_cond_kwargs, guidance_scale, **cn_kwargs, **tc_kwargs)
-                    if blend is not None:
-                        a, b = (1.0, 0.0) if last else model.scheduler.add_noise_coefficients(timesteps_host[i + 1])
-                        self._device_inpaint_blend(model, latents, blend, a, b, with_noise=not last)
-                    continue
-                if affine_step:
-                    if getattr(model.scheduler, "affine_noise", False):
-                        step_noise = torch.randn(latents.shape, device=latents.device, dtype=latents.dtype)
-                    latents = self._affine_iteration(model, latents, affine_bank, step_noise, t, prompt_embeds,
+                    step_noise = torch.randn(latents.shape, dtype=latents.dtype, device=latents.device, generator=state.gen)
+                if kind == "affine" and getattr(model.scheduler, "affine_noise", False):
+                    step_noise = torch.randn(latents.shape, device=latents.device, dtype=latents.dtype)
+                if kind:
+                    # "linear" leaves `timestep_cond` out, which the host path and the other two kinds pass.  Kept as found;
+                    # it cannot show today (a guidance-embedded UNet turns CFG off, and "linear" needs CFG)
+                    unet_kwargs = cn_kwargs if kind == "linear" else {**cn_kwargs, **tc_kwargs}
+                    latents = self._device_iteration(kind, state, model, latents, step_noise, t, prompt_embeds,
                                                      cross_attention_kwargs, added_cond_kwargs, guidance_scale,
-                                                     **cn_kwargs, **tc_kwargs)
+                                                     guidance_rescale, **unet_kwargs)
                     if blend is not None:
-                        a, b = (1.0, 0.0) if last else model.scheduler.add_noise_coefficients(timesteps_host[i + 1])
-                        self._device_inpaint_blend(model, latents, blend, a, b, with_noise=not last)
-                    continue
-                if fused_step:
-                    latents, fused_hist = self._fused_cfg_iteration(model, latents, fused_hist, t, prompt_embeds,
-                                                                    cross_attention_kwargs, added_cond_kwargs,
-                                                                    guidance_scale, guidance_rescale=guidance_rescale,
-                                                                    **cn_kwargs)
-                    if blend is not None:
+                        last = i == len(timesteps_host) - 1
                         a, b = (1.0, 0.0) if last else model.scheduler.add_noise_coefficients(timesteps_host[i + 1])
                         self._device_inpaint_blend(model, latents, blend, a, b, with_noise=not last)
                     continue
@@ -729,7 +759,7 @@ class StableDiffusionUnifiedPipeline:
                 latent_model_input = model.scheduler.scale_model_input(latent_model_input, t)
                 if self.is_inpaint and num_channels_unet == 9:
                     latent_model_input = torch.cat([latent_model_input, mask.to(latent_model_input.dtype),
-                                                    masked_image_latents_2b.to(latent_model_input.dtype)], dim=1)
+                                                    masked_image_latents.to(latent_model_input.dtype)], dim=1)
                 noise_pred = unet(latent_model_input, t, prompt_embeds,
                                         cross_attention_kwargs=cross_attention_kwargs,
                                         added_cond_kwargs=added_cond_kwargs, return_dict=False, **cn_kwargs, **tc_kwargs)[0]
@@ -746,43 +776,25 @@ class StableDiffusionUnifiedPipeline:
                     init_latents_proper = image_latents
                     init_mask = mask.chunk(2)[0] if self.do_classifier_free_guidance else mask
                     if i < len(timesteps_host) - 1:
-                        init_latents_proper = model.scheduler.add_noise(init_latents_proper, noise,
+                        init_latents_proper = model.scheduler.add_noise(init_latents_proper, image_noise,
                                                                         torch.as_tensor([timesteps_host[i + 1]]))
                     latents = ((1 - init_mask) * init_latents_proper.float() + init_mask * latents.float()).to(latents.dtype)
-
         finally:
             if kv_cache is not None:
                 kv_cache(False)
+        return latents
 
-        # ---- decode (:511-529) ----
-        if self.output_type == "pt":
-            cfg = model.vae.config
-            mean = getattr(cfg, "latents_mean", None)
-            std = getattr(cfg, "latents_std", None)
-            if mean is not None and std is not None:
-                m = torch.tensor(mean).view(1, -1, 1, 1).to(latents.device, latents.dtype)
-                s = torch.tensor(std).view(1, -1, 1, 1).to(latents.device, latents.dtype)
-                latents = latents * s / cfg.scaling_factor + m
-            else:
-                latents = latents / cfg.scaling_factor
-            images = model.vae.decode(latents, return_dict=False)[0]
-        elif self.output_type == "latents":
-            images = latents
-        else:
-            raise ValueError(f"Unknown output_type = '{self.output_type}'")
-        return images
-
-    # ------------------------------------------------------------------------------------------
     def _device_inpaint_blend(self, model, latents, blend, a, b, with_noise):
-        import ctypes as C
         lib = self._unet(model)._lib
         img, noise, m = blend
         B, Cc, H, W = latents.shape
-        rc = lib.sd_inpaint_blend(C.c_void_p(latents.data_ptr()), C.c_void_p(img.data_ptr()),
-                                  C.c_void_p(noise.data_ptr()) if with_noise else None, C.c_void_p(m.data_ptr()),
-                                  float(a), float(b), B, Cc, H, W, C.c_void_p(torch.cuda.current_stream().cuda_stream))
-        if rc:
-            raise RuntimeError(lib.sd_last_error().decode())
+        _check(lib, lib.sd_inpaint_blend(_ptr(latents), _ptr(img), _ptr(noise) if with_noise else None, _ptr(m),
+                                         float(a), float(b), B, Cc, H, W, _stream()))
+
+    def _engine_step_possible(self, model, latents, num_channels_unet) -> bool:
+        """What every device step needs: the HIP engine, fp16 CUDA latents and no 9-channel inpainting UNet."""
+        return ((not self.is_inpaint or num_channels_unet == 4) and hasattr(self._unet(model), "_lib")
+                and latents.is_cuda and latents.dtype == torch.float16)
 
     def _fused_step_available(self, model, latents, num_channels_unet=4) -> bool:
         """CFG combine + scheduler update as ONE device kernel each side of the UNet:
@@ -791,125 +803,97 @@ class StableDiffusionUnifiedPipeline:
         (`sd_cfg_duplicate`, `sd_cfg_linear_step`, or `sd_cfg_rescale_linear_step` when guidance_rescale > 0),
         and for inpainting with a 4-channel UNet the mask blend of `:492-506` follows as a third kernel (`sd_inpaint_blend`).  Only with CFG on the HIP engine;
         9-channel inpainting UNets and non-CFG calls take the generic path."""
-        return (self.do_classifier_free_guidance and (not self.is_inpaint or num_channels_unet == 4)
-                and hasattr(model.scheduler, "fused_plan") and getattr(model.scheduler, "supports_fused", True)
-                and hasattr(model.scheduler, "add_noise_coefficients")
-                and hasattr(self._unet(model), "_lib") and latents.is_cuda and latents.dtype == torch.float16)
+        return (self.do_classifier_free_guidance and hasattr(model.scheduler, "fused_plan")
+                and getattr(model.scheduler, "supports_fused", True) and hasattr(model.scheduler, "add_noise_coefficients")
+                and self._engine_step_possible(model, latents, num_channels_unet))
 
-    def _fused_cfg_iteration(self, model, latents, hist, t, prompt_embeds, cross_attention_kwargs, added_cond_kwargs,
-                             guidance_scale, guidance_rescale=0.0, **unet_kwargs):
-        import ctypes as C
-        lib = self._unet(model)._lib
-        plan = model.scheduler.fused_plan(t)
+    def _lcm_step_available(self, model, latents, num_channels_unet=4, guidance_rescale=0.0) -> bool:
+        """LCMScheduler's step as one device kernel (`sd_lcm_step`: guidance combine, boundary condition, re-noising) on
+        the HIP engine with fp16 CUDA latents -- with or without CFG, unlike `_fused_step_available`.  9-channel
+        inpainting UNets and guidance_rescale (a per-sample statistic) take scheduler.step."""
+        return not guidance_rescale > 0.0 and self._engine_step_possible(model, latents, num_channels_unet)
+
+    def _affine_step_available(self, model, latents, num_channels_unet=4, guidance_rescale=0.0) -> bool:
+        """The step of a scheduler with an `affine_plan` (euler_a, DPM++ 2M SDE, PNDM, UniPC) as one device kernel
+        (`sd_sched_affine_step`: guidance combine, update, history writes) on the HIP engine with fp16 CUDA latents, with
+        or without CFG.  9-channel inpainting UNets and guidance_rescale (a per-sample statistic) take scheduler.step."""
+        return (hasattr(model.scheduler, "affine_plan") and not guidance_rescale > 0.0
+                and self._engine_step_possible(model, latents, num_channels_unet))
+
+    def _device_step_kind(self, model, latents, num_channels_unet, guidance_rescale):
+        """The device step of this call's loop (the table in DESIGN.md): "linear" (sd_cfg_linear_step, or
+        sd_cfg_rescale_linear_step under guidance_rescale), "lcm" (sd_lcm_step), "affine" (sd_sched_affine_step), or None
+        for the host path (scheduler.step).  The three predicates are the switches that turn a path off."""
+        if self._fused_step_available(model, latents, num_channels_unet):
+            return "linear"
+        if (isinstance(model.scheduler, _sched.LCMScheduler)
+                and self._lcm_step_available(model, latents, num_channels_unet, guidance_rescale)):
+            return "lcm"
+        if self._affine_step_available(model, latents, num_channels_unet, guidance_rescale):
+            return "affine"
+        return None
+
+    def _device_iteration(self, kind, state, model, latents, noise, t, prompt_embeds, cross_attention_kwargs,
+                          added_cond_kwargs, guidance_scale, guidance_rescale=0.0, **unet_kwargs):
+        """One iteration with the scheduler's update on the device: the plan from the scheduler, the UNet forward, one
+        step entry of the engine over a copy of the latents, the plan committed.  -> the new latents."""
+        sched, unet = model.scheduler, self._unet(model)
+        lib = unet._lib
+        plan = sched.affine_plan(t) if kind == "affine" else sched.fused_plan(t)
         latents = latents.contiguous()
-        B = latents.shape[0]
-        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        noise_pred = self._cfg_forward(model, latents, plan.in_scale, t, prompt_embeds, cross_attention_kwargs,
-                                       added_cond_kwargs, **unet_kwargs)
-        if plan.use_hist and hist is None:
-            hist = torch.zeros(latents.shape, device=latents.device, dtype=torch.float32)
-        out = latents.clone()
-        hist_p = C.c_void_p(hist.data_ptr()) if plan.use_hist else None
-        if guidance_rescale > 0.0:
-            # the rescale needs a standard deviation per sample, so it is not affine: its own statistics + update kernels
-            rc = lib.sd_cfg_rescale_linear_step(C.c_void_p(noise_pred.data_ptr()), C.c_void_p(out.data_ptr()), hist_p, B,
-                                                out[0].numel(), float(guidance_scale), float(guidance_rescale), plan.c_x,
-                                                plan.c_eps, plan.c_hist, plan.h_x, plan.h_eps, None, st)
+        rows = 2 if self.do_classifier_free_guidance else 1          # ("linear" runs under CFG only)
+        if rows == 2:                                # rows = [uncond ; text], from the un-duplicated latents
+            model_out = self._cfg_forward(model, latents, plan.in_scale, t, prompt_embeds, cross_attention_kwargs,
+                                          added_cond_kwargs, **unet_kwargs)
         else:
-            rc = lib.sd_cfg_linear_step(C.c_void_p(noise_pred.data_ptr()), C.c_void_p(out.data_ptr()), hist_p, out.numel(),
-                                        float(guidance_scale), plan.c_x, plan.c_eps, plan.c_hist, plan.h_x, plan.h_eps, st)
-        if rc:
-            raise RuntimeError(lib.sd_last_error().decode())
-        model.scheduler.fused_commit()
-        return out, hist
+            # "lcm" (guidance-embedded: timestep_cond in unet_kwargs, or no guidance) feeds the latents as they are; its
+            # scale_model_input is the identity
+            x = sched.scale_model_input(latents, t) if kind == "affine" else latents
+            model_out = unet(x, t, prompt_embeds, cross_attention_kwargs=cross_attention_kwargs,
+                             added_cond_kwargs=added_cond_kwargs, return_dict=False, **unet_kwargs)[0]
+        if kind == "linear" and plan.use_hist and state.hist is None:
+            state.hist = torch.zeros(latents.shape, device=latents.device, dtype=torch.float32)
+        out = latents.clone()
+        n, g = out.numel(), float(guidance_scale)
+        if kind == "linear":
+            hist_p = _ptr(state.hist) if plan.use_hist else None
+            if guidance_rescale > 0.0:
+                # the rescale needs a standard deviation per sample, so it is not affine: its own statistics + update kernels
+                rc = lib.sd_cfg_rescale_linear_step(_ptr(model_out), _ptr(out), hist_p, out.shape[0], out[0].numel(), g,
+                                                    float(guidance_rescale), plan.c_x, plan.c_eps, plan.c_hist, plan.h_x,
+                                                    plan.h_eps, None, _stream())
+            else:
+                rc = lib.sd_cfg_linear_step(_ptr(model_out), _ptr(out), hist_p, n, g, plan.c_x, plan.c_eps, plan.c_hist,
+                                            plan.h_x, plan.h_eps, _stream())
+        else:
+            noise_p = _ptr(noise.contiguous()) if plan.needs_noise else None
+            if kind == "lcm":
+                rc = lib.sd_lcm_step(_ptr(model_out), rows, _ptr(out), noise_p, None, n, g, plan.d_x, plan.d_out,
+                                     plan.p_den, plan.p_noise, _stream())
+            else:
+                bank_p = _ptr(state.bank) if state.bank is not None else None
+                rc = lib.sd_sched_affine_step(_ptr(model_out), rows, _ptr(out), noise_p, bank_p, n, n, g,
+                                              C.byref(_lib.step_plan(plan)), _stream())
+        _check(lib, rc)
+        (sched.affine_commit if kind == "affine" else sched.fused_commit)()
+        return out
 
     def _cfg_forward(self, model, latents, in_scale, t, prompt_embeds, cross_attention_kwargs, added_cond_kwargs,
                      **unet_kwargs):
         """The UNet forward of one CFG step from the un-duplicated fp16 latents: [2B, ...], negative half first."""
-        import ctypes as C
-        lib = self._unet(model)._lib
-        B = latents.shape[0]
         unet = self._unet(model)
+        B = latents.shape[0]
         if not unet_kwargs and hasattr(unet, "forward_cfg") and getattr(unet, "controlnet", None) is None:
             # the engine takes the un-duplicated latents: no 2B-row copy, and the layers in front of the first
             # cross-attention run once per latent
             return unet.forward_cfg(latents, t, prompt_embeds, added_cond_kwargs=added_cond_kwargs,
                                           in_scale=in_scale, share=self.cfg_share)[0]
         # ControlNet calls: duplicate, then the forward that takes the control image
+        lib = unet._lib
         lat2 = torch.empty((2 * B,) + tuple(latents.shape[1:]), device=latents.device, dtype=latents.dtype)
-        rc = lib.sd_cfg_duplicate(C.c_void_p(latents.data_ptr()), C.c_void_p(lat2.data_ptr()),
-                                  latents[0].numel(), B, in_scale, C.c_void_p(torch.cuda.current_stream().cuda_stream))
-        if rc:
-            raise RuntimeError(lib.sd_last_error().decode())
+        _check(lib, lib.sd_cfg_duplicate(_ptr(latents), _ptr(lat2), latents[0].numel(), B, in_scale, _stream()))
         return unet(lat2, t, prompt_embeds, cross_attention_kwargs=cross_attention_kwargs,
                           added_cond_kwargs=added_cond_kwargs, return_dict=False, **unet_kwargs)[0]
-
-    def _lcm_step_available(self, model, latents, num_channels_unet=4, guidance_rescale=0.0) -> bool:
-        """LCMScheduler's step as one device kernel (`sd_lcm_step`: guidance combine, boundary condition, re-noising) on
-        the HIP engine with fp16 CUDA latents -- with or without CFG, unlike `_fused_step_available`.  9-channel
-        inpainting UNets and guidance_rescale (a per-sample statistic) take scheduler.step."""
-        return ((not self.is_inpaint or num_channels_unet == 4) and not guidance_rescale > 0.0
-                and hasattr(self._unet(model), "_lib") and latents.is_cuda and latents.dtype == torch.float16)
-
-    def _lcm_iteration(self, model, latents, noise, t, prompt_embeds, cross_attention_kwargs, added_cond_kwargs,
-                       guidance_scale, **unet_kwargs):
-        import ctypes as C
-        lib = self._unet(model)._lib
-        plan = model.scheduler.fused_plan(t)
-        latents = latents.contiguous()
-        if self.do_classifier_free_guidance:         # an ordinary UNet (LCM-LoRA): rows = [uncond ; text]
-            rows = 2
-            model_out = self._cfg_forward(model, latents, plan.in_scale, t, prompt_embeds, cross_attention_kwargs,
-                                          added_cond_kwargs, **unet_kwargs)
-        else:                                        # guidance-embedded (timestep_cond in unet_kwargs), or no guidance
-            rows = 1
-            model_out = self._unet(model)(latents, t, prompt_embeds, cross_attention_kwargs=cross_attention_kwargs,
-                                   added_cond_kwargs=added_cond_kwargs, return_dict=False, **unet_kwargs)[0]
-        out = latents.clone()
-        noise_p = C.c_void_p(noise.contiguous().data_ptr()) if plan.needs_noise else None
-        rc = lib.sd_lcm_step(C.c_void_p(model_out.data_ptr()), rows, C.c_void_p(out.data_ptr()), noise_p, None, out.numel(),
-                             float(guidance_scale), plan.d_x, plan.d_out, plan.p_den, plan.p_noise,
-                             C.c_void_p(torch.cuda.current_stream().cuda_stream))
-        if rc:
-            raise RuntimeError(lib.sd_last_error().decode())
-        model.scheduler.fused_commit()
-        return out
-
-    def _affine_step_available(self, model, latents, num_channels_unet=4, guidance_rescale=0.0) -> bool:
-        """The step of a scheduler with an `affine_plan` (euler_a, DPM++ 2M SDE, PNDM, UniPC) as one device kernel
-        (`sd_sched_affine_step`: guidance combine, update, history writes) on the HIP engine with fp16 CUDA latents, with
-        or without CFG.  9-channel inpainting UNets and guidance_rescale (a per-sample statistic) take scheduler.step."""
-        inpaint = getattr(self, "is_inpaint", False)            # (set by a call: a fresh pipeline has not inpainted)
-        return (hasattr(model.scheduler, "affine_plan") and (not inpaint or num_channels_unet == 4)
-                and not guidance_rescale > 0.0 and hasattr(self._unet(model), "_lib") and latents.is_cuda
-                and latents.dtype == torch.float16)
-
-    def _affine_iteration(self, model, latents, bank, noise, t, prompt_embeds, cross_attention_kwargs, added_cond_kwargs,
-                          guidance_scale, **unet_kwargs):
-        import ctypes as C
-        from ._lib import step_plan
-        lib = self._unet(model)._lib
-        plan = model.scheduler.affine_plan(t)
-        latents = latents.contiguous()
-        if self.do_classifier_free_guidance:         # rows = [uncond ; text], from the un-duplicated latents
-            rows = 2
-            model_out = self._cfg_forward(model, latents, plan.in_scale, t, prompt_embeds, cross_attention_kwargs,
-                                          added_cond_kwargs, **unet_kwargs)
-        else:
-            rows = 1
-            model_out = self._unet(model)(model.scheduler.scale_model_input(latents, t), t, prompt_embeds,
-                                   cross_attention_kwargs=cross_attention_kwargs, added_cond_kwargs=added_cond_kwargs,
-                                   return_dict=False, **unet_kwargs)[0]
-        out = latents.clone()
-        noise_p = C.c_void_p(noise.contiguous().data_ptr()) if plan.needs_noise else None
-        bank_p = C.c_void_p(bank.data_ptr()) if bank is not None else None
-        rc = lib.sd_sched_affine_step(C.c_void_p(model_out.data_ptr()), rows, C.c_void_p(out.data_ptr()), noise_p, bank_p,
-                                      out.numel(), out.numel(), float(guidance_scale), C.byref(step_plan(plan)),
-                                      C.c_void_p(torch.cuda.current_stream().cuda_stream))
-        if rc:
-            raise RuntimeError(lib.sd_last_error().decode())
-        model.scheduler.affine_commit()
-        return out
 
     @staticmethod
     def control_image_processor(model):

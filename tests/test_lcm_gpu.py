@@ -357,8 +357,8 @@ def _model(ucfg, seed=11):
 def _fused_vs_host(model, do_cfg, kw, what):
     pipe = StableDiffusionUnifiedPipeline(do_cfg=do_cfg, device="cuda", output_type="latents")
     used = []
-    real = pipe._lcm_iteration
-    pipe._lcm_iteration = lambda *a, **k: (used.append(1), real(*a, **k))[1]
+    real = pipe._device_iteration
+    pipe._device_iteration = lambda *a, **k: (used.append(1), real(*a, **k))[1]
     fused = pipe(model, seed=3, **kw)
     assert len(used) == 4                                    # the device step ran on every iteration
     other = pipe(model, seed=4, **kw)

@@ -207,8 +207,8 @@ def test_pipeline_end_to_end_against_golden(engine_lib, golden):
     assert rel_l2(lat, d["pipe_latents"]) < TOL
 
 
-def test_cfg_ddim_step_kernels(engine_lib):
-    """sd_cfg_duplicate / sd_cfg_ddim_step against the host scheduler arithmetic."""
+def test_cfg_duplicate_and_linear_step_as_ddim(engine_lib):
+    """sd_cfg_duplicate, and sd_cfg_linear_step without a history (the DDIM form), against the host scheduler arithmetic."""
     import ctypes as C
     from stablediffusion_amd.schedulers import DDIMScheduler
     s = DDIMScheduler()
@@ -225,7 +225,8 @@ def test_cfg_ddim_step_kernels(engine_lib):
     ref = s.step(noise, 501, lat)[0]
     cx, ce = s.step_coefficients(501)
     out = lat.clone()
-    assert engine_lib.sd_cfg_ddim_step(C.c_void_p(eps.data_ptr()), C.c_void_p(out.data_ptr()), lat.numel(), 5.0, cx, ce, st) == 0
+    assert engine_lib.sd_cfg_linear_step(C.c_void_p(eps.data_ptr()), C.c_void_p(out.data_ptr()), None, lat.numel(), 5.0, cx, ce,
+                                         0.0, 0.0, 0.0, st) == 0
     torch.cuda.synchronize()
     assert rel_l2(out, ref) < 1e-3
 

@@ -162,12 +162,12 @@ def _embeds(B, seed=3, L=7):
 
 
 def _device_vs_host(model, kw, calls, what, do_cfg=True, stochastic=False):
-    """The device loop (its `_affine_iteration` counted) against the same pipeline with the path switched off, the global
+    """The device loop (its `_device_iteration` counted) against the same pipeline with the path switched off, the global
     generator seeded alike in front of each."""
     pipe = StableDiffusionUnifiedPipeline(do_cfg=do_cfg, device="cuda", output_type="latents")
     used = []
-    real = pipe._affine_iteration
-    pipe._affine_iteration = lambda *a, **k: (used.append(1), real(*a, **k))[1]
+    real = pipe._device_iteration
+    pipe._device_iteration = lambda *a, **k: (used.append(1), real(*a, **k))[1]
     torch.manual_seed(3)
     dev = pipe(model, **kw)
     assert len(used) == calls, (what, len(used))                 # the device step ran on every iteration
@@ -244,8 +244,8 @@ def test_rescale_and_9_channel_unets_stay_on_the_host_path(engine_lib, model):
     pos, neg, lat0 = _embeds(1, seed=4)
     pipe = StableDiffusionUnifiedPipeline(do_cfg=True, device="cuda", output_type="latents")
     used = []
-    real = pipe._affine_iteration
-    pipe._affine_iteration = lambda *a, **k: (used.append(1), real(*a, **k))[1]
+    real = pipe._device_iteration
+    pipe._device_iteration = lambda *a, **k: (used.append(1), real(*a, **k))[1]
     assert pipe._affine_step_available(model, lat0, 4, 0.0)          # (a fresh pipeline can be asked)
     assert not pipe._affine_step_available(model, lat0, 4, 0.7)
     out = pipe(model, prompt_embeds=pos, negative_prompt_embeds=neg, latents=lat0, num_inference_steps=3, guidance_scale=5.0,
