@@ -214,6 +214,30 @@ int sd_unet_cfg_share(const sd_unet_config* cfg);
  * Non-finite factors: SD_ERR_INVALID.  Graph replay (sd_unet_use_graph) with FreeU on is rejected by the forward
  * (SD_ERR_UNSUPPORTED). */
 int sd_unet_set_freeu(sd_unet* u, int enable, float s1, float s2, float b1, float b2);
+/* DeepCache (Ma, Fang, Wang, CVPR 2024): reuse the deep features of the UNet across denoising steps.  With
+ *   L = layers_per_block, s_0 = conv_in's output, s_j = the output of layer j - 1 of down block 0,
+ * layer j of the last up block (j = 0..L) reads cat([hidden, s_{L-j}]).  For a depth d in 1..L the cached feature F_d
+ * is the hidden input of layer L - d of the last up block.  Forwards then run in one of three modes:
+ *   SD_DC_PLAIN  the forward as without the feature;
+ *   SD_DC_STORE  the full forward, bit for bit the plain one with the same launches, which leaves F_d in a buffer the
+ *                handle keeps (counted in sd_unet_memory's workspace_bytes);
+ *   SD_DC_REUSE  time embedding and text / image K/V as always, conv_in, layers 0..d-1 of down block 0 (no
+ *                downsampler), layers L-d..L of the last up block -- the first reading cat([F_d, s_d]) with the stored
+ *                F_d and this step's s_d -- and conv_norm_out / conv_out.  No other block, no ControlNet.
+ * The stored feature holds for one (B, H, W, shared CFG prefix or not); sd_unet_set_deep_cache, _set_freeu,
+ * _set_ip_adapter and _set_controlnet invalidate it.  Holds for sd_unet_forward, _ex, _tc and _cfg.  Errors, nothing
+ * launched: a reuse forward without a stored step of the call's shape: SD_ERR_STATE; a store / reuse forward with graph
+ * replay on, with a ControlNet that would run (attached, control image given, scale != 0), or with FreeU on and fewer
+ * than three blocks (FreeU would touch the last block): SD_ERR_UNSUPPORTED. */
+#define SD_DC_PLAIN 0
+#define SD_DC_STORE 1
+#define SD_DC_REUSE 2
+/* depth 0 = off (the forward is again exactly the plain one, the buffer is released); 1..layers_per_block, anything
+ * else SD_ERR_INVALID.  Every call resets the mode to SD_DC_PLAIN and invalidates the cache. */
+int sd_unet_set_deep_cache(sd_unet* u, int depth);
+/* Mode of the following forwards, until changed.  An unknown mode: SD_ERR_INVALID; store / reuse while the depth is 0:
+ * SD_ERR_STATE. */
+int sd_unet_deep_cache_mode(sd_unet* u, int mode);
 /* Bytes of device memory held (packed weights, workspace). */
 int sd_unet_memory(const sd_unet* u, int64_t* weight_bytes, int64_t* workspace_bytes);
 

@@ -123,6 +123,8 @@ SIGNATURES = {
     "sd_unet_set_ip_adapter": (_I, [_P, _P]),
     "sd_unet_set_ip_adapter_scale": (_I, [_P, _F]),
     "sd_unet_set_freeu": (_I, [_P, _I, _F, _F, _F, _F]),
+    "sd_unet_set_deep_cache": (_I, [_P, _I]),
+    "sd_unet_deep_cache_mode": (_I, [_P, _I]),
     "sd_ip_adapter_create": (_I, [_P, _I, _I, C.POINTER(_P)]),
     "sd_ip_adapter_destroy": (_I, [_P]),
     "sd_ip_adapter_num_weights": (_I, [_P]),

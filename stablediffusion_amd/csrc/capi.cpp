@@ -196,6 +196,7 @@ int sd_unet_set_ip_adapter(sd_unet* u, sd_ip_adapter* a) {
         }
     }
     u->impl.set_ip_adapter(a ? &a->impl : nullptr);
+    u->impl.dc_valid = false;
     return SD_OK;
 }
 int sd_unet_set_controlnet(sd_unet* u, sd_controlnet* cn) {
@@ -206,6 +207,7 @@ int sd_unet_set_controlnet(sd_unet* u, sd_controlnet* cn) {
         if (!controlnet_fits(u->impl.cfg, cn->impl.cfg, &why)) { set_error("sd_unet_set_controlnet: " + why); return SD_ERR_INVALID; }
     }
     u->impl.set_controlnet(cn ? &cn->impl : nullptr);
+    u->impl.dc_valid = false;
     return SD_OK;
 }
 int sd_unet_forward_cn(sd_unet* u, const void* sample, const float* timesteps, const void* ehs, int ehs_len,
@@ -238,6 +240,7 @@ int sd_unet_set_ip_adapter_scale(sd_unet* u, float scale) {
 }
 int sd_unet_set_freeu(sd_unet* u, int enable, float s1, float s2, float b1, float b2) {
     if (!u) { set_error("null handle"); return SD_ERR_INVALID; }
+    u->impl.dc_valid = false;           // (a DeepCache feature stored under other FreeU settings is stale)
     if (!enable) { u->impl.freeu_on = false; return SD_OK; }
     if (!std::isfinite(s1) || !std::isfinite(s2) || !std::isfinite(b1) || !std::isfinite(b2)) {
         set_error("sd_unet_set_freeu: s1, s2, b1, b2 must be finite");
@@ -245,6 +248,23 @@ int sd_unet_set_freeu(sd_unet* u, int enable, float s1, float s2, float b1, floa
     }
     u->impl.freeu_on = true;
     u->impl.freeu_s1 = s1; u->impl.freeu_s2 = s2; u->impl.freeu_b1 = b1; u->impl.freeu_b2 = b2;
+    return SD_OK;
+}
+int sd_unet_set_deep_cache(sd_unet* u, int depth) {
+    if (!u) { set_error("null handle"); return SD_ERR_INVALID; }
+    return u->impl.set_deep_cache(depth);
+}
+int sd_unet_deep_cache_mode(sd_unet* u, int mode) {
+    if (!u) { set_error("null handle"); return SD_ERR_INVALID; }
+    if (mode != SD_DC_PLAIN && mode != SD_DC_STORE && mode != SD_DC_REUSE) {
+        set_error("sd_unet_deep_cache_mode: unknown mode " + std::to_string(mode));
+        return SD_ERR_INVALID;
+    }
+    if (mode != SD_DC_PLAIN && u->impl.dc_depth == 0) {
+        set_error("sd_unet_deep_cache_mode: store / reuse while the depth is 0 (sd_unet_set_deep_cache)");
+        return SD_ERR_STATE;
+    }
+    u->impl.dc_mode = mode;
     return SD_OK;
 }
 
@@ -326,7 +346,7 @@ int sd_controlnet_finalize(sd_controlnet* cn) {
 int sd_unet_memory(const sd_unet* u, int64_t* weight_bytes, int64_t* workspace_bytes) {
     if (!u) { set_error("null handle"); return SD_ERR_INVALID; }
     if (weight_bytes) *weight_bytes = u->impl.ws.packed_bytes();
-    if (workspace_bytes) *workspace_bytes = (int64_t)u->impl.arena.capacity();
+    if (workspace_bytes) *workspace_bytes = (int64_t)(u->impl.arena.capacity() + u->impl.dc_cap);
     return SD_OK;
 }
 

@@ -137,7 +137,8 @@ void UNet::set_controlnet(ControlNet* n) {
     cn = n;
     cond_valid = false;
     cnkv_valid = false;
-    planned_key = -1;
+    dc_valid = false;
+    reset_plans();
 }
 
 int UNet::run_controlnet(Ctx& c, const half_t* sample, const float* timesteps, const half_t* ehs, int L,

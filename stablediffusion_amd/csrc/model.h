@@ -148,7 +148,7 @@ struct Encoder {
     // share: x, xs and tproj hold the first B / 2 images; the first resnet and the start of the first transformer run on
     // those (CfgShare), everything after on all B.
     View run_down(Ctx& c, View x, GnStatBuf*& xs, int B, int& h, int& w, View text_kv, int L, const float* tproj,
-                  const SkipDst& dst, const SkipStat& stat, const CfgShare* share = nullptr);
+                  const SkipDst& dst, const SkipStat& stat, const CfgShare* share = nullptr, int stop_after = -1);
     void run_mid(Ctx& c, View x, GnStatBuf* xs, int B, int h, int w, View text_kv, int L, const float* tproj, View dst);
 };
 
@@ -212,8 +212,12 @@ struct UNet : Encoder {
 
     Arena arena;
     bool finalized = false;
-    long planned_key = -1;
-    long planned_cn = -1;
+    // the last planned key of each DeepCache mode: a loop alternates store / reuse steps, and one key would make a dry
+    // pass at every switch (the arena only grows, so a plan made for one mode stays good while another runs)
+    long planned_key[3] = {-1, -1, -1};
+    long planned_cn[3] = {-1, -1, -1};
+    int planned_depth[3] = {0, 0, 0};
+    void reset_plans() { for (int m = 0; m < 3; ++m) planned_key[m] = planned_cn[m] = -1; }
 
     // ---- optional hipGraph replay of the whole forward (sd_unet_use_graph) ----
     // One captured graph per input shape; inputs / output are staged through engine-owned buffers so
@@ -274,6 +278,19 @@ struct UNet : Encoder {
     bool freeu_on = false;
     float freeu_s1 = 1.f, freeu_s2 = 1.f, freeu_b1 = 1.f, freeu_b2 = 1.f;
 
+    // ---- DeepCache (sd_unet_set_deep_cache / sd_unet_deep_cache_mode): depth 0 = off, the forward as without the
+    // feature.  With depth d in 1..layers_per_block the concatenation buffer cats[nskip-1-d] of run() -- whose hidden half
+    // is the input of layer L-d of the last up block -- lives in dc_buf instead of the arena (grown like kv_cache).  A
+    // store forward is the full forward and leaves that hidden half behind; a reuse forward runs conv_in, d layers of
+    // down block 0 (rewriting the buffer's skip half), layers L-d..L of the last up block and the tail.  Valid for one
+    // (B, H, W, shared CFG prefix or not); not under graphs, not with a running ControlNet.
+    int dc_depth = 0, dc_mode = 0;
+    bool dc_valid = false, dc_cfg = false;
+    half_t* dc_buf = nullptr;
+    size_t dc_cap = 0;
+    int dc_B = 0, dc_H = 0, dc_W = 0;
+    int set_deep_cache(int depth);
+
     ConvW conv_out;
     NormW norm_out;
     std::vector<std::vector<Resnet>> up_res;
@@ -284,7 +301,7 @@ struct UNet : Encoder {
     int run(Ctx& c, const half_t* sample, const float* timesteps, const half_t* ehs, int L,
             const half_t* add_text, const float* add_time_ids, half_t* out, int B, int H, int W,
             const half_t* image_embeds = nullptr, int n_img = 0, const half_t* control = nullptr, int n_ctrl = 0,
-            float cn_scale = 0.f, const CfgIn* cfg_in = nullptr, const float* tcond = nullptr);
+            float cn_scale = 0.f, const CfgIn* cfg_in = nullptr, const float* tcond = nullptr, int dc = 0);
     // ControlNet step of run(): its hidden tensors into sites / mid (allocated by the caller)
     int run_controlnet(Ctx& c, const half_t* sample, const float* timesteps, const half_t* ehs, int L,
                        const half_t* add_text, const float* add_time_ids, int B, int H, int W, const half_t* control,

@@ -372,7 +372,8 @@ void UNet::set_ip_adapter(IPAdapter* a) {
     }
     ip = a;
     ipkv_valid = false;
-    planned_key = -1;
+    dc_valid = false;
+    reset_plans();
 }
 
 // ------------------------------------------------------------------------------------------ blocks
@@ -662,14 +663,16 @@ void Encoder::run_conv_in(Ctx& c, const half_t* sample, int B, int H, int W, Vie
 }
 
 View Encoder::run_down(Ctx& c, View x, GnStatBuf*& xs, int B, int& h, int& w, View text_kv, int L, const float* tproj,
-                       const SkipDst& skip_view, const SkipStat& skip_stat, const CfgShare* share) {
+                       const SkipDst& skip_view, const SkipStat& skip_stat, const CfgShare* share, int stop_after) {
     Arena& a = *c.arena;
     const int nb = cfg.num_blocks;
     const int G = cfg.norm_num_groups;
     const float eps = cfg.norm_eps;
     int skip_i = 1;
     for (int i = 0; i < nb; ++i) {
-        for (int j = 0; j < cfg.layers_per_block; ++j) {
+        // (stop_after >= 0, a DeepCache reuse step: that many layers of block 0 and nothing below them)
+        const int nl = stop_after >= 0 ? std::min(stop_after, cfg.layers_per_block) : cfg.layers_per_block;
+        for (int j = 0; j < nl; ++j) {
             const Resnet& r = down_res[i][j];
             if (cfg.down_block_has_attn[i]) {
                 const size_t mk = a.mark();
@@ -689,6 +692,7 @@ View Encoder::run_down(Ctx& c, View x, GnStatBuf*& xs, int B, int& h, int& w, Vi
             }
             ++skip_i;
         }
+        if (stop_after >= 0) return x;
         if (i != nb - 1) {
             ConvFuse f;
             f.gn_out = skip_stat(skip_i, (long)(h / 2) * (w / 2), down_ds[i].cout);
@@ -725,7 +729,7 @@ int Encoder::num_skips() const { return 1 + cfg.num_blocks * cfg.layers_per_bloc
 int UNet::run(Ctx& c, const half_t* sample, const float* timesteps, const half_t* ehs, int L,
               const half_t* add_text, const float* add_time_ids, half_t* out, int B, int H, int W,
               const half_t* image_embeds, int n_img, const half_t* control, int n_ctrl, float cn_scale, const CfgIn* cfg_in,
-              const float* tcond) {
+              const float* tcond, int dc) {
     Arena& a = *c.arena;
     const int nb = cfg.num_blocks;
     const int* boc = cfg.block_out_channels;
@@ -733,6 +737,7 @@ int UNet::run(Ctx& c, const half_t* sample, const float* timesteps, const half_t
     const float eps = cfg.norm_eps;
     hipStream_t s = c.stream;
     const bool go = !c.dry;
+    const bool reuse = dc == SD_DC_REUSE;
 
     // ---- shared CFG prefix (forward_cfg): B = 2 Bp images from Bp latents and Bp timesteps.  conv_in, the first
     //      resnet and the first transformer up to its attn2 query run on Bp images; run_xformer widens what the rest
@@ -804,8 +809,11 @@ int UNet::run(Ctx& c, const half_t* sample, const float* timesteps, const half_t
     // Skip tensors are produced in down-path order and consumed by the up path in reverse; each
     // up resnet k reads cat_k = [hidden (C1) | skip (C2)].  Allocate every cat_k up front so the
     // down-path producers write their outputs directly into the skip half.
+    // DeepCache (store / reuse): cats[dc_k] is the handle's persistent buffer, whose hidden half a store forward leaves
+    // behind for the reuse forwards after it.  A reuse forward reads no concatenation before that one.
     struct Cat { half_t* p; int c1, c2, h, w; };
     std::vector<Cat> cats;
+    const int dc_k = dc != SD_DC_PLAIN ? num_skips() - 1 - dc_depth : -1;
     {
         int out_ch = boc[nb - 1];
         int h = H >> (nb - 1), w = W >> (nb - 1);
@@ -818,7 +826,8 @@ int UNet::run(Ctx& c, const half_t* sample, const float* timesteps, const half_t
                 ct.c2 = (j == cfg.layers_per_block) ? in_ch : out_ch;
                 ct.c1 = (j == 0) ? prev : out_ch;
                 ct.h = h; ct.w = w;
-                ct.p = a.alloc_h((long)B * h * w * (ct.c1 + ct.c2));
+                const int kc = (int)cats.size();
+                ct.p = kc == dc_k ? dc_buf : (reuse && kc < dc_k) ? nullptr : a.alloc_h((long)B * h * w * (ct.c1 + ct.c2));
                 cats.push_back(ct);
             }
             if (i != nb - 1) { h *= 2; w *= 2; }
@@ -893,11 +902,13 @@ int UNet::run(Ctx& c, const half_t* sample, const float* timesteps, const half_t
     }
 
     // ---- down path ----
+    // (a reuse step stops after dc_depth layers of block 0, the last of which wrote the skip half of cats[dc_k])
     x = run_down(c, x, xs, B, h, w, text_kv, L, tproj, [&](int si) { return skip_view(si); },
-                 [&](int si, long HWs, int C) { return skip_stat(si, HWs, C); }, cfg_in ? &share : nullptr);
+                 [&](int si, long HWs, int C) { return skip_stat(si, HWs, C); }, cfg_in ? &share : nullptr,
+                 reuse ? dc_depth : -1);
 
     // ---- mid block ----
-    run_mid(c, x, xs, B, h, w, text_kv, L, tproj, View(cats[0].p, cats[0].c1 + cats[0].c2, cats[0].c1));
+    if (!reuse) run_mid(c, x, xs, B, h, w, text_kv, L, tproj, View(cats[0].p, cats[0].c1 + cats[0].c2, cats[0].c1));
 
     // ---- ControlNet residuals: skip_i += s (h_i W_i^T + b_i) in the skip half of every concatenation and
     //      mid += s (h_mid W_mid^T + b_mid) in the hidden half of the first, one GEMM per site with the scale and the
@@ -931,6 +942,7 @@ int UNet::run(Ctx& c, const half_t* sample, const float* timesteps, const half_t
     const bool no_cat_stats = no_cat_env || use_cn;
     for (int i = 0; i < nb; ++i) {
         for (int j = 0; j < cfg.layers_per_block + 1; ++j, ++k) {
+            if (reuse && k < dc_k) continue;     // (h, w stayed H, W: the layers that remain are the last block's)
             const Cat& ct = cats[(size_t)k];
             const Resnet& r = up_res[i][j];
             View xin(ct.p, ct.c1 + ct.c2, ct.c1 + ct.c2);
@@ -1065,6 +1077,7 @@ UNet::~UNet() {
     if (gstream) (void)hipStreamDestroy(gstream);
     if (io_slab) (void)hipFree(io_slab);
     if (kv_cache) (void)hipFree(kv_cache);
+    if (dc_buf) (void)hipFree(dc_buf);
     if (ipkv_cache) (void)hipFree(ipkv_cache);
     if (cond_cache) (void)hipFree(cond_cache);
     if (cnkv_cache) (void)hipFree(cnkv_cache);
@@ -1186,6 +1199,32 @@ int UNet::forward(const half_t* sample, const float* timesteps, const half_t* eh
     }
     const bool use_cn = cn && cn_scale != 0.f;
     if (freeu_on && graph_enabled) { set_error("unet: graph replay with FreeU enabled is not supported"); return 4; }
+    const int dc = dc_mode;
+    if (dc != SD_DC_PLAIN) {
+        if (dc_depth <= 0) { set_error("unet: DeepCache store / reuse mode while the depth is 0"); return 2; }
+        if (graph_enabled) { set_error("unet: graph replay with a DeepCache store / reuse mode is not supported"); return 4; }
+        if (use_cn) { set_error("unet: a DeepCache store / reuse mode with a running ControlNet is not supported"); return 4; }
+        if (freeu_on && cfg.num_blocks < 3) {
+            set_error("unet: DeepCache with FreeU needs at least three blocks (FreeU would touch the cached block)");
+            return 4;
+        }
+        if (dc == SD_DC_REUSE && !(dc_valid && dc_buf && dc_B == B && dc_H == H && dc_W == W && dc_cfg == (cfg_in != nullptr))) {
+            set_error("unet: DeepCache reuse forward without a stored step of this shape");
+            return 2;
+        }
+        // persistent concatenation buffer [B H W, C1 + C0] of layer L-d of the last (full-resolution) up block
+        const int* boc = cfg.block_out_channels;
+        const int c1 = dc_depth == cfg.layers_per_block ? boc[cfg.num_blocks > 1 ? 1 : 0] : boc[0];
+        const size_t need = (size_t)B * H * W * (c1 + boc[0]) * sizeof(half_t);
+        if (need > dc_cap) {
+            SD_HIP_CHECK(hipDeviceSynchronize());
+            if (dc_buf) (void)hipFree(dc_buf);
+            dc_buf = nullptr; dc_cap = 0; dc_valid = false;
+            SD_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&dc_buf), need));
+            dc_cap = need;
+        }
+        if (dc == SD_DC_STORE) dc_valid = false;     // (until this forward has run)
+    }
     if (graph_enabled && !prof_enabled())
         return forward_graph(sample, timesteps, ehs, L, add_text, add_time_ids, out, B, H, W, stream, tcond);
     if (kv_cache_on) {          // persistent buffer for the text K/V (outside the per-forward arena)
@@ -1231,11 +1270,14 @@ int UNet::forward(const half_t* sample, const float* timesteps, const half_t* eh
                      (ip ? (long)(n_img * ip->n_tok) << 32 : 0) ^ (cfg_in ? (1L << 61) : 0);
     // (the ControlNet's arena use depends on whether it runs and on n_ctrl: set_controlnet resets the plan)
     const long cn_key = use_cn ? n_ctrl : 0;
-    if (key != planned_key || cn_key != planned_cn) {
+    // (the DeepCache mode and depth belong to the key: one slot per mode, the depth beside it; the plain forward does not
+    // depend on the depth)
+    const int key_depth = dc != SD_DC_PLAIN ? dc_depth : 0;
+    if (key != planned_key[dc] || cn_key != planned_cn[dc] || key_depth != planned_depth[dc]) {
         Ctx dry{&arena, stream, true};
         arena.begin(true);
         int rc = run(dry, sample, timesteps, ehs, L, add_text, add_time_ids, out, B, H, W, image_embeds, n_img, control,
-                     n_ctrl, cn_scale, cfg_in, tcond);
+                     n_ctrl, cn_scale, cfg_in, tcond, dc);
         if (rc) return rc;
         // growing the slab frees the old one: make sure nothing enqueued earlier still uses it
         if (arena.peak() > arena.capacity()) {
@@ -1243,15 +1285,33 @@ int UNet::forward(const half_t* sample, const float* timesteps, const half_t* eh
             rc = arena.reserve(arena.peak());
             if (rc) return rc;
         }
-        planned_key = key;
-        planned_cn = cn_key;
+        planned_key[dc] = key;
+        planned_cn[dc] = cn_key;
+        planned_depth[dc] = key_depth;
     }
     Ctx ctx{&arena, stream, false};
     arena.begin(false);
     int rc = run(ctx, sample, timesteps, ehs, L, add_text, add_time_ids, out, B, H, W, image_embeds, n_img, control, n_ctrl,
-                 cn_scale, cfg_in, tcond);
+                 cn_scale, cfg_in, tcond, dc);
     if (!rc && arena.overflow()) { set_error("unet: workspace overflow (planner bug)"); return 2; }
+    if (!rc && dc == SD_DC_STORE) { dc_valid = true; dc_B = B; dc_H = H; dc_W = W; dc_cfg = cfg_in != nullptr; }
     return rc;
+}
+
+int UNet::set_deep_cache(int depth) {
+    if (depth < 0 || depth > cfg.layers_per_block) {
+        set_error("unet: DeepCache depth must be in [0, layers_per_block]");
+        return 1;
+    }
+    dc_depth = depth;
+    dc_mode = SD_DC_PLAIN;
+    dc_valid = false;
+    if (depth == 0 && dc_buf) {
+        SD_HIP_CHECK(hipDeviceSynchronize());
+        (void)hipFree(dc_buf);
+        dc_buf = nullptr; dc_cap = 0;
+    }
+    return 0;
 }
 
 bool unet_cfg_share_eligible(const sd_unet_config& cfg) {

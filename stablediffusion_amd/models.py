@@ -127,6 +127,7 @@ class HipUNet2DConditionModel:
         self._ip_scale = 1.0
         self._cn = None                # attached HipControlNetModel (attach_controlnet)
         self._freeu = None             # (s1, s2, b1, b2) while FreeU is on (enable_freeu)
+        self._deepcache = None         # (cache_interval, cache_depth) while DeepCache is on (enable_deepcache)
 
     # -- weights -------------------------------------------------------------------------------
     def load_state_dict(self, state_dict: Dict[str, torch.Tensor], strict: bool = True):
@@ -141,7 +142,11 @@ class HipUNet2DConditionModel:
         """A fresh engine of the same configuration on the same device with other weights (LoRA re-fuse:
         the packed weights are immutable once finalized)."""
         new = type(self)(self.cfg, self.device).load_state_dict(state_dict)
-        return new.enable_freeu(*self._freeu) if self._freeu is not None else new     # FreeU survives the rebuild
+        if self._freeu is not None:          # FreeU survives the rebuild
+            new.enable_freeu(*self._freeu)
+        if self._deepcache is not None:      # and so does DeepCache
+            new.enable_deepcache(*self._deepcache)
+        return new
 
     def rebuild_factory(self):
         """`rebuild` without a reference to this engine: the LoRA re-fuse drops the old engine (and its device memory)
@@ -213,6 +218,44 @@ class HipUNet2DConditionModel:
         """diffusers' disable_freeu: the forward is again exactly the plain one."""
         _lib.check(self._lib.sd_unet_set_freeu(self._h, 0, 1.0, 1.0, 1.0, 1.0), "sd_unet_set_freeu")
         self._freeu = None
+        return self
+
+    # the forward modes of DeepCache (sd_engine.h: SD_DC_*)
+    DC_PLAIN, DC_STORE, DC_REUSE = 0, 1, 2
+
+    def enable_deepcache(self, cache_interval: int = 3, cache_depth: int = 1):
+        """DeepCache (Ma, Fang, Wang, CVPR 2024): the pipeline's loop runs the full UNet on every `cache_interval`-th
+        step and, on the steps between, only `cache_depth` layers of down block 0 and the `cache_depth + 1` last layers
+        of the last up block, on the deep feature the full step left in the engine.  Lossy and opt-in; interval 1 is
+        the plain loop.  The settings survive `rebuild`.  Not available under `use_graph` or with a ControlNet that
+        runs.  By hand: `deep_cache_mode`."""
+        for name, v in (("cache_interval", cache_interval), ("cache_depth", cache_depth)):
+            if isinstance(v, bool) or not isinstance(v, int):
+                raise ValueError(f"enable_deepcache: {name} must be an int, got {v!r}")
+        if cache_interval < 1:
+            raise ValueError(f"enable_deepcache: cache_interval must be >= 1, got {cache_interval}")
+        if not 1 <= cache_depth <= self.cfg.layers_per_block:
+            raise ValueError(f"enable_deepcache: cache_depth must be in 1..{self.cfg.layers_per_block} "
+                             f"(layers_per_block), got {cache_depth}")
+        _lib.check(self._lib.sd_unet_set_deep_cache(self._h, cache_depth), "sd_unet_set_deep_cache")
+        self._deepcache = (cache_interval, cache_depth)
+        return self
+
+    def disable_deepcache(self):
+        """The forward is again exactly the plain one and the engine releases the cached feature's buffer."""
+        _lib.check(self._lib.sd_unet_set_deep_cache(self._h, 0), "sd_unet_set_deep_cache")
+        self._deepcache = None
+        return self
+
+    @property
+    def deepcache(self):
+        """(cache_interval, cache_depth) while DeepCache is on, else None."""
+        return self._deepcache
+
+    def deep_cache_mode(self, mode: int):
+        """Mode of the following forwards, until changed: DC_PLAIN (0), DC_STORE (1: the full forward, which keeps the
+        deep feature) or DC_REUSE (2: the shallow forward on the kept feature)."""
+        _lib.check(self._lib.sd_unet_deep_cache_mode(self._h, int(mode)), "sd_unet_deep_cache_mode")
         return self
 
     def attach_controlnet(self, controlnet: Optional["HipControlNetModel"]):

@@ -54,6 +54,7 @@ class SDModelWrapper:
         self._ip_scale = 1.0
         self._cn = None                  # ControlNet (configuration, diffusers-named state dict): load_controlnet
         self._freeu = None               # (s1, s2, b1, b2) while FreeU is on: enable_freeu
+        self._deepcache = None           # (cache_interval, cache_depth) while DeepCache is on: enable_deepcache
         # host copies of the weights the LoRA adapters are folded into (load_lora_weights); the engine
         # itself keeps only its packed device copy
         self._lora = None
@@ -163,9 +164,10 @@ class SDModelWrapper:
         old = self.base
         graph = bool(getattr(old, "_graph_on", False))
         freeu = getattr(old, "_freeu", self._freeu)     # the engine's own record wins: enable_freeu may be called on .base
+        deepcache = getattr(old, "deepcache", self._deepcache)
         self.base = None                     # the old engine's device memory goes before the new one is packed
         del old
-        self.base = self._rebuild_from(fused, graph, freeu)
+        self.base = self._rebuild_from(fused, graph, freeu, deepcache)
         for part in ("text_encoder", "text_encoder_2"):
             if self._te_sd[part] is not None and (self._lora.touches(part) or self._lora_applied is not None):
                 enc = getattr(self, part, None)
@@ -178,7 +180,7 @@ class SDModelWrapper:
                     raise ValueError(f"{type(enc).__name__} cannot take fused text-encoder LoRA weights")
         self._lora_applied = sig
 
-    def _rebuild_from(self, fused, graph, freeu=None):
+    def _rebuild_from(self, fused, graph, freeu=None, deepcache=None):
         base = self._base_factory(fused)
         if graph and hasattr(base, "use_graph"):
             base.use_graph(True)
@@ -189,6 +191,9 @@ class SDModelWrapper:
         self._freeu = freeu
         if freeu is not None:                # and FreeU
             base.enable_freeu(*freeu)
+        self._deepcache = deepcache
+        if deepcache is not None:            # and DeepCache
+            base.enable_deepcache(*deepcache)
         return base
 
     # ---- FreeU (diffusers pipelines' enable_freeu / disable_freeu: forwarded to the UNet) ----
@@ -199,6 +204,15 @@ class SDModelWrapper:
     def disable_freeu(self):
         self.base.disable_freeu()
         self._freeu = None
+
+    # ---- DeepCache (forwarded to the base UNet; the refiner runs plain) ----
+    def enable_deepcache(self, cache_interval: int = 3, cache_depth: int = 1):
+        self.base.enable_deepcache(cache_interval, cache_depth)
+        self._deepcache = (cache_interval, cache_depth)
+
+    def disable_deepcache(self):
+        self.base.disable_deepcache()
+        self._deepcache = None
 
     # ---- ControlNet (diffusers ControlNetModel, one per model; the pipeline takes control_image=) ----
     def _attach_cn(self, base):
@@ -301,6 +315,9 @@ class SDModelWrapper:
             raise ValueError(f"Unknown scheduler name: {scheduler_name}")
         self.scheduler = make(self.scheduler.config)
         self.scheduler_name = scheduler_name
+
+
+_DC_PLAIN, _DC_STORE, _DC_REUSE = 0, 1, 2       # DeepCache forward modes (sd_engine.h: SD_DC_*)
 
 
 def _ptr(t: torch.Tensor):
@@ -701,6 +718,12 @@ class StableDiffusionUnifiedPipeline:
                          for i in range(n)]
         # prompt_embeds is the same tensor on every step: the engine keeps its cross-attention K/V
         # projections for the duration of this loop (switched off again right after it)
+        # DeepCache on this loop's UNet: iteration i runs the full forward and keeps the deep feature when
+        # i % interval == 0 (so the first step of every loop stores: a stale cache is never read), the shallow one on
+        # that feature otherwise.  The mode is engine state, set in front of every forward whichever path the step takes
+        deepcache = getattr(unet, "deepcache", None)
+        if deepcache is not None and control is not None:
+            raise ValueError("DeepCache runs no ControlNet on its reuse steps: disable_deepcache() or drop control_image")
         kv_cache = getattr(unet, "text_kv_cache", None)
         if kv_cache is not None:
             # the cache is keyed by the buffer's address: hand the engine ONE fp16 contiguous tensor for the whole loop
@@ -735,6 +758,8 @@ class StableDiffusionUnifiedPipeline:
             for i, t in enumerate(timesteps_host):
                 cn_kwargs = {} if control is None else dict(controlnet_cond=control,
                                                             controlnet_conditioning_scale=cn_scales[i])
+                if deepcache is not None:
+                    unet.deep_cache_mode(_DC_STORE if i % deepcache[0] == 0 else _DC_REUSE)
                 # the step's noise, drawn before the forward.  The affine schedulers that add noise draw it as their `step`
                 # does: from the global generator, once per step (the last included, whose noise coefficient is 0), so the
                 # device and the host loop consume the same stream
@@ -780,6 +805,8 @@ class StableDiffusionUnifiedPipeline:
                                                                         torch.as_tensor([timesteps_host[i + 1]]))
                     latents = ((1 - init_mask) * init_latents_proper.float() + init_mask * latents.float()).to(latents.dtype)
         finally:
+            if deepcache is not None:
+                unet.deep_cache_mode(_DC_PLAIN)
             if kv_cache is not None:
                 kv_cache(False)
         return latents
