@@ -565,6 +565,40 @@ int sd_bench_conv2d(const void* x_nhwc, const void* w_oihw, void* y_nhwc, int N,
 /* GroupNorm (+ optional SiLU) on NHWC f16, fp32 statistics. */
 int sd_op_groupnorm(const void* x_nhwc, const void* gamma, const void* beta, void* y_nhwc,
                     int N, int HW, int C, int groups, float eps, int silu, void* stream);
+/* Test hook, host only (no device needed): what a GroupNorm launch over x [N, HW, C] with `groups` groups would run
+ * (launch_groupnorm, launch_gn_stats and this entry decide through one function, norm_plan).  have_summaries = 1: the
+ * caller has S_pre (mean, M2) summaries per image, as a producing convolution leaves them.
+ *   out[10] = statistics kernel (0 none, 1 gn_stats_kernel, 2 gn_stats2_kernel), apply kernel (0 gn_fused_kernel<T, NV>,
+ *             1 gn_apply_kernel, 2 gn_apply2_kernel<NV>), T of the fused kernel (else 0), NV (0 for gn_apply_kernel),
+ *             gn_finalize_kernel runs (0 / 1), S = summaries per image the apply pass (or the finalize) merges, pixels
+ *             per summary (ceil(HW / S) for the launch's own statistics pass, 0 = the caller's with have_summaries),
+ *             CB = channels per block of the statistics and apply2 kernels, scratch floats the launch needs, caller's
+ *             summaries used (0 where the single-kernel form runs anyway)
+ * S and pixels per summary describe the statistics pass (sd_op_gn_stats) also where out[0] = 0 without summaries.
+ * Replaces nothing by itself: the operators are the GroupNorms of ResnetBlock2D, Transformer2DModel and the VAE decoder
+ * under sd_unified_pipeline.py:475-482 and :523. */
+int sd_norm_plan(int N, int64_t HW, int C, int groups, int have_summaries, int S_pre, int64_t* out);
+/* sd_norm_plan (without summaries) for `count` problems: problems[i * 4 + {0..3}] = N, HW, C, groups -> out[i * 10 ..]. */
+int sd_norm_plan_batch(int count, const int64_t* problems, int64_t* out);
+/* sd_op_groupnorm with the operands as the engine passes them, for the element-wise kernel tests (tests/test_norm_gpu.py;
+ * the GroupNorms under sd_unified_pipeline.py:475-482 and :523):
+ *   ldx, ldy     row strides in elements: C or a wider multiple of 8 (a column slice of a concatenation buffer)
+ *   summaries    NULL, or device floats [N][S][groups][2] = (mean, M2 = sum (x - mean)^2) of each tile of `rows`
+ *                consecutive pixels x the group's channels, the last tile holding the remainder: what a convolution's
+ *                epilogue leaves.  The launch then makes no statistics pass over x (unless the map is one the
+ *                single-kernel form takes, which ignores them).  SD_ERR_INVALID, nothing launched, unless
+ *                (S - 1) * rows < HW <= S * rows: an empty summary is never valid.
+ *   ran[10]      out: what ran, as sd_norm_plan's out (pixels per summary = `rows` with summaries)
+ * Synchronises. */
+int sd_op_groupnorm_ex(const void* x_nhwc, int64_t ldx, const void* gamma, const void* beta, void* y_nhwc, int64_t ldy, int N,
+                       int64_t HW, int C, int groups, float eps, int silu, const float* summaries, int S, int64_t rows,
+                       int64_t* ran, void* stream);
+/* The statistics pass alone (what runs ahead of the apply pass, of sd_op_groupnorm_concat's merge and of the GroupNorm
+ * fused into a convolution; sd_unified_pipeline.py:475-482): out_host (HOST floats, at least sd_norm_plan's scratch
+ * count) receives [N][*S][groups][2] = (mean, M2) per slab of *rows consecutive pixels; *kernel = 1 gn_stats_kernel,
+ * 2 gn_stats2_kernel.  Synchronises. */
+int sd_op_gn_stats(const void* x_nhwc, int64_t ldx, int N, int64_t HW, int C, int groups, float* out_host, int* S,
+                   int64_t* rows, int* kernel, void* stream);
 /* GroupNorm of a channel concatenation [A | B] (diffusers' up blocks: torch.cat([hidden_states, res_hidden_states], 1) ->
  * ResnetBlock2D.norm1, under sd_unified_pipeline.py:475-482) from per-half summaries, the way the UNet runs it on its big
  * maps: statistics of the first Ca channels over sub-groups of width gcd(C / groups, Ca), of the last Cb over their own
@@ -609,6 +643,14 @@ int sd_op_freeu(void* cat_nhwc, int N, int H, int W, int C1, int C2, float b, fl
 /* LayerNorm over the last dim of [rows, C] f16. */
 int sd_op_layernorm(const void* x, const void* gamma, const void* beta, void* y, int rows, int C,
                     float eps, void* stream);
+/* The same with row strides in elements (C or a wider multiple of 8): the LayerNorms of BasicTransformerBlock and CLIP
+ * under sd_unified_pipeline.py:475-482.  SD_ERR_INVALID for C % 8 != 0 or C > 2048. */
+int sd_op_layernorm_ex(const void* x, int64_t ldx, const void* gamma, const void* beta, void* y, int64_t ldy, int64_t rows,
+                       int C, float eps, void* stream);
+/* Per-row LayerNorm statistics of x [rows, C] f16 (row stride ldx): stat[row * 2 + {0,1}] = (mean, M2 = sum (x - mean)^2),
+ * device floats; the stand-alone producer for the LayerNorm folded into a linear layer (BasicTransformerBlock.norm1-3,
+ * sd_unified_pipeline.py:475-482) where the producing GEMM could not emit them.  C a multiple of 8. */
+int sd_op_row_stats(const void* x, int64_t ldx, float* stat, int64_t rows, int C, void* stream);
 /* softmax(q k^T / sqrt(d)) v.  q [B,Tq,heads*d] (row stride ldq), k/v [B,Tk,heads*d], out like q. */
 int sd_op_attention(const void* q, const void* k, const void* v, void* out, int B, int Tq, int Tk,
                     int heads, int d, int ldq, int ldk, int ldv, int ldo, void* stream);

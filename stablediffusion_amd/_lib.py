@@ -192,6 +192,10 @@ SIGNATURES = {
                                       C.POINTER(_I), _P]),
     "sd_bench_conv2d": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(_F), _P]),
     "sd_op_groupnorm": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _P]),
+    "sd_norm_plan": (_I, [_I, _I64, _I, _I, _I, _I, C.POINTER(_I64)]),
+    "sd_norm_plan_batch": (_I, [_I, C.POINTER(_I64), C.POINTER(_I64)]),
+    "sd_op_groupnorm_ex": (_I, [_P, _I64, _P, _P, _P, _I64, _I, _I64, _I, _I, _F, _I, _P, _I, _I64, C.POINTER(_I64), _P]),
+    "sd_op_gn_stats": (_I, [_P, _I64, _I, _I64, _I, _I, C.POINTER(_F), C.POINTER(_I), C.POINTER(_I64), C.POINTER(_I), _P]),
     "sd_op_groupnorm_concat": (_I, [_P, _I, _I, _P, _P, _P, _I, _I, _I, _F, _I, _P]),
     "sd_bench_groupnorm": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _I, C.POINTER(_F), _P]),
     "sd_op_timestep_sinusoid": (_I, [_P, _P, _I, _I, _I, _F, _P]),
@@ -200,6 +204,8 @@ SIGNATURES = {
     "sd_op_small_linear": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "sd_op_freeu": (_I, [_P, _I, _I, _I, _I, _I, _F, _F, _P]),
     "sd_op_layernorm": (_I, [_P, _P, _P, _P, _I, _I, _F, _P]),
+    "sd_op_layernorm_ex": (_I, [_P, _I64, _P, _P, _P, _I64, _I64, _I, _F, _P]),
+    "sd_op_row_stats": (_I, [_P, _I64, _P, _I64, _I, _P]),
     "sd_op_attention": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "sd_attention_plan": (_I, [_I, _I, _I, _I, _I, _I, _I, C.POINTER(_I)]),
     "sd_op_ip_cross_attention": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _I, _I,

@@ -1188,6 +1188,82 @@ int sd_op_groupnorm(const void* x, const void* gamma_f32, const void* beta_f32, 
     return rc;
 }
 
+static void norm_plan_out(const NormPlan& pl, int64_t* out) {
+    const int64_t o[10] = {pl.stats, pl.apply, pl.apply == 0 ? pl.T : 0, pl.NV, pl.finalize, pl.S, pl.rows, pl.CB, pl.scratch,
+                           pl.use_pre};
+    for (int i = 0; i < 10; ++i) out[i] = o[i];
+}
+
+int sd_norm_plan(int N, int64_t HW, int C, int G, int have_summaries, int S_pre, int64_t* out) {
+    if (!out) { set_error("sd_norm_plan: null argument"); return SD_ERR_INVALID; }
+    if (have_summaries && S_pre < 1) { set_error("sd_norm_plan: summaries need S_pre >= 1"); return SD_ERR_INVALID; }
+    const NormPlan pl = norm_plan(N, HW, C, G, have_summaries != 0, S_pre, 0);
+    if (!pl.valid) { set_error("sd_norm_plan: N, HW >= 1, C a multiple of 8 and of groups, groups <= 256"); return SD_ERR_INVALID; }
+    if (pl.apply == 1 && pl.apply_rows < 1) { set_error("sd_norm_plan: C too large for the apply kernel"); return SD_ERR_UNSUPPORTED; }
+    norm_plan_out(pl, out);
+    return SD_OK;
+}
+
+int sd_norm_plan_batch(int count, const int64_t* problems, int64_t* out) {
+    if (count < 0 || !problems || !out) { set_error("sd_norm_plan_batch: bad arguments"); return SD_ERR_INVALID; }
+    for (int i = 0; i < count; ++i) {
+        const int64_t* q = problems + (size_t)i * 4;
+        const int rc = sd_norm_plan((int)q[0], q[1], (int)q[2], (int)q[3], 0, 0, out + (size_t)i * 10);
+        if (rc) return rc;
+    }
+    return SD_OK;
+}
+
+int sd_op_groupnorm_ex(const void* x, int64_t ldx, const void* gamma_f32, const void* beta_f32, void* y, int64_t ldy, int N,
+                       int64_t HW, int C, int groups, float eps, int silu, const float* summaries, int S, int64_t rows,
+                       int64_t* ran, void* stream) {
+    if (!x || !gamma_f32 || !beta_f32 || !y || !ran || N < 1 || HW < 1 || C < 8 || groups < 1) {
+        set_error("sd_op_groupnorm_ex: bad arguments"); return SD_ERR_INVALID;
+    }
+    if (ldx < C || ldy < C || ldx % 8 != 0 || ldy % 8 != 0) {
+        set_error("sd_op_groupnorm_ex: ldx / ldy must be at least C and a multiple of 8"); return SD_ERR_INVALID;
+    }
+    if (summaries && (S < 1 || rows < 1 || (int64_t)S * rows < HW || (int64_t)(S - 1) * rows >= HW)) {
+        set_error("sd_op_groupnorm_ex: S summaries of `rows` pixels must cover HW with no empty one"); return SD_ERR_INVALID;
+    }
+    const NormPlan pl = norm_plan(N, HW, C, groups, summaries != nullptr, S, rows);
+    if (!pl.valid) { set_error("sd_op_groupnorm_ex: C must be a multiple of 8 and of groups, groups <= 256"); return SD_ERR_INVALID; }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    DevScope scope;
+    float* scratch = nullptr;
+    SD_DEV_ALLOC(scope, scratch, (size_t)pl.scratch * 4);
+    GnStats pre;
+    pre.part = summaries; pre.S = S; pre.rows = rows;
+    NormPlan did;
+    int rc = launch_groupnorm(static_cast<const half_t*>(x), ldx, static_cast<const float*>(gamma_f32),
+                              static_cast<const float*>(beta_f32), static_cast<half_t*>(y), ldy, N, HW, C, groups, eps, silu,
+                              scratch, s, summaries ? &pre : nullptr, &did);
+    hipError_t e = hipStreamSynchronize(s);
+    if (!rc && e != hipSuccess) { set_error(hipGetErrorString(e)); rc = SD_ERR_HIP; }
+    if (!rc) norm_plan_out(did, ran);
+    return rc;
+}
+
+int sd_op_gn_stats(const void* x, int64_t ldx, int N, int64_t HW, int C, int groups, float* out_host, int* S, int64_t* rows,
+                   int* kernel, void* stream) {
+    if (!x || !out_host || !S || !rows || !kernel || N < 1 || HW < 1 || C < 8 || groups < 1 || ldx < C || ldx % 8 != 0) {
+        set_error("sd_op_gn_stats: bad arguments"); return SD_ERR_INVALID;
+    }
+    const NormPlan pl = norm_plan(N, HW, C, groups, false, 0, 0);
+    if (!pl.valid) { set_error("sd_op_gn_stats: C must be a multiple of 8 and of groups, groups <= 256"); return SD_ERR_INVALID; }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    DevScope scope;
+    float* scratch = nullptr;
+    SD_DEV_ALLOC(scope, scratch, (size_t)pl.scratch * 4);
+    GnStats st;
+    int rc = launch_gn_stats(static_cast<const half_t*>(x), ldx, N, HW, C, groups, scratch, &st, s);
+    hipError_t e = hipStreamSynchronize(s);
+    if (!rc && e == hipSuccess) e = hipMemcpy(out_host, scratch, (size_t)N * st.S * groups * 2 * 4, hipMemcpyDeviceToHost);
+    if (!rc && e != hipSuccess) { set_error(hipGetErrorString(e)); rc = SD_ERR_HIP; }
+    if (!rc) { *S = st.S; *rows = st.rows; *kernel = pl.stats2 ? 2 : 1; }
+    return rc;
+}
+
 int sd_op_groupnorm_concat(const void* x, int Ca, int Cb, const void* gamma_f32, const void* beta_f32, void* y, int N, int HW,
                            int groups, float eps, int silu, void* stream) {
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -1294,6 +1370,23 @@ int sd_op_layernorm(const void* x, const void* gamma_f32, const void* beta_f32, 
     return launch_layernorm(static_cast<const half_t*>(x), C, static_cast<const float*>(gamma_f32),
                             static_cast<const float*>(beta_f32), static_cast<half_t*>(y), C, rows, C, eps,
                             static_cast<hipStream_t>(stream));
+}
+
+int sd_op_layernorm_ex(const void* x, int64_t ldx, const void* gamma_f32, const void* beta_f32, void* y, int64_t ldy,
+                       int64_t rows, int C, float eps, void* stream) {
+    if (!x || !gamma_f32 || !beta_f32 || !y || rows < 1 || C < 8 || ldx < C || ldy < C || ldx % 8 != 0 || ldy % 8 != 0) {
+        set_error("sd_op_layernorm_ex: bad arguments (ldx / ldy at least C and a multiple of 8)"); return SD_ERR_INVALID;
+    }
+    return launch_layernorm(static_cast<const half_t*>(x), ldx, static_cast<const float*>(gamma_f32),
+                            static_cast<const float*>(beta_f32), static_cast<half_t*>(y), ldy, rows, C, eps,
+                            static_cast<hipStream_t>(stream));
+}
+
+int sd_op_row_stats(const void* x, int64_t ldx, float* stat, int64_t rows, int C, void* stream) {
+    if (!x || !stat || rows < 1 || C < 8 || ldx < C || ldx % 8 != 0) {
+        set_error("sd_op_row_stats: bad arguments (ldx at least C and a multiple of 8)"); return SD_ERR_INVALID;
+    }
+    return launch_row_stats(static_cast<const half_t*>(x), ldx, stat, rows, C, static_cast<hipStream_t>(stream));
 }
 
 int sd_op_freeu(void* cat_nhwc, int N, int H, int W, int C1, int C2, float b, float s, void* stream) {

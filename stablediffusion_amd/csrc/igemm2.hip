@@ -920,8 +920,10 @@ __global__ __launch_bounds__(512) void conv3x3_halo_kernel(IGemmParams p, float*
                     long rows = (long)IHW - (long)k * p.gni_rows;
                     if (rows > p.gni_rows) rows = p.gni_rows;
                     const float nB = (float)rows * cpgf, mB = src[(long)k * G * 2], qB = src[(long)k * G * 2 + 1];
-                    const float n = nA + nB, d = mB - mA, f = nB / n;
-                    mA += d * f; qA += qB + d * d * nA * f; nA = n;
+                    if (nB > 0.f) {                      // (an empty summary counts nothing, as in stat_merge)
+                        const float n = nA + nB, d = mB - mA, f = nB / n;
+                        mA += d * f; qA += qB + d * d * nA * f; nA = n;
+                    }
                 }
                 red[(pi * G + gi) * 3] = nA; red[(pi * G + gi) * 3 + 1] = mA; red[(pi * G + gi) * 3 + 2] = qA;
             }

@@ -165,9 +165,26 @@ struct GnStats {
 };
 // false for the small maps the single-kernel GroupNorm handles (it reads x once anyway)
 bool gn_wants_stats(long HW, int C, int G);
+// What a GroupNorm launch does (norm_plan: the one function launch_groupnorm, launch_gn_stats and sd_norm_plan decide by).
+struct NormPlan {
+    bool valid = false;     // C % 8 == 0, C % G == 0, G <= 256
+    int stats = 0;          // statistics kernel: 0 none, 1 gn_stats_kernel, 2 gn_stats2_kernel
+    bool stats2 = false;    // the statistics pass, when one runs (launch_gn_stats: always), is gn_stats2_kernel
+    int apply = 0;          // 0 gn_fused_kernel<T, NV>, 1 gn_apply_kernel, 2 gn_apply2_kernel<NV>
+    int T = 0, NV = 0;      // template arguments of the fused / apply2 kernel
+    int unit = 0;           // channels per block of the fused kernel
+    bool use_pre = false;   // caller's summaries are used (they are ignored where the fused kernel runs anyway)
+    bool finalize = false;  // gn_finalize_kernel merges them first (more than 64 per image)
+    int S = 0;              // summaries per image the statistics pass writes, or the caller's
+    long rows = 0;          // pixels per summary
+    int CB = 0;             // channels per block of the statistics and apply2 kernels
+    long apply_rows = 0;    // pixels per block of the apply kernel
+    long scratch = 0;       // gn_scratch_floats
+};
+NormPlan norm_plan(int N, long HW, int C, int G, bool have_summaries, int S_pre, long rows_pre);
 int launch_groupnorm(const half_t* x, long ldx, const float* gamma, const float* beta,
                      half_t* y, long ldy, int N, long HW, int C, int G, float eps, int silu,
-                     float* scratch, hipStream_t s, const GnStats* pre = nullptr);
+                     float* scratch, hipStream_t s, const GnStats* pre = nullptr, NormPlan* ran = nullptr);
 // Statistics pass alone: (mean, M2) summaries of x into `scratch` (gn_scratch_floats), described by *st.
 int launch_gn_stats(const half_t* x, long ldx, int N, long HW, int C, int G, float* scratch, GnStats* st, hipStream_t s);
 // Merges the st.S summaries per image into one (into `out`, N * G * 2 floats) and rewrites *st to describe that.
@@ -181,7 +198,7 @@ int launch_gn_cat_finalize(const GnStats& sa, int Ga, int Ca, const GnStats& sb,
                            hipStream_t s);
 int launch_layernorm(const half_t* x, long ldx, const float* gamma, const float* beta,
                      half_t* y, long ldy, long rows, int C, float eps, hipStream_t s);
-// stat[m * 2 + {0,1}] = sum, sum of squares of row m (the one-part form of IGemmParams::rowstat_out)
+// stat[m * 2 + {0,1}] = (mean, M2 = sum (x - mean)^2) of row m (the one-part form of IGemmParams::rowstat_out)
 int launch_row_stats(const half_t* x, long ldx, float* stat, long rows, int C, hipStream_t s);
 // Pack-time LayerNorm fold of a [rows][K] fp16 weight matrix, in place (rows < rows_scaled are also
 // multiplied by row_scale: the attention query pre-scale):  w[n][k] <- fp16(w[n][k] * gamma[k] * s_n),

@@ -117,7 +117,8 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const half_t* __restrict_
         float nA = per, mA = chan[(tid * cpg) * 2], qA = chan[(tid * cpg) * 2 + 1];
         for (int c = 1; c < cpg; ++c) stat_merge(nA, mA, qA, per, chan[(tid * cpg + c) * 2], chan[(tid * cpg + c) * 2 + 1]);
         float* dst = part + (((long)n * S + s) * G + c0 / cpg + tid) * 2;
-        dst[0] = mA; dst[1] = qA;
+        const bool some = p1 > p0;                   // (gn_slabs leaves no empty slab; one would read nothing and store zeros)
+        dst[0] = some ? mA : 0.f; dst[1] = some ? qA : 0.f;
     }
     (void)ctot;
 }
@@ -426,8 +427,9 @@ __global__ __launch_bounds__(256) void gn_stats2_kernel(const half_t* __restrict
     const int split = (gA + 1) * cpg - ch;                   // channels e < split belong to gA, the rest to gA + 1
     const half_t* img = x + ((long)n * HW) * ldx + c0;
     const bool twog = split < 8;
-    const float pivA = (float)img[p0 * ldx + gA * cpg];
-    const float pivB = twog ? (float)img[p0 * ldx + (gA + 1) * cpg] : 0.f;
+    const long pp = p0 < HW ? p0 : HW - 1;                   // pivot row (gn_slabs leaves no slab that starts at or past HW)
+    const float pivA = (float)img[pp * ldx + gA * cpg];
+    const float pivB = twog ? (float)img[pp * ldx + (gA + 1) * cpg] : 0.f;
     float sa = 0.f, qa = 0.f, sb = 0.f, qb = 0.f;
     if (prow < rows_par) {
         const half_t* base = img + ch;
@@ -467,11 +469,12 @@ __global__ __launch_bounds__(256) void gn_stats2_kernel(const half_t* __restrict
             }
         }
         const float cnt = (float)(p1 - p0) * (float)cpg;
-        const float d = sm / cnt;
-        const float piv = (float)img[p0 * ldx + tid * cpg];
+        const bool some = cnt > 0.f;
+        const float d = some ? sm / cnt : 0.f;
+        const float piv = (float)img[pp * ldx + tid * cpg];
         float* dst = part + (((long)n * S + s) * G + c0 / cpg + tid) * 2;
         dst[0] = piv + d;
-        dst[1] = sq - sm * d;
+        dst[1] = some ? sq - sm * d : 0.f;
     }
 }
 
@@ -704,6 +707,10 @@ int gn_slabs(int N, long HW, int C, int G) {
     const long smax = HW / 64 > 0 ? HW / 64 : 1;
     if (s > smax) s = smax;
     if (s > 256) s = 256;
+    // the kernels give every slab ceil(HW / s) rows: keep only the slabs that then hold at least one (from s (s - 1) >=
+    // HW on the last ones would start at or past HW; a count that already divides into non-empty slabs does not move)
+    const long rows = (HW + s - 1) / s;
+    s = (HW + rows - 1) / rows;
     return (int)s;
 }
 
@@ -718,77 +725,108 @@ long gn_scratch_floats(int N, long HW, int C, int G) {
 // work (a split-K reduction kernel that also reduces per group: +5 us) is a net loss (rocprofv3, round 3).
 bool gn_wants_stats(long HW, int C, int G) { return gn_fused_unit(HW, C, G) == 0 || HW >= 1024; }
 
-static int launch_stats_pass(const half_t* x, long ldx, int N, long HW, int C, int G, int S, float* scratch, hipStream_t s) {
-    const int CB = gn_block_channels(C, G);
+// Every choice launch_groupnorm and launch_gn_stats make, in one place (sd_norm_plan reports it).
+NormPlan norm_plan(int N, long HW, int C, int G, bool have_summaries, int S_pre, long rows_pre) {
+    NormPlan pl;
+    if (N < 1 || HW < 1 || C < 8 || G < 1 || C % 8 != 0 || C % G != 0 || G > 256) return pl;
+    static const bool old = getenv("SD_GN_OLD") != nullptr;             // A/B switch: round-2 kernels and choices
     const int cpg = C / G;
-    static const bool old = getenv("SD_GN_OLD") != nullptr;         // A/B switch: round-2 kernels
-    if (!old && (cpg >= 8 || cpg == 4))
-        hipLaunchKernelGGL(gn_stats2_kernel, dim3(cdiv(C, CB), S, N), dim3(256), 0, s, x, ldx, scratch, HW, C, G, S, CB);
+    pl.valid = true;
+    pl.CB = gn_block_channels(C, G);
+    pl.S = gn_slabs(N, HW, C, G);
+    pl.rows = (HW + pl.S - 1) / pl.S;
+    pl.scratch = gn_scratch_floats(N, HW, C, G);
+    pl.stats2 = !old && (cpg >= 8 || cpg == 4);
+    pl.stats = pl.stats2 ? 2 : 1;
+    // summaries already there (left by the producing convolution's epilogue): apply pass only, at every map size the
+    // producer is asked for them; otherwise the small maps take the single-kernel form (x read once), the big ones
+    // statistics + apply
+    pl.use_pre = have_summaries && (old ? gn_fused_unit(HW, C, G) == 0 : gn_wants_stats(HW, C, G));
+    if (!pl.use_pre) {
+        if (const int U = gn_fused_unit(HW, C, G)) {
+            pl.stats = 0; pl.apply = 0; pl.unit = U;
+            pl.T = HW <= 256 ? 256 : 1024;
+            pl.NV = HW <= 64 ? 4 : 16;
+            return pl;
+        }
+    } else {
+        // one (mean, M2) summary per tile of rows_pre pixels: no statistics pass over x.  Many tiles per image are
+        // merged once, by a small kernel, instead of by every apply block.
+        pl.stats = 0; pl.S = S_pre; pl.rows = rows_pre;
+        pl.finalize = S_pre > 64;
+    }
+    if (!old && pl.CB / cpg <= 128) {
+        // channel-blocked apply: rows per block = (256 / chunks per row) x NV, NV the largest of 8 / 4 / 2 / 1 that still
+        // leaves about 512 blocks (every block pays the summary prologue: fewer, longer blocks won the sweep) (or one pixel row group per block on the small maps)
+        const int cblocks = cdiv(C, pl.CB);
+        const int rows_par = 256 / (pl.CB / 8) > 0 ? 256 / (pl.CB / 8) : 1;
+        int nv = 8;
+        while (nv > 1 && cdiv(HW, (long)rows_par * nv) * cblocks * N < 512) nv >>= 1;
+        pl.apply = 2; pl.NV = nv; pl.apply_rows = (long)rows_par * nv;
+        return pl;
+    }
+    // apply: rows per block so that a thread holds <= GN_APPLY_NV chunks, and >= ~512 blocks overall
+    const int CC = C / 8;
+    long rows_per = (long)256 * GN_APPLY_NV / CC;
+    const long want = cdiv(HW * N, 512);
+    if (rows_per > want) rows_per = want > 0 ? want : 1;
+    pl.apply = 1; pl.apply_rows = rows_per;                             // (< 1: C too large for the kernel)
+    return pl;
+}
+
+static int launch_stats_pass(const half_t* x, long ldx, int N, long HW, int C, int G, const NormPlan& pl, float* scratch, hipStream_t s) {
+    if (pl.stats2)
+        hipLaunchKernelGGL(gn_stats2_kernel, dim3(cdiv(C, pl.CB), pl.S, N), dim3(256), 0, s, x, ldx, scratch, HW, C, G, pl.S, pl.CB);
     else
-        hipLaunchKernelGGL(gn_stats_kernel, dim3(cdiv(C, CB), S, N), dim3(256), 0, s, x, ldx, scratch, HW, C, G, S, CB);
+        hipLaunchKernelGGL(gn_stats_kernel, dim3(cdiv(C, pl.CB), pl.S, N), dim3(256), 0, s, x, ldx, scratch, HW, C, G, pl.S, pl.CB);
     SD_HIP_CHECK(hipGetLastError());
     return 0;
 }
 
 int launch_groupnorm(const half_t* x, long ldx, const float* gamma, const float* beta, half_t* y,
                      long ldy, int N, long HW, int C, int G, float eps, int silu, float* scratch,
-                     hipStream_t s, const GnStats* pre) {
-    if (C % 8 != 0 || C % G != 0 || G > 256) { set_error("groupnorm: C must be a multiple of 8 and of groups"); return 1; }
-    static const bool old = getenv("SD_GN_OLD") != nullptr;             // A/B switch: round-2 kernels and choices
-    const bool have_pre = pre && pre->part && (old ? gn_fused_unit(HW, C, G) == 0 : gn_wants_stats(HW, C, G));
-    // summaries already there (left by the producing convolution's epilogue): apply pass only, at every map size;
-    // otherwise the small maps take the single-kernel form (x read once), the big ones statistics + apply
-    if (!have_pre) {
-        if (const int U = gn_fused_unit(HW, C, G)) {
-            const dim3 grid(C / U, N);
-            const int cpg = C / G;
-            if (HW <= 64)
-                hipLaunchKernelGGL((gn_fused_kernel<256, 4>), grid, dim3(256), 0, s, x, ldx, gamma, beta, y, ldy, (int)HW, C, cpg, U, eps, silu);
-            else if (HW <= 256)
-                hipLaunchKernelGGL((gn_fused_kernel<256, 16>), grid, dim3(256), 0, s, x, ldx, gamma, beta, y, ldy, (int)HW, C, cpg, U, eps, silu);
-            else
-                hipLaunchKernelGGL((gn_fused_kernel<1024, 16>), grid, dim3(1024), 0, s, x, ldx, gamma, beta, y, ldy, (int)HW, C, cpg, U, eps, silu);
-            SD_HIP_CHECK(hipGetLastError());
-            return 0;
-        }
+                     hipStream_t s, const GnStats* pre, NormPlan* ran) {
+    const bool given = pre && pre->part;
+    const NormPlan pl = norm_plan(N, HW, C, G, given, given ? pre->S : 0, given ? pre->rows : 0);
+    if (!pl.valid) { set_error("groupnorm: C must be a multiple of 8 and of groups"); return 1; }
+    if (pl.apply == 1 && pl.apply_rows < 1) { set_error("groupnorm: C too large for the apply kernel"); return 1; }
+    if (ran) *ran = pl;
+    if (pl.apply == 0) {
+        const dim3 grid(C / pl.unit, N);
+        const int cpg = C / G, U = pl.unit;
+        if (pl.T == 256 && pl.NV == 4)
+            hipLaunchKernelGGL((gn_fused_kernel<256, 4>), grid, dim3(256), 0, s, x, ldx, gamma, beta, y, ldy, (int)HW, C, cpg, U, eps, silu);
+        else if (pl.T == 256)
+            hipLaunchKernelGGL((gn_fused_kernel<256, 16>), grid, dim3(256), 0, s, x, ldx, gamma, beta, y, ldy, (int)HW, C, cpg, U, eps, silu);
+        else
+            hipLaunchKernelGGL((gn_fused_kernel<1024, 16>), grid, dim3(1024), 0, s, x, ldx, gamma, beta, y, ldy, (int)HW, C, cpg, U, eps, silu);
+        SD_HIP_CHECK(hipGetLastError());
+        return 0;
     }
-    int S = gn_slabs(N, HW, C, G);
-    long stat_rows = (HW + S - 1) / S;
+    int S = pl.S;
+    long stat_rows = pl.rows;
     const float* part = scratch;
-    if (have_pre) {
-        // one (mean, M2) summary per tile of pre->rows pixels: no statistics pass over x.  Many tiles per image are
-        // merged once, by a small kernel, instead of by every apply block.
-        part = pre->part; S = pre->S; stat_rows = pre->rows;
-        if (S > 64) {
+    if (pl.use_pre) {
+        part = pre->part;
+        if (pl.finalize) {
             hipLaunchKernelGGL(gn_finalize_kernel, dim3(G, N), dim3(256), 0, s, part, scratch, S, G, stat_rows, HW, C / G);
             SD_HIP_CHECK(hipGetLastError());
             part = scratch; S = 1; stat_rows = HW;
         }
     } else {
-        const int rc = launch_stats_pass(x, ldx, N, HW, C, G, S, scratch, s);
+        const int rc = launch_stats_pass(x, ldx, N, HW, C, G, pl, scratch, s);
         if (rc) return rc;
     }
-    const int CB = gn_block_channels(C, G);
-    if (!old && CB / (C / G) <= 128) {
-        // channel-blocked apply: rows per block = (256 / chunks per row) x NV, NV the largest of 8 / 4 / 2 / 1 that still
-        // leaves about 512 blocks (every block pays the summary prologue: fewer, longer blocks won the sweep) (or one pixel row group per block on the small maps)
-        const int cblocks = cdiv(C, CB);
-        const int rows_par = 256 / (CB / 8) > 0 ? 256 / (CB / 8) : 1;
-        int nv = 8;
-        while (nv > 1 && cdiv(HW, (long)rows_par * nv) * cblocks * N < 512) nv >>= 1;
-        const dim3 grid((unsigned)cdiv(HW, (long)rows_par * nv), cblocks, N);
+    const int CB = pl.CB;
+    if (pl.apply == 2) {
+        const dim3 grid((unsigned)cdiv(HW, pl.apply_rows), cdiv(C, CB), N);
 #define SD_GN_APPLY2(NVV) hipLaunchKernelGGL((gn_apply2_kernel<NVV>), grid, dim3(256), 0, s, x, ldx, part, gamma, beta, y, ldy, HW, C, G, S, stat_rows, CB, eps, silu)
-        if (nv == 8) SD_GN_APPLY2(8); else if (nv == 4) SD_GN_APPLY2(4); else if (nv == 2) SD_GN_APPLY2(2); else SD_GN_APPLY2(1);
+        if (pl.NV == 8) SD_GN_APPLY2(8); else if (pl.NV == 4) SD_GN_APPLY2(4); else if (pl.NV == 2) SD_GN_APPLY2(2); else SD_GN_APPLY2(1);
 #undef SD_GN_APPLY2
         SD_HIP_CHECK(hipGetLastError());
         return 0;
     }
-    // apply: rows per block so that a thread holds <= GN_APPLY_NV chunks, and >= ~512 blocks overall
-    const int CC = C / 8;
-    long rows_per = (long)256 * GN_APPLY_NV / CC;
-    if (rows_per < 1) { set_error("groupnorm: C too large for the apply kernel"); return 1; }
-    const long want = cdiv(HW * N, 512);
-    if (rows_per > want) rows_per = want > 0 ? want : 1;
+    const long rows_per = pl.apply_rows;
     hipLaunchKernelGGL(gn_apply_kernel, dim3((unsigned)cdiv(HW, rows_per), N), dim3(256),
                        ((size_t)C * 2 + (size_t)G * 2 + 768) * sizeof(float), s,
                        x, ldx, part, gamma, beta, y, ldy, HW, C, G, S, stat_rows, (int)rows_per, eps, silu);
@@ -837,12 +875,12 @@ __global__ __launch_bounds__(1024) void gn_cat_finalize_kernel(GnCatSrc A, GnCat
             const long rws = isa ? A.rows : B.rows;
             long rows = HW - (long)k * rws;
             if (rows > rws) rows = rws;
-            cnt[q] = ii < nt ? (float)rows * (float)(isa ? ua : ub) : 0.f;
+            cnt[q] = ii < nt && rows > 0 ? (float)rows * (float)(isa ? ua : ub) : 0.f;     // an empty summary counts nothing
         }
         if (i0 == pi) pivot = __shfl(v[0].x, (tid & 32), 64);
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            const float d = v[q].x - pivot;
+            const float d = cnt[q] > 0.f ? v[q].x - pivot : 0.f;
             sa += cnt[q] * d; sb += cnt[q] * d * d; sq += cnt[q] > 0.f ? v[q].y : 0.f; sn += cnt[q];
         }
     }
@@ -879,11 +917,11 @@ int launch_gn_cat_finalize(const GnStats& sa, int Ga, int Ca, const GnStats& sb,
 }
 
 int launch_gn_stats(const half_t* x, long ldx, int N, long HW, int C, int G, float* scratch, GnStats* st, hipStream_t s) {
-    if (C % 8 != 0 || C % G != 0 || G > 256) { set_error("groupnorm: C must be a multiple of 8 and of groups"); return 1; }
-    const int S = gn_slabs(N, HW, C, G);
-    const int rc = launch_stats_pass(x, ldx, N, HW, C, G, S, scratch, s);
+    const NormPlan pl = norm_plan(N, HW, C, G, false, 0, 0);      // (S, rows, CB and the kernel are the statistics pass's)
+    if (!pl.valid) { set_error("groupnorm: C must be a multiple of 8 and of groups"); return 1; }
+    const int rc = launch_stats_pass(x, ldx, N, HW, C, G, pl, scratch, s);
     if (rc) return rc;
-    st->part = scratch; st->S = S; st->rows = (HW + S - 1) / S;
+    st->part = scratch; st->S = pl.S; st->rows = pl.rows;
     return 0;
 }
 

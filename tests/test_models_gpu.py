@@ -122,6 +122,19 @@ def test_vae_decode(engine_lib, tiny_vae, B, h, w):
     assert rel_l2(got, ref) < TOL
 
 
+def test_vae_decode_65x65_latent(engine_lib, tiny_vae):
+    """A 520 x 520 image: 65 x 65, 130 x 130, 260 x 260 and 520 x 520 maps, none of which a convolution tile divides, so
+    every GroupNorm runs its own statistics pass -- on map sizes whose last slabs were empty before gn_slabs dropped
+    them (tests/test_norm_gpu.py has the operator-level cases)."""
+    cfg, sd, vae = tiny_vae
+    z = torch.randn(1, 4, 65, 65, generator=torch.Generator().manual_seed(65)).half()
+    ref = vae_ref.vae_decode(cfg, sd, z.float())
+    got = vae.decode(z.cuda(), return_dict=False)[0]
+    assert got.shape == ref.shape
+    assert torch.isfinite(got.float()).all()
+    assert rel_l2(got, ref) < TOL
+
+
 def test_vae_encode(engine_lib, tiny_vae):
     cfg, sd, vae = tiny_vae
     img = torch.randn(2, 3, 64, 48, generator=torch.Generator().manual_seed(3)).half()
