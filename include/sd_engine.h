@@ -525,14 +525,17 @@ int sd_op_ffn_geglu(const void* x, const void* ln_gamma, const void* ln_beta, fl
  * Consumer: y2 = LayerNorm(y1; gamma, beta, eps) W1^T + b1 from those statistics.  geglu = 0: w1 [O, C], the first
  * rows_scaled output columns times row_scale (the query scale of q|k|v); geglu = 1: w1 [2 O, C] = [hidden | gate] rows,
  * b1 [2 O], y2 = hidden * gelu(gate) [M, O].  *consumer: the igemm2 variant (13 / 14 = wsgemm, 18 = igemm3) or 100 for
- * the persistent GEGLU kernel. */
+ * the persistent GEGLU kernel.  The consumer takes any layout with parts * part_w >= C > (parts - 1) * part_w (the last
+ * part may be narrower) of at most 20 parts per row, what a consumer kernel holds per row; more is SD_ERR_INVALID with
+ * nothing launched and y2 untouched. */
 int sd_op_linear_rowstats(const void* x, const void* w0, const void* b0, const void* res, void* y1, float* stat, int M,
                           int K, int C, int* parts, int* part_w, int* producer, void* stream);
 int sd_op_ln_linear(const void* y1, const float* stat, int parts, int part_w, const void* gamma, const void* beta, float eps,
                     const void* w1, const void* b1, void* y2, int M, int C, int O, int geglu, int rows_scaled, float row_scale,
                     int* consumer, void* stream);
 /* sd_op_ffn_geglu on row statistics of x a producer left (the stat / parts / part_w of sd_op_linear_rowstats) instead of
- * statistics it computes itself: the form the UNet runs. */
+ * statistics it computes itself: the form the UNet runs.  The same layouts as sd_op_ln_linear: at most 20 parts per row,
+ * more is SD_ERR_INVALID with nothing launched and y untouched. */
 int sd_op_ln_ffn_geglu(const void* x, const float* stat, int parts, int part_w, const void* ln_gamma, const void* ln_beta,
                        float ln_eps, const void* w1, const void* b1, const void* w2, const void* b2, void* y, int M, int C,
                        int* fused, void* stream);

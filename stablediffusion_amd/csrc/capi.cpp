@@ -990,6 +990,11 @@ int sd_op_ln_ffn_geglu(const void* x, const float* stat, int parts, int part_w, 
     if (!stat || parts < 1 || part_w < 1 || (long)parts * part_w < C || (long)(parts - 1) * part_w >= C) {
         set_error("sd_op_ln_ffn_geglu: bad statistics layout"); return SD_ERR_INVALID;
     }
+    if (parts > igemm2_max_ln_parts()) {         // (ffn_fused_kernel holds as many; the two-GEMM form would fail at its launch)
+        set_error("sd_op_ln_ffn_geglu: ln_parts " + std::to_string(parts) + " above the limit of " +
+                  std::to_string(igemm2_max_ln_parts()) + " statistics parts per row");
+        return SD_ERR_INVALID;
+    }
     return ffn_geglu_impl(x, stat, parts, part_w, ln_gamma, ln_beta, ln_eps, w1, b1, w2, b2, y, M, C, 0, nullptr, fused, stream);
 }
 
@@ -1039,6 +1044,11 @@ int sd_op_ln_linear(const void* y1, const float* stat, int parts, int part_w, co
     if (!y1 || !stat || !gamma || !beta || !w1 || !y2 || !consumer || M < 1 || C % 64 != 0 || C < 64 || O % 64 != 0 ||
         O < 64 || parts < 1 || part_w < 1 || (long)parts * part_w < C || (long)(parts - 1) * part_w >= C) {
         set_error("sd_op_ln_linear: bad arguments"); return SD_ERR_INVALID;
+    }
+    if (parts > igemm2_max_ln_parts()) {         // refused ahead of the packing launches; launch_igemm2 holds the same check
+        set_error("sd_op_ln_linear: ln_parts " + std::to_string(parts) + " above the limit of " +
+                  std::to_string(igemm2_max_ln_parts()) + " statistics parts per row");
+        return SD_ERR_INVALID;
     }
     const long cols = geglu ? 2L * O : (long)O;
     const long rows = (cols + kWeightRowPad - 1) / kWeightRowPad * kWeightRowPad;

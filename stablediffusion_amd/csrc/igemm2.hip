@@ -1441,8 +1441,17 @@ IGemmPlan igemm2_plan(IGemmParams& p, const IGemmRequest& rq) {
 
 IGemmLaunchNote igemm2_last_launch() { return t_note; }
 
+int igemm2_max_ln_parts() { return kMaxLnParts; }
+
 int launch_igemm2(const IGemmParams& p, float* partial, hipStream_t s, const IGemmPlan* plan) {
     t_note = IGemmLaunchNote();
+    // the streamed tiles are where a folded LayerNorm lands when igemm3 / pgemm / wsgemm decline it, and they load
+    // kMaxLnParts partials per row whatever ln_parts says: a longer layout would be normalised from its first 20 parts
+    if (p.ln_stat && (p.ln_parts < 1 || p.ln_parts > kMaxLnParts)) {
+        set_error("igemm2: ln_parts " + std::to_string(p.ln_parts) + " outside 1.." + std::to_string(kMaxLnParts) +
+                  " (row-statistics parts a folded LayerNorm reads per row)");
+        return 1;
+    }
     IGemmParams q = p;
     IGemmPlan own;
     if (!plan || (plan->splits > 1 && !partial)) {

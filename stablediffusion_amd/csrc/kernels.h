@@ -110,6 +110,8 @@ IGemmPlan igemm2_plan(IGemmParams& p, const IGemmRequest& rq = IGemmRequest());
 // Runs p as planned; plans it itself (requests = p's own rowstat_out / gnstat_out) when no plan is passed.  A plan that
 // splits K needs `partial` of plan->partial_floats; without it the launch is planned again and runs unsplit.
 int launch_igemm2(const IGemmParams& p, float* partial, hipStream_t s, const IGemmPlan* plan = nullptr);
+// Most row-statistics parts per row (IGemmParams::ln_parts) a folded-LayerNorm launch takes; launch_igemm2 fails beyond.
+int igemm2_max_ln_parts();
 // What the calling thread's last launch_igemm2 launched on top of the plan: the split-K slices after the launcher's
 // collapse (cdiv(slabs, cdiv(slabs, plan.splits)), at most plan.splits) and the reduction kernel behind them.
 struct IGemmLaunchNote {

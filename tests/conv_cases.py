@@ -327,6 +327,14 @@ def _activation_error(act, v):
     return e
 
 
+def geglu_reference(h, gt, dh, dg):
+    """(h gelu(g), bound) of the GEGLU rounding point below, from the two halves ahead of any rounding to fp16 and what
+    each may be off by (shared with tests/ln_cases.py)."""
+    dg = 1.13 * dg + _activation_error(2, gt)
+    r = h * _gelu(gt)
+    return r, dh * _gelu(gt).abs() + h.abs() * dg + dh * dg + U16 * r.abs() + 2.0 ** -25
+
+
 def reference(c, x, w, bias, rowadd, res):
     """float64 on the CPU of the fp16 / fp32 operands: (r, bound), both [N, OH, OW, out_cols] float64.
 
@@ -362,9 +370,7 @@ def reference(c, x, w, bias, rowadd, res):
         assert not c.act and res is None
         h, gt = v.chunk(2, dim=-1)
         dh, dg = delta.chunk(2, dim=-1)
-        dg = 1.13 * dg + _activation_error(2, gt)
-        r = h * _gelu(gt)
-        return r, dh * _gelu(gt).abs() + h.abs() * dg + dh * dg + U16 * r.abs() + 2.0 ** -25
+        return geglu_reference(h, gt, dh, dg)
     p, d = v, delta
     if c.act:
         p = _gelu(v) if c.act == 2 else _quick_gelu(v)
