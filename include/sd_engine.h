@@ -90,9 +90,24 @@ typedef struct sd_clip_config {
     float layer_norm_eps;        /* 1e-5 */
 } sd_clip_config;
 
+/* CLIP vision tower hyper-parameters (transformers CLIPVisionConfig): the image encoder an IP-Adapter was trained
+ * against. */
+typedef struct sd_clip_vision_config {
+    int32_t hidden_size;         /* 1024 (ViT-L/14) / 1280 (ViT-H/14) / 1664 (ViT-bigG/14); % 8, <= 2048 */
+    int32_t intermediate_size;   /* 4096 / 5120 / 8192 */
+    int32_t num_layers;          /* 24 / 32 / 48 */
+    int32_t num_heads;           /* 16 / 16 / 16 */
+    int32_t image_size;          /* 224; divisible by patch_size */
+    int32_t patch_size;          /* 14 */
+    int32_t hidden_act;          /* 0 quick_gelu, 1 gelu (erf) */
+    int32_t projection_dim;      /* 768 / 1024 / 1280 */
+    float layer_norm_eps;        /* 1e-5 */
+} sd_clip_vision_config;
+
 typedef struct sd_unet sd_unet;
 typedef struct sd_vae sd_vae;
 typedef struct sd_clip sd_clip;
+typedef struct sd_clip_vision sd_clip_vision;
 typedef struct sd_ip_adapter sd_ip_adapter;
 typedef struct sd_controlnet sd_controlnet;
 
@@ -318,6 +333,35 @@ int sd_clip_forward(sd_clip* c, const int32_t* input_ids, const int32_t* eos_ind
 /* text_encoder.text_model.final_layer_norm(x) for the clip_skip branch (sd_unified_pipeline.py:608). */
 int sd_clip_final_layer_norm(sd_clip* c, const void* x, void* y, int64_t rows, void* stream);
 int sd_clip_memory(const sd_clip* c, int64_t* weight_bytes, int64_t* workspace_bytes);
+
+/* -- CLIP vision tower: fills SDModelWrapper.image_encoder for ip_adapter_image (transformers
+ *    CLIPVisionModelWithProjection).  Weight names are the transformers state-dict keys
+ *    ("vision_model.embeddings.class_embedding", ..., "vision_model.pre_layrnorm.weight" (sic), ...,
+ *    "visual_projection.weight").  Create rejects (SD_ERR_UNSUPPORTED, with a message): image_size not divisible by
+ *    patch_size, hidden_size not divisible by num_heads or not a multiple of 8, and a head dim that is neither one of
+ *    the attention kernels' nor paddable to one of at most 128 (hidden 1664 / 16 heads = 104 runs at 128: the heads
+ *    are zero-padded when the weights are packed). ------------------------------------------------------------------ */
+int sd_clip_vision_create(const sd_clip_vision_config* cfg, sd_clip_vision** out);
+int sd_clip_vision_destroy(sd_clip_vision* c);
+int sd_clip_vision_num_weights(const sd_clip_vision* c);
+int sd_clip_vision_weight_info(const sd_clip_vision* c, int index, const char** key, int64_t* shape4, int* ndim);
+int sd_clip_vision_set_weight(sd_clip_vision* c, const char* key, const void* data, const int64_t* shape, int ndim,
+                              int dtype);
+int sd_clip_vision_finalize(sd_clip_vision* c);
+/* image_encoder(pixel_values, output_hidden_states=True): pixel_values f16 NCHW [B,3,S,S] (device), already
+ * normalised.  T = 1 + (S / P)^2 tokens.  Outputs, each nullable, all f16 on the device:
+ *   hidden_states [num_layers+1, B, T, H]  ([0] = pre_layrnorm(embeddings), then every layer's output)
+ *   last_hidden   [B, T, H]                (= hidden_states[num_layers]: no final norm)
+ *   pooled        [B, H]                   (post_layernorm(last_hidden[:, 0]); pooler_output)
+ *   image_embeds  [B, projection_dim]      (visual_projection(pooled)) */
+int sd_clip_vision_forward(sd_clip_vision* c, const void* pixel_values, void* hidden_states, void* last_hidden,
+                           void* pooled, void* image_embeds, int B, void* stream);
+int sd_clip_vision_memory(const sd_clip_vision* c, int64_t* weight_bytes, int64_t* workspace_bytes);
+/* The embedding stage of the tower alone, one launch: pixels f16 [B,3,S,S], w f16 [H,3,P,P] (patch_embedding.weight, no
+ * bias), class_embedding f16 [H], position_embedding f16 [1 + (S/P)^2, H] -> out f16 [B, 1 + (S/P)^2, H] with row stride
+ * ld_out elements (>= H, a multiple of 8), BEFORE pre_layrnorm.  fp32 accumulation, one fp16 rounding. */
+int sd_op_vit_patch_embed(const void* pixels, const void* w, const void* class_embedding, const void* position_embedding,
+                          void* out, int64_t ld_out, int B, int image_size, int patch_size, int hidden, void* stream);
 
 /* -- denoise-step glue (sd_unified_pipeline.py:467-469, :484-489) ---------------------------- */
 /* latent_model_input = cat([latents]*2) * in_scale   (in_scale = 1 for DDIM / DPM++) */

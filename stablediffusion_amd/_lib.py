@@ -68,6 +68,20 @@ class SdClipConfig(C.Structure):
     ]
 
 
+class SdClipVisionConfig(C.Structure):
+    _fields_ = [
+        ("hidden_size", C.c_int32),
+        ("intermediate_size", C.c_int32),
+        ("num_layers", C.c_int32),
+        ("num_heads", C.c_int32),
+        ("image_size", C.c_int32),
+        ("patch_size", C.c_int32),
+        ("hidden_act", C.c_int32),
+        ("projection_dim", C.c_int32),
+        ("layer_norm_eps", C.c_float),
+    ]
+
+
 class SdProfEntry(C.Structure):
     _fields_ = [("kernel", C.c_char * 64), ("flops", C.c_double), ("bytes", C.c_double),
                 ("ms", C.c_double), ("launches", C.c_int64)]
@@ -158,6 +172,15 @@ SIGNATURES = {
     "sd_clip_forward": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
     "sd_clip_final_layer_norm": (_I, [_P, _P, _P, _I64, _P]),
     "sd_clip_memory": (_I, [_P, C.POINTER(_I64), C.POINTER(_I64)]),
+    "sd_clip_vision_create": (_I, [C.POINTER(SdClipVisionConfig), C.POINTER(_P)]),
+    "sd_clip_vision_destroy": (_I, [_P]),
+    "sd_clip_vision_num_weights": (_I, [_P]),
+    "sd_clip_vision_weight_info": (_I, [_P, _I, C.POINTER(C.c_char_p), C.POINTER(_I64), C.POINTER(_I)]),
+    "sd_clip_vision_set_weight": (_I, [_P, C.c_char_p, _P, C.POINTER(_I64), _I, _I]),
+    "sd_clip_vision_finalize": (_I, [_P]),
+    "sd_clip_vision_forward": (_I, [_P, _P, _P, _P, _P, _P, _I, _P]),
+    "sd_clip_vision_memory": (_I, [_P, C.POINTER(_I64), C.POINTER(_I64)]),
+    "sd_op_vit_patch_embed": (_I, [_P, _P, _P, _P, _P, _I64, _I, _I, _I, _I, _P]),
     "sd_op_attention_ex": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "sd_cfg_duplicate": (_I, [_P, _P, _I64, _I, _F, _P]),
     "sd_inpaint_blend": (_I, [_P, _P, _P, _P, _F, _F, _I, _I, _I, _I, _P]),

@@ -117,6 +117,24 @@ def load_unet_folder(root: str) -> Tuple[UNetConfig, Dict[str, torch.Tensor]]:
     return ucfg, load_safetensors(_find_weights(folder))
 
 
+def load_image_encoder_folder(path: str):
+    """An IP-Adapter's `image_encoder/` folder (transformers CLIPVisionModelWithProjection): `config.json` plus
+    `model.fp16.safetensors` or `model.safetensors` -> (CLIPVisionConfig, state dict).  `path` may also be the folder
+    above it.  Local files only: nothing is downloaded."""
+    from .config import CLIPVisionConfig
+    folder = os.path.join(path, "image_encoder")
+    if not os.path.exists(os.path.join(folder, "config.json")):
+        folder = path
+    with open(os.path.join(folder, "config.json")) as f:
+        cfg = CLIPVisionConfig.from_dict(json.load(f))
+    for name in ("model.fp16.safetensors", "model.safetensors"):
+        p = os.path.join(folder, name)
+        if os.path.exists(p):
+            sd = load_safetensors(p)
+            return cfg, {k: v for k, v in sd.items() if not k.endswith("position_ids")}
+    raise FileNotFoundError(f"no model[.fp16].safetensors under {folder}")
+
+
 SCHEDULER_FIELDS = ("num_train_timesteps", "beta_start", "beta_end", "steps_offset", "timestep_spacing",
                     "prediction_type", "rescale_betas_zero_snr", "original_inference_steps", "timestep_scaling")
 

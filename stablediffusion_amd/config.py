@@ -9,7 +9,7 @@ The pipeline reads a handful of them back through `model.base.config.*` / `model
 """
 from __future__ import annotations
 
-from dataclasses import dataclass, field, asdict
+from dataclasses import dataclass, field, fields, asdict
 from typing import Optional, Tuple
 
 
@@ -126,6 +126,59 @@ def openclip_bigg() -> CLIPTextConfig:
     """SDXL `text_encoder_2` (OpenCLIP ViT-bigG/14 text tower, with projection)."""
     return CLIPTextConfig(hidden_size=1280, intermediate_size=5120, num_hidden_layers=32, num_attention_heads=20,
                           hidden_act="gelu", projection_dim=1280)
+
+
+@dataclass(frozen=True)
+class CLIPVisionConfig:
+    """transformers CLIPVisionConfig fields the engine needs: the image encoder of an IP-Adapter
+    (CLIPVisionModelWithProjection).  Defaults: OpenCLIP ViT-H/14, the tower of the SD1.5 adapters."""
+    hidden_size: int = 1280
+    intermediate_size: int = 5120
+    num_hidden_layers: int = 32
+    num_attention_heads: int = 16
+    image_size: int = 224
+    patch_size: int = 14
+    num_channels: int = 3
+    hidden_act: str = "gelu"
+    projection_dim: int = 1024
+    layer_norm_eps: float = 1e-5
+
+    def to_dict(self):
+        return asdict(self)
+
+    @classmethod
+    def from_dict(cls, d):
+        """From a transformers `config.json` (a CLIPVisionConfig, or a CLIPConfig with a `vision_config` section whose
+        `projection_dim` lives at the top level); unknown keys are ignored."""
+        d = dict(d)
+        if isinstance(d.get("vision_config"), dict):
+            top = d
+            d = dict(d["vision_config"])
+            d.setdefault("projection_dim", top.get("projection_dim", cls.projection_dim))
+        names = {f.name for f in fields(cls)}
+        return cls(**{k: v for k, v in d.items() if k in names})
+
+    @classmethod
+    def from_hf(cls, hf):
+        return cls.from_dict(hf.to_dict())
+
+
+def clip_vit_l14() -> CLIPVisionConfig:
+    """OpenAI CLIP ViT-L/14 vision tower (published values, recalled: DESIGN.md §8)."""
+    return CLIPVisionConfig(hidden_size=1024, intermediate_size=4096, num_hidden_layers=24, num_attention_heads=16,
+                            hidden_act="quick_gelu", projection_dim=768)
+
+
+def clip_vit_h14() -> CLIPVisionConfig:
+    """OpenCLIP ViT-H/14 vision tower: the SD1.5 IP-Adapters' image encoder (recalled: DESIGN.md §8)."""
+    return CLIPVisionConfig()
+
+
+def clip_vit_bigg14() -> CLIPVisionConfig:
+    """OpenCLIP ViT-bigG/14 vision tower: the default SDXL IP-Adapter's image encoder (recalled: DESIGN.md §8).
+    1664 / 16 heads = 104: the engine pads the heads to 128 when it packs the weights."""
+    return CLIPVisionConfig(hidden_size=1664, intermediate_size=8192, num_hidden_layers=48, num_attention_heads=16,
+                            hidden_act="gelu", projection_dim=1280)
 
 
 def sd15_unet() -> UNetConfig:

@@ -12,6 +12,7 @@ using namespace sd;
 struct sd_unet { UNet impl; explicit sd_unet(const sd_unet_config& c) : impl(c) {} };
 struct sd_vae { VAE impl; explicit sd_vae(const sd_vae_config& c) : impl(c) {} };
 struct sd_clip { CLIP impl; explicit sd_clip(const sd_clip_config& c) : impl(c) {} };
+struct sd_clip_vision { CLIPVision impl; explicit sd_clip_vision(const sd_clip_vision_config& c) : impl(c) {} };
 struct sd_controlnet {
     ControlNet impl;
     sd_controlnet(const sd_unet_config& c, int cc) : impl(c, cc) {}
@@ -444,6 +445,81 @@ int sd_clip_memory(const sd_clip* c, int64_t* weight_bytes, int64_t* workspace_b
     if (weight_bytes) *weight_bytes = c->impl.ws.packed_bytes();
     if (workspace_bytes) *workspace_bytes = (int64_t)c->impl.arena.capacity();
     return SD_OK;
+}
+
+// ------------------------------------------------------------------------------------ CLIP vision
+int sd_clip_vision_create(const sd_clip_vision_config* cfg, sd_clip_vision** out) {
+    if (!out || !cfg) { set_error("null argument"); return SD_ERR_INVALID; }
+    if (cfg->hidden_size < 8 || cfg->intermediate_size < 8 || cfg->num_layers < 1 || cfg->num_heads < 1 ||
+        cfg->image_size < 1 || cfg->patch_size < 1 || cfg->projection_dim < 1 ||
+        (cfg->hidden_act != 0 && cfg->hidden_act != 1)) {
+        set_error("sd_clip_vision_create: bad config (sizes must be positive, hidden_act 0 quick_gelu or 1 gelu)");
+        return SD_ERR_INVALID;
+    }
+    if (cfg->image_size % cfg->patch_size != 0) {
+        set_error("sd_clip_vision_create: image_size " + std::to_string(cfg->image_size) + " is not divisible by patch_size " +
+                  std::to_string(cfg->patch_size));
+        return SD_ERR_UNSUPPORTED;
+    }
+    if (cfg->hidden_size % cfg->num_heads != 0) {
+        set_error("sd_clip_vision_create: hidden_size " + std::to_string(cfg->hidden_size) + " is not divisible by num_heads " +
+                  std::to_string(cfg->num_heads));
+        return SD_ERR_UNSUPPORTED;
+    }
+    if (cfg->hidden_size % 8 != 0 || cfg->intermediate_size % 8 != 0 || cfg->hidden_size > 2048) {
+        set_error("sd_clip_vision_create: hidden_size " + std::to_string(cfg->hidden_size) + " / intermediate_size " +
+                  std::to_string(cfg->intermediate_size) + " must be multiples of 8, hidden_size at most 2048");
+        return SD_ERR_UNSUPPORTED;
+    }
+    const int d = cfg->hidden_size / cfg->num_heads;
+    if (clip_vision_padded_head_dim(d) == 0) {
+        set_error("sd_clip_vision_create: unsupported head dim " + std::to_string(d) +
+                  " (heads are zero-padded up to 128 at most)");
+        return SD_ERR_UNSUPPORTED;
+    }
+    *out = new (std::nothrow) sd_clip_vision(*cfg);
+    if (!*out) { set_error("out of host memory"); return SD_ERR_INVALID; }
+    return SD_OK;
+}
+int sd_clip_vision_destroy(sd_clip_vision* c) { delete c; return SD_OK; }
+int sd_clip_vision_num_weights(const sd_clip_vision* c) { return c ? (int)c->impl.ws.order.size() : 0; }
+int sd_clip_vision_weight_info(const sd_clip_vision* c, int index, const char** key, int64_t* shape4, int* ndim) {
+    if (!c) { set_error("null handle"); return SD_ERR_INVALID; }
+    return weight_info(c->impl.ws, index, key, shape4, ndim);
+}
+int sd_clip_vision_set_weight(sd_clip_vision* c, const char* key, const void* data, const int64_t* shape, int ndim, int dtype) {
+    if (!c || !key || !data || !shape) { set_error("null argument"); return SD_ERR_INVALID; }
+    if (c->impl.finalized) { set_error("set_weight after finalize"); return SD_ERR_STATE; }
+    return c->impl.ws.set(key, data, shape, ndim, dtype);
+}
+int sd_clip_vision_finalize(sd_clip_vision* c) {
+    if (!c) { set_error("null handle"); return SD_ERR_INVALID; }
+    return c->impl.finalize();
+}
+int sd_clip_vision_forward(sd_clip_vision* c, const void* pixel_values, void* hidden_states, void* last_hidden, void* pooled,
+                           void* image_embeds, int B, void* stream) {
+    if (!c || !pixel_values) { set_error("null argument"); return SD_ERR_INVALID; }
+    return c->impl.forward(static_cast<const half_t*>(pixel_values), static_cast<half_t*>(hidden_states),
+                           static_cast<half_t*>(last_hidden), static_cast<half_t*>(pooled), static_cast<half_t*>(image_embeds),
+                           B, static_cast<hipStream_t>(stream));
+}
+int sd_clip_vision_memory(const sd_clip_vision* c, int64_t* weight_bytes, int64_t* workspace_bytes) {
+    if (!c) { set_error("null handle"); return SD_ERR_INVALID; }
+    if (weight_bytes) *weight_bytes = c->impl.ws.packed_bytes();
+    if (workspace_bytes) *workspace_bytes = (int64_t)c->impl.arena.capacity();
+    return SD_OK;
+}
+int sd_op_vit_patch_embed(const void* pixels, const void* w, const void* class_embedding, const void* position_embedding,
+                          void* out, int64_t ld_out, int B, int image_size, int patch_size, int hidden, void* stream) {
+    if (!pixels || !w || !class_embedding || !position_embedding || !out ||
+        (reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(position_embedding)) % 16 != 0) {
+        set_error("sd_op_vit_patch_embed: null or misaligned argument (out and position_embedding 16-byte aligned)");
+        return SD_ERR_INVALID;
+    }
+    return launch_vit_patch_embed(static_cast<const half_t*>(pixels), static_cast<const half_t*>(w),
+                                  static_cast<const half_t*>(class_embedding), static_cast<const half_t*>(position_embedding),
+                                  static_cast<half_t*>(out), (long)ld_out, B, image_size, patch_size, hidden,
+                                  static_cast<hipStream_t>(stream));
 }
 
 // ------------------------------------------------------------------------------------- step glue

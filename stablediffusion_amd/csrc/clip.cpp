@@ -72,14 +72,45 @@ int CLIP::finalize() {
     return 0;
 }
 
+void run_clip_layers(Ctx& c, const std::vector<ClipLayer>& layers, const ClipStack& g,
+                     const std::function<half_t*(int)>& slab, int B, int T) {
+    Arena& a = *c.arena;
+    const int H = g.H, I = g.I;
+    const int A = g.heads * g.d;                    // attention width: H, or more with zero-padded heads
+    const long M = (long)B * T;
+    auto up64 = [](int v) { return (v + 63) / 64 * 64; };
+    const int Hp = up64(H), Ap = up64(A), Ip = up64(I);
+    View n(a.alloc_h(M * Hp), Hp, H), qkv(a.alloc_h(M * 3 * A), 3 * A, 3 * A), att(a.alloc_h(M * Ap), Ap, A);
+    View t2(a.alloc_h(M * H), H, H), f(a.alloc_h(M * Ip), Ip, I);
+    // a GEMM reads its packed K columns of every input row: where that is more than the producer writes, the rest must
+    // hold zeros (no width of a published tower needs it)
+    if (!c.dry && !c.err) {
+        hipError_t e = hipSuccess;
+        if (Hp != H) e = hipMemsetAsync(n.p, 0, (size_t)M * Hp * sizeof(half_t), c.stream);
+        if (e == hipSuccess && Ap != A) e = hipMemsetAsync(att.p, 0, (size_t)M * Ap * sizeof(half_t), c.stream);
+        if (e == hipSuccess && Ip != I) e = hipMemsetAsync(f.p, 0, (size_t)M * Ip * sizeof(half_t), c.stream);
+        if (e != hipSuccess) { set_error(std::string("clip: hipMemsetAsync: ") + hipGetErrorString(e)); c.err = 3; }
+    }
+    for (size_t l = 0; l < layers.size(); ++l) {
+        const ClipLayer& w = layers[l];
+        View x(slab((int)l), H, H), y(slab((int)l + 1), H, H);
+        op_layernorm(c, w.ln1, x, n, M, g.eps);
+        op_conv(c, w.qkv, n, B, T, 1, qkv);
+        op_attention(c, qkv.slice(0, A), qkv.slice(A, A), qkv.slice(2 * A, A), att, B, T, T, g.heads, g.d, g.causal,
+                     g.prescaled);
+        op_conv(c, w.out, att, B, T, 1, t2, 1, 0, nullptr, 0, &x);
+        op_layernorm(c, w.ln2, t2, n, M, g.eps);
+        op_conv(c, w.fc1, n, B, T, 1, f, 1, 0, nullptr, 0, nullptr, 0, -1, g.act);
+        op_conv(c, w.fc2, f, B, T, 1, y, 1, 0, nullptr, 0, &t2);
+    }
+}
+
 int CLIP::run(Ctx& c, const int* ids, const int* eos_index, half_t* hidden_states, half_t* last_hidden, half_t* pooled,
               half_t* text_embeds, int B, int T) {
     Arena& a = *c.arena;
     const int H = cfg.hidden_size, I = cfg.intermediate_size, L = cfg.num_layers;
-    const int d = H / cfg.num_heads;
     const long M = (long)B * T;
     const float eps = cfg.layer_norm_eps;
-    const int act = cfg.hidden_act == 0 ? 1 : 2;
     hipStream_t s = c.stream;
     const bool go = !c.dry;
 
@@ -89,19 +120,12 @@ int CLIP::run(Ctx& c, const int* ids, const int* eos_index, half_t* hidden_state
     auto slab = [&](int l) { return hidden_states ? hidden_states + (long)l * M * H : pp[l & 1]; };
 
     if (go && !c.err) c.err = launch_clip_embed(ids, tok, pos, slab(0), B, T, H, cfg.vocab_size, s);
-    View n(a.alloc_h(M * H), H, H), qkv(a.alloc_h(M * 3 * H), 3 * H, 3 * H), att(a.alloc_h(M * H), H, H);
-    View t2(a.alloc_h(M * H), H, H), f(a.alloc_h(M * I), I, I);
-    for (int l = 0; l < L; ++l) {
-        const ClipLayer& w = layers[(size_t)l];
-        View x(slab(l), H, H), y(slab(l + 1), H, H);
-        op_layernorm(c, w.ln1, x, n, M, eps);
-        op_conv(c, w.qkv, n, B, T, 1, qkv);
-        op_attention(c, qkv.slice(0, H), qkv.slice(H, H), qkv.slice(2 * H, H), att, B, T, T, cfg.num_heads, d, 1);
-        op_conv(c, w.out, att, B, T, 1, t2, 1, 0, nullptr, 0, &x);
-        op_layernorm(c, w.ln2, t2, n, M, eps);
-        op_conv(c, w.fc1, n, B, T, 1, f, 1, 0, nullptr, 0, nullptr, 0, -1, act);
-        op_conv(c, w.fc2, f, B, T, 1, y, 1, 0, nullptr, 0, &t2);
-    }
+    ClipStack g;
+    g.H = H; g.I = I; g.heads = cfg.num_heads; g.d = H / cfg.num_heads;
+    g.act = cfg.hidden_act == 0 ? 1 : 2;
+    g.eps = cfg.layer_norm_eps;
+    g.causal = 1;
+    run_clip_layers(c, layers, g, slab, B, T);
     if (last_hidden || pooled || text_embeds) {
         half_t* lh = last_hidden ? last_hidden : a.alloc_h(M * H);
         op_layernorm(c, final_ln, View(slab(L), H, H), View(lh, H, H), M, eps);

@@ -371,6 +371,10 @@ int launch_dup_f32(const float* x, float* out, long n, hipStream_t s);          
 // CLIP text embeddings: out[b, t, :] = token_table[ids[b, t], :] + position_table[t, :]  (ids clamped to the table)
 int launch_clip_embed(const int* ids, const half_t* tok, const half_t* pos, half_t* out, int B, int T, int H, int vocab,
                       hipStream_t s);
+// CLIPVisionEmbeddings before pre_layrnorm (vit.hip), one launch: pixels [B,3,S,S] NCHW, w [H][3][P][P] (the raw conv
+// weight, no bias), cls [H], pos [1 + (S/P)^2][H] -> out [B, 1 + (S/P)^2, H] with row stride ld (>= H, % 8 == 0).
+int launch_vit_patch_embed(const half_t* pixels, const half_t* w, const half_t* cls, const half_t* pos, half_t* out, long ld,
+                           int B, int S, int P, int H, hipStream_t s);
 // out[b, :] = x[b * T + idx[b], :] as f16 (out16) and / or f32 (out32); idx clamped to [0, T)
 int launch_gather_rows(const half_t* x, long ldx, const int* idx, half_t* out16, float* out32, int B, int T, int H,
                        hipStream_t s);

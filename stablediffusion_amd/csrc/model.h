@@ -357,6 +357,20 @@ struct ClipLayer {
     NormW ln1, ln2;
     ConvW qkv, out, fc1, fc2;
 };
+// The pre-LN layer stack both CLIP towers run.  Per layer: LN -> fused q|k|v GEMM -> attention -> out-proj GEMM
+// (+residual) -> LN -> fc1 GEMM (+activation) -> fc2 GEMM (+residual); layer l reads slab(l) and writes slab(l + 1)
+// ([B T, H], row stride H).  d is the head dim the attention runs at: the fused q|k|v matrix has 3 heads d rows and
+// out-proj heads d columns, which is more than H where the vision tower padded its heads at pack time.  Scratch rows
+// that feed a GEMM are as wide as its packed K (a multiple of 64); columns past the real width are zeroed once per call.
+struct ClipStack {
+    int H = 0, I = 0, heads = 1, d = 0;
+    int act = 0;                // IGemmParams::act of fc1
+    float eps = 1e-5f;
+    int causal = 0, prescaled = 0;
+};
+void run_clip_layers(Ctx& c, const std::vector<ClipLayer>& layers, const ClipStack& g,
+                     const std::function<half_t*(int)>& slab, int B, int T);
+
 struct CLIP {
     explicit CLIP(const sd_clip_config& c);
     int finalize();
@@ -378,6 +392,38 @@ struct CLIP {
   private:
     int run(Ctx& c, const int* ids, const int* eos_index, half_t* hidden_states, half_t* last_hidden, half_t* pooled,
             half_t* text_embeds, int B, int T);
+};
+
+// Head dim the attention runs at for a model head dim d: d itself where attention_supported, else the next supported
+// one up to 128 (the heads are zero-padded at pack time), 0 when there is none.
+int clip_vision_padded_head_dim(int d);
+
+// CLIP vision tower (transformers CLIPVisionModelWithProjection): patch / class / position embedding, pre_layrnorm, the
+// non-causal layer stack, post_layernorm of the class token, visual_projection.
+struct CLIPVision {
+    explicit CLIPVision(const sd_clip_vision_config& c);
+    int finalize();
+    int forward(const half_t* pixels, half_t* hidden_states, half_t* last_hidden, half_t* pooled, half_t* image_embeds, int B,
+                hipStream_t stream);
+
+    sd_clip_vision_config cfg;
+    int tokens = 0;             // 1 + (image_size / patch_size)^2
+    int d = 0, dp = 0;          // head dim of the model / the one the attention runs at (dp > d: zero-padded heads)
+    WeightStore ws;
+    Arena arena;
+    bool finalized = false;
+    long planned_key = -1;
+    half_t* cls = nullptr;      // [H]
+    half_t* patch = nullptr;    // [H][3 P P]
+    half_t* pos = nullptr;      // [tokens][H]
+    half_t* proj = nullptr;     // [projection_dim][H], no bias
+    std::vector<ClipLayer> layers;
+    NormW pre_ln, post_ln;
+
+  private:
+    int pack_attn(int i, ClipLayer* l);
+    int run(Ctx& c, const half_t* pixels, half_t* hidden_states, half_t* last_hidden, half_t* pooled, half_t* image_embeds,
+            int B);
 };
 
 }  // namespace sd

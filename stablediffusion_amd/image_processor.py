@@ -24,6 +24,72 @@ except ImportError:                    # pragma: no cover
 _RESAMPLE = {"lanczos": "LANCZOS", "bilinear": "BILINEAR", "bicubic": "BICUBIC", "nearest": "NEAREST"}
 
 
+OPENAI_CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)
+OPENAI_CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
+
+
+class _PixelBatch(dict):
+    """`proc(...).pixel_values`, as transformers' BatchFeature gives it."""
+
+    def __getattr__(self, name):
+        try:
+            return self[name]
+        except KeyError:
+            raise AttributeError(name) from None
+
+
+class ClipImageProcessor:
+    """The preprocessing every CLIP vision tower was trained with (transformers `CLIPImageProcessor` defaults): RGB,
+    shortest edge resized to `size` with PIL bicubic (the long edge truncated, as transformers computes it), centre
+    crop `size` x `size`, scale by 1/255, normalise with CLIP's mean / std.  Fills `SDModelWrapper.feature_extractor`:
+    `proc(images, return_tensors="pt").pixel_values` is float32 [B, 3, size, size].  Inputs: a PIL image, an HWC uint8
+    array, or a list of either.  Pinned against transformers in tests/test_clip_vision.py."""
+
+    def __init__(self, size: int = 224, image_mean=OPENAI_CLIP_MEAN, image_std=OPENAI_CLIP_STD):
+        self.size = int(size)
+        self.image_mean = tuple(float(v) for v in image_mean)
+        self.image_std = tuple(float(v) for v in image_std)
+
+    def _one(self, image) -> np.ndarray:
+        if Image is None:                          # pragma: no cover
+            raise RuntimeError("ClipImageProcessor needs PIL")
+        if isinstance(image, torch.Tensor):
+            image = image.detach().cpu().numpy()
+        if isinstance(image, np.ndarray):
+            if image.ndim != 3 or image.shape[-1] != 3 or image.dtype != np.uint8:
+                raise ValueError("ClipImageProcessor takes arrays as HWC uint8 RGB images")
+            image = Image.fromarray(image)
+        if not isinstance(image, Image.Image):
+            raise ValueError(f"ClipImageProcessor: unsupported input {type(image)}")
+        image = image.convert("RGB")
+        w, h = image.size
+        S = self.size
+        short, long = (w, h) if w <= h else (h, w)
+        new_long = int(S * long / short)
+        nw, nh = (S, new_long) if w <= h else (new_long, S)
+        if (nw, nh) != (w, h):
+            image = image.resize((nw, nh), resample=Image.Resampling.BICUBIC)
+        left, top = (nw - S) // 2, (nh - S) // 2
+        arr = np.asarray(image)[top:top + S, left:left + S, :]
+        x = (arr.astype(np.float64) * (1 / 255)).astype(np.float32)
+        x = (x - np.array(self.image_mean, dtype=np.float32)) / np.array(self.image_std, dtype=np.float32)
+        return np.ascontiguousarray(x.transpose(2, 0, 1))
+
+    def preprocess(self, images, return_tensors: Optional[str] = "pt", **unused):
+        if not isinstance(images, (list, tuple)):
+            images = [images]
+        if not images:
+            raise ValueError("ClipImageProcessor: no images")
+        batch = np.stack([self._one(im) for im in images], axis=0)
+        if return_tensors == "pt":
+            return _PixelBatch(pixel_values=torch.from_numpy(batch))
+        if return_tensors in (None, "np"):
+            return _PixelBatch(pixel_values=batch)
+        raise ValueError(f"return_tensors={return_tensors!r} is not supported (\"pt\" or \"np\")")
+
+    __call__ = preprocess
+
+
 class VaeImageProcessor:
     def __init__(self, do_resize: bool = True, vae_scale_factor: int = 8, resample: str = "lanczos",
                  do_normalize: bool = True, do_binarize: bool = False, do_convert_rgb: bool = False,

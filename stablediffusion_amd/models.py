@@ -828,3 +828,110 @@ class HipCLIPTextModel:
         if hs is not None:
             names.append("hidden_states"); vals.append(tuple(hs[i] for i in range(L + 1)))
         return _ClipOutput(names, vals)
+
+
+class HipCLIPVisionModelWithProjection:
+    """gfx950 engine behind the call surface `encode_image` uses on `SDModelWrapper.image_encoder` (transformers
+    CLIPVisionModelWithProjection): `__call__(pixel_values, output_hidden_states=False)` -> `.image_embeds`,
+    `.last_hidden_state` (no final norm), `.pooler_output`, `.hidden_states`; `.config`, `.dtype`, `.device`,
+    `.parameters()`.  `interpolate_pos_encoding` and attention masks are not supported."""
+
+    def __init__(self, config, device: str = "cuda"):
+        from .config import CLIPVisionConfig
+        if not isinstance(config, CLIPVisionConfig):
+            raise TypeError("config must be a stablediffusion_amd.config.CLIPVisionConfig (see CLIPVisionConfig.from_dict)")
+        acts = {"quick_gelu": 0, "gelu": 1}
+        if config.hidden_act not in acts:
+            raise _lib.EngineError(f"unsupported CLIP activation {config.hidden_act!r}")
+        if config.num_channels != 3:
+            raise _lib.EngineError("the CLIP vision tower reads 3-channel images")
+        self._lib = _lib.load()
+        self.cfg = config
+        self.device = torch.device(device)
+        self.dtype = torch.float16
+        c = _lib.SdClipVisionConfig()
+        c.hidden_size = config.hidden_size
+        c.intermediate_size = config.intermediate_size
+        c.num_layers = config.num_hidden_layers
+        c.num_heads = config.num_attention_heads
+        c.image_size = config.image_size
+        c.patch_size = config.patch_size
+        c.hidden_act = acts[config.hidden_act]
+        c.projection_dim = config.projection_dim
+        c.layer_norm_eps = config.layer_norm_eps
+        self._h = C.c_void_p()
+        _lib.check(self._lib.sd_clip_vision_create(C.byref(c), C.byref(self._h)), "sd_clip_vision_create")
+        self.config = _Config(**config.to_dict())
+        self._finalized = False
+
+    @classmethod
+    def from_state_dict(cls, config, state_dict: Dict[str, torch.Tensor], device: str = "cuda"):
+        return cls(config, device=device).load_state_dict(state_dict)
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None):
+                self._lib.sd_clip_vision_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    def load_state_dict(self, state_dict: Dict[str, torch.Tensor], strict: bool = True):
+        """transformers state-dict keys (`vision_model.*`, `visual_projection.weight`); `position_ids` buffers are
+        ignored, and so is the text half of a full CLIPModel checkpoint."""
+        _lib.require_gpu()
+        sd = {k: v for k, v in state_dict.items()
+              if not k.endswith("position_ids") and (k.startswith("vision_model.") or k.startswith("visual_projection."))}
+        with torch.cuda.device(self.device):
+            _load_weights(self._lib, self._h, "clip_vision", sd, strict)
+            _lib.check(self._lib.sd_clip_vision_finalize(self._h), "sd_clip_vision_finalize")
+        self._finalized = True
+        return self
+
+    def memory(self):
+        w, s = C.c_int64(), C.c_int64()
+        _lib.check(self._lib.sd_clip_vision_memory(self._h, C.byref(w), C.byref(s)), "sd_clip_vision_memory")
+        return w.value, s.value
+
+    def to(self, device=None, dtype=None):
+        if device is not None and not isinstance(device, torch.dtype) and torch.device(device).type != "cuda":
+            raise _lib.EngineError("HipCLIPVisionModelWithProjection lives on the HIP device only")
+        return self
+
+    def eval(self):
+        return self
+
+    def parameters(self):
+        # encode_image reads the first parameter for where and in which dtype the encoder wants its pixels
+        return iter((torch.empty(0, device=self.device, dtype=self.dtype),))
+
+    def __call__(self, pixel_values, output_attentions=None, output_hidden_states=None, return_dict=True,
+                 interpolate_pos_encoding: bool = False, **unused):
+        if not self._finalized:
+            raise _lib.EngineError("weights not loaded")
+        if output_attentions or interpolate_pos_encoding:
+            raise NotImplementedError("HipCLIPVisionModelWithProjection: output_attentions / interpolate_pos_encoding "
+                                      "are not supported")
+        S, H, L, P = self.cfg.image_size, self.cfg.hidden_size, self.cfg.num_hidden_layers, self.cfg.projection_dim
+        if pixel_values.ndim != 4 or tuple(pixel_values.shape[1:]) != (3, S, S):
+            raise ValueError(f"pixel_values must be [B, 3, {S}, {S}], got {tuple(pixel_values.shape)}")
+        px = _as_f16(pixel_values, self.device)
+        B = px.shape[0]
+        T = 1 + (S // self.cfg.patch_size) ** 2
+        f16 = dict(device=self.device, dtype=torch.float16)
+        hs = torch.empty((L + 1, B, T, H), **f16) if output_hidden_states else None
+        last = torch.empty((B, T, H), **f16)
+        pooled = torch.empty((B, H), **f16)
+        emb = torch.empty((B, P), **f16)
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        with torch.cuda.device(self.device):
+            rc = self._lib.sd_clip_vision_forward(self._h, ptr(px), ptr(hs), ptr(last), ptr(pooled), ptr(emb), B,
+                                                  C.c_void_p(_stream_ptr()))
+        _lib.check(rc, "sd_clip_vision_forward")
+        # CLIPVisionModelOutput: image_embeds, last_hidden_state, hidden_states (+ pooler_output by name)
+        names, vals = ["image_embeds", "last_hidden_state"], [emb, last]
+        if hs is not None:
+            names.append("hidden_states"); vals.append(tuple(hs[i] for i in range(L + 1)))
+        out = _ClipOutput(names, vals)
+        out.pooler_output = pooled
+        return out

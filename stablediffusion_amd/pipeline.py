@@ -45,9 +45,10 @@ class SDModelWrapper:
         # the third UNet-shaped slot of models/stable_diffusion.py:40-103: the SDXL refiner (load_refiner).  LoRA, FreeU,
         # IP-Adapter and ControlNet address .base, as the reference's loaders do; a LoRA re-fuse leaves it alone
         self.refiner = refiner
-        # IP-Adapter (sd_unified_pipeline.py:441-449): host image encoder (e.g. transformers'
-        # CLIPVisionModelWithProjection) and its CLIPImageProcessor, built by the caller; the adapter's converted
-        # weights stay here so that a LoRA re-fuse (which rebuilds .base) can attach it again
+        # IP-Adapter (sd_unified_pipeline.py:441-449): the image encoder and its preprocessing -- the engine's own
+        # (load_image_encoder: HipCLIPVisionModelWithProjection + ClipImageProcessor) or a caller-built torch pair
+        # (transformers' CLIPVisionModelWithProjection + CLIPImageProcessor); the adapter's converted weights stay
+        # here so that a LoRA re-fuse (which rebuilds .base) can attach it again
         self.image_encoder = image_encoder
         self.feature_extractor = feature_extractor
         self._ip = None                  # (diffusers-named state dict, image_embed_dim, num_tokens)
@@ -265,6 +266,32 @@ class SDModelWrapper:
             self.base.set_ip_adapter_scale(1.0)
         self._ip = None
         self._ip_scale = 1.0
+
+    def load_image_encoder(self, path_or_cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None):
+        """The CLIP vision tower an IP-Adapter was trained against, on the engine: a local `image_encoder/` folder
+        (checkpoints.load_image_encoder_folder) or a CLIPVisionConfig with its transformers-named state dict.  Sets
+        `.image_encoder` (HipCLIPVisionModelWithProjection) and `.feature_extractor` (ClipImageProcessor at the tower's
+        image size), so `ip_adapter_image=<PIL image>` runs with no torch module on the path.  A LoRA re-fuse rebuilds
+        only the UNet and the text encoders and leaves both alone.  Nothing is downloaded."""
+        from .config import CLIPVisionConfig
+        from .image_processor import ClipImageProcessor
+        from .models import HipCLIPVisionModelWithProjection
+        if isinstance(path_or_cfg, CLIPVisionConfig):
+            if state_dict is None:
+                raise ValueError("load_image_encoder(config, state_dict): the state dict is missing")
+            cfg = path_or_cfg
+        else:
+            if state_dict is not None:
+                raise ValueError("load_image_encoder: a state dict goes with a CLIPVisionConfig, not with a path")
+            from . import checkpoints
+            cfg, state_dict = checkpoints.load_image_encoder_folder(os.fspath(path_or_cfg))
+        self.image_encoder = None            # an old encoder's device memory goes before the new one is packed
+        self.image_encoder = HipCLIPVisionModelWithProjection.from_state_dict(cfg, state_dict, device=str(self.device))
+        self.feature_extractor = ClipImageProcessor(size=cfg.image_size)
+
+    def unload_image_encoder(self):
+        self.image_encoder = None
+        self.feature_extractor = None
 
     def _refuse(self):
         # (kept for callers that want the rebuild now; load / set / delete only mark the state changed)
@@ -948,7 +975,8 @@ class StableDiffusionUnifiedPipeline:
     def encode_image(self, image, device, num_images_per_prompt):
         """diffusers 0.27.2 `encode_image` for the base adapters' ImageProjection: image_encoder(feature_extractor(image)
         .pixel_values).image_embeds, repeated per prompt image; the negative is zeros_like (it still goes through the
-        adapter's projection in the UNet, so its tokens are not zero).  Host PyTorch, once per call."""
+        adapter's projection in the UNet, so its tokens are not zero).  Once per call: on the engine with
+        load_image_encoder's tower (which answers parameters() with its device and dtype), in PyTorch with a torch one."""
         m = self.model
         if m.image_encoder is None:
             raise ValueError("ip_adapter_image needs model.image_encoder (or pass ip_adapter_image_embeds)")
