@@ -163,7 +163,8 @@ int sd_unet_text_kv_cache(sd_unet* u, int enable);
  * in one launch per site; n_img * num_tokens <= 64 and ehs_len <= 160, graph replay (sd_unet_use_graph) is
  * rejected (SD_ERR_UNSUPPORTED).  The image K / V follow sd_unet_text_kv_cache: kept across the forwards of one loop
  * for one (pointer, B, n_img), invalidated by every sd_unet_text_kv_cache call.  Without an adapter, image_embeds
- * must be NULL and the call is sd_unet_forward. */
+ * must be NULL and the call is sd_unet_forward.  With a Resampler adapter (sd_ip_adapter_create_ex) image_embeds means
+ * [B,n_img,T_feat,D_emb] f16, the image encoder's penultimate hidden states; everything else holds as stated. */
 int sd_unet_forward_ex(sd_unet* u, const void* sample, const float* timesteps, const void* ehs, int ehs_len,
                        const void* add_text, const float* add_time_ids, const void* image_embeds, int n_img, void* out,
                        int B, int H, int W, void* stream);
@@ -271,6 +272,44 @@ int sd_ip_adapter_weight_info(const sd_ip_adapter* a, int index, const char** ke
 int sd_ip_adapter_set_weight(sd_ip_adapter* a, const char* key, const void* data, const int64_t* shape, int ndim,
                              int dtype);
 int sd_ip_adapter_finalize(sd_ip_adapter* a);
+/* -- IP-Adapter Plus: the image projection is the perceiver Resampler of the IP-Adapter repository (diffusers'
+ *    IPAdapterPlusImageProjection), restated from memory -- no copy of either is pinned by a test here.  With
+ *    lat = latents per image and x = proj_in(features), each of `depth` layers computes
+ *      q = to_q(norm2(lat)), [k | v] = to_kv(cat([norm1(x), norm2(lat)])), lat += to_out(softmax(q k^T / 8) v),
+ *      lat += W2 gelu_erf(W1 LayerNorm(lat))
+ *    and tokens = norm_out(proj_out(lat)), [num_tokens, cross_attention_dim] per image.  Weight names are the original
+ *    file's `image_proj.*` suffixes, unchanged, under encoder_hid_proj.image_projection_layers.0. :
+ *      latents [1,num_tokens,dim]   proj_in / proj_out .{weight,bias}   norm_out.{weight,bias}
+ *      layers.{i}.0.{norm1,norm2}.{weight,bias}   layers.{i}.0.{to_q,to_kv,to_out}.weight   (heads * 64 query rows)
+ *      layers.{i}.1.0.{weight,bias}   layers.{i}.1.1.weight [ff_mult dim, dim]   layers.{i}.1.3.weight
+ *    followed by the to_{k,v}_ip keys of sd_ip_adapter_create.  The head dim is 64 (dim_head of every published
+ *    file).  sd_ip_adapter_create_ex with kind SD_IP_PROJ_LINEAR is sd_ip_adapter_create (the Resampler fields are
+ *    ignored).  SD_ERR_UNSUPPORTED: what sd_ip_adapter_create rejects; for the Resampler also dim not a positive
+ *    multiple of 64, heads < 1, heads * 64 != dim (another dim_head: published files have dim = heads * 64), depth
+ *    outside [1, 16], ff_mult outside [1, 8].  SD_ERR_INVALID: an unknown kind, null arguments.
+ *    With a Resampler adapter attached, image_embeds of sd_unet_forward_ex / _tc / _cn / _cfg means
+ *    [B, n_img, T_feat, image_embed_dim] f16: the image encoder's hidden_states[-2].  The Resampler runs where the
+ *    linear projection runs, once per loop under the image K / V cache rules of sd_unet_forward_ex. ------ */
+#define SD_IP_PROJ_LINEAR 0
+#define SD_IP_PROJ_RESAMPLER 1
+typedef struct sd_ip_projection_config {
+    int32_t kind;                /* SD_IP_PROJ_* */
+    int32_t image_embed_dim;     /* D_emb: 1280 (ViT-H/14 hidden size) for the published Plus files */
+    int32_t num_tokens;          /* tokens per image: the Resampler's queries (16) */
+    int32_t dim;                 /* Resampler width: 768 (SD1.5 Plus), 1280 (SDXL Plus) */
+    int32_t heads;               /* 12 / 20 */
+    int32_t depth;               /* 4 */
+    int32_t ff_mult;             /* 4 */
+} sd_ip_projection_config;
+int sd_ip_adapter_create_ex(const sd_unet* u, const sd_ip_projection_config* cfg, sd_ip_adapter** out);
+/* Feature tokens per image the Resampler reads (default 257 = 16 x 16 patches + class token; 1 + (image_size /
+ * patch_size)^2 of the tower in use).  Invalidates the image K / V cache of the UNet the adapter is attached to.
+ * SD_ERR_INVALID: T_feat < 1; SD_ERR_UNSUPPORTED: T_feat + num_tokens > 320, the keys the attention kernel holds in
+ * LDS, or a linear adapter. */
+int sd_ip_adapter_set_feature_tokens(sd_ip_adapter* a, int T_feat);
+/* The image projection alone, on the adapter's own workspace: image_embeds as the UNet forward takes them for `rows`
+ * (= B * n_img) images -> tokens [rows, num_tokens, cross_attention_dim] f16.  Both kinds; for tests and tools. */
+int sd_ip_adapter_project(sd_ip_adapter* a, const void* image_embeds, int rows, void* tokens, void* stream);
 
 /* -- ControlNet (diffusers 0.27.2 ControlNetModel), bound to a UNet.  cn_cfg describes its encoder (the up-path fields
  *    are ignored); weight names are diffusers' (stablediffusion_amd/controlnet.py converts original files):
@@ -724,6 +763,17 @@ int sd_op_ip_cross_attention(const void* q, const void* k, const void* v, const 
                              int B, int Tq, int L, int T_ip, int heads, int d, int ldq, int ldk, int ldv, int ldk_ip,
                              int ldv_ip, int ldo, float ip_scale, int prescaled, int iters, float* ms_per_launch,
                              void* stream);
+/* The Resampler's perceiver attention (IP-Adapter Plus), one launch, head dim 64:
+ *   out = softmax(s q [k_x ; k_l]^T) [v_x ; v_l],   s = 1/8, or 1 with prescaled = 1
+ * q / out [B,n_q,heads*64], k_x / v_x [B,T_feat,heads*64] (the projected image features), k_l / v_l [B,n_q,heads*64]
+ * (the projected latents), each with its own row stride (multiples of 8; operands 16-byte aligned).  One softmax over
+ * both key segments.  1 <= n_q <= 16, T_feat >= 1, T_feat + n_q <= 320 (SD_ERR_UNSUPPORTED otherwise).  iters > 0
+ * (timing; synchronises): ms_per_launch[0..1] = this kernel, and the composed form -- two strided copies that build a
+ * concatenated [B, T_feat + n_q, 2 heads 64] K|V buffer, then sd_op_attention_ex on it -- `iters` back-to-back
+ * repetitions each between HIP events. */
+int sd_op_resampler_attention(const void* q, const void* k_x, const void* v_x, const void* k_l, const void* v_l, void* out,
+                              int B, int n_q, int T_feat, int heads, int ldq, int ldk_x, int ldv_x, int ldk_l, int ldv_l,
+                              int ldo, int prescaled, int iters, float* ms_per_launch, void* stream);
 
 /* ControlNet zero-convs: for every problem, y[m, :C] = fp16(y[m, :C] + scale (x[m, :] w^T + bias)) in place; the
  * columns of y past C (row stride ldy) are left alone.  x [M, C] f16 (ldx % 8 == 0), w [C, C] f16 (row = output

@@ -82,6 +82,22 @@ class SdClipVisionConfig(C.Structure):
     ]
 
 
+class SdIPProjectionConfig(C.Structure):
+    _fields_ = [
+        ("kind", C.c_int32),
+        ("image_embed_dim", C.c_int32),
+        ("num_tokens", C.c_int32),
+        ("dim", C.c_int32),
+        ("heads", C.c_int32),
+        ("depth", C.c_int32),
+        ("ff_mult", C.c_int32),
+    ]
+
+
+SD_IP_PROJ_LINEAR = 0
+SD_IP_PROJ_RESAMPLER = 1
+
+
 class SdProfEntry(C.Structure):
     _fields_ = [("kernel", C.c_char * 64), ("flops", C.c_double), ("bytes", C.c_double),
                 ("ms", C.c_double), ("launches", C.c_int64)]
@@ -140,6 +156,9 @@ SIGNATURES = {
     "sd_unet_set_deep_cache": (_I, [_P, _I]),
     "sd_unet_deep_cache_mode": (_I, [_P, _I]),
     "sd_ip_adapter_create": (_I, [_P, _I, _I, C.POINTER(_P)]),
+    "sd_ip_adapter_create_ex": (_I, [_P, C.POINTER(SdIPProjectionConfig), C.POINTER(_P)]),
+    "sd_ip_adapter_set_feature_tokens": (_I, [_P, _I]),
+    "sd_ip_adapter_project": (_I, [_P, _P, _I, _P, _P]),
     "sd_ip_adapter_destroy": (_I, [_P]),
     "sd_ip_adapter_num_weights": (_I, [_P]),
     "sd_ip_adapter_weight_info": (_I, [_P, _I, C.POINTER(C.c_char_p), C.POINTER(_I64), C.POINTER(_I)]),
@@ -233,6 +252,8 @@ SIGNATURES = {
     "sd_attention_plan": (_I, [_I, _I, _I, _I, _I, _I, _I, C.POINTER(_I)]),
     "sd_op_ip_cross_attention": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _I, _I,
                                       C.POINTER(_F), _P]),
+    "sd_op_resampler_attention": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I,
+                                       C.POINTER(_F), _P]),
     "sd_op_controlnet_residuals": (_I, [C.POINTER(SdCnProblem), _I, _F, _I, _I, C.POINTER(_F), _P]),
     "sd_op_controlnet_cond_embed": (_I, [_P, _P, _I, _I, _I, _P, _I, C.POINTER(_F), _P]),
 }

@@ -19,7 +19,7 @@ struct sd_controlnet {
 };
 struct sd_ip_adapter {
     IPAdapter impl;
-    sd_ip_adapter(const sd_unet_config& c, int d, int n) : impl(c, d, n) {}
+    sd_ip_adapter(const sd_unet_config& c, const sd_ip_projection_config& p) : impl(c, p) {}
     ~sd_ip_adapter() { if (impl.attached) impl.attached->set_ip_adapter(nullptr); }
 };
 
@@ -270,9 +270,14 @@ int sd_unet_deep_cache_mode(sd_unet* u, int mode) {
 }
 
 // ------------------------------------------------------------------------------------- IP-Adapter
-int sd_ip_adapter_create(const sd_unet* u, int image_embed_dim, int num_tokens, sd_ip_adapter** out) {
-    if (!u || !out) { set_error("null argument"); return SD_ERR_INVALID; }
+int sd_ip_adapter_create_ex(const sd_unet* u, const sd_ip_projection_config* p, sd_ip_adapter** out) {
+    if (!u || !p || !out) { set_error("null argument"); return SD_ERR_INVALID; }
+    if (p->kind != SD_IP_PROJ_LINEAR && p->kind != SD_IP_PROJ_RESAMPLER) {
+        set_error("sd_ip_adapter_create: unknown projection kind " + std::to_string(p->kind));
+        return SD_ERR_INVALID;
+    }
     const sd_unet_config& c = u->impl.cfg;
+    const int image_embed_dim = p->image_embed_dim, num_tokens = p->num_tokens;
     if (c.cross_attention_dim % 64 != 0) { set_error("sd_ip_adapter_create: cross_attention_dim % 64 != 0"); return SD_ERR_UNSUPPORTED; }
     if (num_tokens < 1 || num_tokens > 16) { set_error("sd_ip_adapter_create: num_tokens must be in [1, 16]"); return SD_ERR_UNSUPPORTED; }
     if (image_embed_dim <= 0 || image_embed_dim % 64 != 0) {
@@ -288,9 +293,52 @@ int sd_ip_adapter_create(const sd_unet* u, int image_embed_dim, int num_tokens, 
             return SD_ERR_UNSUPPORTED;
         }
     }
-    *out = new (std::nothrow) sd_ip_adapter(c, image_embed_dim, num_tokens);
+    sd_ip_projection_config q = *p;
+    if (q.kind == SD_IP_PROJ_RESAMPLER) {
+        if (q.dim <= 0 || q.dim % 64 != 0) { set_error("sd_ip_adapter_create: Resampler dim must be a positive multiple of 64"); return SD_ERR_UNSUPPORTED; }
+        if (q.heads < 1 || (long)q.heads * 64 != q.dim) {
+            set_error("sd_ip_adapter_create: Resampler dim_head (dim / heads) must be 64");
+            return SD_ERR_UNSUPPORTED;
+        }
+        if (q.depth < 1 || q.depth > 16) { set_error("sd_ip_adapter_create: Resampler depth must be in [1, 16]"); return SD_ERR_UNSUPPORTED; }
+        if (q.ff_mult < 1 || q.ff_mult > 8) { set_error("sd_ip_adapter_create: Resampler ff_mult must be in [1, 8]"); return SD_ERR_UNSUPPORTED; }
+    } else {
+        q.dim = q.heads = q.depth = q.ff_mult = 0;
+    }
+    *out = new (std::nothrow) sd_ip_adapter(c, q);
     if (!*out) { set_error("out of host memory"); return SD_ERR_INVALID; }
     return SD_OK;
+}
+int sd_ip_adapter_create(const sd_unet* u, int image_embed_dim, int num_tokens, sd_ip_adapter** out) {
+    sd_ip_projection_config p = {};
+    p.kind = SD_IP_PROJ_LINEAR;
+    p.image_embed_dim = image_embed_dim;
+    p.num_tokens = num_tokens;
+    return sd_ip_adapter_create_ex(u, &p, out);
+}
+int sd_ip_adapter_set_feature_tokens(sd_ip_adapter* a, int T_feat) {
+    if (!a) { set_error("null handle"); return SD_ERR_INVALID; }
+    if (T_feat < 1) { set_error("sd_ip_adapter_set_feature_tokens: T_feat must be >= 1"); return SD_ERR_INVALID; }
+    if (a->impl.kind != SD_IP_PROJ_RESAMPLER) {
+        set_error("sd_ip_adapter_set_feature_tokens: a linear adapter reads one embedding per image");
+        return SD_ERR_UNSUPPORTED;
+    }
+    if (T_feat + a->impl.n_tok > resampler_max_keys()) {
+        set_error("sd_ip_adapter_set_feature_tokens: T_feat + num_tokens must be <= " + std::to_string(resampler_max_keys()));
+        return SD_ERR_UNSUPPORTED;
+    }
+    a->impl.t_feat = T_feat;
+    if (UNet* un = a->impl.attached) {      // the cached image K / V and the arena plan were made for the old count
+        un->ipkv_valid = false;
+        un->dc_valid = false;
+        un->reset_plans();
+    }
+    return SD_OK;
+}
+int sd_ip_adapter_project(sd_ip_adapter* a, const void* image_embeds, int rows, void* tokens, void* stream) {
+    if (!a || !image_embeds || !tokens) { set_error("null argument"); return SD_ERR_INVALID; }
+    return a->impl.project(static_cast<const half_t*>(image_embeds), rows, static_cast<half_t*>(tokens),
+                           static_cast<hipStream_t>(stream));
 }
 int sd_ip_adapter_destroy(sd_ip_adapter* a) { delete a; return SD_OK; }
 int sd_ip_adapter_num_weights(const sd_ip_adapter* a) { return a ? (int)a->impl.ws.order.size() : 0; }
@@ -1553,6 +1601,54 @@ int sd_op_ip_cross_attention(const void* q, const void* k, const void* v, const 
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
     (void)hipFree(tmp);
+    return rc;
+}
+
+int sd_op_resampler_attention(const void* q, const void* k_x, const void* v_x, const void* k_l, const void* v_l, void* out,
+                              int B, int n_q, int T_feat, int heads, int ldq, int ldk_x, int ldv_x, int ldk_l, int ldv_l,
+                              int ldo, int prescaled, int iters, float* ms_per_launch, void* stream) {
+    if (!q || !k_x || !v_x || !k_l || !v_l || !out) { set_error("sd_op_resampler_attention: null argument"); return SD_ERR_INVALID; }
+    const half_t *qh = static_cast<const half_t*>(q), *kxh = static_cast<const half_t*>(k_x), *vxh = static_cast<const half_t*>(v_x);
+    const half_t *klh = static_cast<const half_t*>(k_l), *vlh = static_cast<const half_t*>(v_l);
+    half_t* oh = static_cast<half_t*>(out);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    auto fused = [&]() {
+        return launch_resampler_attention(qh, kxh, vxh, klh, vlh, oh, B, n_q, T_feat, heads, ldq, ldk_x, ldv_x, ldk_l, ldv_l,
+                                          ldo, prescaled, s);
+    };
+    int rc = fused();
+    if (rc || iters <= 0) return rc;
+    if (!ms_per_launch) { set_error("sd_op_resampler_attention: ms_per_launch required with iters > 0"); return SD_ERR_INVALID; }
+    // [0] this kernel, [1] the composed form: K and V concatenated into one [B, Tk, 2 A] buffer, then attn_kernel<64>
+    const int A = heads * 64, Tk = T_feat + n_q;
+    half_t* cat = nullptr;
+    SD_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&cat), (size_t)B * Tk * 2 * A * sizeof(half_t)));
+    auto composed = [&]() {
+        int r = launch_concat_rows_f16(kxh, ldk_x, T_feat, klh, ldk_l, n_q, cat, 2L * A, B, A, s);
+        if (!r) r = launch_concat_rows_f16(vxh, ldv_x, T_feat, vlh, ldv_l, n_q, cat + A, 2L * A, B, A, s);
+        if (!r) r = launch_attention(qh, cat, cat + A, oh, B, n_q, Tk, heads, 64, ldq, 2L * A, 2L * A, ldo, s, 0, prescaled);
+        return r;
+    };
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) rc = SD_ERR_HIP;
+    for (int variant = 0; variant < 2 && !rc; ++variant) {
+        auto one = [&]() { return variant == 0 ? fused() : composed(); };
+        for (int it = 0; it < 2 && !rc; ++it) rc = one();
+        if (rc) break;
+        (void)hipEventRecord(e0, s);
+        for (int it = 0; it < iters && !rc; ++it) rc = one();
+        (void)hipEventRecord(e1, s);
+        float ms = 0.f;
+        hipError_t e = hipEventSynchronize(e1);
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
+        if (e != hipSuccess) { set_error(hipGetErrorString(e)); rc = SD_ERR_HIP; }
+        ms_per_launch[variant] = ms / (float)iters;
+    }
+    if (!rc) rc = fused();                  // leave this kernel's result in out
+    if (!rc && hipStreamSynchronize(s) != hipSuccess) rc = SD_ERR_HIP;
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    (void)hipFree(cat);
     return rc;
 }
 

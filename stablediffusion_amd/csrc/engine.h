@@ -186,5 +186,8 @@ void op_attention(Ctx& c, View q, View k, View v, View out, int B, int Tq, int T
 // out = softmax(q k^T) v + ip_scale softmax(q k_ip^T) v_ip (prescaled queries, ip_attention.hip)
 void op_ip_attention(Ctx& c, View q, View k, View v, View k_ip, View v_ip, View out, int B, int Tq, int L, int T_ip,
                      int heads, int d, float ip_scale);
+// out = softmax(q [kx ; kl]^T) [vx ; vl], head dim 64, prescaled queries (resampler.hip)
+void op_resampler_attention(Ctx& c, View q, View kx, View vx, View kl, View vl, View out, int B, int n_q, int T_feat,
+                            int heads);
 
 }  // namespace sd

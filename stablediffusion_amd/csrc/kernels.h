@@ -237,6 +237,20 @@ int launch_ip_attention(const half_t* q, const half_t* k, const half_t* v, const
                         long ldki, long ldvi, long ldo, float ip_scale, int prescaled, hipStream_t s);
 bool ip_attention_supported(int d);
 int launch_axpy_f16(half_t* y, long ldy, const half_t* x, long ldx, long rows, int cols, float a, hipStream_t s);
+// Perceiver attention of the IP-Adapter Plus Resampler (resampler.hip), one launch, head dim 64:
+//   out = softmax(s q [kx ; kl]^T) [vx ; vl],   s = 1/8 (or 1 with prescaled)
+// q / out [B, n_q, heads*64], kx / vx [B, T_feat, ..], kl / vl [B, n_q, ..], every view with its own row stride (% 8,
+// 16-byte aligned); 1 <= n_q <= 16, 1 <= T_feat, T_feat + n_q <= resampler_max_keys() = 320.  Returns 4 for
+// unsupported shapes.
+int launch_resampler_attention(const half_t* q, const half_t* kx, const half_t* vx, const half_t* kl, const half_t* vl,
+                               half_t* out, int B, int n_q, int T_feat, int heads, long ldq, long ldkx, long ldvx, long ldkl,
+                               long ldvl, long ldo, int prescaled, hipStream_t s);
+int resampler_max_keys();
+// dst[r] = src[r % src_rows] for r < rows, rows of `cols` halves (cols % 8 == 0, dense): the Resampler's latents per image
+int launch_tile_rows_f16(const half_t* src, long src_rows, half_t* dst, long rows, int cols, hipStream_t s);
+// dst[b][r] = r < Tx ? x[b][r] : l[b][r - Tx] over `cols` halves (cols and strides % 8 == 0): timing baseline only
+int launch_concat_rows_f16(const half_t* x, long ldx, int Tx, const half_t* l, long ldl, int Tl, half_t* dst, long ldd, long B,
+                           int cols, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------
 // ControlNet (controlnet.hip)

@@ -86,19 +86,42 @@ std::vector<std::pair<std::string, int>> unet_xattn_sites(const sd_unet_config& 
 // IP-Adapter image prompt bound to a UNet topology (diffusers 0.27.2 ImageProjection + IPAdapterAttnProcessor2_0):
 // tokens = LayerNorm(reshape(image_embeds x W_proj^T + b, [n_tok, ctx])), then at every attn2
 // o = SDPA(q, K_text, V_text) + scale * SDPA(q, tokens W_k_ip^T, tokens W_v_ip^T).
+//
+// IP-Adapter Plus (kind SD_IP_PROJ_RESAMPLER) replaces the projection by the perceiver Resampler of the IP-Adapter
+// repository: n_tok learned latents attend, over `depth` layers, to the tower's penultimate hidden states
+// [T_feat, d_img] per image and to themselves (one softmax over both), each layer followed by an erf-GELU
+// feed-forward; tokens = LayerNorm(proj_out(latents)).  Everything after the tokens is the same.
+struct ResamplerLayer {
+    NormW norm1, norm2, ff_ln;          // of the features, of the latents, in front of the feed-forward
+    ConvW to_q, to_kv, to_out, ff1, ff2;    // no biases; to_q carries log2(e) / 8
+};
 struct IPAdapter {
-    IPAdapter(const sd_unet_config& c, int image_embed_dim, int num_tokens);
+    IPAdapter(const sd_unet_config& c, const sd_ip_projection_config& p);
     int finalize();
+    // image_embeds -> tok [rows n_tok, ctx] (rows = B n_img): image_embeds is [rows, d_img] for the linear kind,
+    // [rows, t_feat, d_img] for the Resampler.  Temporaries come from c.arena; the caller marks and releases.
+    void run_tokens(Ctx& c, const half_t* image_embeds, long rows, half_t* tok);
+    // run_tokens on the adapter's own arena (sd_ip_adapter_project: tests and tools)
+    int project(const half_t* image_embeds, long rows, half_t* tok, hipStream_t stream);
 
     sd_unet_config cfg;
+    int kind = SD_IP_PROJ_LINEAR;
     int d_img = 0, n_tok = 0;
     WeightStore ws;
     bool finalized = false;
     ConvW proj;                         // image_embeds linear [n_tok ctx][d_img]
-    NormW norm;                         // LayerNorm over ctx, eps 1e-5
+    NormW norm;                         // LayerNorm over ctx, eps 1e-5 (the Resampler's norm_out)
     ConvW kv_all;                       // every to_k_ip / to_v_ip, row-concatenated in UNet::kv_all's site order
     int kv_total = 0;
     UNet* attached = nullptr;           // the UNet it is attached to (sd_unet_set_ip_adapter), if any
+    // Resampler
+    int dim = 0, heads = 0, depth = 0, ff_mult = 0;
+    int t_feat = 257;                   // feature tokens per image (sd_ip_adapter_set_feature_tokens)
+    half_t* latents = nullptr;          // [n_tok][dim]
+    ConvW proj_in, proj_out;
+    std::vector<ResamplerLayer> layers;
+    Arena arena;                        // project()'s workspace
+    long planned_rows = -1;
 };
 
 // conv_in, time / add embedding, down path and mid block of a UNet2DConditionModel topology: the part a UNet and a

@@ -565,4 +565,14 @@ void op_ip_attention(Ctx& c, View q, View k, View v, View k_ip, View v_ip, View 
     prof_close(c.stream);
 }
 
+void op_resampler_attention(Ctx& c, View q, View kx, View vx, View kl, View vl, View out, int B, int n_q, int T_feat,
+                            int heads) {
+    if (c.dry || c.err) return;
+    prof_open(c.stream, "resampler_attn_kernel", 4.0 * B * heads * (double)n_q * (T_feat + n_q) * 64,
+              2.0 * B * heads * 64 * (2.0 * n_q + 2.0 * (T_feat + n_q)));
+    c.err = launch_resampler_attention(q.p, kx.p, vx.p, kl.p, vl.p, out.p, B, n_q, T_feat, heads, q.ld, kx.ld, vx.ld, kl.ld,
+                                       vl.ld, out.ld, 1, c.stream);
+    prof_close(c.stream);
+}
+
 }  // namespace sd

@@ -324,16 +324,43 @@ std::vector<std::pair<std::string, int>> unet_xattn_sites(const sd_unet_config& 
 
 namespace {
 const char* kIpProj = "encoder_hid_proj.image_projection_layers.0";
+std::string rs_layer_key(int i, const char* rest) { return std::string(kIpProj) + ".layers." + std::to_string(i) + "." + rest; }
 }
 
-IPAdapter::IPAdapter(const sd_unet_config& c, int image_embed_dim, int num_tokens)
-    : cfg(c), d_img(image_embed_dim), n_tok(num_tokens) {
+IPAdapter::IPAdapter(const sd_unet_config& c, const sd_ip_projection_config& p)
+    : cfg(c), kind(p.kind), d_img(p.image_embed_dim), n_tok(p.num_tokens) {
     const int ctx = cfg.cross_attention_dim;
-    const std::string p = kIpProj;
-    ws.declare(p + ".image_embeds.weight", {(int64_t)n_tok * ctx, d_img});
-    ws.declare(p + ".image_embeds.bias", {(int64_t)n_tok * ctx});
-    ws.declare(p + ".norm.weight", {ctx});
-    ws.declare(p + ".norm.bias", {ctx});
+    const std::string pre = kIpProj;
+    if (kind == SD_IP_PROJ_RESAMPLER) {
+        dim = p.dim; heads = p.heads; depth = p.depth; ff_mult = p.ff_mult;
+        const int64_t A = (int64_t)heads * 64, F = (int64_t)ff_mult * dim;
+        // the original file's names under the diffusers prefix (stablediffusion_amd/ip_adapter.py)
+        ws.declare(pre + ".latents", {1, n_tok, dim});
+        ws.declare(pre + ".proj_in.weight", {dim, d_img});
+        ws.declare(pre + ".proj_in.bias", {dim});
+        ws.declare(pre + ".proj_out.weight", {ctx, dim});
+        ws.declare(pre + ".proj_out.bias", {ctx});
+        ws.declare(pre + ".norm_out.weight", {ctx});
+        ws.declare(pre + ".norm_out.bias", {ctx});
+        for (int i = 0; i < depth; ++i) {
+            for (const char* n : {"0.norm1", "0.norm2"}) {
+                ws.declare(rs_layer_key(i, n) + ".weight", {dim});
+                ws.declare(rs_layer_key(i, n) + ".bias", {dim});
+            }
+            ws.declare(rs_layer_key(i, "0.to_q.weight"), {A, dim});
+            ws.declare(rs_layer_key(i, "0.to_kv.weight"), {2 * A, dim});
+            ws.declare(rs_layer_key(i, "0.to_out.weight"), {dim, A});
+            ws.declare(rs_layer_key(i, "1.0.weight"), {dim});
+            ws.declare(rs_layer_key(i, "1.0.bias"), {dim});
+            ws.declare(rs_layer_key(i, "1.1.weight"), {F, dim});
+            ws.declare(rs_layer_key(i, "1.3.weight"), {dim, F});
+        }
+    } else {
+        ws.declare(pre + ".image_embeds.weight", {(int64_t)n_tok * ctx, d_img});
+        ws.declare(pre + ".image_embeds.bias", {(int64_t)n_tok * ctx});
+        ws.declare(pre + ".norm.weight", {ctx});
+        ws.declare(pre + ".norm.bias", {ctx});
+    }
     for (const auto& site : unet_xattn_sites(cfg, true)) {
         ws.declare(site.first + ".attn2.processor.to_k_ip.0.weight", {site.second, ctx});
         ws.declare(site.first + ".attn2.processor.to_v_ip.0.weight", {site.second, ctx});
@@ -346,8 +373,34 @@ int IPAdapter::finalize() {
     if (!ws.complete(&missing)) { set_error("ip adapter finalize: weight not set: " + missing); return 2; }
     const std::string p = kIpProj;
     int rc;
-    if ((rc = ws.pack_conv(p + ".image_embeds", &proj))) return rc;
-    if ((rc = ws.pack_norm(p + ".norm", &norm))) return rc;
+    if (kind == SD_IP_PROJ_RESAMPLER) {
+        const RawTensor* lt = ws.raw(p + ".latents");
+        if (!lt) { set_error("missing weight: " + p + ".latents"); return 2; }
+        latents = static_cast<half_t*>(ws.dmalloc((size_t)lt->numel * sizeof(half_t)));
+        if (!latents) { set_error("hipMalloc failed"); return 3; }
+        SD_HIP_CHECK(hipMemcpy(latents, lt->dev, (size_t)lt->numel * sizeof(half_t), hipMemcpyDeviceToDevice));
+        if ((rc = ws.pack_conv(p + ".proj_in", &proj_in))) return rc;
+        if ((rc = ws.pack_conv(p + ".proj_out", &proj_out))) return rc;
+        if ((rc = ws.pack_norm(p + ".norm_out", &norm))) return rc;
+        layers.assign((size_t)depth, ResamplerLayer());
+        // softmax's log2(e) / sqrt(64) goes into the query rows, as in the UNet's projections (pack_xformer)
+        const float qs = 1.4426950408889634f / 8.0f;
+        for (int i = 0; i < depth; ++i) {
+            ResamplerLayer& l = layers[(size_t)i];
+            if ((rc = ws.pack_norm(rs_layer_key(i, "0.norm1"), &l.norm1))) return rc;
+            if ((rc = ws.pack_norm(rs_layer_key(i, "0.norm2"), &l.norm2))) return rc;
+            if ((rc = ws.pack_conv(rs_layer_key(i, "0.to_q"), &l.to_q, false))) return rc;
+            if ((rc = launch_scale_f16(l.to_q.w, (long)l.to_q.cout * l.to_q.K, qs, 0))) return rc;
+            if ((rc = ws.pack_conv(rs_layer_key(i, "0.to_kv"), &l.to_kv, false))) return rc;
+            if ((rc = ws.pack_conv(rs_layer_key(i, "0.to_out"), &l.to_out, false))) return rc;
+            if ((rc = ws.pack_norm(rs_layer_key(i, "1.0"), &l.ff_ln))) return rc;
+            if ((rc = ws.pack_conv(rs_layer_key(i, "1.1"), &l.ff1, false))) return rc;
+            if ((rc = ws.pack_conv(rs_layer_key(i, "1.3"), &l.ff2, false))) return rc;
+        }
+    } else {
+        if ((rc = ws.pack_conv(p + ".image_embeds", &proj))) return rc;
+        if ((rc = ws.pack_norm(p + ".norm", &norm))) return rc;
+    }
     // stacked in the UNet's kv_all order, so that a block's ip_kv_off equals its kv_off
     std::vector<std::string> keys;
     kv_total = 0;
@@ -361,6 +414,80 @@ int IPAdapter::finalize() {
     ws.free_raw();
     finalized = true;
     return 0;
+}
+
+void IPAdapter::run_tokens(Ctx& c, const half_t* image_embeds, long rows, half_t* tok) {
+    Arena& a = *c.arena;
+    hipStream_t s = c.stream;
+    const bool go = !c.dry;
+    const int ctx = cfg.cross_attention_dim;
+    if (kind != SD_IP_PROJ_RESAMPLER) {
+        const long ntc = (long)n_tok * ctx;
+        float* e32 = a.alloc_f(rows * d_img);
+        float* p32 = a.alloc_f(rows * ntc);
+        half_t* p16 = a.alloc_h(rows * ntc);
+        if (go && !c.err) c.err = launch_f16_to_f32(image_embeds, e32, rows * d_img, s);
+        if (go && !c.err) {
+            prof_open(s, "small_linear_kernel", 2.0 * rows * ntc * d_img, 2.0 * ntc * d_img);
+            c.err = launch_small_linear(e32, d_img, proj.w, proj.bias, p32, ntc, (int)rows, d_img, (int)ntc, 0, 0, s);
+            prof_close(s);
+        }
+        if (go && !c.err) c.err = launch_f32_to_f16(p32, p16, rows * ntc, s);
+        op_layernorm(c, norm, View(p16, ctx, ctx), View(tok, ctx, ctx), rows * n_tok, 1e-5f);
+        return;
+    }
+    // ---- Resampler: R = rows images, T features and n_tok latents each.  Per layer 10 launches: 3 LayerNorms, to_q and
+    //      to_kv of the latents, to_kv of the features (to_kv is row-wise: no concatenation), the attention, to_out
+    //      (+ latents), W1 (+ GELU), W2 (+ residual). ----
+    const int R = (int)rows, T = t_feat, A = heads * 64, F = ff_mult * dim;
+    const long Mx = rows * T, Ml = rows * n_tok;
+    View x(a.alloc_h(Mx * dim), dim, dim), xn(a.alloc_h(Mx * dim), dim, dim), kvx(a.alloc_h(Mx * 2 * A), 2 * A, 2 * A);
+    View lat(a.alloc_h(Ml * dim), dim, dim), lat2(a.alloc_h(Ml * dim), dim, dim), ln(a.alloc_h(Ml * dim), dim, dim);
+    View q(a.alloc_h(Ml * A), A, A), kvl(a.alloc_h(Ml * 2 * A), 2 * A, 2 * A), att(a.alloc_h(Ml * A), A, A);
+    View f(a.alloc_h(Ml * F), F, F), po(a.alloc_h(Ml * ctx), ctx, ctx);
+    op_conv(c, proj_in, View(const_cast<half_t*>(image_embeds), d_img, d_img), R, T, 1, x);
+    if (go && !c.err) {
+        prof_open(s, "tile_rows_f16_kernel", 0.0, 4.0 * Ml * dim);
+        c.err = launch_tile_rows_f16(latents, n_tok, lat.p, Ml, dim, s);
+        prof_close(s);
+    }
+    for (const ResamplerLayer& l : layers) {
+        op_layernorm(c, l.norm1, x, xn, Mx, 1e-5f);
+        op_layernorm(c, l.norm2, lat, ln, Ml, 1e-5f);
+        op_conv(c, l.to_q, ln, R, n_tok, 1, q);
+        op_conv(c, l.to_kv, xn, R, T, 1, kvx);
+        op_conv(c, l.to_kv, ln, R, n_tok, 1, kvl);
+        op_resampler_attention(c, q, kvx.slice(0, A), kvx.slice(A, A), kvl.slice(0, A), kvl.slice(A, A), att, R, n_tok, T,
+                               heads);
+        op_conv(c, l.to_out, att, R, n_tok, 1, lat2, 1, 0, nullptr, 0, &lat);
+        op_layernorm(c, l.ff_ln, lat2, ln, Ml, 1e-5f);
+        op_conv(c, l.ff1, ln, R, n_tok, 1, f, 1, 0, nullptr, 0, nullptr, 0, -1, 2);
+        op_conv(c, l.ff2, f, R, n_tok, 1, lat, 1, 0, nullptr, 0, &lat2);
+    }
+    op_conv(c, proj_out, lat, R, n_tok, 1, po);
+    op_layernorm(c, norm, po, View(tok, ctx, ctx), Ml, 1e-5f);
+}
+
+int IPAdapter::project(const half_t* image_embeds, long rows, half_t* tok, hipStream_t stream) {
+    if (!finalized) { set_error("ip adapter: project before finalize"); return 2; }
+    if (rows < 1 || rows > 4096) { set_error("ip adapter: project takes 1..4096 images"); return 1; }
+    const long key = rows * 1024 + t_feat;
+    if (key != planned_rows) {
+        Ctx dry{&arena, stream, true};
+        arena.begin(true);
+        run_tokens(dry, image_embeds, rows, tok);
+        if (dry.err) return dry.err;
+        if (arena.peak() > arena.capacity()) {
+            SD_HIP_CHECK(hipDeviceSynchronize());
+            if (int rc = arena.reserve(arena.peak())) return rc;
+        }
+        planned_rows = key;
+    }
+    Ctx ctx{&arena, stream, false};
+    arena.begin(false);
+    run_tokens(ctx, image_embeds, rows, tok);
+    if (!ctx.err && arena.overflow()) { set_error("ip adapter: workspace overflow (planner bug)"); return 2; }
+    return ctx.err;
 }
 
 void UNet::set_ip_adapter(IPAdapter* a) {
@@ -771,8 +898,9 @@ int UNet::run(Ctx& c, const half_t* sample, const float* timesteps, const half_t
         if (kv_cached && go && !c.err) { kv_valid = true; kv_src = ehs; kv_B = B; kv_L = L; }
     }
 
-    // ---- IP-Adapter: image tokens = LayerNorm(image_embeds W_proj^T + b) [B n_img n_tok, ctx], then their K / V for
-    //      every cross-attention block in one GEMM: [B T_ip, ctx] x [ctx, sum 2C] ----
+    // ---- IP-Adapter: image tokens = LayerNorm(image_embeds W_proj^T + b), or the Resampler's (IPAdapter::run_tokens),
+    //      [B n_img n_tok, ctx], then their K / V for every cross-attention block in one GEMM:
+    //      [B T_ip, ctx] x [ctx, sum 2C] ----
     if (ip && image_embeds) {
         const int ctx = cfg.cross_attention_dim, T_ip = n_img * ip->n_tok;
         const long rows = (long)B * n_img, ntc = (long)ip->n_tok * ctx;
@@ -783,19 +911,8 @@ int UNet::run(Ctx& c, const half_t* sample, const float* timesteps, const half_t
         const bool hit = ip_cached && ipkv_valid && ipkv_src == image_embeds && ipkv_B == B && ipkv_n == n_img;
         if (c.dry || !hit) {
             const size_t mk = a.mark();
-            float* e32 = a.alloc_f(rows * ip->d_img);
-            float* p32 = a.alloc_f(rows * ntc);
-            half_t* p16 = a.alloc_h(rows * ntc);
             half_t* tok = a.alloc_h(rows * ntc);
-            if (go && !c.err) c.err = launch_f16_to_f32(image_embeds, e32, rows * ip->d_img, s);
-            if (go && !c.err) {
-                prof_open(s, "small_linear_kernel", 2.0 * rows * ntc * ip->d_img, 2.0 * ntc * ip->d_img);
-                c.err = launch_small_linear(e32, ip->d_img, ip->proj.w, ip->proj.bias, p32, ntc, (int)rows, ip->d_img,
-                                            (int)ntc, 0, 0, s);
-                prof_close(s);
-            }
-            if (go && !c.err) c.err = launch_f32_to_f16(p32, p16, rows * ntc, s);
-            op_layernorm(c, ip->norm, View(p16, ctx, ctx), View(tok, ctx, ctx), rows * ip->n_tok, 1e-5f);
+            ip->run_tokens(c, image_embeds, rows, tok);
             op_conv(c, ip->kv_all, View(tok, ctx, ctx), B, T_ip, 1, ip_kv);
             a.release(mk);
             if (ip_cached && go && !c.err) { ipkv_valid = true; ipkv_src = image_embeds; ipkv_B = B; ipkv_n = n_img; }

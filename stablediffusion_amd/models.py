@@ -190,8 +190,11 @@ class HipUNet2DConditionModel:
         return self
 
     def make_ip_adapter(self, state_dict: Dict[str, torch.Tensor], image_embed_dim: int, num_tokens: int):
-        """A HipIPAdapter for this engine's configuration, loaded from diffusers-named weights."""
-        return HipIPAdapter(self, image_embed_dim, num_tokens).load_state_dict(state_dict)
+        """A HipIPAdapter for this engine's configuration, loaded from diffusers-named weights.  The projection kind
+        comes from the state dict: with an IP-Adapter Plus Resampler under it, its sizes are read from the shapes."""
+        from . import ip_adapter
+        rc = ip_adapter.resampler_config(state_dict, self.cfg) if ip_adapter.is_resampler(state_dict) else None
+        return HipIPAdapter(self, image_embed_dim, num_tokens, resampler=rc).load_state_dict(state_dict)
 
     @property
     def ip_adapter(self):
@@ -310,6 +313,12 @@ class HipUNet2DConditionModel:
             if len(embeds) != 1:
                 raise ValueError(f"one IP-Adapter is attached, got image_embeds for {len(embeds)}")
             embeds = embeds[0]
+        if self._ip.kind == "resampler":
+            want = (B, self._ip.feature_tokens, self._ip.image_embed_dim)
+            if embeds.ndim != 4 or (embeds.shape[0], embeds.shape[2], embeds.shape[3]) != want:
+                raise ValueError(f"image_embeds: an IP-Adapter Plus (Resampler) adapter is attached: expected the image "
+                                 f"encoder's hidden_states[-2] as [{B}, n_img, {want[1]}, {want[2]}], got {tuple(embeds.shape)}")
+            return _as_f16(embeds, dev)
         if embeds.ndim == 2:               # deprecated diffusers form [B, D_img]: one image per prompt
             embeds = embeds[:, None]
         if embeds.ndim != 3 or embeds.shape[0] != B or embeds.shape[2] != self._ip.image_embed_dim:
@@ -478,19 +487,49 @@ class HipUNet2DConditionModel:
 
 class HipIPAdapter:
     """IP-Adapter image projection + per-site to_k_ip / to_v_ip on the engine, bound to a UNet configuration
-    (sd_ip_adapter_*).  Weights in diffusers' post-load naming (stablediffusion_amd.ip_adapter.convert)."""
+    (sd_ip_adapter_*).  Weights in diffusers' post-load naming (stablediffusion_amd.ip_adapter.convert).
+    resampler: an ip_adapter.resampler_config() for an IP-Adapter Plus projection (kind "resampler": image_embeds are
+    then [B, n_img, feature_tokens, image_embed_dim]); None for the base adapters' linear + LayerNorm (kind "linear")."""
 
-    def __init__(self, unet: HipUNet2DConditionModel, image_embed_dim: int, num_tokens: int = 4):
+    def __init__(self, unet: HipUNet2DConditionModel, image_embed_dim: int, num_tokens: int = 4, resampler=None):
         self._lib = _lib.load()
         self.cfg = unet.cfg
         self.device = unet.device
         self.image_embed_dim = int(image_embed_dim)
         self.num_tokens = int(num_tokens)
+        self.kind = "linear" if resampler is None else "resampler"
+        self.resampler = dict(resampler) if resampler is not None else None
+        self._feature_tokens = 257 if resampler is not None else 1
         self._unet = None
         self._h = C.c_void_p()
-        _lib.check(self._lib.sd_ip_adapter_create(unet._h, self.image_embed_dim, self.num_tokens, C.byref(self._h)),
-                   "sd_ip_adapter_create")
+        pc = _lib.SdIPProjectionConfig(kind=_lib.SD_IP_PROJ_LINEAR, image_embed_dim=self.image_embed_dim,
+                                       num_tokens=self.num_tokens)
+        if resampler is not None:
+            pc.kind = _lib.SD_IP_PROJ_RESAMPLER
+            pc.dim, pc.heads, pc.depth, pc.ff_mult = (int(resampler[k]) for k in ("dim", "heads", "depth", "ff_mult"))
+        _lib.check(self._lib.sd_ip_adapter_create_ex(unet._h, C.byref(pc), C.byref(self._h)), "sd_ip_adapter_create_ex")
         self._finalized = False
+
+    @property
+    def feature_tokens(self) -> int:
+        """Rows of one image's features the Resampler reads (hidden_states[-2] of the tower: patches + class token)."""
+        return self._feature_tokens
+
+    @feature_tokens.setter
+    def feature_tokens(self, n: int):
+        _lib.check(self._lib.sd_ip_adapter_set_feature_tokens(self._h, int(n)), "sd_ip_adapter_set_feature_tokens")
+        self._feature_tokens = int(n)
+
+    def project(self, image_embeds: torch.Tensor) -> torch.Tensor:
+        """The image projection alone: embeds as the UNet takes them, [rows, (T_feat,) D] -> tokens [rows, n_tok, ctx]."""
+        _lib.require_gpu()
+        x = _as_f16(image_embeds, self.device)
+        rows = x.shape[0]
+        out = torch.empty(rows, self.num_tokens, self.cfg.cross_attention_dim, dtype=torch.float16, device=x.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.sd_ip_adapter_project(self._h, C.c_void_p(x.data_ptr()), rows, C.c_void_p(out.data_ptr()),
+                                                       C.c_void_p(_stream_ptr())), "sd_ip_adapter_project")
+        return out
 
     def load_state_dict(self, state_dict: Dict[str, torch.Tensor], strict: bool = True):
         _lib.require_gpu()

@@ -245,6 +245,21 @@ class SDModelWrapper:
         sd, d_img, n_tok = self._ip
         base.attach_ip_adapter(base.make_ip_adapter(sd, d_img, n_tok))
         base.set_ip_adapter_scale(self._ip_scale)
+        self._sync_feature_tokens(base)
+
+    @property
+    def ip_adapter_is_plus(self) -> bool:
+        """Whether the loaded IP-Adapter projects hidden_states[-2] through a Resampler (IP-Adapter Plus files)."""
+        from . import ip_adapter
+        return self._ip is not None and ip_adapter.is_resampler(self._ip[0])
+
+    def _sync_feature_tokens(self, base=None):
+        # a Resampler adapter reads (image_size / patch_size)^2 + 1 rows per image of the loaded tower
+        base = self.base if base is None else base
+        vcfg = getattr(self.image_encoder, "cfg", None) or getattr(self.image_encoder, "config", None)
+        adapter = getattr(base, "ip_adapter", None)
+        if self.ip_adapter_is_plus and hasattr(vcfg, "patch_size") and hasattr(adapter, "feature_tokens"):
+            adapter.feature_tokens = (vcfg.image_size // vcfg.patch_size) ** 2 + 1
 
     def load_ip_adapter(self, pretrained_model_name_or_path_or_dict):
         """An original IP-Adapter file (`.bin` / `.safetensors`, a local path) or its state dict: converted, checked
@@ -288,6 +303,7 @@ class SDModelWrapper:
         self.image_encoder = None            # an old encoder's device memory goes before the new one is packed
         self.image_encoder = HipCLIPVisionModelWithProjection.from_state_dict(cfg, state_dict, device=str(self.device))
         self.feature_extractor = ClipImageProcessor(size=cfg.image_size)
+        self._sync_feature_tokens()
 
     def unload_image_encoder(self):
         self.image_encoder = None
@@ -976,7 +992,9 @@ class StableDiffusionUnifiedPipeline:
         """diffusers 0.27.2 `encode_image` for the base adapters' ImageProjection: image_encoder(feature_extractor(image)
         .pixel_values).image_embeds, repeated per prompt image; the negative is zeros_like (it still goes through the
         adapter's projection in the UNet, so its tokens are not zero).  Once per call: on the engine with
-        load_image_encoder's tower (which answers parameters() with its device and dtype), in PyTorch with a torch one."""
+        load_image_encoder's tower (which answers parameters() with its device and dtype), in PyTorch with a torch one.
+        With an IP-Adapter Plus (Resampler) adapter loaded: hidden_states[-2] of the image, [n_img, T_feat, D_emb], and
+        the same of a zero image as the negative."""
         m = self.model
         if m.image_encoder is None:
             raise ValueError("ip_adapter_image needs model.image_encoder (or pass ip_adapter_image_embeds)")
@@ -988,6 +1006,13 @@ class StableDiffusionUnifiedPipeline:
                 raise ValueError("ip_adapter_image needs model.feature_extractor for non-tensor images")
             image = m.feature_extractor(image, return_tensors="pt").pixel_values
         image = image.to(device=enc_device, dtype=dtype)
+        if getattr(m, "ip_adapter_is_plus", False):
+            # diffusers' branch for projection layers other than ImageProjection: the penultimate hidden states of the
+            # image, and of a zero image as the negative: [n_img, T_feat, D_emb] each
+            pos = m.image_encoder(image, output_hidden_states=True).hidden_states[-2]
+            neg = m.image_encoder(torch.zeros_like(image), output_hidden_states=True).hidden_states[-2]
+            return (pos.repeat_interleave(num_images_per_prompt, dim=0).to(device),
+                    neg.repeat_interleave(num_images_per_prompt, dim=0).to(device))
         image_embeds = m.image_encoder(image).image_embeds
         image_embeds = image_embeds.repeat_interleave(num_images_per_prompt, dim=0)
         return image_embeds.to(device), torch.zeros_like(image_embeds).to(device)
@@ -997,7 +1022,8 @@ class StableDiffusionUnifiedPipeline:
         """diffusers 0.27.2 `prepare_ip_adapter_image_embeds` for one adapter -> a list of one [N(.2), n_img, D_img]
         tensor, N = batch x images per prompt, negative half first under CFG (the order of the prompt embeddings).
         Precomputed embeds ([R(.2), n_img, D_img], negative half first under CFG) pass unchanged when R = N and are
-        repeated N / R times otherwise (diffusers repeats them N times: the same for the usual R = 1)."""
+        repeated N / R times otherwise (diffusers repeats them N times: the same for the usual R = 1).  With an
+        IP-Adapter Plus adapter loaded every tensor has one more axis: [.., n_img, T_feat, D_emb]."""
         if ip_adapter_image_embeds is None:
             if isinstance(ip_adapter_image, list) and len(ip_adapter_image) == 1:
                 ip_adapter_image = ip_adapter_image[0]
@@ -1010,7 +1036,11 @@ class StableDiffusionUnifiedPipeline:
         if len(ip_adapter_image_embeds) != 1:
             raise ValueError(f"one IP-Adapter is supported, got image embeds for {len(ip_adapter_image_embeds)}")
         e = ip_adapter_image_embeds[0]
-        if e.ndim != 3:
+        if getattr(getattr(self, "model", None), "ip_adapter_is_plus", False):
+            if e.ndim != 4:
+                raise ValueError("ip_adapter_image_embeds: an IP-Adapter Plus adapter takes the image encoder's "
+                                 f"hidden_states[-2] as [batch, n_img, T_feat, D_emb], got {tuple(e.shape)}")
+        elif e.ndim != 3:
             raise ValueError(f"ip_adapter_image_embeds: expected [batch, n_img, D_img], got {tuple(e.shape)}")
         halves = e.chunk(2) if do_classifier_free_guidance else (e,)
         rows = halves[0].shape[0]
@@ -1019,7 +1049,7 @@ class StableDiffusionUnifiedPipeline:
         if num_images_per_prompt % rows != 0 or any(h.shape[0] != rows for h in halves):
             raise ValueError(f"ip_adapter_image_embeds: {rows} rows per half do not divide the batch {num_images_per_prompt}")
         rep = num_images_per_prompt // rows
-        return [torch.cat([h.repeat(rep, 1, 1) for h in halves]).to(device)]
+        return [torch.cat([h.repeat(rep, *([1] * (h.ndim - 1))) for h in halves]).to(device)]
 
     def encode_prompt(self, prompt, prompt_2=None, negative_prompt=None, negative_prompt_2=None,
                       num_images_per_prompt=1, lora_scale=None, clip_skip=None):
