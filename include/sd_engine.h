@@ -551,6 +551,25 @@ int sd_op_conv2d_ex(const void* x_nhwc, const void* w_oihw, const void* bias, co
                     const void* res_nhwc, void* y_nhwc, int N, int H, int W, int Cin, int Cout, int ksize,
                     int stride, int upsample2x, int geglu, int64_t ldx, int64_t ldres, int64_t ldy, int pad, int act,
                     float acc_scale, float bias_scale, int gn_groups, int* ran, void* stream);
+/* Nearest-2x upsample + 3x3 conv on folded weights: four 2x2 convolutions on the input map, one per output parity
+ * (Upsample2D of the UNet up path and the VAE decoder).
+ * sd_upconv_fold_supported: 1 when op_conv runs the folded kernel for an [N, H, W, Cin] input (dense) and Cout output
+ *   channels: Cin % 64 == 0, Cout % 8 == 0, a 256-pixel patch 64 / 32 / 16 columns wide tiles the H x W input map,
+ *   SD_NO_UPCONV_FOLD unset.  Host only.
+ * sd_op_fold_upconv: the folded pack of w_oihw [Cout, Cin, 3, 3] f16 into `out` [4][Cout][4 Cin] f16 (device): parity
+ *   panel dy * 2 + dx, K order [Cin / 64][a][b][64]; taps summed in fp32 (kernel rows outside, columns inside), rounded
+ *   to f16 once.
+ * sd_op_upconv2x_ex: sd_op_conv2d_ex with ksize 3, stride 1, upsample2x 1 and no GEGLU / activation, packed and
+ *   dispatched as the models do it (both packs, op_conv's decision).  gn_summaries (optional, with gn_groups > 0):
+ *   receives the GroupNorm summaries the launch left, [N][S][gn_groups][2] floats (mean, M2), in a buffer of at least
+ *   N * max(64, ceil(4 H W / 64)) * gn_groups * 2 floats.
+ *   ran[4] out: 1 when the folded kernel ran (0: the 9-tap path), summaries per image S (0: none left), output pixels
+ *   per summary, 0. */
+int sd_upconv_fold_supported(int N, int H, int W, int Cin, int Cout);
+int sd_op_fold_upconv(const void* w_oihw, void* out, int Cout, int Cin, void* stream);
+int sd_op_upconv2x_ex(const void* x_nhwc, const void* w_oihw, const void* bias, const void* rowadd, const void* res_nhwc,
+                      void* y_nhwc, int N, int H, int W, int Cin, int Cout, int64_t ldx, int64_t ldres, int64_t ldy,
+                      float acc_scale, float bias_scale, int gn_groups, float* gn_summaries, int* ran, void* stream);
 /* conv_out: 3x3 / stride 1 / pad 1 convolution to 1..4 output channels (UNet2DConditionModel.conv_out 320 -> 4,
  * AutoencoderKL decoder.conv_out 128 -> 3; diffusers modules under sd_unified_pipeline.py:475-482, :523) with
  * the NHWC -> NCHW change of layout fused: x NHWC f16, w OIHW f16, bias f32, y NCHW f16.  Cin % 64 == 0. */

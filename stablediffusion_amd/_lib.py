@@ -218,6 +218,10 @@ SIGNATURES = {
     "sd_op_conv2d": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "sd_op_conv2d_ex": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I64, _I64, _I64, _I, _I, _F, _F, _I,
                              C.POINTER(_I), _P]),
+    "sd_upconv_fold_supported": (_I, [_I, _I, _I, _I, _I]),
+    "sd_op_fold_upconv": (_I, [_P, _P, _I, _I, _P]),
+    "sd_op_upconv2x_ex": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I64, _I64, _I64, _F, _F, _I, _P,
+                               C.POINTER(_I), _P]),
     "sd_op_conv3x3_small_cout": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "sd_op_conv2d_groupnorm": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _I,
                                     C.POINTER(_I), _P]),

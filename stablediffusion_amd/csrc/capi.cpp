@@ -1788,6 +1788,84 @@ int sd_op_fold_linear(const void* w_outer, const void* b_outer, const void* w_in
     return SD_OK;
 }
 
+int sd_upconv_fold_supported(int N, int H, int W, int Cin, int Cout) {
+    return upconv_fold_supported(N, H, W, Cin, Cout, Cin) ? 1 : 0;
+}
+
+int sd_op_fold_upconv(const void* w_oihw, void* out, int Cout, int Cin, void* stream) {
+    if (!w_oihw || !out || Cout < 1 || Cin < 64 || Cin % 64 != 0) {
+        set_error("sd_op_fold_upconv: bad arguments (Cin must be a multiple of 64)"); return SD_ERR_INVALID;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const long rows = ((long)Cout + kWeightRowPad - 1) / kWeightRowPad * kWeightRowPad, K4 = 4L * Cin;
+    DevScope scope;
+    half_t* wp = nullptr;
+    SD_DEV_ALLOC(scope, wp, (size_t)4 * rows * K4 * sizeof(half_t));
+    SD_HIP_CHECK(hipMemsetAsync(wp, 0, (size_t)4 * rows * K4 * sizeof(half_t), s));
+    if (int rc = launch_fold_upconv(static_cast<const half_t*>(w_oihw), wp, Cout, Cin, s)) return rc;
+    for (int par = 0; par < 4; ++par)           // the panels without their row padding
+        SD_HIP_CHECK(hipMemcpyAsync(static_cast<half_t*>(out) + (long)par * Cout * K4, wp + (long)par * rows * K4,
+                                    (size_t)Cout * K4 * sizeof(half_t), hipMemcpyDeviceToDevice, s));
+    SD_HIP_CHECK(hipStreamSynchronize(s));
+    return SD_OK;
+}
+
+int sd_op_upconv2x_ex(const void* x, const void* w_oihw, const void* bias_f32, const void* rowadd_f32, const void* res,
+                      void* y, int N, int H, int W, int Cin, int Cout, int64_t ldx, int64_t ldres, int64_t ldy,
+                      float acc_scale, float bias_scale, int gn_groups, float* gn_summaries, int* ran, void* stream) {
+    if (!x || !w_oihw || !y || !ran || N < 1 || H < 1 || W < 1 || Cin < 64 || Cin % 64 != 0 || Cout < 1 || gn_groups < 0 ||
+        !(acc_scale > 0.f) || !(bias_scale > 0.f)) {
+        set_error("sd_op_upconv2x_ex: bad arguments (Cin % 64 == 0, positive scales)"); return SD_ERR_INVALID;
+    }
+    auto ld_ok = [](int64_t ld, int dense) { return ld == dense || (ld > dense && ld % 8 == 0); };
+    if (!ld_ok(ldx, Cin) || !ld_ok(ldy, Cout) || (res && !ld_ok(ldres, Cout))) {
+        set_error("sd_op_upconv2x_ex: ldx / ldres / ldy must be the dense width or a wider multiple of 8"); return SD_ERR_INVALID;
+    }
+    for (int i = 0; i < 4; ++i) ran[i] = 0;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // both packs, as WeightStore::pack_conv(fold_up2x) leaves them (the bias stays fp32, as in sd_op_conv2d_ex)
+    const long K = 9L * Cin, rows = ((long)Cout + kWeightRowPad - 1) / kWeightRowPad * kWeightRowPad;
+    DevScope scope;
+    ConvW cw;
+    cw.cin = Cin; cw.cout = Cout; cw.ks = 3; cw.K = K;
+    SD_DEV_ALLOC(scope, cw.w, (size_t)rows * K * sizeof(half_t));
+    SD_DEV_ALLOC(scope, cw.bias, (size_t)rows * sizeof(float));
+    SD_HIP_CHECK(hipMemsetAsync(cw.w, 0, (size_t)rows * K * sizeof(half_t), s));
+    SD_HIP_CHECK(hipMemsetAsync(cw.bias, 0, (size_t)rows * sizeof(float), s));
+    int rc = launch_pack_conv(static_cast<const half_t*>(w_oihw), cw.w, Cout, Cin, 3, 3, K, s);
+    if (rc) return rc;
+    if (bias_f32) SD_HIP_CHECK(hipMemcpyAsync(cw.bias, bias_f32, (size_t)Cout * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (Cout % 8 == 0) {
+        SD_DEV_ALLOC(scope, cw.w_up, (size_t)16 * rows * Cin * sizeof(half_t));
+        SD_HIP_CHECK(hipMemsetAsync(cw.w_up, 0, (size_t)16 * rows * Cin * sizeof(half_t), s));
+        if ((rc = launch_fold_upconv(static_cast<const half_t*>(w_oihw), cw.w_up, Cout, Cin, s))) return rc;
+    }
+    const long OHW = 4L * H * W;
+    GnStatBuf gb;
+    if (gn_groups > 0) SD_DEV_ALLOC(scope, gb.buf, (size_t)gnstat_floats(N, OHW, gn_groups) * sizeof(float));
+    int folded = 0;
+    rc = run_op_on_arena(s, 0, nullptr, [&](Ctx& c) {
+        ConvFuse f;
+        f.acc_scale = acc_scale; f.bias_scale = bias_scale;
+        f.gn_out = gn_groups > 0 ? &gb : nullptr; f.gn_groups = gn_groups;
+        f.fold_ran = &folded;
+        const View rv(const_cast<half_t*>(static_cast<const half_t*>(res)), ldres, Cout);
+        op_conv(c, cw, View(const_cast<half_t*>(static_cast<const half_t*>(x)), ldx, Cin), N, H, W,
+                View(static_cast<half_t*>(y), ldy, Cout), 1, 1, static_cast<const float*>(rowadd_f32), Cout, res ? &rv : nullptr,
+                0, -1, 0, &f);
+    });
+    if (rc) return rc;
+    ran[0] = folded;
+    if (gb.st.part) {
+        ran[1] = gb.st.S; ran[2] = (int)gb.st.rows;
+        if (gn_summaries)
+            SD_HIP_CHECK(hipMemcpyAsync(gn_summaries, gb.st.part, (size_t)N * gb.st.S * gn_groups * 2 * sizeof(float),
+                                        hipMemcpyDeviceToDevice, s));
+    }
+    SD_HIP_CHECK(hipStreamSynchronize(s));
+    return SD_OK;
+}
+
 int sd_op_ffn_geglu_proj_out(const void* x_in, const void* t3, const void* ln_gamma, const void* ln_beta, float ln_eps,
                              const void* w1, const void* b1, const void* w2, const void* b2, const void* w_po,
                              const void* b_po, void* y, float* gn_summaries, int* gn_rows, int M, int C, int imgs, int* fused,

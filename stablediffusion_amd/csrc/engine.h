@@ -49,6 +49,9 @@ struct ConvW {          // conv or linear, packed [rows_pad][K] fp16 + fp32 bias
     int cin = 0, cout = 0, ks = 1;
     long K = 0;         // packed K (>= ks*ks*cin, multiple of 64)
     float* wsum = nullptr;   // row sums of the packed weights: set when a LayerNorm was folded in (fold_ln)
+    // the folded pack of a conv that follows a nearest-2x upsample (pack_conv(fold_up2x): four parity panels
+    // [rows_pad][4 cin], kernels.h: launch_fold_upconv), next to the 9-tap pack: op_conv picks per launch
+    half_t* w_up = nullptr;
 };
 // Per-row (mean, M2) parts of an activation tensor, `parts` pairs per row, part k over the columns
 // [k width, min((k + 1) width, C)): written by the GEMM that produced the tensor (or by launch_row_stats,
@@ -82,6 +85,7 @@ struct ConvFuse {
     float acc_scale = 1.f, bias_scale = 1.f;
     // tile hint of this launch (IGemmRequest::hint_variant / hint_splits): -1 = none
     int tile_variant = -1, tile_splits = 0;
+    int* fold_ran = nullptr;            // single-operator entries: set to 1 when the folded-upsample kernel ran, else 0
 };
 struct NormW {
     float* gamma = nullptr;
@@ -105,7 +109,8 @@ class WeightStore {
     bool complete(std::string* missing) const;
     const RawTensor* raw(const std::string& key) const;
     // packing helpers (device work on the null stream; finalize() synchronises once)
-    int pack_conv(const std::string& prefix, ConvW* out, bool has_bias = true);
+    // fold_up2x: the conv follows a nearest-2x upsample (upsamplers.0.conv): also build the folded pack (ConvW::w_up)
+    int pack_conv(const std::string& prefix, ConvW* out, bool has_bias = true, bool fold_up2x = false);
     int pack_rows(const std::vector<std::string>& weight_keys, const std::vector<std::string>& bias_keys,
                   ConvW* out);                                  // row-concatenated linears
     int pack_geglu(const std::string& prefix, ConvW* out);      // [8C][C] -> 64-row interleave

@@ -1176,6 +1176,267 @@ int launch_halo(const IGemmParams& p, float* partial, int splits, hipStream_t s)
     return launch_halo_t<BN, false, true>(p, partial, splits, s);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Nearest-2x upsample + 3x3 conv as four 2x2 convs on the INPUT map, one per output parity (dy, dx):
+//     y[2i + dy, 2j + dx] = b + sum_{a, b in {0, 1}} W'_{dy,dx}[a, b] . x[i + a - 1 + dy, j + b - 1 + dx]
+// (of the three kernel rows an output pixel sees, two land on the same input row -- their weights are summed at pack
+// time, launch_fold_upconv; columns likewise): 4 taps instead of 9 on the same halo tile.  A block = (256-pixel patch
+// of one input image, N tile, parity); it writes the 256 output pixels of its parity over the patch's 2R x 2Wt output
+// area.  The halo tile [(R + 2) x (Wt + 2) x 64] is the parent's, at input resolution; tap (a, b) reads it at pixel
+// offset (dy + a, dx + b).  Weights: the parity's panel [rows][4 Cin], K order [Cin/64][a][b][64], one [BN x 64] stage
+// per tap through the parent's three-stage ring.  Four taps per slab do not divide over three stages, so the stage of a
+// step is run-time (one scalar, two vector adds per tap); the waits stay compile-time: they count loads in flight, and
+// those are the parent's (two weight stages ahead, the next halo issued at a slab's first tap).
+// No split-K, row add or residual (neither upsample site has them: upconv_fold_plan refuses).
+// ---------------------------------------------------------------------------------------------
+template <int BN>
+__global__ __launch_bounds__(512) void conv3x3_halo_up2x2_kernel(IGemmParams p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    static_assert(BN == 160 || BN == 128, "column tile");
+    constexpr unsigned kOOB = 0x80000000u;
+    constexpr int BM = 256, NW = 8, NT = 512, WAVES_N = 2;
+    constexpr int WTM = 64, WTN = BN / 2, TM = 4, TN = WTN / 16;
+    constexpr int B_INSTR = BN / 8, B_PW = (B_INSTR + NW - 1) / NW, B_REM = B_INSTR % NW;
+    constexpr int B_STAGE_HALVES = BN * 64;
+    constexpr int AJ = 7;
+    constexpr int LDC = BN + 8;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int W = p.W, HW = p.H * p.W;                       // input image: the patch tiles it
+    const int OW = p.OW, OHW = p.OH * p.OW;                  // output image = 2H x 2W
+    const int Wt = halo_patch_width(p.H, W), Wp = Wt + 2;
+    const int R = BM / Wt;
+    const int HP = (R + 2) * Wp;
+    const int A_HALVES = HP * 64;
+    half_t* sA = reinterpret_cast<half_t*>(smem);            // [2][HP][64], swizzled on the pixel index
+    half_t* sB = sA + 2 * A_HALVES;                          // [3][BN][64]
+    half_t* sC = reinterpret_cast<half_t*>(smem);            // epilogue staging overlays both
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave / WAVES_N, wn = wave % WAVES_N;
+    // a "column" of the block grid = (parity, N tile): each has its own weight tile; its rows = the patches
+    const int tiles_n = (p.Cout + BN - 1) / BN, cols = 4 * tiles_n;
+    const int bid = xcd_remap(blockIdx.x, gridDim.x);
+    int tm, tc;
+    if (p.mfast) {
+        const int tiles_m = gridDim.x / cols;
+        tc = bid / tiles_m; tm = bid - tc * tiles_m;
+    } else {
+        tm = bid / cols; tc = bid - tm * cols;
+    }
+    const int par = tc / tiles_n, tn = tc - par * tiles_n;
+    const int dy = par >> 1, dx = par & 1;
+    const int n0 = tn * BN;
+    const int patches_w = W / Wt, patches = (p.H / R) * patches_w;
+    const int img = tm / patches, pidx = tm - img * patches;
+    const int row0 = (pidx / patches_w) * R, col0 = (pidx % patches_w) * Wt;
+    // GEMM row (NHWC pixel index of the OUTPUT) of the tile's local pixel ml
+    auto row_of = [&](int ml) {
+        const int r = ml / Wt;
+        return img * OHW + (2 * (row0 + r) + dy) * OW + 2 * (col0 + (ml - r * Wt)) + dx;
+    };
+    const int nslab = p.Cin / 64;
+
+    const long x_bytes = (long)p.N * HW * p.ldx * 2;
+    __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<half_t*>(p.x), 0, (int)x_bytes, 0x00020000);
+    const long wrows = ((long)p.Cout + kWeightRowPad - 1) / kWeightRowPad * kWeightRowPad;
+    __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<half_t*>(p.w) + (long)par * wrows * p.K, 0,
+                                                                  (int)(wrows * p.K * 2), 0x00020000);
+
+    // ---- halo DMA slots: slot = 64 * instr + lane = 8 * halo pixel + chunk position ----
+    const int NI = (HP * 8 + 63) >> 6;
+    int a_off[AJ];          // byte offset of the source chunk at slab 0; -2: outside the image (zeros); -1: no slot
+#pragma unroll
+    for (int j = 0; j < AJ; ++j) {
+        const int i = wave + NW * j;
+        const int slot = i * 64 + lane;
+        const int hp = slot >> 3, cpos = slot & 7;
+        const int hr = hp / Wp, hc = hp - hr * Wp;
+        const int ih = row0 - 1 + hr, iw = col0 - 1 + hc;
+        const bool inb = ((unsigned)ih < (unsigned)p.H) & ((unsigned)iw < (unsigned)W);
+        const int chunk = cpos ^ (hp & 7);
+        int off = -1;
+        if (i < NI && slot < HP * 8)
+            off = inb ? (int)((((long)img * HW + (long)ih * W + iw) * p.ldx + chunk * 8) * 2) : -2;
+        a_off[j] = off;
+    }
+    auto issueA = [&](int bufi, int slab) {
+        half_t* dst = sA + bufi * A_HALVES;
+#pragma unroll
+        for (int j = 0; j < AJ; ++j) {
+            const int i = wave + NW * j;
+            if (i < NI && a_off[j] != -1) {
+                const unsigned voff = a_off[j] >= 0 ? (unsigned)a_off[j] + (unsigned)(slab * 128) : kOOB;
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (__attribute__((address_space(3))) void*)(dst + i * 512), 16,
+                                                         voff, 0, 0, 0);
+            }
+        }
+    };
+    // ---- weight tile: 8 rows of 64 halves per DMA instruction, chunk ^ (row & 7) on the source side ----
+    const int lrow = lane >> 3;
+    const int chunkB = (lane & 7) ^ lrow;
+    const bool b_hi = B_REM == 0 || wave < B_REM;
+    const int b_cnt = b_hi ? B_PW : B_PW - 1;
+    const int b_first = b_hi ? wave * B_PW : B_REM * B_PW + (wave - B_REM) * (B_PW - 1);
+    unsigned b_off[B_PW];
+#pragma unroll
+    for (int j = 0; j < B_PW; ++j)
+        b_off[j] = (unsigned)((((long)(n0 + (b_first + j) * 8 + lrow)) * p.K + chunkB * 8) * 2);
+    auto issueB = [&](int stage, int g) {       // K order [Cin/64][2][2][64]: step g = slab * 4 + tap
+        half_t* dst = sB + stage * B_STAGE_HALVES;
+#pragma unroll
+        for (int j = 0; j < B_PW; ++j)
+            if (j < b_cnt)
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (__attribute__((address_space(3))) void*)(dst + (b_first + j) * 512),
+                                                         16, b_off[j] + (unsigned)(g * 128), 0, 0, 0);
+    };
+
+    f4 acc[TM][TN];
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j) acc[i][j] = f4{0.f, 0.f, 0.f, 0.f};
+
+    const int fr = lane & 15, fq = lane >> 4;
+    int hp0[TM];                                 // halo pixel of this lane's pixel at halo offset (dy, dx): tap (0, 0)
+#pragma unroll
+    for (int i = 0; i < TM; ++i) {
+        const int ml = wm * WTM + i * 16 + fr;
+        const int r = ml / Wt, c = ml - r * Wt;
+        hp0[i] = (r + dy) * Wp + c + dx;
+    }
+
+    issueA(0, 0);
+    issueB(0, 0);
+    issueB(1, 1);                                // (a slab has four steps: step 1 always exists)
+    // Main loop: slab -> its four taps, unrolled.  Step g = slab * 4 + tap reads weight stage g % 3 (st) and, behind
+    // the barrier, refills stage (g + 2) % 3, which step g - 1 read.  Waits: B(g) must have landed (and at a slab's
+    // first tap its halo, which is older); younger loads that may stay in flight are B(g + 1) -- 2 instructions in the
+    // wave with the smallest share -- and, at taps 1 and 2, the next halo (5) issued at tap 0 behind B(g + 2).
+    int g = 0, st = 0, abuf = 0;
+    bool a_next = false;
+    for (int slab = 0; slab < nslab; ++slab) {
+        const bool lastslab = slab + 1 >= nslab;
+        const half_t* cA = sA + abuf * A_HALVES;
+#pragma unroll
+        for (int tap = 0; tap < 4; ++tap, ++g) {
+            if (lastslab && tap == 3) wait_vmcnt<0>();
+            else if (a_next && (tap == 1 || tap == 2)) wait_vmcnt<7>();
+            else wait_vmcnt<2>();
+            __builtin_amdgcn_s_barrier();
+            const int st2 = st >= 1 ? st - 1 : 2;            // (st + 2) % 3
+            if (!(lastslab && tap >= 2)) issueB(st2, g + 2);
+            if (tap == 0) {
+                a_next = !lastslab;
+                if (a_next) issueA(abuf ^ 1, slab + 1);
+            }
+            const half_t* cB = sB + st * B_STAGE_HALVES;
+            const int tapoff = (tap >> 1) * Wp + (tap & 1);
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks) {
+                h8 fa[TM], fb[TN];
+                const int ch = ks * 4 + fq;
+#pragma unroll
+                for (int i = 0; i < TM; ++i) {
+                    const int hp = hp0[i] + tapoff;
+                    fa[i] = *reinterpret_cast<const h8*>(cA + hp * 64 + ((ch ^ (hp & 7)) << 3));
+                }
+#pragma unroll
+                for (int j = 0; j < TN; ++j) {
+                    const int r = wn * WTN + j * 16 + fr;
+                    fb[j] = *reinterpret_cast<const h8*>(cB + r * 64 + ((ch ^ (r & 7)) << 3));
+                }
+#pragma unroll
+                for (int i = 0; i < TM; ++i)
+#pragma unroll
+                    for (int j = 0; j < TN; ++j)
+                        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fb[j], fa[i], acc[i][j], 0, 0, 0);
+            }
+            st = st == 2 ? 0 : st + 1;
+        }
+        abuf ^= 1;
+    }
+
+    // ---- fused epilogue through LDS (as conv3x3_halo_kernel) ----
+    __syncthreads();
+    const float acc_scale = *reinterpret_cast<const volatile float*>(&p.acc_scale);
+    const float bias_scale = *reinterpret_cast<const volatile float*>(&p.bias_scale);
+    {
+        f4 add[TN];
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+            add[j] = p.bias ? *reinterpret_cast<const f4*>(p.bias + n0 + wn * WTN + j * 16 + fq * 4) * bias_scale : f4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int i = 0; i < TM; ++i) {
+            const int pr = wm * WTM + i * 16 + fr;
+#pragma unroll
+            for (int j = 0; j < TN; ++j) {
+                const int col = wn * WTN + j * 16 + fq * 4;
+                const f4 v = acc[i][j] * acc_scale + add[j];
+                h4 o = {(half_t)v[0], (half_t)v[1], (half_t)v[2], (half_t)v[3]};
+                *reinterpret_cast<h4*>(sC + pr * LDC + col) = o;
+            }
+        }
+    }
+    __syncthreads();
+    constexpr int CH = BN / 8;
+    constexpr int RPP = NT / CH;
+    constexpr int ITER = (BM + RPP - 1) / RPP;
+    const int c8 = tid % CH, rr = tid / CH;
+    const int c = c8 * 8, n = n0 + c;
+    const bool okc = rr < RPP && n < p.Cout;
+    // GroupNorm summaries of the stored tile: the 256 output pixels of this (patch, parity); the consumers count rows
+    // per summary, not which pixels
+    const int cpg = p.gnstat_out ? p.Cout / p.gn_groups : 8;
+    const int g_first = n / cpg;
+    const int gsplit = (g_first + 1) * cpg - n;
+    float gm0 = 0.f, gq0 = 0.f, gm1 = 0.f, gq1 = 0.f;
+    float gp0 = 0.f, gp1 = 0.f;
+    int gnv = 0;
+#pragma unroll
+    for (int it = 0; it < ITER; ++it) {
+        const int r = rr + it * RPP;
+        if (okc && r < BM) {
+            const h8 v = *reinterpret_cast<const h8*>(sC + r * LDC + c);
+            *reinterpret_cast<h8*>(p.y + (long)row_of(r) * p.ldy + n) = v;
+            if (p.gnstat_out) { gn_chunk_accum(v, gsplit, it == 0, gp0, gp1, gm0, gq0, gm1, gq1); ++gnv; }
+        }
+    }
+    if (p.gnstat_out) {
+        float* sG = reinterpret_cast<float*>(smem + ((BM * LDC * 2 + 15) & ~15));     // behind the staging tile
+        gn_part_finish(gsplit, gnv, gp0, gp1, gm0, gq0, gm1, gq1);
+        gn_tile_stats<BM, BN, NT>(sG, tid, gm0, gq0, gm1, gq1, n0, p.Cout, cpg, p.gn_groups,
+                                  p.gnstat_out + (((long)img * patches + pidx) * 4 + par) * p.gn_groups * 2);
+    }
+#endif  // __HIP_DEVICE_COMPILE__
+}
+
+template <int BN>
+int launch_up2x2_t(const IGemmParams& p, hipStream_t s) {
+    const int Wt = halo_patch_width(p.H, p.W), R = 256 / Wt;
+    size_t lds = (size_t)2 * (R + 2) * (Wt + 2) * 128 + (size_t)3 * BN * 128;      // [2 halo tiles | 3 weight stages]
+    const size_t epi = (size_t)256 * (BN + 8) * 2 + 16 + 512 * 16;                 // staging tile + GroupNorm partials
+    if (lds < epi) lds = epi;
+    if (lds > 160 * 1024) { set_error("conv3x3_halo_up2x2_kernel: LDS budget"); return 1; }
+    static size_t attr_by_dev[64] = {};
+    static std::mutex attr_mu;
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    std::lock_guard<std::mutex> attr_lock(attr_mu);
+    size_t& attr = attr_by_dev[dev & 63];
+    if (lds > attr) {
+        SD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_halo_up2x2_kernel<BN>),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        attr = lds;
+    }
+    const int blocks = p.N * (p.H * p.W / 256) * 4 * cdiv(p.Cout, BN);
+    IGemmParams q = p;
+    q.mfast = weights_outweigh_activations(p);      // (p.K = 4 Cin: one parity's panel against the input)
+    hipLaunchKernelGGL((conv3x3_halo_up2x2_kernel<BN>), dim3(blocks), dim3(512), lds, s, q);
+    SD_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
 template <int BM, int BN, int WM, int WN, int STAGES, bool PW, bool STAG, int BKT>
 int launch_v2p(const IGemmParams& p, float* partial, int splits, hipStream_t s) {
     constexpr size_t lds = IGemm2Lds<BM, BN, STAGES, BKT>::TOTAL;
@@ -1437,6 +1698,42 @@ IGemmPlan igemm2_plan(IGemmParams& p, const IGemmRequest& rq) {
     if (pl.kind == kKindPgemmGeglu) snprintf(pl.name, sizeof(pl.name), "geglu_persist_kernel");
     else snprintf(pl.name, sizeof(pl.name), t.name, p.KS == 1 && p.stride == 1 && p.up == 0 ? "true" : "false");
     return pl;
+}
+
+bool upconv_fold_supported(int N, int H, int W, int Cin, int Cout, long ldx) {
+    static const bool off = getenv("SD_NO_UPCONV_FOLD") != nullptr;     // A/B switch: every upsample conv on the 9-tap kernels
+    if (off || N < 1 || H < 1 || W < 1 || Cin < 64 || Cout < 8) return false;
+    const long wrows = ((long)Cout + kWeightRowPad - 1) / kWeightRowPad * kWeightRowPad;
+    return Cin % 64 == 0 && Cout % 8 == 0 && halo_patch_width(H, W) > 0 && (long)N * H * W * ldx * 2 < (1L << 31) &&
+           wrows * 4 * Cin * 2 < (1L << 31) && (long)N * H * W * 4 < (1L << 31);
+}
+
+UpconvFoldPlan upconv_fold_plan(IGemmParams& p, const half_t* w_fold, const IGemmRequest& rq) {
+    UpconvFoldPlan pl;
+    if (!w_fold || p.up != 1 || p.KS != 3 || p.stride != 1 || p.pad != 1 || p.OH != 2 * p.H || p.OW != 2 * p.W ||
+        p.K != 9 * p.Cin || p.geglu || p.act || p.rowadd || p.res || p.ln_stat || p.gni_part || rq.rowstat ||
+        !upconv_fold_supported(p.N, p.H, p.W, p.Cin, p.Cout, p.ldx))
+        return pl;
+    pl.ok = true;
+    pl.bn = p.Cout % 160 == 0 ? 160 : 128;
+    p.w = w_fold; p.K = 4 * p.Cin; p.KS = 2;
+    // GroupNorm summaries under the planner's conditions for an unsplit launch (igemm2_plan, step 1): one per (patch,
+    // parity) = 256 output pixels of one image; group boundaries on tile boundaries
+    const int G = rq.gn_groups, cpg = G > 0 && p.Cout % G == 0 ? p.Cout / G : 0;
+    p.gnstat_out = nullptr; p.gn_groups = 0;
+    if (rq.gnstat && (cpg >= 8 || cpg == 4) && (pl.bn % cpg == 0 || p.Cout <= pl.bn)) {
+        p.gnstat_out = rq.gnstat; p.gn_groups = G;
+        pl.gnstats = true; pl.gn_rows = 256;
+    }
+    snprintf(pl.name, sizeof(pl.name), "conv3x3_halo_kernel<%d>/up2x2", pl.bn);
+    return pl;
+}
+
+int launch_upconv_fold(const IGemmParams& p, const UpconvFoldPlan& plan, hipStream_t s) {
+    if (!plan.ok || p.KS != 2 || p.K != 4 * p.Cin || halo_patch_width(p.H, p.W) == 0) {
+        set_error("launch_upconv_fold: not a folded-upsample problem (upconv_fold_plan decides)"); return 1;
+    }
+    return plan.bn == 160 ? launch_up2x2_t<160>(p, s) : launch_up2x2_t<128>(p, s);
 }
 
 IGemmLaunchNote igemm2_last_launch() { return t_note; }

@@ -110,6 +110,30 @@ IGemmPlan igemm2_plan(IGemmParams& p, const IGemmRequest& rq = IGemmRequest());
 // Runs p as planned; plans it itself (requests = p's own rowstat_out / gnstat_out) when no plan is passed.  A plan that
 // splits K needs `partial` of plan->partial_floats; without it the launch is planned again and runs unsplit.
 int launch_igemm2(const IGemmParams& p, float* partial, hipStream_t s, const IGemmPlan* plan = nullptr);
+// Nearest-2x upsample + 3x3 conv run as four 2x2 convs on the input map, one per output parity, on weights folded at
+// pack time (launch_fold_upconv; conv3x3_halo_up2x2_kernel in igemm2.hip): 4/9 of the 9-tap kernel's MACs.  Decided
+// outside igemm2_plan, which answers every problem as it always has.
+// The shape part of the decision (and SD_NO_UPCONV_FOLD unset): Cin % 64, Cout % 8, a 256-pixel patch (64 / 32 / 16
+// columns wide) tiles the H x W INPUT map, operands within 2 GB.  Host only.
+bool upconv_fold_supported(int N, int H, int W, int Cin, int Cout, long ldx);
+struct UpconvFoldPlan {
+    bool ok = false;                // the folded kernel runs this launch
+    int bn = 0;                     // its column tile
+    bool gnstats = false;           // the epilogue leaves the GroupNorm summaries asked for
+    int gn_rows = 0;                // output pixels per summary (one per patch and parity)
+    char name[64] = "";             // profiler row: "conv3x3_halo_kernel<BN>/up2x2"
+};
+// The one predicate of the dry and the live pass.  p = the 9-tap problem as op_conv poses it (up = 1), w_fold = the
+// folded pack or null; when the plan is ok, p is rewritten to the folded problem (w = w_fold, K = 4 Cin, KS = 2,
+// gnstat_out / gn_groups = what the launch will fill).  Refuses row add, residual, GEGLU, activation, LayerNorm fold,
+// fused input GroupNorm and row statistics: those stay on the 9-tap kernels.
+UpconvFoldPlan upconv_fold_plan(IGemmParams& p, const half_t* w_fold, const IGemmRequest& rq);
+int launch_upconv_fold(const IGemmParams& p, const UpconvFoldPlan& plan, hipStream_t s);
+// The folded pack of a [O][I][3][3] fp16 weight: four parity panels (dy, dx), each [rows][4 I] with rows = O padded
+// to kWeightRowPad (wp zeroed by the caller), K order [I / 64][a][b][64]; rows dy = 0: W'[a=0] = W[kh=0],
+// W'[a=1] = W[1] + W[2]; dy = 1: W'[0] = W[0] + W[1], W'[1] = W[2]; columns likewise.  Taps are summed in fp32
+// (kh-major, kw inside) and rounded to fp16 once.  I % 64 == 0.
+int launch_fold_upconv(const half_t* w_oihw, half_t* wp, int O, int I, hipStream_t s);
 // Most row-statistics parts per row (IGemmParams::ln_parts) a folded-LayerNorm launch takes; launch_igemm2 fails beyond.
 int igemm2_max_ln_parts();
 // What the calling thread's last launch_igemm2 launched on top of the plan: the split-K slices after the launcher's

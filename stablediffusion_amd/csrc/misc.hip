@@ -272,6 +272,28 @@ __global__ void pack_conv_kernel(const half_t* __restrict__ w, half_t* __restric
     wp[i] = val;
 }
 
+// Nearest-2x upsample + 3x3 conv = four 2x2 convs on the input map (kernels.h: launch_fold_upconv).  One thread per
+// folded weight: parity (dy, dx), output row o, K position [I/64][a][b][64].  Row tap a of parity dy covers kernel
+// rows lo..hi (dy 0: {0}, {1, 2}; dy 1: {0, 1}, {2}), columns likewise; summed in fp32, kh-major, one rounding.
+__global__ void fold_upconv_kernel(const half_t* __restrict__ w, half_t* __restrict__ wp, int O, int I, long rows) {
+    const long K4 = 4L * I;
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;  // over 4 * O * K4
+    if (i >= 4 * O * K4) return;
+    const long kq = i % K4;
+    const long o = (i / K4) % O;
+    const int par = (int)(i / (K4 * O));
+    const int dy = par >> 1, dx = par & 1;
+    const int slab = (int)(kq >> 6), cl = (int)(kq & 63);
+    const int tap = slab & 3, a = tap >> 1, b = tap & 1;
+    const long ci = (long)(slab >> 2) * 64 + cl;
+    const int h_lo = a == 0 ? 0 : 2 - (1 - dy), h_hi = a == 0 ? dy : 2;
+    const int w_lo = b == 0 ? 0 : 2 - (1 - dx), w_hi = b == 0 ? dx : 2;
+    float s = 0.f;
+    for (int kh = h_lo; kh <= h_hi; ++kh)
+        for (int kw = w_lo; kw <= w_hi; ++kw) s += (float)w[((o * I + ci) * 3 + kh) * 3 + kw];
+    wp[((long)par * rows + o) * K4 + kq] = (half_t)s;
+}
+
 // sd_unified_pipeline.py:467-472: latent_model_input = scale_model_input(cat([latents]*2))
 __global__ void cfg_duplicate_kernel(const half_t* __restrict__ lat, half_t* __restrict__ out, long n,
                                      float scale) {
@@ -1030,6 +1052,13 @@ int launch_conv3x3_small_cout(const half_t* x, long ldx, const half_t* w, long K
 }
 int launch_pack_conv(const half_t* w, half_t* wp, int O, int I, int KH, int KW, long Kpad, hipStream_t s) {
     hipLaunchKernelGGL(pack_conv_kernel, grid1d((long)O * Kpad), dim3(256), 0, s, w, wp, O, I, KH, KW, Kpad);
+    SD_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+int launch_fold_upconv(const half_t* w, half_t* wp, int O, int I, hipStream_t s) {
+    if (O < 1 || I < 64 || I % 64 != 0) { set_error("fold_upconv: Cin must be a multiple of 64"); return 1; }
+    const long rows = ((long)O + kWeightRowPad - 1) / kWeightRowPad * kWeightRowPad;
+    hipLaunchKernelGGL(fold_upconv_kernel, grid1d(16L * O * I), dim3(256), 0, s, w, wp, O, I, rows);
     SD_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -134,7 +134,7 @@ static int upload_bias(WeightStore* ws, const std::vector<float>& host, int cout
     return 0;
 }
 
-int WeightStore::pack_conv(const std::string& prefix, ConvW* out, bool has_bias) {
+int WeightStore::pack_conv(const std::string& prefix, ConvW* out, bool has_bias, bool fold_up2x) {
     const RawTensor* w = raw(prefix + ".weight");
     if (!w) { set_error("missing weight: " + prefix + ".weight"); return 2; }
     const int O = (int)w->shape[0], I = (int)w->shape[1];
@@ -148,6 +148,15 @@ int WeightStore::pack_conv(const std::string& prefix, ConvW* out, bool has_bias)
     SD_HIP_CHECK(hipMemsetAsync(out->w, 0, (size_t)rows * K * sizeof(half_t), 0));
     int rc = launch_pack_conv(w->dev, out->w, O, I, KH, KW, K, 0);
     if (rc) return rc;
+    out->w_up = nullptr;
+    if (fold_up2x && KH == 3 && KW == 3 && I % 64 == 0 && O % 8 == 0) {
+        // 16/9 of the 9-tap pack on top of it; both stay, the map size at launch decides which runs (op_conv)
+        const size_t bytes = (size_t)4 * rows * 4 * I * sizeof(half_t);
+        out->w_up = static_cast<half_t*>(dmalloc(bytes));
+        if (!out->w_up) { set_error("hipMalloc failed (folded upsample weights)"); return 3; }
+        SD_HIP_CHECK(hipMemsetAsync(out->w_up, 0, bytes, 0));
+        if ((rc = launch_fold_upconv(w->dev, out->w_up, O, I, 0))) return rc;
+    }
     out->bias = nullptr;
     if (has_bias) {
         std::vector<float> b;
@@ -404,6 +413,35 @@ void op_conv(Ctx& c, const ConvW& w, View x, int N, int H, int W, View y, int st
     // one plan per launch: the tile, what the epilogue leaves of the requested statistics, the workspace, the name
     IGemmRequest rq{stat_out ? stat_out->p : nullptr, gn_out ? gn_out->buf : nullptr, fuse ? fuse->gn_groups : 0};
     if (fuse) { rq.hint_variant = fuse->tile_variant; rq.hint_splits = fuse->tile_splits; }
+    if (fuse && fuse->fold_ran) *fuse->fold_ran = 0;
+    // Upsample + 3x3 conv on the folded weights (four 2x2 parity convs, 4/9 of the MACs) where the input map admits a
+    // patch: decided here, ahead of the planner, by the one predicate of the dry and the live pass
+    if (up == 1 && w.w_up) {
+        const UpconvFoldPlan fp = upconv_fold_plan(p, w.w_up, rq);
+        if (fp.ok) {
+            if (gn_out) {
+                gn_out->st = GnStats();
+                if (fp.gnstats) { gn_out->st.part = gn_out->buf; gn_out->st.rows = fp.gn_rows; gn_out->st.S = p.OH * p.OW / fp.gn_rows; }
+            }
+            if (fuse && fuse->fold_ran) *fuse->fold_ran = 1;
+            if (c.dry || c.err) return;
+            if (prof_enabled()) {
+                const char* name = fp.name;
+                static const bool by_shape = getenv("SD_PROF_SHAPES") != nullptr;
+                char nbuf[64];
+                if (by_shape) {
+                    snprintf(nbuf, sizeof(nbuf), "up2x2<%d> %dx%dx%d ks%d%s", fp.bn, p.M, p.Cout, p.K, p.KS, p.gnstat_out ? " gs" : "");
+                    name = nbuf;
+                }
+                // the FLOPs executed: 4 taps (the 9-tap form of the same launch counts 9/4 of them)
+                prof_open(c.stream, name, 2.0 * p.M * w.cout * 4.0 * w.cin,
+                          2.0 * ((double)N * H * W * w.cin + 16.0 * w.cout * w.cin + (double)p.M * w.cout));
+            }
+            c.err = launch_upconv_fold(p, fp, c.stream);
+            prof_close(c.stream);
+            return;
+        }
+    }
     const IGemmPlan plan = igemm2_plan(p, rq);
     const bool v2 = plan.kind != kKindIgemm1;
     if ((p.acc_scale != 1.f || p.bias_scale != 1.f) && !plan.scales_ok) { set_error("op_conv: output scaling needs the LDS-DMA kernels (not GEGLU / weight-stationary)"); c.err = 1; return; }

@@ -283,7 +283,7 @@ int UNet::finalize() {
                 (rc = pack_xformer(p + ".attentions." + std::to_string(j), &up_att[i][j], cfg.num_heads[nb - 1 - i],
                                    cfg.transformer_layers[nb - 1 - i]))) return rc;
         }
-        if (i != nb - 1 && (rc = ws.pack_conv(p + ".upsamplers.0.conv", &up_us[i]))) return rc;
+        if (i != nb - 1 && (rc = ws.pack_conv(p + ".upsamplers.0.conv", &up_us[i], true, true))) return rc;
     }
     if ((rc = ws.pack_norm("conv_norm_out", &norm_out))) return rc;
     if ((rc = ws.pack_conv("conv_out", &conv_out))) return rc;

@@ -132,7 +132,7 @@ int VAE::finalize() {
         d_up[i].resize((size_t)cfg.layers_per_block + 1);
         for (int j = 0; j < cfg.layers_per_block + 1; ++j)
             if ((rc = pack_resnet(p + ".resnets." + std::to_string(j), &d_up[i][j]))) return rc;
-        if (i != nb - 1 && (rc = ws.pack_conv(p + ".upsamplers.0.conv", &d_us[i]))) return rc;
+        if (i != nb - 1 && (rc = ws.pack_conv(p + ".upsamplers.0.conv", &d_us[i], true, true))) return rc;
     }
     if ((rc = ws.pack_norm("decoder.conv_norm_out", &d_norm_out))) return rc;
     if ((rc = ws.pack_conv("decoder.conv_out", &d_conv_out))) return rc;
