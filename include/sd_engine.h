@@ -222,6 +222,31 @@ int sd_unet_forward_cfg(sd_unet* u, const void* latents, const float* timesteps,
 /* 1 when the topology lets sd_unet_forward_cfg share: no per-sample additional embedding (text_time makes the time
  * embedding differ between the halves) and a transformer in down block 0.  Needs no device. */
 int sd_unet_cfg_share(const sd_unet_config* cfg);
+/* Perturbed-attention guidance (Ahn et al., "Self-Rectifying Diffusion Sampling with Perturbed-Attention Guidance", 2024;
+ * diffusers >= 0.30 StableDiffusionPAGPipeline, recalled).  sd_unet_set_pag_layers flags transformers by the site keys
+ * the engine names its Transformer2DModels with -- "down_blocks.i.attentions.j", "mid_block.attentions.0",
+ * "up_blocks.i.attentions.j" -- count = 0 clears every flag; a key that names no transformer of this topology:
+ * SD_ERR_INVALID, nothing changed.  The flags act in sd_unet_forward_pag only; every other forward ignores them.
+ *
+ * sd_unet_forward_pag: one forward on G + 1 groups of B images, G = 2 with cfg != 0 ([uncond ; text ; perturbed]), else 1
+ * ([text ; perturbed]), from the UN-duplicated latents (fp16(latents * in_scale), as sd_unet_forward_cfg):
+ *   latents [B,C,H,W] f16   timesteps [B] f32   ehs [G B,ehs_len,ctx] f16   add_text / add_time_ids: G B rows
+ *   out     [(G+1) B,Cout,H,W] f16
+ * The perturbed group takes the text group's latents, timesteps, ehs and added conditions; in every transformer block of
+ * a flagged transformer its attn1 is to_out(to_v(norm1(x))) -- the identity attention map: no softmax, no Q, no K.
+ * With share != 0 and the first flagged transformer (in execution order: down, mid, up) behind the network's first, the
+ * perturbed group does not exist until that transformer's first attn1: everything before runs on G B images (B up to the
+ * first cross-attention where sd_unet_forward_cfg would share) and one copy launch widens what the remainder reads.
+ * Otherwise -- share == 0, SD_NO_PAG_SHARE or SD_GN_CAT set in the environment, the first transformer flagged -- the
+ * engine duplicates up front and runs (G+1) B images throughout.  The text K / V are projected for G B rows and the
+ * perturbed group's are a copy (kept by sd_unet_text_kv_cache with the rest).  FreeU composes.
+ * SD_ERR_UNSUPPORTED, nothing launched: a ControlNet attached, an IP-Adapter attached at a non-zero scale, a DeepCache
+ * store / reuse mode, graph replay on, a UNet with time_cond_proj_dim (timestep_cond).  SD_ERR_INVALID: no flagged
+ * transformer, null or NaN arguments. */
+int sd_unet_set_pag_layers(sd_unet* u, const char* const* site_keys, int count);
+int sd_unet_forward_pag(sd_unet* u, const void* latents, const float* timesteps, const void* ehs, int ehs_len,
+                        const void* add_text, const float* add_time_ids, float in_scale, int cfg, int share, void* out,
+                        int B, int H, int W, void* stream);
 /* UNet2DConditionModel.enable_freeu(s1, s2, b1, b2) / disable_freeu() of diffusers 0.27.2 (enable = 0: the factors are
  * ignored and the forward is again exactly the plain one).  On, every resnet of up blocks 0 and 1 reads
  *   cat([hidden with its first C1 / 2 channels times b, fourier_filter(skip, threshold = 1, scale = s)])
@@ -426,6 +451,22 @@ int sd_cfg_linear_step(const void* noise_pred_2b, void* latents, float* hist_f32
 int sd_cfg_rescale_linear_step(const void* noise_pred_2b, void* latents, float* hist_f32, int B, int64_t n_per_sample,
                                float guidance_scale, float guidance_rescale, float c_x, float c_eps, float c_hist,
                                float h_x, float h_eps, float* factors_out, void* stream);
+
+/* Perturbed-attention guidance on the device step.  model_out f16 [rows * n] is [uncond ; text ; perturbed] (rows == 3)
+ * or [text ; perturbed] (rows == 2); per element, in fp32 with one rounding to f16:
+ *   e = fp16(fmaf(s, t - p, fmaf(g, t - u, u)))   (rows == 3; g = guidance_scale, s = pag_scale)
+ *   e = fp16(fmaf(s, t - p, t))                   (rows == 2; guidance_scale is not used)
+ * (s == 0 skips the outer fmaf: three rows at s = 0 give sd_cfg_linear_step's eps bit for bit.)
+ * sd_pag_linear_step: then exactly sd_cfg_linear_step's update on e (x0 = h_x x + h_eps e; x <- c_x x + c_eps e +
+ * c_hist hist; hist <- x0; hist_f32 nullable), one launch.  sd_pag_combine: out_f16 [n] <- e, the one-row model output
+ * that sd_lcm_step / sd_sched_affine_step then take with rows = 1 (two launches per step).
+ * 16-byte accesses when n % 8 == 0 and every pointer is 16-byte aligned, a scalar kernel otherwise.
+ * SD_ERR_INVALID (nothing is launched): rows not 2 or 3, n <= 0, a null model_out / latents / out_f16, a non-finite
+ * guidance_scale or pag_scale. */
+int sd_pag_linear_step(const void* model_out, int rows, void* latents, float* hist_f32, int64_t n, float guidance_scale,
+                       float pag_scale, float c_x, float c_eps, float c_hist, float h_x, float h_eps, void* stream);
+int sd_pag_combine(const void* model_out, int rows, void* out_f16, int64_t n, float guidance_scale, float pag_scale,
+                   void* stream);
 
 /* One step of a scheduler that adds noise (LCMScheduler.step; schedulers.py `fused_plan`), one launch:
  *   m   = model_out[i]                                   (rows == 1)

@@ -153,6 +153,8 @@ SIGNATURES = {
     "sd_unet_set_ip_adapter": (_I, [_P, _P]),
     "sd_unet_set_ip_adapter_scale": (_I, [_P, _F]),
     "sd_unet_set_freeu": (_I, [_P, _I, _F, _F, _F, _F]),
+    "sd_unet_set_pag_layers": (_I, [_P, _P, _I]),
+    "sd_unet_forward_pag": (_I, [_P, _P, _P, _P, _I, _P, _P, _F, _I, _I, _P, _I, _I, _I, _P]),
     "sd_unet_set_deep_cache": (_I, [_P, _I]),
     "sd_unet_deep_cache_mode": (_I, [_P, _I]),
     "sd_ip_adapter_create": (_I, [_P, _I, _I, C.POINTER(_P)]),
@@ -205,6 +207,8 @@ SIGNATURES = {
     "sd_inpaint_blend": (_I, [_P, _P, _P, _P, _F, _F, _I, _I, _I, _I, _P]),
     "sd_images_to_uint8": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "sd_cfg_linear_step": (_I, [_P, _P, _P, _I64, _F, _F, _F, _F, _F, _F, _P]),
+    "sd_pag_linear_step": (_I, [_P, _I, _P, _P, _I64, _F, _F, _F, _F, _F, _F, _F, _P]),
+    "sd_pag_combine": (_I, [_P, _I, _P, _I64, _F, _F, _P]),
     "sd_cfg_rescale_linear_step": (_I, [_P, _P, _P, _I, _I64, _F, _F, _F, _F, _F, _F, _F, _P, _P]),
     "sd_lcm_step": (_I, [_P, _I, _P, _P, _P, _I64, _F, _F, _F, _F, _F, _P]),
     "sd_sched_affine_step": (_I, [_P, _I, _P, _P, _P, _I64, _I64, _F, C.POINTER(SdStepPlan), _P]),

@@ -232,6 +232,19 @@ int sd_unet_forward_cfg(sd_unet* u, const void* latents, const float* timesteps,
                                static_cast<const half_t*>(image_embeds), image_embeds ? n_img : 0, in_scale, share != 0,
                                static_cast<half_t*>(out), B, H, W, static_cast<hipStream_t>(stream));
 }
+int sd_unet_set_pag_layers(sd_unet* u, const char* const* site_keys, int count) {
+    if (!u) { set_error("null handle"); return SD_ERR_INVALID; }
+    return u->impl.set_pag_layers(site_keys, count);
+}
+int sd_unet_forward_pag(sd_unet* u, const void* latents, const float* timesteps, const void* ehs, int ehs_len,
+                        const void* add_text, const float* add_time_ids, float in_scale, int cfg, int share, void* out,
+                        int B, int H, int W, void* stream) {
+    if (!u || !latents || !timesteps || !ehs || !out) { set_error("null argument"); return SD_ERR_INVALID; }
+    if (!(in_scale == in_scale)) { set_error("sd_unet_forward_pag: in_scale is NaN"); return SD_ERR_INVALID; }
+    return u->impl.forward_pag(static_cast<const half_t*>(latents), timesteps, static_cast<const half_t*>(ehs), ehs_len,
+                               static_cast<const half_t*>(add_text), add_time_ids, in_scale, cfg != 0, share != 0,
+                               static_cast<half_t*>(out), B, H, W, static_cast<hipStream_t>(stream));
+}
 int sd_unet_cfg_share(const sd_unet_config* cfg) { return cfg && sd::unet_cfg_share_eligible(*cfg) ? 1 : 0; }
 int sd_unet_set_ip_adapter_scale(sd_unet* u, float scale) {
     if (!u) { set_error("null handle"); return SD_ERR_INVALID; }
@@ -592,6 +605,24 @@ int sd_cfg_rescale_linear_step(const void* noise_pred_2b, void* latents, float* 
     return launch_cfg_rescale_linear(static_cast<const half_t*>(noise_pred_2b), static_cast<half_t*>(latents), hist_f32, B,
                                      (long)n_per_sample, guidance_scale, guidance_rescale, c_x, c_eps, c_hist, h_x, h_eps,
                                      factors_out, static_cast<hipStream_t>(stream));
+}
+int sd_pag_linear_step(const void* model_out, int rows, void* latents, float* hist_f32, int64_t n, float guidance_scale,
+                       float pag_scale, float c_x, float c_eps, float c_hist, float h_x, float h_eps, void* stream) {
+    if (!model_out || !latents || (rows != 2 && rows != 3) || n <= 0 || !std::isfinite(guidance_scale) || !std::isfinite(pag_scale)) {
+        set_error("sd_pag_linear_step: bad arguments (non-null model_out / latents, rows 2 or 3, n > 0, finite scales)");
+        return SD_ERR_INVALID;
+    }
+    return launch_pag_linear(static_cast<const half_t*>(model_out), rows, static_cast<half_t*>(latents), hist_f32, (long)n,
+                             guidance_scale, pag_scale, c_x, c_eps, c_hist, h_x, h_eps, static_cast<hipStream_t>(stream));
+}
+int sd_pag_combine(const void* model_out, int rows, void* out_f16, int64_t n, float guidance_scale, float pag_scale,
+                   void* stream) {
+    if (!model_out || !out_f16 || (rows != 2 && rows != 3) || n <= 0 || !std::isfinite(guidance_scale) || !std::isfinite(pag_scale)) {
+        set_error("sd_pag_combine: bad arguments (non-null model_out / out_f16, rows 2 or 3, n > 0, finite scales)");
+        return SD_ERR_INVALID;
+    }
+    return launch_pag_combine(static_cast<const half_t*>(model_out), rows, static_cast<half_t*>(out_f16), (long)n,
+                              guidance_scale, pag_scale, static_cast<hipStream_t>(stream));
 }
 int sd_lcm_step(const void* model_out, int rows, void* latents, const void* noise, void* denoised, int64_t n,
                 float guidance_scale, float d_x, float d_out, float p_den, float p_noise, void* stream) {

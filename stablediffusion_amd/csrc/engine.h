@@ -1,6 +1,7 @@
 // Host-side runtime of the denoise engine: device memory arena, packed-weight store and the
 // execution context shared by the UNet and VAE graphs.  Plain C++ + HIP runtime; no torch.
 #pragma once
+#include <functional>
 #include <map>
 #include <string>
 #include <unordered_map>
@@ -135,6 +136,20 @@ class WeightStore {
     int64_t packed_bytes_ = 0;
 };
 
+// Perturbed-attention guidance (UNet::forward_pag): the forward's N images are the Nq un-perturbed ones followed by the
+// perturbed group, N - Nq copies of the last N - Nq of them whose flagged transformers (Xformer::pag) replace the
+// self-attention map by the identity.  Until the first flagged transformer nothing tells the perturbed group from the
+// group it copies, so with late widening it does not exist before: every launch runs on Nq images inside buffers planned
+// for N, and run_xformer issues one row_dup launch at that transformer's first attn1 -- its own input plus whatever
+// `caller_segs` adds (UNet::run: tproj and the skips written and not yet read).
+struct PagState {
+    int N = 0, Nq = 0;
+    bool widened = false;               // the perturbed group's rows exist (from the start when duplicated up front)
+    int skips_done = 0;                 // skips the down path has written so far
+    int cats_consumed = 0;              // concatenations the up path has read so far
+    std::function<void(std::vector<RowDupSeg>&)> caller_segs;
+};
+
 // Execution context of one forward call.
 struct Ctx {
     Arena* arena;
@@ -153,7 +168,11 @@ struct Ctx {
     View ip_kv;
     int ip_T = 0;
     float ip_scale = 1.f;
+    PagState* pag = nullptr;            // forward_pag only
 };
+// images a launch over an N-image tensor runs on right now: all of them, or the un-perturbed ones in front while the
+// perturbed group of a forward_pag call does not exist yet
+inline int ctx_live(const Ctx& c, int N) { return c.pag && !c.pag->widened ? c.pag->Nq : N; }
 void ctx_gnpool_init(Ctx& c, int N, long HW_max, int G);
 GnStatBuf* ctx_gnbuf(Ctx& c);       // next ring slot with `st` cleared; nullptr when the pool is not set up
 

@@ -396,8 +396,9 @@ int launch_pack_conv(const half_t* w_oihw, half_t* wp, int O, int I, int KH, int
                      hipStream_t s);
 int launch_cfg_duplicate(const half_t* lat, half_t* out, long n_total, float scale, hipStream_t s);
 // Copies `rows` rows of row_bytes bytes (row stride ld_bytes) from src to dst for up to kRowDupMax tensors in one launch;
-// everything 16-byte aligned.  The shared CFG prefix widens its B-row tensors to 2B rows with it (dst = src + B rows).
-constexpr int kRowDupMax = 8;
+// everything 16-byte aligned.  The shared CFG prefix widens its B-row tensors to 2B rows with it (dst = src + B rows);
+// the late-widened perturbed group of forward_pag takes up to 12 skips (SD1.5) + tproj + the transformer's input.
+constexpr int kRowDupMax = 24;
 struct RowDupSeg {
     const void* src = nullptr;
     void* dst = nullptr;
@@ -422,6 +423,12 @@ int launch_scale_f16(half_t* x, long n, float scale, hipStream_t s);     // x *=
 int launch_image_to_uint8(const half_t* img, unsigned char* out, int B, int C, long HW, hipStream_t s);
 int launch_cfg_linear(const half_t* eps2b, half_t* lat, float* hist, long n, float g, float cx, float ce, float ch,
                       float hx, float he, hipStream_t s);
+// Perturbed-attention guidance: e = fp16(fma(s, t - p, fma(g, t - u, u))) of rows [u ; t ; p] (rows == 3) or
+// fp16(fma(s, t - p, t)) of rows [t ; p] (rows == 2; s == 0 skips the outer fma).  launch_pag_linear: launch_cfg_linear's
+// update on that e, one launch; launch_pag_combine: e itself into out [n].
+int launch_pag_linear(const half_t* model_out, int rows, half_t* lat, float* hist, long n, float g, float sp, float cx,
+                      float ce, float ch, float hx, float he, hipStream_t s);
+int launch_pag_combine(const half_t* model_out, int rows, half_t* out, long n, float g, float sp, hipStream_t s);
 // den = dx x + dout m, x <- pden den + pnoise noise (m: model_out, or its CFG combine when rows == 2); noise / denoised
 // nullable.  The scheduler step of LCMScheduler in one launch.
 int launch_lcm_step(const half_t* model_out, int rows, half_t* lat, const half_t* noise, half_t* denoised, long n, float g,

@@ -663,6 +663,73 @@ __global__ __launch_bounds__(256) void rs_apply_kernel(const half_t* __restrict_
     }
 }
 
+// ---- perturbed-attention guidance (Ahn et al. 2024) in front of the same linear update ----
+//   rows [u ; t ; p]: e = fp16(fma(s, t - p, fma(g, t - u, u)));  rows [t ; p]: e = fp16(fma(s, t - p, t))
+// (fp32, one rounding to fp16; s == 0 skips the outer fma, so three rows at s = 0 give cfg_linear_kernel's e bit for bit
+// whatever the signs of its zeros), then cfg_linear_kernel's update with its roundings (rs_axpby).  STEP = false writes e
+// itself: the one-row model output the LCM / affine step entries then take.  VEC: n % 8 == 0 and 16-byte aligned bases.
+template <int ROWS>
+__device__ __forceinline__ float pag_eps(float a, float b, float c, float g, float sp) {
+    // ROWS == 3: (a, b, c) = (u, t, p);  ROWS == 2: (a, b) = (t, p)
+    const float t = ROWS == 3 ? b : a, p = ROWS == 3 ? c : b;
+    float e = ROWS == 3 ? __builtin_fmaf(g, b - a, a) : a;
+    if (sp != 0.f) e = __builtin_fmaf(sp, t - p, e);
+    return (float)(half_t)e;
+}
+template <int ROWS, bool VEC, bool STEP>
+__global__ __launch_bounds__(256) void pag_step_kernel(const half_t* __restrict__ mo, half_t* __restrict__ x,
+                                                       float* __restrict__ h, long n, float g, float sp, float cx, float ce,
+                                                       float ch, float hx, float he) {
+    if (VEC) {
+        const long i = ((long)blockIdx.x * 256 + threadIdx.x) * 8;
+        if (i >= n) return;
+        const h8 va = *reinterpret_cast<const h8*>(mo + i);
+        const h8 vb = *reinterpret_cast<const h8*>(mo + n + i);
+        h8 vc = vb, vx = vb;
+        if (ROWS == 3) vc = *reinterpret_cast<const h8*>(mo + 2 * n + i);
+        if (STEP) vx = *reinterpret_cast<const h8*>(x + i);
+        float hv[8], x0[8];
+        if (STEP && h) {
+            const f4 h0 = *reinterpret_cast<const f4*>(h + i), h1 = *reinterpret_cast<const f4*>(h + i + 4);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { hv[j] = h0[j]; hv[j + 4] = h1[j]; }
+        }
+        h8 o;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const float e = pag_eps<ROWS>((float)va[j], (float)vb[j], (float)vc[j], g, sp);
+            if (!STEP) { o[j] = (half_t)e; continue; }
+            const float xf = (float)vx[j];
+            float out = rs_axpby(cx, xf, ce, e);
+            if (h) {
+                out = __builtin_fmaf(ch, hv[j], out);
+                x0[j] = rs_axpby(hx, xf, he, e);
+            }
+            o[j] = (half_t)out;
+        }
+        *reinterpret_cast<h8*>(x + i) = o;
+        if (STEP && h) {
+            f4 h0, h1;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { h0[j] = x0[j]; h1[j] = x0[j + 4]; }
+            *reinterpret_cast<f4*>(h + i) = h0;
+            *reinterpret_cast<f4*>(h + i + 4) = h1;
+        }
+    } else {
+        const long i = (long)blockIdx.x * 256 + threadIdx.x;
+        if (i >= n) return;
+        const float e = pag_eps<ROWS>((float)mo[i], (float)mo[n + i], ROWS == 3 ? (float)mo[2 * n + i] : 0.f, g, sp);
+        if (!STEP) { x[i] = (half_t)e; return; }
+        const float xf = (float)x[i];
+        float out = rs_axpby(cx, xf, ce, e);
+        if (h) {
+            out = __builtin_fmaf(ch, h[i], out);
+            h[i] = rs_axpby(hx, xf, he, e);
+        }
+        x[i] = (half_t)out;
+    }
+}
+
 // convert_pt_to_numpy (runpod-worker/handler_logic.py:21-29) on the device: the reference runs
 // (x / 2 + 0.5).clamp(0, 1), permute to HWC, * 255, .to(uint8) on the fp16 image tensor, i.e. every
 // step rounds to fp16 and the final cast truncates.  Same op order and roundings here, so the bytes
@@ -1131,6 +1198,26 @@ int launch_lcm_step(const half_t* model_out, int rows, half_t* lat, const half_t
 #undef SD_LCM_LAUNCH
     SD_HIP_CHECK(hipGetLastError());
     return 0;
+}
+template <bool STEP>
+static int launch_pag_step(const half_t* mo, int rows, half_t* x, float* hist, long n, float g, float sp, float cx, float ce,
+                           float ch, float hx, float he, hipStream_t s) {
+    const bool vec = vec8_ok(n, mo, x, hist);
+    const dim3 grid = grid1d(vec ? n / 8 : n);
+#define SD_PAG_LAUNCH(R, V) \
+    hipLaunchKernelGGL((pag_step_kernel<R, V, STEP>), grid, dim3(256), 0, s, mo, x, hist, n, g, sp, cx, ce, ch, hx, he)
+    if (rows == 3) { if (vec) SD_PAG_LAUNCH(3, true); else SD_PAG_LAUNCH(3, false); }
+    else { if (vec) SD_PAG_LAUNCH(2, true); else SD_PAG_LAUNCH(2, false); }
+#undef SD_PAG_LAUNCH
+    SD_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+int launch_pag_linear(const half_t* model_out, int rows, half_t* lat, float* hist, long n, float g, float sp, float cx,
+                      float ce, float ch, float hx, float he, hipStream_t s) {
+    return launch_pag_step<true>(model_out, rows, lat, hist, n, g, sp, cx, ce, ch, hx, he, s);
+}
+int launch_pag_combine(const half_t* model_out, int rows, half_t* out, long n, float g, float sp, hipStream_t s) {
+    return launch_pag_step<false>(model_out, rows, out, nullptr, n, g, sp, 0.f, 0.f, 0.f, 0.f, 0.f, s);
 }
 int launch_sched_affine_step(const half_t* model_out, int rows, half_t* lat, const half_t* noise, float* bank, long stride,
                              long n, float g, const StepRows& p, hipStream_t s) {

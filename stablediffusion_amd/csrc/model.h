@@ -32,6 +32,9 @@ struct Xformer {
     // that block's ff2 and of pout, and run_xformer_tail issues one GEMM over [g | t3] where two ran.
     bool pout_fold = false;
     ConvW ff2p;
+    // perturbed-attention guidance (sd_unet_set_pag_layers): in a forward_pag call the perturbed group's attn1 of every
+    // block here is to_out(to_v(norm1(x))), the identity attention map
+    bool pag = false;
 };
 struct VaeAttn {
     NormW gn;
@@ -212,9 +215,27 @@ struct CfgIn {
     float in_scale = 1.f;
 };
 
+// A forward_pag call: `groups` un-perturbed groups (2: [uncond ; text], 1: [text]) followed by the perturbed copy of the
+// last one; late = that copy is made at the first flagged transformer (PagState), not up front.
+struct PagIn {
+    int groups = 2;
+    bool late = false;
+};
+
 struct UNet : Encoder {
     explicit UNet(const sd_unet_config& c);
     int finalize();
+    // Perturbed-attention guidance.  One forward on [uncond ; text ; perturbed] (cfg) or [text ; perturbed] from B
+    // latents and timesteps; ehs / add_text / add_time_ids hold the un-perturbed groups' rows, the perturbed group takes
+    // the text group's.  share: widen to the perturbed group at the first flagged transformer where it is not the
+    // network's first (after the CFG-shared start where forward_cfg would take it); otherwise, and under
+    // SD_NO_PAG_SHARE, duplicate up front.
+    int forward_pag(const half_t* latents, const float* timesteps, const half_t* ehs, int L, const half_t* add_text,
+                    const float* add_time_ids, float in_scale, bool cfg_on, bool share, half_t* out, int B, int H, int W,
+                    hipStream_t stream);
+    int set_pag_layers(const char* const* site_keys, int count);
+    // every transformer in execution order with its site key ("down_blocks.i.attentions.j", "mid_block.attentions.0", ...)
+    std::vector<std::pair<std::string, Xformer*>> xformer_sites();
     // The forward on cat([latents * in_scale] * 2) with both halves at the same timesteps [B]: ehs / image_embeds / out
     // hold 2B rows, negative half first.  Runs the CFG-shared prefix once per latent when `share`, the topology and the
     // engine's state allow (unet_cfg_share_eligible, no graph replay, no ControlNet, SD_GN_CAT and SD_NO_CFG_SHARE unset);
@@ -229,7 +250,7 @@ struct UNet : Encoder {
                 const half_t* add_text, const float* add_time_ids, half_t* out, int B, int H, int W,
                 hipStream_t stream, const half_t* image_embeds = nullptr, int n_img = 0,
                 const half_t* control = nullptr, int n_ctrl = 0, float cn_scale = 0.f, const CfgIn* cfg_in = nullptr,
-                const float* tcond = nullptr);
+                const float* tcond = nullptr, const PagIn* pag = nullptr);
     void set_ip_adapter(IPAdapter* a);
     void set_controlnet(ControlNet* n);
 
@@ -240,6 +261,7 @@ struct UNet : Encoder {
     long planned_key[3] = {-1, -1, -1};
     long planned_cn[3] = {-1, -1, -1};
     int planned_depth[3] = {0, 0, 0};
+    int planned_pag = 0;
     void reset_plans() { for (int m = 0; m < 3; ++m) planned_key[m] = planned_cn[m] = -1; }
 
     // ---- optional hipGraph replay of the whole forward (sd_unet_use_graph) ----
@@ -268,6 +290,7 @@ struct UNet : Encoder {
     size_t kv_cap = 0;
     const half_t* kv_src = nullptr;
     int kv_B = 0, kv_L = 0;
+    int kv_pag = 0;                     // images of the perturbed group whose copy the cache holds (forward_pag), else 0
 
     // ---- IP-Adapter (sd_unet_set_ip_adapter): nullptr = plain cross-attention, the forward as without the feature.
     // Its stacked K / V of the image tokens follow the text K / V's cache rules: kept across the forwards of one loop
@@ -324,7 +347,8 @@ struct UNet : Encoder {
     int run(Ctx& c, const half_t* sample, const float* timesteps, const half_t* ehs, int L,
             const half_t* add_text, const float* add_time_ids, half_t* out, int B, int H, int W,
             const half_t* image_embeds = nullptr, int n_img = 0, const half_t* control = nullptr, int n_ctrl = 0,
-            float cn_scale = 0.f, const CfgIn* cfg_in = nullptr, const float* tcond = nullptr, int dc = 0);
+            float cn_scale = 0.f, const CfgIn* cfg_in = nullptr, const float* tcond = nullptr, int dc = 0,
+            const PagIn* pag = nullptr);
     // ControlNet step of run(): its hidden tensors into sites / mid (allocated by the caller)
     int run_controlnet(Ctx& c, const half_t* sample, const float* timesteps, const half_t* ehs, int L,
                        const half_t* add_text, const float* add_time_ids, int B, int H, int W, const half_t* control,

@@ -547,7 +547,13 @@ void run_xformer(Ctx& c, const Xformer& t, View x, int N, int H, int W, View out
     const bool fold = !t.blocks.empty() && t.blocks[0].fold;
     // Shared CFG prefix: x holds N / 2 images, and so does everything up to the first block's attn2 query.  Buffers keep
     // their N-image size (the arena plan is the unshared forward's); Np / Mp are what the prefix launches run on.
-    int Np = share ? N / 2 : N;
+    // forward_pag: Nl images exist on entry (ctx_live); the buffers are N images wide all the same.
+    PagState* pg = c.pag;
+    const bool perturb = pg && t.pag;
+    int Nl = ctx_live(c, N);
+    long Ml = (long)Nl * T;
+    if (perturb && share) { set_error("run_xformer: a perturbed transformer inside the shared CFG prefix"); c.err = 2; return; }
+    int Np = share ? Nl / 2 : Nl;
     long Mp = (long)Np * T;
     View hn(a.alloc_h(M * C), C, C);
     op_groupnorm(c, t.gn, x, hn, Np, T, G, 1e-6f, 0, x_stats);
@@ -580,9 +586,60 @@ void run_xformer(Ctx& c, const Xformer& t, View x, int N, int H, int W, View out
             op_conv(c, b.qkv, n, Np, H, W, qkv);
         }
         View att(a.alloc_h(M * C), C, C);
-        op_attention(c, qkv.slice(0, C), qkv.slice(C, C), qkv.slice(2 * C, C), att, Np, T, T, t.heads, d, 0, 1);
         View t2(a.alloc_h(M * C), C, C);
-        op_conv(c, b.out1, att, Np, H, W, t2, 1, 0, nullptr, 0, &cur, 0, -1, 0, fold ? &f_t2 : nullptr);
+        if (!perturb) {
+            op_attention(c, qkv.slice(0, C), qkv.slice(C, C), qkv.slice(2 * C, C), att, Np, T, T, t.heads, d, 0, 1);
+            op_conv(c, b.out1, att, Np, H, W, t2, 1, 0, nullptr, 0, &cur, 0, -1, 0, fold ? &f_t2 : nullptr);
+        } else {
+            // Perturbed self-attention: the attention and its out-projection on the Nq un-perturbed images; the perturbed
+            // group's map is the identity, so its out-projection reads the V columns of qkv in place (no attention launch,
+            // no copy; its Q / K columns were computed with the others' and are never read).  Before the widening the
+            // group is still its source: V and the residual are the source images' rows.
+            const int Nq = pg->Nq, Ng = N - Nq;
+            const long Mq = (long)Nq * T, src0 = pg->widened ? Mq : (long)(Nq - Ng) * T;
+            op_attention(c, qkv.slice(0, C), qkv.slice(C, C), qkv.slice(2 * C, C), att, Nq, T, T, t.heads, d, 0, 1);
+            RowStat sa, sb;
+            ConvFuse fa = f_t2, fb = f_t2;
+            sa.p = st_t2.p;
+            fa.stat_out = &sa; fb.stat_out = &sb;
+            op_conv(c, b.out1, att, Nq, H, W, t2, 1, 0, nullptr, 0, &cur, 0, -1, 0, fold ? &fa : nullptr);
+            sb.p = st_t2.p ? st_t2.p + Mq * sa.parts * 2 : nullptr;
+            const View vp(qkv.p + src0 * qkv.ld + 2 * C, qkv.ld, C), rp(cur.p + src0 * cur.ld, cur.ld, C);
+            op_conv(c, b.out1, vp, Ng, H, W, View(t2.p + Mq * t2.ld, t2.ld, C), 1, 0, nullptr, 0, &rp, 0, -1, 0, fold ? &fb : nullptr);
+            if (fold) {
+                // the row statistics of t2 across the two launches: side by side when both picked one layout, else one
+                // statistics pass over all N images
+                st_t2.parts = sa.parts; st_t2.width = sa.width;
+                if (sa.parts != sb.parts || sa.width != sb.width) {
+                    st_t2.parts = 1; st_t2.width = C;
+                    if (!c.dry && !c.err) {
+                        prof_open(c.stream, "row_stats_kernel", 0.0, 2.0 * M * C);
+                        c.err = launch_row_stats(t2.p, t2.ld, st_t2.p, M, C, c.stream);
+                        prof_close(c.stream);
+                    }
+                }
+            }
+            if (!pg->widened) {
+                // from here on the perturbed group differs: give it rows in everything the remainder reads -- this
+                // transformer's input (proj_out's residual) and the caller's tensors -- in one launch.  (cur and qkv were
+                // read through the source rows above and are dead after this block's out1.)
+                std::vector<RowDupSeg> segs;
+                if (pg->caller_segs) pg->caller_segs(segs);
+                RowDupSeg g;
+                g.src = x.p + src0 * x.ld; g.dst = x.p + Mq * x.ld;
+                g.ld_bytes = x.ld * 2; g.row_bytes = (long)x.C * 2; g.rows = (long)Ng * T;
+                segs.push_back(g);
+                if (!c.dry && !c.err) {
+                    double bytes = 0;
+                    for (const RowDupSeg& sg : segs) bytes += 2.0 * sg.rows * sg.row_bytes;
+                    prof_open(c.stream, "row_dup_kernel", 0.0, bytes);
+                    c.err = launch_row_dup(segs.data(), (int)segs.size(), c.stream);
+                    prof_close(c.stream);
+                }
+                pg->widened = true;
+                Nl = Np = N; Ml = Mp = M;
+            }
+        }
         View q(a.alloc_h(M * C), C, C);
         if (fold) {
             op_conv(c, b.q2, t2, Np, H, W, q, 1, 0, nullptr, 0, nullptr, 0, -1, 0, &f_ln2);
@@ -590,7 +647,7 @@ void run_xformer(Ctx& c, const Xformer& t, View x, int N, int H, int W, View out
             op_layernorm(c, b.ln2, t2, n, Mp, 1e-5f);
             op_conv(c, b.q2, n, Np, H, W, q);
         }
-        if (Np != N) {
+        if (Np != Nl) {
             // the text enters here: from now on the halves differ.  Widen what the N-image remainder reads -- the
             // query, t2 (out2's residual), x (proj_out's residual) and the caller's tensors -- in one launch.
             std::vector<RowDupSeg> segs = share->segs;
@@ -607,35 +664,35 @@ void run_xformer(Ctx& c, const Xformer& t, View x, int N, int H, int W, View out
                 c.err = launch_row_dup(segs.data(), (int)segs.size(), c.stream);
                 prof_close(c.stream);
             }
-            Np = N; Mp = M;
+            Np = Nl; Mp = Ml;
         }
         // IP-Adapter attached: text and image attention in one launch (scale 0: the text attention alone, as without one)
         if (c.ip_kv.p && c.ip_scale != 0.f)
             op_ip_attention(c, q, text_kv.slice(b.kv_off, C), text_kv.slice(b.kv_off + C, C), c.ip_kv.slice(b.ip_kv_off, C),
-                            c.ip_kv.slice(b.ip_kv_off + C, C), att, N, T, L, c.ip_T, t.heads, d, c.ip_scale);
+                            c.ip_kv.slice(b.ip_kv_off + C, C), att, Nl, T, L, c.ip_T, t.heads, d, c.ip_scale);
         else
-            op_attention(c, q, text_kv.slice(b.kv_off, C), text_kv.slice(b.kv_off + C, C), att, N, T, L, t.heads, d, 0, 1);
+            op_attention(c, q, text_kv.slice(b.kv_off, C), text_kv.slice(b.kv_off + C, C), att, Nl, T, L, t.heads, d, 0, 1);
         View t3 = more ? View(a.alloc_h(M * C), C, C) : xformer_tail_t3(a, t, M);
-        op_conv(c, b.out2, att, N, H, W, t3, 1, 0, nullptr, 0, &t2, 0, -1, 0, fold ? &f_t3 : nullptr);
+        op_conv(c, b.out2, att, Nl, H, W, t3, 1, 0, nullptr, 0, &t2, 0, -1, 0, fold ? &f_t3 : nullptr);
         if (more) {
             // norm3 -> GEGLU feed-forward -> + residual: the projection with its GEGLU epilogue and the output linear with
             // its residual epilogue
             View g(a.alloc_h(M * 4 * C), 4 * C, 4 * C);
             if (fold) {
-                op_conv(c, b.ff1, t3, N, H, W, g, 1, 0, nullptr, 0, nullptr, 1, -1, 0, &f_ln3);
+                op_conv(c, b.ff1, t3, Nl, H, W, g, 1, 0, nullptr, 0, nullptr, 1, -1, 0, &f_ln3);
             } else {
-                op_layernorm(c, b.ln3, t3, n, M, 1e-5f);
-                op_conv(c, b.ff1, n, N, H, W, g, 1, 0, nullptr, 0, nullptr, 1);
+                op_layernorm(c, b.ln3, t3, n, Ml, 1e-5f);
+                op_conv(c, b.ff1, n, Nl, H, W, g, 1, 0, nullptr, 0, nullptr, 1);
             }
-            op_conv(c, b.ff2, g, N, H, W, nxt, 1, 0, nullptr, 0, &t3, 0, -1, 0, fold ? &f_cur : nullptr);
+            op_conv(c, b.ff2, g, Nl, H, W, nxt, 1, 0, nullptr, 0, &t3, 0, -1, 0, fold ? &f_cur : nullptr);
         } else {
             // the last block: its feed-forward and proj_out
-            run_xformer_tail(c, t, t3, st_t3, n, nxt, x, N, H, W, out, fo);
+            run_xformer_tail(c, t, t3, st_t3, n, nxt, x, Nl, H, W, out, fo);
         }
         a.release(mb);
         View tmp = cur; cur = nxt; nxt = tmp;
     }
-    if (t.blocks.empty()) op_conv(c, t.pout, cur, N, H, W, out, 1, 0, nullptr, 0, &x, 0, -1, 0, &fo);
+    if (t.blocks.empty()) op_conv(c, t.pout, cur, Nl, H, W, out, 1, 0, nullptr, 0, &x, 0, -1, 0, &fo);
     if (out_stats) *out_stats = fo.gn_out;
     a.release(mk);
 }
@@ -806,15 +863,18 @@ View Encoder::run_down(Ctx& c, View x, GnStatBuf*& xs, int B, int& h, int& w, Vi
                 View tmp(a.alloc_h((long)B * h * w * r.cout), r.cout, r.cout);
                 GnStatBuf* rs = nullptr;
                 const CfgShare* sh = (i == 0 && j == 0) ? share : nullptr;
-                run_resnet(c, r, x, sh ? B / 2 : B, h, w, tmp, G, eps, tproj, temb_total, xs, &rs);
+                const int Bl = ctx_live(c, B);
+                run_resnet(c, r, x, sh ? Bl / 2 : Bl, h, w, tmp, G, eps, tproj, temb_total, xs, &rs);
                 View dst = skip_view(skip_i);
+                if (c.pag) c.pag->skips_done = skip_i;
                 run_xformer(c, down_att[i][j], tmp, B, h, w, dst, G, text_kv, L, rs, &xs, skip_stat(skip_i, (long)h * w, r.cout),
                             0, sh);
                 a.release(mk);
                 x = dst;
             } else {
                 View dst = skip_view(skip_i);
-                run_resnet(c, r, x, B, h, w, dst, G, eps, tproj, temb_total, xs, &xs, 1.f, skip_stat(skip_i, (long)h * w, r.cout));
+                run_resnet(c, r, x, ctx_live(c, B), h, w, dst, G, eps, tproj, temb_total, xs, &xs, 1.f,
+                           skip_stat(skip_i, (long)h * w, r.cout));
                 x = dst;
             }
             ++skip_i;
@@ -825,7 +885,7 @@ View Encoder::run_down(Ctx& c, View x, GnStatBuf*& xs, int B, int& h, int& w, Vi
             f.gn_out = skip_stat(skip_i, (long)(h / 2) * (w / 2), down_ds[i].cout);
             View dst = skip_view(skip_i++);
             f.gn_groups = G;
-            op_conv(c, down_ds[i], x, B, h, w, dst, 2, 0, nullptr, 0, nullptr, 0, -1, 0, &f);
+            op_conv(c, down_ds[i], x, ctx_live(c, B), h, w, dst, 2, 0, nullptr, 0, nullptr, 0, -1, 0, &f);
             xs = f.gn_out;
             h /= 2; w /= 2;
             x = dst;
@@ -846,9 +906,9 @@ void Encoder::run_mid(Ctx& c, View x, GnStatBuf* xs, int B, int h, int w, View t
     const long M = (long)B * h * w;
     View m0(a.alloc_h(M * C), C, C), m1(a.alloc_h(M * C), C, C);
     GnStatBuf *s0 = nullptr, *s1 = nullptr;
-    run_resnet(c, mid_r0, x, B, h, w, m0, G, eps, tproj, temb_total, xs, &s0);
+    run_resnet(c, mid_r0, x, ctx_live(c, B), h, w, m0, G, eps, tproj, temb_total, xs, &s0);
     run_xformer(c, mid_att, m0, B, h, w, m1, G, text_kv, L, s0, &s1);
-    run_resnet(c, mid_r1, m1, B, h, w, dst, G, eps, tproj, temb_total, s1);   // output joins a concat: no consumer
+    run_resnet(c, mid_r1, m1, ctx_live(c, B), h, w, dst, G, eps, tproj, temb_total, s1);   // output joins a concat: no consumer
 }
 
 int Encoder::num_skips() const { return 1 + cfg.num_blocks * cfg.layers_per_block + (cfg.num_blocks - 1); }
@@ -856,7 +916,7 @@ int Encoder::num_skips() const { return 1 + cfg.num_blocks * cfg.layers_per_bloc
 int UNet::run(Ctx& c, const half_t* sample, const float* timesteps, const half_t* ehs, int L,
               const half_t* add_text, const float* add_time_ids, half_t* out, int B, int H, int W,
               const half_t* image_embeds, int n_img, const half_t* control, int n_ctrl, float cn_scale, const CfgIn* cfg_in,
-              const float* tcond, int dc) {
+              const float* tcond, int dc, const PagIn* pag) {
     Arena& a = *c.arena;
     const int nb = cfg.num_blocks;
     const int* boc = cfg.block_out_channels;
@@ -869,7 +929,17 @@ int UNet::run(Ctx& c, const half_t* sample, const float* timesteps, const half_t
     // ---- shared CFG prefix (forward_cfg): B = 2 Bp images from Bp latents and Bp timesteps.  conv_in, the first
     //      resnet and the first transformer up to its attn2 query run on Bp images; run_xformer widens what the rest
     //      reads.  The scaled latents get their buffer whatever the scale, so every step of a loop keeps one plan. ----
-    const int Bp = cfg_in ? B / 2 : B;
+    // ---- perturbed-attention guidance (forward_pag): the last Ng of the B images are the perturbed group, copies of the
+    //      Ng in front of them (the text group).  ehs / add_text / add_time_ids hold Nq = B - Ng rows.  Late: the group
+    //      does not exist until the first flagged transformer (PagState); otherwise `sample` holds all B images. ----
+    PagState pgs;
+    const int Ng = pag ? B / (pag->groups + 1) : 0, Nq = B - Ng;
+    if (pag) {
+        pgs.N = B; pgs.Nq = Nq;
+        pgs.widened = !pag->late;
+        c.pag = &pgs;
+    }
+    const int Bp = cfg_in ? Nq / 2 : Nq;
     CfgShare share;
     if (cfg_in) {
         const long n = (long)Bp * cfg.in_channels * H * W;
@@ -891,11 +961,33 @@ int UNet::run(Ctx& c, const half_t* sample, const float* timesteps, const half_t
     }
 
     // ---- text K/V of every cross-attention block in one GEMM: [B*L, ctx] x [ctx, sum 2C] ----
+    //      (forward_pag: projected for the Nq rows of ehs; the perturbed group gets a copy of the text group's rows, which
+    //      the cache keeps with the rest.  That copy, and up front the group's tproj rows, are one row_dup launch here.)
     const bool kv_cached = kv_cache_on && !graph_enabled && kv_cache != nullptr;
     View text_kv(kv_cached ? kv_cache : a.alloc_h((long)B * L * kv_total), kv_total, kv_total);
-    if (!(kv_cached && kv_valid && kv_src == ehs && kv_B == B && kv_L == L)) {
-        op_conv(c, kv_all, View(const_cast<half_t*>(ehs), cfg.cross_attention_dim, cfg.cross_attention_dim), B, L, 1, text_kv);
-        if (kv_cached && go && !c.err) { kv_valid = true; kv_src = ehs; kv_B = B; kv_L = L; }
+    std::vector<RowDupSeg> pag_now;
+    if (!(kv_cached && kv_valid && kv_src == ehs && kv_B == B && kv_L == L && kv_pag == Ng)) {
+        op_conv(c, kv_all, View(const_cast<half_t*>(ehs), cfg.cross_attention_dim, cfg.cross_attention_dim), Nq, L, 1, text_kv);
+        if (kv_cached && go && !c.err) { kv_valid = true; kv_src = ehs; kv_B = B; kv_L = L; kv_pag = Ng; }
+        if (pag) {
+            RowDupSeg g;
+            g.src = text_kv.p + (long)(Nq - Ng) * L * kv_total; g.dst = text_kv.p + (long)Nq * L * kv_total;
+            g.ld_bytes = g.row_bytes = (long)Ng * L * kv_total * 2; g.rows = 1;
+            pag_now.push_back(g);
+        }
+    }
+    RowDupSeg pag_tproj;
+    if (pag) {
+        pag_tproj.src = tproj + (long)(Nq - Ng) * temb_total; pag_tproj.dst = tproj + (long)Nq * temb_total;
+        pag_tproj.ld_bytes = pag_tproj.row_bytes = (long)Ng * temb_total * 4; pag_tproj.rows = 1;
+        if (!pag->late) pag_now.push_back(pag_tproj);
+    }
+    if (!pag_now.empty() && go && !c.err) {
+        double bytes = 0;
+        for (const RowDupSeg& g : pag_now) bytes += 2.0 * g.rows * g.row_bytes;
+        prof_open(s, "row_dup_kernel", 0.0, bytes);
+        c.err = launch_row_dup(pag_now.data(), (int)pag_now.size(), s);
+        prof_close(s);
     }
 
     // ---- IP-Adapter: image tokens = LayerNorm(image_embeds W_proj^T + b), or the Resampler's (IPAdapter::run_tokens),
@@ -1007,8 +1099,27 @@ int UNet::run(Ctx& c, const half_t* sample, const float* timesteps, const half_t
     // ---- conv_in: one launch straight from the NCHW latents (edge.hip); otherwise (inpainting's 9 channels, odd maps)
     //      im2col into a 64-wide K, then the GEMM kernel ----
     int h = H, w = W;
-    run_conv_in(c, sample, Bp, H, W, skip_view(skip_i), skip_stat(skip_i, (long)H * W, boc[0]), nullptr, &xs);
+    run_conv_in(c, sample, cfg_in ? Bp : ctx_live(c, B), H, W, skip_view(skip_i), skip_stat(skip_i, (long)H * W, boc[0]),
+                nullptr, &xs);
     View x = skip_view(skip_i++);
+    if (pag) {
+        // what the late widening copies besides the flagged transformer's own input: tproj, and every skip that is
+        // written and still to be read by the up path
+        pgs.skips_done = 1;
+        pgs.caller_segs = [&](std::vector<RowDupSeg>& v) {
+            v.push_back(pag_tproj);
+            const int n = std::min(pgs.skips_done, nskip - pgs.cats_consumed);
+            for (int si = 0; si < n; ++si) {
+                const Cat& ct = cats[(size_t)(nskip - 1 - si)];
+                const View sv = skip_view(si);
+                const long px = (long)ct.h * ct.w;
+                RowDupSeg g;
+                g.src = sv.p + (Nq - Ng) * px * sv.ld; g.dst = sv.p + Nq * px * sv.ld;
+                g.ld_bytes = sv.ld * 2; g.row_bytes = (long)sv.C * 2; g.rows = Ng * px;
+                v.push_back(g);
+            }
+        };
+    }
     if (cfg_in) {
         // skip 0 is read again by the last up resnet, on all B images.  (Its GroupNorm summaries are not: their only
         // reader besides the first resnet is the SD_GN_CAT merge, which forward_cfg does not share under.)
@@ -1025,6 +1136,7 @@ int UNet::run(Ctx& c, const half_t* sample, const float* timesteps, const half_t
                  reuse ? dc_depth : -1);
 
     // ---- mid block ----
+    if (pag) pgs.skips_done = nskip;
     if (!reuse) run_mid(c, x, xs, B, h, w, text_kv, L, tproj, View(cats[0].p, cats[0].c1 + cats[0].c2, cats[0].c1));
 
     // ---- ControlNet residuals: skip_i += s (h_i W_i^T + b_i) in the skip half of every concatenation and
@@ -1056,7 +1168,8 @@ int UNet::run(Ctx& c, const half_t* sample, const float* timesteps, const half_t
     int hid_groups = 0;
     // (with a ControlNet the skips' summaries predate the residual add: norm1 always runs its own statistics pass)
     static const bool no_cat_env = getenv("SD_GN_CAT") == nullptr;
-    const bool no_cat_stats = no_cat_env || use_cn;
+    // (forward_pag likewise: a skip's summaries may cover fewer images than the concatenation that reads it)
+    const bool no_cat_stats = no_cat_env || use_cn || pag;
     for (int i = 0; i < nb; ++i) {
         for (int j = 0; j < cfg.layers_per_block + 1; ++j, ++k) {
             if (reuse && k < dc_k) continue;     // (h, w stayed H, W: the layers that remain are the last block's)
@@ -1070,10 +1183,12 @@ int UNet::run(Ctx& c, const half_t* sample, const float* timesteps, const half_t
             // and nobody emits summaries into a hidden half that FreeU will rescale (fu_next).
             const bool fu = freeu_on && i < 2;
             const bool fu_next = freeu_on && (last_in_block ? i + 1 : i) < 2;
+            const int Bl = ctx_live(c, B);      // images this layer's concatenation holds
+            if (pag) pgs.cats_consumed = k + 1;
             if (fu && go && !c.err) {
-                const double elems = (double)B * h * w * (ct.c1 / 2 + ct.c2);
-                prof_open(s, "freeu_kernel", 16.0 * B * h * w * ct.c2, 4.0 * elems);
-                c.err = launch_freeu(xin.p, xin.ld, B, h, w, ct.c1, ct.c2, i == 0 ? freeu_b1 : freeu_b2,
+                const double elems = (double)Bl * h * w * (ct.c1 / 2 + ct.c2);
+                prof_open(s, "freeu_kernel", 16.0 * Bl * h * w * ct.c2, 4.0 * elems);
+                c.err = launch_freeu(xin.p, xin.ld, Bl, h, w, ct.c1, ct.c2, i == 0 ? freeu_b1 : freeu_b2,
                                      i == 0 ? freeu_s1 : freeu_s2, s);
                 prof_close(s);
             }
@@ -1121,14 +1236,14 @@ int UNet::run(Ctx& c, const half_t* sample, const float* timesteps, const half_t
             if (cfg.up_block_has_attn[i]) {
                 View tmp(a.alloc_h((long)B * h * w * r.cout), r.cout, r.cout);
                 GnStatBuf* rs = nullptr;
-                run_resnet(c, r, xin, B, h, w, tmp, G, eps, tproj, temb_total, xin_stats, &rs);
+                run_resnet(c, r, xin, Bl, h, w, tmp, G, eps, tproj, temb_total, xin_stats, &rs);
                 if (last) run_xformer(c, up_att[i][j], tmp, B, h, w, dst, G, text_kv, L, rs, &xs);
                 else if (hid_here) run_xformer(c, up_att[i][j], tmp, B, h, w, dst, G, text_kv, L, rs, &outp, &hid, nx_groups);
                 else run_xformer(c, up_att[i][j], tmp, B, h, w, dst, G, text_kv, L, rs, nullptr);
             } else {
-                if (last) run_resnet(c, r, xin, B, h, w, dst, G, eps, tproj, temb_total, xin_stats, &xs);
-                else if (hid_here) run_resnet(c, r, xin, B, h, w, dst, G, eps, tproj, temb_total, xin_stats, &outp, 1.f, &hid, nx_groups);
-                else run_resnet(c, r, xin, B, h, w, dst, G, eps, tproj, temb_total, xin_stats, nullptr);
+                if (last) run_resnet(c, r, xin, Bl, h, w, dst, G, eps, tproj, temb_total, xin_stats, &xs);
+                else if (hid_here) run_resnet(c, r, xin, Bl, h, w, dst, G, eps, tproj, temb_total, xin_stats, &outp, 1.f, &hid, nx_groups);
+                else run_resnet(c, r, xin, Bl, h, w, dst, G, eps, tproj, temb_total, xin_stats, nullptr);
             }
             if (last) {
                 final_x = dst;   // the temporary stays alive for the tail
@@ -1139,7 +1254,7 @@ int UNet::run(Ctx& c, const half_t* sample, const float* timesteps, const half_t
                     ConvFuse fu;
                     fu.gn_out = nx_groups > 0 ? &hid : nullptr;
                     fu.gn_groups = nx_groups;
-                    op_conv(c, up_us[i], dst, B, h, w, up_dst, 1, 1, nullptr, 0, nullptr, 0, -1, 0, nx_groups > 0 ? &fu : nullptr);
+                    op_conv(c, up_us[i], dst, ctx_live(c, B), h, w, up_dst, 1, 1, nullptr, 0, nullptr, 0, -1, 0, nx_groups > 0 ? &fu : nullptr);
                     outp = fu.gn_out;
                     h *= 2; w *= 2;
                 }
@@ -1151,6 +1266,7 @@ int UNet::run(Ctx& c, const half_t* sample, const float* timesteps, const half_t
     }
 
     // ---- tail: GN + SiLU + conv_out, back to NCHW ----
+    if (pag && !pgs.widened) { set_error("unet: forward_pag reached the tail without a perturbed transformer"); return 2; }
     {
         const int C = boc[0];
         const long M = (long)B * h * w;
@@ -1284,20 +1400,25 @@ int UNet::forward_graph(const half_t* sample, const float* timesteps, const half
 int UNet::forward(const half_t* sample, const float* timesteps, const half_t* ehs, int L, const half_t* add_text,
                   const float* add_time_ids, half_t* out, int B, int H, int W, hipStream_t stream,
                   const half_t* image_embeds, int n_img, const half_t* control, int n_ctrl, float cn_scale, const CfgIn* cfg_in,
-                  const float* tcond) {
+                  const float* tcond, const PagIn* pag) {
     if (!finalized) { set_error("unet: forward before finalize"); return 2; }
+    if (pag && (B % (pag->groups + 1) != 0 || graph_enabled || control || image_embeds || tcond || dc_mode != SD_DC_PLAIN)) {
+        set_error("unet: perturbed-attention forward not available for this call");
+        return 2;
+    }
     if (tcond && cfg.time_cond_proj_dim <= 0) { set_error("unet: timestep_cond given but the UNet has no time_cond_proj_dim"); return 1; }
     if (tcond && cfg_in) { set_error("unet: timestep_cond with the shared CFG prefix (a guidance-embedded UNet runs without CFG)"); return 1; }
     if (tcond && cn) { set_error("unet: timestep_cond with a ControlNet attached is not supported"); return 4; }
-    if (cfg_in && (B % 2 != 0 || graph_enabled || control || !unet_cfg_share_eligible(cfg))) {
+    if (cfg_in && ((pag ? B - B / 3 : B) % 2 != 0 || graph_enabled || control || !unet_cfg_share_eligible(cfg))) {
         set_error("unet: shared CFG prefix not available for this call");
         return 2;
     }
     const int div = 1 << (cfg.num_blocks - 1);
     if (B <= 0 || H % div != 0 || W % div != 0) { set_error("unet: H and W must be divisible by 2^(blocks-1)"); return 1; }
-    if (ip && !image_embeds) { set_error("unet: an IP-Adapter is attached: image_embeds required"); return 1; }
+    // (forward_pag runs with an attached adapter only at scale 0, where the text attention runs alone)
+    if (ip && !image_embeds && !pag) { set_error("unet: an IP-Adapter is attached: image_embeds required"); return 1; }
     if (!ip && image_embeds) { set_error("unet: image_embeds given but no IP-Adapter is attached"); return 1; }
-    if (ip) {
+    if (ip && !pag) {
         if (n_img < 1 || n_img * ip->n_tok > 64) { set_error("unet: images per prompt x adapter tokens must be in [1, 64]"); return 4; }
         if (L < 1 || L > 160) { set_error("unet: with an IP-Adapter the text length must be in [1, 160]"); return 4; }
         if (graph_enabled) { set_error("unet: graph replay with an IP-Adapter attached is not supported"); return 4; }
@@ -1353,7 +1474,7 @@ int UNet::forward(const half_t* sample, const float* timesteps, const half_t* eh
             SD_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&kv_cache), need));
             kv_cap = need;
         }
-        if (ip) {
+        if (ip && !pag) {
             const size_t ineed = (size_t)B * n_img * ip->n_tok * ip->kv_total * sizeof(half_t);
             if (ineed > ipkv_cap) {
                 SD_HIP_CHECK(hipDeviceSynchronize());
@@ -1385,16 +1506,18 @@ int UNet::forward(const half_t* sample, const float* timesteps, const half_t* eh
     // (the IP-Adapter's image token count joins the key: set_ip_adapter resets the plan)
     const long key = ((long)B << 40) ^ ((long)H << 20) ^ (long)W ^ ((long)L << 52) ^ (kv_cache_on ? (1L << 62) : 0) ^
                      (ip ? (long)(n_img * ip->n_tok) << 32 : 0) ^ (cfg_in ? (1L << 61) : 0);
+    // (forward_pag: the groups and whether the perturbed one is widened late; sd_unet_set_pag_layers resets the plan)
+    const int pag_key = pag ? 1 + pag->groups * 2 + (pag->late ? 1 : 0) : 0;
     // (the ControlNet's arena use depends on whether it runs and on n_ctrl: set_controlnet resets the plan)
     const long cn_key = use_cn ? n_ctrl : 0;
     // (the DeepCache mode and depth belong to the key: one slot per mode, the depth beside it; the plain forward does not
     // depend on the depth)
     const int key_depth = dc != SD_DC_PLAIN ? dc_depth : 0;
-    if (key != planned_key[dc] || cn_key != planned_cn[dc] || key_depth != planned_depth[dc]) {
+    if (key != planned_key[dc] || cn_key != planned_cn[dc] || key_depth != planned_depth[dc] || pag_key != planned_pag) {
         Ctx dry{&arena, stream, true};
         arena.begin(true);
         int rc = run(dry, sample, timesteps, ehs, L, add_text, add_time_ids, out, B, H, W, image_embeds, n_img, control,
-                     n_ctrl, cn_scale, cfg_in, tcond, dc);
+                     n_ctrl, cn_scale, cfg_in, tcond, dc, pag);
         if (rc) return rc;
         // growing the slab frees the old one: make sure nothing enqueued earlier still uses it
         if (arena.peak() > arena.capacity()) {
@@ -1405,11 +1528,12 @@ int UNet::forward(const half_t* sample, const float* timesteps, const half_t* eh
         planned_key[dc] = key;
         planned_cn[dc] = cn_key;
         planned_depth[dc] = key_depth;
+        planned_pag = pag_key;
     }
     Ctx ctx{&arena, stream, false};
     arena.begin(false);
     int rc = run(ctx, sample, timesteps, ehs, L, add_text, add_time_ids, out, B, H, W, image_embeds, n_img, control, n_ctrl,
-                 cn_scale, cfg_in, tcond, dc);
+                 cn_scale, cfg_in, tcond, dc, pag);
     if (!rc && arena.overflow()) { set_error("unet: workspace overflow (planner bug)"); return 2; }
     if (!rc && dc == SD_DC_STORE) { dc_valid = true; dc_B = B; dc_H = H; dc_W = W; dc_cfg = cfg_in != nullptr; }
     return rc;
@@ -1472,6 +1596,95 @@ int UNet::forward_cfg(const half_t* latents, const float* timesteps, const half_
     if (int rc = launch_cfg_duplicate(latents, lat2, (long)n, in_scale, stream)) return rc;
     if (int rc = launch_dup_f32(timesteps, ts2, B, stream)) return rc;
     return forward(lat2, ts2, ehs, L, add_text, add_time_ids, out, 2 * B, H, W, stream, image_embeds, n_img);
+}
+
+// ------------------------------------------------------------------------------- perturbed-attention guidance
+std::vector<std::pair<std::string, Xformer*>> UNet::xformer_sites() {
+    std::vector<std::pair<std::string, Xformer*>> v;
+    for (size_t i = 0; i < down_att.size(); ++i)
+        for (size_t j = 0; j < down_att[i].size(); ++j)
+            v.emplace_back("down_blocks." + std::to_string(i) + ".attentions." + std::to_string(j), &down_att[i][j]);
+    v.emplace_back("mid_block.attentions.0", &mid_att);
+    for (size_t i = 0; i < up_att.size(); ++i)
+        for (size_t j = 0; j < up_att[i].size(); ++j)
+            v.emplace_back("up_blocks." + std::to_string(i) + ".attentions." + std::to_string(j), &up_att[i][j]);
+    return v;
+}
+
+int UNet::set_pag_layers(const char* const* keys, int count) {
+    if (!finalized) { set_error("unet: set_pag_layers before finalize"); return 2; }
+    if (count < 0 || (count > 0 && !keys)) { set_error("unet: set_pag_layers: bad arguments"); return 1; }
+    auto sites = xformer_sites();
+    std::vector<Xformer*> pick;
+    for (int k = 0; k < count; ++k) {
+        Xformer* hit = nullptr;
+        for (auto& st : sites)
+            if (keys[k] && st.first == keys[k]) hit = st.second;
+        if (!hit || hit->blocks.empty()) {
+            set_error(std::string("unet: set_pag_layers: no transformer block at '") + (keys[k] ? keys[k] : "(null)") + "'");
+            return 1;
+        }
+        pick.push_back(hit);
+    }
+    for (auto& st : sites) st.second->pag = false;
+    for (Xformer* x : pick) x->pag = true;
+    kv_valid = false;
+    reset_plans();
+    return 0;
+}
+
+int UNet::forward_pag(const half_t* latents, const float* timesteps, const half_t* ehs, int L, const half_t* add_text,
+                      const float* add_time_ids, float in_scale, bool cfg_on, bool share, half_t* out, int B, int H, int W,
+                      hipStream_t stream) {
+    if (!finalized) { set_error("unet: forward before finalize"); return 2; }
+    if (B <= 0 || H <= 0 || W <= 0) { set_error("unet: forward_pag: empty batch"); return 1; }
+    if (cn) { set_error("unet: forward_pag with a ControlNet attached is not supported"); return 4; }
+    if (ip && ip_scale != 0.f) { set_error("unet: forward_pag with an IP-Adapter at a non-zero scale is not supported"); return 4; }
+    if (dc_mode != SD_DC_PLAIN) { set_error("unet: forward_pag in a DeepCache store / reuse mode is not supported (a reuse step has no perturbed branch)"); return 4; }
+    if (graph_enabled) { set_error("unet: forward_pag under graph replay is not supported"); return 4; }
+    if (cfg.time_cond_proj_dim > 0) { set_error("unet: forward_pag on a guidance-embedded UNet (timestep_cond) is not supported"); return 4; }
+    // the flagged transformers in execution order: late widening needs the first of them behind the network's first
+    int first_flagged = -1, idx = 0;
+    for (auto& st : xformer_sites()) {
+        if (st.second->pag && first_flagged < 0) first_flagged = idx;
+        ++idx;
+    }
+    if (first_flagged < 0) { set_error("unet: forward_pag without perturbed layers (sd_unet_set_pag_layers)"); return 1; }
+    static const bool off = getenv("SD_NO_PAG_SHARE") != nullptr;
+    static const bool gn_cat = getenv("SD_GN_CAT") != nullptr;
+    PagIn pag;
+    pag.groups = cfg_on ? 2 : 1;
+    pag.late = share && !off && !gn_cat && first_flagged > 0;
+    const int G = pag.groups, N = (G + 1) * B;
+    if (pag.late && cfg_on && cfg_share_active(true)) {
+        // B latents -> 2B at the first cross-attention (the CFG-shared start) -> 3B at the first flagged transformer
+        CfgIn in;
+        in.latents = latents;
+        in.in_scale = in_scale;
+        return forward(nullptr, timesteps, ehs, L, add_text, add_time_ids, out, N, H, W, stream, nullptr, 0, nullptr, 0, 0.f,
+                       &in, nullptr, &pag);
+    }
+    // the scaled latents and the timesteps once per group, in the buffer forward_cfg's duplicate path uses (late: the
+    // un-perturbed groups only are read)
+    const size_t n = (size_t)B * cfg.in_channels * H * W;
+    const size_t lat_bytes = ((G + 1) * n * sizeof(half_t) + 255) & ~size_t(255), need = lat_bytes + (size_t)N * sizeof(float);
+    if (need > cfg_cap) {
+        SD_HIP_CHECK(hipDeviceSynchronize());
+        if (cfg_slab) (void)hipFree(cfg_slab);
+        cfg_slab = nullptr; cfg_cap = 0;
+        SD_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&cfg_slab), need));
+        cfg_cap = need;
+    }
+    half_t* lat = reinterpret_cast<half_t*>(cfg_slab);
+    float* ts = reinterpret_cast<float*>(cfg_slab + lat_bytes);
+    if (int rc = launch_cfg_duplicate(latents, lat, (long)n, in_scale, stream)) return rc;
+    if (int rc = launch_dup_f32(timesteps, ts, B, stream)) return rc;
+    if (G == 2) {
+        if (int rc = launch_scale_copy_f16(latents, lat + 2 * n, (long)n, in_scale, stream)) return rc;
+        SD_HIP_CHECK(hipMemcpyAsync(ts + 2 * B, timesteps, (size_t)B * sizeof(float), hipMemcpyDeviceToDevice, stream));
+    }
+    return forward(lat, ts, ehs, L, add_text, add_time_ids, out, N, H, W, stream, nullptr, 0, nullptr, 0, 0.f, nullptr, nullptr,
+                   &pag);
 }
 
 }  // namespace sd

@@ -128,6 +128,7 @@ class HipUNet2DConditionModel:
         self._cn = None                # attached HipControlNetModel (attach_controlnet)
         self._freeu = None             # (s1, s2, b1, b2) while FreeU is on (enable_freeu)
         self._deepcache = None         # (cache_interval, cache_depth) while DeepCache is on (enable_deepcache)
+        self._pag = ()                 # site keys of the perturbed transformers (set_pag_layers)
 
     # -- weights -------------------------------------------------------------------------------
     def load_state_dict(self, state_dict: Dict[str, torch.Tensor], strict: bool = True):
@@ -146,6 +147,8 @@ class HipUNet2DConditionModel:
             new.enable_freeu(*self._freeu)
         if self._deepcache is not None:      # and so does DeepCache
             new.enable_deepcache(*self._deepcache)
+        if self._pag:                        # and the perturbed-attention layers
+            new.set_pag_layers(self._pag)
         return new
 
     def rebuild_factory(self):
@@ -222,6 +225,31 @@ class HipUNet2DConditionModel:
         _lib.check(self._lib.sd_unet_set_freeu(self._h, 0, 1.0, 1.0, 1.0, 1.0), "sd_unet_set_freeu")
         self._freeu = None
         return self
+
+    def set_pag_layers(self, layers):
+        """Which transformers `forward_pag` perturbs: diffusers' `pag_applied_layers` spellings ("mid", "down.block_2",
+        "up.block_1.attentions_0", a list of them) or the engine's site keys ("mid_block.attentions.0", ...); None or an
+        empty list clears them.  A name that selects no transformer of this UNet is a ValueError.  The settings survive
+        `rebuild`; every other forward ignores them."""
+        from . import pag
+        if layers is None or (not isinstance(layers, str) and len(tuple(layers)) == 0):
+            keys = ()
+        else:
+            names = (layers,) if isinstance(layers, str) else tuple(layers)
+            sites = pag.transformer_sites(self.cfg)
+            keys = tuple(names) if all(n in sites for n in names) else pag.site_keys(self.cfg, names)
+            keys = tuple(k for k in sites if k in keys)
+        if keys == self._pag:                # (every call resets the engine's plans and its text K/V cache)
+            return self
+        arr = (C.c_char_p * max(len(keys), 1))(*[k.encode() for k in keys])
+        _lib.check(self._lib.sd_unet_set_pag_layers(self._h, arr, len(keys)), "sd_unet_set_pag_layers")
+        self._pag = keys
+        return self
+
+    @property
+    def pag_layers(self):
+        """The engine's site keys of the perturbed transformers, in execution order."""
+        return self._pag
 
     # the forward modes of DeepCache (sd_engine.h: SD_DC_*)
     DC_PLAIN, DC_STORE, DC_REUSE = 0, 1, 2
@@ -464,6 +492,52 @@ class HipUNet2DConditionModel:
                                                img.shape[1] if img is not None else 0, float(in_scale), int(bool(share)),
                                                C.c_void_p(out.data_ptr()), B, H, W, C.c_void_p(_stream_ptr()))
         _lib.check(rc, "sd_unet_forward_cfg")
+        return (out,)
+
+    def forward_pag(self, latents, timestep, encoder_hidden_states, added_cond_kwargs=None, in_scale: float = 1.0,
+                    cfg: bool = True, share: bool = True):
+        """One perturbed-attention-guidance forward from the UN-duplicated latents [B, C, H, W]: the model output of
+        [uncond ; text ; perturbed] (`cfg`) or [text ; perturbed], [(G + 1) B, ...] with G = 2 or 1.
+        encoder_hidden_states and added_cond_kwargs hold the G B rows of the un-perturbed groups; the perturbed group
+        takes the text group's, and in the transformers of `set_pag_layers` its self-attention map is the identity.
+        With `share` the engine creates the perturbed group only where it starts to differ (sd_unet_forward_pag).
+        Not with a ControlNet, an IP-Adapter at a non-zero scale, DeepCache store / reuse, graph replay or a
+        guidance-embedded UNet (EngineError, SD_ERR_UNSUPPORTED)."""
+        if not self._finalized:
+            raise _lib.EngineError("weights not loaded")
+        dev = self.device
+        latents = _as_f16(latents, dev)
+        B, _, H, W = latents.shape
+        G = 2 if cfg else 1
+        ehs = _as_f16(encoder_hidden_states, dev)
+        if ehs.shape[0] != G * B:
+            raise ValueError(f"encoder_hidden_states batch {ehs.shape[0]} != {G} x latents batch {B}")
+        if ehs.shape[2] != self.cfg.cross_attention_dim:
+            raise ValueError("encoder_hidden_states width != cross_attention_dim")
+        if isinstance(timestep, (int, float)):
+            t = torch.full((B,), float(timestep), device=dev, dtype=torch.float32)
+        else:
+            t = torch.as_tensor(timestep, device=dev).to(torch.float32).reshape(-1)
+            if t.numel() not in (1, B):
+                raise ValueError(f"timestep: expected a scalar or {B} values (one per latent), got {t.numel()}")
+            t = t.expand(B).contiguous() if t.numel() == 1 else t.contiguous()
+        pt = pi = None
+        if self.cfg.addition_embed_type == "text_time":
+            if not added_cond_kwargs or "text_embeds" not in added_cond_kwargs or "time_ids" not in added_cond_kwargs:
+                raise ValueError("added_cond_kwargs needs text_embeds and time_ids for text_time conditioning")
+            add_text = _as_f16(added_cond_kwargs["text_embeds"], dev)
+            add_ids = added_cond_kwargs["time_ids"].to(device=dev, dtype=torch.float32).contiguous()
+            _check_time_ids(add_ids, self.cfg)
+            if add_text.shape[0] != G * B or add_ids.shape[0] != G * B:
+                raise ValueError(f"text_embeds / time_ids must hold {G} x latents batch rows")
+            pt, pi = C.c_void_p(add_text.data_ptr()), C.c_void_p(add_ids.data_ptr())
+        out = torch.empty(((G + 1) * B, self.cfg.out_channels, H, W), device=dev, dtype=torch.float16)
+        with torch.cuda.device(dev):
+            rc = self._lib.sd_unet_forward_pag(self._h, C.c_void_p(latents.data_ptr()), C.c_void_p(t.data_ptr()),
+                                               C.c_void_p(ehs.data_ptr()), ehs.shape[1], pt, pi, float(in_scale),
+                                               int(bool(cfg)), int(bool(share)), C.c_void_p(out.data_ptr()), B, H, W,
+                                               C.c_void_p(_stream_ptr()))
+        _lib.check(rc, "sd_unet_forward_pag")
         return (out,)
 
     # LoRA adapters arrive fused into the weights (stablediffusion_amd.weights.fuse_lora); the

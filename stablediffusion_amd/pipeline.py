@@ -22,13 +22,14 @@ Differences from the reference, on purpose:
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from types import SimpleNamespace
 from typing import Any, Dict, List, Optional, Union
 
 import torch
 
-from . import _lib, schedulers as _sched
+from . import _lib, pag as _pag, schedulers as _sched
 from .image_processor import VaeImageProcessor
 
 
@@ -55,6 +56,7 @@ class SDModelWrapper:
         self._ip_scale = 1.0
         self._cn = None                  # ControlNet (configuration, diffusers-named state dict): load_controlnet
         self._freeu = None               # (s1, s2, b1, b2) while FreeU is on: enable_freeu
+        self._pag = None                 # pag_applied_layers as given (set_pag_applied_layers); None: the default
         self._deepcache = None           # (cache_interval, cache_depth) while DeepCache is on: enable_deepcache
         # host copies of the weights the LoRA adapters are folded into (load_lora_weights); the engine
         # itself keeps only its packed device copy
@@ -168,7 +170,7 @@ class SDModelWrapper:
         deepcache = getattr(old, "deepcache", self._deepcache)
         self.base = None                     # the old engine's device memory goes before the new one is packed
         del old
-        self.base = self._rebuild_from(fused, graph, freeu, deepcache)
+        self.base = self._rebuild_from(fused, graph, freeu, deepcache, self._pag)
         for part in ("text_encoder", "text_encoder_2"):
             if self._te_sd[part] is not None and (self._lora.touches(part) or self._lora_applied is not None):
                 enc = getattr(self, part, None)
@@ -181,7 +183,7 @@ class SDModelWrapper:
                     raise ValueError(f"{type(enc).__name__} cannot take fused text-encoder LoRA weights")
         self._lora_applied = sig
 
-    def _rebuild_from(self, fused, graph, freeu=None, deepcache=None):
+    def _rebuild_from(self, fused, graph, freeu=None, deepcache=None, pag=None):
         base = self._base_factory(fused)
         if graph and hasattr(base, "use_graph"):
             base.use_graph(True)
@@ -195,7 +197,22 @@ class SDModelWrapper:
         self._deepcache = deepcache
         if deepcache is not None:            # and DeepCache
             base.enable_deepcache(*deepcache)
+        self._pag = pag
+        if pag is not None and hasattr(base, "set_pag_layers"):     # and the perturbed-attention layers
+            base.set_pag_layers(pag)
         return base
+
+    # ---- perturbed-attention guidance: which transformers `pag_scale > 0` perturbs (diffusers' pag_applied_layers) ----
+    def set_pag_applied_layers(self, layers):
+        """diffusers' `pag_applied_layers` ("mid", "down.block_2", "up.block_1.attentions_0", a list of them; the
+        default without a call is ("mid",)).  Names are checked against the UNet's topology at once where it has one."""
+        names = (layers,) if isinstance(layers, str) else tuple(layers)
+        cfg = getattr(self.base, "cfg", None)
+        if cfg is not None:
+            _pag.site_keys(cfg, names)           # (raises for a name that selects nothing)
+        if hasattr(self.base, "set_pag_layers"):
+            self.base.set_pag_layers(names)
+        self._pag = names
 
     # ---- FreeU (diffusers pipelines' enable_freeu / disable_freeu: forwarded to the UNet) ----
     def enable_freeu(self, s1: float, s2: float, b1: float, b2: float):
@@ -443,6 +460,9 @@ class StableDiffusionUnifiedPipeline:
         # the fused CFG step lets the engine run the start of the UNet once per latent (HipUNet2DConditionModel.forward_cfg);
         # False keeps the engine's duplicate-then-forward form
         self.cfg_share = True
+        # perturbed-attention guidance: the engine creates the perturbed group where it starts to differ
+        # (HipUNet2DConditionModel.forward_pag); False duplicates up front
+        self.pag_share = True
         self._use_refiner = False            # set per call: the UNet of this call is model.refiner
         self.is_inpaint = False              # set per call
 
@@ -506,10 +526,26 @@ class StableDiffusionUnifiedPipeline:
         refiner_start: Optional[float] = None,
         aesthetic_score: float = 6.0,
         negative_aesthetic_score: float = 2.5,
+        # perturbed-attention guidance (diffusers >= 0.30 StableDiffusionPAGPipeline; layers: set_pag_applied_layers)
+        pag_scale: float = 0.0,
+        pag_adaptive_scale: float = 0.0,
     ):
         if refiner_start is not None:
+            if pag_scale is not None and float(pag_scale) > 0.0:
+                raise NotImplementedError("perturbed-attention guidance (pag_scale > 0) does not address the refiner")
             call = {k: v for k, v in locals().items() if k != "self"}
             return self._ensemble_of_experts(call)
+        pag_on = pag_scale is not None and float(pag_scale) > 0.0
+        if pag_on:
+            if not math.isfinite(float(pag_scale)) or not math.isfinite(float(pag_adaptive_scale)) or pag_adaptive_scale < 0:
+                raise ValueError("pag_scale and pag_adaptive_scale must be finite and non-negative")
+            if use_refiner or refiner_start is not None:
+                raise NotImplementedError("perturbed-attention guidance (pag_scale > 0) does not address the refiner")
+            if ip_adapter_image is not None or ip_adapter_image_embeds is not None:
+                raise NotImplementedError("perturbed-attention guidance (pag_scale > 0) with an IP-Adapter image is not supported")
+            if bool(getattr(model, "has_controlnet", False)):
+                raise NotImplementedError("perturbed-attention guidance (pag_scale > 0) with a ControlNet loaded is not "
+                                          "supported (unload_controlnet)")
         if guess_mode:
             raise NotImplementedError("ControlNet guess_mode is not supported")
         self._use_refiner = bool(use_refiner)
@@ -551,6 +587,16 @@ class StableDiffusionUnifiedPipeline:
         if hasattr(model, "apply_adapters"):
             model.apply_adapters()
         unet = self._unet(model)             # (after the re-fuse, which replaces model.base)
+        if pag_on:
+            if getattr(unet, "deepcache", None) is not None:
+                raise NotImplementedError("perturbed-attention guidance (pag_scale > 0) with DeepCache enabled is not "
+                                          "supported: a reuse step skips the perturbed layers (disable_deepcache)")
+            if unet.config.in_channels == 9:
+                raise NotImplementedError("perturbed-attention guidance (pag_scale > 0) with a 9-channel inpaint UNet is "
+                                          "not supported")
+            if tc_dim:
+                raise NotImplementedError("perturbed-attention guidance (pag_scale > 0) with a guidance-embedded UNet "
+                                          "(time_cond_proj_dim) is not supported")
         if image is not None and mask_image is None:
             # img2img keeps the image's own size (`:238` preprocesses without height / width); PIL, numpy and
             # tensor inputs alike go through the image processor (rounded down to a multiple of the VAE factor)
@@ -715,7 +761,8 @@ class StableDiffusionUnifiedPipeline:
                                 controlnet_conditioning_scale=controlnet_conditioning_scale,
                                 control_guidance_start=control_guidance_start, control_guidance_end=control_guidance_end,
                                 mask=mask, masked_image_latents=masked_image_latents_2b, image_latents=image_latents,
-                                image_noise=noise)
+                                image_noise=noise,
+                                pag=(float(pag_scale), float(pag_adaptive_scale)) if pag_on else None)
 
         # ---- decode (:511-529) ----
         if self.output_type == "pt":
@@ -739,7 +786,7 @@ class StableDiffusionUnifiedPipeline:
     def _denoise(self, model, latents, timesteps, prompt_embeds, cross_attention_kwargs, added_cond_kwargs, tc_kwargs,
                  guidance_scale, guidance_rescale, seed, control=None, controlnet_conditioning_scale=1.0,
                  control_guidance_start=0.0, control_guidance_end=1.0, mask=None, masked_image_latents=None,
-                 image_latents=None, image_noise=None):
+                 image_latents=None, image_noise=None, pag=None):
         """The denoising loop (:465-507): `timesteps` over `latents`, the scheduler's update on the device where
         `_device_step_kind` finds one (`_device_iteration`) and in `scheduler.step` otherwise.  `tc_kwargs` is the
         guidance-embedded UNet's `timestep_cond`, `control` the prepared ControlNet image; `mask`, `masked_image_latents`
@@ -774,7 +821,23 @@ class StableDiffusionUnifiedPipeline:
             if prompt_embeds.device.type == "cuda" and (prompt_embeds.dtype != torch.float16 or not prompt_embeds.is_contiguous()):
                 prompt_embeds = prompt_embeds.to(torch.float16).contiguous()
             kv_cache(True)
+        # Perturbed-attention guidance: (pag_scale, pag_adaptive_scale); the step's scale s comes from the scheduler's
+        # timestep on the host, and a step with s = 0 is the plain step.  guidance_rescale > 0 with it takes scheduler.step.
+        pag_rows = None
+        if pag is not None:
+            names = getattr(model, "_pag", None) or _pag.DEFAULT_LAYERS
+            if hasattr(unet, "set_pag_layers"):
+                unet.set_pag_layers(names)
+            else:
+                # a UNet without the engine's forward_pag gets the (G + 1)-group batch: the perturbed group's embeddings
+                # and added conditions are the text group's
+                text = (lambda x: x.chunk(2)[1]) if self.do_classifier_free_guidance else (lambda x: x)
+                pag_rows = (torch.cat([prompt_embeds, text(prompt_embeds)]),
+                            None if added_cond_kwargs is None else
+                            {k: torch.cat([v, text(v)]) for k, v in added_cond_kwargs.items()})
         kind = self._device_step_kind(model, latents, num_channels_unet, guidance_rescale)
+        if pag is not None and guidance_rescale > 0.0:
+            kind = None
         # what the device steps keep from one iteration to the next: "linear"'s fp32 history (made by the first plan that
         # reads one), "affine"'s fp32 bank of `affine_slots` latents-sized slots, LCM's noise generator
         state = SimpleNamespace(hist=None, bank=None, gen=None)
@@ -811,17 +874,37 @@ class StableDiffusionUnifiedPipeline:
                     step_noise = torch.randn(latents.shape, dtype=latents.dtype, device=latents.device, generator=state.gen)
                 if kind == "affine" and getattr(model.scheduler, "affine_noise", False):
                     step_noise = torch.randn(latents.shape, device=latents.device, dtype=latents.dtype)
+                pag_s = _pag.step_scale(pag[0], pag[1], t) if pag is not None else 0.0
                 if kind:
                     # "linear" leaves `timestep_cond` out, which the host path and the other two kinds pass.  Kept as found;
                     # it cannot show today (a guidance-embedded UNet turns CFG off, and "linear" needs CFG)
                     unet_kwargs = cn_kwargs if kind == "linear" else {**cn_kwargs, **tc_kwargs}
                     latents = self._device_iteration(kind, state, model, latents, step_noise, t, prompt_embeds,
                                                      cross_attention_kwargs, added_cond_kwargs, guidance_scale,
-                                                     guidance_rescale, **unet_kwargs)
+                                                     guidance_rescale, pag_s=pag_s, **unet_kwargs)
                     if blend is not None:
                         last = i == len(timesteps_host) - 1
                         a, b = (1.0, 0.0) if last else model.scheduler.add_noise_coefficients(timesteps_host[i + 1])
                         self._device_inpaint_blend(model, latents, blend, a, b, with_noise=not last)
+                    continue
+                if pag_s > 0.0:
+                    # [uncond ; text ; perturbed] or [text ; perturbed] -> eps = u + g (t - u) + s (t - p) / t + s (t - p)
+                    if pag_rows is None:
+                        x = model.scheduler.scale_model_input(latents, t)
+                        noise_pred = unet.forward_pag(x, t, prompt_embeds, added_cond_kwargs=added_cond_kwargs,
+                                                      cfg=self.do_classifier_free_guidance, share=self.pag_share)[0]
+                    else:
+                        groups = 3 if self.do_classifier_free_guidance else 2
+                        x = model.scheduler.scale_model_input(torch.cat([latents] * groups), t)
+                        noise_pred = unet(x, t, pag_rows[0], cross_attention_kwargs=cross_attention_kwargs,
+                                          added_cond_kwargs=pag_rows[1], return_dict=False)[0]
+                    noise_pred_text = noise_pred.chunk(3)[1] if self.do_classifier_free_guidance else None
+                    noise_pred = _pag.combine(noise_pred, guidance_scale, pag_s, self.do_classifier_free_guidance)
+                    if guidance_rescale > 0.0:
+                        noise_pred = rescale_noise_cfg(noise_pred, noise_pred_text, guidance_rescale)
+                    latents = self._host_step(model, noise_pred, t, latents, step_noise if lcm else None, lcm)
+                    latents = self._host_inpaint_blend(model, latents, i, timesteps_host, mask, image_latents, image_noise,
+                                                       num_channels_unet)
                     continue
                 latent_model_input = torch.cat([latents] * 2) if self.do_classifier_free_guidance else latents
                 latent_model_input = model.scheduler.scale_model_input(latent_model_input, t)
@@ -853,6 +936,23 @@ class StableDiffusionUnifiedPipeline:
             if kv_cache is not None:
                 kv_cache(False)
         return latents
+
+    @staticmethod
+    def _host_step(model, noise_pred, t, latents, noise, lcm):
+        if lcm:
+            return model.scheduler.step(noise_pred, t, latents, noise=noise, return_dict=False)[0]
+        return model.scheduler.step(noise_pred, t, latents, return_dict=False)[0]
+
+    def _host_inpaint_blend(self, model, latents, i, timesteps_host, mask, image_latents, image_noise, num_channels_unet):
+        """The 4-channel inpaint blend of the host loop (:492-506), for the perturbed-attention steps."""
+        if not (self.is_inpaint and num_channels_unet == 4):
+            return latents
+        init_latents_proper = image_latents
+        init_mask = mask.chunk(2)[0] if self.do_classifier_free_guidance else mask
+        if i < len(timesteps_host) - 1:
+            init_latents_proper = model.scheduler.add_noise(init_latents_proper, image_noise,
+                                                            torch.as_tensor([timesteps_host[i + 1]]))
+        return ((1 - init_mask) * init_latents_proper.float() + init_mask * latents.float()).to(latents.dtype)
 
     def _device_inpaint_blend(self, model, latents, blend, a, b, with_noise):
         lib = self._unet(model)._lib
@@ -904,7 +1004,7 @@ class StableDiffusionUnifiedPipeline:
         return None
 
     def _device_iteration(self, kind, state, model, latents, noise, t, prompt_embeds, cross_attention_kwargs,
-                          added_cond_kwargs, guidance_scale, guidance_rescale=0.0, **unet_kwargs):
+                          added_cond_kwargs, guidance_scale, guidance_rescale=0.0, pag_s=0.0, **unet_kwargs):
         """One iteration with the scheduler's update on the device: the plan from the scheduler, the UNet forward, one
         step entry of the engine over a copy of the latents, the plan committed.  -> the new latents."""
         sched, unet = model.scheduler, self._unet(model)
@@ -912,7 +1012,13 @@ class StableDiffusionUnifiedPipeline:
         plan = sched.affine_plan(t) if kind == "affine" else sched.fused_plan(t)
         latents = latents.contiguous()
         rows = 2 if self.do_classifier_free_guidance else 1          # ("linear" runs under CFG only)
-        if rows == 2:                                # rows = [uncond ; text], from the un-duplicated latents
+        if pag_s > 0.0:
+            # perturbed-attention guidance: rows = [uncond ; text ; perturbed] or [text ; perturbed], one engine forward
+            rows += 1
+            model_out = unet.forward_pag(latents, t, prompt_embeds, added_cond_kwargs=added_cond_kwargs,
+                                         in_scale=plan.in_scale, cfg=self.do_classifier_free_guidance,
+                                         share=self.pag_share)[0]
+        elif rows == 2:                              # rows = [uncond ; text], from the un-duplicated latents
             model_out = self._cfg_forward(model, latents, plan.in_scale, t, prompt_embeds, cross_attention_kwargs,
                                           added_cond_kwargs, **unet_kwargs)
         else:
@@ -925,9 +1031,17 @@ class StableDiffusionUnifiedPipeline:
             state.hist = torch.zeros(latents.shape, device=latents.device, dtype=torch.float32)
         out = latents.clone()
         n, g = out.numel(), float(guidance_scale)
+        if pag_s > 0.0 and kind != "linear":
+            # the combine as a launch of its own, then the scheduler's entry on its one-row result
+            m = torch.empty_like(out)
+            _check(lib, lib.sd_pag_combine(_ptr(model_out), rows, _ptr(m), n, g, float(pag_s), _stream()))
+            model_out, rows = m, 1
         if kind == "linear":
             hist_p = _ptr(state.hist) if plan.use_hist else None
-            if guidance_rescale > 0.0:
+            if pag_s > 0.0:
+                rc = lib.sd_pag_linear_step(_ptr(model_out), rows, _ptr(out), hist_p, n, g, float(pag_s), plan.c_x, plan.c_eps,
+                                            plan.c_hist, plan.h_x, plan.h_eps, _stream())
+            elif guidance_rescale > 0.0:
                 # the rescale needs a standard deviation per sample, so it is not affine: its own statistics + update kernels
                 rc = lib.sd_cfg_rescale_linear_step(_ptr(model_out), _ptr(out), hist_p, out.shape[0], out[0].numel(), g,
                                                     float(guidance_rescale), plan.c_x, plan.c_eps, plan.c_hist, plan.h_x,
