@@ -79,6 +79,26 @@ bool same_topology(const sd_unet_config& a, const sd_unet_config& b) {
 
 // Whether a ControlNet of configuration n can feed a UNet of configuration u: its residuals must have the shapes of
 // u's skips and mid-block output, and it must read the same sample, text and text_time conditioning.
+// What the six sd_unet_forward* entries share: the null check and the typed pointers of the arguments they all take.
+// (For _cfg / _pag `sample` is the un-duplicated latents and B their count: UNet::forward_cfg.)
+bool fill_call(const sd_unet* u, const void* sample, const float* timesteps, const void* ehs, int ehs_len, const void* add_text,
+               const float* add_time_ids, void* out, int B, int H, int W, UNetCall* c) {
+    if (!u || !sample || !timesteps || !ehs || !out) { set_error("null argument"); return false; }
+    c->sample = static_cast<const half_t*>(sample);
+    c->timesteps = timesteps;
+    c->ehs = static_cast<const half_t*>(ehs);
+    c->L = ehs_len;
+    c->add_text = static_cast<const half_t*>(add_text);
+    c->add_time_ids = add_time_ids;
+    c->out = static_cast<half_t*>(out);
+    c->B = B; c->H = H; c->W = W;
+    return true;
+}
+void with_images(UNetCall* c, const void* image_embeds, int n_img) {
+    c->image_embeds = static_cast<const half_t*>(image_embeds);
+    c->n_img = image_embeds ? n_img : 0;
+}
+
 bool controlnet_fits(const sd_unet_config& u, const sd_unet_config& n, std::string* why) {
     if (n.num_blocks != u.num_blocks || n.layers_per_block != u.layers_per_block) {
         *why = "num_blocks / layers_per_block differ from the UNet's";
@@ -141,10 +161,9 @@ int sd_unet_finalize(sd_unet* u) {
 int sd_unet_forward(sd_unet* u, const void* sample, const float* timesteps, const void* ehs, int ehs_len,
                     const void* add_text, const float* add_time_ids, void* out, int B, int H, int W,
                     void* stream) {
-    if (!u || !sample || !timesteps || !ehs || !out) { set_error("null argument"); return SD_ERR_INVALID; }
-    return u->impl.forward(static_cast<const half_t*>(sample), timesteps, static_cast<const half_t*>(ehs),
-                           ehs_len, static_cast<const half_t*>(add_text), add_time_ids,
-                           static_cast<half_t*>(out), B, H, W, static_cast<hipStream_t>(stream));
+    UNetCall c;
+    if (!fill_call(u, sample, timesteps, ehs, ehs_len, add_text, add_time_ids, out, B, H, W, &c)) return SD_ERR_INVALID;
+    return u->impl.forward(c, static_cast<hipStream_t>(stream));
 }
 int sd_unet_use_graph(sd_unet* u, int enable) {
     if (!u) { set_error("null handle"); return SD_ERR_INVALID; }
@@ -154,25 +173,25 @@ int sd_unet_use_graph(sd_unet* u, int enable) {
 int sd_unet_text_kv_cache(sd_unet* u, int enable) {
     if (!u) { set_error("null handle"); return SD_ERR_INVALID; }
     u->impl.kv_cache_on = enable != 0;
-    u->impl.kv_valid = false;           // every call invalidates: the next forward recomputes
-    u->impl.ipkv_valid = false;         // (the IP-Adapter's image K / V alike)
-    u->impl.cond_valid = false;         // (and the ControlNet's conditioning embedding and text K / V)
-    u->impl.cnkv_valid = false;
+    u->impl.kv_tag.clear();             // every call invalidates: the next forward recomputes
+    u->impl.ipkv_tag.clear();           // (the IP-Adapter's image K / V alike)
+    u->impl.cond_tag.clear();           // (and the ControlNet's conditioning embedding and text K / V)
+    u->impl.cnkv_tag.clear();
     return SD_OK;
 }
 int sd_unet_forward_ex(sd_unet* u, const void* sample, const float* timesteps, const void* ehs, int ehs_len,
                        const void* add_text, const float* add_time_ids, const void* image_embeds, int n_img, void* out,
                        int B, int H, int W, void* stream) {
-    if (!u || !sample || !timesteps || !ehs || !out) { set_error("null argument"); return SD_ERR_INVALID; }
-    return u->impl.forward(static_cast<const half_t*>(sample), timesteps, static_cast<const half_t*>(ehs),
-                           ehs_len, static_cast<const half_t*>(add_text), add_time_ids,
-                           static_cast<half_t*>(out), B, H, W, static_cast<hipStream_t>(stream),
-                           static_cast<const half_t*>(image_embeds), image_embeds ? n_img : 0);
+    UNetCall c;
+    if (!fill_call(u, sample, timesteps, ehs, ehs_len, add_text, add_time_ids, out, B, H, W, &c)) return SD_ERR_INVALID;
+    with_images(&c, image_embeds, n_img);
+    return u->impl.forward(c, static_cast<hipStream_t>(stream));
 }
 int sd_unet_forward_tc(sd_unet* u, const void* sample, const float* timesteps, const void* ehs, int ehs_len,
                        const void* add_text, const float* add_time_ids, const void* image_embeds, int n_img,
                        const float* timestep_cond, int cond_dim, void* out, int B, int H, int W, void* stream) {
-    if (!u || !sample || !timesteps || !ehs || !out) { set_error("null argument"); return SD_ERR_INVALID; }
+    UNetCall c;
+    if (!fill_call(u, sample, timesteps, ehs, ehs_len, add_text, add_time_ids, out, B, H, W, &c)) return SD_ERR_INVALID;
     if (timestep_cond) {
         const int want = u->impl.cfg.time_cond_proj_dim;
         if (want <= 0) { set_error("sd_unet_forward_tc: timestep_cond given but the UNet has no time_cond_proj_dim"); return SD_ERR_INVALID; }
@@ -181,11 +200,9 @@ int sd_unet_forward_tc(sd_unet* u, const void* sample, const float* timesteps, c
             return SD_ERR_INVALID;
         }
     }
-    return u->impl.forward(static_cast<const half_t*>(sample), timesteps, static_cast<const half_t*>(ehs),
-                           ehs_len, static_cast<const half_t*>(add_text), add_time_ids,
-                           static_cast<half_t*>(out), B, H, W, static_cast<hipStream_t>(stream),
-                           static_cast<const half_t*>(image_embeds), image_embeds ? n_img : 0, nullptr, 0, 0.f, nullptr,
-                           timestep_cond);
+    with_images(&c, image_embeds, n_img);
+    c.tcond = timestep_cond;
+    return u->impl.forward(c, static_cast<hipStream_t>(stream));
 }
 int sd_unet_set_ip_adapter(sd_unet* u, sd_ip_adapter* a) {
     if (!u) { set_error("null handle"); return SD_ERR_INVALID; }
@@ -197,7 +214,7 @@ int sd_unet_set_ip_adapter(sd_unet* u, sd_ip_adapter* a) {
         }
     }
     u->impl.set_ip_adapter(a ? &a->impl : nullptr);
-    u->impl.dc_valid = false;
+    u->impl.dc_tag.clear();
     return SD_OK;
 }
 int sd_unet_set_controlnet(sd_unet* u, sd_controlnet* cn) {
@@ -208,29 +225,29 @@ int sd_unet_set_controlnet(sd_unet* u, sd_controlnet* cn) {
         if (!controlnet_fits(u->impl.cfg, cn->impl.cfg, &why)) { set_error("sd_unet_set_controlnet: " + why); return SD_ERR_INVALID; }
     }
     u->impl.set_controlnet(cn ? &cn->impl : nullptr);
-    u->impl.dc_valid = false;
+    u->impl.dc_tag.clear();
     return SD_OK;
 }
 int sd_unet_forward_cn(sd_unet* u, const void* sample, const float* timesteps, const void* ehs, int ehs_len,
                        const void* add_text, const float* add_time_ids, const void* image_embeds, int n_img,
                        const void* control_image, int n_ctrl, float cond_scale, void* out, int B, int H, int W,
                        void* stream) {
-    if (!u || !sample || !timesteps || !ehs || !out) { set_error("null argument"); return SD_ERR_INVALID; }
-    return u->impl.forward(static_cast<const half_t*>(sample), timesteps, static_cast<const half_t*>(ehs),
-                           ehs_len, static_cast<const half_t*>(add_text), add_time_ids,
-                           static_cast<half_t*>(out), B, H, W, static_cast<hipStream_t>(stream),
-                           static_cast<const half_t*>(image_embeds), image_embeds ? n_img : 0,
-                           static_cast<const half_t*>(control_image), control_image ? n_ctrl : 0, cond_scale);
+    UNetCall c;
+    if (!fill_call(u, sample, timesteps, ehs, ehs_len, add_text, add_time_ids, out, B, H, W, &c)) return SD_ERR_INVALID;
+    with_images(&c, image_embeds, n_img);
+    c.control = static_cast<const half_t*>(control_image);
+    c.n_ctrl = control_image ? n_ctrl : 0;
+    c.cn_scale = cond_scale;
+    return u->impl.forward(c, static_cast<hipStream_t>(stream));
 }
 int sd_unet_forward_cfg(sd_unet* u, const void* latents, const float* timesteps, const void* ehs, int ehs_len,
                         const void* add_text, const float* add_time_ids, const void* image_embeds, int n_img,
                         float in_scale, int share, void* out, int B, int H, int W, void* stream) {
-    if (!u || !latents || !timesteps || !ehs || !out) { set_error("null argument"); return SD_ERR_INVALID; }
+    UNetCall c;
+    if (!fill_call(u, latents, timesteps, ehs, ehs_len, add_text, add_time_ids, out, B, H, W, &c)) return SD_ERR_INVALID;
     if (!(in_scale == in_scale)) { set_error("sd_unet_forward_cfg: in_scale is NaN"); return SD_ERR_INVALID; }
-    return u->impl.forward_cfg(static_cast<const half_t*>(latents), timesteps, static_cast<const half_t*>(ehs), ehs_len,
-                               static_cast<const half_t*>(add_text), add_time_ids,
-                               static_cast<const half_t*>(image_embeds), image_embeds ? n_img : 0, in_scale, share != 0,
-                               static_cast<half_t*>(out), B, H, W, static_cast<hipStream_t>(stream));
+    with_images(&c, image_embeds, n_img);
+    return u->impl.forward_cfg(c, in_scale, share != 0, static_cast<hipStream_t>(stream));
 }
 int sd_unet_set_pag_layers(sd_unet* u, const char* const* site_keys, int count) {
     if (!u) { set_error("null handle"); return SD_ERR_INVALID; }
@@ -239,11 +256,10 @@ int sd_unet_set_pag_layers(sd_unet* u, const char* const* site_keys, int count) 
 int sd_unet_forward_pag(sd_unet* u, const void* latents, const float* timesteps, const void* ehs, int ehs_len,
                         const void* add_text, const float* add_time_ids, float in_scale, int cfg, int share, void* out,
                         int B, int H, int W, void* stream) {
-    if (!u || !latents || !timesteps || !ehs || !out) { set_error("null argument"); return SD_ERR_INVALID; }
+    UNetCall c;
+    if (!fill_call(u, latents, timesteps, ehs, ehs_len, add_text, add_time_ids, out, B, H, W, &c)) return SD_ERR_INVALID;
     if (!(in_scale == in_scale)) { set_error("sd_unet_forward_pag: in_scale is NaN"); return SD_ERR_INVALID; }
-    return u->impl.forward_pag(static_cast<const half_t*>(latents), timesteps, static_cast<const half_t*>(ehs), ehs_len,
-                               static_cast<const half_t*>(add_text), add_time_ids, in_scale, cfg != 0, share != 0,
-                               static_cast<half_t*>(out), B, H, W, static_cast<hipStream_t>(stream));
+    return u->impl.forward_pag(c, in_scale, cfg != 0, share != 0, static_cast<hipStream_t>(stream));
 }
 int sd_unet_cfg_share(const sd_unet_config* cfg) { return cfg && sd::unet_cfg_share_eligible(*cfg) ? 1 : 0; }
 int sd_unet_set_ip_adapter_scale(sd_unet* u, float scale) {
@@ -254,7 +270,7 @@ int sd_unet_set_ip_adapter_scale(sd_unet* u, float scale) {
 }
 int sd_unet_set_freeu(sd_unet* u, int enable, float s1, float s2, float b1, float b2) {
     if (!u) { set_error("null handle"); return SD_ERR_INVALID; }
-    u->impl.dc_valid = false;           // (a DeepCache feature stored under other FreeU settings is stale)
+    u->impl.dc_tag.clear();             // (a DeepCache feature stored under other FreeU settings is stale)
     if (!enable) { u->impl.freeu_on = false; return SD_OK; }
     if (!std::isfinite(s1) || !std::isfinite(s2) || !std::isfinite(b1) || !std::isfinite(b2)) {
         set_error("sd_unet_set_freeu: s1, s2, b1, b2 must be finite");
@@ -342,8 +358,8 @@ int sd_ip_adapter_set_feature_tokens(sd_ip_adapter* a, int T_feat) {
     }
     a->impl.t_feat = T_feat;
     if (UNet* un = a->impl.attached) {      // the cached image K / V and the arena plan were made for the old count
-        un->ipkv_valid = false;
-        un->dc_valid = false;
+        un->ipkv_tag.clear();
+        un->dc_tag.clear();
         un->reset_plans();
     }
     return SD_OK;
@@ -408,7 +424,7 @@ int sd_controlnet_finalize(sd_controlnet* cn) {
 int sd_unet_memory(const sd_unet* u, int64_t* weight_bytes, int64_t* workspace_bytes) {
     if (!u) { set_error("null handle"); return SD_ERR_INVALID; }
     if (weight_bytes) *weight_bytes = u->impl.ws.packed_bytes();
-    if (workspace_bytes) *workspace_bytes = (int64_t)(u->impl.arena.capacity() + u->impl.dc_cap);
+    if (workspace_bytes) *workspace_bytes = (int64_t)(u->impl.arena.capacity() + u->impl.dc_buf.capacity());
     return SD_OK;
 }
 

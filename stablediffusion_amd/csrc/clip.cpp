@@ -152,22 +152,9 @@ int CLIP::forward(const int* ids, const int* eos_index, half_t* hidden_states, h
     if (B <= 0 || T <= 0 || T > cfg.max_positions) { set_error("clip: bad shape (T must be <= max_positions)"); return 1; }
     const long key = ((long)B << 32) ^ ((long)T << 8) ^ (hidden_states ? 1 : 0) ^ (last_hidden ? 2 : 0) ^
                      (pooled ? 4 : 0) ^ (text_embeds ? 8 : 0);
-    if (key != planned_key) {
-        Ctx dry{&arena, stream, true};
-        arena.begin(true);
-        int rc = run(dry, ids, eos_index, hidden_states, last_hidden, pooled, text_embeds, B, T);
-        if (rc) return rc;
-        if (arena.peak() > arena.capacity()) {
-            SD_HIP_CHECK(hipDeviceSynchronize());
-            if ((rc = arena.reserve(arena.peak()))) return rc;
-        }
-        planned_key = key;
-    }
-    Ctx ctx{&arena, stream, false};
-    arena.begin(false);
-    int rc = run(ctx, ids, eos_index, hidden_states, last_hidden, pooled, text_embeds, B, T);
-    if (!rc && arena.overflow()) { set_error("clip: workspace overflow (planner bug)"); return 2; }
-    return rc;
+    return plan_and_run(arena, stream, planned_key, key, "clip", [&](Ctx& c) {
+        return run(c, ids, eos_index, hidden_states, last_hidden, pooled, text_embeds, B, T);
+    });
 }
 
 int CLIP::final_layer_norm(const half_t* x, half_t* y, long rows, hipStream_t stream) {

@@ -223,22 +223,9 @@ int CLIPVision::forward(const half_t* pixels, half_t* hidden_states, half_t* las
     if (B <= 0) { set_error("clip_vision: bad batch size"); return 1; }
     const long key = ((long)B << 8) ^ (hidden_states ? 1 : 0) ^ (last_hidden ? 2 : 0) ^ (pooled ? 4 : 0) ^
                      (image_embeds ? 8 : 0);
-    if (key != planned_key) {
-        Ctx dry{&arena, stream, true};
-        arena.begin(true);
-        int rc = run(dry, pixels, hidden_states, last_hidden, pooled, image_embeds, B);
-        if (rc) return rc;
-        if (arena.peak() > arena.capacity()) {
-            SD_HIP_CHECK(hipDeviceSynchronize());
-            if ((rc = arena.reserve(arena.peak()))) return rc;
-        }
-        planned_key = key;
-    }
-    Ctx ctx{&arena, stream, false};
-    arena.begin(false);
-    int rc = run(ctx, pixels, hidden_states, last_hidden, pooled, image_embeds, B);
-    if (!rc && arena.overflow()) { set_error("clip_vision: workspace overflow (planner bug)"); return 2; }
-    return rc;
+    return plan_and_run(arena, stream, planned_key, key, "clip_vision", [&](Ctx& c) {
+        return run(c, pixels, hidden_states, last_hidden, pooled, image_embeds, B);
+    });
 }
 
 }  // namespace sd

@@ -107,19 +107,19 @@ void ControlNet::run_cond_embed(Ctx& c, const half_t* image, int n, int H, int W
     a.release(mk);
 }
 
-int ControlNet::run(Ctx& c, const half_t* sample, const float* timesteps, View text_kv, int L, const half_t* add_text,
-                    const float* add_time_ids, int B, int H, int W, View emb, const std::vector<View>& sites, View mid) {
+int ControlNet::run(Ctx& c, const UNetCall& call, View text_kv, View emb, const std::vector<View>& sites, View mid) {
+    const int B = call.B, H = call.H, W = call.W, L = call.L;
     Arena& a = *c.arena;
     const int G = cfg.norm_num_groups;
     const size_t mk = a.mark();
     float* tproj = nullptr;
-    if (int rc = run_temb(c, timesteps, add_text, add_time_ids, B, &tproj)) return rc;
+    if (int rc = run_temb(c, call.timesteps, call.add_text, call.add_time_ids, B, &tproj)) return rc;
     // GroupNorm summaries: every hidden tensor is read by the next layer only (the zero conv needs none), so the ring
     ctx_gnpool_init(c, B, (long)H * W, G);
     auto stat = [&](int, long HW, int C) -> GnStatBuf* { return gn_wants_stats(HW, C, G) ? ctx_gnbuf(c) : nullptr; };
     GnStatBuf* xs = nullptr;
     // conv_in(sample) + conditioning embedding in one GEMM (the embedding rides on the residual epilogue)
-    run_conv_in(c, sample, B, H, W, sites[0], stat(0, (long)H * W, cfg.block_out_channels[0]), &emb, &xs);
+    run_conv_in(c, call.sample, B, H, W, sites[0], stat(0, (long)H * W, cfg.block_out_channels[0]), &emb, &xs);
     int h = H, w = W;
     View x = run_down(c, sites[0], xs, B, h, w, text_kv, L, tproj, [&](int si) { return sites[(size_t)si]; }, stat);
     run_mid(c, x, xs, B, h, w, text_kv, L, tproj, mid);
@@ -135,15 +135,16 @@ void UNet::set_controlnet(ControlNet* n) {
         n->attached = this;
     }
     cn = n;
-    cond_valid = false;
-    cnkv_valid = false;
-    dc_valid = false;
+    cond_tag.clear();
+    cnkv_tag.clear();
+    dc_tag.clear();
     reset_plans();
 }
 
-int UNet::run_controlnet(Ctx& c, const half_t* sample, const float* timesteps, const half_t* ehs, int L,
-                         const half_t* add_text, const float* add_time_ids, int B, int H, int W, const half_t* control,
-                         int n_ctrl, const std::vector<View>& sites, View mid) {
+int UNet::run_controlnet(Ctx& c, const UNetCall& call, const std::vector<View>& sites, View mid) {
+    const half_t* const ehs = call.ehs;
+    const half_t* const control = call.control;
+    const int B = call.B, H = call.H, W = call.W, L = call.L, n_ctrl = call.n_ctrl;
     Arena& a = *c.arena;
     const bool go = !c.dry;
     hipStream_t s = c.stream;
@@ -152,10 +153,9 @@ int UNet::run_controlnet(Ctx& c, const half_t* sample, const float* timesteps, c
     // ---- conditioning embedding [B H W, C0]: n_ctrl images computed once, sample b reads image b mod n_ctrl (diffusers'
     //      cat([image] * 2) under CFG); kept across the loop like the text K / V.  The planning pass always takes the
     //      computing branch (see the IP-Adapter's K / V). ----
-    const bool cached = kv_cache_on && !graph_enabled && cond_cache != nullptr;
-    half_t* cond = cached ? cond_cache : a.alloc_h((long)B * HWC);
-    const bool hit = cached && cond_valid && cond_src == control && cond_B == B && cond_n == n_ctrl && cond_H == H &&
-                     cond_W == W;
+    const bool cached = kv_cache_on && !graph_enabled && cond_cache.h() != nullptr;
+    half_t* cond = cached ? cond_cache.h() : a.alloc_h((long)B * HWC);
+    const bool hit = cached && cond_tag.matches(control, B, n_ctrl, H, W);
     if (c.dry || !hit) {
         cn->run_cond_embed(c, control, n_ctrl, H, W, View(cond, C0, C0));
         for (int b = n_ctrl; b < B && go && !c.err; b += n_ctrl) {
@@ -163,21 +163,21 @@ int UNet::run_controlnet(Ctx& c, const half_t* sample, const float* timesteps, c
                                                 hipMemcpyDeviceToDevice, s);
             if (e != hipSuccess) { set_error(hipGetErrorString(e)); c.err = 3; }
         }
-        if (cached && go && !c.err) { cond_valid = true; cond_src = control; cond_B = B; cond_n = n_ctrl; cond_H = H; cond_W = W; }
+        if (cached && go && !c.err) cond_tag.set(control, B, n_ctrl, H, W);
     }
     // ---- the ControlNet's own text K / V ----
     const int ctx = cfg.cross_attention_dim;
-    const bool kc = kv_cache_on && !graph_enabled && cnkv_cache != nullptr;
-    View kv(kc ? cnkv_cache : a.alloc_h((long)B * L * cn->kv_total), cn->kv_total, cn->kv_total);
-    const bool khit = kc && cnkv_valid && cnkv_src == ehs && cnkv_B == B && cnkv_L == L;
+    const bool kc = kv_cache_on && !graph_enabled && cnkv_cache.h() != nullptr;
+    View kv(kc ? cnkv_cache.h() : a.alloc_h((long)B * L * cn->kv_total), cn->kv_total, cn->kv_total);
+    const bool khit = kc && cnkv_tag.matches(ehs, B, L);
     if (c.dry || !khit) {
         op_conv(c, cn->kv_all, View(const_cast<half_t*>(ehs), ctx, ctx), B, L, 1, kv);
-        if (kc && go && !c.err) { cnkv_valid = true; cnkv_src = ehs; cnkv_B = B; cnkv_L = L; }
+        if (kc && go && !c.err) cnkv_tag.set(ehs, B, L);
     }
     // ---- the encoder, without IP-Adapter image attention (diffusers' ControlNet attention processors are plain) ----
     const View ip_kv = c.ip_kv;
     c.ip_kv = View();
-    const int rc = cn->run(c, sample, timesteps, kv, L, add_text, add_time_ids, B, H, W, View(cond, C0, C0), sites, mid);
+    const int rc = cn->run(c, call, kv, View(cond, C0, C0), sites, mid);
     c.ip_kv = ip_kv;
     return rc;
 }

@@ -1,6 +1,7 @@
 // Host-side runtime of the denoise engine: device memory arena, packed-weight store and the
 // execution context shared by the UNet and VAE graphs.  Plain C++ + HIP runtime; no torch.
 #pragma once
+#include <cstdlib>
 #include <functional>
 #include <map>
 #include <string>
@@ -42,6 +43,68 @@ class Arena {
     char* base_ = nullptr;
     size_t cap_ = 0, off_ = 0, peak_ = 0;
     bool dry_ = false, overflow_ = false;
+};
+
+// A device buffer a handle keeps across calls, outside the per-call arena: it only grows.  Growing frees the old block,
+// which launches enqueued earlier may still read, so the device is synchronised first; the contents are undefined
+// afterwards, which is why reserve() reports it -- the caller clears whatever says the contents are valid (CacheTag).
+// SD_DEVICEBUF_HOST_ALLOC (the host-only bookkeeping test) swaps the three HIP calls for malloc / free.
+class DeviceBuf {
+  public:
+    DeviceBuf() {}
+    DeviceBuf(const DeviceBuf&) = delete;
+    DeviceBuf& operator=(const DeviceBuf&) = delete;
+    ~DeviceBuf() { if (p_) dev_free(p_); }
+    // at least `bytes`; *grew = the buffer was reallocated (set before the allocation: it stays true when that fails,
+    // and the buffer is then empty)
+    int reserve(size_t bytes, bool* grew) {
+        *grew = bytes > cap_;
+        if (!*grew) return 0;
+        if (int rc = dev_sync()) return rc;
+        if (p_) dev_free(p_);
+        p_ = nullptr; cap_ = 0;
+        if (int rc = dev_alloc(&p_, bytes)) return rc;
+        cap_ = bytes;
+        return 0;
+    }
+    int release() {
+        if (!p_) return 0;
+        if (int rc = dev_sync()) return rc;
+        dev_free(p_);
+        p_ = nullptr; cap_ = 0;
+        return 0;
+    }
+    char* data() const { return static_cast<char*>(p_); }
+    half_t* h() const { return static_cast<half_t*>(p_); }
+    size_t capacity() const { return cap_; }
+
+  private:
+#ifdef SD_DEVICEBUF_HOST_ALLOC
+    static int dev_sync() { return 0; }
+    static void dev_free(void* p) { free(p); }
+    static int dev_alloc(void** p, size_t bytes) { *p = malloc(bytes); return *p ? 0 : 3; }
+#else
+    static int dev_sync() { SD_HIP_CHECK(hipDeviceSynchronize()); return 0; }
+    static void dev_free(void* p) { (void)hipFree(p); }
+    static int dev_alloc(void** p, size_t bytes) { SD_HIP_CHECK(hipMalloc(p, bytes)); return 0; }
+#endif
+    void* p_ = nullptr;
+    size_t cap_ = 0;
+};
+
+// What the contents of a cache were computed from: the source pointer and up to four dims (each cache says which).  A
+// cache is read when matches() holds and filled -- then set() -- when it does not; clear() is every invalidation.
+struct CacheTag {
+    bool valid = false;
+    const void* src = nullptr;
+    int d[4] = {0, 0, 0, 0};
+    bool matches(const void* s, int d0, int d1 = 0, int d2 = 0, int d3 = 0) const {
+        return valid && src == s && d[0] == d0 && d[1] == d1 && d[2] == d2 && d[3] == d3;
+    }
+    void set(const void* s, int d0, int d1 = 0, int d2 = 0, int d3 = 0) {
+        valid = true; src = s; d[0] = d0; d[1] = d1; d[2] = d2; d[3] = d3;
+    }
+    void clear() { valid = false; }
 };
 
 struct ConvW {          // conv or linear, packed [rows_pad][K] fp16 + fp32 bias (padded)
@@ -175,6 +238,32 @@ struct Ctx {
 inline int ctx_live(const Ctx& c, int N) { return c.pag && !c.pag->widened ? c.pag->Nq : N; }
 void ctx_gnpool_init(Ctx& c, int N, long HW_max, int G);
 GnStatBuf* ctx_gnbuf(Ctx& c);       // next ring slot with `st` cleared; nullptr when the pool is not set up
+
+// One call of a model on its arena.  `body(ctx)` issues the model's launches, or, on a dry context, only its allocations.
+// When `key` is not the one `planned` remembers, a dry pass sizes the arena first: an error of that pass returns before
+// anything is allocated; growing the slab frees the old one, so the device is synchronised first (nothing enqueued
+// earlier may still use it); then the key is remembered, whatever the live pass returns.  The arena only grows, so a
+// remembered plan stays good while calls with other keys run.  Returns body's result, or 2 when the live pass asked for
+// more than was planned.
+template <class Key, class Body>
+int plan_and_run(Arena& arena, hipStream_t stream, Key& planned, const Key& key, const char* model, Body body) {
+    if (!(key == planned)) {
+        Ctx dry{&arena, stream, true};
+        arena.begin(true);
+        int rc = body(dry);
+        if (rc) return rc;
+        if (arena.peak() > arena.capacity()) {
+            SD_HIP_CHECK(hipDeviceSynchronize());
+            if ((rc = arena.reserve(arena.peak()))) return rc;
+        }
+        planned = key;
+    }
+    Ctx ctx{&arena, stream, false};
+    arena.begin(false);
+    const int rc = body(ctx);
+    if (!rc && arena.overflow()) { set_error(std::string(model) + ": workspace overflow (planner bug)"); return 2; }
+    return rc;
+}
 
 // ---- optional per-launch timing (bench.py's live roofline): HIP events on the launch stream ----
 struct ProfAgg { double flops = 0, bytes = 0, ms = 0; long launches = 0; };

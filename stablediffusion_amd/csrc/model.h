@@ -81,6 +81,7 @@ bool run_xformer_tail(Ctx& c, const Xformer& t, View t3, const RowStat& st_t3, V
                       View out, const ConvFuse& fo);
 
 struct UNet;
+struct UNetCall;
 
 // Every attn2 of a UNet topology as (transformer block prefix, channels): diffusers' attn_processors order
 // (down, up, mid) with mid_last, the engine's kv_all order (down, mid, up) without.
@@ -200,8 +201,8 @@ struct ControlNet : Encoder {
     void run_cond_embed(Ctx& c, const half_t* image, int n, int H, int W, View out);
     // the encoder on (sample, timestep, text) with emb added after conv_in: the pre-zero-conv hidden tensors of every
     // skip (sites[i]) and of the mid block (mid), all [B h w, C] in the arena
-    int run(Ctx& c, const half_t* sample, const float* timesteps, View text_kv, int L, const half_t* add_text,
-            const float* add_time_ids, int B, int H, int W, View emb, const std::vector<View>& sites, View mid);
+    // (of the call: sample, timesteps, L, add_text, add_time_ids, B, H, W; text_kv = the ControlNet's own projection)
+    int run(Ctx& c, const UNetCall& call, View text_kv, View emb, const std::vector<View>& sites, View mid);
 };
 
 // Whether a UNet topology allows the shared CFG prefix: no per-sample additional embedding (text_time makes the time
@@ -222,17 +223,63 @@ struct PagIn {
     bool late = false;
 };
 
+// One forward of a UNet: what every entry (the six sd_unet_forward* functions, forward_cfg, forward_pag, the graph path)
+// hands to UNet::forward and what forward hands, unchanged, to the planning pass and the live pass of UNet::run.  The
+// defaults are "feature not used".
+struct UNetCall {
+    const half_t* sample = nullptr;         // [B, C, H, W] (unused with cfg_in)
+    const float* timesteps = nullptr;       // [B] ([B / 2] with cfg_in)
+    const half_t* ehs = nullptr;            // [B, L, cross_attention_dim]
+    int L = 0;
+    const half_t* add_text = nullptr;       // text_time conditioning: [B, pooled] and [B, num_time_ids]
+    const float* add_time_ids = nullptr;
+    half_t* out = nullptr;                  // [B, C_out, H, W]
+    int B = 0, H = 0, W = 0;
+    const half_t* image_embeds = nullptr;   // IP-Adapter: n_img image prompts per sample
+    int n_img = 0;
+    const half_t* control = nullptr;        // ControlNet: n_ctrl control images [n_ctrl, 3, 8H, 8W] and the residuals' scale
+    int n_ctrl = 0;
+    float cn_scale = 0.f;
+    const float* tcond = nullptr;           // timestep_cond [B, time_cond_proj_dim] of a guidance-embedded UNet
+    const CfgIn* cfg_in = nullptr;          // shared-CFG mode (forward_cfg)
+    const PagIn* pag = nullptr;             // perturbed-attention mode (forward_pag)
+};
+
+// What the arena plan of a forward depends on.  Compared field by field: a plan is redone exactly when one differs from
+// the last one planned in the same DeepCache mode.
+struct PlanKey {
+    int B = 0, H = 0, W = 0, L = 0;         // (B = 0: nothing planned)
+    bool kv_cache = false;                  // the text K/V live in their persistent buffer, not in the arena
+    int ip_tokens = 0;                      // image tokens per sample of the attached IP-Adapter, 0 without
+    bool cfg_share = false;
+    int pag_groups = 0;                     // forward_pag: 1 or 2, and whether the perturbed group is widened late
+    bool pag_late = false;
+    int n_ctrl = 0;                         // control images of a ControlNet that runs, 0 when none does
+    int dc_depth = 0;                       // DeepCache depth of a store / reuse forward (the plain one ignores it)
+    bool operator==(const PlanKey& o) const {
+        return B == o.B && H == o.H && W == o.W && L == o.L && kv_cache == o.kv_cache && ip_tokens == o.ip_tokens &&
+               cfg_share == o.cfg_share && pag_groups == o.pag_groups && pag_late == o.pag_late && n_ctrl == o.n_ctrl &&
+               dc_depth == o.dc_depth;
+    }
+};
+// What a captured graph depends on (timestep_cond's width is the configuration's: its presence changes the launches).
+struct GraphKey {
+    int B = 0, H = 0, W = 0, L = 0;
+    bool tcond = false;
+    bool operator==(const GraphKey& o) const { return B == o.B && H == o.H && W == o.W && L == o.L && tcond == o.tcond; }
+};
+
 struct UNet : Encoder {
     explicit UNet(const sd_unet_config& c);
     int finalize();
+    // forward_pag / forward_cfg take the call of the UN-duplicated latents: lat.sample [B, C, H, W], lat.timesteps [B],
+    // lat.B = B, while ehs / add_text / add_time_ids / image_embeds / out hold the rows of the forward they build.
     // Perturbed-attention guidance.  One forward on [uncond ; text ; perturbed] (cfg) or [text ; perturbed] from B
     // latents and timesteps; ehs / add_text / add_time_ids hold the un-perturbed groups' rows, the perturbed group takes
     // the text group's.  share: widen to the perturbed group at the first flagged transformer where it is not the
     // network's first (after the CFG-shared start where forward_cfg would take it); otherwise, and under
     // SD_NO_PAG_SHARE, duplicate up front.
-    int forward_pag(const half_t* latents, const float* timesteps, const half_t* ehs, int L, const half_t* add_text,
-                    const float* add_time_ids, float in_scale, bool cfg_on, bool share, half_t* out, int B, int H, int W,
-                    hipStream_t stream);
+    int forward_pag(const UNetCall& lat, float in_scale, bool cfg_on, bool share, hipStream_t stream);
     int set_pag_layers(const char* const* site_keys, int count);
     // every transformer in execution order with its site key ("down_blocks.i.attentions.j", "mid_block.attentions.0", ...)
     std::vector<std::pair<std::string, Xformer*>> xformer_sites();
@@ -240,17 +287,10 @@ struct UNet : Encoder {
     // hold 2B rows, negative half first.  Runs the CFG-shared prefix once per latent when `share`, the topology and the
     // engine's state allow (unet_cfg_share_eligible, no graph replay, no ControlNet, SD_GN_CAT and SD_NO_CFG_SHARE unset);
     // otherwise duplicates into a buffer of its own and runs forward(): bit for bit what callers did before.
-    int forward_cfg(const half_t* latents, const float* timesteps, const half_t* ehs, int L, const half_t* add_text,
-                    const float* add_time_ids, const half_t* image_embeds, int n_img, float in_scale, bool share,
-                    half_t* out, int B, int H, int W, hipStream_t stream);
+    int forward_cfg(const UNetCall& lat, float in_scale, bool share, hipStream_t stream);
     bool cfg_share_active(bool share) const;
-    char* cfg_slab = nullptr;           // forward_cfg's duplicated latents + timesteps when it does not share
-    size_t cfg_cap = 0;
-    int forward(const half_t* sample, const float* timesteps, const half_t* ehs, int L,
-                const half_t* add_text, const float* add_time_ids, half_t* out, int B, int H, int W,
-                hipStream_t stream, const half_t* image_embeds = nullptr, int n_img = 0,
-                const half_t* control = nullptr, int n_ctrl = 0, float cn_scale = 0.f, const CfgIn* cfg_in = nullptr,
-                const float* tcond = nullptr, const PagIn* pag = nullptr);
+    DeviceBuf cfg_slab;                 // forward_cfg's / forward_pag's duplicated latents + timesteps when they do not share
+    int forward(const UNetCall& call, hipStream_t stream);
     void set_ip_adapter(IPAdapter* a);
     void set_controlnet(ControlNet* n);
 
@@ -258,11 +298,8 @@ struct UNet : Encoder {
     bool finalized = false;
     // the last planned key of each DeepCache mode: a loop alternates store / reuse steps, and one key would make a dry
     // pass at every switch (the arena only grows, so a plan made for one mode stays good while another runs)
-    long planned_key[3] = {-1, -1, -1};
-    long planned_cn[3] = {-1, -1, -1};
-    int planned_depth[3] = {0, 0, 0};
-    int planned_pag = 0;
-    void reset_plans() { for (int m = 0; m < 3; ++m) planned_key[m] = planned_cn[m] = -1; }
+    PlanKey planned[3];
+    void reset_plans() { for (PlanKey& k : planned) k = PlanKey(); }
 
     // ---- optional hipGraph replay of the whole forward (sd_unet_use_graph) ----
     // One captured graph per input shape; inputs / output are staged through engine-owned buffers so
@@ -273,50 +310,35 @@ struct UNet : Encoder {
     hipStream_t gstream = nullptr;
     hipEvent_t ev_in = nullptr, ev_out = nullptr;
     hipGraphExec_t gexec = nullptr;
-    long graph_key = -1;
-    char* io_slab = nullptr;
-    size_t io_cap = 0;
-    int forward_graph(const half_t* sample, const float* timesteps, const half_t* ehs, int L, const half_t* add_text,
-                      const float* add_time_ids, half_t* out, int B, int H, int W, hipStream_t stream,
-                      const float* tcond = nullptr);
+    GraphKey graph_key;
+    DeviceBuf io_slab;
+    int forward_graph(const UNetCall& call, hipStream_t stream);
     ~UNet();
 
     // ---- text K/V kept across the forwards of one denoise loop (sd_unet_text_kv_cache) ----
     // encoder_hidden_states is constant over the loop, so the stacked to_k / to_v projection of every
     // cross-attention block is computed by the first forward and reused by the other 49.
     // Valid for one (pointer, batch, length); the caller invalidates when the CONTENTS behind the pointer change.
-    bool kv_cache_on = false, kv_valid = false;
-    half_t* kv_cache = nullptr;
-    size_t kv_cap = 0;
-    const half_t* kv_src = nullptr;
-    int kv_B = 0, kv_L = 0;
-    int kv_pag = 0;                     // images of the perturbed group whose copy the cache holds (forward_pag), else 0
+    bool kv_cache_on = false;
+    DeviceBuf kv_cache;
+    CacheTag kv_tag;                    // (ehs; B, L, images of the perturbed group whose copy it holds (forward_pag) or 0)
 
     // ---- IP-Adapter (sd_unet_set_ip_adapter): nullptr = plain cross-attention, the forward as without the feature.
     // Its stacked K / V of the image tokens follow the text K / V's cache rules: kept across the forwards of one loop
     // for one (pointer, batch, images per prompt), invalidated by every sd_unet_text_kv_cache call, not under graphs.
     IPAdapter* ip = nullptr;
     float ip_scale = 1.f;
-    bool ipkv_valid = false;
-    half_t* ipkv_cache = nullptr;
-    size_t ipkv_cap = 0;
-    const half_t* ipkv_src = nullptr;
-    int ipkv_B = 0, ipkv_n = 0;
+    DeviceBuf ipkv_cache;
+    CacheTag ipkv_tag;                  // (image_embeds; B, n_img)
 
     // ---- ControlNet (sd_unet_set_controlnet): nullptr = the forward as without the feature.  Its conditioning
     // embedding ([B H W, C0], sample b from control image b mod n_ctrl) and its text K / V follow the text K / V's cache
     // rules: kept across the forwards of one loop for one (pointer, B, n_ctrl, H, W) / (pointer, B, L), invalidated by
     // every sd_unet_text_kv_cache call and by set_controlnet, not under graphs.
     ControlNet* cn = nullptr;
-    bool cond_valid = false, cnkv_valid = false;
-    half_t* cond_cache = nullptr;
-    size_t cond_cap = 0;
-    const half_t* cond_src = nullptr;
-    int cond_B = 0, cond_n = 0, cond_H = 0, cond_W = 0;
-    half_t* cnkv_cache = nullptr;
-    size_t cnkv_cap = 0;
-    const half_t* cnkv_src = nullptr;
-    int cnkv_B = 0, cnkv_L = 0;
+    DeviceBuf cond_cache, cnkv_cache;
+    CacheTag cond_tag;                  // (control; B, n_ctrl, H, W)
+    CacheTag cnkv_tag;                  // (ehs; B, L)
 
     // ---- FreeU (sd_unet_set_freeu): off = the forward as without the feature.  On, every resnet of up blocks 0 and 1
     // gets one in-place launch on its concatenation buffer before norm1 reads it: (b1, s1) in block 0, (b2, s2) in
@@ -331,10 +353,8 @@ struct UNet : Encoder {
     // down block 0 (rewriting the buffer's skip half), layers L-d..L of the last up block and the tail.  Valid for one
     // (B, H, W, shared CFG prefix or not); not under graphs, not with a running ControlNet.
     int dc_depth = 0, dc_mode = 0;
-    bool dc_valid = false, dc_cfg = false;
-    half_t* dc_buf = nullptr;
-    size_t dc_cap = 0;
-    int dc_B = 0, dc_H = 0, dc_W = 0;
+    DeviceBuf dc_buf;
+    CacheTag dc_tag;                    // (no pointer; B, H, W, shared CFG prefix or not) of the stored step
     int set_deep_cache(int depth);
 
     ConvW conv_out;
@@ -344,15 +364,10 @@ struct UNet : Encoder {
     std::vector<ConvW> up_us;
 
   private:
-    int run(Ctx& c, const half_t* sample, const float* timesteps, const half_t* ehs, int L,
-            const half_t* add_text, const float* add_time_ids, half_t* out, int B, int H, int W,
-            const half_t* image_embeds = nullptr, int n_img = 0, const half_t* control = nullptr, int n_ctrl = 0,
-            float cn_scale = 0.f, const CfgIn* cfg_in = nullptr, const float* tcond = nullptr, int dc = 0,
-            const PagIn* pag = nullptr);
+    // dc: the DeepCache mode of this forward (SD_DC_*)
+    int run(Ctx& c, const UNetCall& call, int dc = 0);
     // ControlNet step of run(): its hidden tensors into sites / mid (allocated by the caller)
-    int run_controlnet(Ctx& c, const half_t* sample, const float* timesteps, const half_t* ehs, int L,
-                       const half_t* add_text, const float* add_time_ids, int B, int H, int W, const half_t* control,
-                       int n_ctrl, const std::vector<View>& sites, View mid);
+    int run_controlnet(Ctx& c, const UNetCall& call, const std::vector<View>& sites, View mid);
 };
 
 struct VAE {

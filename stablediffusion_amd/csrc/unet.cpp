@@ -472,22 +472,10 @@ int IPAdapter::project(const half_t* image_embeds, long rows, half_t* tok, hipSt
     if (!finalized) { set_error("ip adapter: project before finalize"); return 2; }
     if (rows < 1 || rows > 4096) { set_error("ip adapter: project takes 1..4096 images"); return 1; }
     const long key = rows * 1024 + t_feat;
-    if (key != planned_rows) {
-        Ctx dry{&arena, stream, true};
-        arena.begin(true);
-        run_tokens(dry, image_embeds, rows, tok);
-        if (dry.err) return dry.err;
-        if (arena.peak() > arena.capacity()) {
-            SD_HIP_CHECK(hipDeviceSynchronize());
-            if (int rc = arena.reserve(arena.peak())) return rc;
-        }
-        planned_rows = key;
-    }
-    Ctx ctx{&arena, stream, false};
-    arena.begin(false);
-    run_tokens(ctx, image_embeds, rows, tok);
-    if (!ctx.err && arena.overflow()) { set_error("ip adapter: workspace overflow (planner bug)"); return 2; }
-    return ctx.err;
+    return plan_and_run(arena, stream, planned_rows, key, "ip adapter", [&](Ctx& c) {
+        run_tokens(c, image_embeds, rows, tok);
+        return c.err;
+    });
 }
 
 void UNet::set_ip_adapter(IPAdapter* a) {
@@ -498,8 +486,8 @@ void UNet::set_ip_adapter(IPAdapter* a) {
         a->attached = this;
     }
     ip = a;
-    ipkv_valid = false;
-    dc_valid = false;
+    ipkv_tag.clear();
+    dc_tag.clear();
     reset_plans();
 }
 
@@ -913,10 +901,15 @@ void Encoder::run_mid(Ctx& c, View x, GnStatBuf* xs, int B, int h, int w, View t
 
 int Encoder::num_skips() const { return 1 + cfg.num_blocks * cfg.layers_per_block + (cfg.num_blocks - 1); }
 
-int UNet::run(Ctx& c, const half_t* sample, const float* timesteps, const half_t* ehs, int L,
-              const half_t* add_text, const float* add_time_ids, half_t* out, int B, int H, int W,
-              const half_t* image_embeds, int n_img, const half_t* control, int n_ctrl, float cn_scale, const CfgIn* cfg_in,
-              const float* tcond, int dc, const PagIn* pag) {
+int UNet::run(Ctx& c, const UNetCall& call, int dc) {
+    const half_t* sample = call.sample;
+    const half_t* const ehs = call.ehs;
+    const half_t* const image_embeds = call.image_embeds;
+    half_t* const out = call.out;
+    const int L = call.L, B = call.B, H = call.H, W = call.W, n_img = call.n_img;
+    const float cn_scale = call.cn_scale;
+    const CfgIn* const cfg_in = call.cfg_in;
+    const PagIn* const pag = call.pag;
     Arena& a = *c.arena;
     const int nb = cfg.num_blocks;
     const int* boc = cfg.block_out_channels;
@@ -952,7 +945,7 @@ int UNet::run(Ctx& c, const half_t* sample, const float* timesteps, const half_t
     }
 
     float* tproj = nullptr;
-    if (int rc = run_temb(c, timesteps, add_text, add_time_ids, Bp, &tproj, B, tcond)) return rc;
+    if (int rc = run_temb(c, call.timesteps, call.add_text, call.add_time_ids, Bp, &tproj, B, call.tcond)) return rc;
     if (cfg_in) {
         RowDupSeg g;
         g.src = tproj; g.dst = tproj + (long)Bp * temb_total;
@@ -963,12 +956,12 @@ int UNet::run(Ctx& c, const half_t* sample, const float* timesteps, const half_t
     // ---- text K/V of every cross-attention block in one GEMM: [B*L, ctx] x [ctx, sum 2C] ----
     //      (forward_pag: projected for the Nq rows of ehs; the perturbed group gets a copy of the text group's rows, which
     //      the cache keeps with the rest.  That copy, and up front the group's tproj rows, are one row_dup launch here.)
-    const bool kv_cached = kv_cache_on && !graph_enabled && kv_cache != nullptr;
-    View text_kv(kv_cached ? kv_cache : a.alloc_h((long)B * L * kv_total), kv_total, kv_total);
+    const bool kv_cached = kv_cache_on && !graph_enabled && kv_cache.h() != nullptr;
+    View text_kv(kv_cached ? kv_cache.h() : a.alloc_h((long)B * L * kv_total), kv_total, kv_total);
     std::vector<RowDupSeg> pag_now;
-    if (!(kv_cached && kv_valid && kv_src == ehs && kv_B == B && kv_L == L && kv_pag == Ng)) {
+    if (!(kv_cached && kv_tag.matches(ehs, B, L, Ng))) {
         op_conv(c, kv_all, View(const_cast<half_t*>(ehs), cfg.cross_attention_dim, cfg.cross_attention_dim), Nq, L, 1, text_kv);
-        if (kv_cached && go && !c.err) { kv_valid = true; kv_src = ehs; kv_B = B; kv_L = L; kv_pag = Ng; }
+        if (kv_cached && go && !c.err) kv_tag.set(ehs, B, L, Ng);
         if (pag) {
             RowDupSeg g;
             g.src = text_kv.p + (long)(Nq - Ng) * L * kv_total; g.dst = text_kv.p + (long)Nq * L * kv_total;
@@ -996,18 +989,18 @@ int UNet::run(Ctx& c, const half_t* sample, const float* timesteps, const half_t
     if (ip && image_embeds) {
         const int ctx = cfg.cross_attention_dim, T_ip = n_img * ip->n_tok;
         const long rows = (long)B * n_img, ntc = (long)ip->n_tok * ctx;
-        const bool ip_cached = kv_cache_on && !graph_enabled && ipkv_cache != nullptr;
-        View ip_kv(ip_cached ? ipkv_cache : a.alloc_h((long)B * T_ip * ip->kv_total), ip->kv_total, ip->kv_total);
+        const bool ip_cached = kv_cache_on && !graph_enabled && ipkv_cache.h() != nullptr;
+        View ip_kv(ip_cached ? ipkv_cache.h() : a.alloc_h((long)B * T_ip * ip->kv_total), ip->kv_total, ip->kv_total);
         // the planning pass always takes the computing branch: its temporaries live between mark and release, so the
         // live pass skipping them (cache hit) allocates less and every later tensor keeps its planned address
-        const bool hit = ip_cached && ipkv_valid && ipkv_src == image_embeds && ipkv_B == B && ipkv_n == n_img;
+        const bool hit = ip_cached && ipkv_tag.matches(image_embeds, B, n_img);
         if (c.dry || !hit) {
             const size_t mk = a.mark();
             half_t* tok = a.alloc_h(rows * ntc);
             ip->run_tokens(c, image_embeds, rows, tok);
             op_conv(c, ip->kv_all, View(tok, ctx, ctx), B, T_ip, 1, ip_kv);
             a.release(mk);
-            if (ip_cached && go && !c.err) { ipkv_valid = true; ipkv_src = image_embeds; ipkv_B = B; ipkv_n = n_img; }
+            if (ip_cached && go && !c.err) ipkv_tag.set(image_embeds, B, n_img);
         }
         c.ip_kv = ip_kv;
         c.ip_T = T_ip;
@@ -1036,7 +1029,7 @@ int UNet::run(Ctx& c, const half_t* sample, const float* timesteps, const half_t
                 ct.c1 = (j == 0) ? prev : out_ch;
                 ct.h = h; ct.w = w;
                 const int kc = (int)cats.size();
-                ct.p = kc == dc_k ? dc_buf : (reuse && kc < dc_k) ? nullptr : a.alloc_h((long)B * h * w * (ct.c1 + ct.c2));
+                ct.p = kc == dc_k ? dc_buf.h() : (reuse && kc < dc_k) ? nullptr : a.alloc_h((long)B * h * w * (ct.c1 + ct.c2));
                 cats.push_back(ct);
             }
             if (i != nb - 1) { h *= 2; w *= 2; }
@@ -1069,7 +1062,7 @@ int UNet::run(Ctx& c, const half_t* sample, const float* timesteps, const half_t
     // ---- ControlNet: its encoder on the same sample, timestep and text.  The pre-zero-conv hidden tensors of every
     //      skip and of the mid block live above the concatenation buffers (released after the residual adds); the
     //      ControlNet runs on a GroupNorm ring of its own, this forward's ring is restored after it ----
-    const bool use_cn = cn && control && cn_scale != 0.f && !cfg_in;
+    const bool use_cn = cn && call.control && cn_scale != 0.f && !cfg_in;
     const size_t cn_mark = a.mark();
     std::vector<View> cn_sites;
     std::vector<int> cn_rows;
@@ -1090,8 +1083,7 @@ int UNet::run(Ctx& c, const half_t* sample, const float* timesteps, const half_t
         GnStatBuf ring[Ctx::kGnPool];
         for (int i = 0; i < Ctx::kGnPool; ++i) ring[i] = c.gnpool[i];
         const int ring_next = c.gn_next, ring_groups = c.gn_groups;
-        if (int rc = run_controlnet(c, sample, timesteps, ehs, L, add_text, add_time_ids, B, H, W, control, n_ctrl, cn_sites,
-                                    cn_mid)) return rc;
+        if (int rc = run_controlnet(c, call, cn_sites, cn_mid)) return rc;
         for (int i = 0; i < Ctx::kGnPool; ++i) c.gnpool[i] = ring[i];
         c.gn_next = ring_next; c.gn_groups = ring_groups;
     }
@@ -1303,18 +1295,21 @@ int UNet::run(Ctx& c, const half_t* sample, const float* timesteps, const half_t
     return c.err;
 }
 
+// A persistent buffer grows before the pass that uses it: a growth leaves the contents undefined, so it clears the tag
+// that says what they hold (a CacheTag, or the key of the captured graph that reads the staging buffer).
+template <class Tag>
+static int reserve_cache(DeviceBuf& buf, size_t bytes, Tag& tag) {
+    bool grew = false;
+    const int rc = buf.reserve(bytes, &grew);
+    if (grew) tag = Tag();
+    return rc;
+}
+
 UNet::~UNet() {
     if (gexec) (void)hipGraphExecDestroy(gexec);
     if (ev_in) (void)hipEventDestroy(ev_in);
     if (ev_out) (void)hipEventDestroy(ev_out);
     if (gstream) (void)hipStreamDestroy(gstream);
-    if (io_slab) (void)hipFree(io_slab);
-    if (kv_cache) (void)hipFree(kv_cache);
-    if (dc_buf) (void)hipFree(dc_buf);
-    if (ipkv_cache) (void)hipFree(ipkv_cache);
-    if (cond_cache) (void)hipFree(cond_cache);
-    if (cnkv_cache) (void)hipFree(cnkv_cache);
-    if (cfg_slab) (void)hipFree(cfg_slab);
     if (ip) ip->attached = nullptr;
     if (cn) cn->attached = nullptr;
 }
@@ -1322,9 +1317,9 @@ UNet::~UNet() {
 // Graph path: stage I/O through engine-owned buffers, capture the forward once per shape on an
 // engine-owned stream, afterwards replay it with one hipGraphLaunch fenced against the caller's
 // stream by two events.
-int UNet::forward_graph(const half_t* sample, const float* timesteps, const half_t* ehs, int L,
-                        const half_t* add_text, const float* add_time_ids, half_t* out, int B, int H, int W,
-                        hipStream_t stream, const float* tcond) {
+int UNet::forward_graph(const UNetCall& call, hipStream_t stream) {
+    const int B = call.B, H = call.H, W = call.W, L = call.L;
+    const float* const tcond = call.tcond;
     const bool sdxl = cfg.addition_time_embed_dim > 0;
     const int pdim = sdxl ? cfg.projection_class_embeddings_input_dim - num_time_ids() * cfg.addition_time_embed_dim : 0;
     const int nid = sdxl ? num_time_ids() : 0;
@@ -1339,14 +1334,8 @@ int UNet::forward_graph(const half_t* sample, const float* timesteps, const half
         SD_HIP_CHECK(hipEventCreateWithFlags(&ev_in, hipEventDisableTiming));
         SD_HIP_CHECK(hipEventCreateWithFlags(&ev_out, hipEventDisableTiming));
     }
-    if (need > io_cap) {
-        SD_HIP_CHECK(hipDeviceSynchronize());
-        if (io_slab) (void)hipFree(io_slab);
-        io_slab = nullptr; io_cap = 0; graph_key = -1;
-        SD_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&io_slab), need));
-        io_cap = need;
-    }
-    char* ptr = io_slab;
+    if (int rc = reserve_cache(io_slab, need, graph_key)) return rc;
+    char* ptr = io_slab.data();
     half_t* g_sample = reinterpret_cast<half_t*>(ptr); ptr += n_sample;
     float* g_t = reinterpret_cast<float*>(ptr); ptr += n_t;
     half_t* g_ehs = reinterpret_cast<half_t*>(ptr); ptr += n_ehs;
@@ -1354,23 +1343,28 @@ int UNet::forward_graph(const half_t* sample, const float* timesteps, const half
     float* g_ids = sdxl ? reinterpret_cast<float*>(ptr) : nullptr; ptr += n_ids;
     float* g_tc = tcond ? reinterpret_cast<float*>(ptr) : nullptr; ptr += n_tc;
     half_t* g_out = reinterpret_cast<half_t*>(ptr);
-    SD_HIP_CHECK(hipMemcpyAsync(g_sample, sample, (size_t)B * cfg.in_channels * H * W * 2, hipMemcpyDeviceToDevice, stream));
-    SD_HIP_CHECK(hipMemcpyAsync(g_t, timesteps, (size_t)B * 4, hipMemcpyDeviceToDevice, stream));
-    SD_HIP_CHECK(hipMemcpyAsync(g_ehs, ehs, (size_t)B * L * cfg.cross_attention_dim * 2, hipMemcpyDeviceToDevice, stream));
+    SD_HIP_CHECK(hipMemcpyAsync(g_sample, call.sample, (size_t)B * cfg.in_channels * H * W * 2, hipMemcpyDeviceToDevice, stream));
+    SD_HIP_CHECK(hipMemcpyAsync(g_t, call.timesteps, (size_t)B * 4, hipMemcpyDeviceToDevice, stream));
+    SD_HIP_CHECK(hipMemcpyAsync(g_ehs, call.ehs, (size_t)B * L * cfg.cross_attention_dim * 2, hipMemcpyDeviceToDevice, stream));
     if (sdxl) {
-        if (!add_text || !add_time_ids) { set_error("unet: add_text / add_time_ids required for text_time conditioning"); return 1; }
-        SD_HIP_CHECK(hipMemcpyAsync(g_text, add_text, (size_t)B * pdim * 2, hipMemcpyDeviceToDevice, stream));
-        SD_HIP_CHECK(hipMemcpyAsync(g_ids, add_time_ids, (size_t)B * nid * 4, hipMemcpyDeviceToDevice, stream));
+        if (!call.add_text || !call.add_time_ids) { set_error("unet: add_text / add_time_ids required for text_time conditioning"); return 1; }
+        SD_HIP_CHECK(hipMemcpyAsync(g_text, call.add_text, (size_t)B * pdim * 2, hipMemcpyDeviceToDevice, stream));
+        SD_HIP_CHECK(hipMemcpyAsync(g_ids, call.add_time_ids, (size_t)B * nid * 4, hipMemcpyDeviceToDevice, stream));
     }
     if (tcond) SD_HIP_CHECK(hipMemcpyAsync(g_tc, tcond, (size_t)B * cfg.time_cond_proj_dim * 4, hipMemcpyDeviceToDevice, stream));
-    // (timestep_cond's width is the configuration's: its presence is what changes the captured launches)
-    const long key = ((long)B << 40) ^ ((long)H << 20) ^ (long)W ^ ((long)L << 52) ^ (tcond ? (1L << 62) : 0);
+    GraphKey key;
+    key.B = B; key.H = H; key.W = W; key.L = L; key.tcond = tcond != nullptr;
+    // the same forward on the staged copies
+    UNetCall staged;
+    staged.sample = g_sample; staged.timesteps = g_t; staged.ehs = g_ehs; staged.L = L;
+    staged.add_text = g_text; staged.add_time_ids = g_ids; staged.out = g_out;
+    staged.B = B; staged.H = H; staged.W = W; staged.tcond = g_tc;
     int rc = 0;
-    if (key != graph_key || !gexec) {
+    if (!(key == graph_key) || !gexec) {
         // (re)plan + one eager run on the caller's stream: sets every kernel's LDS attribute (not
         // allowed while capturing) and produces this call's result
         graph_enabled = false;
-        rc = forward(g_sample, g_t, g_ehs, L, g_text, g_ids, g_out, B, H, W, stream, nullptr, 0, nullptr, 0, 0.f, nullptr, g_tc);
+        rc = forward(staged, stream);
         graph_enabled = true;
         if (rc) return rc;
         if (gexec) { (void)hipGraphExecDestroy(gexec); gexec = nullptr; }
@@ -1378,7 +1372,7 @@ int UNet::forward_graph(const half_t* sample, const float* timesteps, const half
         SD_HIP_CHECK(hipStreamBeginCapture(gstream, hipStreamCaptureModeRelaxed));
         Ctx ctx{&arena, gstream, false};
         arena.begin(false);
-        rc = run(ctx, g_sample, g_t, g_ehs, L, g_text, g_ids, g_out, B, H, W, nullptr, 0, nullptr, 0, 0.f, nullptr, g_tc);
+        rc = run(ctx, staged);
         hipError_t e = hipStreamEndCapture(gstream, &graph);
         if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
         if (e != hipSuccess) { set_error(std::string("hipStreamEndCapture: ") + hipGetErrorString(e)); return 3; }
@@ -1393,14 +1387,19 @@ int UNet::forward_graph(const half_t* sample, const float* timesteps, const half
         SD_HIP_CHECK(hipEventRecord(ev_out, gstream));
         SD_HIP_CHECK(hipStreamWaitEvent(stream, ev_out, 0));
     }
-    SD_HIP_CHECK(hipMemcpyAsync(out, g_out, (size_t)B * cfg.out_channels * H * W * 2, hipMemcpyDeviceToDevice, stream));
+    SD_HIP_CHECK(hipMemcpyAsync(call.out, g_out, (size_t)B * cfg.out_channels * H * W * 2, hipMemcpyDeviceToDevice, stream));
     return 0;
 }
 
-int UNet::forward(const half_t* sample, const float* timesteps, const half_t* ehs, int L, const half_t* add_text,
-                  const float* add_time_ids, half_t* out, int B, int H, int W, hipStream_t stream,
-                  const half_t* image_embeds, int n_img, const half_t* control, int n_ctrl, float cn_scale, const CfgIn* cfg_in,
-                  const float* tcond, const PagIn* pag) {
+int UNet::forward(const UNetCall& in, hipStream_t stream) {
+    // the one copy both passes of run() receive: n_img, n_ctrl and cn_scale are normalised on it below
+    UNetCall call = in;
+    const int B = call.B, H = call.H, W = call.W, L = call.L;
+    const half_t* const image_embeds = call.image_embeds;
+    const half_t* const control = call.control;
+    const float* const tcond = call.tcond;
+    const CfgIn* const cfg_in = call.cfg_in;
+    const PagIn* const pag = call.pag;
     if (!finalized) { set_error("unet: forward before finalize"); return 2; }
     if (pag && (B % (pag->groups + 1) != 0 || graph_enabled || control || image_embeds || tcond || dc_mode != SD_DC_PLAIN)) {
         set_error("unet: perturbed-attention forward not available for this call");
@@ -1419,23 +1418,23 @@ int UNet::forward(const half_t* sample, const float* timesteps, const half_t* eh
     if (ip && !image_embeds && !pag) { set_error("unet: an IP-Adapter is attached: image_embeds required"); return 1; }
     if (!ip && image_embeds) { set_error("unet: image_embeds given but no IP-Adapter is attached"); return 1; }
     if (ip && !pag) {
-        if (n_img < 1 || n_img * ip->n_tok > 64) { set_error("unet: images per prompt x adapter tokens must be in [1, 64]"); return 4; }
+        if (call.n_img < 1 || call.n_img * ip->n_tok > 64) { set_error("unet: images per prompt x adapter tokens must be in [1, 64]"); return 4; }
         if (L < 1 || L > 160) { set_error("unet: with an IP-Adapter the text length must be in [1, 160]"); return 4; }
         if (graph_enabled) { set_error("unet: graph replay with an IP-Adapter attached is not supported"); return 4; }
     } else {
-        n_img = 0;
+        call.n_img = 0;
     }
     if (cn && !control) { set_error("unet: a ControlNet is attached: control image required"); return 1; }
     if (!cn && control) { set_error("unet: control image given but no ControlNet is attached"); return 1; }
     if (cn) {
-        if (n_ctrl < 1 || B % n_ctrl != 0) { set_error("unet: the control image count must divide the batch"); return 1; }
-        if (!(cn_scale == cn_scale)) { set_error("unet: conditioning scale is NaN"); return 1; }
+        if (call.n_ctrl < 1 || B % call.n_ctrl != 0) { set_error("unet: the control image count must divide the batch"); return 1; }
+        if (!(call.cn_scale == call.cn_scale)) { set_error("unet: conditioning scale is NaN"); return 1; }
         if (graph_enabled) { set_error("unet: graph replay with a ControlNet attached is not supported"); return 4; }
     } else {
-        n_ctrl = 0;
-        cn_scale = 0.f;
+        call.n_ctrl = 0;
+        call.cn_scale = 0.f;
     }
-    const bool use_cn = cn && cn_scale != 0.f;
+    const bool use_cn = cn && call.cn_scale != 0.f;
     if (freeu_on && graph_enabled) { set_error("unet: graph replay with FreeU enabled is not supported"); return 4; }
     const int dc = dc_mode;
     if (dc != SD_DC_PLAIN) {
@@ -1446,96 +1445,38 @@ int UNet::forward(const half_t* sample, const float* timesteps, const half_t* eh
             set_error("unet: DeepCache with FreeU needs at least three blocks (FreeU would touch the cached block)");
             return 4;
         }
-        if (dc == SD_DC_REUSE && !(dc_valid && dc_buf && dc_B == B && dc_H == H && dc_W == W && dc_cfg == (cfg_in != nullptr))) {
+        if (dc == SD_DC_REUSE && !(dc_buf.h() && dc_tag.matches(nullptr, B, H, W, cfg_in != nullptr))) {
             set_error("unet: DeepCache reuse forward without a stored step of this shape");
             return 2;
         }
         // persistent concatenation buffer [B H W, C1 + C0] of layer L-d of the last (full-resolution) up block
         const int* boc = cfg.block_out_channels;
         const int c1 = dc_depth == cfg.layers_per_block ? boc[cfg.num_blocks > 1 ? 1 : 0] : boc[0];
-        const size_t need = (size_t)B * H * W * (c1 + boc[0]) * sizeof(half_t);
-        if (need > dc_cap) {
-            SD_HIP_CHECK(hipDeviceSynchronize());
-            if (dc_buf) (void)hipFree(dc_buf);
-            dc_buf = nullptr; dc_cap = 0; dc_valid = false;
-            SD_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&dc_buf), need));
-            dc_cap = need;
-        }
-        if (dc == SD_DC_STORE) dc_valid = false;     // (until this forward has run)
+        if (int rc = reserve_cache(dc_buf, (size_t)B * H * W * (c1 + boc[0]) * sizeof(half_t), dc_tag)) return rc;
+        if (dc == SD_DC_STORE) dc_tag.clear();       // (until this forward has run)
     }
-    if (graph_enabled && !prof_enabled())
-        return forward_graph(sample, timesteps, ehs, L, add_text, add_time_ids, out, B, H, W, stream, tcond);
-    if (kv_cache_on) {          // persistent buffer for the text K/V (outside the per-forward arena)
-        const size_t need = (size_t)B * L * kv_total * sizeof(half_t);
-        if (need > kv_cap) {
-            SD_HIP_CHECK(hipDeviceSynchronize());
-            if (kv_cache) (void)hipFree(kv_cache);
-            kv_cache = nullptr; kv_cap = 0; kv_valid = false;
-            SD_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&kv_cache), need));
-            kv_cap = need;
-        }
-        if (ip && !pag) {
-            const size_t ineed = (size_t)B * n_img * ip->n_tok * ip->kv_total * sizeof(half_t);
-            if (ineed > ipkv_cap) {
-                SD_HIP_CHECK(hipDeviceSynchronize());
-                if (ipkv_cache) (void)hipFree(ipkv_cache);
-                ipkv_cache = nullptr; ipkv_cap = 0; ipkv_valid = false;
-                SD_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&ipkv_cache), ineed));
-                ipkv_cap = ineed;
-            }
-        }
+    if (graph_enabled && !prof_enabled()) return forward_graph(call, stream);
+    if (kv_cache_on) {          // persistent buffers for the text K/V and its like (outside the per-forward arena)
+        if (int rc = reserve_cache(kv_cache, (size_t)B * L * kv_total * sizeof(half_t), kv_tag)) return rc;
+        if (ip && !pag)
+            if (int rc = reserve_cache(ipkv_cache, (size_t)B * call.n_img * ip->n_tok * ip->kv_total * sizeof(half_t), ipkv_tag)) return rc;
         if (use_cn) {
-            const size_t cneed = (size_t)B * H * W * cn->cfg.block_out_channels[0] * sizeof(half_t);
-            if (cneed > cond_cap) {
-                SD_HIP_CHECK(hipDeviceSynchronize());
-                if (cond_cache) (void)hipFree(cond_cache);
-                cond_cache = nullptr; cond_cap = 0; cond_valid = false;
-                SD_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&cond_cache), cneed));
-                cond_cap = cneed;
-            }
-            const size_t kneed = (size_t)B * L * cn->kv_total * sizeof(half_t);
-            if (kneed > cnkv_cap) {
-                SD_HIP_CHECK(hipDeviceSynchronize());
-                if (cnkv_cache) (void)hipFree(cnkv_cache);
-                cnkv_cache = nullptr; cnkv_cap = 0; cnkv_valid = false;
-                SD_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&cnkv_cache), kneed));
-                cnkv_cap = kneed;
-            }
+            if (int rc = reserve_cache(cond_cache, (size_t)B * H * W * cn->cfg.block_out_channels[0] * sizeof(half_t), cond_tag)) return rc;
+            if (int rc = reserve_cache(cnkv_cache, (size_t)B * L * cn->kv_total * sizeof(half_t), cnkv_tag)) return rc;
         }
     }
-    // (the IP-Adapter's image token count joins the key: set_ip_adapter resets the plan)
-    const long key = ((long)B << 40) ^ ((long)H << 20) ^ (long)W ^ ((long)L << 52) ^ (kv_cache_on ? (1L << 62) : 0) ^
-                     (ip ? (long)(n_img * ip->n_tok) << 32 : 0) ^ (cfg_in ? (1L << 61) : 0);
-    // (forward_pag: the groups and whether the perturbed one is widened late; sd_unet_set_pag_layers resets the plan)
-    const int pag_key = pag ? 1 + pag->groups * 2 + (pag->late ? 1 : 0) : 0;
-    // (the ControlNet's arena use depends on whether it runs and on n_ctrl: set_controlnet resets the plan)
-    const long cn_key = use_cn ? n_ctrl : 0;
-    // (the DeepCache mode and depth belong to the key: one slot per mode, the depth beside it; the plain forward does not
-    // depend on the depth)
-    const int key_depth = dc != SD_DC_PLAIN ? dc_depth : 0;
-    if (key != planned_key[dc] || cn_key != planned_cn[dc] || key_depth != planned_depth[dc] || pag_key != planned_pag) {
-        Ctx dry{&arena, stream, true};
-        arena.begin(true);
-        int rc = run(dry, sample, timesteps, ehs, L, add_text, add_time_ids, out, B, H, W, image_embeds, n_img, control,
-                     n_ctrl, cn_scale, cfg_in, tcond, dc, pag);
-        if (rc) return rc;
-        // growing the slab frees the old one: make sure nothing enqueued earlier still uses it
-        if (arena.peak() > arena.capacity()) {
-            SD_HIP_CHECK(hipDeviceSynchronize());
-            rc = arena.reserve(arena.peak());
-            if (rc) return rc;
-        }
-        planned_key[dc] = key;
-        planned_cn[dc] = cn_key;
-        planned_depth[dc] = key_depth;
-        planned_pag = pag_key;
-    }
-    Ctx ctx{&arena, stream, false};
-    arena.begin(false);
-    int rc = run(ctx, sample, timesteps, ehs, L, add_text, add_time_ids, out, B, H, W, image_embeds, n_img, control, n_ctrl,
-                 cn_scale, cfg_in, tcond, dc, pag);
-    if (!rc && arena.overflow()) { set_error("unet: workspace overflow (planner bug)"); return 2; }
-    if (!rc && dc == SD_DC_STORE) { dc_valid = true; dc_B = B; dc_H = H; dc_W = W; dc_cfg = cfg_in != nullptr; }
+    // set_ip_adapter, set_controlnet, set_pag_layers and sd_ip_adapter_set_feature_tokens change what a key stands for:
+    // they reset the plans
+    PlanKey key;
+    key.B = B; key.H = H; key.W = W; key.L = L;
+    key.kv_cache = kv_cache_on;
+    key.ip_tokens = ip ? call.n_img * ip->n_tok : 0;
+    key.cfg_share = cfg_in != nullptr;
+    if (pag) { key.pag_groups = pag->groups; key.pag_late = pag->late; }
+    key.n_ctrl = use_cn ? call.n_ctrl : 0;
+    key.dc_depth = dc != SD_DC_PLAIN ? dc_depth : 0;
+    const int rc = plan_and_run(arena, stream, planned[dc], key, "unet", [&](Ctx& c) { return run(c, call, dc); });
+    if (!rc && dc == SD_DC_STORE) dc_tag.set(nullptr, B, H, W, cfg_in != nullptr);
     return rc;
 }
 
@@ -1546,13 +1487,8 @@ int UNet::set_deep_cache(int depth) {
     }
     dc_depth = depth;
     dc_mode = SD_DC_PLAIN;
-    dc_valid = false;
-    if (depth == 0 && dc_buf) {
-        SD_HIP_CHECK(hipDeviceSynchronize());
-        (void)hipFree(dc_buf);
-        dc_buf = nullptr; dc_cap = 0;
-    }
-    return 0;
+    dc_tag.clear();
+    return depth == 0 ? dc_buf.release() : 0;
 }
 
 bool unet_cfg_share_eligible(const sd_unet_config& cfg) {
@@ -1568,34 +1504,33 @@ bool UNet::cfg_share_active(bool share) const {
     return share && !off && !gn_cat && !graph_enabled && !cn && unet_cfg_share_eligible(cfg);
 }
 
-int UNet::forward_cfg(const half_t* latents, const float* timesteps, const half_t* ehs, int L, const half_t* add_text,
-                      const float* add_time_ids, const half_t* image_embeds, int n_img, float in_scale, bool share,
-                      half_t* out, int B, int H, int W, hipStream_t stream) {
+int UNet::forward_cfg(const UNetCall& lat, float in_scale, bool share, hipStream_t stream) {
+    const int B = lat.B, H = lat.H, W = lat.W;
     if (!finalized) { set_error("unet: forward before finalize"); return 2; }
     if (B <= 0 || H <= 0 || W <= 0) { set_error("unet: forward_cfg: empty batch"); return 1; }
+    UNetCall call = lat;
+    call.B = 2 * B;
     if (cfg_share_active(share)) {
         CfgIn in;
-        in.latents = latents;
+        in.latents = lat.sample;
         in.in_scale = in_scale;
-        return forward(nullptr, timesteps, ehs, L, add_text, add_time_ids, out, 2 * B, H, W, stream, image_embeds, n_img,
-                       nullptr, 0, 0.f, &in);
+        call.sample = nullptr;
+        call.cfg_in = &in;
+        return forward(call, stream);
     }
     // not shared: cat([latents * in_scale] * 2) and the doubled timesteps in a buffer of the engine's, then the forward
     // every caller ran before.  (One buffer: calls on one stream are ordered by it, like the graph path's staging.)
     const size_t n = (size_t)B * cfg.in_channels * H * W;
-    const size_t lat_bytes = (2 * n * sizeof(half_t) + 255) & ~size_t(255), need = lat_bytes + 2 * (size_t)B * sizeof(float);
-    if (need > cfg_cap) {
-        SD_HIP_CHECK(hipDeviceSynchronize());
-        if (cfg_slab) (void)hipFree(cfg_slab);
-        cfg_slab = nullptr; cfg_cap = 0;
-        SD_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&cfg_slab), need));
-        cfg_cap = need;
-    }
-    half_t* lat2 = reinterpret_cast<half_t*>(cfg_slab);
-    float* ts2 = reinterpret_cast<float*>(cfg_slab + lat_bytes);
-    if (int rc = launch_cfg_duplicate(latents, lat2, (long)n, in_scale, stream)) return rc;
-    if (int rc = launch_dup_f32(timesteps, ts2, B, stream)) return rc;
-    return forward(lat2, ts2, ehs, L, add_text, add_time_ids, out, 2 * B, H, W, stream, image_embeds, n_img);
+    const size_t lat_bytes = (2 * n * sizeof(half_t) + 255) & ~size_t(255);
+    bool grew = false;
+    if (int rc = cfg_slab.reserve(lat_bytes + 2 * (size_t)B * sizeof(float), &grew)) return rc;
+    half_t* lat2 = cfg_slab.h();
+    float* ts2 = reinterpret_cast<float*>(cfg_slab.data() + lat_bytes);
+    if (int rc = launch_cfg_duplicate(lat.sample, lat2, (long)n, in_scale, stream)) return rc;
+    if (int rc = launch_dup_f32(lat.timesteps, ts2, B, stream)) return rc;
+    call.sample = lat2;
+    call.timesteps = ts2;
+    return forward(call, stream);
 }
 
 // ------------------------------------------------------------------------------- perturbed-attention guidance
@@ -1628,14 +1563,13 @@ int UNet::set_pag_layers(const char* const* keys, int count) {
     }
     for (auto& st : sites) st.second->pag = false;
     for (Xformer* x : pick) x->pag = true;
-    kv_valid = false;
+    kv_tag.clear();
     reset_plans();
     return 0;
 }
 
-int UNet::forward_pag(const half_t* latents, const float* timesteps, const half_t* ehs, int L, const half_t* add_text,
-                      const float* add_time_ids, float in_scale, bool cfg_on, bool share, half_t* out, int B, int H, int W,
-                      hipStream_t stream) {
+int UNet::forward_pag(const UNetCall& lat, float in_scale, bool cfg_on, bool share, hipStream_t stream) {
+    const int B = lat.B, H = lat.H, W = lat.W;
     if (!finalized) { set_error("unet: forward before finalize"); return 2; }
     if (B <= 0 || H <= 0 || W <= 0) { set_error("unet: forward_pag: empty batch"); return 1; }
     if (cn) { set_error("unet: forward_pag with a ControlNet attached is not supported"); return 4; }
@@ -1656,35 +1590,35 @@ int UNet::forward_pag(const half_t* latents, const float* timesteps, const half_
     pag.groups = cfg_on ? 2 : 1;
     pag.late = share && !off && !gn_cat && first_flagged > 0;
     const int G = pag.groups, N = (G + 1) * B;
+    UNetCall call = lat;
+    call.B = N;
+    call.pag = &pag;
     if (pag.late && cfg_on && cfg_share_active(true)) {
         // B latents -> 2B at the first cross-attention (the CFG-shared start) -> 3B at the first flagged transformer
         CfgIn in;
-        in.latents = latents;
+        in.latents = lat.sample;
         in.in_scale = in_scale;
-        return forward(nullptr, timesteps, ehs, L, add_text, add_time_ids, out, N, H, W, stream, nullptr, 0, nullptr, 0, 0.f,
-                       &in, nullptr, &pag);
+        call.sample = nullptr;
+        call.cfg_in = &in;
+        return forward(call, stream);
     }
     // the scaled latents and the timesteps once per group, in the buffer forward_cfg's duplicate path uses (late: the
     // un-perturbed groups only are read)
     const size_t n = (size_t)B * cfg.in_channels * H * W;
-    const size_t lat_bytes = ((G + 1) * n * sizeof(half_t) + 255) & ~size_t(255), need = lat_bytes + (size_t)N * sizeof(float);
-    if (need > cfg_cap) {
-        SD_HIP_CHECK(hipDeviceSynchronize());
-        if (cfg_slab) (void)hipFree(cfg_slab);
-        cfg_slab = nullptr; cfg_cap = 0;
-        SD_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&cfg_slab), need));
-        cfg_cap = need;
-    }
-    half_t* lat = reinterpret_cast<half_t*>(cfg_slab);
-    float* ts = reinterpret_cast<float*>(cfg_slab + lat_bytes);
-    if (int rc = launch_cfg_duplicate(latents, lat, (long)n, in_scale, stream)) return rc;
-    if (int rc = launch_dup_f32(timesteps, ts, B, stream)) return rc;
+    const size_t lat_bytes = ((G + 1) * n * sizeof(half_t) + 255) & ~size_t(255);
+    bool grew = false;
+    if (int rc = cfg_slab.reserve(lat_bytes + (size_t)N * sizeof(float), &grew)) return rc;
+    half_t* latN = cfg_slab.h();
+    float* ts = reinterpret_cast<float*>(cfg_slab.data() + lat_bytes);
+    if (int rc = launch_cfg_duplicate(lat.sample, latN, (long)n, in_scale, stream)) return rc;
+    if (int rc = launch_dup_f32(lat.timesteps, ts, B, stream)) return rc;
     if (G == 2) {
-        if (int rc = launch_scale_copy_f16(latents, lat + 2 * n, (long)n, in_scale, stream)) return rc;
-        SD_HIP_CHECK(hipMemcpyAsync(ts + 2 * B, timesteps, (size_t)B * sizeof(float), hipMemcpyDeviceToDevice, stream));
+        if (int rc = launch_scale_copy_f16(lat.sample, latN + 2 * n, (long)n, in_scale, stream)) return rc;
+        SD_HIP_CHECK(hipMemcpyAsync(ts + 2 * B, lat.timesteps, (size_t)B * sizeof(float), hipMemcpyDeviceToDevice, stream));
     }
-    return forward(lat, ts, ehs, L, add_text, add_time_ids, out, N, H, W, stream, nullptr, 0, nullptr, 0, 0.f, nullptr, nullptr,
-                   &pag);
+    call.sample = latN;
+    call.timesteps = ts;
+    return forward(call, stream);
 }
 
 }  // namespace sd

@@ -328,22 +328,7 @@ int VAE::decode(const half_t* z, half_t* img, int B, int h, int w, hipStream_t s
     if (!finalized) { set_error("vae: decode before finalize"); return 2; }
     if (B <= 0 || h <= 0 || w <= 0) { set_error("vae: bad shape"); return 1; }
     const long key = ((long)B << 40) ^ ((long)h << 20) ^ (long)w;
-    if (key != planned_key) {
-        Ctx dry{&arena, stream, true};
-        arena.begin(true);
-        int rc = run_decode(dry, z, img, B, h, w);
-        if (rc) return rc;
-        if (arena.peak() > arena.capacity()) {
-            SD_HIP_CHECK(hipDeviceSynchronize());
-            if ((rc = arena.reserve(arena.peak()))) return rc;
-        }
-        planned_key = key;
-    }
-    Ctx ctx{&arena, stream, false};
-    arena.begin(false);
-    int rc = run_decode(ctx, z, img, B, h, w);
-    if (!rc && arena.overflow()) { set_error("vae: workspace overflow (planner bug)"); return 2; }
-    return rc;
+    return plan_and_run(arena, stream, planned_key, key, "vae", [&](Ctx& c) { return run_decode(c, z, img, B, h, w); });
 }
 
 int VAE::encode(const half_t* img, half_t* moments, int B, int H, int W, hipStream_t stream) {
@@ -351,22 +336,8 @@ int VAE::encode(const half_t* img, half_t* moments, int B, int H, int W, hipStre
     const int div = 1 << (cfg.num_blocks - 1);
     if (B <= 0 || H % div != 0 || W % div != 0) { set_error("vae: H and W must be divisible by 2^(blocks-1)"); return 1; }
     const long key = (((long)B << 40) ^ ((long)H << 20) ^ (long)W) | (1L << 62);
-    if (key != planned_key) {
-        Ctx dry{&arena, stream, true};
-        arena.begin(true);
-        int rc = run_encode(dry, img, moments, B, H, W, ldexpf(1.f, -encode_shift));
-        if (rc) return rc;
-        if (arena.peak() > arena.capacity()) {
-            SD_HIP_CHECK(hipDeviceSynchronize());
-            if ((rc = arena.reserve(arena.peak()))) return rc;
-        }
-        planned_key = key;
-    }
-    Ctx ctx{&arena, stream, false};
-    arena.begin(false);
-    int rc = run_encode(ctx, img, moments, B, H, W, ldexpf(1.f, -encode_shift));
-    if (!rc && arena.overflow()) { set_error("vae: workspace overflow (planner bug)"); return 2; }
-    return rc;
+    return plan_and_run(arena, stream, planned_key, key, "vae",
+                        [&](Ctx& c) { return run_encode(c, img, moments, B, H, W, ldexpf(1.f, -encode_shift)); });
 }
 
 }  // namespace sd

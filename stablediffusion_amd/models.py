@@ -353,6 +353,43 @@ class HipUNet2DConditionModel:
             raise ValueError(f"image_embeds: expected [{B}, n_img, {self._ip.image_embed_dim}], got {tuple(embeds.shape)}")
         return _as_f16(embeds, dev)
 
+    def _prepare(self, sample, timestep, encoder_hidden_states, added_cond_kwargs, groups=None):
+        """What the three forward entries share: the fp16 sample (or un-duplicated latents) [B, C, H, W], the text rows,
+        the timesteps [B] fp32 and the text_time pair as pointers.  `groups` (forward_cfg / forward_pag): the text and
+        text_time tensors hold groups x B rows and the timestep holds one value or B; None: the plain forward."""
+        if not self._finalized:
+            raise _lib.EngineError("weights not loaded")
+        dev = self.device
+        sample = _as_f16(sample, dev)
+        B = sample.shape[0]
+        ehs = _as_f16(encoder_hidden_states, dev)
+        if ehs.shape[0] != (groups or 1) * B:
+            raise ValueError(f"encoder_hidden_states batch {ehs.shape[0]} != " +
+                             (f"sample batch {B}" if groups is None else f"{groups} x latents batch {B}"))
+        if ehs.shape[2] != self.cfg.cross_attention_dim:
+            raise ValueError("encoder_hidden_states width != cross_attention_dim")
+        if isinstance(timestep, (int, float)):
+            # a fill kernel, not a pageable host-to-device copy (which synchronises) on every step
+            t = torch.full((B,), float(timestep), device=dev, dtype=torch.float32)
+        else:
+            t = torch.as_tensor(timestep, device=dev).to(torch.float32).reshape(-1)
+            if groups is not None and t.numel() not in (1, B):
+                raise ValueError(f"timestep: expected a scalar or {B} values (one per latent), got {t.numel()}")
+            t = t.expand(B).contiguous() if t.numel() == 1 else t.contiguous()
+        pt = pi = None
+        keep = ()
+        if self.cfg.addition_embed_type == "text_time":
+            if not added_cond_kwargs or "text_embeds" not in added_cond_kwargs or "time_ids" not in added_cond_kwargs:
+                raise ValueError("added_cond_kwargs needs text_embeds and time_ids for text_time conditioning")
+            add_text = _as_f16(added_cond_kwargs["text_embeds"], dev)
+            add_ids = added_cond_kwargs["time_ids"].to(device=dev, dtype=torch.float32).contiguous()
+            _check_time_ids(add_ids, self.cfg)
+            if groups is not None and (add_text.shape[0] != groups * B or add_ids.shape[0] != groups * B):
+                raise ValueError(f"text_embeds / time_ids must hold {groups} x latents batch rows")
+            pt, pi = C.c_void_p(add_text.data_ptr()), C.c_void_p(add_ids.data_ptr())
+            keep = (add_text, add_ids)          # (the caller holds them until its engine call has been issued)
+        return dev, sample, ehs, t, pt, pi, keep
+
     # -- reference surface ---------------------------------------------------------------------
     def to(self, device=None, dtype=None):
         if device is not None and torch.device(device).type != "cuda":
@@ -373,31 +410,8 @@ class HipUNet2DConditionModel:
             if v is not None and v is not False:
                 raise NotImplementedError(f"HipUNet2DConditionModel: {k} is not supported; attach the ControlNet to the "
                                           "engine (attach_controlnet) and pass controlnet_cond=")
-        if not self._finalized:
-            raise _lib.EngineError("weights not loaded")
-        dev = self.device
-        sample = _as_f16(sample, dev)
+        dev, sample, ehs, t, pt, pi, _keep = self._prepare(sample, timestep, encoder_hidden_states, added_cond_kwargs)
         B, _, H, W = sample.shape
-        ehs = _as_f16(encoder_hidden_states, dev)
-        if ehs.shape[0] != B:
-            raise ValueError(f"encoder_hidden_states batch {ehs.shape[0]} != sample batch {B}")
-        if ehs.shape[2] != self.cfg.cross_attention_dim:
-            raise ValueError("encoder_hidden_states width != cross_attention_dim")
-        if isinstance(timestep, (int, float)):
-            # a fill kernel, not a pageable host-to-device copy (which synchronises) on every step
-            t = torch.full((B,), float(timestep), device=dev, dtype=torch.float32)
-        else:
-            t = torch.as_tensor(timestep, device=dev).to(torch.float32).reshape(-1)
-            t = t.expand(B).contiguous() if t.numel() == 1 else t.contiguous()
-        add_text = add_ids = None
-        pt = pi = None
-        if self.cfg.addition_embed_type == "text_time":
-            if not added_cond_kwargs or "text_embeds" not in added_cond_kwargs or "time_ids" not in added_cond_kwargs:
-                raise ValueError("added_cond_kwargs needs text_embeds and time_ids for text_time conditioning")
-            add_text = _as_f16(added_cond_kwargs["text_embeds"], dev)
-            add_ids = added_cond_kwargs["time_ids"].to(device=dev, dtype=torch.float32).contiguous()
-            _check_time_ids(add_ids, self.cfg)
-            pt, pi = C.c_void_p(add_text.data_ptr()), C.c_void_p(add_ids.data_ptr())
         img = self._image_embeds(added_cond_kwargs, B, dev)
         ctrl, cscale = self._control(controlnet_cond, controlnet_conditioning_scale, B, H, W, dev)
         tc = None
@@ -410,30 +424,21 @@ class HipUNet2DConditionModel:
             if tc.ndim != 2 or tc.shape[0] != B:
                 raise ValueError(f"timestep_cond: expected [{B}, time_cond_proj_dim], got {tuple(tc.shape)}")
         out = torch.empty((B, self.cfg.out_channels, H, W), device=dev, dtype=torch.float16)
+        # one argument list; the entry is the narrowest that takes what is present (sd_engine.h)
+        head = (self._h, C.c_void_p(sample.data_ptr()), C.c_void_p(t.data_ptr()), C.c_void_p(ehs.data_ptr()), ehs.shape[1],
+                pt, pi)
+        images = (C.c_void_p(img.data_ptr()) if img is not None else None, img.shape[1] if img is not None else 0)
+        tail = (C.c_void_p(out.data_ptr()), B, H, W, C.c_void_p(_stream_ptr()))
+        if tc is not None:
+            fn, extra = self._lib.sd_unet_forward_tc, images + (C.c_void_p(tc.data_ptr()), tc.shape[1])
+        elif ctrl is not None:
+            fn, extra = self._lib.sd_unet_forward_cn, images + (C.c_void_p(ctrl.data_ptr()), ctrl.shape[0], cscale)
+        elif img is not None:
+            fn, extra = self._lib.sd_unet_forward_ex, images
+        else:
+            fn, extra = self._lib.sd_unet_forward, ()
         with torch.cuda.device(dev):
-            if tc is not None:
-                rc = self._lib.sd_unet_forward_tc(self._h, C.c_void_p(sample.data_ptr()), C.c_void_p(t.data_ptr()),
-                                                  C.c_void_p(ehs.data_ptr()), ehs.shape[1], pt, pi,
-                                                  C.c_void_p(img.data_ptr()) if img is not None else None,
-                                                  img.shape[1] if img is not None else 0,
-                                                  C.c_void_p(tc.data_ptr()), tc.shape[1],
-                                                  C.c_void_p(out.data_ptr()), B, H, W, C.c_void_p(_stream_ptr()))
-            elif ctrl is not None:
-                rc = self._lib.sd_unet_forward_cn(self._h, C.c_void_p(sample.data_ptr()), C.c_void_p(t.data_ptr()),
-                                                  C.c_void_p(ehs.data_ptr()), ehs.shape[1], pt, pi,
-                                                  C.c_void_p(img.data_ptr()) if img is not None else None,
-                                                  img.shape[1] if img is not None else 0,
-                                                  C.c_void_p(ctrl.data_ptr()), ctrl.shape[0], cscale,
-                                                  C.c_void_p(out.data_ptr()), B, H, W, C.c_void_p(_stream_ptr()))
-            elif img is None:
-                rc = self._lib.sd_unet_forward(self._h, C.c_void_p(sample.data_ptr()), C.c_void_p(t.data_ptr()),
-                                               C.c_void_p(ehs.data_ptr()), ehs.shape[1], pt, pi,
-                                               C.c_void_p(out.data_ptr()), B, H, W, C.c_void_p(_stream_ptr()))
-            else:
-                rc = self._lib.sd_unet_forward_ex(self._h, C.c_void_p(sample.data_ptr()), C.c_void_p(t.data_ptr()),
-                                                  C.c_void_p(ehs.data_ptr()), ehs.shape[1], pt, pi,
-                                                  C.c_void_p(img.data_ptr()), img.shape[1],
-                                                  C.c_void_p(out.data_ptr()), B, H, W, C.c_void_p(_stream_ptr()))
+            rc = fn(*head, *extra, *tail)
         _lib.check(rc, "sd_unet_forward")
         if return_dict:
             return SimpleNamespace(sample=out)
@@ -458,31 +463,8 @@ class HipUNet2DConditionModel:
             raise _lib.EngineError("weights not loaded")
         if self._cn is not None:
             raise ValueError("forward_cfg takes no ControlNet: duplicate the latents and call the model")
-        dev = self.device
-        latents = _as_f16(latents, dev)
+        dev, latents, ehs, t, pt, pi, _keep = self._prepare(latents, timestep, encoder_hidden_states, added_cond_kwargs, 2)
         B, _, H, W = latents.shape
-        ehs = _as_f16(encoder_hidden_states, dev)
-        if ehs.shape[0] != 2 * B:
-            raise ValueError(f"encoder_hidden_states batch {ehs.shape[0]} != 2 x latents batch {B}")
-        if ehs.shape[2] != self.cfg.cross_attention_dim:
-            raise ValueError("encoder_hidden_states width != cross_attention_dim")
-        if isinstance(timestep, (int, float)):
-            t = torch.full((B,), float(timestep), device=dev, dtype=torch.float32)
-        else:
-            t = torch.as_tensor(timestep, device=dev).to(torch.float32).reshape(-1)
-            if t.numel() not in (1, B):
-                raise ValueError(f"timestep: expected a scalar or {B} values (one per latent), got {t.numel()}")
-            t = t.expand(B).contiguous() if t.numel() == 1 else t.contiguous()
-        pt = pi = None
-        if self.cfg.addition_embed_type == "text_time":
-            if not added_cond_kwargs or "text_embeds" not in added_cond_kwargs or "time_ids" not in added_cond_kwargs:
-                raise ValueError("added_cond_kwargs needs text_embeds and time_ids for text_time conditioning")
-            add_text = _as_f16(added_cond_kwargs["text_embeds"], dev)
-            add_ids = added_cond_kwargs["time_ids"].to(device=dev, dtype=torch.float32).contiguous()
-            _check_time_ids(add_ids, self.cfg)
-            if add_text.shape[0] != 2 * B or add_ids.shape[0] != 2 * B:
-                raise ValueError("text_embeds / time_ids must hold 2 x latents batch rows")
-            pt, pi = C.c_void_p(add_text.data_ptr()), C.c_void_p(add_ids.data_ptr())
         img = self._image_embeds(added_cond_kwargs, 2 * B, dev)
         out = torch.empty((2 * B, self.cfg.out_channels, H, W), device=dev, dtype=torch.float16)
         with torch.cuda.device(dev):
@@ -503,34 +485,9 @@ class HipUNet2DConditionModel:
         With `share` the engine creates the perturbed group only where it starts to differ (sd_unet_forward_pag).
         Not with a ControlNet, an IP-Adapter at a non-zero scale, DeepCache store / reuse, graph replay or a
         guidance-embedded UNet (EngineError, SD_ERR_UNSUPPORTED)."""
-        if not self._finalized:
-            raise _lib.EngineError("weights not loaded")
-        dev = self.device
-        latents = _as_f16(latents, dev)
-        B, _, H, W = latents.shape
         G = 2 if cfg else 1
-        ehs = _as_f16(encoder_hidden_states, dev)
-        if ehs.shape[0] != G * B:
-            raise ValueError(f"encoder_hidden_states batch {ehs.shape[0]} != {G} x latents batch {B}")
-        if ehs.shape[2] != self.cfg.cross_attention_dim:
-            raise ValueError("encoder_hidden_states width != cross_attention_dim")
-        if isinstance(timestep, (int, float)):
-            t = torch.full((B,), float(timestep), device=dev, dtype=torch.float32)
-        else:
-            t = torch.as_tensor(timestep, device=dev).to(torch.float32).reshape(-1)
-            if t.numel() not in (1, B):
-                raise ValueError(f"timestep: expected a scalar or {B} values (one per latent), got {t.numel()}")
-            t = t.expand(B).contiguous() if t.numel() == 1 else t.contiguous()
-        pt = pi = None
-        if self.cfg.addition_embed_type == "text_time":
-            if not added_cond_kwargs or "text_embeds" not in added_cond_kwargs or "time_ids" not in added_cond_kwargs:
-                raise ValueError("added_cond_kwargs needs text_embeds and time_ids for text_time conditioning")
-            add_text = _as_f16(added_cond_kwargs["text_embeds"], dev)
-            add_ids = added_cond_kwargs["time_ids"].to(device=dev, dtype=torch.float32).contiguous()
-            _check_time_ids(add_ids, self.cfg)
-            if add_text.shape[0] != G * B or add_ids.shape[0] != G * B:
-                raise ValueError(f"text_embeds / time_ids must hold {G} x latents batch rows")
-            pt, pi = C.c_void_p(add_text.data_ptr()), C.c_void_p(add_ids.data_ptr())
+        dev, latents, ehs, t, pt, pi, _keep = self._prepare(latents, timestep, encoder_hidden_states, added_cond_kwargs, G)
+        B, _, H, W = latents.shape
         out = torch.empty(((G + 1) * B, self.cfg.out_channels, H, W), device=dev, dtype=torch.float16)
         with torch.cuda.device(dev):
             rc = self._lib.sd_unet_forward_pag(self._h, C.c_void_p(latents.data_ptr()), C.c_void_p(t.data_ptr()),
