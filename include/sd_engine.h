@@ -247,6 +247,24 @@ int sd_unet_set_pag_layers(sd_unet* u, const char* const* site_keys, int count);
 int sd_unet_forward_pag(sd_unet* u, const void* latents, const float* timesteps, const void* ehs, int ehs_len,
                         const void* add_text, const float* add_time_ids, float in_scale, int cfg, int share, void* out,
                         int B, int H, int W, void* stream);
+/* InstructPix2Pix (Brooks et al., "InstructPix2Pix: Learning to Follow Image Editing Instructions", 2023; diffusers 0.27.2
+ * StableDiffusionInstructPix2PixPipeline, recalled): the forward of a UNet whose sample is [latents | image latents],
+ * from the un-concatenated, un-duplicated inputs.  Defined as sd_unet_forward_ex on the sample
+ *   cat([fp16(latents[n % B_lat] * in_scale), n < zero_from ? extra[n % extra_rows] : 0], dim = 1),  n in [0, B)
+ * at the timesteps [B_lat] repeated per group of B_lat images (on the device: no host op per step):
+ *   latents [B_lat,4,H,W] f16   extra [extra_rows,extra_channels,H,W] f16   timesteps [B_lat] f32
+ *   ehs [B,ehs_len,ctx] f16     add_text / add_time_ids: NULL (see below)    out [B,Cout,H,W] f16
+ * Where the first block is 320 wide and H W % 128 == 0 (SD_NO_EDGE_KERNELS unset) conv_in is one launch that reads both
+ * sources (sd_op_unet_conv_in2) and the sample never exists; otherwise one small launch builds it in the workspace and the
+ * forward is sd_unet_forward_ex on it bit for bit.
+ * SD_ERR_INVALID: 4 + extra_channels != in_channels, B % B_lat != 0, more than 25 groups, zero_from outside [0, B],
+ * extra_rows < 1, null or NaN arguments.  SD_ERR_UNSUPPORTED, nothing launched: graph replay on, a ControlNet attached,
+ * a DeepCache store / reuse mode, an IP-Adapter attached at a non-zero scale, a UNet with time_cond_proj_dim, a UNet
+ * with text_time conditioning (the time embedding is computed per latent and tiled, and add_text / add_time_ids differ
+ * per group: such a UNet takes the 8-channel sample through sd_unet_forward_ex).  These are checked before the shapes. */
+int sd_unet_forward_concat(sd_unet* u, const void* latents, int B_lat, float in_scale, const void* extra, int extra_channels,
+                           int extra_rows, int zero_from, const float* timesteps, const void* ehs, int ehs_len,
+                           const void* add_text, const float* add_time_ids, void* out, int B, int H, int W, void* stream);
 /* UNet2DConditionModel.enable_freeu(s1, s2, b1, b2) / disable_freeu() of diffusers 0.27.2 (enable = 0: the factors are
  * ignored and the forward is again exactly the plain one).  On, every resnet of up blocks 0 and 1 reads
  *   cat([hidden with its first C1 / 2 channels times b, fourier_filter(skip, threshold = 1, scale = s)])
@@ -468,6 +486,20 @@ int sd_pag_linear_step(const void* model_out, int rows, void* latents, float* hi
 int sd_pag_combine(const void* model_out, int rows, void* out_f16, int64_t n, float guidance_scale, float pag_scale,
                    void* stream);
 
+/* InstructPix2Pix's dual guidance on the device step.  model_out f16 [3 n] is [text ; image ; uncond] (t: text and image
+ * conditioned, i: image only, u: neither); per element, in fp32 with one rounding to f16:
+ *   e = fp16(fmaf(g_i, i - u, fmaf(g_t, t - i, u)))   (g_t = guidance_scale, g_i = image_guidance_scale)
+ * (an element with i == u skips the outer fmaf, which would add an exact zero: rows [t ; u ; u] give sd_cfg_linear_step's
+ * eps on [u ; t] bit for bit, whatever the signs of its zeros.)
+ * sd_ip2p_linear_step: then exactly sd_cfg_linear_step's update on e, one launch.  sd_ip2p_combine: out_f16 [n] <- e, the
+ * one-row model output that sd_lcm_step / sd_sched_affine_step then take with rows = 1.
+ * 16-byte accesses when n % 8 == 0 and every pointer is 16-byte aligned, a scalar kernel otherwise.
+ * SD_ERR_INVALID (nothing is launched): n <= 0, a null model_out / latents / out_f16, a non-finite scale. */
+int sd_ip2p_linear_step(const void* model_out, void* latents, float* hist_f32, int64_t n, float guidance_scale,
+                        float image_guidance_scale, float c_x, float c_eps, float c_hist, float h_x, float h_eps, void* stream);
+int sd_ip2p_combine(const void* model_out, void* out_f16, int64_t n, float guidance_scale, float image_guidance_scale,
+                    void* stream);
+
 /* One step of a scheduler that adds noise (LCMScheduler.step; schedulers.py `fused_plan`), one launch:
  *   m   = model_out[i]                                   (rows == 1)
  *   m   = fp16(u + g (t - u)), u = out[i], t = out[n+i]  (rows == 2: [uncond ; text], rounded as sd_cfg_linear_step does)
@@ -649,6 +681,14 @@ int sd_op_unet_conv_in(const void* x_nchw, const void* w_oihw, const void* bias,
 int sd_op_unet_conv_out(const void* x_nhwc, const void* gamma, const void* beta, int groups, float eps, int silu,
                         const void* w_oihw, const void* bias, void* y_nchw, int N, int H, int W, int C, int Cout, int iters,
                         float* ms_per_launch, void* stream);
+/* conv_in from two NCHW sources in one launch (edge.hip: conv_head2_kernel), the concatenated sample never built:
+ *   y_nhwc[n] = conv3x3(cat(fp16(a[n % Na] * in_scale), n < zero_from ? b[n % Nb] : 0); w_oihw [320, Ca + Cb, 3, 3]) + bias
+ * a [Na, Ca, H, W], b [Nb, Cb, H, W] f16; y_nhwc [N H W, 320] with row stride ldy (>= 320, % 8 == 0); b is not read for
+ * n >= zero_from.  9 (Ca + Cb) <= 128, N % Na == 0, H W % 128 == 0, Cout == 320; gn_summaries / groups / iters as
+ * sd_op_unet_conv_in.  SD_ERR_INVALID with a message for every other shape, and under SD_NO_EDGE_KERNELS. */
+int sd_op_unet_conv_in2(const void* a, int Na, int Ca, float in_scale, const void* b, int Nb, int Cb, int zero_from,
+                        const void* w_oihw, const void* bias, void* y_nhwc, int64_t ldy, float* gn_summaries, int groups, int N,
+                        int H, int W, int Cout, int iters, float* ms_per_launch, void* stream);
 /* The GEGLU feed-forward of BasicTransformerBlock with its norm and residual (diffusers attention.py: norm3 -> FeedForward
  * (GEGLU) -> + hidden_states, under sd_unified_pipeline.py:475-482):
  *   y = x + (h * gelu(g)) W2^T + b2,   [h | g] = LayerNorm(x; gamma, beta, eps) W1^T + b1

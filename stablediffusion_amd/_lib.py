@@ -155,6 +155,7 @@ SIGNATURES = {
     "sd_unet_set_freeu": (_I, [_P, _I, _F, _F, _F, _F]),
     "sd_unet_set_pag_layers": (_I, [_P, _P, _I]),
     "sd_unet_forward_pag": (_I, [_P, _P, _P, _P, _I, _P, _P, _F, _I, _I, _P, _I, _I, _I, _P]),
+    "sd_unet_forward_concat": (_I, [_P, _P, _I, _F, _P, _I, _I, _I, _P, _P, _I, _P, _P, _P, _I, _I, _I, _P]),
     "sd_unet_set_deep_cache": (_I, [_P, _I]),
     "sd_unet_deep_cache_mode": (_I, [_P, _I]),
     "sd_ip_adapter_create": (_I, [_P, _I, _I, C.POINTER(_P)]),
@@ -209,6 +210,8 @@ SIGNATURES = {
     "sd_cfg_linear_step": (_I, [_P, _P, _P, _I64, _F, _F, _F, _F, _F, _F, _P]),
     "sd_pag_linear_step": (_I, [_P, _I, _P, _P, _I64, _F, _F, _F, _F, _F, _F, _F, _P]),
     "sd_pag_combine": (_I, [_P, _I, _P, _I64, _F, _F, _P]),
+    "sd_ip2p_linear_step": (_I, [_P, _P, _P, _I64, _F, _F, _F, _F, _F, _F, _F, _P]),
+    "sd_ip2p_combine": (_I, [_P, _P, _I64, _F, _F, _P]),
     "sd_cfg_rescale_linear_step": (_I, [_P, _P, _P, _I, _I64, _F, _F, _F, _F, _F, _F, _F, _P, _P]),
     "sd_lcm_step": (_I, [_P, _I, _P, _P, _P, _I64, _F, _F, _F, _F, _F, _P]),
     "sd_sched_affine_step": (_I, [_P, _I, _P, _P, _P, _I64, _I64, _F, C.POINTER(SdStepPlan), _P]),
@@ -231,6 +234,7 @@ SIGNATURES = {
                                     C.POINTER(_I), _P]),
     "sd_op_groupnorm_conv2d": (_I, [_P, _P, _P, _I, _F, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, C.POINTER(_F),
                                     C.POINTER(_I), _P]),
+    "sd_op_unet_conv_in2": (_I, [_P, _I, _I, _F, _P, _I, _I, _I, _P, _P, _P, _I64, _P, _I, _I, _I, _I, _I, _I, C.POINTER(_F), _P]),
     "sd_op_unet_conv_in": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, C.POINTER(_F), _P]),
     "sd_op_unet_conv_out": (_I, [_P, _P, _P, _I, _F, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, C.POINTER(_F), _P]),
     "sd_op_ffn_geglu": (_I, [_P, _P, _P, _F, _P, _P, _P, _P, _P, _I, _I, _I, C.POINTER(_F), C.POINTER(_I), _P]),

@@ -261,6 +261,17 @@ int sd_unet_forward_pag(sd_unet* u, const void* latents, const float* timesteps,
     if (!(in_scale == in_scale)) { set_error("sd_unet_forward_pag: in_scale is NaN"); return SD_ERR_INVALID; }
     return u->impl.forward_pag(c, in_scale, cfg != 0, share != 0, static_cast<hipStream_t>(stream));
 }
+int sd_unet_forward_concat(sd_unet* u, const void* latents, int B_lat, float in_scale, const void* extra, int extra_channels,
+                           int extra_rows, int zero_from, const float* timesteps, const void* ehs, int ehs_len,
+                           const void* add_text, const float* add_time_ids, void* out, int B, int H, int W, void* stream) {
+    UNetCall c;
+    if (!fill_call(u, latents, timesteps, ehs, ehs_len, add_text, add_time_ids, out, B, H, W, &c)) return SD_ERR_INVALID;
+    if (!extra) { set_error("null argument"); return SD_ERR_INVALID; }
+    c.extra = static_cast<const half_t*>(extra);
+    c.extra_channels = extra_channels; c.extra_rows = extra_rows; c.zero_from = zero_from;
+    c.lat_rows = B_lat; c.in_scale = in_scale;
+    return u->impl.forward_concat(c, static_cast<hipStream_t>(stream));
+}
 int sd_unet_cfg_share(const sd_unet_config* cfg) { return cfg && sd::unet_cfg_share_eligible(*cfg) ? 1 : 0; }
 int sd_unet_set_ip_adapter_scale(sd_unet* u, float scale) {
     if (!u) { set_error("null handle"); return SD_ERR_INVALID; }
@@ -639,6 +650,24 @@ int sd_pag_combine(const void* model_out, int rows, void* out_f16, int64_t n, fl
     }
     return launch_pag_combine(static_cast<const half_t*>(model_out), rows, static_cast<half_t*>(out_f16), (long)n,
                               guidance_scale, pag_scale, static_cast<hipStream_t>(stream));
+}
+int sd_ip2p_linear_step(const void* model_out, void* latents, float* hist_f32, int64_t n, float guidance_scale,
+                        float image_guidance_scale, float c_x, float c_eps, float c_hist, float h_x, float h_eps, void* stream) {
+    if (!model_out || !latents || n <= 0 || !std::isfinite(guidance_scale) || !std::isfinite(image_guidance_scale)) {
+        set_error("sd_ip2p_linear_step: bad arguments (non-null model_out / latents, n > 0, finite scales)");
+        return SD_ERR_INVALID;
+    }
+    return launch_ip2p_linear(static_cast<const half_t*>(model_out), static_cast<half_t*>(latents), hist_f32, (long)n,
+                              guidance_scale, image_guidance_scale, c_x, c_eps, c_hist, h_x, h_eps, static_cast<hipStream_t>(stream));
+}
+int sd_ip2p_combine(const void* model_out, void* out_f16, int64_t n, float guidance_scale, float image_guidance_scale,
+                    void* stream) {
+    if (!model_out || !out_f16 || n <= 0 || !std::isfinite(guidance_scale) || !std::isfinite(image_guidance_scale)) {
+        set_error("sd_ip2p_combine: bad arguments (non-null model_out / out_f16, n > 0, finite scales)");
+        return SD_ERR_INVALID;
+    }
+    return launch_ip2p_combine(static_cast<const half_t*>(model_out), static_cast<half_t*>(out_f16), (long)n, guidance_scale,
+                               image_guidance_scale, static_cast<hipStream_t>(stream));
 }
 int sd_lcm_step(const void* model_out, int rows, void* latents, const void* noise, void* denoised, int64_t n,
                 float guidance_scale, float d_x, float d_out, float p_den, float p_noise, void* stream) {
@@ -1286,6 +1315,58 @@ int sd_op_unet_conv_in(const void* x_nchw, const void* w_oihw, const void* bias_
     for (int it = 0; it < n && !rc; ++it) {
         if (timed && it == 2) SD_HIP_CHECK(hipEventRecord(e0, s));
         rc = launch_conv_head(p, s);
+    }
+    if (timed && !rc) {
+        SD_HIP_CHECK(hipEventRecord(e1, s));
+        SD_HIP_CHECK(hipEventSynchronize(e1));
+        float ms = 0.f;
+        SD_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+        *ms_per_launch = ms / (float)iters;
+    }
+    if (e0) { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); }
+    hipError_t e = hipStreamSynchronize(s);
+    if (!rc && e != hipSuccess) { set_error(hipGetErrorString(e)); rc = SD_ERR_HIP; }
+    return rc;
+}
+
+int sd_op_unet_conv_in2(const void* a, int Na, int Ca, float in_scale, const void* b, int Nb, int Cb, int zero_from,
+                        const void* w_oihw, const void* bias_f32, void* y_nhwc, int64_t ldy, float* gn_summaries, int groups, int N,
+                        int H, int W, int Cout, int iters, float* ms_per_launch, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!a || !b || !w_oihw || !bias_f32 || !y_nhwc || N < 1 || Na < 1 || Nb < 1 || Ca < 1 || Cb < 1 || H < 1 || W < 1 ||
+        !(in_scale == in_scale)) {
+        set_error("sd_op_unet_conv_in2: bad arguments");
+        return SD_ERR_INVALID;
+    }
+    const long K = 128;
+    const long rows = ((long)Cout + kWeightRowPad - 1) / kWeightRowPad * kWeightRowPad;
+    Head2Params p;
+    p.a = static_cast<const half_t*>(a); p.Na = Na; p.Ca = Ca; p.in_scale = in_scale;
+    p.b = static_cast<const half_t*>(b); p.Nb = Nb; p.Cb = Cb; p.zero_from = zero_from;
+    p.K = K; p.y = static_cast<half_t*>(y_nhwc); p.ldy = ldy;
+    p.gnstat_out = groups > 0 ? gn_summaries : nullptr; p.G = groups;
+    p.N = N; p.H = H; p.W = W; p.Cout = Cout;
+    if (!conv_head2_supported(p)) {
+        set_error("sd_op_unet_conv_in2: shape outside the one-launch kernel (Cout 320, 9 (Ca + Cb) <= 128, N % Na == 0, H W % 128 == 0, ldy % 8 == 0)");
+        return SD_ERR_INVALID;
+    }
+    DevScope scope;
+    half_t* wp = nullptr;
+    float* bp = nullptr;
+    SD_DEV_ALLOC(scope, wp, (size_t)rows * K * 2);
+    SD_DEV_ALLOC(scope, bp, (size_t)rows * 4);
+    SD_HIP_CHECK(hipMemsetAsync(wp, 0, (size_t)rows * K * 2, s));
+    SD_HIP_CHECK(hipMemsetAsync(bp, 0, (size_t)rows * 4, s));
+    p.w = wp; p.bias = bp;
+    int rc = launch_pack_conv(static_cast<const half_t*>(w_oihw), wp, Cout, Ca + Cb, 3, 3, K, s);
+    if (!rc) SD_HIP_CHECK(hipMemcpyAsync(bp, bias_f32, (size_t)Cout * 4, hipMemcpyDeviceToDevice, s));
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    const bool timed = iters > 0 && ms_per_launch;
+    if (timed) { SD_HIP_CHECK(hipEventCreate(&e0)); SD_HIP_CHECK(hipEventCreate(&e1)); }
+    const int n = timed ? iters + 2 : 1;
+    for (int it = 0; it < n && !rc; ++it) {
+        if (timed && it == 2) SD_HIP_CHECK(hipEventRecord(e0, s));
+        rc = launch_conv_head2(p, s);
     }
     if (timed && !rc) {
         SD_HIP_CHECK(hipEventRecord(e1, s));

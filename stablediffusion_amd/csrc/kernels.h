@@ -378,6 +378,25 @@ struct HeadParams {
 };
 bool conv_head_supported(const HeadParams& p);
 int launch_conv_head(const HeadParams& p, hipStream_t s);
+// conv_in from two sources, one launch (InstructPix2Pix's 8-channel sample, never materialised):
+//   y[n] = conv3x3(cat(fp16(a[n % Na] * in_scale), n < zero_from ? b[n % Nb] : 0)) + bias
+// a [Na, Ca, H, W] / b [Nb, Cb, H, W] NCHW f16, 9 (Ca + Cb) <= K, K = 64 or 128 (pack_conv's pack of [320, Ca + Cb, 3, 3]),
+// N % Na == 0; the scaled latents are rounded to fp16 as launch_scale_copy_f16 rounds them; b is not read for the
+// images from zero_from up.  Output, summaries and the remaining limits as launch_conv_head.
+struct Head2Params {
+    const half_t* a = nullptr; int Na = 0, Ca = 0; float in_scale = 1.f;
+    const half_t* b = nullptr; int Nb = 0, Cb = 0; int zero_from = 0;
+    const half_t* w = nullptr; long K = 0;
+    const float* bias = nullptr;
+    half_t* y = nullptr; long ldy = 0;
+    float* gnstat_out = nullptr; int G = 0;
+    int N = 0, H = 0, W = 0, Cout = 0;
+};
+bool conv_head2_supported(const Head2Params& p);
+int launch_conv_head2(const Head2Params& p, hipStream_t s);
+// The sample launch_conv_head2 reads, materialised: out [N, Ca + Cb, H W] NCHW f16 (the general conv_in path's input)
+int launch_concat_sample(const half_t* a, int Na, int Ca, float in_scale, const half_t* b, int Nb, int Cb, int zero_from,
+                         half_t* out, int N, long HW, hipStream_t s);
 // norm_out -> SiLU -> conv_out: y NCHW f16 [N, Cout <= 4, H, W] = conv3x3(act(GroupNorm(x))) + bias; x NHWC (row stride
 // ldx), GroupNorm summaries of x as (gn_part, gn_S, gn_rows) (GnStats), packed weights [>= Cout][K = 9 C] in
 // pack_conv's K order [C / 64][kh][kw][64].
@@ -429,6 +448,11 @@ int launch_cfg_linear(const half_t* eps2b, half_t* lat, float* hist, long n, flo
 int launch_pag_linear(const half_t* model_out, int rows, half_t* lat, float* hist, long n, float g, float sp, float cx,
                       float ce, float ch, float hx, float he, hipStream_t s);
 int launch_pag_combine(const half_t* model_out, int rows, half_t* out, long n, float g, float sp, hipStream_t s);
+// InstructPix2Pix's dual guidance over rows [text ; image ; uncond]: e = fp16(fma(gi, i - u, fma(gt, t - i, u))).
+// launch_ip2p_linear: launch_cfg_linear's update on that e, one launch; launch_ip2p_combine: e itself into out [n].
+int launch_ip2p_linear(const half_t* model_out, half_t* lat, float* hist, long n, float gt, float gi, float cx, float ce,
+                       float ch, float hx, float he, hipStream_t s);
+int launch_ip2p_combine(const half_t* model_out, half_t* out, long n, float gt, float gi, hipStream_t s);
 // den = dx x + dout m, x <- pden den + pnoise noise (m: model_out, or its CFG combine when rows == 2); noise / denoised
 // nullable.  The scheduler step of LCMScheduler in one launch.
 int launch_lcm_step(const half_t* model_out, int rows, half_t* lat, const half_t* noise, half_t* denoised, long n, float g,

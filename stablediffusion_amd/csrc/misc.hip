@@ -343,6 +343,18 @@ __global__ void scale_copy_f16_kernel(const half_t* __restrict__ lat, half_t* __
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = (half_t)((float)lat[i] * scale);
 }
+// out[n][c][px] = c < Ca ? fp16(a[n % Na][c][px] * scale) : n < zero_from ? b[n % Nb][c - Ca][px] : 0
+__global__ void concat_sample_kernel(const half_t* __restrict__ a, int Na, int Ca, float scale, const half_t* __restrict__ b,
+                                     int Nb, int Cb, int zero_from, half_t* __restrict__ out, long total, long HW) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const long px = i % HW, nc = i / HW;
+    const int C = Ca + Cb, c = (int)(nc % C), n = (int)(nc / C);
+    half_t v = (half_t)0.f;
+    if (c < Ca) v = (half_t)((float)a[((long)(n % Na) * Ca + c) * HW + px] * scale);
+    else if (n < zero_from) v = b[((long)(n % Nb) * Cb + (c - Ca)) * HW + px];
+    out[i] = v;
+}
 __global__ void dup_f32_kernel(const float* __restrict__ x, float* __restrict__ out, long n) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -668,15 +680,26 @@ __global__ __launch_bounds__(256) void rs_apply_kernel(const half_t* __restrict_
 // (fp32, one rounding to fp16; s == 0 skips the outer fma, so three rows at s = 0 give cfg_linear_kernel's e bit for bit
 // whatever the signs of its zeros), then cfg_linear_kernel's update with its roundings (rs_axpby).  STEP = false writes e
 // itself: the one-row model output the LCM / affine step entries then take.  VEC: n % 8 == 0 and 16-byte aligned bases.
-template <int ROWS>
+// Guide::Ip2p is InstructPix2Pix's dual guidance (Brooks et al., eq. 3) through the same kernel: three rows [t ; i ; u]
+// (text+image, image only, neither), e = fp16(fma(gi, i - u, fma(gt, t - i, u))) with (g, sp) = (gt, gi).  An element
+// with i == u skips the outer fma (it would add an exact zero, of the wrong sign when the inner one gives -0), so rows
+// [t ; u ; u] give cfg_linear_kernel's e on [u ; t] bit for bit.
+enum class Guide { Pag2, Pag3, Ip2p };      // which formula, and with it how many rows of model_out are read
+constexpr int guide_rows(Guide f) { return f == Guide::Pag2 ? 2 : 3; }
+template <Guide F>
 __device__ __forceinline__ float pag_eps(float a, float b, float c, float g, float sp) {
-    // ROWS == 3: (a, b, c) = (u, t, p);  ROWS == 2: (a, b) = (t, p)
-    const float t = ROWS == 3 ? b : a, p = ROWS == 3 ? c : b;
-    float e = ROWS == 3 ? __builtin_fmaf(g, b - a, a) : a;
+    if (F == Guide::Ip2p) {
+        float e = __builtin_fmaf(g, a - b, c);
+        if (b != c) e = __builtin_fmaf(sp, b - c, e);
+        return (float)(half_t)e;
+    }
+    // Pag3: (a, b, c) = (u, t, p);  Pag2: (a, b) = (t, p)
+    const float t = F == Guide::Pag3 ? b : a, p = F == Guide::Pag3 ? c : b;
+    float e = F == Guide::Pag3 ? __builtin_fmaf(g, b - a, a) : a;
     if (sp != 0.f) e = __builtin_fmaf(sp, t - p, e);
     return (float)(half_t)e;
 }
-template <int ROWS, bool VEC, bool STEP>
+template <Guide F, bool VEC, bool STEP>
 __global__ __launch_bounds__(256) void pag_step_kernel(const half_t* __restrict__ mo, half_t* __restrict__ x,
                                                        float* __restrict__ h, long n, float g, float sp, float cx, float ce,
                                                        float ch, float hx, float he) {
@@ -686,7 +709,7 @@ __global__ __launch_bounds__(256) void pag_step_kernel(const half_t* __restrict_
         const h8 va = *reinterpret_cast<const h8*>(mo + i);
         const h8 vb = *reinterpret_cast<const h8*>(mo + n + i);
         h8 vc = vb, vx = vb;
-        if (ROWS == 3) vc = *reinterpret_cast<const h8*>(mo + 2 * n + i);
+        if (guide_rows(F) == 3) vc = *reinterpret_cast<const h8*>(mo + 2 * n + i);
         if (STEP) vx = *reinterpret_cast<const h8*>(x + i);
         float hv[8], x0[8];
         if (STEP && h) {
@@ -697,7 +720,7 @@ __global__ __launch_bounds__(256) void pag_step_kernel(const half_t* __restrict_
         h8 o;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            const float e = pag_eps<ROWS>((float)va[j], (float)vb[j], (float)vc[j], g, sp);
+            const float e = pag_eps<F>((float)va[j], (float)vb[j], (float)vc[j], g, sp);
             if (!STEP) { o[j] = (half_t)e; continue; }
             const float xf = (float)vx[j];
             float out = rs_axpby(cx, xf, ce, e);
@@ -718,7 +741,7 @@ __global__ __launch_bounds__(256) void pag_step_kernel(const half_t* __restrict_
     } else {
         const long i = (long)blockIdx.x * 256 + threadIdx.x;
         if (i >= n) return;
-        const float e = pag_eps<ROWS>((float)mo[i], (float)mo[n + i], ROWS == 3 ? (float)mo[2 * n + i] : 0.f, g, sp);
+        const float e = pag_eps<F>((float)mo[i], (float)mo[n + i], guide_rows(F) == 3 ? (float)mo[2 * n + i] : 0.f, g, sp);
         if (!STEP) { x[i] = (half_t)e; return; }
         const float xf = (float)x[i];
         float out = rs_axpby(cx, xf, ce, e);
@@ -1170,6 +1193,15 @@ int launch_scale_copy_f16(const half_t* x, half_t* out, long n, float scale, hip
     SD_HIP_CHECK(hipGetLastError());
     return 0;
 }
+int launch_concat_sample(const half_t* a, int Na, int Ca, float in_scale, const half_t* b, int Nb, int Cb, int zero_from,
+                         half_t* out, int N, long HW, hipStream_t s) {
+    const long total = (long)N * (Ca + Cb) * HW;
+    if (total <= 0) return 0;
+    if (Na < 1 || Nb < 1 || Ca < 0 || Cb < 0) { set_error("concat_sample: bad arguments"); return 1; }
+    hipLaunchKernelGGL(concat_sample_kernel, grid1d(total), dim3(256), 0, s, a, Na, Ca, in_scale, b, Nb, Cb, zero_from, out, total, HW);
+    SD_HIP_CHECK(hipGetLastError());
+    return 0;
+}
 int launch_dup_f32(const float* x, float* out, long n, hipStream_t s) {
     if (n <= 0) return 0;
     hipLaunchKernelGGL(dup_f32_kernel, grid1d(n), dim3(256), 0, s, x, out, n);
@@ -1200,24 +1232,34 @@ int launch_lcm_step(const half_t* model_out, int rows, half_t* lat, const half_t
     return 0;
 }
 template <bool STEP>
-static int launch_pag_step(const half_t* mo, int rows, half_t* x, float* hist, long n, float g, float sp, float cx, float ce,
+static int launch_pag_step(const half_t* mo, Guide form, half_t* x, float* hist, long n, float g, float sp, float cx, float ce,
                            float ch, float hx, float he, hipStream_t s) {
     const bool vec = vec8_ok(n, mo, x, hist);
     const dim3 grid = grid1d(vec ? n / 8 : n);
 #define SD_PAG_LAUNCH(R, V) \
     hipLaunchKernelGGL((pag_step_kernel<R, V, STEP>), grid, dim3(256), 0, s, mo, x, hist, n, g, sp, cx, ce, ch, hx, he)
-    if (rows == 3) { if (vec) SD_PAG_LAUNCH(3, true); else SD_PAG_LAUNCH(3, false); }
-    else { if (vec) SD_PAG_LAUNCH(2, true); else SD_PAG_LAUNCH(2, false); }
+    if (form == Guide::Ip2p) { if (vec) SD_PAG_LAUNCH(Guide::Ip2p, true); else SD_PAG_LAUNCH(Guide::Ip2p, false); }
+    else if (form == Guide::Pag3) { if (vec) SD_PAG_LAUNCH(Guide::Pag3, true); else SD_PAG_LAUNCH(Guide::Pag3, false); }
+    else { if (vec) SD_PAG_LAUNCH(Guide::Pag2, true); else SD_PAG_LAUNCH(Guide::Pag2, false); }
 #undef SD_PAG_LAUNCH
     SD_HIP_CHECK(hipGetLastError());
     return 0;
 }
 int launch_pag_linear(const half_t* model_out, int rows, half_t* lat, float* hist, long n, float g, float sp, float cx,
                       float ce, float ch, float hx, float he, hipStream_t s) {
-    return launch_pag_step<true>(model_out, rows, lat, hist, n, g, sp, cx, ce, ch, hx, he, s);
+    if (rows != 2 && rows != 3) { set_error("pag_linear: rows must be 2 or 3"); return 1; }
+    return launch_pag_step<true>(model_out, rows == 3 ? Guide::Pag3 : Guide::Pag2, lat, hist, n, g, sp, cx, ce, ch, hx, he, s);
 }
 int launch_pag_combine(const half_t* model_out, int rows, half_t* out, long n, float g, float sp, hipStream_t s) {
-    return launch_pag_step<false>(model_out, rows, out, nullptr, n, g, sp, 0.f, 0.f, 0.f, 0.f, 0.f, s);
+    if (rows != 2 && rows != 3) { set_error("pag_combine: rows must be 2 or 3"); return 1; }
+    return launch_pag_step<false>(model_out, rows == 3 ? Guide::Pag3 : Guide::Pag2, out, nullptr, n, g, sp, 0.f, 0.f, 0.f, 0.f, 0.f, s);
+}
+int launch_ip2p_linear(const half_t* model_out, half_t* lat, float* hist, long n, float gt, float gi, float cx, float ce,
+                       float ch, float hx, float he, hipStream_t s) {
+    return launch_pag_step<true>(model_out, Guide::Ip2p, lat, hist, n, gt, gi, cx, ce, ch, hx, he, s);
+}
+int launch_ip2p_combine(const half_t* model_out, half_t* out, long n, float gt, float gi, hipStream_t s) {
+    return launch_pag_step<false>(model_out, Guide::Ip2p, out, nullptr, n, gt, gi, 0.f, 0.f, 0.f, 0.f, 0.f, s);
 }
 int launch_sched_affine_step(const half_t* model_out, int rows, half_t* lat, const half_t* noise, float* bank, long stride,
                              long n, float g, const StepRows& p, hipStream_t s) {

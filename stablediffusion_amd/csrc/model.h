@@ -169,8 +169,10 @@ struct Encoder {
                  int rows_alloc = 0, const float* tcond = nullptr);
     // conv_in into y0: straight from the NCHW latents when the edge kernel takes it and there is no residual, else
     // im2col + GEMM with `res` added in its epilogue.  *xs = the GroupNorm summaries of y0 it left (or nullptr).
+    // cat (a call in two-source mode): `sample` holds the latents alone; one launch from both sources where
+    // conv_head2_supported, otherwise the concatenated sample is built in the arena and takes the path above.
     void run_conv_in(Ctx& c, const half_t* sample, int B, int H, int W, View y0, GnStatBuf* gb, const View* res,
-                     GnStatBuf** xs);
+                     GnStatBuf** xs, const UNetCall* cat = nullptr);
     // down path from x = skip 0 (summaries xs) at h x w: writes skips 1.. through dst / stat, returns the last one.
     // share: x, xs and tproj hold the first B / 2 images; the first resnet and the start of the first transformer run on
     // those (CfgShare), everything after on all B.
@@ -243,6 +245,12 @@ struct UNetCall {
     const float* tcond = nullptr;           // timestep_cond [B, time_cond_proj_dim] of a guidance-embedded UNet
     const CfgIn* cfg_in = nullptr;          // shared-CFG mode (forward_cfg)
     const PagIn* pag = nullptr;             // perturbed-attention mode (forward_pag)
+    // Two-source mode (forward_concat): the sample is cat([fp16(sample[n % lat_rows] * in_scale), n < zero_from ?
+    // extra[n % extra_rows] : 0], dim 1) and is never handed over as a tensor; `sample` holds the lat_rows latents
+    // [lat_rows, in_channels - extra_channels, H, W], `timesteps` lat_rows entries (repeated per group on the device).
+    const half_t* extra = nullptr;          // [extra_rows, extra_channels, H, W]
+    int extra_channels = 0, extra_rows = 0, zero_from = 0, lat_rows = 0;
+    float in_scale = 1.f;
 };
 
 // What the arena plan of a forward depends on.  Compared field by field: a plan is redone exactly when one differs from
@@ -256,10 +264,11 @@ struct PlanKey {
     bool pag_late = false;
     int n_ctrl = 0;                         // control images of a ControlNet that runs, 0 when none does
     int dc_depth = 0;                       // DeepCache depth of a store / reuse forward (the plain one ignores it)
+    int cat_rows = 0;                       // forward_concat: the latents the B images are built from, 0 otherwise
     bool operator==(const PlanKey& o) const {
         return B == o.B && H == o.H && W == o.W && L == o.L && kv_cache == o.kv_cache && ip_tokens == o.ip_tokens &&
                cfg_share == o.cfg_share && pag_groups == o.pag_groups && pag_late == o.pag_late && n_ctrl == o.n_ctrl &&
-               dc_depth == o.dc_depth;
+               dc_depth == o.dc_depth && cat_rows == o.cat_rows;
     }
 };
 // What a captured graph depends on (timestep_cond's width is the configuration's: its presence changes the launches).
@@ -280,6 +289,8 @@ struct UNet : Encoder {
     // network's first (after the CFG-shared start where forward_cfg would take it); otherwise, and under
     // SD_NO_PAG_SHARE, duplicate up front.
     int forward_pag(const UNetCall& lat, float in_scale, bool cfg_on, bool share, hipStream_t stream);
+    // The forward of a call in two-source mode (UNetCall::extra): sd_unet_forward_concat's checks, then forward().
+    int forward_concat(const UNetCall& call, hipStream_t stream);
     int set_pag_layers(const char* const* site_keys, int count);
     // every transformer in execution order with its site key ("down_blocks.i.attentions.j", "mid_block.attentions.0", ...)
     std::vector<std::pair<std::string, Xformer*>> xformer_sites();

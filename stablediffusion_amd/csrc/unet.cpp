@@ -798,7 +798,7 @@ int Encoder::run_temb(Ctx& c, const float* timesteps, const half_t* add_text, co
 }
 
 void Encoder::run_conv_in(Ctx& c, const half_t* sample, int B, int H, int W, View y0, GnStatBuf* gb, const View* res,
-                          GnStatBuf** xs) {
+                          GnStatBuf** xs, const UNetCall* cat) {
     Arena& a = *c.arena;
     const int* boc = cfg.block_out_channels;
     const int G = cfg.norm_num_groups;
@@ -806,15 +806,43 @@ void Encoder::run_conv_in(Ctx& c, const half_t* sample, int B, int H, int W, Vie
     const bool go = !c.dry;
     const size_t mk = a.mark();
     const long M = (long)B * H * W;
+    auto head_stats = [&](float* out) {
+        if (!gb) return;
+        gb->st = GnStats();
+        if (out) { gb->st.part = gb->buf; gb->st.rows = 128; gb->st.S = (int)((long)H * W / 128); }
+    };
+    if (cat) {
+        Head2Params h2;
+        h2.a = sample; h2.Na = cat->lat_rows; h2.Ca = cfg.in_channels - cat->extra_channels; h2.in_scale = cat->in_scale;
+        h2.b = cat->extra; h2.Nb = cat->extra_rows; h2.Cb = cat->extra_channels; h2.zero_from = cat->zero_from;
+        h2.w = conv_in.w; h2.K = conv_in.K; h2.bias = conv_in.bias; h2.y = y0.p; h2.ldy = y0.ld;
+        h2.gnstat_out = (gb && gb->buf) ? gb->buf : nullptr; h2.G = G;
+        h2.N = B; h2.H = H; h2.W = W; h2.Cout = boc[0];
+        if (!res && conv_head2_supported(h2)) {
+            head_stats(h2.gnstat_out);
+            if (go && !c.err) {
+                prof_open(s, "conv_head2_kernel", 2.0 * M * boc[0] * 9.0 * cfg.in_channels, 2.0 * M * (boc[0] + cfg.in_channels));
+                c.err = launch_conv_head2(h2, s);
+                prof_close(s);
+            }
+            *xs = gb;
+            a.release(mk);
+            return;
+        }
+        half_t* full = a.alloc_h(M * cfg.in_channels);
+        if (go && !c.err) {
+            prof_open(s, "concat_sample_kernel", 0.0, 4.0 * M * cfg.in_channels);
+            c.err = launch_concat_sample(h2.a, h2.Na, h2.Ca, h2.in_scale, h2.b, h2.Nb, h2.Cb, h2.zero_from, full, B, (long)H * W, s);
+            prof_close(s);
+        }
+        sample = full;
+    }
     HeadParams hp;
     hp.x_nchw = sample; hp.w = conv_in.w; hp.K = conv_in.K; hp.bias = conv_in.bias; hp.y = y0.p; hp.ldy = y0.ld;
     hp.gnstat_out = (gb && gb->buf) ? gb->buf : nullptr; hp.G = G;
     hp.N = B; hp.Cin = cfg.in_channels; hp.H = H; hp.W = W; hp.Cout = boc[0];
     if (!res && conv_head_supported(hp)) {
-        if (gb) {
-            gb->st = GnStats();
-            if (hp.gnstat_out) { gb->st.part = gb->buf; gb->st.rows = 128; gb->st.S = (int)((long)H * W / 128); }
-        }
+        head_stats(hp.gnstat_out);
         if (go && !c.err) {
             prof_open(s, "conv_head_kernel", 2.0 * M * boc[0] * 9.0 * cfg.in_channels, 2.0 * M * (boc[0] + cfg.in_channels));
             c.err = launch_conv_head(hp, s);
@@ -823,7 +851,11 @@ void Encoder::run_conv_in(Ctx& c, const half_t* sample, int B, int H, int W, Vie
         *xs = gb;
     } else {
         half_t* col = a.alloc_h(M * conv_in.K);
-        if (go && !c.err) c.err = launch_im2col_nchw3x3(sample, col, B, cfg.in_channels, H, W, (int)conv_in.K, s);
+        if (go && !c.err) {
+            prof_open(s, "im2col_nchw3x3_kernel", 0.0, 2.0 * M * (conv_in.K + cfg.in_channels));
+            c.err = launch_im2col_nchw3x3(sample, col, B, cfg.in_channels, H, W, (int)conv_in.K, s);
+            prof_close(s);
+        }
         ConvW pw = conv_in; pw.ks = 1;
         ConvFuse f;
         f.gn_out = gb;
@@ -932,7 +964,10 @@ int UNet::run(Ctx& c, const UNetCall& call, int dc) {
         pgs.widened = !pag->late;
         c.pag = &pgs;
     }
-    const int Bp = cfg_in ? Nq / 2 : Nq;
+    // ---- two-source mode (forward_concat): B images from lat_rows latents and timesteps, group by group.  The time
+    //      embedding runs on the lat_rows and is widened like the shared CFG prefix's, conv_in reads both sources. ----
+    const UNetCall* const cat = call.extra ? &call : nullptr;
+    const int Bp = cat ? call.lat_rows : cfg_in ? Nq / 2 : Nq;
     CfgShare share;
     if (cfg_in) {
         const long n = (long)Bp * cfg.in_channels * H * W;
@@ -951,6 +986,20 @@ int UNet::run(Ctx& c, const UNetCall& call, int dc) {
         g.src = tproj; g.dst = tproj + (long)Bp * temb_total;
         g.ld_bytes = g.row_bytes = (long)Bp * temb_total * 4; g.rows = 1;
         share.segs.push_back(g);
+    }
+    if (cat && B > Bp) {
+        std::vector<RowDupSeg> segs;
+        for (int g0 = Bp; g0 < B; g0 += Bp) {
+            RowDupSeg g;
+            g.src = tproj; g.dst = tproj + (long)g0 * temb_total;
+            g.ld_bytes = g.row_bytes = (long)Bp * temb_total * 4; g.rows = 1;
+            segs.push_back(g);
+        }
+        if (go && !c.err) {
+            prof_open(s, "row_dup_kernel", 0.0, 2.0 * (B - Bp) * temb_total * 4);
+            c.err = launch_row_dup(segs.data(), (int)segs.size(), s);
+            prof_close(s);
+        }
     }
 
     // ---- text K/V of every cross-attention block in one GEMM: [B*L, ctx] x [ctx, sum 2C] ----
@@ -1092,7 +1141,7 @@ int UNet::run(Ctx& c, const UNetCall& call, int dc) {
     //      im2col into a 64-wide K, then the GEMM kernel ----
     int h = H, w = W;
     run_conv_in(c, sample, cfg_in ? Bp : ctx_live(c, B), H, W, skip_view(skip_i), skip_stat(skip_i, (long)H * W, boc[0]),
-                nullptr, &xs);
+                nullptr, &xs, cat);
     View x = skip_view(skip_i++);
     if (pag) {
         // what the late widening copies besides the flagged transformer's own input: tproj, and every skip that is
@@ -1414,10 +1463,11 @@ int UNet::forward(const UNetCall& in, hipStream_t stream) {
     }
     const int div = 1 << (cfg.num_blocks - 1);
     if (B <= 0 || H % div != 0 || W % div != 0) { set_error("unet: H and W must be divisible by 2^(blocks-1)"); return 1; }
-    // (forward_pag runs with an attached adapter only at scale 0, where the text attention runs alone)
-    if (ip && !image_embeds && !pag) { set_error("unet: an IP-Adapter is attached: image_embeds required"); return 1; }
+    // (forward_pag and forward_concat run with an attached adapter only at scale 0, where the text attention runs alone)
+    const bool text_only = pag || call.extra;
+    if (ip && !image_embeds && !text_only) { set_error("unet: an IP-Adapter is attached: image_embeds required"); return 1; }
     if (!ip && image_embeds) { set_error("unet: image_embeds given but no IP-Adapter is attached"); return 1; }
-    if (ip && !pag) {
+    if (ip && !text_only) {
         if (call.n_img < 1 || call.n_img * ip->n_tok > 64) { set_error("unet: images per prompt x adapter tokens must be in [1, 64]"); return 4; }
         if (L < 1 || L > 160) { set_error("unet: with an IP-Adapter the text length must be in [1, 160]"); return 4; }
         if (graph_enabled) { set_error("unet: graph replay with an IP-Adapter attached is not supported"); return 4; }
@@ -1458,7 +1508,7 @@ int UNet::forward(const UNetCall& in, hipStream_t stream) {
     if (graph_enabled && !prof_enabled()) return forward_graph(call, stream);
     if (kv_cache_on) {          // persistent buffers for the text K/V and its like (outside the per-forward arena)
         if (int rc = reserve_cache(kv_cache, (size_t)B * L * kv_total * sizeof(half_t), kv_tag)) return rc;
-        if (ip && !pag)
+        if (ip && !text_only)
             if (int rc = reserve_cache(ipkv_cache, (size_t)B * call.n_img * ip->n_tok * ip->kv_total * sizeof(half_t), ipkv_tag)) return rc;
         if (use_cn) {
             if (int rc = reserve_cache(cond_cache, (size_t)B * H * W * cn->cfg.block_out_channels[0] * sizeof(half_t), cond_tag)) return rc;
@@ -1475,6 +1525,7 @@ int UNet::forward(const UNetCall& in, hipStream_t stream) {
     if (pag) { key.pag_groups = pag->groups; key.pag_late = pag->late; }
     key.n_ctrl = use_cn ? call.n_ctrl : 0;
     key.dc_depth = dc != SD_DC_PLAIN ? dc_depth : 0;
+    key.cat_rows = call.extra ? call.lat_rows : 0;
     const int rc = plan_and_run(arena, stream, planned[dc], key, "unet", [&](Ctx& c) { return run(c, call, dc); });
     if (!rc && dc == SD_DC_STORE) dc_tag.set(nullptr, B, H, W, cfg_in != nullptr);
     return rc;
@@ -1530,6 +1581,33 @@ int UNet::forward_cfg(const UNetCall& lat, float in_scale, bool share, hipStream
     if (int rc = launch_dup_f32(lat.timesteps, ts2, B, stream)) return rc;
     call.sample = lat2;
     call.timesteps = ts2;
+    return forward(call, stream);
+}
+
+// ------------------------------------------------------------------------------- two-source forward (InstructPix2Pix)
+int UNet::forward_concat(const UNetCall& call, hipStream_t stream) {
+    const int B = call.B, Bl = call.lat_rows;
+    if (!finalized) { set_error("unet: forward before finalize"); return 2; }
+    if (B <= 0 || call.H <= 0 || call.W <= 0 || Bl <= 0) { set_error("unet: forward_concat: empty batch"); return 1; }
+    // (what the handle is set up for comes first: a ControlNet only attaches to a 4-channel UNet, which the channel check below
+    // would turn away with another code)
+    if (graph_enabled) { set_error("unet: forward_concat under graph replay is not supported"); return 4; }
+    if (cn) { set_error("unet: forward_concat with a ControlNet attached is not supported"); return 4; }
+    if (dc_mode != SD_DC_PLAIN) { set_error("unet: forward_concat in a DeepCache store / reuse mode is not supported"); return 4; }
+    if (ip && ip_scale != 0.f) { set_error("unet: forward_concat with an IP-Adapter at a non-zero scale is not supported"); return 4; }
+    if (cfg.time_cond_proj_dim > 0) { set_error("unet: forward_concat on a guidance-embedded UNet (timestep_cond) is not supported"); return 4; }
+    // (the time embedding is computed for the B_lat latents and tiled: text_time conditioning differs per group)
+    if (cfg.addition_time_embed_dim > 0) { set_error("unet: forward_concat on a text_time UNet (add_text / add_time_ids per row) is not supported"); return 4; }
+    if (!call.extra || call.extra_rows < 1) { set_error("unet: forward_concat: the second source is missing"); return 1; }
+    if (call.extra_channels < 1 || call.extra_channels >= cfg.in_channels || cfg.in_channels - call.extra_channels != 4) {
+        set_error("unet: forward_concat: 4 latent channels + extra_channels " + std::to_string(call.extra_channels) +
+                  " != in_channels " + std::to_string(cfg.in_channels));
+        return 1;
+    }
+    if (B % Bl != 0) { set_error("unet: forward_concat: the latents must divide the batch (B % B_lat != 0)"); return 1; }
+    if (B / Bl - 1 > kRowDupMax) { set_error("unet: forward_concat: more than " + std::to_string(kRowDupMax + 1) + " groups"); return 1; }
+    if (call.zero_from < 0 || call.zero_from > B) { set_error("unet: forward_concat: zero_from outside [0, B]"); return 1; }
+    if (!(call.in_scale == call.in_scale)) { set_error("unet: forward_concat: in_scale is NaN"); return 1; }
     return forward(call, stream);
 }
 

@@ -497,6 +497,39 @@ class HipUNet2DConditionModel:
         _lib.check(rc, "sd_unet_forward_pag")
         return (out,)
 
+    def forward_concat(self, latents, timestep, encoder_hidden_states, image_latents, zero_from: Optional[int] = None,
+                       added_cond_kwargs=None, in_scale: float = 1.0):
+        """One forward of a UNet whose sample is [latents | image latents] (InstructPix2Pix) from the un-concatenated,
+        UN-duplicated inputs: latents [B_lat, 4, H, W], image_latents [rows, in_channels - 4, H, W] and
+        encoder_hidden_states [B, ...] with B a multiple of B_lat.  Image n of the B reads fp16(latents[n % B_lat] *
+        in_scale) and image_latents[n % rows], or zeros from image `zero_from` on (default B: none); the timesteps (a
+        scalar or B_lat values) repeat per group.  What self(torch.cat([...], dim=1), ...) returns on that sample, without
+        the sample ever being built where the engine's two-source conv_in takes the shape (sd_unet_forward_concat).
+        Not with a ControlNet, an IP-Adapter at a non-zero scale, DeepCache store / reuse, graph replay, a
+        guidance-embedded UNet or a text_time UNet, whose added conditions differ per group (EngineError,
+        SD_ERR_UNSUPPORTED)."""
+        ehs_rows = encoder_hidden_states.shape[0]
+        B_lat = latents.shape[0]
+        if B_lat < 1 or ehs_rows % B_lat != 0:
+            raise ValueError(f"encoder_hidden_states batch {ehs_rows} is no multiple of the latents batch {B_lat}")
+        dev, latents, ehs, t, pt, pi, _keep = self._prepare(latents, timestep, encoder_hidden_states, added_cond_kwargs,
+                                                            ehs_rows // B_lat)
+        B, (_, Cl, H, W) = ehs_rows, latents.shape
+        extra = _as_f16(image_latents, dev)
+        if extra.ndim != 4 or tuple(extra.shape[2:]) != (H, W) or extra.shape[0] < 1:
+            raise ValueError(f"image_latents: expected [rows, C, {H}, {W}], got {tuple(extra.shape)}")
+        if Cl + extra.shape[1] != self.cfg.in_channels:
+            raise ValueError(f"latents ({Cl}) + image_latents ({extra.shape[1]}) channels != in_channels {self.cfg.in_channels}")
+        zero_from = B if zero_from is None else int(zero_from)
+        out = torch.empty((B, self.cfg.out_channels, H, W), device=dev, dtype=torch.float16)
+        with torch.cuda.device(dev):
+            rc = self._lib.sd_unet_forward_concat(self._h, C.c_void_p(latents.data_ptr()), B_lat, float(in_scale),
+                                                  C.c_void_p(extra.data_ptr()), extra.shape[1], extra.shape[0], zero_from,
+                                                  C.c_void_p(t.data_ptr()), C.c_void_p(ehs.data_ptr()), ehs.shape[1], pt, pi,
+                                                  C.c_void_p(out.data_ptr()), B, H, W, C.c_void_p(_stream_ptr()))
+        _lib.check(rc, "sd_unet_forward_concat")
+        return (out,)
+
     # LoRA adapters arrive fused into the weights (stablediffusion_amd.weights.fuse_lora); the
     # reference's runtime adapter switches (stable_diffusion.py:252-335) are not part of the engine.
     def set_adapters(self, *a, **k):

@@ -29,7 +29,7 @@ from typing import Any, Dict, List, Optional, Union
 
 import torch
 
-from . import _lib, pag as _pag, schedulers as _sched
+from . import _lib, pag as _pag, pix2pix as _p2p, schedulers as _sched
 from .image_processor import VaeImageProcessor
 
 
@@ -521,6 +521,9 @@ class StableDiffusionUnifiedPipeline:
         control_guidance_start: float = 0.0,
         control_guidance_end: float = 1.0,
         guess_mode: bool = False,
+        # InstructPix2Pix (diffusers StableDiffusionInstructPix2PixPipeline): an 8-channel UNet selects the mode, `image`
+        # is the picture to edit; None: 1.5 there, and nothing anywhere else
+        image_guidance_scale: Optional[float] = None,
         # SDXL refiner (diffusers StableDiffusionXLImg2ImgPipeline on model.refiner; the reference's handler TODO)
         use_refiner: bool = False,
         refiner_start: Optional[float] = None,
@@ -530,10 +533,17 @@ class StableDiffusionUnifiedPipeline:
         pag_scale: float = 0.0,
         pag_adaptive_scale: float = 0.0,
     ):
+        edit = _p2p.is_edit_unet(getattr(getattr(model, "base", None), "config", None))
+        if image_guidance_scale is not None and not edit:
+            raise ValueError("image_guidance_scale is InstructPix2Pix's: it needs a UNet with in_channels == 8")
+        if edit:
+            self._check_pix2pix(model, locals())
+            image_guidance_scale = float(_p2p.DEFAULT_IMAGE_GUIDANCE_SCALE if image_guidance_scale is None
+                                         else image_guidance_scale)
         if refiner_start is not None:
             if pag_scale is not None and float(pag_scale) > 0.0:
                 raise NotImplementedError("perturbed-attention guidance (pag_scale > 0) does not address the refiner")
-            call = {k: v for k, v in locals().items() if k != "self"}
+            call = {k: v for k, v in locals().items() if k not in ("self", "edit")}
             return self._ensemble_of_experts(call)
         pag_on = pag_scale is not None and float(pag_scale) > 0.0
         if pag_on:
@@ -603,9 +613,9 @@ class StableDiffusionUnifiedPipeline:
             image = model.image_processor.preprocess(image)
             if image.shape[1] != 4:
                 height, width = image.shape[-2], image.shape[-1]
-            elif use_refiner:
+            elif use_refiner or edit:
                 # the hand-off passes latents: the size the time ids state is theirs (diffusers' img2img reads it back
-                # from the prepared latents), not the refiner's sample_size
+                # from the prepared latents), not the refiner's sample_size.  (InstructPix2Pix: image latents as given.)
                 height = height or image.shape[-2] * model.vae_scale_factor
                 width = width or image.shape[-1] * model.vae_scale_factor
         if has_cn and image is None and (height is None or width is None):
@@ -640,7 +650,14 @@ class StableDiffusionUnifiedPipeline:
         self.is_inpaint = False
         mask = masked_image_latents_2b = image_latents = noise = None
         num_channels_unet = unet.config.in_channels
-        if image is None:
+        edit_latents = None
+        if edit:
+            # ---- InstructPix2Pix: pure noise, as txt2img; the image enters through the UNet's last four channels ----
+            n = batch_size * num_images_per_prompt
+            shape = (n, model.vae.config.latent_channels, height // model.vae_scale_factor, width // model.vae_scale_factor)
+            latents = self.prepare_latents_txt2img(shape, prompt_embeds.dtype, seed, latents)
+            edit_latents = self.prepare_image_latents_pix2pix(image, n, latents.dtype, tuple(latents.shape[-2:]))
+        elif image is None:
             shape = (batch_size * num_images_per_prompt, unet.config.in_channels,
                      height // model.vae_scale_factor, width // model.vae_scale_factor)
             latents = self.prepare_latents_txt2img(shape, prompt_embeds.dtype, seed, latents)
@@ -752,7 +769,9 @@ class StableDiffusionUnifiedPipeline:
                 raise ValueError("ControlNet needs a 4-channel UNet (9-channel inpaint UNets are not supported)")
             control = self.prepare_control_image(model, control_image, height, width, batch_size, num_images_per_prompt)
 
-        if self.do_classifier_free_guidance:
+        if self.do_classifier_free_guidance and edit:
+            prompt_embeds = _p2p.embed_rows(prompt_embeds, negative_prompt_embeds)       # [text ; image ; uncond]
+        elif self.do_classifier_free_guidance:
             prompt_embeds = torch.cat([negative_prompt_embeds, prompt_embeds], dim=0)
         prompt_embeds = prompt_embeds.to(self.device)
 
@@ -762,7 +781,8 @@ class StableDiffusionUnifiedPipeline:
                                 control_guidance_start=control_guidance_start, control_guidance_end=control_guidance_end,
                                 mask=mask, masked_image_latents=masked_image_latents_2b, image_latents=image_latents,
                                 image_noise=noise,
-                                pag=(float(pag_scale), float(pag_adaptive_scale)) if pag_on else None)
+                                pag=(float(pag_scale), float(pag_adaptive_scale)) if pag_on else None,
+                                edit=(edit_latents, image_guidance_scale) if edit else None)
 
         # ---- decode (:511-529) ----
         if self.output_type == "pt":
@@ -786,11 +806,12 @@ class StableDiffusionUnifiedPipeline:
     def _denoise(self, model, latents, timesteps, prompt_embeds, cross_attention_kwargs, added_cond_kwargs, tc_kwargs,
                  guidance_scale, guidance_rescale, seed, control=None, controlnet_conditioning_scale=1.0,
                  control_guidance_start=0.0, control_guidance_end=1.0, mask=None, masked_image_latents=None,
-                 image_latents=None, image_noise=None, pag=None):
+                 image_latents=None, image_noise=None, pag=None, edit=None):
         """The denoising loop (:465-507): `timesteps` over `latents`, the scheduler's update on the device where
         `_device_step_kind` finds one (`_device_iteration`) and in `scheduler.step` otherwise.  `tc_kwargs` is the
         guidance-embedded UNet's `timestep_cond`, `control` the prepared ControlNet image; `mask`, `masked_image_latents`
-        (doubled under CFG), `image_latents` and `image_noise` are the inpainting tensors."""
+        (doubled under CFG), `image_latents` and `image_noise` are the inpainting tensors; `edit` is InstructPix2Pix's
+        (image latents, image_guidance_scale): `latents` then hold 4 of the UNet's 8 channels."""
         unet = self._unet(model)
         num_channels_unet = unet.config.in_channels
         # The reference iterates over the device tensor `timesteps`; reading each element on the host
@@ -875,13 +896,22 @@ class StableDiffusionUnifiedPipeline:
                 if kind == "affine" and getattr(model.scheduler, "affine_noise", False):
                     step_noise = torch.randn(latents.shape, device=latents.device, dtype=latents.dtype)
                 pag_s = _pag.step_scale(pag[0], pag[1], t) if pag is not None else 0.0
+                if edit is not None and not kind:
+                    # InstructPix2Pix on scheduler.step: the same forward, [text ; image ; uncond] -> eps
+                    x = model.scheduler.scale_model_input(latents, t)
+                    noise_pred = self._edit_forward(unet, x, 1.0, t, prompt_embeds, edit[0], cross_attention_kwargs)
+                    if self.do_classifier_free_guidance:
+                        # (in fp32, as the device entries combine: three terms at g_t = 7.5 cost fp16 a digit)
+                        noise_pred = _p2p.combine(noise_pred.float(), guidance_scale, edit[1]).to(noise_pred.dtype)
+                    latents = self._host_step(model, noise_pred, t, latents, step_noise if lcm else None, lcm)
+                    continue
                 if kind:
                     # "linear" leaves `timestep_cond` out, which the host path and the other two kinds pass.  Kept as found;
                     # it cannot show today (a guidance-embedded UNet turns CFG off, and "linear" needs CFG)
                     unet_kwargs = cn_kwargs if kind == "linear" else {**cn_kwargs, **tc_kwargs}
                     latents = self._device_iteration(kind, state, model, latents, step_noise, t, prompt_embeds,
                                                      cross_attention_kwargs, added_cond_kwargs, guidance_scale,
-                                                     guidance_rescale, pag_s=pag_s, **unet_kwargs)
+                                                     guidance_rescale, pag_s=pag_s, edit=edit, **unet_kwargs)
                     if blend is not None:
                         last = i == len(timesteps_host) - 1
                         a, b = (1.0, 0.0) if last else model.scheduler.add_noise_coefficients(timesteps_host[i + 1])
@@ -936,6 +966,36 @@ class StableDiffusionUnifiedPipeline:
             if kv_cache is not None:
                 kv_cache(False)
         return latents
+
+    @staticmethod
+    def _check_pix2pix(model, kw):
+        """What an InstructPix2Pix call (a UNet with in_channels == 8) takes and what it does not."""
+        base = model.base
+        igs = kw["image_guidance_scale"]
+        if kw["mask_image"] is not None or kw["masked_image_latents"] is not None:
+            raise ValueError("InstructPix2Pix takes no mask_image (it edits the whole picture)")
+        if kw["strength"] != 1.0:
+            raise ValueError("InstructPix2Pix starts from pure noise: there is no strength")
+        if kw["guidance_rescale"] is not None and float(kw["guidance_rescale"]) > 0.0:
+            raise ValueError("InstructPix2Pix takes no guidance_rescale")
+        if kw["image"] is None:
+            raise ValueError("InstructPix2Pix (a UNet with in_channels == 8) needs image=, the picture to edit")
+        if igs is not None and not math.isfinite(float(igs)):
+            raise ValueError("image_guidance_scale must be finite")
+        if kw["use_refiner"] or kw["refiner_start"] is not None:
+            raise NotImplementedError("InstructPix2Pix does not address the refiner")
+        if bool(getattr(model, "has_controlnet", False)) or kw["control_image"] is not None:
+            raise NotImplementedError("InstructPix2Pix with a ControlNet loaded is not supported (unload_controlnet)")
+        if kw["ip_adapter_image"] is not None or kw["ip_adapter_image_embeds"] is not None:
+            raise NotImplementedError("InstructPix2Pix with an IP-Adapter image is not supported")
+        if kw["pag_scale"] is not None and float(kw["pag_scale"]) > 0.0:
+            raise NotImplementedError("InstructPix2Pix with perturbed-attention guidance (pag_scale > 0) is not supported")
+        if getattr(base, "deepcache", None) is not None:
+            raise NotImplementedError("InstructPix2Pix with DeepCache enabled is not supported (disable_deepcache)")
+        if getattr(base.config, "addition_embed_type", None) == "text_time":
+            raise NotImplementedError("InstructPix2Pix on a text_time (SDXL edit) UNet is not supported")
+        if int(getattr(base.config, "time_cond_proj_dim", None) or 0) > 0:
+            raise NotImplementedError("InstructPix2Pix on a guidance-embedded UNet (time_cond_proj_dim) is not supported")
 
     @staticmethod
     def _host_step(model, noise_pred, t, latents, noise, lcm):
@@ -1004,7 +1064,7 @@ class StableDiffusionUnifiedPipeline:
         return None
 
     def _device_iteration(self, kind, state, model, latents, noise, t, prompt_embeds, cross_attention_kwargs,
-                          added_cond_kwargs, guidance_scale, guidance_rescale=0.0, pag_s=0.0, **unet_kwargs):
+                          added_cond_kwargs, guidance_scale, guidance_rescale=0.0, pag_s=0.0, edit=None, **unet_kwargs):
         """One iteration with the scheduler's update on the device: the plan from the scheduler, the UNet forward, one
         step entry of the engine over a copy of the latents, the plan committed.  -> the new latents."""
         sched, unet = model.scheduler, self._unet(model)
@@ -1012,7 +1072,12 @@ class StableDiffusionUnifiedPipeline:
         plan = sched.affine_plan(t) if kind == "affine" else sched.fused_plan(t)
         latents = latents.contiguous()
         rows = 2 if self.do_classifier_free_guidance else 1          # ("linear" runs under CFG only)
-        if pag_s > 0.0:
+        if edit is not None:
+            # InstructPix2Pix: rows = [text ; image ; uncond] or the one conditioned group, from the un-duplicated,
+            # un-concatenated latents and image latents
+            rows = _p2p.GROUPS if self.do_classifier_free_guidance else 1
+            model_out = self._edit_forward(unet, latents, plan.in_scale, t, prompt_embeds, edit[0], cross_attention_kwargs)
+        elif pag_s > 0.0:
             # perturbed-attention guidance: rows = [uncond ; text ; perturbed] or [text ; perturbed], one engine forward
             rows += 1
             model_out = unet.forward_pag(latents, t, prompt_embeds, added_cond_kwargs=added_cond_kwargs,
@@ -1036,9 +1101,16 @@ class StableDiffusionUnifiedPipeline:
             m = torch.empty_like(out)
             _check(lib, lib.sd_pag_combine(_ptr(model_out), rows, _ptr(m), n, g, float(pag_s), _stream()))
             model_out, rows = m, 1
+        if edit is not None and rows == _p2p.GROUPS and kind != "linear":
+            m = torch.empty_like(out)
+            _check(lib, lib.sd_ip2p_combine(_ptr(model_out), _ptr(m), n, g, float(edit[1]), _stream()))
+            model_out, rows = m, 1
         if kind == "linear":
             hist_p = _ptr(state.hist) if plan.use_hist else None
-            if pag_s > 0.0:
+            if edit is not None:
+                rc = lib.sd_ip2p_linear_step(_ptr(model_out), _ptr(out), hist_p, n, g, float(edit[1]), plan.c_x, plan.c_eps,
+                                             plan.c_hist, plan.h_x, plan.h_eps, _stream())
+            elif pag_s > 0.0:
                 rc = lib.sd_pag_linear_step(_ptr(model_out), rows, _ptr(out), hist_p, n, g, float(pag_s), plan.c_x, plan.c_eps,
                                             plan.c_hist, plan.h_x, plan.h_eps, _stream())
             elif guidance_rescale > 0.0:
@@ -1061,6 +1133,21 @@ class StableDiffusionUnifiedPipeline:
         _check(lib, rc)
         (sched.affine_commit if kind == "affine" else sched.fused_commit)()
         return out
+
+    def _edit_forward(self, unet, latents, in_scale, t, prompt_embeds, image_latents, cross_attention_kwargs):
+        """The UNet forward of one InstructPix2Pix step from the un-duplicated 4-channel latents and the image latents:
+        [3B, ...] in [text ; image ; uncond] order under CFG (the third group reads zero image latents), [B, ...] without.
+        The engine takes both tensors as they are (forward_concat); any other UNet gets the 8-channel sample."""
+        cfg = self.do_classifier_free_guidance
+        B = latents.shape[0]
+        if hasattr(unet, "forward_concat"):
+            return unet.forward_concat(latents, t, prompt_embeds, image_latents, zero_from=2 * B if cfg else B,
+                                       in_scale=in_scale)[0]
+        x = latents if in_scale == 1.0 else latents * in_scale
+        if cfg:
+            x, image_latents = torch.cat([x] * _p2p.GROUPS), _p2p.image_rows(image_latents)
+        return unet(torch.cat([x, image_latents.to(x.dtype)], dim=1), t, prompt_embeds,
+                    cross_attention_kwargs=cross_attention_kwargs, added_cond_kwargs=None, return_dict=False)[0]
 
     def _cfg_forward(self, model, latents, in_scale, t, prompt_embeds, cross_attention_kwargs, added_cond_kwargs,
                      **unet_kwargs):
@@ -1258,6 +1345,21 @@ class StableDiffusionUnifiedPipeline:
         else:
             latents = latents.to(self.device)
         return latents * self.model.scheduler.init_noise_sigma
+
+    def prepare_image_latents_pix2pix(self, image, batch_size, dtype, hw):
+        """InstructPix2Pix's image latents [batch_size, 4, h, w]: the MODE of vae.encode(image), not multiplied by the
+        scaling factor (diffusers' prepare_image_latents); a 4-channel `image` is taken as those latents.  Encoded once."""
+        if not isinstance(image, torch.Tensor):
+            raise ValueError(f"`image` has to be a torch.Tensor in [-1, 1] (got {type(image)})")
+        image = image.to(device=self.device, dtype=dtype)
+        z = image if image.shape[1] == 4 else self.model.vae.encode(image).latent_dist.mode().to(dtype)
+        if tuple(z.shape[-2:]) != tuple(hw):
+            raise ValueError(f"image latents are {tuple(z.shape[-2:])}, the run's latents {tuple(hw)}")
+        if batch_size > z.shape[0] and batch_size % z.shape[0] == 0:
+            z = torch.cat([z] * (batch_size // z.shape[0]), dim=0)
+        elif batch_size != z.shape[0]:
+            raise ValueError(f"Cannot duplicate `image` of batch size {z.shape[0]} to {batch_size} text prompts.")
+        return z.contiguous()
 
     def prepare_latents_img2img(self, image, timestep, batch_size, num_images_per_prompt, dtype, seed=None,
                                 add_noise=True):
