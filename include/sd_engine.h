@@ -392,6 +392,51 @@ int sd_vae_encode(sd_vae* v, const void* img, void* moments, int B, int H, int W
 int sd_vae_encode_range_shift(sd_vae* v, int shift);
 int sd_vae_memory(const sd_vae* v, int64_t* weight_bytes, int64_t* workspace_bytes);
 
+/* -- Debug taps: the input and the output view of every block of ONE forward, copied as the block read and wrote them
+ *    (NHWC f16 with their row stride), for tests that compare each block with a reference on the block's own input.
+ *    Off (the default) a forward does nothing for them: the same launches, allocations and bits as without the facility.
+ *    sd_unet_tap(u, 1) / sd_vae_tap(v, 1): every following sd_unet_forward / _ex / _tc / _cn (sd_vae_decode / _encode)
+ *    replaces the records with its own, in buffers outside the workspace arena; the copies run on the forward's stream
+ *    and the forward's output is bit for bit what it is with taps off.  While taps are on, graph replay,
+ *    sd_unet_forward_cfg where it would share the CFG prefix, sd_unet_forward_pag, sd_unet_forward_concat and the
+ *    DeepCache store / reuse modes return SD_ERR_UNSUPPORTED and launch nothing.  (enable = 0 frees the records.)
+ *    Records, in execution order (names are diffusers prefixes):
+ *      UNet: "emb" (f32 [B, 4 C0]: silu(time_embedding (+ add_embedding)), the form the device keeps), "conv_in" (its
+ *      output; its input is the sample), every "*.resnets.j", "*.attentions.j", "*.downsamplers.0", "*.upsamplers.0"
+ *      (an up-path resnet's input is the [x | skip] concatenation), "tail" (input of conv_norm_out -> SiLU -> conv_out;
+ *      its output is the forward's).
+ *      VAE: "decoder.conv_in" (output of post_quant_conv + conv_in), "decoder.mid_block.resnets.j",
+ *      "decoder.mid_block.attentions.0", "decoder.up_blocks.i.resnets.j", "decoder.up_blocks.i.upsamplers.0",
+ *      "decoder.tail" (input); "encoder.conv_in", "encoder.down_blocks.i.resnets.j",
+ *      "encoder.down_blocks.i.downsamplers.0", "encoder.mid_block.*", "encoder.tail" (input).
+ *    A record holds N H W rows of `ld` elements; the view is columns [c0, c0 + C).  kind: SD_TAP_IN / SD_TAP_OUT, and
+ *    SD_TAP_PRE = the rows of an output view narrower than its row (ld > C) as they were before the block ran, so a
+ *    test can see that the block left the other columns alone.  scale: the activations are stored scale times their
+ *    value (sd_vae_encode_range_shift: 2^-shift; 1 otherwise).
+ *    _tap_info: SD_ERR_INVALID for a null argument or an index outside [0, _tap_count).  _tap_read synchronises the
+ *    device and copies record `index` to host memory `dst`; `bytes` must equal the record's (SD_ERR_INVALID). ---------- */
+#define SD_TAP_IN 0
+#define SD_TAP_OUT 1
+#define SD_TAP_PRE 2
+typedef struct sd_tap_info {
+    const char* name;   /* owned by the handle, valid until its next forward or sd_*_tap call */
+    int32_t kind;       /* SD_TAP_* */
+    int32_t dtype;      /* SD_DTYPE_F16 / SD_DTYPE_F32 */
+    int32_t N, H, W, C; /* the view: [N, H, W, C] */
+    int32_t c0;         /* first column of the view inside a row of the record */
+    int64_t ld;         /* elements per row of the record */
+    int64_t bytes;
+    float scale;
+} sd_tap_info;
+int sd_unet_tap(sd_unet* u, int enable);
+int sd_unet_tap_count(const sd_unet* u);
+int sd_unet_tap_info(const sd_unet* u, int index, sd_tap_info* info);
+int sd_unet_tap_read(sd_unet* u, int index, void* dst, int64_t bytes);
+int sd_vae_tap(sd_vae* v, int enable);
+int sd_vae_tap_count(const sd_vae* v);
+int sd_vae_tap_info(const sd_vae* v, int index, sd_tap_info* info);
+int sd_vae_tap_read(sd_vae* v, int index, void* dst, int64_t bytes);
+
 /* -- CLIP text encoder: replaces SDModelWrapper.text_encoder / .text_encoder_2 as encode_prompt calls
  *    them (sd_unified_pipeline.py:592-608).  Weight names are the
  *    transformers state-dict keys ("text_model.embeddings.token_embedding.weight", ...,

@@ -103,6 +103,15 @@ class SdProfEntry(C.Structure):
                 ("ms", C.c_double), ("launches", C.c_int64)]
 
 
+class SdTapInfo(C.Structure):
+    _fields_ = [("name", C.c_char_p), ("kind", C.c_int32), ("dtype", C.c_int32), ("N", C.c_int32), ("H", C.c_int32),
+                ("W", C.c_int32), ("C", C.c_int32), ("c0", C.c_int32), ("ld", C.c_int64), ("bytes", C.c_int64),
+                ("scale", C.c_float)]
+
+
+SD_TAP_IN, SD_TAP_OUT, SD_TAP_PRE = 0, 1, 2
+
+
 class SdCnProblem(C.Structure):
     _fields_ = [("x", C.c_void_p), ("ldx", C.c_int64), ("w", C.c_void_p), ("bias", C.c_void_p),
                 ("y", C.c_void_p), ("ldy", C.c_int64), ("M", C.c_int), ("C", C.c_int)]
@@ -185,6 +194,14 @@ SIGNATURES = {
     "sd_vae_encode": (_I, [_P, _P, _P, _I, _I, _I, _P]),
     "sd_vae_encode_range_shift": (_I, [_P, _I]),
     "sd_vae_memory": (_I, [_P, C.POINTER(_I64), C.POINTER(_I64)]),
+    "sd_unet_tap": (_I, [_P, _I]),
+    "sd_unet_tap_count": (_I, [_P]),
+    "sd_unet_tap_info": (_I, [_P, _I, C.POINTER(SdTapInfo)]),
+    "sd_unet_tap_read": (_I, [_P, _I, _P, _I64]),
+    "sd_vae_tap": (_I, [_P, _I]),
+    "sd_vae_tap_count": (_I, [_P]),
+    "sd_vae_tap_info": (_I, [_P, _I, C.POINTER(SdTapInfo)]),
+    "sd_vae_tap_read": (_I, [_P, _I, _P, _I64]),
     "sd_clip_create": (_I, [C.POINTER(SdClipConfig), C.POINTER(_P)]),
     "sd_clip_destroy": (_I, [_P]),
     "sd_clip_num_weights": (_I, [_P]),

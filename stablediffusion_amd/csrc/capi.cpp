@@ -99,6 +99,39 @@ void with_images(UNetCall* c, const void* image_embeds, int n_img) {
     c->n_img = image_embeds ? n_img : 0;
 }
 
+// the list / info / read-back trio of the debug taps, shared by the UNet's and the VAE's entries
+int tap_switch(sd::TapSink& t, int enable) {
+    t.clear();
+    t.on = enable != 0;
+    t.scale = 1.f;
+    return SD_OK;
+}
+int tap_info(const sd::TapSink& t, int index, sd_tap_info* info) {
+    if (!info) { set_error("null argument"); return SD_ERR_INVALID; }
+    if (index < 0 || index >= (int)t.entries.size()) { set_error("tap index out of range"); return SD_ERR_INVALID; }
+    const sd::TapEntry& e = t.entries[(size_t)index];
+    info->name = e.name.c_str();
+    info->kind = e.kind;
+    info->dtype = e.f32 ? SD_DTYPE_F32 : SD_DTYPE_F16;
+    info->N = e.N; info->H = e.H; info->W = e.W; info->C = e.C; info->c0 = e.c0;
+    info->ld = e.ld;
+    info->bytes = (int64_t)e.bytes;
+    info->scale = t.scale;
+    return SD_OK;
+}
+int tap_read(const sd::TapSink& t, int index, void* dst, int64_t bytes) {
+    if (!dst) { set_error("null argument"); return SD_ERR_INVALID; }
+    if (index < 0 || index >= (int)t.entries.size()) { set_error("tap index out of range"); return SD_ERR_INVALID; }
+    const sd::TapEntry& e = t.entries[(size_t)index];
+    if (bytes != (int64_t)e.bytes) {
+        set_error("tap read: " + std::to_string(bytes) + " bytes asked, the record holds " + std::to_string(e.bytes));
+        return SD_ERR_INVALID;
+    }
+    SD_HIP_CHECK(hipDeviceSynchronize());
+    SD_HIP_CHECK(hipMemcpy(dst, e.dev, e.bytes, hipMemcpyDeviceToHost));
+    return SD_OK;
+}
+
 bool controlnet_fits(const sd_unet_config& u, const sd_unet_config& n, std::string* why) {
     if (n.num_blocks != u.num_blocks || n.layers_per_block != u.layers_per_block) {
         *why = "num_blocks / layers_per_block differ from the UNet's";
@@ -271,6 +304,19 @@ int sd_unet_forward_concat(sd_unet* u, const void* latents, int B_lat, float in_
     c.extra_channels = extra_channels; c.extra_rows = extra_rows; c.zero_from = zero_from;
     c.lat_rows = B_lat; c.in_scale = in_scale;
     return u->impl.forward_concat(c, static_cast<hipStream_t>(stream));
+}
+int sd_unet_tap(sd_unet* u, int enable) {
+    if (!u) { set_error("null handle"); return SD_ERR_INVALID; }
+    return tap_switch(u->impl.taps, enable);
+}
+int sd_unet_tap_count(const sd_unet* u) { return u ? (int)u->impl.taps.entries.size() : 0; }
+int sd_unet_tap_info(const sd_unet* u, int index, sd_tap_info* info) {
+    if (!u) { set_error("null handle"); return SD_ERR_INVALID; }
+    return tap_info(u->impl.taps, index, info);
+}
+int sd_unet_tap_read(sd_unet* u, int index, void* dst, int64_t bytes) {
+    if (!u) { set_error("null handle"); return SD_ERR_INVALID; }
+    return tap_read(u->impl.taps, index, dst, bytes);
 }
 int sd_unet_cfg_share(const sd_unet_config* cfg) { return cfg && sd::unet_cfg_share_eligible(*cfg) ? 1 : 0; }
 int sd_unet_set_ip_adapter_scale(sd_unet* u, float scale) {
@@ -480,6 +526,19 @@ int sd_vae_encode_range_shift(sd_vae* v, int shift) {
     if (!v || shift < 0 || shift > 14) { set_error("sd_vae_encode_range_shift: shift in 0..14"); return SD_ERR_INVALID; }
     v->impl.encode_shift = shift;
     return SD_OK;
+}
+int sd_vae_tap(sd_vae* v, int enable) {
+    if (!v) { set_error("null handle"); return SD_ERR_INVALID; }
+    return tap_switch(v->impl.taps, enable);
+}
+int sd_vae_tap_count(const sd_vae* v) { return v ? (int)v->impl.taps.entries.size() : 0; }
+int sd_vae_tap_info(const sd_vae* v, int index, sd_tap_info* info) {
+    if (!v) { set_error("null handle"); return SD_ERR_INVALID; }
+    return tap_info(v->impl.taps, index, info);
+}
+int sd_vae_tap_read(sd_vae* v, int index, void* dst, int64_t bytes) {
+    if (!v) { set_error("null handle"); return SD_ERR_INVALID; }
+    return tap_read(v->impl.taps, index, dst, bytes);
 }
 int sd_vae_memory(const sd_vae* v, int64_t* weight_bytes, int64_t* workspace_bytes) {
     if (!v) { set_error("null handle"); return SD_ERR_INVALID; }

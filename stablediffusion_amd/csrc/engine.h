@@ -17,9 +17,10 @@ struct View {
     half_t* p = nullptr;
     long ld = 0;
     int C = 0;
+    int c0 = 0;         // column of `p` inside its row (slice keeps it): what a debug tap needs to copy whole rows
     View() {}
     View(half_t* p_, long ld_, int C_) : p(p_), ld(ld_), C(C_) {}
-    View slice(int c0, int c) const { return View(p + c0, ld, c); }
+    View slice(int c, int n) const { View v(p + c, ld, n); v.c0 = c0 + c; return v; }
 };
 
 // Bump allocator over one hipMalloc'ed slab with stack-style mark/release.  In "dry" mode no memory
@@ -213,6 +214,31 @@ struct PagState {
     std::function<void(std::vector<RowDupSeg>&)> caller_segs;
 };
 
+// Debug taps (sd_unet_tap / sd_vae_tap): copies of the activation views at block boundaries of ONE forward, for the
+// per-block tests.  Off (Ctx::tap == nullptr, the default) a forward does no tap work at all: no launch, no allocation,
+// the arena plan and the profile are what they are without the facility.  On, the live pass copies each tapped view on
+// the forward's stream into a buffer of the sink's own (hipMalloc, outside the arena; the planning pass records
+// nothing, so no plan depends on it).  A view narrower than its row is copied with its whole rows (View::c0 says
+// where they start): the test sees the row stride the block read or wrote through, and, for an output, the
+// neighbouring columns before (kind kTapPre) and after the block.
+enum { kTapIn = 0, kTapOut = 1, kTapPre = 2 };
+struct TapEntry {
+    std::string name;   // diffusers prefix of the block ("down_blocks.0.resnets.1", "conv_in", "tail", "emb")
+    int kind = kTapIn;
+    int f32 = 0;        // elements are float (the time embedding) instead of half
+    int N = 0, H = 0, W = 0, C = 0, c0 = 0;
+    long ld = 0;        // row stride of the copy in elements: rows N H W, columns [c0, c0 + C) are the view
+    void* dev = nullptr;
+    size_t bytes = 0;
+};
+struct TapSink {
+    bool on = false;
+    float scale = 1.f;  // stream scale the activations carry (VAE::run_encode: 2^-encode_shift), 1 otherwise
+    std::vector<TapEntry> entries;
+    ~TapSink() { clear(); }
+    void clear();       // synchronises the device when there is something to free
+};
+
 // Execution context of one forward call.
 struct Ctx {
     Arena* arena;
@@ -232,7 +258,18 @@ struct Ctx {
     int ip_T = 0;
     float ip_scale = 1.f;
     PagState* pag = nullptr;            // forward_pag only
+    TapSink* tap = nullptr;             // debug taps of this forward (nullptr: off)
 };
+// Record view `v` ([N H W, v.C] fp16, kind kTap*) under `name`; nothing on a dry or failed context.  Callers guard with
+// `if (c.tap)` so that a forward without taps does not even build the name.
+void ctx_tap(Ctx& c, const std::string& name, int kind, View v, int N, int H, int W);
+void ctx_tap_f32(Ctx& c, const std::string& name, const float* p, int rows, int cols);
+// a block's boundary: before it runs, its input and (where the output view is narrower than its row) the rows it will
+// write into; after it, the output
+inline void ctx_tap_begin(Ctx& c, const std::string& name, View in, int N, int H, int W, View out, int Ho, int Wo) {
+    ctx_tap(c, name, kTapIn, in, N, H, W);
+    if (out.C != out.ld) ctx_tap(c, name, kTapPre, out, N, Ho, Wo);
+}
 // images a launch over an N-image tensor runs on right now: all of them, or the un-perturbed ones in front while the
 // perturbed group of a forward_pag call does not exist yet
 inline int ctx_live(const Ctx& c, int N) { return c.pag && !c.pag->widened ? c.pag->Nq : N; }

@@ -368,6 +368,11 @@ struct UNet : Encoder {
     CacheTag dc_tag;                    // (no pointer; B, H, W, shared CFG prefix or not) of the stored step
     int set_deep_cache(int depth);
 
+    // ---- debug taps (sd_unet_tap; engine.h: TapSink): on, the plain forward records the input and output view of
+    // every block; the modes whose launches differ from the plain forward's are refused (tap_refuses: 4 when `mode`).
+    TapSink taps;
+    int tap_refuses(bool mode);
+
     ConvW conv_out;
     NormW norm_out;
     std::vector<std::vector<Resnet>> up_res;
@@ -390,6 +395,7 @@ struct VAE {
     // engine's answer to `config.force_upcast` (sd_unified_pipeline.py:1020-1036 runs such VAEs in fp32 around encode
     // because their activations leave fp16's range).  0 = plain fp16 storage.
     int encode_shift = 0;
+    TapSink taps;                       // debug taps of the next decode / encode (sd_vae_tap; engine.h)
 
     sd_vae_config cfg;
     WeightStore ws;

@@ -368,6 +368,45 @@ GnStatBuf* ctx_gnbuf(Ctx& c) {
     return b;
 }
 
+// ------------------------------------------------------------------------------------- debug taps
+void TapSink::clear() {
+    if (entries.empty()) return;
+    (void)hipDeviceSynchronize();           // copies into the buffers may still be in flight
+    for (TapEntry& e : entries)
+        if (e.dev) (void)hipFree(e.dev);
+    entries.clear();
+}
+
+static void tap_copy(Ctx& c, TapEntry e, const void* src) {
+    hipError_t err = hipMalloc(&e.dev, e.bytes);
+    if (err == hipSuccess) {
+        c.tap->entries.push_back(e);        // (owned by the sink from here on)
+        err = hipMemcpyAsync(e.dev, src, e.bytes, hipMemcpyDeviceToDevice, c.stream);
+    }
+    if (err != hipSuccess) { set_error(std::string("tap ") + e.name + ": " + hipGetErrorString(err)); c.err = 3; }
+}
+
+void ctx_tap(Ctx& c, const std::string& name, int kind, View v, int N, int H, int W) {
+    if (!c.tap || c.dry || c.err) return;
+    if (!v.p || v.c0 < 0 || v.c0 + v.C > v.ld) { set_error("tap " + name + ": view does not lie inside its row"); c.err = 1; return; }
+    TapEntry e;
+    e.name = name; e.kind = kind;
+    e.N = N; e.H = H; e.W = W; e.C = v.C; e.ld = v.ld;
+    // a full-width view is one block; a narrower one is copied with its rows, from the row start
+    e.c0 = v.C == v.ld ? 0 : v.c0;
+    e.bytes = (size_t)N * H * W * v.ld * sizeof(half_t);
+    tap_copy(c, e, v.p - e.c0);
+}
+
+void ctx_tap_f32(Ctx& c, const std::string& name, const float* p, int rows, int cols) {
+    if (!c.tap || c.dry || c.err) return;
+    TapEntry e;
+    e.name = name; e.kind = kTapOut; e.f32 = 1;
+    e.N = rows; e.H = 1; e.W = 1; e.C = cols; e.ld = cols;
+    e.bytes = (size_t)rows * cols * sizeof(float);
+    tap_copy(c, e, p);
+}
+
 // -------------------------------------------------------------------------------------------- ops
 void op_conv(Ctx& c, const ConvW& w, View x, int N, int H, int W, View y, int stride, int up,
              const float* rowadd, int rowadd_ld, const View* res, int geglu, int pad, int act, const ConvFuse* fuse) {

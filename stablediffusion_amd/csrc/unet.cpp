@@ -492,6 +492,21 @@ void UNet::set_ip_adapter(IPAdapter* a) {
 }
 
 // ------------------------------------------------------------------------------------------ blocks
+namespace {
+// Debug taps (engine.h: TapSink) around one block, named by its diffusers prefix: "<grp>.<i>.<kind>.<j>", or
+// "<grp>.<kind>.<j>" with i < 0 (the mid block).  Without a sink neither builds the name.
+std::string tap_name(const char* grp, int i, const char* kind, int j) {
+    return std::string(grp) + (i < 0 ? "" : "." + std::to_string(i)) + "." + kind + "." + std::to_string(j);
+}
+inline void tap_begin(Ctx& c, const char* grp, int i, const char* kind, int j, View in, int N, int H, int W, View out,
+                      int Ho, int Wo) {
+    if (c.tap) ctx_tap_begin(c, tap_name(grp, i, kind, j), in, N, H, W, out, Ho, Wo);
+}
+inline void tap_end(Ctx& c, const char* grp, int i, const char* kind, int j, View out, int N, int Ho, int Wo) {
+    if (c.tap) ctx_tap(c, tap_name(grp, i, kind, j), kTapOut, out, N, Ho, Wo);
+}
+}  // namespace
+
 void run_resnet(Ctx& c, const Resnet& r, View x, int N, int H, int W, View out, int G, float eps,
                 const float* tproj, int tproj_ld, const GnStatBuf* x_stats, GnStatBuf** out_stats, float stream_scale,
                 GnStatBuf* out_buf, int out_groups) {
@@ -792,6 +807,7 @@ int Encoder::run_temb(Ctx& c, const float* timesteps, const half_t* add_text, co
     }
     // every resnet consumes the embedding only as time_emb_proj(silu(emb)): the SiLU is applied once
     // here instead of inside the weight-bandwidth-bound stacked GEMV
+    if (c.tap) ctx_tap_f32(c, "emb", emb, B, temb);             // (what exists on the device: silu(emb))
     if (go && !c.err) c.err = launch_small_linear(emb, temb, temb_stack.w, temb_stack.bias, tproj, temb_total, B, temb, temb_total, 0, 0, s);
 
     return c.err;
@@ -884,17 +900,23 @@ View Encoder::run_down(Ctx& c, View x, GnStatBuf*& xs, int B, int& h, int& w, Vi
                 GnStatBuf* rs = nullptr;
                 const CfgShare* sh = (i == 0 && j == 0) ? share : nullptr;
                 const int Bl = ctx_live(c, B);
+                tap_begin(c, "down_blocks", i, "resnets", j, x, B, h, w, tmp, h, w);
                 run_resnet(c, r, x, sh ? Bl / 2 : Bl, h, w, tmp, G, eps, tproj, temb_total, xs, &rs);
+                tap_end(c, "down_blocks", i, "resnets", j, tmp, B, h, w);
                 View dst = skip_view(skip_i);
                 if (c.pag) c.pag->skips_done = skip_i;
+                tap_begin(c, "down_blocks", i, "attentions", j, tmp, B, h, w, dst, h, w);
                 run_xformer(c, down_att[i][j], tmp, B, h, w, dst, G, text_kv, L, rs, &xs, skip_stat(skip_i, (long)h * w, r.cout),
                             0, sh);
+                tap_end(c, "down_blocks", i, "attentions", j, dst, B, h, w);
                 a.release(mk);
                 x = dst;
             } else {
                 View dst = skip_view(skip_i);
+                tap_begin(c, "down_blocks", i, "resnets", j, x, B, h, w, dst, h, w);
                 run_resnet(c, r, x, ctx_live(c, B), h, w, dst, G, eps, tproj, temb_total, xs, &xs, 1.f,
                            skip_stat(skip_i, (long)h * w, r.cout));
+                tap_end(c, "down_blocks", i, "resnets", j, dst, B, h, w);
                 x = dst;
             }
             ++skip_i;
@@ -905,7 +927,9 @@ View Encoder::run_down(Ctx& c, View x, GnStatBuf*& xs, int B, int& h, int& w, Vi
             f.gn_out = skip_stat(skip_i, (long)(h / 2) * (w / 2), down_ds[i].cout);
             View dst = skip_view(skip_i++);
             f.gn_groups = G;
+            tap_begin(c, "down_blocks", i, "downsamplers", 0, x, B, h, w, dst, h / 2, w / 2);
             op_conv(c, down_ds[i], x, ctx_live(c, B), h, w, dst, 2, 0, nullptr, 0, nullptr, 0, -1, 0, &f);
+            tap_end(c, "down_blocks", i, "downsamplers", 0, dst, B, h / 2, w / 2);
             xs = f.gn_out;
             h /= 2; w /= 2;
             x = dst;
@@ -926,9 +950,15 @@ void Encoder::run_mid(Ctx& c, View x, GnStatBuf* xs, int B, int h, int w, View t
     const long M = (long)B * h * w;
     View m0(a.alloc_h(M * C), C, C), m1(a.alloc_h(M * C), C, C);
     GnStatBuf *s0 = nullptr, *s1 = nullptr;
+    tap_begin(c, "mid_block", -1, "resnets", 0, x, B, h, w, m0, h, w);
     run_resnet(c, mid_r0, x, ctx_live(c, B), h, w, m0, G, eps, tproj, temb_total, xs, &s0);
+    tap_end(c, "mid_block", -1, "resnets", 0, m0, B, h, w);
+    tap_begin(c, "mid_block", -1, "attentions", 0, m0, B, h, w, m1, h, w);
     run_xformer(c, mid_att, m0, B, h, w, m1, G, text_kv, L, s0, &s1);
+    tap_end(c, "mid_block", -1, "attentions", 0, m1, B, h, w);
+    tap_begin(c, "mid_block", -1, "resnets", 1, m1, B, h, w, dst, h, w);
     run_resnet(c, mid_r1, m1, ctx_live(c, B), h, w, dst, G, eps, tproj, temb_total, s1);   // output joins a concat: no consumer
+    tap_end(c, "mid_block", -1, "resnets", 1, dst, B, h, w);
 }
 
 int Encoder::num_skips() const { return 1 + cfg.num_blocks * cfg.layers_per_block + (cfg.num_blocks - 1); }
@@ -1088,7 +1118,7 @@ int UNet::run(Ctx& c, const UNetCall& call, int dc) {
     int skip_i = 0;   // index of the next skip to produce; consumer is cats[nskip-1-skip_i]
     auto skip_view = [&](int si) {
         const Cat& ct = cats[(size_t)(nskip - 1 - si)];
-        return View(ct.p + ct.c1, ct.c1 + ct.c2, ct.c2);
+        return View(ct.p, ct.c1 + ct.c2, ct.c1 + ct.c2).slice(ct.c1, ct.c2);
     };
 
     // ---- GroupNorm summaries travel from the convolution that writes a tensor to the GroupNorm that reads
@@ -1132,7 +1162,10 @@ int UNet::run(Ctx& c, const UNetCall& call, int dc) {
         GnStatBuf ring[Ctx::kGnPool];
         for (int i = 0; i < Ctx::kGnPool; ++i) ring[i] = c.gnpool[i];
         const int ring_next = c.gn_next, ring_groups = c.gn_groups;
+        TapSink* const tap = c.tap;         // (the ControlNet's encoder shares run_down / run_mid: its blocks are not tapped)
+        c.tap = nullptr;
         if (int rc = run_controlnet(c, call, cn_sites, cn_mid)) return rc;
+        c.tap = tap;
         for (int i = 0; i < Ctx::kGnPool; ++i) c.gnpool[i] = ring[i];
         c.gn_next = ring_next; c.gn_groups = ring_groups;
     }
@@ -1140,9 +1173,11 @@ int UNet::run(Ctx& c, const UNetCall& call, int dc) {
     // ---- conv_in: one launch straight from the NCHW latents (edge.hip); otherwise (inpainting's 9 channels, odd maps)
     //      im2col into a 64-wide K, then the GEMM kernel ----
     int h = H, w = W;
+    if (c.tap) ctx_tap(c, "conv_in", kTapPre, skip_view(skip_i), B, H, W);      // (its input is the caller's sample)
     run_conv_in(c, sample, cfg_in ? Bp : ctx_live(c, B), H, W, skip_view(skip_i), skip_stat(skip_i, (long)H * W, boc[0]),
                 nullptr, &xs, cat);
     View x = skip_view(skip_i++);
+    if (c.tap) ctx_tap(c, "conv_in", kTapOut, x, B, H, W);
     if (pag) {
         // what the late widening copies besides the flagged transformer's own input: tproj, and every skip that is
         // written and still to be read by the up path
@@ -1277,14 +1312,20 @@ int UNet::run(Ctx& c, const UNetCall& call, int dc) {
             if (cfg.up_block_has_attn[i]) {
                 View tmp(a.alloc_h((long)B * h * w * r.cout), r.cout, r.cout);
                 GnStatBuf* rs = nullptr;
+                tap_begin(c, "up_blocks", i, "resnets", j, xin, B, h, w, tmp, h, w);
                 run_resnet(c, r, xin, Bl, h, w, tmp, G, eps, tproj, temb_total, xin_stats, &rs);
+                tap_end(c, "up_blocks", i, "resnets", j, tmp, B, h, w);
+                tap_begin(c, "up_blocks", i, "attentions", j, tmp, B, h, w, dst, h, w);
                 if (last) run_xformer(c, up_att[i][j], tmp, B, h, w, dst, G, text_kv, L, rs, &xs);
                 else if (hid_here) run_xformer(c, up_att[i][j], tmp, B, h, w, dst, G, text_kv, L, rs, &outp, &hid, nx_groups);
                 else run_xformer(c, up_att[i][j], tmp, B, h, w, dst, G, text_kv, L, rs, nullptr);
+                tap_end(c, "up_blocks", i, "attentions", j, dst, B, h, w);
             } else {
+                tap_begin(c, "up_blocks", i, "resnets", j, xin, B, h, w, dst, h, w);
                 if (last) run_resnet(c, r, xin, Bl, h, w, dst, G, eps, tproj, temb_total, xin_stats, &xs);
                 else if (hid_here) run_resnet(c, r, xin, Bl, h, w, dst, G, eps, tproj, temb_total, xin_stats, &outp, 1.f, &hid, nx_groups);
                 else run_resnet(c, r, xin, Bl, h, w, dst, G, eps, tproj, temb_total, xin_stats, nullptr);
+                tap_end(c, "up_blocks", i, "resnets", j, dst, B, h, w);
             }
             if (last) {
                 final_x = dst;   // the temporary stays alive for the tail
@@ -1295,7 +1336,9 @@ int UNet::run(Ctx& c, const UNetCall& call, int dc) {
                     ConvFuse fu;
                     fu.gn_out = nx_groups > 0 ? &hid : nullptr;
                     fu.gn_groups = nx_groups;
+                    tap_begin(c, "up_blocks", i, "upsamplers", 0, dst, B, h, w, up_dst, 2 * h, 2 * w);
                     op_conv(c, up_us[i], dst, ctx_live(c, B), h, w, up_dst, 1, 1, nullptr, 0, nullptr, 0, -1, 0, nx_groups > 0 ? &fu : nullptr);
+                    tap_end(c, "up_blocks", i, "upsamplers", 0, up_dst, B, 2 * h, 2 * w);
                     outp = fu.gn_out;
                     h *= 2; w *= 2;
                 }
@@ -1311,6 +1354,7 @@ int UNet::run(Ctx& c, const UNetCall& call, int dc) {
     {
         const int C = boc[0];
         const long M = (long)B * h * w;
+        if (c.tap) ctx_tap(c, "tail", kTapIn, final_x, B, h, w);                // (its output is the forward's)
         TailParams tp;
         tp.x = final_x.p; tp.ldx = final_x.ld;
         if (xs && xs->st.part) { tp.gn_part = xs->st.part; tp.gn_S = xs->st.S; tp.gn_rows = xs->st.rows; }
@@ -1450,6 +1494,7 @@ int UNet::forward(const UNetCall& in, hipStream_t stream) {
     const CfgIn* const cfg_in = call.cfg_in;
     const PagIn* const pag = call.pag;
     if (!finalized) { set_error("unet: forward before finalize"); return 2; }
+    if (int rc = tap_refuses(graph_enabled || cfg_in || pag || call.extra || dc_mode != SD_DC_PLAIN)) return rc;
     if (pag && (B % (pag->groups + 1) != 0 || graph_enabled || control || image_embeds || tcond || dc_mode != SD_DC_PLAIN)) {
         set_error("unet: perturbed-attention forward not available for this call");
         return 2;
@@ -1526,9 +1571,20 @@ int UNet::forward(const UNetCall& in, hipStream_t stream) {
     key.n_ctrl = use_cn ? call.n_ctrl : 0;
     key.dc_depth = dc != SD_DC_PLAIN ? dc_depth : 0;
     key.cat_rows = call.extra ? call.lat_rows : 0;
-    const int rc = plan_and_run(arena, stream, planned[dc], key, "unet", [&](Ctx& c) { return run(c, call, dc); });
+    if (taps.on) taps.clear();              // one forward's records at a time
+    const int rc = plan_and_run(arena, stream, planned[dc], key, "unet", [&](Ctx& c) {
+        c.tap = taps.on ? &taps : nullptr;
+        return run(c, call, dc);
+    });
     if (!rc && dc == SD_DC_STORE) dc_tag.set(nullptr, B, H, W, cfg_in != nullptr);
     return rc;
+}
+
+int UNet::tap_refuses(bool mode) {
+    if (!taps.on || !mode) return 0;
+    set_error("unet: debug taps are on (sd_unet_tap): graph replay, the shared CFG prefix, forward_pag, forward_concat and "
+              "the DeepCache store / reuse modes do not run; their suites prove them against the plain forward");
+    return 4;
 }
 
 int UNet::set_deep_cache(int depth) {
@@ -1559,6 +1615,9 @@ int UNet::forward_cfg(const UNetCall& lat, float in_scale, bool share, hipStream
     const int B = lat.B, H = lat.H, W = lat.W;
     if (!finalized) { set_error("unet: forward before finalize"); return 2; }
     if (B <= 0 || H <= 0 || W <= 0) { set_error("unet: forward_cfg: empty batch"); return 1; }
+    // (not shared it is the plain forward on the duplicated latents, which taps; under graph replay forward() refuses,
+    // and nothing may be launched before it does)
+    if (int rc = tap_refuses(cfg_share_active(share) || graph_enabled)) return rc;
     UNetCall call = lat;
     call.B = 2 * B;
     if (cfg_share_active(share)) {
@@ -1589,6 +1648,7 @@ int UNet::forward_concat(const UNetCall& call, hipStream_t stream) {
     const int B = call.B, Bl = call.lat_rows;
     if (!finalized) { set_error("unet: forward before finalize"); return 2; }
     if (B <= 0 || call.H <= 0 || call.W <= 0 || Bl <= 0) { set_error("unet: forward_concat: empty batch"); return 1; }
+    if (int rc = tap_refuses(true)) return rc;
     // (what the handle is set up for comes first: a ControlNet only attaches to a 4-channel UNet, which the channel check below
     // would turn away with another code)
     if (graph_enabled) { set_error("unet: forward_concat under graph replay is not supported"); return 4; }
@@ -1650,6 +1710,7 @@ int UNet::forward_pag(const UNetCall& lat, float in_scale, bool cfg_on, bool sha
     const int B = lat.B, H = lat.H, W = lat.W;
     if (!finalized) { set_error("unet: forward before finalize"); return 2; }
     if (B <= 0 || H <= 0 || W <= 0) { set_error("unet: forward_pag: empty batch"); return 1; }
+    if (int rc = tap_refuses(true)) return rc;
     if (cn) { set_error("unet: forward_pag with a ControlNet attached is not supported"); return 4; }
     if (ip && ip_scale != 0.f) { set_error("unet: forward_pag with an IP-Adapter at a non-zero scale is not supported"); return 4; }
     if (dc_mode != SD_DC_PLAIN) { set_error("unet: forward_pag in a DeepCache store / reuse mode is not supported (a reuse step has no perturbed branch)"); return 4; }

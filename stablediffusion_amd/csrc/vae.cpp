@@ -158,6 +158,20 @@ int VAE::finalize() {
     return 0;
 }
 
+namespace {
+// debug taps (engine.h: TapSink) around one block; without a sink the name is not even built
+template <class S>
+inline void tap_begin(Ctx& c, const S& name, View in, int N, int H, int W, View out, int Ho, int Wo) {
+    if (c.tap) ctx_tap_begin(c, std::string(name), in, N, H, W, out, Ho, Wo);
+}
+template <class S>
+inline void tap_end(Ctx& c, const S& name, View out, int N, int Ho, int Wo) {
+    if (c.tap) ctx_tap(c, std::string(name), kTapOut, out, N, Ho, Wo);
+}
+// (the name of a numbered block, formed only when a sink is attached)
+#define SD_VAE_TAP(c, expr) ((c).tap ? std::string(expr) : std::string())
+}  // namespace
+
 void VAE::run_attn(Ctx& c, const VaeAttn& at, View x, int N, int H, int W, View out, const GnStatBuf* x_stats,
                    GnStatBuf** out_stats, float stream_scale) {
     Arena& a = *c.arena;
@@ -213,18 +227,28 @@ int VAE::run_decode(Ctx& c, const half_t* z, half_t* img, int B, int h, int w) {
         xs = f.gn_out;
         a.release(mk);
     }
+    tap_end(c, "decoder.conv_in", x, B, h, w);          // (post_quant_conv + conv_in: its input is the caller's z)
     // ping-pong activation buffers sized for the largest level, allocated once
     // (every resnet's temporaries are stack-released inside run_resnet)
     View y(a.alloc_h(M * top), top, top);
+    tap_begin(c, "decoder.mid_block.resnets.0", x, B, h, w, y, h, w);
     run_resnet(c, d_mid0, x, B, h, w, y, G, kVaeEps, nullptr, 0, xs, &xs);
+    tap_end(c, "decoder.mid_block.resnets.0", y, B, h, w);
+    tap_begin(c, "decoder.mid_block.attentions.0", y, B, h, w, x, h, w);
     run_attn(c, d_attn, y, B, h, w, x, xs, &xs);
+    tap_end(c, "decoder.mid_block.attentions.0", x, B, h, w);
+    tap_begin(c, "decoder.mid_block.resnets.1", x, B, h, w, y, h, w);
     run_resnet(c, d_mid1, x, B, h, w, y, G, kVaeEps, nullptr, 0, xs, &xs);
+    tap_end(c, "decoder.mid_block.resnets.1", y, B, h, w);
     View cur = y;
     for (int i = 0; i < nb; ++i) {
         for (int j = 0; j < cfg.layers_per_block + 1; ++j) {
             const Resnet& r = d_up[i][j];
             View nxt(a.alloc_h(M * r.cout), r.cout, r.cout);
+            const std::string tn = SD_VAE_TAP(c, "decoder.up_blocks." + std::to_string(i) + ".resnets." + std::to_string(j));
+            tap_begin(c, tn, cur, B, h, w, nxt, h, w);
             run_resnet(c, r, cur, B, h, w, nxt, G, kVaeEps, nullptr, 0, xs, &xs);
+            tap_end(c, tn, nxt, B, h, w);
             cur = nxt;
         }
         if (i != nb - 1) {
@@ -232,7 +256,10 @@ int VAE::run_decode(Ctx& c, const half_t* z, half_t* img, int B, int h, int w) {
             View nxt(a.alloc_h(M * 4 * C), C, C);
             ConvFuse f;
             gn_fuse(f, (long)h * w * 4, C);
+            const std::string tn = SD_VAE_TAP(c, "decoder.up_blocks." + std::to_string(i) + ".upsamplers.0");
+            tap_begin(c, tn, cur, B, h, w, nxt, 2 * h, 2 * w);
             op_conv(c, d_us[i], cur, B, h, w, nxt, 1, 1, nullptr, 0, nullptr, 0, -1, 0, &f);
+            tap_end(c, tn, nxt, B, 2 * h, 2 * w);
             xs = f.gn_out;
             h *= 2; w *= 2; M *= 4;
             cur = nxt;
@@ -241,6 +268,7 @@ int VAE::run_decode(Ctx& c, const half_t* z, half_t* img, int B, int h, int w) {
     {
         const int C = boc[0];
         View hn(a.alloc_h(M * C), C, C);
+        if (c.tap) ctx_tap(c, "decoder.tail", kTapIn, cur, B, h, w);        // (its output is the caller's image)
         op_groupnorm(c, d_norm_out, cur, hn, B, (long)h * w, G, kVaeEps, 1, xs);
         if (cfg.out_channels <= 4 && d_conv_out.ks == 3 && d_conv_out.K == 9L * C && M >= kSmallCoutMinPixels) {
             if (go && !c.err) {
@@ -291,11 +319,16 @@ int VAE::run_encode(Ctx& c, const half_t* img, half_t* moments, int B, int H, in
         xs = f.gn_out;
         a.release(mk);
     }
+    if (c.tap) c.tap->scale = ss;
+    tap_end(c, "encoder.conv_in", cur, B, h, w);        // (its input is the caller's image)
     for (int i = 0; i < nb; ++i) {
         for (int j = 0; j < cfg.layers_per_block; ++j) {
             const Resnet& r = e_down[i][j];
             View nxt(a.alloc_h(M * r.cout), r.cout, r.cout);
+            const std::string tn = SD_VAE_TAP(c, "encoder.down_blocks." + std::to_string(i) + ".resnets." + std::to_string(j));
+            tap_begin(c, tn, cur, B, h, w, nxt, h, w);
             run_resnet(c, r, cur, B, h, w, nxt, G, kVaeEps, nullptr, 0, xs, &xs, ss);
+            tap_end(c, tn, nxt, B, h, w);
             cur = nxt;
         }
         if (i != nb - 1) {
@@ -304,7 +337,10 @@ int VAE::run_encode(Ctx& c, const half_t* img, half_t* moments, int B, int H, in
             ConvFuse f;
             gn_fuse(f, (long)(h / 2) * (w / 2), C);
             f.bias_scale = ss;                   // (reads the scaled stream)
+            const std::string tn = SD_VAE_TAP(c, "encoder.down_blocks." + std::to_string(i) + ".downsamplers.0");
+            tap_begin(c, tn, cur, B, h, w, nxt, h / 2, w / 2);
             op_conv(c, e_ds[i], cur, B, h, w, nxt, 2, 0, nullptr, 0, nullptr, 0, /*pad=*/0, 0, &f);
+            tap_end(c, tn, nxt, B, h / 2, w / 2);
             xs = f.gn_out;
             h /= 2; w /= 2; M /= 4;
             cur = nxt;
@@ -312,9 +348,16 @@ int VAE::run_encode(Ctx& c, const half_t* img, half_t* moments, int B, int H, in
     }
     const int top = boc[nb - 1];
     View t0(a.alloc_h(M * top), top, top), t1(a.alloc_h(M * top), top, top);
+    tap_begin(c, "encoder.mid_block.resnets.0", cur, B, h, w, t0, h, w);
     run_resnet(c, e_mid0, cur, B, h, w, t0, G, kVaeEps, nullptr, 0, xs, &xs, ss);
+    tap_end(c, "encoder.mid_block.resnets.0", t0, B, h, w);
+    tap_begin(c, "encoder.mid_block.attentions.0", t0, B, h, w, t1, h, w);
     run_attn(c, e_attn, t0, B, h, w, t1, xs, &xs, ss);
+    tap_end(c, "encoder.mid_block.attentions.0", t1, B, h, w);
+    tap_begin(c, "encoder.mid_block.resnets.1", t1, B, h, w, t0, h, w);
     run_resnet(c, e_mid1, t1, B, h, w, t0, G, kVaeEps, nullptr, 0, xs, &xs, ss);
+    tap_end(c, "encoder.mid_block.resnets.1", t0, B, h, w);
+    if (c.tap) ctx_tap(c, "encoder.tail", kTapIn, t0, B, h, w);             // (its output is the caller's moments)
     op_groupnorm(c, e_norm_out, t0, t1, B, (long)h * w, G, kVaeEps * ss * ss, 1, xs);
     View o(a.alloc_h(M * lc2), lc2, lc2);
     op_conv(c, e_conv_out, t1, B, h, w, o);
@@ -328,7 +371,11 @@ int VAE::decode(const half_t* z, half_t* img, int B, int h, int w, hipStream_t s
     if (!finalized) { set_error("vae: decode before finalize"); return 2; }
     if (B <= 0 || h <= 0 || w <= 0) { set_error("vae: bad shape"); return 1; }
     const long key = ((long)B << 40) ^ ((long)h << 20) ^ (long)w;
-    return plan_and_run(arena, stream, planned_key, key, "vae", [&](Ctx& c) { return run_decode(c, z, img, B, h, w); });
+    if (taps.on) { taps.clear(); taps.scale = 1.f; }
+    return plan_and_run(arena, stream, planned_key, key, "vae", [&](Ctx& c) {
+        c.tap = taps.on ? &taps : nullptr;
+        return run_decode(c, z, img, B, h, w);
+    });
 }
 
 int VAE::encode(const half_t* img, half_t* moments, int B, int H, int W, hipStream_t stream) {
@@ -336,8 +383,11 @@ int VAE::encode(const half_t* img, half_t* moments, int B, int H, int W, hipStre
     const int div = 1 << (cfg.num_blocks - 1);
     if (B <= 0 || H % div != 0 || W % div != 0) { set_error("vae: H and W must be divisible by 2^(blocks-1)"); return 1; }
     const long key = (((long)B << 40) ^ ((long)H << 20) ^ (long)W) | (1L << 62);
-    return plan_and_run(arena, stream, planned_key, key, "vae",
-                        [&](Ctx& c) { return run_encode(c, img, moments, B, H, W, ldexpf(1.f, -encode_shift)); });
+    if (taps.on) { taps.clear(); taps.scale = 1.f; }
+    return plan_and_run(arena, stream, planned_key, key, "vae", [&](Ctx& c) {
+        c.tap = taps.on ? &taps : nullptr;
+        return run_encode(c, img, moments, B, H, W, ldexpf(1.f, -encode_shift));
+    });
 }
 
 }  // namespace sd

@@ -32,6 +32,34 @@ def _stream_ptr() -> int:
     return torch.cuda.current_stream().cuda_stream
 
 
+def _read_taps(lib, handle, model: str) -> Dict[str, dict]:
+    """The debug-tap records of a handle's last forward (sd_engine.h: sd_unet_tap / sd_vae_tap), by block name:
+    {"in", "out": the views as NCHW tensors (fp32 [rows, cols] for the time embedding), "in_rows", "out_rows",
+    "pre_rows": the whole NHWC rows [N, H, W, ld] the view was copied with (only where it is narrower than its row),
+    "out_c0": the view's first column in them, "scale": the factor the stored activations carry}."""
+    count = getattr(lib, f"sd_{model}_tap_count")
+    info_fn, read = getattr(lib, f"sd_{model}_tap_info"), getattr(lib, f"sd_{model}_tap_read")
+    kinds = {_lib.SD_TAP_IN: "in", _lib.SD_TAP_OUT: "out", _lib.SD_TAP_PRE: "pre"}
+    taps: Dict[str, dict] = {}
+    for i in range(count(handle)):
+        info = _lib.SdTapInfo()
+        _lib.check(info_fn(handle, i, C.byref(info)), f"sd_{model}_tap_info")
+        f32 = info.dtype == _lib.SD_DTYPE_F32
+        rows = torch.empty((info.N, info.H, info.W, info.ld), dtype=torch.float32 if f32 else torch.float16)
+        _lib.check(read(handle, i, C.c_void_p(rows.data_ptr()), rows.numel() * rows.element_size()), f"sd_{model}_tap_read")
+        rec = taps.setdefault(info.name.decode(), {"scale": float(info.scale)})
+        kind = kinds[info.kind]
+        if f32:
+            rec[kind] = rows.reshape(info.N, info.ld)
+            continue
+        if kind != "pre":
+            rec[kind] = rows[..., info.c0:info.c0 + info.C].permute(0, 3, 1, 2).contiguous()
+        if info.ld != info.C:
+            rec[kind + "_rows"] = rows
+            rec[kind + "_c0"] = info.c0
+    return taps
+
+
 def _as_f16(x: torch.Tensor, device) -> torch.Tensor:
     return x.to(device=device, dtype=torch.float16).contiguous()
 
@@ -446,6 +474,20 @@ class HipUNet2DConditionModel:
 
     forward = __call__
 
+    def forward_tapped(self, *args, **kwargs):
+        """One plain forward (the arguments of __call__) with the engine's debug taps on: (out, taps), `taps` as
+        _read_taps returns them with the sample as conv_in's input and the output as the tail's."""
+        _lib.check(self._lib.sd_unet_tap(self._h, 1), "sd_unet_tap")
+        try:
+            out = self(*args, **kwargs)[0]
+            taps = _read_taps(self._lib, self._h, "unet")
+        finally:
+            _lib.check(self._lib.sd_unet_tap(self._h, 0), "sd_unet_tap")
+        sample = args[0] if args else kwargs["sample"]
+        taps["conv_in"]["in"] = sample.detach().to("cpu", torch.float16)
+        taps["tail"]["out"] = out.cpu()
+        return out, taps
+
     @property
     def cfg_share_eligible(self) -> bool:
         """Whether this topology lets forward_cfg run the CFG-shared start of the UNet once per latent."""
@@ -780,6 +822,25 @@ class HipAutoencoderKL:
 
     def encode(self, x, return_dict=True):
         return SimpleNamespace(latent_dist=_LatentDist(self.encode_moments(x)))
+
+    def _tapped(self, fn, x, first: str, last: str):
+        _lib.check(self._lib.sd_vae_tap(self._h, 1), "sd_vae_tap")
+        try:
+            out = fn(x)
+            taps = _read_taps(self._lib, self._h, "vae")
+        finally:
+            _lib.check(self._lib.sd_vae_tap(self._h, 0), "sd_vae_tap")
+        taps[first]["in"] = x.detach().to("cpu", torch.float16)
+        taps[last]["out"] = out.cpu()
+        return out, taps
+
+    def decode_tapped(self, z):
+        """decode(z) with the engine's debug taps on: (img, taps), `taps` as _read_taps returns them."""
+        return self._tapped(lambda t: self.decode(t)[0], z, "decoder.conv_in", "decoder.tail")
+
+    def encode_tapped(self, x):
+        """One sd_vae_encode at the range shift in effect, with the debug taps on: (moments, taps)."""
+        return self._tapped(self.encode_moments, x, "encoder.conv_in", "encoder.tail")
 
     def __del__(self):
         try:
