@@ -147,13 +147,22 @@ int sd_unet_forward(sd_unet* u, const void* sample, const float* timesteps, cons
                     int B, int H, int W, void* stream);
 /* Replay the whole forward from a captured hipGraph (one per input shape; inputs / output staged
  * through engine-owned buffers, fenced against `stream` with events).  Host cost per forward drops
- * from ~480 kernel launches to one hipGraphLaunch; results are bitwise those of the eager path. */
+ * from ~480 kernel launches to one hipGraphLaunch; results are bitwise those of the eager path.
+ * A handle holds one graph.  A call captures -- runs eagerly on the staged copies, then records -- when there is no
+ * graph, when (B, H, W, ehs_len, timestep_cond present) differ from the captured call's, or when the workspace or the
+ * staging buffer the graph's addresses point into has been reallocated since (a larger forward run with replay off or
+ * under sd_prof_enable); every other call replays.  Going back to an earlier shape captures again. */
 int sd_unet_use_graph(sd_unet* u, int enable);
+/* Captures and replays (see sd_unet_use_graph) of this handle since its creation; either pointer may be NULL.  Calls
+ * that do not reach the graph path (replay off, a refused call, a forward under sd_prof_enable) count as neither. */
+int sd_unet_graph_stats(const sd_unet* u, int64_t* captures, int64_t* replays);
 /* Text K/V reuse across the forwards of ONE denoise loop (sd_unified_pipeline.py:465-507 passes the same
  * prompt_embeds to every step): enable = 1 makes the next forward compute the stacked attn2.to_k / to_v
  * projections of encoder_hidden_states and later forwards with the same (pointer, batch, length) reuse
  * them.  Every call of this function -- with 1 or 0 -- invalidates what is cached: call it (again) whenever
- * the CONTENTS behind the pointer may have changed, i.e. at the start of each pipeline call.  Off by default. */
+ * the CONTENTS behind the pointer may have changed, i.e. at the start of each pipeline call.  Off by default.
+ * Under graph replay (sd_unet_use_graph) nothing is cached, in a replay or in a capturing call: the forward reads staged
+ * copies, whose address says nothing about the caller's tensor, so every call projects its own encoder_hidden_states. */
 int sd_unet_text_kv_cache(sd_unet* u, int enable);
 /* sd_unet_forward with IP-Adapter image prompts (sd_unified_pipeline.py:441-449, diffusers 0.27.2
  * added_cond_kwargs["image_embeds"]):

@@ -153,6 +153,7 @@ SIGNATURES = {
     "sd_unet_finalize": (_I, [_P]),
     "sd_unet_forward": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _P]),
     "sd_unet_use_graph": (_I, [_P, _I]),
+    "sd_unet_graph_stats": (_I, [_P, C.POINTER(_I64), C.POINTER(_I64)]),
     "sd_unet_text_kv_cache": (_I, [_P, _I]),
     "sd_unet_memory": (_I, [_P, C.POINTER(_I64), C.POINTER(_I64)]),
     "sd_unet_forward_ex": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _I, _P, _I, _I, _I, _P]),

@@ -203,6 +203,12 @@ int sd_unet_use_graph(sd_unet* u, int enable) {
     u->impl.graph_enabled = enable != 0;
     return SD_OK;
 }
+int sd_unet_graph_stats(const sd_unet* u, int64_t* captures, int64_t* replays) {
+    if (!u) { set_error("null handle"); return SD_ERR_INVALID; }
+    if (captures) *captures = u->impl.graph_captures;
+    if (replays) *replays = u->impl.graph_replays;
+    return SD_OK;
+}
 int sd_unet_text_kv_cache(sd_unet* u, int enable) {
     if (!u) { set_error("null handle"); return SD_ERR_INVALID; }
     u->impl.kv_cache_on = enable != 0;

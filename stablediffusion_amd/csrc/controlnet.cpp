@@ -153,7 +153,7 @@ int UNet::run_controlnet(Ctx& c, const UNetCall& call, const std::vector<View>& 
     // ---- conditioning embedding [B H W, C0]: n_ctrl images computed once, sample b reads image b mod n_ctrl (diffusers'
     //      cat([image] * 2) under CFG); kept across the loop like the text K / V.  The planning pass always takes the
     //      computing branch (see the IP-Adapter's K / V). ----
-    const bool cached = kv_cache_on && !graph_enabled && cond_cache.h() != nullptr;
+    const bool cached = ptr_caches_live() && cond_cache.h() != nullptr;
     half_t* cond = cached ? cond_cache.h() : a.alloc_h((long)B * HWC);
     const bool hit = cached && cond_tag.matches(control, B, n_ctrl, H, W);
     if (c.dry || !hit) {
@@ -167,7 +167,7 @@ int UNet::run_controlnet(Ctx& c, const UNetCall& call, const std::vector<View>& 
     }
     // ---- the ControlNet's own text K / V ----
     const int ctx = cfg.cross_attention_dim;
-    const bool kc = kv_cache_on && !graph_enabled && cnkv_cache.h() != nullptr;
+    const bool kc = ptr_caches_live() && cnkv_cache.h() != nullptr;
     View kv(kc ? cnkv_cache.h() : a.alloc_h((long)B * L * cn->kv_total), cn->kv_total, cn->kv_total);
     const bool khit = kc && cnkv_tag.matches(ehs, B, L);
     if (c.dry || !khit) {

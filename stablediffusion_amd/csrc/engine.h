@@ -37,6 +37,7 @@ class Arena {
     void release(size_t m) { off_ = m; }
     size_t peak() const { return peak_; }
     size_t capacity() const { return cap_; }
+    const char* base() const { return base_; }      // (with capacity(): what a captured graph's addresses depend on)
     bool dry() const { return dry_; }
     bool overflow() const { return overflow_; }
 

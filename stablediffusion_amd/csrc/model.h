@@ -277,6 +277,24 @@ struct GraphKey {
     bool tcond = false;
     bool operator==(const GraphKey& o) const { return B == o.B && H == o.H && W == o.W && L == o.L && tcond == o.tcond; }
 };
+// The device addresses a captured graph has baked in: every activation lies in the arena's slab, every input and the
+// output in the staging slab.  Either slab is freed when it grows (Arena::reserve, DeviceBuf::reserve), and the arena
+// grows under any larger forward the handle runs eagerly in between (graph replay switched off and on again, the
+// profiler on, an adapter or a ControlNet attached), so the key alone does not say that a graph may run.
+struct GraphDeps {
+    const void* arena_base = nullptr;
+    size_t arena_cap = 0;
+    const void* io_base = nullptr;
+    bool operator==(const GraphDeps& o) const {
+        return arena_base == o.arena_base && arena_cap == o.arena_cap && io_base == o.io_base;
+    }
+};
+// May the captured graph be launched for this call?  Only when there is one, it was captured for this key, and both
+// slabs are where (and as large as) they were at the capture; otherwise forward_graph captures again.
+inline bool graph_may_replay(const GraphKey& key, const GraphDeps& now, const GraphKey& captured_key,
+                             const GraphDeps& captured, bool have_exec) {
+    return have_exec && key == captured_key && now == captured;
+}
 
 struct UNet : Encoder {
     explicit UNet(const sd_unet_config& c);
@@ -317,12 +335,19 @@ struct UNet : Encoder {
     // the captured pointers stay valid whatever tensors the caller passes.  The ~480 launches of a
     // forward then cost the host one hipGraphLaunch (CPU time per step 2 ms -> ~0.02 ms); GPU time is
     // unchanged (kernel boundaries cost the same under a graph, MI355X_MICROARCH.md price list).
+    // The handle holds one graph; graph_may_replay says per call whether it is launched or captured anew.
     bool graph_enabled = false;
     hipStream_t gstream = nullptr;
     hipEvent_t ev_in = nullptr, ev_out = nullptr;
     hipGraphExec_t gexec = nullptr;
     GraphKey graph_key;
+    GraphDeps graph_deps;               // (of the capture gexec came from: graph_may_replay)
     DeviceBuf io_slab;
+    // forward_graph's eager pass runs with graph_enabled off; this says it is one.  The pointer-keyed caches below see
+    // the staging slab's addresses there, which name no caller tensor, so they neither read nor fill under it.
+    bool graph_pass = false;
+    bool ptr_caches_live() const { return kv_cache_on && !graph_enabled && !graph_pass; }
+    int64_t graph_captures = 0, graph_replays = 0;      // since creation (sd_unet_graph_stats)
     int forward_graph(const UNetCall& call, hipStream_t stream);
     ~UNet();
 

@@ -1035,7 +1035,7 @@ int UNet::run(Ctx& c, const UNetCall& call, int dc) {
     // ---- text K/V of every cross-attention block in one GEMM: [B*L, ctx] x [ctx, sum 2C] ----
     //      (forward_pag: projected for the Nq rows of ehs; the perturbed group gets a copy of the text group's rows, which
     //      the cache keeps with the rest.  That copy, and up front the group's tproj rows, are one row_dup launch here.)
-    const bool kv_cached = kv_cache_on && !graph_enabled && kv_cache.h() != nullptr;
+    const bool kv_cached = ptr_caches_live() && kv_cache.h() != nullptr;
     View text_kv(kv_cached ? kv_cache.h() : a.alloc_h((long)B * L * kv_total), kv_total, kv_total);
     std::vector<RowDupSeg> pag_now;
     if (!(kv_cached && kv_tag.matches(ehs, B, L, Ng))) {
@@ -1068,7 +1068,7 @@ int UNet::run(Ctx& c, const UNetCall& call, int dc) {
     if (ip && image_embeds) {
         const int ctx = cfg.cross_attention_dim, T_ip = n_img * ip->n_tok;
         const long rows = (long)B * n_img, ntc = (long)ip->n_tok * ctx;
-        const bool ip_cached = kv_cache_on && !graph_enabled && ipkv_cache.h() != nullptr;
+        const bool ip_cached = ptr_caches_live() && ipkv_cache.h() != nullptr;
         View ip_kv(ip_cached ? ipkv_cache.h() : a.alloc_h((long)B * T_ip * ip->kv_total), ip->kv_total, ip->kv_total);
         // the planning pass always takes the computing branch: its temporaries live between mark and release, so the
         // live pass skipping them (cache hit) allocates less and every later tensor keeps its planned address
@@ -1453,11 +1453,15 @@ int UNet::forward_graph(const UNetCall& call, hipStream_t stream) {
     staged.add_text = g_text; staged.add_time_ids = g_ids; staged.out = g_out;
     staged.B = B; staged.H = H; staged.W = W; staged.tcond = g_tc;
     int rc = 0;
-    if (!(key == graph_key) || !gexec) {
+    const GraphDeps now{arena.base(), arena.capacity(), io_slab.data()};
+    if (!graph_may_replay(key, now, graph_key, graph_deps, gexec != nullptr)) {
         // (re)plan + one eager run on the caller's stream: sets every kernel's LDS attribute (not
-        // allowed while capturing) and produces this call's result
+        // allowed while capturing) and produces this call's result.  It reads the staged copies, so it stays clear of
+        // the pointer-keyed caches (graph_pass), like the captured pass after it.
         graph_enabled = false;
+        graph_pass = true;
         rc = forward(staged, stream);
+        graph_pass = false;
         graph_enabled = true;
         if (rc) return rc;
         if (gexec) { (void)hipGraphExecDestroy(gexec); gexec = nullptr; }
@@ -1469,14 +1473,18 @@ int UNet::forward_graph(const UNetCall& call, hipStream_t stream) {
         hipError_t e = hipStreamEndCapture(gstream, &graph);
         if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
         if (e != hipSuccess) { set_error(std::string("hipStreamEndCapture: ") + hipGetErrorString(e)); return 3; }
+        if (arena.overflow()) { (void)hipGraphDestroy(graph); set_error("unet: workspace overflow while capturing (planner bug)"); return 2; }
         e = hipGraphInstantiate(&gexec, graph, nullptr, nullptr, 0);
         (void)hipGraphDestroy(graph);
         if (e != hipSuccess) { gexec = nullptr; set_error(std::string("hipGraphInstantiate: ") + hipGetErrorString(e)); return 3; }
         graph_key = key;
+        graph_deps = GraphDeps{arena.base(), arena.capacity(), io_slab.data()};     // (the eager pass may have grown the arena)
+        ++graph_captures;
     } else {
         SD_HIP_CHECK(hipEventRecord(ev_in, stream));
         SD_HIP_CHECK(hipStreamWaitEvent(gstream, ev_in, 0));
         SD_HIP_CHECK(hipGraphLaunch(gexec, gstream));
+        ++graph_replays;
         SD_HIP_CHECK(hipEventRecord(ev_out, gstream));
         SD_HIP_CHECK(hipStreamWaitEvent(stream, ev_out, 0));
     }
@@ -1551,7 +1559,9 @@ int UNet::forward(const UNetCall& in, hipStream_t stream) {
         if (dc == SD_DC_STORE) dc_tag.clear();       // (until this forward has run)
     }
     if (graph_enabled && !prof_enabled()) return forward_graph(call, stream);
-    if (kv_cache_on) {          // persistent buffers for the text K/V and its like (outside the per-forward arena)
+    // persistent buffers for the text K/V and its like (outside the per-forward arena; not in forward_graph's eager pass)
+    const bool caches = kv_cache_on && !graph_pass;
+    if (caches) {
         if (int rc = reserve_cache(kv_cache, (size_t)B * L * kv_total * sizeof(half_t), kv_tag)) return rc;
         if (ip && !text_only)
             if (int rc = reserve_cache(ipkv_cache, (size_t)B * call.n_img * ip->n_tok * ip->kv_total * sizeof(half_t), ipkv_tag)) return rc;
@@ -1564,7 +1574,7 @@ int UNet::forward(const UNetCall& in, hipStream_t stream) {
     // they reset the plans
     PlanKey key;
     key.B = B; key.H = H; key.W = W; key.L = L;
-    key.kv_cache = kv_cache_on;
+    key.kv_cache = caches;
     key.ip_tokens = ip ? call.n_img * ip->n_tok : 0;
     key.cfg_share = cfg_in != nullptr;
     if (pag) { key.pag_groups = pag->groups; key.pag_late = pag->late; }

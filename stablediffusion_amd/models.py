@@ -196,6 +196,12 @@ class HipUNet2DConditionModel:
         self._graph_on = bool(enable)          # (carried over to the engine a LoRA re-fuse builds)
         return self
 
+    def graph_stats(self):
+        """(captures, replays) of `use_graph` on this engine since it was created (sd_unet_graph_stats)."""
+        c, r = C.c_int64(), C.c_int64()
+        _lib.check(self._lib.sd_unet_graph_stats(self._h, C.byref(c), C.byref(r)), "sd_unet_graph_stats")
+        return c.value, r.value
+
     def text_kv_cache(self, enable: bool = True):
         """Reuse the cross-attention K/V projections of `encoder_hidden_states` across the forwards of one
         denoise loop (same tensor every step).  Each call invalidates the cache; the pipeline calls it with

@@ -1,5 +1,5 @@
 // Host-only check of the engine's bookkeeping types, built with -fsanitize=address,undefined by test_host_pieces.py:
-// PlanKey / GraphKey equality, CacheTag, and DeviceBuf with its three device calls swapped for malloc / free
+// PlanKey / GraphKey equality, the graph replay decision (graph_may_replay), CacheTag, and DeviceBuf with its three device calls swapped for malloc / free
 // (SD_DEVICEBUF_HOST_ALLOC).  No GPU, no HIP call; a leak or an out-of-bounds write fails the run through the sanitizer.
 #include <cstdio>
 #include <cstring>
@@ -61,6 +61,49 @@ static void plan_keys() {
     CHECK(!(g == h));
 }
 
+// graph_may_replay: the one place that says whether UNet::forward_graph launches its captured graph or captures again
+static void graph_replay_decision() {
+    char arena_a[64], arena_b[64], io_a[16], io_b[16];      // stand-ins for the slabs: only their addresses are used
+    GraphKey k;
+    k.B = 2; k.H = 8; k.W = 8; k.L = 77;
+    const GraphDeps d{arena_a, 4096, io_a};
+    // same key, nothing moved: replay
+    CHECK(graph_may_replay(k, d, k, d, true));
+    // every key field, one at a time: capture
+    GraphKey o;
+    o = k; o.B = 1; CHECK(!graph_may_replay(o, d, k, d, true));
+    o = k; o.H = 16; CHECK(!graph_may_replay(o, d, k, d, true));
+    o = k; o.W = 16; CHECK(!graph_may_replay(o, d, k, d, true));
+    o = k; o.L = 32; CHECK(!graph_may_replay(o, d, k, d, true));
+    o = k; o.tcond = true; CHECK(!graph_may_replay(o, d, k, d, true));
+    // (H and W swapped is another key)
+    GraphKey hw = k, wh = k;
+    hw.H = 24; hw.W = 16; wh.H = 16; wh.W = 24;
+    CHECK(!graph_may_replay(hw, d, wh, d, true) && graph_may_replay(hw, d, hw, d, true));
+    // arena regrown with the same key: another slab, or -- the allocator handing the old address out again -- the same
+    // address with another capacity
+    GraphDeps n = d;
+    n.arena_base = arena_b; n.arena_cap = 8192; CHECK(!graph_may_replay(k, n, k, d, true));
+    n = d; n.arena_cap = 8192; CHECK(!graph_may_replay(k, n, k, d, true));
+    n = d; n.arena_base = arena_b; CHECK(!graph_may_replay(k, n, k, d, true));
+    // staging slab regrown
+    n = d; n.io_base = io_b; CHECK(!graph_may_replay(k, n, k, d, true));
+    // no executable (never captured, or the last capture failed), whatever else agrees
+    CHECK(!graph_may_replay(k, d, k, d, false));
+    CHECK(!graph_may_replay(GraphKey(), GraphDeps(), GraphKey(), GraphDeps(), false));
+    // what forward_graph does after a capture -- remember the key and the slabs as they are then -- makes the next
+    // call with that key a replay, and the one after a regrowth a capture
+    GraphKey captured_key;
+    GraphDeps captured;
+    bool have = false;
+    CHECK(!graph_may_replay(k, d, captured_key, captured, have));
+    captured_key = k; captured = GraphDeps{arena_b, 8192, io_a}; have = true;   // (the capturing call grew the arena itself)
+    const GraphDeps after{arena_b, 8192, io_a};
+    CHECK(graph_may_replay(k, after, captured_key, captured, have));
+    const GraphDeps regrown{arena_a, 16384, io_a};
+    CHECK(!graph_may_replay(k, regrown, captured_key, captured, have));
+}
+
 static void cache_tags() {
     int x = 0, y = 0;
     CacheTag t;
@@ -102,6 +145,7 @@ static void device_bufs() {
 
 int main() {
     plan_keys();
+    graph_replay_decision();
     cache_tags();
     device_bufs();
     if (failures) std::printf("host pieces: %d check(s) failed\n", failures);

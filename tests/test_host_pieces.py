@@ -1,4 +1,4 @@
-"""The engine's host-side bookkeeping types (PlanKey, GraphKey, CacheTag, DeviceBuf) under AddressSanitizer and
+"""The engine's host-side bookkeeping (PlanKey, GraphKey, graph_may_replay, CacheTag, DeviceBuf) under AddressSanitizer and
 UndefinedBehaviorSanitizer: tests/host_pieces.cpp is compiled as a stand-alone host program, with DeviceBuf's device
 calls swapped for malloc / free, and run.  No GPU and nothing loaded into this process."""
 import os

@@ -501,3 +501,5 @@ def test_unet_hipgraph_replay_is_bitwise_eager(engine_lib):
         a = eager(x, t, ehs)[0]
         b = graph(x.clone(), t.clone(), ehs.clone())[0]
         assert torch.equal(a, b), (B, H, W)
+    # the first call, the shape change and the way back capture (one graph per handle); the other two replay
+    assert graph.graph_stats() == (3, 2) and eager.graph_stats() == (0, 0)
