@@ -604,6 +604,39 @@ int sd_sched_affine_step(const void* model_out, int rows, void* latents, const v
 int sd_inpaint_blend(void* latents, const void* image_latents, const void* noise, const void* mask,
                      float a, float b, int B, int C, int H, int W, void* stream);
 
+/* -- MultiDiffusion (Bar-Tal et al. 2023; diffusers' StableDiffusionPanoramaPipeline): a large latent canvas is denoised
+ * as overlapping [h, w] windows ("views") whose model outputs are averaged where they overlap.  View v = iy * nx + ix
+ * sits at (ys[iy], xs[ix]); with wrap_x its columns are taken modulo Wc (a 360-degree panorama).  At most 64 starts per
+ * axis; they travel in the launch parameters, so ys / xs are HOST arrays.
+ *
+ * sd_view_plan: the starts of one axis of length L for windows of `win` at `stride`: 0, stride, 2 stride, .. <= L - win,
+ * and a final L - win when the last one is not already there, so every position is covered; L <= win gives the single
+ * start 0 (the caller's window is then L).  With wrap: 0, stride, .. < L, and win <= L is required.  A stride above win
+ * counts as win (the windows abut), so no position is ever left out.  Needs no device.
+ * Returns the count (written to starts[0 .. count)), or -SD_ERR_INVALID: non-positive L / win / stride / cap, a null
+ * starts, win > L on a wrapped axis, more than 64 starts, cap below the count.
+ *
+ * sd_views_gather: windows[v * B + b, c, y, x] = canvas[b, c, ys[iy] + y, (xs[ix] + x) mod Wc], a pure f16 copy of
+ * canvas [B, C, Hc, Wc] into windows [ny * nx * B, C, h, w].
+ *
+ * sd_views_merge: eps_out[g * B + b, c, Y, X] = f16(sum_v wt(Y - ys, X - xs) out_{g,v,b}[c, Y - ys, X - xs] / sum_v wt(..))
+ * over the views that cover (Y, X), taken in ascending v, fp32 sums, one rounding; no atomics, so the result is
+ * deterministic.  window_weights: a DEVICE [h, w] fp32 profile, or NULL for all ones.  Its values must be finite and
+ * positive: they live on the device, so this is not checked, and a sum that is zero or not finite gives inf / nan there.
+ * model_out holds the UNet outputs of chunks of views_per_chunk views (the last may be smaller), each [G, size, B, C, h, w]:
+ * the row of (g, v, b) is (v / vpc) vpc G B + (g size + v % vpc) B + b.  eps_out is [G * B, C, Hc, Wc]: what a forward of
+ * the whole canvas would return to the step entries above.
+ *
+ * Both: SD_ERR_INVALID with nothing launched for a null pointer, a non-positive size, ny or nx outside 1..64, h > Hc or
+ * w > Wc, a start outside the canvas (a window that ends outside it, when not wrapped), a pixel that no view covers,
+ * views_per_chunk < 1.  One 16-byte access per 8 halves when w, Wc and every x start are multiples of 8 and the device
+ * pointers are 16-byte aligned; one element per thread otherwise. */
+int sd_view_plan(int L, int win, int stride, int wrap, int* starts, int cap);
+int sd_views_gather(const void* canvas, void* windows, int B, int C, int Hc, int Wc, int h, int w, const int* ys, int ny,
+                    const int* xs, int nx, int wrap_x, void* stream);
+int sd_views_merge(const void* model_out, void* eps_out, const float* window_weights, int G, int B, int C, int Hc, int Wc,
+                   int h, int w, const int* ys, int ny, const int* xs, int nx, int wrap_x, int views_per_chunk, void* stream);
+
 /* convert_pt_to_numpy (runpod-worker/handler_logic.py:21-29): decoded images [B,C,H,W] f16 in [-1,1] ->
  * [B,H,W,C] uint8, with the reference's fp16 roundings and truncating cast (bit-exact with running
  * the reference's op sequence on the same fp16 tensor).  C <= 4. */

@@ -225,6 +225,9 @@ SIGNATURES = {
     "sd_cfg_duplicate": (_I, [_P, _P, _I64, _I, _F, _P]),
     "sd_inpaint_blend": (_I, [_P, _P, _P, _P, _F, _F, _I, _I, _I, _I, _P]),
     "sd_images_to_uint8": (_I, [_P, _P, _I, _I, _I, _I, _P]),
+    "sd_view_plan": (_I, [_I, _I, _I, _I, C.POINTER(_I), _I]),
+    "sd_views_gather": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, C.POINTER(_I), _I, C.POINTER(_I), _I, _I, _P]),
+    "sd_views_merge": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, C.POINTER(_I), _I, C.POINTER(_I), _I, _I, _I, _P]),
     "sd_cfg_linear_step": (_I, [_P, _P, _P, _I64, _F, _F, _F, _F, _F, _F, _P]),
     "sd_pag_linear_step": (_I, [_P, _I, _P, _P, _I64, _F, _F, _F, _F, _F, _F, _F, _P]),
     "sd_pag_combine": (_I, [_P, _I, _P, _I64, _F, _F, _P]),

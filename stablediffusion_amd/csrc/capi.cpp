@@ -804,6 +804,78 @@ int sd_inpaint_blend(void* latents, const void* image_latents, const void* noise
                                 (long)H * W, static_cast<hipStream_t>(stream));
 }
 
+// ------------------------------------------------------------------------------------- MultiDiffusion views
+int sd_view_plan(int L, int win, int stride, int wrap, int* starts, int cap) {
+    if (L < 1 || win < 1 || stride < 1 || !starts || cap < 1) {
+        set_error("sd_view_plan: bad arguments (L, win, stride, cap >= 1, non-null starts)");
+        return -SD_ERR_INVALID;
+    }
+    if (wrap && win > L) { set_error("sd_view_plan: a wrapped axis needs win <= L"); return -SD_ERR_INVALID; }
+    if (stride > win) stride = win;                  // (a larger stride would leave gaps: the windows abut instead)
+    long count;                                      // every start is a multiple of the stride, but for a final L - win
+    bool tail = false;
+    if (wrap) count = ((long)L + stride - 1) / stride;
+    else if (L <= win) count = 1;
+    else {
+        count = (long)(L - win) / stride + 1;
+        tail = (L - win) % stride != 0;
+        count += tail;
+    }
+    if (count > VIEW_MAX_STARTS) { set_error("sd_view_plan: more than 64 starts on one axis"); return -SD_ERR_INVALID; }
+    if (count > cap) { set_error("sd_view_plan: `starts` is too small"); return -SD_ERR_INVALID; }
+    for (int i = 0; i < (int)count; ++i) starts[i] = i * stride;
+    if (tail) starts[count - 1] = L - win;
+    return (int)count;
+}
+
+namespace {
+// The starts of one axis into `dst`, checked: 1..64 of them, each window inside the axis (or, wrapped, starting inside it),
+// every position covered.
+const char* check_view_axis(const int* starts, int n, int win, int L, bool wrap, int* dst) {
+    if (n < 1 || n > VIEW_MAX_STARTS) return "1..64 starts per axis";
+    if (win < 1 || win > L) return "a window must fit the canvas (1 <= h <= Hc, 1 <= w <= Wc)";
+    std::vector<char> covered((size_t)L, 0);
+    for (int i = 0; i < n; ++i) {
+        const int s = starts[i];
+        if (s < 0 || s >= L || (!wrap && s > L - win)) return "a start outside the canvas";
+        for (int k = 0; k < win; ++k) covered[(size_t)((s + k) % L)] = 1;
+        dst[i] = s;
+    }
+    for (int p = 0; p < L; ++p)
+        if (!covered[(size_t)p]) return "a pixel that no view covers";
+    return nullptr;
+}
+}  // namespace
+
+int sd_views_gather(const void* canvas, void* windows, int B, int C, int Hc, int Wc, int h, int w, const int* ys, int ny,
+                    const int* xs, int nx, int wrap_x, void* stream) {
+    if (!canvas || !windows || !ys || !xs || B < 1 || C < 1 || Hc < 1 || Wc < 1) {
+        set_error("sd_views_gather: bad arguments (non-null canvas / windows / ys / xs, positive sizes)");
+        return SD_ERR_INVALID;
+    }
+    ViewStarts st = {};
+    const char* why = check_view_axis(ys, ny, h, Hc, false, st.ys);
+    if (!why) why = check_view_axis(xs, nx, w, Wc, wrap_x != 0, st.xs);
+    if (why) { set_error(std::string("sd_views_gather: ") + why); return SD_ERR_INVALID; }
+    return launch_views_gather(static_cast<const half_t*>(canvas), static_cast<half_t*>(windows), B, C, Hc, Wc, h, w, st, ny,
+                               nx, wrap_x != 0, static_cast<hipStream_t>(stream));
+}
+
+int sd_views_merge(const void* model_out, void* eps_out, const float* window_weights, int G, int B, int C, int Hc, int Wc,
+                   int h, int w, const int* ys, int ny, const int* xs, int nx, int wrap_x, int views_per_chunk, void* stream) {
+    if (!model_out || !eps_out || !ys || !xs || G < 1 || B < 1 || C < 1 || Hc < 1 || Wc < 1 || views_per_chunk < 1) {
+        set_error("sd_views_merge: bad arguments (non-null model_out / eps_out / ys / xs, positive sizes, "
+                  "views_per_chunk >= 1)");
+        return SD_ERR_INVALID;
+    }
+    ViewStarts st = {};
+    const char* why = check_view_axis(ys, ny, h, Hc, false, st.ys);
+    if (!why) why = check_view_axis(xs, nx, w, Wc, wrap_x != 0, st.xs);
+    if (why) { set_error(std::string("sd_views_merge: ") + why); return SD_ERR_INVALID; }
+    return launch_views_merge(static_cast<const half_t*>(model_out), static_cast<half_t*>(eps_out), window_weights, G, B, C,
+                              Hc, Wc, h, w, st, ny, nx, wrap_x != 0, views_per_chunk, static_cast<hipStream_t>(stream));
+}
+
 // ------------------------------------------------------------------------------------------- probe
 int sd_probe_mfma(int iters, float* tflops, void* stream) {
     if (iters < 1 || !tflops) { set_error("sd_probe_mfma: bad arguments"); return SD_ERR_INVALID; }

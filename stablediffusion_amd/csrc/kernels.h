@@ -453,6 +453,22 @@ int launch_pag_combine(const half_t* model_out, int rows, half_t* out, long n, f
 int launch_ip2p_linear(const half_t* model_out, half_t* lat, float* hist, long n, float gt, float gi, float cx, float ce,
                        float ch, float hx, float he, hipStream_t s);
 int launch_ip2p_combine(const half_t* model_out, half_t* out, long n, float gt, float gi, hipStream_t s);
+// MultiDiffusion windows (views.hip).  A view v = iy * nx + ix is the [h, w] window of a [rows, C, Hc, Wc] canvas at
+// (ys[iy], xs[ix]); with wrap_x its columns are taken modulo Wc.  The starts travel by value in the launch parameters.
+constexpr int VIEW_MAX_STARTS = 64;
+struct ViewStarts {
+    int ys[VIEW_MAX_STARTS];
+    int xs[VIEW_MAX_STARTS];
+};
+// windows[v * B + b, c, y, x] = canvas[b, c, ys + y, (xs + x) mod Wc]: a pure fp16 copy.
+int launch_views_gather(const half_t* canvas, half_t* windows, int B, int C, int Hc, int Wc, int h, int w,
+                        const ViewStarts& st, int ny, int nx, int wrap_x, hipStream_t s);
+// eps[g * B + b, c, Y, X] = fp16(sum_v wt * out_{g,v,b} / sum_v wt) over the views that cover (Y, X), in ascending v, fp32
+// sums, one rounding; wt [h, w] fp32 or NULL (all ones).  model_out holds the forwards of chunks of `vpc` views, laid out
+// [chunk][group][view in chunk][b]: the row of (g, v, b) is (v / vpc) vpc G B + (g size + v % vpc) B + b with
+// size = min(vpc, V - (v / vpc) vpc).  Every pixel must be covered by a view (the C entry checks it).
+int launch_views_merge(const half_t* model_out, half_t* eps, const float* wt, int G, int B, int C, int Hc, int Wc, int h,
+                       int w, const ViewStarts& st, int ny, int nx, int wrap_x, int vpc, hipStream_t s);
 // den = dx x + dout m, x <- pden den + pnoise noise (m: model_out, or its CFG combine when rows == 2); noise / denoised
 // nullable.  The scheduler step of LCMScheduler in one launch.
 int launch_lcm_step(const half_t* model_out, int rows, half_t* lat, const half_t* noise, half_t* denoised, long n, float g,

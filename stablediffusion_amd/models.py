@@ -435,7 +435,7 @@ class HipUNet2DConditionModel:
 
     def __call__(self, sample, timestep, encoder_hidden_states, cross_attention_kwargs=None,
                  added_cond_kwargs=None, return_dict=False, controlnet_cond=None, controlnet_conditioning_scale=None,
-                 timestep_cond=None, **unused):
+                 timestep_cond=None, out=None, **unused):
         # diffusers' residual-tensor interface (a ControlNet run outside the engine): not taken -- silently dropping
         # it would return the plain UNet's output.  Attach the ControlNet instead (attach_controlnet).
         for k in ("down_block_additional_residuals", "mid_block_additional_residual", "down_intrablock_additional_residuals",
@@ -457,7 +457,7 @@ class HipUNet2DConditionModel:
             tc = timestep_cond.to(device=dev, dtype=torch.float32).contiguous()
             if tc.ndim != 2 or tc.shape[0] != B:
                 raise ValueError(f"timestep_cond: expected [{B}, time_cond_proj_dim], got {tuple(tc.shape)}")
-        out = torch.empty((B, self.cfg.out_channels, H, W), device=dev, dtype=torch.float16)
+        out = self._out_buffer(out, (B, self.cfg.out_channels, H, W), dev)
         # one argument list; the entry is the narrowest that takes what is present (sd_engine.h)
         head = (self._h, C.c_void_p(sample.data_ptr()), C.c_void_p(t.data_ptr()), C.c_void_p(ehs.data_ptr()), ehs.shape[1],
                 pt, pi)
@@ -500,8 +500,19 @@ class HipUNet2DConditionModel:
         c = _unet_config_struct(self.cfg)
         return bool(self._lib.sd_unet_cfg_share(C.byref(c)))
 
+    @staticmethod
+    def _out_buffer(out, shape, dev):
+        """The forward's output tensor: a fresh one, or the caller's `out=` (fp16, contiguous, on the device, of exactly
+        the output's shape -- e.g. a slice of a larger buffer), which the engine then writes in place."""
+        if out is None:
+            return torch.empty(shape, device=dev, dtype=torch.float16)
+        same_dev = out.device.type == dev.type and (dev.index is None or out.device.index == dev.index)
+        if tuple(out.shape) != tuple(shape) or out.dtype != torch.float16 or not same_dev or not out.is_contiguous():
+            raise ValueError(f"out= must be a contiguous fp16 tensor of shape {tuple(shape)} on {dev}")
+        return out
+
     def forward_cfg(self, latents, timestep, encoder_hidden_states, added_cond_kwargs=None, in_scale: float = 1.0,
-                    share: bool = True):
+                    share: bool = True, out=None):
         """One classifier-free-guidance forward from the UN-duplicated latents [B, C, H, W]: what
         self(torch.cat([fp16(latents * in_scale)] * 2), timestep, encoder_hidden_states) returns ([2B, ...], negative
         half first; encoder_hidden_states and added_cond_kwargs hold 2B rows).  With `share` the engine runs everything
@@ -514,7 +525,7 @@ class HipUNet2DConditionModel:
         dev, latents, ehs, t, pt, pi, _keep = self._prepare(latents, timestep, encoder_hidden_states, added_cond_kwargs, 2)
         B, _, H, W = latents.shape
         img = self._image_embeds(added_cond_kwargs, 2 * B, dev)
-        out = torch.empty((2 * B, self.cfg.out_channels, H, W), device=dev, dtype=torch.float16)
+        out = self._out_buffer(out, (2 * B, self.cfg.out_channels, H, W), dev)
         with torch.cuda.device(dev):
             rc = self._lib.sd_unet_forward_cfg(self._h, C.c_void_p(latents.data_ptr()), C.c_void_p(t.data_ptr()),
                                                C.c_void_p(ehs.data_ptr()), ehs.shape[1], pt, pi,

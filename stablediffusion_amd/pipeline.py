@@ -29,7 +29,7 @@ from typing import Any, Dict, List, Optional, Union
 
 import torch
 
-from . import _lib, pag as _pag, pix2pix as _p2p, schedulers as _sched
+from . import _lib, pag as _pag, pix2pix as _p2p, schedulers as _sched, views as _views
 from .image_processor import VaeImageProcessor
 
 
@@ -524,6 +524,15 @@ class StableDiffusionUnifiedPipeline:
         # InstructPix2Pix (diffusers StableDiffusionInstructPix2PixPipeline): an 8-channel UNet selects the mode, `image`
         # is the picture to edit; None: 1.5 there, and nothing anywhere else
         image_guidance_scale: Optional[float] = None,
+        # MultiDiffusion (diffusers StableDiffusionPanoramaPipeline; stablediffusion_amd.views): the canvas is denoised as
+        # overlapping windows of `view_window` latent pixels (an int or (h, w); None: off) every `view_stride` (default:
+        # half the window), `view_batch_size` windows per UNet forward (default: 4 latents per forward), merged with
+        # `view_blend` weights ("uniform" / "gaussian"); `circular_padding` wraps the x axis
+        view_window=None,
+        view_stride=None,
+        view_batch_size: Optional[int] = None,
+        view_blend: str = "uniform",
+        circular_padding: bool = False,
         # SDXL refiner (diffusers StableDiffusionXLImg2ImgPipeline on model.refiner; the reference's handler TODO)
         use_refiner: bool = False,
         refiner_start: Optional[float] = None,
@@ -533,6 +542,11 @@ class StableDiffusionUnifiedPipeline:
         pag_scale: float = 0.0,
         pag_adaptive_scale: float = 0.0,
     ):
+        views = None
+        if view_window is not None:
+            self._check_views(model, locals())
+            views = dict(window=view_window, stride=view_stride, batch=view_batch_size, blend=view_blend,
+                         circular=bool(circular_padding))
         edit = _p2p.is_edit_unet(getattr(getattr(model, "base", None), "config", None))
         if image_guidance_scale is not None and not edit:
             raise ValueError("image_guidance_scale is InstructPix2Pix's: it needs a UNet with in_channels == 8")
@@ -543,7 +557,7 @@ class StableDiffusionUnifiedPipeline:
         if refiner_start is not None:
             if pag_scale is not None and float(pag_scale) > 0.0:
                 raise NotImplementedError("perturbed-attention guidance (pag_scale > 0) does not address the refiner")
-            call = {k: v for k, v in locals().items() if k not in ("self", "edit")}
+            call = {k: v for k, v in locals().items() if k not in ("self", "edit", "views")}
             return self._ensemble_of_experts(call)
         pag_on = pag_scale is not None and float(pag_scale) > 0.0
         if pag_on:
@@ -624,6 +638,9 @@ class StableDiffusionUnifiedPipeline:
             height, width = ci.shape[-2], ci.shape[-1]
         height = height or unet.config.sample_size * model.vae_scale_factor
         width = width or unet.config.sample_size * model.vae_scale_factor
+        if views is not None:                # a plan that cannot be made is refused here, before anything runs
+            _views.plan_views(height // model.vae_scale_factor, width // model.vae_scale_factor, views["window"],
+                              views["stride"], views["circular"])
 
         if prompt is not None and isinstance(prompt, str):
             batch_size = 1
@@ -782,7 +799,7 @@ class StableDiffusionUnifiedPipeline:
                                 mask=mask, masked_image_latents=masked_image_latents_2b, image_latents=image_latents,
                                 image_noise=noise,
                                 pag=(float(pag_scale), float(pag_adaptive_scale)) if pag_on else None,
-                                edit=(edit_latents, image_guidance_scale) if edit else None)
+                                edit=(edit_latents, image_guidance_scale) if edit else None, views=views)
 
         # ---- decode (:511-529) ----
         if self.output_type == "pt":
@@ -806,12 +823,13 @@ class StableDiffusionUnifiedPipeline:
     def _denoise(self, model, latents, timesteps, prompt_embeds, cross_attention_kwargs, added_cond_kwargs, tc_kwargs,
                  guidance_scale, guidance_rescale, seed, control=None, controlnet_conditioning_scale=1.0,
                  control_guidance_start=0.0, control_guidance_end=1.0, mask=None, masked_image_latents=None,
-                 image_latents=None, image_noise=None, pag=None, edit=None):
+                 image_latents=None, image_noise=None, pag=None, edit=None, views=None):
         """The denoising loop (:465-507): `timesteps` over `latents`, the scheduler's update on the device where
         `_device_step_kind` finds one (`_device_iteration`) and in `scheduler.step` otherwise.  `tc_kwargs` is the
         guidance-embedded UNet's `timestep_cond`, `control` the prepared ControlNet image; `mask`, `masked_image_latents`
         (doubled under CFG), `image_latents` and `image_noise` are the inpainting tensors; `edit` is InstructPix2Pix's
-        (image latents, image_guidance_scale): `latents` then hold 4 of the UNet's 8 channels."""
+        (image latents, image_guidance_scale): `latents` then hold 4 of the UNet's 8 channels; `views` is MultiDiffusion's
+        window plan (__call__'s view_* arguments): every model output of the loop then comes from ViewRunner.forward."""
         unet = self._unet(model)
         num_channels_unet = unet.config.in_channels
         # The reference iterates over the device tensor `timesteps`; reading each element on the host
@@ -856,6 +874,15 @@ class StableDiffusionUnifiedPipeline:
                 pag_rows = (torch.cat([prompt_embeds, text(prompt_embeds)]),
                             None if added_cond_kwargs is None else
                             {k: torch.cat([v, text(v)]) for k, v in added_cond_kwargs.items()})
+        # MultiDiffusion: the windows of this loop, their buffers and the embeddings repeated per chunk size, made once (after
+        # the conversion above: the repeats are what the engine's K/V cache then sees)
+        runner = None
+        if views is not None:
+            groups = 2 if self.do_classifier_free_guidance else 1
+            B = latents.shape[0]
+            plan = _views.plan_views(latents.shape[-2], latents.shape[-1], views["window"], views["stride"], views["circular"])
+            batch = max(1, 4 // B) if views["batch"] is None else int(views["batch"])
+            runner = _views.ViewRunner(plan, B, groups, batch, views["blend"], prompt_embeds, lib=getattr(unet, "_lib", None))
         kind = self._device_step_kind(model, latents, num_channels_unet, guidance_rescale)
         if pag is not None and guidance_rescale > 0.0:
             kind = None
@@ -911,7 +938,7 @@ class StableDiffusionUnifiedPipeline:
                     unet_kwargs = cn_kwargs if kind == "linear" else {**cn_kwargs, **tc_kwargs}
                     latents = self._device_iteration(kind, state, model, latents, step_noise, t, prompt_embeds,
                                                      cross_attention_kwargs, added_cond_kwargs, guidance_scale,
-                                                     guidance_rescale, pag_s=pag_s, edit=edit, **unet_kwargs)
+                                                     guidance_rescale, pag_s=pag_s, edit=edit, views=runner, **unet_kwargs)
                     if blend is not None:
                         last = i == len(timesteps_host) - 1
                         a, b = (1.0, 0.0) if last else model.scheduler.add_noise_coefficients(timesteps_host[i + 1])
@@ -936,14 +963,22 @@ class StableDiffusionUnifiedPipeline:
                     latents = self._host_inpaint_blend(model, latents, i, timesteps_host, mask, image_latents, image_noise,
                                                        num_channels_unet)
                     continue
-                latent_model_input = torch.cat([latents] * 2) if self.do_classifier_free_guidance else latents
-                latent_model_input = model.scheduler.scale_model_input(latent_model_input, t)
-                if self.is_inpaint and num_channels_unet == 9:
-                    latent_model_input = torch.cat([latent_model_input, mask.to(latent_model_input.dtype),
-                                                    masked_image_latents.to(latent_model_input.dtype)], dim=1)
-                noise_pred = unet(latent_model_input, t, prompt_embeds,
-                                        cross_attention_kwargs=cross_attention_kwargs,
-                                        added_cond_kwargs=added_cond_kwargs, return_dict=False, **cn_kwargs, **tc_kwargs)[0]
+                if runner is not None:
+                    # MultiDiffusion: the same forward per chunk of windows, merged into a canvas-shaped [G B, ...] output
+                    def run(windows, embeds, out, groups=runner.G):
+                        x = torch.cat([windows] * groups) if groups > 1 else windows
+                        return unet(x, t, embeds, cross_attention_kwargs=cross_attention_kwargs, added_cond_kwargs=None,
+                                    return_dict=False)[0]
+                    noise_pred = runner.forward(model.scheduler.scale_model_input(latents, t), run)
+                else:
+                    latent_model_input = torch.cat([latents] * 2) if self.do_classifier_free_guidance else latents
+                    latent_model_input = model.scheduler.scale_model_input(latent_model_input, t)
+                    if self.is_inpaint and num_channels_unet == 9:
+                        latent_model_input = torch.cat([latent_model_input, mask.to(latent_model_input.dtype),
+                                                        masked_image_latents.to(latent_model_input.dtype)], dim=1)
+                    noise_pred = unet(latent_model_input, t, prompt_embeds,
+                                      cross_attention_kwargs=cross_attention_kwargs,
+                                      added_cond_kwargs=added_cond_kwargs, return_dict=False, **cn_kwargs, **tc_kwargs)[0]
                 if self.do_classifier_free_guidance:
                     noise_pred_uncond, noise_pred_text = noise_pred.chunk(2)
                     noise_pred = guidance_scale * (noise_pred_text - noise_pred_uncond) + noise_pred_uncond
@@ -996,6 +1031,45 @@ class StableDiffusionUnifiedPipeline:
             raise NotImplementedError("InstructPix2Pix on a text_time (SDXL edit) UNet is not supported")
         if int(getattr(base.config, "time_cond_proj_dim", None) or 0) > 0:
             raise NotImplementedError("InstructPix2Pix on a guidance-embedded UNet (time_cond_proj_dim) is not supported")
+
+    @staticmethod
+    def _check_views(model, kw):
+        """What a MultiDiffusion call (view_window given) does not take: raised before anything runs."""
+        base = getattr(model, "base", None)
+        cfg = getattr(base, "config", None)
+        if kw["use_refiner"] or kw["refiner_start"] is not None:
+            raise NotImplementedError("view_window (MultiDiffusion) does not address the refiner")
+        if bool(getattr(model, "has_controlnet", False)) or kw["control_image"] is not None:
+            raise NotImplementedError("view_window (MultiDiffusion) with a ControlNet loaded is not supported "
+                                      "(unload_controlnet): the control image would need windows of its own")
+        if kw["ip_adapter_image"] is not None or kw["ip_adapter_image_embeds"] is not None:
+            raise NotImplementedError("view_window (MultiDiffusion) with an IP-Adapter image is not supported")
+        if kw["pag_scale"] is not None and float(kw["pag_scale"]) > 0.0:
+            raise NotImplementedError("view_window (MultiDiffusion) with perturbed-attention guidance (pag_scale > 0) is "
+                                      "not supported")
+        if getattr(base, "deepcache", None) is not None:
+            raise NotImplementedError("view_window (MultiDiffusion) with DeepCache enabled is not supported: one cached "
+                                      "feature cannot serve several windows (disable_deepcache)")
+        if int(getattr(cfg, "in_channels", 4)) in (8, 9):
+            raise NotImplementedError("view_window (MultiDiffusion) with an 8- or 9-channel UNet is not supported: the extra "
+                                      "channels would need windows of their own")
+        if getattr(cfg, "addition_embed_type", None) == "text_time":
+            raise NotImplementedError("view_window (MultiDiffusion) on a text_time (SDXL) UNet is not supported: every "
+                                      "window would need its own crop conditioning")
+        if int(getattr(cfg, "time_cond_proj_dim", None) or 0) > 0:
+            raise NotImplementedError("view_window (MultiDiffusion) on a guidance-embedded UNet (time_cond_proj_dim) is not "
+                                      "supported")
+        if kw["guidance_rescale"] is not None and float(kw["guidance_rescale"]) > 0.0:
+            raise ValueError("view_window (MultiDiffusion) takes no guidance_rescale: its per-sample statistic differs "
+                             "between a window and the canvas")
+        window = _views.as_pair(kw["view_window"])
+        if min(window) < 1:
+            raise ValueError("view_window must be positive")
+        if kw["view_stride"] is not None and min(_views.as_pair(kw["view_stride"])) < 1:
+            raise ValueError("view_stride must be at least 1")
+        if kw["view_batch_size"] is not None and int(kw["view_batch_size"]) < 1:
+            raise ValueError("view_batch_size must be at least 1")
+        _views.window_weights(kw["view_blend"], 1, 1)          # (an unknown name raises)
 
     @staticmethod
     def _host_step(model, noise_pred, t, latents, noise, lcm):
@@ -1064,9 +1138,12 @@ class StableDiffusionUnifiedPipeline:
         return None
 
     def _device_iteration(self, kind, state, model, latents, noise, t, prompt_embeds, cross_attention_kwargs,
-                          added_cond_kwargs, guidance_scale, guidance_rescale=0.0, pag_s=0.0, edit=None, **unet_kwargs):
+                          added_cond_kwargs, guidance_scale, guidance_rescale=0.0, pag_s=0.0, edit=None, views=None,
+                          **unet_kwargs):
         """One iteration with the scheduler's update on the device: the plan from the scheduler, the UNet forward, one
-        step entry of the engine over a copy of the latents, the plan committed.  -> the new latents."""
+        step entry of the engine over a copy of the latents, the plan committed.  -> the new latents.  `views`
+        (MultiDiffusion's ViewRunner) makes the model output from the canvas's windows; it has the canvas's shape, so
+        everything after it is the same."""
         sched, unet = model.scheduler, self._unet(model)
         lib = unet._lib
         plan = sched.affine_plan(t) if kind == "affine" else sched.fused_plan(t)
@@ -1083,6 +1160,15 @@ class StableDiffusionUnifiedPipeline:
             model_out = unet.forward_pag(latents, t, prompt_embeds, added_cond_kwargs=added_cond_kwargs,
                                          in_scale=plan.in_scale, cfg=self.do_classifier_free_guidance,
                                          share=self.pag_share)[0]
+        elif views is not None and rows == 2:
+            # one forward_cfg per chunk of windows, written straight into the runner's buffer
+            def run(windows, embeds, dst):
+                unet.forward_cfg(windows, t, embeds, in_scale=plan.in_scale, share=self.cfg_share, out=dst)
+            model_out = views.forward(latents, run)
+        elif views is not None:
+            def run(windows, embeds, dst):
+                unet(windows, t, embeds, cross_attention_kwargs=cross_attention_kwargs, return_dict=False, out=dst)
+            model_out = views.forward(sched.scale_model_input(latents, t) if kind == "affine" else latents, run)
         elif rows == 2:                              # rows = [uncond ; text], from the un-duplicated latents
             model_out = self._cfg_forward(model, latents, plan.in_scale, t, prompt_embeds, cross_attention_kwargs,
                                           added_cond_kwargs, **unet_kwargs)
