@@ -684,6 +684,25 @@ int sd_igemm_force(int variant, int splits);
  *   name[64]  = the kernel's name as rocprofv3 prints it
  * Returns SD_ERR_INVALID with "igemm2: bad variant" when a forced id is not in the table. */
 int sd_igemm_plan(const int* geom, const int* flags, int64_t* out, char* name);
+/* The 80-column form of the 3x3 halo kernel (conv3x3_halo_kernel<80>), decided ahead of the planner above for the
+ * launches whose 128- / 160-column halo grid leaves compute units idle.  Host only (no device needed).
+ *   geom, flags  as sd_igemm_plan
+ *   cus          the compute-unit count the rule fills; 0: the device's (256 where there is none)
+ *   out[6]     = ok (0: the launch stays with sd_igemm_plan's answer), tile columns, split-K slices, GroupNorm summaries
+ *                from the launch (0 / 1), pixels per summary, split-K workspace in floats
+ *   name[64]   = the profiler row, empty when not ok
+ * SD_NO_HALO80=1 in the environment (read once per process) turns the form off.  sd_op_conv2d_ex reports it as kind 80.
+ * sd_halo80_force, tests / tools: -1 the rule, 0 never, 1 whenever the kernel takes the problem (any Cout % 8 == 0,
+ * split-K until the grid covers the compute units). */
+int sd_halo80_plan(const int* geom, const int* flags, int cus, int64_t* out, char* name);
+int sd_halo80_force(int mode);
+/* Test entry: sd_op_conv2d (stride 1, dense operands, bias / residual optional) asking the launch for GroupNorm summaries
+ * of its output for gn_groups groups.  summaries (device, summaries_floats floats, at least N * max(64, ceil(OH OW / 64))
+ * * gn_groups * 2) receives what the launch left: [(n * S + slab) * gn_groups + g][mean, M2] over *rows pixels per slab,
+ * S = OH OW / *rows; *rows = 0 when the launch left none.  ran[4] as sd_op_conv2d_ex. */
+int sd_op_conv2d_gnstats(const void* x_nhwc, const void* w_oihw, const void* bias, const void* res_nhwc, void* y_nhwc,
+                         int N, int H, int W, int Cin, int Cout, int ksize, int gn_groups, float* summaries,
+                         int64_t summaries_floats, int* rows, int* ran, void* stream);
 
 /* -- single operators, exported for the parity tests (tests/test_ops_gpu.py) ----------------- */
 /* Implicit-GEMM convolution / linear on NHWC f16:

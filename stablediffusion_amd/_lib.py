@@ -238,6 +238,8 @@ SIGNATURES = {
     "sd_sched_affine_step": (_I, [_P, _I, _P, _P, _P, _I64, _I64, _F, C.POINTER(SdStepPlan), _P]),
     "sd_igemm_force": (_I, [_I, _I]),
     "sd_igemm_plan": (_I, [C.POINTER(_I), C.POINTER(_I), C.POINTER(_I64), C.c_char_p]),
+    "sd_halo80_force": (_I, [_I]),
+    "sd_halo80_plan": (_I, [C.POINTER(_I), C.POINTER(_I), _I, C.POINTER(_I64), C.c_char_p]),
     "sd_probe_mfma": (_I, [_I, C.POINTER(_F), _P]),
     "sd_probe_lds_dma": (_I, [_I64, _I, _I, _I, C.POINTER(_F), _P]),
     "sd_probe_copy": (_I, [_I64, _I, C.POINTER(_F), _P]),
@@ -246,6 +248,7 @@ SIGNATURES = {
     "sd_op_conv2d": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "sd_op_conv2d_ex": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I64, _I64, _I64, _I, _I, _F, _F, _I,
                              C.POINTER(_I), _P]),
+    "sd_op_conv2d_gnstats": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _I64, C.POINTER(_I), C.POINTER(_I), _P]),
     "sd_upconv_fold_supported": (_I, [_I, _I, _I, _I, _I]),
     "sd_op_fold_upconv": (_I, [_P, _P, _I, _I, _P]),
     "sd_op_upconv2x_ex": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I64, _I64, _I64, _F, _F, _I, _P,

@@ -927,6 +927,41 @@ int sd_igemm_plan(const int* geom, const int* flags, int64_t* out, char* name) {
     return SD_OK;
 }
 
+int sd_halo80_force(int mode) { halo80_force(mode); return SD_OK; }
+
+int sd_halo80_plan(const int* geom, const int* flags, int cus, int64_t* out, char* name) {
+    if (!geom || !flags || !out || !name) { set_error("sd_halo80_plan: null argument"); return SD_ERR_INVALID; }
+    const int N = geom[0], H = geom[1], W = geom[2], Cin = geom[3], Cout = geom[4], ks = geom[5], stride = geom[6], up = geom[7];
+    if (N < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1 || (ks != 1 && ks != 3) || stride < 1 || up < 0 || up > 1 || cus < 0) {
+        set_error("sd_halo80_plan: bad geometry"); return SD_ERR_INVALID;
+    }
+    // the problem as sd_igemm_plan poses it (same geom / flags)
+    float* const set = reinterpret_cast<float*>(8);
+    const half_t* const seth = reinterpret_cast<const half_t*>(set);
+    IGemmParams p{};
+    p.x = seth; p.ldx = Cin; p.w = seth; p.y = reinterpret_cast<half_t*>(set);
+    p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.KS = ks; p.stride = stride; p.up = up;
+    p.pad = geom[8] >= 0 ? geom[8] : (ks == 3 ? 1 : 0);
+    const int IH = H << up, IW = W << up;
+    if (stride == 1) { p.OH = IH; p.OW = IW; }
+    else if (p.pad == 0) { p.OH = (IH + 1 - ks) / stride + 1; p.OW = (IW + 1 - ks) / stride + 1; }
+    else { p.OH = (IH + 2 * p.pad - ks) / stride + 1; p.OW = (IW + 2 * p.pad - ks) / stride + 1; }
+    p.M = N * p.OH * p.OW; p.K = ks * ks * Cin;
+    p.geglu = flags[0]; p.act = flags[1];
+    p.ldy = p.geglu ? Cout / 2 : Cout;
+    if (flags[2]) { p.res = seth; p.ldres = p.ldy; }
+    if (flags[3]) { p.rowadd = set; p.rowadd_ld = Cout; }
+    if (flags[4]) p.bias = set;
+    if (flags[5] > 0) { p.ln_stat = set; p.ln_parts = flags[5]; p.ln_part_w = (p.K + flags[5] - 1) / flags[5]; p.ln_C = p.K; p.ln_eps = 1e-5f; p.ln_wsum = set; }
+    if (flags[8] > 0) { p.gni_part = set; p.gni_S = 1; p.gni_rows = (long)H * W; p.gni_groups = flags[8]; p.gni_eps = 1e-5f; p.gni_gb = set; }
+    if (flags[9]) { p.acc_scale = 0.5f; p.bias_scale = 0.5f; }
+    const Halo80Plan pl = halo80_plan(p, IGemmRequest{flags[6] ? set : nullptr, flags[7] > 0 ? set : nullptr, flags[7]}, cus);
+    const int64_t o[6] = {pl.ok, pl.bn, pl.splits, pl.gnstats, pl.gn_rows, pl.partial_floats};
+    for (int i = 0; i < 6; ++i) out[i] = o[i];
+    snprintf(name, 64, "%s", pl.name);
+    return SD_OK;
+}
+
 // --------------------------------------------------------------------------------------- profiling
 int sd_prof_enable(int on) { prof_enable(on != 0); return SD_OK; }
 int sd_prof_collect(sd_prof_entry* out, int max_entries, int* n_entries) {
@@ -1003,6 +1038,9 @@ struct ConvEx {
     float acc_scale, bias_scale;
     int gn_groups;
     int* ran;
+    float* gn_copy = nullptr;       // sd_op_conv2d_gnstats: the summaries the launch left are copied here (gn_copy_floats at most)
+    long gn_copy_floats = 0;
+    int* gn_rows = nullptr;         // ... and the pixels per summary (0: none left)
 };
 
 static int conv2d_impl(const void* x, const void* w_oihw, const void* bias_f32, const void* rowadd_f32, const void* res,
@@ -1100,7 +1138,19 @@ static int conv2d_impl(const void* x, const void* w_oihw, const void* bias_f32, 
             SD_HIP_CHECK(hipMemsetAsync(res_bench, 0, (size_t)p.M * ocols * sizeof(half_t), s));
             p.res = res_bench;
         }
-        const IGemmPlan plan = igemm2_plan(p, IGemmRequest{nullptr, gnbuf, gn ? gn->groups : ex ? ex->gn_groups : 0});
+        // as op_conv: the 80-column halo tile is asked first; its plan is reported in the planner's terms
+        const IGemmRequest rq{nullptr, gnbuf, gn ? gn->groups : ex ? ex->gn_groups : 0};
+        const Halo80Plan hp = halo80_plan(p, rq);
+        IGemmPlan plan;
+        if (hp.ok) {
+            plan.kind = plan.variant = kKindHalo80;
+            plan.splits = hp.splits; plan.partial_floats = hp.partial_floats;
+            plan.bm = 256; plan.bn = hp.bn;
+            plan.gnstats = hp.gnstats; plan.gn_rows = hp.gn_rows;
+            plan.scales_ok = true;
+        } else {
+            plan = igemm2_plan(p, rq);
+        }
         if (ex && !plan.scales_ok && (p.acc_scale != 1.f || p.bias_scale != 1.f)) {
             set_error("sd_op_conv2d_ex: the planned kernel does not take acc_scale / bias_scale"); return SD_ERR_INVALID;
         }
@@ -1138,11 +1188,18 @@ static int conv2d_impl(const void* x, const void* w_oihw, const void* bias_f32, 
         for (int it = 0; it < iters + (ms_out ? 2 : 0) && !rc; ++it) {
             if (ms_out && it == 2) SD_HIP_CHECK(hipEventRecord(e0, s));     // two warm-up launches
             if (wring) p.w = reinterpret_cast<half_t*>(reinterpret_cast<char*>(wring) + wbytes * (size_t)(it % nrot));
-            rc = launch_igemm2(p, partial, s, &plan);
+            rc = hp.ok ? launch_halo80(p, hp, partial, s) : launch_igemm2(p, partial, s, &plan);
         }
         if (ex && ex->ran) {
             const IGemmLaunchNote note = igemm2_last_launch();
             ex->ran[0] = plan.kind; ex->ran[1] = plan.variant; ex->ran[2] = note.splits; ex->ran[3] = note.reducer;
+        }
+        if (ex && ex->gn_rows) {
+            *ex->gn_rows = plan.gnstats ? plan.gn_rows : 0;
+            long n = gnstat_floats(N, (long)p.OH * p.OW, ex->gn_groups);
+            if (n > ex->gn_copy_floats) n = ex->gn_copy_floats;
+            if (plan.gnstats && ex->gn_copy && n > 0 && !rc)
+                SD_HIP_CHECK(hipMemcpyAsync(ex->gn_copy, gnbuf, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, s));
         }
         if (gn && !rc)
             rc = launch_groupnorm(p.y, p.ldy, gn->gamma, gn->beta, static_cast<half_t*>(gn->y), Cout, N, (long)p.OH * p.OW, Cout,
@@ -1191,6 +1248,21 @@ int sd_op_conv2d_ex(const void* x, const void* w_oihw, const void* bias_f32, con
     const ConvEx ex{(long)ldx, (long)ldres, (long)ldy, pad, act, acc_scale, bias_scale, gn_groups, ran};
     return conv2d_impl(x, w_oihw, bias_f32, rowadd_f32, res, y, N, H, W, Cin, Cout, ksize, stride, upsample2x, geglu,
                        stream, 1, nullptr, nullptr, nullptr, &ex);
+}
+
+int sd_op_conv2d_gnstats(const void* x, const void* w_oihw, const void* bias_f32, const void* res, void* y, int N, int H,
+                         int W, int Cin, int Cout, int ksize, int gn_groups, float* summaries, int64_t summaries_floats,
+                         int* rows, int* ran, void* stream) {
+    if (!x || !w_oihw || !y || !summaries || !rows || !ran || N < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1 ||
+        (ksize != 1 && ksize != 3) || gn_groups < 1 || summaries_floats < 0) {
+        set_error("sd_op_conv2d_gnstats: bad arguments"); return SD_ERR_INVALID;
+    }
+    for (int i = 0; i < 4; ++i) ran[i] = 0;
+    *rows = 0;
+    ConvEx ex{Cin, Cout, Cout, -1, 0, 1.f, 1.f, gn_groups, ran};
+    ex.gn_copy = summaries; ex.gn_copy_floats = (long)summaries_floats; ex.gn_rows = rows;
+    return conv2d_impl(x, w_oihw, bias_f32, nullptr, res, y, N, H, W, Cin, Cout, ksize, 1, 0, 0, stream, 1, nullptr, nullptr,
+                       nullptr, &ex);
 }
 
 int sd_op_conv3x3_small_cout(const void* x, const void* w_oihw, const void* bias_f32, void* y_nchw, int N, int H, int W,

@@ -92,6 +92,45 @@ __device__ __forceinline__ void gn_tile_stats(float* sG, int tid, float gm0, flo
         *reinterpret_cast<float2*>(dst + (long)g * 2) = float2{pvt + a, q - s * a};
     }
 }
+// The same merge with a wave per group: the lanes take the group's pieces interleaved, a butterfly adds their pivot-shifted
+// sums (a fixed order too).  For the 80-column halo tile, whose 51 row parts per chunk one thread per group walks for
+// about 6 us (measured: 68.9 us against 63 us on the 8192 x 640 x 5760 conv).
+template <int BM, int BN, int NT>
+__device__ __forceinline__ void gn_tile_stats_wave(float* sG, int tid, float gm0, float gq0, float gm1, float gq1, int n0,
+                                                   int Cout, int cpg, int groups, float* dst) {
+    constexpr int CH = BN / 8;
+    constexpr int RPP = NT / CH;
+    *reinterpret_cast<f4*>(sG + tid * 4) = f4{gm0, gq0, gm1, gq1};
+    __syncthreads();
+    const int cols = Cout - n0 < BN ? Cout - n0 : BN;
+    const int ng = cols / cpg;
+    const int lane = tid & 63;
+    for (int t = tid >> 6; t < ng; t += NT / 64) {       // wave-uniform
+        const int g = n0 / cpg + t;
+        const int cfirst = (t * cpg) / 8, clast = ((t + 1) * cpg - 1) / 8;
+        const int cf = n0 + cfirst * 8;
+        const float pvt = sG[((cf / cpg == g) ? 0 : 2) + cfirst * 4];
+        const int pieces = (clast - cfirst + 1) * RPP;
+        float s = 0.f, q = 0.f;
+        for (int k = lane; k < pieces; k += 64) {
+            const int ci = k / RPP, rr = k - ci * RPP, c8 = cfirst + ci;
+            const int c0 = n0 + c8 * 8;
+            const int part = (c0 / cpg == g) ? 0 : 2;
+            const int lo = c0 > g * cpg ? c0 : g * cpg, hi = c0 + 8 < (g + 1) * cpg ? c0 + 8 : (g + 1) * cpg;
+            const float2 v = *reinterpret_cast<const float2*>(sG + (rr * CH + c8) * 4 + part);
+            const float nk = (float)(((BM - rr + RPP - 1) / RPP) * (hi - lo));
+            const float d = v.x - pvt;
+            s += nk * d;
+            q += v.y + nk * d * d;
+        }
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) { s += __shfl_xor(s, o); q += __shfl_xor(q, o); }
+        if (lane == 0) {
+            const float a = s / (float)(BM * cpg);
+            *reinterpret_cast<float2*>(dst + (long)g * 2) = float2{pvt + a, q - s * a};
+        }
+    }
+}
 // One stored row chunk (8 channels from n) into the thread's sums of the chunk's first group (channels e < gsplit) and
 // of its second, each shifted by a pivot: the first value of that part the thread sees (first = its first row).  The
 // sums then cancel nothing whatever |mean| / std is; gn_part_finish turns them into (mean, M2).
@@ -706,7 +745,8 @@ inline int launch_splitk_epilogue(const IGemmParams& p, const float* partial, in
 // it at shifted pixel offsets; only the weights [160 x 64 per tap] still stream, through a 3-deep
 // ring.  The XOR swizzle is on the halo pixel index, so the 16 consecutive pixels of an MFMA operand
 // stay conflict-free at every shift.  The 256 pixels are an R x Wt patch (64 / 32 / 16 columns wide,
-// whichever tiles the image), so any H x W that such a patch divides qualifies; 8 waves (4 x 2).
+// whichever tiles the image), so any H x W that such a patch divides qualifies; 8 waves (4 x 2; 8 x 1 in the 80-column
+// form, which halo80_plan routes: twice the blocks where the wide tiles leave CUs idle).
 // ---------------------------------------------------------------------------------------------
 // Width of the 256-pixel patch a block covers: the widest of 64 / 32 / 16 columns that tiles the image
 // (W % Wt == 0 and H % (256 / Wt) == 0); 0 if none does.
@@ -740,11 +780,17 @@ __host__ __device__ inline int halo_patch_width(int H, int W) {
 template <int BN, bool GNF, bool KHU>
 __global__ __launch_bounds__(512) void conv3x3_halo_kernel(IGemmParams p, float* partial, int slabs_per_split) {
 #if defined(__HIP_DEVICE_COMPILE__)
-    static_assert(BN == 160 || BN == 128, "column tile");
+    static_assert(BN == 160 || BN == 128 || BN == 80, "column tile");
+    static_assert(!(GNF && BN == 80), "the 80-column form has no fused input GroupNorm");
     constexpr unsigned kOOB = 0x80000000u;
-    constexpr int BM = 256, NW = 8, NT = 512, WAVES_N = 2;
-    constexpr int WTM = 64, WTN = BN / 2, TM = 4, TN = WTN / 16;
-    constexpr int B_INSTR = BN / 8, B_PW = (B_INSTR + NW - 1) / NW, B_REM = B_INSTR % NW;   // 160: 20 = 4 waves x 3 + 4 x 2; 128: 2 each
+    // wave grid 4 x 2 (64 x BN/2 per wave); at 80 columns 8 x 1 (32 x 80 per wave: 20 MFMAs per tap, 40 accumulators)
+    constexpr int BM = 256, NW = 8, NT = 512, WAVES_N = BN == 80 ? 1 : 2;
+    constexpr int WTM = BM / (NW / WAVES_N), WTN = BN / WAVES_N, TM = WTM / 16, TN = WTN / 16;
+    static_assert(WTN % 16 == 0 && WTM % 16 == 0, "wave tile must be MFMA-shaped");
+    // 160: 20 = 4 waves x 3 + 4 x 2; 128: 2 each; 80: 10 = 2 waves x 2 + 6 x 1
+    constexpr int B_INSTR = BN / 8, B_PW = (B_INSTR + NW - 1) / NW, B_REM = B_INSTR % NW;
+    constexpr int B_MIN = B_REM == 0 ? B_PW : B_PW - 1;     // the smallest share of a weight stage any wave issues
+    constexpr int A_MIN = 5;                                 // ... and of a halo tile (41 - 50 instructions over 8 waves)
     constexpr int B_STAGE_HALVES = BN * 64;     // three ring stages: one per tap of a kernel row
     constexpr int AJ = 7;                        // halo DMA instructions per wave, at most
     constexpr int KH_UNROLL = KHU ? 3 : 1;
@@ -967,8 +1013,8 @@ __global__ __launch_bounds__(512) void conv3x3_halo_kernel(IGemmParams p, float*
                 // B(g) must have landed (and at the first tap the slab's halo, which is older).  Younger loads
                 // that may stay in flight: B(g + 1), and the next halo while it is younger than B(g) (taps 1, 2).
                 if (lastrow && kw == 2) wait_vmcnt<0>();
-                else if (a_next && kh == 0 && kw >= 1) wait_vmcnt<7>();
-                else wait_vmcnt<2>();
+                else if (a_next && kh == 0 && kw >= 1) wait_vmcnt<B_MIN + A_MIN>();
+                else wait_vmcnt<B_MIN>();
                 // (GNF: this wave's in-place writes -- halo slots, scale | shift -- are done before it meets the barrier)
                 if constexpr (GNF) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 __builtin_amdgcn_s_barrier();
@@ -1047,8 +1093,11 @@ __global__ __launch_bounds__(512) void conv3x3_halo_kernel(IGemmParams p, float*
     {
         f4 add[TN];
 #pragma unroll
-        for (int j = 0; j < TN; ++j)
-            add[j] = p.bias ? *reinterpret_cast<const f4*>(p.bias + n0 + wn * WTN + j * 16 + fq * 4) * bias_scale : f4{0.f, 0.f, 0.f, 0.f};
+        for (int j = 0; j < TN; ++j) {
+            // (80 columns: a ragged last tile checks the column instead of relying on the bias's padded length)
+            const bool inb = BN != 80 || n0 + wn * WTN + j * 16 + fq * 4 < p.Cout;
+            add[j] = p.bias && inb ? *reinterpret_cast<const f4*>(p.bias + n0 + wn * WTN + j * 16 + fq * 4) * bias_scale : f4{0.f, 0.f, 0.f, 0.f};
+        }
         if (p.rowadd) {          // one image per tile: the row add is the same for every row
             const float* ra = p.rowadd + (long)img * p.rowadd_ld + n0 + wn * WTN + fq * 4;
             f4 r4[TN];
@@ -1090,7 +1139,7 @@ __global__ __launch_bounds__(512) void conv3x3_halo_kernel(IGemmParams p, float*
     // GroupNorm summaries of the stored tile (as igemm2_kernel's epilogue) -- in the 128-column form only: with 64
     // accumulator registers instead of 80 the allocator keeps the main loop free of spill reloads (the header
     // comment has what happened at 160 columns)
-    constexpr bool GN = BN == 128 || !KHU;
+    constexpr bool GN = BN != 160 || !KHU;              // (80 columns: 40 accumulator registers, room to spare)
     const int cpg = (GN && p.gnstat_out) ? p.Cout / p.gn_groups : 8;
     const int g_first = n / cpg;
     const int gsplit = (g_first + 1) * cpg - n;
@@ -1114,8 +1163,9 @@ __global__ __launch_bounds__(512) void conv3x3_halo_kernel(IGemmParams p, float*
         if (p.gnstat_out) {
             float* sG = reinterpret_cast<float*>(smem + ((BM * LDC * 2 + 15) & ~15));     // behind the staging tile
             gn_part_finish(gsplit, gnv, gp0, gp1, gm0, gq0, gm1, gq1);
-            gn_tile_stats<BM, BN, NT>(sG, tid, gm0, gq0, gm1, gq1, n0, p.Cout, cpg, p.gn_groups,
-                                      p.gnstat_out + ((long)img * patches + pidx) * p.gn_groups * 2);
+            float* const gdst = p.gnstat_out + ((long)img * patches + pidx) * p.gn_groups * 2;
+            if constexpr (BN == 80) gn_tile_stats_wave<BM, BN, NT>(sG, tid, gm0, gq0, gm1, gq1, n0, p.Cout, cpg, p.gn_groups, gdst);
+            else gn_tile_stats<BM, BN, NT>(sG, tid, gm0, gq0, gm1, gq1, n0, p.Cout, cpg, p.gn_groups, gdst);
         }
     }
 #endif  // __HIP_DEVICE_COMPILE__
@@ -1133,6 +1183,8 @@ int launch_halo_t(const IGemmParams& p, float* partial, int splits, hipStream_t 
     // [2 halo tiles | 3 weight stages | GNF: 128 floats scale / shift + 64 floats mean / rstd]
     size_t lds = (size_t)2 * (R + 2) * (Wt + 2) * 128 + (size_t)3 * BN * 128 + (GNF ? 768 : 0);
     const size_t epi = (size_t)256 * (BN + 8) * 2 + 16 + 512 * 16;       // staging tile + GroupNorm partials
+    // the largest patch (64 columns: 6 x 66 halo pixels) fits at every column tile
+    static_assert(2 * 6 * 66 * 128 + 3 * BN * 128 + (GNF ? 768 : 0) <= 160 * 1024, "LDS budget");
     if (lds < epi) lds = epi;
     if (lds > 160 * 1024) { set_error("conv3x3_halo_kernel: LDS budget"); return 1; }
     static size_t attr_by_dev[64] = {};
@@ -1474,6 +1526,7 @@ int launch_v2(const IGemmParams& p, float* partial, int splits, hipStream_t s) {
 // consistent value each; the tile choice itself is per launch
 std::atomic<int> g_force_variant{-1};
 std::atomic<int> g_force_splits{0};
+std::atomic<int> g_halo80_mode{-1};         // sd_halo80_force: -1 the rule, 0 never, 1 whenever the kernel takes the problem
 
 // ---------------------------------------------------------------------------------------------
 // The variant table: one row per variant id.  The ids are an external contract (sd_igemm_force, the tuner's
@@ -1734,6 +1787,86 @@ int launch_upconv_fold(const IGemmParams& p, const UpconvFoldPlan& plan, hipStre
         set_error("launch_upconv_fold: not a folded-upsample problem (upconv_fold_plan decides)"); return 1;
     }
     return plan.bn == 160 ? launch_up2x2_t<160>(p, s) : launch_up2x2_t<128>(p, s);
+}
+
+void halo80_force(int mode) { g_halo80_mode = mode < -1 || mode > 1 ? -1 : mode; }
+
+// CUs of the device, asked once per process (the devices of one box are the same part); 256 where there is none to ask
+// (planning on the host)
+static int device_cus() {
+    static const int cus = [] {
+        int dev = 0, n = 0;
+        if (hipGetDevice(&dev) != hipSuccess ||
+            hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1)
+            n = 256;
+        return n;
+    }();
+    return cus;
+}
+
+// The 80-column halo tile, decided ahead of igemm2_plan (which answers every problem as it always has).
+// The kernel takes: 3x3, stride 1, pad 1, no upsample, halo_supported, no GroupNorm fused into the input, no LayerNorm
+// fold, no row statistics.  Split-K in that form: the fewest slices that put a block on every CU, while the longest
+// slice keeps two slabs.
+// The rule (sd_halo80_force(-1)), from the per-shape comparison in profiles/halo80.txt: the launch moves when
+//   * Cout is a multiple of 80 (no padded columns are computed),
+//   * the 80-column tiles, UNSPLIT, are one round on more than 3/4 of the CUs and at most all of them, and
+//   * K is at most 10 slabs deep (Cin <= 640).
+// On 256 CUs that is M x Cout = 16384 x 320, 8192 x 640 and 4096 x 1280: where the planner runs 160 tiles of 128 columns
+// on 256 CUs, two split-K slices of 128 tiles of 160 columns with a reduction behind them, or (16384 x 320 x 2880) the
+// streamed 128 x 80 tile.  Measured 6-22 % faster there in every round.  A block of this tile pays more per tap than the
+// wide ones (0.57 us against 0.53 us at 128 columns: every wave reads all 80 weight rows from LDS for 20 MFMAs) and less
+// per launch, so it loses beyond 10 slabs (+7 % at 20, +11 % at 30); with two slices to fill the chip (2048 x 1280) it
+// wins 4 % at 10 slabs and loses 7-11 % deeper, and is not taken.
+Halo80Plan halo80_plan(IGemmParams& p, const IGemmRequest& rq, int cus) {
+    Halo80Plan pl;
+    static const bool off = getenv("SD_NO_HALO80") != nullptr;         // A/B switch: every conv as igemm2_plan says
+    const int mode = g_halo80_mode.load();
+    if (off || mode == 0) return pl;
+    if (p.KS != 3 || p.stride != 1 || p.pad != 1 || p.up != 0 || p.gni_part || p.ln_stat || rq.rowstat ||
+        !igemm2_supported(p) || !halo_supported(p))
+        return pl;
+    if (cus <= 0) cus = device_cus();
+    const long tiles = (long)(p.M / 256) * cdiv(p.Cout, 80);
+    const int nslab = p.Cin / 64;
+    int sp = 1;
+    if (mode < 0) {
+        if (g_force_variant.load() >= 0 || valid_id(rq.hint_variant)) return pl;      // a forced or hinted tile runs as itself
+        if (p.Cout % 80 != 0 || nslab > 10 || tiles > cus || tiles * 4 <= (long)cus * 3) return pl;
+        // (what it takes over: a halo or a streamed tile of the table -- a 3x3 problem the planner hands to the old igemm
+        // kernel is not one the LDS-DMA kernels take)
+        IGemmParams q = p;
+        const IGemmPlan cur = igemm2_plan(q, rq);
+        if (!valid_id(cur.kind) || (kVariants[cur.kind].family != Family::Halo && kVariants[cur.kind].family != Family::Tile))
+            return pl;
+    } else if (!rq.no_workspace) {
+        while (tiles * sp < cus && sp < 8 && cdiv(nslab, sp + 1) >= 2) ++sp;
+    }
+    pl.ok = true;
+    pl.bn = 80;
+    pl.splits = sp;
+    pl.partial_floats = sp > 1 ? (long)sp * p.M * p.Cout : 0;
+    // GroupNorm summaries under the planner's conditions (igemm2_plan, step 1): from the epilogue of an unsplit launch when
+    // group boundaries fall on tile boundaries, from the split-K reduction otherwise
+    const int G = rq.gn_groups, cpg = G > 0 && p.Cout % G == 0 ? p.Cout / G : 0;
+    p.gnstat_out = nullptr; p.gn_groups = 0; p.rowstat_out = nullptr;
+    if (rq.gnstat && (cpg >= 8 || cpg == 4)) {
+        p.gnstat_out = rq.gnstat; p.gn_groups = G;
+        pl.gn_rows = sp > 1 ? splitk_gs_rows(p, G) : (80 % cpg == 0 || p.Cout <= 80 ? 256 : 0);
+        pl.gnstats = pl.gn_rows > 0;
+        if (!pl.gnstats) { p.gnstat_out = nullptr; p.gn_groups = 0; }
+    }
+    snprintf(pl.name, sizeof(pl.name), "conv3x3_halo_kernel<80>");
+    return pl;
+}
+
+int launch_halo80(const IGemmParams& p, const Halo80Plan& plan, float* partial, hipStream_t s) {
+    t_note = IGemmLaunchNote();
+    if (!plan.ok || p.KS != 3 || p.stride != 1 || p.up != 0 || p.gni_part || p.ln_stat || !halo_supported(p) ||
+        (plan.splits > 1 && !partial)) {
+        set_error("launch_halo80: not a problem of the 80-column halo tile (halo80_plan decides)"); return 1;
+    }
+    return launch_halo_t<80, false, true>(p, partial, plan.splits, s);
 }
 
 IGemmLaunchNote igemm2_last_launch() { return t_note; }

@@ -90,6 +90,7 @@ bool igemm2_tuned_pointwise(int M, int N, int K, int* variant, int* splits);
 constexpr int kKindPgemmGeglu = 100;    // geglu_persist_kernel (pgemm.hip)
 constexpr int kKindIgemm1 = -1;         // not an LDS-DMA problem (!igemm2_supported): launch_igemm
 constexpr int kKindBadVariant = -2;     // a forced variant id outside the table: the launch fails
+constexpr int kKindHalo80 = 80;         // conv3x3_halo_kernel<80>, outside the planner (halo80_plan); only sd_op_conv2d_ex reports it
 struct IGemmPlan {
     int kind = kKindIgemm1;         // the kernel that runs: a variant id of igemm2.hip's table, or one of the above
     int variant = -1;               // the tile the choice landed on (differs from kind where pgemm / igemm3 / its fallback take over)
@@ -129,6 +130,26 @@ struct UpconvFoldPlan {
 // fused input GroupNorm and row statistics: those stay on the 9-tap kernels.
 UpconvFoldPlan upconv_fold_plan(IGemmParams& p, const half_t* w_fold, const IGemmRequest& rq);
 int launch_upconv_fold(const IGemmParams& p, const UpconvFoldPlan& plan, hipStream_t s);
+// The 80-column form of the halo kernel (conv3x3_halo_kernel<80>: 256 pixels x 80 columns, waves 8 x 1): twice the
+// blocks of the 160-column tile on the same halo tiles, for the launches whose 128- / 160-column grid leaves CUs idle
+// (M = 8192 x Cout = 640 is 32 x 5 tiles of 128 columns on 256 CUs, and 32 x 8 of these).  Decided outside igemm2_plan,
+// like the folded upsample.
+struct Halo80Plan {
+    bool ok = false;                // the 80-column kernel runs this launch
+    int bn = 0;                     // its column tile (80)
+    int splits = 1;                 // split-K slices
+    long partial_floats = 0;        // fp32 workspace the caller passes as `partial` (0: none)
+    bool gnstats = false;           // the epilogue, or the split-K reduction, leaves the GroupNorm summaries asked for
+    int gn_rows = 0;                // pixels per summary
+    char name[64] = "";             // profiler row: "conv3x3_halo_kernel<80>"
+};
+// The one predicate of the dry and the live pass; host only, pure.  p = the problem as op_conv poses it; when the plan
+// is ok, p.gnstat_out / p.gn_groups are set to what the launch will fill.  cus: the CU count the rule fills (0: the
+// device's).  SD_NO_HALO80=1 (read once) turns it off.  The rule is stated at the definition (igemm2.hip).
+Halo80Plan halo80_plan(IGemmParams& p, const IGemmRequest& rq, int cus = 0);
+int launch_halo80(const IGemmParams& p, const Halo80Plan& plan, float* partial, hipStream_t s);
+// tests / tools: -1 the rule, 0 never, 1 whenever the kernel takes the problem (split-K until the grid covers the CUs)
+void halo80_force(int mode);
 // The folded pack of a [O][I][3][3] fp16 weight: four parity panels (dy, dx), each [rows][4 I] with rows = O padded
 // to kWeightRowPad (wp zeroed by the caller), K order [I / 64][a][b][64]; rows dy = 0: W'[a=0] = W[kh=0],
 // W'[a=1] = W[1] + W[2]; dy = 1: W'[0] = W[0] + W[1], W'[1] = W[2]; columns likewise.  Taps are summed in fp32

@@ -481,6 +481,34 @@ void op_conv(Ctx& c, const ConvW& w, View x, int N, int H, int W, View y, int st
             return;
         }
     }
+    // The 80-column halo tile where the planner's halo grid leaves CUs idle: asked first, by the one predicate of the dry
+    // and the live pass (its split-K workspace is planned in both)
+    if (w.ks == 3 && stride == 1 && up == 0 && !geglu && !act) {
+        const Halo80Plan hp = halo80_plan(p, rq);
+        if (hp.ok) {
+            if (gn_out) {
+                gn_out->st = GnStats();
+                if (hp.gnstats) { gn_out->st.part = gn_out->buf; gn_out->st.rows = hp.gn_rows; gn_out->st.S = p.OH * p.OW / hp.gn_rows; }
+            }
+            float* partial = hp.partial_floats > 0 ? c.arena->alloc_f(hp.partial_floats) : nullptr;
+            if (c.dry || c.err) return;
+            if (prof_enabled()) {
+                const char* name = hp.name;
+                static const bool by_shape = getenv("SD_PROF_SHAPES") != nullptr;
+                char nbuf[64];
+                if (by_shape) {
+                    snprintf(nbuf, sizeof(nbuf), "h80/k%d %dx%dx%d ks%d%s%s", hp.splits, p.M, p.Cout, p.K, p.KS, res ? " res" : "",
+                             p.gnstat_out ? " gs" : "");
+                    name = nbuf;
+                }
+                prof_open(c.stream, name, 2.0 * p.M * w.cout * 9.0 * w.cin,
+                          2.0 * ((double)N * H * W * w.cin + (double)w.cout * w.K + (double)p.M * w.cout * (res ? 2 : 1)));
+            }
+            c.err = launch_halo80(p, hp, partial, c.stream);
+            prof_close(c.stream);
+            return;
+        }
+    }
     const IGemmPlan plan = igemm2_plan(p, rq);
     const bool v2 = plan.kind != kKindIgemm1;
     if ((p.acc_scale != 1.f || p.bias_scale != 1.f) && !plan.scales_ok) { set_error("op_conv: output scaling needs the LDS-DMA kernels (not GEGLU / weight-stationary)"); c.err = 1; return; }
