@@ -696,6 +696,13 @@ int sd_igemm_plan(const int* geom, const int* flags, int64_t* out, char* name);
  * split-K until the grid covers the compute units). */
 int sd_halo80_plan(const int* geom, const int* flags, int cus, int64_t* out, char* name);
 int sd_halo80_force(int mode);
+/* The whole decision for a convolution launch, as the engine's graphs take it (conv_plan), host only (no device needed):
+ * the folded upsample where upsample2x = 1 and have_fold says a folded pack is at hand (kind 220, sd_upconv_fold_supported
+ * and none of GEGLU / activation / row add / residual / LayerNorm fold / fused input GroupNorm / row statistics), then the
+ * 80-column halo tile (kind 80, as sd_halo80_plan), then the variant table (as sd_igemm_plan).
+ *   geom, flags, out[12], name[64]  as sd_igemm_plan; variant = kind and 256 tile rows for kinds 220 and 80
+ *   cus                             as sd_halo80_plan */
+int sd_conv_plan(const int* geom, const int* flags, int have_fold, int cus, int64_t* out, char* name);
 /* Test entry: sd_op_conv2d (stride 1, dense operands, bias / residual optional) asking the launch for GroupNorm summaries
  * of its output for gn_groups groups.  summaries (device, summaries_floats floats, at least N * max(64, ceil(OH OW / 64))
  * * gn_groups * 2) receives what the launch left: [(n * S + slab) * gn_groups + g][mean, M2] over *rows pixels per slab,

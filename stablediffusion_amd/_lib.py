@@ -240,6 +240,7 @@ SIGNATURES = {
     "sd_igemm_plan": (_I, [C.POINTER(_I), C.POINTER(_I), C.POINTER(_I64), C.c_char_p]),
     "sd_halo80_force": (_I, [_I]),
     "sd_halo80_plan": (_I, [C.POINTER(_I), C.POINTER(_I), _I, C.POINTER(_I64), C.c_char_p]),
+    "sd_conv_plan": (_I, [C.POINTER(_I), C.POINTER(_I), _I, _I, C.POINTER(_I64), C.c_char_p]),
     "sd_probe_mfma": (_I, [_I, C.POINTER(_F), _P]),
     "sd_probe_lds_dma": (_I, [_I64, _I, _I, _I, C.POINTER(_F), _P]),
     "sd_probe_copy": (_I, [_I64, _I, C.POINTER(_F), _P]),

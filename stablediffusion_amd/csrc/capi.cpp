@@ -893,23 +893,19 @@ int sd_probe_copy(int64_t bytes, int iters, float* gbs, void* stream) {
 // ------------------------------------------------------------------------------------------ tuning
 int sd_igemm_force(int variant, int splits) { igemm2_force(variant, splits); return SD_OK; }
 
-int sd_igemm_plan(const int* geom, const int* flags, int64_t* out, char* name) {
-    if (!geom || !flags || !out || !name) { set_error("sd_igemm_plan: null argument"); return SD_ERR_INVALID; }
+// The problem and the requests the plan entries describe by geom[9] / flags[10] (include/sd_engine.h: sd_igemm_plan).  An
+// operand that is "present" is a dummy non-null pointer: the planner only asks whether one is set.
+static int plan_problem(const char* entry, const int* geom, const int* flags, const void* out, const void* name,
+                        IGemmParams* problem, IGemmRequest* rq) {
+    if (!geom || !flags || !out || !name) { set_error(std::string(entry) + ": null argument"); return SD_ERR_INVALID; }
     const int N = geom[0], H = geom[1], W = geom[2], Cin = geom[3], Cout = geom[4], ks = geom[5], stride = geom[6], up = geom[7];
     if (N < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1 || (ks != 1 && ks != 3) || stride < 1 || up < 0 || up > 1) {
-        set_error("sd_igemm_plan: bad geometry"); return SD_ERR_INVALID;
+        set_error(std::string(entry) + ": bad geometry"); return SD_ERR_INVALID;
     }
-    float* const set = reinterpret_cast<float*>(8);          // "present": the planner only asks whether a pointer is set
+    float* const set = reinterpret_cast<float*>(8);
     const half_t* const seth = reinterpret_cast<const half_t*>(set);
-    IGemmParams p{};
+    IGemmParams p = conv_problem(N, H, W, Cin, Cout, ks, stride, up, geom[8]);
     p.x = seth; p.ldx = Cin; p.w = seth; p.y = reinterpret_cast<half_t*>(set);
-    p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.KS = ks; p.stride = stride; p.up = up;
-    p.pad = geom[8] >= 0 ? geom[8] : (ks == 3 ? 1 : 0);
-    const int IH = H << up, IW = W << up;                    // output size as op_conv derives it
-    if (stride == 1) { p.OH = IH; p.OW = IW; }
-    else if (p.pad == 0) { p.OH = (IH + 1 - ks) / stride + 1; p.OW = (IW + 1 - ks) / stride + 1; }
-    else { p.OH = (IH + 2 * p.pad - ks) / stride + 1; p.OW = (IW + 2 * p.pad - ks) / stride + 1; }
-    p.M = N * p.OH * p.OW; p.K = ks * ks * Cin;
     p.geglu = flags[0]; p.act = flags[1];
     p.ldy = p.geglu ? Cout / 2 : Cout;
     if (flags[2]) { p.res = seth; p.ldres = p.ldy; }
@@ -918,7 +914,12 @@ int sd_igemm_plan(const int* geom, const int* flags, int64_t* out, char* name) {
     if (flags[5] > 0) { p.ln_stat = set; p.ln_parts = flags[5]; p.ln_part_w = (p.K + flags[5] - 1) / flags[5]; p.ln_C = p.K; p.ln_eps = 1e-5f; p.ln_wsum = set; }
     if (flags[8] > 0) { p.gni_part = set; p.gni_S = 1; p.gni_rows = (long)H * W; p.gni_groups = flags[8]; p.gni_eps = 1e-5f; p.gni_gb = set; }
     if (flags[9]) { p.acc_scale = 0.5f; p.bias_scale = 0.5f; }
-    const IGemmPlan pl = igemm2_plan(p, IGemmRequest{flags[6] ? set : nullptr, flags[7] > 0 ? set : nullptr, flags[7]});
+    *problem = p;
+    *rq = IGemmRequest{flags[6] ? set : nullptr, flags[7] > 0 ? set : nullptr, flags[7]};
+    return SD_OK;
+}
+
+static int plan_answer(const IGemmPlan& pl, int64_t* out, char* name) {
     if (pl.kind == kKindBadVariant) return SD_ERR_INVALID;
     const int64_t o[12] = {pl.kind, pl.variant, pl.splits, pl.partial_floats, pl.rowstats, pl.rs_parts, pl.rs_part_w,
                            pl.gnstats, pl.gn_rows, pl.scales_ok, pl.bm, pl.bn};
@@ -927,38 +928,34 @@ int sd_igemm_plan(const int* geom, const int* flags, int64_t* out, char* name) {
     return SD_OK;
 }
 
+int sd_igemm_plan(const int* geom, const int* flags, int64_t* out, char* name) {
+    IGemmParams p;
+    IGemmRequest rq;
+    if (int rc = plan_problem("sd_igemm_plan", geom, flags, out, name, &p, &rq)) return rc;
+    return plan_answer(igemm2_plan(p, rq), out, name);
+}
+
+int sd_conv_plan(const int* geom, const int* flags, int have_fold, int cus, int64_t* out, char* name) {
+    IGemmParams p;
+    IGemmRequest rq;
+    if (int rc = plan_problem("sd_conv_plan", geom, flags, out, name, &p, &rq)) return rc;
+    if (cus < 0) { set_error("sd_conv_plan: bad geometry"); return SD_ERR_INVALID; }
+    return plan_answer(conv_plan(p, have_fold ? p.w : nullptr, rq, cus), out, name);
+}
+
 int sd_halo80_force(int mode) { halo80_force(mode); return SD_OK; }
 
 int sd_halo80_plan(const int* geom, const int* flags, int cus, int64_t* out, char* name) {
-    if (!geom || !flags || !out || !name) { set_error("sd_halo80_plan: null argument"); return SD_ERR_INVALID; }
-    const int N = geom[0], H = geom[1], W = geom[2], Cin = geom[3], Cout = geom[4], ks = geom[5], stride = geom[6], up = geom[7];
-    if (N < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1 || (ks != 1 && ks != 3) || stride < 1 || up < 0 || up > 1 || cus < 0) {
-        set_error("sd_halo80_plan: bad geometry"); return SD_ERR_INVALID;
-    }
-    // the problem as sd_igemm_plan poses it (same geom / flags)
-    float* const set = reinterpret_cast<float*>(8);
-    const half_t* const seth = reinterpret_cast<const half_t*>(set);
-    IGemmParams p{};
-    p.x = seth; p.ldx = Cin; p.w = seth; p.y = reinterpret_cast<half_t*>(set);
-    p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.KS = ks; p.stride = stride; p.up = up;
-    p.pad = geom[8] >= 0 ? geom[8] : (ks == 3 ? 1 : 0);
-    const int IH = H << up, IW = W << up;
-    if (stride == 1) { p.OH = IH; p.OW = IW; }
-    else if (p.pad == 0) { p.OH = (IH + 1 - ks) / stride + 1; p.OW = (IW + 1 - ks) / stride + 1; }
-    else { p.OH = (IH + 2 * p.pad - ks) / stride + 1; p.OW = (IW + 2 * p.pad - ks) / stride + 1; }
-    p.M = N * p.OH * p.OW; p.K = ks * ks * Cin;
-    p.geglu = flags[0]; p.act = flags[1];
-    p.ldy = p.geglu ? Cout / 2 : Cout;
-    if (flags[2]) { p.res = seth; p.ldres = p.ldy; }
-    if (flags[3]) { p.rowadd = set; p.rowadd_ld = Cout; }
-    if (flags[4]) p.bias = set;
-    if (flags[5] > 0) { p.ln_stat = set; p.ln_parts = flags[5]; p.ln_part_w = (p.K + flags[5] - 1) / flags[5]; p.ln_C = p.K; p.ln_eps = 1e-5f; p.ln_wsum = set; }
-    if (flags[8] > 0) { p.gni_part = set; p.gni_S = 1; p.gni_rows = (long)H * W; p.gni_groups = flags[8]; p.gni_eps = 1e-5f; p.gni_gb = set; }
-    if (flags[9]) { p.acc_scale = 0.5f; p.bias_scale = 0.5f; }
-    const Halo80Plan pl = halo80_plan(p, IGemmRequest{flags[6] ? set : nullptr, flags[7] > 0 ? set : nullptr, flags[7]}, cus);
-    const int64_t o[6] = {pl.ok, pl.bn, pl.splits, pl.gnstats, pl.gn_rows, pl.partial_floats};
+    IGemmParams p;
+    IGemmRequest rq;
+    if (int rc = plan_problem("sd_halo80_plan", geom, flags, out, name, &p, &rq)) return rc;
+    if (cus < 0) { set_error("sd_halo80_plan: bad geometry"); return SD_ERR_INVALID; }
+    // the second stage's answer alone: conv_plan without a folded pack, and nothing where the table's row stays
+    const IGemmPlan pl = conv_plan(p, nullptr, rq, cus);
+    const bool ok = pl.kind == kKindHalo80;
+    const int64_t o[6] = {ok, ok ? pl.bn : 0, ok ? pl.splits : 1, ok && pl.gnstats, ok ? pl.gn_rows : 0, ok ? pl.partial_floats : 0};
     for (int i = 0; i < 6; ++i) out[i] = o[i];
-    snprintf(name, 64, "%s", pl.name);
+    snprintf(name, 64, "%s", ok ? pl.name : "");
     return SD_OK;
 }
 
@@ -1074,23 +1071,12 @@ static int conv2d_impl(const void* x, const void* w_oihw, const void* bias_f32, 
     }
     float* partial = nullptr;
     if (!rc) {
-        IGemmParams p;
+        IGemmParams p = conv_problem(N, H, W, Cin, Cout, ksize, stride, upsample2x, ex ? ex->pad : -1);
         p.x = static_cast<const half_t*>(x); p.ldx = Cin;
         p.w = wp; p.bias = bp;
         p.rowadd = static_cast<const float*>(rowadd_f32); p.rowadd_ld = Cout;
         p.res = static_cast<const half_t*>(res);
-        p.N = N; p.H = H; p.W = W; p.Cin = Cin;
-        p.KS = ksize; p.stride = stride; p.up = upsample2x; p.pad = ksize == 3 ? 1 : 0;
-        const int IH = H << upsample2x, IW = W << upsample2x;
-        p.OH = (IH + 2 * p.pad - ksize) / stride + 1;
-        p.OW = (IW + 2 * p.pad - ksize) / stride + 1;
-        if (ex && ex->pad >= 0) {               // output size as op_conv derives it from an explicit padding
-            p.pad = ex->pad;
-            if (stride == 1) { p.OH = IH; p.OW = IW; }
-            else if (p.pad == 0) { p.OH = (IH + 1 - ksize) / stride + 1; p.OW = (IW + 1 - ksize) / stride + 1; }
-            else { p.OH = (IH + 2 * p.pad - ksize) / stride + 1; p.OW = (IW + 2 * p.pad - ksize) / stride + 1; }
-        }
-        p.Cout = Cout; p.M = N * p.OH * p.OW; p.K = (int)K; p.geglu = geglu;
+        p.geglu = geglu;
         const int ocols = geglu ? Cout / 2 : Cout;
         p.ldres = ocols; p.y = static_cast<half_t*>(y); p.ldy = ocols;
         float* gnbuf = nullptr;
@@ -1138,19 +1124,9 @@ static int conv2d_impl(const void* x, const void* w_oihw, const void* bias_f32, 
             SD_HIP_CHECK(hipMemsetAsync(res_bench, 0, (size_t)p.M * ocols * sizeof(half_t), s));
             p.res = res_bench;
         }
-        // as op_conv: the 80-column halo tile is asked first; its plan is reported in the planner's terms
+        // planned as op_conv plans, but without a folded pack: an upsampling launch here runs the 9-tap kernels
         const IGemmRequest rq{nullptr, gnbuf, gn ? gn->groups : ex ? ex->gn_groups : 0};
-        const Halo80Plan hp = halo80_plan(p, rq);
-        IGemmPlan plan;
-        if (hp.ok) {
-            plan.kind = plan.variant = kKindHalo80;
-            plan.splits = hp.splits; plan.partial_floats = hp.partial_floats;
-            plan.bm = 256; plan.bn = hp.bn;
-            plan.gnstats = hp.gnstats; plan.gn_rows = hp.gn_rows;
-            plan.scales_ok = true;
-        } else {
-            plan = igemm2_plan(p, rq);
-        }
+        const IGemmPlan plan = conv_plan(p, nullptr, rq);
         if (ex && !plan.scales_ok && (p.acc_scale != 1.f || p.bias_scale != 1.f)) {
             set_error("sd_op_conv2d_ex: the planned kernel does not take acc_scale / bias_scale"); return SD_ERR_INVALID;
         }
@@ -1188,7 +1164,7 @@ static int conv2d_impl(const void* x, const void* w_oihw, const void* bias_f32, 
         for (int it = 0; it < iters + (ms_out ? 2 : 0) && !rc; ++it) {
             if (ms_out && it == 2) SD_HIP_CHECK(hipEventRecord(e0, s));     // two warm-up launches
             if (wring) p.w = reinterpret_cast<half_t*>(reinterpret_cast<char*>(wring) + wbytes * (size_t)(it % nrot));
-            rc = hp.ok ? launch_halo80(p, hp, partial, s) : launch_igemm2(p, partial, s, &plan);
+            rc = launch_igemm2(p, partial, s, &plan);
         }
         if (ex && ex->ran) {
             const IGemmLaunchNote note = igemm2_last_launch();

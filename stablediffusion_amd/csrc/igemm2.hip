@@ -692,15 +692,29 @@ __global__ __launch_bounds__(256) void splitk_epilogue_gs_kernel(IGemmParams p, 
             float2{pvt + a, q - s * a};
     }
 }
+// Channels per group where an epilogue or the reduction kernel can leave GroupNorm summaries for `groups` groups of Cout
+// channels, else 0: a 16-byte chunk of a row may touch at most two groups
+inline int gn_cpg(int Cout, int groups) {
+    const int cpg = groups > 0 && Cout % groups == 0 ? Cout / groups : 0;
+    return cpg >= 8 || cpg == 4 ? cpg : 0;
+}
 // Rows per block of that kernel for a problem (0: it cannot leave the summaries) and its column block
 inline int splitk_gs_rows(const IGemmParams& p, int groups) {
     const int OHW = p.OH * p.OW;
-    if (groups <= 0 || groups > 256 || p.Cout % groups != 0) return 0;
-    const int cpg = p.Cout / groups;
-    if (!(cpg >= 8 || cpg == 4)) return 0;
+    if (groups > 256 || gn_cpg(p.Cout, groups) == 0) return 0;
     for (int rb = 4; rb <= 16; rb <<= 1)
         if (OHW % rb == 0 && OHW / rb <= 64) return rb;
     return 0;
+}
+// Pixels per GroupNorm summary a launch of bm x bn tiles in `splits` K slices leaves for `groups` groups, 0 when it cannot:
+// from the epilogue of an unsplit launch when every tile lies inside one image and group boundaries fall on tile
+// boundaries (or one tile holds every column), from the split-K reduction kernel when the launch splits.  bm = 0: a
+// kernel without the summary epilogue.  The one statement of the rule: every stage of conv_plan asks here.
+inline int gn_summary_rows(const IGemmParams& p, int bm, int bn, int splits, int groups) {
+    const int cpg = gn_cpg(p.Cout, groups);
+    if (cpg == 0 || bm == 0) return 0;
+    if (splits > 1) return splitk_gs_rows(p, groups);
+    return (p.OH * p.OW) % bm == 0 && (bn % cpg == 0 || p.Cout <= bn) ? bm : 0;
 }
 inline int splitk_gs_cols(const IGemmParams& p) {
     const int cpg = p.Cout / p.gn_groups;
@@ -746,7 +760,7 @@ inline int launch_splitk_epilogue(const IGemmParams& p, const float* partial, in
 // ring.  The XOR swizzle is on the halo pixel index, so the 16 consecutive pixels of an MFMA operand
 // stay conflict-free at every shift.  The 256 pixels are an R x Wt patch (64 / 32 / 16 columns wide,
 // whichever tiles the image), so any H x W that such a patch divides qualifies; 8 waves (4 x 2; 8 x 1 in the 80-column
-// form, which halo80_plan routes: twice the blocks where the wide tiles leave CUs idle).
+// form, which conv_plan routes: twice the blocks where the wide tiles leave CUs idle).
 // ---------------------------------------------------------------------------------------------
 // Width of the 256-pixel patch a block covers: the widest of 64 / 32 / 16 columns that tiles the image
 // (W % Wt == 0 and H % (256 / Wt) == 0); 0 if none does.
@@ -1239,7 +1253,7 @@ int launch_halo(const IGemmParams& p, float* partial, int splits, hipStream_t s)
 // per tap through the parent's three-stage ring.  Four taps per slab do not divide over three stages, so the stage of a
 // step is run-time (one scalar, two vector adds per tap); the waits stay compile-time: they count loads in flight, and
 // those are the parent's (two weight stages ahead, the next halo issued at a slab's first tap).
-// No split-K, row add or residual (neither upsample site has them: upconv_fold_plan refuses).
+// No split-K, row add or residual (neither upsample site has them: conv_plan refuses).
 // ---------------------------------------------------------------------------------------------
 template <int BN>
 __global__ __launch_bounds__(512) void conv3x3_halo_up2x2_kernel(IGemmParams p) {
@@ -1713,17 +1727,14 @@ IGemmPlan igemm2_plan(IGemmParams& p, const IGemmRequest& rq) {
     route();
     // (asked of the problem before the requests below, as op_conv always has)
     pl.scales_ok = !p.geglu && !is_ws(v);
-    // 1. GroupNorm summaries of the output: from the epilogue when every tile lies inside one image and group boundaries
-    //    fall on tile boundaries, from the split-K reduction kernel when the launch splits; a 16-byte chunk may touch at
-    //    most two groups
-    const int G = rq.gn_groups, cpg = G > 0 && p.Cout % G == 0 ? p.Cout / G : 0;
-    if (rq.gnstat && !p.geglu && (cpg >= 8 || cpg == 4)) {
+    // 1. GroupNorm summaries of the output (gn_summary_rows), of the tile the request itself routes to; the
+    //    weight-stationary kernel has no summary epilogue
+    const int G = rq.gn_groups;
+    if (rq.gnstat && !p.geglu && gn_cpg(p.Cout, G)) {
         p.gnstat_out = rq.gnstat; p.gn_groups = G;
         route();
         const Variant& t = kVariants[is_halo(v) && !halo_supported(p) ? kHaloFallback : v];
-        if (is_ws(v)) pl.gn_rows = 0;
-        else if (sp > 1) pl.gn_rows = splitk_gs_rows(p, G);
-        else pl.gn_rows = (p.OH * p.OW) % t.bm == 0 && (t.bn % cpg == 0 || p.Cout <= t.bn) ? t.bm : 0;
+        pl.gn_rows = gn_summary_rows(p, is_ws(v) ? 0 : t.bm, t.bn, sp, G);
         pl.gnstats = pl.gn_rows > 0;
         if (!pl.gnstats) { p.gnstat_out = nullptr; p.gn_groups = 0; }
     }
@@ -1761,32 +1772,30 @@ bool upconv_fold_supported(int N, int H, int W, int Cin, int Cout, long ldx) {
            wrows * 4 * Cin * 2 < (1L << 31) && (long)N * H * W * 4 < (1L << 31);
 }
 
-UpconvFoldPlan upconv_fold_plan(IGemmParams& p, const half_t* w_fold, const IGemmRequest& rq) {
-    UpconvFoldPlan pl;
-    if (!w_fold || p.up != 1 || p.KS != 3 || p.stride != 1 || p.pad != 1 || p.OH != 2 * p.H || p.OW != 2 * p.W ||
-        p.K != 9 * p.Cin || p.geglu || p.act || p.rowadd || p.res || p.ln_stat || p.gni_part || rq.rowstat ||
-        !upconv_fold_supported(p.N, p.H, p.W, p.Cin, p.Cout, p.ldx))
-        return pl;
-    pl.ok = true;
-    pl.bn = p.Cout % 160 == 0 ? 160 : 128;
-    p.w = w_fold; p.K = 4 * p.Cin; p.KS = 2;
-    // GroupNorm summaries under the planner's conditions for an unsplit launch (igemm2_plan, step 1): one per (patch,
-    // parity) = 256 output pixels of one image; group boundaries on tile boundaries
-    const int G = rq.gn_groups, cpg = G > 0 && p.Cout % G == 0 ? p.Cout / G : 0;
-    p.gnstat_out = nullptr; p.gn_groups = 0;
-    if (rq.gnstat && (cpg >= 8 || cpg == 4) && (pl.bn % cpg == 0 || p.Cout <= pl.bn)) {
-        p.gnstat_out = rq.gnstat; p.gn_groups = G;
-        pl.gnstats = true; pl.gn_rows = 256;
-    }
-    snprintf(pl.name, sizeof(pl.name), "conv3x3_halo_kernel<%d>/up2x2", pl.bn);
+// The plan of a launch outside the table (stages 1 and 2 of conv_plan): 256-row tiles, split over K or not, whose kernel
+// honours the output scales and writes no row statistics; p's statistics outputs are set to what the launch will fill
+// (what the table stage granted for its own tile, when it was asked first, is withdrawn).
+static IGemmPlan off_table_plan(IGemmParams& p, const IGemmRequest& rq, int kind, int bn, int splits, const char* name) {
+    IGemmPlan pl;
+    pl.kind = pl.variant = kind;
+    pl.splits = splits;
+    pl.partial_floats = splits > 1 ? (long)splits * p.M * p.Cout : 0;
+    pl.bm = 256; pl.bn = bn;
+    pl.rs_part_w = p.Cout;
+    pl.scales_ok = true;
+    p.gnstat_out = nullptr; p.gn_groups = 0; p.rowstat_out = nullptr;
+    pl.gn_rows = rq.gnstat ? gn_summary_rows(p, pl.bm, bn, splits, rq.gn_groups) : 0;
+    pl.gnstats = pl.gn_rows > 0;
+    if (pl.gnstats) { p.gnstat_out = rq.gnstat; p.gn_groups = rq.gn_groups; }
+    snprintf(pl.name, sizeof(pl.name), "%s", name);
     return pl;
 }
 
-int launch_upconv_fold(const IGemmParams& p, const UpconvFoldPlan& plan, hipStream_t s) {
-    if (!plan.ok || p.KS != 2 || p.K != 4 * p.Cin || halo_patch_width(p.H, p.W) == 0) {
-        set_error("launch_upconv_fold: not a folded-upsample problem (upconv_fold_plan decides)"); return 1;
-    }
-    return plan.bn == 160 ? launch_up2x2_t<160>(p, s) : launch_up2x2_t<128>(p, s);
+// Stage 1 of conv_plan: whether the folded upsample takes p (the 9-tap problem as posed, up = 1) on the pack w_fold.
+static bool upconv_fold_takes(const IGemmParams& p, const half_t* w_fold, const IGemmRequest& rq) {
+    return w_fold && p.up == 1 && p.KS == 3 && p.stride == 1 && p.pad == 1 && p.OH == 2 * p.H && p.OW == 2 * p.W &&
+           p.K == 9 * p.Cin && !p.geglu && !p.act && !p.rowadd && !p.res && !p.ln_stat && !p.gni_part && !rq.rowstat &&
+           upconv_fold_supported(p.N, p.H, p.W, p.Cin, p.Cout, p.ldx);
 }
 
 void halo80_force(int mode) { g_halo80_mode = mode < -1 || mode > 1 ? -1 : mode; }
@@ -1804,7 +1813,7 @@ static int device_cus() {
     return cus;
 }
 
-// The 80-column halo tile, decided ahead of igemm2_plan (which answers every problem as it always has).
+// Stage 2 of conv_plan: the 80-column halo tile, ahead of the table stage (which answers every problem as it always has).
 // The kernel takes: 3x3, stride 1, pad 1, no upsample, halo_supported, no GroupNorm fused into the input, no LayerNorm
 // fold, no row statistics.  Split-K in that form: the fewest slices that put a block on every CU, while the longest
 // slice keeps two slabs.
@@ -1818,55 +1827,47 @@ static int device_cus() {
 // wide ones (0.57 us against 0.53 us at 128 columns: every wave reads all 80 weight rows from LDS for 20 MFMAs) and less
 // per launch, so it loses beyond 10 slabs (+7 % at 20, +11 % at 30); with two slices to fill the chip (2048 x 1280) it
 // wins 4 % at 10 slabs and loses 7-11 % deeper, and is not taken.
-Halo80Plan halo80_plan(IGemmParams& p, const IGemmRequest& rq, int cus) {
-    Halo80Plan pl;
-    static const bool off = getenv("SD_NO_HALO80") != nullptr;         // A/B switch: every conv as igemm2_plan says
+// What the stage says of p before the table has answered: 0 the launch is not its, 1 it is (in *splits slices), -1 it
+// is where the table stage runs a halo or a streamed tile (halo80_takes_over).
+static int halo80_wants(const IGemmParams& p, const IGemmRequest& rq, int cus, int* splits) {
+    static const bool off = getenv("SD_NO_HALO80") != nullptr;         // A/B switch: every conv as the table stage says
     const int mode = g_halo80_mode.load();
-    if (off || mode == 0) return pl;
+    *splits = 1;
+    if (off || mode == 0) return 0;
     if (p.KS != 3 || p.stride != 1 || p.pad != 1 || p.up != 0 || p.gni_part || p.ln_stat || rq.rowstat ||
         !igemm2_supported(p) || !halo_supported(p))
-        return pl;
+        return 0;
     if (cus <= 0) cus = device_cus();
     const long tiles = (long)(p.M / 256) * cdiv(p.Cout, 80);
     const int nslab = p.Cin / 64;
-    int sp = 1;
     if (mode < 0) {
-        if (g_force_variant.load() >= 0 || valid_id(rq.hint_variant)) return pl;      // a forced or hinted tile runs as itself
-        if (p.Cout % 80 != 0 || nslab > 10 || tiles > cus || tiles * 4 <= (long)cus * 3) return pl;
-        // (what it takes over: a halo or a streamed tile of the table -- a 3x3 problem the planner hands to the old igemm
-        // kernel is not one the LDS-DMA kernels take)
-        IGemmParams q = p;
-        const IGemmPlan cur = igemm2_plan(q, rq);
-        if (!valid_id(cur.kind) || (kVariants[cur.kind].family != Family::Halo && kVariants[cur.kind].family != Family::Tile))
-            return pl;
-    } else if (!rq.no_workspace) {
-        while (tiles * sp < cus && sp < 8 && cdiv(nslab, sp + 1) >= 2) ++sp;
+        if (g_force_variant.load() >= 0 || valid_id(rq.hint_variant)) return 0;       // a forced or hinted tile runs as itself
+        if (p.Cout % 80 != 0 || nslab > 10 || tiles > cus || tiles * 4 <= (long)cus * 3) return 0;
+        return -1;
     }
-    pl.ok = true;
-    pl.bn = 80;
-    pl.splits = sp;
-    pl.partial_floats = sp > 1 ? (long)sp * p.M * p.Cout : 0;
-    // GroupNorm summaries under the planner's conditions (igemm2_plan, step 1): from the epilogue of an unsplit launch when
-    // group boundaries fall on tile boundaries, from the split-K reduction otherwise
-    const int G = rq.gn_groups, cpg = G > 0 && p.Cout % G == 0 ? p.Cout / G : 0;
-    p.gnstat_out = nullptr; p.gn_groups = 0; p.rowstat_out = nullptr;
-    if (rq.gnstat && (cpg >= 8 || cpg == 4)) {
-        p.gnstat_out = rq.gnstat; p.gn_groups = G;
-        pl.gn_rows = sp > 1 ? splitk_gs_rows(p, G) : (80 % cpg == 0 || p.Cout <= 80 ? 256 : 0);
-        pl.gnstats = pl.gn_rows > 0;
-        if (!pl.gnstats) { p.gnstat_out = nullptr; p.gn_groups = 0; }
-    }
-    snprintf(pl.name, sizeof(pl.name), "conv3x3_halo_kernel<80>");
-    return pl;
+    if (!rq.no_workspace)
+        while (tiles * *splits < cus && *splits < 8 && cdiv(nslab, *splits + 1) >= 2) ++*splits;
+    return 1;
+}
+// (a 3x3 problem the table hands to the old igemm kernel is not one the LDS-DMA kernels take)
+static bool halo80_takes_over(const IGemmPlan& table) {
+    return valid_id(table.kind) && (kVariants[table.kind].family == Family::Halo || kVariants[table.kind].family == Family::Tile);
 }
 
-int launch_halo80(const IGemmParams& p, const Halo80Plan& plan, float* partial, hipStream_t s) {
-    t_note = IGemmLaunchNote();
-    if (!plan.ok || p.KS != 3 || p.stride != 1 || p.up != 0 || p.gni_part || p.ln_stat || !halo_supported(p) ||
-        (plan.splits > 1 && !partial)) {
-        set_error("launch_halo80: not a problem of the 80-column halo tile (halo80_plan decides)"); return 1;
+IGemmPlan conv_plan(IGemmParams& p, const half_t* w_fold, const IGemmRequest& rq, int cus) {
+    if (upconv_fold_takes(p, w_fold, rq)) {
+        p.w = w_fold; p.K = 4 * p.Cin; p.KS = 2;
+        // (summaries: one per (patch, parity) = 256 output pixels of one image)
+        const int bn = p.Cout % 160 == 0 ? 160 : 128;
+        return off_table_plan(p, rq, kKindUpconvFold, bn, 1, bn == 160 ? "conv3x3_halo_kernel<160>/up2x2" : "conv3x3_halo_kernel<128>/up2x2");
     }
-    return launch_halo_t<80, false, true>(p, partial, plan.splits, s);
+    int splits;
+    const int h80 = halo80_wants(p, rq, cus, &splits);
+    if (h80 <= 0) {
+        const IGemmPlan table = igemm2_plan(p, rq);
+        if (h80 == 0 || !halo80_takes_over(table)) return table;
+    }
+    return off_table_plan(p, rq, kKindHalo80, 80, splits, "conv3x3_halo_kernel<80>");
 }
 
 IGemmLaunchNote igemm2_last_launch() { return t_note; }
@@ -1875,6 +1876,19 @@ int igemm2_max_ln_parts() { return kMaxLnParts; }
 
 int launch_igemm2(const IGemmParams& p, float* partial, hipStream_t s, const IGemmPlan* plan) {
     t_note = IGemmLaunchNote();
+    if (plan && plan->kind == kKindUpconvFold) {
+        if (p.KS != 2 || p.K != 4 * p.Cin || halo_patch_width(p.H, p.W) == 0) {
+            set_error("launch_upconv_fold: not a folded-upsample problem (upconv_fold_plan decides)"); return 1;
+        }
+        return plan->bn == 160 ? launch_up2x2_t<160>(p, s) : launch_up2x2_t<128>(p, s);
+    }
+    if (plan && plan->kind == kKindHalo80) {
+        if (p.KS != 3 || p.stride != 1 || p.up != 0 || p.gni_part || p.ln_stat || !halo_supported(p) ||
+            (plan->splits > 1 && !partial)) {
+            set_error("launch_halo80: not a problem of the 80-column halo tile (halo80_plan decides)"); return 1;
+        }
+        return launch_halo_t<80, false, true>(p, partial, plan->splits, s);
+    }
     // the streamed tiles are where a folded LayerNorm lands when igemm3 / pgemm / wsgemm decline it, and they load
     // kMaxLnParts partials per row whatever ln_parts says: a longer layout would be normalised from its first 20 parts
     if (p.ln_stat && (p.ln_parts < 1 || p.ln_parts > kMaxLnParts)) {

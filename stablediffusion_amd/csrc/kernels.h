@@ -67,6 +67,22 @@ struct IGemmParams {
     //      kernels and their split-K reductions; IGemmPlan::scales_ok).  Scales are powers of two.  See VAE::run_encode. ----
     float acc_scale = 1.f, bias_scale = 1.f;
 };
+// The geometry of a convolution over an [N, H, W, Cin] input (nearest-2x upsampled first when up = 1), everything else
+// left zero: pad < 0 takes the kernel size's default (1 for 3x3, 0 for 1x1); an explicit pad of 0 under a stride is the
+// VAE encoder's Downsample2D (F.pad (0,1,0,1), then the strided conv with padding 0: the right / bottom zero column is
+// the gather's ordinary bounds check).  K = ks ks Cin; a caller whose pack pads K sets its own.
+inline IGemmParams conv_problem(int N, int H, int W, int Cin, int Cout, int ks, int stride, int up, int pad) {
+    IGemmParams p{};
+    p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout;
+    p.KS = ks; p.stride = stride; p.up = up;
+    p.pad = pad >= 0 ? pad : (ks == 3 ? 1 : 0);
+    const int IH = H << up, IW = W << up;
+    if (stride == 1) { p.OH = IH; p.OW = IW; }
+    else if (pad == 0) { p.OH = (IH + 1 - ks) / stride + 1; p.OW = (IW + 1 - ks) / stride + 1; }
+    else { p.OH = (IH + 2 * p.pad - ks) / stride + 1; p.OW = (IW + 2 * p.pad - ks) / stride + 1; }
+    p.M = N * p.OH * p.OW; p.K = ks * ks * Cin;
+    return p;
+}
 // Whether launch_igemm2 can apply a GroupNorm of `groups` groups to this problem's input (p.gni_* set by the caller).
 bool igemm2_gn_fusable(const IGemmParams& p, int groups);
 int launch_igemm(const IGemmParams& p, hipStream_t s);
@@ -86,11 +102,12 @@ struct IGemmRequest {
 };
 // The tuned table's row for a plain pointwise problem (ks 1, stride 1, no upsample, no GEGLU), if it has one.
 bool igemm2_tuned_pointwise(int M, int N, int K, int* variant, int* splits);
-// How one launch runs, decided once (igemm2_plan) and handed to launch_igemm2.
+// How one launch runs, decided once (conv_plan; igemm2_plan for a linear) and handed to launch_igemm2.
 constexpr int kKindPgemmGeglu = 100;    // geglu_persist_kernel (pgemm.hip)
 constexpr int kKindIgemm1 = -1;         // not an LDS-DMA problem (!igemm2_supported): launch_igemm
 constexpr int kKindBadVariant = -2;     // a forced variant id outside the table: the launch fails
-constexpr int kKindHalo80 = 80;         // conv3x3_halo_kernel<80>, outside the planner (halo80_plan); only sd_op_conv2d_ex reports it
+constexpr int kKindHalo80 = 80;         // conv3x3_halo_kernel<80>: conv_plan's second stage, not a row of the table
+constexpr int kKindUpconvFold = 220;    // conv3x3_halo_up2x2_kernel on the folded pack: conv_plan's first stage
 struct IGemmPlan {
     int kind = kKindIgemm1;         // the kernel that runs: a variant id of igemm2.hip's table, or one of the above
     int variant = -1;               // the tile the choice landed on (differs from kind where pgemm / igemm3 / its fallback take over)
@@ -104,50 +121,31 @@ struct IGemmPlan {
     bool scales_ok = false;         // acc_scale / bias_scale are honoured (not the GEGLU / weight-stationary forms)
     char name[64] = "";             // the kernel as rocprofv3 names it
 };
-// Plans the launch of p.  Requests are resolved in the order GroupNorm summaries, row statistics, workspace (each granted
-// one can change the tile, and with it the next answer); p.gnstat_out / p.gn_groups / p.rowstat_out are set to the
-// buffers the launch will fill and left null for the rest.  Host code only.
+// The table stage: plans the launch of p among the rows of the variant table.  Requests are resolved in the order GroupNorm
+// summaries, row statistics, workspace (each granted one can change the tile, and with it the next answer);
+// p.gnstat_out / p.gn_groups / p.rowstat_out are set to the buffers the launch will fill and left null for the rest.
+// Host code only.  A linear calls it directly; a convolution goes through conv_plan.
 IGemmPlan igemm2_plan(IGemmParams& p, const IGemmRequest& rq = IGemmRequest());
-// Runs p as planned; plans it itself (requests = p's own rowstat_out / gnstat_out) when no plan is passed.  A plan that
-// splits K needs `partial` of plan->partial_floats; without it the launch is planned again and runs unsplit.
+// The whole decision for a convolution launch, the one predicate of the planning and the live pass.  In this order:
+//   1. the folded upsample (kKindUpconvFold), when p.up == 1 and a folded pack is given: nearest-2x upsample + 3x3 conv
+//      run as four 2x2 convs on the input map, one per output parity, on weights folded at pack time (launch_fold_upconv;
+//      conv3x3_halo_up2x2_kernel): 4/9 of the 9-tap kernel's MACs.  Takes what upconv_fold_supported admits; row add,
+//      residual, GEGLU, activation, LayerNorm fold, fused input GroupNorm and row statistics stay on the 9-tap kernels.
+//      p is rewritten to the folded problem: w = w_fold, K = 4 Cin, KS = 2;
+//   2. the 80-column halo tile (kKindHalo80; conv3x3_halo_kernel<80>: 256 pixels x 80 columns, waves 8 x 1): twice the
+//      blocks of the 160-column tile on the same halo tiles, for the launches whose 128- / 160-column grid leaves CUs idle
+//      (M = 8192 x Cout = 640 is 32 x 5 tiles of 128 columns on 256 CUs, and 32 x 8 of these).  cus: the CU count its
+//      rule fills (0: the device's).  SD_NO_HALO80=1 (read once) turns it off.  The rule is stated at the definition;
+//   3. the table (igemm2_plan), whose answer the rule of stage 2 reads: it is computed once per launch.
+// Every route sets p.gnstat_out / p.gn_groups / p.rowstat_out to what the launch will fill.  Host only, pure.
+IGemmPlan conv_plan(IGemmParams& p, const half_t* w_fold, const IGemmRequest& rq, int cus = 0);
+// Runs p as planned, every kind of plan; plans it itself by the table (requests = p's own rowstat_out / gnstat_out) when
+// no plan is passed.  A table plan that splits K needs `partial` of plan->partial_floats; without it the launch is
+// planned again and runs unsplit.
 int launch_igemm2(const IGemmParams& p, float* partial, hipStream_t s, const IGemmPlan* plan = nullptr);
-// Nearest-2x upsample + 3x3 conv run as four 2x2 convs on the input map, one per output parity, on weights folded at
-// pack time (launch_fold_upconv; conv3x3_halo_up2x2_kernel in igemm2.hip): 4/9 of the 9-tap kernel's MACs.  Decided
-// outside igemm2_plan, which answers every problem as it always has.
-// The shape part of the decision (and SD_NO_UPCONV_FOLD unset): Cin % 64, Cout % 8, a 256-pixel patch (64 / 32 / 16
-// columns wide) tiles the H x W INPUT map, operands within 2 GB.  Host only.
+// The shape part of stage 1 (and SD_NO_UPCONV_FOLD unset): Cin % 64, Cout % 8, a 256-pixel patch (64 / 32 / 16 columns
+// wide) tiles the H x W INPUT map, operands within 2 GB.  Host only.
 bool upconv_fold_supported(int N, int H, int W, int Cin, int Cout, long ldx);
-struct UpconvFoldPlan {
-    bool ok = false;                // the folded kernel runs this launch
-    int bn = 0;                     // its column tile
-    bool gnstats = false;           // the epilogue leaves the GroupNorm summaries asked for
-    int gn_rows = 0;                // output pixels per summary (one per patch and parity)
-    char name[64] = "";             // profiler row: "conv3x3_halo_kernel<BN>/up2x2"
-};
-// The one predicate of the dry and the live pass.  p = the 9-tap problem as op_conv poses it (up = 1), w_fold = the
-// folded pack or null; when the plan is ok, p is rewritten to the folded problem (w = w_fold, K = 4 Cin, KS = 2,
-// gnstat_out / gn_groups = what the launch will fill).  Refuses row add, residual, GEGLU, activation, LayerNorm fold,
-// fused input GroupNorm and row statistics: those stay on the 9-tap kernels.
-UpconvFoldPlan upconv_fold_plan(IGemmParams& p, const half_t* w_fold, const IGemmRequest& rq);
-int launch_upconv_fold(const IGemmParams& p, const UpconvFoldPlan& plan, hipStream_t s);
-// The 80-column form of the halo kernel (conv3x3_halo_kernel<80>: 256 pixels x 80 columns, waves 8 x 1): twice the
-// blocks of the 160-column tile on the same halo tiles, for the launches whose 128- / 160-column grid leaves CUs idle
-// (M = 8192 x Cout = 640 is 32 x 5 tiles of 128 columns on 256 CUs, and 32 x 8 of these).  Decided outside igemm2_plan,
-// like the folded upsample.
-struct Halo80Plan {
-    bool ok = false;                // the 80-column kernel runs this launch
-    int bn = 0;                     // its column tile (80)
-    int splits = 1;                 // split-K slices
-    long partial_floats = 0;        // fp32 workspace the caller passes as `partial` (0: none)
-    bool gnstats = false;           // the epilogue, or the split-K reduction, leaves the GroupNorm summaries asked for
-    int gn_rows = 0;                // pixels per summary
-    char name[64] = "";             // profiler row: "conv3x3_halo_kernel<80>"
-};
-// The one predicate of the dry and the live pass; host only, pure.  p = the problem as op_conv poses it; when the plan
-// is ok, p.gnstat_out / p.gn_groups are set to what the launch will fill.  cus: the CU count the rule fills (0: the
-// device's).  SD_NO_HALO80=1 (read once) turns it off.  The rule is stated at the definition (igemm2.hip).
-Halo80Plan halo80_plan(IGemmParams& p, const IGemmRequest& rq, int cus = 0);
-int launch_halo80(const IGemmParams& p, const Halo80Plan& plan, float* partial, hipStream_t s);
 // tests / tools: -1 the rule, 0 never, 1 whenever the kernel takes the problem (split-K until the grid covers the CUs)
 void halo80_force(int mode);
 // The folded pack of a [O][I][3][3] fp16 weight: four parity panels (dy, dx), each [rows][4 I] with rows = O padded

@@ -408,34 +408,47 @@ void ctx_tap_f32(Ctx& c, const std::string& name, const float* p, int rows, int 
 }
 
 // -------------------------------------------------------------------------------------------- ops
+// The profiler row of a convolution launch: its name and the FLOPs / bytes it is charged.  cin = the channels the weights
+// really have (p.Cin is the padded K of a pointwise launch).  SD_PROF_SHAPES=1 (tools/profile_layers.py): one row per
+// (kernel or tile variant, split-K, problem shape, fused extras) instead of one per kernel instantiation.
+struct ConvProfRow { char name[64]; double flops, bytes; };
+static ConvProfRow conv_prof_row(const IGemmPlan& plan, const IGemmParams& p, int cin) {
+    static const bool by_shape = getenv("SD_PROF_SHAPES") != nullptr;
+    ConvProfRow r;
+    const bool fold = plan.kind == kKindUpconvFold;
+    if (!by_shape || plan.kind == kKindIgemm1) {
+        snprintf(r.name, sizeof(r.name), "%s", plan.name);
+    } else {
+        char kernel[24];
+        if (fold) snprintf(kernel, sizeof(kernel), "up2x2<%d>", plan.bn);
+        else if (plan.kind == kKindHalo80) snprintf(kernel, sizeof(kernel), "h80/k%d", plan.splits);
+        else snprintf(kernel, sizeof(kernel), "%s%d/k%d", plan.kind == kKindPgemmGeglu ? "pg" : "v", plan.variant, plan.splits);
+        snprintf(r.name, sizeof(r.name), "%s %dx%dx%d ks%d%s%s%s%s%s%s", kernel, p.M, p.Cout, p.K, p.KS, p.res ? " res" : "",
+                 p.geglu ? " geglu" : "", p.ln_stat ? " ln" : "", p.rowstat_out ? " rs" : "", p.gnstat_out ? " gs" : "",
+                 p.gni_part ? " gn" : "");
+    }
+    // the FLOPs executed: the folded upsample (KS = 2) runs 4 taps, where the 9-tap form of the same launch counts 9/4 of
+    // them, and reads four parity panels of K = 4 Cin weights per row
+    const double weights = (fold ? 4.0 : 1.0) * p.Cout * p.K;
+    const double out_cols = p.geglu ? p.Cout / 2 : p.Cout;
+    r.flops = 2.0 * p.M * p.Cout * (double)(p.KS * p.KS) * cin;
+    r.bytes = 2.0 * ((double)p.N * p.H * p.W * p.Cin + weights + (double)p.M * out_cols * (p.res ? 2 : 1));
+    return r;
+}
+
 void op_conv(Ctx& c, const ConvW& w, View x, int N, int H, int W, View y, int stride, int up,
              const float* rowadd, int rowadd_ld, const View* res, int geglu, int pad, int act, const ConvFuse* fuse) {
     const RowStat* ln_in = fuse ? fuse->ln_in : nullptr;
     const float ln_eps = fuse ? fuse->ln_eps : 0.f;
     RowStat* stat_out = fuse ? fuse->stat_out : nullptr;
     GnStatBuf* gn_out = fuse ? fuse->gn_out : nullptr;
-    IGemmParams p;
+    IGemmParams p = conv_problem(N, H, W, w.ks == 1 ? (int)w.K : w.cin, w.cout, w.ks, stride, up, pad);
+    p.K = (int)w.K;         // (the pack's K)
     p.x = x.p; p.ldx = x.ld;
     p.w = w.w; p.bias = w.bias;
     p.rowadd = rowadd; p.rowadd_ld = rowadd_ld;
     p.res = res ? res->p : nullptr; p.ldres = res ? res->ld : 0;
     p.y = y.p; p.ldy = y.ld;
-    p.N = N; p.H = H; p.W = W; p.Cin = (w.ks == 1) ? (int)w.K : w.cin;
-    p.KS = w.ks; p.stride = stride; p.up = up;
-    p.pad = pad >= 0 ? pad : (w.ks == 3 ? 1 : 0);
-    const int IH = H << up, IW = W << up;
-    if (stride == 1) {
-        p.OH = IH; p.OW = IW;
-    } else if (p.pad == 0) {
-        // VAE encoder Downsample2D: F.pad (0,1,0,1) then stride-2 conv with padding 0 -> the
-        // right / bottom zero column is the gather's ordinary bounds check.
-        p.OH = (IH + 1 - w.ks) / stride + 1; p.OW = (IW + 1 - w.ks) / stride + 1;
-    } else {
-        p.OH = (IH + 2 * p.pad - w.ks) / stride + 1; p.OW = (IW + 2 * p.pad - w.ks) / stride + 1;
-    }
-    p.Cout = w.cout;
-    p.M = N * p.OH * p.OW;
-    p.K = (int)w.K;
     p.geglu = geglu;
     p.act = act;
     if (ln_in) {
@@ -449,67 +462,12 @@ void op_conv(Ctx& c, const ConvW& w, View x, int N, int H, int W, View y, int st
         if (c.dry) p.gni_part = reinterpret_cast<const float*>(8);      // planning pass: only "is set" matters (tile choice)
     }
     if (fuse && (fuse->acc_scale != 1.f || fuse->bias_scale != 1.f)) { p.acc_scale = fuse->acc_scale; p.bias_scale = fuse->bias_scale; }
-    // one plan per launch: the tile, what the epilogue leaves of the requested statistics, the workspace, the name
+    // one plan per launch, the same in the planning and the live pass: the kernel (folded upsample, 80-column halo tile or
+    // a row of the table), what it leaves of the requested statistics, the workspace, the name
     IGemmRequest rq{stat_out ? stat_out->p : nullptr, gn_out ? gn_out->buf : nullptr, fuse ? fuse->gn_groups : 0};
     if (fuse) { rq.hint_variant = fuse->tile_variant; rq.hint_splits = fuse->tile_splits; }
-    if (fuse && fuse->fold_ran) *fuse->fold_ran = 0;
-    // Upsample + 3x3 conv on the folded weights (four 2x2 parity convs, 4/9 of the MACs) where the input map admits a
-    // patch: decided here, ahead of the planner, by the one predicate of the dry and the live pass
-    if (up == 1 && w.w_up) {
-        const UpconvFoldPlan fp = upconv_fold_plan(p, w.w_up, rq);
-        if (fp.ok) {
-            if (gn_out) {
-                gn_out->st = GnStats();
-                if (fp.gnstats) { gn_out->st.part = gn_out->buf; gn_out->st.rows = fp.gn_rows; gn_out->st.S = p.OH * p.OW / fp.gn_rows; }
-            }
-            if (fuse && fuse->fold_ran) *fuse->fold_ran = 1;
-            if (c.dry || c.err) return;
-            if (prof_enabled()) {
-                const char* name = fp.name;
-                static const bool by_shape = getenv("SD_PROF_SHAPES") != nullptr;
-                char nbuf[64];
-                if (by_shape) {
-                    snprintf(nbuf, sizeof(nbuf), "up2x2<%d> %dx%dx%d ks%d%s", fp.bn, p.M, p.Cout, p.K, p.KS, p.gnstat_out ? " gs" : "");
-                    name = nbuf;
-                }
-                // the FLOPs executed: 4 taps (the 9-tap form of the same launch counts 9/4 of them)
-                prof_open(c.stream, name, 2.0 * p.M * w.cout * 4.0 * w.cin,
-                          2.0 * ((double)N * H * W * w.cin + 16.0 * w.cout * w.cin + (double)p.M * w.cout));
-            }
-            c.err = launch_upconv_fold(p, fp, c.stream);
-            prof_close(c.stream);
-            return;
-        }
-    }
-    // The 80-column halo tile where the planner's halo grid leaves CUs idle: asked first, by the one predicate of the dry
-    // and the live pass (its split-K workspace is planned in both)
-    if (w.ks == 3 && stride == 1 && up == 0 && !geglu && !act) {
-        const Halo80Plan hp = halo80_plan(p, rq);
-        if (hp.ok) {
-            if (gn_out) {
-                gn_out->st = GnStats();
-                if (hp.gnstats) { gn_out->st.part = gn_out->buf; gn_out->st.rows = hp.gn_rows; gn_out->st.S = p.OH * p.OW / hp.gn_rows; }
-            }
-            float* partial = hp.partial_floats > 0 ? c.arena->alloc_f(hp.partial_floats) : nullptr;
-            if (c.dry || c.err) return;
-            if (prof_enabled()) {
-                const char* name = hp.name;
-                static const bool by_shape = getenv("SD_PROF_SHAPES") != nullptr;
-                char nbuf[64];
-                if (by_shape) {
-                    snprintf(nbuf, sizeof(nbuf), "h80/k%d %dx%dx%d ks%d%s%s", hp.splits, p.M, p.Cout, p.K, p.KS, res ? " res" : "",
-                             p.gnstat_out ? " gs" : "");
-                    name = nbuf;
-                }
-                prof_open(c.stream, name, 2.0 * p.M * w.cout * 9.0 * w.cin,
-                          2.0 * ((double)N * H * W * w.cin + (double)w.cout * w.K + (double)p.M * w.cout * (res ? 2 : 1)));
-            }
-            c.err = launch_halo80(p, hp, partial, c.stream);
-            prof_close(c.stream);
-            return;
-        }
-    }
-    const IGemmPlan plan = igemm2_plan(p, rq);
+    const IGemmPlan plan = conv_plan(p, up == 1 ? w.w_up : nullptr, rq);
+    if (fuse && fuse->fold_ran) *fuse->fold_ran = plan.kind == kKindUpconvFold;
     const bool v2 = plan.kind != kKindIgemm1;
     if ((p.acc_scale != 1.f || p.bias_scale != 1.f) && !plan.scales_ok) { set_error("op_conv: output scaling needs the LDS-DMA kernels (not GEGLU / weight-stationary)"); c.err = 1; return; }
     if (ln_in && !v2) { set_error("op_conv: the LayerNorm fold needs the LDS-DMA kernel"); c.err = 1; return; }
@@ -523,22 +481,8 @@ void op_conv(Ctx& c, const ConvW& w, View x, int N, int H, int W, View y, int st
     float* partial = plan.partial_floats > 0 ? c.arena->alloc_f(plan.partial_floats) : nullptr;
     if (c.dry || c.err) return;
     if (prof_enabled()) {
-        const double kreal = (double)w.ks * w.ks * w.cin;
-        const double in_px = (double)N * H * W;
-        const char* name = plan.name;
-        // SD_PROF_SHAPES=1 (tools/profile_layers.py): one row per (tile variant, split-K, problem shape,
-        // fused extras) instead of one per kernel instantiation
-        static const bool by_shape = getenv("SD_PROF_SHAPES") != nullptr;
-        char nbuf[64];
-        if (v2 && by_shape) {
-            snprintf(nbuf, sizeof(nbuf), "%s%d/k%d %dx%dx%d ks%d%s%s%s%s%s%s", plan.kind == kKindPgemmGeglu ? "pg" : "v", plan.variant,
-                     plan.splits, p.M, p.Cout, p.K, p.KS, res ? " res" : "", geglu ? " geglu" : "", p.ln_stat ? " ln" : "",
-                     p.rowstat_out ? " rs" : "", p.gnstat_out ? " gs" : "", p.gni_part ? " gn" : "");
-            name = nbuf;
-        }
-        prof_open(c.stream, name, 2.0 * p.M * w.cout * kreal,
-                  2.0 * (in_px * (w.ks == 1 ? (double)w.K : w.cin) + (double)w.cout * w.K +
-                         (double)p.M * (geglu ? w.cout / 2 : w.cout) * (res ? 2 : 1)));
+        const ConvProfRow row = conv_prof_row(plan, p, w.cin);
+        prof_open(c.stream, row.name, row.flops, row.bytes);
     }
     c.err = launch_igemm2(p, partial, c.stream, &plan);
     prof_close(c.stream);
@@ -577,10 +521,9 @@ void op_gn_conv(Ctx& c, const NormW& n, const ConvW& w, View x, int N, int H, in
     static const bool off = getenv("SD_GN_FUSE") == nullptr || getenv("SD_NO_GN_FUSE") != nullptr;
     const long HW = (long)H * W;
     // the problem as op_conv will pose it (stride 1, no upsample: the only form that follows a GroupNorm)
-    IGemmParams q;
-    q.x = x.p; q.ldx = x.ld; q.N = N; q.H = H; q.W = W; q.Cin = (w.ks == 1) ? (int)w.K : w.cin;
-    q.KS = w.ks; q.stride = 1; q.up = 0; q.pad = w.ks == 3 ? 1 : 0; q.OH = H; q.OW = W; q.Cout = w.cout;
-    q.M = N * H * W; q.K = (int)w.K;
+    IGemmParams q = conv_problem(N, H, W, w.ks == 1 ? (int)w.K : w.cin, w.cout, w.ks, 1, 0, -1);
+    q.K = (int)w.K;
+    q.x = x.p; q.ldx = x.ld;
     const bool fused = !off && n.gb && n.C == q.Cin && igemm2_gn_fusable(q, G);
     if (!fused) {
         const size_t mk = c.arena->mark();
