@@ -794,6 +794,15 @@ int sd_op_unet_conv_in(const void* x_nchw, const void* w_oihw, const void* bias,
 int sd_op_unet_conv_out(const void* x_nhwc, const void* gamma, const void* beta, int groups, float eps, int silu,
                         const void* w_oihw, const void* bias, void* y_nchw, int N, int H, int W, int C, int Cout, int iters,
                         float* ms_per_launch, void* stream);
+/* sd_op_unet_conv_out with the operands the UNet gives conv_tail_kernel (sd_op_unet_conv_out is this with ldx = C and no
+ * summaries): x_nhwc rows ldx >= C halves apart (ldx % 8 == 0; columns from C on are never read); summaries NULL (a
+ * statistics pass of its own) or device floats [N][S][groups][2] = (mean, M2) of every tile of `rows` consecutive pixels x
+ * group, the last tile holding the remainder, as a producing convolution's epilogue leaves them: the kernel merges them in
+ * its prologue.  SD_ERR_INVALID with nothing launched unless (S - 1) rows < H W <= S rows, and for the shapes
+ * sd_op_unet_conv_out refuses.  iters / ms_per_launch as sd_op_unet_conv_in (0 / NULL: one launch, not timed). */
+int sd_op_unet_conv_out_ex(const void* x_nhwc, int64_t ldx, const void* gamma, const void* beta, int groups, float eps, int silu,
+                           const void* w_oihw, const void* bias, void* y_nchw, int N, int H, int W, int C, int Cout,
+                           const float* summaries, int S, int64_t rows, int iters, float* ms_per_launch, void* stream);
 /* conv_in from two NCHW sources in one launch (edge.hip: conv_head2_kernel), the concatenated sample never built:
  *   y_nhwc[n] = conv3x3(cat(fp16(a[n % Na] * in_scale), n < zero_from ? b[n % Nb] : 0); w_oihw [320, Ca + Cb, 3, 3]) + bias
  * a [Na, Ca, H, W], b [Nb, Cb, H, W] f16; y_nhwc [N H W, 320] with row stride ldy (>= 320, % 8 == 0); b is not read for
@@ -933,6 +942,10 @@ int sd_op_timestep_cond_embedding(const float* t, const float* cond, const void*
  * W f16 row-major [n_out, k]. */
 int sd_op_small_linear(const float* x, const void* w_f16, const float* bias, float* y, int B, int K, int n_out,
                        int silu_in, int silu_out, void* stream);
+/* Which kernel sd_op_small_linear (and every launch of the time-embedding path) runs for [B, K] x [n_out, K]^T, decided
+ * on the host by the function the launcher itself asks: 1 skinny_linear_kernel (MFMA; B <= 16, K % 32 == 0, K <= 1280,
+ * n_out % 16 == 0), 0 small_linear_kernel (GEMV), -1 refused (K % 8 != 0, or an argument below 1).  No device needed. */
+int sd_small_linear_plan(int B, int K, int n_out);
 /* diffusers 0.27.2 apply_freeu on one concatenation cat_nhwc [N, H, W, C1 + C2] f16, in place:
  *   cat[..., :C1 / 2] *= b;   cat[..., C1:] = fourier_filter(cat[..., C1:], threshold = 1, scale = s) over (H, W)
  * i.e. the skip's frequencies {-1, 0} x {-1, 0} times s and the real part kept, computed in closed form from seven fp32

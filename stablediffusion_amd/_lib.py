@@ -271,6 +271,7 @@ SIGNATURES = {
                                       C.POINTER(_I), _P]),
     "sd_bench_conv2d": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(_F), _P]),
     "sd_op_groupnorm": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _P]),
+    "sd_op_unet_conv_out_ex": (_I, [_P, _I64, _P, _P, _I, _F, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _I64, _I, C.POINTER(_F), _P]),
     "sd_norm_plan": (_I, [_I, _I64, _I, _I, _I, _I, C.POINTER(_I64)]),
     "sd_norm_plan_batch": (_I, [_I, C.POINTER(_I64), C.POINTER(_I64)]),
     "sd_op_groupnorm_ex": (_I, [_P, _I64, _P, _P, _P, _I64, _I, _I64, _I, _I, _F, _I, _P, _I, _I64, C.POINTER(_I64), _P]),
@@ -280,6 +281,7 @@ SIGNATURES = {
     "sd_op_timestep_sinusoid": (_I, [_P, _P, _I, _I, _I, _F, _P]),
     "sd_op_text_time_input": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _F, _P]),
     "sd_op_timestep_cond_embedding": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _F, _P]),
+    "sd_small_linear_plan": (_I, [_I, _I, _I]),
     "sd_op_small_linear": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "sd_op_freeu": (_I, [_P, _I, _I, _I, _I, _I, _F, _F, _P]),
     "sd_op_layernorm": (_I, [_P, _P, _P, _P, _I, _I, _F, _P]),

@@ -1478,6 +1478,12 @@ int sd_op_unet_conv_in(const void* x_nchw, const void* w_oihw, const void* bias_
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (!x_nchw || !w_oihw || !bias_f32 || !y_nhwc || N < 1 || Cin < 1) { set_error("sd_op_unet_conv_in: bad arguments"); return SD_ERR_INVALID; }
     const long K = 64;
+    HeadParams p;
+    p.x_nchw = static_cast<const half_t*>(x_nchw); p.w = nullptr; p.K = K; p.bias = nullptr; p.y = static_cast<half_t*>(y_nhwc); p.ldy = Cout;
+    p.gnstat_out = groups > 0 ? gn_summaries : nullptr; p.G = groups;
+    p.N = N; p.Cin = Cin; p.H = H; p.W = W; p.Cout = Cout;
+    // (refused before anything is allocated or launched)
+    if (H < 1 || W < 1 || 9 * Cin > K || !conv_head_supported(p)) { set_error("sd_op_unet_conv_in: shape outside the one-launch kernel (Cout 320, 9 Cin <= 64, H W % 128 == 0)"); return SD_ERR_INVALID; }
     const long rows = ((long)Cout + kWeightRowPad - 1) / kWeightRowPad * kWeightRowPad;
     DevScope scope;
     half_t* wp = nullptr;
@@ -1486,11 +1492,7 @@ int sd_op_unet_conv_in(const void* x_nchw, const void* w_oihw, const void* bias_
     SD_DEV_ALLOC(scope, bp, (size_t)rows * 4);
     SD_HIP_CHECK(hipMemsetAsync(wp, 0, (size_t)rows * K * 2, s));
     SD_HIP_CHECK(hipMemsetAsync(bp, 0, (size_t)rows * 4, s));
-    HeadParams p;
-    p.x_nchw = static_cast<const half_t*>(x_nchw); p.w = wp; p.K = K; p.bias = bp; p.y = static_cast<half_t*>(y_nhwc); p.ldy = Cout;
-    p.gnstat_out = groups > 0 ? gn_summaries : nullptr; p.G = groups;
-    p.N = N; p.Cin = Cin; p.H = H; p.W = W; p.Cout = Cout;
-    if (9 * Cin > K || !conv_head_supported(p)) { set_error("sd_op_unet_conv_in: shape outside the one-launch kernel (Cout 320, 9 Cin <= 64, H W % 128 == 0)"); return SD_ERR_INVALID; }
+    p.w = wp; p.bias = bp;
     int rc = launch_pack_conv(static_cast<const half_t*>(w_oihw), wp, Cout, Cin, 3, 3, K, s);
     if (!rc) SD_HIP_CHECK(hipMemcpyAsync(bp, bias_f32, (size_t)Cout * 4, hipMemcpyDeviceToDevice, s));
     hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -1566,33 +1568,46 @@ int sd_op_unet_conv_in2(const void* a, int Na, int Ca, float in_scale, const voi
     return rc;
 }
 
-int sd_op_unet_conv_out(const void* x_nhwc, const void* gamma_f32, const void* beta_f32, int groups, float eps, int silu,
-                        const void* w_oihw, const void* bias_f32, void* y_nchw, int N, int H, int W, int C, int Cout, int iters,
-                        float* ms_per_launch, void* stream) {
+int sd_op_unet_conv_out_ex(const void* x_nhwc, int64_t ldx, const void* gamma_f32, const void* beta_f32, int groups, float eps,
+                           int silu, const void* w_oihw, const void* bias_f32, void* y_nchw, int N, int H, int W, int C, int Cout,
+                           const float* summaries, int S, int64_t rows, int iters, float* ms_per_launch, void* stream) {
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (!x_nhwc || !gamma_f32 || !beta_f32 || !w_oihw || !bias_f32 || !y_nchw || groups < 1 || C % 64 != 0) { set_error("sd_op_unet_conv_out: bad arguments"); return SD_ERR_INVALID; }
+    if (!x_nhwc || !gamma_f32 || !beta_f32 || !w_oihw || !bias_f32 || !y_nchw || N < 1 || H < 1 || W < 1 || groups < 1 || C < 64 ||
+        C % 64 != 0 || Cout < 1) {
+        set_error("sd_op_unet_conv_out: bad arguments"); return SD_ERR_INVALID;
+    }
+    const long HW = (long)H * W;
+    if (ldx < C || ldx % 8 != 0) { set_error("sd_op_unet_conv_out: ldx must be at least C and a multiple of 8"); return SD_ERR_INVALID; }
+    if (summaries && (S < 1 || rows < 1 || (int64_t)S * rows < HW || (int64_t)(S - 1) * rows >= HW)) {
+        set_error("sd_op_unet_conv_out: S summaries of `rows` pixels must cover H W with no empty one"); return SD_ERR_INVALID;
+    }
     const long K = 9L * C;
-    const long rows = ((long)Cout + kWeightRowPad - 1) / kWeightRowPad * kWeightRowPad;
+    TailParams p;
+    p.x = static_cast<const half_t*>(x_nhwc); p.ldx = ldx;
+    p.gn_part = summaries ? summaries : static_cast<const float*>(gamma_f32);      // (own pass: replaced below; non-null for the check)
+    p.gn_S = summaries ? S : 1; p.gn_rows = summaries ? rows : HW;
+    p.G = groups; p.eps = eps; p.gamma = static_cast<const float*>(gamma_f32); p.beta = static_cast<const float*>(beta_f32); p.silu = silu;
+    p.w = nullptr; p.K = K; p.bias = nullptr; p.y = static_cast<half_t*>(y_nchw);
+    p.N = N; p.H = H; p.W = W; p.C = C; p.Cout = Cout;
+    if (!conv_tail_supported(p)) { set_error("sd_op_unet_conv_out: shape outside the one-launch kernel (C 320, Cout <= 4, H % 8 == 0, W % 16 == 0, groups <= 32)"); return SD_ERR_INVALID; }
+    const long wrows = ((long)Cout + kWeightRowPad - 1) / kWeightRowPad * kWeightRowPad;
     DevScope scope;
     half_t* wp = nullptr;
     float *bp = nullptr, *scratch = nullptr;
-    SD_DEV_ALLOC(scope, wp, (size_t)rows * K * 2);
-    SD_DEV_ALLOC(scope, bp, (size_t)rows * 4);
-    SD_DEV_ALLOC(scope, scratch, (size_t)gn_scratch_floats(N, (long)H * W, C, groups) * 4);
-    SD_HIP_CHECK(hipMemsetAsync(wp, 0, (size_t)rows * K * 2, s));
-    SD_HIP_CHECK(hipMemsetAsync(bp, 0, (size_t)rows * 4, s));
+    SD_DEV_ALLOC(scope, wp, (size_t)wrows * K * 2);
+    SD_DEV_ALLOC(scope, bp, (size_t)wrows * 4);
+    if (!summaries) SD_DEV_ALLOC(scope, scratch, (size_t)gn_scratch_floats(N, HW, C, groups) * 4);
+    SD_HIP_CHECK(hipMemsetAsync(wp, 0, (size_t)wrows * K * 2, s));
+    SD_HIP_CHECK(hipMemsetAsync(bp, 0, (size_t)wrows * 4, s));
     int rc = launch_pack_conv(static_cast<const half_t*>(w_oihw), wp, Cout, C, 3, 3, K, s);
     if (!rc) SD_HIP_CHECK(hipMemcpyAsync(bp, bias_f32, (size_t)Cout * 4, hipMemcpyDeviceToDevice, s));
-    GnStats st;
-    if (!rc) rc = launch_gn_stats(static_cast<const half_t*>(x_nhwc), C, N, (long)H * W, C, groups, scratch, &st, s);
+    if (!rc && !summaries) {
+        GnStats st;
+        rc = launch_gn_stats(static_cast<const half_t*>(x_nhwc), ldx, N, HW, C, groups, scratch, &st, s);
+        p.gn_part = st.part; p.gn_S = st.S; p.gn_rows = st.rows;
+    }
     if (rc) return rc;
-    TailParams p;
-    p.x = static_cast<const half_t*>(x_nhwc); p.ldx = C;
-    p.gn_part = st.part; p.gn_S = st.S; p.gn_rows = st.rows;
-    p.G = groups; p.eps = eps; p.gamma = static_cast<const float*>(gamma_f32); p.beta = static_cast<const float*>(beta_f32); p.silu = silu;
-    p.w = wp; p.K = K; p.bias = bp; p.y = static_cast<half_t*>(y_nchw);
-    p.N = N; p.H = H; p.W = W; p.C = C; p.Cout = Cout;
-    if (!conv_tail_supported(p)) { set_error("sd_op_unet_conv_out: shape outside the one-launch kernel (C 320, Cout <= 4, H % 8 == 0, W % 16 == 0, groups <= 32)"); return SD_ERR_INVALID; }
+    p.w = wp; p.bias = bp;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     const bool timed = iters > 0 && ms_per_launch;
     if (timed) { SD_HIP_CHECK(hipEventCreate(&e0)); SD_HIP_CHECK(hipEventCreate(&e1)); }
@@ -1612,6 +1627,13 @@ int sd_op_unet_conv_out(const void* x_nhwc, const void* gamma_f32, const void* b
     hipError_t e = hipStreamSynchronize(s);
     if (!rc && e != hipSuccess) { set_error(hipGetErrorString(e)); rc = SD_ERR_HIP; }
     return rc;
+}
+
+int sd_op_unet_conv_out(const void* x_nhwc, const void* gamma_f32, const void* beta_f32, int groups, float eps, int silu,
+                        const void* w_oihw, const void* bias_f32, void* y_nchw, int N, int H, int W, int C, int Cout, int iters,
+                        float* ms_per_launch, void* stream) {
+    return sd_op_unet_conv_out_ex(x_nhwc, C, gamma_f32, beta_f32, groups, eps, silu, w_oihw, bias_f32, y_nchw, N, H, W, C, Cout,
+                                  nullptr, 0, 0, iters, ms_per_launch, stream);
 }
 
 int sd_bench_conv2d(const void* x, const void* w_oihw, void* y, int N, int H, int W, int Cin, int Cout, int ksize,
@@ -1803,6 +1825,11 @@ int sd_op_timestep_cond_embedding(const float* t, const float* cond, const void*
     }
     return launch_timestep_cond(t, cond, static_cast<const half_t*>(w_f16), cond_dim, out, B, dim, cond_dim, flip_sin_to_cos,
                                 freq_shift, static_cast<hipStream_t>(stream));
+}
+
+int sd_small_linear_plan(int B, int K, int n_out) {
+    if (B < 1 || K < 1 || n_out < 1) { set_error("sd_small_linear_plan: bad arguments"); return -1; }
+    return small_linear_plan(B, K, n_out);
 }
 
 int sd_op_small_linear(const float* x, const void* w_f16, const float* bias, float* y, int B, int K, int n_out, int silu_in,

@@ -362,6 +362,9 @@ int launch_timestep_cond(const float* t, const float* cond, const half_t* w, lon
 // y[b, n] = bias[n] + sum_k act(x[b, k]) * W[n, k]  for small b (time-embedding MLPs); fp32 in/out.
 int launch_small_linear(const float* x, long ldx, const half_t* w, const float* bias, float* y,
                         long ldy, int B, int K, int Nout, int silu_in, int silu_out, hipStream_t s);
+// The kernel launch_small_linear runs (the one place that decides; sd_small_linear_plan reports it): 1 skinny_linear_kernel,
+// 0 small_linear_kernel, -1 refused (K % 8).  Host only.
+int small_linear_plan(int B, int K, int Nout);
 int launch_add_f32(float* y, const float* x, long n, int silu, hipStream_t s);   // y = act(y + x), x may be null
 int launch_f16_to_f32(const half_t* x, float* y, long n, hipStream_t s);
 int launch_f32_to_f16(const float* x, half_t* y, long n, hipStream_t s);

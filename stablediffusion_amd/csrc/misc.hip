@@ -1075,11 +1075,17 @@ __global__ __launch_bounds__(256) void skinny_linear_kernel(const float* __restr
     }
 }
 
+int small_linear_plan(int B, int K, int Nout) {
+    static const bool no_skinny = getenv("SD_NO_SKINNY_LINEAR") != nullptr;
+    if (K % 8 != 0) return -1;
+    return !no_skinny && B <= 16 && K % 32 == 0 && K <= 4 * SK_MAXKS * 32 && Nout % 16 == 0 ? 1 : 0;
+}
+
 int launch_small_linear(const float* x, long ldx, const half_t* w, const float* bias, float* y, long ldy,
                         int B, int K, int Nout, int silu_in, int silu_out, hipStream_t s) {
-    if (K % 8 != 0 || ldx % 4 != 0) { set_error("small_linear: K%8, ldx%4"); return 1; }
-    static const bool no_skinny = getenv("SD_NO_SKINNY_LINEAR") != nullptr;
-    if (!no_skinny && B <= 16 && K % 32 == 0 && K <= 4 * SK_MAXKS * 32 && Nout % 16 == 0) {
+    const int plan = small_linear_plan(B, K, Nout);
+    if (plan < 0 || ldx % 4 != 0) { set_error("small_linear: K%8, ldx%4"); return 1; }
+    if (plan == 1) {
         const int tiles = Nout / 16;
         hipLaunchKernelGGL(skinny_linear_kernel, dim3(tiles < 512 ? tiles : 512), dim3(256), 0, s, x, ldx, w, bias, y, ldy, B, K, Nout,
                            silu_in, silu_out);
