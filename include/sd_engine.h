@@ -282,6 +282,31 @@ int sd_unet_forward_concat(sd_unet* u, const void* latents, int B_lat, float in_
  * Non-finite factors: SD_ERR_INVALID.  Graph replay (sd_unet_use_graph) with FreeU on is rejected by the forward
  * (SD_ERR_UNSUPPORTED). */
 int sd_unet_set_freeu(sd_unet* u, int enable, float s1, float s2, float b1, float b2);
+/* Token merging (Bolya & Hoffman, "Token Merging for Fast Stable Diffusion"; tomesd's apply_patch with its defaults:
+ * merge_attn only) for the self-attention of every BasicTransformerBlock whose map is at most max_downsample times
+ * smaller than the sample (sample_height / H <= max_downsample, max_downsample in {1, 2, 4, 8}).  Such a block matches
+ * its tokens on the residual stream norm1 reads (sd_op_tome_match with site = the block's ordinal among all
+ * BasicTransformerBlocks in execution order of the full forward, step = sd_unet_tome_step's), merges the rows of the
+ * q|k|v projection (the projections are linear: the mean of projected rows is the projection of the mean), runs the
+ * attention on T' = T - r rows and copies its output back through the unmerge map; the q|k|v and out-projection GEMMs
+ * stay full-size.  A block with r = 0 runs the plain path bit for bit.  ratio = 0 means off: the other arguments are
+ * ignored, the buffer is released and the forward is again exactly the plain one, with the same launches.
+ * Holds for sd_unet_forward, _ex, _tc and _cfg and with the DeepCache modes.  With debug taps on (sd_unet_tap) every
+ * merging block also records the view its match read, as the input of "tome.<site>".  SD_ERR_INVALID: ratio outside
+ * [0, 0.75] or NaN, sx or sy outside 1..8, an unlisted max_downsample.  With it on the forward returns
+ * SD_ERR_UNSUPPORTED, nothing launched, for a merging block of more than 16384 tokens or without a whole cell, with
+ * graph replay on (sd_unet_use_graph), in sd_unet_forward_pag / sd_unet_forward_concat, and with FreeU on, a ControlNet
+ * attached or an IP-Adapter attached (no test composes those with it yet). */
+int sd_unet_set_tome(sd_unet* u, double ratio, int max_downsample, int sx, int sy, int use_rand, uint32_t seed);
+/* The step index the destination draw of the following forwards hashes (the loop's iteration; 0 until set). */
+int sd_unet_tome_step(sd_unet* u, uint32_t step);
+/* The merging blocks of the last forward, in execution order: their count, and for the k-th one
+ * info5 = (site, H, W, r, T') and, when map_host is non-NULL, its unmerge maps [images, H W] int32 (cap = the entries
+ * map_host holds).  The maps live in a buffer the handle keeps (counted in sd_unet_memory's workspace_bytes) until the
+ * next forward.  sd_unet_tome_read returns the number of images the block ran on (half the batch inside the shared CFG
+ * prefix), or -SD_ERR_*; it synchronises the device. */
+int sd_unet_tome_sites(const sd_unet* u);
+int sd_unet_tome_read(sd_unet* u, int k, int32_t* info5, int32_t* map_host, int64_t cap);
 /* DeepCache (Ma, Fang, Wang, CVPR 2024): reuse the deep features of the UNet across denoising steps.  With
  *   L = layers_per_block, s_0 = conv_in's output, s_j = the output of layer j - 1 of down block 0,
  * layer j of the last up block (j = 0..L) reads cat([hidden, s_{L-j}]).  For a depth d in 1..L the cached feature F_d
@@ -952,6 +977,51 @@ int sd_small_linear_plan(int B, int K, int n_out);
  * moments per (image, channel) plane and rounded to f16 once; cat[..., C1 / 2 : C1] is not touched.  C1 even, C2 >= 1,
  * finite factors (SD_ERR_INVALID otherwise); H + W <= 4096 (SD_ERR_UNSUPPORTED beyond). */
 int sd_op_freeu(void* cat_nhwc, int N, int H, int W, int C1, int C2, float b, float s, void* stream);
+/* Token merging, operator by operator (tomesd's bipartite_soft_matching_random2d; sd_unet_set_tome).  An H x W map of
+ * T = H W tokens is cut into sy x sx cells; with hsy = H / sy, wsx = W / sx, cell = cy wsx + cx draws
+ *   k = use_rand ? mix32(seed, step, site, cell) % (sx sy) : 0,   in uint32 arithmetic
+ *   h = seed ^ step 0x9E3779B9 ^ site 0x85EBCA6B ^ cell 0xC2B2AE35;
+ *   h ^= h >> 16; h *= 0x85EBCA6B; h ^= h >> 13; h *= 0xC2B2AE35; h ^= h >> 16
+ * and its destination token is (cy sy + k / sx, cx sx + k % sx); every other token, the rows and columns past the whole
+ * cells included, is a source: Nd = hsy wsx, Ns = T - Nd.  The draw is shared by all images.  r = min(Ns, int(T ratio))
+ * sources merge.  Ranks are raster order within each set.  With s[i, j] = <x_i, x_j> / (|x_i| |x_j|) (0 for a zero row),
+ * node_max_i = max_j s[i, j] and node_idx_i the lowest destination rank that attains it, the r sources of largest
+ * node_max merge (ties to the lower source rank).  The merged sequence has T' = T - r rows: the unmerged sources in
+ * source-rank order, then the destinations in destination-rank order, a destination row being the mean over itself
+ * and the sources merged into it.  map[t] in [0, T') is the merged row token t reads back.
+ *
+ * sd_tome_plan: info4 = (Nd, Ns, r, T') and, when dst_tok is non-NULL, the Nd destination tokens in rank order.  Needs
+ * no device.  sd_tome_plan_bytes: the size of the opaque plan buffer (device memory) for B images of T tokens.
+ *
+ * sd_op_tome_match: x [B, H W, C] f16 with row stride ldx (ldx % 8 == 0, C % 32 == 0, 16-byte aligned) -> plan, in
+ * three launches: fp32 reciprocal norms and the rank tables; x_src x_dst^T on fp16 MFMAs with fp32 accumulation over
+ * all of C, scaled by the two reciprocal norms afterwards, with a running (max, lowest argmax) per source (the scores
+ * are never stored); one block per image that selects the r largest by a radix select of the order-preserving bit
+ * pattern, compacts the unmerged ranks by a prefix sum and lists every merged row's members in ascending token index.
+ * No global atomics: the result is reproducible bit for bit.  map_out [B, T] int32, node_max [B, Ns] f32 and
+ * node_idx [B, Ns] int32 (DEVICE, each nullable) receive copies.  SD_ERR_INVALID: bad arguments, r = 0;
+ * SD_ERR_UNSUPPORTED, nothing launched: T > 16384, Nd = 0.
+ *
+ * sd_op_tome_plan_from_map: a plan from a caller's map_host [B, T] (HOST) onto T_merged rows, so that merge / unmerge
+ * can be driven with any grouping; every row of [0, T_merged) needs a member.  Synchronises the stream.
+ *
+ * sd_op_tome_merge: dst [B T', ldd] <- per merged row the mean of its member rows of src [B T, lds] over `cols` columns:
+ * f16 in, fp32 sum in ascending token index, one IEEE divide by the member count, one rounding to f16.
+ * sd_op_tome_unmerge: dst [B T, ldd] row t <- src [B T', lds] row map[t], a pure copy.  Both use 16-byte accesses when
+ * cols, both row strides and both pointers allow and one element per thread otherwise, and touch nothing outside the
+ * `cols` columns or beyond the last row.  The plan is device memory the host does not read: a buffer that holds no plan
+ * for this T and at least B images (its header says) makes both launches write nothing, and they still return SD_OK. */
+int sd_tome_plan(int H, int W, int sx, int sy, double ratio, int use_rand, uint32_t seed, uint32_t step, uint32_t site,
+                 int32_t* info4, int32_t* dst_tok);
+int64_t sd_tome_plan_bytes(int B, int T);
+int sd_op_tome_match(const void* x, int64_t ldx, int B, int H, int W, int C, int sx, int sy, double ratio, int use_rand,
+                     uint32_t seed, uint32_t step, uint32_t site, void* plan, int32_t* map_out, float* node_max,
+                     int32_t* node_idx, void* stream);
+int sd_op_tome_plan_from_map(const int32_t* map_host, int B, int T, int T_merged, void* plan, void* stream);
+int sd_op_tome_merge(const void* src, int64_t lds, int cols, const void* plan, int B, int T, void* dst, int64_t ldd,
+                     void* stream);
+int sd_op_tome_unmerge(const void* src, int64_t lds, int cols, const void* plan, int B, int T, void* dst, int64_t ldd,
+                       void* stream);
 /* LayerNorm over the last dim of [rows, C] f16. */
 int sd_op_layernorm(const void* x, const void* gamma, const void* beta, void* y, int rows, int C,
                     float eps, void* stream);

@@ -163,6 +163,10 @@ SIGNATURES = {
     "sd_unet_set_ip_adapter": (_I, [_P, _P]),
     "sd_unet_set_ip_adapter_scale": (_I, [_P, _F]),
     "sd_unet_set_freeu": (_I, [_P, _I, _F, _F, _F, _F]),
+    "sd_unet_set_tome": (_I, [_P, C.c_double, _I, _I, _I, _I, C.c_uint32]),
+    "sd_unet_tome_step": (_I, [_P, C.c_uint32]),
+    "sd_unet_tome_sites": (_I, [_P]),
+    "sd_unet_tome_read": (_I, [_P, _I, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _I64]),
     "sd_unet_set_pag_layers": (_I, [_P, _P, _I]),
     "sd_unet_forward_pag": (_I, [_P, _P, _P, _P, _I, _P, _P, _F, _I, _I, _P, _I, _I, _I, _P]),
     "sd_unet_forward_concat": (_I, [_P, _P, _I, _F, _P, _I, _I, _I, _P, _P, _I, _P, _P, _P, _I, _I, _I, _P]),
@@ -284,6 +288,14 @@ SIGNATURES = {
     "sd_small_linear_plan": (_I, [_I, _I, _I]),
     "sd_op_small_linear": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "sd_op_freeu": (_I, [_P, _I, _I, _I, _I, _I, _F, _F, _P]),
+    "sd_tome_plan": (_I, [_I, _I, _I, _I, C.c_double, _I, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32),
+                          C.POINTER(C.c_int32)]),
+    "sd_tome_plan_bytes": (_I64, [_I, _I]),
+    "sd_op_tome_match": (_I, [_P, _I64, _I, _I, _I, _I, _I, _I, C.c_double, _I, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P, _P,
+                              _P, _P]),
+    "sd_op_tome_plan_from_map": (_I, [C.POINTER(C.c_int32), _I, _I, _I, _P, _P]),
+    "sd_op_tome_merge": (_I, [_P, _I64, _I, _P, _I, _I, _P, _I64, _P]),
+    "sd_op_tome_unmerge": (_I, [_P, _I64, _I, _P, _I, _I, _P, _I64, _P]),
     "sd_op_layernorm": (_I, [_P, _P, _P, _P, _I, _I, _F, _P]),
     "sd_op_layernorm_ex": (_I, [_P, _I64, _P, _P, _P, _I64, _I64, _I, _F, _P]),
     "sd_op_row_stats": (_I, [_P, _I64, _P, _I64, _I, _P]),

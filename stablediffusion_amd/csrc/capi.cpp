@@ -343,6 +343,31 @@ int sd_unet_set_freeu(sd_unet* u, int enable, float s1, float s2, float b1, floa
     u->impl.freeu_s1 = s1; u->impl.freeu_s2 = s2; u->impl.freeu_b1 = b1; u->impl.freeu_b2 = b2;
     return SD_OK;
 }
+int sd_unet_set_tome(sd_unet* u, double ratio, int max_downsample, int sx, int sy, int use_rand, uint32_t seed) {
+    if (!u) { set_error("null handle"); return SD_ERR_INVALID; }
+    if (!u->impl.finalized) { set_error("sd_unet_set_tome before finalize"); return SD_ERR_STATE; }
+    return u->impl.set_tome(ratio, max_downsample, sx, sy, use_rand, seed);
+}
+int sd_unet_tome_step(sd_unet* u, uint32_t step) {
+    if (!u) { set_error("null handle"); return SD_ERR_INVALID; }
+    u->impl.tome.step = step;
+    return SD_OK;
+}
+int sd_unet_tome_sites(const sd_unet* u) { return u ? (int)u->impl.tome_used.size() : 0; }
+int sd_unet_tome_read(sd_unet* u, int k, int32_t* info5, int32_t* map_host, int64_t cap) {
+    if (!u || !info5) { set_error("null argument"); return -SD_ERR_INVALID; }
+    if (k < 0 || k >= (int)u->impl.tome_used.size()) { set_error("sd_unet_tome_read: no such merged block in the last forward"); return -SD_ERR_INVALID; }
+    const TomeUsed& t = u->impl.tome_used[(size_t)k];
+    info5[0] = t.site; info5[1] = t.H; info5[2] = t.W; info5[3] = t.r; info5[4] = t.Tm;
+    if (!map_host) return t.B;
+    const int T = t.H * t.W;
+    if (cap < (int64_t)t.B * T) { set_error("sd_unet_tome_read: map_host is too small"); return -SD_ERR_INVALID; }
+    if (!u->impl.tome_buf.data()) { set_error("sd_unet_tome_read: the maps were released"); return -SD_ERR_STATE; }
+    if (hipDeviceSynchronize() != hipSuccess) { set_error("sd_unet_tome_read: device error"); return -SD_ERR_HIP; }
+    for (int b = 0; b < t.B; ++b)
+        if (tome_plan_read_map(u->impl.tome_buf.data() + t.plan_off, b, T, map_host + (long)b * T)) return -SD_ERR_HIP;
+    return t.B;
+}
 int sd_unet_set_deep_cache(sd_unet* u, int depth) {
     if (!u) { set_error("null handle"); return SD_ERR_INVALID; }
     return u->impl.set_deep_cache(depth);
@@ -487,7 +512,7 @@ int sd_controlnet_finalize(sd_controlnet* cn) {
 int sd_unet_memory(const sd_unet* u, int64_t* weight_bytes, int64_t* workspace_bytes) {
     if (!u) { set_error("null handle"); return SD_ERR_INVALID; }
     if (weight_bytes) *weight_bytes = u->impl.ws.packed_bytes();
-    if (workspace_bytes) *workspace_bytes = (int64_t)(u->impl.arena.capacity() + u->impl.dc_buf.capacity());
+    if (workspace_bytes) *workspace_bytes = (int64_t)(u->impl.arena.capacity() + u->impl.dc_buf.capacity() + u->impl.tome_buf.capacity());
     return SD_OK;
 }
 
@@ -1866,6 +1891,44 @@ int sd_op_row_stats(const void* x, int64_t ldx, float* stat, int64_t rows, int C
 int sd_op_freeu(void* cat_nhwc, int N, int H, int W, int C1, int C2, float b, float s, void* stream) {
     if (!cat_nhwc) { set_error("sd_op_freeu: null argument"); return SD_ERR_INVALID; }
     return launch_freeu(static_cast<half_t*>(cat_nhwc), (long)C1 + C2, N, H, W, C1, C2, b, s, static_cast<hipStream_t>(stream));
+}
+
+int sd_tome_plan(int H, int W, int sx, int sy, double ratio, int use_rand, uint32_t seed, uint32_t step, uint32_t site,
+                 int32_t* info4, int32_t* dst_tok) {
+    if (!info4) { set_error("sd_tome_plan: null argument"); return SD_ERR_INVALID; }
+    TomeGeom g;
+    if (tome_geom(H, W, sx, sy, ratio, use_rand, seed, step, site, &g)) return SD_ERR_INVALID;
+    info4[0] = g.Nd; info4[1] = g.Ns; info4[2] = g.r; info4[3] = g.Tm;
+    if (dst_tok) tome_dst_tokens(g, dst_tok);
+    return SD_OK;
+}
+int64_t sd_tome_plan_bytes(int B, int T) { return tome_plan_bytes(B, T); }
+int sd_op_tome_match(const void* x, int64_t ldx, int B, int H, int W, int C, int sx, int sy, double ratio, int use_rand,
+                     uint32_t seed, uint32_t step, uint32_t site, void* plan, int32_t* map_out, float* node_max,
+                     int32_t* node_idx, void* stream) {
+    if (!x || !plan) { set_error("sd_op_tome_match: null argument"); return SD_ERR_INVALID; }
+    TomeGeom g;
+    if (tome_geom(H, W, sx, sy, ratio, use_rand, seed, step, site, &g)) return SD_ERR_INVALID;
+    if (!tome_supported(g)) {
+        set_error("sd_op_tome_match: more than 16384 tokens, or a map without a whole cell, is not supported");
+        return SD_ERR_UNSUPPORTED;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (int rc = launch_tome_match(static_cast<const half_t*>(x), ldx, B, C, g, plan, s)) return rc;
+    return tome_plan_fetch(plan, B, g.T, g.Ns, map_out, node_max, node_idx, s);
+}
+int sd_op_tome_plan_from_map(const int32_t* map_host, int B, int T, int T_merged, void* plan, void* stream) {
+    return tome_plan_from_map(map_host, B, T, T_merged, plan, static_cast<hipStream_t>(stream));
+}
+int sd_op_tome_merge(const void* src, int64_t lds, int cols, const void* plan, int B, int T, void* dst, int64_t ldd,
+                     void* stream) {
+    return launch_tome_merge(static_cast<const half_t*>(src), lds, cols, plan, B, T, 0, static_cast<half_t*>(dst), ldd,
+                             static_cast<hipStream_t>(stream));
+}
+int sd_op_tome_unmerge(const void* src, int64_t lds, int cols, const void* plan, int B, int T, void* dst, int64_t ldd,
+                       void* stream) {
+    return launch_tome_unmerge(static_cast<const half_t*>(src), lds, cols, plan, B, T, static_cast<half_t*>(dst), ldd,
+                               static_cast<hipStream_t>(stream));
 }
 
 int sd_op_attention(const void* q, const void* k, const void* v, void* out, int B, int Tq, int Tk, int heads, int d,

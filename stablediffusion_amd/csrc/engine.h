@@ -215,6 +215,22 @@ struct PagState {
     std::function<void(std::vector<RowDupSeg>&)> caller_segs;
 };
 
+// Token merging (UNet::set_tome) as one forward sees it: the settings, the plan buffer of every transformer block that
+// merges at this forward's shape (by the block's ordinal among all BasicTransformerBlocks in execution order of the full
+// forward; -1: the block runs the plain path) and the list of the blocks that did merge, filled by the live pass.
+struct TomeUsed {
+    int site = 0, H = 0, W = 0, r = 0, Tm = 0, B = 0;
+    long plan_off = 0;
+};
+struct TomeRun {
+    double ratio = 0.0;
+    int sx = 2, sy = 2, use_rand = 1;
+    uint32_t seed = 0, step = 0;
+    char* buf = nullptr;                // the plan buffers (UNet::tome_buf)
+    std::vector<long> plan_off;
+    std::vector<TomeUsed>* used = nullptr;
+};
+
 // Debug taps (sd_unet_tap / sd_vae_tap): copies of the activation views at block boundaries of ONE forward, for the
 // per-block tests.  Off (Ctx::tap == nullptr, the default) a forward does no tap work at all: no launch, no allocation,
 // the arena plan and the profile are what they are without the facility.  On, the live pass copies each tapped view on
@@ -260,6 +276,8 @@ struct Ctx {
     float ip_scale = 1.f;
     PagState* pag = nullptr;            // forward_pag only
     TapSink* tap = nullptr;             // debug taps of this forward (nullptr: off)
+    // token merging of this forward (nullptr: off, and always inside a ControlNet's encoder: tomesd patches the UNet only)
+    const TomeRun* tome = nullptr;
 };
 // Record view `v` ([N H W, v.C] fp16, kind kTap*) under `name`; nothing on a dry or failed context.  Callers guard with
 // `if (c.tap)` so that a forward without taps does not even build the name.

@@ -491,6 +491,40 @@ int launch_views_gather(const half_t* canvas, half_t* windows, int B, int C, int
 // size = min(vpc, V - (v / vpc) vpc).  Every pixel must be covered by a view (the C entry checks it).
 int launch_views_merge(const half_t* model_out, half_t* eps, const float* wt, int G, int B, int C, int Hc, int Wc, int h,
                        int w, const ViewStarts& st, int ny, int nx, int wrap_x, int vpc, hipStream_t s);
+// Token merging (tome.hip; Bolya & Hoffman 2023, tomesd's bipartite_soft_matching_random2d).  The H x W map is cut into
+// sy x sx cells; cell (cy, cx) of the hsy x wsx whole ones gives one destination token, (cy sy + k / sx, cx sx + k % sx) with
+// k = 0 or mix32(seed, step, site, cell) % (sx sy); every other token is a source.  r = min(Ns, int(T ratio)) sources, those
+// of largest cosine similarity to their best destination, are merged into it: T' = T - r rows, the unmerged sources in
+// raster order, then the destinations in raster order (a destination row = the mean of itself and its merged sources).
+struct TomeGeom {
+    int H, W, sx, sy, hsy, wsx, use_rand;
+    uint32_t seed, step, site;
+    int T, Nd, Ns, r, Tm;
+};
+// Fills *g; 1 for sx / sy outside 1..8, a ratio outside [0, 0.75] (or NaN), an empty map.  Host only, no device.
+int tome_geom(int H, int W, int sx, int sy, double ratio, int use_rand, uint32_t seed, uint32_t step, uint32_t site, TomeGeom* g);
+void tome_dst_tokens(const TomeGeom& g, int* dst_tok);          // [Nd] destination tokens in rank order (host)
+bool tome_supported(const TomeGeom& g);                         // T <= 16384, Nd >= 1, the selection's keys fit the LDS
+long tome_plan_bytes(int B, int T);                             // the opaque plan buffer of B images of T tokens
+// Three launches (norms + rank tables, match, select) from x [B T, C] fp16 (row stride ldx % 8 == 0, C % 32 == 0, 16-byte
+// aligned) into `plan`: the unmerge map, the member lists of every merged row, node_max / node_idx of every source.
+// g.r >= 1.  Returns 4 where !tome_supported.  stage: 0 all three, in order; 1 / 2 / 3 that launch alone (the forward times
+// them one by one).
+int launch_tome_match(const half_t* x, long ldx, int B, int C, const TomeGeom& g, void* plan, hipStream_t s, int stage = 0);
+// Copies of a plan's map [B, T] / node_max [B, Ns] / node_idx [B, Ns] into device arrays (each nullable), on the stream.
+int tome_plan_fetch(const void* plan, int B, int T, int Ns, int* map_out, float* node_max, int* node_idx, hipStream_t s);
+int tome_plan_read_map(const void* plan, int b, int T, int* map_host);      // synchronous copy to the host
+// A plan from a caller's map [B, T] (host) onto T' rows: the member lists in ascending token index.  Every row of [0, T')
+// needs a member.  Synchronises the stream.
+int tome_plan_from_map(const int* map_host, int B, int T, int Tm, void* plan, hipStream_t s);
+// dst [B T', ldd] <- per merged row the mean of src's [B T, lds] member rows over `cols` columns: fp32 sum in ascending
+// token index, one IEEE divide by the member count, one rounding.  Tm_host: T' when the host knows it (0: the grid covers
+// T rows and the kernel reads T' from the plan).  16-byte accesses when cols, both strides and both pointers allow.
+int launch_tome_merge(const half_t* src, long lds, int cols, const void* plan, int B, int T, int Tm_host, half_t* dst, long ldd,
+                      hipStream_t s);
+// dst [B T, ldd] row t <- src [B T', lds] row map[t]: a pure copy of `cols` columns.
+int launch_tome_unmerge(const half_t* src, long lds, int cols, const void* plan, int B, int T, half_t* dst, long ldd,
+                        hipStream_t s);
 // den = dx x + dout m, x <- pden den + pnoise noise (m: model_out, or its CFG combine when rows == 2); noise / denoised
 // nullable.  The scheduler step of LCMScheduler in one launch.
 int launch_lcm_step(const half_t* model_out, int rows, half_t* lat, const half_t* noise, half_t* denoised, long n, float g,

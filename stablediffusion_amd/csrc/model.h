@@ -35,6 +35,9 @@ struct Xformer {
     // perturbed-attention guidance (sd_unet_set_pag_layers): in a forward_pag call the perturbed group's attn1 of every
     // block here is to_out(to_v(norm1(x))), the identity attention map
     bool pag = false;
+    // ordinal of blocks[0] among all BasicTransformerBlocks of the UNet in execution order (UNet::finalize): the `site` of
+    // token merging's destination draw
+    int tome_site0 = 0;
 };
 struct VaeAttn {
     NormW gn;
@@ -265,10 +268,13 @@ struct PlanKey {
     int n_ctrl = 0;                         // control images of a ControlNet that runs, 0 when none does
     int dc_depth = 0;                       // DeepCache depth of a store / reuse forward (the plain one ignores it)
     int cat_rows = 0;                       // forward_concat: the latents the B images are built from, 0 otherwise
+    double tome_ratio = 0.0;                // token merging: what the merged rows per block depend on (0: off)
+    int tome_ds = 0, tome_sx = 0, tome_sy = 0;
     bool operator==(const PlanKey& o) const {
         return B == o.B && H == o.H && W == o.W && L == o.L && kv_cache == o.kv_cache && ip_tokens == o.ip_tokens &&
                cfg_share == o.cfg_share && pag_groups == o.pag_groups && pag_late == o.pag_late && n_ctrl == o.n_ctrl &&
-               dc_depth == o.dc_depth && cat_rows == o.cat_rows;
+               dc_depth == o.dc_depth && cat_rows == o.cat_rows && tome_ratio == o.tome_ratio && tome_ds == o.tome_ds &&
+               tome_sx == o.tome_sx && tome_sy == o.tome_sy;
     }
 };
 // What a captured graph depends on (timestep_cond's width is the configuration's: its presence changes the launches).
@@ -392,6 +398,20 @@ struct UNet : Encoder {
     DeviceBuf dc_buf;
     CacheTag dc_tag;                    // (no pointer; B, H, W, shared CFG prefix or not) of the stored step
     int set_deep_cache(int depth);
+
+    // ---- token merging (sd_unet_set_tome): ratio 0 = off, the forward as without the feature.  On, attn1 of every
+    // transformer block whose map is at most tome_max_ds times smaller than the sample runs on T' = T - r merged rows:
+    // match on the block's input (tome.hip: three launches), merge of the q|k|v rows, the attention at T', unmerge of its
+    // output; the q|k|v and out-projection GEMMs stay full-size.  The plan buffers of all merging blocks live in tome_buf
+    // (grown like kv_cache; the unmerge maps of the last forward are read from it).  Not under graphs, not in
+    // forward_pag / forward_concat; a ControlNet's encoder runs without it.
+    TomeRun tome;
+    int tome_max_ds = 1;
+    DeviceBuf tome_buf;
+    std::vector<TomeUsed> tome_used;    // the merging blocks of the last forward, in execution order
+    int set_tome(double ratio, int max_downsample, int sx, int sy, int use_rand, uint32_t seed);
+    // the blocks that merge for an H x W sample, in execution order of the full forward, with their plan offsets
+    int tome_layout(int B, int H, int W, std::vector<TomeUsed>* sites, size_t* bytes);
 
     // ---- debug taps (sd_unet_tap; engine.h: TapSink): on, the plain forward records the input and output view of
     // every block; the modes whose launches differ from the plain forward's are refused (tap_refuses: 4 when `mode`).

@@ -293,6 +293,8 @@ int UNet::finalize() {
     SD_HIP_CHECK(hipDeviceSynchronize());
     ws.free_raw();
     finalized = true;
+    int site = 0;
+    for (auto& st : xformer_sites()) { st.second->tome_site0 = site; site += (int)st.second->blocks.size(); }
     return 0;
 }
 
@@ -590,7 +592,47 @@ void run_xformer(Ctx& c, const Xformer& t, View x, int N, int H, int W, View out
         }
         View att(a.alloc_h(M * C), C, C);
         View t2(a.alloc_h(M * C), C, C);
-        if (!perturb) {
+        const int tsite = t.tome_site0 + (int)bi;
+        const long tome_off = c.tome && !perturb && tsite < (int)c.tome->plan_off.size() ? c.tome->plan_off[(size_t)tsite] : -1;
+        if (tome_off >= 0) {
+            // Token merging: the match reads the residual stream norm1 reads; the projections are linear, so the mean of
+            // the projected rows is the projection of the mean of the normalised rows, and the q|k|v launch above and
+            // out1 below stay as they are.  Attention runs on T' rows; its output is copied back through the unmerge map.
+            const TomeRun& tr = *c.tome;
+            TomeGeom g;
+            if (tome_geom(H, W, tr.sx, tr.sy, tr.ratio, tr.use_rand, tr.seed, tr.step, (uint32_t)tsite, &g) || g.r < 1) {
+                set_error("run_xformer: token merging planned for a block that cannot merge"); c.err = 2; return;
+            }
+            void* plan = tr.buf + tome_off;
+            if (c.tap) ctx_tap(c, "tome." + std::to_string(tsite), kTapIn, cur, Np, H, W);     // what the match reads
+            View qm(a.alloc_h((long)N * g.Tm * 3 * C), 3 * C, 3 * C), am(a.alloc_h((long)N * g.Tm * C), C, C);
+            if (!c.dry && !c.err) {
+                hipStream_t s = c.stream;
+                static const char* const stage_name[3] = {"tome_prep_kernel", "tome_match_kernel", "tome_select_kernel"};
+                for (int st = 1; st <= 3 && !c.err; ++st) {
+                    prof_open(s, stage_name[st - 1], st == 2 ? 2.0 * Np * g.Ns * g.Nd * C : 0.0, st == 3 ? 24.0 * Mp : 2.0 * Mp * C);
+                    c.err = launch_tome_match(cur.p, cur.ld, Np, C, g, plan, s, st);
+                    prof_close(s);
+                }
+                if (!c.err) {
+                    prof_open(s, "tome_merge_kernel", 0.0, 2.0 * (Mp + (double)Np * g.Tm) * 3 * C);
+                    c.err = launch_tome_merge(qkv.p, qkv.ld, 3 * C, plan, Np, T, g.Tm, qm.p, qm.ld, s);
+                    prof_close(s);
+                }
+                if (tr.used) {
+                    TomeUsed u;
+                    u.site = tsite; u.H = H; u.W = W; u.r = g.r; u.Tm = g.Tm; u.B = Np; u.plan_off = tome_off;
+                    tr.used->push_back(u);
+                }
+            }
+            op_attention(c, qm.slice(0, C), qm.slice(C, C), qm.slice(2 * C, C), am, Np, g.Tm, g.Tm, t.heads, d, 0, 1);
+            if (!c.dry && !c.err) {
+                prof_open(c.stream, "tome_unmerge_kernel", 0.0, 4.0 * Mp * C);
+                c.err = launch_tome_unmerge(am.p, am.ld, C, plan, Np, T, att.p, att.ld, c.stream);
+                prof_close(c.stream);
+            }
+            op_conv(c, b.out1, att, Np, H, W, t2, 1, 0, nullptr, 0, &cur, 0, -1, 0, fold ? &f_t2 : nullptr);
+        } else if (!perturb) {
             op_attention(c, qkv.slice(0, C), qkv.slice(C, C), qkv.slice(2 * C, C), att, Np, T, T, t.heads, d, 0, 1);
             op_conv(c, b.out1, att, Np, H, W, t2, 1, 0, nullptr, 0, &cur, 0, -1, 0, fold ? &f_t2 : nullptr);
         } else {
@@ -1164,7 +1206,10 @@ int UNet::run(Ctx& c, const UNetCall& call, int dc) {
         const int ring_next = c.gn_next, ring_groups = c.gn_groups;
         TapSink* const tap = c.tap;         // (the ControlNet's encoder shares run_down / run_mid: its blocks are not tapped)
         c.tap = nullptr;
+        const TomeRun* const tome_run = c.tome;     // (and they run without token merging)
+        c.tome = nullptr;
         if (int rc = run_controlnet(c, call, cn_sites, cn_mid)) return rc;
+        c.tome = tome_run;
         c.tap = tap;
         for (int i = 0; i < Ctx::kGnPool; ++i) c.gnpool[i] = ring[i];
         c.gn_next = ring_next; c.gn_groups = ring_groups;
@@ -1539,6 +1584,31 @@ int UNet::forward(const UNetCall& in, hipStream_t stream) {
     }
     const bool use_cn = cn && call.cn_scale != 0.f;
     if (freeu_on && graph_enabled) { set_error("unet: graph replay with FreeU enabled is not supported"); return 4; }
+    // token merging: which blocks merge at this shape, and their plan buffers, before anything is launched
+    const bool tome_on = tome.ratio > 0.0;
+    tome.plan_off.clear();
+    tome.buf = nullptr;
+    if (tome_on) {
+        if (graph_enabled) { set_error("unet: graph replay with token merging enabled is not supported"); return 4; }
+        if (pag) { set_error("unet: forward_pag with token merging enabled is not supported"); return 4; }
+        if (call.extra) { set_error("unet: forward_concat with token merging enabled is not supported"); return 4; }
+        // (no test composes these with token merging yet: refused, not silently trusted)
+        if (freeu_on) { set_error("unet: FreeU with token merging enabled is not supported"); return 4; }
+        if (cn) { set_error("unet: a ControlNet attached with token merging enabled is not supported"); return 4; }
+        if (ip) { set_error("unet: an IP-Adapter attached with token merging enabled is not supported"); return 4; }
+        std::vector<TomeUsed> sites;
+        size_t bytes = 0;
+        if (int rc = tome_layout(B, H, W, &sites, &bytes)) return rc;
+        bool grew = false;
+        if (int rc = tome_buf.reserve(bytes > 0 ? bytes : 256, &grew)) return rc;
+        tome.buf = tome_buf.data();
+        for (const TomeUsed& u : sites) {
+            if ((size_t)u.site >= tome.plan_off.size()) tome.plan_off.resize((size_t)u.site + 1, -1);
+            tome.plan_off[(size_t)u.site] = u.plan_off;
+        }
+        tome_used.clear();
+        tome.used = &tome_used;
+    }
     const int dc = dc_mode;
     if (dc != SD_DC_PLAIN) {
         if (dc_depth <= 0) { set_error("unet: DeepCache store / reuse mode while the depth is 0"); return 2; }
@@ -1581,9 +1651,11 @@ int UNet::forward(const UNetCall& in, hipStream_t stream) {
     key.n_ctrl = use_cn ? call.n_ctrl : 0;
     key.dc_depth = dc != SD_DC_PLAIN ? dc_depth : 0;
     key.cat_rows = call.extra ? call.lat_rows : 0;
+    if (tome_on) { key.tome_ratio = tome.ratio; key.tome_ds = tome_max_ds; key.tome_sx = tome.sx; key.tome_sy = tome.sy; }
     if (taps.on) taps.clear();              // one forward's records at a time
     const int rc = plan_and_run(arena, stream, planned[dc], key, "unet", [&](Ctx& c) {
         c.tap = taps.on ? &taps : nullptr;
+        c.tome = tome_on ? &tome : nullptr;
         return run(c, call, dc);
     });
     if (!rc && dc == SD_DC_STORE) dc_tag.set(nullptr, B, H, W, cfg_in != nullptr);
@@ -1606,6 +1678,60 @@ int UNet::set_deep_cache(int depth) {
     dc_mode = SD_DC_PLAIN;
     dc_tag.clear();
     return depth == 0 ? dc_buf.release() : 0;
+}
+
+int UNet::set_tome(double ratio, int max_downsample, int sx, int sy, int use_rand, uint32_t seed) {
+    if (!(ratio >= 0.0 && ratio <= 0.75)) { set_error("unet: token merging ratio must be in [0, 0.75]"); return 1; }
+    if (ratio == 0.0) {
+        dc_tag.clear();                 // (a DeepCache feature stored under other settings is stale)
+        tome.ratio = 0.0;
+        tome_used.clear();
+        return tome_buf.release();
+    }
+    if (sx < 1 || sx > 8 || sy < 1 || sy > 8) { set_error("unet: token merging cell sizes sx, sy must be in 1..8"); return 1; }
+    if (max_downsample != 1 && max_downsample != 2 && max_downsample != 4 && max_downsample != 8) {
+        set_error("unet: token merging max_downsample must be 1, 2, 4 or 8");
+        return 1;
+    }
+    dc_tag.clear();
+    tome.ratio = ratio; tome.sx = sx; tome.sy = sy; tome.use_rand = use_rand ? 1 : 0; tome.seed = seed;
+    tome_max_ds = max_downsample;
+    tome_used.clear();
+    return 0;
+}
+
+int UNet::tome_layout(int B, int H, int W, std::vector<TomeUsed>* sites, size_t* bytes) {
+    const int nb = cfg.num_blocks;
+    size_t at = 0;
+    int rc = 0;
+    auto visit = [&](const Xformer& t, int level) {
+        const int h = H >> level, w = W >> level;
+        if ((1 << level) > tome_max_ds || rc) return;
+        for (size_t bi = 0; bi < t.blocks.size(); ++bi) {
+            TomeGeom g;
+            if ((rc = tome_geom(h, w, tome.sx, tome.sy, tome.ratio, tome.use_rand, tome.seed, tome.step,
+                                (uint32_t)(t.tome_site0 + (int)bi), &g)))
+                return;
+            if (g.r < 1) continue;                                  // nothing to merge: the plain path, bit for bit
+            if (!tome_supported(g)) {
+                set_error("unet: token merging on a " + std::to_string(h) + " x " + std::to_string(w) +
+                          " map is not supported (more than 16384 tokens, or no whole cell)");
+                rc = 4;
+                return;
+            }
+            TomeUsed u;
+            u.site = t.tome_site0 + (int)bi; u.H = h; u.W = w; u.r = g.r; u.Tm = g.Tm; u.B = B; u.plan_off = (long)at;
+            sites->push_back(u);
+            at += ((size_t)tome_plan_bytes(B, g.T) + 255) & ~size_t(255);
+        }
+    };
+    for (int i = 0; i < nb && i < (int)down_att.size(); ++i)
+        for (const Xformer& t : down_att[(size_t)i]) visit(t, i);
+    visit(mid_att, nb - 1);
+    for (int i = 0; i < nb && i < (int)up_att.size(); ++i)
+        for (const Xformer& t : up_att[(size_t)i]) visit(t, nb - 1 - i);
+    *bytes = at;
+    return rc;
 }
 
 bool unet_cfg_share_eligible(const sd_unet_config& cfg) {

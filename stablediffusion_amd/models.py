@@ -157,6 +157,7 @@ class HipUNet2DConditionModel:
         self._freeu = None             # (s1, s2, b1, b2) while FreeU is on (enable_freeu)
         self._deepcache = None         # (cache_interval, cache_depth) while DeepCache is on (enable_deepcache)
         self._pag = ()                 # site keys of the perturbed transformers (set_pag_layers)
+        self._tome = None              # (ratio, max_downsample, sx, sy, use_rand, seed) while token merging is on
 
     # -- weights -------------------------------------------------------------------------------
     def load_state_dict(self, state_dict: Dict[str, torch.Tensor], strict: bool = True):
@@ -177,6 +178,8 @@ class HipUNet2DConditionModel:
             new.enable_deepcache(*self._deepcache)
         if self._pag:                        # and the perturbed-attention layers
             new.set_pag_layers(self._pag)
+        if self._tome is not None:           # and token merging
+            new.enable_tome(*self._tome)
         return new
 
     def rebuild_factory(self):
@@ -259,6 +262,62 @@ class HipUNet2DConditionModel:
         _lib.check(self._lib.sd_unet_set_freeu(self._h, 0, 1.0, 1.0, 1.0, 1.0), "sd_unet_set_freeu")
         self._freeu = None
         return self
+
+    def enable_tome(self, ratio: float = 0.5, max_downsample: int = 1, sx: int = 2, sy: int = 2, use_rand: bool = True,
+                    seed: int = 0):
+        """Token merging (tomesd.apply_patch with its defaults, same argument names): the self-attention of every
+        transformer block at most `max_downsample` times smaller than the sample runs on the tokens left after
+        `int(T * ratio)` of them were merged into their most similar destination token (one per `sy` x `sx` cell, drawn
+        per step when `use_rand`).  Lossy and opt-in.  The settings survive `rebuild`.  Not available under `use_graph`,
+        in `forward_pag` or on an 8-channel edit UNet's two-source forward."""
+        if isinstance(ratio, bool) or not isinstance(ratio, (int, float)) or not 0.0 <= float(ratio) <= 0.75:
+            raise ValueError(f"enable_tome: ratio must be in [0, 0.75], got {ratio!r}")
+        for name, v in (("sx", sx), ("sy", sy)):
+            if isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= 8:
+                raise ValueError(f"enable_tome: {name} must be an int in 1..8, got {v!r}")
+        if isinstance(max_downsample, bool) or max_downsample not in (1, 2, 4, 8):
+            raise ValueError(f"enable_tome: max_downsample must be 1, 2, 4 or 8, got {max_downsample!r}")
+        if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 32:
+            raise ValueError(f"enable_tome: seed must be an int in [0, 2^32), got {seed!r}")
+        if float(ratio) == 0.0:
+            return self.disable_tome()
+        vals = (float(ratio), int(max_downsample), int(sx), int(sy), bool(use_rand), int(seed))
+        _lib.check(self._lib.sd_unet_set_tome(self._h, vals[0], vals[1], vals[2], vals[3], int(vals[4]), vals[5]),
+                   "sd_unet_set_tome")
+        self._tome = vals
+        return self
+
+    def disable_tome(self):
+        """The forward is again exactly the plain one and the engine releases the merge plans' buffer."""
+        _lib.check(self._lib.sd_unet_set_tome(self._h, 0.0, 1, 2, 2, 0, 0), "sd_unet_set_tome")
+        self._tome = None
+        return self
+
+    @property
+    def tome(self):
+        """(ratio, max_downsample, sx, sy, use_rand, seed) while token merging is on, else None."""
+        return self._tome
+
+    def tome_step(self, i: int):
+        """The denoising iteration the destination draw of the following forwards hashes (the pipeline's loop calls it)."""
+        _lib.check(self._lib.sd_unet_tome_step(self._h, int(i) & 0xFFFFFFFF), "sd_unet_tome_step")
+        return self
+
+    def tome_sites(self):
+        """The blocks that merged in the last forward, in execution order: dicts with site, H, W, r, T_merged and the
+        unmerge maps [images, H * W] (int32 tensor on the CPU)."""
+        out = []
+        for k in range(self._lib.sd_unet_tome_sites(self._h)):
+            info = (C.c_int32 * 5)()
+            n = self._lib.sd_unet_tome_read(self._h, k, info, None, 0)
+            if n < 0:
+                _lib.check(-n, "sd_unet_tome_read")
+            maps = torch.empty(n, info[1] * info[2], dtype=torch.int32)
+            n = self._lib.sd_unet_tome_read(self._h, k, info, C.cast(maps.data_ptr(), C.POINTER(C.c_int32)), maps.numel())
+            if n < 0:
+                _lib.check(-n, "sd_unet_tome_read")
+            out.append(dict(site=info[0], H=info[1], W=info[2], r=info[3], T_merged=info[4], maps=maps))
+        return out
 
     def set_pag_layers(self, layers):
         """Which transformers `forward_pag` perturbs: diffusers' `pag_applied_layers` spellings ("mid", "down.block_2",

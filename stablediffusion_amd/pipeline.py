@@ -168,9 +168,12 @@ class SDModelWrapper:
         graph = bool(getattr(old, "_graph_on", False))
         freeu = getattr(old, "_freeu", self._freeu)     # the engine's own record wins: enable_freeu may be called on .base
         deepcache = getattr(old, "deepcache", self._deepcache)
+        tome = getattr(old, "tome", None)
         self.base = None                     # the old engine's device memory goes before the new one is packed
         del old
         self.base = self._rebuild_from(fused, graph, freeu, deepcache, self._pag)
+        if tome is not None:                 # token merging survives the re-fuse too
+            self.base.enable_tome(*tome)
         for part in ("text_encoder", "text_encoder_2"):
             if self._te_sd[part] is not None and (self._lora.touches(part) or self._lora_applied is not None):
                 enc = getattr(self, part, None)
@@ -231,6 +234,14 @@ class SDModelWrapper:
     def disable_deepcache(self):
         self.base.disable_deepcache()
         self._deepcache = None
+
+    # ---- token merging (tomesd.apply_patch's arguments; forwarded to the base UNet, the refiner runs plain) ----
+    def enable_tome(self, ratio: float = 0.5, max_downsample: int = 1, sx: int = 2, sy: int = 2, use_rand: bool = True,
+                    seed: int = 0):
+        self.base.enable_tome(ratio, max_downsample, sx, sy, use_rand, seed)
+
+    def disable_tome(self):
+        self.base.disable_tome()
 
     # ---- ControlNet (diffusers ControlNetModel, one per model; the pipeline takes control_image=) ----
     def _attach_cn(self, base):
@@ -611,6 +622,23 @@ class StableDiffusionUnifiedPipeline:
         if hasattr(model, "apply_adapters"):
             model.apply_adapters()
         unet = self._unet(model)             # (after the re-fuse, which replaces model.base)
+        if getattr(unet, "tome", None) is not None:
+            # token merging: what the engine's forward refuses is refused here, before anything runs
+            if pag_on:
+                raise NotImplementedError("token merging (enable_tome) with perturbed-attention guidance (pag_scale > 0) is "
+                                          "not supported (disable_tome)")
+            if unet.config.in_channels == 8:
+                raise NotImplementedError("token merging (enable_tome) with an 8-channel edit UNet is not supported: its "
+                                          "two-source forward runs without it (disable_tome)")
+            if getattr(unet, "_graph_on", False):
+                raise NotImplementedError("token merging (enable_tome) under use_graph is not supported (disable_tome)")
+            if view_window is not None:
+                raise NotImplementedError("token merging (enable_tome) with view_window (MultiDiffusion) is not supported "
+                                          "(disable_tome)")
+            for attr, what in (("_freeu", "FreeU enabled"), ("_cn", "a ControlNet loaded"), ("_ip", "an IP-Adapter loaded")):
+                if getattr(unet, attr, None) is not None:
+                    raise NotImplementedError(f"token merging (enable_tome) with {what} is not supported yet: the engine's "
+                                              "forward refuses the combination (disable_tome)")
         if pag_on:
             if getattr(unet, "deepcache", None) is not None:
                 raise NotImplementedError("perturbed-attention guidance (pag_scale > 0) with DeepCache enabled is not "
@@ -853,6 +881,7 @@ class StableDiffusionUnifiedPipeline:
         deepcache = getattr(unet, "deepcache", None)
         if deepcache is not None and control is not None:
             raise ValueError("DeepCache runs no ControlNet on its reuse steps: disable_deepcache() or drop control_image")
+        tome_on = getattr(unet, "tome", None) is not None and hasattr(unet, "tome_step")
         kv_cache = getattr(unet, "text_kv_cache", None)
         if kv_cache is not None:
             # the cache is keyed by the buffer's address: hand the engine ONE fp16 contiguous tensor for the whole loop
@@ -914,6 +943,8 @@ class StableDiffusionUnifiedPipeline:
                                                             controlnet_conditioning_scale=cn_scales[i])
                 if deepcache is not None:
                     unet.deep_cache_mode(_DC_STORE if i % deepcache[0] == 0 else _DC_REUSE)
+                if tome_on:
+                    unet.tome_step(i)        # the iteration token merging's destination draw hashes
                 # the step's noise, drawn before the forward.  The affine schedulers that add noise draw it as their `step`
                 # does: from the global generator, once per step (the last included, whose noise coefficient is 0), so the
                 # device and the host loop consume the same stream
