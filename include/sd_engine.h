@@ -741,7 +741,8 @@ int sd_op_conv2d_gnstats(const void* x_nhwc, const void* w_oihw, const void* bia
  *   y[n,oh,ow,co] = bias[co] + rowadd[n,co] + res[n,oh,ow,co]
  *                 + sum_{kh,kw,ci} x[n, (oh*stride+kh-pad)>>up, (ow*stride+kw-pad)>>up, ci] * w[co,kh,kw,ci]
  * w is PyTorch [Cout,Cin,KH,KW] (f16, device), bias [Cout] / rowadd [N,Cout] f32 device (nullable);
- * packed internally per call (test path only; synchronises). */
+ * packed per call by the packers a model load uses (the bias stays f32; GEGLU needs ksize 1) and run through the engine's
+ * op_conv halves on a private arena (test path only; synchronises). */
 int sd_op_conv2d(const void* x_nhwc, const void* w_oihw, const void* bias, const void* rowadd,
                  const void* res_nhwc, void* y_nhwc, int N, int H, int W, int Cin, int Cout,
                  int ksize, int stride, int upsample2x, int geglu, void* stream);
@@ -752,8 +753,8 @@ int sd_op_conv2d(const void* x_nhwc, const void* w_oihw, const void* bias, const
  *                     downsample (right / bottom zero column), output size as in sd_igemm_plan
  *   act               0 none, 1 quick-GELU, 2 erf-GELU after the bias
  *   acc_scale, bias_scale   y = acc_scale * conv + bias_scale * bias (+ rowadd + res), powers of two
- *   gn_groups         > 0: the launch is also asked for the GroupNorm summaries of y for that many groups (left in a
- *                     buffer dropped on return); a split launch then reduces with splitk_epilogue_gs_kernel
+ *   gn_groups         > 0: the launch is also asked for the GroupNorm summaries of y for that many groups (ConvFuse::gn_out,
+ *                     a buffer dropped on return); a split launch then reduces with splitk_epilogue_gs_kernel
  *   ran[4]            out: kind and tile variant of the plan the launch ran (as sd_igemm_plan's out[0], out[1]), the
  *                     split-K slices the launcher started (at most the planned count), the reduction kernel behind
  *                     them (0 none, 1 splitk_epilogue_kernel, 2 splitk_epilogue_gs_kernel)
@@ -769,7 +770,8 @@ int sd_op_conv2d_ex(const void* x_nhwc, const void* w_oihw, const void* bias, co
  *   SD_NO_UPCONV_FOLD unset.  Host only.
  * sd_op_fold_upconv: the folded pack of w_oihw [Cout, Cin, 3, 3] f16 into `out` [4][Cout][4 Cin] f16 (device): parity
  *   panel dy * 2 + dx, K order [Cin / 64][a][b][64]; taps summed in fp32 (kernel rows outside, columns inside), rounded
- *   to f16 once.
+ *   to f16 once.  Built by the packer of a model load (pack_conv with the fold), which folds for Cout % 8 == 0 only:
+ *   SD_ERR_UNSUPPORTED otherwise.
  * sd_op_upconv2x_ex: sd_op_conv2d_ex with ksize 3, stride 1, upsample2x 1 and no GEGLU / activation, packed and
  *   dispatched as the models do it (both packs, op_conv's decision).  gn_summaries (optional, with gn_groups > 0):
  *   receives the GroupNorm summaries the launch left, [N][S][gn_groups][2] floats (mean, M2), in a buffer of at least
@@ -799,8 +801,9 @@ int sd_op_conv2d_groupnorm(const void* x_nhwc, const void* w_oihw, const void* b
  * norm2 -> SiLU -> conv2; diffusers resnet.py under sd_unified_pipeline.py:475-482, :523):
  *   y = conv(act(GroupNorm(x; gamma, beta, groups, eps))) + bias + rowadd + res
  * For 3x3 / stride-1 convolutions the convolution applies the norm to its input tiles in LDS and the normalised
- * tensor never exists in HBM (*fused = 1); otherwise a GroupNorm kernel runs first (*fused = 0).  iters > 0: timed
- * like sd_bench_conv2d (the statistics pass is outside the timed launches), ms_per_launch written. */
+ * tensor never exists in HBM (*fused = 1: op_gn_conv_fused took it; SD_NO_GN_FUSE=1 turns that off); otherwise a
+ * GroupNorm kernel runs first (*fused = 0).  iters > 0: timed like sd_bench_conv2d (the statistics pass is outside the
+ * timed launches), ms_per_launch written. */
 int sd_op_groupnorm_conv2d(const void* x_nhwc, const void* gamma, const void* beta, int groups, float eps, int silu,
                            const void* w_oihw, const void* bias, const void* rowadd, const void* res_nhwc, void* y_nhwc,
                            int N, int H, int W, int Cin, int Cout, int ksize, int iters, float* ms_per_launch, int* fused,
@@ -891,7 +894,8 @@ int sd_op_ffn_geglu_proj_out(const void* x_in, const void* t3, const void* ln_ga
                              const void* b_po, void* y, float* gn_summaries, int* gn_rows, int M, int C, int imgs, int* fused,
                              void* stream);
 /* Same operator, timed: `iters` back-to-back launches bracketed by HIP events on `stream`
- * (after two warm-up launches); used by tools/tune_igemm.py to pick tile variants per shape. */
+ * (after two warm-up launches); used by tools/tune_igemm.py to pick tile variants per shape.  The launch is planned once,
+ * ahead of the loop: a timed launch is launch_igemm2 on that plan, nothing else. */
 int sd_bench_conv2d(const void* x_nhwc, const void* w_oihw, void* y_nhwc, int N, int H, int W, int Cin,
                     int Cout, int ksize, int stride, int upsample2x, int geglu, int iters,
                     float* ms_per_launch, void* stream);

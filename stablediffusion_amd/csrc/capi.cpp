@@ -1,5 +1,6 @@
 // extern "C" surface of libsd_engine.so -- see include/sd_engine.h for the contract and for the
 // reference interfaces (file:line) each entry point replaces.
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <new>
@@ -1003,229 +1004,221 @@ int sd_prof_collect(sd_prof_entry* out, int max_entries, int* n_entries) {
 }
 
 // ------------------------------------------------------------------------- single-operator entries
-// Test / tuner path only: packs the weight on every call (allocation + sync); never used by the models.
-// Device buffers of the single-operator entries: freed on every return path (hipFree waits for the device),
-// including the SD_HIP_CHECK early returns.
-struct DevScope {
-    std::vector<void*> bufs;
-    ~DevScope() { for (void* p : bufs) (void)hipFree(p); }
-    void drop(void* p) { for (auto& b : bufs) if (b == p) { (void)hipFree(b); b = nullptr; } }
-};
-#define SD_DEV_ALLOC(scope, ptr, bytes)                                              \
-    do {                                                                             \
-        SD_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&(ptr)), (bytes)));          \
-        (scope).bufs.push_back(ptr);                                                 \
-    } while (0)
+// Test / tuner path only: packs the weight on every call (allocation + sync); never used by the models.  The entries
+// pack with the engine's packers (a local WeightStore owns the packed buffers and frees them on every return path) and
+// run through the engine's op wrappers on a private arena, so they exercise the host code a forward runs.
 
-// Optional GroupNorm behind the convolution (sd_op_conv2d_groupnorm): the conv's epilogue leaves the
-// GroupNorm summaries when the launch can (IGemmPlan::gnstats), the GroupNorm then skips its own pass.
-struct GnTail {
-    const float* gamma; const float* beta; void* y; int groups; float eps; int silu; int* fused;
-};
+}  // extern "C"
 
-// Optional GroupNorm (+ SiLU) in FRONT of the convolution (sd_op_groupnorm_conv2d): statistics pass over x, then the
-// convolution applies the norm to its halo tiles in LDS (igemm2_gn_fusable) -- or, when the launch cannot, a GroupNorm
-// kernel runs first; *fused tells which path ran.
-struct GnHead {
-    const float* gamma; const float* beta; int groups; float eps; int silu; int* fused;
-};
-
-// [hidden | gate] rows (half_rows each) -> every 128-row group = 64 hidden rows, then their 64 gate rows, weights
-// [.][K] and bias alike: mirrors WeightStore::pack_geglu.
-static int geglu_interleave(half_t* wg, float* bg, const half_t* w, const float* b, long half_rows, long K, hipStream_t s) {
-    for (long blk = 0; blk < half_rows / 64; ++blk) {
-        SD_HIP_CHECK(hipMemcpyAsync(wg + blk * 128 * K, w + blk * 64 * K, (size_t)64 * K * 2, hipMemcpyDeviceToDevice, s));
-        SD_HIP_CHECK(hipMemcpyAsync(wg + (blk * 128 + 64) * K, w + (half_rows + blk * 64) * K, (size_t)64 * K * 2, hipMemcpyDeviceToDevice, s));
-        SD_HIP_CHECK(hipMemcpyAsync(bg + blk * 128, b + blk * 64, 64 * 4, hipMemcpyDeviceToDevice, s));
-        SD_HIP_CHECK(hipMemcpyAsync(bg + blk * 128 + 64, b + half_rows + blk * 64, 64 * 4, hipMemcpyDeviceToDevice, s));
-    }
-    return 0;
-}
-
-// y[M, ldy] = x[M, K] W^T + bias as a pointwise problem of Cout GEMM columns (one image of M x 1 pixels)
-static IGemmParams pointwise_params(const half_t* x, const half_t* w, const float* bias, half_t* y, long ldy, int M, int K, int Cout) {
-    IGemmParams p{};
-    p.x = x; p.ldx = K; p.w = w; p.bias = bias; p.y = y; p.ldy = ldy;
-    p.N = 1; p.H = M; p.W = 1; p.Cin = K; p.OH = M; p.OW = 1; p.Cout = Cout; p.KS = 1; p.stride = 1; p.pad = 0; p.up = 0;
-    p.M = M; p.K = K;
-    return p;
-}
-
-// What sd_op_conv2d_ex adds to the plain entry: operand strides in elements, an explicit padding (-1: the kernel size's
-// default), the epilogue's activation and scales, GroupNorm summaries asked of the launch (into a buffer dropped on
-// return: they pick the split-K reduction kernel), and `ran` = kind, variant, split-K slices launched, reduction kernel.
-struct ConvEx {
-    long ldx, ldres, ldy;
-    int pad, act;
-    float acc_scale, bias_scale;
-    int gn_groups;
-    int* ran;
-    float* gn_copy = nullptr;       // sd_op_conv2d_gnstats: the summaries the launch left are copied here (gn_copy_floats at most)
-    long gn_copy_floats = 0;
-    int* gn_rows = nullptr;         // ... and the pixels per summary (0: none left)
-};
-
-static int conv2d_impl(const void* x, const void* w_oihw, const void* bias_f32, const void* rowadd_f32, const void* res,
-                       void* y, int N, int H, int W, int Cin, int Cout, int ksize, int stride, int upsample2x,
-                       int geglu, void* stream, int iters, float* ms_out, const GnTail* gn = nullptr,
-                       const GnHead* gh = nullptr, const ConvEx* ex = nullptr) {
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const long K = (long)ksize * ksize * Cin;
-    if (K % 64 != 0 || Cin % 64 != 0) { set_error("sd_op_conv2d: Cin must be a multiple of 64"); return SD_ERR_INVALID; }
-    const long rows = (Cout + kWeightRowPad - 1) / kWeightRowPad * kWeightRowPad;
-    DevScope scope;
-    half_t* wp = nullptr;
-    float* bp = nullptr;
-    SD_DEV_ALLOC(scope, wp, (size_t)rows * K * sizeof(half_t));
-    SD_DEV_ALLOC(scope, bp, (size_t)rows * sizeof(float));
-    SD_HIP_CHECK(hipMemsetAsync(wp, 0, (size_t)rows * K * sizeof(half_t), s));
-    SD_HIP_CHECK(hipMemsetAsync(bp, 0, (size_t)rows * sizeof(float), s));
-    int rc = launch_pack_conv(static_cast<const half_t*>(w_oihw), wp, Cout, Cin, ksize, ksize, K, s);
-    if (!rc && bias_f32)
-        SD_HIP_CHECK(hipMemcpyAsync(bp, bias_f32, (size_t)Cout * sizeof(float), hipMemcpyDeviceToDevice, s));
-    if (!rc && geglu) {
-        half_t* wg = nullptr; float* bg = nullptr;
-        SD_DEV_ALLOC(scope, wg, (size_t)rows * K * sizeof(half_t));
-        SD_DEV_ALLOC(scope, bg, (size_t)rows * sizeof(float));
-        SD_HIP_CHECK(hipMemsetAsync(wg, 0, (size_t)rows * K * sizeof(half_t), s));
-        SD_HIP_CHECK(hipMemsetAsync(bg, 0, (size_t)rows * sizeof(float), s));
-        if (int r = geglu_interleave(wg, bg, wp, bp, Cout / 2, K, s)) return r;
-        SD_HIP_CHECK(hipStreamSynchronize(s));
-        scope.drop(wp); scope.drop(bp);
-        wp = wg; bp = bg;
-    }
-    float* partial = nullptr;
+namespace {
+// Two untimed calls of `launch`, then `iters` of them between two events on `s`: *ms = milliseconds per call.
+template <class F>
+int time_launches(hipStream_t s, int iters, float* ms, F launch) {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    int rc = 0;
+    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) { set_error("hipEventCreate failed"); rc = SD_ERR_HIP; }
+    for (int it = 0; it < 2 && !rc; ++it) rc = launch();
+    if (!rc) (void)hipEventRecord(e0, s);
+    for (int it = 0; it < iters && !rc; ++it) rc = launch();
     if (!rc) {
-        IGemmParams p = conv_problem(N, H, W, Cin, Cout, ksize, stride, upsample2x, ex ? ex->pad : -1);
-        p.x = static_cast<const half_t*>(x); p.ldx = Cin;
-        p.w = wp; p.bias = bp;
-        p.rowadd = static_cast<const float*>(rowadd_f32); p.rowadd_ld = Cout;
-        p.res = static_cast<const half_t*>(res);
-        p.geglu = geglu;
-        const int ocols = geglu ? Cout / 2 : Cout;
-        p.ldres = ocols; p.y = static_cast<half_t*>(y); p.ldy = ocols;
-        float* gnbuf = nullptr;
-        float* gnscratch = nullptr;
-        if (ex) {
-            p.ldx = ex->ldx; p.ldres = ex->ldres; p.ldy = ex->ldy;
-            p.act = ex->act; p.acc_scale = ex->acc_scale; p.bias_scale = ex->bias_scale;
-            if (ex->gn_groups > 0) SD_DEV_ALLOC(scope, gnbuf, (size_t)gnstat_floats(N, (long)p.OH * p.OW, ex->gn_groups) * 4);
-        }
-        if (gn) {
-            if (gn->fused) *gn->fused = 0;
-            SD_DEV_ALLOC(scope, gnscratch, (size_t)gn_scratch_floats(N, (long)p.OH * p.OW, Cout, gn->groups) * 4);
-            SD_DEV_ALLOC(scope, gnbuf, (size_t)gnstat_floats(N, (long)p.OH * p.OW, gn->groups) * 4);
-        }
-        if (gh) {
-            if (gh->fused) *gh->fused = 0;
-            const long HW = (long)H * W;
-            float* hscratch = nullptr;
-            SD_DEV_ALLOC(scope, hscratch, (size_t)(gn_scratch_floats(N, HW, Cin, gh->groups) + (long)N * gh->groups * 2) * 4);
-            static const bool no_fuse = getenv("SD_NO_GN_FUSE") != nullptr;
-            if (!no_fuse && Cin % 64 == 0 && igemm2_gn_fusable(p, gh->groups)) {
-                // [Cin / 64][64 gamma | 64 beta], as WeightStore::pack_norm leaves it
-                float* gb = nullptr;
-                SD_DEV_ALLOC(scope, gb, (size_t)Cin * 2 * 4);
-                for (int blk = 0; blk < Cin / 64; ++blk) {
-                    SD_HIP_CHECK(hipMemcpyAsync(gb + blk * 128, gh->gamma + blk * 64, 256, hipMemcpyDeviceToDevice, s));
-                    SD_HIP_CHECK(hipMemcpyAsync(gb + blk * 128 + 64, gh->beta + blk * 64, 256, hipMemcpyDeviceToDevice, s));
-                }
-                GnStats st;
-                rc = launch_gn_stats(p.x, p.ldx, N, HW, Cin, gh->groups, hscratch, &st, s);
-                if (!rc && st.S > 64) rc = launch_gn_finalize(&st, hscratch + gn_scratch_floats(N, HW, Cin, gh->groups), N, HW, Cin, gh->groups, s);
-                p.gni_part = st.part; p.gni_S = st.S; p.gni_rows = st.rows; p.gni_groups = gh->groups; p.gni_eps = gh->eps;
-                p.gni_silu = gh->silu; p.gni_gb = gb;
-                if (gh->fused) *gh->fused = 1;
-            } else {
-                half_t* hn = nullptr;
-                SD_DEV_ALLOC(scope, hn, (size_t)N * HW * Cin * sizeof(half_t));
-                rc = launch_groupnorm(p.x, p.ldx, gh->gamma, gh->beta, hn, Cin, N, HW, Cin, gh->groups, gh->eps, gh->silu, hscratch, s);
-                p.x = hn;
-            }
-        }
-        half_t* res_bench = nullptr;   // SD_BENCH_RES=1 (tuner): time the launch with the fused residual add
-        if (ms_out && !res && getenv("SD_BENCH_RES")) {
-            SD_DEV_ALLOC(scope, res_bench, (size_t)p.M * ocols * sizeof(half_t));
-            SD_HIP_CHECK(hipMemsetAsync(res_bench, 0, (size_t)p.M * ocols * sizeof(half_t), s));
-            p.res = res_bench;
-        }
-        // planned as op_conv plans, but without a folded pack: an upsampling launch here runs the 9-tap kernels
-        const IGemmRequest rq{nullptr, gnbuf, gn ? gn->groups : ex ? ex->gn_groups : 0};
-        const IGemmPlan plan = conv_plan(p, nullptr, rq);
-        if (ex && !plan.scales_ok && (p.acc_scale != 1.f || p.bias_scale != 1.f)) {
-            set_error("sd_op_conv2d_ex: the planned kernel does not take acc_scale / bias_scale"); return SD_ERR_INVALID;
-        }
-        if (ex && plan.kind == kKindIgemm1 && p.act) {
-            set_error("sd_op_conv2d_ex: the planned kernel has no activation epilogue"); return SD_ERR_INVALID;
-        }
-        if (plan.partial_floats > 0) SD_DEV_ALLOC(scope, partial, (size_t)plan.partial_floats * sizeof(float));
-        GnStats gst;
-        if (plan.gnstats) {
-            gst.part = gnbuf; gst.rows = plan.gn_rows; gst.S = p.OH * p.OW / plan.gn_rows;
-            if (gn && gn->fused) *gn->fused = 1;
-        }
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (ms_out) { SD_HIP_CHECK(hipEventCreate(&e0)); SD_HIP_CHECK(hipEventCreate(&e1)); }
-        // SD_BENCH_COLD_MB=<n> (tuner): rotate through copies of the packed weights totalling n MB, so
-        // every timed launch streams its weights from HBM as it does inside a UNet forward (1.7 GB of
-        // weights per forward never stay in the 256 MB Infinity Cache); unset = same buffer every launch.
-        half_t* wring = nullptr;
-        long nrot = 1;
-        const size_t wbytes = (size_t)rows * K * sizeof(half_t);
-        if (ms_out) {
-            const char* cold = getenv("SD_BENCH_COLD_MB");
-            const long mb = cold ? atol(cold) : 0;
-            if (mb > 0) {
-                nrot = ((long)mb * 1000000L + (long)wbytes - 1) / (long)wbytes;
-                if (nrot > iters + 2) nrot = iters + 2;
-                if (nrot > 1) {
-                    SD_DEV_ALLOC(scope, wring, wbytes * (size_t)nrot);
-                    for (long r = 0; r < nrot; ++r)
-                        SD_HIP_CHECK(hipMemcpyAsync(reinterpret_cast<char*>(wring) + wbytes * (size_t)r, wp, wbytes,
-                                                    hipMemcpyDeviceToDevice, s));
-                }
-            }
-        }
-        for (int it = 0; it < iters + (ms_out ? 2 : 0) && !rc; ++it) {
-            if (ms_out && it == 2) SD_HIP_CHECK(hipEventRecord(e0, s));     // two warm-up launches
-            if (wring) p.w = reinterpret_cast<half_t*>(reinterpret_cast<char*>(wring) + wbytes * (size_t)(it % nrot));
-            rc = launch_igemm2(p, partial, s, &plan);
-        }
-        if (ex && ex->ran) {
-            const IGemmLaunchNote note = igemm2_last_launch();
-            ex->ran[0] = plan.kind; ex->ran[1] = plan.variant; ex->ran[2] = note.splits; ex->ran[3] = note.reducer;
-        }
-        if (ex && ex->gn_rows) {
-            *ex->gn_rows = plan.gnstats ? plan.gn_rows : 0;
-            long n = gnstat_floats(N, (long)p.OH * p.OW, ex->gn_groups);
-            if (n > ex->gn_copy_floats) n = ex->gn_copy_floats;
-            if (plan.gnstats && ex->gn_copy && n > 0 && !rc)
-                SD_HIP_CHECK(hipMemcpyAsync(ex->gn_copy, gnbuf, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, s));
-        }
-        if (gn && !rc)
-            rc = launch_groupnorm(p.y, p.ldy, gn->gamma, gn->beta, static_cast<half_t*>(gn->y), Cout, N, (long)p.OH * p.OW, Cout,
-                                  gn->groups, gn->eps, gn->silu, gnscratch, s, gst.part ? &gst : nullptr);
-        if (gn) (void)hipStreamSynchronize(s);
-        if (ms_out && !rc) {
-            SD_HIP_CHECK(hipEventRecord(e1, s));
-            SD_HIP_CHECK(hipEventSynchronize(e1));
-            float ms = 0.f;
-            SD_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-            *ms_out = ms / (float)iters;
-        }
-        if (e0) { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); }
-        if (wring || res_bench) (void)hipStreamSynchronize(s);
+        float t = 0.f;
+        hipError_t e = hipEventRecord(e1, s);
+        if (e == hipSuccess) e = hipEventSynchronize(e1);
+        if (e == hipSuccess) e = hipEventElapsedTime(&t, e0, e1);
+        if (e != hipSuccess) { set_error(hipGetErrorString(e)); rc = SD_ERR_HIP; }
+        *ms = t / (float)iters;
     }
-    hipError_t e = hipStreamSynchronize(s);
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    return rc;
+}
+
+// `launch` once, or timed when iters > 0 and there is somewhere to put the figure; then waits for the stream.
+template <class F>
+int launch_or_time(hipStream_t s, int iters, float* ms, F launch) {
+    int rc = iters > 0 && ms ? time_launches(s, iters, ms, launch) : launch();
+    const hipError_t e = hipStreamSynchronize(s);
     if (!rc && e != hipSuccess) { set_error(hipGetErrorString(e)); rc = SD_ERR_HIP; }
     return rc;
 }
 
+// Runs `body(ctx)` once as a planning pass and then for real on a private arena (the op entries' workspace): once, or
+// timed (time_launches) with iters > 0.
+template <class F>
+int run_op_on_arena(hipStream_t s, int iters, float* ms, F body) {
+    if (iters > 0 && !ms) { set_error("ms_per_launch required with iters > 0"); return SD_ERR_INVALID; }
+    Arena arena;
+    Ctx dry{&arena, s, true};
+    arena.begin(true);
+    body(dry);
+    if (dry.err) return dry.err;
+    if (int rc = arena.reserve(arena.peak() > 0 ? arena.peak() : 256)) return rc;
+    return launch_or_time(s, iters, ms, [&]() {
+        Ctx c{&arena, s, false};
+        arena.begin(false);
+        body(c);
+        return c.err;
+    });
+}
+
+// The entries' operands as the packers take them.  The packers work on the null stream, so an entry waits for its own
+// stream first (pack_begin) and for the device afterwards (pack_end).  Biases, gamma and beta arrive as fp32 device
+// arrays and reach the packers as fp32 host arrays: nothing rounds them on the way.  A null bias packs as zeros.
+int pack_begin(hipStream_t s) { SD_HIP_CHECK(hipStreamSynchronize(s)); return 0; }
+int pack_end() { SD_HIP_CHECK(hipDeviceSynchronize()); return 0; }
+
+int host_f32(const void* dev_f32, long n, std::vector<float>* out) {
+    out->assign((size_t)n, 0.f);
+    if (dev_f32) SD_HIP_CHECK(hipMemcpy(out->data(), dev_f32, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// w [O][I][ks][ks] f16; geglu: a [hidden | gate] linear, interleaved per 64 rows; fold_up2x: also the folded pack
+int pack_conv_op(WeightStore& ws, const void* w, int O, int I, int ks, const void* bias_f32, bool geglu, bool fold_up2x,
+                 ConvW* out) {
+    std::vector<float> b;
+    if (int rc = host_f32(bias_f32, O, &b)) return rc;
+    const half_t* wh = static_cast<const half_t*>(w);
+    return geglu ? ws.pack_geglu(wh, O, I, b.data(), out) : ws.pack_conv(wh, O, I, ks, ks, b.data(), out, fold_up2x);
+}
+
+int pack_norm_op(WeightStore& ws, const void* gamma_f32, const void* beta_f32, int C, NormW* out) {
+    std::vector<float> g, b;
+    if (int rc = host_f32(gamma_f32, C, &g)) return rc;
+    if (int rc = host_f32(beta_f32, C, &b)) return rc;
+    return ws.pack_norm(g.data(), b.data(), C, out);
+}
+
+View view_of(const void* p, long ld, int C) { return View(const_cast<half_t*>(static_cast<const half_t*>(p)), ld, C); }
+
+// What the conv entries add to the plain sd_op_conv2d; everything is optional.
+struct ConvOpts {
+    long ldx = 0, ldres = 0, ldy = 0;       // operand strides in elements (0: dense)
+    int pad = -1, act = 0;                  // explicit padding (-1: the kernel size's default), the epilogue's activation
+    float acc_scale = 1.f, bias_scale = 1.f;
+    // GroupNorm summaries asked of the launch (they pick the split-K reduction kernel), kept for the call only ...
+    int gn_groups = 0;
+    float* gn_copy = nullptr;               // ... or copied out (sd_op_conv2d_gnstats; gn_copy_floats at most)
+    long gn_copy_floats = 0;
+    int* gn_rows = nullptr;                 // the pixels per summary (0: none left)
+    int* ran = nullptr;                     // kind, variant, split-K slices launched, reduction kernel
+    // A GroupNorm (+ SiLU) of norm_groups groups behind the convolution (sd_op_conv2d_groupnorm: y_gn receives it; the
+    // conv is asked for its summaries, *fused = it left them) or in front of it (sd_op_groupnorm_conv2d: inside the
+    // convolution where the launch takes it, *fused = 1, a GroupNorm kernel first otherwise).
+    enum { kNoNorm, kNormBehind, kNormInFront } norm = kNoNorm;
+    const void *gamma = nullptr, *beta = nullptr;
+    int norm_groups = 0, silu = 0;
+    float eps = 0.f;
+    void* y_gn = nullptr;
+    int* fused = nullptr;
+    // timing: `iters` launches of the convolution alone between events, after two warm-ups
+    int iters = 0;
+    float* ms = nullptr;
+};
+
+int conv2d_impl(const void* x, const void* w_oihw, const void* bias_f32, const void* rowadd_f32, const void* res, void* y,
+                int N, int H, int W, int Cin, int Cout, int ksize, int stride, int upsample2x, int geglu, void* stream,
+                const ConvOpts& o = ConvOpts()) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if ((long)ksize * ksize * Cin % 64 != 0 || Cin % 64 != 0) { set_error("sd_op_conv2d: Cin must be a multiple of 64"); return SD_ERR_INVALID; }
+    if (geglu && ksize != 1) { set_error("sd_op_conv2d: GEGLU takes a linear (ksize 1)"); return SD_ERR_INVALID; }
+    if (o.fused) *o.fused = 0;
+    const bool behind = o.norm == ConvOpts::kNormBehind, in_front = o.norm == ConvOpts::kNormInFront;
+    const IGemmParams geo = conv_problem(N, H, W, Cin, Cout, ksize, stride, upsample2x, o.pad);    // (the output map)
+    const long HW = (long)H * W, OHW = (long)geo.OH * geo.OW;
+    const int ocols = geglu ? Cout / 2 : Cout;
+    const int gn_groups = behind ? o.norm_groups : o.gn_groups;
+    if (int rc = pack_begin(s)) return rc;
+    WeightStore ws;
+    ConvW cw;                               // (no folded pack: an upsampling launch here runs the 9-tap kernels)
+    NormW nw;
+    int rc = pack_conv_op(ws, w_oihw, Cout, Cin, ksize, bias_f32, geglu != 0, false, &cw);
+    if (!rc && o.norm) rc = pack_norm_op(ws, o.gamma, o.beta, in_front ? Cin : Cout, &nw);
+    if (rc) return rc;
+    GnStatBuf gb;
+    if (gn_groups > 0 && !(gb.buf = static_cast<float*>(ws.dmalloc((size_t)gnstat_floats(N, OHW, gn_groups) * sizeof(float))))) {
+        set_error("hipMalloc failed (GroupNorm summaries)"); return SD_ERR_HIP;
+    }
+    // SD_BENCH_RES=1 (tuner): time the launch with the fused residual add
+    if (o.ms && !res && getenv("SD_BENCH_RES")) {
+        const size_t bytes = (size_t)geo.M * ocols * sizeof(half_t);
+        void* zero = ws.dmalloc(bytes);
+        if (!zero) { set_error("hipMalloc failed (SD_BENCH_RES)"); return SD_ERR_HIP; }
+        SD_HIP_CHECK(hipMemsetAsync(zero, 0, bytes, 0));
+        res = zero;
+    }
+    // SD_BENCH_COLD_MB=<n> (tuner): rotate through copies of the packed weights totalling n MB, so
+    // every timed launch streams its weights from HBM as it does inside a UNet forward (1.7 GB of
+    // weights per forward never stay in the 256 MB Infinity Cache); unset = same buffer every launch.
+    char* wring = nullptr;
+    long nrot = 1;
+    const size_t wbytes = (size_t)weight_rows(Cout) * cw.K * sizeof(half_t);
+    const char* cold = o.ms ? getenv("SD_BENCH_COLD_MB") : nullptr;
+    if (cold && atol(cold) > 0) {
+        nrot = std::min((atol(cold) * 1000000L + (long)wbytes - 1) / (long)wbytes, (long)o.iters + 2);
+        if (nrot > 1) {
+            if (!(wring = static_cast<char*>(ws.dmalloc(wbytes * (size_t)nrot)))) { set_error("hipMalloc failed (SD_BENCH_COLD_MB)"); return SD_ERR_HIP; }
+            for (long r = 0; r < nrot; ++r)
+                SD_HIP_CHECK(hipMemcpyAsync(wring + wbytes * (size_t)r, cw.w, wbytes, hipMemcpyDeviceToDevice, 0));
+        }
+    }
+    if ((rc = pack_end())) return rc;
+
+    const View xv = view_of(x, o.ldx ? o.ldx : Cin, Cin), rv = view_of(res, o.ldres ? o.ldres : ocols, ocols);
+    const View yv = view_of(y, o.ldy ? o.ldy : ocols, ocols);
+    const float* rowadd = static_cast<const float*>(rowadd_f32);
+    ConvLaunch l;
+    bool fused_in_front = false;
+    rc = run_op_on_arena(s, 0, nullptr, [&](Ctx& c) {
+        ConvFuse f;
+        f.acc_scale = o.acc_scale; f.bias_scale = o.bias_scale;
+        f.gn_out = gb.buf ? &gb : nullptr; f.gn_groups = gn_groups;
+        if (in_front) {
+            fused_in_front = op_gn_conv_fused(c, nw, cw, xv, N, H, W, yv, o.norm_groups, o.eps, o.silu, nullptr, rowadd, Cout,
+                                              res ? &rv : nullptr, &f, &l);
+            if (!fused_in_front) {
+                View hn(c.arena->alloc_h((long)N * HW * Cin), Cin, Cin);
+                op_groupnorm(c, nw, xv, hn, N, HW, o.norm_groups, o.eps, o.silu);
+                conv_prepare(c, cw, hn, N, H, W, yv, 1, 0, rowadd, Cout, res ? &rv : nullptr, 0, -1, 0, &f, &l);
+            }
+        } else {
+            conv_prepare(c, cw, xv, N, H, W, yv, stride, upsample2x, rowadd, Cout, res ? &rv : nullptr, geglu, o.pad, o.act, &f, &l);
+        }
+        if (!c.dry && !c.err) {
+            if (o.ms) {                     // the plan is made once: a timed launch costs the host what it costs a forward
+                long it = 0;
+                c.err = time_launches(s, o.iters, o.ms, [&]() {
+                    if (wring) l.p.w = reinterpret_cast<half_t*>(wring + wbytes * (size_t)(it++ % nrot));
+                    return launch_igemm2(l.p, l.partial, s, &l.plan);
+                });
+            } else {
+                conv_launch(c, l, yv, nullptr);
+            }
+        }
+        if (behind) op_groupnorm(c, nw, yv, view_of(o.y_gn, Cout, Cout), N, OHW, o.norm_groups, o.eps, o.silu, &gb);
+    });
+    if (rc) return rc;
+    if (o.ran) {
+        const IGemmLaunchNote note = igemm2_last_launch();
+        o.ran[0] = l.plan.kind; o.ran[1] = l.plan.variant; o.ran[2] = note.splits; o.ran[3] = note.reducer;
+    }
+    if (o.fused) *o.fused = behind ? gb.st.part != nullptr : fused_in_front;
+    if (o.gn_rows) {
+        *o.gn_rows = gb.st.part ? (int)gb.st.rows : 0;
+        const long n = std::min(gnstat_floats(N, OHW, gn_groups), o.gn_copy_floats);
+        if (gb.st.part && o.gn_copy && n > 0) SD_HIP_CHECK(hipMemcpy(o.gn_copy, gb.st.part, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice));
+        SD_HIP_CHECK(hipDeviceSynchronize());
+    }
+    return SD_OK;
+}
+}  // namespace
+
+extern "C" {
+
 int sd_op_conv2d(const void* x, const void* w_oihw, const void* bias_f32, const void* rowadd_f32, const void* res,
                  void* y, int N, int H, int W, int Cin, int Cout, int ksize, int stride, int upsample2x,
                  int geglu, void* stream) {
-    return conv2d_impl(x, w_oihw, bias_f32, rowadd_f32, res, y, N, H, W, Cin, Cout, ksize, stride, upsample2x, geglu,
-                       stream, 1, nullptr);
+    return conv2d_impl(x, w_oihw, bias_f32, rowadd_f32, res, y, N, H, W, Cin, Cout, ksize, stride, upsample2x, geglu, stream);
 }
 
 int sd_op_conv2d_ex(const void* x, const void* w_oihw, const void* bias_f32, const void* rowadd_f32, const void* res,
@@ -1246,9 +1239,10 @@ int sd_op_conv2d_ex(const void* x, const void* w_oihw, const void* bias_f32, con
         set_error("sd_op_conv2d_ex: pad in -1..1, act in 0..2, positive scales"); return SD_ERR_INVALID;
     }
     for (int i = 0; i < 4; ++i) ran[i] = 0;
-    const ConvEx ex{(long)ldx, (long)ldres, (long)ldy, pad, act, acc_scale, bias_scale, gn_groups, ran};
-    return conv2d_impl(x, w_oihw, bias_f32, rowadd_f32, res, y, N, H, W, Cin, Cout, ksize, stride, upsample2x, geglu,
-                       stream, 1, nullptr, nullptr, nullptr, &ex);
+    ConvOpts o;
+    o.ldx = (long)ldx; o.ldres = res ? (long)ldres : 0; o.ldy = (long)ldy;
+    o.pad = pad; o.act = act; o.acc_scale = acc_scale; o.bias_scale = bias_scale; o.gn_groups = gn_groups; o.ran = ran;
+    return conv2d_impl(x, w_oihw, bias_f32, rowadd_f32, res, y, N, H, W, Cin, Cout, ksize, stride, upsample2x, geglu, stream, o);
 }
 
 int sd_op_conv2d_gnstats(const void* x, const void* w_oihw, const void* bias_f32, const void* res, void* y, int N, int H,
@@ -1260,38 +1254,36 @@ int sd_op_conv2d_gnstats(const void* x, const void* w_oihw, const void* bias_f32
     }
     for (int i = 0; i < 4; ++i) ran[i] = 0;
     *rows = 0;
-    ConvEx ex{Cin, Cout, Cout, -1, 0, 1.f, 1.f, gn_groups, ran};
-    ex.gn_copy = summaries; ex.gn_copy_floats = (long)summaries_floats; ex.gn_rows = rows;
-    return conv2d_impl(x, w_oihw, bias_f32, nullptr, res, y, N, H, W, Cin, Cout, ksize, 1, 0, 0, stream, 1, nullptr, nullptr,
-                       nullptr, &ex);
+    ConvOpts o;
+    o.gn_groups = gn_groups; o.ran = ran;
+    o.gn_copy = summaries; o.gn_copy_floats = (long)summaries_floats; o.gn_rows = rows;
+    return conv2d_impl(x, w_oihw, bias_f32, nullptr, res, y, N, H, W, Cin, Cout, ksize, 1, 0, 0, stream, o);
 }
 
 int sd_op_conv3x3_small_cout(const void* x, const void* w_oihw, const void* bias_f32, void* y_nchw, int N, int H, int W,
                              int Cin, int Cout, void* stream) {
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (Cin % 64 != 0 || Cout < 1 || Cout > 4) { set_error("sd_op_conv3x3_small_cout: Cin % 64 == 0, Cout in 1..4"); return SD_ERR_INVALID; }
-    const long K = 9L * Cin;
-    DevScope scope;
-    half_t* wp = nullptr;
-    SD_DEV_ALLOC(scope, wp, (size_t)kWeightRowPad * K * sizeof(half_t));
-    SD_HIP_CHECK(hipMemsetAsync(wp, 0, (size_t)kWeightRowPad * K * sizeof(half_t), s));
-    int rc = launch_pack_conv(static_cast<const half_t*>(w_oihw), wp, Cout, Cin, 3, 3, K, s);
-    if (!rc)
-        rc = launch_conv3x3_small_cout(static_cast<const half_t*>(x), Cin, wp, K, static_cast<const float*>(bias_f32),
-                                       static_cast<half_t*>(y_nchw), N, H, W, Cin, Cout, s);
-    hipError_t e = hipStreamSynchronize(s);
-    if (!rc && e != hipSuccess) { set_error(hipGetErrorString(e)); rc = SD_ERR_HIP; }
-    return rc;
+    if (int rc = pack_begin(s)) return rc;
+    WeightStore ws;
+    ConvW cw;                               // (the kernel reads the caller's bias as it is)
+    int rc = ws.pack_conv(static_cast<const half_t*>(w_oihw), Cout, Cin, 3, 3, nullptr, &cw);
+    if (rc || (rc = pack_end())) return rc;
+    return launch_or_time(s, 0, nullptr, [&]() {
+        return launch_conv3x3_small_cout(static_cast<const half_t*>(x), Cin, cw.w, cw.K, static_cast<const float*>(bias_f32),
+                                         static_cast<half_t*>(y_nchw), N, H, W, Cin, Cout, s);
+    });
 }
 
 int sd_op_conv2d_groupnorm(const void* x, const void* w_oihw, const void* bias_f32, const void* rowadd_f32, const void* res,
                            void* y_conv, const void* gamma_f32, const void* beta_f32, void* y_gn, int N, int H, int W,
                            int Cin, int Cout, int ksize, int stride, int upsample2x, int groups, float eps, int silu,
                            int* stats_from_epilogue, void* stream) {
-    GnTail gn{static_cast<const float*>(gamma_f32), static_cast<const float*>(beta_f32), y_gn, groups, eps, silu,
-              stats_from_epilogue};
-    return conv2d_impl(x, w_oihw, bias_f32, rowadd_f32, res, y_conv, N, H, W, Cin, Cout, ksize, stride, upsample2x, 0,
-                       stream, 1, nullptr, &gn);
+    ConvOpts o;
+    o.norm = ConvOpts::kNormBehind;
+    o.gamma = gamma_f32; o.beta = beta_f32; o.norm_groups = groups; o.eps = eps; o.silu = silu;
+    o.y_gn = y_gn; o.fused = stats_from_epilogue;
+    return conv2d_impl(x, w_oihw, bias_f32, rowadd_f32, res, y_conv, N, H, W, Cin, Cout, ksize, stride, upsample2x, 0, stream, o);
 }
 
 int sd_op_groupnorm_conv2d(const void* x, const void* gamma_f32, const void* beta_f32, int groups, float eps, int silu,
@@ -1299,9 +1291,11 @@ int sd_op_groupnorm_conv2d(const void* x, const void* gamma_f32, const void* bet
                            int H, int W, int Cin, int Cout, int ksize, int iters, float* ms_per_launch, int* fused,
                            void* stream) {
     if (!x || !gamma_f32 || !beta_f32 || !w_oihw || !y || groups < 1) { set_error("sd_op_groupnorm_conv2d: bad arguments"); return SD_ERR_INVALID; }
-    GnHead gh{static_cast<const float*>(gamma_f32), static_cast<const float*>(beta_f32), groups, eps, silu, fused};
-    return conv2d_impl(x, w_oihw, bias_f32, rowadd_f32, res, y, N, H, W, Cin, Cout, ksize, 1, 0, 0, stream,
-                       iters > 0 ? iters : 1, iters > 0 ? ms_per_launch : nullptr, nullptr, &gh);
+    ConvOpts o;
+    o.norm = ConvOpts::kNormInFront;
+    o.gamma = gamma_f32; o.beta = beta_f32; o.norm_groups = groups; o.eps = eps; o.silu = silu; o.fused = fused;
+    if (iters > 0) { o.iters = iters; o.ms = ms_per_launch; }
+    return conv2d_impl(x, w_oihw, bias_f32, rowadd_f32, res, y, N, H, W, Cin, Cout, ksize, 1, 0, 0, stream, o);
 }
 
 static int ffn_geglu_impl(const void* x, const float* x_stat, int stat_parts, int stat_w, const void* ln_gamma,
@@ -1309,81 +1303,46 @@ static int ffn_geglu_impl(const void* x, const float* x_stat, int stat_parts, in
                           void* y, int M, int C, int iters, float* ms_per_launch, int* fused, void* stream) {
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (!x || !ln_gamma || !ln_beta || !w1 || !b1 || !w2 || !b2 || !y || M < 1 || C % 64 != 0) { set_error("sd_op_ffn_geglu: bad arguments"); return SD_ERR_INVALID; }
-    const long H4 = 4L * C, O1 = 8L * C;
-    const long r1 = (O1 + kWeightRowPad - 1) / kWeightRowPad * kWeightRowPad, r2 = ((long)C + kWeightRowPad - 1) / kWeightRowPad * kWeightRowPad;
-    DevScope scope;
-    half_t *wg = nullptr, *w2p = nullptr, *hid = nullptr;
-    float *bg = nullptr, *nb = nullptr, *wsum = nullptr, *b2p = nullptr, *stat = nullptr;
-    SD_DEV_ALLOC(scope, wg, (size_t)r1 * C * 2);
-    SD_DEV_ALLOC(scope, bg, (size_t)r1 * 4);
-    SD_DEV_ALLOC(scope, nb, (size_t)r1 * 4);
-    SD_DEV_ALLOC(scope, wsum, (size_t)r1 * 4);
-    SD_DEV_ALLOC(scope, w2p, (size_t)r2 * H4 * 2);
-    SD_DEV_ALLOC(scope, b2p, (size_t)r2 * 4);
-    if (!x_stat) SD_DEV_ALLOC(scope, stat, (size_t)M * 2 * 4);
-    SD_HIP_CHECK(hipMemsetAsync(wg, 0, (size_t)r1 * C * 2, s));
-    SD_HIP_CHECK(hipMemsetAsync(bg, 0, (size_t)r1 * 4, s));
-    SD_HIP_CHECK(hipMemsetAsync(nb, 0, (size_t)r1 * 4, s));
-    SD_HIP_CHECK(hipMemsetAsync(wsum, 0, (size_t)r1 * 4, s));
-    SD_HIP_CHECK(hipMemsetAsync(w2p, 0, (size_t)r2 * H4 * 2, s));
-    SD_HIP_CHECK(hipMemsetAsync(b2p, 0, (size_t)r2 * 4, s));
-    if (int r = geglu_interleave(wg, bg, static_cast<const half_t*>(w1), static_cast<const float*>(b1), H4, C, s)) return r;
-    SD_HIP_CHECK(hipMemcpyAsync(w2p, w2, (size_t)C * H4 * 2, hipMemcpyDeviceToDevice, s));
-    SD_HIP_CHECK(hipMemcpyAsync(b2p, b2, (size_t)C * 4, hipMemcpyDeviceToDevice, s));
-    int rc = launch_ln_fold(wg, C, (int)O1, static_cast<const float*>(ln_gamma), static_cast<const float*>(ln_beta), bg, nb, wsum, 0, 1.0f, s);
-    if (!rc && !x_stat) rc = launch_row_stats(static_cast<const half_t*>(x), C, stat, M, C, s);
-    if (rc) return rc;
-    const float* st = x_stat ? x_stat : stat;
-    const int parts = x_stat ? stat_parts : 1, part_w = x_stat ? stat_w : C;
-    FfnParams p;
-    p.x = static_cast<const half_t*>(x); p.ldx = C; p.y = static_cast<half_t*>(y); p.ldy = C;
-    p.w1 = wg; p.b1 = nb; p.wsum1 = wsum; p.w1_rows = (int)r1;
-    p.w2 = w2p; p.b2 = b2p; p.w2_rows = (int)r2;
-    p.ln_stat = st; p.ln_parts = parts; p.ln_part_w = part_w; p.ln_eps = ln_eps;
-    p.M = M; p.C = C; p.hidden = (int)H4;
-    const bool use_fused = ffn_fused_supported(p);
-    if (fused) *fused = use_fused ? 1 : 0;
-    // the two-GEMM form: projection with its GEGLU epilogue, output linear with its residual
-    if (!use_fused || ms_per_launch) SD_DEV_ALLOC(scope, hid, (size_t)M * H4 * 2);
-    IGemmParams g1 = pointwise_params(p.x, wg, nb, hid, H4, M, C, (int)O1);
-    g1.geglu = 1;
-    g1.ln_stat = st; g1.ln_parts = parts; g1.ln_part_w = part_w; g1.ln_C = C; g1.ln_eps = ln_eps; g1.ln_wsum = wsum;
-    IGemmParams g2 = pointwise_params(hid, w2p, b2p, p.y, C, M, (int)H4, C);
-    g2.res = p.x; g2.ldres = C;
-    const IGemmPlan plan1 = igemm2_plan(g1), plan2 = igemm2_plan(g2);
-    float* partial = nullptr;
-    if ((!use_fused || ms_per_launch) && plan2.partial_floats > 0) SD_DEV_ALLOC(scope, partial, (size_t)plan2.partial_floats * 4);
-    auto two_gemms = [&]() { int r = launch_igemm2(g1, nullptr, s, &plan1); return r ? r : launch_igemm2(g2, partial, s, &plan2); };
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (ms_per_launch) { SD_HIP_CHECK(hipEventCreate(&e0)); SD_HIP_CHECK(hipEventCreate(&e1)); }
-    const int n = ms_per_launch ? iters + 2 : 1;
-    for (int it = 0; it < n && !rc; ++it) {
-        if (ms_per_launch && it == 2) SD_HIP_CHECK(hipEventRecord(e0, s));
-        rc = use_fused ? launch_ffn_fused(p, s) : two_gemms();
+    const int hidden = 4 * C;
+    if (int rc = pack_begin(s)) return rc;
+    // packed as Encoder::pack_xformer packs a block whose LayerNorm folds into the projection
+    WeightStore ws;
+    NormW ln3;
+    ConvW ff1, ff2;
+    int rc;
+    if ((rc = pack_norm_op(ws, ln_gamma, ln_beta, C, &ln3)) || (rc = pack_conv_op(ws, w1, 2 * hidden, C, 1, b1, true, false, &ff1)) ||
+        (rc = ws.fold_ln(&ff1, ln3, 0, 1.0f)) || (rc = pack_conv_op(ws, w2, C, hidden, 1, b2, false, false, &ff2))) return rc;
+    RowStat st;
+    st.p = const_cast<float*>(x_stat); st.parts = stat_parts; st.width = stat_w;
+    if (!x_stat) {                          // no producer: one part over the whole row
+        st.p = static_cast<float*>(ws.dmalloc((size_t)rowstat_floats(M, C) * sizeof(float)));
+        if (!st.p) { set_error("hipMalloc failed (row statistics)"); return SD_ERR_HIP; }
+        st.parts = 1; st.width = C;
+        if ((rc = launch_row_stats(static_cast<const half_t*>(x), C, st.p, M, C, 0))) return rc;
     }
-    if (ms_per_launch && !rc) {
-        SD_HIP_CHECK(hipEventRecord(e1, s));
-        SD_HIP_CHECK(hipEventSynchronize(e1));
-        float ms = 0.f;
-        SD_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-        ms_per_launch[0] = ms / (float)iters;
-        if (use_fused) {                 // [1]: the two-GEMM form on the same operands
-            for (int it = 0; it < 2 && !rc; ++it) rc = two_gemms();
-            SD_HIP_CHECK(hipEventRecord(e0, s));
-            for (int it = 0; it < iters && !rc; ++it) rc = two_gemms();
-            SD_HIP_CHECK(hipEventRecord(e1, s));
-            SD_HIP_CHECK(hipEventSynchronize(e1));
-            SD_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-            ms_per_launch[1] = ms / (float)iters;
-            if (!rc) rc = launch_ffn_fused(p, s);          // leave the fused result in y
-        } else {
-            ms_per_launch[1] = ms_per_launch[0];
-        }
-    }
-    if (e0) { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); }
-    hipError_t e = hipStreamSynchronize(s);
-    if (!rc && e != hipSuccess) { set_error(hipGetErrorString(e)); rc = SD_ERR_HIP; }
-    return rc;
+    if ((rc = pack_end())) return rc;
+    const View xv = view_of(x, C, C), yv = view_of(y, C, C);
+    bool ran_fused = false;
+    // ffn.hip's one launch where it takes the problem (unless two_gemms), otherwise the projection with its GEGLU epilogue
+    // and the output linear with its residual epilogue: run_xformer_tail's choice and launches
+    auto run = [&](bool two_gemms, int n, float* ms) {
+        return run_op_on_arena(s, n, ms, [&](Ctx& c) {
+            ran_fused = !two_gemms && op_ffn_fused(c, ff1, ff2, xv, st, ln_eps, M, yv);
+            if (ran_fused) return;
+            View g(c.arena->alloc_h((long)M * hidden), hidden, hidden);
+            ConvFuse f_ln3;
+            f_ln3.ln_in = &st; f_ln3.ln_eps = ln_eps;
+            op_conv(c, ff1, xv, 1, M, 1, g, 1, 0, nullptr, 0, nullptr, 1, -1, 0, &f_ln3);
+            op_conv(c, ff2, g, 1, M, 1, yv, 1, 0, nullptr, 0, &xv, 0, -1, 0, nullptr);
+        });
+    };
+    const int n = ms_per_launch ? iters : 0;
+    rc = run(false, n, ms_per_launch);
+    if (fused) *fused = ran_fused ? 1 : 0;
+    if (rc || n < 1) return rc;
+    if (!ran_fused) { ms_per_launch[1] = ms_per_launch[0]; return SD_OK; }
+    rc = run(true, n, ms_per_launch + 1);   // [1]: the two-GEMM form on the same operands
+    return rc ? rc : run(false, 0, nullptr);                // leave the fused result in y
 }
 
 int sd_op_ffn_geglu(const void* x, const void* ln_gamma, const void* ln_beta, float ln_eps, const void* w1, const void* b1,
@@ -1410,42 +1369,37 @@ int sd_op_ln_ffn_geglu(const void* x, const float* stat, int parts, int part_w, 
 
 // The folded-LayerNorm chain of a transformer block at op level (unet.cpp run_xformer), in two calls that share the
 // row-statistics buffer so a test can force the producer's and the consumer's kernel separately (sd_igemm_force).
-// Producer: y1 = x W0^T + b0 (+ res) with op_conv's rule for the statistics: from the GEMM epilogue when the launch
-// can emit them (IGemmPlan::rowstats), row_stats_kernel over y1 otherwise.
+// Producer: y1 = x W0^T + b0 (+ res), an op_conv asked for the row statistics of its output (ConvFuse::stat_out): from
+// the GEMM epilogue when the launch can emit them (*producer = its kernel), row_stats_kernel over y1 otherwise (-1).
 int sd_op_linear_rowstats(const void* x, const void* w0, const void* b0, const void* res, void* y1, float* stat, int M,
                           int K, int C, int* parts, int* part_w, int* producer, void* stream) {
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (!x || !w0 || !y1 || !stat || !parts || !part_w || !producer || M < 1 || K % 64 != 0 || K < 64 || C % 8 != 0 || C < 8) {
         set_error("sd_op_linear_rowstats: bad arguments"); return SD_ERR_INVALID;
     }
-    const long rows = ((long)C + kWeightRowPad - 1) / kWeightRowPad * kWeightRowPad;
-    DevScope scope;
-    half_t* wp = nullptr;
-    float *bp = nullptr, *partial = nullptr;
-    SD_DEV_ALLOC(scope, wp, (size_t)rows * K * 2);
-    SD_DEV_ALLOC(scope, bp, (size_t)rows * 4);
-    SD_HIP_CHECK(hipMemsetAsync(wp, 0, (size_t)rows * K * 2, s));
-    SD_HIP_CHECK(hipMemsetAsync(bp, 0, (size_t)rows * 4, s));
-    int rc = launch_pack_conv(static_cast<const half_t*>(w0), wp, C, K, 1, 1, K, s);
-    if (rc) return rc;
-    if (b0) SD_HIP_CHECK(hipMemcpyAsync(bp, b0, (size_t)C * 4, hipMemcpyDeviceToDevice, s));
-    IGemmParams p = pointwise_params(static_cast<const half_t*>(x), wp, bp, static_cast<half_t*>(y1), C, M, K, C);
-    p.res = static_cast<const half_t*>(res); p.ldres = C;
-    const IGemmPlan plan = igemm2_plan(p, IGemmRequest{stat});
-    const bool own = plan.rowstats;
-    if (plan.partial_floats > 0) SD_DEV_ALLOC(scope, partial, (size_t)plan.partial_floats * 4);
-    *producer = own ? plan.kind : -1;
-    *parts = plan.rs_parts;
-    *part_w = plan.rs_part_w;
-    rc = launch_igemm2(p, partial, s, &plan);
-    if (!rc && !own) rc = launch_row_stats(p.y, C, stat, M, C, s);
-    hipError_t e = hipStreamSynchronize(s);
-    if (!rc && e != hipSuccess) { set_error(hipGetErrorString(e)); rc = SD_ERR_HIP; }
+    if (int rc = pack_begin(s)) return rc;
+    WeightStore ws;
+    ConvW cw;
+    int rc = pack_conv_op(ws, w0, C, K, 1, b0, false, false, &cw);
+    if (rc || (rc = pack_end())) return rc;
+    RowStat st;
+    st.p = stat;
+    ConvLaunch l;
+    const View yv = view_of(y1, C, C), rv = view_of(res, C, C);
+    rc = run_op_on_arena(s, 0, nullptr, [&](Ctx& c) {
+        ConvFuse f;
+        f.stat_out = &st;
+        if (conv_prepare(c, cw, view_of(x, K, K), 1, M, 1, yv, 1, 0, nullptr, 0, res ? &rv : nullptr, 0, -1, 0, &f, &l))
+            conv_launch(c, l, yv, &st);
+    });
+    *producer = l.plan.rowstats ? l.plan.kind : -1;
+    *parts = st.parts;
+    *part_w = st.width;
     return rc;
 }
 
-// Consumer: y2 = LayerNorm(y1) W1^T + b1 with the norm folded into W1 (launch_ln_fold, as WeightStore::fold_ln) and
-// its statistics from the producer's buffer.  geglu = 0: W1 [O, C], the first rows_scaled outputs times row_scale
+// Consumer: y2 = LayerNorm(y1) W1^T + b1 with the norm folded into W1 (WeightStore::fold_ln) and its statistics from the
+// producer's buffer (ConvFuse::ln_in).  geglu = 0: W1 [O, C], the first rows_scaled outputs times row_scale
 // (the q of q|k|v); geglu = 1: W1 [2 O, C] = [hidden | gate] rows, y2 = hidden * gelu(gate) [M, O].
 int sd_op_ln_linear(const void* y1, const float* stat, int parts, int part_w, const void* gamma, const void* beta, float eps,
                     const void* w1, const void* b1, void* y2, int M, int C, int O, int geglu, int rows_scaled, float row_scale,
@@ -1460,41 +1414,24 @@ int sd_op_ln_linear(const void* y1, const float* stat, int parts, int part_w, co
                   std::to_string(igemm2_max_ln_parts()) + " statistics parts per row");
         return SD_ERR_INVALID;
     }
-    const long cols = geglu ? 2L * O : (long)O;
-    const long rows = (cols + kWeightRowPad - 1) / kWeightRowPad * kWeightRowPad;
-    DevScope scope;
-    half_t *wp = nullptr, *wf = nullptr;
-    float *bp = nullptr, *bf = nullptr, *nb = nullptr, *wsum = nullptr;
-    SD_DEV_ALLOC(scope, wp, (size_t)rows * C * 2);
-    SD_DEV_ALLOC(scope, bp, (size_t)rows * 4);
-    SD_DEV_ALLOC(scope, nb, (size_t)rows * 4);
-    SD_DEV_ALLOC(scope, wsum, (size_t)rows * 4);
-    SD_HIP_CHECK(hipMemsetAsync(wp, 0, (size_t)rows * C * 2, s));
-    SD_HIP_CHECK(hipMemsetAsync(bp, 0, (size_t)rows * 4, s));
-    SD_HIP_CHECK(hipMemsetAsync(nb, 0, (size_t)rows * 4, s));
-    SD_HIP_CHECK(hipMemsetAsync(wsum, 0, (size_t)rows * 4, s));
-    int rc = launch_pack_conv(static_cast<const half_t*>(w1), wp, (int)cols, C, 1, 1, C, s);
-    if (rc) return rc;
-    if (b1) SD_HIP_CHECK(hipMemcpyAsync(bp, b1, (size_t)cols * 4, hipMemcpyDeviceToDevice, s));
-    wf = wp; bf = bp;
-    if (geglu) {
-        SD_DEV_ALLOC(scope, wf, (size_t)rows * C * 2);
-        SD_DEV_ALLOC(scope, bf, (size_t)rows * 4);
-        SD_HIP_CHECK(hipMemsetAsync(wf, 0, (size_t)rows * C * 2, s));
-        SD_HIP_CHECK(hipMemsetAsync(bf, 0, (size_t)rows * 4, s));
-        if (int r = geglu_interleave(wf, bf, wp, bp, O, C, s)) return r;
-    }
-    rc = launch_ln_fold(wf, C, (int)cols, static_cast<const float*>(gamma), static_cast<const float*>(beta), bf, nb, wsum,
-                        geglu ? 0 : rows_scaled, row_scale, s);
-    if (rc) return rc;
-    IGemmParams g = pointwise_params(static_cast<const half_t*>(y1), wf, nb, static_cast<half_t*>(y2), O, M, C, (int)cols);
-    g.geglu = geglu;
-    g.ln_stat = stat; g.ln_parts = parts; g.ln_part_w = part_w; g.ln_C = C; g.ln_eps = eps; g.ln_wsum = wsum;
-    const IGemmPlan plan = igemm2_plan(g, IGemmRequest{nullptr, nullptr, 0, true});      // (no workspace: never split)
-    *consumer = plan.kind;
-    rc = launch_igemm2(g, nullptr, s, &plan);
-    hipError_t e = hipStreamSynchronize(s);
-    if (!rc && e != hipSuccess) { set_error(hipGetErrorString(e)); rc = SD_ERR_HIP; }
+    if (int rc = pack_begin(s)) return rc;
+    WeightStore ws;
+    NormW ln;
+    ConvW cw;
+    int rc;
+    if ((rc = pack_norm_op(ws, gamma, beta, C, &ln)) || (rc = pack_conv_op(ws, w1, geglu ? 2 * O : O, C, 1, b1, geglu != 0, false, &cw)) ||
+        (rc = ws.fold_ln(&cw, ln, geglu ? 0 : rows_scaled, row_scale)) || (rc = pack_end())) return rc;
+    RowStat st;
+    st.p = const_cast<float*>(stat); st.parts = parts; st.width = part_w;
+    ConvLaunch l;
+    const View yv = view_of(y2, O, O);
+    rc = run_op_on_arena(s, 0, nullptr, [&](Ctx& c) {
+        ConvFuse f;
+        f.ln_in = &st; f.ln_eps = eps;
+        if (conv_prepare(c, cw, view_of(y1, C, C), 1, M, 1, yv, 1, 0, nullptr, 0, nullptr, geglu, -1, 0, &f, &l))
+            conv_launch(c, l, yv, nullptr);
+    });
+    *consumer = l.plan.kind;
     return rc;
 }
 
@@ -1509,36 +1446,13 @@ int sd_op_unet_conv_in(const void* x_nchw, const void* w_oihw, const void* bias_
     p.N = N; p.Cin = Cin; p.H = H; p.W = W; p.Cout = Cout;
     // (refused before anything is allocated or launched)
     if (H < 1 || W < 1 || 9 * Cin > K || !conv_head_supported(p)) { set_error("sd_op_unet_conv_in: shape outside the one-launch kernel (Cout 320, 9 Cin <= 64, H W % 128 == 0)"); return SD_ERR_INVALID; }
-    const long rows = ((long)Cout + kWeightRowPad - 1) / kWeightRowPad * kWeightRowPad;
-    DevScope scope;
-    half_t* wp = nullptr;
-    float* bp = nullptr;
-    SD_DEV_ALLOC(scope, wp, (size_t)rows * K * 2);
-    SD_DEV_ALLOC(scope, bp, (size_t)rows * 4);
-    SD_HIP_CHECK(hipMemsetAsync(wp, 0, (size_t)rows * K * 2, s));
-    SD_HIP_CHECK(hipMemsetAsync(bp, 0, (size_t)rows * 4, s));
-    p.w = wp; p.bias = bp;
-    int rc = launch_pack_conv(static_cast<const half_t*>(w_oihw), wp, Cout, Cin, 3, 3, K, s);
-    if (!rc) SD_HIP_CHECK(hipMemcpyAsync(bp, bias_f32, (size_t)Cout * 4, hipMemcpyDeviceToDevice, s));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    const bool timed = iters > 0 && ms_per_launch;
-    if (timed) { SD_HIP_CHECK(hipEventCreate(&e0)); SD_HIP_CHECK(hipEventCreate(&e1)); }
-    const int n = timed ? iters + 2 : 1;
-    for (int it = 0; it < n && !rc; ++it) {
-        if (timed && it == 2) SD_HIP_CHECK(hipEventRecord(e0, s));
-        rc = launch_conv_head(p, s);
-    }
-    if (timed && !rc) {
-        SD_HIP_CHECK(hipEventRecord(e1, s));
-        SD_HIP_CHECK(hipEventSynchronize(e1));
-        float ms = 0.f;
-        SD_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-        *ms_per_launch = ms / (float)iters;
-    }
-    if (e0) { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); }
-    hipError_t e = hipStreamSynchronize(s);
-    if (!rc && e != hipSuccess) { set_error(hipGetErrorString(e)); rc = SD_ERR_HIP; }
-    return rc;
+    if (int rc = pack_begin(s)) return rc;
+    WeightStore ws;
+    ConvW cw;
+    int rc = pack_conv_op(ws, w_oihw, Cout, Cin, 3, bias_f32, false, false, &cw);
+    if (rc || (rc = pack_end())) return rc;
+    p.w = cw.w; p.K = cw.K; p.bias = cw.bias;
+    return launch_or_time(s, iters, ms_per_launch, [&]() { return launch_conv_head(p, s); });
 }
 
 int sd_op_unet_conv_in2(const void* a, int Na, int Ca, float in_scale, const void* b, int Nb, int Cb, int zero_from,
@@ -1550,47 +1464,23 @@ int sd_op_unet_conv_in2(const void* a, int Na, int Ca, float in_scale, const voi
         set_error("sd_op_unet_conv_in2: bad arguments");
         return SD_ERR_INVALID;
     }
-    const long K = 128;
-    const long rows = ((long)Cout + kWeightRowPad - 1) / kWeightRowPad * kWeightRowPad;
     Head2Params p;
     p.a = static_cast<const half_t*>(a); p.Na = Na; p.Ca = Ca; p.in_scale = in_scale;
     p.b = static_cast<const half_t*>(b); p.Nb = Nb; p.Cb = Cb; p.zero_from = zero_from;
-    p.K = K; p.y = static_cast<half_t*>(y_nhwc); p.ldy = ldy;
+    p.K = 128; p.y = static_cast<half_t*>(y_nhwc); p.ldy = ldy;
     p.gnstat_out = groups > 0 ? gn_summaries : nullptr; p.G = groups;
     p.N = N; p.H = H; p.W = W; p.Cout = Cout;
     if (!conv_head2_supported(p)) {
         set_error("sd_op_unet_conv_in2: shape outside the one-launch kernel (Cout 320, 9 (Ca + Cb) <= 128, N % Na == 0, H W % 128 == 0, ldy % 8 == 0)");
         return SD_ERR_INVALID;
     }
-    DevScope scope;
-    half_t* wp = nullptr;
-    float* bp = nullptr;
-    SD_DEV_ALLOC(scope, wp, (size_t)rows * K * 2);
-    SD_DEV_ALLOC(scope, bp, (size_t)rows * 4);
-    SD_HIP_CHECK(hipMemsetAsync(wp, 0, (size_t)rows * K * 2, s));
-    SD_HIP_CHECK(hipMemsetAsync(bp, 0, (size_t)rows * 4, s));
-    p.w = wp; p.bias = bp;
-    int rc = launch_pack_conv(static_cast<const half_t*>(w_oihw), wp, Cout, Ca + Cb, 3, 3, K, s);
-    if (!rc) SD_HIP_CHECK(hipMemcpyAsync(bp, bias_f32, (size_t)Cout * 4, hipMemcpyDeviceToDevice, s));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    const bool timed = iters > 0 && ms_per_launch;
-    if (timed) { SD_HIP_CHECK(hipEventCreate(&e0)); SD_HIP_CHECK(hipEventCreate(&e1)); }
-    const int n = timed ? iters + 2 : 1;
-    for (int it = 0; it < n && !rc; ++it) {
-        if (timed && it == 2) SD_HIP_CHECK(hipEventRecord(e0, s));
-        rc = launch_conv_head2(p, s);
-    }
-    if (timed && !rc) {
-        SD_HIP_CHECK(hipEventRecord(e1, s));
-        SD_HIP_CHECK(hipEventSynchronize(e1));
-        float ms = 0.f;
-        SD_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-        *ms_per_launch = ms / (float)iters;
-    }
-    if (e0) { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); }
-    hipError_t e = hipStreamSynchronize(s);
-    if (!rc && e != hipSuccess) { set_error(hipGetErrorString(e)); rc = SD_ERR_HIP; }
-    return rc;
+    if (int rc = pack_begin(s)) return rc;
+    WeightStore ws;
+    ConvW cw;
+    int rc = pack_conv_op(ws, w_oihw, Cout, Ca + Cb, 3, bias_f32, false, false, &cw);
+    if (rc || (rc = pack_end())) return rc;
+    p.w = cw.w; p.K = cw.K; p.bias = cw.bias;       // (64 for up to 7 input channels, as a model's conv_in packs)
+    return launch_or_time(s, iters, ms_per_launch, [&]() { return launch_conv_head2(p, s); });
 }
 
 int sd_op_unet_conv_out_ex(const void* x_nhwc, int64_t ldx, const void* gamma_f32, const void* beta_f32, int groups, float eps,
@@ -1606,52 +1496,28 @@ int sd_op_unet_conv_out_ex(const void* x_nhwc, int64_t ldx, const void* gamma_f3
     if (summaries && (S < 1 || rows < 1 || (int64_t)S * rows < HW || (int64_t)(S - 1) * rows >= HW)) {
         set_error("sd_op_unet_conv_out: S summaries of `rows` pixels must cover H W with no empty one"); return SD_ERR_INVALID;
     }
-    const long K = 9L * C;
     TailParams p;
     p.x = static_cast<const half_t*>(x_nhwc); p.ldx = ldx;
     p.gn_part = summaries ? summaries : static_cast<const float*>(gamma_f32);      // (own pass: replaced below; non-null for the check)
     p.gn_S = summaries ? S : 1; p.gn_rows = summaries ? rows : HW;
     p.G = groups; p.eps = eps; p.gamma = static_cast<const float*>(gamma_f32); p.beta = static_cast<const float*>(beta_f32); p.silu = silu;
-    p.w = nullptr; p.K = K; p.bias = nullptr; p.y = static_cast<half_t*>(y_nchw);
+    p.w = nullptr; p.K = 9L * C; p.bias = nullptr; p.y = static_cast<half_t*>(y_nchw);
     p.N = N; p.H = H; p.W = W; p.C = C; p.Cout = Cout;
     if (!conv_tail_supported(p)) { set_error("sd_op_unet_conv_out: shape outside the one-launch kernel (C 320, Cout <= 4, H % 8 == 0, W % 16 == 0, groups <= 32)"); return SD_ERR_INVALID; }
-    const long wrows = ((long)Cout + kWeightRowPad - 1) / kWeightRowPad * kWeightRowPad;
-    DevScope scope;
-    half_t* wp = nullptr;
-    float *bp = nullptr, *scratch = nullptr;
-    SD_DEV_ALLOC(scope, wp, (size_t)wrows * K * 2);
-    SD_DEV_ALLOC(scope, bp, (size_t)wrows * 4);
-    if (!summaries) SD_DEV_ALLOC(scope, scratch, (size_t)gn_scratch_floats(N, HW, C, groups) * 4);
-    SD_HIP_CHECK(hipMemsetAsync(wp, 0, (size_t)wrows * K * 2, s));
-    SD_HIP_CHECK(hipMemsetAsync(bp, 0, (size_t)wrows * 4, s));
-    int rc = launch_pack_conv(static_cast<const half_t*>(w_oihw), wp, Cout, C, 3, 3, K, s);
-    if (!rc) SD_HIP_CHECK(hipMemcpyAsync(bp, bias_f32, (size_t)Cout * 4, hipMemcpyDeviceToDevice, s));
-    if (!rc && !summaries) {
+    if (int rc = pack_begin(s)) return rc;
+    WeightStore ws;
+    ConvW cw;
+    int rc = pack_conv_op(ws, w_oihw, Cout, C, 3, bias_f32, false, false, &cw);
+    if (!rc && !summaries) {                // the statistics pass, outside the timed launches
+        float* scratch = static_cast<float*>(ws.dmalloc((size_t)gn_scratch_floats(N, HW, C, groups) * sizeof(float)));
+        if (!scratch) { set_error("hipMalloc failed (GroupNorm scratch)"); return SD_ERR_HIP; }
         GnStats st;
-        rc = launch_gn_stats(static_cast<const half_t*>(x_nhwc), ldx, N, HW, C, groups, scratch, &st, s);
+        rc = launch_gn_stats(static_cast<const half_t*>(x_nhwc), ldx, N, HW, C, groups, scratch, &st, 0);
         p.gn_part = st.part; p.gn_S = st.S; p.gn_rows = st.rows;
     }
-    if (rc) return rc;
-    p.w = wp; p.bias = bp;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    const bool timed = iters > 0 && ms_per_launch;
-    if (timed) { SD_HIP_CHECK(hipEventCreate(&e0)); SD_HIP_CHECK(hipEventCreate(&e1)); }
-    const int n = timed ? iters + 2 : 1;
-    for (int it = 0; it < n && !rc; ++it) {
-        if (timed && it == 2) SD_HIP_CHECK(hipEventRecord(e0, s));
-        rc = launch_conv_tail(p, s);
-    }
-    if (timed && !rc) {
-        SD_HIP_CHECK(hipEventRecord(e1, s));
-        SD_HIP_CHECK(hipEventSynchronize(e1));
-        float ms = 0.f;
-        SD_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-        *ms_per_launch = ms / (float)iters;
-    }
-    if (e0) { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); }
-    hipError_t e = hipStreamSynchronize(s);
-    if (!rc && e != hipSuccess) { set_error(hipGetErrorString(e)); rc = SD_ERR_HIP; }
-    return rc;
+    if (rc || (rc = pack_end())) return rc;
+    p.w = cw.w; p.K = cw.K; p.bias = cw.bias;
+    return launch_or_time(s, iters, ms_per_launch, [&]() { return launch_conv_tail(p, s); });
 }
 
 int sd_op_unet_conv_out(const void* x_nhwc, const void* gamma_f32, const void* beta_f32, int groups, float eps, int silu,
@@ -1664,9 +1530,22 @@ int sd_op_unet_conv_out(const void* x_nhwc, const void* gamma_f32, const void* b
 int sd_bench_conv2d(const void* x, const void* w_oihw, void* y, int N, int H, int W, int Cin, int Cout, int ksize,
                     int stride, int upsample2x, int geglu, int iters, float* ms_per_launch, void* stream) {
     if (iters < 1 || !ms_per_launch) { set_error("sd_bench_conv2d: bad arguments"); return SD_ERR_INVALID; }
-    return conv2d_impl(x, w_oihw, nullptr, nullptr, nullptr, y, N, H, W, Cin, Cout, ksize, stride, upsample2x, geglu,
-                       stream, iters, ms_per_launch);
+    ConvOpts o;
+    o.iters = iters; o.ms = ms_per_launch;
+    return conv2d_impl(x, w_oihw, nullptr, nullptr, nullptr, y, N, H, W, Cin, Cout, ksize, stride, upsample2x, geglu, stream, o);
 }
+
+// Scratch buffers of the entries below: freed on every return path (hipFree waits for the device), including the
+// SD_HIP_CHECK early returns.
+struct DevScope {
+    std::vector<void*> bufs;
+    ~DevScope() { for (void* p : bufs) (void)hipFree(p); }
+};
+#define SD_DEV_ALLOC(scope, ptr, bytes)                                              \
+    do {                                                                             \
+        SD_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&(ptr)), (bytes)));          \
+        (scope).bufs.push_back(ptr);                                                 \
+    } while (0)
 
 int sd_op_groupnorm(const void* x, const void* gamma_f32, const void* beta_f32, void* y, int N, int HW, int C,
                     int groups, float eps, int silu, void* stream) {
@@ -1796,9 +1675,6 @@ int sd_bench_groupnorm(const void* x, const void* gamma_f32, const void* beta_f3
     DevScope scope;
     float* scratch = nullptr;
     SD_DEV_ALLOC(scope, scratch, (size_t)gn_scratch_floats(N, HW, C, groups) * 4);
-    hipEvent_t e0, e1;
-    SD_HIP_CHECK(hipEventCreate(&e0));
-    SD_HIP_CHECK(hipEventCreate(&e1));
     int rc = 0;
     // SD_GN_BENCH_APPLY=1: the statistics pass runs once, outside the timed launches, and every timed launch is the
     // apply pass alone on those summaries -- what a GroupNorm costs when the producing convolution left them
@@ -1809,21 +1685,12 @@ int sd_bench_groupnorm(const void* x, const void* gamma_f32, const void* beta_f3
         SD_DEV_ALLOC(scope, scratch2, (size_t)gn_scratch_floats(N, HW, C, groups) * 4);
         rc = launch_gn_stats(static_cast<const half_t*>(x), C, N, HW, C, groups, scratch2, &st, s);
     }
-    for (int i = 0; i < iters + 2 && !rc; ++i) {
-        if (i == 2) (void)hipEventRecord(e0, s);
-        rc = launch_groupnorm(static_cast<const half_t*>(x), C, static_cast<const float*>(gamma_f32),
-                              static_cast<const float*>(beta_f32), static_cast<half_t*>(y), C, N, HW, C, groups,
-                              eps, silu, scratch, s, st.part ? &st : nullptr);
-    }
-    (void)hipEventRecord(e1, s);
-    hipError_t e = hipEventSynchronize(e1);
-    float ms = 0.f;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-    *ms_per_launch = ms / iters;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    if (!rc && e != hipSuccess) { set_error(hipGetErrorString(e)); rc = SD_ERR_HIP; }
-    return rc;
+    if (rc) return rc;
+    return time_launches(s, iters, ms_per_launch, [&]() {
+        return launch_groupnorm(static_cast<const half_t*>(x), C, static_cast<const float*>(gamma_f32),
+                                static_cast<const float*>(beta_f32), static_cast<half_t*>(y), C, N, HW, C, groups,
+                                eps, silu, scratch, s, st.part ? &st : nullptr);
+    });
 }
 
 int sd_op_timestep_sinusoid(const float* t, float* out, int count, int dim, int flip_sin_to_cos, float freq_shift,
@@ -1984,25 +1851,10 @@ int sd_op_ip_cross_attention(const void* q, const void* k, const void* v, const 
         if (!r) r = launch_axpy_f16(oh, ldo, tmp, ldt, (long)B * Tq, heads * d, ip_scale, s);
         return r;
     };
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) rc = SD_ERR_HIP;
-    for (int variant = 0; variant < 3 && !rc; ++variant) {
-        auto one = [&]() { return variant == 0 ? fused() : variant == 1 ? text() : unfused(); };
-        for (int it = 0; it < 2 && !rc; ++it) rc = one();
-        if (rc) break;
-        (void)hipEventRecord(e0, s);
-        for (int it = 0; it < iters && !rc; ++it) rc = one();
-        (void)hipEventRecord(e1, s);
-        float ms = 0.f;
-        hipError_t e = hipEventSynchronize(e1);
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-        if (e != hipSuccess) { set_error(hipGetErrorString(e)); rc = SD_ERR_HIP; }
-        ms_per_launch[variant] = ms / (float)iters;
-    }
+    for (int variant = 0; variant < 3 && !rc; ++variant)
+        rc = time_launches(s, iters, ms_per_launch + variant, [&]() { return variant == 0 ? fused() : variant == 1 ? text() : unfused(); });
     if (!rc) rc = fused();                  // leave the fused result in out
     if (!rc && hipStreamSynchronize(s) != hipSuccess) rc = SD_ERR_HIP;
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
     (void)hipFree(tmp);
     return rc;
 }
@@ -2032,74 +1884,13 @@ int sd_op_resampler_attention(const void* q, const void* k_x, const void* v_x, c
         if (!r) r = launch_attention(qh, cat, cat + A, oh, B, n_q, Tk, heads, 64, ldq, 2L * A, 2L * A, ldo, s, 0, prescaled);
         return r;
     };
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) rc = SD_ERR_HIP;
-    for (int variant = 0; variant < 2 && !rc; ++variant) {
-        auto one = [&]() { return variant == 0 ? fused() : composed(); };
-        for (int it = 0; it < 2 && !rc; ++it) rc = one();
-        if (rc) break;
-        (void)hipEventRecord(e0, s);
-        for (int it = 0; it < iters && !rc; ++it) rc = one();
-        (void)hipEventRecord(e1, s);
-        float ms = 0.f;
-        hipError_t e = hipEventSynchronize(e1);
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-        if (e != hipSuccess) { set_error(hipGetErrorString(e)); rc = SD_ERR_HIP; }
-        ms_per_launch[variant] = ms / (float)iters;
-    }
+    for (int variant = 0; variant < 2 && !rc; ++variant)
+        rc = time_launches(s, iters, ms_per_launch + variant, [&]() { return variant == 0 ? fused() : composed(); });
     if (!rc) rc = fused();                  // leave this kernel's result in out
     if (!rc && hipStreamSynchronize(s) != hipSuccess) rc = SD_ERR_HIP;
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
     (void)hipFree(cat);
     return rc;
 }
-
-}  // extern "C"
-
-namespace {
-// Runs `body(ctx)` once as a planning pass and once for real on a private arena (the op entries' workspace), `iters`
-// more times between events when timing.
-template <class F>
-int run_op_on_arena(hipStream_t s, int iters, float* ms, F body) {
-    Arena arena;
-    Ctx dry{&arena, s, true};
-    arena.begin(true);
-    body(dry);
-    if (dry.err) return dry.err;
-    if (int rc = arena.reserve(arena.peak() > 0 ? arena.peak() : 256)) return rc;
-    auto live = [&]() {
-        Ctx c{&arena, s, false};
-        arena.begin(false);
-        body(c);
-        return c.err;
-    };
-    int rc = live();
-    if (!rc && iters > 0) {
-        if (!ms) { set_error("ms_per_launch required with iters > 0"); return SD_ERR_INVALID; }
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) rc = SD_ERR_HIP;
-        if (!rc) rc = live();                       // warm-up
-        if (!rc) (void)hipEventRecord(e0, s);
-        for (int it = 0; it < iters && !rc; ++it) rc = live();
-        if (!rc) {
-            (void)hipEventRecord(e1, s);
-            float t = 0.f;
-            hipError_t e = hipEventSynchronize(e1);
-            if (e == hipSuccess) e = hipEventElapsedTime(&t, e0, e1);
-            if (e != hipSuccess) { set_error(hipGetErrorString(e)); rc = SD_ERR_HIP; }
-            *ms = t / (float)iters;
-        }
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-    }
-    const hipError_t e = hipStreamSynchronize(s);
-    if (!rc && e != hipSuccess) { set_error(hipGetErrorString(e)); rc = SD_ERR_HIP; }
-    return rc;
-}
-}  // namespace
-
-extern "C" {
 
 int sd_op_controlnet_residuals(const sd_cn_problem* problems, int count, float scale, int mode, int iters,
                                float* ms_per_launch, void* stream) {
@@ -2118,44 +1909,23 @@ int sd_op_controlnet_residuals(const sd_cn_problem* problems, int count, float s
     }
     if (!cn_residual_supported(rp)) { set_error("sd_op_controlnet_residuals: unsupported strides or alignment"); return SD_ERR_UNSUPPORTED; }
     if (mode == 0) return run_op_on_arena(s, iters, ms_per_launch, [&](Ctx& c) { if (!c.dry) c.err = launch_cn_residual(rp, s); });
-    // unfused: one GEMM per problem, y = scale (x W^T) + scale b + y; the GEMM kernels read whole weight tiles, so the
-    // weights and biases are copied into row-padded buffers first
+    // unfused: one GEMM per problem, y = scale (x W^T) + scale b + y, on weights packed as a model's linears are
+    if (int rc = pack_begin(s)) return rc;
+    WeightStore wst;
     std::vector<ConvW> ws((size_t)count);
-    std::vector<void*> owned;
-    int rc = 0;
-    for (int i = 0; i < count && !rc; ++i) {
-        const sd_cn_problem& q = problems[i];
-        const long rows = ((long)q.C + kWeightRowPad - 1) / kWeightRowPad * kWeightRowPad;
-        void *w = nullptr, *b = nullptr;
-        if (hipMalloc(&w, (size_t)rows * q.C * sizeof(half_t)) != hipSuccess || hipMalloc(&b, (size_t)rows * sizeof(float)) != hipSuccess) {
-            set_error("sd_op_controlnet_residuals: out of device memory"); rc = SD_ERR_HIP;
+    for (int i = 0; i < count; ++i)
+        if (int rc = pack_conv_op(wst, problems[i].w, problems[i].C, problems[i].C, 1, problems[i].bias, false, false, &ws[(size_t)i])) return rc;
+    if (int rc = pack_end()) return rc;
+    if (scale == 0.f) return SD_OK;
+    return run_op_on_arena(s, iters, ms_per_launch, [&](Ctx& c) {
+        for (int i = 0; i < count; ++i) {
+            const sd_cn_problem& q = problems[i];
+            View y(static_cast<half_t*>(q.y), q.ldy, q.C);
+            ConvFuse f;
+            f.acc_scale = scale; f.bias_scale = scale;
+            op_conv(c, ws[(size_t)i], view_of(q.x, q.ldx, q.C), 1, q.M, 1, y, 1, 0, nullptr, 0, &y, 0, -1, 0, &f);
         }
-        if (w) owned.push_back(w);
-        if (b) owned.push_back(b);
-        if (rc) break;
-        if (hipMemsetAsync(w, 0, (size_t)rows * q.C * sizeof(half_t), s) != hipSuccess ||
-            hipMemsetAsync(b, 0, (size_t)rows * sizeof(float), s) != hipSuccess ||
-            hipMemcpyAsync(w, q.w, (size_t)q.C * q.C * sizeof(half_t), hipMemcpyDeviceToDevice, s) != hipSuccess ||
-            hipMemcpyAsync(b, q.bias, (size_t)q.C * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) {
-            set_error("sd_op_controlnet_residuals: copy failed"); rc = SD_ERR_HIP;
-        }
-        ConvW& cw = ws[(size_t)i];
-        cw.w = static_cast<half_t*>(w); cw.bias = static_cast<float*>(b); cw.cin = q.C; cw.cout = q.C; cw.ks = 1; cw.K = q.C;
-    }
-    if (!rc && scale != 0.f)
-        rc = run_op_on_arena(s, iters, ms_per_launch, [&](Ctx& c) {
-            for (int i = 0; i < count; ++i) {
-                const sd_cn_problem& q = problems[i];
-                View y(static_cast<half_t*>(q.y), q.ldy, q.C);
-                ConvFuse f;
-                f.acc_scale = scale; f.bias_scale = scale;
-                op_conv(c, ws[(size_t)i], View(const_cast<half_t*>(static_cast<const half_t*>(q.x)), q.ldx, q.C), 1, q.M, 1,
-                        y, 1, 0, nullptr, 0, &y, 0, -1, 0, &f);
-            }
-        });
-    (void)hipStreamSynchronize(s);
-    for (void* p : owned) (void)hipFree(p);
-    return rc;
+    });
 }
 
 int sd_op_controlnet_cond_embed(sd_controlnet* cn, const void* image, int n, int H, int W, void* out, int iters,
@@ -2199,18 +1969,17 @@ int sd_op_fold_upconv(const void* w_oihw, void* out, int Cout, int Cin, void* st
     if (!w_oihw || !out || Cout < 1 || Cin < 64 || Cin % 64 != 0) {
         set_error("sd_op_fold_upconv: bad arguments (Cin must be a multiple of 64)"); return SD_ERR_INVALID;
     }
+    if (Cout % 8 != 0) { set_error("sd_op_fold_upconv: no folded pack is built for Cout % 8 != 0"); return SD_ERR_UNSUPPORTED; }
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const long rows = ((long)Cout + kWeightRowPad - 1) / kWeightRowPad * kWeightRowPad, K4 = 4L * Cin;
-    DevScope scope;
-    half_t* wp = nullptr;
-    SD_DEV_ALLOC(scope, wp, (size_t)4 * rows * K4 * sizeof(half_t));
-    SD_HIP_CHECK(hipMemsetAsync(wp, 0, (size_t)4 * rows * K4 * sizeof(half_t), s));
-    if (int rc = launch_fold_upconv(static_cast<const half_t*>(w_oihw), wp, Cout, Cin, s)) return rc;
+    if (int rc = pack_begin(s)) return rc;
+    WeightStore ws;
+    ConvW cw;
+    if (int rc = ws.pack_conv(static_cast<const half_t*>(w_oihw), Cout, Cin, 3, 3, nullptr, &cw, true)) return rc;
+    const long K4 = 4L * Cin, rows = weight_rows(Cout);
     for (int par = 0; par < 4; ++par)           // the panels without their row padding
-        SD_HIP_CHECK(hipMemcpyAsync(static_cast<half_t*>(out) + (long)par * Cout * K4, wp + (long)par * rows * K4,
-                                    (size_t)Cout * K4 * sizeof(half_t), hipMemcpyDeviceToDevice, s));
-    SD_HIP_CHECK(hipStreamSynchronize(s));
-    return SD_OK;
+        SD_HIP_CHECK(hipMemcpyAsync(static_cast<half_t*>(out) + (long)par * Cout * K4, cw.w_up + (long)par * rows * K4,
+                                    (size_t)Cout * K4 * sizeof(half_t), hipMemcpyDeviceToDevice, 0));
+    return pack_end();
 }
 
 int sd_op_upconv2x_ex(const void* x, const void* w_oihw, const void* bias_f32, const void* rowadd_f32, const void* res,
@@ -2226,39 +1995,28 @@ int sd_op_upconv2x_ex(const void* x, const void* w_oihw, const void* bias_f32, c
     }
     for (int i = 0; i < 4; ++i) ran[i] = 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    // both packs, as WeightStore::pack_conv(fold_up2x) leaves them (the bias stays fp32, as in sd_op_conv2d_ex)
-    const long K = 9L * Cin, rows = ((long)Cout + kWeightRowPad - 1) / kWeightRowPad * kWeightRowPad;
-    DevScope scope;
-    ConvW cw;
-    cw.cin = Cin; cw.cout = Cout; cw.ks = 3; cw.K = K;
-    SD_DEV_ALLOC(scope, cw.w, (size_t)rows * K * sizeof(half_t));
-    SD_DEV_ALLOC(scope, cw.bias, (size_t)rows * sizeof(float));
-    SD_HIP_CHECK(hipMemsetAsync(cw.w, 0, (size_t)rows * K * sizeof(half_t), s));
-    SD_HIP_CHECK(hipMemsetAsync(cw.bias, 0, (size_t)rows * sizeof(float), s));
-    int rc = launch_pack_conv(static_cast<const half_t*>(w_oihw), cw.w, Cout, Cin, 3, 3, K, s);
+    if (int rc = pack_begin(s)) return rc;
+    WeightStore ws;
+    ConvW cw;                               // both packs, where a model's upsampler conv gets both
+    int rc = pack_conv_op(ws, w_oihw, Cout, Cin, 3, bias_f32, false, true, &cw);
     if (rc) return rc;
-    if (bias_f32) SD_HIP_CHECK(hipMemcpyAsync(cw.bias, bias_f32, (size_t)Cout * sizeof(float), hipMemcpyDeviceToDevice, s));
-    if (Cout % 8 == 0) {
-        SD_DEV_ALLOC(scope, cw.w_up, (size_t)16 * rows * Cin * sizeof(half_t));
-        SD_HIP_CHECK(hipMemsetAsync(cw.w_up, 0, (size_t)16 * rows * Cin * sizeof(half_t), s));
-        if ((rc = launch_fold_upconv(static_cast<const half_t*>(w_oihw), cw.w_up, Cout, Cin, s))) return rc;
-    }
-    const long OHW = 4L * H * W;
     GnStatBuf gb;
-    if (gn_groups > 0) SD_DEV_ALLOC(scope, gb.buf, (size_t)gnstat_floats(N, OHW, gn_groups) * sizeof(float));
-    int folded = 0;
+    if (gn_groups > 0 && !(gb.buf = static_cast<float*>(ws.dmalloc((size_t)gnstat_floats(N, 4L * H * W, gn_groups) * sizeof(float))))) {
+        set_error("hipMalloc failed (GroupNorm summaries)"); return SD_ERR_HIP;
+    }
+    if ((rc = pack_end())) return rc;
+    ConvLaunch l;
+    const View yv = view_of(y, ldy, Cout), rv = view_of(res, ldres, Cout);
     rc = run_op_on_arena(s, 0, nullptr, [&](Ctx& c) {
         ConvFuse f;
         f.acc_scale = acc_scale; f.bias_scale = bias_scale;
         f.gn_out = gn_groups > 0 ? &gb : nullptr; f.gn_groups = gn_groups;
-        f.fold_ran = &folded;
-        const View rv(const_cast<half_t*>(static_cast<const half_t*>(res)), ldres, Cout);
-        op_conv(c, cw, View(const_cast<half_t*>(static_cast<const half_t*>(x)), ldx, Cin), N, H, W,
-                View(static_cast<half_t*>(y), ldy, Cout), 1, 1, static_cast<const float*>(rowadd_f32), Cout, res ? &rv : nullptr,
-                0, -1, 0, &f);
+        if (conv_prepare(c, cw, view_of(x, ldx, Cin), N, H, W, yv, 1, 1, static_cast<const float*>(rowadd_f32), Cout,
+                         res ? &rv : nullptr, 0, -1, 0, &f, &l))
+            conv_launch(c, l, yv, nullptr);
     });
     if (rc) return rc;
-    ran[0] = folded;
+    ran[0] = l.plan.kind == kKindUpconvFold;
     if (gb.st.part) {
         ran[1] = gb.st.S; ran[2] = (int)gb.st.rows;
         if (gn_summaries)

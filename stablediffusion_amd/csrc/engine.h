@@ -109,6 +109,8 @@ struct CacheTag {
     void clear() { valid = false; }
 };
 
+// rows of a packed weight matrix of `cout` outputs (zero rows up to a multiple of kWeightRowPad)
+inline long weight_rows(long cout) { return (cout + kWeightRowPad - 1) / kWeightRowPad * kWeightRowPad; }
 struct ConvW {          // conv or linear, packed [rows_pad][K] fp16 + fp32 bias (padded)
     half_t* w = nullptr;
     float* bias = nullptr;
@@ -141,7 +143,7 @@ struct ConvFuse {
     RowStat* stat_out = nullptr;        // row statistics of the OUTPUT for the LayerNorm that follows
     GnStatBuf* gn_out = nullptr;        // GroupNorm summaries of the OUTPUT for the GroupNorm that follows
     int gn_groups = 0;
-    // GroupNorm (+ SiLU) of the INPUT applied inside the convolution (set by op_gn_conv when igemm2_gn_fusable):
+    // GroupNorm (+ SiLU) of the INPUT applied inside the convolution (set by op_gn_conv_fused):
     const struct NormW* gn_in = nullptr;
     GnStats gn_in_stats;                // (mean, M2) summaries of the input
     int gn_in_groups = 0;
@@ -151,7 +153,6 @@ struct ConvFuse {
     float acc_scale = 1.f, bias_scale = 1.f;
     // tile hint of this launch (IGemmRequest::hint_variant / hint_splits): -1 = none
     int tile_variant = -1, tile_splits = 0;
-    int* fold_ran = nullptr;            // single-operator entries: set to 1 when the folded-upsample kernel ran, else 0
 };
 struct NormW {
     float* gamma = nullptr;
@@ -174,13 +175,19 @@ class WeightStore {
     int set(const std::string& key, const void* data, const int64_t* shape, int ndim, int dtype);
     bool complete(std::string* missing) const;
     const RawTensor* raw(const std::string& key) const;
-    // packing helpers (device work on the null stream; finalize() synchronises once)
+    // packing helpers (device work on the null stream; finalize() synchronises once).  Each comes in two forms: by key
+    // (the model load: the raw tensors of `prefix`) and on the operands themselves (fp16 device weights, fp32 host bias /
+    // gamma / beta; bias_host may be nullptr: no bias), which the first resolves to and the single-operator entries call.
     // fold_up2x: the conv follows a nearest-2x upsample (upsamplers.0.conv): also build the folded pack (ConvW::w_up)
     int pack_conv(const std::string& prefix, ConvW* out, bool has_bias = true, bool fold_up2x = false);
+    int pack_conv(const half_t* w_oihw_dev, int O, int I, int KH, int KW, const float* bias_host, ConvW* out,
+                  bool fold_up2x = false);
     int pack_rows(const std::vector<std::string>& weight_keys, const std::vector<std::string>& bias_keys,
                   ConvW* out);                                  // row-concatenated linears
     int pack_geglu(const std::string& prefix, ConvW* out);      // [8C][C] -> 64-row interleave
+    int pack_geglu(const half_t* w_dev, long O, long I, const float* bias_host, ConvW* out);
     int pack_norm(const std::string& prefix, NormW* out);
+    int pack_norm(const float* gamma_host, const float* beta_host, int C, NormW* out);
     // Fold LayerNorm `ln` (applied to the GEMM's input) into the packed linear `w`: W <- W diag(gamma)
     // (rows < rows_scaled additionally times row_scale), bias <- bias + W beta, w->wsum = row sums.
     int fold_ln(ConvW* w, const NormW& ln, int rows_scaled, float row_scale);
@@ -330,6 +337,22 @@ void prof_close(hipStream_t s);
 int prof_collect(std::map<std::string, ProfAgg>* out);   // synchronises, aggregates by kernel name
 
 // ---- op wrappers: skip the launch in dry mode, latch the first error ----
+// A convolution launch as conv_prepare leaves it: the problem, its plan, the split-K workspace (arena), whether
+// row_stats_kernel runs behind it (statistics asked for that the epilogue does not write), the weights' real channels.
+struct ConvLaunch {
+    IGemmParams p;
+    IGemmPlan plan;
+    float* partial = nullptr;
+    bool stats_after = false;
+    int cin = 0;
+};
+// op_conv = conv_prepare + conv_launch.  conv_prepare poses and plans the launch, refuses what the planned kernel cannot
+// do, fills in what the plan leaves of the requested statistics (fuse->gn_out->st, fuse->stat_out's layout) and takes the
+// workspace from the arena -- all of it the same in the planning and the live pass; false when there is nothing to launch
+// (planning pass, or an error latched).  conv_launch issues it (stat_out: ConvFuse::stat_out).
+bool conv_prepare(Ctx& c, const ConvW& w, View x, int N, int H, int W, View y, int stride, int up, const float* rowadd,
+                  int rowadd_ld, const View* res, int geglu, int pad, int act, const ConvFuse* fuse, ConvLaunch* out);
+void conv_launch(Ctx& c, const ConvLaunch& l, View y, RowStat* stat_out);
 void op_conv(Ctx& c, const ConvW& w, View x, int N, int H, int W, View y, int stride = 1, int up = 0,
              const float* rowadd = nullptr, int rowadd_ld = 0, const View* res = nullptr, int geglu = 0,
              int pad = -1, int act = 0, const ConvFuse* fuse = nullptr);
@@ -340,12 +363,20 @@ inline long rowstat_floats(long M, int C) { return M * ((C + 63) / 64) * 2; }
 inline long gnstat_floats(int N, long HW, int G) { const long t = (HW + 63) / 64; return (long)N * (t > 64 ? t : 64) * G * 2; }
 void op_groupnorm(Ctx& c, const NormW& n, View x, View y, int N, long HW, int G, float eps, int silu,
                   const GnStatBuf* pre = nullptr);
-// y = conv(act(GroupNorm(x))): inside the convolution when the launch can apply the norm to its halo tiles in LDS
-// (igemm2_gn_fusable; the normalised tensor never exists), otherwise GroupNorm kernel + convolution.  `pre` = the
-// summaries of x its producer left (or nullptr: a statistics pass runs); the other arguments as op_conv's.
+// y = conv(act(GroupNorm(x))): GroupNorm kernel + convolution, or, under SD_GN_FUSE=1, op_gn_conv_fused where it takes
+// the problem.  `pre` = the summaries of x its producer left (or nullptr: a statistics pass runs); the other arguments
+// as op_conv's.
 void op_gn_conv(Ctx& c, const NormW& n, const ConvW& w, View x, int N, int H, int W, View y, int G, float eps, int silu,
                 const GnStatBuf* pre, const float* rowadd = nullptr, int rowadd_ld = 0, const View* res = nullptr,
                 const ConvFuse* fuse = nullptr);
+// The same inside the convolution: the launch applies the norm to its halo tiles in LDS and the normalised tensor never
+// exists.  Returns false -- nothing launched or allocated -- when the launch cannot take the norm (no per-64 pack of
+// gamma / beta, n.C != Cin, !igemm2_gn_fusable) or SD_NO_GN_FUSE is set.  `prepared` (the timed operator entry): the
+// statistics launches are issued, the convolution is only prepared into it and its arena allocations stay for the
+// caller's conv_launch.
+bool op_gn_conv_fused(Ctx& c, const NormW& n, const ConvW& w, View x, int N, int H, int W, View y, int G, float eps,
+                      int silu, const GnStatBuf* pre, const float* rowadd = nullptr, int rowadd_ld = 0,
+                      const View* res = nullptr, const ConvFuse* fuse = nullptr, ConvLaunch* prepared = nullptr);
 void op_layernorm(Ctx& c, const NormW& n, View x, View y, long rows, float eps);
 // y = x + GEGLU(LN(x) ff1) ff2 in one launch (ffn.hip) when the problem fits it (C = 320, LayerNorm folded into ff1, the
 // row statistics of x at hand); returns false -- nothing launched -- when it does not: the caller runs the two GEMMs.

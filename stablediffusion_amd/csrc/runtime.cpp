@@ -124,10 +124,10 @@ int WeightStore::host_floats(const std::string& key, std::vector<float>* out) co
 
 static long round_up(long a, long b) { return (a + b - 1) / b * b; }
 
-static int upload_bias(WeightStore* ws, const std::vector<float>& host, int cout, float** dst) {
-    const long padded = round_up(cout, kWeightRowPad);
+static int upload_bias(WeightStore* ws, const float* host, int cout, float** dst) {
+    const long padded = weight_rows(cout);
     std::vector<float> buf((size_t)padded, 0.f);
-    std::memcpy(buf.data(), host.data(), (size_t)cout * sizeof(float));
+    std::memcpy(buf.data(), host, (size_t)cout * sizeof(float));
     *dst = static_cast<float*>(ws->dmalloc((size_t)padded * sizeof(float)));
     if (!*dst) { set_error("hipMalloc failed (bias)"); return 3; }
     SD_HIP_CHECK(hipMemcpy(*dst, buf.data(), (size_t)padded * sizeof(float), hipMemcpyHostToDevice));
@@ -137,16 +137,23 @@ static int upload_bias(WeightStore* ws, const std::vector<float>& host, int cout
 int WeightStore::pack_conv(const std::string& prefix, ConvW* out, bool has_bias, bool fold_up2x) {
     const RawTensor* w = raw(prefix + ".weight");
     if (!w) { set_error("missing weight: " + prefix + ".weight"); return 2; }
-    const int O = (int)w->shape[0], I = (int)w->shape[1];
     const int KH = w->shape.size() == 4 ? (int)w->shape[2] : 1;
     const int KW = w->shape.size() == 4 ? (int)w->shape[3] : 1;
+    std::vector<float> b;
+    if (has_bias)
+        if (int rc = host_floats(prefix + ".bias", &b)) return rc;
+    return pack_conv(w->dev, (int)w->shape[0], (int)w->shape[1], KH, KW, has_bias ? b.data() : nullptr, out, fold_up2x);
+}
+
+int WeightStore::pack_conv(const half_t* w_dev, int O, int I, int KH, int KW, const float* bias_host, ConvW* out,
+                           bool fold_up2x) {
     const long K = round_up((long)KH * KW * I, 64);
-    const long rows = round_up(O, kWeightRowPad);
+    const long rows = weight_rows(O);
     out->cin = I; out->cout = O; out->ks = KH; out->K = K;
     out->w = static_cast<half_t*>(dmalloc((size_t)rows * K * sizeof(half_t)));
     if (!out->w) { set_error("hipMalloc failed (weights)"); return 3; }
     SD_HIP_CHECK(hipMemsetAsync(out->w, 0, (size_t)rows * K * sizeof(half_t), 0));
-    int rc = launch_pack_conv(w->dev, out->w, O, I, KH, KW, K, 0);
+    int rc = launch_pack_conv(w_dev, out->w, O, I, KH, KW, K, 0);
     if (rc) return rc;
     out->w_up = nullptr;
     if (fold_up2x && KH == 3 && KW == 3 && I % 64 == 0 && O % 8 == 0) {
@@ -155,17 +162,10 @@ int WeightStore::pack_conv(const std::string& prefix, ConvW* out, bool has_bias,
         out->w_up = static_cast<half_t*>(dmalloc(bytes));
         if (!out->w_up) { set_error("hipMalloc failed (folded upsample weights)"); return 3; }
         SD_HIP_CHECK(hipMemsetAsync(out->w_up, 0, bytes, 0));
-        if ((rc = launch_fold_upconv(w->dev, out->w_up, O, I, 0))) return rc;
+        if ((rc = launch_fold_upconv(w_dev, out->w_up, O, I, 0))) return rc;
     }
     out->bias = nullptr;
-    if (has_bias) {
-        std::vector<float> b;
-        rc = host_floats(prefix + ".bias", &b);
-        if (rc) return rc;
-        rc = upload_bias(this, b, O, &out->bias);
-        if (rc) return rc;
-    }
-    return 0;
+    return bias_host ? upload_bias(this, bias_host, O, &out->bias) : 0;
 }
 
 int WeightStore::pack_rows(const std::vector<std::string>& wkeys, const std::vector<std::string>& bkeys,
@@ -180,7 +180,7 @@ int WeightStore::pack_rows(const std::vector<std::string>& wkeys, const std::vec
         total += w->shape[0];
     }
     if (I % 64 != 0) { set_error("pack_rows: inner dim must be a multiple of 64"); return 1; }
-    const long rows = round_up(total, kWeightRowPad);
+    const long rows = weight_rows(total);
     out->cin = I; out->cout = (int)total; out->ks = 1; out->K = I;
     out->w = static_cast<half_t*>(dmalloc((size_t)rows * I * sizeof(half_t)));
     if (!out->w) { set_error("hipMalloc failed (weights)"); return 3; }
@@ -202,7 +202,7 @@ int WeightStore::pack_rows(const std::vector<std::string>& wkeys, const std::vec
             all.insert(all.end(), b.begin(), b.end());
         }
         if ((long)all.size() != total) { set_error("pack_rows: bias length mismatch"); return 1; }
-        int rc = upload_bias(this, all, (int)total, &out->bias);
+        int rc = upload_bias(this, all.data(), (int)total, &out->bias);
         if (rc) return rc;
     }
     return 0;
@@ -214,28 +214,31 @@ int WeightStore::pack_rows(const std::vector<std::string>& wkeys, const std::vec
 int WeightStore::pack_geglu(const std::string& prefix, ConvW* out) {
     const RawTensor* w = raw(prefix + ".weight");
     if (!w) { set_error("missing weight: " + prefix + ".weight"); return 2; }
-    const long O = w->shape[0], I = w->shape[1];
+    std::vector<float> b;
+    if (int rc = host_floats(prefix + ".bias", &b)) return rc;
+    return pack_geglu(w->dev, w->shape[0], w->shape[1], b.data(), out);
+}
+
+int WeightStore::pack_geglu(const half_t* w_dev, long O, long I, const float* b, ConvW* out) {
     const long half_rows = O / 2;
     if (half_rows % 64 != 0 || I % 64 != 0) { set_error("pack_geglu: dims must be multiples of 64"); return 1; }
-    const long rows = round_up(O, kWeightRowPad);
+    const long rows = weight_rows(O);
     out->cin = (int)I; out->cout = (int)O; out->ks = 1; out->K = I;
     out->w = static_cast<half_t*>(dmalloc((size_t)rows * I * sizeof(half_t)));
     if (!out->w) { set_error("hipMalloc failed (weights)"); return 3; }
     SD_HIP_CHECK(hipMemsetAsync(out->w, 0, (size_t)rows * I * sizeof(half_t), 0));
-    std::vector<float> b, bp((size_t)O);
-    int rc = host_floats(prefix + ".bias", &b);
-    if (rc) return rc;
+    std::vector<float> bp((size_t)O, 0.f);
     for (long blk = 0; blk < half_rows / 64; ++blk) {
-        SD_HIP_CHECK(hipMemcpyAsync(out->w + (blk * 128) * I, w->dev + (blk * 64) * I,
+        SD_HIP_CHECK(hipMemcpyAsync(out->w + (blk * 128) * I, w_dev + (blk * 64) * I,
                                     (size_t)64 * I * sizeof(half_t), hipMemcpyDeviceToDevice, 0));
-        SD_HIP_CHECK(hipMemcpyAsync(out->w + (blk * 128 + 64) * I, w->dev + (half_rows + blk * 64) * I,
+        SD_HIP_CHECK(hipMemcpyAsync(out->w + (blk * 128 + 64) * I, w_dev + (half_rows + blk * 64) * I,
                                     (size_t)64 * I * sizeof(half_t), hipMemcpyDeviceToDevice, 0));
-        for (int e = 0; e < 64; ++e) {
+        for (int e = 0; b && e < 64; ++e) {
             bp[(size_t)(blk * 128 + e)] = b[(size_t)(blk * 64 + e)];
             bp[(size_t)(blk * 128 + 64 + e)] = b[(size_t)(half_rows + blk * 64 + e)];
         }
     }
-    return upload_bias(this, bp, (int)O, &out->bias);
+    return upload_bias(this, bp.data(), (int)O, &out->bias);
 }
 
 int WeightStore::pack_norm(const std::string& prefix, NormW* out) {
@@ -244,16 +247,22 @@ int WeightStore::pack_norm(const std::string& prefix, NormW* out) {
     if (rc) return rc;
     rc = host_floats(prefix + ".bias", &b);
     if (rc) return rc;
-    out->C = (int)g.size();
-    out->gamma = static_cast<float*>(dmalloc(g.size() * sizeof(float)));
-    out->beta = static_cast<float*>(dmalloc(b.size() * sizeof(float)));
+    if (b.size() != g.size()) { set_error("pack_norm: " + prefix + ".weight and .bias differ in length"); return 1; }
+    return pack_norm(g.data(), b.data(), (int)g.size(), out);
+}
+
+int WeightStore::pack_norm(const float* g, const float* b, int C, NormW* out) {
+    const size_t n = (size_t)C;
+    out->C = C;
+    out->gamma = static_cast<float*>(dmalloc(n * sizeof(float)));
+    out->beta = static_cast<float*>(dmalloc(n * sizeof(float)));
     if (!out->gamma || !out->beta) { set_error("hipMalloc failed (norm)"); return 3; }
-    SD_HIP_CHECK(hipMemcpy(out->gamma, g.data(), g.size() * sizeof(float), hipMemcpyHostToDevice));
-    SD_HIP_CHECK(hipMemcpy(out->beta, b.data(), b.size() * sizeof(float), hipMemcpyHostToDevice));
+    SD_HIP_CHECK(hipMemcpy(out->gamma, g, n * sizeof(float), hipMemcpyHostToDevice));
+    SD_HIP_CHECK(hipMemcpy(out->beta, b, n * sizeof(float), hipMemcpyHostToDevice));
     out->gb = nullptr;
-    if (g.size() % 64 == 0) {          // packed per 64 channels for the convolution-fused GroupNorm
-        std::vector<float> gb(2 * g.size());
-        for (size_t blk = 0; blk < g.size() / 64; ++blk)
+    if (n % 64 == 0) {                 // packed per 64 channels for the convolution-fused GroupNorm
+        std::vector<float> gb(2 * n);
+        for (size_t blk = 0; blk < n / 64; ++blk)
             for (int e = 0; e < 64; ++e) {
                 gb[blk * 128 + e] = g[blk * 64 + e];
                 gb[blk * 128 + 64 + e] = b[blk * 64 + e];
@@ -267,7 +276,7 @@ int WeightStore::pack_norm(const std::string& prefix, NormW* out) {
 
 int WeightStore::fold_ln(ConvW* w, const NormW& ln, int rows_scaled, float row_scale) {
     if (ln.C != w->K || w->ks != 1) { set_error("fold_ln: LayerNorm width must equal the linear's K"); return 1; }
-    const long padded = round_up(w->cout, kWeightRowPad);
+    const long padded = weight_rows(w->cout);
     float* nb = static_cast<float*>(dmalloc((size_t)padded * sizeof(float)));
     w->wsum = static_cast<float*>(dmalloc((size_t)padded * sizeof(float)));
     if (!nb || !w->wsum) { set_error("hipMalloc failed (fold_ln)"); return 3; }
@@ -290,7 +299,7 @@ int WeightStore::fold_linear(const std::string& outer, const std::string& inner,
     }
     const int O = (int)wo->shape[0], J = (int)wo->shape[1], Ki = (int)wi->shape[1];
     const long K = round_up((long)Ki + J, 64);
-    const long rows = round_up(O, kWeightRowPad);
+    const long rows = weight_rows(O);
     out->cin = Ki + J; out->cout = O; out->ks = 1; out->K = K;
     out->w = static_cast<half_t*>(dmalloc((size_t)rows * K * sizeof(half_t)));
     if (!out->w) { set_error("hipMalloc failed (weights)"); return 3; }
@@ -307,7 +316,7 @@ int WeightStore::fold_linear(const std::string& outer, const std::string& inner,
         for (int j = 0; j < J; ++j) acc += (double)wof[(size_t)n * J + j] * bi[(size_t)j];
         b[(size_t)n] = (float)acc;
     }
-    return upload_bias(this, b, O, &out->bias);
+    return upload_bias(this, b.data(), O, &out->bias);
 }
 
 // ---------------------------------------------------------------------------------------- profiler
@@ -436,13 +445,14 @@ static ConvProfRow conv_prof_row(const IGemmPlan& plan, const IGemmParams& p, in
     return r;
 }
 
-void op_conv(Ctx& c, const ConvW& w, View x, int N, int H, int W, View y, int stride, int up,
-             const float* rowadd, int rowadd_ld, const View* res, int geglu, int pad, int act, const ConvFuse* fuse) {
+bool conv_prepare(Ctx& c, const ConvW& w, View x, int N, int H, int W, View y, int stride, int up, const float* rowadd,
+                  int rowadd_ld, const View* res, int geglu, int pad, int act, const ConvFuse* fuse, ConvLaunch* out) {
     const RowStat* ln_in = fuse ? fuse->ln_in : nullptr;
     const float ln_eps = fuse ? fuse->ln_eps : 0.f;
     RowStat* stat_out = fuse ? fuse->stat_out : nullptr;
     GnStatBuf* gn_out = fuse ? fuse->gn_out : nullptr;
-    IGemmParams p = conv_problem(N, H, W, w.ks == 1 ? (int)w.K : w.cin, w.cout, w.ks, stride, up, pad);
+    IGemmParams& p = out->p;
+    p = conv_problem(N, H, W, w.ks == 1 ? (int)w.K : w.cin, w.cout, w.ks, stride, up, pad);
     p.K = (int)w.K;         // (the pack's K)
     p.x = x.p; p.ldx = x.ld;
     p.w = w.w; p.bias = w.bias;
@@ -452,7 +462,7 @@ void op_conv(Ctx& c, const ConvW& w, View x, int N, int H, int W, View y, int st
     p.geglu = geglu;
     p.act = act;
     if (ln_in) {
-        if (!w.wsum) { set_error("op_conv: LayerNorm statistics passed to a linear without folded weights"); c.err = 1; return; }
+        if (!w.wsum) { set_error("op_conv: LayerNorm statistics passed to a linear without folded weights"); c.err = 1; return false; }
         p.ln_stat = ln_in->p; p.ln_parts = ln_in->parts; p.ln_part_w = ln_in->width; p.ln_C = (int)w.K; p.ln_eps = ln_eps; p.ln_wsum = w.wsum;
     }
     if (fuse && fuse->gn_in) {
@@ -466,31 +476,42 @@ void op_conv(Ctx& c, const ConvW& w, View x, int N, int H, int W, View y, int st
     // a row of the table), what it leaves of the requested statistics, the workspace, the name
     IGemmRequest rq{stat_out ? stat_out->p : nullptr, gn_out ? gn_out->buf : nullptr, fuse ? fuse->gn_groups : 0};
     if (fuse) { rq.hint_variant = fuse->tile_variant; rq.hint_splits = fuse->tile_splits; }
-    const IGemmPlan plan = conv_plan(p, up == 1 ? w.w_up : nullptr, rq);
-    if (fuse && fuse->fold_ran) *fuse->fold_ran = plan.kind == kKindUpconvFold;
+    const IGemmPlan& plan = out->plan = conv_plan(p, up == 1 ? w.w_up : nullptr, rq);
     const bool v2 = plan.kind != kKindIgemm1;
-    if ((p.acc_scale != 1.f || p.bias_scale != 1.f) && !plan.scales_ok) { set_error("op_conv: output scaling needs the LDS-DMA kernels (not GEGLU / weight-stationary)"); c.err = 1; return; }
-    if (ln_in && !v2) { set_error("op_conv: the LayerNorm fold needs the LDS-DMA kernel"); c.err = 1; return; }
-    if (act && !v2) { set_error("op_conv: activation epilogue needs the LDS-DMA kernel (Cin % 64, Cout % 8)"); c.err = 1; return; }
+    if ((p.acc_scale != 1.f || p.bias_scale != 1.f) && !plan.scales_ok) { set_error("op_conv: output scaling needs the LDS-DMA kernels (not GEGLU / weight-stationary)"); c.err = 1; return false; }
+    if (ln_in && !v2) { set_error("op_conv: the LayerNorm fold needs the LDS-DMA kernel"); c.err = 1; return false; }
+    if (act && !v2) { set_error("op_conv: activation epilogue needs the LDS-DMA kernel (Cin % 64, Cout % 8)"); c.err = 1; return false; }
     if (gn_out) {
         gn_out->st = GnStats();
         if (plan.gnstats) { gn_out->st.part = gn_out->buf; gn_out->st.rows = plan.gn_rows; gn_out->st.S = p.OH * p.OW / plan.gn_rows; }
     }
-    const bool own_stats = plan.rowstats;      // the GEMM's epilogue writes the row statistics itself
     if (stat_out) { stat_out->parts = plan.rs_parts; stat_out->width = plan.rs_part_w; }
-    float* partial = plan.partial_floats > 0 ? c.arena->alloc_f(plan.partial_floats) : nullptr;
-    if (c.dry || c.err) return;
+    out->stats_after = stat_out && !plan.rowstats;      // (otherwise the GEMM's epilogue writes the row statistics itself)
+    out->partial = plan.partial_floats > 0 ? c.arena->alloc_f(plan.partial_floats) : nullptr;
+    out->cin = w.cin;
+    return !(c.dry || c.err);
+}
+
+void conv_launch(Ctx& c, const ConvLaunch& l, View y, RowStat* stat_out) {
+    const IGemmParams& p = l.p;
     if (prof_enabled()) {
-        const ConvProfRow row = conv_prof_row(plan, p, w.cin);
+        const ConvProfRow row = conv_prof_row(l.plan, p, l.cin);
         prof_open(c.stream, row.name, row.flops, row.bytes);
     }
-    c.err = launch_igemm2(p, partial, c.stream, &plan);
+    c.err = launch_igemm2(p, l.partial, c.stream, &l.plan);
     prof_close(c.stream);
-    if (stat_out && !own_stats && !c.err) {
-        prof_open(c.stream, "row_stats_kernel", 0.0, 2.0 * p.M * w.cout);
-        c.err = launch_row_stats(y.p, y.ld, stat_out->p, p.M, w.cout, c.stream);
+    if (l.stats_after && !c.err) {
+        prof_open(c.stream, "row_stats_kernel", 0.0, 2.0 * p.M * p.Cout);
+        c.err = launch_row_stats(y.p, y.ld, stat_out->p, p.M, p.Cout, c.stream);
         prof_close(c.stream);
     }
+}
+
+void op_conv(Ctx& c, const ConvW& w, View x, int N, int H, int W, View y, int stride, int up,
+             const float* rowadd, int rowadd_ld, const View* res, int geglu, int pad, int act, const ConvFuse* fuse) {
+    ConvLaunch l;
+    if (conv_prepare(c, w, x, N, H, W, y, stride, up, rowadd, rowadd_ld, res, geglu, pad, act, fuse, &l))
+        conv_launch(c, l, y, fuse ? fuse->stat_out : nullptr);
 }
 
 void op_groupnorm(Ctx& c, const NormW& n, View x, View y, int N, long HW, int G, float eps, int silu,
@@ -518,34 +539,34 @@ void op_gn_conv(Ctx& c, const NormW& n, const ConvW& w, View x, int N, int H, in
     // Off unless SD_GN_FUSE=1: measured slower than GroupNorm kernel + convolution on every UNet shape (the in-LDS
     // transform does not hide behind the MFMAs, profiles/r03_gn_fused_conv.txt); the kernel stays for the operator
     // test (sd_op_groupnorm_conv2d) and as the base of the next attempt.
-    static const bool off = getenv("SD_GN_FUSE") == nullptr || getenv("SD_NO_GN_FUSE") != nullptr;
+    static const bool on = getenv("SD_GN_FUSE") != nullptr;
+    if (on && op_gn_conv_fused(c, n, w, x, N, H, W, y, G, eps, silu, pre, rowadd, rowadd_ld, res, fuse)) return;
+    const size_t mk = c.arena->mark();
+    View hn(c.arena->alloc_h((long)N * H * W * n.C), n.C, n.C);
+    op_groupnorm(c, n, x, hn, N, (long)H * W, G, eps, silu, pre);
+    op_conv(c, w, hn, N, H, W, y, 1, 0, rowadd, rowadd_ld, res, 0, -1, 0, fuse);
+    c.arena->release(mk);
+}
+
+bool op_gn_conv_fused(Ctx& c, const NormW& n, const ConvW& w, View x, int N, int H, int W, View y, int G, float eps,
+                      int silu, const GnStatBuf* pre, const float* rowadd, int rowadd_ld, const View* res,
+                      const ConvFuse* fuse, ConvLaunch* prepared) {
+    static const bool off = getenv("SD_NO_GN_FUSE") != nullptr;         // kill switch
     const long HW = (long)H * W;
-    // the problem as op_conv will pose it (stride 1, no upsample: the only form that follows a GroupNorm)
+    // the problem as conv_prepare will pose it (stride 1, no upsample: the only form that follows a GroupNorm)
     IGemmParams q = conv_problem(N, H, W, w.ks == 1 ? (int)w.K : w.cin, w.cout, w.ks, 1, 0, -1);
     q.K = (int)w.K;
     q.x = x.p; q.ldx = x.ld;
-    const bool fused = !off && n.gb && n.C == q.Cin && igemm2_gn_fusable(q, G);
-    if (!fused) {
-        const size_t mk = c.arena->mark();
-        View hn(c.arena->alloc_h((long)N * HW * n.C), n.C, n.C);
-        op_groupnorm(c, n, x, hn, N, HW, G, eps, silu, pre);
-        op_conv(c, w, hn, N, H, W, y, 1, 0, rowadd, rowadd_ld, res, 0, -1, 0, fuse);
-        c.arena->release(mk);
-        return;
-    }
+    if (off || !n.gb || n.C != q.Cin || !igemm2_gn_fusable(q, G)) return false;
     const size_t mk = c.arena->mark();
     ConvFuse f = fuse ? *fuse : ConvFuse();
     f.gn_in = &n; f.gn_in_groups = G; f.gn_in_eps = eps; f.gn_in_silu = silu;
-    float* scratch = c.arena->alloc_f(gn_scratch_floats(N, HW, n.C, G) + (long)N * G * 2);
+    const long stat_floats = gn_scratch_floats(N, HW, n.C, G);
+    float* scratch = c.arena->alloc_f(stat_floats + (long)N * G * 2);   // the statistics pass's summaries | the merged ones
+    const bool go = !c.dry && !c.err;
     if (pre && pre->st.part) {
         f.gn_in_stats = pre->st;
-        // many summaries per image (the VAE's 512 x 512 maps): merged once by a small kernel, not by every block's prologue
-        if (f.gn_in_stats.S > 64 && !c.dry && !c.err) {
-            prof_open(c.stream, "gn_finalize_kernel", 0.0, 8.0 * N * f.gn_in_stats.S * G);
-            c.err = launch_gn_finalize(&f.gn_in_stats, scratch, N, HW, n.C, G, c.stream);
-            prof_close(c.stream);
-        }
-    } else if (!c.dry && !c.err) {
+    } else if (go) {
         static thread_local char gbuf[64];
         static const bool by_shape = getenv("SD_PROF_SHAPES") != nullptr;
         const char* name = "groupnorm(stats)";
@@ -554,23 +575,33 @@ void op_gn_conv(Ctx& c, const NormW& n, const ConvW& w, View x, int N, int H, in
         c.err = launch_gn_stats(x.p, x.ld, N, HW, n.C, G, scratch, &f.gn_in_stats, c.stream);
         prof_close(c.stream);
     }
+    // many summaries per image (the VAE's 512 x 512 maps): merged once by a small kernel, not by every block's prologue
+    if (f.gn_in_stats.S > 64 && go && !c.err) {
+        prof_open(c.stream, "gn_finalize_kernel", 0.0, 8.0 * N * f.gn_in_stats.S * G);
+        c.err = launch_gn_finalize(&f.gn_in_stats, scratch + stat_floats, N, HW, n.C, G, c.stream);
+        prof_close(c.stream);
+    }
+    if (prepared) {
+        conv_prepare(c, w, x, N, H, W, y, 1, 0, rowadd, rowadd_ld, res, 0, -1, 0, &f, prepared);
+        return true;
+    }
     op_conv(c, w, x, N, H, W, y, 1, 0, rowadd, rowadd_ld, res, 0, -1, 0, &f);
     c.arena->release(mk);
+    return true;
 }
 
 bool op_ffn_fused(Ctx& c, const ConvW& ff1, const ConvW& ff2, View x, const RowStat& x_stat, float ln_eps, long M, View y) {
     FfnParams p;
     p.x = x.p; p.ldx = x.ld; p.y = y.p; p.ldy = y.ld;
     p.w1 = ff1.w; p.b1 = ff1.bias; p.wsum1 = ff1.wsum;
-    p.w1_rows = (int)(((long)ff1.cout + kWeightRowPad - 1) / kWeightRowPad * kWeightRowPad);
+    p.w1_rows = (int)weight_rows(ff1.cout);
     p.w2 = ff2.w; p.b2 = ff2.bias;
-    p.w2_rows = (int)(((long)ff2.cout + kWeightRowPad - 1) / kWeightRowPad * kWeightRowPad);
+    p.w2_rows = (int)weight_rows(ff2.cout);
     p.ln_stat = x_stat.p; p.ln_parts = x_stat.parts; p.ln_part_w = x_stat.width; p.ln_eps = ln_eps;
     p.M = (int)M; p.C = (int)ff1.K; p.hidden = (int)ff2.K;
     if (c.dry) p.ln_stat = reinterpret_cast<const float*>(8);          // planning pass: only "is set" matters
     if (ff1.ks != 1 || ff2.ks != 1 || ff2.cout != ff1.K || ff1.cout != 2 * ff2.K || x.C != p.C || !ff1.wsum) return false;
-    if (c.dry ? !(ffn_fused_width(p.C, p.hidden) && M % 128 == 0 && M / 128 >= 64) : !ffn_fused_supported(p))
-        return false;
+    if (!ffn_fused_supported(p)) return false;   // the one predicate of both passes: everything it reads is known when planning
     if (c.dry || c.err) return true;
     prof_open(c.stream, "ffn_fused_kernel", 2.0 * M * ((double)ff1.cout * ff1.K + (double)ff2.cout * ff2.K),
               2.0 * ((double)M * p.C * 2 + (double)ff1.cout * ff1.K + (double)ff2.cout * ff2.K));
