@@ -331,7 +331,8 @@ int sd_unet_set_deep_cache(sd_unet* u, int depth);
 /* Mode of the following forwards, until changed.  An unknown mode: SD_ERR_INVALID; store / reuse while the depth is 0:
  * SD_ERR_STATE. */
 int sd_unet_deep_cache_mode(sd_unet* u, int mode);
-/* Bytes of device memory held (packed weights, workspace). */
+/* Bytes of device memory held (packed weights, workspace).  The workspace is the arena, the DeepCache and token-merging
+ * buffers, the duplicated-latents buffer of sd_unet_forward_cfg / _pag and the staging buffer of graph replay. */
 int sd_unet_memory(const sd_unet* u, int64_t* weight_bytes, int64_t* workspace_bytes);
 
 /* -- IP-Adapter: the `encoder_hid_proj` ImageProjection and every attn2's to_k_ip / to_v_ip that diffusers'
@@ -387,6 +388,8 @@ int sd_ip_adapter_set_feature_tokens(sd_ip_adapter* a, int T_feat);
 /* The image projection alone, on the adapter's own workspace: image_embeds as the UNet forward takes them for `rows`
  * (= B * n_img) images -> tokens [rows, num_tokens, cross_attention_dim] f16.  Both kinds; for tests and tools. */
 int sd_ip_adapter_project(sd_ip_adapter* a, const void* image_embeds, int rows, void* tokens, void* stream);
+/* Bytes of device memory held (packed weights, sd_ip_adapter_project's workspace). */
+int sd_ip_adapter_memory(const sd_ip_adapter* a, int64_t* weight_bytes, int64_t* workspace_bytes);
 
 /* -- ControlNet (diffusers 0.27.2 ControlNetModel), bound to a UNet.  cn_cfg describes its encoder (the up-path fields
  *    are ignored); weight names are diffusers' (stablediffusion_amd/controlnet.py converts original files):
@@ -470,6 +473,25 @@ int sd_vae_tap(sd_vae* v, int enable);
 int sd_vae_tap_count(const sd_vae* v);
 int sd_vae_tap_info(const sd_vae* v, int index, sd_tap_info* info);
 int sd_vae_tap_read(sd_vae* v, int index, void* dst, int64_t bytes);
+
+/* -- Workspace poisoning: a TEST FACILITY, like the taps; no product path calls it.  A handle's scratch memory carries no
+ *    state from call to call, so a call's result may not depend on what an earlier call left there, non-finite values
+ *    included.  These entries overwrite that memory so that a test can see it: the handle's workspace arena over its whole
+ *    capacity and, for the UNet, the buffer of forward_cfg's / forward_pag's duplicated latents and the staging buffer of
+ *    graph replay.  The tagged caches (text / image / ControlNet K/V, the conditioning embedding, the DeepCache feature,
+ *    the token-merging plans) hold state and are left alone.
+ *      pattern SD_POISON_NAN: every byte 0xFF (NaN as f16, f32 and f64, -1 as an integer);
+ *      pattern SD_POISON_INF: every 16-bit word 0x7C00 (f16 +Inf).
+ *    *bytes_filled = the sum of the filled buffers' capacities, which is sd_*_memory's workspace_bytes less (UNet) the
+ *    DeepCache and token-merging buffers; 0 with SD_OK for a handle that has allocated nothing.  The device is
+ *    synchronised before the fill and after it.  SD_ERR_INVALID, nothing launched: a null argument, an unknown pattern. */
+#define SD_POISON_NAN 0
+#define SD_POISON_INF 1
+int sd_unet_poison_workspace(sd_unet* u, int pattern, int64_t* bytes_filled);
+int sd_vae_poison_workspace(sd_vae* v, int pattern, int64_t* bytes_filled);
+int sd_clip_poison_workspace(sd_clip* c, int pattern, int64_t* bytes_filled);
+int sd_clip_vision_poison_workspace(sd_clip_vision* c, int pattern, int64_t* bytes_filled);
+int sd_ip_adapter_poison_workspace(sd_ip_adapter* a, int pattern, int64_t* bytes_filled);
 
 /* -- CLIP text encoder: replaces SDModelWrapper.text_encoder / .text_encoder_2 as encode_prompt calls
  *    them (sd_unified_pipeline.py:592-608).  Weight names are the

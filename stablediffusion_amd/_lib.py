@@ -207,6 +207,12 @@ SIGNATURES = {
     "sd_vae_tap_count": (_I, [_P]),
     "sd_vae_tap_info": (_I, [_P, _I, C.POINTER(SdTapInfo)]),
     "sd_vae_tap_read": (_I, [_P, _I, _P, _I64]),
+    "sd_unet_poison_workspace": (_I, [_P, _I, C.POINTER(_I64)]),
+    "sd_vae_poison_workspace": (_I, [_P, _I, C.POINTER(_I64)]),
+    "sd_clip_poison_workspace": (_I, [_P, _I, C.POINTER(_I64)]),
+    "sd_clip_vision_poison_workspace": (_I, [_P, _I, C.POINTER(_I64)]),
+    "sd_ip_adapter_poison_workspace": (_I, [_P, _I, C.POINTER(_I64)]),
+    "sd_ip_adapter_memory": (_I, [_P, C.POINTER(_I64), C.POINTER(_I64)]),
     "sd_clip_create": (_I, [C.POINTER(SdClipConfig), C.POINTER(_P)]),
     "sd_clip_destroy": (_I, [_P]),
     "sd_clip_num_weights": (_I, [_P]),

@@ -100,6 +100,37 @@ void with_images(UNetCall* c, const void* image_embeds, int n_img) {
     c->n_img = image_embeds ? n_img : 0;
 }
 
+// sd_*_poison_workspace: fill the `n` scratch buffers of a handle (an empty one is skipped) and report their capacities.
+// Synchronised on both sides: nothing enqueued earlier may still write them, and the caller's next launch finds them filled.
+struct PoisonBuf { const void* p; size_t bytes; };
+int poison_buffers(const PoisonBuf* bufs, int n, int pattern, int64_t* bytes_filled) {
+    if (!bytes_filled) { set_error("null argument"); return SD_ERR_INVALID; }
+    if (pattern != SD_POISON_NAN && pattern != SD_POISON_INF) {
+        set_error("sd_*_poison_workspace: unknown pattern " + std::to_string(pattern));
+        return SD_ERR_INVALID;
+    }
+    *bytes_filled = 0;
+    SD_HIP_CHECK(hipDeviceSynchronize());
+    for (int i = 0; i < n; ++i) {
+        char* p = static_cast<char*>(const_cast<void*>(bufs[i].p));
+        const size_t bytes = bufs[i].bytes;
+        if (!p || !bytes) continue;
+        if (pattern == SD_POISON_NAN) {
+            SD_HIP_CHECK(hipMemsetAsync(p, 0xFF, bytes, 0));
+        } else {
+            SD_HIP_CHECK(hipMemsetD16Async(p, 0x7C00, bytes / 2, 0));
+            if (bytes & 1) SD_HIP_CHECK(hipMemsetAsync(p + bytes - 1, 0x7C, 1, 0));
+        }
+        *bytes_filled += (int64_t)bytes;
+    }
+    SD_HIP_CHECK(hipDeviceSynchronize());
+    return SD_OK;
+}
+int poison_arena(const sd::Arena& a, int pattern, int64_t* bytes_filled) {
+    const PoisonBuf b{a.base(), a.capacity()};
+    return poison_buffers(&b, 1, pattern, bytes_filled);
+}
+
 // the list / info / read-back trio of the debug taps, shared by the UNet's and the VAE's entries
 int tap_switch(sd::TapSink& t, int enable) {
     t.clear();
@@ -325,6 +356,13 @@ int sd_unet_tap_read(sd_unet* u, int index, void* dst, int64_t bytes) {
     if (!u) { set_error("null handle"); return SD_ERR_INVALID; }
     return tap_read(u->impl.taps, index, dst, bytes);
 }
+int sd_unet_poison_workspace(sd_unet* u, int pattern, int64_t* bytes_filled) {
+    if (!u) { set_error("null handle"); return SD_ERR_INVALID; }
+    const UNet& n = u->impl;
+    const PoisonBuf bufs[3] = {{n.arena.base(), n.arena.capacity()}, {n.cfg_slab.data(), n.cfg_slab.capacity()},
+                               {n.io_slab.data(), n.io_slab.capacity()}};
+    return poison_buffers(bufs, 3, pattern, bytes_filled);
+}
 int sd_unet_cfg_share(const sd_unet_config* cfg) { return cfg && sd::unet_cfg_share_eligible(*cfg) ? 1 : 0; }
 int sd_unet_set_ip_adapter_scale(sd_unet* u, float scale) {
     if (!u) { set_error("null handle"); return SD_ERR_INVALID; }
@@ -458,6 +496,16 @@ int sd_ip_adapter_project(sd_ip_adapter* a, const void* image_embeds, int rows, 
     return a->impl.project(static_cast<const half_t*>(image_embeds), rows, static_cast<half_t*>(tokens),
                            static_cast<hipStream_t>(stream));
 }
+int sd_ip_adapter_memory(const sd_ip_adapter* a, int64_t* weight_bytes, int64_t* workspace_bytes) {
+    if (!a) { set_error("null handle"); return SD_ERR_INVALID; }
+    if (weight_bytes) *weight_bytes = a->impl.ws.packed_bytes();
+    if (workspace_bytes) *workspace_bytes = (int64_t)a->impl.arena.capacity();
+    return SD_OK;
+}
+int sd_ip_adapter_poison_workspace(sd_ip_adapter* a, int pattern, int64_t* bytes_filled) {
+    if (!a) { set_error("null handle"); return SD_ERR_INVALID; }
+    return poison_arena(a->impl.arena, pattern, bytes_filled);
+}
 int sd_ip_adapter_destroy(sd_ip_adapter* a) { delete a; return SD_OK; }
 int sd_ip_adapter_num_weights(const sd_ip_adapter* a) { return a ? (int)a->impl.ws.order.size() : 0; }
 int sd_ip_adapter_weight_info(const sd_ip_adapter* a, int index, const char** key, int64_t* shape4, int* ndim) {
@@ -513,7 +561,8 @@ int sd_controlnet_finalize(sd_controlnet* cn) {
 int sd_unet_memory(const sd_unet* u, int64_t* weight_bytes, int64_t* workspace_bytes) {
     if (!u) { set_error("null handle"); return SD_ERR_INVALID; }
     if (weight_bytes) *weight_bytes = u->impl.ws.packed_bytes();
-    if (workspace_bytes) *workspace_bytes = (int64_t)(u->impl.arena.capacity() + u->impl.dc_buf.capacity() + u->impl.tome_buf.capacity());
+    if (workspace_bytes) *workspace_bytes = (int64_t)(u->impl.arena.capacity() + u->impl.dc_buf.capacity() + u->impl.tome_buf.capacity() +
+                                                      u->impl.cfg_slab.capacity() + u->impl.io_slab.capacity());
     return SD_OK;
 }
 
@@ -572,6 +621,10 @@ int sd_vae_tap_read(sd_vae* v, int index, void* dst, int64_t bytes) {
     if (!v) { set_error("null handle"); return SD_ERR_INVALID; }
     return tap_read(v->impl.taps, index, dst, bytes);
 }
+int sd_vae_poison_workspace(sd_vae* v, int pattern, int64_t* bytes_filled) {
+    if (!v) { set_error("null handle"); return SD_ERR_INVALID; }
+    return poison_arena(v->impl.arena, pattern, bytes_filled);
+}
 int sd_vae_memory(const sd_vae* v, int64_t* weight_bytes, int64_t* workspace_bytes) {
     if (!v) { set_error("null handle"); return SD_ERR_INVALID; }
     if (weight_bytes) *weight_bytes = v->impl.ws.packed_bytes();
@@ -618,6 +671,10 @@ int sd_clip_final_layer_norm(sd_clip* c, const void* x, void* y, int64_t rows, v
     if (rows == 0) return SD_OK;
     return c->impl.final_layer_norm(static_cast<const half_t*>(x), static_cast<half_t*>(y), (long)rows,
                                     static_cast<hipStream_t>(stream));
+}
+int sd_clip_poison_workspace(sd_clip* c, int pattern, int64_t* bytes_filled) {
+    if (!c) { set_error("null handle"); return SD_ERR_INVALID; }
+    return poison_arena(c->impl.arena, pattern, bytes_filled);
 }
 int sd_clip_memory(const sd_clip* c, int64_t* weight_bytes, int64_t* workspace_bytes) {
     if (!c) { set_error("null handle"); return SD_ERR_INVALID; }
@@ -681,6 +738,10 @@ int sd_clip_vision_forward(sd_clip_vision* c, const void* pixel_values, void* hi
     return c->impl.forward(static_cast<const half_t*>(pixel_values), static_cast<half_t*>(hidden_states),
                            static_cast<half_t*>(last_hidden), static_cast<half_t*>(pooled), static_cast<half_t*>(image_embeds),
                            B, static_cast<hipStream_t>(stream));
+}
+int sd_clip_vision_poison_workspace(sd_clip_vision* c, int pattern, int64_t* bytes_filled) {
+    if (!c) { set_error("null handle"); return SD_ERR_INVALID; }
+    return poison_arena(c->impl.arena, pattern, bytes_filled);
 }
 int sd_clip_vision_memory(const sd_clip_vision* c, int64_t* weight_bytes, int64_t* workspace_bytes) {
     if (!c) { set_error("null handle"); return SD_ERR_INVALID; }

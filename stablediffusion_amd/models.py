@@ -60,6 +60,16 @@ def _read_taps(lib, handle, model: str) -> Dict[str, dict]:
     return taps
 
 
+def _poison(obj, model: str, pattern: int) -> int:
+    """sd_<model>_poison_workspace on `obj`'s handle (a test facility, sd_engine.h): the scratch memory of the handle is
+    filled with NaN (pattern 0: bytes 0xFF) or fp16 +Inf (pattern 1: words 0x7C00).  Returns the bytes filled."""
+    n = C.c_int64()
+    name = f"sd_{model}_poison_workspace"
+    with torch.cuda.device(obj.device):
+        _lib.check(getattr(obj._lib, name)(obj._h, int(pattern), C.byref(n)), name)
+    return n.value
+
+
 def _as_f16(x: torch.Tensor, device) -> torch.Tensor:
     return x.to(device=device, dtype=torch.float16).contiguous()
 
@@ -192,6 +202,10 @@ class HipUNet2DConditionModel:
         w, s = C.c_int64(), C.c_int64()
         _lib.check(self._lib.sd_unet_memory(self._h, C.byref(w), C.byref(s)), "sd_unet_memory")
         return w.value, s.value
+
+    def _poison_workspace(self, pattern: int = 0) -> int:
+        """Test facility: overwrite the engine's scratch memory (see `_poison`); returns the bytes filled."""
+        return _poison(self, "unet", pattern)
 
     def use_graph(self, enable: bool = True):
         """Replay the forward from a captured hipGraph (one host call per step instead of ~480)."""
@@ -713,6 +727,15 @@ class HipIPAdapter:
                                                        C.c_void_p(_stream_ptr())), "sd_ip_adapter_project")
         return out
 
+    def memory(self):
+        w, s = C.c_int64(), C.c_int64()
+        _lib.check(self._lib.sd_ip_adapter_memory(self._h, C.byref(w), C.byref(s)), "sd_ip_adapter_memory")
+        return w.value, s.value
+
+    def _poison_workspace(self, pattern: int = 0) -> int:
+        """Test facility: overwrite the scratch memory of `project` (see `_poison`); returns the bytes filled."""
+        return _poison(self, "ip_adapter", pattern)
+
     def load_state_dict(self, state_dict: Dict[str, torch.Tensor], strict: bool = True):
         _lib.require_gpu()
         with torch.cuda.device(self.device):
@@ -834,6 +857,10 @@ class HipAutoencoderKL:
         w, s = C.c_int64(), C.c_int64()
         _lib.check(self._lib.sd_vae_memory(self._h, C.byref(w), C.byref(s)), "sd_vae_memory")
         return w.value, s.value
+
+    def _poison_workspace(self, pattern: int = 0) -> int:
+        """Test facility: overwrite the engine's scratch memory (see `_poison`); returns the bytes filled."""
+        return _poison(self, "vae", pattern)
 
     def to(self, device=None, dtype=None):
         # the reference flips the VAE to fp32 around encode when force_upcast is set
@@ -1013,6 +1040,10 @@ class HipCLIPTextModel:
         _lib.check(self._lib.sd_clip_memory(self._h, C.byref(w), C.byref(s)), "sd_clip_memory")
         return w.value, s.value
 
+    def _poison_workspace(self, pattern: int = 0) -> int:
+        """Test facility: overwrite the engine's scratch memory (see `_poison`); returns the bytes filled."""
+        return _poison(self, "clip", pattern)
+
     def to(self, device=None, dtype=None):
         if device is not None and not isinstance(device, torch.dtype) and torch.device(device).type != "cuda":
             raise _lib.EngineError("HipCLIPTextModel lives on the HIP device only")
@@ -1132,6 +1163,10 @@ class HipCLIPVisionModelWithProjection:
         w, s = C.c_int64(), C.c_int64()
         _lib.check(self._lib.sd_clip_vision_memory(self._h, C.byref(w), C.byref(s)), "sd_clip_vision_memory")
         return w.value, s.value
+
+    def _poison_workspace(self, pattern: int = 0) -> int:
+        """Test facility: overwrite the engine's scratch memory (see `_poison`); returns the bytes filled."""
+        return _poison(self, "clip_vision", pattern)
 
     def to(self, device=None, dtype=None):
         if device is not None and not isinstance(device, torch.dtype) and torch.device(device).type != "cuda":

@@ -66,6 +66,25 @@ def test_unsupported_config_is_rejected(engine_lib):
     assert b"unsupported" in engine_lib.sd_last_error()
 
 
+def test_poison_workspace_rejects_bad_arguments(engine_lib):
+    """sd_*_poison_workspace (the test hook): a null handle, a null count and an unknown pattern are SD_ERR_INVALID before
+    anything touches the device, for each of the five handle types."""
+    n = C.c_int64(-7)
+    for name in ("unet", "vae", "clip", "clip_vision", "ip_adapter"):
+        fn = getattr(engine_lib, f"sd_{name}_poison_workspace")
+        assert fn(None, 0, C.byref(n)) == 1, name
+        assert b"null" in engine_lib.sd_last_error()
+    net = HipUNet2DConditionModel(config.tiny_unet())
+    vae = HipAutoencoderKL(config.tiny_vae())
+    for fn, h in ((engine_lib.sd_unet_poison_workspace, net._h), (engine_lib.sd_vae_poison_workspace, vae._h)):
+        assert fn(h, 0, None) == 1
+        for pattern in (-1, 2):
+            assert fn(h, pattern, C.byref(n)) == 1
+            assert b"pattern" in engine_lib.sd_last_error()
+    assert n.value == -7
+    assert engine_lib.sd_ip_adapter_memory(None, None, None) == 1
+
+
 def test_clip_manifest_matches_transformers_state_dict(engine_lib):
     """The weight names / shapes sd_clip_weight_info reports are exactly the state-dict entries of
     transformers' CLIPTextModel(WithProjection) of the same config (host objects only, no GPU)."""
