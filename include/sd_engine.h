@@ -331,8 +331,26 @@ int sd_unet_set_deep_cache(sd_unet* u, int depth);
 /* Mode of the following forwards, until changed.  An unknown mode: SD_ERR_INVALID; store / reuse while the depth is 0:
  * SD_ERR_STATE. */
 int sd_unet_deep_cache_mode(sd_unet* u, int mode);
-/* Bytes of device memory held (packed weights, workspace).  The workspace is the arena, the DeepCache and token-merging
- * buffers, the duplicated-latents buffer of sd_unet_forward_cfg / _pag and the staging buffer of graph replay. */
+/* Regional prompts ("attention couple"; this project's own semantics, not a diffusers 0.27.2 feature): R prompts of
+ * L tokens each ride in one encoder_hidden_states of ehs_len = R L tokens, and at every attn2
+ *   out[n, t] = sum_r W_l[n % Bw, t, r] softmax(s q[n, t] K[n, rL:(r+1)L]^T) V[n, rL:(r+1)L]
+ * in one launch (sd_op_region_cross_attention) in place of the plain cross-attention; attn1 and everything else are
+ * unchanged.  weights [Bw, R, H, W] fp32 on the device are the sample-resolution ones (sum 1 over R per pixel is the
+ * caller's business); a transformer on an (H >> l, W >> l) map reads their 2x2 mean l times over (sd_op_region_pyramid,
+ * one launch on `stream`, into a buffer the handle keeps with a copy of `weights`; both are counted in sd_unet_memory's
+ * workspace_bytes, and sd_unet_poison_workspace overwrites the level weights, which the next forward then rebuilds).
+ * Forwards issued on `stream` afterwards see them.  1 <= R <= 8, H and W divisible by 2^(blocks-1) (SD_ERR_INVALID),
+ * every cross-attention head dim in {32, 40, 64, 80, 160} (SD_ERR_UNSUPPORTED).  weights == NULL or R == 0 clears the
+ * regions: the buffers are released and the forward is again exactly the plain one, with the same launches.
+ * With regions set, sd_unet_forward, _ex (no image embeds) and _cfg (shared prefix included: the text enters after it)
+ * take them; the text-K/V cache composes.  SD_ERR_INVALID: ehs_len % R != 0, B % Bw != 0 (B: the forward's batch, twice
+ * the latents' for _cfg), H or W other than the ones set.  SD_ERR_UNSUPPORTED, nothing launched: a ControlNet attached,
+ * an IP-Adapter attached at a non-zero scale, sd_unet_forward_pag, _concat, _tc with a timestep_cond, graph replay on,
+ * token merging on, a DeepCache store / reuse mode, more than 160 tokens per region. */
+int sd_unet_set_regions(sd_unet* u, const float* weights, int Bw, int R, int H, int W, void* stream);
+/* Bytes of device memory held (packed weights, workspace).  The workspace is the arena, the DeepCache, token-merging
+ * and regional-prompt buffers, the duplicated-latents buffer of sd_unet_forward_cfg / _pag and the staging buffer of
+ * graph replay. */
 int sd_unet_memory(const sd_unet* u, int64_t* weight_bytes, int64_t* workspace_bytes);
 
 /* -- IP-Adapter: the `encoder_hid_proj` ImageProjection and every attn2's to_k_ip / to_v_ip that diffusers'
@@ -478,12 +496,13 @@ int sd_vae_tap_read(sd_vae* v, int index, void* dst, int64_t bytes);
  *    state from call to call, so a call's result may not depend on what an earlier call left there, non-finite values
  *    included.  These entries overwrite that memory so that a test can see it: the handle's workspace arena over its whole
  *    capacity and, for the UNet, the buffer of forward_cfg's / forward_pag's duplicated latents and the staging buffer of
- *    graph replay.  The tagged caches (text / image / ControlNet K/V, the conditioning embedding, the DeepCache feature,
- *    the token-merging plans) hold state and are left alone.
+ *    graph replay, and the per-level weights of regional prompts (rebuilt by the next forward from the handle's copy of
+ *    the caller's weights).  The tagged caches (text / image / ControlNet K/V, the conditioning embedding, the DeepCache
+ *    feature, the token-merging plans) and that copy hold state and are left alone.
  *      pattern SD_POISON_NAN: every byte 0xFF (NaN as f16, f32 and f64, -1 as an integer);
  *      pattern SD_POISON_INF: every 16-bit word 0x7C00 (f16 +Inf).
  *    *bytes_filled = the sum of the filled buffers' capacities, which is sd_*_memory's workspace_bytes less (UNet) the
- *    DeepCache and token-merging buffers; 0 with SD_OK for a handle that has allocated nothing.  The device is
+ *    DeepCache and token-merging buffers and the copy of the regional weights; 0 with SD_OK for a handle that has allocated nothing.  The device is
  *    synchronised before the fill and after it.  SD_ERR_INVALID, nothing launched: a null argument, an unknown pattern. */
 #define SD_POISON_NAN 0
 #define SD_POISON_INF 1
@@ -1085,6 +1104,26 @@ int sd_op_ip_cross_attention(const void* q, const void* k, const void* v, const 
                              int B, int Tq, int L, int T_ip, int heads, int d, int ldq, int ldk, int ldv, int ldk_ip,
                              int ldv_ip, int ldo, float ip_scale, int prescaled, int iters, float* ms_per_launch,
                              void* stream);
+/* Regional cross-attention (sd_unet_set_regions), one launch:
+ *   out[n, t] = sum_r w[n % Bw, t, r] softmax(s q[n, t] k[n, rL:(r+1)L]^T) v[n, rL:(r+1)L],   s = 1/sqrt(d), or 1 with
+ * prescaled = 1.  q / out [B,Tq,heads*d], k / v [B,R L,heads*d], each with its own row stride (multiples of 8);
+ * w [Bw,Tq,R] fp32, Bw divides B.  Each segment's softmax is exact; a wave skips a segment that is zero for all 16
+ * queries of its tile, and a query whose weight is zero inside a running segment adds an exact zero.  d in
+ * {32, 40, 64, 80, 160}, 1 <= R <= 8, 1 <= L <= 160 (SD_ERR_UNSUPPORTED otherwise, nothing launched); SD_ERR_INVALID for a
+ * null pointer, a stride that is no multiple of 8, Bw < 1 or B % Bw != 0. */
+int sd_op_region_cross_attention(const void* q, const void* k, const void* v, const float* w, void* out, int B, int Tq, int L,
+                                 int R, int heads, int d, int ldq, int ldk, int ldv, int ldo, int Bw, int prescaled,
+                                 void* stream);
+/* Host only (no device needed): how that launch holds the R segments in its 160 KiB of LDS.  out4 = segments per group,
+ * groups, bytes of dynamic LDS, query tiles per block.  One group: every segment is resident and a block of four waves
+ * walks its share of the 64-query tiles against them (out4[3] = 0: as many as its share).  More: one 128-query tile
+ * per block of eight waves (out4[3] = 1), K / V restaged between groups while the output stays in registers.  SD_ERR_UNSUPPORTED for d, R or L
+ * outside the launch's. */
+int sd_region_plan(int R, int L, int d, int* out4);
+/* The per-level weights of sd_unet_set_regions from weights [Bw,R,H,W] fp32, one launch: level l = 0..levels-1 of `out`
+ * is [Bw, (H >> l)(W >> l), R] fp32 -- level 0 the input transposed, level l the 2x2 mean of level l - 1 -- back to
+ * back.  1 <= levels <= 4, H and W divisible by 2^(levels-1), 1 <= R <= 8 (SD_ERR_INVALID otherwise). */
+int sd_op_region_pyramid(const float* weights, float* out, int Bw, int R, int H, int W, int levels, void* stream);
 /* The Resampler's perceiver attention (IP-Adapter Plus), one launch, head dim 64:
  *   out = softmax(s q [k_x ; k_l]^T) [v_x ; v_l],   s = 1/8, or 1 with prescaled = 1
  * q / out [B,n_q,heads*64], k_x / v_x [B,T_feat,heads*64] (the projected image features), k_l / v_l [B,n_q,heads*64]

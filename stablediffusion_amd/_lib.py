@@ -170,6 +170,7 @@ SIGNATURES = {
     "sd_unet_set_pag_layers": (_I, [_P, _P, _I]),
     "sd_unet_forward_pag": (_I, [_P, _P, _P, _P, _I, _P, _P, _F, _I, _I, _P, _I, _I, _I, _P]),
     "sd_unet_forward_concat": (_I, [_P, _P, _I, _F, _P, _I, _I, _I, _P, _P, _I, _P, _P, _P, _I, _I, _I, _P]),
+    "sd_unet_set_regions": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "sd_unet_set_deep_cache": (_I, [_P, _I]),
     "sd_unet_deep_cache_mode": (_I, [_P, _I]),
     "sd_ip_adapter_create": (_I, [_P, _I, _I, C.POINTER(_P)]),
@@ -309,6 +310,9 @@ SIGNATURES = {
     "sd_attention_plan": (_I, [_I, _I, _I, _I, _I, _I, _I, C.POINTER(_I)]),
     "sd_op_ip_cross_attention": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _I, _I,
                                       C.POINTER(_F), _P]),
+    "sd_op_region_cross_attention": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "sd_region_plan": (_I, [_I, _I, _I, C.POINTER(_I)]),
+    "sd_op_region_pyramid": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
     "sd_op_resampler_attention": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I,
                                        C.POINTER(_F), _P]),
     "sd_op_controlnet_residuals": (_I, [C.POINTER(SdCnProblem), _I, _F, _I, _I, C.POINTER(_F), _P]),

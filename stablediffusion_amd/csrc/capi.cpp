@@ -358,10 +358,13 @@ int sd_unet_tap_read(sd_unet* u, int index, void* dst, int64_t bytes) {
 }
 int sd_unet_poison_workspace(sd_unet* u, int pattern, int64_t* bytes_filled) {
     if (!u) { set_error("null handle"); return SD_ERR_INVALID; }
-    const UNet& n = u->impl;
-    const PoisonBuf bufs[3] = {{n.arena.base(), n.arena.capacity()}, {n.cfg_slab.data(), n.cfg_slab.capacity()},
-                               {n.io_slab.data(), n.io_slab.capacity()}};
-    return poison_buffers(bufs, 3, pattern, bytes_filled);
+    UNet& n = u->impl;
+    // (the level weights of regional prompts are scratch too: the next forward rebuilds them from the kept copy)
+    const PoisonBuf bufs[4] = {{n.arena.base(), n.arena.capacity()}, {n.cfg_slab.data(), n.cfg_slab.capacity()},
+                               {n.io_slab.data(), n.io_slab.capacity()}, {n.region_buf.data(), n.region_buf.capacity()}};
+    const int rc = poison_buffers(bufs, 4, pattern, bytes_filled);
+    if (rc == SD_OK && n.region_buf.capacity()) n.region_stale = true;
+    return rc;
 }
 int sd_unet_cfg_share(const sd_unet_config* cfg) { return cfg && sd::unet_cfg_share_eligible(*cfg) ? 1 : 0; }
 int sd_unet_set_ip_adapter_scale(sd_unet* u, float scale) {
@@ -406,6 +409,10 @@ int sd_unet_tome_read(sd_unet* u, int k, int32_t* info5, int32_t* map_host, int6
     for (int b = 0; b < t.B; ++b)
         if (tome_plan_read_map(u->impl.tome_buf.data() + t.plan_off, b, T, map_host + (long)b * T)) return -SD_ERR_HIP;
     return t.B;
+}
+int sd_unet_set_regions(sd_unet* u, const float* weights, int Bw, int R, int H, int W, void* stream) {
+    if (!u) { set_error("null handle"); return SD_ERR_INVALID; }
+    return u->impl.set_regions(weights, Bw, R, H, W, static_cast<hipStream_t>(stream));
 }
 int sd_unet_set_deep_cache(sd_unet* u, int depth) {
     if (!u) { set_error("null handle"); return SD_ERR_INVALID; }
@@ -562,7 +569,8 @@ int sd_unet_memory(const sd_unet* u, int64_t* weight_bytes, int64_t* workspace_b
     if (!u) { set_error("null handle"); return SD_ERR_INVALID; }
     if (weight_bytes) *weight_bytes = u->impl.ws.packed_bytes();
     if (workspace_bytes) *workspace_bytes = (int64_t)(u->impl.arena.capacity() + u->impl.dc_buf.capacity() + u->impl.tome_buf.capacity() +
-                                                      u->impl.cfg_slab.capacity() + u->impl.io_slab.capacity());
+                                                      u->impl.cfg_slab.capacity() + u->impl.io_slab.capacity() +
+                                                      u->impl.region_src.capacity() + u->impl.region_buf.capacity());
     return SD_OK;
 }
 
@@ -1918,6 +1926,27 @@ int sd_op_ip_cross_attention(const void* q, const void* k, const void* v, const 
     if (!rc && hipStreamSynchronize(s) != hipSuccess) rc = SD_ERR_HIP;
     (void)hipFree(tmp);
     return rc;
+}
+
+int sd_op_region_cross_attention(const void* q, const void* k, const void* v, const float* w, void* out, int B, int Tq, int L,
+                                 int R, int heads, int d, int ldq, int ldk, int ldv, int ldo, int Bw, int prescaled,
+                                 void* stream) {
+    return launch_region_attention(static_cast<const half_t*>(q), static_cast<const half_t*>(k), static_cast<const half_t*>(v),
+                                   w, static_cast<half_t*>(out), B, Tq, L, R, heads, d, ldq, ldk, ldv, ldo, Bw, prescaled,
+                                   static_cast<hipStream_t>(stream));
+}
+
+int sd_op_region_pyramid(const float* weights, float* out, int Bw, int R, int H, int W, int levels, void* stream) {
+    return launch_region_pyramid(weights, out, Bw, R, H, W, levels, static_cast<hipStream_t>(stream));
+}
+
+int sd_region_plan(int R, int L, int d, int* out4) {
+    if (!out4) { set_error("sd_region_plan: null argument"); return SD_ERR_INVALID; }
+    RegionPlan pl;
+    if (int rc = region_plan(R, L, d, &pl)) return rc;
+    out4[0] = pl.seg_per_group; out4[1] = pl.groups; out4[2] = pl.lds_bytes;
+    out4[3] = pl.groups > 1 ? 1 : 0;
+    return SD_OK;
 }
 
 int sd_op_resampler_attention(const void* q, const void* k_x, const void* v_x, const void* k_l, const void* v_l, void* out,

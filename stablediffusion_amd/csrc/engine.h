@@ -285,6 +285,11 @@ struct Ctx {
     TapSink* tap = nullptr;             // debug taps of this forward (nullptr: off)
     // token merging of this forward (nullptr: off, and always inside a ControlNet's encoder: tomesd patches the UNet only)
     const TomeRun* tome = nullptr;
+    // Regional prompts of this forward (nullptr: off): the handle's weight pyramid (UNet::region_buf) for a
+    // region_H x region_W sample, region_R regions in an encoder_hidden_states of region_R * (L / region_R) tokens,
+    // weight batch region_Bw.  run_xformer then issues region_xattn_kernel at every attn2 instead of the plain launch.
+    const float* region_w = nullptr;
+    int region_R = 0, region_Bw = 0, region_H = 0, region_W = 0;
 };
 // Record view `v` ([N H W, v.C] fp16, kind kTap*) under `name`; nothing on a dry or failed context.  Callers guard with
 // `if (c.tap)` so that a forward without taps does not even build the name.
@@ -386,6 +391,10 @@ void op_attention(Ctx& c, View q, View k, View v, View out, int B, int Tq, int T
 // out = softmax(q k^T) v + ip_scale softmax(q k_ip^T) v_ip (prescaled queries, ip_attention.hip)
 void op_ip_attention(Ctx& c, View q, View k, View v, View k_ip, View v_ip, View out, int B, int Tq, int L, int T_ip,
                      int heads, int d, float ip_scale);
+// out[n, t] = sum_r w[n % Bw, t, r] softmax(q k_r^T) v_r over the R segments of L keys each (prescaled queries,
+// region_attention.hip)
+void op_region_attention(Ctx& c, View q, View k, View v, const float* w, View out, int B, int Tq, int L, int R, int heads,
+                         int d, int Bw);
 // out = softmax(q [kx ; kl]^T) [vx ; vl], head dim 64, prescaled queries (resampler.hip)
 void op_resampler_attention(Ctx& c, View q, View kx, View vx, View kl, View vl, View out, int B, int n_q, int T_feat,
                             int heads);

@@ -280,6 +280,23 @@ int launch_ip_attention(const half_t* q, const half_t* k, const half_t* v, const
                         long ldki, long ldvi, long ldo, float ip_scale, int prescaled, hipStream_t s);
 bool ip_attention_supported(int d);
 int launch_axpy_f16(half_t* y, long ldy, const half_t* x, long ldx, long rows, int cols, float a, hipStream_t s);
+// Regional prompts (region_attention.hip), one launch:
+//   out[n, t] = sum_r w[n % Bw, t, r] softmax(s q[n, t] k[n, rL:(r+1)L]^T) v[n, rL:(r+1)L],   s as above
+// q / out [B, Tq, heads*d], k / v [B, R L, ..] with their own row strides (% 8); w [Bw, Tq, R] fp32, Bw divides B;
+// d as ip_attention_supported, 1 <= R <= 8, 1 <= L <= 160 (4 otherwise; 1 for null pointers, strides, Bw).
+// region_plan: how the launch holds the R segments in LDS -- `groups` groups of at most `seg_per_group` segments of
+// `seg_bytes` each, `lds_bytes` of dynamic LDS; groups == 1: all resident, a block walks several query tiles; more: one
+// query tile per block, K / V restaged between groups.  Host only; launch_region_attention dispatches on it.
+struct RegionPlan { int seg_per_group = 0, groups = 0, lds_bytes = 0, seg_bytes = 0; };
+int region_plan(int R, int L, int d, RegionPlan* pl);
+int launch_region_attention(const half_t* q, const half_t* k, const half_t* v, const float* w, half_t* out, int B, int Tq,
+                            int L, int R, int heads, int d, long ldq, long ldk, long ldv, long ldo, int Bw, int prescaled,
+                            hipStream_t s);
+// The weights of every UNet level from the sample-resolution ones w [Bw, R, H, W] fp32, one launch: level l of `out` is
+// [Bw, (H >> l)(W >> l), R] (the layout launch_region_attention reads), the 2x2 mean of level l - 1, at float offset
+// region_level_offset(.., l); levels in [1, 4], H and W divisible by 2^(levels-1) (1 otherwise).
+long region_level_offset(int Bw, int R, int H, int W, int level);
+int launch_region_pyramid(const float* w, float* out, int Bw, int R, int H, int W, int levels, hipStream_t s);
 // Perceiver attention of the IP-Adapter Plus Resampler (resampler.hip), one launch, head dim 64:
 //   out = softmax(s q [kx ; kl]^T) [vx ; vl],   s = 1/8 (or 1 with prescaled)
 // q / out [B, n_q, heads*64], kx / vx [B, T_feat, ..], kl / vl [B, n_q, ..], every view with its own row stride (% 8,

@@ -413,6 +413,21 @@ struct UNet : Encoder {
     // the blocks that merge for an H x W sample, in execution order of the full forward, with their plan offsets
     int tome_layout(int B, int H, int W, std::vector<TomeUsed>* sites, size_t* bytes);
 
+    // ---- regional prompts (sd_unet_set_regions): region_R = 0 is off, the forward as without the feature.  On, every
+    // attn2 of forward / forward_cfg runs region_xattn_kernel on the R segments of an encoder_hidden_states of R * L
+    // tokens, weighted per query by the level's weights.  region_src keeps the caller's [Bw, R, H, W] weights; region_buf
+    // is every level's [Bw, T_l, R] (one region_pyramid_kernel launch), scratch that the next forward rebuilds from
+    // region_src when sd_unet_poison_workspace has overwritten it (region_stale).  Not under graphs, not with a
+    // ControlNet, an IP-Adapter at a non-zero scale, token merging, a DeepCache store / reuse mode, timestep_cond,
+    // forward_pag or forward_concat: regions_refuse says so before anything is launched.
+    int region_R = 0, region_Bw = 0, region_H = 0, region_W = 0;
+    DeviceBuf region_src, region_buf;
+    bool region_stale = false;
+    int set_regions(const float* weights, int Bw, int R, int H, int W, hipStream_t stream);
+    // 0 when regions are off or the call may run with them; else the code (1 / 4) with the message set.  B is the batch of
+    // the forward the call builds (2 B of forward_cfg's latents).
+    int regions_refuse(const UNetCall& call, int B, bool pag_or_concat);
+
     // ---- debug taps (sd_unet_tap; engine.h: TapSink): on, the plain forward records the input and output view of
     // every block; the modes whose launches differ from the plain forward's are refused (tap_refuses: 4 when `mode`).
     TapSink taps;

@@ -644,6 +644,19 @@ void op_ip_attention(Ctx& c, View q, View k, View v, View k_ip, View v_ip, View 
     prof_close(c.stream);
 }
 
+void op_region_attention(Ctx& c, View q, View k, View v, const float* w, View out, int B, int Tq, int L, int R, int heads,
+                         int d, int Bw) {
+    if (c.dry || c.err) return;
+    if (prof_enabled()) {
+        static thread_local char name[32];
+        snprintf(name, sizeof(name), "region_xattn_kernel<%d>", d);
+        prof_open(c.stream, name, 4.0 * B * heads * (double)Tq * R * L * d,
+                  2.0 * B * heads * d * (2.0 * Tq + 2.0 * R * L) + 4.0 * B * (double)Tq * R);
+    }
+    c.err = launch_region_attention(q.p, k.p, v.p, w, out.p, B, Tq, L, R, heads, d, q.ld, k.ld, v.ld, out.ld, Bw, 1, c.stream);
+    prof_close(c.stream);
+}
+
 void op_resampler_attention(Ctx& c, View q, View kx, View vx, View kl, View vl, View out, int B, int n_q, int T_feat,
                             int heads) {
     if (c.dry || c.err) return;

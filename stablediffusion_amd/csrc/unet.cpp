@@ -711,8 +711,21 @@ void run_xformer(Ctx& c, const Xformer& t, View x, int N, int H, int W, View out
             }
             Np = Nl; Mp = Ml;
         }
+        // Regional prompts: the R segments of the text K / V, weighted per query by this level's weights, in one launch
+        if (c.region_w) {
+            int lvl = 0;
+            while ((c.region_H >> lvl) > H) ++lvl;
+            if ((c.region_H >> lvl) != H || (c.region_W >> lvl) != W || L % c.region_R != 0) {
+                set_error("run_xformer: no regional weights for a " + std::to_string(H) + " x " + std::to_string(W) + " map");
+                c.err = 2;
+                return;
+            }
+            op_region_attention(c, q, text_kv.slice(b.kv_off, C), text_kv.slice(b.kv_off + C, C),
+                                c.region_w + region_level_offset(c.region_Bw, c.region_R, c.region_H, c.region_W, lvl), att, Nl,
+                                T, L / c.region_R, c.region_R, t.heads, d, c.region_Bw);
+        }
         // IP-Adapter attached: text and image attention in one launch (scale 0: the text attention alone, as without one)
-        if (c.ip_kv.p && c.ip_scale != 0.f)
+        else if (c.ip_kv.p && c.ip_scale != 0.f)
             op_ip_attention(c, q, text_kv.slice(b.kv_off, C), text_kv.slice(b.kv_off + C, C), c.ip_kv.slice(b.ip_kv_off, C),
                             c.ip_kv.slice(b.ip_kv_off + C, C), att, Nl, T, L, c.ip_T, t.heads, d, c.ip_scale);
         else
@@ -1547,6 +1560,7 @@ int UNet::forward(const UNetCall& in, hipStream_t stream) {
     const CfgIn* const cfg_in = call.cfg_in;
     const PagIn* const pag = call.pag;
     if (!finalized) { set_error("unet: forward before finalize"); return 2; }
+    if (int rc = regions_refuse(call, B, pag || call.extra)) return rc;
     if (int rc = tap_refuses(graph_enabled || cfg_in || pag || call.extra || dc_mode != SD_DC_PLAIN)) return rc;
     if (pag && (B % (pag->groups + 1) != 0 || graph_enabled || control || image_embeds || tcond || dc_mode != SD_DC_PLAIN)) {
         set_error("unet: perturbed-attention forward not available for this call");
@@ -1567,7 +1581,8 @@ int UNet::forward(const UNetCall& in, hipStream_t stream) {
     if (!ip && image_embeds) { set_error("unet: image_embeds given but no IP-Adapter is attached"); return 1; }
     if (ip && !text_only) {
         if (call.n_img < 1 || call.n_img * ip->n_tok > 64) { set_error("unet: images per prompt x adapter tokens must be in [1, 64]"); return 4; }
-        if (L < 1 || L > 160) { set_error("unet: with an IP-Adapter the text length must be in [1, 160]"); return 4; }
+        // (with regional prompts set the adapter is at scale 0 and its kernel does not run: regions_refuse has the limit)
+        if (!region_R && (L < 1 || L > 160)) { set_error("unet: with an IP-Adapter the text length must be in [1, 160]"); return 4; }
         if (graph_enabled) { set_error("unet: graph replay with an IP-Adapter attached is not supported"); return 4; }
     } else {
         call.n_img = 0;
@@ -1653,13 +1668,80 @@ int UNet::forward(const UNetCall& in, hipStream_t stream) {
     key.cat_rows = call.extra ? call.lat_rows : 0;
     if (tome_on) { key.tome_ratio = tome.ratio; key.tome_ds = tome_max_ds; key.tome_sx = tome.sx; key.tome_sy = tome.sy; }
     if (taps.on) taps.clear();              // one forward's records at a time
+    if (region_R && region_stale) {
+        // the level weights were overwritten (sd_unet_poison_workspace): rebuild them from the kept copy
+        if (int rc = launch_region_pyramid(reinterpret_cast<const float*>(region_src.data()),
+                                           reinterpret_cast<float*>(region_buf.data()), region_Bw, region_R, region_H, region_W,
+                                           cfg.num_blocks, stream))
+            return rc;
+        region_stale = false;
+    }
     const int rc = plan_and_run(arena, stream, planned[dc], key, "unet", [&](Ctx& c) {
         c.tap = taps.on ? &taps : nullptr;
         c.tome = tome_on ? &tome : nullptr;
+        if (region_R) {
+            c.region_w = reinterpret_cast<const float*>(region_buf.data());
+            c.region_R = region_R; c.region_Bw = region_Bw; c.region_H = region_H; c.region_W = region_W;
+        }
         return run(c, call, dc);
     });
     if (!rc && dc == SD_DC_STORE) dc_tag.set(nullptr, B, H, W, cfg_in != nullptr);
     return rc;
+}
+
+int UNet::set_regions(const float* weights, int Bw, int R, int H, int W, hipStream_t stream) {
+    if (!weights || R == 0) {
+        region_R = region_Bw = region_H = region_W = 0;
+        region_stale = false;
+        dc_tag.clear();                 // (a DeepCache feature stored with regions is stale)
+        if (int rc = region_src.release()) return rc;
+        return region_buf.release();
+    }
+    if (!finalized) { set_error("unet: set_regions before finalize"); return 2; }
+    if (R < 1 || R > 8) { set_error("unet: set_regions: more than 8 regions (or fewer than 1)"); return 4; }
+    const int div = 1 << (cfg.num_blocks - 1);
+    if (Bw < 1 || H < 1 || W < 1 || H % div != 0 || W % div != 0) {
+        set_error("unet: set_regions: Bw >= 1 and H, W divisible by 2^(blocks-1) required");
+        return 1;
+    }
+    for (auto& st : xformer_sites()) {
+        const Xformer& t = *st.second;
+        if (!t.blocks.empty() && !ip_attention_supported(t.C / t.heads)) {
+            set_error("unet: set_regions: head dim " + std::to_string(t.C / t.heads) + " at " + st.first +
+                      " is not one the regional cross-attention runs at (32, 40, 64, 80, 160)");
+            return 4;
+        }
+    }
+    const size_t n = (size_t)Bw * R * H * W;
+    bool grew = false;
+    if (int rc = region_src.reserve(n * sizeof(float), &grew)) return rc;
+    if (int rc = region_buf.reserve((size_t)region_level_offset(Bw, R, H, W, cfg.num_blocks) * sizeof(float), &grew)) return rc;
+    SD_HIP_CHECK(hipMemcpyAsync(region_src.data(), weights, n * sizeof(float), hipMemcpyDeviceToDevice, stream));
+    if (int rc = launch_region_pyramid(reinterpret_cast<const float*>(region_src.data()), reinterpret_cast<float*>(region_buf.data()),
+                                       Bw, R, H, W, cfg.num_blocks, stream))
+        return rc;
+    region_R = R; region_Bw = Bw; region_H = H; region_W = W;
+    region_stale = false;
+    dc_tag.clear();
+    return 0;
+}
+
+int UNet::regions_refuse(const UNetCall& call, int B, bool pag_or_concat) {
+    if (region_R == 0) return 0;
+    const char* why = nullptr;
+    if (pag_or_concat) why = "forward_pag / forward_concat";
+    else if (graph_enabled) why = "graph replay";
+    else if (cn) why = "an attached ControlNet";
+    else if (ip && ip_scale != 0.f) why = "an IP-Adapter at a non-zero scale";
+    else if (call.tcond) why = "timestep_cond (forward_tc)";
+    else if (tome.ratio > 0.0) why = "token merging";
+    else if (dc_mode != SD_DC_PLAIN) why = "a DeepCache store / reuse mode";
+    if (why) { set_error(std::string("unet: regional prompts are set: ") + why + " is not supported with them"); return 4; }
+    if (call.L % region_R != 0) { set_error("unet: regional prompts: ehs_len is no multiple of the regions"); return 1; }
+    if (B % region_Bw != 0) { set_error("unet: regional prompts: the weights' batch does not divide the batch"); return 1; }
+    if (call.H != region_H || call.W != region_W) { set_error("unet: regional prompts: H / W differ from the ones set"); return 1; }
+    if (call.L / region_R > 160) { set_error("unet: regional prompts: more than 160 tokens per region"); return 4; }
+    return 0;
 }
 
 int UNet::tap_refuses(bool mode) {
@@ -1753,6 +1835,7 @@ int UNet::forward_cfg(const UNetCall& lat, float in_scale, bool share, hipStream
     if (B <= 0 || H <= 0 || W <= 0) { set_error("unet: forward_cfg: empty batch"); return 1; }
     // (not shared it is the plain forward on the duplicated latents, which taps; under graph replay forward() refuses,
     // and nothing may be launched before it does)
+    if (int rc = regions_refuse(lat, 2 * B, false)) return rc;
     if (int rc = tap_refuses(cfg_share_active(share) || graph_enabled)) return rc;
     UNetCall call = lat;
     call.B = 2 * B;
@@ -1784,6 +1867,7 @@ int UNet::forward_concat(const UNetCall& call, hipStream_t stream) {
     const int B = call.B, Bl = call.lat_rows;
     if (!finalized) { set_error("unet: forward before finalize"); return 2; }
     if (B <= 0 || call.H <= 0 || call.W <= 0 || Bl <= 0) { set_error("unet: forward_concat: empty batch"); return 1; }
+    if (int rc = regions_refuse(call, B, true)) return rc;
     if (int rc = tap_refuses(true)) return rc;
     // (what the handle is set up for comes first: a ControlNet only attaches to a 4-channel UNet, which the channel check below
     // would turn away with another code)
@@ -1846,6 +1930,7 @@ int UNet::forward_pag(const UNetCall& lat, float in_scale, bool cfg_on, bool sha
     const int B = lat.B, H = lat.H, W = lat.W;
     if (!finalized) { set_error("unet: forward before finalize"); return 2; }
     if (B <= 0 || H <= 0 || W <= 0) { set_error("unet: forward_pag: empty batch"); return 1; }
+    if (int rc = regions_refuse(lat, B, true)) return rc;
     if (int rc = tap_refuses(true)) return rc;
     if (cn) { set_error("unet: forward_pag with a ControlNet attached is not supported"); return 4; }
     if (ip && ip_scale != 0.f) { set_error("unet: forward_pag with an IP-Adapter at a non-zero scale is not supported"); return 4; }

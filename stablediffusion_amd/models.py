@@ -168,6 +168,7 @@ class HipUNet2DConditionModel:
         self._deepcache = None         # (cache_interval, cache_depth) while DeepCache is on (enable_deepcache)
         self._pag = ()                 # site keys of the perturbed transformers (set_pag_layers)
         self._tome = None              # (ratio, max_downsample, sx, sy, use_rand, seed) while token merging is on
+        self._regions = None           # (Bw, R, H, W) while regional prompts are set (set_regions)
 
     # -- weights -------------------------------------------------------------------------------
     def load_state_dict(self, state_dict: Dict[str, torch.Tensor], strict: bool = True):
@@ -306,6 +307,38 @@ class HipUNet2DConditionModel:
         _lib.check(self._lib.sd_unet_set_tome(self._h, 0.0, 1, 2, 2, 0, 0), "sd_unet_set_tome")
         self._tome = None
         return self
+
+    def set_regions(self, weights):
+        """Regional prompts (stablediffusion_amd.regions): weights [Bw, R, H, W] at the sample's latent size, one row per
+        batch row of the following forwards (row n reads n % Bw; under CFG the [2B, ...] of regions.batch_weights), summing
+        to 1 over R.  Until clear_regions() every `attn2` of __call__ / forward_cfg weighs the R segments of an
+        encoder_hidden_states of R L tokens per query, in one engine launch; everything else is the plain forward.
+        Not with a ControlNet, an IP-Adapter at a non-zero scale, forward_pag / forward_concat, timestep_cond, graph
+        replay, token merging or a DeepCache store / reuse step (EngineError, SD_ERR_UNSUPPORTED)."""
+        if not self._finalized:
+            raise _lib.EngineError("weights not loaded")
+        if not isinstance(weights, torch.Tensor) or weights.ndim != 4:
+            raise ValueError("set_regions: expected weights [Bw, R, H, W]")
+        Bw, R, H, W = weights.shape
+        if not 1 <= R <= 8:
+            raise ValueError(f"set_regions: 1 to 8 regions, got {R}")
+        w = weights.to(device=self.device, dtype=torch.float32).contiguous()
+        with torch.cuda.device(self.device):
+            rc = self._lib.sd_unet_set_regions(self._h, C.c_void_p(w.data_ptr()), Bw, R, H, W, C.c_void_p(_stream_ptr()))
+        _lib.check(rc, "sd_unet_set_regions")
+        self._regions = (Bw, R, H, W)
+        return self
+
+    def clear_regions(self):
+        """The forward is again exactly the plain one and the engine releases the regional weights."""
+        _lib.check(self._lib.sd_unet_set_regions(self._h, None, 0, 0, 0, 0, None), "sd_unet_set_regions")
+        self._regions = None
+        return self
+
+    @property
+    def regions(self):
+        """(Bw, R, H, W) while regional prompts are set, else None."""
+        return self._regions
 
     @property
     def tome(self):

@@ -29,7 +29,7 @@ from typing import Any, Dict, List, Optional, Union
 
 import torch
 
-from . import _lib, pag as _pag, pix2pix as _p2p, schedulers as _sched, views as _views
+from . import _lib, pag as _pag, pix2pix as _p2p, regions as _regions, schedulers as _sched, views as _views
 from .image_processor import VaeImageProcessor
 
 
@@ -544,6 +544,14 @@ class StableDiffusionUnifiedPipeline:
         view_batch_size: Optional[int] = None,
         view_blend: str = "uniform",
         circular_padding: bool = False,
+        # regional prompts (stablediffusion_amd.regions; this project's own semantics): `prompt` holds wherever no mask
+        # does, region_prompts[i] where region_masks[i] ([R-1, H, W] / [R-1, 1, H, W] in [0, 1], or PIL images) does;
+        # region_base_weight >= 0 keeps that much of `prompt` everywhere.  With prompt_embeds=, region_prompt_embeds=
+        # holds one [B, L, D] per region.  One UNet forward per step, whatever the number of regions
+        region_prompts=None,
+        region_masks=None,
+        region_base_weight: float = 0.0,
+        region_prompt_embeds=None,
         # SDXL refiner (diffusers StableDiffusionXLImg2ImgPipeline on model.refiner; the reference's handler TODO)
         use_refiner: bool = False,
         refiner_start: Optional[float] = None,
@@ -553,6 +561,9 @@ class StableDiffusionUnifiedPipeline:
         pag_scale: float = 0.0,
         pag_adaptive_scale: float = 0.0,
     ):
+        regional = region_prompts is not None or region_masks is not None or region_prompt_embeds is not None
+        if regional:
+            _regions.check_call(model, getattr(model, "base", None), locals())
         views = None
         if view_window is not None:
             self._check_views(model, locals())
@@ -568,7 +579,7 @@ class StableDiffusionUnifiedPipeline:
         if refiner_start is not None:
             if pag_scale is not None and float(pag_scale) > 0.0:
                 raise NotImplementedError("perturbed-attention guidance (pag_scale > 0) does not address the refiner")
-            call = {k: v for k, v in locals().items() if k not in ("self", "edit", "views")}
+            call = {k: v for k, v in locals().items() if k not in ("self", "edit", "views", "regional")}
             return self._ensemble_of_experts(call)
         pag_on = pag_scale is not None and float(pag_scale) > 0.0
         if pag_on:
@@ -689,6 +700,20 @@ class StableDiffusionUnifiedPipeline:
                 if negative_prompt_embeds is None:
                     raise ValueError("negative_prompt_embeds is required with prompt_embeds when CFG is on")
                 negative_prompt_embeds = negative_prompt_embeds.to(self.device)
+
+        if regional:
+            # one encoder_hidden_states of R L tokens: [prompt | region 1 | ...]; the negative repeats per segment
+            if region_prompt_embeds is None:
+                region_prompt_embeds = []
+                for rp in region_prompts:
+                    rp = batch_size * [rp] if isinstance(rp, str) else list(rp)
+                    if len(rp) != batch_size:
+                        raise ValueError(f"a region prompt list holds {len(rp)} prompts for a batch of {batch_size}")
+                    region_prompt_embeds.append(self.encode_prompt(rp, None, negative_prompt, negative_prompt_2,
+                                                                   num_images_per_prompt, None, clip_skip)[0])
+            prompt_embeds, negative_prompt_embeds = _regions.join_embeds(
+                prompt_embeds, list(region_prompt_embeds),
+                negative_prompt_embeds if self.do_classifier_free_guidance else None)
 
         timesteps, num_inference_steps = retrieve_timesteps(model.scheduler, num_inference_steps, self.device)
 
@@ -820,14 +845,23 @@ class StableDiffusionUnifiedPipeline:
             prompt_embeds = torch.cat([negative_prompt_embeds, prompt_embeds], dim=0)
         prompt_embeds = prompt_embeds.to(self.device)
 
-        latents = self._denoise(model, latents, timesteps, prompt_embeds, cross_attention_kwargs, added_cond_kwargs,
-                                tc_kwargs, guidance_scale, guidance_rescale, seed, control=control,
-                                controlnet_conditioning_scale=controlnet_conditioning_scale,
-                                control_guidance_start=control_guidance_start, control_guidance_end=control_guidance_end,
-                                mask=mask, masked_image_latents=masked_image_latents_2b, image_latents=image_latents,
-                                image_noise=noise,
-                                pag=(float(pag_scale), float(pag_adaptive_scale)) if pag_on else None,
-                                edit=(edit_latents, image_guidance_scale) if edit else None, views=views)
+        if regional:
+            # the [2B, R, h, w] weights (uncond rows one-hot on the base prompt) are engine state for this loop only
+            rw = _regions.region_weights(_regions.masks_tensor(model, region_masks, height, width), latents.shape[-2],
+                                         latents.shape[-1], region_base_weight)
+            unet.set_regions(_regions.batch_weights(rw, latents.shape[0], self.do_classifier_free_guidance))
+        try:
+            latents = self._denoise(model, latents, timesteps, prompt_embeds, cross_attention_kwargs, added_cond_kwargs,
+                                    tc_kwargs, guidance_scale, guidance_rescale, seed, control=control,
+                                    controlnet_conditioning_scale=controlnet_conditioning_scale,
+                                    control_guidance_start=control_guidance_start, control_guidance_end=control_guidance_end,
+                                    mask=mask, masked_image_latents=masked_image_latents_2b, image_latents=image_latents,
+                                    image_noise=noise,
+                                    pag=(float(pag_scale), float(pag_adaptive_scale)) if pag_on else None,
+                                    edit=(edit_latents, image_guidance_scale) if edit else None, views=views)
+        finally:
+            if regional:
+                unet.clear_regions()
 
         # ---- decode (:511-529) ----
         if self.output_type == "pt":
