@@ -1163,8 +1163,7 @@ View view_of(const void* p, long ld, int C) { return View(const_cast<half_t*>(st
 // What the conv entries add to the plain sd_op_conv2d; everything is optional.
 struct ConvOpts {
     long ldx = 0, ldres = 0, ldy = 0;       // operand strides in elements (0: dense)
-    int pad = -1, act = 0;                  // explicit padding (-1: the kernel size's default), the epilogue's activation
-    float acc_scale = 1.f, bias_scale = 1.f;
+    ConvArgs conv;                          // pad, act, acc_scale, bias_scale; conv2d_impl fills in the rest
     // GroupNorm summaries asked of the launch (they pick the split-K reduction kernel), kept for the call only ...
     int gn_groups = 0;
     float* gn_copy = nullptr;               // ... or copied out (sd_op_conv2d_gnstats; gn_copy_floats at most)
@@ -1193,7 +1192,7 @@ int conv2d_impl(const void* x, const void* w_oihw, const void* bias_f32, const v
     if (geglu && ksize != 1) { set_error("sd_op_conv2d: GEGLU takes a linear (ksize 1)"); return SD_ERR_INVALID; }
     if (o.fused) *o.fused = 0;
     const bool behind = o.norm == ConvOpts::kNormBehind, in_front = o.norm == ConvOpts::kNormInFront;
-    const IGemmParams geo = conv_problem(N, H, W, Cin, Cout, ksize, stride, upsample2x, o.pad);    // (the output map)
+    const IGemmParams geo = conv_problem(N, H, W, Cin, Cout, ksize, stride, upsample2x, o.conv.pad);    // (the output map)
     const long HW = (long)H * W, OHW = (long)geo.OH * geo.OW;
     const int ocols = geglu ? Cout / 2 : Cout;
     const int gn_groups = behind ? o.norm_groups : o.gn_groups;
@@ -1235,24 +1234,20 @@ int conv2d_impl(const void* x, const void* w_oihw, const void* bias_f32, const v
 
     const View xv = view_of(x, o.ldx ? o.ldx : Cin, Cin), rv = view_of(res, o.ldres ? o.ldres : ocols, ocols);
     const View yv = view_of(y, o.ldy ? o.ldy : ocols, ocols);
-    const float* rowadd = static_cast<const float*>(rowadd_f32);
     ConvLaunch l;
     bool fused_in_front = false;
     rc = run_op_on_arena(s, 0, nullptr, [&](Ctx& c) {
-        ConvFuse f;
-        f.acc_scale = o.acc_scale; f.bias_scale = o.bias_scale;
+        ConvArgs f = o.conv;
+        f.stride = stride; f.up = upsample2x; f.geglu = geglu;
+        f.rowadd = static_cast<const float*>(rowadd_f32); f.rowadd_ld = Cout;
+        f.res = rv;
         f.gn_out = gb.buf ? &gb : nullptr; f.gn_groups = gn_groups;
-        if (in_front) {
-            fused_in_front = op_gn_conv_fused(c, nw, cw, xv, N, H, W, yv, o.norm_groups, o.eps, o.silu, nullptr, rowadd, Cout,
-                                              res ? &rv : nullptr, &f, &l);
-            if (!fused_in_front) {
-                View hn(c.arena->alloc_h((long)N * HW * Cin), Cin, Cin);
-                op_groupnorm(c, nw, xv, hn, N, HW, o.norm_groups, o.eps, o.silu);
-                conv_prepare(c, cw, hn, N, H, W, yv, 1, 0, rowadd, Cout, res ? &rv : nullptr, 0, -1, 0, &f, &l);
-            }
-        } else {
-            conv_prepare(c, cw, xv, N, H, W, yv, stride, upsample2x, rowadd, Cout, res ? &rv : nullptr, geglu, o.pad, o.act, &f, &l);
+        View cx = xv;                       // what the convolution reads: x, or the output of a GroupNorm kernel in front
+        if (in_front && !(fused_in_front = op_gn_conv_fused(c, nw, cw, xv, N, H, W, yv, o.norm_groups, o.eps, o.silu, nullptr, f, &l))) {
+            cx = View(c.arena->alloc_h((long)N * HW * Cin), Cin, Cin);
+            op_groupnorm(c, nw, xv, cx, N, HW, o.norm_groups, o.eps, o.silu);
         }
+        if (!fused_in_front) conv_prepare(c, cw, cx, N, H, W, yv, f, &l);
         if (!c.dry && !c.err) {
             if (o.ms) {                     // the plan is made once: a timed launch costs the host what it costs a forward
                 long it = 0;
@@ -1310,7 +1305,8 @@ int sd_op_conv2d_ex(const void* x, const void* w_oihw, const void* bias_f32, con
     for (int i = 0; i < 4; ++i) ran[i] = 0;
     ConvOpts o;
     o.ldx = (long)ldx; o.ldres = res ? (long)ldres : 0; o.ldy = (long)ldy;
-    o.pad = pad; o.act = act; o.acc_scale = acc_scale; o.bias_scale = bias_scale; o.gn_groups = gn_groups; o.ran = ran;
+    o.conv.pad = pad; o.conv.act = act; o.conv.acc_scale = acc_scale; o.conv.bias_scale = bias_scale;
+    o.gn_groups = gn_groups; o.ran = ran;
     return conv2d_impl(x, w_oihw, bias_f32, rowadd_f32, res, y, N, H, W, Cin, Cout, ksize, stride, upsample2x, geglu, stream, o);
 }
 
@@ -1399,10 +1395,11 @@ static int ffn_geglu_impl(const void* x, const float* x_stat, int stat_parts, in
             ran_fused = !two_gemms && op_ffn_fused(c, ff1, ff2, xv, st, ln_eps, M, yv);
             if (ran_fused) return;
             View g(c.arena->alloc_h((long)M * hidden), hidden, hidden);
-            ConvFuse f_ln3;
+            ConvArgs f_ln3;
+            f_ln3.geglu = 1;
             f_ln3.ln_in = &st; f_ln3.ln_eps = ln_eps;
-            op_conv(c, ff1, xv, 1, M, 1, g, 1, 0, nullptr, 0, nullptr, 1, -1, 0, &f_ln3);
-            op_conv(c, ff2, g, 1, M, 1, yv, 1, 0, nullptr, 0, &xv, 0, -1, 0, nullptr);
+            op_conv(c, ff1, xv, 1, M, 1, g, f_ln3);
+            op_conv(c, ff2, g, 1, M, 1, yv, conv_res(xv));
         });
     };
     const int n = ms_per_launch ? iters : 0;
@@ -1438,7 +1435,7 @@ int sd_op_ln_ffn_geglu(const void* x, const float* stat, int parts, int part_w, 
 
 // The folded-LayerNorm chain of a transformer block at op level (unet.cpp run_xformer), in two calls that share the
 // row-statistics buffer so a test can force the producer's and the consumer's kernel separately (sd_igemm_force).
-// Producer: y1 = x W0^T + b0 (+ res), an op_conv asked for the row statistics of its output (ConvFuse::stat_out): from
+// Producer: y1 = x W0^T + b0 (+ res), an op_conv asked for the row statistics of its output (ConvArgs::stat_out): from
 // the GEMM epilogue when the launch can emit them (*producer = its kernel), row_stats_kernel over y1 otherwise (-1).
 int sd_op_linear_rowstats(const void* x, const void* w0, const void* b0, const void* res, void* y1, float* stat, int M,
                           int K, int C, int* parts, int* part_w, int* producer, void* stream) {
@@ -1456,9 +1453,9 @@ int sd_op_linear_rowstats(const void* x, const void* w0, const void* b0, const v
     ConvLaunch l;
     const View yv = view_of(y1, C, C), rv = view_of(res, C, C);
     rc = run_op_on_arena(s, 0, nullptr, [&](Ctx& c) {
-        ConvFuse f;
+        ConvArgs f = conv_res(rv);
         f.stat_out = &st;
-        if (conv_prepare(c, cw, view_of(x, K, K), 1, M, 1, yv, 1, 0, nullptr, 0, res ? &rv : nullptr, 0, -1, 0, &f, &l))
+        if (conv_prepare(c, cw, view_of(x, K, K), 1, M, 1, yv, f, &l))
             conv_launch(c, l, yv, &st);
     });
     *producer = l.plan.rowstats ? l.plan.kind : -1;
@@ -1468,7 +1465,7 @@ int sd_op_linear_rowstats(const void* x, const void* w0, const void* b0, const v
 }
 
 // Consumer: y2 = LayerNorm(y1) W1^T + b1 with the norm folded into W1 (WeightStore::fold_ln) and its statistics from the
-// producer's buffer (ConvFuse::ln_in).  geglu = 0: W1 [O, C], the first rows_scaled outputs times row_scale
+// producer's buffer (ConvArgs::ln_in).  geglu = 0: W1 [O, C], the first rows_scaled outputs times row_scale
 // (the q of q|k|v); geglu = 1: W1 [2 O, C] = [hidden | gate] rows, y2 = hidden * gelu(gate) [M, O].
 int sd_op_ln_linear(const void* y1, const float* stat, int parts, int part_w, const void* gamma, const void* beta, float eps,
                     const void* w1, const void* b1, void* y2, int M, int C, int O, int geglu, int rows_scaled, float row_scale,
@@ -1495,9 +1492,10 @@ int sd_op_ln_linear(const void* y1, const float* stat, int parts, int part_w, co
     ConvLaunch l;
     const View yv = view_of(y2, O, O);
     rc = run_op_on_arena(s, 0, nullptr, [&](Ctx& c) {
-        ConvFuse f;
+        ConvArgs f;
+        f.geglu = geglu;
         f.ln_in = &st; f.ln_eps = eps;
-        if (conv_prepare(c, cw, view_of(y1, C, C), 1, M, 1, yv, 1, 0, nullptr, 0, nullptr, geglu, -1, 0, &f, &l))
+        if (conv_prepare(c, cw, view_of(y1, C, C), 1, M, 1, yv, f, &l))
             conv_launch(c, l, yv, nullptr);
     });
     *consumer = l.plan.kind;
@@ -2011,9 +2009,9 @@ int sd_op_controlnet_residuals(const sd_cn_problem* problems, int count, float s
         for (int i = 0; i < count; ++i) {
             const sd_cn_problem& q = problems[i];
             View y(static_cast<half_t*>(q.y), q.ldy, q.C);
-            ConvFuse f;
+            ConvArgs f = conv_res(y);
             f.acc_scale = scale; f.bias_scale = scale;
-            op_conv(c, ws[(size_t)i], view_of(q.x, q.ldx, q.C), 1, q.M, 1, y, 1, 0, nullptr, 0, &y, 0, -1, 0, &f);
+            op_conv(c, ws[(size_t)i], view_of(q.x, q.ldx, q.C), 1, q.M, 1, y, f);
         }
     });
 }
@@ -2098,12 +2096,12 @@ int sd_op_upconv2x_ex(const void* x, const void* w_oihw, const void* bias_f32, c
     ConvLaunch l;
     const View yv = view_of(y, ldy, Cout), rv = view_of(res, ldres, Cout);
     rc = run_op_on_arena(s, 0, nullptr, [&](Ctx& c) {
-        ConvFuse f;
+        ConvArgs f = conv_res(rv);
+        f.up = 1;
+        f.rowadd = static_cast<const float*>(rowadd_f32); f.rowadd_ld = Cout;
         f.acc_scale = acc_scale; f.bias_scale = bias_scale;
         f.gn_out = gn_groups > 0 ? &gb : nullptr; f.gn_groups = gn_groups;
-        if (conv_prepare(c, cw, view_of(x, ldx, Cin), N, H, W, yv, 1, 1, static_cast<const float*>(rowadd_f32), Cout,
-                         res ? &rv : nullptr, 0, -1, 0, &f, &l))
-            conv_launch(c, l, yv, nullptr);
+        if (conv_prepare(c, cw, view_of(x, ldx, Cin), N, H, W, yv, f, &l)) conv_launch(c, l, yv, nullptr);
     });
     if (rc) return rc;
     ran[0] = l.plan.kind == kKindUpconvFold;
@@ -2170,7 +2168,7 @@ int sd_op_ffn_geglu_proj_out(const void* x_in, const void* t3, const void* ln_ga
         }
         gb = GnStatBuf();
         gb.buf = gn_summaries;
-        ConvFuse fo;
+        ConvArgs fo;
         fo.gn_out = gn_summaries ? &gb : nullptr;
         fo.gn_groups = G;
         View x(const_cast<half_t*>(static_cast<const half_t*>(x_in)), C, C);

@@ -91,6 +91,8 @@ void run_clip_layers(Ctx& c, const std::vector<ClipLayer>& layers, const ClipSta
         if (e == hipSuccess && Ip != I) e = hipMemsetAsync(f.p, 0, (size_t)M * Ip * sizeof(half_t), c.stream);
         if (e != hipSuccess) { set_error(std::string("clip: hipMemsetAsync: ") + hipGetErrorString(e)); c.err = 3; }
     }
+    ConvArgs fc1;
+    fc1.act = g.act;
     for (size_t l = 0; l < layers.size(); ++l) {
         const ClipLayer& w = layers[l];
         View x(slab((int)l), H, H), y(slab((int)l + 1), H, H);
@@ -98,10 +100,10 @@ void run_clip_layers(Ctx& c, const std::vector<ClipLayer>& layers, const ClipSta
         op_conv(c, w.qkv, n, B, T, 1, qkv);
         op_attention(c, qkv.slice(0, A), qkv.slice(A, A), qkv.slice(2 * A, A), att, B, T, T, g.heads, g.d, g.causal,
                      g.prescaled);
-        op_conv(c, w.out, att, B, T, 1, t2, 1, 0, nullptr, 0, &x);
+        op_conv(c, w.out, att, B, T, 1, t2, conv_res(x));
         op_layernorm(c, w.ln2, t2, n, M, g.eps);
-        op_conv(c, w.fc1, n, B, T, 1, f, 1, 0, nullptr, 0, nullptr, 0, -1, g.act);
-        op_conv(c, w.fc2, f, B, T, 1, y, 1, 0, nullptr, 0, &t2);
+        op_conv(c, w.fc1, n, B, T, 1, f, fc1);
+        op_conv(c, w.fc2, f, B, T, 1, y, conv_res(t2));
     }
 }
 

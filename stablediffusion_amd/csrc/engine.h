@@ -136,8 +136,15 @@ struct GnStatBuf {
     float* buf = nullptr;
     GnStats st;
 };
-// What an op_conv launch fuses besides bias / row add / residual / GEGLU / activation.
-struct ConvFuse {
+// Everything optional about an op_conv launch: the geometry besides the weights' own, what the epilogue adds and what
+// the launch fuses.  A default-constructed one asks for nothing: a stride-1 convolution (or linear) with its bias.
+struct ConvArgs {
+    // conv_problem's: up = 1 upsamples the input 2x (nearest) first, pad = -1 is the kernel size's default
+    int stride = 1, up = 0, pad = -1;
+    const float* rowadd = nullptr;      // fp32 row per image ([N][rowadd_ld]) added to every pixel (the time embedding)
+    int rowadd_ld = 0;
+    View res;                           // residual added in the epilogue, by value (p == nullptr: none)
+    int geglu = 0, act = 0;             // GEGLU pack (y = hidden * gelu(gate), cout / 2 columns); IGemmParams::act
     const RowStat* ln_in = nullptr;     // LayerNorm of the INPUT, folded into this linear (ConvW::wsum set)
     float ln_eps = 0.f;
     RowStat* stat_out = nullptr;        // row statistics of the OUTPUT for the LayerNorm that follows
@@ -154,6 +161,8 @@ struct ConvFuse {
     // tile hint of this launch (IGemmRequest::hint_variant / hint_splits): -1 = none
     int tile_variant = -1, tile_splits = 0;
 };
+// `base` (by default nothing) plus the residual `res`: a copy, since residuals differ per launch where a struct is shared
+inline ConvArgs conv_res(View res, const ConvArgs& base = ConvArgs()) { ConvArgs a = base; a.res = res; return a; }
 struct NormW {
     float* gamma = nullptr;
     float* beta = nullptr;
@@ -352,15 +361,12 @@ struct ConvLaunch {
     int cin = 0;
 };
 // op_conv = conv_prepare + conv_launch.  conv_prepare poses and plans the launch, refuses what the planned kernel cannot
-// do, fills in what the plan leaves of the requested statistics (fuse->gn_out->st, fuse->stat_out's layout) and takes the
+// do, fills in what the plan leaves of the requested statistics (a.gn_out->st, a.stat_out's layout) and takes the
 // workspace from the arena -- all of it the same in the planning and the live pass; false when there is nothing to launch
-// (planning pass, or an error latched).  conv_launch issues it (stat_out: ConvFuse::stat_out).
-bool conv_prepare(Ctx& c, const ConvW& w, View x, int N, int H, int W, View y, int stride, int up, const float* rowadd,
-                  int rowadd_ld, const View* res, int geglu, int pad, int act, const ConvFuse* fuse, ConvLaunch* out);
+// (planning pass, or an error latched).  conv_launch issues it (stat_out: ConvArgs::stat_out).
+bool conv_prepare(Ctx& c, const ConvW& w, View x, int N, int H, int W, View y, const ConvArgs& a, ConvLaunch* out);
 void conv_launch(Ctx& c, const ConvLaunch& l, View y, RowStat* stat_out);
-void op_conv(Ctx& c, const ConvW& w, View x, int N, int H, int W, View y, int stride = 1, int up = 0,
-             const float* rowadd = nullptr, int rowadd_ld = 0, const View* res = nullptr, int geglu = 0,
-             int pad = -1, int act = 0, const ConvFuse* fuse = nullptr);
+void op_conv(Ctx& c, const ConvW& w, View x, int N, int H, int W, View y, const ConvArgs& a = ConvArgs());
 // floats a RowStat buffer needs for an [M, C] tensor whatever tile the producer picks
 inline long rowstat_floats(long M, int C) { return M * ((C + 63) / 64) * 2; }
 // floats a GnStatBuf needs for N images of HW pixels (tiles of >= 64 pixels) and G groups
@@ -369,19 +375,17 @@ inline long gnstat_floats(int N, long HW, int G) { const long t = (HW + 63) / 64
 void op_groupnorm(Ctx& c, const NormW& n, View x, View y, int N, long HW, int G, float eps, int silu,
                   const GnStatBuf* pre = nullptr);
 // y = conv(act(GroupNorm(x))): GroupNorm kernel + convolution, or, under SD_GN_FUSE=1, op_gn_conv_fused where it takes
-// the problem.  `pre` = the summaries of x its producer left (or nullptr: a statistics pass runs); the other arguments
-// as op_conv's.
+// the problem.  `pre` = the summaries of x its producer left (or nullptr: a statistics pass runs); `a` as op_conv's,
+// but for its stride, up, pad, geglu and act: the convolution behind a GroupNorm is posed with their defaults.
 void op_gn_conv(Ctx& c, const NormW& n, const ConvW& w, View x, int N, int H, int W, View y, int G, float eps, int silu,
-                const GnStatBuf* pre, const float* rowadd = nullptr, int rowadd_ld = 0, const View* res = nullptr,
-                const ConvFuse* fuse = nullptr);
+                const GnStatBuf* pre, const ConvArgs& a = ConvArgs());
 // The same inside the convolution: the launch applies the norm to its halo tiles in LDS and the normalised tensor never
 // exists.  Returns false -- nothing launched or allocated -- when the launch cannot take the norm (no per-64 pack of
 // gamma / beta, n.C != Cin, !igemm2_gn_fusable) or SD_NO_GN_FUSE is set.  `prepared` (the timed operator entry): the
 // statistics launches are issued, the convolution is only prepared into it and its arena allocations stay for the
 // caller's conv_launch.
 bool op_gn_conv_fused(Ctx& c, const NormW& n, const ConvW& w, View x, int N, int H, int W, View y, int G, float eps,
-                      int silu, const GnStatBuf* pre, const float* rowadd = nullptr, int rowadd_ld = 0,
-                      const View* res = nullptr, const ConvFuse* fuse = nullptr, ConvLaunch* prepared = nullptr);
+                      int silu, const GnStatBuf* pre, const ConvArgs& a = ConvArgs(), ConvLaunch* prepared = nullptr);
 void op_layernorm(Ctx& c, const NormW& n, View x, View y, long rows, float eps);
 // y = x + GEGLU(LN(x) ff1) ff2 in one launch (ffn.hip) when the problem fits it (C = 320, LayerNorm folded into ff1, the
 // row statistics of x at hand); returns false -- nothing launched -- when it does not: the caller runs the two GEMMs.

@@ -46,14 +46,11 @@ struct VaeAttn {
 };
 
 // x_stats: GroupNorm summaries of x left by the convolution that produced it (or nullptr);
-// *out_stats: where the block leaves the summaries of `out` for the GroupNorm that consumes it next.
+// out_stats: where the block leaves the summaries of `out` for the GroupNorm that consumes it next (GnOut below).
 // stream_scale s (a power of two, the VAE encoder's range-scaled form): x and out hold s times the block's true input /
 // output.  GroupNorm is invariant to the scale of its input up to eps, so norm1 / norm2 run with eps * s^2, conv1 /
 // conv2 emit s * (conv + bias), the shortcut (whose input carries s already) only scales its bias: the block computes the
 // same function, with every stored activation s times smaller.
-// out_buf / out_groups: where and at which granularity those summaries are written (default: the next ring slot, G
-// groups) -- a skip connection's live until the up path reads them, and an output that becomes the hidden half of a
-// concatenation is summarised over the sub-groups that concatenation's GroupNorm can merge (gn_cat_unit).
 // Shared CFG prefix (UNet::run with a CfgIn): the N images are the two halves of a classifier-free-guidance batch built
 // from the same N / 2 latents, and up to the first cross-attention of the first transformer nothing tells the halves
 // apart.  The layers before it run on the first N / 2 images only; `segs` are the tensors the caller wants widened to N
@@ -63,12 +60,29 @@ struct CfgShare {
     std::vector<RowDupSeg> segs;
 };
 
+// The GroupNorm summaries of `out` that a block asks of its last launch, for the GroupNorm that reads `out` next.
+struct GnOut {
+    // receives the buffer the launch is asked to write them into, or nullptr where it is asked for none (a map whose
+    // GroupNorm takes no summaries: gn_wants_stats).  nullptr here: nobody reads them, the launch is asked for none.
+    GnStatBuf** report;
+    GnStatBuf* buf;     // that buffer, instead of the next ring slot: a skip's summaries live until the up path reads them
+    // instead of G groups: an output that becomes the hidden half of a concatenation is summarised over the sub-groups
+    // that concatenation's GroupNorm can merge (gn_cat_unit)
+    int groups;
+    GnOut(GnStatBuf** report_ = nullptr, GnStatBuf* buf_ = nullptr, int groups_ = 0) : report(report_), buf(buf_), groups(groups_) {}
+};
+// `o` as the request of the launch that writes HW pixels of C channels per image (a->gn_out, a->gn_groups); reports the buffer
+inline void gn_out_resolve(Ctx& c, const GnOut& o, long HW, int C, int G, ConvArgs* a) {
+    a->gn_out = (o.report && gn_wants_stats(HW, C, G)) ? (o.buf ? o.buf : ctx_gnbuf(c)) : nullptr;
+    a->gn_groups = o.groups > 0 ? o.groups : G;
+    if (o.report) *o.report = a->gn_out;
+}
+
 void run_resnet(Ctx& c, const Resnet& r, View x, int N, int H, int W, View out, int G, float eps,
-                const float* tproj, int tproj_ld, const GnStatBuf* x_stats = nullptr, GnStatBuf** out_stats = nullptr,
-                float stream_scale = 1.f, GnStatBuf* out_buf = nullptr, int out_groups = 0);
+                const float* tproj, int tproj_ld, const GnStatBuf* x_stats = nullptr, const GnOut& out_stats = GnOut(),
+                float stream_scale = 1.f);
 void run_xformer(Ctx& c, const Xformer& t, View x, int N, int H, int W, View out, int G, View text_kv, int L,
-                 const GnStatBuf* x_stats = nullptr, GnStatBuf** out_stats = nullptr, GnStatBuf* out_buf = nullptr,
-                 int out_groups = 0, const CfgShare* share = nullptr);
+                 const GnStatBuf* x_stats = nullptr, const GnOut& out_stats = GnOut(), const CfgShare* share = nullptr);
 
 // The end of a transformer, from the residual stream after attn2 (t3, row statistics st_t3 when the LayerNorms are
 // folded) to its output: out = proj_out(t3 + ff(norm3(t3))) + x, with `fo` (the GroupNorm-summary request) on the launch
@@ -81,7 +95,7 @@ void run_xformer(Ctx& c, const Xformer& t, View x, int N, int H, int W, View out
 int pack_xformer_tail(WeightStore& ws, const std::string& proj_out, const std::string& ff2, Xformer* x, TBlock* last);
 View xformer_tail_t3(Arena& a, const Xformer& t, long M);
 bool run_xformer_tail(Ctx& c, const Xformer& t, View t3, const RowStat& st_t3, View n, View nxt, View x, int N, int H, int W,
-                      View out, const ConvFuse& fo);
+                      View out, const ConvArgs& fo);
 
 struct UNet;
 struct UNetCall;

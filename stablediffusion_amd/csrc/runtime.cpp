@@ -445,48 +445,43 @@ static ConvProfRow conv_prof_row(const IGemmPlan& plan, const IGemmParams& p, in
     return r;
 }
 
-bool conv_prepare(Ctx& c, const ConvW& w, View x, int N, int H, int W, View y, int stride, int up, const float* rowadd,
-                  int rowadd_ld, const View* res, int geglu, int pad, int act, const ConvFuse* fuse, ConvLaunch* out) {
-    const RowStat* ln_in = fuse ? fuse->ln_in : nullptr;
-    const float ln_eps = fuse ? fuse->ln_eps : 0.f;
-    RowStat* stat_out = fuse ? fuse->stat_out : nullptr;
-    GnStatBuf* gn_out = fuse ? fuse->gn_out : nullptr;
+bool conv_prepare(Ctx& c, const ConvW& w, View x, int N, int H, int W, View y, const ConvArgs& a, ConvLaunch* out) {
     IGemmParams& p = out->p;
-    p = conv_problem(N, H, W, w.ks == 1 ? (int)w.K : w.cin, w.cout, w.ks, stride, up, pad);
+    p = conv_problem(N, H, W, w.ks == 1 ? (int)w.K : w.cin, w.cout, w.ks, a.stride, a.up, a.pad);
     p.K = (int)w.K;         // (the pack's K)
     p.x = x.p; p.ldx = x.ld;
     p.w = w.w; p.bias = w.bias;
-    p.rowadd = rowadd; p.rowadd_ld = rowadd_ld;
-    p.res = res ? res->p : nullptr; p.ldres = res ? res->ld : 0;
+    p.rowadd = a.rowadd; p.rowadd_ld = a.rowadd_ld;
+    p.res = a.res.p; p.ldres = a.res.p ? a.res.ld : 0;
     p.y = y.p; p.ldy = y.ld;
-    p.geglu = geglu;
-    p.act = act;
-    if (ln_in) {
+    p.geglu = a.geglu;
+    p.act = a.act;
+    if (a.ln_in) {
         if (!w.wsum) { set_error("op_conv: LayerNorm statistics passed to a linear without folded weights"); c.err = 1; return false; }
-        p.ln_stat = ln_in->p; p.ln_parts = ln_in->parts; p.ln_part_w = ln_in->width; p.ln_C = (int)w.K; p.ln_eps = ln_eps; p.ln_wsum = w.wsum;
+        p.ln_stat = a.ln_in->p; p.ln_parts = a.ln_in->parts; p.ln_part_w = a.ln_in->width; p.ln_C = (int)w.K; p.ln_eps = a.ln_eps; p.ln_wsum = w.wsum;
     }
-    if (fuse && fuse->gn_in) {
-        p.gni_part = fuse->gn_in_stats.part; p.gni_S = fuse->gn_in_stats.S; p.gni_rows = fuse->gn_in_stats.rows;
-        p.gni_groups = fuse->gn_in_groups; p.gni_eps = fuse->gn_in_eps; p.gni_silu = fuse->gn_in_silu;
-        p.gni_gb = fuse->gn_in->gb;
+    if (a.gn_in) {
+        p.gni_part = a.gn_in_stats.part; p.gni_S = a.gn_in_stats.S; p.gni_rows = a.gn_in_stats.rows;
+        p.gni_groups = a.gn_in_groups; p.gni_eps = a.gn_in_eps; p.gni_silu = a.gn_in_silu;
+        p.gni_gb = a.gn_in->gb;
         if (c.dry) p.gni_part = reinterpret_cast<const float*>(8);      // planning pass: only "is set" matters (tile choice)
     }
-    if (fuse && (fuse->acc_scale != 1.f || fuse->bias_scale != 1.f)) { p.acc_scale = fuse->acc_scale; p.bias_scale = fuse->bias_scale; }
+    if (a.acc_scale != 1.f || a.bias_scale != 1.f) { p.acc_scale = a.acc_scale; p.bias_scale = a.bias_scale; }
     // one plan per launch, the same in the planning and the live pass: the kernel (folded upsample, 80-column halo tile or
     // a row of the table), what it leaves of the requested statistics, the workspace, the name
-    IGemmRequest rq{stat_out ? stat_out->p : nullptr, gn_out ? gn_out->buf : nullptr, fuse ? fuse->gn_groups : 0};
-    if (fuse) { rq.hint_variant = fuse->tile_variant; rq.hint_splits = fuse->tile_splits; }
-    const IGemmPlan& plan = out->plan = conv_plan(p, up == 1 ? w.w_up : nullptr, rq);
+    IGemmRequest rq{a.stat_out ? a.stat_out->p : nullptr, a.gn_out ? a.gn_out->buf : nullptr, a.gn_groups};
+    rq.hint_variant = a.tile_variant; rq.hint_splits = a.tile_splits;
+    const IGemmPlan& plan = out->plan = conv_plan(p, a.up == 1 ? w.w_up : nullptr, rq);
     const bool v2 = plan.kind != kKindIgemm1;
     if ((p.acc_scale != 1.f || p.bias_scale != 1.f) && !plan.scales_ok) { set_error("op_conv: output scaling needs the LDS-DMA kernels (not GEGLU / weight-stationary)"); c.err = 1; return false; }
-    if (ln_in && !v2) { set_error("op_conv: the LayerNorm fold needs the LDS-DMA kernel"); c.err = 1; return false; }
-    if (act && !v2) { set_error("op_conv: activation epilogue needs the LDS-DMA kernel (Cin % 64, Cout % 8)"); c.err = 1; return false; }
-    if (gn_out) {
-        gn_out->st = GnStats();
-        if (plan.gnstats) { gn_out->st.part = gn_out->buf; gn_out->st.rows = plan.gn_rows; gn_out->st.S = p.OH * p.OW / plan.gn_rows; }
+    if (a.ln_in && !v2) { set_error("op_conv: the LayerNorm fold needs the LDS-DMA kernel"); c.err = 1; return false; }
+    if (a.act && !v2) { set_error("op_conv: activation epilogue needs the LDS-DMA kernel (Cin % 64, Cout % 8)"); c.err = 1; return false; }
+    if (a.gn_out) {
+        a.gn_out->st = GnStats();
+        if (plan.gnstats) { a.gn_out->st.part = a.gn_out->buf; a.gn_out->st.rows = plan.gn_rows; a.gn_out->st.S = p.OH * p.OW / plan.gn_rows; }
     }
-    if (stat_out) { stat_out->parts = plan.rs_parts; stat_out->width = plan.rs_part_w; }
-    out->stats_after = stat_out && !plan.rowstats;      // (otherwise the GEMM's epilogue writes the row statistics itself)
+    if (a.stat_out) { a.stat_out->parts = plan.rs_parts; a.stat_out->width = plan.rs_part_w; }
+    out->stats_after = a.stat_out && !plan.rowstats;      // (otherwise the GEMM's epilogue writes the row statistics itself)
     out->partial = plan.partial_floats > 0 ? c.arena->alloc_f(plan.partial_floats) : nullptr;
     out->cin = w.cin;
     return !(c.dry || c.err);
@@ -507,11 +502,9 @@ void conv_launch(Ctx& c, const ConvLaunch& l, View y, RowStat* stat_out) {
     }
 }
 
-void op_conv(Ctx& c, const ConvW& w, View x, int N, int H, int W, View y, int stride, int up,
-             const float* rowadd, int rowadd_ld, const View* res, int geglu, int pad, int act, const ConvFuse* fuse) {
+void op_conv(Ctx& c, const ConvW& w, View x, int N, int H, int W, View y, const ConvArgs& a) {
     ConvLaunch l;
-    if (conv_prepare(c, w, x, N, H, W, y, stride, up, rowadd, rowadd_ld, res, geglu, pad, act, fuse, &l))
-        conv_launch(c, l, y, fuse ? fuse->stat_out : nullptr);
+    if (conv_prepare(c, w, x, N, H, W, y, a, &l)) conv_launch(c, l, y, a.stat_out);
 }
 
 void op_groupnorm(Ctx& c, const NormW& n, View x, View y, int N, long HW, int G, float eps, int silu,
@@ -534,23 +527,25 @@ void op_groupnorm(Ctx& c, const NormW& n, View x, View y, int N, long HW, int G,
     prof_close(c.stream);
 }
 
+// the convolution behind a GroupNorm: stride 1, no upsample, default padding, no GEGLU, no activation, whatever `a` says
+static ConvArgs gn_conv_args(ConvArgs a) { a.stride = 1; a.up = 0; a.pad = -1; a.geglu = 0; a.act = 0; return a; }
+
 void op_gn_conv(Ctx& c, const NormW& n, const ConvW& w, View x, int N, int H, int W, View y, int G, float eps, int silu,
-                const GnStatBuf* pre, const float* rowadd, int rowadd_ld, const View* res, const ConvFuse* fuse) {
+                const GnStatBuf* pre, const ConvArgs& a) {
     // Off unless SD_GN_FUSE=1: measured slower than GroupNorm kernel + convolution on every UNet shape (the in-LDS
     // transform does not hide behind the MFMAs, profiles/r03_gn_fused_conv.txt); the kernel stays for the operator
     // test (sd_op_groupnorm_conv2d) and as the base of the next attempt.
     static const bool on = getenv("SD_GN_FUSE") != nullptr;
-    if (on && op_gn_conv_fused(c, n, w, x, N, H, W, y, G, eps, silu, pre, rowadd, rowadd_ld, res, fuse)) return;
+    if (on && op_gn_conv_fused(c, n, w, x, N, H, W, y, G, eps, silu, pre, a)) return;
     const size_t mk = c.arena->mark();
     View hn(c.arena->alloc_h((long)N * H * W * n.C), n.C, n.C);
     op_groupnorm(c, n, x, hn, N, (long)H * W, G, eps, silu, pre);
-    op_conv(c, w, hn, N, H, W, y, 1, 0, rowadd, rowadd_ld, res, 0, -1, 0, fuse);
+    op_conv(c, w, hn, N, H, W, y, gn_conv_args(a));
     c.arena->release(mk);
 }
 
 bool op_gn_conv_fused(Ctx& c, const NormW& n, const ConvW& w, View x, int N, int H, int W, View y, int G, float eps,
-                      int silu, const GnStatBuf* pre, const float* rowadd, int rowadd_ld, const View* res,
-                      const ConvFuse* fuse, ConvLaunch* prepared) {
+                      int silu, const GnStatBuf* pre, const ConvArgs& a, ConvLaunch* prepared) {
     static const bool off = getenv("SD_NO_GN_FUSE") != nullptr;         // kill switch
     const long HW = (long)H * W;
     // the problem as conv_prepare will pose it (stride 1, no upsample: the only form that follows a GroupNorm)
@@ -559,7 +554,7 @@ bool op_gn_conv_fused(Ctx& c, const NormW& n, const ConvW& w, View x, int N, int
     q.x = x.p; q.ldx = x.ld;
     if (off || !n.gb || n.C != q.Cin || !igemm2_gn_fusable(q, G)) return false;
     const size_t mk = c.arena->mark();
-    ConvFuse f = fuse ? *fuse : ConvFuse();
+    ConvArgs f = gn_conv_args(a);
     f.gn_in = &n; f.gn_in_groups = G; f.gn_in_eps = eps; f.gn_in_silu = silu;
     const long stat_floats = gn_scratch_floats(N, HW, n.C, G);
     float* scratch = c.arena->alloc_f(stat_floats + (long)N * G * 2);   // the statistics pass's summaries | the merged ones
@@ -582,10 +577,10 @@ bool op_gn_conv_fused(Ctx& c, const NormW& n, const ConvW& w, View x, int N, int
         prof_close(c.stream);
     }
     if (prepared) {
-        conv_prepare(c, w, x, N, H, W, y, 1, 0, rowadd, rowadd_ld, res, 0, -1, 0, &f, prepared);
+        conv_prepare(c, w, x, N, H, W, y, f, prepared);
         return true;
     }
-    op_conv(c, w, x, N, H, W, y, 1, 0, rowadd, rowadd_ld, res, 0, -1, 0, &f);
+    op_conv(c, w, x, N, H, W, y, f);
     c.arena->release(mk);
     return true;
 }

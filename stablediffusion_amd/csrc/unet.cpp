@@ -448,6 +448,8 @@ void IPAdapter::run_tokens(Ctx& c, const half_t* image_embeds, long rows, half_t
     View q(a.alloc_h(Ml * A), A, A), kvl(a.alloc_h(Ml * 2 * A), 2 * A, 2 * A), att(a.alloc_h(Ml * A), A, A);
     View f(a.alloc_h(Ml * F), F, F), po(a.alloc_h(Ml * ctx), ctx, ctx);
     op_conv(c, proj_in, View(const_cast<half_t*>(image_embeds), d_img, d_img), R, T, 1, x);
+    ConvArgs gelu;
+    gelu.act = 2;
     if (go && !c.err) {
         prof_open(s, "tile_rows_f16_kernel", 0.0, 4.0 * Ml * dim);
         c.err = launch_tile_rows_f16(latents, n_tok, lat.p, Ml, dim, s);
@@ -461,10 +463,10 @@ void IPAdapter::run_tokens(Ctx& c, const half_t* image_embeds, long rows, half_t
         op_conv(c, l.to_kv, ln, R, n_tok, 1, kvl);
         op_resampler_attention(c, q, kvx.slice(0, A), kvx.slice(A, A), kvl.slice(0, A), kvl.slice(A, A), att, R, n_tok, T,
                                heads);
-        op_conv(c, l.to_out, att, R, n_tok, 1, lat2, 1, 0, nullptr, 0, &lat);
+        op_conv(c, l.to_out, att, R, n_tok, 1, lat2, conv_res(lat));
         op_layernorm(c, l.ff_ln, lat2, ln, Ml, 1e-5f);
-        op_conv(c, l.ff1, ln, R, n_tok, 1, f, 1, 0, nullptr, 0, nullptr, 0, -1, 2);
-        op_conv(c, l.ff2, f, R, n_tok, 1, lat, 1, 0, nullptr, 0, &lat2);
+        op_conv(c, l.ff1, ln, R, n_tok, 1, f, gelu);
+        op_conv(c, l.ff2, f, R, n_tok, 1, lat, conv_res(lat2));
     }
     op_conv(c, proj_out, lat, R, n_tok, 1, po);
     op_layernorm(c, norm, po, View(tok, ctx, ctx), Ml, 1e-5f);
@@ -510,8 +512,7 @@ inline void tap_end(Ctx& c, const char* grp, int i, const char* kind, int j, Vie
 }  // namespace
 
 void run_resnet(Ctx& c, const Resnet& r, View x, int N, int H, int W, View out, int G, float eps,
-                const float* tproj, int tproj_ld, const GnStatBuf* x_stats, GnStatBuf** out_stats, float stream_scale,
-                GnStatBuf* out_buf, int out_groups) {
+                const float* tproj, int tproj_ld, const GnStatBuf* x_stats, const GnOut& out_stats, float stream_scale) {
     Arena& a = *c.arena;
     const size_t mk = a.mark();
     const long M = (long)N * H * W;
@@ -520,29 +521,27 @@ void run_resnet(Ctx& c, const Resnet& r, View x, int N, int H, int W, View out, 
     // Both GroupNorm + SiLU pairs run inside the convolution that consumes them where the launch allows (op_gn_conv);
     // conv1's epilogue leaves the GroupNorm summaries of h2 for norm2, conv2's those of `out` for whoever normalises it.
     const long HW = (long)H * W;
-    ConvFuse f1;
+    ConvArgs f1;
     f1.gn_out = gn_wants_stats(HW, r.cout, G) ? ctx_gnbuf(c) : nullptr;
     f1.gn_groups = G;
     f1.acc_scale = s; f1.bias_scale = s;
-    op_gn_conv(c, r.n1, r.c1, x, N, H, W, h2, G, eps_s, 1, x_stats, tproj ? tproj + r.temb_off : nullptr, tproj_ld, nullptr, &f1);
-    View res = x;
+    f1.rowadd = tproj ? tproj + r.temb_off : nullptr; f1.rowadd_ld = tproj_ld;
+    op_gn_conv(c, r.n1, r.c1, x, N, H, W, h2, G, eps_s, 1, x_stats, f1);
+    ConvArgs f2 = conv_res(x);
     if (r.has_sc) {
-        res = View(a.alloc_h(M * r.cout), r.cout, r.cout);
-        ConvFuse fs;
+        f2.res = View(a.alloc_h(M * r.cout), r.cout, r.cout);
+        ConvArgs fs;
         fs.bias_scale = s;                       // (its input carries the stream's scale already)
-        op_conv(c, r.sc, x, N, H, W, res, 1, 0, nullptr, 0, nullptr, 0, -1, 0, s != 1.f ? &fs : nullptr);
+        op_conv(c, r.sc, x, N, H, W, f2.res, fs);
     }
-    ConvFuse f2;
-    f2.gn_out = (out_stats && gn_wants_stats(HW, r.cout, G)) ? (out_buf ? out_buf : ctx_gnbuf(c)) : nullptr;
-    f2.gn_groups = out_groups > 0 ? out_groups : G;
+    gn_out_resolve(c, out_stats, HW, r.cout, G, &f2);
     f2.acc_scale = s; f2.bias_scale = s;
-    op_gn_conv(c, r.n2, r.c2, h2, N, H, W, out, G, eps_s, 1, f1.gn_out, nullptr, 0, &res, &f2);
-    if (out_stats) *out_stats = f2.gn_out;
+    op_gn_conv(c, r.n2, r.c2, h2, N, H, W, out, G, eps_s, 1, f1.gn_out, f2);
     a.release(mk);
 }
 
 void run_xformer(Ctx& c, const Xformer& t, View x, int N, int H, int W, View out, int G, View text_kv, int L,
-                 const GnStatBuf* x_stats, GnStatBuf** out_stats, GnStatBuf* out_buf, int out_groups, const CfgShare* share) {
+                 const GnStatBuf* x_stats, const GnOut& out_stats, const CfgShare* share) {
     Arena& a = *c.arena;
     const size_t mk = a.mark();
     const int C = t.C;
@@ -565,31 +564,29 @@ void run_xformer(Ctx& c, const Xformer& t, View x, int N, int H, int W, View out
     View cur(a.alloc_h(M * C), C, C), nxt(a.alloc_h(M * C), C, C);
     // row statistics of the residual stream at the three LayerNorm sites (cur -> ln1, t2 -> ln2, t3 -> ln3)
     RowStat st_cur, st_t2, st_t3;
+    // producers of / consumers at the three LayerNorm sites: without the fold they ask for nothing, and the consumers
+    // read `n`, the output of the LayerNorm's own launch
+    ConvArgs f_cur, f_t2, f_t3, f_ln1, f_ln2, f_ln3;
     if (fold) {
         st_cur.p = a.alloc_f(rowstat_floats(M, C));
         st_t2.p = a.alloc_f(rowstat_floats(M, C));
         st_t3.p = a.alloc_f(rowstat_floats(M, C));
+        f_cur.stat_out = &st_cur; f_t2.stat_out = &st_t2; f_t3.stat_out = &st_t3;
+        f_ln1.ln_in = &st_cur; f_ln2.ln_in = &st_t2; f_ln3.ln_in = &st_t3;
+        f_ln1.ln_eps = f_ln2.ln_eps = f_ln3.ln_eps = 1e-5f;
     }
-    ConvFuse f_cur, f_t2, f_t3, f_ln1, f_ln2, f_ln3;          // producers of / consumers at the three LayerNorm sites
-    f_cur.stat_out = &st_cur; f_t2.stat_out = &st_t2; f_t3.stat_out = &st_t3;
-    f_ln1.ln_in = &st_cur; f_ln2.ln_in = &st_t2; f_ln3.ln_in = &st_t3;
-    f_ln1.ln_eps = f_ln2.ln_eps = f_ln3.ln_eps = 1e-5f;
-    op_conv(c, t.pin, hn, Np, H, W, cur, 1, 0, nullptr, 0, nullptr, 0, -1, 0, fold ? &f_cur : nullptr);
-    ConvFuse fo;                                               // the launch that writes `out`
-    fo.gn_out = (out_stats && gn_wants_stats(T, C, G)) ? (out_buf ? out_buf : ctx_gnbuf(c)) : nullptr;
-    fo.gn_groups = out_groups > 0 ? out_groups : G;
+    f_ln3.geglu = 1;                                           // (ff1, with the fold or behind norm3's own launch)
+    op_conv(c, t.pin, hn, Np, H, W, cur, f_cur);
+    ConvArgs fo;                                               // the launch that writes `out`
+    gn_out_resolve(c, out_stats, T, C, G, &fo);
     for (size_t bi = 0; bi < t.blocks.size(); ++bi) {
         const TBlock& b = t.blocks[bi];
         const bool more = bi + 1 < t.blocks.size();
         const size_t mb = a.mark();
         View n(fold ? nullptr : a.alloc_h(M * C), C, C);
         View qkv(a.alloc_h(M * 3 * C), 3 * C, 3 * C);
-        if (fold) {
-            op_conv(c, b.qkv, cur, Np, H, W, qkv, 1, 0, nullptr, 0, nullptr, 0, -1, 0, &f_ln1);
-        } else {
-            op_layernorm(c, b.ln1, cur, n, Mp, 1e-5f);
-            op_conv(c, b.qkv, n, Np, H, W, qkv);
-        }
+        if (!fold) op_layernorm(c, b.ln1, cur, n, Mp, 1e-5f);
+        op_conv(c, b.qkv, fold ? cur : n, Np, H, W, qkv, f_ln1);
         View att(a.alloc_h(M * C), C, C);
         View t2(a.alloc_h(M * C), C, C);
         const int tsite = t.tome_site0 + (int)bi;
@@ -631,10 +628,10 @@ void run_xformer(Ctx& c, const Xformer& t, View x, int N, int H, int W, View out
                 c.err = launch_tome_unmerge(am.p, am.ld, C, plan, Np, T, att.p, att.ld, c.stream);
                 prof_close(c.stream);
             }
-            op_conv(c, b.out1, att, Np, H, W, t2, 1, 0, nullptr, 0, &cur, 0, -1, 0, fold ? &f_t2 : nullptr);
+            op_conv(c, b.out1, att, Np, H, W, t2, conv_res(cur, f_t2));
         } else if (!perturb) {
             op_attention(c, qkv.slice(0, C), qkv.slice(C, C), qkv.slice(2 * C, C), att, Np, T, T, t.heads, d, 0, 1);
-            op_conv(c, b.out1, att, Np, H, W, t2, 1, 0, nullptr, 0, &cur, 0, -1, 0, fold ? &f_t2 : nullptr);
+            op_conv(c, b.out1, att, Np, H, W, t2, conv_res(cur, f_t2));
         } else {
             // Perturbed self-attention: the attention and its out-projection on the Nq un-perturbed images; the perturbed
             // group's map is the identity, so its out-projection reads the V columns of qkv in place (no attention launch,
@@ -644,13 +641,13 @@ void run_xformer(Ctx& c, const Xformer& t, View x, int N, int H, int W, View out
             const long Mq = (long)Nq * T, src0 = pg->widened ? Mq : (long)(Nq - Ng) * T;
             op_attention(c, qkv.slice(0, C), qkv.slice(C, C), qkv.slice(2 * C, C), att, Nq, T, T, t.heads, d, 0, 1);
             RowStat sa, sb;
-            ConvFuse fa = f_t2, fb = f_t2;
+            ConvArgs fa = conv_res(cur, f_t2), fb = f_t2;
             sa.p = st_t2.p;
-            fa.stat_out = &sa; fb.stat_out = &sb;
-            op_conv(c, b.out1, att, Nq, H, W, t2, 1, 0, nullptr, 0, &cur, 0, -1, 0, fold ? &fa : nullptr);
+            if (fold) { fa.stat_out = &sa; fb.stat_out = &sb; }
+            op_conv(c, b.out1, att, Nq, H, W, t2, fa);
             sb.p = st_t2.p ? st_t2.p + Mq * sa.parts * 2 : nullptr;
             const View vp(qkv.p + src0 * qkv.ld + 2 * C, qkv.ld, C), rp(cur.p + src0 * cur.ld, cur.ld, C);
-            op_conv(c, b.out1, vp, Ng, H, W, View(t2.p + Mq * t2.ld, t2.ld, C), 1, 0, nullptr, 0, &rp, 0, -1, 0, fold ? &fb : nullptr);
+            op_conv(c, b.out1, vp, Ng, H, W, View(t2.p + Mq * t2.ld, t2.ld, C), conv_res(rp, fb));
             if (fold) {
                 // the row statistics of t2 across the two launches: side by side when both picked one layout, else one
                 // statistics pass over all N images
@@ -686,12 +683,8 @@ void run_xformer(Ctx& c, const Xformer& t, View x, int N, int H, int W, View out
             }
         }
         View q(a.alloc_h(M * C), C, C);
-        if (fold) {
-            op_conv(c, b.q2, t2, Np, H, W, q, 1, 0, nullptr, 0, nullptr, 0, -1, 0, &f_ln2);
-        } else {
-            op_layernorm(c, b.ln2, t2, n, Mp, 1e-5f);
-            op_conv(c, b.q2, n, Np, H, W, q);
-        }
+        if (!fold) op_layernorm(c, b.ln2, t2, n, Mp, 1e-5f);
+        op_conv(c, b.q2, fold ? t2 : n, Np, H, W, q, f_ln2);
         if (Np != Nl) {
             // the text enters here: from now on the halves differ.  Widen what the N-image remainder reads -- the
             // query, t2 (out2's residual), x (proj_out's residual) and the caller's tensors -- in one launch.
@@ -731,18 +724,14 @@ void run_xformer(Ctx& c, const Xformer& t, View x, int N, int H, int W, View out
         else
             op_attention(c, q, text_kv.slice(b.kv_off, C), text_kv.slice(b.kv_off + C, C), att, Nl, T, L, t.heads, d, 0, 1);
         View t3 = more ? View(a.alloc_h(M * C), C, C) : xformer_tail_t3(a, t, M);
-        op_conv(c, b.out2, att, Nl, H, W, t3, 1, 0, nullptr, 0, &t2, 0, -1, 0, fold ? &f_t3 : nullptr);
+        op_conv(c, b.out2, att, Nl, H, W, t3, conv_res(t2, f_t3));
         if (more) {
             // norm3 -> GEGLU feed-forward -> + residual: the projection with its GEGLU epilogue and the output linear with
             // its residual epilogue
             View g(a.alloc_h(M * 4 * C), 4 * C, 4 * C);
-            if (fold) {
-                op_conv(c, b.ff1, t3, Nl, H, W, g, 1, 0, nullptr, 0, nullptr, 1, -1, 0, &f_ln3);
-            } else {
-                op_layernorm(c, b.ln3, t3, n, Ml, 1e-5f);
-                op_conv(c, b.ff1, n, Nl, H, W, g, 1, 0, nullptr, 0, nullptr, 1);
-            }
-            op_conv(c, b.ff2, g, Nl, H, W, nxt, 1, 0, nullptr, 0, &t3, 0, -1, 0, fold ? &f_cur : nullptr);
+            if (!fold) op_layernorm(c, b.ln3, t3, n, Ml, 1e-5f);
+            op_conv(c, b.ff1, fold ? t3 : n, Nl, H, W, g, f_ln3);
+            op_conv(c, b.ff2, g, Nl, H, W, nxt, conv_res(t3, f_cur));
         } else {
             // the last block: its feed-forward and proj_out
             run_xformer_tail(c, t, t3, st_t3, n, nxt, x, Nl, H, W, out, fo);
@@ -750,8 +739,7 @@ void run_xformer(Ctx& c, const Xformer& t, View x, int N, int H, int W, View out
         a.release(mb);
         View tmp = cur; cur = nxt; nxt = tmp;
     }
-    if (t.blocks.empty()) op_conv(c, t.pout, cur, Nl, H, W, out, 1, 0, nullptr, 0, &x, 0, -1, 0, &fo);
-    if (out_stats) *out_stats = fo.gn_out;
+    if (t.blocks.empty()) op_conv(c, t.pout, cur, Nl, H, W, out, conv_res(x, fo));
     a.release(mk);
 }
 
@@ -762,27 +750,28 @@ View xformer_tail_t3(Arena& a, const Xformer& t, long M) {
 }
 
 bool run_xformer_tail(Ctx& c, const Xformer& t, View t3, const RowStat& st_t3, View n, View nxt, View x, int N, int H, int W,
-                      View out, const ConvFuse& fo) {
+                      View out, const ConvArgs& fo) {
     Arena& a = *c.arena;
     const TBlock& b = t.blocks.back();
     const int C = t.C;
     const long M = (long)N * H * W;
     const int hidden = b.ff1.cout / 2;
-    ConvFuse f_ln3;
-    f_ln3.ln_in = &st_t3; f_ln3.ln_eps = 1e-5f;
+    const bool fold = b.fold;
+    ConvArgs f_ln3;                         // ff1: GEGLU, on the folded norm3 where the block folds it
+    f_ln3.geglu = 1;
+    if (fold || t.pout_fold) { f_ln3.ln_in = &st_t3; f_ln3.ln_eps = 1e-5f; }
     if (t.pout_fold) {
         if (t3.ld != hidden + C || t.ff2p.cin != hidden + C) { set_error("run_xformer_tail: t3 is not xformer_tail_t3's view"); c.err = 1; return false; }
         View gt(t3.p - hidden, t3.ld, hidden + C);          // [g | t3]
-        op_conv(c, b.ff1, t3, N, H, W, gt.slice(0, hidden), 1, 0, nullptr, 0, nullptr, 1, -1, 0, &f_ln3);
+        op_conv(c, b.ff1, t3, N, H, W, gt.slice(0, hidden), f_ln3);
         // K = hidden + C is in no tuned table: the tile measured for ff.net.2 alone (same M and N, K = hidden) is the
         // nearest measured answer, and keeps the table's split-K where it has one
-        ConvFuse f = fo;
+        ConvArgs f = conv_res(x, fo);
         int v, sp;
         if (igemm2_tuned_pointwise((int)M, C, hidden, &v, &sp)) { f.tile_variant = v; f.tile_splits = sp; }
-        op_conv(c, t.ff2p, gt, N, H, W, out, 1, 0, nullptr, 0, &x, 0, -1, 0, &f);
+        op_conv(c, t.ff2p, gt, N, H, W, out, f);
         return false;
     }
-    const bool fold = b.fold;
     // norm3 -> GEGLU feed-forward -> + residual: one launch with the 4C-wide hidden tensor kept on the CU where the
     // problem fits it (the 64 x 64 level: ffn.hip), otherwise the projection with its GEGLU epilogue and the output
     // linear with its residual epilogue
@@ -790,16 +779,12 @@ bool run_xformer_tail(Ctx& c, const Xformer& t, View t3, const RowStat& st_t3, V
     if (!fused) {
         const size_t mk = a.mark();
         View g(a.alloc_h(M * hidden), hidden, hidden);
-        if (fold) {
-            op_conv(c, b.ff1, t3, N, H, W, g, 1, 0, nullptr, 0, nullptr, 1, -1, 0, &f_ln3);
-        } else {
-            op_layernorm(c, b.ln3, t3, n, M, 1e-5f);
-            op_conv(c, b.ff1, n, N, H, W, g, 1, 0, nullptr, 0, nullptr, 1);
-        }
-        op_conv(c, b.ff2, g, N, H, W, nxt, 1, 0, nullptr, 0, &t3, 0, -1, 0, nullptr);
+        if (!fold) op_layernorm(c, b.ln3, t3, n, M, 1e-5f);
+        op_conv(c, b.ff1, fold ? t3 : n, N, H, W, g, f_ln3);
+        op_conv(c, b.ff2, g, N, H, W, nxt, conv_res(t3));
         a.release(mk);
     }
-    op_conv(c, t.pout, nxt, N, H, W, out, 1, 0, nullptr, 0, &x, 0, -1, 0, &fo);
+    op_conv(c, t.pout, nxt, N, H, W, out, conv_res(x, fo));
     return fused;
 }
 
@@ -928,10 +913,11 @@ void Encoder::run_conv_in(Ctx& c, const half_t* sample, int B, int H, int W, Vie
             prof_close(s);
         }
         ConvW pw = conv_in; pw.ks = 1;
-        ConvFuse f;
+        ConvArgs f;
         f.gn_out = gb;
         f.gn_groups = G;
-        op_conv(c, pw, View(col, conv_in.K, (int)conv_in.K), B, H, W, y0, 1, 0, nullptr, 0, res, 0, -1, 0, &f);
+        if (res) f.res = *res;
+        op_conv(c, pw, View(col, conv_in.K, (int)conv_in.K), B, H, W, y0, f);
         *xs = f.gn_out;
     }
     a.release(mk);
@@ -961,16 +947,16 @@ View Encoder::run_down(Ctx& c, View x, GnStatBuf*& xs, int B, int& h, int& w, Vi
                 View dst = skip_view(skip_i);
                 if (c.pag) c.pag->skips_done = skip_i;
                 tap_begin(c, "down_blocks", i, "attentions", j, tmp, B, h, w, dst, h, w);
-                run_xformer(c, down_att[i][j], tmp, B, h, w, dst, G, text_kv, L, rs, &xs, skip_stat(skip_i, (long)h * w, r.cout),
-                            0, sh);
+                run_xformer(c, down_att[i][j], tmp, B, h, w, dst, G, text_kv, L, rs,
+                            GnOut(&xs, skip_stat(skip_i, (long)h * w, r.cout)), sh);
                 tap_end(c, "down_blocks", i, "attentions", j, dst, B, h, w);
                 a.release(mk);
                 x = dst;
             } else {
                 View dst = skip_view(skip_i);
                 tap_begin(c, "down_blocks", i, "resnets", j, x, B, h, w, dst, h, w);
-                run_resnet(c, r, x, ctx_live(c, B), h, w, dst, G, eps, tproj, temb_total, xs, &xs, 1.f,
-                           skip_stat(skip_i, (long)h * w, r.cout));
+                run_resnet(c, r, x, ctx_live(c, B), h, w, dst, G, eps, tproj, temb_total, xs,
+                           GnOut(&xs, skip_stat(skip_i, (long)h * w, r.cout)));
                 tap_end(c, "down_blocks", i, "resnets", j, dst, B, h, w);
                 x = dst;
             }
@@ -978,12 +964,13 @@ View Encoder::run_down(Ctx& c, View x, GnStatBuf*& xs, int B, int& h, int& w, Vi
         }
         if (stop_after >= 0) return x;
         if (i != nb - 1) {
-            ConvFuse f;
+            ConvArgs f;
+            f.stride = 2;
             f.gn_out = skip_stat(skip_i, (long)(h / 2) * (w / 2), down_ds[i].cout);
             View dst = skip_view(skip_i++);
             f.gn_groups = G;
             tap_begin(c, "down_blocks", i, "downsamplers", 0, x, B, h, w, dst, h / 2, w / 2);
-            op_conv(c, down_ds[i], x, ctx_live(c, B), h, w, dst, 2, 0, nullptr, 0, nullptr, 0, -1, 0, &f);
+            op_conv(c, down_ds[i], x, ctx_live(c, B), h, w, dst, f);
             tap_end(c, "down_blocks", i, "downsamplers", 0, dst, B, h / 2, w / 2);
             xs = f.gn_out;
             h /= 2; w /= 2;
@@ -1279,13 +1266,13 @@ int UNet::run(Ctx& c, const UNetCall& call, int dc) {
     //      the residuals only to what the up path reads.  (The grouped cn_residual_kernel is slower than these launches
     //      today: DESIGN.md §4.)  Then the ControlNet's tensors and the mid block's temporaries are dead. ----
     if (use_cn) {
-        ConvFuse f;
+        ConvArgs f;
         f.acc_scale = cn_scale; f.bias_scale = cn_scale;
         for (int si = 0; si <= nskip; ++si) {
             const View xh = si < nskip ? cn_sites[(size_t)si] : cn_mid;
             const View y = si < nskip ? skip_view(si) : View(cats[0].p, cats[0].c1 + cats[0].c2, cats[0].c1);
             const ConvW& zw = si < nskip ? cn->zero[(size_t)si] : cn->zero_mid;
-            op_conv(c, zw, xh, 1, cn_rows[(size_t)si], 1, y, 1, 0, nullptr, 0, &y, 0, -1, 0, &f);
+            op_conv(c, zw, xh, 1, cn_rows[(size_t)si], 1, y, conv_res(y, f));
         }
     }
     if (use_cn) a.release(cn_mark);
@@ -1367,6 +1354,8 @@ int UNet::run(Ctx& c, const UNetCall& call, int dc) {
             const bool hid_here = nx_groups > 0 && !last_in_block;       // this layer's last convolution writes the hidden half
             GnStatBuf* outp = nullptr;
             xs = nullptr;
+            // the last layer's summaries go to the tail, a hidden half's into `hid`; nobody reads any other output's
+            const GnOut summ = last ? GnOut(&xs) : hid_here ? GnOut(&outp, &hid, nx_groups) : GnOut();
             if (cfg.up_block_has_attn[i]) {
                 View tmp(a.alloc_h((long)B * h * w * r.cout), r.cout, r.cout);
                 GnStatBuf* rs = nullptr;
@@ -1374,15 +1363,11 @@ int UNet::run(Ctx& c, const UNetCall& call, int dc) {
                 run_resnet(c, r, xin, Bl, h, w, tmp, G, eps, tproj, temb_total, xin_stats, &rs);
                 tap_end(c, "up_blocks", i, "resnets", j, tmp, B, h, w);
                 tap_begin(c, "up_blocks", i, "attentions", j, tmp, B, h, w, dst, h, w);
-                if (last) run_xformer(c, up_att[i][j], tmp, B, h, w, dst, G, text_kv, L, rs, &xs);
-                else if (hid_here) run_xformer(c, up_att[i][j], tmp, B, h, w, dst, G, text_kv, L, rs, &outp, &hid, nx_groups);
-                else run_xformer(c, up_att[i][j], tmp, B, h, w, dst, G, text_kv, L, rs, nullptr);
+                run_xformer(c, up_att[i][j], tmp, B, h, w, dst, G, text_kv, L, rs, summ);
                 tap_end(c, "up_blocks", i, "attentions", j, dst, B, h, w);
             } else {
                 tap_begin(c, "up_blocks", i, "resnets", j, xin, B, h, w, dst, h, w);
-                if (last) run_resnet(c, r, xin, Bl, h, w, dst, G, eps, tproj, temb_total, xin_stats, &xs);
-                else if (hid_here) run_resnet(c, r, xin, Bl, h, w, dst, G, eps, tproj, temb_total, xin_stats, &outp, 1.f, &hid, nx_groups);
-                else run_resnet(c, r, xin, Bl, h, w, dst, G, eps, tproj, temb_total, xin_stats, nullptr);
+                run_resnet(c, r, xin, Bl, h, w, dst, G, eps, tproj, temb_total, xin_stats, summ);
                 tap_end(c, "up_blocks", i, "resnets", j, dst, B, h, w);
             }
             if (last) {
@@ -1391,11 +1376,12 @@ int UNet::run(Ctx& c, const UNetCall& call, int dc) {
                 if (last_in_block) {
                     const Cat& nx = cats[(size_t)k + 1];
                     View up_dst(nx.p, nx.c1 + nx.c2, nx.c1);
-                    ConvFuse fu;
+                    ConvArgs fu;
+                    fu.up = 1;
                     fu.gn_out = nx_groups > 0 ? &hid : nullptr;
                     fu.gn_groups = nx_groups;
                     tap_begin(c, "up_blocks", i, "upsamplers", 0, dst, B, h, w, up_dst, 2 * h, 2 * w);
-                    op_conv(c, up_us[i], dst, ctx_live(c, B), h, w, up_dst, 1, 1, nullptr, 0, nullptr, 0, -1, 0, nx_groups > 0 ? &fu : nullptr);
+                    op_conv(c, up_us[i], dst, ctx_live(c, B), h, w, up_dst, fu);
                     tap_end(c, "up_blocks", i, "upsamplers", 0, up_dst, B, 2 * h, 2 * w);
                     outp = fu.gn_out;
                     h *= 2; w *= 2;

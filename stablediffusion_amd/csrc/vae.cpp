@@ -184,12 +184,10 @@ void VAE::run_attn(Ctx& c, const VaeAttn& at, View x, int N, int H, int W, View 
     op_conv(c, at.qkv, hn, N, H, W, qkv);
     View o(a.alloc_h(M * C), C, C);
     op_attention(c, qkv.slice(0, C), qkv.slice(C, C), qkv.slice(2 * C, C), o, N, H * W, H * W, 1, C);
-    ConvFuse fo;
-    fo.gn_out = (out_stats && gn_wants_stats((long)H * W, C, cfg.norm_num_groups)) ? ctx_gnbuf(c) : nullptr;
-    fo.gn_groups = cfg.norm_num_groups;
+    ConvArgs fo = conv_res(x);
+    gn_out_resolve(c, out_stats, (long)H * W, C, cfg.norm_num_groups, &fo);
     fo.acc_scale = stream_scale; fo.bias_scale = stream_scale;      // the projection's output joins the (scaled) residual stream
-    op_conv(c, at.out, o, N, H, W, out, 1, 0, nullptr, 0, &x, 0, -1, 0, &fo);
-    if (out_stats) *out_stats = fo.gn_out;
+    op_conv(c, at.out, o, N, H, W, out, fo);
     a.release(mk);
 }
 
@@ -207,7 +205,7 @@ int VAE::run_decode(Ctx& c, const half_t* z, half_t* img, int B, int h, int w) {
     // GroupNorm summaries ride from each convolution's epilogue to the GroupNorm that follows (engine.h)
     ctx_gnpool_init(c, B, (long)h * w << (2 * (nb - 1)), G);
     GnStatBuf* xs = nullptr;
-    auto gn_fuse = [&](ConvFuse& f, long HW, int C) {
+    auto gn_fuse = [&](ConvArgs& f, long HW, int C) {
         f.gn_out = gn_wants_stats(HW, C, G) ? ctx_gnbuf(c) : nullptr;
         f.gn_groups = G;
     };
@@ -221,9 +219,9 @@ int VAE::run_decode(Ctx& c, const half_t* z, half_t* img, int B, int h, int w) {
         if (go && !c.err) c.err = launch_pointwise_nchw(z, pq_w, pq_b, pq, B, lc, lc, (long)h * w, s);
         if (go && !c.err) c.err = launch_im2col_nchw3x3(pq, col, B, lc, h, w, (int)d_conv_in.K, s);
         ConvW pw = d_conv_in; pw.ks = 1;
-        ConvFuse f;
+        ConvArgs f;
         gn_fuse(f, (long)h * w, top);
-        op_conv(c, pw, View(col, d_conv_in.K, (int)d_conv_in.K), B, h, w, x, 1, 0, nullptr, 0, nullptr, 0, -1, 0, &f);
+        op_conv(c, pw, View(col, d_conv_in.K, (int)d_conv_in.K), B, h, w, x, f);
         xs = f.gn_out;
         a.release(mk);
     }
@@ -254,11 +252,12 @@ int VAE::run_decode(Ctx& c, const half_t* z, half_t* img, int B, int h, int w) {
         if (i != nb - 1) {
             const int C = d_us[i].cout;
             View nxt(a.alloc_h(M * 4 * C), C, C);
-            ConvFuse f;
+            ConvArgs f;
+            f.up = 1;
             gn_fuse(f, (long)h * w * 4, C);
             const std::string tn = SD_VAE_TAP(c, "decoder.up_blocks." + std::to_string(i) + ".upsamplers.0");
             tap_begin(c, tn, cur, B, h, w, nxt, 2 * h, 2 * w);
-            op_conv(c, d_us[i], cur, B, h, w, nxt, 1, 1, nullptr, 0, nullptr, 0, -1, 0, &f);
+            op_conv(c, d_us[i], cur, B, h, w, nxt, f);
             tap_end(c, tn, nxt, B, 2 * h, 2 * w);
             xs = f.gn_out;
             h *= 2; w *= 2; M *= 4;
@@ -302,7 +301,7 @@ int VAE::run_encode(Ctx& c, const half_t* img, half_t* moments, int B, int H, in
     long M = (long)B * h * w;
     ctx_gnpool_init(c, B, (long)H * W, G);
     GnStatBuf* xs = nullptr;
-    auto gn_fuse = [&](ConvFuse& f, long HW, int C) {
+    auto gn_fuse = [&](ConvArgs& f, long HW, int C) {
         f.gn_out = gn_wants_stats(HW, C, G) ? ctx_gnbuf(c) : nullptr;
         f.gn_groups = G;
     };
@@ -312,10 +311,10 @@ int VAE::run_encode(Ctx& c, const half_t* img, half_t* moments, int B, int H, in
         half_t* col = a.alloc_h(M * e_conv_in.K);
         if (go && !c.err) c.err = launch_im2col_nchw3x3(img, col, B, cfg.in_channels, h, w, (int)e_conv_in.K, s);
         ConvW pw = e_conv_in; pw.ks = 1;
-        ConvFuse f;
+        ConvArgs f;
         gn_fuse(f, (long)h * w, boc[0]);
         f.acc_scale = ss; f.bias_scale = ss;
-        op_conv(c, pw, View(col, e_conv_in.K, (int)e_conv_in.K), B, h, w, cur, 1, 0, nullptr, 0, nullptr, 0, -1, 0, &f);
+        op_conv(c, pw, View(col, e_conv_in.K, (int)e_conv_in.K), B, h, w, cur, f);
         xs = f.gn_out;
         a.release(mk);
     }
@@ -334,12 +333,13 @@ int VAE::run_encode(Ctx& c, const half_t* img, half_t* moments, int B, int H, in
         if (i != nb - 1) {
             const int C = e_ds[i].cout;
             View nxt(a.alloc_h(M / 4 * C), C, C);
-            ConvFuse f;
+            ConvArgs f;
+            f.stride = 2; f.pad = 0;             // (Downsample2D: conv_problem)
             gn_fuse(f, (long)(h / 2) * (w / 2), C);
             f.bias_scale = ss;                   // (reads the scaled stream)
             const std::string tn = SD_VAE_TAP(c, "encoder.down_blocks." + std::to_string(i) + ".downsamplers.0");
             tap_begin(c, tn, cur, B, h, w, nxt, h / 2, w / 2);
-            op_conv(c, e_ds[i], cur, B, h, w, nxt, 2, 0, nullptr, 0, nullptr, 0, /*pad=*/0, 0, &f);
+            op_conv(c, e_ds[i], cur, B, h, w, nxt, f);
             tap_end(c, tn, nxt, B, h / 2, w / 2);
             xs = f.gn_out;
             h /= 2; w /= 2; M /= 4;
