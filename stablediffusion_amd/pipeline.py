@@ -29,7 +29,7 @@ from typing import Any, Dict, List, Optional, Union
 
 import torch
 
-from . import _lib, pag as _pag, pix2pix as _p2p, regions as _regions, schedulers as _sched, views as _views
+from . import _lib, combos as _combos, pag as _pag, pix2pix as _p2p, regions as _regions, schedulers as _sched, views as _views
 from .image_processor import VaeImageProcessor
 
 
@@ -561,61 +561,35 @@ class StableDiffusionUnifiedPipeline:
         pag_scale: float = 0.0,
         pag_adaptive_scale: float = 0.0,
     ):
-        regional = region_prompts is not None or region_masks is not None or region_prompt_embeds is not None
+        self._use_refiner = bool(use_refiner)
+        facts = _combos.call_facts(self, model, **{k: v for k, v in locals().items() if k not in ("self", "model")})
+        _combos.refuse(facts)                # what does not run together is refused here, before anything runs
+        regional, edit, pag_on = facts.regional, facts.edit, facts.pag
         if regional:
-            _regions.check_call(model, getattr(model, "base", None), locals())
+            _regions.check_call(region_prompts, region_masks, region_prompt_embeds, region_base_weight, prompt_embeds)
         views = None
         if view_window is not None:
-            self._check_views(model, locals())
+            self._check_views(view_window, view_stride, view_batch_size, view_blend)
             views = dict(window=view_window, stride=view_stride, batch=view_batch_size, blend=view_blend,
                          circular=bool(circular_padding))
-        edit = _p2p.is_edit_unet(getattr(getattr(model, "base", None), "config", None))
-        if image_guidance_scale is not None and not edit:
-            raise ValueError("image_guidance_scale is InstructPix2Pix's: it needs a UNet with in_channels == 8")
         if edit:
-            self._check_pix2pix(model, locals())
+            if image_guidance_scale is not None and not math.isfinite(float(image_guidance_scale)):
+                raise ValueError("image_guidance_scale must be finite")
             image_guidance_scale = float(_p2p.DEFAULT_IMAGE_GUIDANCE_SCALE if image_guidance_scale is None
                                          else image_guidance_scale)
         if refiner_start is not None:
-            if pag_scale is not None and float(pag_scale) > 0.0:
-                raise NotImplementedError("perturbed-attention guidance (pag_scale > 0) does not address the refiner")
-            call = {k: v for k, v in locals().items() if k not in ("self", "edit", "views", "regional")}
+            call = {k: v for k, v in locals().items() if k not in ("self", "facts", "edit", "views", "regional", "pag_on")}
             return self._ensemble_of_experts(call)
-        pag_on = pag_scale is not None and float(pag_scale) > 0.0
-        if pag_on:
-            if not math.isfinite(float(pag_scale)) or not math.isfinite(float(pag_adaptive_scale)) or pag_adaptive_scale < 0:
-                raise ValueError("pag_scale and pag_adaptive_scale must be finite and non-negative")
-            if use_refiner or refiner_start is not None:
-                raise NotImplementedError("perturbed-attention guidance (pag_scale > 0) does not address the refiner")
-            if ip_adapter_image is not None or ip_adapter_image_embeds is not None:
-                raise NotImplementedError("perturbed-attention guidance (pag_scale > 0) with an IP-Adapter image is not supported")
-            if bool(getattr(model, "has_controlnet", False)):
-                raise NotImplementedError("perturbed-attention guidance (pag_scale > 0) with a ControlNet loaded is not "
-                                          "supported (unload_controlnet)")
-        if guess_mode:
-            raise NotImplementedError("ControlNet guess_mode is not supported")
-        self._use_refiner = bool(use_refiner)
-        if use_refiner:
-            if getattr(model, "refiner", None) is None:
-                raise ValueError("use_refiner=True but the model has no refiner (SDModelWrapper.load_refiner)")
-            if prompt_embeds is None and (getattr(model, "text_encoder_2", None) is None
-                                          or getattr(model, "tokenizer_2", None) is None):
-                raise ValueError("the refiner reads text_encoder_2 / tokenizer_2, which this model does not have")
-            if control_image is not None or ip_adapter_image is not None or ip_adapter_image_embeds is not None:
-                raise ValueError("the refiner takes no ControlNet or IP-Adapter inputs (they belong to model.base)")
-            if image is None:
-                raise ValueError("use_refiner=True is an image-to-image call: image= (pixels or 4-channel latents) is required")
-        tc_dim = int(getattr(self._unet(model).config, "time_cond_proj_dim", None) or 0)
+        if pag_on and (not math.isfinite(float(pag_scale)) or not math.isfinite(float(pag_adaptive_scale))
+                       or pag_adaptive_scale < 0):
+            raise ValueError("pag_scale and pag_adaptive_scale must be finite and non-negative")
+        tc_dim = _combos.guidance_embed_dim(self._unet(model))
         self._guidance_embedded = tc_dim > 0
         if not 0.0 <= float(guidance_rescale) <= 1.0:
             raise ValueError(f"guidance_rescale must lie in [0, 1], got {guidance_rescale}")
         # as in diffusers: only with CFG on and a positive value
         guidance_rescale = float(guidance_rescale) if self.do_classifier_free_guidance else 0.0
-        has_cn = bool(getattr(model, "has_controlnet", False)) and not use_refiner     # (a ControlNet belongs to .base)
-        if control_image is not None and not has_cn:
-            raise ValueError("control_image given but no ControlNet is loaded (SDModelWrapper.load_controlnet)")
-        if has_cn and control_image is None:
-            raise ValueError("a ControlNet is loaded: control_image is required (or unload_controlnet)")
+        has_cn = facts.cn_loaded and not use_refiner     # (a ControlNet belongs to .base)
         if has_cn:
             if any(isinstance(v, (list, tuple)) for v in (controlnet_conditioning_scale, control_guidance_start,
                                                           control_guidance_end)):
@@ -633,33 +607,6 @@ class StableDiffusionUnifiedPipeline:
         if hasattr(model, "apply_adapters"):
             model.apply_adapters()
         unet = self._unet(model)             # (after the re-fuse, which replaces model.base)
-        if getattr(unet, "tome", None) is not None:
-            # token merging: what the engine's forward refuses is refused here, before anything runs
-            if pag_on:
-                raise NotImplementedError("token merging (enable_tome) with perturbed-attention guidance (pag_scale > 0) is "
-                                          "not supported (disable_tome)")
-            if unet.config.in_channels == 8:
-                raise NotImplementedError("token merging (enable_tome) with an 8-channel edit UNet is not supported: its "
-                                          "two-source forward runs without it (disable_tome)")
-            if getattr(unet, "_graph_on", False):
-                raise NotImplementedError("token merging (enable_tome) under use_graph is not supported (disable_tome)")
-            if view_window is not None:
-                raise NotImplementedError("token merging (enable_tome) with view_window (MultiDiffusion) is not supported "
-                                          "(disable_tome)")
-            for attr, what in (("_freeu", "FreeU enabled"), ("_cn", "a ControlNet loaded"), ("_ip", "an IP-Adapter loaded")):
-                if getattr(unet, attr, None) is not None:
-                    raise NotImplementedError(f"token merging (enable_tome) with {what} is not supported yet: the engine's "
-                                              "forward refuses the combination (disable_tome)")
-        if pag_on:
-            if getattr(unet, "deepcache", None) is not None:
-                raise NotImplementedError("perturbed-attention guidance (pag_scale > 0) with DeepCache enabled is not "
-                                          "supported: a reuse step skips the perturbed layers (disable_deepcache)")
-            if unet.config.in_channels == 9:
-                raise NotImplementedError("perturbed-attention guidance (pag_scale > 0) with a 9-channel inpaint UNet is "
-                                          "not supported")
-            if tc_dim:
-                raise NotImplementedError("perturbed-attention guidance (pag_scale > 0) with a guidance-embedded UNet "
-                                          "(time_cond_proj_dim) is not supported")
         if image is not None and mask_image is None:
             # img2img keeps the image's own size (`:238` preprocesses without height / width); PIL, numpy and
             # tensor inputs alike go through the image processor (rounded down to a multiple of the VAE factor)
@@ -828,15 +775,11 @@ class StableDiffusionUnifiedPipeline:
         # guidance-embedded UNet: the guidance scale goes in as an embedding, once per call, to every forward
         tc_kwargs = {}
         if tc_dim:
-            if has_cn:
-                raise NotImplementedError("a guidance-embedded UNet (time_cond_proj_dim) with a ControlNet is not supported")
             w = torch.full((batch_size * num_images_per_prompt,), float(guidance_scale) - 1.0)
             tc_kwargs = {"timestep_cond": guidance_scale_embedding(w, tc_dim).to(self.device)}
 
         control = None
         if has_cn:
-            if num_channels_unet != 4:
-                raise ValueError("ControlNet needs a 4-channel UNet (9-channel inpaint UNets are not supported)")
             control = self.prepare_control_image(model, control_image, height, width, batch_size, num_images_per_prompt)
 
         if self.do_classifier_free_guidance and edit:
@@ -913,8 +856,6 @@ class StableDiffusionUnifiedPipeline:
         # i % interval == 0 (so the first step of every loop stores: a stale cache is never read), the shallow one on
         # that feature otherwise.  The mode is engine state, set in front of every forward whichever path the step takes
         deepcache = getattr(unet, "deepcache", None)
-        if deepcache is not None and control is not None:
-            raise ValueError("DeepCache runs no ControlNet on its reuse steps: disable_deepcache() or drop control_image")
         tome_on = getattr(unet, "tome", None) is not None and hasattr(unet, "tome_step")
         kv_cache = getattr(unet, "text_kv_cache", None)
         if kv_cache is not None:
@@ -1068,73 +1009,15 @@ class StableDiffusionUnifiedPipeline:
         return latents
 
     @staticmethod
-    def _check_pix2pix(model, kw):
-        """What an InstructPix2Pix call (a UNet with in_channels == 8) takes and what it does not."""
-        base = model.base
-        igs = kw["image_guidance_scale"]
-        if kw["mask_image"] is not None or kw["masked_image_latents"] is not None:
-            raise ValueError("InstructPix2Pix takes no mask_image (it edits the whole picture)")
-        if kw["strength"] != 1.0:
-            raise ValueError("InstructPix2Pix starts from pure noise: there is no strength")
-        if kw["guidance_rescale"] is not None and float(kw["guidance_rescale"]) > 0.0:
-            raise ValueError("InstructPix2Pix takes no guidance_rescale")
-        if kw["image"] is None:
-            raise ValueError("InstructPix2Pix (a UNet with in_channels == 8) needs image=, the picture to edit")
-        if igs is not None and not math.isfinite(float(igs)):
-            raise ValueError("image_guidance_scale must be finite")
-        if kw["use_refiner"] or kw["refiner_start"] is not None:
-            raise NotImplementedError("InstructPix2Pix does not address the refiner")
-        if bool(getattr(model, "has_controlnet", False)) or kw["control_image"] is not None:
-            raise NotImplementedError("InstructPix2Pix with a ControlNet loaded is not supported (unload_controlnet)")
-        if kw["ip_adapter_image"] is not None or kw["ip_adapter_image_embeds"] is not None:
-            raise NotImplementedError("InstructPix2Pix with an IP-Adapter image is not supported")
-        if kw["pag_scale"] is not None and float(kw["pag_scale"]) > 0.0:
-            raise NotImplementedError("InstructPix2Pix with perturbed-attention guidance (pag_scale > 0) is not supported")
-        if getattr(base, "deepcache", None) is not None:
-            raise NotImplementedError("InstructPix2Pix with DeepCache enabled is not supported (disable_deepcache)")
-        if getattr(base.config, "addition_embed_type", None) == "text_time":
-            raise NotImplementedError("InstructPix2Pix on a text_time (SDXL edit) UNet is not supported")
-        if int(getattr(base.config, "time_cond_proj_dim", None) or 0) > 0:
-            raise NotImplementedError("InstructPix2Pix on a guidance-embedded UNet (time_cond_proj_dim) is not supported")
-
-    @staticmethod
-    def _check_views(model, kw):
-        """What a MultiDiffusion call (view_window given) does not take: raised before anything runs."""
-        base = getattr(model, "base", None)
-        cfg = getattr(base, "config", None)
-        if kw["use_refiner"] or kw["refiner_start"] is not None:
-            raise NotImplementedError("view_window (MultiDiffusion) does not address the refiner")
-        if bool(getattr(model, "has_controlnet", False)) or kw["control_image"] is not None:
-            raise NotImplementedError("view_window (MultiDiffusion) with a ControlNet loaded is not supported "
-                                      "(unload_controlnet): the control image would need windows of its own")
-        if kw["ip_adapter_image"] is not None or kw["ip_adapter_image_embeds"] is not None:
-            raise NotImplementedError("view_window (MultiDiffusion) with an IP-Adapter image is not supported")
-        if kw["pag_scale"] is not None and float(kw["pag_scale"]) > 0.0:
-            raise NotImplementedError("view_window (MultiDiffusion) with perturbed-attention guidance (pag_scale > 0) is "
-                                      "not supported")
-        if getattr(base, "deepcache", None) is not None:
-            raise NotImplementedError("view_window (MultiDiffusion) with DeepCache enabled is not supported: one cached "
-                                      "feature cannot serve several windows (disable_deepcache)")
-        if int(getattr(cfg, "in_channels", 4)) in (8, 9):
-            raise NotImplementedError("view_window (MultiDiffusion) with an 8- or 9-channel UNet is not supported: the extra "
-                                      "channels would need windows of their own")
-        if getattr(cfg, "addition_embed_type", None) == "text_time":
-            raise NotImplementedError("view_window (MultiDiffusion) on a text_time (SDXL) UNet is not supported: every "
-                                      "window would need its own crop conditioning")
-        if int(getattr(cfg, "time_cond_proj_dim", None) or 0) > 0:
-            raise NotImplementedError("view_window (MultiDiffusion) on a guidance-embedded UNet (time_cond_proj_dim) is not "
-                                      "supported")
-        if kw["guidance_rescale"] is not None and float(kw["guidance_rescale"]) > 0.0:
-            raise ValueError("view_window (MultiDiffusion) takes no guidance_rescale: its per-sample statistic differs "
-                             "between a window and the canvas")
-        window = _views.as_pair(kw["view_window"])
-        if min(window) < 1:
+    def _check_views(view_window, view_stride, view_batch_size, view_blend):
+        """MultiDiffusion's own arguments (what it does not run with: combos.REFUSALS)."""
+        if min(_views.as_pair(view_window)) < 1:
             raise ValueError("view_window must be positive")
-        if kw["view_stride"] is not None and min(_views.as_pair(kw["view_stride"])) < 1:
+        if view_stride is not None and min(_views.as_pair(view_stride)) < 1:
             raise ValueError("view_stride must be at least 1")
-        if kw["view_batch_size"] is not None and int(kw["view_batch_size"]) < 1:
+        if view_batch_size is not None and int(view_batch_size) < 1:
             raise ValueError("view_batch_size must be at least 1")
-        _views.window_weights(kw["view_blend"], 1, 1)          # (an unknown name raises)
+        _views.window_weights(view_blend, 1, 1)          # (an unknown name raises)
 
     @staticmethod
     def _host_step(model, noise_pred, t, latents, noise, lcm):
@@ -1631,19 +1514,6 @@ class StableDiffusionUnifiedPipeline:
         r = call.pop("refiner_start")
         if isinstance(r, bool) or not isinstance(r, (int, float)) or not 0.0 < float(r) < 1.0:
             raise ValueError(f"refiner_start must lie in (0, 1), got {r!r}")
-        if call["use_refiner"]:
-            raise ValueError("refiner_start runs base and refiner in one call: it cannot be combined with use_refiner=True")
-        if call["denoising_end"] is not None:
-            raise ValueError("refiner_start sets the base's denoising_end itself: pass one or the other")
-        model = call["model"]
-        if getattr(model, "refiner", None) is None:
-            raise ValueError("refiner_start given but the model has no refiner (SDModelWrapper.load_refiner)")
-        if getattr(model, "text_encoder_2", None) is None or getattr(model, "tokenizer_2", None) is None:
-            raise ValueError("the refiner reads text_encoder_2 / tokenizer_2, which this model does not have")
-        if call["prompt_embeds"] is not None:
-            raise ValueError("refiner_start needs prompts: base and refiner take different embeddings")
-        if call["mask_image"] is not None:
-            raise NotImplementedError("refiner_start with inpainting is not supported")
         saved = self.output_type
         self.output_type = "latents"
         try:

@@ -83,10 +83,9 @@ def _count(region_masks) -> int:
     return len(region_masks) if isinstance(region_masks, (list, tuple)) else 1
 
 
-def check_call(model, unet, kw) -> int:
-    """The pipeline call's regional arguments (`kw`: its locals), checked before anything runs; returns R.  ValueError for
-    arguments that contradict each other, NotImplementedError for what regional prompts do not compose with."""
-    prompts, masks, embeds = kw["region_prompts"], kw["region_masks"], kw["region_prompt_embeds"]
+def check_call(prompts, masks, embeds, base_weight, prompt_embeds) -> int:
+    """The pipeline call's regional arguments, checked before anything runs; returns R.  (What regional prompts do not
+    run with: combos.REFUSALS.)"""
     if masks is None or (prompts is None and embeds is None):
         raise ValueError("regional prompts need region_masks and region_prompts (or region_prompt_embeds)")
     if isinstance(prompts, str):
@@ -101,36 +100,11 @@ def check_call(model, unet, kw) -> int:
         raise ValueError(f"{n} region prompts but {nm} region masks")
     if isinstance(masks, torch.Tensor) and (masks.ndim not in (3, 4) or (masks.ndim == 4 and masks.shape[1] != 1)):
         raise ValueError("region_masks: expected a tensor [R-1, H, W] or [R-1, 1, H, W]")
-    bw = float(kw["region_base_weight"])
+    bw = float(base_weight)
     if not bw >= 0.0 or bw == float("inf"):
         raise ValueError(f"region_base_weight must be finite and >= 0, got {bw}")
-    if kw["prompt_embeds"] is not None and embeds is None:
+    if prompt_embeds is not None and embeds is None:
         raise NotImplementedError("prompt_embeds= with regional prompts needs region_prompt_embeds= (one [B, L, D] per region)")
-    if kw["prompt_embeds"] is None and embeds is not None:
+    if prompt_embeds is None and embeds is not None:
         raise NotImplementedError("region_prompt_embeds= goes with prompt_embeds= (region_prompts= with prompt=)")
-    if bool(getattr(model, "has_controlnet", False)) or kw["control_image"] is not None:
-        raise NotImplementedError("regional prompts with a ControlNet loaded are not supported (unload_controlnet)")
-    if kw["ip_adapter_image"] is not None or kw["ip_adapter_image_embeds"] is not None:
-        raise NotImplementedError("regional prompts with an IP-Adapter image are not supported")
-    if kw["pag_scale"] is not None and float(kw["pag_scale"]) > 0.0:
-        raise NotImplementedError("regional prompts with perturbed-attention guidance (pag_scale > 0) are not supported")
-    if kw["view_window"] is not None:
-        raise NotImplementedError("regional prompts with view_window (MultiDiffusion) are not supported")
-    if kw["use_refiner"] or kw["refiner_start"] is not None:
-        raise NotImplementedError("regional prompts do not address the refiner")
-    if getattr(unet, "deepcache", None) is not None:
-        raise NotImplementedError("regional prompts with DeepCache enabled are not supported (disable_deepcache)")
-    if getattr(unet, "tome", None) is not None:
-        raise NotImplementedError("regional prompts with token merging enabled are not supported (disable_tome)")
-    if getattr(unet, "_graph_on", False):
-        raise NotImplementedError("regional prompts under use_graph are not supported")
-    if getattr(unet, "_ip", None) is not None and float(getattr(unet, "_ip_scale", 1.0)) != 0.0:
-        raise NotImplementedError("regional prompts with an IP-Adapter attached at a non-zero scale are not supported")
-    cfg = unet.config
-    if cfg.in_channels in (8, 9):
-        raise NotImplementedError("regional prompts with an 8- or 9-channel UNet are not supported")
-    if int(getattr(cfg, "time_cond_proj_dim", None) or 0) > 0:
-        raise NotImplementedError("regional prompts with a guidance-embedded UNet (time_cond_proj_dim) are not supported")
-    if not hasattr(unet, "set_regions") or not hasattr(unet, "clear_regions"):
-        raise NotImplementedError(f"{type(unet).__name__} has no set_regions: regional prompts need the engine's UNet")
     return n + 1
