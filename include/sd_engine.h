@@ -703,6 +703,76 @@ int sd_views_gather(const void* canvas, void* windows, int B, int C, int Hc, int
 int sd_views_merge(const void* model_out, void* eps_out, const float* window_weights, int G, int B, int C, int Hc, int Wc,
                    int h, int w, const int* ys, int ny, const int* xs, int nx, int wrap_x, int views_per_chunk, void* stream);
 
+/* -- Tiled VAE: replaces diffusers 0.27.2 AutoencoderKL.tiled_decode / tiled_encode / blend_v / blend_h (what
+ * `vae.enable_tiling()` switches on; the semantics are recalled, not pinned: DESIGN.md section 8).  A canvas is cut into
+ * tiles of `tile_in` whose starts are `stride_in` apart (diffusers' overlap_size = int(tile_in (1 - f))), every tile runs
+ * through the unchanged decoder / encoder at its own size -- tiles at the far border are truncated, down to one latent
+ * pixel -- and the outputs are cross-faded over `blend` = int(tile_out f) rows / columns in raster order and cropped to
+ * `limit` = tile_out - blend.  decode: in = latents, out = image; encode: in = image, out = moments.
+ *
+ * sd_vae_tile_plan: the plan of one canvas, host only (needs no device).  h, w: the canvas in INPUT space.  Tile k of an
+ * axis starts at k stride_in and has size_y[k] / size_x[k] = min(tile_in, L - k stride_in): all full-size but at most the
+ * last two, so there are at most 3 x 3 shape classes (diffusers truncates the tile before the last too whenever
+ * L < (n - 2) stride_in + tile_in; with one truncated tile per axis there are the four classes interior / last column /
+ * last row / corner).  Class c holds the class_ny[c] x class_nx[c] tiles from (class_iy0[c], class_ix0[c]) on, in raster
+ * order, each of input shape class_h[c] x class_w[c].
+ * SD_ERR_INVALID: a null plan, a non-positive size, tile_overlap_factor outside [0, 0.5], blend > tile_out / 2 (the two
+ * bounds the merge's closed form rests on), more than SD_VAE_TILE_MAX_AXIS = 64 tiles on an axis, tile_sample no
+ * multiple of tile_latent, and factors for which the crops would not tile the output canvas: it takes
+ * int(tile_latent (1 - f)) tile_sample / tile_latent == tile_sample - int(tile_sample f) (likewise for encode, where H
+ * and W must also be multiples of the scale); diffusers returns a canvas of another size there.
+ *
+ * sd_vae_tile_stack: where the merge expects each tile's output: tile_offsets[iy * nx + ix] = the element offset of tile
+ * (iy, ix) in the stack, its B images [B, C, th, tw] together (th, tw in OUTPUT space); *total = the stack's elements.
+ * The layout is [class][tile in raster order][b]; it is fixed by the plan, so the merge takes no table.
+ *
+ * sd_vae_decode_tiled / sd_vae_encode_tiled: sd_vae_decode / sd_vae_encode of a canvas by tiles, tile_sample =
+ * tile_latent 2^(blocks - 1).  Tiles of one class, of all B images, are stacked (one gather launch per chunk of
+ * tile_batch images, 1..32) and run through the plain decode / encode; one merge launch writes the canvas.  The workspace
+ * is then the plain call's for one chunk plus the chunk's input and the stack of tile outputs (sd_vae_memory_tiled).
+ * sd_vae_encode_range_shift applies to every tile alike.  Debug taps are NOT supported here: while sd_vae_tap is on both
+ * return SD_ERR_UNSUPPORTED with nothing launched.  sd_vae_poison_workspace covers the arena as before; the two tile
+ * buffers are written in full before they are read.  A canvas of one tile is that tile's plain call plus a copying merge.
+ *
+ * sd_vae_memory_tiled: sd_vae_memory, plus *tile_bytes = the chunk-input and tile-stack buffers' capacities (0 until a
+ * tiled call has run).  sd_vae_memory's own answer keeps its meaning (the arena).
+ *
+ * Operator entries (test / tool path): sd_op_vae_tiles_gather copies n <= 32 tiles [th, tw] at (ys[i], xs[i]) of image
+ * bs[i] of a canvas [., C, Hc, Wc] with row stride ld (HOST arrays: the tile list travels in the launch parameters) into
+ * stack [n, C, th, tw]; sd_op_vae_tiles_merge writes canvas [B, C, out_h, out_w] (row stride ld >= out_w) from `tiles`
+ * laid out as sd_vae_tile_stack says, stack_elems = the elements `tiles` holds (checked against the plan's).  iters > 0:
+ * *ms_per_launch = the mean of that many launches.  SD_ERR_INVALID with nothing launched: a null pointer, a tile outside
+ * the canvas, ld below the width, a stack smaller than the plan's.  Both kernels move 16 bytes per thread when widths,
+ * starts, strides (and for the merge tile_out, blend, limit) are multiples of 8 and the pointers 16-byte aligned, one
+ * element otherwise. */
+#define SD_VAE_TILE_MAX_AXIS 64
+#define SD_VAE_TILE_MAX_CLASSES 9
+#define SD_VAE_TILE_MAX_BATCH 32
+typedef struct sd_vae_tiles {
+    int32_t ny, nx;                     /* tiles per axis */
+    int32_t tile_in, stride_in;         /* input space */
+    int32_t tile_out, blend, limit;     /* output space */
+    int32_t scale;                      /* tile_sample / tile_latent */
+    int32_t in_h, in_w, out_h, out_w;
+    int32_t size_y[SD_VAE_TILE_MAX_AXIS], size_x[SD_VAE_TILE_MAX_AXIS];   /* input space */
+    int32_t n_classes;
+    int32_t class_h[SD_VAE_TILE_MAX_CLASSES], class_w[SD_VAE_TILE_MAX_CLASSES], class_count[SD_VAE_TILE_MAX_CLASSES];
+    int32_t class_iy0[SD_VAE_TILE_MAX_CLASSES], class_ny[SD_VAE_TILE_MAX_CLASSES];
+    int32_t class_ix0[SD_VAE_TILE_MAX_CLASSES], class_nx[SD_VAE_TILE_MAX_CLASSES];
+} sd_vae_tiles;
+int sd_vae_tile_plan(int encode, int h, int w, int tile_sample, int tile_latent, double overlap_factor,
+                          sd_vae_tiles* plan);
+int sd_vae_tile_stack(const sd_vae_tiles* plan, int B, int C, int64_t* tile_offsets, int64_t* total);
+int sd_vae_decode_tiled(sd_vae* v, const void* z, void* img, int B, int h, int w, int tile_latent, double overlap_factor,
+                        int tile_batch, void* stream);
+int sd_vae_encode_tiled(sd_vae* v, const void* img, void* moments, int B, int H, int W, int tile_latent,
+                        double overlap_factor, int tile_batch, void* stream);
+int sd_vae_memory_tiled(const sd_vae* v, int64_t* weight_bytes, int64_t* workspace_bytes, int64_t* tile_bytes);
+int sd_op_vae_tiles_gather(const void* canvas, int64_t ld, void* stack, const int* bs, const int* ys, const int* xs, int n,
+                           int B, int C, int Hc, int Wc, int th, int tw, int iters, float* ms_per_launch, void* stream);
+int sd_op_vae_tiles_merge(const void* tiles, int64_t stack_elems, void* canvas, int64_t ld, const sd_vae_tiles* plan,
+                          int B, int C, int iters, float* ms_per_launch, void* stream);
+
 /* convert_pt_to_numpy (runpod-worker/handler_logic.py:21-29): decoded images [B,C,H,W] f16 in [-1,1] ->
  * [B,H,W,C] uint8, with the reference's fp16 roundings and truncating cast (bit-exact with running
  * the reference's op sequence on the same fp16 tensor).  C <= 4. */

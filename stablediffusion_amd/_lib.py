@@ -54,6 +54,28 @@ class SdVAEConfig(C.Structure):
     ]
 
 
+SD_VAE_TILE_MAX_AXIS = 64
+SD_VAE_TILE_MAX_CLASSES = 9
+SD_VAE_TILE_MAX_BATCH = 32
+
+
+class SdVAETiles(C.Structure):
+    """sd_vae_tiles (include/sd_engine.h): the plan of one tiled decode / encode."""
+    _fields_ = [
+        ("ny", C.c_int32), ("nx", C.c_int32),
+        ("tile_in", C.c_int32), ("stride_in", C.c_int32),
+        ("tile_out", C.c_int32), ("blend", C.c_int32), ("limit", C.c_int32),
+        ("scale", C.c_int32),
+        ("in_h", C.c_int32), ("in_w", C.c_int32), ("out_h", C.c_int32), ("out_w", C.c_int32),
+        ("size_y", C.c_int32 * SD_VAE_TILE_MAX_AXIS), ("size_x", C.c_int32 * SD_VAE_TILE_MAX_AXIS),
+        ("n_classes", C.c_int32),
+        ("class_h", C.c_int32 * SD_VAE_TILE_MAX_CLASSES), ("class_w", C.c_int32 * SD_VAE_TILE_MAX_CLASSES),
+        ("class_count", C.c_int32 * SD_VAE_TILE_MAX_CLASSES),
+        ("class_iy0", C.c_int32 * SD_VAE_TILE_MAX_CLASSES), ("class_ny", C.c_int32 * SD_VAE_TILE_MAX_CLASSES),
+        ("class_ix0", C.c_int32 * SD_VAE_TILE_MAX_CLASSES), ("class_nx", C.c_int32 * SD_VAE_TILE_MAX_CLASSES),
+    ]
+
+
 class SdClipConfig(C.Structure):
     _fields_ = [
         ("vocab_size", C.c_int32),
@@ -239,6 +261,14 @@ SIGNATURES = {
     "sd_view_plan": (_I, [_I, _I, _I, _I, C.POINTER(_I), _I]),
     "sd_views_gather": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, C.POINTER(_I), _I, C.POINTER(_I), _I, _I, _P]),
     "sd_views_merge": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, C.POINTER(_I), _I, C.POINTER(_I), _I, _I, _I, _P]),
+    "sd_vae_tile_plan": (_I, [_I, _I, _I, _I, _I, C.c_double, C.POINTER(SdVAETiles)]),
+    "sd_vae_tile_stack": (_I, [C.POINTER(SdVAETiles), _I, _I, C.POINTER(_I64), C.POINTER(_I64)]),
+    "sd_vae_decode_tiled": (_I, [_P, _P, _P, _I, _I, _I, _I, C.c_double, _I, _P]),
+    "sd_vae_encode_tiled": (_I, [_P, _P, _P, _I, _I, _I, _I, C.c_double, _I, _P]),
+    "sd_vae_memory_tiled": (_I, [_P, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64)]),
+    "sd_op_vae_tiles_gather": (_I, [_P, _I64, _P, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), _I, _I, _I, _I, _I, _I, _I, _I,
+                                    C.POINTER(_F), _P]),
+    "sd_op_vae_tiles_merge": (_I, [_P, _I64, _P, _I64, C.POINTER(SdVAETiles), _I, _I, _I, C.POINTER(_F), _P]),
     "sd_cfg_linear_step": (_I, [_P, _P, _P, _I64, _F, _F, _F, _F, _F, _F, _P]),
     "sd_pag_linear_step": (_I, [_P, _I, _P, _P, _I64, _F, _F, _F, _F, _F, _F, _F, _P]),
     "sd_pag_combine": (_I, [_P, _I, _P, _I64, _F, _F, _P]),

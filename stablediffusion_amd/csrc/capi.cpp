@@ -639,6 +639,42 @@ int sd_vae_memory(const sd_vae* v, int64_t* weight_bytes, int64_t* workspace_byt
     if (workspace_bytes) *workspace_bytes = (int64_t)v->impl.arena.capacity();
     return SD_OK;
 }
+int sd_vae_memory_tiled(const sd_vae* v, int64_t* weight_bytes, int64_t* workspace_bytes, int64_t* tile_bytes) {
+    if (int rc = sd_vae_memory(v, weight_bytes, workspace_bytes)) return rc;
+    if (tile_bytes) *tile_bytes = (int64_t)(v->impl.tile_in.capacity() + v->impl.tile_stack.capacity());
+    return SD_OK;
+}
+int sd_vae_tile_plan(int encode, int h, int w, int tile_sample, int tile_latent, double overlap_factor, sd_vae_tiles* plan) {
+    return vae_tile_plan(encode, h, w, tile_sample, tile_latent, overlap_factor, plan) ? SD_ERR_INVALID : SD_OK;
+}
+int sd_vae_tile_stack(const sd_vae_tiles* plan, int B, int C, int64_t* tile_offsets, int64_t* total) {
+    if (!plan || B < 1 || C < 1) { set_error("sd_vae_tile_stack: a plan, B >= 1, C >= 1"); return SD_ERR_INVALID; }
+    long class_off[SD_VAE_TILE_MAX_CLASSES];
+    const long n = vae_tile_stack(*plan, B, C, nullptr, class_off);
+    const bool enc = plan->tile_out < plan->tile_in;
+    for (int c = 0; tile_offsets && c < plan->n_classes; ++c) {
+        const long oh = enc ? plan->class_h[c] / plan->scale : plan->class_h[c] * plan->scale;
+        const long ow = enc ? plan->class_w[c] / plan->scale : plan->class_w[c] * plan->scale;
+        for (int t = 0; t < plan->class_count[c]; ++t) {
+            const int iy = plan->class_iy0[c] + t / plan->class_nx[c], ix = plan->class_ix0[c] + t % plan->class_nx[c];
+            tile_offsets[iy * plan->nx + ix] = class_off[c] + (long)t * B * C * oh * ow;
+        }
+    }
+    if (total) *total = n;
+    return SD_OK;
+}
+int sd_vae_decode_tiled(sd_vae* v, const void* z, void* img, int B, int h, int w, int tile_latent, double overlap_factor,
+                        int tile_batch, void* stream) {
+    if (!v || !z || !img) { set_error("null argument"); return SD_ERR_INVALID; }
+    return v->impl.decode_tiled(static_cast<const half_t*>(z), static_cast<half_t*>(img), B, h, w, tile_latent,
+                                overlap_factor, tile_batch, static_cast<hipStream_t>(stream));
+}
+int sd_vae_encode_tiled(sd_vae* v, const void* img, void* moments, int B, int H, int W, int tile_latent,
+                        double overlap_factor, int tile_batch, void* stream) {
+    if (!v || !img || !moments) { set_error("null argument"); return SD_ERR_INVALID; }
+    return v->impl.encode_tiled(static_cast<const half_t*>(img), static_cast<half_t*>(moments), B, H, W, tile_latent,
+                                overlap_factor, tile_batch, static_cast<hipStream_t>(stream));
+}
 
 // ------------------------------------------------------------------------------------------- CLIP
 int sd_clip_create(const sd_clip_config* cfg, sd_clip** out) {
@@ -2177,6 +2213,44 @@ int sd_op_ffn_geglu_proj_out(const void* x_in, const void* t3, const void* ln_ga
     if (fused) *fused = ran_fused ? 1 : 0;
     if (gn_rows) *gn_rows = gb.st.part ? (int)gb.st.rows : 0;
     return rc;
+}
+
+int sd_op_vae_tiles_gather(const void* canvas, int64_t ld, void* stack, const int* bs, const int* ys, const int* xs, int n,
+                           int B, int C, int Hc, int Wc, int th, int tw, int iters, float* ms_per_launch, void* stream) {
+    if (!canvas || !stack || !bs || !ys || !xs || n < 1 || n > VAE_TILE_MAX_BATCH || B < 1 || C < 1 || th < 1 || tw < 1 ||
+        th > Hc || tw > Wc || ld < Wc) {
+        set_error("sd_op_vae_tiles_gather: bad arguments (non-null pointers, 1..32 tiles no larger than the canvas, ld >= Wc)");
+        return SD_ERR_INVALID;
+    }
+    if (iters > 0 && !ms_per_launch) { set_error("ms_per_launch required with iters > 0"); return SD_ERR_INVALID; }
+    VaeGatherList l = {};
+    for (int i = 0; i < n; ++i) {
+        if (bs[i] < 0 || bs[i] >= B || ys[i] < 0 || ys[i] > Hc - th || xs[i] < 0 || xs[i] > Wc - tw) {
+            set_error("sd_op_vae_tiles_gather: a tile outside the canvas"); return SD_ERR_INVALID;
+        }
+        l.b[i] = bs[i]; l.ys[i] = ys[i]; l.xs[i] = xs[i];
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return launch_or_time(s, iters, ms_per_launch, [&]() {
+        return launch_vae_tile_gather(static_cast<const half_t*>(canvas), ld, static_cast<half_t*>(stack), l, n, C, Hc, th, tw, s);
+    });
+}
+
+int sd_op_vae_tiles_merge(const void* tiles, int64_t stack_elems, void* canvas, int64_t ld, const sd_vae_tiles* plan, int B,
+                          int C, int iters, float* ms_per_launch, void* stream) {
+    if (!tiles || !canvas || !plan || B < 1 || C < 1) { set_error("sd_op_vae_tiles_merge: null argument, or B or C < 1"); return SD_ERR_INVALID; }
+    if (iters > 0 && !ms_per_launch) { set_error("ms_per_launch required with iters > 0"); return SD_ERR_INVALID; }
+    if (!vae_tile_plan_valid(*plan)) { set_error("sd_op_vae_tiles_merge: not a plan of sd_vae_tile_plan"); return SD_ERR_INVALID; }
+    VaeMergeGeom g;
+    const long need = vae_tile_stack(*plan, B, C, &g, nullptr);
+    if (stack_elems < need || ld < plan->out_w) {
+        set_error("sd_op_vae_tiles_merge: `tiles` is smaller than the plan's stack, or ld below the canvas width");
+        return SD_ERR_INVALID;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return launch_or_time(s, iters, ms_per_launch, [&]() {
+        return launch_vae_tile_merge(static_cast<const half_t*>(tiles), static_cast<half_t*>(canvas), ld, g, s);
+    });
 }
 
 }  // extern "C"

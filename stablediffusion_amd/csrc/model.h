@@ -465,6 +465,13 @@ struct VAE {
     int finalize();
     int decode(const half_t* z, half_t* img, int B, int h, int w, hipStream_t stream);
     int encode(const half_t* img, half_t* moments, int B, int H, int W, hipStream_t stream);
+    // diffusers' tiled_decode / tiled_encode (vae_tiles.hip): tiles of one shape run stacked through decode / encode in
+    // chunks of tile_batch images, one gather launch per chunk, one merge launch per canvas
+    int decode_tiled(const half_t* z, half_t* img, int B, int h, int w, int tile_latent, double f, int tile_batch,
+                     hipStream_t stream);
+    int encode_tiled(const half_t* img, half_t* moments, int B, int H, int W, int tile_latent, double f, int tile_batch,
+                     hipStream_t stream);
+    DeviceBuf tile_in, tile_stack;      // a chunk's gathered tiles; every tile's output, for the merge
     // The encoder with every inter-layer activation stored 2^-k times smaller (same function: see run_resnet): the
     // engine's answer to `config.force_upcast` (sd_unified_pipeline.py:1020-1036 runs such VAEs in fp32 around encode
     // because their activations leave fp16's range).  0 = plain fp16 storage.
@@ -502,7 +509,30 @@ struct VAE {
                   GnStatBuf** out_stats, float stream_scale = 1.f);
     int run_decode(Ctx& c, const half_t* z, half_t* img, int B, int h, int w);
     int run_encode(Ctx& c, const half_t* img, half_t* moments, int B, int H, int W, float stream_scale);
+    int run_tiled(bool enc, const sd_vae_tiles& p, const half_t* in, half_t* out, int B, int tile_batch, hipStream_t stream);
 };
+
+// Tiled VAE (vae_tiles.hip).  The plan is sd_vae_tile_plan's (include/sd_engine.h), host only.  vae_tile_stack lays the
+// tiles' outputs out for the merge -- [class][tile, raster order][b][C][th][tw] -- and returns the stack's elements;
+// class_off (optional) takes the offset of each of the plan's classes.
+constexpr int VAE_TILE_MAX_BATCH = 32;
+struct VaeGatherList {          // image i of a gathered chunk: canvas image b[i], tile start (ys[i], xs[i]); by value
+    int b[VAE_TILE_MAX_BATCH];
+    int ys[VAE_TILE_MAX_BATCH];
+    int xs[VAE_TILE_MAX_BATCH];
+};
+struct VaeMergeGeom {           // output space; nfy / nfx = full-size tiles in front on each axis (then at most two more)
+    int Ho, Wo, T, blend, limit, nfy, nfx, B, C;
+    long cls_off[9];            // stack offset of shape class (cy, cx), c = 0 full, 1 + k = k-th tile behind the full ones
+};
+int vae_tile_plan(int encode, int h, int w, int tile_sample, int tile_latent, double f, sd_vae_tiles* out);
+bool vae_tile_plan_valid(const sd_vae_tiles& p);        // p is, field for field, what the plan function builds
+long vae_tile_stack(const sd_vae_tiles& p, int B, int C, VaeMergeGeom* g, long* class_off);
+// stack[i, c, y, x] = canvas[b_i, c, ys_i + y, xs_i + x], canvas [.., C, Hc, .] with row stride ld; n <= VAE_TILE_MAX_BATCH
+int launch_vae_tile_gather(const half_t* canvas, long ld, half_t* stack, const VaeGatherList& l, int n, int C, int Hc,
+                           int th, int tw, hipStream_t s);
+// canvas [B, C, Ho, Wo] (row stride ld) from the raw tiles in `tiles`, every pixel written once (vae_tiles.hip)
+int launch_vae_tile_merge(const half_t* tiles, half_t* canvas, long ld, const VaeMergeGeom& g, hipStream_t s);
 
 // CLIP text encoder (transformers CLIPTextModel / CLIPTextModelWithProjection): the text side of
 // encode_prompt, /root/reference/pipelines/sd_unified_pipeline.py:583-608.

@@ -390,4 +390,61 @@ int VAE::encode(const half_t* img, half_t* moments, int B, int H, int W, hipStre
     });
 }
 
+// The tiles of one shape class, of all B images, form the sequence (tile, b); chunks of tile_batch of it are gathered
+// into tile_in and run through decode / encode, whose output lands at its place in tile_stack; then one merge launch.
+int VAE::run_tiled(bool enc, const sd_vae_tiles& p, const half_t* in, half_t* out, int B, int tile_batch, hipStream_t stream) {
+    const int Cin = enc ? cfg.in_channels : cfg.latent_channels;
+    const int Cout = enc ? 2 * cfg.latent_channels : cfg.out_channels;
+    VaeMergeGeom g;
+    long class_off[SD_VAE_TILE_MAX_CLASSES];
+    const long total = vae_tile_stack(p, B, Cout, &g, class_off);
+    bool grew = false;
+    int rc;
+    const long chunk_in = (long)(tile_batch < p.ny * p.nx * B ? tile_batch : p.ny * p.nx * B) * Cin * p.class_h[0] * p.class_w[0];
+    if ((rc = tile_in.reserve((size_t)chunk_in * sizeof(half_t), &grew))) return rc;
+    if ((rc = tile_stack.reserve((size_t)total * sizeof(half_t), &grew))) return rc;
+    for (int c = 0; c < p.n_classes; ++c) {
+        const int th = p.class_h[c], tw = p.class_w[c];
+        const int oh = enc ? th / p.scale : th * p.scale, ow = enc ? tw / p.scale : tw * p.scale;
+        const int N = p.class_count[c] * B;
+        for (int n0 = 0; n0 < N; n0 += tile_batch) {
+            const int n = N - n0 < tile_batch ? N - n0 : tile_batch;
+            VaeGatherList l = {};
+            for (int i = 0; i < n; ++i) {
+                const int t = (n0 + i) / B;
+                l.b[i] = (n0 + i) % B;
+                l.ys[i] = (p.class_iy0[c] + t / p.class_nx[c]) * p.stride_in;
+                l.xs[i] = (p.class_ix0[c] + t % p.class_nx[c]) * p.stride_in;
+            }
+            if ((rc = launch_vae_tile_gather(in, p.in_w, tile_in.h(), l, n, Cin, p.in_h, th, tw, stream))) return rc;
+            half_t* dst = tile_stack.h() + class_off[c] + (long)n0 * Cout * oh * ow;
+            rc = enc ? encode(tile_in.h(), dst, n, th, tw, stream) : decode(tile_in.h(), dst, n, th, tw, stream);
+            if (rc) return rc;
+        }
+    }
+    return launch_vae_tile_merge(tile_stack.h(), out, p.out_w, g, stream);
+}
+
+int VAE::decode_tiled(const half_t* z, half_t* img, int B, int h, int w, int tile_latent, double f, int tile_batch,
+                      hipStream_t stream) {
+    if (!finalized) { set_error("vae: decode before finalize"); return 2; }
+    if (B <= 0 || tile_batch < 1 || tile_batch > VAE_TILE_MAX_BATCH) { set_error("vae: B >= 1 and tile_batch in 1..32"); return 1; }
+    if (taps.on) { set_error("vae: debug taps do not cover the tiled calls"); return 4; }
+    if (tile_latent < 1) { set_error("vae: tile_latent >= 1"); return 1; }
+    sd_vae_tiles p;
+    if (vae_tile_plan(0, h, w, tile_latent << (cfg.num_blocks - 1), tile_latent, f, &p)) return 1;
+    return run_tiled(false, p, z, img, B, tile_batch, stream);
+}
+
+int VAE::encode_tiled(const half_t* img, half_t* moments, int B, int H, int W, int tile_latent, double f, int tile_batch,
+                      hipStream_t stream) {
+    if (!finalized) { set_error("vae: encode before finalize"); return 2; }
+    if (B <= 0 || tile_batch < 1 || tile_batch > VAE_TILE_MAX_BATCH) { set_error("vae: B >= 1 and tile_batch in 1..32"); return 1; }
+    if (taps.on) { set_error("vae: debug taps do not cover the tiled calls"); return 4; }
+    if (tile_latent < 1) { set_error("vae: tile_latent >= 1"); return 1; }
+    sd_vae_tiles p;
+    if (vae_tile_plan(1, H, W, tile_latent << (cfg.num_blocks - 1), tile_latent, f, &p)) return 1;
+    return run_tiled(true, p, img, moments, B, tile_batch, stream);
+}
+
 }  // namespace sd

@@ -877,6 +877,13 @@ class HipAutoencoderKL:
         self.config = _Config(**config.to_dict())
         self._finalized = False
         self._enc_shift = 0           # sd_vae_encode_range_shift in effect (force_upcast VAEs: raised on overflow)
+        # diffusers' AutoencoderKL tiling state (autoencoder_kl.py __init__; semantics recalled: DESIGN.md section 8)
+        self.use_tiling = False
+        self.use_slicing = False
+        self.tile_sample_min_size = config.sample_size
+        self.tile_latent_min_size = int(config.sample_size / (2 ** (len(config.block_out_channels) - 1)))
+        self.tile_overlap_factor = 0.25
+        self.tile_batch = 4           # images per stacked tile chunk: the batch the benchmark's decode is measured at
 
     def load_state_dict(self, state_dict: Dict[str, torch.Tensor], strict: bool = True):
         _lib.require_gpu()
@@ -907,6 +914,59 @@ class HipAutoencoderKL:
     def eval(self):
         return self
 
+    # -- diffusers' AutoencoderKL switches (enable_tiling / enable_slicing and the three tile attributes, all writable)
+    def enable_tiling(self, use_tiling: bool = True):
+        """Decode / encode canvases larger than one tile as overlapping tiles (diffusers' tiled_decode / tiled_encode;
+        sd_vae_decode_tiled / sd_vae_encode_tiled): the workspace stops growing with the canvas."""
+        self.use_tiling = bool(use_tiling)
+
+    def disable_tiling(self):
+        self.enable_tiling(False)
+
+    def enable_slicing(self):
+        """Decode / encode one image of the batch at a time and concatenate."""
+        self.use_slicing = True
+
+    def disable_slicing(self):
+        self.use_slicing = False
+
+    def memory_tiled(self):
+        """(weight bytes, arena bytes, bytes of the tiled calls' chunk-input and tile-stack buffers)."""
+        w, s, t = C.c_int64(), C.c_int64(), C.c_int64()
+        _lib.check(self._lib.sd_vae_memory_tiled(self._h, C.byref(w), C.byref(s), C.byref(t)), "sd_vae_memory_tiled")
+        return w.value, s.value, t.value
+
+    def _call(self, name: str, src: torch.Tensor, dst: torch.Tensor, *args):
+        """One engine entry `name(handle, src, dst, *args, stream)` on this model's device."""
+        with torch.cuda.device(self.device):
+            rc = getattr(self._lib, name)(self._h, C.c_void_p(src.data_ptr()), C.c_void_p(dst.data_ptr()), *args,
+                                          C.c_void_p(_stream_ptr()))
+        _lib.check(rc, name)
+
+    def _tile_args(self):
+        f = 2 ** (len(self.cfg.block_out_channels) - 1)
+        tl, ts = int(self.tile_latent_min_size), int(self.tile_sample_min_size)
+        if ts != tl * f:
+            raise _lib.EngineError(f"tile_sample_min_size ({ts}) must be tile_latent_min_size ({tl}) times the VAE's scale ({f})")
+        return tl, float(self.tile_overlap_factor), int(self.tile_batch)
+
+    def _run(self, kind: str, src: torch.Tensor, dst: torch.Tensor):
+        """decode / encode `src` into `dst`, routed as diffusers routes: sliced per image when slicing is on and the batch
+        holds more than one, tiled when tiling is on and the canvas exceeds one tile in either direction."""
+        if self.use_slicing and src.shape[0] > 1:
+            for i in range(src.shape[0]):
+                self._run_one(kind, src[i:i + 1], dst[i:i + 1])
+        else:
+            self._run_one(kind, src, dst)
+
+    def _run_one(self, kind: str, src: torch.Tensor, dst: torch.Tensor):
+        B, _, h, w = src.shape
+        tile = self.tile_latent_min_size if kind == "decode" else self.tile_sample_min_size
+        if self.use_tiling and (h > tile or w > tile):
+            self._call(f"sd_vae_{kind}_tiled", src, dst, B, h, w, *self._tile_args())
+        else:
+            self._call(f"sd_vae_{kind}", src, dst, B, h, w)
+
     def decode(self, z, return_dict=False, **unused):
         if not self._finalized:
             raise _lib.EngineError("weights not loaded")
@@ -914,10 +974,7 @@ class HipAutoencoderKL:
         B, _, h, w = z.shape
         f = 2 ** (len(self.cfg.block_out_channels) - 1)
         img = torch.empty((B, self.cfg.out_channels, h * f, w * f), device=self.device, dtype=torch.float16)
-        with torch.cuda.device(self.device):
-            rc = self._lib.sd_vae_decode(self._h, C.c_void_p(z.data_ptr()), C.c_void_p(img.data_ptr()), B, h, w,
-                                         C.c_void_p(_stream_ptr()))
-        _lib.check(rc, "sd_vae_decode")
+        self._run("decode", z, img)
         if return_dict:
             return SimpleNamespace(sample=img)
         return (img,)
@@ -930,25 +987,20 @@ class HipAutoencoderKL:
         f = 2 ** (len(self.cfg.block_out_channels) - 1)
         mom = torch.empty((B, 2 * self.cfg.latent_channels, H // f, W // f), device=self.device,
                           dtype=torch.float16)
-        with torch.cuda.device(self.device):
-            rc = self._lib.sd_vae_encode(self._h, C.c_void_p(x.data_ptr()), C.c_void_p(mom.data_ptr()), B, H, W,
-                                         C.c_void_p(_stream_ptr()))
-        _lib.check(rc, "sd_vae_encode")
+        self._run("encode", x, mom)
         if getattr(self.cfg, "force_upcast", False) and not bool(torch.isfinite(mom).all()):
             # The reference runs the VAE in fp32 around encode when force_upcast is set (sd_unified_pipeline.py:1020-1036:
             # the SDXL VAE's activations leave fp16's range on some images).  The engine's equivalent: the same encoder
             # with every inter-layer activation stored 2^-k times smaller (GroupNorm is scale-invariant, eps scaled
             # along: sd_vae_encode_range_shift), k raised until the moments are finite and kept for the handle's next
-            # calls.  fp32 accumulators and statistics as always; nothing overflows silently.
+            # calls.  fp32 accumulators and statistics as always; nothing overflows silently.  A sliced or tiled encode
+            # is re-run whole -- every image, every tile -- at the raised shift.
             for shift in (4, 8, 12):
                 if shift <= self._enc_shift:
                     continue
                 _lib.check(self._lib.sd_vae_encode_range_shift(self._h, shift), "sd_vae_encode_range_shift")
                 self._enc_shift = shift
-                with torch.cuda.device(self.device):
-                    rc = self._lib.sd_vae_encode(self._h, C.c_void_p(x.data_ptr()), C.c_void_p(mom.data_ptr()), B, H, W,
-                                                 C.c_void_p(_stream_ptr()))
-                _lib.check(rc, "sd_vae_encode")
+                self._run("encode", x, mom)
                 if bool(torch.isfinite(mom).all()):
                     break
             else:

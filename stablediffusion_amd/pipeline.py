@@ -226,6 +226,20 @@ class SDModelWrapper:
         self.base.disable_freeu()
         self._freeu = None
 
+    # ---- tiled / sliced VAE (diffusers pipelines' enable_vae_tiling / enable_vae_slicing: forwarded to the VAE; they
+    #      live below every feature switch of the pipeline and take no call keyword) ----
+    def enable_vae_tiling(self):
+        self.vae.enable_tiling()
+
+    def disable_vae_tiling(self):
+        self.vae.disable_tiling()
+
+    def enable_vae_slicing(self):
+        self.vae.enable_slicing()
+
+    def disable_vae_slicing(self):
+        self.vae.disable_slicing()
+
     # ---- DeepCache (forwarded to the base UNet; the refiner runs plain) ----
     def enable_deepcache(self, cache_interval: int = 3, cache_depth: int = 1):
         self.base.enable_deepcache(cache_interval, cache_depth)
