@@ -307,6 +307,32 @@ int sd_unet_tome_step(sd_unet* u, uint32_t step);
  * prefix), or -SD_ERR_*; it synchronises the device. */
 int sd_unet_tome_sites(const sd_unet* u);
 int sd_unet_tome_read(sd_unet* u, int k, int32_t* info5, int32_t* map_host, int64_t cap);
+/* HyperTile (tfernd/HyperTile, as A1111 / Forge / SD.Next / ComfyUI ship it; scale_depth off): the self-attention of
+ * every BasicTransformerBlock of a level l <= max_depth (its map is Hs x Ws = H >> l x W >> l) is restricted to the
+ * tokens of one spatial tile, and the division nh x nw is drawn anew per step (sd_hypertile_plan with site = the block's
+ * ordinal as for token merging, step = sd_unet_hypertile_step's; tile_size in tokens of the site's own level).  The
+ * draw is the same for every image of the batch and both CFG halves.  Token (y, x) of image b attends to exactly the
+ * tokens of tile (y / th, x / tw) of image b; scale, head split and pre-scaled queries are unchanged.  A site that
+ * draws (1, 1) issues the plain launches and is bit for bit the plain block.  nw == 1 cuts the NHWC rows into contiguous
+ * bands: the attention kernel runs in place with batch B nh, nothing is copied.  Otherwise the q|k|v rows are gathered
+ * into tile order (sd_op_hypertile_gather), the unchanged attention kernel runs with batch B nh nw on th tw tokens and
+ * its output is scattered back (sd_op_hypertile_scatter); the gather buffers are workspace, planned for every site
+ * that can draw nw > 1.  Only attn1 changes: cross-attention, IP-Adapter, regional weights, FreeU, DeepCache and
+ * ControlNet residuals see raster-order rows; a ControlNet's own encoder runs without tiling.  tile_size = 0 means
+ * off: the other arguments are ignored and the forward is again exactly the plain one, with the same launches.
+ * SD_ERR_INVALID: tile_size < 0, swap_size outside 1..8, max_depth outside 0..3.  SD_ERR_UNSUPPORTED, nothing changed:
+ * token merging is on (and sd_unet_set_tome with a ratio > 0 while HyperTile is on): both rewrite attn1's rows.  With
+ * it on the forward returns SD_ERR_UNSUPPORTED, nothing launched, with graph replay on (the division changes per step)
+ * and in sd_unet_forward_pag (the perturbed branch's identity attention). */
+int sd_unet_set_hypertile(sd_unet* u, int tile_size, int swap_size, int max_depth, uint32_t seed);
+/* The step index the division draw of the following forwards hashes (the loop's iteration; 0 until set). */
+int sd_unet_hypertile_step(sd_unet* u, uint32_t step);
+/* The participating sites (level <= max_depth) of the last forward, in execution order: their count, and for the k-th
+ * one info8 = (site, Hs, Ws, nh, nw, images, copied 0/1, level).  images is the batch the block ran on (half of it inside
+ * the shared CFG prefix); copied says whether the gather / scatter launches ran (nw > 1).  SD_ERR_INVALID for a null
+ * argument or k outside [0, sites).  Neither touches the device. */
+int sd_unet_hypertile_sites(const sd_unet* u);
+int sd_unet_hypertile_read(const sd_unet* u, int k, int32_t* info8);
 /* DeepCache (Ma, Fang, Wang, CVPR 2024): reuse the deep features of the UNet across denoising steps.  With
  *   L = layers_per_block, s_0 = conv_in's output, s_j = the output of layer j - 1 of down block 0,
  * layer j of the last up block (j = 0..L) reads cat([hidden, s_{L-j}]).  For a depth d in 1..L the cached feature F_d
@@ -1137,6 +1163,24 @@ int sd_op_tome_merge(const void* src, int64_t lds, int cols, const void* plan, i
                      void* stream);
 int sd_op_tome_unmerge(const void* src, int64_t lds, int cols, const void* plan, int B, int T, void* dst, int64_t ldd,
                        void* stream);
+/* HyperTile, operator by operator (sd_unet_set_hypertile).  One axis of n tokens has the candidate tile extents
+ *   extents = the first swap_size divisors e of n with e >= min(tile_size, n), ascending;  counts[i] = n / extents[i]
+ * (most tiles first; never empty, e = n divides), and a site draws
+ *   nh = counts_h[mix32(seed, step, site, 0) % len(counts_h)],  nw = counts_w[mix32(seed, step, site, 1) % len(counts_w)]
+ * with token merging's mix32 (above).  sd_hypertile_plan: out4 = (nh, nw, th, tw) with th = Hs / nh, tw = Ws / nw.  Needs
+ * no device.  SD_ERR_INVALID: Hs, Ws or tile_size < 1, Hs Ws > 2^24, swap_size outside 1..8, a null out4.
+ *
+ * sd_op_hypertile_gather: all images and tiles of src [B Hs Ws, lds] f16 in one launch,
+ *   dst row ((b nh + ty) nw + tx) th tw + y tw + x  <-  src row (b Hs + ty th + y) Ws + tx tw + x,  columns [0, cols),
+ * a pure copy with 16 bytes per lane.  sd_op_hypertile_scatter: the inverse map (src in tile order, dst in raster
+ * order).  Neither writes a column of dst past `cols` or a row past B Hs Ws.  SD_ERR_INVALID with nothing launched
+ * unless cols % 8 == 0, both row strides % 8 == 0 and >= cols, both pointers 16-byte aligned, Hs % nh == 0,
+ * Ws % nw == 0 and B, nh, nw >= 1. */
+int sd_hypertile_plan(int Hs, int Ws, int tile_size, int swap_size, uint32_t seed, uint32_t step, uint32_t site, int32_t* out4);
+int sd_op_hypertile_gather(const void* src, int64_t lds, int cols, int B, int Hs, int Ws, int nh, int nw, void* dst, int64_t ldd,
+                           void* stream);
+int sd_op_hypertile_scatter(const void* src, int64_t lds, int cols, int B, int Hs, int Ws, int nh, int nw, void* dst, int64_t ldd,
+                            void* stream);
 /* LayerNorm over the last dim of [rows, C] f16. */
 int sd_op_layernorm(const void* x, const void* gamma, const void* beta, void* y, int rows, int C,
                     float eps, void* stream);

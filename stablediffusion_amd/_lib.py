@@ -189,6 +189,10 @@ SIGNATURES = {
     "sd_unet_tome_step": (_I, [_P, C.c_uint32]),
     "sd_unet_tome_sites": (_I, [_P]),
     "sd_unet_tome_read": (_I, [_P, _I, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _I64]),
+    "sd_unet_set_hypertile": (_I, [_P, _I, _I, _I, C.c_uint32]),
+    "sd_unet_hypertile_step": (_I, [_P, C.c_uint32]),
+    "sd_unet_hypertile_sites": (_I, [_P]),
+    "sd_unet_hypertile_read": (_I, [_P, _I, C.POINTER(C.c_int32)]),
     "sd_unet_set_pag_layers": (_I, [_P, _P, _I]),
     "sd_unet_forward_pag": (_I, [_P, _P, _P, _P, _I, _P, _P, _F, _I, _I, _P, _I, _I, _I, _P]),
     "sd_unet_forward_concat": (_I, [_P, _P, _I, _F, _P, _I, _I, _I, _P, _P, _I, _P, _P, _P, _I, _I, _I, _P]),
@@ -333,6 +337,9 @@ SIGNATURES = {
     "sd_op_tome_plan_from_map": (_I, [C.POINTER(C.c_int32), _I, _I, _I, _P, _P]),
     "sd_op_tome_merge": (_I, [_P, _I64, _I, _P, _I, _I, _P, _I64, _P]),
     "sd_op_tome_unmerge": (_I, [_P, _I64, _I, _P, _I, _I, _P, _I64, _P]),
+    "sd_hypertile_plan": (_I, [_I, _I, _I, _I, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32)]),
+    "sd_op_hypertile_gather": (_I, [_P, _I64, _I, _I, _I, _I, _I, _I, _P, _I64, _P]),
+    "sd_op_hypertile_scatter": (_I, [_P, _I64, _I, _I, _I, _I, _I, _I, _P, _I64, _P]),
     "sd_op_layernorm": (_I, [_P, _P, _P, _P, _I, _I, _F, _P]),
     "sd_op_layernorm_ex": (_I, [_P, _I64, _P, _P, _P, _I64, _I64, _I, _F, _P]),
     "sd_op_row_stats": (_I, [_P, _I64, _P, _I64, _I, _P]),

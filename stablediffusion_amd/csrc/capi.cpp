@@ -410,6 +410,28 @@ int sd_unet_tome_read(sd_unet* u, int k, int32_t* info5, int32_t* map_host, int6
         if (tome_plan_read_map(u->impl.tome_buf.data() + t.plan_off, b, T, map_host + (long)b * T)) return -SD_ERR_HIP;
     return t.B;
 }
+int sd_unet_set_hypertile(sd_unet* u, int tile_size, int swap_size, int max_depth, uint32_t seed) {
+    if (!u) { set_error("null handle"); return SD_ERR_INVALID; }
+    if (!u->impl.finalized) { set_error("sd_unet_set_hypertile before finalize"); return SD_ERR_STATE; }
+    return u->impl.set_hypertile(tile_size, swap_size, max_depth, seed);
+}
+int sd_unet_hypertile_step(sd_unet* u, uint32_t step) {
+    if (!u) { set_error("null handle"); return SD_ERR_INVALID; }
+    u->impl.hypertile.step = step;
+    return SD_OK;
+}
+int sd_unet_hypertile_sites(const sd_unet* u) { return u ? (int)u->impl.hypertile_used.size() : 0; }
+int sd_unet_hypertile_read(const sd_unet* u, int k, int32_t* info8) {
+    if (!u || !info8) { set_error("null argument"); return SD_ERR_INVALID; }
+    if (k < 0 || k >= (int)u->impl.hypertile_used.size()) {
+        set_error("sd_unet_hypertile_read: no such HyperTile site in the last forward");
+        return SD_ERR_INVALID;
+    }
+    const HyperTileUsed& t = u->impl.hypertile_used[(size_t)k];
+    info8[0] = t.site; info8[1] = t.H; info8[2] = t.W; info8[3] = t.nh; info8[4] = t.nw; info8[5] = t.B; info8[6] = t.copied;
+    info8[7] = t.level;
+    return SD_OK;
+}
 int sd_unet_set_regions(sd_unet* u, const float* weights, int Bw, int R, int H, int W, void* stream) {
     if (!u) { set_error("null handle"); return SD_ERR_INVALID; }
     return u->impl.set_regions(weights, Bw, R, H, W, static_cast<hipStream_t>(stream));
@@ -1899,6 +1921,24 @@ int sd_op_tome_unmerge(const void* src, int64_t lds, int cols, const void* plan,
                        void* stream) {
     return launch_tome_unmerge(static_cast<const half_t*>(src), lds, cols, plan, B, T, static_cast<half_t*>(dst), ldd,
                                static_cast<hipStream_t>(stream));
+}
+
+int sd_hypertile_plan(int Hs, int Ws, int tile_size, int swap_size, uint32_t seed, uint32_t step, uint32_t site, int32_t* out4) {
+    if (!out4) { set_error("sd_hypertile_plan: null argument"); return SD_ERR_INVALID; }
+    HyperTileGeom g;
+    if (hypertile_plan(Hs, Ws, tile_size, swap_size, seed, step, site, &g)) return SD_ERR_INVALID;
+    out4[0] = g.nh; out4[1] = g.nw; out4[2] = g.th; out4[3] = g.tw;
+    return SD_OK;
+}
+int sd_op_hypertile_gather(const void* src, int64_t lds, int cols, int B, int Hs, int Ws, int nh, int nw, void* dst, int64_t ldd,
+                           void* stream) {
+    return launch_hypertile_gather(static_cast<const half_t*>(src), lds, cols, B, Hs, Ws, nh, nw, static_cast<half_t*>(dst), ldd,
+                                   static_cast<hipStream_t>(stream));
+}
+int sd_op_hypertile_scatter(const void* src, int64_t lds, int cols, int B, int Hs, int Ws, int nh, int nw, void* dst, int64_t ldd,
+                            void* stream) {
+    return launch_hypertile_scatter(static_cast<const half_t*>(src), lds, cols, B, Hs, Ws, nh, nw, static_cast<half_t*>(dst), ldd,
+                                    static_cast<hipStream_t>(stream));
 }
 
 int sd_op_attention(const void* q, const void* k, const void* v, void* out, int B, int Tq, int Tk, int heads, int d,

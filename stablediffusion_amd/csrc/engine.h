@@ -247,6 +247,19 @@ struct TomeRun {
     std::vector<TomeUsed>* used = nullptr;
 };
 
+// HyperTile (UNet::set_hypertile) as one forward sees it: the settings, the sample's size (a site's level is read off its
+// map) and the list of the participating sites (level <= max_depth) of the live pass with the division each drew.
+struct HyperTileUsed {
+    int site = 0, H = 0, W = 0, nh = 1, nw = 1, B = 0, copied = 0, level = 0;
+};
+struct HyperTileRun {
+    int tile_size = 0;                  // 0: off
+    int swap_size = 2, max_depth = 0;
+    uint32_t seed = 0, step = 0;
+    int H0 = 0, W0 = 0;                 // the forward's sample
+    std::vector<HyperTileUsed>* used = nullptr;
+};
+
 // Debug taps (sd_unet_tap / sd_vae_tap): copies of the activation views at block boundaries of ONE forward, for the
 // per-block tests.  Off (Ctx::tap == nullptr, the default) a forward does no tap work at all: no launch, no allocation,
 // the arena plan and the profile are what they are without the facility.  On, the live pass copies each tapped view on
@@ -294,6 +307,8 @@ struct Ctx {
     TapSink* tap = nullptr;             // debug taps of this forward (nullptr: off)
     // token merging of this forward (nullptr: off, and always inside a ControlNet's encoder: tomesd patches the UNet only)
     const TomeRun* tome = nullptr;
+    // HyperTile of this forward (nullptr: off, and always inside a ControlNet's encoder, as token merging)
+    const HyperTileRun* hypertile = nullptr;
     // Regional prompts of this forward (nullptr: off): the handle's weight pyramid (UNet::region_buf) for a
     // region_H x region_W sample, region_R regions in an encoder_hidden_states of region_R * (L / region_R) tokens,
     // weight batch region_Bw.  run_xformer then issues region_xattn_kernel at every attn2 instead of the plain launch.

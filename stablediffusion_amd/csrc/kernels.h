@@ -513,6 +513,12 @@ int launch_views_merge(const half_t* model_out, half_t* eps, const float* wt, in
 // k = 0 or mix32(seed, step, site, cell) % (sx sy); every other token is a source.  r = min(Ns, int(T ratio)) sources, those
 // of largest cosine similarity to their best destination, are merged into it: T' = T - r rows, the unmerged sources in
 // raster order, then the destinations in raster order (a destination row = the mean of itself and its merged sources).
+// The counter hash of every per-step draw (token merging's destination tokens, HyperTile's divisions).
+__host__ __device__ inline uint32_t mix32(uint32_t seed, uint32_t step, uint32_t site, uint32_t cell) {
+    uint32_t h = seed ^ (step * 0x9E3779B9u) ^ (site * 0x85EBCA6Bu) ^ (cell * 0xC2B2AE35u);
+    h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;
+    return h;
+}
 struct TomeGeom {
     int H, W, sx, sy, hsy, wsx, use_rand;
     uint32_t seed, step, site;
@@ -542,6 +548,26 @@ int launch_tome_merge(const half_t* src, long lds, int cols, const void* plan, i
 // dst [B T, ldd] row t <- src [B T', lds] row map[t]: a pure copy of `cols` columns.
 int launch_tome_unmerge(const half_t* src, long lds, int cols, const void* plan, int B, int T, half_t* dst, long ldd,
                         hipStream_t s);
+// HyperTile (hypertile.hip; tfernd/HyperTile): the Hs x Ws map of a self-attention site is cut into nh x nw tiles of
+// th x tw tokens and every token attends to the tokens of its own tile.  Per axis of n tokens the candidate tile extents
+// are the first swap_size divisors e of n with e >= min(tile_size, n), in ascending order; counts[i] = n / e_i (most tiles
+// first, never empty).  nh = counts_h[mix32(seed, step, site, 0) % len], nw = counts_w[mix32(seed, step, site, 1) % len].
+constexpr int kHyperTileMaxSwap = 8;
+struct HyperTileGeom {
+    int Hs, Ws, nh, nw, th, tw;
+};
+// counts [<= 8] of one axis; returns how many (0: n < 1, tile_size < 1 or swap_size outside 1..8).  Host only.
+int hypertile_counts(int n, int tile_size, int swap_size, int* counts);
+// Fills *g with the draw; 1 for arguments hypertile_counts refuses or Hs Ws > 2^24.  Host only, no device.
+int hypertile_plan(int Hs, int Ws, int tile_size, int swap_size, uint32_t seed, uint32_t step, uint32_t site, HyperTileGeom* g);
+// gather: dst row ((b nh + ty) nw + tx) th tw + y tw + x <- src row (b Hs + ty th + y) Ws + tx tw + x over `cols` columns
+// of [B Hs Ws] rows, a pure fp16 copy with 16 bytes per lane in one launch; scatter: the inverse map.  cols % 8 == 0, both
+// row strides % 8 == 0 and >= cols, 16-byte aligned pointers, nh | Hs, nw | Ws, B, nh, nw >= 1: anything else returns 1 with
+// nothing launched.  Columns past `cols` of dst are not written.
+int launch_hypertile_gather(const half_t* src, long lds, int cols, int B, int Hs, int Ws, int nh, int nw, half_t* dst, long ldd,
+                            hipStream_t s);
+int launch_hypertile_scatter(const half_t* src, long lds, int cols, int B, int Hs, int Ws, int nh, int nw, half_t* dst, long ldd,
+                             hipStream_t s);
 // den = dx x + dout m, x <- pden den + pnoise noise (m: model_out, or its CFG combine when rows == 2); noise / denoised
 // nullable.  The scheduler step of LCMScheduler in one launch.
 int launch_lcm_step(const half_t* model_out, int rows, half_t* lat, const half_t* noise, half_t* denoised, long n, float g,

@@ -284,11 +284,13 @@ struct PlanKey {
     int cat_rows = 0;                       // forward_concat: the latents the B images are built from, 0 otherwise
     double tome_ratio = 0.0;                // token merging: what the merged rows per block depend on (0: off)
     int tome_ds = 0, tome_sx = 0, tome_sy = 0;
+    int ht_tile = 0, ht_swap = 0, ht_depth = 0; // HyperTile: what the gather buffers of the sites depend on (0: off)
     bool operator==(const PlanKey& o) const {
         return B == o.B && H == o.H && W == o.W && L == o.L && kv_cache == o.kv_cache && ip_tokens == o.ip_tokens &&
                cfg_share == o.cfg_share && pag_groups == o.pag_groups && pag_late == o.pag_late && n_ctrl == o.n_ctrl &&
                dc_depth == o.dc_depth && cat_rows == o.cat_rows && tome_ratio == o.tome_ratio && tome_ds == o.tome_ds &&
-               tome_sx == o.tome_sx && tome_sy == o.tome_sy;
+               tome_sx == o.tome_sx && tome_sy == o.tome_sy && ht_tile == o.ht_tile && ht_swap == o.ht_swap &&
+               ht_depth == o.ht_depth;
     }
 };
 // What a captured graph depends on (timestep_cond's width is the configuration's: its presence changes the launches).
@@ -426,6 +428,18 @@ struct UNet : Encoder {
     int set_tome(double ratio, int max_downsample, int sx, int sy, int use_rand, uint32_t seed);
     // the blocks that merge for an H x W sample, in execution order of the full forward, with their plan offsets
     int tome_layout(int B, int H, int W, std::vector<TomeUsed>* sites, size_t* bytes);
+
+    // ---- HyperTile (sd_unet_set_hypertile): tile_size 0 = off, the forward as without the feature.  On, attn1 of every
+    // transformer block of a level <= max_depth draws a division nh x nw of its map per step (kernels.h: hypertile_plan)
+    // and attends within the tiles: (1, 1) runs the plain launches; nw == 1 cuts the NHWC rows into contiguous bands, so
+    // the attention runs on qkv / att in place with batch B nh; otherwise the q|k|v rows are gathered into tile order,
+    // the attention runs with batch B nh nw and its output is scattered back (hypertile.hip).  The gather buffers are
+    // arena scratch, planned for every site that has a candidate nw > 1, whatever a step draws.  Not together with token
+    // merging (both rewrite attn1's rows), not under graphs (the division changes per step), not in forward_pag; a
+    // ControlNet's encoder runs without it.
+    HyperTileRun hypertile;
+    std::vector<HyperTileUsed> hypertile_used;  // the participating sites of the last forward, in execution order
+    int set_hypertile(int tile_size, int swap_size, int max_depth, uint32_t seed);
 
     // ---- regional prompts (sd_unet_set_regions): region_R = 0 is off, the forward as without the feature.  On, every
     // attn2 of forward / forward_cfg runs region_xattn_kernel on the R segments of an encoder_hidden_states of R * L

@@ -43,14 +43,9 @@ __host__ __device__ inline long tome_o_rn(int T) { return 4L * T + 1; }
 __host__ __device__ inline long tome_o_nmax(int T) { return 5L * T + 1; }
 __host__ __device__ inline long tome_o_nidx(int T) { return 6L * T + 1; }
 
-__host__ __device__ inline uint32_t tome_mix32(uint32_t seed, uint32_t step, uint32_t site, uint32_t cell) {
-    uint32_t h = seed ^ (step * 0x9E3779B9u) ^ (site * 0x85EBCA6Bu) ^ (cell * 0xC2B2AE35u);
-    h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;
-    return h;
-}
 // the destination token of cell (cy, cx)
 __host__ __device__ inline int tome_dst_token(const TomeGeom& g, int cy, int cx) {
-    const int k = g.use_rand ? (int)(tome_mix32(g.seed, g.step, g.site, (uint32_t)(cy * g.wsx + cx)) % (uint32_t)(g.sx * g.sy)) : 0;
+    const int k = g.use_rand ? (int)(mix32(g.seed, g.step, g.site, (uint32_t)(cy * g.wsx + cx)) % (uint32_t)(g.sx * g.sy)) : 0;
     return (cy * g.sy + k / g.sx) * g.W + cx * g.sx + k % g.sx;
 }
 }  // namespace

@@ -540,6 +540,24 @@ void run_resnet(Ctx& c, const Resnet& r, View x, int N, int H, int W, View out, 
     a.release(mk);
 }
 
+// Does block `bi` of `t`, on an H x W map, take part in HyperTile in this forward?  Then *u holds its site, level and this
+// step's division, and u->copied whether any candidate division has nw > 1 (the site's gather buffers are then planned).
+static bool hypertile_site(const Ctx& c, const Xformer& t, int bi, int H, int W, HyperTileUsed* u) {
+    const HyperTileRun* hr = c.hypertile;
+    if (!hr || hr->tile_size <= 0) return false;
+    int lvl = 0;
+    while ((hr->H0 >> lvl) > H) ++lvl;
+    if ((hr->H0 >> lvl) != H || (hr->W0 >> lvl) != W || lvl > hr->max_depth) return false;
+    HyperTileGeom g;
+    const int site = t.tome_site0 + bi;
+    if (hypertile_plan(H, W, hr->tile_size, hr->swap_size, hr->seed, hr->step, (uint32_t)site, &g)) return false;
+    int cw[kHyperTileMaxSwap];
+    const int kw = hypertile_counts(W, hr->tile_size, hr->swap_size, cw);
+    u->site = site; u->H = H; u->W = W; u->nh = g.nh; u->nw = g.nw; u->level = lvl;
+    u->copied = kw > 1 || cw[0] > 1;
+    return true;
+}
+
 void run_xformer(Ctx& c, const Xformer& t, View x, int N, int H, int W, View out, int G, View text_kv, int L,
                  const GnStatBuf* x_stats, const GnOut& out_stats, const CfgShare* share) {
     Arena& a = *c.arena;
@@ -590,6 +608,7 @@ void run_xformer(Ctx& c, const Xformer& t, View x, int N, int H, int W, View out
         View att(a.alloc_h(M * C), C, C);
         View t2(a.alloc_h(M * C), C, C);
         const int tsite = t.tome_site0 + (int)bi;
+        HyperTileUsed ht;
         const long tome_off = c.tome && !perturb && tsite < (int)c.tome->plan_off.size() ? c.tome->plan_off[(size_t)tsite] : -1;
         if (tome_off >= 0) {
             // Token merging: the match reads the residual stream norm1 reads; the projections are linear, so the mean of
@@ -627,6 +646,35 @@ void run_xformer(Ctx& c, const Xformer& t, View x, int N, int H, int W, View out
                 prof_open(c.stream, "tome_unmerge_kernel", 0.0, 4.0 * Mp * C);
                 c.err = launch_tome_unmerge(am.p, am.ld, C, plan, Np, T, att.p, att.ld, c.stream);
                 prof_close(c.stream);
+            }
+            op_conv(c, b.out1, att, Np, H, W, t2, conv_res(cur, f_t2));
+        } else if (!perturb && hypertile_site(c, t, (int)bi, H, W, &ht)) {
+            // HyperTile: attention within the tiles of this step's division; every other launch of the block is row-wise
+            // and stays in raster order.  (ht.copied says whether a candidate nw > 1 exists: then the gather buffers are
+            // planned, whatever this step drew.)
+            const bool plan_copy = ht.copied != 0;
+            ht.copied = ht.nw > 1;
+            ht.B = Np;
+            View qg(plan_copy ? a.alloc_h(M * 3 * C) : nullptr, 3 * C, 3 * C), ag(plan_copy ? a.alloc_h(M * C) : nullptr, C, C);
+            if (!c.dry && !c.err && c.hypertile->used) c.hypertile->used->push_back(ht);
+            if (ht.nw == 1) {
+                // horizontal bands (the whole map when nh == 1: the plain launch): contiguous row ranges, nothing to copy
+                op_attention(c, qkv.slice(0, C), qkv.slice(C, C), qkv.slice(2 * C, C), att, Np * ht.nh, T / ht.nh, T / ht.nh,
+                             t.heads, d, 0, 1);
+            } else {
+                if (!c.dry && !c.err) {
+                    prof_open(c.stream, "hypertile_gather_kernel", 0.0, 2.0 * Mp * 3 * C * 2);
+                    c.err = launch_hypertile_gather(qkv.p, qkv.ld, 3 * C, Np, H, W, ht.nh, ht.nw, qg.p, qg.ld, c.stream);
+                    prof_close(c.stream);
+                }
+                const int tt = T / (ht.nh * ht.nw);
+                op_attention(c, qg.slice(0, C), qg.slice(C, C), qg.slice(2 * C, C), ag, Np * ht.nh * ht.nw, tt, tt, t.heads, d,
+                             0, 1);
+                if (!c.dry && !c.err) {
+                    prof_open(c.stream, "hypertile_scatter_kernel", 0.0, 2.0 * Mp * C * 2);
+                    c.err = launch_hypertile_scatter(ag.p, ag.ld, C, Np, H, W, ht.nh, ht.nw, att.p, att.ld, c.stream);
+                    prof_close(c.stream);
+                }
             }
             op_conv(c, b.out1, att, Np, H, W, t2, conv_res(cur, f_t2));
         } else if (!perturb) {
@@ -1208,8 +1256,11 @@ int UNet::run(Ctx& c, const UNetCall& call, int dc) {
         c.tap = nullptr;
         const TomeRun* const tome_run = c.tome;     // (and they run without token merging)
         c.tome = nullptr;
+        const HyperTileRun* const ht_run = c.hypertile;
+        c.hypertile = nullptr;
         if (int rc = run_controlnet(c, call, cn_sites, cn_mid)) return rc;
         c.tome = tome_run;
+        c.hypertile = ht_run;
         c.tap = tap;
         for (int i = 0; i < Ctx::kGnPool; ++i) c.gnpool[i] = ring[i];
         c.gn_next = ring_next; c.gn_groups = ring_groups;
@@ -1610,6 +1661,16 @@ int UNet::forward(const UNetCall& in, hipStream_t stream) {
         tome_used.clear();
         tome.used = &tome_used;
     }
+    // HyperTile: refused before anything is launched where the division cannot change per step or attn1 is not an attention
+    const bool ht_on = hypertile.tile_size > 0;
+    if (ht_on) {
+        if (tome_on) { set_error("unet: HyperTile with token merging enabled is not supported"); return 4; }
+        if (graph_enabled) { set_error("unet: graph replay with HyperTile enabled is not supported"); return 4; }
+        if (pag) { set_error("unet: forward_pag with HyperTile enabled is not supported"); return 4; }
+        hypertile.H0 = H; hypertile.W0 = W;
+        hypertile_used.clear();
+        hypertile.used = &hypertile_used;
+    }
     const int dc = dc_mode;
     if (dc != SD_DC_PLAIN) {
         if (dc_depth <= 0) { set_error("unet: DeepCache store / reuse mode while the depth is 0"); return 2; }
@@ -1653,6 +1714,7 @@ int UNet::forward(const UNetCall& in, hipStream_t stream) {
     key.dc_depth = dc != SD_DC_PLAIN ? dc_depth : 0;
     key.cat_rows = call.extra ? call.lat_rows : 0;
     if (tome_on) { key.tome_ratio = tome.ratio; key.tome_ds = tome_max_ds; key.tome_sx = tome.sx; key.tome_sy = tome.sy; }
+    if (ht_on) { key.ht_tile = hypertile.tile_size; key.ht_swap = hypertile.swap_size; key.ht_depth = hypertile.max_depth; }
     if (taps.on) taps.clear();              // one forward's records at a time
     if (region_R && region_stale) {
         // the level weights were overwritten (sd_unet_poison_workspace): rebuild them from the kept copy
@@ -1665,6 +1727,7 @@ int UNet::forward(const UNetCall& in, hipStream_t stream) {
     const int rc = plan_and_run(arena, stream, planned[dc], key, "unet", [&](Ctx& c) {
         c.tap = taps.on ? &taps : nullptr;
         c.tome = tome_on ? &tome : nullptr;
+        c.hypertile = ht_on ? &hypertile : nullptr;
         if (region_R) {
             c.region_w = reinterpret_cast<const float*>(region_buf.data());
             c.region_R = region_R; c.region_Bw = region_Bw; c.region_H = region_H; c.region_W = region_W;
@@ -1756,6 +1819,7 @@ int UNet::set_tome(double ratio, int max_downsample, int sx, int sy, int use_ran
         tome_used.clear();
         return tome_buf.release();
     }
+    if (hypertile.tile_size > 0) { set_error("unet: token merging while HyperTile is on is not supported (both rewrite attn1's rows)"); return 4; }
     if (sx < 1 || sx > 8 || sy < 1 || sy > 8) { set_error("unet: token merging cell sizes sx, sy must be in 1..8"); return 1; }
     if (max_downsample != 1 && max_downsample != 2 && max_downsample != 4 && max_downsample != 8) {
         set_error("unet: token merging max_downsample must be 1, 2, 4 or 8");
@@ -1765,6 +1829,23 @@ int UNet::set_tome(double ratio, int max_downsample, int sx, int sy, int use_ran
     tome.ratio = ratio; tome.sx = sx; tome.sy = sy; tome.use_rand = use_rand ? 1 : 0; tome.seed = seed;
     tome_max_ds = max_downsample;
     tome_used.clear();
+    return 0;
+}
+
+int UNet::set_hypertile(int tile_size, int swap_size, int max_depth, uint32_t seed) {
+    if (tile_size < 0) { set_error("unet: HyperTile tile_size must be >= 0 (0: off)"); return 1; }
+    if (tile_size == 0) {
+        dc_tag.clear();                 // (a DeepCache feature stored under other settings is stale)
+        hypertile.tile_size = 0;
+        hypertile_used.clear();
+        return 0;
+    }
+    if (swap_size < 1 || swap_size > kHyperTileMaxSwap) { set_error("unet: HyperTile swap_size must be in 1..8"); return 1; }
+    if (max_depth < 0 || max_depth > 3) { set_error("unet: HyperTile max_depth must be in 0..3"); return 1; }
+    if (tome.ratio > 0.0) { set_error("unet: HyperTile while token merging is on is not supported (both rewrite attn1's rows)"); return 4; }
+    dc_tag.clear();
+    hypertile.tile_size = tile_size; hypertile.swap_size = swap_size; hypertile.max_depth = max_depth; hypertile.seed = seed;
+    hypertile_used.clear();
     return 0;
 }
 

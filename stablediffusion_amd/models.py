@@ -168,6 +168,7 @@ class HipUNet2DConditionModel:
         self._deepcache = None         # (cache_interval, cache_depth) while DeepCache is on (enable_deepcache)
         self._pag = ()                 # site keys of the perturbed transformers (set_pag_layers)
         self._tome = None              # (ratio, max_downsample, sx, sy, use_rand, seed) while token merging is on
+        self._hypertile = None         # (tile_size, swap_size, max_depth, seed) while HyperTile is on
         self._regions = None           # (Bw, R, H, W) while regional prompts are set (set_regions)
 
     # -- weights -------------------------------------------------------------------------------
@@ -191,6 +192,8 @@ class HipUNet2DConditionModel:
             new.set_pag_layers(self._pag)
         if self._tome is not None:           # and token merging
             new.enable_tome(*self._tome)
+        if getattr(self, "_hypertile", None) is not None:    # and HyperTile
+            new.enable_hypertile(*self._hypertile)
         return new
 
     def rebuild_factory(self):
@@ -307,6 +310,47 @@ class HipUNet2DConditionModel:
         _lib.check(self._lib.sd_unet_set_tome(self._h, 0.0, 1, 2, 2, 0, 0), "sd_unet_set_tome")
         self._tome = None
         return self
+
+    def enable_hypertile(self, tile_size: int = 32, swap_size: int = 2, max_depth: int = 0, seed: int = 0):
+        """HyperTile: the self-attention of every transformer block of a level <= `max_depth` attends within the tiles
+        of a division of its map that is drawn anew per step (stablediffusion_amd.hypertile.plan; `tile_size` in tokens
+        of the block's own level, `swap_size` candidates per axis).  Lossy and opt-in.  The settings survive `rebuild`.
+        Not together with token merging, not under `use_graph`, not in `forward_pag` (EngineError, SD_ERR_UNSUPPORTED)."""
+        for name, v, lo, hi in (("tile_size", tile_size, 1, 2 ** 31 - 1), ("swap_size", swap_size, 1, 8),
+                                ("max_depth", max_depth, 0, 3), ("seed", seed, 0, 2 ** 32 - 1)):
+            if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+                raise ValueError(f"enable_hypertile: {name} must be an int in [{lo}, {hi}], got {v!r}")
+        vals = (int(tile_size), int(swap_size), int(max_depth), int(seed))
+        _lib.check(self._lib.sd_unet_set_hypertile(self._h, *vals), "sd_unet_set_hypertile")
+        self._hypertile = vals
+        return self
+
+    def disable_hypertile(self):
+        """The forward is again exactly the plain one."""
+        _lib.check(self._lib.sd_unet_set_hypertile(self._h, 0, 1, 0, 0), "sd_unet_set_hypertile")
+        self._hypertile = None
+        return self
+
+    @property
+    def hypertile(self):
+        """(tile_size, swap_size, max_depth, seed) while HyperTile is on, else None."""
+        return self._hypertile
+
+    def hypertile_step(self, i: int):
+        """The denoising iteration the division draw of the following forwards hashes (the pipeline's loop calls it)."""
+        _lib.check(self._lib.sd_unet_hypertile_step(self._h, int(i) & 0xFFFFFFFF), "sd_unet_hypertile_step")
+        return self
+
+    def hypertile_sites(self):
+        """The self-attention sites HyperTile covered in the last forward, in execution order: dicts with site, H, W,
+        nh, nw, images, copied (the gather / scatter launches ran) and level."""
+        out = []
+        for k in range(self._lib.sd_unet_hypertile_sites(self._h)):
+            info = (C.c_int32 * 8)()
+            _lib.check(self._lib.sd_unet_hypertile_read(self._h, k, info), "sd_unet_hypertile_read")
+            out.append(dict(site=info[0], H=info[1], W=info[2], nh=info[3], nw=info[4], images=info[5],
+                            copied=bool(info[6]), level=info[7]))
+        return out
 
     def set_regions(self, weights):
         """Regional prompts (stablediffusion_amd.regions): weights [Bw, R, H, W] at the sample's latent size, one row per

@@ -169,11 +169,14 @@ class SDModelWrapper:
         freeu = getattr(old, "_freeu", self._freeu)     # the engine's own record wins: enable_freeu may be called on .base
         deepcache = getattr(old, "deepcache", self._deepcache)
         tome = getattr(old, "tome", None)
+        hypertile = getattr(old, "hypertile", None)
         self.base = None                     # the old engine's device memory goes before the new one is packed
         del old
         self.base = self._rebuild_from(fused, graph, freeu, deepcache, self._pag)
         if tome is not None:                 # token merging survives the re-fuse too
             self.base.enable_tome(*tome)
+        if hypertile is not None:            # and HyperTile
+            self.base.enable_hypertile(*hypertile)
         for part in ("text_encoder", "text_encoder_2"):
             if self._te_sd[part] is not None and (self._lora.touches(part) or self._lora_applied is not None):
                 enc = getattr(self, part, None)
@@ -256,6 +259,17 @@ class SDModelWrapper:
 
     def disable_tome(self):
         self.base.disable_tome()
+
+    # ---- HyperTile (forwarded to the base UNet, and to the refiner when one is loaded) ----
+    def enable_hypertile(self, tile_size: int = 32, swap_size: int = 2, max_depth: int = 0, seed: int = 0):
+        self.base.enable_hypertile(tile_size, swap_size, max_depth, seed)
+        if self.refiner is not None and hasattr(self.refiner, "enable_hypertile"):
+            self.refiner.enable_hypertile(tile_size, swap_size, max_depth, seed)
+
+    def disable_hypertile(self):
+        self.base.disable_hypertile()
+        if self.refiner is not None and hasattr(self.refiner, "disable_hypertile"):
+            self.refiner.disable_hypertile()
 
     # ---- ControlNet (diffusers ControlNetModel, one per model; the pipeline takes control_image=) ----
     def _attach_cn(self, base):
@@ -871,6 +885,7 @@ class StableDiffusionUnifiedPipeline:
         # that feature otherwise.  The mode is engine state, set in front of every forward whichever path the step takes
         deepcache = getattr(unet, "deepcache", None)
         tome_on = getattr(unet, "tome", None) is not None and hasattr(unet, "tome_step")
+        hypertile_on = getattr(unet, "hypertile", None) is not None and hasattr(unet, "hypertile_step")
         kv_cache = getattr(unet, "text_kv_cache", None)
         if kv_cache is not None:
             # the cache is keyed by the buffer's address: hand the engine ONE fp16 contiguous tensor for the whole loop
@@ -934,6 +949,8 @@ class StableDiffusionUnifiedPipeline:
                     unet.deep_cache_mode(_DC_STORE if i % deepcache[0] == 0 else _DC_REUSE)
                 if tome_on:
                     unet.tome_step(i)        # the iteration token merging's destination draw hashes
+                if hypertile_on:
+                    unet.hypertile_step(i)   # and the one HyperTile's division draw hashes
                 # the step's noise, drawn before the forward.  The affine schedulers that add noise draw it as their `step`
                 # does: from the global generator, once per step (the last included, whose noise coefficient is 0), so the
                 # device and the host loop consume the same stream
