@@ -199,6 +199,12 @@ int sd_unet_set_ip_adapter_scale(sd_unet* u, float scale);
 /* Attach a ControlNet created for this UNet (sd_controlnet_create; NULL detaches: the forward is again exactly the
  * plain one).  One ControlNet per UNet; attaching it to another UNet detaches it from the first. */
 int sd_unet_set_controlnet(sd_unet* u, sd_controlnet* cn);
+/* MultiControlNet (diffusers 0.27.2 MultiControlNetModel): attach `count` <= SD_MAX_CONTROLNETS ControlNets, each created
+ * for this UNet and finalized, none twice (SD_ERR_INVALID / SD_ERR_STATE, nothing changed); count == 0 detaches all.  The
+ * list replaces whatever was attached, and sd_unet_set_controlnet replaces a list by its one net (or none); a net attached
+ * to another UNet is detached there.  Everything that rejects an attached ControlNet rejects a list the same way. */
+#define SD_MAX_CONTROLNETS 4
+int sd_unet_set_controlnets(sd_unet* u, sd_controlnet* const* cns, int count);
 /* sd_unet_forward_ex with ControlNet conditioning (diffusers 0.27.2 ControlNetModel feeding
  * down_block_additional_residuals / mid_block_additional_residual):
  *   control_image [n_ctrl,3,8H,8W] f16 in [0, 1]   sample b is conditioned on image b mod n_ctrl (n_ctrl divides B)
@@ -212,6 +218,27 @@ int sd_unet_forward_cn(sd_unet* u, const void* sample, const float* timesteps, c
                        const void* add_text, const float* add_time_ids, const void* image_embeds, int n_img,
                        const void* control_image, int n_ctrl, float cond_scale, void* out, int B, int H, int W,
                        void* stream);
+/* sd_unet_forward_cn for the attached list: control_images[i] [n_ctrl[i],3,8H,8W] f16 and cond_scales[i] belong to net i
+ * of sd_unet_set_controlnets; n_nets must equal the attached count (SD_ERR_INVALID).  A net at scale 0 does not run and
+ * its image may be NULL; with every scale 0 (or no net attached and n_nets == 0) the call is the plain forward; with one
+ * running net it is sd_unet_forward_cn with that net attached alone, bit for bit.  Two or more running nets: every
+ * residual site's hidden tensors lie side by side in one buffer [rows, n C] and the sum of the residuals
+ *   y += sum_i s_i (h_i W_i^T + b_i) = [h_1 | ... | h_n] [s_1 W_1 | ... | s_n W_n]^T + sum_i s_i b_i
+ * is one GEMM per site on weights folded by cn_fold_scales_kernel (one launch for all sites, w_cat = fp16(w * s): one
+ * rounding), refolded only when the running nets or a scale change -- or, with the K-concatenated form switched off
+ * (sd_cn_kcat_force, SD_NO_CN_KCAT=1), one GEMM per net and site.  SD_ERR_INVALID, nothing launched: a NULL image or an
+ * n_ctrl that does not divide B for a running net, a NaN scale.  sd_unet_forward_cn (and every other forward) with more
+ * than one net attached is SD_ERR_INVALID.  The caches of sd_unet_forward_cn hold per net. */
+int sd_unet_forward_mcn(sd_unet* u, const void* sample, const float* timesteps, const void* ehs, int ehs_len,
+                        const void* add_text, const float* add_time_ids, const void* image_embeds, int n_img,
+                        const void* const* control_images, const int* n_ctrl, const float* cond_scales, int n_nets,
+                        void* out, int B, int H, int W, void* stream);
+/* Fold launches (cn_fold_scales_kernel) this UNet has issued since its creation. */
+int64_t sd_unet_cn_fold_count(const sd_unet* u);
+/* How two or more running ControlNets add their residuals, process-wide (tests / tools): -1 the default, 0 chained (one
+ * GEMM per net and site), 1 K-concatenated (one GEMM per site on the folded weights).  SD_NO_CN_KCAT=1 in the
+ * environment makes the default the chained form. */
+int sd_cn_kcat_force(int mode);
 /* The UNet forward of one classifier-free-guidance step from the UN-duplicated latents: what
  * sd_cfg_duplicate(latents, in_scale) followed by sd_unet_forward(_ex) returns, negative half first.
  *   latents   [B,C,H,W] f16        timesteps [B] f32 (both halves share them)
@@ -1267,6 +1294,29 @@ typedef struct sd_cn_problem {
 } sd_cn_problem;
 int sd_op_controlnet_residuals(const sd_cn_problem* problems, int count, float scale, int mode, int iters,
                                float* ms_per_launch, void* stream);
+/* The MultiControlNet fold alone: w[i] [C, C] f16 and bias[i] [C] f32 (DEVICE pointers in HOST arrays of n entries),
+ * scales [n] (host) -> w_cat [C, n C] f16 with w_cat[o, i C + k] = fp16(float(w_i[o, k]) * scales[i]) and b_cat [C] f32 =
+ * sum_i scales[i] bias_i in fp32, net order.  Packed as the forward packs a zero-conv and folded by the launch the
+ * forward issues.  1 <= n <= 4, C % 64 == 0 (SD_ERR_INVALID); outputs 16-byte aligned.  iters > 0 times the fold launch. */
+int sd_op_cn_fold_scales(const void* const* w, const float* const* bias, const float* scales, int n, int C, void* w_cat,
+                         float* b_cat, int iters, float* ms_per_launch, void* stream);
+/* The residual stage of n ControlNets: for every problem y[m, :C] += sum_i scales[i] (x_i[m, :] w_i^T + bias_i) in place
+ * (y's columns past C are left alone).
+ *   mode 0: chained, one GEMM per net with its scale and the residual in the epilogue (a net at scale 0 is skipped);
+ *   mode 1: the weights folded by one grouped launch (sd_op_cn_fold_scales' kernel), then one GEMM with K = n C per
+ *           problem; the sources must be neighbouring column slices of one buffer (x[i] = x[0] + i C, equal ldx).
+ * C % 64 == 0, 1 <= count <= 16, 1 <= n <= 4, x 16-byte aligned with ldx % 8 == 0 (SD_ERR_INVALID).  iters > 0
+ * (timing; synchronises): ms_per_launch[0] = one application of the mode's GEMMs, and in mode 1 ms_per_launch[1] = the
+ * grouped fold launch over all problems (ms_per_launch holds two floats). */
+typedef struct sd_cn_multi_problem {
+    const void* x[SD_MAX_CONTROLNETS]; int64_t ldx[SD_MAX_CONTROLNETS];
+    const void* w[SD_MAX_CONTROLNETS];
+    const float* bias[SD_MAX_CONTROLNETS];
+    void* y; int64_t ldy;
+    int M, C;
+} sd_cn_multi_problem;
+int sd_op_controlnet_residuals_multi(const sd_cn_multi_problem* problems, int count, const float* scales, int n, int mode,
+                                     int iters, float* ms_per_launch, void* stream);
 /* The ControlNet's conditioning embedding: image [n,3,8H,8W] f16 -> out [n,H,W,block_out_channels[0]] f16 (NHWC).
  * iters > 0 (timing; synchronises): *ms_per_launch = one embedding, averaged over `iters` runs. */
 int sd_op_controlnet_cond_embed(sd_controlnet* cn, const void* image, int n, int H, int W, void* out, int iters,

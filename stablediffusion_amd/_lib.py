@@ -139,6 +139,16 @@ class SdCnProblem(C.Structure):
                 ("y", C.c_void_p), ("ldy", C.c_int64), ("M", C.c_int), ("C", C.c_int)]
 
 
+SD_MAX_CONTROLNETS = 4
+
+
+class SdCnMultiProblem(C.Structure):
+    """One residual site of sd_op_controlnet_residuals_multi: up to four sources, weights and biases onto one y."""
+    _fields_ = [("x", C.c_void_p * SD_MAX_CONTROLNETS), ("ldx", C.c_int64 * SD_MAX_CONTROLNETS),
+                ("w", C.c_void_p * SD_MAX_CONTROLNETS), ("bias", C.c_void_p * SD_MAX_CONTROLNETS),
+                ("y", C.c_void_p), ("ldy", C.c_int64), ("M", C.c_int), ("C", C.c_int)]
+
+
 class SdStepPlan(C.Structure):
     """One scheduler step for sd_sched_affine_step: rows of float64 coefficients over (x, m, z, h_0 .. h_3)."""
     _fields_ = [("n_slots", C.c_int32), ("n_writes", C.c_int32), ("write_slot", C.c_int32 * SD_STEP_MAX_WRITES),
@@ -210,6 +220,11 @@ SIGNATURES = {
     "sd_ip_adapter_finalize": (_I, [_P]),
     "sd_unet_set_controlnet": (_I, [_P, _P]),
     "sd_unet_forward_cn": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _I, _P, _I, _F, _P, _I, _I, _I, _P]),
+    "sd_unet_set_controlnets": (_I, [_P, C.POINTER(_P), _I]),
+    "sd_unet_forward_mcn": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _I, C.POINTER(_P), C.POINTER(_I), C.POINTER(_F), _I, _P, _I,
+                                _I, _I, _P]),
+    "sd_unet_cn_fold_count": (_I64, [_P]),
+    "sd_cn_kcat_force": (_I, [_I]),
     "sd_controlnet_create": (_I, [_P, C.POINTER(SdUNetConfig), _I, C.POINTER(_P)]),
     "sd_controlnet_destroy": (_I, [_P]),
     "sd_controlnet_num_weights": (_I, [_P]),
@@ -353,6 +368,8 @@ SIGNATURES = {
     "sd_op_resampler_attention": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I,
                                        C.POINTER(_F), _P]),
     "sd_op_controlnet_residuals": (_I, [C.POINTER(SdCnProblem), _I, _F, _I, _I, C.POINTER(_F), _P]),
+    "sd_op_cn_fold_scales": (_I, [C.POINTER(_P), C.POINTER(_P), C.POINTER(_F), _I, _I, _P, _P, _I, C.POINTER(_F), _P]),
+    "sd_op_controlnet_residuals_multi": (_I, [C.POINTER(SdCnMultiProblem), _I, C.POINTER(_F), _I, _I, _I, C.POINTER(_F), _P]),
     "sd_op_controlnet_cond_embed": (_I, [_P, _P, _I, _I, _I, _P, _I, C.POINTER(_F), _P]),
 }
 

@@ -195,3 +195,41 @@ def load(path_or_dict: Union[str, os.PathLike, Dict], unet_cfg: UNetConfig) -> T
         cfg = infer_config(sd, unet_cfg)
     check_state_dict(sd, cfg)
     return cfg, sd
+
+
+def _per_net(v, n, name):
+    if isinstance(v, (list, tuple)):
+        if len(v) != n:
+            raise ValueError(f"{name}: {len(v)} entries for {n} ControlNet{'s' if n != 1 else ''}")
+        return [float(x) for x in v]
+    return [float(v)] * n
+
+
+def keep_schedule(n_steps, scales, starts=0.0, ends=1.0):
+    """The conditioning scales of a denoising loop, one row of per-net scales per step (diffusers' controlnet_keep times
+    the scale): scale_i * (1 - float(step / n < start_i or (step + 1) / n > end_i)).  Lists give one entry per net;
+    floats broadcast to the net count (one net when all three are floats)."""
+    n_nets = max([len(v) for v in (scales, starts, ends) if isinstance(v, (list, tuple))], default=1)
+    sc, st, en = (_per_net(v, n_nets, k) for v, k in ((scales, "controlnet_conditioning_scale"),
+                                                      (starts, "control_guidance_start"), (ends, "control_guidance_end")))
+    n = int(n_steps)
+    return [[s * (1.0 - float(i / n < a or (i + 1) / n > b)) for s, a, b in zip(sc, st, en)] for i in range(n)]
+
+
+def list_arguments(n_nets, control_image, scales, starts, ends):
+    """The argument checks of a call with `n_nets` ControlNets loaded as a list (ValueError, before anything runs):
+    control_image a non-empty list with one entry per net; scale and guidance window floats or lists of the net count,
+    every window 0 <= start < end <= 1.  Returns (scales, starts, ends) as lists of n_nets floats."""
+    if not isinstance(control_image, (list, tuple)):
+        raise ValueError(f"{n_nets} ControlNets are loaded: control_image must be a list with one entry per net")
+    if len(control_image) == 0:
+        raise ValueError("control_image is an empty list")
+    if len(control_image) != n_nets:
+        raise ValueError(f"control_image: {len(control_image)} entries for {n_nets} ControlNets")
+    sc = _per_net(scales, n_nets, "controlnet_conditioning_scale")
+    st = _per_net(starts, n_nets, "control_guidance_start")
+    en = _per_net(ends, n_nets, "control_guidance_end")
+    for a, b in zip(st, en):
+        if not 0.0 <= a < b <= 1.0:
+            raise ValueError("need 0 <= control_guidance_start < control_guidance_end <= 1")
+    return sc, st, en

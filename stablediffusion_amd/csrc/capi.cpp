@@ -246,8 +246,7 @@ int sd_unet_text_kv_cache(sd_unet* u, int enable) {
     u->impl.kv_cache_on = enable != 0;
     u->impl.kv_tag.clear();             // every call invalidates: the next forward recomputes
     u->impl.ipkv_tag.clear();           // (the IP-Adapter's image K / V alike)
-    u->impl.cond_tag.clear();           // (and the ControlNet's conditioning embedding and text K / V)
-    u->impl.cnkv_tag.clear();
+    u->impl.clear_cn_tags();            // (and every ControlNet's conditioning embedding and text K / V)
     return SD_OK;
 }
 int sd_unet_forward_ex(sd_unet* u, const void* sample, const float* timesteps, const void* ehs, int ehs_len,
@@ -295,10 +294,52 @@ int sd_unet_set_controlnet(sd_unet* u, sd_controlnet* cn) {
         std::string why;
         if (!controlnet_fits(u->impl.cfg, cn->impl.cfg, &why)) { set_error("sd_unet_set_controlnet: " + why); return SD_ERR_INVALID; }
     }
-    u->impl.set_controlnet(cn ? &cn->impl : nullptr);
+    if (int rc = u->impl.set_controlnet(cn ? &cn->impl : nullptr)) return rc;
     u->impl.dc_tag.clear();
     return SD_OK;
 }
+int sd_unet_set_controlnets(sd_unet* u, sd_controlnet* const* cns, int count) {
+    if (!u || (count > 0 && !cns)) { set_error("null argument"); return SD_ERR_INVALID; }
+    if (count < 0 || count > SD_MAX_CONTROLNETS) {
+        set_error("sd_unet_set_controlnets: at most " + std::to_string(SD_MAX_CONTROLNETS) + " ControlNets");
+        return SD_ERR_INVALID;
+    }
+    ControlNet* nets[SD_MAX_CONTROLNETS] = {};
+    for (int i = 0; i < count; ++i) {
+        if (!cns[i]) { set_error("sd_unet_set_controlnets: null ControlNet in the list"); return SD_ERR_INVALID; }
+        if (!cns[i]->impl.finalized) { set_error("sd_unet_set_controlnets: ControlNet not finalized"); return SD_ERR_STATE; }
+        std::string why;
+        if (!controlnet_fits(u->impl.cfg, cns[i]->impl.cfg, &why)) { set_error("sd_unet_set_controlnets: " + why); return SD_ERR_INVALID; }
+        for (int j = 0; j < i; ++j)
+            if (cns[j] == cns[i]) { set_error("sd_unet_set_controlnets: the same ControlNet twice in the list"); return SD_ERR_INVALID; }
+        nets[i] = &cns[i]->impl;
+    }
+    if (int rc = u->impl.set_controlnets(nets, count)) return rc;
+    u->impl.dc_tag.clear();
+    return SD_OK;
+}
+int sd_unet_forward_mcn(sd_unet* u, const void* sample, const float* timesteps, const void* ehs, int ehs_len,
+                        const void* add_text, const float* add_time_ids, const void* image_embeds, int n_img,
+                        const void* const* control_images, const int* n_ctrl, const float* cond_scales, int n_nets,
+                        void* out, int B, int H, int W, void* stream) {
+    UNetCall c;
+    if (!fill_call(u, sample, timesteps, ehs, ehs_len, add_text, add_time_ids, out, B, H, W, &c)) return SD_ERR_INVALID;
+    if (n_nets < 0 || n_nets > SD_MAX_CONTROLNETS || (n_nets > 0 && (!control_images || !n_ctrl || !cond_scales))) {
+        set_error("sd_unet_forward_mcn: n_nets outside 0.." + std::to_string(SD_MAX_CONTROLNETS) + " or a null list");
+        return SD_ERR_INVALID;
+    }
+    with_images(&c, image_embeds, n_img);
+    c.mcn = true;
+    c.n_nets = n_nets;
+    for (int i = 0; i < n_nets; ++i) {
+        c.mc_control[i] = static_cast<const half_t*>(control_images[i]);
+        c.mc_n_ctrl[i] = n_ctrl[i];
+        c.mc_scale[i] = cond_scales[i];
+    }
+    return u->impl.forward(c, static_cast<hipStream_t>(stream));
+}
+int64_t sd_unet_cn_fold_count(const sd_unet* u) { return u ? u->impl.cn_fold_count : 0; }
+int sd_cn_kcat_force(int mode) { cn_kcat_force(mode); return SD_OK; }
 int sd_unet_forward_cn(sd_unet* u, const void* sample, const float* timesteps, const void* ehs, int ehs_len,
                        const void* add_text, const float* add_time_ids, const void* image_embeds, int n_img,
                        const void* control_image, int n_ctrl, float cond_scale, void* out, int B, int H, int W,
@@ -2088,6 +2129,109 @@ int sd_op_controlnet_residuals(const sd_cn_problem* problems, int count, float s
             ConvArgs f = conv_res(y);
             f.acc_scale = scale; f.bias_scale = scale;
             op_conv(c, ws[(size_t)i], view_of(q.x, q.ldx, q.C), 1, q.M, 1, y, f);
+        }
+    });
+}
+
+int sd_op_cn_fold_scales(const void* const* w, const float* const* bias, const float* scales, int n, int C, void* w_cat,
+                         float* b_cat, int iters, float* ms_per_launch, void* stream) {
+    if (!w || !bias || !scales || !w_cat || !b_cat) { set_error("sd_op_cn_fold_scales: null argument"); return SD_ERR_INVALID; }
+    if (n < 1 || n > kCnMaxNets || C <= 0 || C % 64 != 0) { set_error("sd_op_cn_fold_scales: 1..4 nets, C % 64 == 0 required"); return SD_ERR_INVALID; }
+    if ((reinterpret_cast<uintptr_t>(w_cat) & 15) || (reinterpret_cast<uintptr_t>(b_cat) & 15)) { set_error("sd_op_cn_fold_scales: outputs must be 16-byte aligned"); return SD_ERR_UNSUPPORTED; }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (int rc = pack_begin(s)) return rc;
+    WeightStore wst;
+    std::vector<ConvW> zs((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        if (!w[i] || !bias[i]) { set_error("sd_op_cn_fold_scales: null argument"); return SD_ERR_INVALID; }
+        if (int rc = pack_conv_op(wst, w[i], C, C, 1, bias[i], false, false, &zs[(size_t)i])) return rc;
+    }
+    // the fold works on whole packed rows: into packed-size buffers, of which the caller's [C][n C] / [C] are the top
+    const long rows = weight_rows(C);
+    half_t* wc = static_cast<half_t*>(wst.dmalloc((size_t)rows * n * C * sizeof(half_t)));
+    float* bc = static_cast<float*>(wst.dmalloc((size_t)rows * sizeof(float)));
+    if (!wc || !bc) { set_error("hipMalloc failed (folded weights)"); return SD_ERR_HIP; }
+    if (int rc = pack_end()) return rc;
+    CnFoldParams fp;
+    fp.n = n; fp.count = 1;
+    for (int i = 0; i < n; ++i) { fp.s[0].w[i] = zs[(size_t)i].w; fp.s[0].bias[i] = zs[(size_t)i].bias; fp.scale[i] = scales[i]; }
+    fp.s[0].w_cat = wc; fp.s[0].b_cat = bc; fp.s[0].rows = (int)rows; fp.s[0].C = C; fp.s[0].first = 0;
+    fp.total = cn_fold_blocks((int)rows, C, n);
+    if (iters > 0 && !ms_per_launch) { set_error("ms_per_launch required with iters > 0"); return SD_ERR_INVALID; }
+    if (int rc = launch_or_time(s, iters, ms_per_launch, [&]() { return launch_cn_fold_scales(fp, s); })) return rc;
+    SD_HIP_CHECK(hipMemcpyAsync(w_cat, wc, (size_t)C * n * C * sizeof(half_t), hipMemcpyDeviceToDevice, s));
+    SD_HIP_CHECK(hipMemcpyAsync(b_cat, bc, (size_t)C * sizeof(float), hipMemcpyDeviceToDevice, s));
+    SD_HIP_CHECK(hipStreamSynchronize(s));
+    return SD_OK;
+}
+
+int sd_op_controlnet_residuals_multi(const sd_cn_multi_problem* problems, int count, const float* scales, int n, int mode,
+                                     int iters, float* ms_per_launch, void* stream) {
+    if (!problems || !scales || count < 1 || count > kCnMaxProblems) { set_error("sd_op_controlnet_residuals_multi: 1..16 problems"); return SD_ERR_INVALID; }
+    if (n < 1 || n > kCnMaxNets) { set_error("sd_op_controlnet_residuals_multi: 1..4 nets"); return SD_ERR_INVALID; }
+    if (mode != 0 && mode != 1) { set_error("sd_op_controlnet_residuals_multi: mode must be 0 (chained) or 1 (folded, one GEMM)"); return SD_ERR_INVALID; }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    for (int i = 0; i < count; ++i) {
+        const sd_cn_multi_problem& q = problems[i];
+        if (q.C <= 0 || q.C % 64 != 0 || q.M <= 0 || !q.y || q.ldy < q.C) { set_error("sd_op_controlnet_residuals_multi: C % 64 == 0, M >= 1, ldy >= C required"); return SD_ERR_INVALID; }
+        for (int j = 0; j < n; ++j)
+            if (!q.x[j] || !q.w[j] || !q.bias[j] || q.ldx[j] < q.C || q.ldx[j] % 8 != 0 || (reinterpret_cast<uintptr_t>(q.x[j]) & 15)) {
+                set_error("sd_op_controlnet_residuals_multi: null or misaligned source"); return SD_ERR_INVALID;
+            }
+        if (mode == 1)
+            for (int j = 1; j < n; ++j)
+                if (q.ldx[j] != q.ldx[0] || static_cast<const half_t*>(q.x[j]) != static_cast<const half_t*>(q.x[0]) + (long)j * q.C) {
+                    set_error("sd_op_controlnet_residuals_multi: mode 1 takes sources that are neighbouring column slices of one buffer");
+                    return SD_ERR_INVALID;
+                }
+    }
+    if (int rc = pack_begin(s)) return rc;
+    WeightStore wst;
+    std::vector<ConvW> zs((size_t)count * n);
+    std::vector<ConvW> cat((size_t)count);
+    CnFoldParams fp;
+    fp.n = n;
+    for (int i = 0; i < count; ++i) {
+        const sd_cn_multi_problem& q = problems[i];
+        for (int j = 0; j < n; ++j)
+            if (int rc = pack_conv_op(wst, q.w[j], q.C, q.C, 1, q.bias[j], false, false, &zs[(size_t)i * n + j])) return rc;
+        if (mode == 1) {
+            const long rows = weight_rows(q.C);
+            ConvW& zw = cat[(size_t)i];
+            zw.w = static_cast<half_t*>(wst.dmalloc((size_t)rows * n * q.C * sizeof(half_t)));
+            zw.bias = static_cast<float*>(wst.dmalloc((size_t)rows * sizeof(float)));
+            if (!zw.w || !zw.bias) { set_error("hipMalloc failed (folded weights)"); return SD_ERR_HIP; }
+            zw.cin = n * q.C; zw.cout = q.C; zw.ks = 1; zw.K = (long)n * q.C;
+            CnFoldSite& f = fp.s[fp.count++];
+            for (int j = 0; j < n; ++j) { f.w[j] = zs[(size_t)i * n + j].w; f.bias[j] = zs[(size_t)i * n + j].bias; }
+            f.w_cat = zw.w; f.b_cat = zw.bias; f.rows = (int)rows; f.C = q.C; f.first = fp.total;
+            fp.total += cn_fold_blocks((int)rows, q.C, n);
+        }
+    }
+    for (int j = 0; j < n; ++j) fp.scale[j] = scales[j];
+    if (int rc = pack_end()) return rc;
+    if (mode == 1) {
+        // one grouped fold launch over all problems, as the forward issues it when the scales change (timed on its own)
+        if (iters > 0 && !ms_per_launch) { set_error("ms_per_launch required with iters > 0"); return SD_ERR_INVALID; }
+        if (int rc = launch_or_time(s, iters, iters > 0 ? ms_per_launch + 1 : nullptr, [&]() { return launch_cn_fold_scales(fp, s); })) return rc;
+        return run_op_on_arena(s, iters, ms_per_launch, [&](Ctx& c) {
+            for (int i = 0; i < count; ++i) {
+                const sd_cn_multi_problem& q = problems[i];
+                View y(static_cast<half_t*>(q.y), q.ldy, q.C);
+                op_conv(c, cat[(size_t)i], view_of(q.x[0], q.ldx[0], n * q.C), 1, q.M, 1, y, conv_res(y));
+            }
+        });
+    }
+    return run_op_on_arena(s, iters, ms_per_launch, [&](Ctx& c) {
+        for (int i = 0; i < count; ++i) {
+            const sd_cn_multi_problem& q = problems[i];
+            View y(static_cast<half_t*>(q.y), q.ldy, q.C);
+            for (int j = 0; j < n; ++j) {
+                if (scales[j] == 0.f) continue;
+                ConvArgs f = conv_res(y);
+                f.acc_scale = scales[j]; f.bias_scale = scales[j];
+                op_conv(c, zs[(size_t)i * n + j], view_of(q.x[j], q.ldx[j], q.C), 1, q.M, 1, y, f);
+            }
         }
     });
 }

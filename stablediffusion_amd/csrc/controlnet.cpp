@@ -47,7 +47,7 @@ ControlNet::ControlNet(const sd_unet_config& c, int conditioning_channels) : Enc
 }
 
 ControlNet::~ControlNet() {
-    if (attached) attached->set_controlnet(nullptr);
+    if (attached) attached->drop_controlnet(this);
 }
 
 int ControlNet::finalize() {
@@ -127,21 +127,88 @@ int ControlNet::run(Ctx& c, const UNetCall& call, View text_kv, View emb, const 
     return c.err;
 }
 
-void UNet::set_controlnet(ControlNet* n) {
-    if (cn == n) return;
-    if (cn) cn->attached = nullptr;
-    if (n) {
-        if (n->attached && n->attached != this) n->attached->set_controlnet(nullptr);
+int UNet::set_controlnets(ControlNet* const* nets, int count) {
+    const std::vector<ControlNet*> want(nets, nets + count);
+    if (want == cns) return 0;
+    // the folded weights of every site, sized for all the nets of the list (one net folds nothing)
+    std::vector<long> woff, boff;
+    long wtot = 0, btot = 0;
+    if (count > 1) {
+        const int nsites = num_skips() + 1;
+        for (int si = 0; si < nsites; ++si) {
+            const ConvW& z = si < nsites - 1 ? want[0]->zero[(size_t)si] : want[0]->zero_mid;
+            const long rows = weight_rows(z.cout);
+            woff.push_back(wtot); boff.push_back(btot);
+            wtot += rows * count * z.K;
+            btot += rows;
+        }
+        bool grew = false;
+        if (int rc = cn_wcat.reserve((size_t)wtot * sizeof(half_t), &grew)) return rc;
+        if (int rc = cn_bcat.reserve((size_t)btot * sizeof(float), &grew)) return rc;
+    }
+    for (ControlNet* o : cns) o->attached = nullptr;
+    for (ControlNet* n : want) {
+        if (n->attached && n->attached != this) n->attached->drop_controlnet(n);
         n->attached = this;
     }
-    cn = n;
-    cond_tag.clear();
-    cnkv_tag.clear();
+    cns = want;
+    cn = cns.empty() ? nullptr : cns[0];
+    cn_wcat_off = woff; cn_bcat_off = boff;
+    cn_fold_tag = CnFoldTag();
+    clear_cn_tags();
     dc_tag.clear();
     reset_plans();
+    return 0;
 }
 
-int UNet::run_controlnet(Ctx& c, const UNetCall& call, const std::vector<View>& sites, View mid) {
+void UNet::drop_controlnet(ControlNet* n) {
+    std::vector<ControlNet*> rest;
+    for (ControlNet* o : cns)
+        if (o != n) rest.push_back(o);
+    n->attached = nullptr;
+    (void)set_controlnets(rest.data(), (int)rest.size());      // (a shorter list needs no larger buffer: it cannot fail)
+}
+
+const ConvW& UNet::cn_zero(int i, int si) const {
+    const ControlNet* n = cns[(size_t)i];
+    return si < (int)n->zero.size() ? n->zero[(size_t)si] : n->zero_mid;
+}
+
+int UNet::cn_fold(const int* idx, const float* scale, int n, hipStream_t s) {
+    bool same = cn_fold_tag.valid && cn_fold_tag.n == n;
+    for (int j = 0; j < n && same; ++j) same = cn_fold_tag.idx[j] == idx[j] && cn_fold_tag.scale[j] == scale[j];
+    if (same) return 0;
+    CnFoldParams fp;
+    fp.n = n;
+    const int nsites = num_skips() + 1;
+    for (int si = 0; si < nsites; ++si) {
+        CnFoldSite& q = fp.s[fp.count++];
+        const ConvW& z0 = cn_zero(idx[0], si);
+        for (int j = 0; j < n; ++j) { q.w[j] = cn_zero(idx[j], si).w; q.bias[j] = cn_zero(idx[j], si).bias; }
+        q.w_cat = cn_wcat.h() + cn_wcat_off[(size_t)si];
+        q.b_cat = reinterpret_cast<float*>(cn_bcat.data()) + cn_bcat_off[(size_t)si];
+        q.rows = (int)weight_rows(z0.cout); q.C = (int)z0.K;
+        q.first = fp.total;
+        fp.total += cn_fold_blocks(q.rows, q.C, n);
+    }
+    for (int j = 0; j < n; ++j) fp.scale[j] = scale[j];
+    cn_fold_tag.valid = false;
+    prof_open(s, "cn_fold_scales_kernel", 0.0, 0.0);
+    const int rc = launch_cn_fold_scales(fp, s);
+    prof_close(s);
+    if (rc) return rc;
+    cn_fold_tag.valid = true; cn_fold_tag.n = n;
+    for (int j = 0; j < n; ++j) { cn_fold_tag.idx[j] = idx[j]; cn_fold_tag.scale[j] = scale[j]; }
+    ++cn_fold_count;
+    return 0;
+}
+
+int UNet::run_controlnet(Ctx& c, const UNetCall& call, int net, const std::vector<View>& sites, View mid) {
+    ControlNet* const cn = cns[(size_t)net];
+    DeviceBuf& cond_cache = this->cond_cache[net];
+    DeviceBuf& cnkv_cache = this->cnkv_cache[net];
+    CacheTag& cond_tag = this->cond_tag[net];
+    CacheTag& cnkv_tag = this->cnkv_tag[net];
     const half_t* const ehs = call.ehs;
     const half_t* const control = call.control;
     const int B = call.B, H = call.H, W = call.W, L = call.L, n_ctrl = call.n_ctrl;

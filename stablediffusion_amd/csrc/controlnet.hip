@@ -4,6 +4,11 @@
 //                        y_i = fp16(y_i + s (x_i W_i^T + b_i)) for up to 16 independent problems (K = N = C_i).
 //   cn_cond_conv_kernel  one layer of ControlNetConditioningEmbedding: 3x3 conv, stride 1 or 2, pad 1, bias, SiLU,
 //                        NHWC fp16 out (NCHW fp16 in for the first layer, which reads the control image).
+//   cn_fold_scales_kernel  MultiControlNet: every site's zero-conv weights of the running nets, scaled and column-
+//                        concatenated for one GEMM on [h_1 | ... | h_n]; one grouped launch.
+#include <atomic>
+#include <cstdlib>
+
 #include "kernels.h"
 
 namespace sd {
@@ -81,6 +86,52 @@ __global__ __launch_bounds__(256) void cn_residual_kernel(CnResParams P) {
             for (int e = 0; e < 4; ++e) o[e] = (half_t)((float)old[e] + s * (acc[i][j][e] + bias[e]));
             *reinterpret_cast<h4*>(yr + col) = o;
         }
+    }
+}
+
+// --------------------------------------------------------------------------- MultiControlNet scale fold
+// One lane per 16-byte piece of an output: first the rows x n x C / 8 pieces of w_cat, then the rows / 4 pieces of
+// b_cat.  Memory-bound copy with one multiply per element; the site of a block is found as cn_residual_kernel does.
+__global__ __launch_bounds__(256) void cn_fold_scales_kernel(CnFoldParams P) {
+    const int blk = blockIdx.x;
+    CnFoldSite q = P.s[0];
+#pragma unroll
+    for (int i = 1; i < kCnMaxProblems; ++i)
+        if (i < P.count && blk >= P.s[i].first) q = P.s[i];
+    const long item = (long)(blk - q.first) * 256 + threadIdx.x;
+    const int c8 = q.C >> 3;
+    const long nw = (long)q.rows * P.n * c8;
+    if (item < nw) {
+        const int kc = (int)(item % c8);
+        const long r = item / c8;
+        const int net = (int)(r % P.n);
+        const long o = r / P.n;
+        const half_t* w = q.w[0];
+        float s = P.scale[0];
+#pragma unroll
+        for (int j = 1; j < kCnMaxNets; ++j)
+            if (net == j) { w = q.w[j]; s = P.scale[j]; }
+        const h8 v = *reinterpret_cast<const h8*>(w + o * q.C + kc * 8);
+        h8 out;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) out[e] = (half_t)((float)v[e] * s);
+        *reinterpret_cast<h8*>(q.w_cat + o * ((long)P.n * q.C) + (long)net * q.C + kc * 8) = out;
+    } else if (item - nw < (q.rows >> 2)) {
+#pragma clang fp contract(off)
+        const long o4 = (item - nw) * 4;
+        f4 acc = f4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int j = 0; j < kCnMaxNets; ++j) {
+            if (j >= P.n) break;
+            const f4 b = *reinterpret_cast<const f4*>(q.bias[j] + o4);
+            const float s = P.scale[j];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float t = s * b[e];
+                acc[e] = j == 0 ? t : acc[e] + t;
+            }
+        }
+        *reinterpret_cast<f4*>(q.b_cat + o4) = acc;
     }
 }
 
@@ -185,6 +236,43 @@ int launch_cn_residual(const CnResParams& p, hipStream_t s) {
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { set_error(hipGetErrorString(e)); return 3; }
     return 0;
+}
+
+int cn_fold_blocks(int rows, int C, int n) { return (int)cdiv((long)rows * n * (C / 8) + rows / 4, 256); }
+
+bool cn_fold_supported(const CnFoldParams& p) {
+    if (p.count < 1 || p.count > kCnMaxProblems || p.n < 1 || p.n > kCnMaxNets) return false;
+    int next = 0;
+    for (int i = 0; i < p.count; ++i) {
+        const CnFoldSite& q = p.s[i];
+        if (q.C <= 0 || q.C % 8 != 0 || q.rows <= 0 || q.rows % 4 != 0 || q.first != next) return false;
+        if (!q.w_cat || !q.b_cat || (reinterpret_cast<uintptr_t>(q.w_cat) & 15) || (reinterpret_cast<uintptr_t>(q.b_cat) & 15)) return false;
+        for (int j = 0; j < p.n; ++j)
+            if (!q.w[j] || !q.bias[j] || (reinterpret_cast<uintptr_t>(q.w[j]) & 15) || (reinterpret_cast<uintptr_t>(q.bias[j]) & 15)) return false;
+        next += cn_fold_blocks(q.rows, q.C, p.n);
+    }
+    return next == p.total;
+}
+
+int launch_cn_fold_scales(const CnFoldParams& p, hipStream_t s) {
+    if (!cn_fold_supported(p)) { set_error("cn_fold_scales: unsupported site table"); return 4; }
+    hipLaunchKernelGGL(cn_fold_scales_kernel, dim3((unsigned)p.total), dim3(256), 0, s, p);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { set_error(hipGetErrorString(e)); return 3; }
+    return 0;
+}
+
+namespace {
+std::atomic<int> g_cn_kcat_mode{-1};
+// The default for two or more running nets (profiles/multi_controlnet.txt).
+constexpr bool kCnKcatDefault = true;
+}  // namespace
+void cn_kcat_force(int mode) { g_cn_kcat_mode = mode < -1 || mode > 1 ? -1 : mode; }
+bool cn_kcat_on() {
+    const int m = g_cn_kcat_mode;
+    if (m >= 0) return m == 1;
+    static const bool off = getenv("SD_NO_CN_KCAT") != nullptr && getenv("SD_NO_CN_KCAT")[0] == '1';
+    return kCnKcatDefault && !off;
 }
 
 bool cn_cond_conv_supported(const CnCondConvParams& p) {

@@ -337,6 +337,34 @@ struct CnResParams {
 int cn_residual_tiles(int M, int C);
 bool cn_residual_supported(const CnResParams& p);
 int launch_cn_residual(const CnResParams& p, hipStream_t s);
+// MultiControlNet: the zero-convs of n nets at one residual site folded into one linear on the column-concatenated
+// hidden tensors [h_1 | ... | h_n], for every site in one launch:
+//   w_cat[o, i C + k] = fp16(float(w_i[o, k]) * scale[i])     (one fp32 multiply, round to nearest)
+//   b_cat[o]          = sum_i scale[i] * bias_i[o]            (fp32, in net order, no contraction)
+// w_i packed [rows][C] (WeightStore::pack_conv of a 1x1 conv: rows = weight_rows(C), zero past C), bias_i fp32 [rows],
+// w_cat [rows][n C], b_cat [rows]; C % 8 == 0, rows % 4 == 0, every pointer 16-byte aligned.  first = the site's first
+// 256-thread block in the joint list (cn_fold_blocks of the ones before it), total = all blocks.
+constexpr int kCnMaxNets = 4;
+struct CnFoldSite {
+    const half_t* w[kCnMaxNets] = {};
+    const float* bias[kCnMaxNets] = {};
+    half_t* w_cat = nullptr;
+    float* b_cat = nullptr;
+    int rows = 0, C = 0;
+    int first = 0;
+};
+struct CnFoldParams {
+    CnFoldSite s[kCnMaxProblems];
+    float scale[kCnMaxNets] = {};
+    int n = 0, count = 0, total = 0;
+};
+int cn_fold_blocks(int rows, int C, int n);
+bool cn_fold_supported(const CnFoldParams& p);
+int launch_cn_fold_scales(const CnFoldParams& p, hipStream_t s);
+// sd_cn_kcat_force: how two or more running ControlNets add their residuals: -1 the default (SD_NO_CN_KCAT=1 in the
+// environment selects the chained form), 0 chained per-net launches per site, 1 one K-concatenated GEMM per site
+void cn_kcat_force(int mode);
+bool cn_kcat_on();
 // One layer of ControlNetConditioningEmbedding: y = act(conv3x3(x) + bias), stride 1 or 2, pad 1.  x NCHW fp16 with
 // Cin = 3 (nchw = 1: the control image) or NHWC fp16 with Cin in {16, 32, 96}; y NHWC fp16 [N, OH, OW, Cout],
 // Cout % 16 == 0; w from launch_cn_pack_cond, bias fp32 [Cout]; silu = 1 applies SiLU.

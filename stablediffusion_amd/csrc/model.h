@@ -259,6 +259,15 @@ struct UNetCall {
     const half_t* control = nullptr;        // ControlNet: n_ctrl control images [n_ctrl, 3, 8H, 8W] and the residuals' scale
     int n_ctrl = 0;
     float cn_scale = 0.f;
+    // MultiControlNet (sd_unet_forward_mcn): mcn = the call names one image / count / scale per attached net, by index.
+    // UNet::forward normalises: cn_active = the nets that run (scale != 0); with one, control / n_ctrl / cn_scale are its
+    // and cn_idx says which; with two or more, cn_act[] lists them and control / n_ctrl are the first one's.
+    bool mcn = false;
+    int n_nets = 0;
+    const half_t* mc_control[kCnMaxNets] = {};
+    int mc_n_ctrl[kCnMaxNets] = {};
+    float mc_scale[kCnMaxNets] = {};
+    int cn_idx = 0, cn_active = 0, cn_act[kCnMaxNets] = {};
     const float* tcond = nullptr;           // timestep_cond [B, time_cond_proj_dim] of a guidance-embedded UNet
     const CfgIn* cfg_in = nullptr;          // shared-CFG mode (forward_cfg)
     const PagIn* pag = nullptr;             // perturbed-attention mode (forward_pag)
@@ -280,6 +289,7 @@ struct PlanKey {
     int pag_groups = 0;                     // forward_pag: 1 or 2, and whether the perturbed group is widened late
     bool pag_late = false;
     int n_ctrl = 0;                         // control images of a ControlNet that runs, 0 when none does
+    int cn_n[kCnMaxNets] = {0, 0, 0, 0};    // ... of every attached net that runs, by its index (0: it does not)
     int dc_depth = 0;                       // DeepCache depth of a store / reuse forward (the plain one ignores it)
     int cat_rows = 0;                       // forward_concat: the latents the B images are built from, 0 otherwise
     double tome_ratio = 0.0;                // token merging: what the merged rows per block depend on (0: off)
@@ -287,7 +297,8 @@ struct PlanKey {
     int ht_tile = 0, ht_swap = 0, ht_depth = 0; // HyperTile: what the gather buffers of the sites depend on (0: off)
     bool operator==(const PlanKey& o) const {
         return B == o.B && H == o.H && W == o.W && L == o.L && kv_cache == o.kv_cache && ip_tokens == o.ip_tokens &&
-               cfg_share == o.cfg_share && pag_groups == o.pag_groups && pag_late == o.pag_late && n_ctrl == o.n_ctrl &&
+               cfg_share == o.cfg_share && pag_groups == o.pag_groups && pag_late == o.pag_late && n_ctrl == o.n_ctrl && cn_n[0] == o.cn_n[0] &&
+               cn_n[1] == o.cn_n[1] && cn_n[2] == o.cn_n[2] && cn_n[3] == o.cn_n[3] &&
                dc_depth == o.dc_depth && cat_rows == o.cat_rows && tome_ratio == o.tome_ratio && tome_ds == o.tome_ds &&
                tome_sx == o.tome_sx && tome_sy == o.tome_sy && ht_tile == o.ht_tile && ht_swap == o.ht_swap &&
                ht_depth == o.ht_depth;
@@ -343,7 +354,7 @@ struct UNet : Encoder {
     DeviceBuf cfg_slab;                 // forward_cfg's / forward_pag's duplicated latents + timesteps when they do not share
     int forward(const UNetCall& call, hipStream_t stream);
     void set_ip_adapter(IPAdapter* a);
-    void set_controlnet(ControlNet* n);
+    int set_controlnet(ControlNet* n) { return set_controlnets(&n, n ? 1 : 0); }
 
     Arena arena;
     bool finalized = false;
@@ -393,10 +404,32 @@ struct UNet : Encoder {
     // embedding ([B H W, C0], sample b from control image b mod n_ctrl) and its text K / V follow the text K / V's cache
     // rules: kept across the forwards of one loop for one (pointer, B, n_ctrl, H, W) / (pointer, B, L), invalidated by
     // every sd_unet_text_kv_cache call and by set_controlnet, not under graphs.
+    // MultiControlNet (sd_unet_set_controlnets): up to kCnMaxNets nets in `cns`, every cache per net (by its index in the
+    // list); cn = cns[0] or nullptr is what every "a ControlNet is attached" check reads, so a list is refused wherever
+    // one net is.  One running net (the others at scale 0) takes the single-net path; two or more write their hidden
+    // tensors into column slices of one wide buffer per site and add their residuals with one GEMM per site on the
+    // folded weights cn_wcat / cn_bcat ([rows][n C] fp16 / [rows] fp32 per site, sized for all attached nets at attach,
+    // refolded when the (running nets, scales) tag changes) -- or, with cn_kcat_on() false, one GEMM per net and site.
     ControlNet* cn = nullptr;
-    DeviceBuf cond_cache, cnkv_cache;
-    CacheTag cond_tag;                  // (control; B, n_ctrl, H, W)
-    CacheTag cnkv_tag;                  // (ehs; B, L)
+    std::vector<ControlNet*> cns;
+    DeviceBuf cond_cache[kCnMaxNets], cnkv_cache[kCnMaxNets];
+    CacheTag cond_tag[kCnMaxNets];      // (control; B, n_ctrl, H, W)
+    CacheTag cnkv_tag[kCnMaxNets];      // (ehs; B, L)
+    void clear_cn_tags() { for (int i = 0; i < kCnMaxNets; ++i) { cond_tag[i].clear(); cnkv_tag[i].clear(); } }
+    DeviceBuf cn_wcat, cn_bcat;
+    std::vector<long> cn_wcat_off, cn_bcat_off;     // per site (skips, then mid), in elements
+    struct CnFoldTag {
+        bool valid = false;
+        int n = 0, idx[kCnMaxNets] = {};
+        float scale[kCnMaxNets] = {};
+    } cn_fold_tag;
+    int64_t cn_fold_count = 0;          // fold launches since creation (sd_unet_cn_fold_count)
+    int set_controlnets(ControlNet* const* nets, int count);
+    void drop_controlnet(ControlNet* n);    // (a net being destroyed: the others stay attached)
+    // zero-conv of attached net `i` at site si (si == number of skips: the mid block's)
+    const ConvW& cn_zero(int i, int si) const;
+    // fold the running nets' zero-convs for one K-concatenated GEMM per site, unless the tag says they are folded
+    int cn_fold(const int* idx, const float* scale, int n, hipStream_t s);
 
     // ---- FreeU (sd_unet_set_freeu): off = the forward as without the feature.  On, every resnet of up blocks 0 and 1
     // gets one in-place launch on its concatenation buffer before norm1 reads it: (b1, s1) in block 0, (b2, s2) in
@@ -471,7 +504,8 @@ struct UNet : Encoder {
     // dc: the DeepCache mode of this forward (SD_DC_*)
     int run(Ctx& c, const UNetCall& call, int dc = 0);
     // ControlNet step of run(): its hidden tensors into sites / mid (allocated by the caller)
-    int run_controlnet(Ctx& c, const UNetCall& call, const std::vector<View>& sites, View mid);
+    // (net = its index in cns; call.control / n_ctrl are that net's)
+    int run_controlnet(Ctx& c, const UNetCall& call, int net, const std::vector<View>& sites, View mid);
 };
 
 struct VAE {

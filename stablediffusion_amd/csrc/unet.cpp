@@ -1231,7 +1231,10 @@ int UNet::run(Ctx& c, const UNetCall& call, int dc) {
     // ---- ControlNet: its encoder on the same sample, timestep and text.  The pre-zero-conv hidden tensors of every
     //      skip and of the mid block live above the concatenation buffers (released after the residual adds); the
     //      ControlNet runs on a GroupNorm ring of its own, this forward's ring is restored after it ----
+    //      With n_act >= 2 running nets (MultiControlNet) every site is one wide buffer [rows, n_act C] and net k's encoder
+    //      writes the column slice [k C, (k + 1) C): the operand of one K-concatenated residual GEMM per site.
     const bool use_cn = cn && call.control && cn_scale != 0.f && !cfg_in;
+    const int n_act = !use_cn ? 0 : call.cn_active > 1 ? call.cn_active : 1;
     const size_t cn_mark = a.mark();
     std::vector<View> cn_sites;
     std::vector<int> cn_rows;
@@ -1239,7 +1242,7 @@ int UNet::run(Ctx& c, const UNetCall& call, int dc) {
     if (use_cn) {
         int hh = H, ww = W;
         auto site = [&](int C) {
-            cn_sites.emplace_back(a.alloc_h((long)B * hh * ww * C), C, C);
+            cn_sites.emplace_back(a.alloc_h((long)B * hh * ww * n_act * C), (long)n_act * C, n_act * C);
             cn_rows.push_back(B * hh * ww);
         };
         site(boc[0]);
@@ -1247,7 +1250,7 @@ int UNet::run(Ctx& c, const UNetCall& call, int dc) {
             for (int j = 0; j < cfg.layers_per_block; ++j) site(boc[i]);
             if (i != nb - 1) { hh /= 2; ww /= 2; site(boc[i]); }
         }
-        cn_mid = View(a.alloc_h((long)B * hh * ww * boc[nb - 1]), boc[nb - 1], boc[nb - 1]);
+        cn_mid = View(a.alloc_h((long)B * hh * ww * n_act * boc[nb - 1]), (long)n_act * boc[nb - 1], n_act * boc[nb - 1]);
         cn_rows.push_back(B * hh * ww);
         GnStatBuf ring[Ctx::kGnPool];
         for (int i = 0; i < Ctx::kGnPool; ++i) ring[i] = c.gnpool[i];
@@ -1258,7 +1261,22 @@ int UNet::run(Ctx& c, const UNetCall& call, int dc) {
         c.tome = nullptr;
         const HyperTileRun* const ht_run = c.hypertile;
         c.hypertile = nullptr;
-        if (int rc = run_controlnet(c, call, cn_sites, cn_mid)) return rc;
+        if (n_act == 1) {
+            if (int rc = run_controlnet(c, call, call.cn_idx, cn_sites, cn_mid)) return rc;
+        } else {
+            // one net after the other, each on its own image, embedding and text K / V; a net's temporaries are dead when
+            // its encoder has run
+            for (int k = 0; k < n_act; ++k) {
+                const int net = call.cn_act[k];
+                UNetCall one = call;
+                one.control = call.mc_control[net]; one.n_ctrl = call.mc_n_ctrl[net];
+                std::vector<View> sl;
+                for (const View& v : cn_sites) sl.push_back(v.slice(k * (v.C / n_act), v.C / n_act));
+                const size_t mk = a.mark();
+                if (int rc = run_controlnet(c, one, net, sl, cn_mid.slice(k * (cn_mid.C / n_act), cn_mid.C / n_act))) return rc;
+                a.release(mk);
+            }
+        }
         c.tome = tome_run;
         c.hypertile = ht_run;
         c.tap = tap;
@@ -1316,14 +1334,38 @@ int UNet::run(Ctx& c, const UNetCall& call, int dc) {
     //      residual in its epilogue.  After the mid block: the skips were the down path's inputs too, and diffusers adds
     //      the residuals only to what the up path reads.  (The grouped cn_residual_kernel is slower than these launches
     //      today: DESIGN.md §4.)  Then the ControlNet's tensors and the mid block's temporaries are dead. ----
+    //      Two or more running nets: y += [h_1 | ... | h_n] [s_1 W_1 | ... | s_n W_n]^T + sum s_k b_k, one GEMM per site
+    //      with K = n C on the folded weights (UNet::cn_fold: refolded only when the running nets or a scale changed) --
+    //      or, with the K-concatenated form switched off (cn_kcat_on), one GEMM per net and site on its column slice.
     if (use_cn) {
-        ConvArgs f;
-        f.acc_scale = cn_scale; f.bias_scale = cn_scale;
+        const bool kcat = n_act > 1 && cn_kcat_on();
+        if (kcat && go && !c.err) {
+            float sc[kCnMaxNets];
+            for (int k = 0; k < n_act; ++k) sc[k] = call.mc_scale[call.cn_act[k]];
+            c.err = cn_fold(call.cn_act, sc, n_act, s);
+        }
         for (int si = 0; si <= nskip; ++si) {
             const View xh = si < nskip ? cn_sites[(size_t)si] : cn_mid;
             const View y = si < nskip ? skip_view(si) : View(cats[0].p, cats[0].c1 + cats[0].c2, cats[0].c1);
-            const ConvW& zw = si < nskip ? cn->zero[(size_t)si] : cn->zero_mid;
-            op_conv(c, zw, xh, 1, cn_rows[(size_t)si], 1, y, conv_res(y, f));
+            if (n_act == 1) {
+                ConvArgs f;
+                f.acc_scale = cn_scale; f.bias_scale = cn_scale;
+                op_conv(c, cn_zero(call.cn_idx, si), xh, 1, cn_rows[(size_t)si], 1, y, conv_res(y, f));
+            } else if (kcat) {
+                const ConvW& z0 = cn_zero(call.cn_act[0], si);
+                ConvW zw;
+                zw.w = cn_wcat.h() + cn_wcat_off[(size_t)si];
+                zw.bias = reinterpret_cast<float*>(cn_bcat.data()) + cn_bcat_off[(size_t)si];
+                zw.cin = n_act * z0.cin; zw.cout = z0.cout; zw.ks = 1; zw.K = n_act * z0.K;
+                op_conv(c, zw, xh, 1, cn_rows[(size_t)si], 1, y, conv_res(y));
+            } else {
+                const int C = xh.C / n_act;
+                for (int k = 0; k < n_act; ++k) {
+                    ConvArgs f;
+                    f.acc_scale = f.bias_scale = call.mc_scale[call.cn_act[k]];
+                    op_conv(c, cn_zero(call.cn_act[k], si), xh.slice(k * C, C), 1, cn_rows[(size_t)si], 1, y, conv_res(y, f));
+                }
+            }
         }
     }
     if (use_cn) a.release(cn_mark);
@@ -1499,7 +1541,7 @@ UNet::~UNet() {
     if (ev_out) (void)hipEventDestroy(ev_out);
     if (gstream) (void)hipStreamDestroy(gstream);
     if (ip) ip->attached = nullptr;
-    if (cn) cn->attached = nullptr;
+    for (ControlNet* n : cns) n->attached = nullptr;
 }
 
 // Graph path: stage I/O through engine-owned buffers, capture the forward once per shape on an
@@ -1591,6 +1633,30 @@ int UNet::forward(const UNetCall& in, hipStream_t stream) {
     // the one copy both passes of run() receive: n_img, n_ctrl and cn_scale are normalised on it below
     UNetCall call = in;
     const int B = call.B, H = call.H, W = call.W, L = call.L;
+    // MultiControlNet: the list's images / counts / scales onto the single net's fields (UNetCall::mcn)
+    bool mcn_idle = false;
+    call.cn_active = 0; call.cn_idx = 0;
+    if (call.mcn) {
+        if (call.n_nets != (int)cns.size()) { set_error("unet: forward_mcn: n_nets differs from the attached ControlNets"); return 1; }
+        call.control = nullptr; call.n_ctrl = 0; call.cn_scale = 0.f;
+        for (int i = 0; i < call.n_nets; ++i) {
+            if (!(call.mc_scale[i] == call.mc_scale[i])) { set_error("unet: conditioning scale is NaN"); return 1; }
+            if (call.mc_scale[i] == 0.f) continue;
+            if (!call.mc_control[i]) { set_error("unet: forward_mcn: control image required for a ControlNet at a non-zero scale"); return 1; }
+            if (call.mc_n_ctrl[i] < 1 || B <= 0 || B % call.mc_n_ctrl[i] != 0) { set_error("unet: the control image count must divide the batch"); return 1; }
+            call.cn_act[call.cn_active++] = i;
+        }
+        mcn_idle = call.cn_active == 0;
+        if (!mcn_idle) {
+            const int i = call.cn_act[0];
+            call.control = call.mc_control[i]; call.n_ctrl = call.mc_n_ctrl[i];
+            call.cn_scale = call.cn_active == 1 ? call.mc_scale[i] : 1.f;
+            call.cn_idx = i;
+        }
+    } else if (cns.size() > 1) {
+        set_error("unet: more than one ControlNet is attached: sd_unet_forward_mcn takes their images and scales");
+        return 1;
+    }
     const half_t* const image_embeds = call.image_embeds;
     const half_t* const control = call.control;
     const float* const tcond = call.tcond;
@@ -1624,10 +1690,10 @@ int UNet::forward(const UNetCall& in, hipStream_t stream) {
     } else {
         call.n_img = 0;
     }
-    if (cn && !control) { set_error("unet: a ControlNet is attached: control image required"); return 1; }
+    if (cn && !control && !mcn_idle) { set_error("unet: a ControlNet is attached: control image required"); return 1; }
     if (!cn && control) { set_error("unet: control image given but no ControlNet is attached"); return 1; }
     if (cn) {
-        if (call.n_ctrl < 1 || B % call.n_ctrl != 0) { set_error("unet: the control image count must divide the batch"); return 1; }
+        if (!mcn_idle && (call.n_ctrl < 1 || B % call.n_ctrl != 0)) { set_error("unet: the control image count must divide the batch"); return 1; }
         if (!(call.cn_scale == call.cn_scale)) { set_error("unet: conditioning scale is NaN"); return 1; }
         if (graph_enabled) { set_error("unet: graph replay with a ControlNet attached is not supported"); return 4; }
     } else {
@@ -1697,9 +1763,11 @@ int UNet::forward(const UNetCall& in, hipStream_t stream) {
         if (int rc = reserve_cache(kv_cache, (size_t)B * L * kv_total * sizeof(half_t), kv_tag)) return rc;
         if (ip && !text_only)
             if (int rc = reserve_cache(ipkv_cache, (size_t)B * call.n_img * ip->n_tok * ip->kv_total * sizeof(half_t), ipkv_tag)) return rc;
-        if (use_cn) {
-            if (int rc = reserve_cache(cond_cache, (size_t)B * H * W * cn->cfg.block_out_channels[0] * sizeof(half_t), cond_tag)) return rc;
-            if (int rc = reserve_cache(cnkv_cache, (size_t)B * L * cn->kv_total * sizeof(half_t), cnkv_tag)) return rc;
+        for (int k = 0; use_cn && k < (call.cn_active > 1 ? call.cn_active : 1); ++k) {
+            const int i = call.cn_active > 1 ? call.cn_act[k] : call.cn_idx;
+            const ControlNet* n = cns[(size_t)i];
+            if (int rc = reserve_cache(cond_cache[i], (size_t)B * H * W * n->cfg.block_out_channels[0] * sizeof(half_t), cond_tag[i])) return rc;
+            if (int rc = reserve_cache(cnkv_cache[i], (size_t)B * L * n->kv_total * sizeof(half_t), cnkv_tag[i])) return rc;
         }
     }
     // set_ip_adapter, set_controlnet, set_pag_layers and sd_ip_adapter_set_feature_tokens change what a key stands for:
@@ -1711,6 +1779,8 @@ int UNet::forward(const UNetCall& in, hipStream_t stream) {
     key.cfg_share = cfg_in != nullptr;
     if (pag) { key.pag_groups = pag->groups; key.pag_late = pag->late; }
     key.n_ctrl = use_cn ? call.n_ctrl : 0;
+    if (use_cn && call.cn_active > 1) for (int k = 0; k < call.cn_active; ++k) key.cn_n[call.cn_act[k]] = call.mc_n_ctrl[call.cn_act[k]];
+    else if (use_cn) key.cn_n[call.cn_idx] = call.n_ctrl;
     key.dc_depth = dc != SD_DC_PLAIN ? dc_depth : 0;
     key.cat_rows = call.extra ? call.lat_rows : 0;
     if (tome_on) { key.tome_ratio = tome.ratio; key.tome_ds = tome_max_ds; key.tome_sx = tome.sx; key.tome_sy = tome.sy; }

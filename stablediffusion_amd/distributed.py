@@ -135,6 +135,11 @@ def sharded_txt2img(pipeline, model, latents_full: torch.Tensor, prompt_embeds_f
     (`sd_unified_pipeline.py:773-781` semantics) so sharded == unsharded per sample.  `broadcast=False`: the text
     embeddings were broadcast already (a caller that runs several passes over the same prompts broadcasts once).
     """
+    ci = call_kwargs.get("control_image")
+    if isinstance(ci, (list, tuple)) and any(isinstance(c, (list, tuple)) or (isinstance(c, torch.Tensor) and c.ndim == 4)
+                                             for c in ci):
+        # (each net's batch would have to be split with the latents: not built, and not silently broadcast)
+        raise NotImplementedError("sharded_txt2img: a list of control-image batches (MultiControlNet) is not supported")
     total = latents_full.shape[0]
     extra = [t for t in (pooled_full, negative_pooled_full) if t is not None]
     if broadcast:

@@ -163,7 +163,8 @@ class HipUNet2DConditionModel:
         self._finalized = False
         self._ip = None                # attached HipIPAdapter (attach_ip_adapter)
         self._ip_scale = 1.0
-        self._cn = None                # attached HipControlNetModel (attach_controlnet)
+        self._cn = None                # attached HipControlNetModel (attach_controlnet); the first of an attached list
+        self._cns = None               # the attached list (attach_controlnets), None while a single net or none is attached
         self._freeu = None             # (s1, s2, b1, b2) while FreeU is on (enable_freeu)
         self._deepcache = None         # (cache_interval, cache_depth) while DeepCache is on (enable_deepcache)
         self._pag = ()                 # site keys of the perturbed transformers (set_pag_layers)
@@ -483,10 +484,52 @@ class HipUNet2DConditionModel:
         if controlnet is not None:
             old = controlnet._unet() if controlnet._unet is not None else None
             if old is not None and old is not self:
-                old._cn = None
+                old._forget_controlnet(controlnet)
             controlnet._unet = weakref.ref(self)
+        for other in self._cns or ():
+            if other is not controlnet:
+                other._unet = None
         self._cn = controlnet
+        self._cns = None
         return self
+
+    def attach_controlnets(self, controlnets):
+        """Attach a list of ControlNets built for this UNet (MultiControlNet; an empty list detaches all).  While a list
+        is attached, controlnet_cond= and controlnet_conditioning_scale= are lists with one entry per net (a float scale
+        broadcasts); a net at scale 0 does not run."""
+        nets = list(controlnets)
+        if len(nets) > _lib.SD_MAX_CONTROLNETS:
+            raise ValueError(f"at most {_lib.SD_MAX_CONTROLNETS} ControlNets, got {len(nets)}")
+        arr = (C.c_void_p * max(len(nets), 1))(*[n._h for n in nets])
+        _lib.check(self._lib.sd_unet_set_controlnets(self._h, arr, len(nets)), "sd_unet_set_controlnets")
+        for old in ([self._cn] if self._cn is not None else []) + list(self._cns or ()):
+            if not any(old is n for n in nets):
+                old._unet = None
+        for n in nets:
+            prev = n._unet() if n._unet is not None else None
+            if prev is not None and prev is not self:
+                prev._forget_controlnet(n)
+            n._unet = weakref.ref(self)
+        self._cn = nets[0] if nets else None
+        self._cns = nets if nets else None
+        return self
+
+    @property
+    def controlnets(self):
+        """The attached list (attach_controlnets), or the single attached net as a list of one; [] without."""
+        return list(self._cns) if self._cns is not None else ([self._cn] if self._cn is not None else [])
+
+    def cn_fold_count(self) -> int:
+        """Launches of the MultiControlNet scale fold since this engine was created (sd_unet_cn_fold_count)."""
+        return int(self._lib.sd_unet_cn_fold_count(self._h))
+
+    def _forget_controlnet(self, net):
+        """`net` was attached elsewhere or destroyed: the engine has dropped it from this UNet's list already."""
+        if self._cns is not None:
+            self._cns = [n for n in self._cns if n is not net] or None
+            self._cn = self._cns[0] if self._cns else None
+        elif self._cn is net:
+            self._cn = None
 
     def make_controlnet(self, cn_config: UNetConfig, state_dict: Dict[str, torch.Tensor]):
         """A HipControlNetModel for this engine, loaded from diffusers-named weights."""
@@ -503,15 +546,44 @@ class HipUNet2DConditionModel:
             return None, 0.0
         if controlnet_cond is None or scale is None:
             raise ValueError("a ControlNet is attached: controlnet_cond and controlnet_conditioning_scale are required")
+        if self._cns is not None:
+            return self._control_list(controlnet_cond, scale, B, H, W, dev)
         if isinstance(controlnet_cond, (list, tuple)) or isinstance(scale, (list, tuple)):
-            raise NotImplementedError("MultiControlNet (lists of control images / scales) is not supported")
+            raise NotImplementedError("MultiControlNet (lists of control images / scales) needs a list of nets: "
+                                      "attach_controlnets")
+        return self._control_image(controlnet_cond, B, H, W, dev), float(scale)
+
+    @staticmethod
+    def _control_image(controlnet_cond, B, H, W, dev):
         cond = _as_f16(controlnet_cond, dev)
         n = cond.shape[0]
         if cond.ndim != 4 or cond.shape[1] != 3 or cond.shape[2] != 8 * H or cond.shape[3] != 8 * W:
             raise ValueError(f"controlnet_cond: expected [n, 3, {8 * H}, {8 * W}], got {tuple(cond.shape)}")
         if n < 1 or B % n:
             raise ValueError(f"controlnet_cond: {n} images do not divide the batch {B}")
-        return cond, float(scale)
+        return cond
+
+    def _control_list(self, controlnet_cond, scale, B, H, W, dev):
+        """With a list attached: one image and one scale per net (a float scale broadcasts); a net at scale 0 does not
+        run and its image may be None.  Returns ([images or None], [scales])."""
+        N = len(self._cns)
+        if not isinstance(controlnet_cond, (list, tuple)) or len(controlnet_cond) != N:
+            raise ValueError(f"a list of {N} ControlNets is attached: controlnet_cond must be a list of {N} images")
+        if isinstance(scale, (list, tuple)):
+            if len(scale) != N:
+                raise ValueError(f"controlnet_conditioning_scale: {len(scale)} scales for {N} ControlNets")
+            scales = [float(v) for v in scale]
+        else:
+            scales = [float(scale)] * N
+        conds = []
+        for img, sc in zip(controlnet_cond, scales):
+            if img is None:
+                if sc != 0.0:
+                    raise ValueError("controlnet_cond: None for a ControlNet at a non-zero scale")
+                conds.append(None)
+            else:
+                conds.append(self._control_image(img, B, H, W, dev))
+        return conds, scales
 
     def _image_embeds(self, added_cond_kwargs, B, dev):
         embeds = (added_cond_kwargs or {}).get("image_embeds")
@@ -615,6 +687,11 @@ class HipUNet2DConditionModel:
         tail = (C.c_void_p(out.data_ptr()), B, H, W, C.c_void_p(_stream_ptr()))
         if tc is not None:
             fn, extra = self._lib.sd_unet_forward_tc, images + (C.c_void_p(tc.data_ptr()), tc.shape[1])
+        elif isinstance(ctrl, list):
+            N = len(ctrl)
+            ptrs = (C.c_void_p * N)(*[c.data_ptr() if c is not None else None for c in ctrl])
+            counts = (C.c_int * N)(*[c.shape[0] if c is not None else 0 for c in ctrl])
+            fn, extra = self._lib.sd_unet_forward_mcn, images + (ptrs, counts, (C.c_float * N)(*cscale), N)
         elif ctrl is not None:
             fn, extra = self._lib.sd_unet_forward_cn, images + (C.c_void_p(ctrl.data_ptr()), ctrl.shape[0], cscale)
         elif img is not None:
@@ -876,7 +953,7 @@ class HipControlNetModel:
             if getattr(self, "_h", None):
                 u = self._unet() if self._unet is not None else None
                 if u is not None:
-                    u._cn = None
+                    u._forget_controlnet(self)
                 self._lib.sd_controlnet_destroy(self._h)     # (detaches it first)
                 self._h = None
         except Exception:

@@ -55,6 +55,7 @@ class SDModelWrapper:
         self._ip = None                  # (diffusers-named state dict, image_embed_dim, num_tokens)
         self._ip_scale = 1.0
         self._cn = None                  # ControlNet (configuration, diffusers-named state dict): load_controlnet
+        self._cn_list = False            # ... or a list of those pairs: load_controlnets (MultiControlNet)
         self._freeu = None               # (s1, s2, b1, b2) while FreeU is on: enable_freeu
         self._pag = None                 # pag_applied_layers as given (set_pag_applied_layers); None: the default
         self._deepcache = None           # (cache_interval, cache_depth) while DeepCache is on: enable_deepcache
@@ -271,26 +272,54 @@ class SDModelWrapper:
         if self.refiner is not None and hasattr(self.refiner, "disable_hypertile"):
             self.refiner.disable_hypertile()
 
-    # ---- ControlNet (diffusers ControlNetModel, one per model; the pipeline takes control_image=) ----
+    # ---- ControlNet (diffusers ControlNetModel, or a list of them: MultiControlNetModel; the pipeline takes
+    #      control_image=) ----
     def _attach_cn(self, base):
+        if self._cn_list:
+            base.attach_controlnets([base.make_controlnet(cfg, sd) for cfg, sd in self._cn])
+            return
         cfg, sd = self._cn
         base.attach_controlnet(base.make_controlnet(cfg, sd))
 
     def load_controlnet(self, pretrained_model_name_or_path_or_dict):
         """A ControlNet for this model's UNet: a diffusers folder (config.json + weights), an original (lllyasviel 1.0 /
         1.1) `.pth` / `.safetensors` file, or a state dict (stablediffusion_amd.controlnet.load: converted, checked).
-        Replaces a ControlNet loaded before.  Lists (MultiControlNet) are not supported."""
+        Replaces whatever was loaded before.  A list (MultiControlNet) goes to load_controlnets."""
         from . import controlnet
         if isinstance(pretrained_model_name_or_path_or_dict, (list, tuple)):
-            raise NotImplementedError("MultiControlNet (a list of ControlNets) is not supported")
+            raise NotImplementedError("load_controlnet takes one ControlNet: a list (MultiControlNet) goes to load_controlnets")
         cfg, sd = controlnet.load(pretrained_model_name_or_path_or_dict, self.base.cfg)
-        self._cn = (cfg, sd)
+        self.unload_controlnet()
+        self._cn, self._cn_list = (cfg, sd), False
+        self._attach_cn(self.base)
+
+    def load_controlnets(self, sources):
+        """MultiControlNet (diffusers MultiControlNetModel): a list of ControlNets, each given as load_controlnet takes
+        one.  The pipeline then takes control_image= as a list with one entry per net, and scale / guidance window as
+        floats or lists of that length.  Replaces whatever was loaded before."""
+        from . import controlnet
+        from ._lib import SD_MAX_CONTROLNETS
+        if not isinstance(sources, (list, tuple)):
+            raise ValueError("load_controlnets takes a list of ControlNets (load_controlnet takes one)")
+        if not 1 <= len(sources) <= SD_MAX_CONTROLNETS:
+            raise ValueError(f"load_controlnets takes 1 to {SD_MAX_CONTROLNETS} ControlNets, got {len(sources)}")
+        loaded = [controlnet.load(src, self.base.cfg) for src in sources]
+        self.unload_controlnet()
+        self._cn, self._cn_list = loaded, True
         self._attach_cn(self.base)
 
     def unload_controlnet(self):
         if self._cn is not None:
-            self.base.attach_controlnet(None)
-        self._cn = None
+            if self._cn_list:
+                self.base.attach_controlnets([])
+            else:
+                self.base.attach_controlnet(None)
+        self._cn, self._cn_list = None, False
+
+    @property
+    def controlnet_list_len(self) -> int:
+        """The nets loaded through load_controlnets; 0 when none or a single one (load_controlnet) is loaded."""
+        return len(self._cn) if self._cn_list else 0
 
     @property
     def has_controlnet(self) -> bool:
@@ -618,7 +647,17 @@ class StableDiffusionUnifiedPipeline:
         # as in diffusers: only with CFG on and a positive value
         guidance_rescale = float(guidance_rescale) if self.do_classifier_free_guidance else 0.0
         has_cn = facts.cn_loaded and not use_refiner     # (a ControlNet belongs to .base)
-        if has_cn:
+        n_cn_list = getattr(model, "controlnet_list_len", 0) if has_cn else 0
+        if n_cn_list:
+            # MultiControlNet: argument checks of the lists, before anything runs
+            from . import controlnet as _controlnet
+            controlnet_conditioning_scale, control_guidance_start, control_guidance_end = _controlnet.list_arguments(
+                n_cn_list, control_image, controlnet_conditioning_scale, control_guidance_start, control_guidance_end)
+            proc = self.control_image_processor(model)
+            sizes = [tuple(proc.preprocess(ci, height=height, width=width).shape[-2:]) for ci in control_image]
+            if len(set(sizes)) != 1:
+                raise ValueError(f"control images of different sizes after preprocessing: {sizes}")
+        elif has_cn:
             if any(isinstance(v, (list, tuple)) for v in (controlnet_conditioning_scale, control_guidance_start,
                                                           control_guidance_end)):
                 raise NotImplementedError("MultiControlNet (lists of scales / guidance windows) is not supported")
@@ -648,7 +687,8 @@ class StableDiffusionUnifiedPipeline:
                 width = width or image.shape[-1] * model.vae_scale_factor
         if has_cn and image is None and (height is None or width is None):
             # txt2img: the run's size comes from the control image (diffusers' check_image / prepare_image)
-            ci = self.control_image_processor(model).preprocess(control_image, height=height, width=width)
+            first = control_image[0] if n_cn_list else control_image       # (a list: the first net's image)
+            ci = self.control_image_processor(model).preprocess(first, height=height, width=width)
             height, width = ci.shape[-2], ci.shape[-1]
         height = height or unet.config.sample_size * model.vae_scale_factor
         width = width or unet.config.sample_size * model.vae_scale_factor
@@ -808,7 +848,11 @@ class StableDiffusionUnifiedPipeline:
 
         control = None
         if has_cn:
-            control = self.prepare_control_image(model, control_image, height, width, batch_size, num_images_per_prompt)
+            if n_cn_list:
+                control = [self.prepare_control_image(model, ci, height, width, batch_size, num_images_per_prompt)
+                           for ci in control_image]
+            else:
+                control = self.prepare_control_image(model, control_image, height, width, batch_size, num_images_per_prompt)
 
         if self.do_classifier_free_guidance and edit:
             prompt_embeds = _p2p.embed_rows(prompt_embeds, negative_prompt_embeds)       # [text ; image ; uncond]
@@ -874,10 +918,10 @@ class StableDiffusionUnifiedPipeline:
         # per prompt image (its batch under CFG maps sample b onto image b mod N: diffusers' cat([image] * 2))
         cn_scales = None
         if control is not None:
-            n = len(timesteps_host)
-            cn_scales = [float(controlnet_conditioning_scale) *
-                         (1.0 - float(i / n < control_guidance_start or (i + 1) / n > control_guidance_end))
-                         for i in range(n)]
+            from .controlnet import keep_schedule
+            rows = keep_schedule(len(timesteps_host), controlnet_conditioning_scale, control_guidance_start,
+                                 control_guidance_end)
+            cn_scales = rows if isinstance(control, list) else [r[0] for r in rows]
         # prompt_embeds is the same tensor on every step: the engine keeps its cross-attention K/V
         # projections for the duration of this loop (switched off again right after it)
         # DeepCache on this loop's UNet: iteration i runs the full forward and keeps the deep feature when
