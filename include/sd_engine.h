@@ -1245,6 +1245,11 @@ int sd_op_ip_cross_attention(const void* q, const void* k, const void* v, const 
                              int B, int Tq, int L, int T_ip, int heads, int d, int ldq, int ldk, int ldv, int ldk_ip,
                              int ldv_ip, int ldo, float ip_scale, int prescaled, int iters, float* ms_per_launch,
                              void* stream);
+/* Test hook, host only (no device needed): the shape of that launch (which takes its grid and LDS size from the same
+ * function).  out4 = query rows per block tile, tiles per (batch, head), blocks per (batch, head), bytes of dynamic LDS.
+ * With fewer blocks than tiles a block walks the tiles b, b + blocks, ... against the K / V it staged once.  The same
+ * codes as the launch for L, T_ip and d out of range and for a NaN ip_scale; all counts 0 for an empty problem. */
+int sd_ip_attention_plan(int B, int Tq, int L, int T_ip, int heads, int d, float ip_scale, int* out4);
 /* Regional cross-attention (sd_unet_set_regions), one launch:
  *   out[n, t] = sum_r w[n % Bw, t, r] softmax(s q[n, t] k[n, rL:(r+1)L]^T) v[n, rL:(r+1)L],   s = 1/sqrt(d), or 1 with
  * prescaled = 1.  q / out [B,Tq,heads*d], k / v [B,R L,heads*d], each with its own row stride (multiples of 8);
@@ -1321,6 +1326,13 @@ int sd_op_controlnet_residuals_multi(const sd_cn_multi_problem* problems, int co
  * iters > 0 (timing; synchronises): *ms_per_launch = one embedding, averaged over `iters` runs. */
 int sd_op_controlnet_cond_embed(sd_controlnet* cn, const void* image, int n, int H, int W, void* out, int iters,
                                 float* ms_per_launch, void* stream);
+/* One layer of that embedding alone: y = act(conv3x3(x, w) + bias), pad 1, stride 1 or 2, act = SiLU (silu = 1) or the
+ * identity.  x [N,3,IH,IW] f16 NCHW with Cin = 3 (nchw = 1, the control image) or [N,IH,IW,Cin] f16 NHWC with Cin in
+ * {16, 32, 96} (nchw = 0); w [Cout,Cin,3,3] f16, bias [Cout] f16, Cout % 16 == 0; y [N,OH,OW,Cout] f16 NHWC with
+ * OH = (IH - 1) / stride + 1, OW likewise.  The weights and the bias are packed by the launches a ControlNet's
+ * finalisation uses.  SD_ERR_UNSUPPORTED for any other layer (nothing is written). */
+int sd_op_cn_cond_conv(const void* x, int nchw, const void* w_oihw_f16, const void* bias_f16, int N, int IH, int IW, int Cin,
+                       int Cout, int stride, int silu, void* y, void* stream);
 
 #ifdef __cplusplus
 }

@@ -362,6 +362,7 @@ SIGNATURES = {
     "sd_attention_plan": (_I, [_I, _I, _I, _I, _I, _I, _I, C.POINTER(_I)]),
     "sd_op_ip_cross_attention": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _I, _I,
                                       C.POINTER(_F), _P]),
+    "sd_ip_attention_plan": (_I, [_I, _I, _I, _I, _I, _I, _F, C.POINTER(_I)]),
     "sd_op_region_cross_attention": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "sd_region_plan": (_I, [_I, _I, _I, C.POINTER(_I)]),
     "sd_op_region_pyramid": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
@@ -371,6 +372,7 @@ SIGNATURES = {
     "sd_op_cn_fold_scales": (_I, [C.POINTER(_P), C.POINTER(_P), C.POINTER(_F), _I, _I, _P, _P, _I, C.POINTER(_F), _P]),
     "sd_op_controlnet_residuals_multi": (_I, [C.POINTER(SdCnMultiProblem), _I, C.POINTER(_F), _I, _I, _I, C.POINTER(_F), _P]),
     "sd_op_controlnet_cond_embed": (_I, [_P, _P, _I, _I, _I, _P, _I, C.POINTER(_F), _P]),
+    "sd_op_cn_cond_conv": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
 }
 
 _lib = None

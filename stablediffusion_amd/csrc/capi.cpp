@@ -2043,6 +2043,14 @@ int sd_op_ip_cross_attention(const void* q, const void* k, const void* v, const 
     return rc;
 }
 
+int sd_ip_attention_plan(int B, int Tq, int L, int T_ip, int heads, int d, float ip_scale, int* out4) {
+    if (!out4) { set_error("sd_ip_attention_plan: null argument"); return SD_ERR_INVALID; }
+    IpPlan pl;
+    if (int rc = ip_attention_plan(B, Tq, L, T_ip, heads, d, ip_scale, &pl)) return rc;
+    out4[0] = pl.tile_rows; out4[1] = pl.qtiles; out4[2] = pl.qblocks; out4[3] = pl.lds_bytes;
+    return SD_OK;
+}
+
 int sd_op_region_cross_attention(const void* q, const void* k, const void* v, const float* w, void* out, int B, int Tq, int L,
                                  int R, int heads, int d, int ldq, int ldk, int ldv, int ldo, int Bw, int prescaled,
                                  void* stream) {
@@ -2244,6 +2252,27 @@ int sd_op_controlnet_cond_embed(sd_controlnet* cn, const void* image, int n, int
     const int C0 = cn->impl.cfg.block_out_channels[0];
     return run_op_on_arena(static_cast<hipStream_t>(stream), iters, ms_per_launch, [&](Ctx& c) {
         cn->impl.run_cond_embed(c, static_cast<const half_t*>(image), n, H, W, View(static_cast<half_t*>(out), C0, C0));
+    });
+}
+
+int sd_op_cn_cond_conv(const void* x, int nchw, const void* w_oihw_f16, const void* bias_f16, int N, int IH, int IW, int Cin,
+                       int Cout, int stride, int silu, void* y, void* stream) {
+    if (!x || !w_oihw_f16 || !bias_f16 || !y) { set_error("sd_op_cn_cond_conv: null argument"); return SD_ERR_INVALID; }
+    CnCondConvParams p;
+    p.x = static_cast<const half_t*>(x); p.nchw = nchw != 0;
+    p.y = static_cast<half_t*>(y);
+    p.N = N; p.IH = IH; p.IW = IW; p.Cin = Cin; p.Cout = Cout; p.stride = stride; p.silu = silu != 0;
+    if (stride == 1 || stride == 2) { p.OH = (IH - 1) / stride + 1; p.OW = (IW - 1) / stride + 1; }
+    if (!cn_cond_conv_supported(p)) { set_error("sd_op_cn_cond_conv: unsupported layer"); return SD_ERR_UNSUPPORTED; }
+    // the weights and the bias as ControlNet::finalize packs them, here into the entry's arena
+    return run_op_on_arena(static_cast<hipStream_t>(stream), 0, nullptr, [&](Ctx& c) {
+        float* w = c.arena->alloc_f((long)Cout * Cin * 9);
+        float* b = c.arena->alloc_f(Cout);
+        if (c.dry || c.err) return;
+        c.err = launch_cn_pack_cond(static_cast<const half_t*>(w_oihw_f16), w, Cout, Cin, c.stream);
+        if (!c.err) c.err = launch_f16_to_f32(static_cast<const half_t*>(bias_f16), b, Cout, c.stream);
+        p.w = w; p.bias = b;
+        if (!c.err) c.err = launch_cn_cond_conv(p, c.stream);
     });
 }
 

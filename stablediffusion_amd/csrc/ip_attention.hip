@@ -106,30 +106,25 @@ __global__ __launch_bounds__(64 * NWV) void ip_xattn_kernel(const half_t* __rest
 #endif  // __HIP_DEVICE_COMPILE__
 }
 
-template <int D, int QT, int NWV>
-int launch_ip(const half_t* q, const half_t* k, const half_t* v, const half_t* kip, const half_t* vip, half_t* out, int B,
-              int Tq, int L, int Tip, int heads, long ldq, long ldk, long ldv, long ldki, long ldvi, long ldo, float lam,
-              bool prescaled, hipStream_t s) {
+// Every instantiation below runs 16 * kIpQT * kIpNWV = 64 queries per block tile.
+constexpr int kIpQT = 1, kIpNWV = 4;
+
+template <int D>
+int launch_ip(const IpPlan& pl, const half_t* q, const half_t* k, const half_t* v, const half_t* kip, const half_t* vip,
+              half_t* out, int B, int Tq, int L, int Tip, int heads, long ldq, long ldk, long ldv, long ldki, long ldvi,
+              long ldo, float lam, bool prescaled, hipStream_t s) {
     constexpr int STR = ip_kstr(D) + ip_vstr(D);
     constexpr size_t lds_max = (size_t)32 * (kMaxTextSteps + kMaxIpSteps) * STR * 2;
     static_assert(lds_max <= 160 * 1024, "LDS");
     static PerDeviceOnce attr_once;
     if (attr_once.first()) {
-        SD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&ip_xattn_kernel<D, QT, NWV>),
+        SD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&ip_xattn_kernel<D, kIpQT, kIpNWV>),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
     }
-    const int rows = 32 * ((L + 31) / 32) + (lam != 0.f ? 32 * ((Tip + 31) / 32) : 0);
-    const size_t lds = (size_t)rows * STR * 2;
     const float scale_log2e = prescaled ? 1.0f : 1.4426950408889634f / sqrtf((float)D);
-    // enough blocks for about four per CU, each walking several query tiles against the K / V it staged
-    constexpr int QB = 16 * QT * NWV;
-    const int qtiles = cdiv(Tq, QB);
-    const long bh = (long)B * heads;
-    int qblocks = (int)((1024 + bh - 1) / bh);
-    if (qblocks > qtiles) qblocks = qtiles;
-    if (qblocks < 1) qblocks = 1;
-    hipLaunchKernelGGL((ip_xattn_kernel<D, QT, NWV>), dim3((unsigned)(bh * qblocks)), dim3(64 * NWV), lds, s, q, k, v, kip,
-                       vip, out, Tq, L, Tip, heads, ldq, ldk, ldv, ldki, ldvi, ldo, scale_log2e, lam, qblocks);
+    hipLaunchKernelGGL((ip_xattn_kernel<D, kIpQT, kIpNWV>), dim3((unsigned)((long)B * heads * pl.qblocks)), dim3(64 * kIpNWV),
+                       (size_t)pl.lds_bytes, s, q, k, v, kip, vip, out, Tq, L, Tip, heads, ldq, ldk, ldv, ldki, ldvi, ldo,
+                       scale_log2e, lam, pl.qblocks);
     SD_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -163,24 +158,41 @@ int launch_axpy_f16(half_t* y, long ldy, const half_t* x, long ldx, long rows, i
 
 bool ip_attention_supported(int d) { return d == 32 || d == 40 || d == 64 || d == 80 || d == 160; }
 
+int ip_attention_plan(int B, int Tq, int L, int Tip, int heads, int d, float ip_scale, IpPlan* pl) {
+    *pl = IpPlan();
+    if (L < 1 || L > 32 * kMaxTextSteps) { set_error("ip attention: text length must be in [1, 160]"); return 4; }
+    if (Tip < 1 || Tip > 32 * kMaxIpSteps) { set_error("ip attention: image tokens must be in [1, 64]"); return 4; }
+    if (!(ip_scale == ip_scale)) { set_error("ip attention: scale is NaN"); return 1; }
+    if (!ip_attention_supported(d)) { set_error("ip attention: unsupported head dim " + std::to_string(d)); return 4; }
+    pl->tile_rows = 16 * kIpQT * kIpNWV;
+    if (B <= 0 || Tq <= 0 || heads <= 0) return 0;      // nothing to launch
+    // all text keys and values, and the image ones unless ip_scale == 0, in rows padded to 32-key steps
+    const int rows = 32 * ((L + 31) / 32) + (ip_scale != 0.f ? 32 * ((Tip + 31) / 32) : 0);
+    pl->lds_bytes = rows * (ip_kstr(d) + ip_vstr(d)) * 2;
+    // enough blocks for about four per CU, each walking several query tiles against the K / V it staged
+    pl->qtiles = cdiv(Tq, pl->tile_rows);
+    const long bh = (long)B * heads;
+    long qblocks = (1024 + bh - 1) / bh;
+    if (qblocks > pl->qtiles) qblocks = pl->qtiles;
+    if (qblocks < 1) qblocks = 1;
+    pl->qblocks = (int)qblocks;
+    return 0;
+}
+
 int launch_ip_attention(const half_t* q, const half_t* k, const half_t* v, const half_t* kip, const half_t* vip,
                         half_t* out, int B, int Tq, int L, int Tip, int heads, int d, long ldq, long ldk, long ldv,
                         long ldki, long ldvi, long ldo, float ip_scale, int prescaled, hipStream_t s) {
     if ((ldq | ldk | ldv | ldki | ldvi | ldo) % 8 != 0) { set_error("ip attention: row strides must be multiples of 8"); return 1; }
     if (B <= 0 || Tq <= 0 || heads <= 0) return 0;
-    if (L < 1 || L > 32 * kMaxTextSteps) { set_error("ip attention: text length must be in [1, 160]"); return 4; }
-    if (Tip < 1 || Tip > 32 * kMaxIpSteps) { set_error("ip attention: image tokens must be in [1, 64]"); return 4; }
-    if (!(ip_scale == ip_scale)) { set_error("ip attention: scale is NaN"); return 1; }
+    IpPlan pl;
+    if (int rc = ip_attention_plan(B, Tq, L, Tip, heads, d, ip_scale, &pl)) return rc;
     const bool ps = prescaled != 0;
     switch (d) {
-        case 32: return launch_ip<32, 1, 4>(q, k, v, kip, vip, out, B, Tq, L, Tip, heads, ldq, ldk, ldv, ldki, ldvi, ldo, ip_scale, ps, s);
-        case 40: return launch_ip<40, 1, 4>(q, k, v, kip, vip, out, B, Tq, L, Tip, heads, ldq, ldk, ldv, ldki, ldvi, ldo, ip_scale, ps, s);
-        case 64: return launch_ip<64, 1, 4>(q, k, v, kip, vip, out, B, Tq, L, Tip, heads, ldq, ldk, ldv, ldki, ldvi, ldo, ip_scale, ps, s);
-        case 80: return launch_ip<80, 1, 4>(q, k, v, kip, vip, out, B, Tq, L, Tip, heads, ldq, ldk, ldv, ldki, ldvi, ldo, ip_scale, ps, s);
-        case 160: return launch_ip<160, 1, 4>(q, k, v, kip, vip, out, B, Tq, L, Tip, heads, ldq, ldk, ldv, ldki, ldvi, ldo, ip_scale, ps, s);
-        default:
-            set_error("ip attention: unsupported head dim " + std::to_string(d));
-            return 4;
+        case 32: return launch_ip<32>(pl, q, k, v, kip, vip, out, B, Tq, L, Tip, heads, ldq, ldk, ldv, ldki, ldvi, ldo, ip_scale, ps, s);
+        case 40: return launch_ip<40>(pl, q, k, v, kip, vip, out, B, Tq, L, Tip, heads, ldq, ldk, ldv, ldki, ldvi, ldo, ip_scale, ps, s);
+        case 64: return launch_ip<64>(pl, q, k, v, kip, vip, out, B, Tq, L, Tip, heads, ldq, ldk, ldv, ldki, ldvi, ldo, ip_scale, ps, s);
+        case 80: return launch_ip<80>(pl, q, k, v, kip, vip, out, B, Tq, L, Tip, heads, ldq, ldk, ldv, ldki, ldvi, ldo, ip_scale, ps, s);
+        default: return launch_ip<160>(pl, q, k, v, kip, vip, out, B, Tq, L, Tip, heads, ldq, ldk, ldv, ldki, ldvi, ldo, ip_scale, ps, s);
     }
 }
 

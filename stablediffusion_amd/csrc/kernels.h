@@ -279,6 +279,12 @@ int launch_ip_attention(const half_t* q, const half_t* k, const half_t* v, const
                         half_t* out, int B, int Tq, int L, int Tip, int heads, int d, long ldq, long ldk, long ldv,
                         long ldki, long ldvi, long ldo, float ip_scale, int prescaled, hipStream_t s);
 bool ip_attention_supported(int d);
+// ip_attention_plan: the launch's shape -- a block tile of `tile_rows` queries, `qtiles` of them per (batch, head),
+// `qblocks` blocks per (batch, head) (a block walks the tiles qblk, qblk + qblocks, ... when qblocks < qtiles) and
+// `lds_bytes` of dynamic LDS.  Returns the launch's codes for L, Tip, a NaN scale and d; all zero counts for an empty
+// problem.  Host only; launch_ip_attention takes its grid and LDS size from it.
+struct IpPlan { int tile_rows = 0, qtiles = 0, qblocks = 0, lds_bytes = 0; };
+int ip_attention_plan(int B, int Tq, int L, int Tip, int heads, int d, float ip_scale, IpPlan* pl);
 int launch_axpy_f16(half_t* y, long ldy, const half_t* x, long ldx, long rows, int cols, float a, hipStream_t s);
 // Regional prompts (region_attention.hip), one launch:
 //   out[n, t] = sum_r w[n % Bw, t, r] softmax(s q[n, t] k[n, rL:(r+1)L]^T) v[n, rL:(r+1)L],   s as above

@@ -6,6 +6,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import cn_cases as cc
 from cn_oracle import cond_embedding, synth_cn_state_dict, unet_cn_forward
 from conftest import rel_l2
 from oracle import unet_ref
@@ -110,6 +111,108 @@ def test_residual_op_rejects(engine_lib):
     arr[0] = _lib.SdCnProblem(x.data_ptr(), 96, w.data_ptr(), b.data_ptr(), buf.data_ptr(), buf.stride(0), 64, 96)
     assert engine_lib.sd_op_controlnet_residuals(arr, 1, 1.0, 0, 0, None, stream()) == 4
     assert engine_lib.sd_op_controlnet_residuals(arr, 17, 1.0, 0, 0, None, stream()) == 1
+
+
+GUARD_ROWS, GUARD_COLS = 2, 24
+SENTINEL = 0x7E5A              # an fp16 NaN pattern, compared as int16
+
+
+def _run_table(lib, table, mode, seed):
+    """One sd_op_controlnet_residuals call on a table of (M, C) problems, every y inside an int16 sentinel buffer with
+    guard rows around it and guard columns to its right.  Returns [(got float64 [M, C], want, bound)]."""
+    probs = [cc.residual_problem(M, C_, seed + i) for i, (M, C_) in enumerate(table)]
+    dev = []
+    arr = (_lib.SdCnProblem * len(probs))()
+    for i, (x, w, b, y0) in enumerate(probs):
+        M, C_ = x.shape
+        buf = torch.full((M + 2 * GUARD_ROWS, C_ + GUARD_COLS), SENTINEL, dtype=torch.int16, device="cuda")
+        buf[GUARD_ROWS:GUARD_ROWS + M, :C_] = y0.view(torch.int16).cuda()
+        xd, wd, bd = x.cuda(), w.cuda(), b.cuda()
+        dev.append((xd, wd, bd, buf))
+        arr[i] = _lib.SdCnProblem(xd.data_ptr(), C_, wd.data_ptr(), bd.data_ptr(), buf[GUARD_ROWS:].data_ptr(), buf.stride(0), M, C_)
+    rc = lib.sd_op_controlnet_residuals(arr, len(probs), cc.RES_SCALE, mode, 0, None, stream())
+    assert rc == 0, lib.sd_last_error()
+    torch.cuda.synchronize()
+    out = []
+    for (x, w, b, y0), (*_, buf) in zip(probs, dev):
+        M, C_ = x.shape
+        hb = buf.cpu()
+        assert (hb[:GUARD_ROWS] == SENTINEL).all() and (hb[GUARD_ROWS + M:] == SENTINEL).all(), "guard rows were written"
+        assert (hb[:, C_:] == SENTINEL).all(), "guard columns were written"
+        got = hb[GUARD_ROWS:GUARD_ROWS + M, :C_].contiguous().view(torch.float16).double()
+        out.append((got,) + cc.residual_reference(x, w, b, y0, C.c_float(cc.RES_SCALE).value))
+    return out
+
+
+@pytest.mark.parametrize("mode", [0, 1], ids=["grouped", "unfused"])
+@pytest.mark.parametrize("table", sorted(cc.RES_TABLES))
+def test_residuals_element_by_element(engine_lib, table, mode):
+    """cn_residual_kernel (mode 0) on a full table of 16 problems -- M around the 32-row wave slab and the 128-row
+    tile, C from 64 to 1280 -- and on a table of one, per element against float64 with the n = 1 form of the chained
+    bound of tests/test_multi_controlnet_gpu.py; the per-problem GEMMs (mode 1) on the same data meet the same bound."""
+    for (M, C_), (got, want, bound) in zip(cc.RES_TABLES[table], _run_table(engine_lib, cc.RES_TABLES[table], mode, seed=77)):
+        assert torch.isfinite(got).all()
+        err = (got - want).abs()
+        print("residuals %s mode %d M %d C %d: rel_l2 %.2e, worst |err| / bound %.3f" % (table, mode, M, C_, rel_l2(got, want),
+                                                                                        (err / bound).max()))
+        worst = (err - bound).argmax()
+        assert (err <= bound).all(), (M, C_, "element", int(worst), err.flatten()[worst].item(), bound.flatten()[worst].item())
+
+
+# ------------------------------------------------------------------------- one conditioning layer, per element
+def _run_cond_conv(lib, case, x, w, b):
+    """sd_op_cn_cond_conv on CPU operands (x NCHW); returns (code, int16 bits [N, OH, OW, Cout]) after checking the
+    guard rows in front of and behind y."""
+    OH, OW = cc.out_hw(case)
+    rows = case.N * OH * OW
+    xd = (x if case.Cin == 3 else x.permute(0, 2, 3, 1)).contiguous().cuda()
+    wd, bd = w.cuda(), b.cuda()
+    G = 4
+    ybuf = torch.full((G + rows + G, case.Cout), SENTINEL, dtype=torch.int16, device="cuda")
+    code = lib.sd_op_cn_cond_conv(C.c_void_p(xd.data_ptr()), 1 if case.Cin == 3 else 0, C.c_void_p(wd.data_ptr()),
+                                  C.c_void_p(bd.data_ptr()), case.N, case.IH, case.IW, case.Cin, case.Cout, case.stride,
+                                  case.silu, C.c_void_p(ybuf[G:].data_ptr()), stream())
+    torch.cuda.synchronize()
+    hb = ybuf.cpu()
+    assert (hb[:G] == SENTINEL).all() and (hb[G + rows:] == SENTINEL).all(), "guard rows around y were written"
+    return code, hb[G:G + rows].contiguous().view(case.N, OH, OW, case.Cout)
+
+
+@pytest.mark.parametrize("case", cc.CASES, ids=[cc.case_id(c) for c in cc.CASES])
+def test_cond_conv_layer_element_by_element(engine_lib, case):
+    """cn_cond_conv_kernel alone, every template variant at stride 1 and 2, against float64 conv2d + SiLU of the fp16
+    operands with the bound of cn_cases.bound (tests/test_cn_cases.py proves it on an emulation); the border ring, where
+    taps fall outside the image, is reported and asserted on its own."""
+    x, w, b, out, y, A = cc.inputs_and_reference(case)
+    code, bits = _run_cond_conv(engine_lib, case, x, w, b)
+    assert code == 0, engine_lib.sd_last_error()
+    got = bits.view(torch.float16).double()
+    assert torch.isfinite(got).all()
+    ratio = (got - out).abs() / cc.bound(case, out, y, A)
+    ring = cc.border_ring(case)
+    assert ring.any()
+    print("%s: rel_l2 %.2e, worst |err| / bound %.3f, on the border ring %.3f" % (cc.case_id(case), rel_l2(got, out), ratio.max(),
+                                                                               ratio[:, ring].max()))
+    assert ratio[:, ring].max() <= 1.0, "a border pixel"
+    assert ratio.max() <= 1.0
+
+
+def test_cond_conv_layer_rejections_write_nothing(engine_lib):
+    for case in [cc.Case(8, 16, 1, 1, 4, 4, 1), cc.Case(16, 24, 1, 1, 4, 4, 1), cc.Case(16, 16, 3, 1, 4, 4, 1),
+                 cc.Case(16, 16, 1, 0, 4, 4, 1)]:
+        x = torch.zeros(max(case.N, 1), case.Cin, 4, 4, dtype=torch.float16)
+        w = torch.zeros(case.Cout, case.Cin, 3, 3, dtype=torch.float16)
+        OH, OW = cc.out_hw(case)
+        ybuf = torch.full((16 + max(case.N, 1) * OH * OW, case.Cout), SENTINEL, dtype=torch.int16, device="cuda")
+        xd, wd, bd = x.cuda(), w.cuda(), torch.zeros(case.Cout, dtype=torch.float16, device="cuda")
+        code = engine_lib.sd_op_cn_cond_conv(C.c_void_p(xd.data_ptr()), 0, C.c_void_p(wd.data_ptr()), C.c_void_p(bd.data_ptr()),
+                                             case.N, 4, 4, case.Cin, case.Cout, case.stride, 1, C.c_void_p(ybuf.data_ptr()),
+                                             stream())
+        torch.cuda.synchronize()
+        assert code == 4, case
+        assert engine_lib.sd_last_error()
+        assert (ybuf == SENTINEL).all()
+    assert engine_lib.sd_op_cn_cond_conv(None, 0, None, None, 1, 4, 4, 16, 16, 1, 1, None, stream()) == 1
 
 
 # ------------------------------------------------------------------------------------ conditioning embedding
