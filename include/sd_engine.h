@@ -110,6 +110,7 @@ typedef struct sd_clip sd_clip;
 typedef struct sd_clip_vision sd_clip_vision;
 typedef struct sd_ip_adapter sd_ip_adapter;
 typedef struct sd_controlnet sd_controlnet;
+typedef struct sd_motion sd_motion;
 
 /* -- library ------------------------------------------------------------------------------- */
 const char* sd_last_error(void);
@@ -478,6 +479,55 @@ int sd_controlnet_weight_info(const sd_controlnet* cn, int index, const char** k
 int sd_controlnet_set_weight(sd_controlnet* cn, const char* key, const void* data, const int64_t* shape, int ndim,
                              int dtype);
 int sd_controlnet_finalize(sd_controlnet* cn);
+
+/* -- AnimateDiff motion adapter (diffusers 0.27.2 MotionAdapter / UNetMotionModel / TransformerTemporalModel, recalled:
+ * the library is not installed where this was written; tests/motion_oracle.py restates the semantics in float) ----------
+ * The UNet's batch is V videos of num_frames consecutive frames; the text embedding of a video is repeated per frame.
+ * One motion module runs behind every (resnet, transformer) pair of the down and up blocks (behind the resnet in a block
+ * without attention) and, with use_mid_block, behind the mid block's transformer, before its second resnet; what goes
+ * into a skip connection is the module's output.  A module, on x [V F, C, H, W]:
+ *   GroupNorm(32, eps 1e-6) with statistics over a group's channels and all F H W positions of one video; proj_in
+ *   (Linear, bias); h += to_out(attn(LN1(h) + pe)); h += to_out2(attn(LN2(h) + pe)); h += FF_geglu(LN3(h)); proj_out;
+ *   + x.  Both attentions are self-attention over the F frames of one pixel of one video with num_heads[block] heads
+ * (to_q / to_k / to_v without bias), pe[f, 2i] = sin(f 10000^(-2i/C)), pe[f, 2i+1] = cos(same) for
+ * f < max_seq_length <= 32.  The position rows are folded into a per-frame fp32 table at sd_motion_finalize
+ * (sd_op_motion_pos_bias) and the attention is one launch on the q|k|v rows in place (sd_op_temporal_attention).
+ * Weight keys are the diffusers MotionAdapter's ("down_blocks.0.motion_modules.1.transformer_blocks.0.attn1.to_q.weight",
+ * "mid_block.motion_modules.0.proj_in.bias", ...) without the stored pos_embed.pe tables. */
+typedef struct sd_motion_config {
+    int32_t num_blocks;
+    int32_t block_out_channels[SD_MAX_BLOCKS];
+    int32_t num_heads[SD_MAX_BLOCKS];              /* per down block; reversed for up blocks */
+    int32_t layers_per_block;
+    int32_t max_seq_length;                        /* 1..32 */
+    int32_t use_mid_block;
+} sd_motion_config;
+/* For the UNet `u`: blocks, channels and layers_per_block must be the UNet's, every head dim C / heads one of 32, 40, 64,
+ * 80, 160 and every C a multiple of 64 (SD_ERR_INVALID / SD_ERR_UNSUPPORTED). */
+int sd_motion_create(const sd_unet* u, const sd_motion_config* cfg, sd_motion** out);
+int sd_motion_destroy(sd_motion* m);              /* detaches it from its UNet first */
+int sd_motion_num_weights(const sd_motion* m);
+int sd_motion_weight_info(const sd_motion* m, int index, const char** key, int64_t* shape4, int* ndim);
+int sd_motion_set_weight(sd_motion* m, const char* key, const void* data, const int64_t* shape, int ndim, int dtype);
+int sd_motion_finalize(sd_motion* m);
+/* Attach a finalized adapter created for this UNet (NULL detaches: every forward is again exactly the plain one, with the
+ * same launches).  Attached, nothing changes either until a call names its frames:
+ * sd_unet_forward_motion = sd_unet_forward on B = V num_frames frames with the modules running (num_frames = 0: the plain
+ * forward); sd_unet_forward_cfg_ex = sd_unet_forward_cfg with num_frames, on B = V num_frames latents: the shared CFG
+ * prefix ends before the first module, the CFG batch is 2V videos.
+ * SD_ERR_INVALID: B % num_frames != 0, num_frames < 0 or > max_seq_length, num_frames > 0 without an adapter.
+ * SD_ERR_UNSUPPORTED, nothing launched, with num_frames >= 1: graph replay, a DeepCache store / reuse mode, token merging,
+ * HyperTile, sd_unet_forward_pag, sd_unet_forward_concat, regional prompts, an attached ControlNet, an IP-Adapter at a
+ * non-zero scale (at scale 0 the text attention runs alone and image_embeds may be NULL), FreeU and text_time UNets -- none is
+ * composed with frames yet, nothing is ignored.  timestep_cond cannot be expressed with frames: sd_unet_forward_tc names
+ * none, and the two entries that do take no timestep_cond.
+ * With debug taps on a module records its input and output as "<block>.motion_modules.<j>". */
+int sd_unet_set_motion(sd_unet* u, sd_motion* m);
+int sd_unet_forward_motion(sd_unet* u, const void* sample, const float* timesteps, const void* ehs, int ehs_len, int num_frames,
+                           void* out, int B, int H, int W, void* stream);
+int sd_unet_forward_cfg_ex(sd_unet* u, const void* latents, const float* timesteps, const void* ehs, int ehs_len,
+                           const void* add_text, const float* add_time_ids, const void* image_embeds, int n_img,
+                           float in_scale, int share, int num_frames, void* out, int B, int H, int W, void* stream);
 
 /* -- VAE: replaces the object in SDModelWrapper.vae (stable_diffusion.py:110-116) ------------ */
 int sd_vae_create(const sd_vae_config* cfg, sd_vae** out);
@@ -1208,6 +1258,30 @@ int sd_op_hypertile_gather(const void* src, int64_t lds, int cols, int B, int Hs
                            void* stream);
 int sd_op_hypertile_scatter(const void* src, int64_t lds, int cols, int B, int Hs, int Ws, int nh, int nw, void* dst, int64_t ldd,
                             void* stream);
+/* Temporal self-attention of an AnimateDiff motion module (diffusers 0.27.2 TransformerTemporalModel, recalled): every
+ * pixel p of every video v attends over its own F frames, in one launch and without a permuted copy on either side.
+ * Frame f of the pixel is row (v F + f) HW + p of q, k, v and out (f16, their own row strides: q | k | v are read where the
+ * row-wise q|k|v GEMM left them), heads split the columns [h d, (h + 1) d):
+ *   out_f = sum_g softmax_g(s (q_f + bias[f, 0:C])(k_g + bias[g, C:2C])^T) (v_g + bias[g, 2C:3C]),   C = heads d,
+ * s = 1 / sqrt(d), or 1 with prescaled != 0 (q and its bias already carry log2(e) / sqrt(d), as the UNet's packed query
+ * projections do; the exponential is then base 2).  bias [>= F, ldb] f32 is the position term of sd_op_motion_pos_bias,
+ * added in fp32 before the operand is rounded to f16; NULL: none.  The softmax is exact over the F keys (one pass, no
+ * running maximum); probabilities are rounded to nearest f16 and normalised by the sum of the rounded values, fp32
+ * accumulation, f16 store.  F = 1 returns f16(v + bias) bit for bit.  Nothing is read or written outside the V F HW rows
+ * and the heads d (3 heads d for the table) columns.
+ * 1 <= F <= 32, d in {32, 40, 64, 80, 160}: otherwise SD_ERR_UNSUPPORTED.  SD_ERR_INVALID: row strides not multiples of 8
+ * or below heads d, ldb not a multiple of 4 or below 3 heads d, pointers not 16-byte aligned, V F HW >= 2^31.
+ * sd_temporal_attention_plan names what runs for a shape, out7 = (head dim, 16-frame tiles per axis, pixels per block,
+ * waves per block, contraction of the PV MFMA: 16 = 16x16x16 / 32 = 16x16x32, LDS bytes per block, blocks); the launch
+ * dispatches on the same function.  Needs no device.
+ * sd_op_motion_pos_bias: out[f, n] = (n < scale_rows ? scale : 1) sum_c pe[f, c] w[n, c] for f < F, n < N, with
+ * pe[f, 2i] = sin(f 10000^(-2i/C)), pe[f, 2i+1] = cos(same) and w [N, C] f16 a projection weight BEFORE any LayerNorm
+ * fold: (LN(h) + pe_f) W^T = LN(h) W^T + pe_f W^T.  float64 inside, one rounding to f32.  C % 8 == 0, C <= 4096. */
+int sd_temporal_attention_plan(int V, int F, int HW, int heads, int d, int64_t* out7);
+int sd_op_temporal_attention(const void* q, const void* k, const void* v, void* out, const float* bias, int64_t ldq, int64_t ldk,
+                             int64_t ldv, int64_t ldo, int64_t ldb, int V, int F, int HW, int heads, int d, int prescaled,
+                             void* stream);
+int sd_op_motion_pos_bias(const void* w, int N, int C, int F, float scale, int scale_rows, float* out, int64_t ldo, void* stream);
 /* LayerNorm over the last dim of [rows, C] f16. */
 int sd_op_layernorm(const void* x, const void* gamma, const void* beta, void* y, int rows, int C,
                     float eps, void* stream);

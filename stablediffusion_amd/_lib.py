@@ -120,6 +120,18 @@ SD_IP_PROJ_LINEAR = 0
 SD_IP_PROJ_RESAMPLER = 1
 
 
+class SdMotionConfig(C.Structure):
+    """sd_motion_config (include/sd_engine.h): an AnimateDiff motion adapter for a UNet topology."""
+    _fields_ = [
+        ("num_blocks", C.c_int32),
+        ("block_out_channels", C.c_int32 * SD_MAX_BLOCKS),
+        ("num_heads", C.c_int32 * SD_MAX_BLOCKS),
+        ("layers_per_block", C.c_int32),
+        ("max_seq_length", C.c_int32),
+        ("use_mid_block", C.c_int32),
+    ]
+
+
 class SdProfEntry(C.Structure):
     _fields_ = [("kernel", C.c_char * 64), ("flops", C.c_double), ("bytes", C.c_double),
                 ("ms", C.c_double), ("launches", C.c_int64)]
@@ -355,6 +367,18 @@ SIGNATURES = {
     "sd_hypertile_plan": (_I, [_I, _I, _I, _I, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32)]),
     "sd_op_hypertile_gather": (_I, [_P, _I64, _I, _I, _I, _I, _I, _I, _P, _I64, _P]),
     "sd_op_hypertile_scatter": (_I, [_P, _I64, _I, _I, _I, _I, _I, _I, _P, _I64, _P]),
+    "sd_motion_create": (_I, [_P, C.POINTER(SdMotionConfig), C.POINTER(C.c_void_p)]),
+    "sd_motion_destroy": (_I, [_P]),
+    "sd_motion_num_weights": (_I, [_P]),
+    "sd_motion_weight_info": (_I, [_P, _I, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.POINTER(_I)]),
+    "sd_motion_set_weight": (_I, [_P, C.c_char_p, _P, C.POINTER(C.c_int64), _I, _I]),
+    "sd_motion_finalize": (_I, [_P]),
+    "sd_unet_set_motion": (_I, [_P, _P]),
+    "sd_unet_forward_motion": (_I, [_P, _P, _P, _P, _I, _I, _P, _I, _I, _I, _P]),
+    "sd_unet_forward_cfg_ex": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _I, _F, _I, _I, _P, _I, _I, _I, _P]),
+    "sd_temporal_attention_plan": (_I, [_I, _I, _I, _I, _I, C.POINTER(_I64)]),
+    "sd_op_temporal_attention": (_I, [_P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I, _I, _I, _I, _I, _I, _P]),
+    "sd_op_motion_pos_bias": (_I, [_P, _I, _I, _I, _F, _I, _P, _I64, _P]),
     "sd_op_layernorm": (_I, [_P, _P, _P, _P, _I, _I, _F, _P]),
     "sd_op_layernorm_ex": (_I, [_P, _I64, _P, _P, _P, _I64, _I64, _I, _F, _P]),
     "sd_op_row_stats": (_I, [_P, _I64, _P, _I64, _I, _P]),

@@ -18,6 +18,10 @@ struct sd_controlnet {
     ControlNet impl;
     sd_controlnet(const sd_unet_config& c, int cc) : impl(c, cc) {}
 };
+struct sd_motion {
+    MotionAdapter impl;
+    explicit sd_motion(const sd_motion_config& c) : impl(c) {}
+};
 struct sd_ip_adapter {
     IPAdapter impl;
     sd_ip_adapter(const sd_unet_config& c, const sd_ip_projection_config& p) : impl(c, p) {}
@@ -162,6 +166,16 @@ int tap_read(const sd::TapSink& t, int index, void* dst, int64_t bytes) {
     SD_HIP_CHECK(hipDeviceSynchronize());
     SD_HIP_CHECK(hipMemcpy(dst, e.dev, e.bytes, hipMemcpyDeviceToHost));
     return SD_OK;
+}
+
+bool motion_fits(const sd_unet_config& u, const sd_motion_config& m, std::string* why) {
+    if (m.num_blocks != u.num_blocks || m.layers_per_block != u.layers_per_block) {
+        *why = "num_blocks / layers_per_block differ from the UNet's";
+        return false;
+    }
+    for (int i = 0; i < u.num_blocks; ++i)
+        if (m.block_out_channels[i] != u.block_out_channels[i]) { *why = "block_out_channels differ from the UNet's"; return false; }
+    return true;
 }
 
 bool controlnet_fits(const sd_unet_config& u, const sd_unet_config& n, std::string* why) {
@@ -360,6 +374,65 @@ int sd_unet_forward_cfg(sd_unet* u, const void* latents, const float* timesteps,
     if (!(in_scale == in_scale)) { set_error("sd_unet_forward_cfg: in_scale is NaN"); return SD_ERR_INVALID; }
     with_images(&c, image_embeds, n_img);
     return u->impl.forward_cfg(c, in_scale, share != 0, static_cast<hipStream_t>(stream));
+}
+int sd_unet_forward_cfg_ex(sd_unet* u, const void* latents, const float* timesteps, const void* ehs, int ehs_len,
+                           const void* add_text, const float* add_time_ids, const void* image_embeds, int n_img,
+                           float in_scale, int share, int num_frames, void* out, int B, int H, int W, void* stream) {
+    UNetCall c;
+    if (!fill_call(u, latents, timesteps, ehs, ehs_len, add_text, add_time_ids, out, B, H, W, &c)) return SD_ERR_INVALID;
+    if (!(in_scale == in_scale)) { set_error("sd_unet_forward_cfg_ex: in_scale is NaN"); return SD_ERR_INVALID; }
+    with_images(&c, image_embeds, n_img);
+    c.num_frames = num_frames;
+    return u->impl.forward_cfg(c, in_scale, share != 0, static_cast<hipStream_t>(stream));
+}
+int sd_unet_forward_motion(sd_unet* u, const void* sample, const float* timesteps, const void* ehs, int ehs_len, int num_frames,
+                           void* out, int B, int H, int W, void* stream) {
+    UNetCall c;
+    if (!fill_call(u, sample, timesteps, ehs, ehs_len, nullptr, nullptr, out, B, H, W, &c)) return SD_ERR_INVALID;
+    c.num_frames = num_frames;
+    return u->impl.forward(c, static_cast<hipStream_t>(stream));
+}
+int sd_unet_set_motion(sd_unet* u, sd_motion* m) {
+    if (!u) { set_error("null handle"); return SD_ERR_INVALID; }
+    if (!u->impl.finalized) { set_error("sd_unet_set_motion before finalize"); return SD_ERR_STATE; }
+    if (m) {
+        if (!m->impl.finalized) { set_error("sd_unet_set_motion: motion adapter not finalized"); return SD_ERR_STATE; }
+        std::string why;
+        if (!motion_fits(u->impl.cfg, m->impl.mcfg, &why)) { set_error("sd_unet_set_motion: " + why); return SD_ERR_INVALID; }
+    }
+    return u->impl.set_motion(m ? &m->impl : nullptr);
+}
+int sd_motion_create(const sd_unet* u, const sd_motion_config* cfg, sd_motion** out) {
+    if (!u || !cfg || !out) { set_error("null argument"); return SD_ERR_INVALID; }
+    std::string why;
+    if (!motion_fits(u->impl.cfg, *cfg, &why)) { set_error("sd_motion_create: " + why); return SD_ERR_INVALID; }
+    if (cfg->max_seq_length < 1 || cfg->max_seq_length > 32) { set_error("sd_motion_create: max_seq_length must be in 1..32"); return SD_ERR_UNSUPPORTED; }
+    for (int i = 0; i < cfg->num_blocks; ++i) {
+        const int C = cfg->block_out_channels[i], h = cfg->num_heads[i];
+        if (h < 1 || C % h != 0 || temporal_attention_plan(1, 1, 1, h, C / h).D == 0 || C % 64 != 0) {
+            set_error("sd_motion_create: block " + std::to_string(i) + ": channels must be a multiple of 64 and the head dim one of "
+                      "32, 40, 64, 80, 160");
+            return SD_ERR_UNSUPPORTED;
+        }
+    }
+    *out = new (std::nothrow) sd_motion(*cfg);
+    if (!*out) { set_error("out of host memory"); return SD_ERR_INVALID; }
+    return SD_OK;
+}
+int sd_motion_destroy(sd_motion* m) { delete m; return SD_OK; }
+int sd_motion_num_weights(const sd_motion* m) { return m ? (int)m->impl.ws.order.size() : 0; }
+int sd_motion_weight_info(const sd_motion* m, int index, const char** key, int64_t* shape4, int* ndim) {
+    if (!m) { set_error("null handle"); return SD_ERR_INVALID; }
+    return weight_info(m->impl.ws, index, key, shape4, ndim);
+}
+int sd_motion_set_weight(sd_motion* m, const char* key, const void* data, const int64_t* shape, int ndim, int dtype) {
+    if (!m || !key || !data || !shape) { set_error("null argument"); return SD_ERR_INVALID; }
+    if (m->impl.finalized) { set_error("set_weight after finalize"); return SD_ERR_STATE; }
+    return m->impl.ws.set(key, data, shape, ndim, dtype);
+}
+int sd_motion_finalize(sd_motion* m) {
+    if (!m) { set_error("null handle"); return SD_ERR_INVALID; }
+    return m->impl.finalize();
 }
 int sd_unet_set_pag_layers(sd_unet* u, const char* const* site_keys, int count) {
     if (!u) { set_error("null handle"); return SD_ERR_INVALID; }
@@ -1980,6 +2053,29 @@ int sd_op_hypertile_scatter(const void* src, int64_t lds, int cols, int B, int H
                             void* stream) {
     return launch_hypertile_scatter(static_cast<const half_t*>(src), lds, cols, B, Hs, Ws, nh, nw, static_cast<half_t*>(dst), ldd,
                                     static_cast<hipStream_t>(stream));
+}
+
+int sd_temporal_attention_plan(int V, int F, int HW, int heads, int d, int64_t* out7) {
+    if (!out7) { set_error("sd_temporal_attention_plan: null argument"); return SD_ERR_INVALID; }
+    const TattnPlan pl = temporal_attention_plan(V, F, HW, heads, d);
+    if (pl.D == 0) {
+        set_error("temporal_attention: needs V, HW, heads >= 1, 1 <= F <= 32 and a head dim of 32, 40, 64, 80 or 160");
+        return SD_ERR_UNSUPPORTED;
+    }
+    const int64_t o[7] = {pl.D, pl.FT, pl.pixels, pl.waves, pl.pv_k, pl.lds_bytes, pl.blocks};
+    for (int i = 0; i < 7; ++i) out7[i] = o[i];
+    return SD_OK;
+}
+int sd_op_temporal_attention(const void* q, const void* k, const void* v, void* out, const float* bias, int64_t ldq, int64_t ldk,
+                             int64_t ldv, int64_t ldo, int64_t ldb, int V, int F, int HW, int heads, int d, int prescaled,
+                             void* stream) {
+    return launch_temporal_attention(static_cast<const half_t*>(q), static_cast<const half_t*>(k), static_cast<const half_t*>(v),
+                                     static_cast<half_t*>(out), bias, ldq, ldk, ldv, ldo, ldb, V, F, HW, heads, d, prescaled,
+                                     static_cast<hipStream_t>(stream));
+}
+int sd_op_motion_pos_bias(const void* w, int N, int C, int F, float scale, int scale_rows, float* out, int64_t ldo, void* stream) {
+    return launch_motion_pos_bias(static_cast<const half_t*>(w), N, C, F, scale, scale_rows, out, ldo,
+                                  static_cast<hipStream_t>(stream));
 }
 
 int sd_op_attention(const void* q, const void* k, const void* v, void* out, int B, int Tq, int Tk, int heads, int d,

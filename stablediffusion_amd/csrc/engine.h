@@ -309,6 +309,10 @@ struct Ctx {
     const TomeRun* tome = nullptr;
     // HyperTile of this forward (nullptr: off, and always inside a ControlNet's encoder, as token merging)
     const HyperTileRun* hypertile = nullptr;
+    // motion adapter of this forward (nullptr: off, and always inside a ControlNet's encoder): its modules run behind the
+    // blocks of run_down / run_mid / the up path on videos of motion_frames consecutive images
+    const struct MotionAdapter* motion = nullptr;
+    int motion_frames = 0;
     // Regional prompts of this forward (nullptr: off): the handle's weight pyramid (UNet::region_buf) for a
     // region_H x region_W sample, region_R regions in an encoder_hidden_states of region_R * (L / region_R) tokens,
     // weight batch region_Bw.  run_xformer then issues region_xattn_kernel at every attn2 instead of the plain launch.

@@ -602,6 +602,22 @@ int launch_hypertile_gather(const half_t* src, long lds, int cols, int B, int Hs
                             hipStream_t s);
 int launch_hypertile_scatter(const half_t* src, long lds, int cols, int B, int Hs, int Ws, int nh, int nw, half_t* dst, long ldd,
                              hipStream_t s);
+// Temporal self-attention of a motion module (temporal_attention.hip), one launch: every pixel p of every video v attends
+// over its F <= 32 frames; frame f of the pixel is row (v F + f) HW + p of q / k / v / out (their own row strides), heads
+// split the columns as in launch_attention.  bias: fp32 [>= F][ldb] with the q | k | v position terms at columns
+// 0 | C | 2C (C = heads d), added in fp32 before the operand is rounded to fp16; null: none.  d in {32, 40, 64, 80, 160}.
+// Returns 1 (arguments) / 4 (F, d) with the message set, nothing launched.
+struct TattnPlan { int D, FT, pixels, waves, pv_k, lds_bytes; long blocks; };   // D == 0: refused
+// FT: 16-frame tiles per axis (1 or 2), pixels per block, waves per block, contraction of the PV MFMA (16x16x16 or
+// 16x16x32), static LDS of a block, blocks of the launch.  Host only; launch_temporal_attention dispatches on it.
+TattnPlan temporal_attention_plan(int V, int F, int HW, int heads, int d);
+int launch_temporal_attention(const half_t* q, const half_t* k, const half_t* v, half_t* out, const float* bias, long ldq,
+                              long ldk, long ldv, long ldo, long ldb, int V, int F, int HW, int heads, int d, int prescaled,
+                              hipStream_t s);
+// out[f, n] = (n < scale_rows ? scale : 1) * sum_c pe[f, c] w[n, c] for f < F, n < N: the sinusoidal position rows
+// pe[f, 2i] = sin(f 10000^(-2i/C)), pe[f, 2i+1] = cos(same) pushed through a projection weight w [N][C] fp16 (float64
+// inside, one rounding to fp32).  C % 8 == 0, C <= 4096.
+int launch_motion_pos_bias(const half_t* w, int N, int C, int F, float scale, int scale_rows, float* out, long ldo, hipStream_t s);
 // den = dx x + dout m, x <- pden den + pnoise noise (m: model_out, or its CFG combine when rows == 2); noise / denoised
 // nullable.  The scheduler step of LCMScheduler in one launch.
 int launch_lcm_step(const half_t* model_out, int rows, half_t* lat, const half_t* noise, half_t* denoised, long n, float g,

@@ -100,6 +100,36 @@ bool run_xformer_tail(Ctx& c, const Xformer& t, View t3, const RowStat& st_t3, V
 struct UNet;
 struct UNetCall;
 
+// AnimateDiff motion adapter (motion.cpp; diffusers 0.27.2 MotionAdapter, recalled): one module per (resnet, transformer)
+// pair of the down and up blocks and, optionally, one in the mid block.  A module is GroupNorm(32) over a whole video,
+// proj_in, one transformer block whose two attentions are self-attention over the frames of a pixel, proj_out, + x.
+struct MotionModule {
+    NormW gn, ln1, ln2, ln3;            // (the LayerNorms are folded into qkv1 / qkv2 / ff1)
+    ConvW pin, pout, qkv1, out1, qkv2, out2, ff1, ff2;
+    float* pb1 = nullptr;               // position tables [max_seq_length][3C] fp32 of attn1 / attn2 (launch_motion_pos_bias)
+    float* pb2 = nullptr;
+    int C = 0, heads = 1;
+};
+struct MotionAdapter {
+    explicit MotionAdapter(const sd_motion_config& m);
+    ~MotionAdapter();
+    int finalize();
+
+    sd_motion_config mcfg;
+    WeightStore ws;
+    bool finalized = false;
+    std::vector<std::vector<MotionModule>> down, up;
+    MotionModule mid;
+    UNet* attached = nullptr;
+
+  private:
+    int pack_module(const std::string& p, int heads, MotionModule* m);
+};
+// out = module(x) on N = V F frames of H x W, the frames of a video consecutive; out_stats / G_out: the GroupNorm
+// summaries its last launch leaves (GnOut).  x and out may not overlap.
+void run_motion(Ctx& c, const MotionModule& m, View x, int N, int F, int H, int W, View out, const GnOut& out_stats, int G_out);
+void op_temporal_attention(Ctx& c, View qkv, const float* bias, View out, int V, int F, int HW, int heads, int d);
+
 // Every attn2 of a UNet topology as (transformer block prefix, channels): diffusers' attn_processors order
 // (down, up, mid) with mid_last, the engine's kv_all order (down, mid, up) without.
 std::vector<std::pair<std::string, int>> unet_xattn_sites(const sd_unet_config& cfg, bool mid_last);
@@ -270,6 +300,7 @@ struct UNetCall {
     int cn_idx = 0, cn_active = 0, cn_act[kCnMaxNets] = {};
     const float* tcond = nullptr;           // timestep_cond [B, time_cond_proj_dim] of a guidance-embedded UNet
     const CfgIn* cfg_in = nullptr;          // shared-CFG mode (forward_cfg)
+    int num_frames = 0;                     // motion adapter: the B images are B / num_frames videos (0: the modules do not run)
     const PagIn* pag = nullptr;             // perturbed-attention mode (forward_pag)
     // Two-source mode (forward_concat): the sample is cat([fp16(sample[n % lat_rows] * in_scale), n < zero_from ?
     // extra[n % extra_rows] : 0], dim 1) and is never handed over as a tensor; `sample` holds the lat_rows latents
@@ -295,13 +326,14 @@ struct PlanKey {
     double tome_ratio = 0.0;                // token merging: what the merged rows per block depend on (0: off)
     int tome_ds = 0, tome_sx = 0, tome_sy = 0;
     int ht_tile = 0, ht_swap = 0, ht_depth = 0; // HyperTile: what the gather buffers of the sites depend on (0: off)
+    int motion_frames = 0;                  // frames per video when a motion adapter runs, 0 otherwise
     bool operator==(const PlanKey& o) const {
         return B == o.B && H == o.H && W == o.W && L == o.L && kv_cache == o.kv_cache && ip_tokens == o.ip_tokens &&
                cfg_share == o.cfg_share && pag_groups == o.pag_groups && pag_late == o.pag_late && n_ctrl == o.n_ctrl && cn_n[0] == o.cn_n[0] &&
                cn_n[1] == o.cn_n[1] && cn_n[2] == o.cn_n[2] && cn_n[3] == o.cn_n[3] &&
                dc_depth == o.dc_depth && cat_rows == o.cat_rows && tome_ratio == o.tome_ratio && tome_ds == o.tome_ds &&
                tome_sx == o.tome_sx && tome_sy == o.tome_sy && ht_tile == o.ht_tile && ht_swap == o.ht_swap &&
-               ht_depth == o.ht_depth;
+               ht_depth == o.ht_depth && motion_frames == o.motion_frames;
     }
 };
 // What a captured graph depends on (timestep_cond's width is the configuration's: its presence changes the launches).
@@ -488,6 +520,15 @@ struct UNet : Encoder {
     // 0 when regions are off or the call may run with them; else the code (1 / 4) with the message set.  B is the batch of
     // the forward the call builds (2 B of forward_cfg's latents).
     int regions_refuse(const UNetCall& call, int B, bool pag_or_concat);
+
+    // ---- motion adapter (sd_unet_set_motion): nullptr = the forward as without the feature.  Attached, a call with
+    // num_frames >= 1 runs a module behind every (resnet, transformer) pair; what is not composed with frames is refused
+    // before anything is launched (motion_refuse).
+    MotionAdapter* motion = nullptr;
+    int set_motion(MotionAdapter* m);
+    // 0 when no module runs for this call or it may run; else the code (1 / 4) with the message set.  frames_rows: the
+    // rows the frames must divide (the latents of forward_cfg, the batch otherwise).
+    int motion_refuse(const UNetCall& call, int frames_rows, bool pag_or_concat);
 
     // ---- debug taps (sd_unet_tap; engine.h: TapSink): on, the plain forward records the input and output view of
     // every block; the modes whose launches differ from the plain forward's are refused (tap_refuses: 4 when `mode`).

@@ -495,6 +495,46 @@ void UNet::set_ip_adapter(IPAdapter* a) {
     reset_plans();
 }
 
+int UNet::set_motion(MotionAdapter* m) {
+    if (motion == m) return 0;
+    if (motion) motion->attached = nullptr;
+    if (m) {
+        if (m->attached && m->attached != this) m->attached->set_motion(nullptr);
+        m->attached = this;
+    }
+    motion = m;
+    dc_tag.clear();
+    reset_plans();
+    return 0;
+}
+
+int UNet::motion_refuse(const UNetCall& call, int frames_rows, bool pag_or_concat) {
+    const int F = call.num_frames;
+    if (F == 0) return 0;
+    if (F < 0) { set_error("unet: num_frames is negative"); return 1; }
+    if (!motion) { set_error("unet: num_frames given but no motion adapter is attached"); return 1; }
+    const char* why = nullptr;
+    if (pag_or_concat) why = "forward_pag / forward_concat";
+    else if (graph_enabled) why = "graph replay";
+    else if (dc_mode != SD_DC_PLAIN) why = "a DeepCache store / reuse mode";
+    else if (tome.ratio > 0.0) why = "token merging";
+    else if (hypertile.tile_size > 0) why = "HyperTile";
+    else if (region_R) why = "regional prompts";
+    else if (cn) why = "an attached ControlNet";
+    else if (ip && ip_scale != 0.f) why = "an IP-Adapter at a non-zero scale";
+    else if (freeu_on) why = "FreeU";
+    // (timestep_cond cannot meet frames: sd_unet_forward_tc names none, and the entries that do take no timestep_cond)
+    else if (cfg.addition_time_embed_dim > 0) why = "a text_time UNet";
+    if (why) { set_error(std::string("unet: a motion adapter runs (num_frames >= 1): ") + why + " is not supported with it"); return 4; }
+    if (F > motion->mcfg.max_seq_length) {
+        set_error("unet: num_frames " + std::to_string(F) + " exceeds the adapter's max_seq_length " +
+                  std::to_string(motion->mcfg.max_seq_length));
+        return 1;
+    }
+    if (frames_rows <= 0 || frames_rows % F != 0) { set_error("unet: the batch is no multiple of num_frames"); return 1; }
+    return 0;
+}
+
 // ------------------------------------------------------------------------------------------ blocks
 namespace {
 // Debug taps (engine.h: TapSink) around one block, named by its diffusers prefix: "<grp>.<i>.<kind>.<j>", or
@@ -994,18 +1034,35 @@ View Encoder::run_down(Ctx& c, View x, GnStatBuf*& xs, int B, int& h, int& w, Vi
                 tap_end(c, "down_blocks", i, "resnets", j, tmp, B, h, w);
                 View dst = skip_view(skip_i);
                 if (c.pag) c.pag->skips_done = skip_i;
-                tap_begin(c, "down_blocks", i, "attentions", j, tmp, B, h, w, dst, h, w);
-                run_xformer(c, down_att[i][j], tmp, B, h, w, dst, G, text_kv, L, rs,
-                            GnOut(&xs, skip_stat(skip_i, (long)h * w, r.cout)), sh);
-                tap_end(c, "down_blocks", i, "attentions", j, dst, B, h, w);
+                // (a motion module behind the pair: the transformer writes a temporary, the module's last launch the skip)
+                const MotionModule* mm = c.motion ? &c.motion->down[(size_t)i][(size_t)j] : nullptr;
+                const View xo = mm ? View(a.alloc_h((long)B * h * w * r.cout), r.cout, r.cout) : dst;
+                const GnOut skip_out(&xs, skip_stat(skip_i, (long)h * w, r.cout));
+                tap_begin(c, "down_blocks", i, "attentions", j, tmp, B, h, w, xo, h, w);
+                run_xformer(c, down_att[i][j], tmp, B, h, w, xo, G, text_kv, L, rs, mm ? GnOut() : skip_out, sh);
+                tap_end(c, "down_blocks", i, "attentions", j, xo, B, h, w);
+                if (mm) {
+                    tap_begin(c, "down_blocks", i, "motion_modules", j, xo, B, h, w, dst, h, w);
+                    run_motion(c, *mm, xo, B, c.motion_frames, h, w, dst, skip_out, G);
+                    tap_end(c, "down_blocks", i, "motion_modules", j, dst, B, h, w);
+                }
                 a.release(mk);
                 x = dst;
             } else {
                 View dst = skip_view(skip_i);
-                tap_begin(c, "down_blocks", i, "resnets", j, x, B, h, w, dst, h, w);
-                run_resnet(c, r, x, ctx_live(c, B), h, w, dst, G, eps, tproj, temb_total, xs,
-                           GnOut(&xs, skip_stat(skip_i, (long)h * w, r.cout)));
-                tap_end(c, "down_blocks", i, "resnets", j, dst, B, h, w);
+                const MotionModule* mm = c.motion ? &c.motion->down[(size_t)i][(size_t)j] : nullptr;
+                const size_t mk = a.mark();
+                const View xo = mm ? View(a.alloc_h((long)B * h * w * r.cout), r.cout, r.cout) : dst;
+                const GnOut skip_out(&xs, skip_stat(skip_i, (long)h * w, r.cout));
+                tap_begin(c, "down_blocks", i, "resnets", j, x, B, h, w, xo, h, w);
+                run_resnet(c, r, x, ctx_live(c, B), h, w, xo, G, eps, tproj, temb_total, xs, mm ? GnOut() : skip_out);
+                tap_end(c, "down_blocks", i, "resnets", j, xo, B, h, w);
+                if (mm) {
+                    tap_begin(c, "down_blocks", i, "motion_modules", j, xo, B, h, w, dst, h, w);
+                    run_motion(c, *mm, xo, B, c.motion_frames, h, w, dst, skip_out, G);
+                    tap_end(c, "down_blocks", i, "motion_modules", j, dst, B, h, w);
+                }
+                a.release(mk);
                 x = dst;
             }
             ++skip_i;
@@ -1046,6 +1103,14 @@ void Encoder::run_mid(Ctx& c, View x, GnStatBuf* xs, int B, int h, int w, View t
     tap_begin(c, "mid_block", -1, "attentions", 0, m0, B, h, w, m1, h, w);
     run_xformer(c, mid_att, m0, B, h, w, m1, G, text_kv, L, s0, &s1);
     tap_end(c, "mid_block", -1, "attentions", 0, m1, B, h, w);
+    if (c.motion && c.motion->mcfg.use_mid_block) {
+        // behind the transformer, before the second resnet, which reads the module's own summaries
+        View m2(a.alloc_h(M * C), C, C);
+        tap_begin(c, "mid_block", -1, "motion_modules", 0, m1, B, h, w, m2, h, w);
+        run_motion(c, c.motion->mid, m1, B, c.motion_frames, h, w, m2, GnOut(&s1), G);
+        tap_end(c, "mid_block", -1, "motion_modules", 0, m2, B, h, w);
+        m1 = m2;
+    }
     tap_begin(c, "mid_block", -1, "resnets", 1, m1, B, h, w, dst, h, w);
     run_resnet(c, mid_r1, m1, ctx_live(c, B), h, w, dst, G, eps, tproj, temb_total, s1);   // output joins a concat: no consumer
     tap_end(c, "mid_block", -1, "resnets", 1, dst, B, h, w);
@@ -1449,19 +1514,27 @@ int UNet::run(Ctx& c, const UNetCall& call, int dc) {
             xs = nullptr;
             // the last layer's summaries go to the tail, a hidden half's into `hid`; nobody reads any other output's
             const GnOut summ = last ? GnOut(&xs) : hid_here ? GnOut(&outp, &hid, nx_groups) : GnOut();
+            // (a motion module behind the layer: it writes `dst`, with the summaries asked of the layer's last launch)
+            const MotionModule* mm = c.motion ? &c.motion->up[(size_t)i][(size_t)j] : nullptr;
+            const View xo = mm ? View(a.alloc_h((long)B * h * w * r.cout), r.cout, r.cout) : dst;
             if (cfg.up_block_has_attn[i]) {
                 View tmp(a.alloc_h((long)B * h * w * r.cout), r.cout, r.cout);
                 GnStatBuf* rs = nullptr;
                 tap_begin(c, "up_blocks", i, "resnets", j, xin, B, h, w, tmp, h, w);
                 run_resnet(c, r, xin, Bl, h, w, tmp, G, eps, tproj, temb_total, xin_stats, &rs);
                 tap_end(c, "up_blocks", i, "resnets", j, tmp, B, h, w);
-                tap_begin(c, "up_blocks", i, "attentions", j, tmp, B, h, w, dst, h, w);
-                run_xformer(c, up_att[i][j], tmp, B, h, w, dst, G, text_kv, L, rs, summ);
-                tap_end(c, "up_blocks", i, "attentions", j, dst, B, h, w);
+                tap_begin(c, "up_blocks", i, "attentions", j, tmp, B, h, w, xo, h, w);
+                run_xformer(c, up_att[i][j], tmp, B, h, w, xo, G, text_kv, L, rs, mm ? GnOut() : summ);
+                tap_end(c, "up_blocks", i, "attentions", j, xo, B, h, w);
             } else {
-                tap_begin(c, "up_blocks", i, "resnets", j, xin, B, h, w, dst, h, w);
-                run_resnet(c, r, xin, Bl, h, w, dst, G, eps, tproj, temb_total, xin_stats, summ);
-                tap_end(c, "up_blocks", i, "resnets", j, dst, B, h, w);
+                tap_begin(c, "up_blocks", i, "resnets", j, xin, B, h, w, xo, h, w);
+                run_resnet(c, r, xin, Bl, h, w, xo, G, eps, tproj, temb_total, xin_stats, mm ? GnOut() : summ);
+                tap_end(c, "up_blocks", i, "resnets", j, xo, B, h, w);
+            }
+            if (mm) {
+                tap_begin(c, "up_blocks", i, "motion_modules", j, xo, B, h, w, dst, h, w);
+                run_motion(c, *mm, xo, B, c.motion_frames, h, w, dst, summ, G);
+                tap_end(c, "up_blocks", i, "motion_modules", j, dst, B, h, w);
             }
             if (last) {
                 final_x = dst;   // the temporary stays alive for the tail
@@ -1542,6 +1615,7 @@ UNet::~UNet() {
     if (gstream) (void)hipStreamDestroy(gstream);
     if (ip) ip->attached = nullptr;
     for (ControlNet* n : cns) n->attached = nullptr;
+    if (motion) motion->attached = nullptr;
 }
 
 // Graph path: stage I/O through engine-owned buffers, capture the forward once per shape on an
@@ -1664,6 +1738,8 @@ int UNet::forward(const UNetCall& in, hipStream_t stream) {
     const PagIn* const pag = call.pag;
     if (!finalized) { set_error("unet: forward before finalize"); return 2; }
     if (int rc = regions_refuse(call, B, pag || call.extra)) return rc;
+    if (int rc = motion_refuse(call, cfg_in ? B / 2 : B, pag || call.extra)) return rc;
+    const bool motion_on = motion && call.num_frames >= 1;
     if (int rc = tap_refuses(graph_enabled || cfg_in || pag || call.extra || dc_mode != SD_DC_PLAIN)) return rc;
     if (pag && (B % (pag->groups + 1) != 0 || graph_enabled || control || image_embeds || tcond || dc_mode != SD_DC_PLAIN)) {
         set_error("unet: perturbed-attention forward not available for this call");
@@ -1679,7 +1755,8 @@ int UNet::forward(const UNetCall& in, hipStream_t stream) {
     const int div = 1 << (cfg.num_blocks - 1);
     if (B <= 0 || H % div != 0 || W % div != 0) { set_error("unet: H and W must be divisible by 2^(blocks-1)"); return 1; }
     // (forward_pag and forward_concat run with an attached adapter only at scale 0, where the text attention runs alone)
-    const bool text_only = pag || call.extra;
+    // (so does a motion forward: sd_unet_forward_motion takes no image_embeds, and motion_refuse let scale 0 alone through)
+    const bool text_only = pag || call.extra || (motion_on && !image_embeds);
     if (ip && !image_embeds && !text_only) { set_error("unet: an IP-Adapter is attached: image_embeds required"); return 1; }
     if (!ip && image_embeds) { set_error("unet: image_embeds given but no IP-Adapter is attached"); return 1; }
     if (ip && !text_only) {
@@ -1785,6 +1862,7 @@ int UNet::forward(const UNetCall& in, hipStream_t stream) {
     key.cat_rows = call.extra ? call.lat_rows : 0;
     if (tome_on) { key.tome_ratio = tome.ratio; key.tome_ds = tome_max_ds; key.tome_sx = tome.sx; key.tome_sy = tome.sy; }
     if (ht_on) { key.ht_tile = hypertile.tile_size; key.ht_swap = hypertile.swap_size; key.ht_depth = hypertile.max_depth; }
+    key.motion_frames = motion_on ? call.num_frames : 0;
     if (taps.on) taps.clear();              // one forward's records at a time
     if (region_R && region_stale) {
         // the level weights were overwritten (sd_unet_poison_workspace): rebuild them from the kept copy
@@ -1798,6 +1876,8 @@ int UNet::forward(const UNetCall& in, hipStream_t stream) {
         c.tap = taps.on ? &taps : nullptr;
         c.tome = tome_on ? &tome : nullptr;
         c.hypertile = ht_on ? &hypertile : nullptr;
+        c.motion = motion_on ? motion : nullptr;
+        c.motion_frames = motion_on ? call.num_frames : 0;
         if (region_R) {
             c.region_w = reinterpret_cast<const float*>(region_buf.data());
             c.region_R = region_R; c.region_Bw = region_Bw; c.region_H = region_H; c.region_W = region_W;
@@ -1973,6 +2053,7 @@ int UNet::forward_cfg(const UNetCall& lat, float in_scale, bool share, hipStream
     // (not shared it is the plain forward on the duplicated latents, which taps; under graph replay forward() refuses,
     // and nothing may be launched before it does)
     if (int rc = regions_refuse(lat, 2 * B, false)) return rc;
+    if (int rc = motion_refuse(lat, B, false)) return rc;
     if (int rc = tap_refuses(cfg_share_active(share) || graph_enabled)) return rc;
     UNetCall call = lat;
     call.B = 2 * B;
@@ -2005,6 +2086,8 @@ int UNet::forward_concat(const UNetCall& call, hipStream_t stream) {
     if (!finalized) { set_error("unet: forward before finalize"); return 2; }
     if (B <= 0 || call.H <= 0 || call.W <= 0 || Bl <= 0) { set_error("unet: forward_concat: empty batch"); return 1; }
     if (int rc = regions_refuse(call, B, true)) return rc;
+    // (this entry cannot name frames: with an adapter attached it would silently run without the modules)
+    if (motion) { set_error("unet: forward_concat with a motion adapter attached is not supported"); return 4; }
     if (int rc = tap_refuses(true)) return rc;
     // (what the handle is set up for comes first: a ControlNet only attaches to a 4-channel UNet, which the channel check below
     // would turn away with another code)
@@ -2068,6 +2151,7 @@ int UNet::forward_pag(const UNetCall& lat, float in_scale, bool cfg_on, bool sha
     if (!finalized) { set_error("unet: forward before finalize"); return 2; }
     if (B <= 0 || H <= 0 || W <= 0) { set_error("unet: forward_pag: empty batch"); return 1; }
     if (int rc = regions_refuse(lat, B, true)) return rc;
+    if (motion) { set_error("unet: forward_pag with a motion adapter attached is not supported"); return 4; }
     if (int rc = tap_refuses(true)) return rc;
     if (cn) { set_error("unet: forward_pag with a ControlNet attached is not supported"); return 4; }
     if (ip && ip_scale != 0.f) { set_error("unet: forward_pag with an IP-Adapter at a non-zero scale is not supported"); return 4; }

@@ -171,6 +171,7 @@ class HipUNet2DConditionModel:
         self._tome = None              # (ratio, max_downsample, sx, sy, use_rand, seed) while token merging is on
         self._hypertile = None         # (tile_size, swap_size, max_depth, seed) while HyperTile is on
         self._regions = None           # (Bw, R, H, W) while regional prompts are set (set_regions)
+        self._motion = None            # attached HipMotionAdapter (attach_motion_adapter)
 
     # -- weights -------------------------------------------------------------------------------
     def load_state_dict(self, state_dict: Dict[str, torch.Tensor], strict: bool = True):
@@ -474,6 +475,29 @@ class HipUNet2DConditionModel:
         _lib.check(self._lib.sd_unet_deep_cache_mode(self._h, int(mode)), "sd_unet_deep_cache_mode")
         return self
 
+    def attach_motion_adapter(self, adapter: Optional["HipMotionAdapter"]):
+        """Attach an AnimateDiff motion adapter built for this UNet's topology (None detaches: every forward is again
+        exactly the plain one).  Attached, a call with num_frames= treats its batch as videos of that many consecutive
+        frames and runs a motion module behind every (resnet, transformer) pair; without num_frames nothing changes."""
+        _lib.check(self._lib.sd_unet_set_motion(self._h, adapter._h if adapter is not None else None), "sd_unet_set_motion")
+        if self._motion is not None and self._motion is not adapter:
+            self._motion._unet = None
+        if adapter is not None:
+            old = adapter._unet() if adapter._unet is not None else None
+            if old is not None and old is not self:
+                old._motion = None
+            adapter._unet = weakref.ref(self)
+        self._motion = adapter
+        return self
+
+    def make_motion_adapter(self, config, state_dict: Dict[str, torch.Tensor]):
+        """A HipMotionAdapter for this engine from an engine-named state dict (stablediffusion_amd.motion.load)."""
+        return HipMotionAdapter(self, config).load_state_dict(state_dict)
+
+    @property
+    def motion_adapter(self):
+        return self._motion
+
     def attach_controlnet(self, controlnet: Optional["HipControlNetModel"]):
         """Attach a ControlNet built for this UNet (None detaches).  While attached, every call needs controlnet_cond=
         and controlnet_conditioning_scale=; the residuals are added inside the engine's forward."""
@@ -657,7 +681,7 @@ class HipUNet2DConditionModel:
 
     def __call__(self, sample, timestep, encoder_hidden_states, cross_attention_kwargs=None,
                  added_cond_kwargs=None, return_dict=False, controlnet_cond=None, controlnet_conditioning_scale=None,
-                 timestep_cond=None, out=None, **unused):
+                 timestep_cond=None, out=None, num_frames=None, **unused):
         # diffusers' residual-tensor interface (a ControlNet run outside the engine): not taken -- silently dropping
         # it would return the plain UNet's output.  Attach the ControlNet instead (attach_controlnet).
         for k in ("down_block_additional_residuals", "mid_block_additional_residual", "down_intrablock_additional_residuals",
@@ -668,7 +692,10 @@ class HipUNet2DConditionModel:
                                           "engine (attach_controlnet) and pass controlnet_cond=")
         dev, sample, ehs, t, pt, pi, _keep = self._prepare(sample, timestep, encoder_hidden_states, added_cond_kwargs)
         B, _, H, W = sample.shape
-        img = self._image_embeds(added_cond_kwargs, B, dev)
+        if num_frames and self._ip is not None and self._ip_scale == 0.0 and not (added_cond_kwargs or {}).get("image_embeds"):
+            img = None          # frames with an IP-Adapter at scale 0: the text attention alone, no image_embeds needed
+        else:
+            img = self._image_embeds(added_cond_kwargs, B, dev)
         ctrl, cscale = self._control(controlnet_cond, controlnet_conditioning_scale, B, H, W, dev)
         tc = None
         if timestep_cond is not None:
@@ -685,7 +712,13 @@ class HipUNet2DConditionModel:
                 pt, pi)
         images = (C.c_void_p(img.data_ptr()) if img is not None else None, img.shape[1] if img is not None else 0)
         tail = (C.c_void_p(out.data_ptr()), B, H, W, C.c_void_p(_stream_ptr()))
-        if tc is not None:
+        if num_frames:
+            # videos of num_frames consecutive frames through the attached motion adapter: the entry takes neither images
+            # nor a ControlNet nor timestep_cond, and the engine refuses every state it does not compose with frames
+            if tc is not None or ctrl is not None or img is not None or pt is not None:
+                raise NotImplementedError("num_frames= takes no timestep_cond, ControlNet, image_embeds or text_time conditions")
+            fn, extra = self._lib.sd_unet_forward_motion, None
+        elif tc is not None:
             fn, extra = self._lib.sd_unet_forward_tc, images + (C.c_void_p(tc.data_ptr()), tc.shape[1])
         elif isinstance(ctrl, list):
             N = len(ctrl)
@@ -699,7 +732,10 @@ class HipUNet2DConditionModel:
         else:
             fn, extra = self._lib.sd_unet_forward, ()
         with torch.cuda.device(dev):
-            rc = fn(*head, *extra, *tail)
+            if extra is None:
+                rc = fn(*head[:5], int(num_frames), *tail)
+            else:
+                rc = fn(*head, *extra, *tail)
         _lib.check(rc, "sd_unet_forward")
         if return_dict:
             return SimpleNamespace(sample=out)
@@ -739,7 +775,7 @@ class HipUNet2DConditionModel:
         return out
 
     def forward_cfg(self, latents, timestep, encoder_hidden_states, added_cond_kwargs=None, in_scale: float = 1.0,
-                    share: bool = True, out=None):
+                    share: bool = True, out=None, num_frames=None):
         """One classifier-free-guidance forward from the UN-duplicated latents [B, C, H, W]: what
         self(torch.cat([fp16(latents * in_scale)] * 2), timestep, encoder_hidden_states) returns ([2B, ...], negative
         half first; encoder_hidden_states and added_cond_kwargs hold 2B rows).  With `share` the engine runs everything
@@ -753,12 +789,15 @@ class HipUNet2DConditionModel:
         B, _, H, W = latents.shape
         img = self._image_embeds(added_cond_kwargs, 2 * B, dev)
         out = self._out_buffer(out, (2 * B, self.cfg.out_channels, H, W), dev)
+        head = (self._h, C.c_void_p(latents.data_ptr()), C.c_void_p(t.data_ptr()), C.c_void_p(ehs.data_ptr()), ehs.shape[1],
+                pt, pi, C.c_void_p(img.data_ptr()) if img is not None else None, img.shape[1] if img is not None else 0,
+                float(in_scale), int(bool(share)))
+        tail = (C.c_void_p(out.data_ptr()), B, H, W, C.c_void_p(_stream_ptr()))
         with torch.cuda.device(dev):
-            rc = self._lib.sd_unet_forward_cfg(self._h, C.c_void_p(latents.data_ptr()), C.c_void_p(t.data_ptr()),
-                                               C.c_void_p(ehs.data_ptr()), ehs.shape[1], pt, pi,
-                                               C.c_void_p(img.data_ptr()) if img is not None else None,
-                                               img.shape[1] if img is not None else 0, float(in_scale), int(bool(share)),
-                                               C.c_void_p(out.data_ptr()), B, H, W, C.c_void_p(_stream_ptr()))
+            if num_frames:      # the B latents are B / num_frames videos (attach_motion_adapter)
+                rc = self._lib.sd_unet_forward_cfg_ex(*head, int(num_frames), *tail)
+            else:
+                rc = self._lib.sd_unet_forward_cfg(*head, *tail)
         _lib.check(rc, "sd_unet_forward_cfg")
         return (out,)
 
@@ -905,6 +944,47 @@ class HipIPAdapter:
                 if u is not None:
                     u._ip = None
                 self._lib.sd_ip_adapter_destroy(self._h)     # (detaches it first)
+                self._h = None
+        except Exception:
+            pass
+
+
+class HipMotionAdapter:
+    """diffusers MotionAdapter (AnimateDiff) on the engine, built for a UNet's topology (sd_motion_*): attach it with
+    HipUNet2DConditionModel.attach_motion_adapter and pass num_frames= to the UNet's calls.  Weights in diffusers naming
+    without the stored position tables (stablediffusion_amd.motion.load converts and checks both file layouts)."""
+
+    def __init__(self, unet: HipUNet2DConditionModel, config):
+        self._lib = _lib.load()
+        self.cfg = config
+        self.device = unet.device
+        self._unet = None
+        config.check(unet.cfg)
+        nb = len(config.block_out_channels)
+        c = _lib.SdMotionConfig(num_blocks=nb, layers_per_block=config.motion_layers_per_block,
+                                max_seq_length=config.motion_max_seq_length, use_mid_block=int(config.use_motion_mid_block))
+        for i in range(nb):
+            c.block_out_channels[i] = config.block_out_channels[i]
+            c.num_heads[i] = config.motion_num_attention_heads[i]
+        self._h = C.c_void_p()
+        _lib.check(self._lib.sd_motion_create(unet._h, C.byref(c), C.byref(self._h)), "sd_motion_create")
+        self._finalized = False
+
+    def load_state_dict(self, state_dict: Dict[str, torch.Tensor], strict: bool = True):
+        _lib.require_gpu()
+        with torch.cuda.device(self.device):
+            _load_weights(self._lib, self._h, "motion", state_dict, strict)
+            _lib.check(self._lib.sd_motion_finalize(self._h), "sd_motion_finalize")
+        self._finalized = True
+        return self
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None):
+                u = self._unet() if self._unet is not None else None
+                if u is not None:
+                    u._motion = None
+                self._lib.sd_motion_destroy(self._h)     # (detaches it first)
                 self._h = None
         except Exception:
             pass

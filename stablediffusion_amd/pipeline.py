@@ -57,6 +57,7 @@ class SDModelWrapper:
         self._cn = None                  # ControlNet (configuration, diffusers-named state dict): load_controlnet
         self._cn_list = False            # ... or a list of those pairs: load_controlnets (MultiControlNet)
         self._freeu = None               # (s1, s2, b1, b2) while FreeU is on: enable_freeu
+        self._motion = None              # motion adapter (configuration, engine-named state dict): load_motion_adapter
         self._pag = None                 # pag_applied_layers as given (set_pag_applied_layers); None: the default
         self._deepcache = None           # (cache_interval, cache_depth) while DeepCache is on: enable_deepcache
         # host copies of the weights the LoRA adapters are folded into (load_lora_weights); the engine
@@ -198,6 +199,8 @@ class SDModelWrapper:
             self._attach_ip(base)
         if self._cn is not None:             # and so does the ControlNet
             self._attach_cn(base)
+        if self._motion is not None:         # and the motion adapter
+            self._attach_motion(base)
         self._freeu = freeu
         if freeu is not None:                # and FreeU
             base.enable_freeu(*freeu)
@@ -271,6 +274,30 @@ class SDModelWrapper:
         self.base.disable_hypertile()
         if self.refiner is not None and hasattr(self.refiner, "disable_hypertile"):
             self.refiner.disable_hypertile()
+
+    # ---- AnimateDiff motion adapter (diffusers MotionAdapter; stablediffusion_amd.animatediff.animate runs it) ----
+    def _attach_motion(self, base):
+        cfg, sd = self._motion
+        base.attach_motion_adapter(base.make_motion_adapter(cfg, sd))
+
+    def load_motion_adapter(self, pretrained_model_name_or_path_or_dict, config=None):
+        """A motion adapter for this model's UNet: a diffusers MotionAdapter folder, an original `mm_sd_v15*` file or a
+        state dict in either naming (stablediffusion_amd.motion.load: converted, checked).  Replaces one loaded before;
+        survives a LoRA re-fuse."""
+        from . import motion
+        cfg, sd = motion.load(pretrained_model_name_or_path_or_dict, self.base.cfg, config)
+        self.unload_motion_adapter()
+        self._motion = (cfg, sd)
+        self._attach_motion(self.base)
+
+    def unload_motion_adapter(self):
+        if self._motion is not None:
+            self.base.attach_motion_adapter(None)
+        self._motion = None
+
+    @property
+    def has_motion_adapter(self) -> bool:
+        return self._motion is not None
 
     # ---- ControlNet (diffusers ControlNetModel, or a list of them: MultiControlNetModel; the pipeline takes
     #      control_image=) ----
